@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
 """Benchmark of the hybrid-retrieval hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload ucc_hybrid|synth10m]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload ucc_hybrid|synth10m] [--dump-outputs DIR] [--full]
+
+A plain run sets up, runs W untimed steps, times exactly K steps (one window), optionally writes the last timed step's
+outputs (--dump-outputs) and prints the result line.  Everything else below — repeated windows (median of 5), roofline,
+latency, oracle agreement, CPU baseline, the other configurations and the HBM scans — runs only with --full.
 
 Contract (driver): ONE JSON line on rank 0.  metric = queries/sec (+ Recall@10 of the hybrid
 top-10) on the UCC-en corpus, BASELINE.json configs[1] (dense + BM25 + fusion, top-10,
@@ -11,7 +15,7 @@ resident in HBM.  The K-step timed region (barrier + synchronize on both sides, 
 is repeated over `--windows` windows in the same run; `value` is the MEDIAN window and every
 window is listed in `timing`.
 
-Objects in the same line (rank 0, N = 1 unless noted):
+Objects in the same line with --full (rank 0, N = 1 unless noted):
   roofline            dominant kernel of the timed region (dense scores), HIP events bracketing
                       that kernel on its launch stream, all windows
   ucc_colbert         BASELINE configs[2]: dense + BM25 + ColBERT MaxSim hybrid, own roofline
@@ -110,7 +114,13 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=200, help="untimed steps before the first window (5 left the first windows on a clock still ramping: 0.426, 0.408, 0.399, 0.391, 0.391 ms)")
-    ap.add_argument("--windows", type=int, default=5, help="timed regions of --steps steps each (median is reported)")
+    ap.add_argument("--windows", type=int, default=None,
+                    help="timed regions of --steps steps each (median is reported); default 1, 5 with --full")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: roofline, latency, oracle agreement, CPU baseline, "
+                         "the other configurations and the HBM scans (a plain run times the headline step only)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last timed step returned as DIR/<name>.npy")
     ap.add_argument("--workload", default="ucc_hybrid", choices=["ucc_hybrid", "synth10m"])
     ap.add_argument("--shard", default="auto", choices=["auto", "queries", "corpus"])
     ap.add_argument("--repeat", type=int, default=32, help="ucc_hybrid: the query set is tiled this many times per step")
@@ -123,7 +133,12 @@ def parse():
                     help="run ONE of the side objects alone and print {name: object} (profiling passes)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.windows is None:
+        a.windows = 5 if a.full else 1
+    if a.dump_outputs and (a.only or a.workload != "ucc_hybrid"):
+        ap.error("--dump-outputs writes the outputs of the ucc_hybrid headline step (no --only, no other --workload)")
+    return a
 
 
 # ---------------------------------------------------------------------------
@@ -345,6 +360,35 @@ def event_ms(torch, fn, reps):
     return e0.elapsed_time(e1) / reps
 
 
+DUMP_ROWS = 16384  # query rows of the step written by --dump-outputs (about 30 MB at k = 10)
+
+
+def host_outputs(torch, res):
+    """What search_batch() hands its caller, copied to the host as float32 / float64 arrays (ids as float64, exact), for
+    a fixed seeded sample of DUMP_ROWS query rows (all rows when the batch is smaller).  Fused entries past count[q] are
+    unspecified: they are written as id -1 with zero values and mask, so two builds compare entry for entry."""
+    nq = int(res.ids.shape[0])
+    rows = np.arange(nq) if nq <= DUMP_ROWS else np.sort(np.random.default_rng(0).choice(nq, DUMP_ROWS, replace=False))
+    rows_d = torch.from_numpy(rows).to(res.ids.device)
+    out = {}
+    for name in ("ids", "vals", "mask", "count", "dense_scores", "dense_ids", "bm25_scores", "bm25_ids"):
+        t = getattr(res, name)
+        if t is not None:
+            a = t.index_select(0, rows_d).cpu().numpy()
+            out[name] = a.astype(np.float32 if a.dtype in (np.float32, np.int32) else np.float64)
+    past = np.arange(out["ids"].shape[1])[None, :] >= out["count"][:, None]
+    out["ids"][past] = -1
+    out["mask"][past] = 0
+    out["vals"][past] = 0
+    return out
+
+
+def write_outputs(out_dir, arrays):
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    mib = sum(a.nbytes for a in arrays.values()) / 2**20
+    log(f"outputs of the last timed step: {sorted(arrays)} -> {out_dir} ({mib:.1f} MiB)")
 
 
 def maxsim_roofline(ms, tokens, nq, q_len=32, dim=128, note="", plan=""):
@@ -1003,25 +1047,24 @@ def main():
 
         for _ in range(a.warmup):
             step()
-        # HIP events around the dense scores kernel, window by window: `value` is the MEDIAN window, and the
+        # --full: HIP events around the dense scores kernel, window by window: `value` is the MEDIAN window, and the
         # roofline is that same window's launches (all windows are listed beside it)
         per_window = []
-        dts = timed_windows(torch, dist, world, device, step, a.steps, 0, a.windows,
-                            before=lambda wi: R.dense.profile_begin(a.steps),
-                            after=lambda wi: per_window.append(R.dense.profile_end()))
+        profile = dict(before=lambda wi: R.dense.profile_begin(a.steps),
+                       after=lambda wi: per_window.append(R.dense.profile_end())) if a.full else {}
+        dts = timed_windows(torch, dist, world, device, step, a.steps, 0, a.windows, **profile)
         st = window_stats(dts, a.steps)
-        wi_med = min(range(len(dts)), key=lambda i: (abs(dts[i] / a.steps * 1e3 - st["median"]), i))
-        scan_ms, launches = per_window[wi_med]
-        launch_ms_windows = [round(ms / max(n, 1), 6) for ms, n in per_window]
+        res = last["res"]
+        if a.dump_outputs and rank == 0:  # before anything else reuses the engine's output buffers
+            write_outputs(a.dump_outputs, host_outputs(torch, res))
         queries_per_step_total = nq * (world if shard == "queries" else 1)
         value = queries_per_step_total / (st["median"] * 1e-3)
-        res = last["res"]
         ids = res.ids[:, :K].cpu().numpy()
         cnt = res.count.cpu().numpy()
         rec = hybrid_recall(ids[:nq0], cnt[:nq0], W["chunks"], W["queries"], K)
         # ---- single-query latency through the same kernels (B = 1) ----------
         lat_us = lat_p50 = lat_p99 = lat_graph_p50 = lat_graph_p99 = None
-        if rank == 0:
+        if rank == 0 and a.full:
             eng = R.eng
             q1 = R.q_emb[:1].contiguous()
             t1 = R.q_terms[: int(R.q_ptr_h[1])].contiguous() if R.q_ptr_h[1] > 0 else R.q_terms[:1]
@@ -1054,25 +1097,29 @@ def main():
 
         rows_local = hi - lo
         d = W["X"].shape[1]
-        # Dominant kernel of the step = the dense scores kernel: [rows x d] . [d x nq] in exact fp32 on the
-        # matrix pipe.  At UCC-en size X (1.8 MB) is L2-resident, so the bound is the fp32 MFMA rate
-        # (157.3 TFLOP/s = the fp32 vector rate, MI355X_MICROARCH.md), not HBM.
         plan = R.dense.plan_info(nq, K)
         kernel = plan.split(" ")[0]
         flops_per_launch = 2.0 * rows_local * d * nq
-        per_launch_ms = scan_ms / max(launches, 1)
-        achieved = flops_per_launch / (per_launch_ms * 1e-3) / 1e12 if per_launch_ms > 0 else 0.0
-        klabel, kpeak = dense_scores_roofline(plan, flops_per_launch, per_launch_ms)
-        roofline = {"bound": "mfma", "kernel": klabel, "plan": plan,
-                    "achieved": achieved, "peak": kpeak, "unit": "TFLOP/s",
-                    "frac": achieved / kpeak,
-                    "traffic": pmc_traffic("ucc_hybrid", kernel, plan) if (rep == 32 and shard == "queries") else None,
-                    "launch_ms": per_launch_ms, "launches_timed": launches, "launch_ms_windows": launch_ms_windows,
-                    "algorithmic_flops": flops_per_launch,
-                    "algorithmic_bytes": float(rows_local) * d * 4 + nq * d * 4 + float(rows_local) * nq * 4,
-                    "note": "HIP events around the scores kernel alone: launch_ms = mean over the launches of the MEDIAN "
-                            "window (the window `value` is quoted on); every window's mean is in launch_ms_windows; "
-                            "HBM-roofline evidence for the same channel on a 30.7 GB matrix is in hbm_scan"}
+        if a.full:
+            # Dominant kernel of the step = the dense scores kernel: [rows x d] . [d x nq] in exact fp32 on the
+            # matrix pipe.  At UCC-en size X (1.8 MB) is L2-resident, so the bound is the fp32 MFMA rate
+            # (157.3 TFLOP/s = the MI355X fp32 vector rate), not HBM.
+            wi_med = min(range(len(dts)), key=lambda i: (abs(dts[i] / a.steps * 1e3 - st["median"]), i))
+            scan_ms, launches = per_window[wi_med]
+            launch_ms_windows = [round(ms / max(n, 1), 6) for ms, n in per_window]
+            per_launch_ms = scan_ms / max(launches, 1)
+            achieved = flops_per_launch / (per_launch_ms * 1e-3) / 1e12 if per_launch_ms > 0 else 0.0
+            klabel, kpeak = dense_scores_roofline(plan, flops_per_launch, per_launch_ms)
+            roofline = {"bound": "mfma", "kernel": klabel, "plan": plan,
+                        "achieved": achieved, "peak": kpeak, "unit": "TFLOP/s",
+                        "frac": achieved / kpeak,
+                        "traffic": pmc_traffic("ucc_hybrid", kernel, plan) if (rep == 32 and shard == "queries") else None,
+                        "launch_ms": per_launch_ms, "launches_timed": launches, "launch_ms_windows": launch_ms_windows,
+                        "algorithmic_flops": flops_per_launch,
+                        "algorithmic_bytes": float(rows_local) * d * 4 + nq * d * 4 + float(rows_local) * nq * 4,
+                        "note": "HIP events around the scores kernel alone: launch_ms = mean over the launches of the MEDIAN "
+                                "window (the window `value` is quoted on); every window's mean is in launch_ms_windows; "
+                                "HBM-roofline evidence for the same channel on a 30.7 GB matrix is in hbm_scan"}
         result = {
             "metric": "queries/sec + Recall@10 (hybrid top-10) on UCC-en", "value": value, "unit": "queries/s",
             "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": st["median"],
@@ -1083,11 +1130,13 @@ def main():
                                    "(BASELINE configs[1])", "queries_per_step_per_gpu": nq, "unique_queries": nq0,
                        "top_k": K, "shard": shard, "fusion": "rrf_norm_blend w=0.6/0.4 alpha=0.5 rrf_k=60 "
                        "min_final=0.2"},
-            "timing": st, "recall_at_10": rec, "latency_b1_us": lat_us, "latency_b1_p50_us": lat_p50,
-            "latency_b1_p99_us": lat_p99, "latency_b1_graph_p50_us": lat_graph_p50,
-            "latency_b1_graph_p99_us": lat_graph_p99, "roofline": roofline,
+            "timing": st, "recall_at_10": rec,
         }
-        if rank == 0:
+        if a.full:
+            result.update({"latency_b1_us": lat_us, "latency_b1_p50_us": lat_p50, "latency_b1_p99_us": lat_p99,
+                           "latency_b1_graph_p50_us": lat_graph_p50, "latency_b1_graph_p99_us": lat_graph_p99,
+                           "roofline": roofline})
+        if rank == 0 and a.full:
             # agreement@10 with the CPU oracle on identical inputs
             sample = list(range(0, nq0, max(1, nq0 // 256)))
             result["agreement_at_10_vs_oracle"] = agreement(ids, cnt, oracle_pipeline(W, sample, K), sample, K)
@@ -1102,7 +1151,7 @@ def main():
                 result["recall_at_80"] = hybrid_recall(ids80, cnt80, W["chunks"], W["queries"], K80)
             if not a.no_cpu_baseline:
                 result["cpu_baseline"] = cpu_baseline(W, a.cpu_seconds)
-        if rank == 0 and shard == "queries":
+        if rank == 0 and shard == "queries" and a.full:
             # ---- the same step with the BM25 query side INSIDE the timed region: the batch's query texts are tokenised
             # (jieba.cut restated, bm25_retriever.py:73) and looked up by the native batched tokeniser, the CSR goes up
             # through pinned staging, then the kernels — term ids are produced in the step, not resident beforehand.
@@ -1139,9 +1188,9 @@ def main():
                     "fused_ids_equal_the_resident_step": same_ids, "blob_bytes": len(blob)}
             except Exception as e:  # noqa: BLE001 - report, never hide
                 result["with_tokenisation"] = {"error": repr(e)}
-        if rank == 0 and plan.startswith("dsh_scores_kernel"):
+        if rank == 0 and a.full and plan.startswith("dsh_scores_kernel"):
             result["two_pass_exact_fallback_queries"] = R.dense.two_pass_fallbacks()  # of every two-pass step so far
-        if rank == 0 and shard == "queries" and plan.startswith("dsh_scores_kernel"):
+        if rank == 0 and shard == "queries" and a.full and plan.startswith("dsh_scores_kernel"):
             # the same step with the dense channel's EXACT long-batch form (AMDR_DENSE_SMALL_HI=0: dense_panel_scores_kernel on
             # the fp32 matrix instructions + dense_select_fuse_kernel) — what `value` was measured on in rounds 1-3
             prev = os.environ.get("AMDR_DENSE_SMALL_HI")
@@ -1175,7 +1224,7 @@ def main():
         R.close()
         del R
         torch.cuda.empty_cache()
-        if rep != 1:
+        if rep != 1 and a.full:
             # the UN-tiled batch next to the headline: the 1 168-query evaluation set once per step (what the
             # reference's evaluation harness loops over; the headline tiles it `rep` times to fill the chip)
             R1 = Resident(torch, W, local, rep=1, lo=lo, hi=hi)
@@ -1189,7 +1238,7 @@ def main():
             R1.close()
             del R1
             torch.cuda.empty_cache()
-        extras = not a.no_extras
+        extras = a.full and not a.no_extras
         if rank == 0 and extras and world == 1:
             for name, fn in (("dense_only_d384", lambda: run_dense_only_d384(torch, local, K, max(3, min(a.steps, 10)), rep)),
                              ("ucc_colbert", lambda: run_ucc_colbert(torch, local, params, K, max(3, min(a.steps, 10)))),
@@ -1242,7 +1291,7 @@ def main():
         dist.barrier()
         dist.destroy_process_group()
     if rank == 0:
-        if a.workload == "ucc_hybrid":
+        if a.workload == "ucc_hybrid" and a.full:
             # one compact entry per BASELINE.json config, inside `config` (which the driver's record keeps whole) and
             # again as the LAST key of the line (the driver also keeps the tail of stdout)
             def pick(o, *path):

@@ -9,7 +9,7 @@ FILT=${3:-amdr::}
 mkdir -p $O
 run() { # name, counters...
   n=$1; shift
-  if [ "$OBJ" = headline ]; then ARGS="--steps 3 --warmup 1 --windows 1 --no-cpu-baseline --no-extras"; else ARGS="--only $OBJ --steps 3"; fi
+  if [ "$OBJ" = headline ]; then ARGS="--full --steps 3 --warmup 1 --windows 1 --no-cpu-baseline --no-extras"; else ARGS="--only $OBJ --steps 3"; fi
   timeout -k 10 200 rocprofv3 --kernel-trace --pmc "$@" -d $O/$n --output-format csv -- python3 $R/bench.py $ARGS > $O/$n.log 2>&1
   echo "pass $n rc=$?" >> $O/progress.log
   f=$(find $O/$n -name "*counter_collection.csv" 2>/dev/null | head -1)

@@ -48,9 +48,9 @@ def sources_fingerprint(key: str) -> str:
 
 # object -> (command after `python3`, kernels whose traffic is summed, key of the plan string in the command's JSON line)
 OBJECTS = {
-    "ucc_hybrid": (["bench.py", "--steps", "5", "--warmup", "1", "--windows", "1", "--no-cpu-baseline", "--no-extras"],
+    "ucc_hybrid": (["bench.py", "--full", "--steps", "5", "--warmup", "1", "--windows", "1", "--no-cpu-baseline", "--no-extras"],
                    ["dsh_scores_kernel", "dsh_split_queries_kernel"], ("roofline", "plan")),
-    "ucc_hybrid_second_pass": (["bench.py", "--steps", "5", "--warmup", "1", "--windows", "1", "--no-cpu-baseline", "--no-extras"],
+    "ucc_hybrid_second_pass": (["bench.py", "--full", "--steps", "5", "--warmup", "1", "--windows", "1", "--no-cpu-baseline", "--no-extras"],
                                ["dense_hi_select_fuse_kernel", "bm25_score_topk_kernel"], ("roofline", "plan")),
     "dense_only_d384": (["bench.py", "--only", "dense_only_d384", "--steps", "5"],
                         ["dsh_scores_kernel", "dsh_split_queries_kernel"],

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Median duration of each kernel of the timed UCC-en hybrid step from a rocprofv3 kernel trace:
-    rocprofv3 --kernel-trace -d DIR -o kt --output-format csv -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-extras
+    rocprofv3 --kernel-trace -d DIR -o kt --output-format csv -- python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-extras
     python3 scripts/step_kernels.py DIR
 Only launches with >= 10 000 workgroup threads x queries are listed (the 37 376-query step)."""
 import csv

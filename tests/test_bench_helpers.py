@@ -57,3 +57,37 @@ def test_pmc_traffic_is_keyed_on_kernel_plan_and_sources(tmp_path, monkeypatch):
     assert bench.pmc_traffic("synth10m_b32", "dense_hi_tilemax_kernel") is None      # measured on other sources
     assert bench.pmc_traffic("old_style", "k") is None                                # no fingerprint at all
     assert bench.pmc_traffic("no_such_entry", "k") is None
+
+
+def test_dumped_outputs_are_float_masked_and_fixed(tmp_path):
+    """bench.py --dump-outputs: float32 / float64 arrays of what search_batch() returned, entries past count[q] (unspecified
+    in the fused lists) written as id -1 / zeros, the same seeded row sample every run, under 64 MB at the headline's
+    shape (37 376 queries, k = 10: 20 fused entries of 9 values each)."""
+    import types
+
+    import numpy as np
+    import torch
+
+    nq, K, mo = 37376, 10, 20
+    g = torch.Generator().manual_seed(1)
+    res = types.SimpleNamespace(
+        ids=torch.randint(0, 591, (nq, mo), generator=g), vals=torch.rand((nq, mo, 9), generator=g, dtype=torch.float64),
+        mask=torch.randint(1, 4, (nq, mo), generator=g, dtype=torch.int32),
+        count=torch.randint(0, mo + 1, (nq,), generator=g, dtype=torch.int32),
+        dense_scores=torch.rand((nq, K), generator=g), dense_ids=torch.randint(0, 591, (nq, K), generator=g),
+        bm25_scores=torch.rand((nq, K), generator=g, dtype=torch.float64), bm25_ids=torch.randint(0, 591, (nq, K), generator=g))
+    out = bench.host_outputs(torch, res)
+    assert sorted(out) == sorted(["ids", "vals", "mask", "count", "dense_scores", "dense_ids", "bm25_scores", "bm25_ids"])
+    assert all(a.dtype in (np.float32, np.float64) for a in out.values())
+    assert out["ids"].dtype == np.float64 and out["vals"].dtype == np.float64 and out["dense_scores"].dtype == np.float32
+    assert sum(a.nbytes for a in out.values()) <= 64 * 2**20
+    rows = np.sort(np.random.default_rng(0).choice(nq, bench.DUMP_ROWS, replace=False))
+    assert out["count"].shape == (bench.DUMP_ROWS,) and np.array_equal(out["count"], res.count.numpy()[rows])
+    past = np.arange(mo)[None, :] >= out["count"][:, None]
+    assert (out["ids"][past] == -1).all() and (out["vals"][past] == 0).all() and (out["mask"][past] == 0).all()
+    assert np.array_equal(out["ids"][~past], res.ids.numpy()[rows][~past].astype(np.float64))
+    assert np.array_equal(out["bm25_ids"], res.bm25_ids.numpy()[rows].astype(np.float64))
+    again = bench.host_outputs(torch, res)
+    assert all(np.array_equal(out[n], again[n]) for n in out)
+    bench.write_outputs(str(tmp_path / "dump"), out)
+    assert np.array_equal(np.load(tmp_path / "dump" / "vals.npy"), out["vals"])
