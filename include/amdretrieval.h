@@ -48,6 +48,7 @@ typedef struct amdr_dense_small amdr_dense_small_t;
 typedef struct amdr_bm25 amdr_bm25_t;
 typedef struct amdr_maxsim amdr_maxsim_t;
 typedef struct amdr_tokenizer amdr_tokenizer_t;
+typedef struct amdr_tokenizer_device amdr_tokenizer_device_t;
 
 /* ---- library ---------------------------------------------------------- */
 const char* amdr_last_error(void);
@@ -165,6 +166,30 @@ int amdr_tokenizer_encode_ptrs(const amdr_tokenizer_t* t, const char* const* tex
 int amdr_tokenizer_spans(const char* text, int64_t n_bytes, int32_t* starts, int32_t* ends, int32_t capacity,
                          int32_t* n_tokens);
 int amdr_tokenizer_destroy(amdr_tokenizer_t* t);
+/* pack n queries that lie where they are (texts[q] = n_bytes[q] UTF-8 bytes; a Python caller takes the pointers from
+ * the str objects themselves, csrc/pystrings.c) back to back into the caller's blob (e.g. pinned host memory, the source
+ * of ONE host-to-device copy): offsets[nq + 1] with offsets[0] = 0, query q = blob[offsets[q] .. offsets[q + 1]).
+ * AMDR_EINVAL when the bytes exceed capacity (nothing is copied).  Host code; the copies run on the tokeniser's pool. */
+int amdr_tokenizer_pack(const char* const* texts, const int64_t* n_bytes, int32_t nq, char* blob, int64_t capacity,
+                        int64_t* offsets);
+
+/* ---- the same tokeniser on the device --------------------------------------
+ * Replaces the same call site (legalrag/retrieval/bm25_retriever.py:73-74) as amdr_tokenizer_encode, with the query
+ * texts already in HBM: writes the CSR amdr_bm25_search_device takes, byte for byte what amdr_tokenizer_encode writes
+ * for the same blob (term_ids, q_ptr [nq+1] with q_ptr[0] = 0, needs_segmenter [nq]; a Han query: flag 1, no terms).
+ * create: a device copy of a host tokeniser's vocabulary table (same hash, probe order, first id of a repeated term).
+ * reserve: the largest batch (queries, bytes < 2^31) later calls take; the workspace is 16 bytes per byte of text.
+ * encode_device: the blob text_dev[n_bytes] and offsets_dev[nq+1] are device pointers (query q = text_dev[offs[q] ..
+ * offs[q+1]), ascending, <= n_bytes); term_ids_dev holds capacity entries and capacity >= n_bytes is required (tokens
+ * <= bytes: it always suffices).  Only enqueues (4 launches on `stream`) and allocates nothing: capturable.  Returns
+ * AMDR_EINVAL, and enqueues nothing, when capacity < n_bytes or the call exceeds the reserve.  Calls on one handle
+ * share its workspace: order them (one stream). */
+int amdr_tokenizer_device_create(const amdr_tokenizer_t* host, int32_t device, amdr_tokenizer_device_t** out);
+int amdr_tokenizer_device_reserve(amdr_tokenizer_device_t* h, int32_t nq_max, int64_t bytes_max);
+int amdr_tokenizer_encode_device(amdr_tokenizer_device_t* h, const char* text_dev, const int64_t* offs_dev, int32_t nq,
+                                 int64_t n_bytes, int32_t* term_ids_dev, int64_t capacity, int64_t* q_ptr_dev,
+                                 int32_t* needs_segmenter_dev, void* stream);
+int amdr_tokenizer_device_destroy(amdr_tokenizer_device_t* h);
 
 /* ---- ColBERT channel: exhaustive late-interaction MaxSim ---------------
  * Replaces `Searcher.search(query, k)` (legalrag/retrieval/colbert_retriever.py:152).

@@ -34,6 +34,8 @@ EXPORTS = (
     "amdr_bm25_create", "amdr_bm25_ndocs", "amdr_bm25_reserve", "amdr_bm25_search", "amdr_bm25_search_device",
     "amdr_bm25_scores", "amdr_bm25_destroy",
     "amdr_tokenizer_create", "amdr_tokenizer_encode", "amdr_tokenizer_encode_joined", "amdr_tokenizer_encode_ptrs", "amdr_tokenizer_spans", "amdr_tokenizer_destroy",
+    "amdr_tokenizer_pack", "amdr_tokenizer_device_create", "amdr_tokenizer_device_reserve", "amdr_tokenizer_encode_device",
+    "amdr_tokenizer_device_destroy",
     "amdr_maxsim_create", "amdr_maxsim_ndocs", "amdr_maxsim_plan_info", "amdr_maxsim_reserve", "amdr_maxsim_search",
     "amdr_maxsim_search_device", "amdr_maxsim_scores", "amdr_maxsim_destroy",
     "amdr_fuse", "amdr_fuse_device", "amdr_rerank_blend", "amdr_rerank_blend_device", "amdr_fuse_compact_device",
@@ -57,6 +59,8 @@ SIGNATURES = {
     "amdr_bm25_destroy": "P",
     "amdr_tokenizer_create": "PPlP", "amdr_tokenizer_encode": "PPPiPlPP", "amdr_tokenizer_encode_joined": "PPliPlPP", "amdr_tokenizer_encode_ptrs": "PPPiPlPP", "amdr_tokenizer_spans": "PlPPiP",
     "amdr_tokenizer_destroy": "P",
+    "amdr_tokenizer_pack": "PPiPlP", "amdr_tokenizer_device_create": "PiP", "amdr_tokenizer_device_reserve": "Pil",
+    "amdr_tokenizer_encode_device": "PPPilPlPPP", "amdr_tokenizer_device_destroy": "P",
     "amdr_maxsim_create": "PPliiP", "amdr_maxsim_ndocs": "PP", "amdr_maxsim_plan_info": "PiPi", "amdr_maxsim_reserve": "Pii",
     "amdr_maxsim_search": "PPiiiPP", "amdr_maxsim_search_device": "PPiiiPPP", "amdr_maxsim_scores": "PPiiP",
     "amdr_maxsim_destroy": "P",
@@ -454,6 +458,99 @@ class Tokenizer:
     def close(self) -> None:
         if self._h:
             load().amdr_tokenizer_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+
+def utf8_views(texts: Sequence[Optional[str]]):
+    """(ptrs i64 [n], lens i64 [n], total bytes, maybe_han bool [n], keepalive) of a list of str: the UTF-8 bytes where
+    CPython keeps them (csrc/pystrings.c; without that glue, one encode per text, held by `keepalive`).  maybe_han[i] is
+    False where text i certainly holds no Han character (its storage kind cannot represent U+4E00 and above): an O(1)
+    test per string, no scan.  `texts` (or keepalive) must stay alive while the pointers are used."""
+    n = len(texts)
+    ptrs, lens = np.empty(n, dtype=np.int64), np.empty(n, dtype=np.int64)
+    wide = np.zeros(n, dtype=np.uint8)
+    views = _pystrings()
+    if views is not None:
+        total = int(views.utf8_views(texts, ptrs.ctypes.data, lens.ctypes.data, wide.ctypes.data)) if n else 0
+        return ptrs, lens, total, wide.astype(bool), None
+    enc = [(t or "").encode("utf-8") for t in texts]
+    for i, e in enumerate(enc):
+        ptrs[i] = C.cast(C.c_char_p(e), C.c_void_p).value or 0
+        lens[i] = len(e)
+        wide[i] = any(ord(ch) >= 0x4E00 for ch in (texts[i] or ""))
+    return ptrs, lens, int(lens.sum()), wide.astype(bool), enc
+
+
+def pack_utf8(ptrs: np.ndarray, lens: np.ndarray, blob_addr: int, capacity: int, offs_addr: int) -> None:
+    """The texts behind (ptrs, lens) back to back into the caller's buffer at blob_addr (capacity bytes), offsets
+    [n + 1] at offs_addr (amdr_tokenizer_pack; GIL released, the copies on the tokeniser's worker pool)."""
+    n = int(ptrs.shape[0])
+    _check(load().amdr_tokenizer_pack(ptrs.ctypes.data, lens.ctypes.data, n, _vp(blob_addr), int(capacity), _vp(offs_addr)),
+           "amdr_tokenizer_pack")
+
+
+def pack_texts(texts: Sequence[Optional[str]]) -> Tuple[np.ndarray, np.ndarray]:
+    """(blob u8 [total], offsets i64 [n + 1]): b"".join(t.encode() for t in texts) and its cumulative lengths, built by
+    amdr_tokenizer_pack from the strings' own UTF-8 views."""
+    ptrs, lens, total, _, keep = utf8_views(texts)
+    blob = np.empty(max(total, 1), dtype=np.uint8)
+    offs = np.empty(len(texts) + 1, dtype=np.int64)
+    pack_utf8(ptrs, lens, blob.ctypes.data, blob.size, offs.ctypes.data)
+    del keep
+    return blob[:total], offs
+
+
+class DeviceTokenizer:
+    """The batched query tokeniser on the device (amdr_tokenizer_*_device, csrc/tokenize.hip): a copy of a host
+    Tokenizer's vocabulary in HBM; encode_device turns a UTF-8 blob + offsets already on the device into the term-id
+    CSR amdr_bm25_search_device takes, byte for byte what Tokenizer.encode gives for the same bytes.  Enqueue only;
+    capturable after reserve()."""
+
+    def __init__(self, tok: "Tokenizer", *, device: int = 0):
+        self.device = int(device)
+        self._h = C.c_void_p()
+        self._tok = tok  # the host table is copied at creation; kept for callers that want both forms
+        _check(load().amdr_tokenizer_device_create(tok._h, C.c_int32(device), C.byref(self._h)),
+               "amdr_tokenizer_device_create")
+        self.nq_max, self.bytes_max = 0, -1
+
+    def reserve(self, nq_max: int, bytes_max: int) -> None:
+        _check(load().amdr_tokenizer_device_reserve(self._h, C.c_int32(nq_max), C.c_int64(bytes_max)),
+               "amdr_tokenizer_device_reserve")
+        self.nq_max, self.bytes_max = max(self.nq_max, int(nq_max)), max(self.bytes_max, int(bytes_max))
+
+    def encode_device_ptrs(self, text: int, offs: int, nq: int, n_bytes: int, term_ids: int, capacity: int, q_ptr: int,
+                           needs_segmenter: int, stream: int = 0) -> None:
+        _check(load().amdr_tokenizer_encode_device(self._h, _vp(text), _vp(offs), C.c_int32(nq), C.c_int64(n_bytes),
+                                                   _vp(term_ids), C.c_int64(capacity), _vp(q_ptr), _vp(needs_segmenter),
+                                                   _vp(stream)), "amdr_tokenizer_encode_device")
+
+    def encode_device(self, blob, offs, term_ids, q_ptr, needs_segmenter, *, nq: Optional[int] = None,
+                      n_bytes: Optional[int] = None, stream: Optional[int] = None) -> None:
+        """On torch device tensors: blob u8 [>= n_bytes], offs i64 [nq + 1] -> term_ids i32 [capacity = its length],
+        q_ptr i64 [nq + 1], needs_segmenter i32 [nq].  nq / n_bytes default to the tensors' sizes; stream to torch's
+        current stream."""
+        import torch
+        nq = int(offs.numel()) - 1 if nq is None else int(nq)
+        n_bytes = int(blob.numel()) if n_bytes is None else int(n_bytes)
+        for t in (blob, offs, term_ids, q_ptr, needs_segmenter):
+            assert t.is_cuda and t.is_contiguous()
+        assert offs.dtype == torch.int64 and term_ids.dtype == torch.int32 and q_ptr.dtype == torch.int64
+        assert needs_segmenter.dtype == torch.int32 and blob.element_size() == 1
+        if stream is None:
+            stream = int(torch.cuda.current_stream(blob.device).cuda_stream)
+        self.encode_device_ptrs(blob.data_ptr(), offs.data_ptr(), nq, n_bytes, term_ids.data_ptr(), int(term_ids.numel()),
+                                q_ptr.data_ptr(), needs_segmenter.data_ptr(), stream)
+
+    def close(self) -> None:
+        if getattr(self, "_h", None) and self._h.value:
+            load().amdr_tokenizer_device_destroy(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):

@@ -80,6 +80,26 @@ class RetrievalConfig:
                                          # HBM and every search all-gathers the per-shard top-k (retrieval/sharding.py)
     zh_tokenizer: str = "jieba"          # "jieba" (raises if Han text meets no segmenter) | "char" (explicit
                                          # opt-in to the inexact one-character stand-in, text.py)
+    query_tokenizer: str = "host"        # BM25 query side of search_batch / search_batch_arrays: "host" (native
+                                         # tokeniser on CPU threads) | "device" (tokenised on the GPU, csrc/tokenize.hip,
+                                         # for batches whose text the device rule decides; any other batch: host)
+
+    def __post_init__(self) -> None:
+        query_tokenizer_mode(self)
+
+
+QUERY_TOKENIZERS = ("host", "device")
+
+
+def query_tokenizer_mode(cfg) -> str:
+    """`query_tokenizer` of a RetrievalConfig (or of `cfg.retrieval` of a duck-typed app config): "host" by default;
+    ValueError for any other value than "host" / "device"."""
+    r = getattr(cfg, "retrieval", cfg)
+    m = getattr(r, "query_tokenizer", None)
+    m = "host" if m is None else m
+    if m not in QUERY_TOKENIZERS:
+        raise ValueError(f"retrieval.query_tokenizer must be one of {QUERY_TOKENIZERS}, got {m!r}")
+    return m
 
 
 @dataclass

@@ -28,194 +28,11 @@
 #include <vector>
 
 #include "common.hpp"
-
-// The vocabulary as an open-addressing table over ONE copy of the term bytes: a lookup hashes the token's bytes where
-// they lie in the query (no std::string is built per token) and compares with memcmp.
-struct amdr_tokenizer {
-  std::string blob;               // all terms, back to back
-  std::vector<int64_t> offs;      // term i = blob[offs[i] .. offs[i + 1])
-  std::vector<int32_t> slots;     // -1 = empty, else a term id; size = power of two >= 2 x terms
-  uint32_t mask = 0;
-  int32_t single[256];            // one-byte tokens (blanks and punctuation are two thirds of a query's tokens): direct
-  static inline uint32_t hash(const unsigned char* p, size_t n) {  // FNV-1a, folded
-    uint64_t h = 1469598103934665603ull;
-    for (size_t i = 0; i < n; ++i) h = (h ^ p[i]) * 1099511628211ull;
-    return (uint32_t)(h ^ (h >> 32));
-  }
-  inline int32_t find(const unsigned char* p, size_t n) const {
-    if (n == 1) return single[p[0]];
-    return find_slow(p, n);
-  }
-  inline int32_t find_slow(const unsigned char* p, size_t n) const {
-    if (slots.empty()) return -1;
-    for (uint32_t i = hash(p, n) & mask;; i = (i + 1) & mask) {
-      const int32_t id = slots[i];
-      if (id < 0) return -1;
-      const int64_t lo = offs[id];
-      if ((size_t)(offs[id + 1] - lo) == n && memcmp(blob.data() + lo, p, n) == 0) return id;
-    }
-  }
-};
+#include "tokenize_rule.hpp"
 
 namespace {
 
-inline bool is_alnum(uint32_t c) { return (c >= '0' && c <= '9') || (c >= 'a' && c <= 'z') || (c >= 'A' && c <= 'Z'); }
-inline bool is_digit(uint32_t c) { return c >= '0' && c <= '9'; }
-inline bool is_han(uint32_t c) { return c >= 0x4E00 && c <= 0x9FD5; }
-inline bool is_block(uint32_t c) {
-  return is_alnum(c) || is_han(c) || c == '+' || c == '#' || c == '&' || c == '.' || c == '_' || c == '%' || c == '-';
-}
-// Python str.isspace() == what \s matches in a str pattern
-inline bool is_space(uint32_t c) {
-  return (c >= 0x09 && c <= 0x0D) || (c >= 0x1C && c <= 0x20) || c == 0x85 || c == 0xA0 || c == 0x1680 ||
-         (c >= 0x2000 && c <= 0x200A) || c == 0x2028 || c == 0x2029 || c == 0x202F || c == 0x205F || c == 0x3000;
-}
-
-// decode one UTF-8 code point at p (< end); malformed bytes are taken one at a time (Python str input cannot be
-// malformed; this only keeps the scan inside the buffer)
-inline uint32_t decode(const unsigned char* p, const unsigned char* end, int* len) {
-  const unsigned char b = *p;
-  if (b < 0x80) {
-    *len = 1;
-    return b;
-  }
-  int n = (b >= 0xF0) ? 4 : (b >= 0xE0) ? 3 : (b >= 0xC0) ? 2 : 1;
-  if (n == 1 || p + n > end) {
-    *len = 1;
-    return 0xFFFD;
-  }
-  uint32_t c = b & (0xFF >> (n + 1));
-  for (int i = 1; i < n; ++i) c = (c << 6) | (p[i] & 0x3F);
-  *len = n;
-  return c;
-}
-
-struct Span {
-  int32_t lo, hi;  // byte range of a token
-};
-
-// finalseg's non-Han rule on an ASCII buffer [lo, hi)
-template <class Emit>
-inline void finalseg_ascii(const unsigned char* s, int lo, int hi, Emit&& emit) {
-  int i = lo;
-  while (i < hi) {
-    int j = i;
-    if (is_alnum(s[i])) {
-      while (j < hi && is_alnum(s[j])) ++j;
-      if (j + 1 < hi && s[j] == '.' && is_digit(s[j + 1])) {
-        ++j;
-        while (j < hi && is_digit(s[j])) ++j;
-      }
-      if (j < hi && s[j] == '%') ++j;
-    } else {
-      while (j < hi && !is_alnum(s[j])) ++j;
-    }
-    emit(i, j);
-    i = j;
-  }
-}
-
-inline int dict_word_at(const unsigned char* s, int i, int hi) {  // length of an ASCII dictionary word starting at i, or 0
-  static const char* const kWords[] = {"AT&T", "C++", "c++", "C#", "c#"};
-  for (const char* w : kWords) {
-    const int n = (int)strlen(w);
-    if (i + n <= hi && memcmp(s + i, w, n) == 0) return n;
-  }
-  return 0;
-}
-
-// a block without Han characters (ASCII by construction)
-template <class Emit>
-inline void cut_block(const unsigned char* s, int lo, int hi, Emit&& emit) {
-  bool marks = false;
-  for (int i = lo; i < hi; ++i) marks |= (s[i] == '&' || s[i] == '+' || s[i] == '#');
-  auto flush = [&](int a, int b) {
-    if (b - a == 1)
-      emit(a, b);
-    else if (b > a)
-      finalseg_ascii(s, a, b, emit);
-  };
-  if (!marks) {
-    flush(lo, hi);
-    return;
-  }
-  int buf = lo, i = lo;
-  while (i < hi) {
-    const int n = dict_word_at(s, i, hi);
-    if (n) {
-      flush(buf, i);
-      emit(i, i + n);
-      i += n;
-      buf = i;
-    } else {
-      ++i;
-    }
-  }
-  flush(buf, hi);
-}
-
-// byte classes of the ASCII fast path: 1 = block character ([a-zA-Z0-9+#&._%-]), 0 = anything else
-struct AsciiBlock {
-  unsigned char t[256];
-  AsciiBlock() {
-    for (int c = 0; c < 256; ++c) t[c] = (c < 0x80 && is_block((uint32_t)c)) ? 1 : 0;
-  }
-};
-static const AsciiBlock kAsciiBlock;
-
-// tokens of one sentence; returns false (nothing emitted is meaningful) when it holds a Han character
-template <class Emit>
-inline bool tokenize(const unsigned char* s, int n, Emit&& emit) {
-  // pure ASCII (every English query): no decoding, no Han check, one table lookup per byte — the same rule
-  bool ascii = true;
-  for (int i = 0; i < n; ++i) ascii &= s[i] < 0x80;
-  if (ascii) {
-    int i = 0;
-    while (i < n) {
-      if (kAsciiBlock.t[s[i]]) {
-        int j = i + 1;
-        while (j < n && kAsciiBlock.t[s[j]]) ++j;
-        cut_block(s, i, j, emit);
-        i = j;
-      } else if (s[i] == '\r' && i + 1 < n && s[i + 1] == '\n') {
-        emit(i, i + 2);
-        i += 2;
-      } else {
-        emit(i, i + 1);
-        ++i;
-      }
-    }
-    return true;
-  }
-  const unsigned char* end = s + n;
-  for (int i = 0; i < n;) {  // Han anywhere -> the whole sentence goes to the caller's segmenter
-    int len;
-    if (is_han(decode(s + i, end, &len))) return false;
-    i += len;
-  }
-  int i = 0;
-  while (i < n) {
-    int len;
-    const uint32_t c = decode(s + i, end, &len);
-    if (is_block(c)) {
-      int j = i;
-      while (j < n) {
-        int l2;
-        if (!is_block(decode(s + j, end, &l2))) break;
-        j += l2;
-      }
-      cut_block(s, i, j, emit);
-      i = j;
-    } else if (c == '\r' && i + 1 < n && s[i + 1] == '\n') {
-      emit(i, i + 2);
-      i += 2;
-    } else {  // one whitespace character, or any other character on its own
-      emit(i, i + len);
-      i += len;
-    }
-  }
-  return true;
-}
+using amdr_tok::tokenize;
 
 }  // namespace
 
@@ -457,6 +274,33 @@ int amdr_tokenizer_encode_joined(const amdr_tokenizer_t* t, const char* text_blo
   offs[(size_t)nq] = n_bytes;
   return encode_offsets(t, reinterpret_cast<const unsigned char*>(text_blob), offs.data(), 1, nq, term_ids, capacity, q_ptr,
                         needs_segmenter);
+}
+
+int amdr_tokenizer_pack(const char* const* texts, const int64_t* n_bytes, int32_t nq, char* blob, int64_t capacity,
+                        int64_t* offsets) {
+  AMDR_REQUIRE(nq >= 0 && offsets && (nq == 0 || (texts && n_bytes)), "tokenizer_pack: null buffer");
+  AMDR_REQUIRE(capacity >= 0 && (capacity == 0 || blob), "tokenizer_pack: null blob");
+  int64_t tot = 0;
+  for (int32_t q = 0; q < nq; ++q) {
+    AMDR_REQUIRE(n_bytes[q] >= 0 && (n_bytes[q] == 0 || texts[q]), "tokenizer_pack: bad text at query %d", q);
+    tot += n_bytes[q];
+  }
+  AMDR_REQUIRE(tot <= capacity, "tokenizer_pack: blob too small (capacity %lld, %lld bytes)", (long long)capacity,
+               (long long)tot);
+  offsets[0] = 0;
+  for (int32_t q = 0; q < nq; ++q) offsets[q + 1] = offsets[q] + n_bytes[q];
+  // the copies on the tokeniser's worker pool: one range of queries per worker, as encode_core cuts them
+  Pool& pool = Pool::get();
+  int parts = pool.workers();
+  if (parts > nq / 1024) parts = nq / 1024;
+  if (parts < 1) parts = 1;
+  std::function<void(int)> copy = [&](int p) {
+    const int32_t lo = (int32_t)((int64_t)nq * p / parts), hi = (int32_t)((int64_t)nq * (p + 1) / parts);
+    for (int32_t q = lo; q < hi; ++q)
+      if (n_bytes[q]) memcpy(blob + offsets[q], texts[q], (size_t)n_bytes[q]);
+  };
+  pool.run(parts, copy);
+  return AMDR_OK;
 }
 
 int amdr_tokenizer_spans(const char* text, int64_t n_bytes, int32_t* starts, int32_t* ends, int32_t capacity,

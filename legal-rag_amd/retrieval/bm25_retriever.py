@@ -101,12 +101,8 @@ class BM25Retriever:
         # per query, not per process (round 3 sent every English query through per-query Python once jieba was importable).
         native_ok = text._custom_cut is None
         if native_ok:
-            tok = self.__dict__.get("_native_tok")
-            if tok is None or tok[0] is not self.bm25:
-                tok = (self.bm25, _native.Tokenizer(list(self.bm25.vocab().keys())))
-                self.__dict__["_native_tok"] = tok
             qs = questions  # (None counts as the empty query inside the native call)
-            terms, q_ptr, hard = tok[1].encode(qs)
+            terms, q_ptr, hard = self.native_tokenizer().encode(qs)
             if text.HAVE_JIEBA:
                 qs = [q or "" for q in questions]
                 joined = "\0".join(qs)
@@ -134,6 +130,42 @@ class BM25Retriever:
         out_ptr = np.zeros(n + 1, dtype=np.int64)
         np.cumsum(lens, out=out_ptr[1:])
         return (np.concatenate(parts).astype(np.int32) if parts else np.zeros(0, np.int32)), out_ptr, exact
+
+    def native_tokenizer(self):
+        """The batched native tokeniser (_native.Tokenizer) over this index's vocabulary, built once per loaded index."""
+        from .. import _native
+        tok = self.__dict__.get("_native_tok")
+        if tok is None or tok[0] is not self.bm25:
+            tok = (self.bm25, _native.Tokenizer(list(self.bm25.vocab().keys())))
+            self.__dict__["_native_tok"] = tok
+        return tok[1]
+
+    def device_tokenizer(self):
+        """The same tokeniser on this retriever's GPU (_native.DeviceTokenizer: a copy of native_tokenizer()'s table)."""
+        from .. import _native
+        self.load()
+        ent = self.__dict__.get("_device_tok")
+        if ent is None or ent[0] is not self.bm25 or ent[1] != self.device_index:
+            ent = (self.bm25, self.device_index, _native.DeviceTokenizer(self.native_tokenizer(), device=self.device_index))
+            self.__dict__["_device_tok"] = ent
+        return ent[2]
+
+    def device_text_batch(self, questions: Sequence[str]):
+        """The batch's UTF-8 views (_native.utf8_views: ptrs, lens, total bytes, keepalive) when the device tokeniser
+        decides EVERY query exactly as term_ids_batch would, else None (the caller takes term_ids_batch): no registered
+        segmenter, no Han character (an O(1) test of each string's storage kind first; only strings that could hold one
+        are searched) and, when jieba is importable, none of its ASCII dictionary entries — term_ids_batch's routing.
+        Every query of such a batch is tokenised exactly (zh_exact)."""
+        import numpy as np
+        from .. import _native
+        if text._custom_cut is not None:
+            return None
+        ptrs, lens, total, maybe_han, keep = _native.utf8_views(questions)
+        if maybe_han.any() and any(text.contains_han(questions[i] or "") for i in np.flatnonzero(maybe_han)):
+            return None
+        if text.HAVE_JIEBA and any(w in "\0".join(q or "" for q in questions) for w in text._ASCII_DICT_WORDS):
+            return None
+        return ptrs, lens, total, keep
 
     @property
     def zh_exact(self) -> bool:

@@ -35,6 +35,7 @@ class BatchResult:
     colbert_scores: Optional[torch.Tensor] = None
     rerank: Optional[torch.Tensor] = None  # f64 [nq, max_out, 2] (raw, norm) after rerank_blend
     packed: Optional[torch.Tensor] = None  # u8: ids | vals | mask | count in ONE allocation (one D2H for the host API)
+    needs_segmenter: Optional[torch.Tensor] = None  # i32 [nq] of a text-in step (q_text): 1 = Han query, no BM25 terms
 
     def to_host(self):
         """(ids, vals, mask, count) as numpy arrays through ONE device-to-host copy (the first `.cpu()` of a result
@@ -59,7 +60,7 @@ class HybridEngine:
                  maxsim: Optional[_native.MaxSimIndex] = None, *, device: int = 0,
                  dense_row2uid: Optional[torch.Tensor] = None, bm25_row2uid: Optional[torch.Tensor] = None,
                  colbert_row2uid: Optional[torch.Tensor] = None, shard_offset: Optional[int] = None,
-                 shard_group=None):
+                 shard_group=None, tokenizer: Optional[_native.DeviceTokenizer] = None):
         if not torch.cuda.is_available():
             raise RuntimeError("HybridEngine needs a GPU (no CPU fallback)")
         self.dense, self.bm25, self.maxsim = dense, bm25, maxsim
@@ -73,6 +74,8 @@ class HybridEngine:
         # ONCE per batch, merges W*k -> k per channel (merge_parts_kernel) and fuses the GLOBAL lists — the
         # result is identical on every rank.  None: one index holds everything, nothing is exchanged.
         self.shard_offset, self.shard_group = shard_offset, shard_group
+        # the BM25 query side on the device (text-in steps, q_text=): a copy of the BM25 vocabulary's host tokeniser
+        self.tokenizer = tokenizer
 
     def _buf(self, name, shape, dtype):
         key = (name, tuple(shape), dtype)
@@ -109,6 +112,41 @@ class HybridEngine:
         dev[: n1 + n2].copy_(host[: n1 + n2], non_blocking=True)
         return dev[:n1].view(torch.int64), dev[n1:n1 + n2].view(torch.int32)
 
+    def upload_text(self, ptrs, lens, total: int):
+        """Query texts (UTF-8 pointer / length arrays, _native.utf8_views) -> (blob u8 [total], offs i64 [n + 1]) on the
+        device: packed straight into pinned staging (amdr_tokenizer_pack: offsets first, then the bytes) and sent up
+        by ONE host-to-device copy."""
+        n = int(ptrs.shape[0])
+        n1 = (n + 1) * 8
+        nbytes = n1 + int(total)
+        host = self._pinned("txt", nbytes)
+        base = host.data_ptr()
+        _native.pack_utf8(ptrs, lens, base + n1, int(total), base)
+        dev = self._bufs.get(("txt_dev",))
+        if dev is None or dev.numel() < nbytes:
+            dev = torch.empty((host.numel(),), dtype=torch.uint8, device=self.tdev)
+            self._bufs[("txt_dev",)] = dev
+        dev[:nbytes].copy_(host[:nbytes], non_blocking=True)
+        return dev[n1:nbytes], dev[:n1].view(torch.int64)
+
+    def tokenize_device(self, blob: torch.Tensor, offs: torch.Tensor):
+        """BM25 query side of a text-in step on the device: (q_terms i32, q_ptr i64 [nq + 1], needs_segmenter i32 [nq])
+        from the UTF-8 blob and its offsets (device tensors; nq = offs.numel() - 1, n_bytes = blob.numel()).  q_terms
+        is the whole term buffer (sized from the reserve: tokens <= bytes); q_ptr says which part is used.  A query that
+        holds a Han character gets needs_segmenter = 1 and no terms (the caller decides what to do with it)."""
+        if self.tokenizer is None:
+            raise RuntimeError("tokenize_device: this engine has no device tokeniser (HybridEngine(..., tokenizer=))")
+        assert blob.is_cuda and blob.element_size() == 1 and offs.is_cuda and offs.dtype == torch.int64
+        nq, n_bytes = int(offs.numel()) - 1, int(blob.numel())
+        tok = self.tokenizer
+        if nq > tok.nq_max or n_bytes > tok.bytes_max:
+            tok.reserve(max(nq, tok.nq_max), max(n_bytes, tok.bytes_max))  # eager first use (capture() reserves first)
+        tt = self._buf("tkt", (max(tok.bytes_max, 1),), torch.int32)
+        tp = self._buf("tkp", (nq + 1,), torch.int64)
+        tf = self._buf("tkf", (max(nq, 1),), torch.int32)
+        tok.encode_device(blob, offs.contiguous(), tt, tp, tf[:nq], nq=nq, n_bytes=n_bytes, stream=_stream())
+        return tt, tp, tf[:nq]
+
     def compact_to_host(self, res: "BatchResult", w: int):
         """(rows i64 [nq, w], scores f64 [nq, w], channel mask i32 [nq, w], count i32 [nq]) of a fused result on the host:
         compacted by ONE kernel (amdr_fuse_compact_device), ONE copy into pinned memory, one synchronise."""
@@ -130,7 +168,12 @@ class HybridEngine:
         return (h[:o1].view("int64").reshape(nq, w).copy(), h[o1:o2].view("float64").reshape(nq, w).copy(),
                 h[o2:o3].view("int32").reshape(nq, w).copy(), h[o3:tot].view("int32").copy())
 
-    def reserve(self, nq: int, k: int, total_terms: int = 0) -> None:
+    def reserve(self, nq: int, k: int, total_terms: int = 0, bytes_max: int = 0) -> None:
+        """bytes_max > 0: text-in steps of up to that many bytes of query text (q_text); BM25 then takes up to bytes_max
+        terms (tokens <= bytes)."""
+        if bytes_max > 0 and self.tokenizer is not None:
+            self.tokenizer.reserve(nq, bytes_max)
+            total_terms = max(total_terms, bytes_max)
         if self.dense is not None:
             self.dense.reserve(nq, k)
         if self.bm25 is not None:
@@ -246,8 +289,17 @@ class HybridEngine:
     # -- whole pipeline ---------------------------------------------------------
     def search_batch(self, params: _native.FuseParams, k: int, *, q_emb: Optional[torch.Tensor] = None,
                      q_terms: Optional[torch.Tensor] = None, q_ptr: Optional[torch.Tensor] = None,
-                     q_tok: Optional[torch.Tensor] = None) -> BatchResult:
-        """dense + bm25 (+ colbert) top-k -> fuse -> min_final filter, all on device."""
+                     q_tok: Optional[torch.Tensor] = None, q_text=None) -> BatchResult:
+        """dense + bm25 (+ colbert) top-k -> fuse -> min_final filter, all on device.
+        q_text = (blob u8, offs i64 [nq + 1]) device tensors: the BM25 query side as text, tokenised on the device
+        (tokenize_device) in the same stream, instead of q_terms / q_ptr."""
+        if q_text is not None:
+            if q_terms is not None or q_ptr is not None:
+                raise ValueError("search_batch: pass q_text or q_terms / q_ptr, not both")
+            q_terms, q_ptr, flags = self.tokenize_device(*q_text)
+            res = self.search_batch(params, k, q_emb=q_emb, q_terms=q_terms, q_ptr=q_ptr, q_tok=q_tok)
+            res.needs_segmenter = flags
+            return res
         d = b = c = None
         nq = None
         if (self.dense is not None and q_emb is not None and self.bm25 is not None and q_ptr is not None
@@ -311,7 +363,7 @@ class HybridEngine:
     # -- hipGraph form -----------------------------------------------------------
     def capture(self, params: _native.FuseParams, k: int, *, q_emb: Optional[torch.Tensor] = None,
                 q_terms: Optional[torch.Tensor] = None, q_ptr: Optional[torch.Tensor] = None,
-                q_tok: Optional[torch.Tensor] = None):
+                q_tok: Optional[torch.Tensor] = None, q_text=None):
         """Record one search_batch over the given tensors into a hipGraph.
 
         Returns (graph, result): `graph.replay()` re-runs the whole step — every kernel of every
@@ -322,17 +374,23 @@ class HybridEngine:
         kernels is launch-bound at small batch: replay removes the per-kernel launch gaps.  (Measured: the BM25
         channel on a forked branch of the captured graph — it does not depend on the dense channel — replays in
         45 us against 33 us for the plain chain: the fork / join nodes cost more than the 5-us kernel they hide.)
+        With q_text = (blob, offs) the graph starts from query BYTES: tokeniser + channels + fusion; a replay takes new
+        text written into the same two tensors (same nq, at most blob.numel() bytes, offs[nq] <= that).
         """
         if self.shard_offset is not None:
             raise RuntimeError("capture: a sharded step contains a collective; it is not recorded into a hipGraph")
-        nq = (q_emb.shape[0] if q_emb is not None else q_ptr.shape[0] - 1 if q_ptr is not None else q_tok.shape[0])
-        self.reserve(int(nq), int(k), int(q_terms.numel()) if q_terms is not None else 0)
+        if q_text is not None:
+            nq = int(q_text[1].numel()) - 1
+            self.reserve(nq, int(k), 0, bytes_max=max(int(q_text[0].numel()), 1))
+        else:
+            nq = (q_emb.shape[0] if q_emb is not None else q_ptr.shape[0] - 1 if q_ptr is not None else q_tok.shape[0])
+            self.reserve(int(nq), int(k), int(q_terms.numel()) if q_terms is not None else 0)
         side = torch.cuda.Stream(device=self.tdev)
         side.wait_stream(torch.cuda.current_stream(self.tdev))
         with torch.cuda.stream(side):  # eager warm-up sizes every lazily grown buffer outside the capture
-            self.search_batch(params, k, q_emb=q_emb, q_terms=q_terms, q_ptr=q_ptr, q_tok=q_tok)
+            self.search_batch(params, k, q_emb=q_emb, q_terms=q_terms, q_ptr=q_ptr, q_tok=q_tok, q_text=q_text)
         side.synchronize()
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph):
-            res = self.search_batch(params, k, q_emb=q_emb, q_terms=q_terms, q_ptr=q_ptr, q_tok=q_tok)
+            res = self.search_batch(params, k, q_emb=q_emb, q_terms=q_terms, q_ptr=q_ptr, q_tok=q_tok, q_text=q_text)
         return graph, res

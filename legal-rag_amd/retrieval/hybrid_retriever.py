@@ -32,6 +32,7 @@ from typing import Any, Dict, List, Optional, Sequence, Set
 import numpy as np
 
 from .. import _native
+from ..config import query_tokenizer_mode
 from ..schemas import RetrievalHit
 from .bm25_retriever import BM25Retriever
 from .colbert_retriever import ColBERTRetriever
@@ -556,9 +557,12 @@ class HybridRetriever:
                             device=dev, shard_offset=offset, shard_group=shard.group if shard is not None else None)
 
     def _batch_native(self, questions: Sequence[str], eff: int, native, min_final: float, arrays: bool = False,
-                      q_emb=None, compact_w: int = 0):
+                      q_emb=None, compact_w: int = 0, device_tok: bool = False):
         """Embed / tokenise on the host, then dense + BM25 (+ MaxSim) top-k -> fuse -> min_final
         count for the whole batch on torch's current stream, one synchronise, results built once.
+        device_tok (cfg.retrieval.query_tokenizer = "device"): a batch the device rule decides
+        (BM25Retriever.device_text_batch) goes up as UTF-8 text and is tokenised on the GPU in the same stream
+        (HybridEngine.tokenize_device); any other batch takes the host tokeniser as before.
         Returns ([fused hits with score >= min_final per question], (t_after_dense_prep, t_after_bm25_prep,
         t_after_colbert_prep))."""
         import torch
@@ -576,7 +580,7 @@ class HybridRetriever:
             for idxs, nat in ((blank, (store, bm, None)), (rest, native)):
                 if idxs:
                     part, stamps = self._batch_native([questions[i] for i in idxs], eff, nat, min_final,
-                                                      q_emb=None if q_emb is None else q_emb[idxs])
+                                                      q_emb=None if q_emb is None else q_emb[idxs], device_tok=device_tok)
                     for i, h in zip(idxs, part):
                         out[i] = h
             return out, stamps
@@ -590,9 +594,13 @@ class HybridRetriever:
             if q_emb.shape != (len(questions), store.index.d):
                 raise ValueError(f"q_emb must be [{len(questions)}, {store.index.d}], got {tuple(q_emb.shape)}")
         t1 = time.time()
-        qt, qp, exact = bm.term_ids_batch(questions)  # native batched tokeniser + vocabulary lookup
-        if qt.size == 0:
-            qt = np.zeros(1, dtype=np.int32)  # pack_queries' convention for "no term at all"
+        txt = bm.device_text_batch(questions) if device_tok else None
+        if txt is None:
+            qt, qp, exact = bm.term_ids_batch(questions)  # native batched tokeniser + vocabulary lookup
+            if qt.size == 0:
+                qt = np.zeros(1, dtype=np.int32)  # pack_queries' convention for "no term at all"
+        else:
+            exact = np.ones(len(questions), dtype=bool)  # text without Han characters: tokenised exactly
         t2 = time.time()
         q_tok_h = None
         if col is not None:
@@ -623,9 +631,16 @@ class HybridRetriever:
                 eng = self._make_engine(store, bm, col, dev)
                 engines[col is not None] = eng
                 self.__dict__["_native_engine"] = engines
-            # BM25 query CSR in ONE host-to-device copy through pinned staging: q_ptr (i64) then q_terms (i32)
-            q_ptr_d, q_terms_d = eng.upload_csr(np.ascontiguousarray(qp, dtype=np.int64),
-                                                np.ascontiguousarray(qt, dtype=np.int32))
+            if txt is None:
+                # BM25 query CSR in ONE host-to-device copy through pinned staging: q_ptr (i64) then q_terms (i32)
+                q_ptr_d, q_terms_d = eng.upload_csr(np.ascontiguousarray(qp, dtype=np.int64),
+                                                    np.ascontiguousarray(qt, dtype=np.int32))
+            else:
+                # the query texts in ONE host-to-device copy (packed into pinned staging), the CSR made on the device
+                eng.tokenizer = bm.device_tokenizer()
+                blob_d, offs_d = eng.upload_text(txt[0], txt[1], txt[2])
+                q_terms_d, q_ptr_d, _ = eng.tokenize_device(blob_d, offs_d)
+                del txt
             try:
                 res = eng.search_batch(self._params(kn, min_final), eff, q_emb=q_emb, q_terms=q_terms_d, q_ptr=q_ptr_d,
                                        q_tok=None if q_tok_h is None else
@@ -676,7 +691,8 @@ class HybridRetriever:
         if native is None:
             raise RuntimeError("search_batch requires this package's own dense / BM25 (/ ColBERT) retrievers built "
                                "over the same chunk list")
-        outs, _ = self._batch_native(questions, eff, native, float(getattr(rcfg, "min_final_score", 0.0)), q_emb=q_emb)
+        outs, _ = self._batch_native(questions, eff, native, float(getattr(rcfg, "min_final_score", 0.0)), q_emb=q_emb,
+                                     device_tok=query_tokenizer_mode(self.cfg) == "device")
         if getattr(rcfg, "enable_graph", False) and decisions is not None:
             seed_n = int(getattr(rcfg, "graph_seed_k", max(10, top_k * 3)))
             for i, dec in enumerate(decisions):
@@ -705,12 +721,13 @@ class HybridRetriever:
             # PCIe instead of the full fused record (9 doubles for every candidate of every channel: 1.6 KB per query)
             (rows, scores, cmask, cnt, exact), _ = self._batch_native(
                 list(questions), eff, native, float(getattr(rcfg, "min_final_score", 0.0)), arrays=True, q_emb=q_emb,
-                compact_w=top_k)
+                compact_w=top_k, device_tok=query_tokenizer_mode(self.cfg) == "device")
             return {"rows": rows, "scores": scores, "count": cnt, "channel_mask": cmask, "zh_exact": exact,
                     "chunks": native[0].chunks}
         (ids, vals, mask, cnt, exact), _ = self._batch_native(list(questions), eff, native,
                                                                 float(getattr(rcfg, "min_final_score", 0.0)), arrays=True,
-                                                                q_emb=q_emb)
+                                                                q_emb=q_emb,
+                                                                device_tok=query_tokenizer_mode(self.cfg) == "device")
         w = min(top_k, ids.shape[1])
         keep = np.arange(w)[None, :] < np.minimum(cnt, w)[:, None]
         return {"rows": np.where(keep, ids[:, :w], -1), "scores": np.where(keep, vals[:, :w, _native.FV["score"]], 0.0),
