@@ -555,7 +555,7 @@ __global__ __launch_bounds__(64) void dense_select_fuse_kernel(amdr_fuse_params_
 //      butterfly sum);
 //   3. sorted by (exact score, lower id first): the dense channel's top-k — then the fusion, as before.
 // More than 32 rows inside the margin (mass near-ties), or no bound for the query (eps NaN): the half-wave re-scores EVERY
-// row exactly (into LDS) and the plain selectors run on that.  margin_scale (test hook) widens the margin.
+// row exactly (over its own row of S) and the plain selectors run on that.  margin_scale (test hook) widens the margin.
 template <int V>
 __device__ __forceinline__ int select_row_pair_margin(const float* __restrict__ S, long ldS, long n, int q, bool has_q, int k,
                                                       float margin, int lane, C32* scratch, C32& out, int& need) {
@@ -733,24 +733,24 @@ __global__ __launch_bounds__(64) void dense_hi_select_fuse_kernel(amdr_fuse_para
     if (lane == 0 && fallbacks) atomicAdd(fallbacks, (unsigned int)__popcll(fbm));
     const C32 keep = out;
     const int keep_need = need, keep_got = got;
-    // the exact scores of the half's whole row, in LDS (two rows of 1 024 floats behind the selectors' scratch), then the
-    // plain selectors on them
-    float* xs = reinterpret_cast<float*>(buf + 128);
-    for (int r = sl; r < 1024; r += 32) xs[1024 * half + r] = 0.f;
-    wave_lds_fence();
+    // the exact scores of the half's whole row, written over its own row of S (the selector above has read it into
+    // registers, and this block is its only reader), then the plain selectors on them.  (They were two rows of 1 024
+    // floats in LDS: 8 KiB in every block for a path the headline takes for no query, and the LDS capped the kernel at
+    // three waves per SIMD where its registers allow four.)  Rows r >= n are never read: the selectors mask them.
+    float* xs = const_cast<float*>(S);
     for (long r = 0; r < n; ++r) {
       const float v = row_dot(r);
-      if (exact_all && sl == 0) xs[1024 * half + r] = v;
+      if (exact_all && sl == 0) xs[(size_t)q * ldS + r] = v;
     }
-    wave_lds_fence();
+    __threadfence_block();  // the stores are complete before the wave reads them back (one CU: its L1 is write-through)
     C32 o2 = C32::pad();
-    int g2 = select_row_pair_any(xs, 1024, n, half, has_q && exact_all, kd, lane, buf, o2);
+    int g2 = select_row_pair_any(xs, ldS, n, q, has_q && exact_all, kd, lane, buf, o2);
     if (g2 < 0) {  // mass ties at the cut among EXACT scores: the staged selector, one half after the other
       for (int hh = 0; hh < 2; ++hh) {
         const int qq = 2 * blockIdx.x + hh;
         const bool mine_h = __shfl((int)exact_all, 32 * hh) != 0;
         if (qq >= nq || !mine_h) continue;
-        const float* row = xs + 1024 * hh;
+        const float* row = xs + (size_t)qq * ldS;
         WaveTopK<C32> tk;
         tk.init(buf, 128, kd);
         for (long base = 0; base < n; base += 64) {
@@ -1096,13 +1096,15 @@ int dense_select_fuse_launch(const FuseTail& t, int q0, const float* S, long ldS
   return AMDR_OK;
 }
 
-// second pass of the two-pass long-batch form (dense_hi_select_fuse_kernel); t == nullptr: the dense lists only
+// second pass of the two-pass long-batch form (dense_hi_select_fuse_kernel); t == nullptr: the dense lists only.
+// S is the caller's scratch score matrix: a query that takes the whole-row fallback gets its row overwritten with exact
+// scores.
 int dense_hi_select_launch(const FuseTail* t, int q0, const float* S, long ldS, long n, int m, int kd, const float* X,
                            const float* Q, int d, const float* eps, float* fin_scores, int64_t* fin_ids,
                            unsigned int* fallbacks, hipStream_t st) {
   const char* ms = getenv("AMDR_DENSE_SMALL_HI_MARGIN");  // test hook: widens the candidate margin (a huge one: every
   const float margin_scale = ms ? (float)atof(ms) : 1.f;  // query takes the exact fallback inside the kernel)
-  const size_t lds = 128 * sizeof(C32) + 2 * 1024 * sizeof(float);  // the selectors' scratch + two rows of exact scores
+  const size_t lds = 128 * sizeof(C32);  // the selectors' scratch (the whole-row fallback re-uses the rows of S)
   if (t) {
     const int mo = kd + t->kb;
     ChanIn c0{nullptr, nullptr, (const long long*)t->dense_row2uid, kd, 0};
