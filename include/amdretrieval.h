@@ -49,6 +49,7 @@ typedef struct amdr_bm25 amdr_bm25_t;
 typedef struct amdr_maxsim amdr_maxsim_t;
 typedef struct amdr_tokenizer amdr_tokenizer_t;
 typedef struct amdr_tokenizer_device amdr_tokenizer_device_t;
+typedef struct amdr_graph amdr_graph_t;
 
 /* ---- library ---------------------------------------------------------- */
 const char* amdr_last_error(void);
@@ -343,6 +344,76 @@ int amdr_rerank_blend_device(int32_t nq, int32_t max_out, const int32_t* count, 
 int amdr_fuse_compact_device(int32_t nq, int32_t max_out, int32_t w, const int64_t* ids, const double* vals,
                              const int32_t* mask, const int32_t* count, int64_t* out_rows, double* out_scores,
                              int32_t* out_mask, int32_t* out_count, int32_t device, void* stream);
+
+/* ---- graph channel: law-graph walk + re-scoring of the walked articles --------------------------------------------
+ * Replaces, for a whole batch, the per-query host stage HybridRetriever.search runs for a GRAPH_AUGMENTED decision
+ * (legalrag/retrieval/hybrid_retriever.py:312-322): LawGraphStore.walk (graph_store.py:89-169, a Python BFS over up to
+ * graph_limit nodes), the re-embedding of every visited article and its cosine with the query, the score product and
+ * the sort (graph_retriever.py:82-219).  csrc/graph.hip.
+ * Graph tables (host arrays, copied to the device at creation), over n_nodes interned article ids:
+ *   node_ptr i64 [n_nodes + 1], edge_dst i32 / edge_rel i32 / edge_conf_raw f64 / edge_conf_eff f64 /
+ *   edge_has_evidence i32 [n_edges]   CSR adjacency in file order; conf_raw = float(conf or 1.0) (the min_conf filter),
+ *                                     conf_eff = the edge confidence the score takes (conf_raw with evidence, else the
+ *                                     stored destination's meta "_edge_conf" or 1.0)
+ *   node_present i32 [n_nodes]        1 = a stored node (found and expanded); 0 = a destination only (claimed, never
+ *                                     emitted), as on the host
+ *   node_row i64 [n_nodes]            chunk row of the node's article (-1: no chunk, empty text)
+ *   row_node i32 [n_rows]             node of the stripped article key of a chunk row (-1: none)
+ *   row_norm f32 [n_rows]             row L2 norms as the host computes them; row_lang i32 [n_rows] (nullable)
+ * Per call (amdr_graph_params_t): limit in [1, 4096] found nodes, default_depth (seeds), min_conf (> 0: edges with
+ * conf_raw below it are skipped), per relation max_depth (a node reached by relation r expands while its depth <
+ * max_depth[r]), allowed (0/1) and weight, decay[0 .. limit] (decay[depth]), lang (-1 = any; else rows whose row_lang
+ * differs drop out).  The tables are HOST pointers for amdr_graph_walk / amdr_graph_search and DEVICE pointers for
+ * amdr_graph_search_device.
+ * Per query: seeds = the first min(seed_n <= 1024, seed_count[q]) entries of row q of seeds [*, ld]; the walk equals
+ * LawGraphStore.walk node for node; every found node with a chunk row scores
+ *   semantic = <q, X[row]> / (sqrtf(<q, q>) * row_norm[row] + 1e-9f)   (fp32; the dot as amdr_dense_score_rows)
+ *   final    = ((double)semantic * decay[depth]) * weight[rel] * conf_eff
+ * and the top k <= AMDR_MAX_K by final are written, ties -> earlier walk position: out_count [n], out_rows i64,
+ * out_final f64, out_semantic f32, out_depth i32, out_rel i32, out_conf f64 (conf_eff) [n, k] (past out_count: -1 /
+ * 0).  The only difference from the host path: numpy computes |q| with BLAS in its own summation order.
+ * The dense handle gives the resident chunk matrix (same device; its rows are the chunk rows above). */
+typedef struct amdr_graph_params {
+  int32_t limit;
+  int32_t default_depth;
+  int32_t lang;
+  int32_t pad0;
+  double min_conf;
+  const int32_t* rel_max_depth;
+  const int32_t* rel_allowed;
+  const double* rel_weight;
+  const double* decay;
+} amdr_graph_params_t;
+int amdr_graph_create(const int64_t* node_ptr, const int32_t* edge_dst, const int32_t* edge_rel,
+                      const double* edge_conf_raw, const double* edge_conf_eff, const int32_t* edge_has_evidence,
+                      const int32_t* node_present, const int64_t* node_row, const int32_t* row_node,
+                      const float* row_norm, const int32_t* row_lang, int32_t n_nodes, int64_t n_edges,
+                      int64_t n_rows, int32_t n_rel, int32_t device, amdr_graph_t** out);
+/* sizes the "_device" workspace: up to nq_max queries per call, k <= k_max, limit <= limit_max */
+int amdr_graph_reserve(amdr_graph_t* h, int32_t nq_max, int32_t k_max, int32_t limit_max);
+/* the walk alone (host pointers; seeds are NODE ids here): per query out_count [nq] and, in found order, out_node /
+ * out_depth / out_parent / out_rel / out_evidence (edge_has_evidence) i32 and out_conf (edge_conf_raw) f64 [nq, limit]
+ * (past out_count: -1 / 0).  LawGraphStore.walk (graph_store.py:89-169); the hook the walk tests use. */
+int amdr_graph_walk(amdr_graph_t* h, const int64_t* seeds_host, const int32_t* seed_count_host, int32_t ld,
+                    int32_t seed_n, int32_t nq, const amdr_graph_params_t* params, int32_t* out_count,
+                    int32_t* out_node, int32_t* out_depth, int32_t* out_parent, int32_t* out_rel, int32_t* out_evidence,
+                    double* out_conf);
+/* walk + re-scoring + top-k from host query vectors Q [nq, d] and seed CHUNK rows [nq, ld] (GraphRetriever.search,
+ * graph_retriever.py:82-219) */
+int amdr_graph_search(amdr_graph_t* h, amdr_dense_t* dense, const float* Q_host, const int64_t* seeds_host,
+                      const int32_t* seed_count_host, int32_t ld, int32_t seed_n, int32_t nq, int32_t k,
+                      const amdr_graph_params_t* params, int32_t* out_count, int64_t* out_rows, double* out_final,
+                      float* out_semantic, int32_t* out_depth, int32_t* out_rel, double* out_conf);
+/* the same on device pointers, enqueued on `stream` (capturable after amdr_graph_reserve): for g < ng the query row
+ * q = qsel[g] (qsel nullable: q = g) of Q [*, d], seeds [*, ld] (e.g. BatchResult ids, the fused list) and seed_count
+ * [*] (its count); outputs indexed by g.  Replaces the per-query loop of HybridRetriever.search_batch over the
+ * graph-mode queries (hybrid_retriever.py:312-322 once per query: walk, store._embed(question), score, sort). */
+int amdr_graph_search_device(amdr_graph_t* h, amdr_dense_t* dense, const float* Q_dev, const int32_t* qsel_dev,
+                             const int64_t* seeds_dev, const int32_t* seed_count_dev, int32_t ld, int32_t seed_n,
+                             int32_t ng, int32_t k, const amdr_graph_params_t* params, int32_t* out_count,
+                             int64_t* out_rows, double* out_final, float* out_semantic, int32_t* out_depth,
+                             int32_t* out_rel, double* out_conf, void* stream);
+int amdr_graph_destroy(amdr_graph_t* h);
 
 /* ---- multi-GPU: merge per-shard top-k after the RCCL all-gather --------
  * No reference counterpart (the reference is single-process).

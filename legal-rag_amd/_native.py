@@ -41,6 +41,8 @@ EXPORTS = (
     "amdr_fuse", "amdr_fuse_device", "amdr_rerank_blend", "amdr_rerank_blend_device", "amdr_fuse_compact_device",
     "amdr_merge_topk_f32_device", "amdr_merge_topk_f64_device",
     "amdr_shard_row_words", "amdr_shard_pack_device", "amdr_shard_merge_device",
+    "amdr_graph_create", "amdr_graph_reserve", "amdr_graph_walk", "amdr_graph_search", "amdr_graph_search_device",
+    "amdr_graph_destroy",
 )
 
 
@@ -69,6 +71,9 @@ SIGNATURES = {
     "amdr_fuse_compact_device": "iiiPPPPPPPPiP",
     "amdr_merge_topk_f32_device": "PPiiiiPPiP", "amdr_merge_topk_f64_device": "PPiiiiPPiP",
     "amdr_shard_row_words": "PiP", "amdr_shard_pack_device": "PiilPiP", "amdr_shard_merge_device": "PiiPiiP",
+    "amdr_graph_create": "P" * 11 + "illiiP", "amdr_graph_reserve": "Piii", "amdr_graph_walk": "PPPiiiP" + "P" * 7,
+    "amdr_graph_search": "PPPPPiiiiP" + "P" * 7, "amdr_graph_search_device": "PPPPPPiiiiP" + "P" * 8,
+    "amdr_graph_destroy": "P",
 }
 _KIND = {"P": C.c_void_p, "i": C.c_int32, "l": C.c_int64, "d": C.c_double}
 
@@ -85,6 +90,18 @@ class FuseParams(C.Structure):
 class ShardChan(C.Structure):
     """amdr_shard_chan_t: one channel of the shard exchange (device pointers)."""
     _fields_ = [("scores", C.c_void_p), ("ids", C.c_void_p), ("k", C.c_int32), ("f64", C.c_int32)]
+
+
+class GraphParams(C.Structure):
+    """amdr_graph_params_t: per-call parameters of the graph channel (table pointers: host for walk / search, device
+    for search_device)."""
+    _fields_ = [("limit", C.c_int32), ("default_depth", C.c_int32), ("lang", C.c_int32), ("pad0", C.c_int32),
+                ("min_conf", C.c_double), ("rel_max_depth", C.c_void_p), ("rel_allowed", C.c_void_p),
+                ("rel_weight", C.c_void_p), ("decay", C.c_void_p)]
+
+
+GRAPH_MAX_LIMIT = 4096
+GRAPH_MAX_SEEDS = 1024
 
 
 _lib: Optional[C.CDLL] = None
@@ -660,6 +677,102 @@ class MaxSimIndex:
         try:
             self.close()
         except Exception:
+            pass
+
+
+# ---------------------------------------------------------------------------
+class GraphIndex:
+    """The law graph in HBM for the graph channel (amdr_graph_*, csrc/graph.hip): CSR adjacency over interned article
+    ids plus the node <-> chunk-row maps; walk + re-scoring + top-k of a whole batch against a DenseIndex's matrix
+    (replaces LawGraphStore.walk + GraphRetriever.search per query, graph_store.py:89-169, graph_retriever.py:82-219)."""
+
+    def __init__(self, node_ptr, edge_dst, edge_rel, edge_conf_raw, edge_conf_eff, edge_has_evidence, node_present,
+                 node_row, row_node, row_norm, row_lang=None, *, n_rel: int, device: int = 0):
+        a = dict(node_ptr=_c(node_ptr, np.int64), edge_dst=_c(edge_dst, np.int32), edge_rel=_c(edge_rel, np.int32),
+                 conf_raw=_c(edge_conf_raw, np.float64), conf_eff=_c(edge_conf_eff, np.float64),
+                 evid=_c(edge_has_evidence, np.int32), present=_c(node_present, np.int32), node_row=_c(node_row, np.int64),
+                 row_node=_c(row_node, np.int32), row_norm=_c(row_norm, np.float32))
+        lang = None if row_lang is None else _c(row_lang, np.int32)
+        self.n_nodes = int(a["present"].shape[0])
+        self.n_edges = int(a["edge_dst"].shape[0])
+        self.n_rows = int(a["row_node"].shape[0])
+        self.n_rel = int(n_rel)
+        self.device = int(device)
+        if a["node_ptr"].shape[0] != self.n_nodes + 1 or a["node_row"].shape[0] != self.n_nodes:
+            raise ValueError("GraphIndex: node tables disagree in length")
+        self._h = C.c_void_p()
+        _check(load().amdr_graph_create(*(x.ctypes.data for x in a.values()), None if lang is None else lang.ctypes.data,
+                                        self.n_nodes, self.n_edges, self.n_rows, self.n_rel, self.device,
+                                        C.byref(self._h)), "amdr_graph_create")
+
+    def reserve(self, nq_max: int, k_max: int, limit_max: int) -> None:
+        _check(load().amdr_graph_reserve(self._h, int(nq_max), int(k_max), int(limit_max)), "amdr_graph_reserve")
+
+    @staticmethod
+    def host_params(limit: int, default_depth: int, min_conf: float, rel_max_depth, rel_allowed, rel_weight, decay,
+                    lang: int = -1):
+        """(GraphParams over host arrays, the arrays: keep them alive for the call)."""
+        keep = (_c(rel_max_depth, np.int32), _c(rel_allowed, np.int32), _c(rel_weight, np.float64), _c(decay, np.float64))
+        if keep[3].shape[0] < int(limit) + 1:
+            raise ValueError("decay needs limit + 1 entries")
+        p = GraphParams(int(limit), int(default_depth), int(lang), 0, float(min_conf), *(x.ctypes.data or None for x in keep))
+        return p, keep
+
+    def walk(self, seeds: Sequence[Sequence[int]], params: GraphParams):
+        """Per query, the walk from NODE ids: list of (node, depth, parent, relation, has_evidence, conf_raw) tuples."""
+        nq = len(seeds)
+        ld = max([len(s) for s in seeds] + [1])
+        S = np.full((max(nq, 1), ld), -1, dtype=np.int64)
+        for i, s in enumerate(seeds):
+            S[i, :len(s)] = s
+        cnt = np.array([len(s) for s in seeds] + [0] * (nq == 0), dtype=np.int32)
+        L = int(params.limit)
+        outs = [np.empty((max(nq, 1), L), dtype=t) for t in (np.int32,) * 5 + (np.float64,)]
+        oc = np.zeros(max(nq, 1), dtype=np.int32)
+        _check(load().amdr_graph_walk(self._h, S.ctypes.data, cnt.ctypes.data, ld, ld, nq, C.byref(params), oc.ctypes.data,
+                                      *(o.ctypes.data for o in outs)), "amdr_graph_walk")
+        node, depth, parent, rel, evid, conf = outs
+        return [[(int(node[q, i]), int(depth[q, i]), int(parent[q, i]), int(rel[q, i]), bool(evid[q, i]),
+                  float(conf[q, i])) for i in range(int(oc[q]))] for q in range(nq)]
+
+    def search(self, dense: "DenseIndex", Q: np.ndarray, seeds: np.ndarray, seed_count: np.ndarray, seed_n: int, k: int,
+               params: GraphParams):
+        """Host-pointer search: Q f32 [nq, d], seeds i64 chunk rows [nq, ld], seed_count i32 [nq] -> dict of
+        count [nq] and rows / final / semantic / depth / relation / edge_conf [nq, k]."""
+        Q = _c(Q, np.float32).reshape(-1, dense.d)
+        nq = Q.shape[0]
+        seeds = _c(seeds, np.int64).reshape(nq, -1)
+        seed_count = _c(seed_count, np.int32).reshape(nq)
+        out = self._outputs(nq, k)
+        _check(load().amdr_graph_search(self._h, dense._h, Q.ctypes.data, seeds.ctypes.data, seed_count.ctypes.data,
+                                        seeds.shape[1], int(seed_n), nq, int(k), C.byref(params),
+                                        *(out[n].ctypes.data for n in self.OUTS)), "amdr_graph_search")
+        return out
+
+    OUTS = ("count", "rows", "final", "semantic", "depth", "relation", "edge_conf")
+    _OUT_T = (np.int32, np.int64, np.float64, np.float32, np.int32, np.int32, np.float64)
+
+    @classmethod
+    def _outputs(cls, nq: int, k: int):
+        return {n: np.empty((nq,) if n == "count" else (nq, k), dtype=t) for n, t in zip(cls.OUTS, cls._OUT_T)}
+
+    def search_device(self, dense: "DenseIndex", q_ptr: int, qsel_ptr: int, seeds_ptr: int, seed_count_ptr: int, ld: int,
+                      seed_n: int, ng: int, k: int, params: GraphParams, outs: Sequence[int], stream: int = 0) -> None:
+        """Device pointers; outs = the seven output pointers in OUTS order.  Enqueue only."""
+        _check(load().amdr_graph_search_device(self._h, dense._h, _vp(q_ptr), _vp(qsel_ptr), _vp(seeds_ptr),
+                                               _vp(seed_count_ptr), int(ld), int(seed_n), int(ng), int(k),
+                                               C.byref(params), *(_vp(o) for o in outs), _vp(stream)),
+               "amdr_graph_search_device")
+
+    def close(self) -> None:
+        if getattr(self, "_h", None) and self._h.value:
+            load().amdr_graph_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
             pass
 
 

@@ -83,9 +83,13 @@ class RetrievalConfig:
     query_tokenizer: str = "host"        # BM25 query side of search_batch / search_batch_arrays: "host" (native
                                          # tokeniser on CPU threads) | "device" (tokenised on the GPU, csrc/tokenize.hip,
                                          # for batches whose text the device rule decides; any other batch: host)
+    graph_channel: str = "host"          # graph stage of search_batch for GRAPH_AUGMENTED decisions: "host" (walk and
+                                         # re-scoring per query, graph_retriever.py) | "device" (one csrc/graph.hip
+                                         # call for all graph-mode queries of the batch)
 
     def __post_init__(self) -> None:
         query_tokenizer_mode(self)
+        graph_channel_mode(self)
 
 
 QUERY_TOKENIZERS = ("host", "device")
@@ -99,6 +103,20 @@ def query_tokenizer_mode(cfg) -> str:
     m = "host" if m is None else m
     if m not in QUERY_TOKENIZERS:
         raise ValueError(f"retrieval.query_tokenizer must be one of {QUERY_TOKENIZERS}, got {m!r}")
+    return m
+
+
+GRAPH_CHANNELS = ("host", "device")
+
+
+def graph_channel_mode(cfg) -> str:
+    """`graph_channel` of a RetrievalConfig (or of `cfg.retrieval`): "host" by default; ValueError for any other value
+    than "host" / "device"."""
+    r = getattr(cfg, "retrieval", cfg)
+    m = getattr(r, "graph_channel", None)
+    m = "host" if m is None else m
+    if m not in GRAPH_CHANNELS:
+        raise ValueError(f"retrieval.graph_channel must be one of {GRAPH_CHANNELS}, got {m!r}")
     return m
 
 

@@ -199,6 +199,8 @@ int bm25_small_raw(amdr_bm25_t* h, int nq, int k, Bm25Raw* out);  // (bm25.hip)
 std::mutex& dense_mutex(amdr_dense_t* h);
 std::mutex& bm25_mutex(amdr_bm25_t* h);
 int dense_device_of(const amdr_dense_t* h);
+// the resident chunk matrix of a dense handle (graph.hip re-scores walked articles against it)
+void dense_matrix(const amdr_dense_t* h, const float** X, long* n, int* d);
 
 // ---- long-batch dense path: dense_panel.hip (panel of chunk rows shared by a block through LDS) ----
 struct DensePanelPlan {

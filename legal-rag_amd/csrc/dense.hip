@@ -1056,6 +1056,11 @@ int dense_small_raw(amdr_dense_t* h, int nq, DenseRaw* out) {
 }
 std::mutex& dense_mutex(amdr_dense_t* h) { return h->mu; }
 int dense_device_of(const amdr_dense_t* h) { return h->device; }
+void dense_matrix(const amdr_dense_t* h, const float** X, long* n, int* d) {
+  *X = h->X;
+  *n = (long)h->n;
+  *d = h->d;
+}
 }  // namespace amdr
 
 extern "C" {

@@ -16,6 +16,7 @@ from typing import Optional
 
 import os
 
+import numpy as np
 import torch
 
 from .. import _native
@@ -36,6 +37,7 @@ class BatchResult:
     rerank: Optional[torch.Tensor] = None  # f64 [nq, max_out, 2] (raw, norm) after rerank_blend
     packed: Optional[torch.Tensor] = None  # u8: ids | vals | mask | count in ONE allocation (one D2H for the host API)
     needs_segmenter: Optional[torch.Tensor] = None  # i32 [nq] of a text-in step (q_text): 1 = Han query, no BM25 terms
+    graph: Optional[dict] = None  # graph_topk outputs of a captured step that ends with the graph stage
 
     def to_host(self):
         """(ids, vals, mask, count) as numpy arrays through ONE device-to-host copy (the first `.cpu()` of a result
@@ -76,6 +78,11 @@ class HybridEngine:
         self.shard_offset, self.shard_group = shard_offset, shard_group
         # the BM25 query side on the device (text-in steps, q_text=): a copy of the BM25 vocabulary's host tokeniser
         self.tokenizer = tokenizer
+        # the graph channel (graph_topk): a GraphIndex over the dense matrix's rows and its per-call parameters
+        self.graph: Optional[_native.GraphIndex] = None
+        self.graph_params: Optional[_native.GraphParams] = None
+        self.graph_limit = 0
+        self._graph_key = None
 
     def _buf(self, name, shape, dtype):
         key = (name, tuple(shape), dtype)
@@ -199,6 +206,48 @@ class HybridEngine:
             self.bm25.reserve(nq, k, max(total_terms, 1))
         if self.maxsim is not None:
             self.maxsim.reserve(nq, k)
+        if self.graph is not None and self.graph_limit > 0:
+            self.graph.reserve(nq, k, self.graph_limit)
+
+    # -- graph channel ------------------------------------------------------------
+    def set_graph(self, graph: _native.GraphIndex, params: dict, lang: int = -1) -> None:
+        """The graph channel of this engine: the GraphIndex and one call's parameters (graph_retriever.graph_call_params);
+        the parameter tables go up to the device once per distinct parameter set."""
+        import numpy as np
+        key = (id(graph), int(params["limit"]), int(params["default_depth"]), float(params["min_conf"]), int(lang),
+               params["rel_max_depth"].tobytes(), params["rel_allowed"].tobytes(), params["rel_weight"].tobytes(),
+               params["decay"].tobytes())
+        if self.graph is graph and self._graph_key == key:
+            return
+        tabs = tuple(torch.from_numpy(np.ascontiguousarray(params[n])).to(self.tdev)
+                     for n in ("rel_max_depth", "rel_allowed", "rel_weight", "decay"))
+        torch.cuda.current_stream(self.tdev).synchronize()
+        self.graph, self._graph_tabs, self._graph_key = graph, tabs, key
+        self.graph_limit = int(params["limit"])
+        self.graph_params = _native.GraphParams(int(params["limit"]), int(params["default_depth"]), int(lang), 0,
+                                                float(params["min_conf"]), *(t.data_ptr() for t in tabs))
+
+    def graph_topk(self, seeds: torch.Tensor, seed_count: torch.Tensor, q_emb: torch.Tensor, k: int, seed_n: int,
+                   qsel: Optional[torch.Tensor] = None) -> dict:
+        """The graph stage on the current stream (amdr_graph_search_device): for g < ng the query q = qsel[g] (default
+        g) walks from the first min(seed_n, seed_count[q]) chunk rows of seeds[q] (the fused list: BatchResult ids /
+        count) and re-scores the walked articles against q_emb[q] (the non-query embedding of the question).
+        Returns the outputs (_native.GraphIndex.OUTS), indexed by g.  Capturable after reserve()."""
+        if self.graph is None or self.graph_params is None:
+            raise RuntimeError("graph_topk: this engine has no graph channel (set_graph)")
+        assert seeds.is_cuda and seeds.dtype == torch.int64 and seeds.is_contiguous() and seed_count.dtype == torch.int32
+        assert q_emb.is_cuda and q_emb.dtype == torch.float32 and q_emb.is_contiguous()
+        ld = int(seeds.shape[1])
+        ng = int(qsel.numel()) if qsel is not None else int(seeds.shape[0])
+        if qsel is not None:
+            assert qsel.is_cuda and qsel.dtype == torch.int32 and qsel.is_contiguous()
+        k = int(k)
+        outs = {n: self._buf("g_" + n, (ng,) if n == "count" else (ng, k), getattr(torch, np.dtype(t).name))
+                for n, t in zip(_native.GraphIndex.OUTS, _native.GraphIndex._OUT_T)}
+        self.graph.search_device(self.dense, q_emb.data_ptr(), qsel.data_ptr() if qsel is not None else 0,
+                                 seeds.data_ptr(), seed_count.data_ptr(), ld, min(int(seed_n), ld, _native.GRAPH_MAX_SEEDS),
+                                 ng, k, self.graph_params, [outs[n].data_ptr() for n in _native.GraphIndex.OUTS], _stream())
+        return outs
 
     # -- channels (device in, device out) -----------------------------------
     def dense_topk(self, q_emb: torch.Tensor, k: int):
@@ -382,7 +431,7 @@ class HybridEngine:
     # -- hipGraph form -----------------------------------------------------------
     def capture(self, params: _native.FuseParams, k: int, *, q_emb: Optional[torch.Tensor] = None,
                 q_terms: Optional[torch.Tensor] = None, q_ptr: Optional[torch.Tensor] = None,
-                q_tok: Optional[torch.Tensor] = None, q_text=None):
+                q_tok: Optional[torch.Tensor] = None, q_text=None, graph: Optional[dict] = None):
         """Record one search_batch over the given tensors into a hipGraph.
 
         Returns (graph, result): `graph.replay()` re-runs the whole step — every kernel of every
@@ -395,6 +444,8 @@ class HybridEngine:
         45 us against 33 us for the plain chain: the fork / join nodes cost more than the 5-us kernel they hide.)
         With q_text = (blob, offs) the graph starts from query BYTES: tokeniser + channels + fusion; a replay takes new
         text written into the same two tensors (same nq, at most blob.numel() bytes, offs[nq] <= that).
+        graph = dict(q_emb=, k=, seed_n=, qsel=None): the step ends with graph_topk over the fused list (set_graph
+        first); its outputs are result.graph.
         """
         if self.shard_offset is not None:
             raise RuntimeError("capture: a sharded step contains a collective; it is not recorded into a hipGraph")
@@ -404,12 +455,23 @@ class HybridEngine:
         else:
             nq = (q_emb.shape[0] if q_emb is not None else q_ptr.shape[0] - 1 if q_ptr is not None else q_tok.shape[0])
             self.reserve(int(nq), int(k), int(q_terms.numel()) if q_terms is not None else 0)
+        gstage = graph
+        if gstage is not None:
+            ng = int(gstage["qsel"].numel()) if gstage.get("qsel") is not None else int(nq)
+            self.graph.reserve(ng, int(gstage["k"]), self.graph_limit)
+
+        def step():
+            r = self.search_batch(params, k, q_emb=q_emb, q_terms=q_terms, q_ptr=q_ptr, q_tok=q_tok, q_text=q_text)
+            if gstage is not None:
+                r.graph = self.graph_topk(r.ids, r.count, gstage["q_emb"], gstage["k"], gstage["seed_n"],
+                                          qsel=gstage.get("qsel"))
+            return r
         side = torch.cuda.Stream(device=self.tdev)
         side.wait_stream(torch.cuda.current_stream(self.tdev))
         with torch.cuda.stream(side):  # eager warm-up sizes every lazily grown buffer outside the capture
-            self.search_batch(params, k, q_emb=q_emb, q_terms=q_terms, q_ptr=q_ptr, q_tok=q_tok, q_text=q_text)
+            step()
         side.synchronize()
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph):
-            res = self.search_batch(params, k, q_emb=q_emb, q_terms=q_terms, q_ptr=q_ptr, q_tok=q_tok, q_text=q_text)
+            res = step()
         return graph, res

@@ -20,13 +20,14 @@ against vectors produced by the reference's own code).
 from __future__ import annotations
 
 import copy
+import math
 from dataclasses import dataclass
-from typing import Any, Dict, List, Optional
+from typing import Any, Dict, List, Optional, Sequence
 
 import numpy as np
 
 from ..schemas import LawChunk, RetrievalHit
-from .graph_store import LawGraphStore
+from .graph_store import LawGraphStore, _clean
 from .vector_store import VectorStore
 
 _REL_WEIGHT = {"defined_by": 1.20, "defines_term": 1.10, "cite": 1.15, "cited": 1.15, "ref": 1.15, "amend": 1.10,
@@ -49,6 +50,114 @@ def _relation_weight(relations: List[str]) -> float:
 def _article_key(obj: Any) -> Optional[str]:
     aid = getattr(obj, "article_id", None) or getattr(obj, "id", None)
     return str(aid) if aid else None
+
+
+@dataclass
+class GraphTables:
+    """Host form of the device graph channel's tables (include/amdretrieval.h amdr_graph_create) over the interned
+    article ids `names`: every stored node, every edge destination and every stripped chunk key."""
+    names: List[str]
+    rel_names: List[str]
+    lang_names: List[str]
+    node_ptr: np.ndarray      # i64 [n + 1]
+    edge_dst: np.ndarray      # i32 [E]
+    edge_rel: np.ndarray      # i32 [E]
+    conf_raw: np.ndarray      # f64 [E]  float(conf or 1.0): the min_conf filter
+    conf_eff: np.ndarray      # f64 [E]  the conf the score takes (the stored node's _edge_conf without evidence)
+    evidence: np.ndarray      # i32 [E]
+    present: np.ndarray       # i32 [n]  a stored node
+    node_row: np.ndarray      # i64 [n]  chunk row of the article (last chunk wins), -1: none / empty text
+    row_node: np.ndarray      # i32 [rows] node of the chunk's stripped key, -1: none
+    row_lang: np.ndarray      # i32 [rows] index into lang_names
+
+
+def build_graph_tables(graph: LawGraphStore, chunks: Sequence[LawChunk]) -> GraphTables:
+    """The tables of amdr_graph_create from LawGraphStore.nodes / .adj and the store's chunks, by the expressions the
+    host walk and GraphRetriever.search use (graph_store.py walk, _bind_rows, search's hydration)."""
+    graph.load()
+    index: Dict[str, int] = {}
+    names: List[str] = []
+
+    def intern(x: str) -> int:
+        i = index.get(x)
+        if i is None:
+            i = index[x] = len(names)
+            names.append(x)
+        return i
+
+    for aid in graph.nodes:
+        intern(aid)
+    for aid in list(graph.nodes):
+        for dst, _rel, _conf, _ev in graph.adj.get(aid, []):
+            intern(dst)
+    row_node = np.full(len(chunks), -1, dtype=np.int32)
+    row_of: Dict[str, int] = {}
+    langs: Dict[str, int] = {}
+    row_lang = np.zeros(len(chunks), dtype=np.int32)
+    for row, c in enumerate(chunks):
+        key = _article_key(c)
+        if key:
+            row_of[key] = row  # the last chunk of an id wins (_bind_rows)
+            if _clean(key):
+                row_node[row] = intern(_clean(key))  # seeds are stripped by walk()
+        row_lang[row] = langs.setdefault((getattr(c, "lang", None) or "zh").strip().lower(), len(langs))
+    n = len(names)
+    rels: Dict[str, int] = {}
+    node_ptr = np.zeros(n + 1, dtype=np.int64)
+    dst_l, rel_l, raw_l, eff_l, ev_l = [], [], [], [], []
+    for i, aid in enumerate(names):
+        for dst, rel, conf, ev in graph.adj.get(aid, []) if aid in graph.nodes else []:
+            dst_l.append(index[dst])
+            rel_l.append(rels.setdefault(rel, len(rels)))
+            raw_l.append(float(conf))
+            if ev:
+                eff_l.append(float(conf))
+            else:
+                stored = graph.nodes.get(dst)
+                eff_l.append(float(((getattr(stored, "meta", {}) or {}).get("_edge_conf", 1.0)) or 1.0) if stored else 1.0)
+            ev_l.append(1 if ev else 0)
+        node_ptr[i + 1] = len(dst_l)
+    node_row = np.full(n, -1, dtype=np.int64)
+    for i, aid in enumerate(names):
+        row = row_of.get(aid)
+        if row is not None and (getattr(chunks[row], "text", "") or "").strip():
+            node_row[i] = row
+    return GraphTables(names=names, rel_names=list(rels), lang_names=list(langs), node_ptr=node_ptr,
+                       edge_dst=np.asarray(dst_l, dtype=np.int32), edge_rel=np.asarray(rel_l, dtype=np.int32),
+                       conf_raw=np.asarray(raw_l, dtype=np.float64), conf_eff=np.asarray(eff_l, dtype=np.float64),
+                       evidence=np.asarray(ev_l, dtype=np.int32),
+                       present=np.asarray([1 if a in graph.nodes else 0 for a in names], dtype=np.int32),
+                       node_row=node_row, row_node=row_node, row_lang=row_lang)
+
+
+def _depth_bound(v: Any) -> int:
+    """dist >= v for an integer dist, as an integer bound."""
+    return int(max(-(2 ** 31), min(2 ** 31 - 1, math.ceil(float(v)))))
+
+
+def graph_call_params(rcfg: Any, rel_names: Sequence[str], top_k: int) -> Dict[str, Any]:
+    """Per-call parameters of the device channel from cfg.retrieval, resolved as GraphRetriever.search and
+    LawGraphStore.walk resolve them: limit, default_depth, min_conf, gamma and the per-relation max_depth / allowed /
+    weight tables, decay[depth] for depth 0 .. limit."""
+    k = max(1, int(top_k))
+    depths = rcfg.graph_walk_depths if hasattr(rcfg, "graph_walk_depths") else {"default": 2}
+    limit = int(getattr(rcfg, "graph_limit", k * 8) if rcfg else k * 8)
+    rel_types = getattr(rcfg, "graph_rel_types", None) if rcfg else None
+    min_conf = float(getattr(rcfg, "graph_min_conf", 0.0) if rcfg else 0.0)
+    gamma = float(getattr(rcfg, "graph_depth_gamma", 0.7) if rcfg else 0.7)
+    if depths is None:
+        depths = getattr(rcfg, "graph_walk_depths", None) or {"default": 2}
+    default_depth = depths.get("default", 2)
+    limit = max(1, int(limit))
+    allowed = {str(r) for r in rel_types} if rel_types else None
+    return {
+        "limit": limit, "default_depth": _depth_bound(default_depth), "min_conf": float(min_conf or 0.0), "gamma": gamma,
+        "rel_max_depth": np.asarray([_depth_bound(depths.get(r, default_depth) if r else default_depth)
+                                     for r in rel_names] or [0], dtype=np.int32),
+        "rel_allowed": np.asarray([1 if allowed is None or r in allowed else 0 for r in rel_names] or [0], dtype=np.int32),
+        "rel_weight": np.asarray([_relation_weight([r]) for r in rel_names] or [1.0], dtype=np.float64),
+        "decay": np.asarray([_depth_decay(d, gamma=gamma) for d in range(limit + 1)], dtype=np.float64),
+    }
 
 
 @dataclass
@@ -94,6 +203,73 @@ class GraphRetriever:
                 norms[lo:min(lo + 65536, r1)] = np.linalg.norm(index.reconstruct_n(lo, min(65536, r1 - lo)), axis=1)
             self._norms = norms
         return self._norms
+
+    # ------------------------------------------------------------- device channel
+    def device_graph(self):
+        """(GraphIndex, GraphTables) of the graph channel on the device, built once per loaded index (rebuilt when the
+        store reloads).  ValueError for a row-sharded index (no device walk there) or a store without a device matrix."""
+        from .. import _native
+        norms = self._row_norms()  # rebinds the rows when the store reloaded
+        index = getattr(self.store, "index", None)
+        if norms is None:
+            raise ValueError("graph_channel='device' needs the store's chunk matrix on the device (a native index)")
+        if hasattr(index, "spec"):
+            raise ValueError("graph_channel='device' does not run on a row-sharded index (cfg.retrieval.shard); "
+                             "use graph_channel='host'")
+        cached = self.__dict__.get("_dev_graph")
+        if cached is not None and cached[0] is index:
+            return cached[1], cached[2]
+        t = build_graph_tables(self.graph, list(getattr(self.store, "chunks", []) or []))
+        if len(t.row_node) != int(index.ntotal):
+            raise ValueError(f"graph_channel='device': {len(t.row_node)} chunks but {int(index.ntotal)} matrix rows")
+        g = _native.GraphIndex(t.node_ptr, t.edge_dst, t.edge_rel, t.conf_raw, t.conf_eff, t.evidence, t.present,
+                               t.node_row, t.row_node, norms, t.row_lang, n_rel=len(t.rel_names),
+                               device=int(getattr(index, "_device", getattr(self.cfg.retrieval, "device", 0)) or 0))
+        self.__dict__["_dev_graph"] = (index, g, t)
+        return g, t
+
+    def device_params(self, top_k: int, lang: Optional[str] = None):
+        """(graph_call_params dict, lang id) for a call: the limits of the device channel are checked here."""
+        from .. import _native
+        _g, t = self.device_graph()
+        p = graph_call_params(getattr(self.cfg, "retrieval", None), t.rel_names, top_k)
+        if p["limit"] > _native.GRAPH_MAX_LIMIT:
+            raise ValueError(f"graph_channel='device': graph_limit {p['limit']} exceeds the device limit of "
+                             f"{_native.GRAPH_MAX_LIMIT}")
+        lang_id = -1 if not lang else (t.lang_names.index(lang) if lang in t.lang_names else len(t.lang_names))
+        return p, lang_id
+
+    def hits_from_device(self, out: Dict[str, np.ndarray], qi: int, params: Dict[str, Any]) -> List[RetrievalHit]:
+        """RetrievalHits of query qi of a device call, with GraphRetriever.search's fields and score_breakdown keys."""
+        _g, t = self.device_graph()
+        chunks = self.store.chunks
+        hits: List[RetrievalHit] = []
+        for r in range(int(out["count"][qi])):
+            cc = copy.copy(chunks[int(out["rows"][qi, r])])
+            cc.source = "graph"
+            depth, rel = int(out["depth"][qi, r]), int(out["relation"][qi, r])
+            s, final, conf = float(out["semantic"][qi, r]), float(out["final"][qi, r]), float(out["edge_conf"][qi, r])
+            hits.append(RetrievalHit(chunk=cc, score=final, rank=r + 1, source="graph", score_breakdown={
+                "channel": "graph", "semantic": s, "depth_decay": float(params["decay"][depth]),
+                "relation_weight": float(params["rel_weight"][rel]), "edge_conf": conf, "final": final,
+                "graph_depth": depth, "relations": [t.rel_names[rel]]}))
+        return hits
+
+    def search_device(self, q_vecs: np.ndarray, seed_rows: np.ndarray, seed_count: np.ndarray, *, top_k: int = 10,
+                      lang: Optional[str] = None) -> List[List[RetrievalHit]]:
+        """GraphRetriever.search for a batch in one device call (host pointers): q_vecs [nq, d] (the NON-query
+        embeddings, as store._embed(question)), seed_rows [nq, ld] chunk rows of the seeds, seed_count [nq]."""
+        from .. import _native
+        g, _t = self.device_graph()
+        p, lang_id = self.device_params(top_k, lang)
+        seed_rows = np.asarray(seed_rows, dtype=np.int64).reshape(len(seed_count), -1)
+        hp, keep = _native.GraphIndex.host_params(p["limit"], p["default_depth"], p["min_conf"], p["rel_max_depth"],
+                                                  p["rel_allowed"], p["rel_weight"], p["decay"], lang_id)
+        k = max(1, int(top_k))
+        out = g.search(self.store.index.native, q_vecs, seed_rows, seed_count, min(seed_rows.shape[1], _native.GRAPH_MAX_SEEDS),
+                       k, hp)
+        del keep
+        return [self.hits_from_device(out, qi, p) for qi in range(len(seed_count))]
 
     def _semantic(self, question: str, chunks: List[LawChunk], keys: List[str]) -> List[float]:
         qvec = np.asarray(self.store._embed(question), dtype=np.float32).reshape(-1)

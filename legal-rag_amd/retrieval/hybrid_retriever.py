@@ -32,7 +32,7 @@ from typing import Any, Dict, List, Optional, Sequence, Set
 import numpy as np
 
 from .. import _native
-from ..config import query_tokenizer_mode
+from ..config import graph_channel_mode, query_tokenizer_mode
 from ..schemas import RetrievalHit
 from .bm25_retriever import BM25Retriever
 from .colbert_retriever import ColBERTRetriever
@@ -557,12 +557,14 @@ class HybridRetriever:
                             device=dev, shard_offset=offset, shard_group=shard.group if shard is not None else None)
 
     def _batch_native(self, questions: Sequence[str], eff: int, native, min_final: float, arrays: bool = False,
-                      q_emb=None, compact_w: int = 0, device_tok: bool = False):
+                      q_emb=None, compact_w: int = 0, device_tok: bool = False, graph_stage: Optional[Dict[str, Any]] = None):
         """Embed / tokenise on the host, then dense + BM25 (+ MaxSim) top-k -> fuse -> min_final
         count for the whole batch on torch's current stream, one synchronise, results built once.
         device_tok (cfg.retrieval.query_tokenizer = "device"): a batch the device rule decides
         (BM25Retriever.device_text_batch) goes up as UTF-8 text and is tokenised on the GPU in the same stream
         (HybridEngine.tokenize_device); any other batch takes the host tokeniser as before.
+        graph_stage: {"fn": callable(engine, BatchResult)} run on the device result inside the batch lock (the graph
+        channel of graph_channel = "device"); what it returns goes to graph_stage["out"].
         Returns ([fused hits with score >= min_final per question], (t_after_dense_prep, t_after_bm25_prep,
         t_after_colbert_prep))."""
         import torch
@@ -577,6 +579,8 @@ class HybridRetriever:
             stamps = (time.time(),) * 3
             if arrays:
                 raise ValueError("search_batch_arrays: empty questions are not supported in the columnar form")
+            if graph_stage is not None:
+                raise ValueError("graph_channel='device': empty questions are not supported with the ColBERT channel on")
             for idxs, nat in ((blank, (store, bm, None)), (rest, native)):
                 if idxs:
                     part, stamps = self._batch_native([questions[i] for i in idxs], eff, nat, min_final,
@@ -655,6 +659,8 @@ class HybridRetriever:
                 if eng is None:
                     eng = engines[False] = self._make_engine(store, bm, None, dev)
                 res = eng.search_batch(self._params(kn, min_final), eff, q_emb=q_emb, q_terms=q_terms_d, q_ptr=q_ptr_d)
+            if graph_stage is not None:
+                graph_stage["out"] = graph_stage["fn"](eng, res)
             if arrays and compact_w:
                 # the lean columnar form: rows / scores / masks of the first compact_w hits, compacted on the device
                 rows, scores, cmask, cnt = eng.compact_to_host(res, compact_w)
@@ -691,43 +697,115 @@ class HybridRetriever:
         if native is None:
             raise RuntimeError("search_batch requires this package's own dense / BM25 (/ ColBERT) retrievers built "
                                "over the same chunk list")
+        graph_on = getattr(rcfg, "enable_graph", False) and decisions is not None
+        seed_n = int(getattr(rcfg, "graph_seed_k", max(10, top_k * 3)))
+        sel = [i for i, dec in enumerate(decisions) if _is_graph_mode(getattr(dec, "mode", None))] if graph_on else []
+        stage = None
+        if sel and self.graph is not None and graph_channel_mode(self.cfg) == "device":
+            stage = self._graph_device_stage(questions, sel, eff, seed_n, native)
         outs, _ = self._batch_native(questions, eff, native, float(getattr(rcfg, "min_final_score", 0.0)), q_emb=q_emb,
-                                     device_tok=query_tokenizer_mode(self.cfg) == "device")
-        if getattr(rcfg, "enable_graph", False) and decisions is not None:
-            seed_n = int(getattr(rcfg, "graph_seed_k", max(10, top_k * 3)))
-            for i, dec in enumerate(decisions):
-                if _is_graph_mode(getattr(dec, "mode", None)):
-                    seeds = outs[i][:seed_n]
-                    outs[i] = seeds + self.search_graph(questions[i], eff, decision=dec, seeds=seeds)
+                                     device_tok=query_tokenizer_mode(self.cfg) == "device", graph_stage=stage)
+        if stage is not None:
+            # one device call served every graph-mode query; the same relabelling as search_graph
+            gout, gp = stage["out"], stage["params"]
+            for j, i in enumerate(sel):
+                hits = self.graph.hits_from_device(gout, j, gp)
+                for h in hits:
+                    h.source = "retriever"
+                    h.score_breakdown["channel"] = ["graph"]
+                outs[i] = outs[i][:seed_n] + hits
+        else:
+            for i in sel:
+                seeds = outs[i][:seed_n]
+                outs[i] = seeds + self.search_graph(questions[i], eff, decision=decisions[i], seeds=seeds)
         if getattr(rcfg, "enable_rerank", False):
             outs = self._rerank_stage(questions, outs, llm, top_k)
         return [_dedup_keep_best(hits)[:top_k] for hits in outs]
 
-    def search_batch_arrays(self, questions: Sequence[str], top_k: int = 10, q_emb=None, values: bool = True) -> Dict[str, Any]:
+    def _graph_device_stage(self, questions: Sequence[str], sel: Sequence[int], k: int, seed_n: int, native,
+                            lang: Optional[str] = None) -> Dict[str, Any]:
+        """The graph channel of a batch on the device (graph_channel = "device"): the graph-mode questions embedded once
+        (non-query form, as GraphRetriever's store._embed(question)), then ONE amdr_graph_search_device call over the
+        fused lists of the batch, seeds = the first graph_seed_k fused hits.  Row-sharded indexes and parameters outside
+        the kernel's limits raise ValueError (no silent host path)."""
+        import torch
+        store = native[0]
+        if getattr(store.index, "spec", None) is not None:
+            raise ValueError("graph_channel='device' does not run on a row-sharded index (cfg.retrieval.shard); "
+                             "use graph_channel='host'")
+        g, _t = self.graph.device_graph()
+        params, lang_id = self.graph.device_params(k, lang)
+        if k > _native.MAX_K:
+            raise ValueError(f"graph_channel='device': depth {k} exceeds {_native.MAX_K}")
+        sel = list(sel)
+        emb = store.embed_device([questions[i] for i in sel], is_query=False)
+
+        def fn(eng, res):
+            eng.set_graph(g, params, lang_id)
+            nq = int(res.ids.shape[0])
+            q_full = eng._buf("gq", (nq, int(emb.shape[1])), torch.float32)
+            qsel = torch.tensor(sel, dtype=torch.int32).to(eng.tdev, non_blocking=True)
+            q_full.index_copy_(0, qsel.long(), emb.to(eng.tdev, dtype=torch.float32))
+            eng.graph.reserve(len(sel), k, eng.graph_limit)
+            outs = eng.graph_topk(res.ids, res.count, q_full, k, seed_n, qsel=qsel)
+            return {n: v.cpu().numpy() for n, v in outs.items()}
+        return {"fn": fn, "params": params}
+
+    def search_batch_arrays(self, questions: Sequence[str], top_k: int = 10, q_emb=None, values: bool = True,
+                            decisions: Optional[Sequence[Any]] = None) -> Dict[str, Any]:
         """`search_batch` without building RetrievalHit objects (pydantic construction, not the GPU, bounds
         `search_batch` at a few thousand queries/s): columnar results for bulk callers (evaluation sweeps,
         offline scoring).  rows[q, j] indexes `self.dense.store.chunks`; entries j >= count[q] are -1 / 0.
         `q_emb` ([n, d] numpy array or device tensor): query embeddings the caller's encoder already produced
         (a deployment batches its BERT forward itself); default: this store's encoder.
-        The rows of one index are distinct chunks, so the dedup step of search() has nothing to merge."""
+        The rows of one index are distinct chunks, so the dedup step of search() has nothing to merge.
+        `decisions` (one per question): the graph channel runs on the device for the GRAPH_AUGMENTED ones (when
+        cfg.retrieval.enable_graph and a graph is loaded) and the result gains graph_rows / graph_scores (final) /
+        graph_semantic / graph_depth / graph_relation (index into graph_relation_names) / graph_edge_conf [n, top_k] and
+        graph_count [n] (0 for the other queries)."""
         rcfg = self.cfg.retrieval
         top_k = max(1, int(top_k))
         eff = self._eff_depth(top_k, "search_batch_arrays")
         native = self._native_channels(eff)
         if native is None:
             raise RuntimeError("search_batch_arrays requires this package's own retrievers built over the same chunk list")
+        if decisions is not None and len(decisions) != len(questions):
+            raise ValueError("search_batch_arrays: decisions must have one entry per question")
+        graph_on = decisions is not None and getattr(rcfg, "enable_graph", False) and self.graph is not None
+        sel = [i for i, dec in enumerate(decisions) if _is_graph_mode(getattr(dec, "mode", None))] if graph_on else []
+        stage = (self._graph_device_stage(list(questions), sel, top_k,
+                                          int(getattr(rcfg, "graph_seed_k", max(10, top_k * 3))), native) if sel else None)
+        out = self._search_batch_arrays(questions, top_k, eff, native, q_emb, values, stage)
+        if graph_on:
+            n, g = len(questions), (stage or {}).get("out")
+            for col, name, dt, fill in (("rows", "rows", np.int64, -1), ("scores", "final", np.float64, 0.0),
+                                        ("semantic", "semantic", np.float32, 0.0), ("depth", "depth", np.int32, 0),
+                                        ("relation", "relation", np.int32, -1), ("edge_conf", "edge_conf", np.float64, 0.0)):
+                a = np.full((n, top_k), fill, dtype=dt)
+                if g is not None:
+                    a[sel] = g[name]
+                out["graph_" + col] = a
+            out["graph_count"] = np.zeros(n, dtype=np.int32)
+            if g is not None:
+                out["graph_count"][sel] = g["count"]
+            out["graph_relation_names"] = list(self.graph.device_graph()[1].rel_names)
+        return out
+
+    def _search_batch_arrays(self, questions, top_k: int, eff: int, native, q_emb, values: bool, stage):
+        rcfg = self.cfg.retrieval
         if not values:
             # `values=False`: rows / scores / count / channel_mask only, cut to top_k on the device — 20 bytes per hit over
             # PCIe instead of the full fused record (9 doubles for every candidate of every channel: 1.6 KB per query)
             (rows, scores, cmask, cnt, exact), _ = self._batch_native(
                 list(questions), eff, native, float(getattr(rcfg, "min_final_score", 0.0)), arrays=True, q_emb=q_emb,
-                compact_w=top_k, device_tok=query_tokenizer_mode(self.cfg) == "device")
+                compact_w=top_k, device_tok=query_tokenizer_mode(self.cfg) == "device", graph_stage=stage)
             return {"rows": rows, "scores": scores, "count": cnt, "channel_mask": cmask, "zh_exact": exact,
                     "chunks": native[0].chunks}
         (ids, vals, mask, cnt, exact), _ = self._batch_native(list(questions), eff, native,
                                                                 float(getattr(rcfg, "min_final_score", 0.0)), arrays=True,
                                                                 q_emb=q_emb,
-                                                                device_tok=query_tokenizer_mode(self.cfg) == "device")
+                                                                device_tok=query_tokenizer_mode(self.cfg) == "device",
+                                                                graph_stage=stage)
         w = min(top_k, ids.shape[1])
         keep = np.arange(w)[None, :] < np.minimum(cnt, w)[:, None]
         return {"rows": np.where(keep, ids[:, :w], -1), "scores": np.where(keep, vals[:, :w, _native.FV["score"]], 0.0),
