@@ -91,36 +91,18 @@ void dense_mfma_plan(long n, int d, int nq, int k, DenseMfmaPlan* p);
 // (dense_hi.hip) is enqueued unconditionally and decides on the device whether it runs
 int dense_mfma_launch_scores(const DenseMfmaPlan& p, const float* X, long n, int d, const float* Q, int nq, float* S,
                              hipStream_t st, int mode = 0, const int* tile_list = nullptr,
-                             const int* tile_count = nullptr, long n_real = 0, const int* gate = nullptr,
-                             int list_stride = 0);
+                             const int* tile_count = nullptr, long n_real = 0, const int* gate = nullptr);
 // two-level top-k helpers: sorted unique list of the candidate tiles (a bitmap in LDS up to kUniqueBitmapTilesMax tiles,
 // any number of candidates; beyond, a one-wave sort of <= 8 192 candidates); column -> row id of the final hits
 constexpr int kUniqueBitmapTilesMax = 1 << 20;
-int dense_tiles_unique_launch(const int64_t* tile_ids, int n_in, long n_tiles, int* list, int* count, hipStream_t st,
-                              const int* gate = nullptr);
-int dense_tiles_sort_per_query_launch(const int64_t* tile_ids, int m, int kc, int* list, int* count, hipStream_t st);
-int dense_tiles_remap_launch(int64_t* ids, int total, const int* list, const int* count, long n_real, hipStream_t st,
-                             const int* gate = nullptr, int k = 1, int list_stride = 0);
+int dense_tiles_unique_launch(const int64_t* tile_ids, int n_in, long n_tiles, int* list, int* count, hipStream_t st);
+int dense_tiles_remap_launch(int64_t* ids, int total, const int* list, const int* count, long n_real, hipStream_t st);
 int dense_mfma_launch_topk(const DenseMfmaPlan& p, const float* S, long n, int nq, int k, void* part,
-                           float* fin_scores, int64_t* fin_ids, hipStream_t st, const int* gate = nullptr);
+                           float* fin_scores, int64_t* fin_ids, hipStream_t st);
 
 // ---- fp16 first pass of the two-level top-k on large matrices: dense_hi.hip ----
 bool dense_hi_supported(int d);
 int dense_hi_max_queries(int d);  // queries per scan: 64, 48 at d = 1 024
-long dense_hi_sample_stride(long n);
-long dense_hi_sample_items(long n);
-size_t dense_hi_mt_bytes(long n);                       // maxima of the sample, [items][64]
-size_t dense_hi_cand_entries(long n, int m, int kc);    // 8-byte entries of the flat candidate list
-int dense_hi_launch_sample(const float* X, long n, int d, const float* Q, int nq, float* MT, hipStream_t st, float x_scale);
-int dense_hi_launch_transpose(const float* MT, long items, int nq, long ldM, float* M, hipStream_t st);
-int dense_hi_launch_emit(const float* X, long n, int d, const float* Q, int nq, const float* tau, int tau_stride, void* cand,
-                         unsigned int* total, size_t cap, hipStream_t st, float x_scale);
-size_t dense_hi_cand_part_bytes(int m, int kc);
-int dense_hi_launch_cand_topk(const void* cand, const unsigned int* total, size_t cap, int m, int kc, void* part,
-                              int* nparts, hipStream_t st);
-int dense_hi_launch_check(const float* vals, int64_t* ids, int m, int kc1, int k, const float* Q, int d,
-                          float row_norm_max, float x_scale, long n_tiles, const unsigned int* total, size_t cap, int* flag,
-                          unsigned int* unresolved, hipStream_t st);
 int dense_stats_launch(const float* X, long n, int d, unsigned int* out2, hipStream_t st);
 // round 4: the tail of a large search in four launches + two gated ones (dense_hi.hip, dense_mfma.hip)
 long dense_hi2_sample_stride(long n, int qtiles);

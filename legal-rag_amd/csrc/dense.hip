@@ -158,10 +158,8 @@ __global__ __launch_bounds__(256) void dense_all_scores_kernel(const float* __re
 // One block per query: stream the per-block lists, keep the best k, decode.
 __global__ __launch_bounds__(256) void dense_merge_kernel(const C32* __restrict__ part, int nparts, int nq, int k,
                                                            int cap, float* __restrict__ out_scores,
-                                                           long long* __restrict__ out_ids,
-                                                           const int* __restrict__ gate) {
+                                                           long long* __restrict__ out_ids) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  if (gate != nullptr && *gate == 0) return;  // gated launch: see run_search_two_level
   C32* lists = reinterpret_cast<C32*>(smem);
   int* cnts = reinterpret_cast<int*>(lists + (size_t)kWaves * cap);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -281,7 +279,7 @@ struct amdr_dense {
   int hi_level = 0;
   bool hi_off = false;
   int64_t hi_passes = 0;        // passes (<= 64 queries each) through the fp16 first pass
-  int64_t lvl_p0 = 0;           // hi_passes / flagged-pass counter when the current level was entered
+  int64_t lvl_p0 = 0;           // device pass / flagged-pass counters when the current level was entered
   unsigned int lvl_f0 = 0;
   unsigned int* hi_host = nullptr;  // pinned: the device's (unresolved queries, flagged passes, passes), copied back after every search
   hipEvent_t hi_ev = nullptr;       // recorded behind that copy: hi_adapt reads hi_host only once it has completed
@@ -502,7 +500,7 @@ int run_search_batched(amdr_dense* h, int ws, const float* Q_dev, int nq, int k,
     if (!direct) {
       size_t lds = (size_t)kWaves * p.cap * sizeof(C32) + kWaves * sizeof(int);
       hipLaunchKernelGGL(dense_merge_kernel, dim3(m), dim3(256), lds, st, partb.as<C32>(), p.slabs, m, k, p.cap,
-                         scores_dev + (size_t)q0 * k, (long long*)ids_dev + (size_t)q0 * k, (const int*)nullptr);
+                         scores_dev + (size_t)q0 * k, (long long*)ids_dev + (size_t)q0 * k);
       AMDR_HIP(hipGetLastError());
     }
     if (tail && (rc = dense_fuse_plain_launch(*tail, q0, m, k, scores_dev + (size_t)q0 * k, ids_dev + (size_t)q0 * k, st)))
@@ -540,12 +538,12 @@ int two_level_chunk(int nq, int k) {
 
 // The fp16 first pass (dense_hi.hip): the tile maxima of step 1 come from v_mfma_f32_32x32x16_f16 on fp16 roundings of
 // both operands — 64 queries per scan instead of 32, the scan bound by HBM alone.  Approximate maxima a(t) lie within
-// eps_q of the exact ones (dense_hi_check_kernel states the bound), so the candidate set is widened: the kc = k +
+// eps_q of the exact ones (dense_hi_select_kernel states the bound), so the candidate set is widened: the kc = k +
 // max(k, 22) + 1 tiles with the largest a(t) are re-scored, and the answer is exact if the kc-th largest a(t) lies below
 // T_k - 2 eps_q (T_k = the k-th largest): the k tiles on top have exact maxima >= T_k - eps, hence s_k >= T_k - eps,
 // and a tile holding a row >= s_k has a(t) >= s_k - eps >= T_k - 2 eps — it is among the first kc - 1.  Steps 3-4 are
-// the unchanged exact kernels: same ids, same score bits.  A query the bound does not separate raises a device flag;
-// the exact chain is enqueued behind, every launch gated on that flag (no host round trip), and rewrites the batch.
+// exact: same ids, same score bits.  A query the bound does not separate raises a device flag; the exact first pass is
+// enqueued behind, gated on that flag (no host round trip), and gives that query its k tiles.
 // Extra candidates: the tiles expected within 2 eps below the cut grow with k (about 0.4 k on unit-norm Gaussian rows)
 // and with how tightly the matrix clusters around a query's best rows, which only the data knows: three widths.
 constexpr int kHiLevels = 3;
@@ -569,18 +567,10 @@ bool hi_applies(const amdr_dense* h, int nq, int k) {
   if (e && e[0] == '1') return tiles >= 2L * hi_kc_max(k);  // pinned on (tests)
   return dense_stream_nontemporal((long)h->n, h->d) && tiles >= 64L * hi_kc_max(k);
 }
-int hi_chunk(const amdr_dense* h, int nq, int k) {  // the same at every level: a handle's passes keep their shape when its level moves
-  int c = dense_hi_max_queries(h->d);
-  // the candidate union is a bitmap over the tiles (any number of candidates) up to 2^20 tiles; beyond, the one-wave sort
-  // and its 8 192-candidate limit (>= 32 queries for every admitted k)
-  if (((long)h->n + 31) / 32 > kUniqueBitmapTilesMax && kTwoLevelTilesMax / hi_kc_max(k) < c) c = kTwoLevelTilesMax / hi_kc_max(k);
-  return nq < c ? nq : c;
-}
 // Between searches (host side, no synchronisation: the counters are whatever the last completed copy-back left).  One
-// unresolved query sends its whole pass through the exact chain as well (+2 scans for a 1-scan pass), so what is
-// counted is PASSES whose flag went up: more than 10 % of >= 4 passes at this width -> the next width (+3 % per pass);
-// at the widest, more than half -> the exact passes alone are cheaper (1 + 2 f > 2).
-bool hi_tail2();
+// unresolved query sends its whole pass through the exact first pass as well, so what is counted is PASSES whose flag
+// went up: more than 10 % of >= 4 passes at this width -> the next width (+3 % per pass); at the widest, more than half
+// -> the exact passes alone are cheaper (1 + 2 f > 2).
 void hi_adapt(amdr_dense* h) {
   if (!h->hi_host || h->hi_off || getenv("AMDR_DENSE_HI_LEVEL")) return;
   // the counters are whatever the last COMPLETED copy-back left: the pinned words are read only after the event behind
@@ -591,9 +581,9 @@ void hi_adapt(amdr_dense* h) {
     for (int i = 0; i < 3; ++i) h->hi_seen[i] = h->hi_host[i];
   }
   const unsigned int f = h->hi_seen[1];
-  // passes: counted on the device next to the flags under the round-4 tail (a hipGraph replay bumps both; the host's
-  // own count would not see replays), on the host under the round-3 tail
-  const int64_t passes = hi_tail2() ? (int64_t)h->hi_seen[2] : h->hi_passes;
+  // passes: counted on the device next to the flags (a hipGraph replay bumps both; the host's own count would not see
+  // replays)
+  const int64_t passes = (int64_t)h->hi_seen[2];
   const int64_t p = passes - h->lvl_p0;
   const int64_t bad = (int64_t)(f - h->lvl_f0);
   if (p < 4) return;
@@ -610,11 +600,6 @@ void hi_adapt(amdr_dense* h) {
     h->lvl_p0 = passes;
     h->lvl_f0 = f;
   }
-}
-// AMDR_DENSE_HI_TAIL=0 pins the round-3 tail (flat candidate list, ~18 launches per 64-query pass): A/B, tests
-bool hi_tail2() {
-  const char* e = getenv("AMDR_DENSE_HI_TAIL");
-  return !(e && e[0] == '0');
 }
 constexpr int kHi2Tiles = 4;  // query tiles per pass of the round-4 tail: 256 queries (192 at d = 1 024) share one tail
 int hi2_chunk(const amdr_dense* h, int nq) {
@@ -656,43 +641,26 @@ void hi2_plan(const amdr_dense* h, int m, int k, int kc, Hi2Plan* p) {
 }
 
 struct TwoLevelPlan {
-  DenseMfmaPlan scan, tk1, pass2;  // full scan (mode 1), top-kc over the tile maxima, candidate re-scoring + its top-k
+  DenseMfmaPlan scan, tk1, pass2;  // full scan (mode 1), top-k over the tile maxima, candidate re-scoring + its top-k
   long tiles, cand_rows;
   size_t m_bytes, s2_bytes, aux_bytes, part_bytes;
-  // fp16 first pass only: the sample (tk1 then ranks ITS maxima), the flat candidate list
-  long sample_items;
-  size_t s2_own, mt_bytes, cand_entries;
 };
-// kc = candidate tiles per query: k in the exact form, hi_kc(k, level) behind the fp16 first pass
-void two_level_plan(const amdr_dense* h, int m, int k, int kc, TwoLevelPlan* t) {
-  const bool hi = kc != k;
+// the exact form: every query of the pass against the UNION of their k candidate tiles each (one list)
+void two_level_plan(const amdr_dense* h, int m, int k, TwoLevelPlan* t) {
   t->tiles = ((long)h->n + 31) / 32;
-  t->sample_items = hi ? dense_hi_sample_items((long)h->n) : 0;
-  if (!hi) dense_mfma_plan((long)h->n, h->d, m, k, &t->scan);  // the exact first pass only
-  dense_mfma_plan(hi ? t->sample_items : t->tiles, h->d, m, kc, &t->tk1);  // only its top-k half is used: columns = tiles
-  // exact form: every query of the pass against the UNION of their candidate tiles (one list); behind the fp16 pass a
-  // query against its own kc tiles (mode 3 of the scores kernel: block row = query, <= 16 tiles per block)
-  t->cand_rows = hi ? (long)kc * 32 : (long)m * kc * 32;
+  dense_mfma_plan((long)h->n, h->d, m, k, &t->scan);
+  dense_mfma_plan(t->tiles, h->d, m, k, &t->tk1);  // only its top-k half is used: columns = tiles
+  t->cand_rows = (long)m * k * 32;
   dense_mfma_plan(t->cand_rows, h->d, m, k, &t->pass2);
-  if (hi) {
-    // a (query, tile) pass is 11.7 us of fp32 matrix time on one SIMD and the check drops the tiles below a query's cut
-    // (~14 of 33 stay): four tiles per block = one per SIMD, blocks beyond a query's list return before staging anything
-    t->pass2.rows_per_block = 4 * 32;
-    t->pass2.grid_x = (int)((t->cand_rows + t->pass2.rows_per_block - 1) / t->pass2.rows_per_block);
-    t->pass2.grid_y = m;
-  }
   t->m_bytes = ((size_t)m * t->tk1.ld * sizeof(float) + 255) / 256 * 256;
-  t->s2_own = ((size_t)m * t->pass2.ld * sizeof(float) + 255) / 256 * 256;
-  t->mt_bytes = hi ? (dense_hi_mt_bytes((long)h->n) + 255) / 256 * 256 : 0;
-  t->cand_entries = hi ? dense_hi_cand_entries((long)h->n, m, kc) : 0;
-  t->s2_bytes = t->s2_own + t->mt_bytes + t->cand_entries * sizeof(C32);  // S2 | sample maxima | candidate list
-  // tile ids + maxima, union list + count; behind the fp16 pass also the sample's top-kc (ids + maxima)
-  t->aux_bytes = (size_t)m * kc * (sizeof(int64_t) + sizeof(float)) * (hi ? 2 : 1) + (size_t)(m * kc + 64) * sizeof(int) + 256;
+  t->s2_bytes = ((size_t)m * t->pass2.ld * sizeof(float) + 255) / 256 * 256;
+  t->aux_bytes = (size_t)m * k * (sizeof(int64_t) + sizeof(float)) + (size_t)(m * k + 64) * sizeof(int) + 256;  // tile ids +
+                                                                                                           // maxima, union + count
   t->part_bytes = t->tk1.part_bytes > t->pass2.part_bytes ? t->tk1.part_bytes : t->pass2.part_bytes;
-  if (hi && dense_hi_cand_part_bytes(m, kc) > t->part_bytes) t->part_bytes = dense_hi_cand_part_bytes(m, kc);
 }
 // Workspace for one search of nq queries at depth k: the maximum over every chunk size the pass loop will use — the
 // full chunk AND the remainder (a smaller chunk can need MORE slab-list space: slabs(m) * m is not monotone in m).
+// Behind the fp16 first pass: its passes, and the exact passes a handle that gave it up runs instead.
 // With `all` (amdr_dense_reserve: calls within (nq_max, k_max) must allocate nothing) the maximum over every batch
 // size <= nq and every depth <= k that takes this path — a smaller k takes more queries per pass (a larger matrix of
 // tile maxima) and the path's own applicability test depends on k.
@@ -704,16 +672,6 @@ struct TwoLevelNeed {
     aux = t.aux_bytes + 256 > aux ? t.aux_bytes + 256 : aux;  // + the gate flag behind the lists
   }
 };
-void two_level_need_exact(const amdr_dense* h, int nq, int k, TwoLevelNeed* need) {
-  const int chunk = two_level_chunk(nq, k);
-  TwoLevelPlan t;
-  two_level_plan(h, chunk, k, k, &t);
-  need->add(t);
-  if (nq % chunk) {
-    two_level_plan(h, nq % chunk, k, k, &t);
-    need->add(t);
-  }
-}
 void hi2_need(const amdr_dense* h, int nq, int k, TwoLevelNeed* need) {  // monotone in the pass size and in kc
   Hi2Plan p;
   hi2_plan(h, hi2_chunk(h, nq), k, hi_kc_max(k), &p);
@@ -721,17 +679,13 @@ void hi2_need(const amdr_dense* h, int nq, int k, TwoLevelNeed* need) {  // mono
   need->aux = p.aux_bytes + 256 > need->aux ? p.aux_bytes + 256 : need->aux;
 }
 void two_level_need(const amdr_dense* h, int nq, int k, TwoLevelNeed* need) {
-  if (!hi_applies(h, nq, k)) return two_level_need_exact(h, nq, k, need);
-  if (hi_tail2()) hi2_need(h, nq, k, need);
-  const int chunk = hi_chunk(h, nq, k);
+  if (hi_applies(h, nq, k)) hi2_need(h, nq, k, need);
+  const int chunk = two_level_chunk(nq, k);
   TwoLevelPlan t;
   for (int m : {chunk, nq % chunk}) {
     if (m == 0) continue;
-    for (int l = 0; l < kHiLevels; ++l) {  // the level can move between searches: reserve for all three
-      two_level_plan(h, m, k, hi_kc(k, l), &t);
-      need->add(t);
-    }
-    two_level_need_exact(h, m, k, need);  // the gated exact chain of the same pass
+    two_level_plan(h, m, k, &t);
+    need->add(t);
   }
 }
 int two_level_ensure(amdr_dense* h, int ws, int nq, int k, bool all = false) {
@@ -744,17 +698,11 @@ int two_level_ensure(amdr_dense* h, int ws, int nq, int k, bool all = false) {
       // all run the two-level form: cover every m a pass can have
       const bool hi = hi_applies(h, nq, kk);
       if (!hi && !two_level_applies(h, nq < 95 ? nq : 95, kk) && !two_level_applies(h, nq, kk)) continue;
-      if (hi && hi_tail2()) hi2_need(h, nq, kk, &need);
+      if (hi) hi2_need(h, nq, kk, &need);
       TwoLevelPlan t;
-      if (hi)
-        for (int m = 1; m <= hi_chunk(h, nq, kk); ++m)
-          for (int l = 0; l < kHiLevels; ++l) {
-            two_level_plan(h, m, kk, hi_kc(kk, l), &t);
-            need.add(t);
-          }
       const int cmax = two_level_chunk(nq, kk);
       for (int m = 1; m <= cmax; ++m) {
-        two_level_plan(h, m, kk, kk, &t);
+        two_level_plan(h, m, kk, &t);
         need.add(t);
       }
     }
@@ -767,102 +715,50 @@ int two_level_ensure(amdr_dense* h, int ws, int nq, int k, bool all = false) {
 
 // one top-k pass over a [m][ld] score matrix with `cols` valid columns (slab lists + merge, or direct)
 int topk_pass(const DenseMfmaPlan& p, const float* S, long cols, int m, int k, DevBuf& partb, float* out_scores,
-              int64_t* out_ids, hipStream_t st, const int* gate = nullptr) {
+              int64_t* out_ids, hipStream_t st) {
   const bool direct = p.slabs == 1;
-  int rc = dense_mfma_launch_topk(p, S, cols, m, k, partb.p, direct ? out_scores : nullptr, direct ? out_ids : nullptr, st,
-                                  gate);
+  int rc = dense_mfma_launch_topk(p, S, cols, m, k, partb.p, direct ? out_scores : nullptr, direct ? out_ids : nullptr, st);
   if (rc) return rc;
   if (!direct) {
     size_t lds = (size_t)kWaves * p.cap * sizeof(C32) + kWaves * sizeof(int);
     hipLaunchKernelGGL(dense_merge_kernel, dim3(m), dim3(256), lds, st, partb.as<C32>(), p.slabs, m, k, p.cap, out_scores,
-                       (long long*)out_ids, gate);
+                       (long long*)out_ids);
     AMDR_HIP(hipGetLastError());
   }
   return AMDR_OK;
 }
 
-// One pass of <= chunk queries.  kc_hi > 0: the fp16 first pass with kc_hi candidate tiles per query, its check raises
-// *flag; otherwise the exact first pass, every launch gated on *gate when given.
-int two_level_pass(amdr_dense* h, int ws, const float* Qc, int m, int k, int kc_hi, float* out_scores, int64_t* out_ids,
-                   hipStream_t st, int* flag, const int* gate) {
-  const bool hi = kc_hi > 0;
-  const int kc = hi ? kc_hi : k;
+// One pass of <= two_level_chunk queries of the exact form.
+int two_level_pass(amdr_dense* h, int ws, const float* Qc, int m, int k, float* out_scores, int64_t* out_ids,
+                   hipStream_t st) {
   TwoLevelPlan t;
-  two_level_plan(h, m, k, kc, &t);
+  two_level_plan(h, m, k, &t);
   float* M = h->smat[ws].as<float>();
-  unsigned char* s2p = reinterpret_cast<unsigned char*>(h->smat[ws].p) + t.m_bytes;
-  float* S2 = reinterpret_cast<float*>(s2p);
+  float* S2 = reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(h->smat[ws].p) + t.m_bytes);
   unsigned char* aux = reinterpret_cast<unsigned char*>(h->aux[ws].p);
   int64_t* tile_ids = reinterpret_cast<int64_t*>(aux);
-  float* tile_max = reinterpret_cast<float*>(aux + (size_t)m * kc * sizeof(int64_t));
-  int* list = reinterpret_cast<int*>(aux + (size_t)m * kc * (sizeof(int64_t) + sizeof(float)));
-  int* count = list + (size_t)m * kc;
+  float* tile_max = reinterpret_cast<float*>(aux + (size_t)m * k * sizeof(int64_t));
+  int* list = reinterpret_cast<int*>(aux + (size_t)m * k * (sizeof(int64_t) + sizeof(float)));
+  int* count = list + (size_t)m * k;
   int rc;
-  const bool prof = !gate && h->prof_on && (size_t)(h->prof_used + 2) <= h->prof_ev.size();
-  if (hi) {
-    // 1a. maxima of a strided sample of the tiles -> per query the kc-th best = the threshold of the full scan
-    float* MT = reinterpret_cast<float*>(s2p + t.s2_own);
-    void* cand = s2p + t.s2_own + t.mt_bytes;
-    int64_t* ts_ids = reinterpret_cast<int64_t*>(count + 64);
-    float* ts_max = reinterpret_cast<float*>(ts_ids + (size_t)m * kc);
-    unsigned int* total = reinterpret_cast<unsigned int*>(flag) + 16;
-    if ((rc = dense_hi_launch_sample(h->X, (long)h->n, h->d, Qc, m, MT, st, h->x_scale))) return rc;
-    if ((rc = dense_hi_launch_transpose(MT, t.sample_items, m, t.tk1.ld, M, st))) return rc;
-    if ((rc = topk_pass(t.tk1, M, t.sample_items, m, kc, h->part[ws], ts_max, ts_ids, st))) return rc;
-    AMDR_HIP(hipMemsetAsync(total, 0, sizeof(unsigned int), st));
-    // 1b. the scan (the launch the profiling events bracket): maxima that reach the threshold -> flat candidate list
-    if (prof) AMDR_HIP(hipEventRecord(h->prof_ev[h->prof_used], st));
-    if ((rc = dense_hi_launch_emit(h->X, (long)h->n, h->d, Qc, m, ts_max + (kc - 1), kc, cand, total, t.cand_entries, st,
-                                   h->x_scale)))
-      return rc;
-    if (prof) {
-      AMDR_HIP(hipEventRecord(h->prof_ev[h->prof_used + 1], st));
-      h->prof_used += 2;
-    }
-    // 2. kc candidate tiles per query; is the cut wide enough?
-    int nparts = 0;
-    if ((rc = dense_hi_launch_cand_topk(cand, total, t.cand_entries, m, kc, h->part[ws].p, &nparts, st))) return rc;
-    {
-      const int mcap = topk_cap(kc);
-      const size_t lds = (size_t)kWaves * mcap * sizeof(C32) + kWaves * sizeof(int);
-      hipLaunchKernelGGL(dense_merge_kernel, dim3(m), dim3(256), lds, st, h->part[ws].as<C32>(), nparts, m, kc, mcap, tile_max,
-                         (long long*)tile_ids, (const int*)nullptr);
-      AMDR_HIP(hipGetLastError());
-    }
-    h->hi_queries += m;
-    h->hi_passes += 1;
-    if ((rc = dense_hi_launch_check(tile_max, tile_ids, m, kc, k, Qc, h->d, h->row_norm_max, h->x_scale, t.tiles, total,
-                                    t.cand_entries, flag, h->stats.as<unsigned int>() + 2, st)))
-      return rc;
-  } else {
-    // 1. tile maxima (the scan: this is the launch the profiling events bracket)
-    if (prof) AMDR_HIP(hipEventRecord(h->prof_ev[h->prof_used], st));
-    DenseMfmaPlan scan = t.scan;
-    scan.ld = t.tk1.ld;
-    if ((rc = dense_mfma_launch_scores(scan, h->X, (long)h->n, h->d, Qc, m, M, st, 1, nullptr, nullptr, 0, gate))) return rc;
-    if (prof) {
-      AMDR_HIP(hipEventRecord(h->prof_ev[h->prof_used + 1], st));
-      h->prof_used += 2;
-    }
-    // 2. k candidate tiles per query
-    if ((rc = topk_pass(t.tk1, M, t.tiles, m, kc, h->part[ws], tile_max, tile_ids, st, gate))) return rc;
+  const bool prof = h->prof_on && (size_t)(h->prof_used + 2) <= h->prof_ev.size();
+  // 1. tile maxima (the scan: this is the launch the profiling events bracket)
+  if (prof) AMDR_HIP(hipEventRecord(h->prof_ev[h->prof_used], st));
+  DenseMfmaPlan scan = t.scan;
+  scan.ld = t.tk1.ld;
+  if ((rc = dense_mfma_launch_scores(scan, h->X, (long)h->n, h->d, Qc, m, M, st, 1))) return rc;
+  if (prof) {
+    AMDR_HIP(hipEventRecord(h->prof_ev[h->prof_used + 1], st));
+    h->prof_used += 2;
   }
-  if (hi) {
-    // 3. every query's own candidate tiles, ascending; their exact scores; 4. top-k, columns -> row ids
-    if ((rc = dense_tiles_sort_per_query_launch(tile_ids, m, kc, list, count, st))) return rc;
-    if ((rc = dense_mfma_launch_scores(t.pass2, h->X, t.cand_rows, h->d, Qc, m, S2, st, 3, list, count, (long)h->n, nullptr, kc)))
-      return rc;
-    if ((rc = topk_pass(t.pass2, S2, t.cand_rows, m, k, h->part[ws], out_scores, out_ids, st))) return rc;
-    return dense_tiles_remap_launch(out_ids, m * k, list, count, (long)h->n, st, nullptr, k, kc);
-  }
-  // ... their sorted union
-  if ((rc = dense_tiles_unique_launch(tile_ids, m * kc, t.tiles, list, count, st, gate))) return rc;
+  // 2. k candidate tiles per query, their sorted union
+  if ((rc = topk_pass(t.tk1, M, t.tiles, m, k, h->part[ws], tile_max, tile_ids, st))) return rc;
+  if ((rc = dense_tiles_unique_launch(tile_ids, m * k, t.tiles, list, count, st))) return rc;
   // 3. exact scores of the candidate tiles' rows
-  if ((rc = dense_mfma_launch_scores(t.pass2, h->X, t.cand_rows, h->d, Qc, m, S2, st, 2, list, count, (long)h->n, gate)))
-    return rc;
+  if ((rc = dense_mfma_launch_scores(t.pass2, h->X, t.cand_rows, h->d, Qc, m, S2, st, 2, list, count, (long)h->n))) return rc;
   // 4. top-k of the candidates, columns -> row ids
-  if ((rc = topk_pass(t.pass2, S2, t.cand_rows, m, k, h->part[ws], out_scores, out_ids, st, gate))) return rc;
-  return dense_tiles_remap_launch(out_ids, m * k, list, count, (long)h->n, st, gate);
+  if ((rc = topk_pass(t.pass2, S2, t.cand_rows, m, k, h->part[ws], out_scores, out_ids, st))) return rc;
+  return dense_tiles_remap_launch(out_ids, m * k, list, count, (long)h->n, st);
 }
 
 // One pass (<= 4 query tiles) of the round-4 tail: see dense_hi.hip.  Launches: sample, tau, one scan per query tile,
@@ -925,9 +821,9 @@ int run_search_two_level(amdr_dense* h, int ws, const float* Q_dev, int nq, int 
   (void)hipStreamIsCapturing(st, &cap_st);
   const bool capturing = cap_st != hipStreamCaptureStatusNone;
   if (hi && !capturing) hi_adapt(h);
-  const bool tail2 = hi && hi_tail2() && !h->hi_off;
-  const int chunk = tail2 ? hi2_chunk(h, nq) : hi ? hi_chunk(h, nq, k) : two_level_chunk(nq, k);
+  // a handle that gave the fp16 pass up runs the exact passes, ungated
   const int kc_hi = hi && !h->hi_off ? hi_kc(k, hi_level_of(h)) : 0;
+  const int chunk = kc_hi ? hi2_chunk(h, nq) : two_level_chunk(nq, k);
   // the gate flag: behind the largest list layout of this call (two_level_ensure sized aux for it)
   int* flag = reinterpret_cast<int*>(reinterpret_cast<unsigned char*>(h->aux[ws].p) + h->aux[ws].cap - 256);
   for (int q0 = 0; q0 < nq; q0 += chunk) {
@@ -935,27 +831,9 @@ int run_search_two_level(amdr_dense* h, int ws, const float* Q_dev, int nq, int 
     const float* Qc = Q_dev + (size_t)q0 * h->d;
     float* os = scores_dev + (size_t)q0 * k;
     int64_t* oi = ids_dev + (size_t)q0 * k;
-    if (!hi) {
-      if ((rc = two_level_pass(h, ws, Qc, m, k, 0, os, oi, st, nullptr, nullptr))) return rc;
-      continue;
-    }
-    if (tail2) {  // (the flag is reset by the pass's own tau kernel)
-      if ((rc = hi2_pass(h, ws, Qc, m, k, kc_hi, os, oi, st, flag))) return rc;
-      continue;
-    }
-    if (kc_hi) {
-      AMDR_HIP(hipMemsetAsync(flag, 0, sizeof(int), st));
-      if ((rc = two_level_pass(h, ws, Qc, m, k, kc_hi, os, oi, st, flag, nullptr))) return rc;
-    }
-    // the exact chain holds 32-query tiles; behind the fp16 pass it runs only if the flag was raised — and
-    // unconditionally, in the same pass shapes (same workspace), on a handle that gave the fp16 pass up
-    const int ec = two_level_chunk(m, k);
-    for (int e0 = 0; e0 < m; e0 += ec) {
-      const int em = m - e0 < ec ? m - e0 : ec;
-      if ((rc = two_level_pass(h, ws, Qc + (size_t)e0 * h->d, em, k, 0, os + (size_t)e0 * k, oi + (size_t)e0 * k, st,
-                               nullptr, kc_hi ? flag : nullptr)))
-        return rc;
-    }
+    // (the flag is reset by the fp16 pass's own tau kernel)
+    rc = kc_hi ? hi2_pass(h, ws, Qc, m, k, kc_hi, os, oi, st, flag) : two_level_pass(h, ws, Qc, m, k, os, oi, st);
+    if (rc) return rc;
   }
   if (kc_hi && h->hi_host && !capturing && !h->hi_copy_pending) {  // what hi_adapt reads before a later search
     AMDR_HIP(hipMemcpyAsync(h->hi_host, h->stats.as<unsigned int>() + 2, 3 * sizeof(unsigned int), hipMemcpyDeviceToHost, st));
@@ -1000,7 +878,7 @@ int run_search(amdr_dense* h, int ws, const float* Q_dev, int nq, int k, float* 
   int nparts = h->n > 0 ? p.grid_x : 0;
   size_t lds = (size_t)kWaves * p.cap * sizeof(C32) + kWaves * sizeof(int);
   hipLaunchKernelGGL(dense_merge_kernel, dim3(nq), dim3(256), lds, st, part, nparts, nq, k, p.cap, scores_dev,
-                     (long long*)ids_dev, (const int*)nullptr);
+                     (long long*)ids_dev);
   AMDR_HIP(hipGetLastError());
   return AMDR_OK;
 }
@@ -1158,13 +1036,12 @@ int amdr_dense_add(amdr_dense_t* h, const float* X_host, int64_t n_add) {
   // the matrix changed: what the fp16 first pass learnt about it (width level, given up) starts over
   h->hi_level = 0;
   h->hi_off = false;
-  h->lvl_p0 = h->hi_passes;
   if (h->hi_copy_pending && hipEventSynchronize(h->hi_ev) == hipSuccess) {
     h->hi_copy_pending = false;
     for (int i = 0; i < 3; ++i) h->hi_seen[i] = h->hi_host[i];
   }
   h->lvl_f0 = h->hi_seen[1];
-  if (hi_tail2()) h->lvl_p0 = (int64_t)h->hi_seen[2];
+  h->lvl_p0 = (int64_t)h->hi_seen[2];
   return update_stats(h, row0, n_add);
 }
 
@@ -1317,8 +1194,7 @@ int amdr_dense_workspace_plan(int64_t n, int32_t d, int32_t nq, int32_t k, int64
     TwoLevelNeed need, used;
     two_level_need(&h, nq, k, &need);
     out6[0] = (int64_t)need.smat, out6[1] = (int64_t)need.part, out6[2] = (int64_t)need.aux;
-    const bool hi = hi_applies(&h, nq, k);
-    if (hi && hi_tail2()) {  // the round-4 tail: passes of up to four query tiles, any of the three widths
+    if (hi_applies(&h, nq, k)) {  // passes of up to four query tiles, any of the three widths
       const int c2 = hi2_chunk(&h, nq);
       for (int q0 = 0; q0 < nq; q0 += c2)
         for (int l = 0; l < kHiLevels; ++l) {
@@ -1328,20 +1204,11 @@ int amdr_dense_workspace_plan(int64_t n, int32_t d, int32_t nq, int32_t k, int64
           used.aux = p.aux_bytes + 256 > used.aux ? p.aux_bytes + 256 : used.aux;
         }
     }
-    const int chunk = hi ? hi_chunk(&h, nq, k) : two_level_chunk(nq, k);
-    for (int q0 = 0; q0 < nq; q0 += chunk) {  // what the pass loop of run_search_two_level touches (round-3 tail / given up)
-      const int m = nq - q0 < chunk ? nq - q0 : chunk;
+    const int chunk = two_level_chunk(nq, k);
+    for (int q0 = 0; q0 < nq; q0 += chunk) {  // the exact passes (a handle that gave the fp16 pass up runs them too)
       TwoLevelPlan t;
-      if (hi)
-        for (int l = 0; l < kHiLevels; ++l) {
-          two_level_plan(&h, m, k, hi_kc(k, l), &t);
-          used.add(t);
-        }
-      const int ec = hi ? two_level_chunk(m, k) : m;
-      for (int e0 = 0; e0 < m; e0 += ec) {
-        two_level_plan(&h, m - e0 < ec ? m - e0 : ec, k, k, &t);
-        used.add(t);
-      }
+      two_level_plan(&h, nq - q0 < chunk ? nq - q0 : chunk, k, &t);
+      used.add(t);
     }
     out6[3] = (int64_t)used.smat, out6[4] = (int64_t)used.part, out6[5] = (int64_t)used.aux;
   } else if (nq >= kBatchedMin && dense_mfma_supported(d)) {
@@ -1364,7 +1231,7 @@ int amdr_dense_plan_info(const amdr_dense_t* h, int32_t nq, int32_t k, char* buf
     snprintf(buf, buf_len, "empty index");
     return AMDR_OK;
   }
-  if (hi_applies(h, nq, k) && !h->hi_off && hi_tail2()) {
+  if (hi_applies(h, nq, k) && !h->hi_off) {
     const int m = hi2_chunk(h, nq), kc = hi_kc(k, hi_level_of(h));
     Hi2Plan p;
     hi2_plan(h, m, k, kc, &p);
@@ -1377,36 +1244,15 @@ int amdr_dense_plan_info(const amdr_dense_t* h, int32_t nq, int32_t k, char* buf
              dense_hi2_sample_stride((long)h->n, p.qtiles), hi_level_of(h), kc, kc);
     return AMDR_OK;
   }
-  if (hi_applies(h, nq, k) && !h->hi_off) {
-    TwoLevelPlan t;
-    const int m = hi_chunk(h, nq, k), kc = hi_kc(k, hi_level_of(h));
-    two_level_plan(h, m, k, kc, &t);
-    snprintf(buf, buf_len,
-             "dense_hi_tilemax_kernel fp16 first pass queries_per_launch=%d two-level: top-%d of %ld approximate tile "
-             "maxima (width level %d; threshold from a sample of every %ld-th tile), cut checked against the rounding bound "
-             "+ exact re-scoring of every query's tiles at or above its cut (<= %d each) + top-k (exact first pass behind a "
-             "device flag)",
-             m, kc, t.tiles, hi_level_of(h), dense_hi_sample_stride((long)h->n), kc);
-    return AMDR_OK;
-  }
-  if (hi_applies(h, nq, k)) {  // the handle gave the fp16 pass up: exact passes in the same shapes
-    TwoLevelPlan t;
-    const int m = two_level_chunk(hi_chunk(h, nq, k), k);
-    two_level_plan(h, m, k, k, &t);
-    snprintf(buf, buf_len,
-             "dense_mfma_scores_kernel tile-maxima grid=%dx%d queries_per_launch=%d two-level: top-%d of %ld tile maxima "
-             "+ re-scoring of <= %d candidate tiles + top-k (fp16 first pass given up: too many unresolved queries)",
-             t.scan.grid_x, t.scan.grid_y, m, k, t.tiles, m * k);
-    return AMDR_OK;
-  }
-  if (two_level_applies(h, nq, k)) {
+  if (hi_applies(h, nq, k) || two_level_applies(h, nq, k)) {  // (hi_applies: the handle gave the fp16 pass up)
     TwoLevelPlan t;
     const int m = two_level_chunk(nq, k);
-    two_level_plan(h, m, k, k, &t);
+    two_level_plan(h, m, k, &t);
     snprintf(buf, buf_len,
              "dense_mfma_scores_kernel tile-maxima grid=%dx%d queries_per_launch=%d two-level: top-%d of %ld tile maxima "
-             "+ re-scoring of <= %d candidate tiles + top-k",
-             t.scan.grid_x, t.scan.grid_y, m, k, t.tiles, m * k);
+             "+ re-scoring of <= %d candidate tiles + top-k%s",
+             t.scan.grid_x, t.scan.grid_y, m, k, t.tiles, m * k,
+             hi_applies(h, nq, k) ? " (fp16 first pass given up: too many unresolved queries)" : "");
     return AMDR_OK;
   }
   const bool batched = nq >= kBatchedMin && dense_mfma_supported(h->d);

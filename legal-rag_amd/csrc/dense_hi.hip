@@ -6,9 +6,9 @@
 // peak and cannot hold more than 32 queries (a 96-KiB fp32 query tile in LDS).  The first pass only has to find
 // candidate tiles, and the second pass is exact — so here it runs on v_mfma_f32_32x32x16_f16 with fp16 ROUNDINGS of
 // both operands (hi parts, csrc/maxsim.hip): 16x the matrix rate, a 96-KiB tile now holds 64 queries, the scan is
-// bound by HBM alone.  Every approximate tile maximum lies within a proven eps of the exact one (dense_hi_check_kernel
-// states the bound), the candidate cut is widened by it (dense.hip run_search_two_level / two_level_pass), the
-// re-scoring pass is the unchanged exact fp32 kernel: ids and score bits are those of the exact forms.  A query whose
+// bound by HBM alone.  Every approximate tile maximum lies within a proven eps of the exact one (dense_hi_select_kernel
+// states the bound), the candidate cut is widened by it (dense.hip hi2_pass), the re-scoring is exact fp32 in the same
+// MFMA k order: ids and score bits are those of the exact forms.  A query whose
 // cut the bound does not separate (mass near-ties) raises a device flag and the exact first pass runs for that batch
 // (gated launches: no host round trip).
 //
@@ -17,9 +17,9 @@
 // coalesced 16-B/lane fp32 loads (4 rows x 256 B per wave instruction, non-temporal, 2 chunks of 64 floats per row in
 // flight across tile boundaries), conversion to fp16 in registers (the matrix's power-of-two scale applied), a
 // wave-private 4-KiB fp16 stage in LDS, fragments back, 8 MFMAs per 64-float chunk (32 rows x 64 queries), one maximum per
-// tile and query.  Two launches per search: a SAMPLE of every s-th tile writes its maxima (MT[item][queries]) and gives
+// tile and query.  Two launches per search: a SAMPLE of every s-th tile writes its maxima (MT[query][item]) and gives
 // each query a threshold (the kc-th best sampled maximum, a lower bound of the kc-th best overall); the full SCAN then
-// lets only the maxima that reach the threshold leave the kernel, as entries of one flat candidate list.  Writing all
+// lets only the maxima that reach the threshold leave the kernel, as entries of per-query candidate lists.  Writing all
 // 20 M maxima of a 10 M-row scan cost 0.3-0.9 ms of 5 whatever the layout.
 #include "common.hpp"
 #include "topk.hpp"
@@ -49,22 +49,20 @@ __host__ __device__ constexpr int hi_query_tile(int d) { return d > 896 ? 48 : 6
 // grid: 1-D over row slabs; LDS: 64 x d halves (query tile) + kHiWaves x 4 KiB (stages).  M[q][tile] is the maximum of
 // (x * x_scale) . (q * 2^-e_q) over the tile's rows — a per-query positive scaling of the scores, which is all a
 // per-query ranking of tiles needs; keeping the scaled value keeps it clear of fp32's subnormal range
-// EMIT = false: item i of the launch is tile i * tile_stride (a strided SAMPLE of the tiles), its maxima go to MT[i][cols].
+// EMIT = false: item i of the launch is tile i * tile_stride (a strided SAMPLE of the tiles), its maxima go to
+// MT[query][i] (leading dimension ldMT: one 4-byte store per (item, query); the threshold kernel then reads a query's row
+// with coalesced loads: 27 -> 6 us).
 // EMIT = true (the full scan, tile_stride 1): a tile's maximum leaves the kernel only if it reaches tau[query] — the kc-th
 // best maximum of the sample, a lower bound of the kc-th best overall, so every tile of a query's global top-kc passes
-// — as a packed (score, query << 26 | tile) entry of ONE flat list: staged in a wave-private LDS buffer, appended with one
-// atomic per flush (normally one per wave and launch).  ~kc x tile_stride entries per query instead of every maximum.
+// — as a packed (score, tile) entry of the query's own list, staged in a wave-private LDS buffer as (score, query << 26 |
+// tile).  ~kc x tile_stride entries per query instead of every maximum.
 struct HiEmit {
-  const float* tau;     // [nq], stride tau_stride floats
-  int tau_stride;
-  C32* cand;            // flat list
-  unsigned int* total;  // entries appended (may pass cap: the check kernel raises the flag)
-  unsigned int cap;
-  int wbuf;             // entries of the wave-private staging buffer
-  // per-query lists (round 4; qcount != nullptr): query q's entries (score, tile) go to qlist[q * qcap ..], qcount[q] counts
-  // them (it may pass qcap: dense_hi_select_kernel then raises the flag for that query).  The block bins the staged
-  // entries of its 8 waves by query in LDS and reserves its share of every list with ONE atomic per query (256 blocks x
-  // 64 atomics per scan), instead of one flat list that a second kernel had to filter per query (49 + 11 us).
+  const float* tau;  // [nq]
+  int wbuf;          // entries of the wave-private staging buffer
+  // query q's entries (score, tile) go to qlist[q * qcap ..], qcount[q] counts them (it may pass qcap:
+  // dense_hi_select_kernel then raises the flag for that query).  The block bins the staged entries of its 8 waves by query
+  // in LDS and reserves its share of every list with ONE atomic per query (256 blocks x 64 atomics per scan), instead of
+  // one flat list that a second kernel had to filter per query (49 + 11 us).
   C32* qlist;
   unsigned int* qcount;
   unsigned int qcap;
@@ -74,7 +72,7 @@ constexpr int kHiQShift = 26;  // tiles < 2^26
 
 template <int D64, bool EMIT>  // d / 64
 __device__ __forceinline__ void hi_tilemax_pass(const float* __restrict__ X, long n, const float* __restrict__ Q, int nq,
-                                                float* __restrict__ MT /*[items][cols]*/, int cols, float x_scale,
+                                                float* __restrict__ MT /*[queries][ldMT]*/, long ldMT, float x_scale,
                                                 long tile_stride, long n_items, const HiEmit& em, unsigned char* smem,
                                                 int qoff /* first query of this pass in tau / qlist / qcount */) {
   constexpr int d = D64 * 64;
@@ -86,14 +84,11 @@ __device__ __forceinline__ void hi_tilemax_pass(const float* __restrict__ X, lon
   const int r32 = lane & 31, h = lane >> 5;
 
   // grid.y > 1 (the sample of a multi-tile search): block row y works for query tile y
-  // round 4 (sample only): em.tau_stride < 0 asks for the query-major layout MT[query][ld = -tau_stride] (one 4-byte store
-  // per (item, query); the threshold kernel then reads a query's row with coalesced loads: 27 -> 6 us)
-  const long q_ld = (!EMIT && em.tau_stride < 0) ? -(long)em.tau_stride : 0;
   if (gridDim.y > 1) {
     Q += (size_t)blockIdx.y * QT * d;
     nq -= (int)blockIdx.y * QT;
     nq = nq < 0 ? 0 : (nq > QT ? QT : nq);
-    MT += q_ld ? (size_t)blockIdx.y * QT * q_ld : (size_t)blockIdx.y * n_items * cols;
+    MT += (size_t)blockIdx.y * QT * ldMT;
   }
   // The wave's first two chunks of X are requested BEFORE the query tile is converted (they do not depend on it): the
   // two memory round trips at the head of every launch overlap instead of following each other.
@@ -186,32 +181,20 @@ __device__ __forceinline__ void hi_tilemax_pass(const float* __restrict__ X, lon
   }
   __syncthreads();
 
-  float mt[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) mt[j] = 0.f;
   // EMIT: the wave's staging buffer and its fill (wave-uniform), the lane's threshold
   C32* wbuf = reinterpret_cast<C32*>(smem + QT * d * 2 + kHiWaves * kHiStageBytes) + (size_t)wave * (EMIT ? em.wbuf : 0);
   int wcnt = 0;
-  const float tau = (EMIT && lane < nq) ? em.tau[(size_t)(qoff + lane) * em.tau_stride] : 0.f;
+  const float tau = (EMIT && lane < nq) ? em.tau[qoff + lane] : 0.f;
   unsigned int* const qcount = EMIT ? em.qcount + qoff : nullptr;
   C32* const qlist = EMIT ? em.qlist + (size_t)qoff * em.qcap : nullptr;
-  const bool perq = EMIT && em.qcount != nullptr;
-  auto flush = [&]() {
-    if (perq) {  // a full buffer in the middle of a run (rare): one returning atomic per entry
-      for (int i = lane; i < wcnt; i += 64) {
-        C32 c = wbuf[i];
-        const unsigned int id = 0xffffffffu - (unsigned int)c.c;
-        const unsigned int q = id >> kHiQShift;
-        c.c = (c.c & 0xffffffff00000000ull) | (u64)(0xffffffffu - (id & ((1u << kHiQShift) - 1u)));
-        const unsigned int pos = atomicAdd(qcount + q, 1u);
-        if (pos < em.qcap) qlist[(size_t)q * em.qcap + pos] = c;
-      }
-    } else {
-      unsigned int base = 0;
-      if (lane == 0) base = atomicAdd(em.total, (unsigned int)wcnt);
-      base = (unsigned int)__builtin_amdgcn_readfirstlane((int)base);
-      for (int i = lane; i < wcnt; i += 64)
-        if (base + (unsigned int)i < em.cap) em.cand[base + i] = wbuf[i];
+  auto flush = [&]() {  // a full buffer in the middle of a run (rare): one returning atomic per entry
+    for (int i = lane; i < wcnt; i += 64) {
+      C32 c = wbuf[i];
+      const unsigned int id = 0xffffffffu - (unsigned int)c.c;
+      const unsigned int q = id >> kHiQShift;
+      c.c = (c.c & 0xffffffff00000000ull) | (u64)(0xffffffffu - (id & ((1u << kHiQShift) - 1u)));
+      const unsigned int pos = atomicAdd(qcount + q, 1u);
+      if (pos < em.qcap) qlist[(size_t)q * em.qcap + pos] = c;
     }
     wcnt = 0;
     wave_lds_fence();
@@ -279,7 +262,7 @@ __device__ __forceinline__ void hi_tilemax_pass(const float* __restrict__ X, lon
       for (int j = 1; j < 16; ++j) m = fmaxf(m, acc[b][j]);
       mq[b] = fmaxf(m, __uint_as_float(lane_xor<32>(__float_as_uint(m))));
     }
-    // In the scaled units of the lane's query (see the check kernel).
+    // In the scaled units of the lane's query (see the select kernel).
     const float mine = h ? mq[1] : mq[0];
     if (EMIT) {
       // What the maxima cost when all of them were written (timing-only build without any store: 4.38 ms per scan):
@@ -294,26 +277,11 @@ __device__ __forceinline__ void hi_tilemax_pass(const float* __restrict__ X, lon
         wcnt += __popcll(pm);
         if (wcnt + 64 > em.wbuf) flush();
       }
-    } else if (q_ld) {
-      if (lane < nq) MT[(size_t)lane * q_ld + t] = mine;
     } else {
-      // MT[item][cols], cols = the queries rounded up to 16: one contiguous row per item, the maxima of 8 items collected
-      // in registers and written as 8 back-to-back row stores.
-      const int j8 = (int)((t - t_lo) & 7);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) mt[j] = j8 == j ? mine : mt[j];
-      if (j8 == 7 || !has_next) {  // wave-uniform
-        float* dst = MT + (size_t)(t - j8) * cols + lane;
-        if (lane < cols) {
-#pragma unroll
-          for (int j = 0; j < 8; ++j)
-            if (j <= j8) dst[(size_t)j * cols] = mt[j];
-        }
-      }
+      if (lane < nq) MT[(size_t)lane * ldMT + t] = mine;
     }
   }
-  if (EMIT && !perq && wcnt > 0) flush();
-  if (perq) {  // block-uniform: every wave of the block gets here
+  if (EMIT) {  // block-uniform: every wave of the block gets here
     // the staged entries of the block's 8 waves, binned by query: rank inside the block by LDS atomics, one global atomic
     // per query with an entry reserves the block's share of that query's list
     int* bh = reinterpret_cast<int*>(smem + QT * d * 2 + kHiWaves * kHiStageBytes + (size_t)kHiWaves * em.wbuf * sizeof(C32));
@@ -358,8 +326,8 @@ __device__ __forceinline__ void hi_tilemax_pass(const float* __restrict__ X, lon
 template <int D64, bool EMIT>
 __global__ __launch_bounds__(kHiWaves * 64) void dense_hi_tilemax_kernel(const float* __restrict__ X, long n,
                                                                          const float* __restrict__ Q, int nq,
-                                                                         float* __restrict__ MT /*[items][cols]*/,
-                                                                         int cols, float x_scale, long tile_stride,
+                                                                         float* __restrict__ MT /*[queries][ldMT]*/,
+                                                                         long ldMT, float x_scale, long tile_stride,
                                                                          long n_items, HiEmit em) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int QT = hi_query_tile(D64 * 64);
@@ -371,72 +339,10 @@ __global__ __launch_bounds__(kHiWaves * 64) void dense_hi_tilemax_kernel(const f
       nq_y = nq - y * QT;
       nq_y = nq_y > QT ? QT : nq_y;
     }
-    hi_tilemax_pass<D64, EMIT>(X, n, Q + (size_t)y * QT * (D64 * 64), nq_y, MT, cols, x_scale, tile_stride, n_items, em, smem,
+    hi_tilemax_pass<D64, EMIT>(X, n, Q + (size_t)y * QT * (D64 * 64), nq_y, MT, ldMT, x_scale, tile_stride, n_items, em, smem,
                                y * QT);
     if (y + 1 < tiles) __syncthreads();  // every wave is done with this tile's queries and lists before the next is converted
   }
-}
-
-// Top-kc of every query from the flat list of the emitting scan, step 1: block (part p, query q) reads the p-th slice of
-// the list (from L2), keeps the query's entries, writes its best kc as part[p][q][kc] — the layout dense_merge_kernel
-// merges.  (score desc, tile asc) like every other top-k here.  One block per query over the whole list took 227 us.
-constexpr int kHiCandParts = 16;
-__global__ __launch_bounds__(256) void dense_hi_cand_topk_kernel(const C32* __restrict__ cand,
-                                                                 const unsigned int* __restrict__ total, unsigned int cap,
-                                                                 int nq, int kc, int tcap, C32* __restrict__ part) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  C32* lists = reinterpret_cast<C32*>(smem);
-  int* cnts = reinterpret_cast<int*>(lists + (size_t)4 * tcap);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const unsigned int qi = blockIdx.y;
-  WaveTopK<C32> tk;
-  tk.init(lists + (size_t)wave * tcap, tcap, kc);
-  unsigned int n = *total;
-  if (n > cap) n = cap;
-  const unsigned int per = (n + gridDim.x - 1) / gridDim.x;
-  const unsigned int lo = blockIdx.x * per, hi = lo + per < n ? lo + per : n;
-  // eight entries per lane are requested before the first is looked at: one load per trip was one L2 round trip per 256
-  // entries and wave (66 trips, ~40 of the kernel's 49 us)
-  constexpr int UN = 8;
-  for (unsigned int base = lo + (unsigned int)wave * 64; base < hi; base += 256 * UN) {
-    C32 e[UN];
-#pragma unroll
-    for (int u = 0; u < UN; ++u) {
-      const unsigned int i = base + 256 * u + lane;
-      e[u] = i < hi ? cand[i] : C32::pad();
-    }
-#pragma unroll
-    for (int u = 0; u < UN; ++u) {
-      C32 c = e[u];
-      const unsigned int id = 0xffffffffu - (unsigned int)c.c;
-      const bool v = !c.is_pad() && (id >> kHiQShift) == qi;
-      c.c = (c.c & 0xffffffff00000000ull) | (u64)(0xffffffffu - (id & ((1u << kHiQShift) - 1u)));
-      tk.push_lanes(c, v, lane);
-    }
-  }
-  tk.finalize(lane);
-  block_combine_topk(tk, lists, tcap, 4, wave, lane, cnts);
-  if (wave == 0) {
-    C32* out = part + ((size_t)blockIdx.x * nq + qi) * kc;
-    for (int j = lane; j < kc; j += 64) out[j] = j < tk.cnt ? tk.buf[j] : C32::pad();
-  }
-}
-
-// MT[tile][cols] -> M[q][tile] (the layout the top-k pass reads): 256 tiles per block through LDS, 1-KiB runs per query row
-constexpr int kHiTrTiles = 256;
-__host__ __device__ inline int hi_mt_cols(int nq) { return (nq + 15) & ~15; }
-__global__ __launch_bounds__(256) void dense_hi_transpose_kernel(const float* __restrict__ MT, long tiles, int nq, long ldM,
-                                                                 float* __restrict__ M, int tpb /* <= kHiTrTiles, x 64 */) {
-  __shared__ float patch[kHiTrTiles][65];
-  const long t0 = (long)blockIdx.x * tpb;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int cols = hi_mt_cols(nq);
-  for (int r = wave; r < tpb; r += 4)
-    if (t0 + r < tiles && lane < cols) patch[r][lane] = MT[(size_t)(t0 + r) * cols + lane];
-  __syncthreads();
-  for (int q = wave; q < nq; q += 4)
-    for (int r = lane; r < tpb; r += 64)
-      if (t0 + r < tiles) M[(size_t)q * ldM + t0 + r] = patch[r][q];
 }
 
 // largest |component| and largest row L2 norm of a matrix (float bits; both are non-negative)
@@ -464,73 +370,6 @@ __global__ __launch_bounds__(256) void dense_stats_kernel(const float* __restric
   }
 }
 
-// After the top-kc1 of the approximate tile maxima (vals [m][kc1], descending, in each query's scaled units): is every
-// tile that can hold one of a query's k best rows among its first kc1 - 1?  Yes if the kc1-th maximum lies below
-// T_k - 2 eps_q (T_k = the k-th largest approximate maximum): the k tiles on top have exact maxima >= T_k - eps, so
-// the k-th best score s_k >= T_k - eps, and a tile holding a row >= s_k has an approximate maximum >= T_k - 2 eps.
-// Otherwise the flag is raised: the exact first pass runs for this batch.
-//
-// eps_q, in scaled units (x' = x * 2^-ex, |x'| < 1; q' = q * 2^-eq, |q'| < 1): per component the fp16 rounding is
-// |dx'| <= 2^-11 |x'| + 2^-25 (the second term covers fp16's subnormal range), the same for q'.  Hence
-//   |x^ . q^ - x' . q'| <= (2^-10 + 2^-22) |x'| |q'| + 2^-25 (|q'|_1 + |x'|_1) (1 + 2^-11) <= ... + d 2^-24 (1 + 2^-11)
-// (the products of two fp16 values are exact in the MFMA's fp32, the accumulation of d of them adds d 2^-24 |x'| |q'|;
-// so does the accumulation inside the exact kernel this pass is compared with).  |x'| <= R * 2^-ex with R the largest
-// row norm.  The comparison only holds if the exact fp32 scores neither overflow nor sink into fp32's subnormal
-// range: |ex + eq| <= 100 is required, else the flag is raised.
-__global__ __launch_bounds__(64) void dense_hi_check_kernel(const float* __restrict__ vals, int kc1, int k,
-                                                            const float* __restrict__ Q, int d, float row_norm_max,
-                                                            float x_scale, int x_exp, long n_tiles,
-                                                            long long* __restrict__ ids,
-                                                            const unsigned int* __restrict__ total, unsigned int cap,
-                                                            int* __restrict__ flag, unsigned int* __restrict__ unresolved) {
-  const int q = blockIdx.x, lane = threadIdx.x;
-  float amax = 0.f;
-  bool nan = false;
-  for (int j = lane; j < d; j += 64) {
-    const float x = Q[(size_t)q * d + j];
-    nan |= x != x;
-    amax = fmaxf(amax, fabsf(x));
-  }
-#pragma unroll
-  for (int sft = 1; sft < 64; sft <<= 1) amax = fmaxf(amax, __shfl_xor(amax, sft));
-  nan = __any(nan);
-  int e = 0;
-  if (amax > 0.f && amax <= FLT_MAX) (void)frexpf(amax, &e);
-  const float sc = ldexpf(1.f, -e);  // the tile kernel's scale of this query
-  float ss = 0.f;
-  for (int j = lane; j < d; j += 64) {
-    const float x = Q[(size_t)q * d + j] * sc;
-    ss += x * x;
-  }
-#pragma unroll
-  for (int sft = 1; sft < 64; sft <<= 1) ss += __shfl_xor(ss, sft);
-  const float rel = 1.125f * (9.765625e-4f + 2.4e-7f + 2.f * (float)(d + 8) * 5.9604645e-8f);
-  const float eps = rel * sqrtf(ss) * (row_norm_max * x_scale) + 1.125f * (float)d * 5.9604645e-8f;
-  const bool bad = nan || !(amax <= FLT_MAX) || !(eps == eps) || e + x_exp > 100 || e + x_exp < -100;
-  const float* v = vals + (size_t)q * kc1;
-  bool raise = bad;
-  // the flat candidate list overflowed (the sample's threshold let too many maxima pass), or the query has fewer than kc1
-  // candidates (a NaN threshold: fewer than kc1 sample tiles with a real maximum): the exact chain decides
-  if (*total > cap || ids[(size_t)q * kc1 + kc1 - 1] < 0) raise = true;
-  float cut = -FLT_MAX;
-  if (!raise && n_tiles >= kc1) {  // fewer tiles than candidates: every tile is one already
-    const float Tk = v[k - 1], last = v[kc1 - 1];
-    cut = Tk - 2.f * eps;
-    raise = !(last < cut);
-  }
-  if (raise) {  // (every lane holds the same values: one lane reports)
-    if (lane == 0) {
-      if (atomicOr(flag, 1) == 0) atomicAdd(unresolved + 1, 1u);  // passes whose flag went up (the first query to raise it)
-      atomicAdd(unresolved, 1u);                                   // queries; both: amdr_dense_hi_counters
-    }
-    return;
-  }
-  // Resolved: only the tiles at or above the cut can hold one of the k best rows — the others are dropped from the
-  // query's list (the list is sorted by maximum: a suffix), ~14 of 33 stay at k = 10 and the exact pass scores those.
-  for (int j = lane; j < kc1; j += 64)
-    if (v[j] < cut) ids[(size_t)q * kc1 + j] = -1ll;
-}
-
 // d = 1 024: a 48-query tile (96 KiB; 64 queries + the stages would take all 160 KiB of LDS)
 bool dense_hi_supported(int d) { return d >= 128 && d <= 1024 && d % 128 == 0; }
 int dense_hi_max_queries(int d) { return hi_query_tile(d); }
@@ -555,20 +394,20 @@ static size_t dense_hi_lds(int d, bool emit) {
 }
 
 template <int D64, bool EMIT>
-static int launch_hi(const float* X, long n, const float* Q, int nq, int grid, float* MT, float x_scale, long tile_stride,
-                     long n_items, const HiEmit& em, hipStream_t st, int grid_y = 1) {
+static int launch_hi(const float* X, long n, const float* Q, int nq, int grid, float* MT, long ldMT, float x_scale,
+                     long tile_stride, long n_items, const HiEmit& em, hipStream_t st, int grid_y) {
   const size_t lds = dense_hi_lds(D64 * 64, EMIT);
   AMDR_HIP(hipFuncSetAttribute((const void*)dense_hi_tilemax_kernel<D64, EMIT>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                (int)lds));
   hipLaunchKernelGGL((dense_hi_tilemax_kernel<D64, EMIT>), dim3(grid, grid_y), dim3(kHiWaves * 64), lds, st, X, n, Q, nq, MT,
-                     grid_y > 1 ? 64 : hi_mt_cols(nq), x_scale, tile_stride, n_items, em);
+                     ldMT, x_scale, tile_stride, n_items, em);
   AMDR_HIP(hipGetLastError());
   return AMDR_OK;
 }
 
 template <bool EMIT>
-static int launch_hi_d(const float* X, long n, int d, const float* Q, int nq, float* MT, float x_scale, long tile_stride,
-                       const HiEmit& em, hipStream_t st, int grid_y = 1, int scan_tiles = 1) {
+static int launch_hi_d(const float* X, long n, int d, const float* Q, int nq, float* MT, long ldMT, float x_scale,
+                       long tile_stride, const HiEmit& em, hipStream_t st, int grid_y, int scan_tiles) {
   if (!dense_hi_supported(d) || nq < 1 || nq > grid_y * scan_tiles * hi_query_tile(d))
     return fail(AMDR_EINVAL, "dense (fp16 first pass): d=%d nq=%d", d, nq);
   // one persistent block per CU (the query tile fills most of its LDS)
@@ -585,82 +424,16 @@ static int launch_hi_d(const float* X, long n, int d, const float* Q, int nq, fl
   if (blocks < 1) blocks = 1;
   const int grid = (int)blocks;
   switch (d / 64) {
-    case 2: return launch_hi<2, EMIT>(X, n, Q, nq, grid, MT, x_scale, tile_stride, n_items, em, st, grid_y);
-    case 4: return launch_hi<4, EMIT>(X, n, Q, nq, grid, MT, x_scale, tile_stride, n_items, em, st, grid_y);
-    case 6: return launch_hi<6, EMIT>(X, n, Q, nq, grid, MT, x_scale, tile_stride, n_items, em, st, grid_y);
-    case 8: return launch_hi<8, EMIT>(X, n, Q, nq, grid, MT, x_scale, tile_stride, n_items, em, st, grid_y);
-    case 10: return launch_hi<10, EMIT>(X, n, Q, nq, grid, MT, x_scale, tile_stride, n_items, em, st, grid_y);
-    case 12: return launch_hi<12, EMIT>(X, n, Q, nq, grid, MT, x_scale, tile_stride, n_items, em, st, grid_y);
-    case 14: return launch_hi<14, EMIT>(X, n, Q, nq, grid, MT, x_scale, tile_stride, n_items, em, st, grid_y);
-    case 16: return launch_hi<16, EMIT>(X, n, Q, nq, grid, MT, x_scale, tile_stride, n_items, em, st, grid_y);
+    case 2: return launch_hi<2, EMIT>(X, n, Q, nq, grid, MT, ldMT, x_scale, tile_stride, n_items, em, st, grid_y);
+    case 4: return launch_hi<4, EMIT>(X, n, Q, nq, grid, MT, ldMT, x_scale, tile_stride, n_items, em, st, grid_y);
+    case 6: return launch_hi<6, EMIT>(X, n, Q, nq, grid, MT, ldMT, x_scale, tile_stride, n_items, em, st, grid_y);
+    case 8: return launch_hi<8, EMIT>(X, n, Q, nq, grid, MT, ldMT, x_scale, tile_stride, n_items, em, st, grid_y);
+    case 10: return launch_hi<10, EMIT>(X, n, Q, nq, grid, MT, ldMT, x_scale, tile_stride, n_items, em, st, grid_y);
+    case 12: return launch_hi<12, EMIT>(X, n, Q, nq, grid, MT, ldMT, x_scale, tile_stride, n_items, em, st, grid_y);
+    case 14: return launch_hi<14, EMIT>(X, n, Q, nq, grid, MT, ldMT, x_scale, tile_stride, n_items, em, st, grid_y);
+    case 16: return launch_hi<16, EMIT>(X, n, Q, nq, grid, MT, ldMT, x_scale, tile_stride, n_items, em, st, grid_y);
     default: return fail(AMDR_EINVAL, "dense (fp16 first pass): unsupported dim %d", d);
   }
-}
-
-// the sample: every s-th tile, at most ONE tile per wave of the persistent grid (256 CUs x 8 waves): the pass is bound by
-// the latency of a wave's own chunk chain, a second tile on some waves doubled it (2 442 tiles: 56 us)
-long dense_hi_sample_stride(long n) {
-  const long tiles = (n + 31) / 32;
-  const long s = (tiles + 2047) / 2048;
-  return s < 1 ? 1 : s;
-}
-long dense_hi_sample_items(long n) {
-  const long tiles = (n + 31) / 32, s = dense_hi_sample_stride(n);
-  return (tiles + s - 1) / s;
-}
-size_t dense_hi_mt_bytes(long n) { return (size_t)dense_hi_sample_items(n) * 64 * sizeof(float); }
-// entries of the flat candidate list: 4x the expected m * kc * stride, at least 64 Ki
-size_t dense_hi_cand_entries(long n, int m, int kc) {
-  size_t e = (size_t)m * kc * dense_hi_sample_stride(n) * 4 + 65536;
-  const char* env = getenv("AMDR_DENSE_HI_CAP");  // test hook: a short list overflows -> the exact chain takes over
-  if (env && atol(env) >= 64) e = (size_t)atol(env);
-  const size_t all = (size_t)((n + 31) / 32) * m;  // never more than every maximum
-  return e < all ? e : all + 64;
-}
-
-// maxima of the sampled tiles of <= 64 queries: MT[item][cols]
-int dense_hi_launch_sample(const float* X, long n, int d, const float* Q, int nq, float* MT, hipStream_t st, float x_scale) {
-  HiEmit em{};
-  return launch_hi_d<false>(X, n, d, Q, nq, MT, x_scale, dense_hi_sample_stride(n), em, st);
-}
-// the full scan: every tile maximum >= tau[q * tau_stride] into the flat list (*total zeroed by the caller)
-int dense_hi_launch_emit(const float* X, long n, int d, const float* Q, int nq, const float* tau, int tau_stride, void* cand,
-                         unsigned int* total, size_t cap, hipStream_t st, float x_scale) {
-  if ((n + 31) / 32 >= (1l << kHiQShift)) return fail(AMDR_EINVAL, "dense (fp16 first pass): too many tiles");
-  HiEmit em{tau, tau_stride, (C32*)cand, total, (unsigned int)cap, hi_wbuf_entries(d)};
-  return launch_hi_d<true>(X, n, d, Q, nq, nullptr, x_scale, 1, em, st);
-}
-size_t dense_hi_cand_part_bytes(int m, int kc) { return (size_t)kHiCandParts * m * kc * sizeof(C32); }
-// step 1 of the candidates' top-kc: part[kHiCandParts][m][kc] (dense_hi_cand_part_bytes); the caller merges the parts
-int dense_hi_launch_cand_topk(const void* cand, const unsigned int* total, size_t cap, int m, int kc, void* part,
-                              int* nparts, hipStream_t st) {
-  const int tcap = topk_cap(kc);
-  const size_t lds = (size_t)4 * tcap * sizeof(C32) + 4 * sizeof(int);
-  hipLaunchKernelGGL(dense_hi_cand_topk_kernel, dim3(kHiCandParts, m), dim3(256), lds, st, (const C32*)cand, total,
-                     (unsigned int)cap, m, kc, tcap, (C32*)part);
-  AMDR_HIP(hipGetLastError());
-  *nparts = kHiCandParts;
-  return AMDR_OK;
-}
-
-int dense_hi_launch_transpose(const float* MT, long items, int nq, long ldM, float* M, hipStream_t st) {
-  const int tpb = items >= 64 * 1024 ? kHiTrTiles : 64;  // a short sample: more, smaller blocks
-  hipLaunchKernelGGL(dense_hi_transpose_kernel, dim3((unsigned)((items + tpb - 1) / tpb)), dim3(256), 0, st, MT, items, nq, ldM,
-                     M, tpb);
-  AMDR_HIP(hipGetLastError());
-  return AMDR_OK;
-}
-
-int dense_hi_launch_check(const float* vals, int64_t* ids, int m, int kc1, int k, const float* Q, int d,
-                          float row_norm_max, float x_scale, long n_tiles, const unsigned int* total, size_t cap, int* flag,
-                          unsigned int* unresolved, hipStream_t st) {
-  int x_exp = 0;
-  (void)frexpf(x_scale, &x_exp);  // x_scale = 2^-ex = 0.5 * 2^(1 - ex)
-  x_exp = 1 - x_exp;
-  hipLaunchKernelGGL(dense_hi_check_kernel, dim3(m), dim3(64), 0, st, vals, kc1, k, Q, d, row_norm_max, x_scale, x_exp, n_tiles,
-                     (long long*)ids, total, (unsigned int)cap, flag, unresolved);
-  AMDR_HIP(hipGetLastError());
-  return AMDR_OK;
 }
 
 // max |component| and max row norm of X[row0 .. row0 + n): out2 must hold two zeroed unsigned ints
@@ -745,9 +518,22 @@ __device__ __forceinline__ int select_list(const C32* __restrict__ src, unsigned
 }
 
 // One block per query: (1) the kc best entries of the query's candidate list (score desc, tile asc — the order of every
-// top-k here); (2) the check of dense_hi_check_kernel: is every tile that can hold one of the k best rows among them?
-// (3) resolved -> the tiles at or above the cut T_k - 2 eps, ASCENDING, into list[q * kc ..], count[q]; unresolved ->
-// count[q] = 0, unres[q] = 1, the flag raised: the gated exact pass fills the query's list instead.
+// top-k here); (2) the check: is every tile that can hold one of the k best rows among them?  (3) resolved -> the tiles
+// at or above the cut T_k - 2 eps, ASCENDING, into list[q * kc ..], count[q]; unresolved -> count[q] = 0, unres[q] = 1,
+// the flag raised: the gated exact pass fills the query's list instead.
+//
+// The check, on the top-kc1 of the approximate tile maxima (descending, in the query's scaled units): is every tile that
+// can hold one of the query's k best rows among the first kc1 - 1?  Yes if the kc1-th maximum lies below T_k - 2 eps_q
+// (T_k = the k-th largest approximate maximum): the k tiles on top have exact maxima >= T_k - eps, so the k-th best
+// score s_k >= T_k - eps, and a tile holding a row >= s_k has an approximate maximum >= T_k - 2 eps.
+//
+// eps_q, in scaled units (x' = x * 2^-ex, |x'| < 1; q' = q * 2^-eq, |q'| < 1): per component the fp16 rounding is
+// |dx'| <= 2^-11 |x'| + 2^-25 (the second term covers fp16's subnormal range), the same for q'.  Hence
+//   |x^ . q^ - x' . q'| <= (2^-10 + 2^-22) |x'| |q'| + 2^-25 (|q'|_1 + |x'|_1) (1 + 2^-11) <= ... + d 2^-24 (1 + 2^-11)
+// (the products of two fp16 values are exact in the MFMA's fp32, the accumulation of d of them adds d 2^-24 |x'| |q'|;
+// so does the accumulation inside the exact kernel this pass is compared with).  |x'| <= R * 2^-ex with R the largest
+// row norm.  The comparison only holds if the exact fp32 scores neither overflow nor sink into fp32's subnormal
+// range: |ex + eq| <= 100 is required, else the flag is raised.
 __global__ __launch_bounds__(256) void dense_hi_select_kernel(const C32* __restrict__ qlist,
                                                               const unsigned int* __restrict__ qcount, unsigned int qcap,
                                                               int kc1, int k, int tcap, const float* __restrict__ Q, int d,
@@ -806,7 +592,7 @@ __global__ __launch_bounds__(256) void dense_hi_select_kernel(const C32* __restr
     block_combine_topk(tk, lists, tcap, 4, wave, lane, cnts);
     if (wave != 0) return;
   }
-  // ---- the rounding bound of this query (dense_hi_check_kernel states it)
+  // ---- the rounding bound of this query (stated above the kernel)
   float amax = 0.f;
   bool nan = false;
   for (int j = lane; j < d; j += 64) {
@@ -939,9 +725,8 @@ size_t dense_hi2_qcap(long n, int qtiles, int kc) {
 long dense_hi2_sample_ld(long n, int qtiles) { return (dense_hi2_sample_items(n, qtiles) + 63) / 64 * 64; }
 int dense_hi2_launch_sample(const float* X, long n, int d, const float* Q, int nq, int qtiles, float* MT, hipStream_t st,
                             float x_scale) {
-  HiEmit em{};
-  em.tau_stride = -(int)dense_hi2_sample_ld(n, qtiles);  // query-major maxima: MT[query][ld]
-  return launch_hi_d<false>(X, n, d, Q, nq, MT, x_scale, dense_hi2_sample_stride(n, qtiles), em, st, qtiles);
+  return launch_hi_d<false>(X, n, d, Q, nq, MT, dense_hi2_sample_ld(n, qtiles), x_scale, dense_hi2_sample_stride(n, qtiles),
+                            HiEmit{}, st, qtiles, 1);
 }
 int dense_hi2_launch_tau(const float* MT, long n, int d, int nq, int qtiles, int kc, float* tau, unsigned int* qcount,
                          int* flag, unsigned int* stats, hipStream_t st) {
@@ -956,8 +741,8 @@ int dense_hi2_launch_tau(const float* MT, long n, int d, int nq, int qtiles, int
 int dense_hi2_launch_emit(const float* X, long n, int d, const float* Q, int nq, const float* tau, void* qlist,
                           unsigned int* qcount, size_t qcap, hipStream_t st, float x_scale, int qtiles) {
   if ((n + 31) / 32 >= (1l << kHiQShift)) return fail(AMDR_EINVAL, "dense (fp16 first pass): too many tiles");
-  HiEmit em{tau, 1, nullptr, nullptr, 0u, hi_wbuf_entries(d), (C32*)qlist, qcount, (unsigned int)qcap, qtiles};
-  return launch_hi_d<true>(X, n, d, Q, nq, nullptr, x_scale, 1, em, st, 1, qtiles);
+  const HiEmit em{tau, hi_wbuf_entries(d), (C32*)qlist, qcount, (unsigned int)qcap, qtiles};
+  return launch_hi_d<true>(X, n, d, Q, nq, nullptr, 0, x_scale, 1, em, st, 1, qtiles);
 }
 int dense_hi2_launch_select(const void* qlist, const unsigned int* qcount, size_t qcap, int m, int kc, int k, const float* Q,
                             int d, float row_norm_max, float x_scale, long n_tiles, int* list, int* count, int* unres,

@@ -115,7 +115,7 @@ __global__ __launch_bounds__(WAVES * 64) void dense_mfma_scores_kernel(const flo
                                                                  float* __restrict__ S /*[queries][ldS]*/, int mode,
                                                                  const int* __restrict__ tile_list,
                                                                  const int* __restrict__ tile_count, long n_real,
-                                                                 const int* __restrict__ gate, int list_stride) {
+                                                                 const int* __restrict__ gate) {
   if (gate != nullptr && *gate == 0) return;  // a gated launch (dense_hi.hip): decided on the device, block-uniform
   // mode 0: S[query][row] for every row.
   // mode 1: S[query][tile] = MAXIMUM of the query's scores over the 32-row tile (first pass of the two-level
@@ -123,9 +123,6 @@ __global__ __launch_bounds__(WAVES * 64) void dense_mfma_scores_kernel(const flo
   // mode 2: `n` counts VIRTUAL rows, 32 per entry of tile_list; virtual tile t reads chunk tile tile_list[t]
   //         (t < *tile_count, else it is filled with -FLT_MAX) and writes S[query][32 t ..]: the exact re-scoring of
   //         the candidate tiles — same loads, same MFMA k order, the same bits as mode 0.
-  // mode 3: mode 2 PER QUERY: block row `by` is query `by` alone (the LDS tile holds it in row 0, zeros below), its
-  //         candidate tiles are tile_list[by * list_stride ..], tile_count[by] of them, its scores S[by][32 t ..]:
-  //         a query is scored against its own candidates only, not against the union of a whole batch's.
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int d = D8 * 8;
   constexpr int NCH = d / kKC;  // chunks per row: 12 / 24 / 32 (always even: d % 64 == 0)
@@ -158,27 +155,11 @@ __global__ __launch_bounds__(WAVES * 64) void dense_mfma_scores_kernel(const flo
     const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
     // with a single LDS tile (gy == 1) nothing is shared between blocks: plain order (a 10 M-row
     // scan measured 1 % slower remapped, the UCC-en launch 1.3 % faster and 3.7x less fabric traffic)
-    // (mode 3: plain order too — low bx = the head of every query's list = the live blocks; in XCD-contiguous order they
-    // would all land on the first XCDs and the blocks beyond the lists on the last)
-    const int logical = (gy == 1 || mode == 3) ? bid : (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
+    const int logical = gy == 1 ? bid : (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
     bx = logical / gy;
     by = logical - bx * gy;
   }
-  int q0 = by * 32;
-  if (mode == 3) {
-    q0 = by;
-    nq = by + 1;
-    tile_list += (size_t)by * list_stride;
-    tile_count += by;
-    // a block whose tiles all lie beyond the query's list has nothing to score: its columns can never win
-    const long lo3 = (long)bx * rows_per_block;
-    if ((lo3 >> 5) >= *tile_count) {
-      long hi3 = lo3 + rows_per_block;
-      if (hi3 > n) hi3 = n;
-      for (long c = lo3 + threadIdx.x; c < hi3; c += WAVES * 64) S[(size_t)by * ldS + c] = -FLT_MAX;
-      return;
-    }
-  }
+  const int q0 = by * 32;
 
   // ---- stage the query tile, row-major with a per-row XOR swizzle of the 16-byte slots:
   //   qs[i * d/4 + (k4 ^ (i & 15))] = Q[q0+i][4*k4 .. 4*k4+3]
@@ -221,10 +202,10 @@ __global__ __launch_bounds__(WAVES * 64) void dense_mfma_scores_kernel(const flo
   // loader role of this lane inside a 1-KiB piece: 8 rows x 8 slots
   const int lrow = lane >> 3, lslot = lane & 7;
 
-  const int n_list = (mode >= 2) ? *tile_count : 0;
+  const int n_list = mode == 2 ? *tile_count : 0;
   for (long r0 = row_lo + (long)wave * 32; r0 < row_hi; r0 += (long)WAVES * 32) {
     long src0 = r0, src_hi = row_hi;  // rows actually read
-    if (mode >= 2) {
+    if (mode == 2) {
       const int t = (int)(r0 >> 5);
       if (t >= n_list) {  // beyond the candidate list: columns that can never win
 #pragma unroll
@@ -329,7 +310,7 @@ __global__ __launch_bounds__(WAVES * 64) void dense_mfma_scores_kernel(const flo
 #pragma unroll
         for (int bj = 0; bj < 2; ++bj) {
           f32x4 v = acc[bi][bj];
-          if (mode >= 2) {  // rows past the end of the matrix inside the last tile are no candidates
+          if (mode == 2) {  // rows past the end of the matrix inside the last tile are no candidates
 #pragma unroll
             for (int r = 0; r < 4; ++r)
               if (src0 + 16 * bj + 4 * kq + r >= n_real) v[r] = -FLT_MAX;
@@ -350,10 +331,8 @@ __global__ __launch_bounds__(WAVES * 64) void scores_slab_topk_kernel(const floa
                                                                        int cap, long rows_per_slab,
                                                                        C32* __restrict__ part,
                                                                        float* __restrict__ fin_scores,
-                                                                       long long* __restrict__ fin_ids,
-                                                                       const int* __restrict__ gate) {
+                                                                       long long* __restrict__ fin_ids) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  if (gate != nullptr && *gate == 0) return;
   C32* lists = reinterpret_cast<C32*>(smem);
   int* cnts = reinterpret_cast<int*>(lists + (size_t)WAVES * cap);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -420,10 +399,8 @@ __global__ __launch_bounds__(WAVES * 64) void scores_slab_topk_kernel(const floa
 
 __global__ __launch_bounds__(64) void scores_pair_topk_kernel(const float* __restrict__ S, long ldS, long n, int nq,
                                                               int k, int cap, float* __restrict__ fin_scores,
-                                                              long long* __restrict__ fin_ids,
-                                                              const int* __restrict__ gate) {
+                                                              long long* __restrict__ fin_ids) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  if (gate != nullptr && *gate == 0) return;
   C32* buf = reinterpret_cast<C32*>(smem);  // cap entries (>= 128): staged-selector list; the pair selector uses 64
   const int lane = threadIdx.x;
   const int q = 2 * blockIdx.x + (lane >> 5);
@@ -466,17 +443,10 @@ __global__ __launch_bounds__(64) void scores_pair_topk_kernel(const float* __res
 // list without duplicates + its length.  One wave; bitonic sort in LDS (descending on id + 1, so that "none" sorts
 // last), neighbour compare, one prefix sum.
 __global__ __launch_bounds__(64) void tiles_unique_kernel(const long long* __restrict__ tile_ids, int n_in, int cap,
-                                                          int* __restrict__ list, int* __restrict__ count,
-                                                          const int* __restrict__ gate) {
+                                                          int* __restrict__ list, int* __restrict__ count) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  if (gate != nullptr && *gate == 0) return;
   C32* buf = reinterpret_cast<C32*>(smem);
   const int lane = threadIdx.x;
-  // block b sorts ids [b * n_in, (b + 1) * n_in) into list + b * n_in, count[b]: one block for the union of a batch,
-  // one per query for the per-query candidate lists behind the fp16 first pass
-  tile_ids += (size_t)blockIdx.x * n_in;
-  list += (size_t)blockIdx.x * n_in;
-  count += blockIdx.x;
   for (int i = lane; i < cap; i += 64) {
     const long long v = i < n_in ? tile_ids[i] : -1ll;
     buf[i].c = v >= 0 ? (u64)(v + 1) : 0ull;
@@ -510,10 +480,8 @@ __global__ __launch_bounds__(64) void tiles_unique_kernel(const long long* __res
 // candidates of a 64-query pass behind the fp16 first pass — more than every other step after the scan together.
 __global__ __launch_bounds__(1024) void tiles_unique_bitmap_kernel(const long long* __restrict__ tile_ids, int n_in,
                                                                    int n_tiles, int* __restrict__ list,
-                                                                   int* __restrict__ count,
-                                                                   const int* __restrict__ gate) {
+                                                                   int* __restrict__ count) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  if (gate != nullptr && *gate == 0) return;
   const int words = (n_tiles + 31) >> 5;
   unsigned int* bm = reinterpret_cast<unsigned int*>(smem);
   int* wsum = reinterpret_cast<int*>(bm + words);  // 16 wave totals
@@ -560,15 +528,9 @@ __global__ __launch_bounds__(1024) void tiles_unique_bitmap_kernel(const long lo
 // row ids (the list is ascending), so ties were already broken towards the lower id.
 __global__ __launch_bounds__(256) void tiles_remap_ids_kernel(long long* __restrict__ ids, int total,
                                                               const int* __restrict__ list,
-                                                              const int* __restrict__ count, long n_real,
-                                                              const int* __restrict__ gate, int k, int list_stride) {
-  if (gate != nullptr && *gate == 0) return;
+                                                              const int* __restrict__ count, long n_real) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i < total) {
-    if (list_stride > 0) {  // per-query lists: entry i belongs to query i / k
-      list += (size_t)(i / k) * list_stride;
-      count += i / k;
-    }
     const long long c = ids[i];
     if (c >= 0) {
       // a filler column (beyond the candidate list, or past the end of the matrix inside the last tile: score
@@ -581,48 +543,37 @@ __global__ __launch_bounds__(256) void tiles_remap_ids_kernel(long long* __restr
   }
 }
 
-int dense_tiles_unique_launch(const int64_t* tile_ids, int n_in, long n_tiles, int* list, int* count, hipStream_t st,
-                              const int* gate) {
+int dense_tiles_unique_launch(const int64_t* tile_ids, int n_in, long n_tiles, int* list, int* count, hipStream_t st) {
   if (n_tiles > 0 && n_tiles <= kUniqueBitmapTilesMax && n_in >= 512) {
     const size_t lds = (size_t)((n_tiles + 31) / 32) * 4 + 64;
     AMDR_HIP(hipFuncSetAttribute((const void*)tiles_unique_bitmap_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                  128 * 1024 + 64));
     hipLaunchKernelGGL(tiles_unique_bitmap_kernel, dim3(1), dim3(1024), lds, st, (const long long*)tile_ids, n_in,
-                       (int)n_tiles, list, count, gate);
+                       (int)n_tiles, list, count);
     AMDR_HIP(hipGetLastError());
     return AMDR_OK;
   }
   int cap = 64;
   while (cap < n_in) cap <<= 1;
   hipLaunchKernelGGL(tiles_unique_kernel, dim3(1), dim3(64), (size_t)cap * sizeof(C32), st, (const long long*)tile_ids, n_in,
-                     cap, list, count, gate);
+                     cap, list, count);
   AMDR_HIP(hipGetLastError());
   return AMDR_OK;
 }
-// one sorted duplicate-free list per query: ids [m][kc] -> list [m][kc] (ascending), count [m]
-int dense_tiles_sort_per_query_launch(const int64_t* tile_ids, int m, int kc, int* list, int* count, hipStream_t st) {
-  int cap = 64;
-  while (cap < kc) cap <<= 1;
-  hipLaunchKernelGGL(tiles_unique_kernel, dim3(m), dim3(64), (size_t)cap * sizeof(C32), st, (const long long*)tile_ids, kc, cap,
-                     list, count, (const int*)nullptr);
-  AMDR_HIP(hipGetLastError());
-  return AMDR_OK;
-}
-int dense_tiles_remap_launch(int64_t* ids, int total, const int* list, const int* count, long n_real, hipStream_t st,
-                             const int* gate, int k, int list_stride) {
+int dense_tiles_remap_launch(int64_t* ids, int total, const int* list, const int* count, long n_real, hipStream_t st) {
   hipLaunchKernelGGL(tiles_remap_ids_kernel, dim3(ceil_div(total, 256)), dim3(256), 0, st, (long long*)ids, total, list,
-                     count, n_real, gate, k, list_stride);
+                     count, n_real);
   AMDR_HIP(hipGetLastError());
   return AMDR_OK;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// Round 4: exact scores of every query's OWN candidate tiles behind the fp16 first pass, lean form.  Mode 3 of the tile
-// kernel above did this with a whole 32-query LDS tile per block (96 KiB staged, 31 of 32 MFMA columns idle, one block
+// Round 4: exact scores of every query's OWN candidate tiles behind the fp16 first pass, lean form.  A retired mode 3 of
+// the tile kernel above did this with a whole 32-query LDS tile per block (96 KiB staged, 31 of 32 MFMA columns idle, one block
 // per CU: 38 us per 64 queries).  Here a wave scores ONE (query, tile): the tile's rows stream through the wave's 4-KiB
 // stage exactly as above (same loads, same fragments), the B operand is the query's own components broadcast to all 16
 // columns, and only the two row blocks are multiplied: 16 MFMAs per chunk instead of 32, the k-steps in the SAME order —
-// acc[bj] sees the sequence the tile kernel's acc[bi][bj] sees, hence the same bits (tested against modes 0 / 2 / 3).
+// acc[bj] sees the sequence the tile kernel's acc[bi][bj] sees, hence the same bits (tested against modes 0 / 2).
 // 20 KiB of LDS per 4-wave block: the candidate tiles of a batch spread over every CU.
 // grid: (queries, ceil(max tiles per query / WPB)).
 template <int D8, int WPB>
@@ -850,7 +801,7 @@ void dense_mfma_plan(long n, int d, int nq, int k, DenseMfmaPlan* p) {
 template <int D8, int WAVES, bool NTL>
 static int launch_scores(const DenseMfmaPlan& p, const float* X, long n, const float* Q, int nq, float* S,
                          hipStream_t st, int mode, const int* tile_list, const int* tile_count, long n_real,
-                         const int* gate, int list_stride) {
+                         const int* gate) {
   // 128-160 KiB of dynamic LDS needs the opt-in.  The attribute belongs to the (function, device)
   // pair, the C ABI takes a device ordinal, and setting it is cheap: set on every launch for the
   // current device rather than remembering "done" per process.
@@ -859,20 +810,20 @@ static int launch_scores(const DenseMfmaPlan& p, const float* X, long n, const f
                                D8 * 8 * 32 * (int)sizeof(float) + WAVES * kStageBufs * kStageBytes));
   hipLaunchKernelGGL((dense_mfma_scores_kernel<D8, WAVES, NTL>), dim3(p.grid_x * p.grid_y), dim3(WAVES * 64),
                      p.lds_scores, st, X, n, Q, nq, p.rows_per_block, p.grid_x, p.grid_y, p.ld, S, mode, tile_list, tile_count,
-                     n_real, gate, list_stride);
+                     n_real, gate);
   return AMDR_OK;
 }
 
 int dense_mfma_launch_scores(const DenseMfmaPlan& p, const float* X, long n, int d, const float* Q, int nq, float* S,
                              hipStream_t st, int mode, const int* tile_list, const int* tile_count, long n_real,
-                             const int* gate, int list_stride) {
+                             const int* gate) {
   int rc = AMDR_OK;
   const bool nt = dense_stream_nontemporal(mode >= 2 ? n_real : n, d) && mode < 2;  // candidate tiles are re-read: cacheable
   switch (d) {
 #define AMDR_CASE(D)                                                          \
   case D:                                                                     \
-    rc = nt ? launch_scores<D / 8, scores_waves(D), true>(p, X, n, Q, nq, S, st, mode, tile_list, tile_count, n_real, gate, list_stride)   \
-            : launch_scores<D / 8, scores_waves(D), false>(p, X, n, Q, nq, S, st, mode, tile_list, tile_count, n_real, gate, list_stride); \
+    rc = nt ? launch_scores<D / 8, scores_waves(D), true>(p, X, n, Q, nq, S, st, mode, tile_list, tile_count, n_real, gate)   \
+            : launch_scores<D / 8, scores_waves(D), false>(p, X, n, Q, nq, S, st, mode, tile_list, tile_count, n_real, gate); \
     break;
     AMDR_CASE(64) AMDR_CASE(128) AMDR_CASE(192) AMDR_CASE(256) AMDR_CASE(320) AMDR_CASE(384)
     AMDR_CASE(448) AMDR_CASE(512) AMDR_CASE(576) AMDR_CASE(640) AMDR_CASE(704) AMDR_CASE(768)
@@ -886,23 +837,23 @@ int dense_mfma_launch_scores(const DenseMfmaPlan& p, const float* X, long n, int
 }
 
 int dense_mfma_launch_topk(const DenseMfmaPlan& p, const float* S, long n, int nq, int k, void* part,
-                           float* fin_scores, int64_t* fin_ids, hipStream_t st, const int* gate) {
+                           float* fin_scores, int64_t* fin_ids, hipStream_t st) {
   const int waves = p.rows_per_slab <= kSelectRowsMax ? 1 : kBW;
   size_t lds = (size_t)waves * p.cap * sizeof(C32) + waves * sizeof(int);
   const char* pair_env = getenv("AMDR_TOPK_PAIR");  // "0" pins one query per wave (A/B, tests)
   const bool pair_off = pair_env && pair_env[0] == '0';
   if (fin_ids && p.slabs == 1 && n <= 1024 && k <= 32 && nq >= 2 && !pair_off) {
     hipLaunchKernelGGL(scores_pair_topk_kernel, dim3((nq + 1) / 2), dim3(64), (size_t)p.cap * sizeof(C32), st, S, p.ld,
-                       n, nq, k, p.cap, fin_scores, (long long*)fin_ids, gate);
+                       n, nq, k, p.cap, fin_scores, (long long*)fin_ids);
     AMDR_HIP(hipGetLastError());
     return AMDR_OK;
   }
   if (waves == 1)
     hipLaunchKernelGGL(scores_slab_topk_kernel<1>, dim3(p.slabs, nq), dim3(64), lds, st, S, p.ld, n, nq, k, p.cap,
-                       p.rows_per_slab, (C32*)part, fin_scores, (long long*)fin_ids, gate);
+                       p.rows_per_slab, (C32*)part, fin_scores, (long long*)fin_ids);
   else
     hipLaunchKernelGGL(scores_slab_topk_kernel<kBW>, dim3(p.slabs, nq), dim3(256), lds, st, S, p.ld, n, nq, k, p.cap,
-                       p.rows_per_slab, (C32*)part, fin_scores, (long long*)fin_ids, gate);
+                       p.rows_per_slab, (C32*)part, fin_scores, (long long*)fin_ids);
   AMDR_HIP(hipGetLastError());
   return AMDR_OK;
 }

@@ -601,138 +601,12 @@ __global__ __launch_bounds__(kMsQ * 64) __attribute__((amdgpu_waves_per_eu(4, 4)
 // identical ids and scores by construction, and by test against the one-pass form.  On the UCC-en / Civil-Code-zh
 // stores 11-13 of 591 / 1 260 documents per query pass the cut at k = 10 (about 90 at k = 80).  A query with more than
 // `cap` candidates (mass near-ties) re-scores every document instead (maxsim_overflow_kernel).
-// Pass 1: the ring kernel above with 64-token tiles of the hi-only image (16-KiB stages again, half the barriers per
-// document), 16 MFMAs and 16 ds_read_b128 per tile, no fma in the epilogue.
+// Pass 1: a ring kernel like the one above with 64-token tiles of the hi-only image (16-KiB stages again, half the
+// barriers per document), no fma in the epilogue.
 __device__ __forceinline__ int ms_hi_off(int row, int slot) { return row * 256 + ((slot ^ (row & 15)) << 4); }
 
-template <int NBUF>
-__global__ __launch_bounds__(kMsQ * 64) __attribute__((amdgpu_waves_per_eu(4, 4))) void maxsim_hi_ring_kernel(
-    const unsigned char* __restrict__ img_hi, const long long* __restrict__ doc_ptr, long n_docs, int docs_per_block,
-    const float* __restrict__ Q, int nq, int q_len, float* __restrict__ approx /*[nq, n_docs]*/, float unscale_d) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char ring[];  // [NBUF][64 * 256]
-  constexpr int kStage = 64 * 256;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int r32 = lane & 31, h = lane >> 5;
-  const int qi = blockIdx.x * kMsQ + wave;
-  const bool live = qi < nq;
-  const long d0 = (long)blockIdx.y * docs_per_block;
-  long d1 = d0 + docs_per_block;
-  if (d1 > n_docs) d1 = n_docs;
-
-  ms8h qh[8], ql_unused[8];
-  float unscale;
-  ms_load_query_h(Q + (size_t)(live ? qi : 0) * q_len * kDim, q_len, live, r32, h, qh, ql_unused, unscale);
-  unscale *= unscale_d;
-
-  // DMA role: piece u (0, 1) of this wave covers stage bytes [(2 wave + u) * 1024, + 1024) = tile rows 4 (2 wave + u) .. + 3
-  // (256 B each); lane l: row + (l >> 4), PHYSICAL slot l & 15, which holds logical slot ^ (row & 15)
-  long poff[2];
-#pragma unroll
-  for (int u = 0; u < 2; ++u) {
-    const int prow = 4 * (2 * wave + u) + (lane >> 4);
-    poff[u] = (long)prow * 256 + (((lane & 15) ^ (prow & 15)) << 4);
-  }
-  int foff[8];  // fragment reads: row r32 (+ 32 for the second row block: 32 * 256 B further, same row & 15), chunk 2 s + h
-#pragma unroll
-  for (int st = 0; st < 8; ++st) foff[st] = ms_hi_off(r32, 2 * st + h);
-
-  struct Cur {
-    long doc, t_lo;
-    int len, tok0;
-  };
-  auto advance = [&](Cur& c) {
-    c.tok0 += 64;
-    if (c.tok0 >= c.len) {
-      c.doc += 1;
-      c.tok0 = 0;
-      if (c.doc < d1) {
-        c.t_lo = doc_ptr[c.doc];
-        c.len = (int)(doc_ptr[c.doc + 1] - c.t_lo);
-      }
-    }
-  };
-  auto issue = [&](const Cur& c, int stage) {
-    const unsigned char* src = img_hi + (size_t)(c.t_lo + c.tok0) * 256;  // wave-uniform
-#pragma unroll
-    for (int u = 0; u < 2; ++u)
-      __builtin_amdgcn_global_load_lds(AMDR_MS_GPTR(src + poff[u]),
-                                       AMDR_MS_LPTR(ring + stage * kStage + (2 * wave + u) * 1024), 16, 0, 0);
-  };
-  Cur prod, cur;
-  prod.doc = d0;
-  prod.t_lo = doc_ptr[d0];
-  prod.len = (int)(doc_ptr[d0 + 1] - prod.t_lo);
-  prod.tok0 = 0;
-  cur = prod;
-  int issued = 0, done = 0;
-#pragma unroll
-  for (int i = 0; i < NBUF - 1; ++i) {
-    if (prod.doc < d1) {
-      issue(prod, issued % NBUF);
-      ++issued;
-      advance(prod);
-    }
-  }
-  float best = -FLT_MAX;
-  while (cur.doc < d1) {
-    __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0); then this wave's pieces of tile `done` (see maxsim_scores_ring_kernel)
-    const int behind = issued - done - 1;
-    if (behind >= 3) {
-      __builtin_amdgcn_s_waitcnt(0x0F76);
-    } else if (behind == 2) {
-      __builtin_amdgcn_s_waitcnt(0x0F74);
-    } else if (behind == 1) {
-      __builtin_amdgcn_s_waitcnt(0x0F72);
-    } else {
-      __builtin_amdgcn_s_waitcnt(0x0F70);
-    }
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    if (prod.doc < d1) {
-      issue(prod, issued % NBUF);
-      ++issued;
-      advance(prod);
-    }
-    const unsigned char* tile = ring + (done % NBUF) * kStage;
-    const int remain = cur.len - cur.tok0;
-    ms8h a0[8], a1[8];
-#pragma unroll
-    for (int st = 0; st < 8; ++st) a0[st] = *reinterpret_cast<const ms8h*>(tile + foff[st]);
-    f32x16 c0, c1;
-#pragma unroll
-    for (int j = 0; j < 16; ++j) c0[j] = c1[j] = 0.f;
-#pragma unroll
-    for (int st = 0; st < 8; ++st) c0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0[st], qh[st], c0, 0, 0, 0);
-    if (remain > 32) {  // wave-uniform: the second 32-token row block holds tokens of this document
-#pragma unroll
-      for (int st = 0; st < 8; ++st) a1[st] = *reinterpret_cast<const ms8h*>(tile + 32 * 256 + foff[st]);
-#pragma unroll
-      for (int st = 0; st < 8; ++st) c1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1[st], qh[st], c1, 0, 0, 0);
-    }
-    if (remain < 64) {  // last tile of a document: rows >= remain are no tokens of it
-      asm volatile("" ::: "memory");
-#pragma unroll
-      for (int j = 0; j < 16; ++j) {
-        const int row = (j & 3) + 8 * (j >> 2) + 4 * h;
-        if (row >= remain) c0[j] = -FLT_MAX;
-        if (32 + row >= remain) c1[j] = -FLT_MAX;
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < 16; ++j) best = fmaxf(best, fmaxf(c0[j], c1[j]));
-    if (remain <= 64) {
-      const float total = ms_finish_h(best, r32, h, q_len, unscale);
-      if (live && lane == 0) approx[(size_t)qi * n_docs + cur.doc] = total;
-      best = -FLT_MAX;
-    }
-    ++done;
-    advance(cur);
-  }
-}
-
-// Pass 1, two queries per wave.  PMC / arithmetic on the kernel above: a wave reads the whole 16-KiB tile from LDS for 16
-// MFMAs of 32 cycles — 16 waves per CU x 16 KiB per 2 048 pipe cycles = 125 B per clock, the LDS's whole bandwidth: it
+// Pass 1, two queries per wave.  PMC / arithmetic on the first form of pass 1 (one query per wave, 16 MFMAs and 16
+// ds_read_b128 per tile; retired): a wave reads the whole 16-KiB tile from LDS for 16 MFMAs of 32 cycles — 16 waves per CU x 16 KiB per 2 048 pipe cycles = 125 B per clock, the LDS's whole bandwidth: it
 // ran at half its matrix floor (1.0 ms against 0.52).  Here a wave keeps the hi fragments of TWO queries (64 VGPRs) and
 // feeds both from one read of the tile: half the LDS bytes per MFMA.  A block = 4 waves = 8 queries (the tile is shared
 // by as many queries as before), 3 stages = 48 KiB, three blocks per CU.
@@ -754,8 +628,8 @@ __device__ __forceinline__ float ms_max3(float a, float b, float c) {  // max(a,
 template <int NBUF>
 __global__ __launch_bounds__(kMsQ2 * 64) __attribute__((amdgpu_waves_per_eu(3, NBUF == 2 ? 5 : 3))) void maxsim_hi2_ring_kernel(
     const unsigned char* __restrict__ img_hi, const long long* __restrict__ doc_ptr, long n_docs, int docs_per_block,
-    const float* __restrict__ Q, int nq, int q_len, float* __restrict__ approx /*[nq, n_docs]*/, float unscale_d,
-    const unsigned char* __restrict__ img_q /* nullable: the queries' split images (maxsim_split_queries_kernel) */,
+    int nq, int q_len, float* __restrict__ approx /*[nq, n_docs]*/, float unscale_d,
+    const unsigned char* __restrict__ img_q /* the queries' split images (maxsim_split_queries_kernel) */,
     const float* __restrict__ unscale_q) {
   extern __shared__ __attribute__((aligned(16))) unsigned char ring[];  // [NBUF][64 * 256]
   constexpr int kStage = 64 * 256;
@@ -768,22 +642,13 @@ __global__ __launch_bounds__(kMsQ2 * 64) __attribute__((amdgpu_waves_per_eu(3, N
   long d1 = d0 + docs_per_block;
   if (d1 > n_docs) d1 = n_docs;
 
+  // the fragments as maxsim_split_queries_kernel left them (a query is scored by n_docs / docs_per_block blocks: splitting
+  // it in each of them was 10-20 % of this kernel's vector instructions); a dead wave takes query 0's
   ms8h qha[8], qhb[8];
-  float unscale_a, unscale_b;
-  if (img_q) {
-    // the fragments as maxsim_split_queries_kernel left them (a query is scored by n_docs / docs_per_block blocks:
-    // splitting it in each of them was 10-20 % of this kernel's vector instructions); a dead wave takes query 0's
-    ms_load_query_img_hi(img_q, live_a ? qa : 0, r32, h, qha);
-    ms_load_query_img_hi(img_q, live_b ? qb : 0, r32, h, qhb);
-    unscale_a = unscale_q[live_a ? qa : 0];
-    unscale_b = unscale_q[live_b ? qb : 0];
-  } else {
-    ms8h lo_unused[8];
-    ms_load_query_h(Q + (size_t)(live_a ? qa : 0) * q_len * kDim, q_len, live_a, r32, h, qha, lo_unused, unscale_a);
-    ms_load_query_h(Q + (size_t)(live_b ? qb : 0) * q_len * kDim, q_len, live_b, r32, h, qhb, lo_unused, unscale_b);
-  }
-  unscale_a *= unscale_d;
-  unscale_b *= unscale_d;
+  ms_load_query_img_hi(img_q, live_a ? qa : 0, r32, h, qha);
+  ms_load_query_img_hi(img_q, live_b ? qb : 0, r32, h, qhb);
+  const float unscale_a = unscale_q[live_a ? qa : 0] * unscale_d;
+  const float unscale_b = unscale_q[live_b ? qb : 0] * unscale_d;
 
   // DMA role: pieces 4 wave .. 4 wave + 3 of the tile's 16 (1 KiB = 4 rows of 256 B each); lane l: row + (l >> 4),
   // PHYSICAL slot l & 15, which holds logical slot ^ (row & 15)
@@ -881,7 +746,7 @@ __global__ __launch_bounds__(kMsQ2 * 64) __attribute__((amdgpu_waves_per_eu(3, N
       // tried and dropped: the fragment reads of the NEXT 32-token row block issued before the current block's 32 MFMAs
       // (the compiler's order here is two reads, s_waitcnt lgkmcnt(0), four MFMAs, eight times per tile) with a second
       // fragment set — 64 more VGPRs, two waves per SIMD, four ring stages: 1.136 against 1.101 ms per hybrid step, slower
-      // at every block size (scripts/sweep_maxsim_docs.sh).  Neither the reads per MFMA nor their latency is what keeps
+      // at every block size.  Neither the reads per MFMA nor their latency is what keeps
       // the matrix pipe at half duty.
 #pragma unroll
       for (int j = 0; j < 16; j += 2) {
@@ -907,11 +772,11 @@ __global__ __launch_bounds__(kMsQ2 * 64) __attribute__((amdgpu_waves_per_eu(3, N
 // zero) and stores its power-of-two unscale — the scale rule and ms_split of ms_load_query_h: identical fragments.  The
 // re-scoring pass takes a query's fragments for every (document, query) item it serves, 15 k times per UCC-en batch:
 // splitting them in the scoring wave each time cost ~500 vector instructions per item and wave.
-// `norm_sum` (nullable): the sum of the token rows' Euclidean norms, which the candidate margin of the two-pass top-k is
-// built on (maxsim_select_kernel) — the rows are in this wave's registers anyway.
+// `norm_sum`: the sum of the token rows' Euclidean norms, which the candidate margin of the two-pass top-k is built on
+// (maxsim_select_kernel) — the rows are in this wave's registers anyway.
 __device__ __forceinline__ void ms_split_query_wave(const float* __restrict__ Qq, int q_len, int lane,
                                                     unsigned char* __restrict__ img, float* __restrict__ unscale,
-                                                    float* __restrict__ norm_sum = nullptr) {
+                                                    float* __restrict__ norm_sum) {
   // one pass over the query: lane holds (row, group of 8 components) g = lane + 64 it — 16 lanes per row, 4 rows per step
   float x[8][8];
   float m = 0.f, nsum = 0.f;
@@ -946,7 +811,7 @@ __device__ __forceinline__ void ms_split_query_wave(const float* __restrict__ Qq
   const float sc = ldexpf(1.f, -e);
   if (lane == 0) {
     *unscale = ldexpf(1.f, e);
-    if (norm_sum) *norm_sum = nsum;
+    *norm_sum = nsum;
   }
 #pragma unroll
   for (int it = 0; it < 8; ++it) {
@@ -971,18 +836,14 @@ __global__ __launch_bounds__(256) void maxsim_split_queries_kernel(const float* 
 }
 
 // Between the passes, one wave per query: T = the k-th best first-pass score, eps from the query's token norms, the
-// list of documents with a first-pass score >= T - 2 eps (ascending ids, at most cap; more -> overflow), and the
-// re-scored row initialised to "not a candidate".
-__global__ __launch_bounds__(64) void maxsim_select_kernel(const float* __restrict__ approx, long n_docs,
-                                                           const float* __restrict__ Q, int q_len, int k, int cap_sel,
-                                                           float d_norm_max, float unscale_d, int cap,
-                                                           float* __restrict__ exact /*[nq, n_docs]*/,
+// list of documents with a first-pass score >= T - 2 eps (ascending ids, at most cap; more -> overflow).
+__global__ __launch_bounds__(64) void maxsim_select_kernel(const float* __restrict__ approx, long n_docs, int q_len, int k,
+                                                           int cap_sel, float d_norm_max, float unscale_d, int cap,
                                                            int* __restrict__ cand /*[nq, cap]*/, int* __restrict__ cnt,
                                                            int* __restrict__ overflow, int* __restrict__ dcnt,
                                                            int* __restrict__ dlist /*[n_docs][nq]*/, int nq,
-                                                           const float* __restrict__ norm_sum /* nullable: with */,
-                                                           const float* __restrict__ unscale_in /* the split images */,
-                                                           int init_exact) {
+                                                           const float* __restrict__ norm_sum /* with the split images */,
+                                                           const float* __restrict__ unscale_in /* (split_queries) */) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   C32* buf = reinterpret_cast<C32*>(smem);
   const int lane = threadIdx.x & 63, q = blockIdx.x;
@@ -1013,28 +874,8 @@ __global__ __launch_bounds__(64) void maxsim_select_kernel(const float* __restri
   wave_lds_fence();
   const float T = tk.cnt >= k ? tk.buf[k - 1].score() : -FLT_MAX;  // fewer than k documents: every one is a candidate
   wave_lds_fence();
-  // eps: token norms and the query's power-of-two scale, as the scoring kernels take it
-  float nsum = 0.f, unscale_q;
-  if (norm_sum) {  // left by maxsim_split_queries_kernel
-    nsum = norm_sum[q];
-    unscale_q = unscale_in[q];
-  } else {
-    const float* Qq = Q + (size_t)q * q_len * kDim;
-    float amax = 0.f;
-    for (int i = 0; i < q_len; ++i) {
-      const float a = Qq[i * kDim + lane], b = Qq[i * kDim + 64 + lane];
-      float ss = a * a + b * b;
-      amax = fmaxf(amax, fmaxf(fabsf(a), fabsf(b)));
-#pragma unroll
-      for (int sft = 1; sft < 64; sft <<= 1) ss += __shfl_xor(ss, sft);
-      nsum += sqrtf(ss);
-    }
-#pragma unroll
-    for (int sft = 1; sft < 64; sft <<= 1) amax = fmaxf(amax, __shfl_xor(amax, sft));
-    int e = 0;
-    if (amax > 0.f && amax <= FLT_MAX) (void)frexpf(amax, &e);
-    unscale_q = ldexpf(1.f, e);
-  }
+  // eps: token norms and the query's power-of-two scale, as the scoring kernels take it (maxsim_split_queries_kernel)
+  const float nsum = norm_sum[q], unscale_q = unscale_in[q];
   const float eps = 1.5f * 9.765625e-4f * nsum * d_norm_max * 1.0001f +
                     (float)q_len * 256.f * 2.98023224e-8f * unscale_q * unscale_d;  // + operands in fp16's subnormal range
   const float thr = (T == -FLT_MAX) ? -FLT_MAX : T - 2.f * eps;
@@ -1044,7 +885,6 @@ __global__ __launch_bounds__(64) void maxsim_select_kernel(const float* __restri
     const bool v = d < n_docs;
     const float a = v ? row[d] : 0.f;
     const bool pass = v && (a >= thr || thr == -FLT_MAX);
-    if (v && init_exact) exact[(size_t)q * n_docs + d] = -FLT_MAX;  // (only rowscores_topk_kernel reads whole rows)
     const unsigned long long m = __ballot(pass);
     const int at = n + __popcll(lane ? (m & (~0ull >> (64 - lane))) : 0ull);
     if (pass && at < cap) cand[(size_t)q * cap + at] = (int)d;
@@ -1054,7 +894,7 @@ __global__ __launch_bounds__(64) void maxsim_select_kernel(const float* __restri
     overflow[q] = n > cap ? 1 : 0;
     cnt[q] = n > cap ? 0 : n;
   }
-  if (dcnt != nullptr && n <= cap) {
+  if (n <= cap) {
     // round 4: the re-scoring pass walks the pairs BY DOCUMENT — the query joins the list of each of its candidates
     // (row d of dlist, one slot per query at most: no offsets to compute, no second pass to fill them)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's own list, just written
@@ -1105,72 +945,6 @@ __device__ __forceinline__ float ms_exact_doc_lds(const unsigned char* __restric
     ms_tile_h(ah, al, qh, ql, h, len - tok0, best);
   }
   return ms_finish_h(best, r32, h, q_len, unscale);
-}
-
-// exclusive prefix sum of the candidate counts: off[q] = first item of query q in the flat work list, off[nq] = items
-__global__ __launch_bounds__(256) void maxsim_offsets_kernel(const int* __restrict__ cnt, int nq, int* __restrict__ off) {
-  __shared__ int part[256];
-  int carry = 0;
-  for (int base = 0; base < nq; base += 256) {
-    const int i = base + threadIdx.x;
-    const int v = i < nq ? cnt[i] : 0;
-    part[threadIdx.x] = v;
-    __syncthreads();
-    for (int sft = 1; sft < 256; sft <<= 1) {
-      const int o = threadIdx.x >= sft ? part[threadIdx.x - sft] : 0;
-      __syncthreads();
-      part[threadIdx.x] += o;
-      __syncthreads();
-    }
-    if (i < nq) off[i] = carry + part[threadIdx.x] - v;
-    carry += part[255];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) off[nq] = carry;
-}
-
-// Pass 2: the candidate (query, document) pairs as ONE flat work list cut into equal contiguous shares, one per wave of
-// a grid that just fills the chip (a grid of (slot, query) blocks was mostly empty blocks queueing for LDS: 0.76 ms for
-// 15 k pairs).  A share's items mostly belong to one query: its fragments are loaded once per query change.
-__global__ __launch_bounds__(256) void maxsim_rescore_kernel(const unsigned char* __restrict__ img,
-                                                             const long long* __restrict__ doc_ptr, long n_docs,
-                                                             const float* __restrict__ Q, int nq, int q_len,
-                                                             float unscale_d, const int* __restrict__ cand,
-                                                             const int* __restrict__ off, int cap,
-                                                             float* __restrict__ exact) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char stages[];
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int total = off[nq];
-  const int G = gridDim.x * kMsWaves, g = blockIdx.x * kMsWaves + wave;
-  const int share = (total + G - 1) / G;
-  const int lo = g * share;
-  int hi = lo + share;
-  if (hi > total) hi = total;
-  if (lo >= hi) return;  // whole wave
-  int q = 0;
-  {  // the query of item lo: the last q with off[q] <= lo
-    int a = 0, b = nq;
-    while (b - a > 1) {
-      const int m = (a + b) >> 1;
-      if (off[m] <= lo) a = m; else b = m;
-    }
-    q = a;
-  }
-  ms8h qh[8], ql[8];
-  float unscale = 1.f;
-  int q_loaded = -1;
-  for (int item = lo; item < hi; ++item) {
-    while (item >= off[q + 1]) ++q;  // queries without candidates are skipped
-    if (q != q_loaded) {
-      ms_load_query_h(Q + (size_t)q * q_len * kDim, q_len, true, lane & 31, lane >> 5, qh, ql, unscale);
-      unscale *= unscale_d;
-      q_loaded = q;
-    }
-    const long doc = cand[(size_t)q * cap + (item - off[q])];
-    const float total_s = ms_exact_doc_lds(img, doc_ptr, doc, qh, ql, lane, q_len, unscale, stages + wave * 16384);
-    if (lane == 0) exact[(size_t)q * n_docs + doc] = total_s;
-  }
 }
 
 __device__ __forceinline__ void ms_load_query_img(const unsigned char* __restrict__ img_q, int qi, int r32, int h,
@@ -1492,7 +1266,7 @@ size_t ms_workspace_bytes(const MsShape& s, int nq, int k, bool want_topk) {
   if (!ms_two_pass(s, nq, k, want_topk)) return rows;
   // three row blocks (first-pass scores, re-scored scores, the per-document query lists of the re-scoring pass) + the
   // candidate lists [nq * cap], counters, the item table (<= n_docs + pairs / 8 descriptors of 32 bytes); an upper bound
-  return 3 * rows + ((size_t)nq * ms_cand_cap(k) + 3 * (size_t)nq + 1) * sizeof(int) + 256 +  // (3rd: dlist [n_docs][nq])
+  return 3 * rows + ((size_t)nq * ms_cand_cap(k) + 2 * (size_t)nq) * sizeof(int) + 256 +  // (3rd: dlist [n_docs][nq])
          ((size_t)nq * ms_cand_cap(k) + 4 * (size_t)s.n_docs + 8) * sizeof(int) +
          ((size_t)s.n_docs + (size_t)nq * ms_cand_cap(k) / kMsQ + 8) * sizeof(MsItem) +
          (size_t)nq * (32 * 512 + 2 * sizeof(float)) + 512;  // + the split image of the queries, their scales, norm sums
@@ -1529,128 +1303,68 @@ int ms_run(amdr_maxsim* h, const float* Q_dev, int nq, int q_len, int k, float* 
     int* cnt = cand + (size_t)nq * cap;
     int* ovf = cnt + nq;
     const int cap_sel = topk_cap(k);
-    int* off = ovf + nq;                      // [nq + 1] (round-3 form)
-    int* dcnt = off + nq + 1;                 // round 4: [n_docs] candidates per document
+    int* dcnt = ovf + nq;                     // [n_docs] candidates per document
     int* ioff = dcnt + h->n_docs;             // [1] items of the re-scoring pass
     MsItem* items = reinterpret_cast<MsItem*>(((uintptr_t)(ioff + 1) + 31) & ~(uintptr_t)31);
     unsigned char* img_q = reinterpret_cast<unsigned char*>(
         ((uintptr_t)(items + h->n_docs + (size_t)nq * cap / kMsQ + 8) + 255) & ~(uintptr_t)255);
     float* unscale_q = reinterpret_cast<float*>(img_q + (size_t)nq * 32 * 512);
     float* nsum_q = unscale_q + nq;
-    const char* rs = getenv("AMDR_MAXSIM_RESCORE");  // "0": one wave per pair (the round-3 form; A/B, tests)
-    const bool by_doc = !(rs && rs[0] == '0');
-    const char* fc = getenv("AMDR_MAXSIM_FINAL");  // "0": rank the whole re-scored rows (rowscores_topk_kernel; A/B, tests)
-    const bool final_cand = !(fc && fc[0] == '0');
     // documents per block of pass 1 (round 4, scripts/ab_maxsim_env.py — variants interleaved in one process, channel ms):
     // UCC-en 16 / 24 / 29 / 32: 0.891 / 0.884 / 0.897 / 0.903, Civil-Code-zh 16 / 24 / 32 / 48 / 64: 1.161 / 1.161 / 1.163 /
     // 1.101* / 1.095* (*another box: 32 = 1.090).  Whole rounds of the chip's block slots (29 documents: 3 066 blocks = 3.99
-    // rounds of 768, against 3.6 at 32) bought nothing, nor did 2 or 4 ring stages (AMDR_MAXSIM_RING1; 5 or 2 blocks per
-    // CU instead of 3: -0.5 % / +2 %): the pass sits on a plateau that scheduling does not move.
+    // rounds of 768, against 3.6 at 32) bought nothing, nor did 2 or 4 ring stages (5 or 2 blocks per CU instead of 3:
+    // -0.5 % / +2 %): the pass sits on a plateau that scheduling does not move.
     const char* dpb = getenv("AMDR_MAXSIM_DOCS");
     long docs = dpb && atoi(dpb) > 0 ? atoi(dpb) : 24;
     while (ceil_div(h->n_docs, docs) > 65535) docs *= 2;
-    if (by_doc)
-      hipLaunchKernelGGL(maxsim_split_queries_kernel, dim3(ceil_div(nq, 4)), dim3(256), 0, st, Q_dev, nq, q_len, img_q,
-                         unscale_q, nsum_q);
-    const char* h2 = getenv("AMDR_MAXSIM_HI2");  // "0": one query per wave (A/B)
-    if (h2 && h2[0] == '0') {
-      AMDR_HIP(hipFuncSetAttribute((const void*)maxsim_hi_ring_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   4 * 16384));
-      hipLaunchKernelGGL((maxsim_hi_ring_kernel<4>), dim3(ceil_div(nq, kMsQ), ceil_div(h->n_docs, docs)), dim3(kMsQ * 64),
-                         4 * 16384, st, h->img_hi, h->doc_ptr, (long)h->n_docs, (int)docs, Q_dev, nq, q_len, approx,
-                         unscale_d);
-    } else {
-      const char* ps = getenv("AMDR_MAXSIM_PRESPLIT");  // "0": every block of pass 1 splits its queries itself (A/B)
-      const bool presplit = by_doc && !(ps && ps[0] == '0');
-      const char* r1 = getenv("AMDR_MAXSIM_RING1");  // LDS stages of pass 1 (2 / 3 / 4: 5 / 3 / 2 blocks per CU)
-      const int nb1 = r1 ? atoi(r1) : 3;
-#define AMDR_MS_PASS1(NB)                                                                                              \
-  do {                                                                                                                 \
-    AMDR_HIP(hipFuncSetAttribute((const void*)maxsim_hi2_ring_kernel<NB>, hipFuncAttributeMaxDynamicSharedMemorySize,  \
-                                 NB * 16384));                                                                         \
-    hipLaunchKernelGGL((maxsim_hi2_ring_kernel<NB>), dim3(ceil_div(nq, 2 * kMsQ2), ceil_div(h->n_docs, docs)),        \
-                       dim3(kMsQ2 * 64), NB * 16384, st, h->img_hi, h->doc_ptr, (long)h->n_docs, (int)docs, Q_dev, nq, \
-                       q_len, approx, unscale_d, presplit ? img_q : (const unsigned char*)nullptr, unscale_q);         \
-  } while (0)
-      if (nb1 == 2) AMDR_MS_PASS1(2);
-      else if (nb1 == 4) AMDR_MS_PASS1(4);
-      else AMDR_MS_PASS1(3);
-#undef AMDR_MS_PASS1
-    }
-    if (by_doc) AMDR_HIP(hipMemsetAsync(dcnt, 0, (size_t)h->n_docs * sizeof(int), st));
+    hipLaunchKernelGGL(maxsim_split_queries_kernel, dim3(ceil_div(nq, 4)), dim3(256), 0, st, Q_dev, nq, q_len, img_q,
+                       unscale_q, nsum_q);
+    constexpr int kRing1 = 3;  // LDS stages of pass 1: three blocks per CU
+    AMDR_HIP(hipFuncSetAttribute((const void*)maxsim_hi2_ring_kernel<kRing1>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                 kRing1 * 16384));
+    hipLaunchKernelGGL((maxsim_hi2_ring_kernel<kRing1>), dim3(ceil_div(nq, 2 * kMsQ2), ceil_div(h->n_docs, docs)),
+                       dim3(kMsQ2 * 64), kRing1 * 16384, st, h->img_hi, h->doc_ptr, (long)h->n_docs, (int)docs, nq, q_len,
+                       approx, unscale_d, img_q, unscale_q);
+    AMDR_HIP(hipMemsetAsync(dcnt, 0, (size_t)h->n_docs * sizeof(int), st));
     hipLaunchKernelGGL(maxsim_select_kernel, dim3(nq), dim3(64), (size_t)cap_sel * sizeof(C32), st, approx,
-                       (long)h->n_docs, Q_dev, q_len, k, cap_sel, h->d_norm_max, unscale_d, cap, exact, cand, cnt, ovf,
-                       by_doc ? dcnt : (int*)nullptr, dlist, nq, by_doc ? nsum_q : (const float*)nullptr, unscale_q,
-                       final_cand ? 0 : 1);
+                       (long)h->n_docs, q_len, k, cap_sel, h->d_norm_max, unscale_d, cap, cand, cnt, ovf, dcnt, dlist, nq,
+                       nsum_q, unscale_q);
     constexpr int kPairLds = kMsWaves * 16384;
     AMDR_HIP(hipFuncSetAttribute((const void*)maxsim_overflow_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kPairLds));
     int dev = 0, cus = 256;
     AMDR_HIP(hipGetDevice(&dev));
     AMDR_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    if (by_doc) {
-      hipLaunchKernelGGL(maxsim_items_kernel, dim3(1), dim3(256), 0, st, dcnt, (long)h->n_docs, h->doc_ptr, ioff, items);
-      const char* e_rr = getenv("AMDR_MAXSIM_RESCORE_RING");
-      const char* e_rb = getenv("AMDR_MAXSIM_RESCORE_BLOCKS");
-      // Ring depth and blocks per CU of the re-scoring pass (same process, interleaved, 1 168 UCC-en queries, whole channel):
-      // 4 stages x 2 blocks per CU (64 KB of LDS each: 4 waves per SIMD) 0.8916 ms; 3 x 3: 0.8903; 2 x 4 (8 waves per SIMD):
-      // 0.8837; 2 stages with 6 / 8 blocks per CU in the grid (the items then outnumber the blocks by little: the hardware
-      // deals them) 0.8815 / 0.8793.  What the deeper ring bought inside a block, twice the resident waves buy across
-      // blocks: the per-item latencies (descriptor -> query list -> query fragments -> first tile) overlap another
-      // block's products.  Civil-Code-zh: 1.1017 -> 1.0947.
-      const int rr = e_rr ? atoi(e_rr) : 2;
-      const int rb = e_rb ? atoi(e_rb) : (rr == 3 ? 3 : rr == 2 ? 8 : 2);
-#define AMDR_MS_RESCORE(NB)                                                                                              \
-  do {                                                                                                                   \
-    AMDR_HIP(hipFuncSetAttribute((const void*)maxsim_rescore_ring_kernel<NB>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                 NB * 16384));                                                                           \
-    hipLaunchKernelGGL((maxsim_rescore_ring_kernel<NB>), dim3((rb >= 1 && rb <= 8 ? rb : 2) * cus), dim3(kMsQ * 64),     \
-                       NB * 16384, st, h->img, (long)h->n_docs, img_q, unscale_q, q_len, unscale_d, items, ioff, dlist,  \
-                       nq, exact);                                                                                       \
-  } while (0)
-      if (rr == 3) AMDR_MS_RESCORE(3);
-      else if (rr == 2) AMDR_MS_RESCORE(2);
-      else AMDR_MS_RESCORE(4);
-#undef AMDR_MS_RESCORE
-    } else {
-      AMDR_HIP(hipFuncSetAttribute((const void*)maxsim_rescore_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kPairLds));
-      hipLaunchKernelGGL(maxsim_offsets_kernel, dim3(1), dim3(256), 0, st, cnt, nq, off);
-      hipLaunchKernelGGL(maxsim_rescore_kernel, dim3(2 * cus), dim3(256), kPairLds, st, h->img, h->doc_ptr, (long)h->n_docs,
-                         Q_dev, nq, q_len, unscale_d, cand, off, cap, exact);
-    }
+    hipLaunchKernelGGL(maxsim_items_kernel, dim3(1), dim3(256), 0, st, dcnt, (long)h->n_docs, h->doc_ptr, ioff, items);
+    // Ring depth and blocks per CU of the re-scoring pass (same process, interleaved, 1 168 UCC-en queries, whole channel):
+    // 4 stages x 2 blocks per CU (64 KB of LDS each: 4 waves per SIMD) 0.8916 ms; 3 x 3: 0.8903; 2 x 4 (8 waves per SIMD):
+    // 0.8837; 2 stages with 6 / 8 blocks per CU in the grid (the items then outnumber the blocks by little: the hardware
+    // deals them) 0.8815 / 0.8793.  What the deeper ring bought inside a block, twice the resident waves buy across
+    // blocks: the per-item latencies (descriptor -> query list -> query fragments -> first tile) overlap another
+    // block's products.  Civil-Code-zh: 1.1017 -> 1.0947.
+    constexpr int kRing2 = 2, kBlocks2 = 8;
+    AMDR_HIP(hipFuncSetAttribute((const void*)maxsim_rescore_ring_kernel<kRing2>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                 kRing2 * 16384));
+    hipLaunchKernelGGL((maxsim_rescore_ring_kernel<kRing2>), dim3(kBlocks2 * cus), dim3(kMsQ * 64), kRing2 * 16384, st, h->img,
+                       (long)h->n_docs, img_q, unscale_q, q_len, unscale_d, items, ioff, dlist, nq, exact);
     hipLaunchKernelGGL(maxsim_overflow_kernel, dim3(nq), dim3(256), kPairLds, st, h->img, h->doc_ptr, (long)h->n_docs,
                        Q_dev, q_len, unscale_d, ovf, exact);
     AMDR_HIP(hipGetLastError());
-    if (final_cand) {
-      hipLaunchKernelGGL(maxsim_final_topk_kernel, dim3(ceil_div(nq, 4)), dim3(256), (size_t)4 * cap_sel * sizeof(C32), st,
-                         exact, (long)h->n_docs, nq, cand, cnt, ovf, cap, k, cap_sel, scores_dev, (long long*)ids_dev);
-      AMDR_HIP(hipGetLastError());
-      return AMDR_OK;
-    }
-    full_dev = exact;  // the final top-k ranks the re-scored rows
-  } else if (batch && half) {
-    const char* rg = getenv("AMDR_MAXSIM_RING");  // LDS stages (2 / 3 / 4 / 6; measured best: 4)
-    const int nbuf = rg ? atoi(rg) : 4;
+    hipLaunchKernelGGL(maxsim_final_topk_kernel, dim3(ceil_div(nq, 4)), dim3(256), (size_t)4 * cap_sel * sizeof(C32), st,
+                       exact, (long)h->n_docs, nq, cand, cnt, ovf, cap, k, cap_sel, scores_dev, (long long*)ids_dev);
+    AMDR_HIP(hipGetLastError());
+    return AMDR_OK;
+  }
+  if (batch && half) {
+    constexpr int kRing = 4;  // LDS stages (2 / 3 / 4 / 6 measured; best: 4)
     const char* dpb = getenv("AMDR_MAXSIM_DOCS");  // documents per block (measured best: 16)
     long docs = dpb && atoi(dpb) > 0 ? atoi(dpb) : 16;
     while (ceil_div(h->n_docs, docs) > 65535) docs *= 2;
-    dim3 grid(ceil_div(nq, kMsQ), ceil_div(h->n_docs, docs));
-#define AMDR_MS_RING(NB)                                                                                             \
-  {                                                                                                                  \
-    AMDR_HIP(hipFuncSetAttribute((const void*)maxsim_scores_ring_kernel<NB>,                                         \
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, NB * 16384));                           \
-    hipLaunchKernelGGL((maxsim_scores_ring_kernel<NB>), grid, dim3(kMsQ * 64), NB * 16384, st, h->img, h->doc_ptr,    \
-                       (long)h->n_docs, (int)docs, Q_dev, nq, q_len, full_dev, unscale_d);                           \
-  }
-    if (nbuf == 2) {
-      AMDR_MS_RING(2)
-    } else if (nbuf == 3) {
-      AMDR_MS_RING(3)
-    } else if (nbuf == 6) {
-      AMDR_MS_RING(6)
-    } else {
-      AMDR_MS_RING(4)
-    }
-#undef AMDR_MS_RING
+    AMDR_HIP(hipFuncSetAttribute((const void*)maxsim_scores_ring_kernel<kRing>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                 kRing * 16384));
+    hipLaunchKernelGGL((maxsim_scores_ring_kernel<kRing>), dim3(ceil_div(nq, kMsQ), ceil_div(h->n_docs, docs)),
+                       dim3(kMsQ * 64), kRing * 16384, st, h->img, h->doc_ptr, (long)h->n_docs, (int)docs, Q_dev, nq, q_len,
+                       full_dev, unscale_d);
   } else if (batch && ceil_div(h->n_docs, kMsDocs) <= 65535) {
     dim3 grid(ceil_div(nq, kMsQ), ceil_div(h->n_docs, kMsDocs));
     hipLaunchKernelGGL(maxsim_scores_blocked_kernel, grid, dim3(kMsQ * 64), 0, st, h->D, h->doc_ptr, (long)h->n_docs,
@@ -1764,20 +1478,17 @@ int amdr_maxsim_ndocs(const amdr_maxsim_t* h, int64_t* n) {
 int amdr_maxsim_plan_info(const amdr_maxsim_t* h, int32_t nq, char* buf, int32_t buf_len) {
   AMDR_REQUIRE(h && buf && buf_len > 0, "maxsim_plan_info: null");
   AMDR_REQUIRE(nq >= 1, "maxsim_plan_info: nq=%d", nq);
-  const char* pin = getenv("AMDR_MAXSIM_F16X3");
-  const bool half = h->img != nullptr && !(pin && pin[0] == '0');
+  const MsShape s = ms_shape(h);
+  const bool half = ms_half(s);
   const bool batch = nq >= kMsQ;
-  if (half && batch && h->img_hi && !(getenv("AMDR_MAXSIM_TWOPASS") && getenv("AMDR_MAXSIM_TWOPASS")[0] == '0'))
+  // the ABI has no k: the two-pass form as ms_run takes it at the shallowest depth
+  if (ms_two_pass(s, nq, 1, true))
     snprintf(buf, buf_len,
              "maxsim_hi2_ring_kernel split-fp16 two-pass top-k (k <= n_docs / 4): maxsim_split_queries_kernel + pass 1 hi "
-             "parts only (1 x v_mfma_f32_32x32x16_f16 per block, two queries per wave) + maxsim_select_kernel + %s "
-             "(hi + lo/2048, 3 MFMAs per block, candidates only) + %s; full score rows: maxsim_scores_ring_kernel",
-             (getenv("AMDR_MAXSIM_RESCORE") && getenv("AMDR_MAXSIM_RESCORE")[0] == '0')
-                 ? "maxsim_rescore_kernel (one wave per candidate pair)"
-                 : "maxsim_rescore_ring_kernel<2> (pairs grouped by document: a block = one document x 8 of its queries; 8 blocks per CU)",
-             (getenv("AMDR_MAXSIM_FINAL") && getenv("AMDR_MAXSIM_FINAL")[0] == '0')
-                 ? "rowscores_topk_kernel"
-                 : "maxsim_final_topk_kernel (the candidates only)");
+             "parts only (1 x v_mfma_f32_32x32x16_f16 per block, two queries per wave) + maxsim_select_kernel + "
+             "maxsim_rescore_ring_kernel<2> (pairs grouped by document: a block = one document x 8 of its queries; 8 blocks "
+             "per CU) (hi + lo/2048, 3 MFMAs per block, candidates only) + maxsim_final_topk_kernel (the candidates only); "
+             "full score rows: maxsim_scores_ring_kernel");
   else if (half)
     snprintf(buf, buf_len, "%s split-fp16 (hi + lo/2048, 3 x v_mfma_f32_32x32x16_f16 per block) + rowscores_topk_kernel",
              batch ? "maxsim_scores_ring_kernel" : "maxsim_scores_h_kernel");

@@ -30,4 +30,3 @@ for m in (64, 128, 192, 256):
     c = run(f"one   nocap   m={m}", Q[:m])
     print("   equal to exact:", np.array_equal(a, ref[:m]), np.array_equal(b, ref[:m]), np.array_equal(c, ref[:m]))
 run("second half alone (T=1)", Q[64:128], AMDR_DENSE_HI_CAP=cap)
-run("old tail m=128", Q[:128], AMDR_DENSE_HI_TAIL="0")

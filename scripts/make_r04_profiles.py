@@ -5,7 +5,7 @@
                                                            --hs gpurun_out/r4]
 
 Inputs: scripts/final_evidence.sh (bench line un-profiled / under rocprofv3 --kernel-trace --stats / 2-rank gloo
-rehearsal), scripts/trace_hi_tail.sh (tail64, tail256), scripts/pmc_sq.sh (SQ counters), scripts/trace_hybrid_small.sh,
+rehearsal), scripts/pmc_sq.sh (SQ counters), scripts/trace_hybrid_small.sh,
 scripts/pmc_traffic.py (profiles/pmc_traffic.json).  The tables are the scripts' own summaries, copied; the headers say
 which command produced them."""
 import argparse
@@ -58,32 +58,6 @@ def main():
         "the large scans (`hbm_scan`, `hbm_scan_d1024`, `shard8_proxy`); `shard_pack_kernel` / `shard_merge_kernel` = the exchange at "
         "world = 1.\n\n")
     (P / "r04_bench_kernel_trace.md").write_text(head + (F / "kernel_trace.md").read_text())
-    # ---- the large scan's tail
-    out = ["# Round 4 — what follows the large scan: launch timelines and per-kernel tables (1.25 M x 768, top-10)\n",
-           "`scripts/trace_hi_tail.sh` (rocprofv3 --kernel-trace around `scripts/ab_hi_tail.py`, 6 searches per case).  `tail1` = round 4's chain "
-           "(default), `tail0` = round 3's (`AMDR_DENSE_HI_TAIL=0`).  Timelines: the last 12 dispatches of the run in start order (start offset, "
-           "duration, gap to the end of the previous dispatch, us).\n"]
-    for case in ("tail64", "tail256"):
-        d = F / case
-        if not d.exists():
-            continue
-        for t in ("1", "0"):
-            run = d / f"run{t}.json"
-            line = ""
-            if run.exists():
-                for ln in run.read_text().splitlines():
-                    if ln.startswith("{"):
-                        o = json.loads(ln)
-                        line = (f"B = {o['B']}: scan {o['scan_ms_per_search']} ms in {o['scan_launches_per_search']} launch(es), stream "
-                                f"{o['stream_ms']} ms per search, behind the scan {o['tail_us']} us (under the profiler), counters {o['counters']}")
-            out.append(f"\n## {case}, tail {t} ({'round 4' if t == '1' else 'round 3'})\n{line}\n")
-            tl = d / f"timeline_tail{t}.md"
-            if tl.exists():
-                out.append("\n" + tl.read_text())
-            kt = d / f"kt_tail{t}.md"
-            if kt.exists():
-                out.append("\n" + "\n".join(kt.read_text().splitlines()[:16]) + "\n")
-    (P / "r04_dense_tail.md").write_text("\n".join(out))
     # ---- PMC
     rec = json.loads((P / "pmc_traffic.json").read_text())
     lines = ["# Round 4 — PMC passes (rocprofv3, separate runs, --kernel-trace only beside --pmc)\n",

@@ -668,33 +668,14 @@ def test_maxsim_two_pass_topk_equals_one_pass(nat, monkeypatch):
 
     def run(D, doc_ptr, Q, k):
         out = {}
-        # "1": two passes, the candidates re-scored by document (round 4: a block = one document x 8 of its queries);
-        # "1r3": two passes, one wave per candidate pair (round 3); "0": one pass
-        # "1w": as "1" with the round-4 shortcuts off — every block of pass 1 splits its own queries, the final top-k
-        # ranks whole re-scored rows
-        for flag, rescore, short in (("1", "1", "1"), ("1r3", "0", "1"), ("0", "1", "1"), ("1w", "1", "0")):
-            monkeypatch.setenv("AMDR_MAXSIM_TWOPASS", flag[0])
-            monkeypatch.setenv("AMDR_MAXSIM_RESCORE", rescore)
-            monkeypatch.setenv("AMDR_MAXSIM_PRESPLIT", short)
-            monkeypatch.setenv("AMDR_MAXSIM_FINAL", short)
+        # "1": two passes, the candidates re-scored by document (a block = one document x 8 of its queries); "0": one pass
+        for flag in ("0", "1"):
+            monkeypatch.setenv("AMDR_MAXSIM_TWOPASS", flag)
             idx = nat.MaxSimIndex(D, doc_ptr)
             out[flag] = idx.search(Q, k)
             idx.close()
-        # the re-scoring pass's ring depth / blocks per CU (default 2 stages, grid of 8 blocks per CU): the persistent
-        # form of the start of the round (4 stages, 2 blocks per CU) and one block per CU (every block walks many items)
-        for flag, ring, blocks in (("1g4", "4", "2"), ("1g3", "3", "1")):
-            monkeypatch.setenv("AMDR_MAXSIM_TWOPASS", "1")
-            monkeypatch.setenv("AMDR_MAXSIM_RESCORE_RING", ring)
-            monkeypatch.setenv("AMDR_MAXSIM_RESCORE_BLOCKS", blocks)
-            idx = nat.MaxSimIndex(D, doc_ptr)
-            out[flag] = idx.search(Q, k)
-            idx.close()
-        for name in ("AMDR_MAXSIM_RESCORE", "AMDR_MAXSIM_PRESPLIT", "AMDR_MAXSIM_FINAL", "AMDR_MAXSIM_RESCORE_RING",
-                     "AMDR_MAXSIM_RESCORE_BLOCKS"):
-            monkeypatch.delenv(name)
-        for other in ("0", "1r3", "1w", "1g4", "1g3"):
-            assert np.array_equal(out["1"][1], out[other][1]), (k, other)
-            assert np.array_equal(out["1"][0], out[other][0]), (k, other)
+        assert np.array_equal(out["1"][1], out["0"][1]), k
+        assert np.array_equal(out["1"][0], out["0"][0]), k
         return out["1"]
 
     for n_docs, nq, q_len, ks in ((591, 24, 32, (1, 10, 80)), (130, 9, 17, (5, 32)), (1300, 16, 32, (10,)), (50, 8, 32, (10, 13))):
@@ -752,24 +733,22 @@ def test_maxsim_two_pass_on_the_ucc_token_store_vs_oracle(nat, monkeypatch):
     qs = synthetic_queries(chunks, seed=0)[::12][:96]
     Q = np.stack([te.encode_query(q.strip()) for q, _, _ in qs]).astype(np.float32)
     ref = OM.maxsim_scores(Q, D, doc_ptr)
-    for rescore in ("1", "0"):
-        monkeypatch.setenv("AMDR_MAXSIM_RESCORE", rescore)
-        idx = nat.MaxSimIndex(D, doc_ptr)
-        assert "two-pass" in idx.plan_info(len(Q)), idx.plan_info(len(Q))
-        for k in (10, 80):
-            s, i = idx.search(Q, k)
-            for b in range(len(Q)):
-                order = np.lexsort((np.arange(ref.shape[1]), -ref[b]))
-                es, ei = ref[b, order[:k]], order[:k]
-                assert len(set(i[b].tolist())) == k
-                assert np.max(np.abs(s[b] - ref[b, i[b]])) <= TOL, (k, b)
-                assert np.all(ref[b, i[b]] >= es[-1] - TOL)
-                clear = es > es[-1] + TOL
-                assert set(ei[clear].tolist()) <= set(i[b].tolist())
-                gaps_ok = np.abs(np.diff(es)) > TOL
-                sep = np.concatenate([[True], gaps_ok]) & np.concatenate([gaps_ok, [True]])
-                assert np.all((i[b] == ei)[sep]), (k, b)
-        idx.close()
+    idx = nat.MaxSimIndex(D, doc_ptr)
+    assert "two-pass" in idx.plan_info(len(Q)), idx.plan_info(len(Q))
+    for k in (10, 80):
+        s, i = idx.search(Q, k)
+        for b in range(len(Q)):
+            order = np.lexsort((np.arange(ref.shape[1]), -ref[b]))
+            es, ei = ref[b, order[:k]], order[:k]
+            assert len(set(i[b].tolist())) == k
+            assert np.max(np.abs(s[b] - ref[b, i[b]])) <= TOL, (k, b)
+            assert np.all(ref[b, i[b]] >= es[-1] - TOL)
+            clear = es > es[-1] + TOL
+            assert set(ei[clear].tolist()) <= set(i[b].tolist())
+            gaps_ok = np.abs(np.diff(es)) > TOL
+            sep = np.concatenate([[True], gaps_ok]) & np.concatenate([gaps_ok, [True]])
+            assert np.all((i[b] == ei)[sep]), (k, b)
+    idx.close()
 
 
 def test_maxsim_fuzz_vs_oracle(nat):

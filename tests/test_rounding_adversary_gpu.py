@@ -184,38 +184,27 @@ def test_dense_hi_large_scan_on_the_inversion_corpus(nat, monkeypatch, d, nq):
     case = RA.dense_inversion(rng, d, k, groups=groups, reps=reps, n_total=9017, tiles=281)
     X, Q, top = case["X"], case["Q"], case["top"]
     assert np.array_equal(np.argsort(-RA.exact_dense(X, Q), axis=1, kind="stable")[:, :k], top)
-    for tail in ("1", "0"):  # dense_hi_select_kernel / dense_hi_check_kernel: the two copies of the bound
-        monkeypatch.setenv("AMDR_DENSE_HI_TAIL", tail)
-        out = {}
-        for name, hi, tl in (("hi", "1", "1"), ("exact", "0", "1"), ("full", "0", "0")):
-            monkeypatch.setenv("AMDR_DENSE_HI", hi)
-            monkeypatch.setenv("AMDR_DENSE_TWO_LEVEL", tl)
-            idx = nat.DenseIndex(X)
-            if name == "hi":
-                assert "dense_hi_tilemax_kernel" in idx.plan_info(nq, k), idx.plan_info(nq, k)
-            out[name] = idx.search(Q, k)
-            if name == "hi":
-                out["counters"] = idx.hi_counters()
-            idx.close()
-        took, bad, _, in_use = out["counters"][:4]
-        assert (took, bad, in_use) == (nq, 0, True), (tail, out["counters"])  # the fp16 pass answered, not the exact chain
-        assert np.array_equal(out["hi"][1], top), tail
-        for other in ("exact", "full"):
-            assert np.array_equal(out["hi"][1], out[other][1]), (tail, other)
-            assert np.array_equal(out["hi"][0].view(np.uint32), out[other][0].view(np.uint32)), (tail, other)
+    out = {}
+    for name, hi, tl in (("hi", "1", "1"), ("exact", "0", "1"), ("full", "0", "0")):
+        monkeypatch.setenv("AMDR_DENSE_HI", hi)
+        monkeypatch.setenv("AMDR_DENSE_TWO_LEVEL", tl)
+        idx = nat.DenseIndex(X)
+        if name == "hi":
+            assert "dense_hi_tilemax_kernel" in idx.plan_info(nq, k), idx.plan_info(nq, k)
+        out[name] = idx.search(Q, k)
+        if name == "hi":
+            out["counters"] = idx.hi_counters()
+        idx.close()
+    took, bad, _, in_use = out["counters"][:4]
+    assert (took, bad, in_use) == (nq, 0, True), out["counters"]  # the fp16 pass answered, not the exact chain
+    assert np.array_equal(out["hi"][1], top)
+    for other in ("exact", "full"):
+        assert np.array_equal(out["hi"][1], out[other][1]), other
+        assert np.array_equal(out["hi"][0].view(np.uint32), out[other][0].view(np.uint32)), other
 
 
-_MS_VARIANTS = [{}]
-for _hi2 in ("1", "0"):
-    for _ring in (("2", "3", "4") if _hi2 == "1" else (None,)):
-        for _docs in (None, "1", "7"):
-            for _rs in ("1", "0"):
-                v = {"AMDR_MAXSIM_HI2": _hi2, "AMDR_MAXSIM_RESCORE": _rs}
-                if _ring:
-                    v["AMDR_MAXSIM_RING1"] = _ring
-                if _docs:
-                    v["AMDR_MAXSIM_DOCS"] = _docs
-                _MS_VARIANTS.append(v)
+# documents per block of pass 1: the default, one, and seven (blocks that end inside the store's groups)
+_MS_VARIANTS = [{}, {"AMDR_MAXSIM_DOCS": "1"}, {"AMDR_MAXSIM_DOCS": "7"}]
 
 
 def _ms_check(nat, monkeypatch, D, doc_ptr, Q, k, top, variants):
@@ -253,5 +242,4 @@ def test_maxsim_two_pass_on_the_inversion_store(nat, monkeypatch, k, nc):
 def test_maxsim_two_pass_with_subnormal_query_tokens(nat, monkeypatch):
     rng = np.random.default_rng(9)
     c = RA.maxsim_subnormal(rng, 8, 24, 4, 60)
-    variants = [{}, {"AMDR_MAXSIM_RESCORE": "0"}, {"AMDR_MAXSIM_HI2": "0"}, {"AMDR_MAXSIM_HI2": "0", "AMDR_MAXSIM_RESCORE": "0"}]
-    _ms_check(nat, monkeypatch, c["D"], c["doc_ptr"], c["Q"], 4, None, variants)
+    _ms_check(nat, monkeypatch, c["D"], c["doc_ptr"], c["Q"], 4, None, [{}])
