@@ -94,11 +94,11 @@ int amdr_dense_read_rows(const amdr_dense_t* h, int64_t row0, int64_t nrows, flo
  * is cut (e.g. "dense_panel_scores_kernel nb=6 parts=7 blocks=2044 + scores_slab_topk_kernel"):
  * written NUL-terminated into buf.  No device work.  bench.py names its roofline kernel with it. */
 int amdr_dense_plan_info(const amdr_dense_t* h, int32_t nq, int32_t k, char* buf, int32_t buf_len);
-/* Host-only (no device is touched): workspace bytes a batched search of nq queries at depth k on an [n, d] matrix
- * RESERVES before its passes — out6[0..2] = score / tile-maxima matrix, slab lists, candidate-tile lists — and the
- * maximum any single pass (full chunks and the remainder) then USES — out6[3..5].  Zeros for the 1-4 query forms.
- * A test holds out6[3+i] <= out6[i] over shapes with many row slabs (tests/test_abi.py). */
-int amdr_dense_workspace_plan(int64_t n, int32_t d, int32_t nq, int32_t k, int64_t* out6);
+/* Host-only (no device is touched): on an [n, d] matrix, out6[0..2] = the bytes amdr_dense_reserve(nq_max, k_max) sizes
+ * for the "_device" calls — score / tile-maxima matrix, slab lists, candidate-tile lists — and out6[3..5] = the most any
+ * pass (full chunks and the remainder) of amdr_dense_search_device(nq, k) uses, whichever form the call takes.  A test
+ * holds out6[3+i] <= out6[i] for every nq <= nq_max, k <= k_max (tests/test_abi.py). */
+int amdr_dense_workspace_plan(int64_t n, int32_t d, int32_t nq_max, int32_t k_max, int32_t nq, int32_t k, int64_t* out6);
 /* Large scans (chunk matrix far beyond the caches, >= 5 queries): the first pass of the two-level top-k runs on the
  * fp16 matrix instructions over fp16 roundings of both operands, 64 queries per scan; its candidate cut is widened by a
  * proven rounding bound and the second pass is the exact fp32 kernel, so ids and score bits are those of the exact

@@ -55,7 +55,7 @@ SIGNATURES = {
     "amdr_dense_create": "PliiP", "amdr_dense_create_from_device": "PliiP", "amdr_dense_add": "PPl",
     "amdr_dense_ntotal": "PP", "amdr_dense_dim": "PP", "amdr_dense_reserve": "Pii", "amdr_dense_search": "PPiiPP",
     "amdr_dense_search_device": "PPiiPPP", "amdr_dense_search_fuse_device": "PPiiPPPPiPPPPPPPP", "amdr_hybrid_small_device": "PPPPPiiiPPPPPPPPPPPP", "amdr_dense_small_create": "PP", "amdr_dense_small_approx_device": "PPiPlPP", "amdr_dense_small_destroy": "P", "amdr_dense_two_pass_fallbacks": "PP", "amdr_dense_read_rows": "PllP", "amdr_dense_score_rows": "PPiPiP",
-    "amdr_dense_plan_info": "PiiPi", "amdr_dense_workspace_plan": "liiiP", "amdr_dense_hi_counters": "PP", "amdr_dense_profile_begin": "Pi", "amdr_dense_profile_end": "PPP", "amdr_dense_destroy": "P",
+    "amdr_dense_plan_info": "PiiPi", "amdr_dense_workspace_plan": "liiiiiP", "amdr_dense_hi_counters": "PP", "amdr_dense_profile_begin": "Pi", "amdr_dense_profile_end": "PPP", "amdr_dense_destroy": "P",
     "amdr_bm25_create": "PPPPPlldddiP", "amdr_bm25_ndocs": "PP", "amdr_bm25_reserve": "Piil", "amdr_bm25_workspace_plan": "liiiiP", "amdr_bm25_plan_info": "PiiPi",
     "amdr_bm25_search": "PPPiiPP", "amdr_bm25_search_device": "PPPiiPPP", "amdr_bm25_scores": "PPPiP",
     "amdr_bm25_destroy": "P",
@@ -186,11 +186,13 @@ def device_name(device: int = 0) -> str:
     return buf.value.decode()
 
 
-def dense_workspace_plan(n: int, d: int, nq: int, k: int) -> Tuple[Tuple[int, int, int], Tuple[int, int, int]]:
-    """(reserved, used by the largest pass) workspace bytes of one batched dense search — host-only arithmetic."""
+def dense_workspace_plan(n: int, d: int, nq_max: int, k_max: int, nq: int,
+                         k: int) -> Tuple[Tuple[int, int, int], Tuple[int, int, int]]:
+    """(bytes DenseIndex.reserve(nq_max, k_max) sizes, bytes the largest pass of search_device(nq, k) uses), each as
+    (score matrix, slab lists, candidate-tile lists) — host-only arithmetic."""
     out = (C.c_int64 * 6)()
-    _check(load().amdr_dense_workspace_plan(C.c_int64(n), C.c_int32(d), C.c_int32(nq), C.c_int32(k), out),
-           "amdr_dense_workspace_plan")
+    _check(load().amdr_dense_workspace_plan(C.c_int64(n), C.c_int32(d), C.c_int32(nq_max), C.c_int32(k_max), C.c_int32(nq),
+                                            C.c_int32(k), out), "amdr_dense_workspace_plan")
     v = [int(x) for x in out]
     return tuple(v[:3]), tuple(v[3:])
 

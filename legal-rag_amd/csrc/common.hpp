@@ -85,7 +85,8 @@ struct DenseMfmaPlan {
   size_t lds_scores, s_bytes, part_bytes;
 };
 bool dense_mfma_supported(int d);
-void dense_mfma_plan(long n, int d, int nq, int k, DenseMfmaPlan* p);
+// grid = false: the top-k half and the sizes only (the search for the scores grid costs ~10 us on a large matrix)
+void dense_mfma_plan(long n, int d, int nq, int k, DenseMfmaPlan* p, bool grid = true);
 // mode 0: every row's score; 1: per-tile maxima; 2: re-scoring of the tiles in tile_list (dense_mfma.hip)
 // `gate` (nullable device int): the launch does nothing unless *gate != 0 — the exact first pass behind the fp16 one
 // (dense_hi.hip) is enqueued unconditionally and decides on the device whether it runs

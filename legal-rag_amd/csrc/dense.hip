@@ -13,6 +13,7 @@
 #include "dense_dot.hpp"
 #include "topk.hpp"
 
+#include <algorithm>
 #include <cfloat>
 #include <mutex>
 #include <new>
@@ -364,149 +365,20 @@ int launch_scan_ch(const ScanPlan& p, const amdr_dense* h, const float* Q, int n
     case 4: launch_scan<NQ, 4>(p, h, Q, nq, k, part, fs, fi, st); break;
     default: return fail(AMDR_EINVAL, "dense: unsupported dim %d", h->d);
   }
+  AMDR_HIP(hipGetLastError());
   return AMDR_OK;
 }
 
-// Batches of >= kBatchedMin queries take the 32-query-tile MFMA path (dense_mfma.hip);
-// the score matrix workspace is bounded, so very large batches go in chunks of queries.
-constexpr int kBatchedMin = 5;  // measured: from 5 queries up one MFMA tile pass beats the 8-query GEMV pass
-constexpr int64_t kRowWavesMax = 16384;  // rows up to which 1-4 queries take one wave per (query, row)
+// ---- queries per pass of each form ---------------------------------------------------------------------------------------
+// Batched forms (dense_mfma.hip, dense_panel.hip): the score matrix workspace is bounded, so very large batches go in
+// chunks of queries.
 constexpr size_t kScoreBytesMax = (size_t)4 << 30;
-
 int batched_chunk(const amdr_dense* h, int nq) {
   size_t per_q = (size_t)h->n * sizeof(float);
   long c = (long)(kScoreBytesMax / (per_q ? per_q : 1));
   c = (c / 32) * 32;
   if (c < 32) c = 32;
   return nq < c ? nq : (int)c;
-}
-
-// Slab-list bytes of one batched search: the full chunk AND the remainder pass (planned for its own size:
-// slabs(m) * m is not monotone in m, so a shorter pass can need more).
-size_t batched_part_need(const amdr_dense* h, int nq, int k) {
-  const int chunk = batched_chunk(h, nq);
-  DenseMfmaPlan p;
-  dense_mfma_plan((long)h->n, h->d, chunk, k, &p);
-  size_t need = p.part_bytes;
-  if (nq % chunk) {
-    dense_mfma_plan((long)h->n, h->d, nq % chunk, k, &p);
-    need = p.part_bytes > need ? p.part_bytes : need;
-  }
-  return need;
-}
-
-// Two-pass form: scores S[q][row] (fp32-MFMA tiles for batches, one wave per (query, row) for the
-// 1-4 query call on a short corpus), then slab top-k (+ merge when there are several slabs).
-// The two-pass form of a LONG batch on a SHORT corpus: approximate scores on the fp16 matrix instructions (16 x the exact
-// form's rate), then per query the rows inside a proven margin of its k-th best re-scored exactly (DESIGN.md 4.11).  From
-// 4 096 queries per launch (below, the first pass's fixed cost eats the gain: 1 168 queries 28 us against 26 for the whole
-// exact search), one slab of <= 1 024 rows, d a multiple of 128, k (+ the BM25 depth when fused) <= 32.
-// AMDR_DENSE_SMALL_HI=0 pins the exact form, AMDR_DENSE_SMALL_HI_MIN the batch size it starts at.
-bool small_hi_shape(const amdr_dense* h, int m, int k, int kb) {
-  const char* e = getenv("AMDR_DENSE_SMALL_HI");
-  if (e && e[0] == '0') return false;
-  const char* mn = getenv("AMDR_DENSE_SMALL_HI_MIN");
-  const int m_min = mn && atoi(mn) > 0 ? atoi(mn) : 4096;
-  // depth <= 12: the second pass finds its candidates with the pair selector's 32 slots per query; from k ~ 14 up those
-  // overflow on most queries and the query re-scores its whole row (37 376 queries on 1 024 x 768: k = 12 230 against 517 us
-  // for the exact form, k = 14 465 against 536, k = 20 2 099 against 619)
-  return m >= m_min && h->n >= 1 && h->n <= 1024 && h->d >= 128 && h->d <= 1024 && h->d % 128 == 0 && k >= 1 && k <= 12 &&
-         k + kb <= 32;
-}
-// the image and the workspaces of that form; false: not available now (creation failed before, non-finite matrix, or a
-// stream is capturing and nothing was reserved) — the caller takes the exact form
-bool small_hi_ready(amdr_dense* h, int m, hipStream_t st) {
-  if (h->small_failed) return false;
-  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  const bool capturing = st && hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
-  if (!h->small) {
-    if (capturing) return false;
-    if (dense_small_create_from(h->device, h->X, h->n, h->d, &h->small) != AMDR_OK || !dense_small_usable(h->small)) {
-      h->small_failed = true;  // (a matrix the fp16 scale range cannot hold stays on the exact form)
-      return false;
-    }
-  }
-  const size_t need = (size_t)m * sizeof(float);
-  if (capturing && (h->small_eps.cap < need || !h->small_fb.p)) return false;
-  if (h->small_eps.ensure(need) != AMDR_OK) return false;
-  if (!h->small_fb.p) {
-    if (h->small_fb.ensure(sizeof(unsigned int)) != AMDR_OK) return false;
-    (void)hipMemset(h->small_fb.p, 0, sizeof(unsigned int));
-  }
-  return capturing ? true : dense_small_reserve(h->small, m) == AMDR_OK;
-}
-
-int run_search_batched(amdr_dense* h, int ws, const float* Q_dev, int nq, int k, float* scores_dev, int64_t* ids_dev,
-                       hipStream_t st, bool row_waves = false, const FuseTail* tail = nullptr) {
-  DevBuf& smat = h->smat[ws];
-  DevBuf& partb = h->part[ws];
-  const int chunk = batched_chunk(h, nq);
-  DenseMfmaPlan p;
-  dense_mfma_plan((long)h->n, h->d, chunk, k, &p);
-  int rc = smat.ensure(p.s_bytes);
-  if (!rc) rc = partb.ensure(batched_part_need(h, nq, k));
-  if (rc) return rc;
-  for (int q0 = 0; q0 < nq; q0 += chunk) {
-    const int m = nq - q0 < chunk ? nq - q0 : chunk;
-    if (m != chunk) dense_mfma_plan((long)h->n, h->d, m, k, &p);
-    const bool prof = h->prof_on && (size_t)(h->prof_used + 2) <= h->prof_ev.size();
-    if (prof) AMDR_HIP(hipEventRecord(h->prof_ev[h->prof_used], st));
-    const int kb_fused = tail ? tail->kb : 0;
-    const bool fuse_here = tail && dense_select_fuse_applies((long)h->n, p.slabs, m, k, tail->kb);
-    if (!row_waves && p.slabs == 1 && (fuse_here || !tail) && small_hi_shape(h, m, k, kb_fused) && small_hi_ready(h, m, st)) {
-      rc = amdr_dense_small_approx_device(h->small, Q_dev + (size_t)q0 * h->d, m, smat.as<float>(), p.ld,
-                                          h->small_eps.as<float>(), st);
-      if (rc) return rc;
-      if (prof) {
-        AMDR_HIP(hipEventRecord(h->prof_ev[h->prof_used + 1], st));
-        h->prof_used += 2;
-      }
-      if ((rc = dense_hi_select_launch(tail, q0, smat.as<float>(), p.ld, (long)h->n, m, k, h->X, Q_dev + (size_t)q0 * h->d, h->d,
-                                       h->small_eps.as<float>(), scores_dev + (size_t)q0 * k, ids_dev + (size_t)q0 * k,
-                                       h->small_fb.as<unsigned int>(), st)))
-        return rc;
-      continue;
-    }
-    if (row_waves) {
-      hipLaunchKernelGGL(dense_all_scores_kernel, dim3(ceil_div((long)m * h->n, kWaves)), dim3(256), 0, st, h->X,
-                         (long)h->n, h->d, Q_dev + (size_t)q0 * h->d, m, p.ld, smat.as<float>());
-      AMDR_HIP(hipGetLastError());
-    } else if (dense_panel_supported((long)h->n, h->d, m)) {
-      DensePanelPlan pp;
-      dense_panel_plan((long)h->n, h->d, m, &pp);
-      rc = dense_panel_launch_scores(pp, h->X, (long)h->n, h->d, Q_dev + (size_t)q0 * h->d, m, p.ld,
-                                     smat.as<float>(), st);
-      if (rc) return rc;
-    } else {
-      rc = dense_mfma_launch_scores(p, h->X, (long)h->n, h->d, Q_dev + (size_t)q0 * h->d, m, smat.as<float>(), st);
-      if (rc) return rc;
-    }
-    if (prof) {
-      AMDR_HIP(hipEventRecord(h->prof_ev[h->prof_used + 1], st));
-      h->prof_used += 2;
-    }
-    const bool direct = p.slabs == 1;  // one slab: its list is the answer, no merge launch
-    if (tail && dense_select_fuse_applies((long)h->n, p.slabs, m, k, tail->kb)) {
-      // ranking of the rows and the fusion with the BM25 lists in one kernel (fuse.hip dense_select_fuse_kernel)
-      if ((rc = dense_select_fuse_launch(*tail, q0, smat.as<float>(), p.ld, (long)h->n, m, k, p.cap,
-                                         scores_dev + (size_t)q0 * k, ids_dev + (size_t)q0 * k, st)))
-        return rc;
-      continue;
-    }
-    rc = dense_mfma_launch_topk(p, smat.as<float>(), (long)h->n, m, k, partb.p,
-                                direct ? scores_dev + (size_t)q0 * k : nullptr,
-                                direct ? ids_dev + (size_t)q0 * k : nullptr, st);
-    if (rc) return rc;
-    if (!direct) {
-      size_t lds = (size_t)kWaves * p.cap * sizeof(C32) + kWaves * sizeof(int);
-      hipLaunchKernelGGL(dense_merge_kernel, dim3(m), dim3(256), lds, st, partb.as<C32>(), p.slabs, m, k, p.cap,
-                         scores_dev + (size_t)q0 * k, (long long*)ids_dev + (size_t)q0 * k);
-      AMDR_HIP(hipGetLastError());
-    }
-    if (tail && (rc = dense_fuse_plain_launch(*tail, q0, m, k, scores_dev + (size_t)q0 * k, ids_dev + (size_t)q0 * k, st)))
-      return rc;
-  }
-  return AMDR_OK;
 }
 
 // Two-level top-k for batches on a matrix far larger than the caches (the 10 M-row scans): the score matrix of the
@@ -519,15 +391,6 @@ int run_search_batched(amdr_dense* h, int ws, const float* Q_dev, int nq, int k,
 // Exact: at most k - 1 tiles hold a score above a query's k-th best s_k, so the k-th largest tile maximum T <= s_k
 // and every tile that holds one of the top k has a maximum >= T; among tiles AT T the lower tile ids are kept, which
 // is where the lower row ids of equal scores live.  queries x k <= 8 192 candidate tiles per pass.
-bool two_level_applies(const amdr_dense* h, int nq, int k) {
-  const char* e = getenv("AMDR_DENSE_TWO_LEVEL");
-  if (e && e[0] == '0') return false;
-  if (!(nq >= kBatchedMin && h->n > 0 && dense_mfma_supported(h->d))) return false;
-  const long tiles = ((long)h->n + 31) / 32;
-  if (e && e[0] == '1') return tiles >= 2L * k;  // pinned on (tests): any matrix with enough tiles
-  if (dense_panel_supported((long)h->n, h->d, batched_chunk(h, nq))) return false;  // >= 96 queries: the panel kernel
-  return dense_stream_nontemporal((long)h->n, h->d) && tiles >= 64L * k;
-}
 constexpr int kTwoLevelTilesMax = 8192;  // candidate tiles per pass (queries x k): one wave sorts them in 64 KiB of LDS
 int two_level_chunk(int nq, int k) {
   int c = (kTwoLevelTilesMax / k) / 32 * 32;  // >= 32 for every k <= AMDR_MAX_K = 256
@@ -550,33 +413,125 @@ constexpr int kHiLevels = 3;
 constexpr int kHiExtra[kHiLevels] = {22, 54, 96};
 int hi_kc(int k, int level) { return k + (k > kHiExtra[level] ? k : kHiExtra[level]) + 1; }
 int hi_kc_max(int k) { return hi_kc(k, kHiLevels - 1); }
-int hi_level_of(const amdr_dense* h) {
-  const char* e = getenv("AMDR_DENSE_HI_LEVEL");  // pins the width (tests, A/B)
-  if (e && e[0] >= '0' && e[0] < '0' + kHiLevels) return e[0] - '0';
-  return h->hi_level;
+constexpr int kHi2Tiles = 4;  // query tiles per pass of the round-4 tail: 256 queries (192 at d = 1 024) share one tail
+int hi2_chunk(const amdr_dense* h, int nq) {
+  const int c = kHi2Tiles * dense_hi_max_queries(h->d);
+  return nq < c ? nq : c;
 }
-bool hi_applies(const amdr_dense* h, int nq, int k) {
-  const char* e = getenv("AMDR_DENSE_HI");
-  if (e && e[0] == '0') return false;
-  const char* e2 = getenv("AMDR_DENSE_TWO_LEVEL");
-  if (e2 && e2[0] == '0') return false;
-  if (!(h->hi_ok && nq >= kBatchedMin && h->n > 0 && dense_mfma_supported(h->d))) return false;
-  if (hi_kc_max(k) > AMDR_MAX_K) return false;  // k <= 127
-  const long tiles = ((long)h->n + 31) / 32;
-  if (tiles >= (1l << 26)) return false;  // (query, tile) packed in 32 bits of a candidate entry
-  if (e && e[0] == '1') return tiles >= 2L * hi_kc_max(k);  // pinned on (tests)
-  return dense_stream_nontemporal((long)h->n, h->d) && tiles >= 64L * hi_kc_max(k);
+
+// ---- the route: which form a search of nq queries at depth k takes ----------------------------------------------------------
+// The environment pins that steer it, read once per call (tests set them between calls of one process: nothing is kept
+// from one call to the next).
+struct DensePins {
+  char two_level = 0, hi = 0;  // AMDR_DENSE_TWO_LEVEL, AMDR_DENSE_HI: '0' off, '1' on wherever there are enough tiles (tests)
+  bool hi_level_set = false;   // AMDR_DENSE_HI_LEVEL: pins the width of the fp16 pass's candidate cut (tests, A/B);
+  int hi_level = -1;           // set, but not a level: the handle keeps the width it has
+  bool small_hi = true;        // AMDR_DENSE_SMALL_HI=0 pins the exact form of long batches on a short corpus
+  int small_hi_min = 4096;     // AMDR_DENSE_SMALL_HI_MIN: the batch size its fp16 two-pass form starts at
+};
+DensePins read_pins() {
+  auto pin = [](const char* name) { const char* e = getenv(name); return e && (e[0] == '0' || e[0] == '1') ? e[0] : '\0'; };
+  DensePins p;
+  p.two_level = pin("AMDR_DENSE_TWO_LEVEL");
+  p.hi = pin("AMDR_DENSE_HI");
+  const char* l = getenv("AMDR_DENSE_HI_LEVEL");
+  p.hi_level_set = l != nullptr;
+  if (l && l[0] >= '0' && l[0] < '0' + kHiLevels) p.hi_level = l[0] - '0';
+  p.small_hi = pin("AMDR_DENSE_SMALL_HI") != '0';
+  const char* mn = getenv("AMDR_DENSE_SMALL_HI_MIN");
+  if (mn && atoi(mn) > 0) p.small_hi_min = atoi(mn);
+  return p;
 }
+
+enum class Form {
+  Scan,      // dense_scan_topk_kernel: the GEMV scan with per-wave top-k (+ merge)
+  RowWaves,  // one wave per (query, row) writes the score matrix, slab top-k ranks it
+  Batched,   // the score matrix from MFMA tiles, the panel kernel or the fp16 two-pass form; slab top-k or fused select
+  TwoLevel,  // exact two-level top-k
+  Hi,        // two-level top-k behind the fp16 first pass
+};
+struct Route {
+  Form form;
+  int chunk;         // queries per pass (the last pass of a call may be shorter)
+  bool hi;           // the fp16 first pass applies to this call: form Hi, or TwoLevel on a handle that gave the pass up
+  int hi_level, kc;  // form Hi: the width level of the candidate cut, the tiles re-scored per query
+};
+constexpr int kBatchedMin = 5;  // measured: from 5 queries up one MFMA tile pass beats the 8-query GEMV pass
+constexpr int64_t kRowWavesMax = 16384;  // rows up to which fewer queries take one wave per (query, row)
+// In nq the route has two thresholds, both monotone: kBatchedMin, and the batch size from which the exact two-level form
+// yields to the panel kernel (the fp16 first pass does not).  Below kBatchedMin, and for a dimension outside the MFMA
+// forms, k does not enter.  reserve_need enumerates on these two facts.
+Route dense_route(const amdr_dense* h, const DensePins& pins, int nq, int k) {
+  Route r{Form::Scan, nq, false, 0, 0};
+  const long n = (long)h->n;
+  if (nq >= kBatchedMin && n > 0 && dense_mfma_supported(h->d)) {
+    r.form = Form::Batched;
+    r.chunk = batched_chunk(h, nq);
+    if (pins.two_level == '0') return r;
+    const long tiles = (n + 31) / 32;
+    const int kc_max = hi_kc_max(k);
+    // kc_max <= AMDR_MAX_K: k <= 127; tiles < 2^26: (query, tile) packed in 32 bits of a candidate entry
+    r.hi = pins.hi != '0' && h->hi_ok && kc_max <= AMDR_MAX_K && tiles < (1l << 26) &&
+           (pins.hi == '1' ? tiles >= 2L * kc_max : dense_stream_nontemporal(n, h->d) && tiles >= 64L * kc_max);
+    if (r.hi && !h->hi_off) {
+      r.form = Form::Hi;
+      r.chunk = hi2_chunk(h, nq);
+      r.hi_level = pins.hi_level >= 0 ? pins.hi_level : h->hi_level;
+      r.kc = hi_kc(k, r.hi_level);
+    } else if (r.hi ||  // a handle that gave the fp16 pass up runs the exact passes, ungated
+               (pins.two_level == '1' ? tiles >= 2L * k                   // pinned on: any matrix with enough tiles
+                                      : !dense_panel_supported(n, h->d, r.chunk) &&  // >= 96 queries: the panel kernel
+                                            dense_stream_nontemporal(n, h->d) && tiles >= 64L * k)) {
+      r.form = Form::TwoLevel;
+      r.chunk = two_level_chunk(nq, k);
+    }
+  } else if (n > 0 && n <= kRowWavesMax) {
+    r.form = Form::RowWaves;
+    r.chunk = batched_chunk(h, nq);
+  }
+  return r;
+}
+
+// The two-pass form of a LONG batch on a SHORT corpus: approximate scores on the fp16 matrix instructions (16 x the exact
+// form's rate), then per query the rows inside a proven margin of its k-th best re-scored exactly (DESIGN.md 4.11).  From
+// 4 096 queries per launch (below, the first pass's fixed cost eats the gain: 1 168 queries 28 us against 26 for the whole
+// exact search), one slab of <= 1 024 rows, d a multiple of 128, k (+ the BM25 depth when fused) <= 32.
+bool small_hi_shape(const amdr_dense* h, const DensePins& pins, int m, int k, int kb) {
+  // depth <= 12: the second pass finds its candidates with the pair selector's 32 slots per query; from k ~ 14 up those
+  // overflow on most queries and the query re-scores its whole row (37 376 queries on 1 024 x 768: k = 12 230 against 517 us
+  // for the exact form, k = 14 465 against 536, k = 20 2 099 against 619)
+  return pins.small_hi && m >= pins.small_hi_min && h->n >= 1 && h->n <= 1024 && h->d >= 128 && h->d <= 1024 &&
+         h->d % 128 == 0 && k >= 1 && k <= 12 && k + kb <= 32;
+}
+// One pass of m queries of the forms that go through a score matrix S[q][row] (Batched, RowWaves; p = its plan): who
+// writes S, who ranks it.  What depends on run-time state (small_hi_ready: image present, stream capturing) is decided
+// where the pass runs.
+struct PassForm {
+  enum Scores { RowWaves, Panel, Tiles } scores;  // the exact kernels
+  bool small_hi;     // the fp16 two-pass form applies instead of `scores` and the ranking below
+  bool select_fuse;  // ranking of the rows and the fusion with the BM25 lists in one kernel (fuse.hip dense_select_fuse_kernel);
+                     // else slab top-k (+ merge when there are several slabs), then the plain fusion if a tail follows
+};
+PassForm batched_pass_form(const amdr_dense* h, const DensePins& pins, const Route& r, const DenseMfmaPlan& p, int m, int k,
+                           const FuseTail* tail) {
+  PassForm f;
+  f.scores = r.form == Form::RowWaves ? PassForm::RowWaves : dense_panel_supported((long)h->n, h->d, m) ? PassForm::Panel : PassForm::Tiles;
+  f.select_fuse = tail && dense_select_fuse_applies((long)h->n, p.slabs, m, k, tail->kb);
+  f.small_hi = r.form == Form::Batched && p.slabs == 1 && (f.select_fuse || !tail) &&
+               small_hi_shape(h, pins, m, k, tail ? tail->kb : 0);
+  return f;
+}
+
 // Between searches (host side, no synchronisation: the counters are whatever the last completed copy-back left).  One
 // unresolved query sends its whole pass through the exact first pass as well, so what is counted is PASSES whose flag
 // went up: more than 10 % of >= 4 passes at this width -> the next width (+3 % per pass); at the widest, more than half
-// -> the exact passes alone are cheaper (1 + 2 f > 2).
-void hi_adapt(amdr_dense* h) {
-  if (!h->hi_host || h->hi_off || getenv("AMDR_DENSE_HI_LEVEL")) return;
+// -> the exact passes alone are cheaper (1 + 2 f > 2).  True: the handle's route changed.
+bool hi_adapt(amdr_dense* h, const DensePins& pins) {
+  if (!h->hi_host || h->hi_off || pins.hi_level_set) return false;
   // the counters are whatever the last COMPLETED copy-back left: the pinned words are read only after the event behind
   // their copy has been reached (round 3 read them while a copy could still be in flight)
   if (h->hi_copy_pending) {
-    if (hipEventQuery(h->hi_ev) != hipSuccess) return;  // still on its way: adapt at the next search
+    if (hipEventQuery(h->hi_ev) != hipSuccess) return false;  // still on its way: adapt at the next search
     h->hi_copy_pending = false;
     for (int i = 0; i < 3; ++i) h->hi_seen[i] = h->hi_host[i];
   }
@@ -586,45 +541,41 @@ void hi_adapt(amdr_dense* h) {
   const int64_t passes = (int64_t)h->hi_seen[2];
   const int64_t p = passes - h->lvl_p0;
   const int64_t bad = (int64_t)(f - h->lvl_f0);
-  if (p < 4) return;
+  if (p < 4) return false;
   bool move = false;
   if (h->hi_level + 1 < kHiLevels) {
     move = bad * 10 > p;
     if (move) ++h->hi_level;
   } else {
-    const char* e = getenv("AMDR_DENSE_HI");
-    move = bad * 2 > p && !(e && e[0] == '1');  // this matrix is not for the fp16 pass
+    move = bad * 2 > p && pins.hi != '1';  // this matrix is not for the fp16 pass
     if (move) h->hi_off = true;
   }
   if (move || p >= (1 << 16)) {  // a new window
     h->lvl_p0 = passes;
     h->lvl_f0 = f;
   }
-}
-constexpr int kHi2Tiles = 4;  // query tiles per pass of the round-4 tail: 256 queries (192 at d = 1 024) share one tail
-int hi2_chunk(const amdr_dense* h, int nq) {
-  const int c = kHi2Tiles * dense_hi_max_queries(h->d);
-  return nq < c ? nq : c;
+  return move;
 }
 
+// ---- workspaces -----------------------------------------------------------------------------------------------------
 // Workspace of one pass of the round-4 tail.  smat: exact tile maxima M [m][ldM] (written only when the flag goes up) |
 // re-scored columns S2 [m][32 kc] | sample maxima MT [qtiles][items][64] | per-query candidate lists [m][qcap];
-// aux: list [m][kc] | count, unres [m] | tau [m] | qcount [m] (the gate flag sits at the end of aux, as before).
+// aux: list [m][kc] | count, unres [m] | tau [m] | qcount [m] | the gate flag.
 struct Hi2Plan {
   int qtiles, kc;
   long tiles, ldM, ldS2;
   size_t qcap;
   DenseMfmaPlan scan;
   size_t off_S2, off_MT, off_qlist, smat_bytes;
-  size_t off_count, off_unres, off_tau, off_qcount, aux_bytes;
+  size_t off_count, off_unres, off_tau, off_qcount, off_flag, aux_bytes;
 };
-void hi2_plan(const amdr_dense* h, int m, int k, int kc, Hi2Plan* p) {
+void hi2_plan(const amdr_dense* h, int m, int k, int kc, Hi2Plan* p, bool grids = true) {
   auto up = [](size_t b) { return (b + 255) / 256 * 256; };
   const int qt = dense_hi_max_queries(h->d);
   p->qtiles = (m + qt - 1) / qt;
   p->kc = kc;
   p->tiles = ((long)h->n + 31) / 32;
-  dense_mfma_plan((long)h->n, h->d, m, k, &p->scan);
+  dense_mfma_plan((long)h->n, h->d, m, k, &p->scan, grids);
   p->ldM = (p->tiles + 31) / 32 * 32;
   p->scan.ld = p->ldM;
   p->ldS2 = (long)kc * 32;
@@ -637,7 +588,8 @@ void hi2_plan(const amdr_dense* h, int m, int k, int kc, Hi2Plan* p) {
   p->off_unres = p->off_count + up((size_t)m * sizeof(int));
   p->off_tau = p->off_unres + up((size_t)m * sizeof(int));
   p->off_qcount = p->off_tau + up((size_t)m * sizeof(float));
-  p->aux_bytes = p->off_qcount + up((size_t)m * sizeof(unsigned int));
+  p->off_flag = p->off_qcount + up((size_t)m * sizeof(unsigned int));
+  p->aux_bytes = p->off_flag + 256;
 }
 
 struct TwoLevelPlan {
@@ -646,84 +598,204 @@ struct TwoLevelPlan {
   size_t m_bytes, s2_bytes, aux_bytes, part_bytes;
 };
 // the exact form: every query of the pass against the UNION of their k candidate tiles each (one list)
-void two_level_plan(const amdr_dense* h, int m, int k, TwoLevelPlan* t) {
+void two_level_plan(const amdr_dense* h, int m, int k, TwoLevelPlan* t, bool grids = true) {
   t->tiles = ((long)h->n + 31) / 32;
-  dense_mfma_plan((long)h->n, h->d, m, k, &t->scan);
-  dense_mfma_plan(t->tiles, h->d, m, k, &t->tk1);  // only its top-k half is used: columns = tiles
+  dense_mfma_plan((long)h->n, h->d, m, k, &t->scan, grids);
+  dense_mfma_plan(t->tiles, h->d, m, k, &t->tk1, false);  // only its top-k half is used: columns = tiles
+  t->scan.ld = t->tk1.ld;                                 // (mode 1 writes one maximum per tile)
   t->cand_rows = (long)m * k * 32;
-  dense_mfma_plan(t->cand_rows, h->d, m, k, &t->pass2);
+  dense_mfma_plan(t->cand_rows, h->d, m, k, &t->pass2, grids);
   t->m_bytes = ((size_t)m * t->tk1.ld * sizeof(float) + 255) / 256 * 256;
   t->s2_bytes = ((size_t)m * t->pass2.ld * sizeof(float) + 255) / 256 * 256;
-  t->aux_bytes = (size_t)m * k * (sizeof(int64_t) + sizeof(float)) + (size_t)(m * k + 64) * sizeof(int) + 256;  // tile ids +
-                                                                                                           // maxima, union + count
+  // tile ids + maxima, union + count; + 256 that nothing addresses (where the fp16 pass's flag once sat: sizes as before)
+  t->aux_bytes = (size_t)m * k * (sizeof(int64_t) + sizeof(float)) + (size_t)(m * k + 64) * sizeof(int) + 256 + 256;
   t->part_bytes = t->tk1.part_bytes > t->pass2.part_bytes ? t->tk1.part_bytes : t->pass2.part_bytes;
 }
-// Workspace for one search of nq queries at depth k: the maximum over every chunk size the pass loop will use — the
-// full chunk AND the remainder (a smaller chunk can need MORE slab-list space: slabs(m) * m is not monotone in m).
-// Behind the fp16 first pass: its passes, and the exact passes a handle that gave it up runs instead.
-// With `all` (amdr_dense_reserve: calls within (nq_max, k_max) must allocate nothing) the maximum over every batch
-// size <= nq and every depth <= k that takes this path — a smaller k takes more queries per pass (a larger matrix of
-// tile maxima) and the path's own applicability test depends on k.
-struct TwoLevelNeed {
-  size_t smat = 0, part = 0, aux = 0;
-  void add(const TwoLevelPlan& t) {
-    smat = t.m_bytes + t.s2_bytes > smat ? t.m_bytes + t.s2_bytes : smat;
-    part = t.part_bytes > part ? t.part_bytes : part;
-    aux = t.aux_bytes + 256 > aux ? t.aux_bytes + 256 : aux;  // + the gate flag behind the lists
-  }
+
+struct Need {  // bytes of smat / part / aux
+  size_t smat, part, aux;
+  void add(const Need& o) { smat = std::max(smat, o.smat), part = std::max(part, o.part), aux = std::max(aux, o.aux); }
 };
-void hi2_need(const amdr_dense* h, int nq, int k, TwoLevelNeed* need) {  // monotone in the pass size and in kc
-  Hi2Plan p;
-  hi2_plan(h, hi2_chunk(h, nq), k, hi_kc_max(k), &p);
-  need->smat = p.smat_bytes > need->smat ? p.smat_bytes : need->smat;
-  need->aux = p.aux_bytes + 256 > need->aux ? p.aux_bytes + 256 : need->aux;
-}
-void two_level_need(const amdr_dense* h, int nq, int k, TwoLevelNeed* need) {
-  if (hi_applies(h, nq, k)) hi2_need(h, nq, k, need);
-  const int chunk = two_level_chunk(nq, k);
-  TwoLevelPlan t;
-  for (int m : {chunk, nq % chunk}) {
-    if (m == 0) continue;
-    two_level_plan(h, m, k, &t);
-    need->add(t);
+// the score scratch of the one-launch serving step (dense_small_raw): nq rows of S
+size_t score_rows_bytes(const amdr_dense* h, int nq) { return (size_t)nq * (size_t)(((long)h->n + 31) / 32 * 32) * sizeof(float); }
+
+// One pass of m queries at depth k, from the plans the pass itself runs on (sizes only: without their launch grids).
+// Form Hi is sized for its widest candidate cut: the width level a handle has learnt does not enter.
+Need pass_need(const amdr_dense* h, Form form, int m, int k) {
+  if (form == Form::Scan) {
+    ScanPlan p;
+    make_plan(h->n, h->d, m, k, &p);
+    return {0, p.part_bytes, 0};
   }
-}
-int two_level_ensure(amdr_dense* h, int ws, int nq, int k, bool all = false) {
-  TwoLevelNeed need;
-  if (!all) {
-    two_level_need(h, nq, k, &need);
-  } else {
-    for (int kk = 1; kk <= k; ++kk) {
-      // a call's path is chosen on its whole batch; its passes (full chunks and a remainder of ANY size) then
-      // all run the two-level form: cover every m a pass can have
-      const bool hi = hi_applies(h, nq, kk);
-      if (!hi && !two_level_applies(h, nq < 95 ? nq : 95, kk) && !two_level_applies(h, nq, kk)) continue;
-      if (hi) hi2_need(h, nq, kk, &need);
-      TwoLevelPlan t;
-      const int cmax = two_level_chunk(nq, kk);
-      for (int m = 1; m <= cmax; ++m) {
-        two_level_plan(h, m, kk, &t);
-        need.add(t);
-      }
-    }
+  if (form == Form::TwoLevel) {
+    TwoLevelPlan t;
+    two_level_plan(h, m, k, &t, false);
+    return {t.m_bytes + t.s2_bytes, t.part_bytes, t.aux_bytes};
   }
-  int rc = need.smat ? h->smat[ws].ensure(need.smat) : AMDR_OK;
-  if (!rc && need.part) rc = h->part[ws].ensure(need.part);
-  if (!rc && need.aux) rc = h->aux[ws].ensure(need.aux);
+  if (form == Form::Hi) {
+    Hi2Plan p;
+    hi2_plan(h, m, k, hi_kc_max(k), &p, false);
+    return {p.smat_bytes, 0, p.aux_bytes};
+  }
+  DenseMfmaPlan p;  // RowWaves, Batched
+  dense_mfma_plan((long)h->n, h->d, m, k, &p, false);
+  return {p.s_bytes, p.part_bytes, 0};
+}
+// One call: the maximum over every pass its loop will run — the full chunk AND the remainder, planned for its own size
+// (a shorter pass can need MORE slab-list space: slabs(m) * m is not monotone in m).  Where the fp16 first pass applies,
+// its passes and the exact ones: a handle gives the pass up (and add() gives it back) between a reserve and a call.
+// (Hi2Plan grows with m in every term — the sample stride, hence qcap, with the number of query tiles: no remainder.)
+Need call_need(const amdr_dense* h, const Route& r, int nq, int k) {
+  const Form form = r.hi ? Form::TwoLevel : r.form;
+  const int chunk = r.hi ? two_level_chunk(nq, k) : r.chunk;
+  Need need = pass_need(h, form, chunk, k);
+  if (nq % chunk) need.add(pass_need(h, form, nq % chunk, k));
+  if (r.hi) need.add(pass_need(h, Form::Hi, hi2_chunk(h, nq), k));
+  return need;
+}
+// amdr_dense_reserve: the maximum of call_need over every call with nq <= nq_max and k <= k_max.  Within one form and
+// pass size the plans grow with k (the slab counts of DenseMfmaPlan do not depend on it), except the scan's, whose
+// grid depends on the staging capacity topk_cap(k): monotone inside a capacity class only.
+Need reserve_need(const amdr_dense* h, const DensePins& pins, int nq_max, int k_max) {
+  Need need{0, 0, 0};
+  // 1. the forms whose route k does not enter (see dense_route): every batch size (the scan's slab lists
+  //    grid_x(nq, k) * nq * k * 8 are monotone in neither argument; the passes of the row-waves form are the chunks
+  //    of these batch sizes) at the deepest k of every capacity class
+  int ks[8], nk = 0;
+  for (int k = 1; k < k_max; ++k)
+    if (topk_cap(k + 1) != topk_cap(k)) ks[nk++] = k;  // three classes up to AMDR_MAX_K
+  ks[nk++] = k_max;
+  int nq = 1;
+  for (; nq <= nq_max; ++nq) {
+    const Route r = dense_route(h, pins, nq, k_max);
+    if (r.form != Form::Scan && r.form != Form::RowWaves) break;
+    for (int i = 0; i < nk; ++i) need.add(pass_need(h, r.form, r.chunk, ks[i]));
+    if (r.form == Form::RowWaves) need.add({score_rows_bytes(h, r.chunk), 0, 0});  // (the same bytes: by construction now)
+  }
+  if (nq > nq_max) return need;
+  // 2. batches: at every depth the forms of [nq, nq_max] are those of its two ends (dense_route: one monotone threshold
+  //    above the first).  A call's passes — full chunks and a remainder of ANY size — all run its form: every pass
+  //    size up to the form's largest.  A smaller k takes more queries per two-level pass (a larger matrix of tile
+  //    maxima) and those forms' own applicability depends on k: they at every k, the batched form at its deepest.
+  int k_batched = 0;
+  for (int k = 1; k <= k_max; ++k) {
+    const Route lo = dense_route(h, pins, nq, k), hi = dense_route(h, pins, nq_max, k);
+    if (lo.form == Form::Batched || hi.form == Form::Batched) k_batched = k;
+    if (hi.hi) need.add(pass_need(h, Form::Hi, hi2_chunk(h, nq_max), k));  // (the fp16 pass does not look at nq)
+    if (hi.hi || lo.form == Form::TwoLevel || hi.form == Form::TwoLevel)
+      for (int m = two_level_chunk(nq_max, k); m >= 1; --m) need.add(pass_need(h, Form::TwoLevel, m, k));
+  }
+  if (k_batched)
+    for (int m = batched_chunk(h, nq_max); m >= 1; --m) need.add(pass_need(h, Form::Batched, m, k_batched));
+  return need;
+}
+int ensure_need(amdr_dense* h, int ws, const Need& need) {
+  int rc = h->smat[ws].ensure(need.smat);
+  if (!rc) rc = h->part[ws].ensure(need.part);
+  if (!rc) rc = h->aux[ws].ensure(need.aux);
   return rc;
 }
 
+// ---- running a search ----------------------------------------------------------------------------------------------------
+// `launch` (the scan of a pass) between a pair of the handle's profiling events (amdr_dense_profile_begin / _end:
+// bench.py roofline); a ring that is used up brackets nothing
+template <class F>
+int profiled(amdr_dense* h, hipStream_t st, F&& launch) {
+  const bool on = h->prof_on && (size_t)(h->prof_used + 2) <= h->prof_ev.size();
+  if (on) AMDR_HIP(hipEventRecord(h->prof_ev[h->prof_used], st));
+  const int rc = launch();
+  if (rc) return rc;
+  if (on) {
+    AMDR_HIP(hipEventRecord(h->prof_ev[h->prof_used + 1], st));
+    h->prof_used += 2;
+  }
+  return AMDR_OK;
+}
+
+// the nparts slab lists of each of nq queries -> its top k
+int launch_merge(const C32* part, int nparts, int nq, int k, int cap, float* out_scores, int64_t* out_ids, hipStream_t st) {
+  const size_t lds = (size_t)kWaves * cap * sizeof(C32) + kWaves * sizeof(int);
+  hipLaunchKernelGGL(dense_merge_kernel, dim3(nq), dim3(256), lds, st, part, nparts, nq, k, cap, out_scores, (long long*)out_ids);
+  AMDR_HIP(hipGetLastError());
+  return AMDR_OK;
+}
 // one top-k pass over a [m][ld] score matrix with `cols` valid columns (slab lists + merge, or direct)
 int topk_pass(const DenseMfmaPlan& p, const float* S, long cols, int m, int k, DevBuf& partb, float* out_scores,
               int64_t* out_ids, hipStream_t st) {
-  const bool direct = p.slabs == 1;
+  const bool direct = p.slabs == 1;  // one slab: its list is the answer, no merge launch
   int rc = dense_mfma_launch_topk(p, S, cols, m, k, partb.p, direct ? out_scores : nullptr, direct ? out_ids : nullptr, st);
-  if (rc) return rc;
-  if (!direct) {
-    size_t lds = (size_t)kWaves * p.cap * sizeof(C32) + kWaves * sizeof(int);
-    hipLaunchKernelGGL(dense_merge_kernel, dim3(m), dim3(256), lds, st, partb.as<C32>(), p.slabs, m, k, p.cap, out_scores,
-                       (long long*)out_ids);
-    AMDR_HIP(hipGetLastError());
+  if (rc || direct) return rc;
+  return launch_merge(partb.as<C32>(), p.slabs, m, k, p.cap, out_scores, out_ids, st);
+}
+
+// the image and the workspaces of the fp16 two-pass form; false: not available now (creation failed before, non-finite
+// matrix, or a stream is capturing and nothing was reserved) — the caller takes the exact form
+bool small_hi_ready(amdr_dense* h, int m, hipStream_t st) {
+  if (h->small_failed) return false;
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  const bool capturing = st && hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
+  if (!h->small) {
+    if (capturing) return false;
+    if (dense_small_create_from(h->device, h->X, h->n, h->d, &h->small) != AMDR_OK || !dense_small_usable(h->small)) {
+      h->small_failed = true;  // (a matrix the fp16 scale range cannot hold stays on the exact form)
+      return false;
+    }
+  }
+  const size_t need = (size_t)m * sizeof(float);
+  if (capturing && (h->small_eps.cap < need || !h->small_fb.p)) return false;
+  if (h->small_eps.ensure(need) != AMDR_OK) return false;
+  if (!h->small_fb.p) {
+    if (h->small_fb.ensure(sizeof(unsigned int)) != AMDR_OK) return false;
+    (void)hipMemset(h->small_fb.p, 0, sizeof(unsigned int));
+  }
+  return capturing ? true : dense_small_reserve(h->small, m) == AMDR_OK;
+}
+
+// Forms Batched and RowWaves: scores S[q][row] (fp32-MFMA tiles or the panel kernel for batches, one wave per (query,
+// row) for few queries on a short corpus), then slab top-k (+ merge when there are several slabs); with a tail, the
+// fusion pass by pass.
+int run_search_batched(amdr_dense* h, int ws, const DensePins& pins, const Route& r, const float* Q_dev, int nq, int k,
+                       float* scores_dev, int64_t* ids_dev, hipStream_t st, const FuseTail* tail) {
+  float* S = h->smat[ws].as<float>();
+  const long n = (long)h->n;
+  DenseMfmaPlan p;
+  int rc;
+  for (int q0 = 0; q0 < nq; q0 += r.chunk) {
+    const int m = nq - q0 < r.chunk ? nq - q0 : r.chunk;
+    if (q0 == 0 || m != r.chunk) dense_mfma_plan(n, h->d, m, k, &p);
+    const PassForm f = batched_pass_form(h, pins, r, p, m, k, tail);
+    const float* Qc = Q_dev + (size_t)q0 * h->d;
+    float* os = scores_dev + (size_t)q0 * k;
+    int64_t* oi = ids_dev + (size_t)q0 * k;
+    if (f.small_hi && small_hi_ready(h, m, st)) {
+      rc = profiled(h, st, [&] { return amdr_dense_small_approx_device(h->small, Qc, m, S, p.ld, h->small_eps.as<float>(), st); });
+      if (rc) return rc;
+      if ((rc = dense_hi_select_launch(tail, q0, S, p.ld, n, m, k, h->X, Qc, h->d, h->small_eps.as<float>(), os, oi,
+                                       h->small_fb.as<unsigned int>(), st)))
+        return rc;
+      continue;
+    }
+    rc = profiled(h, st, [&]() -> int {
+      if (f.scores == PassForm::RowWaves) {
+        hipLaunchKernelGGL(dense_all_scores_kernel, dim3(ceil_div((long)m * n, kWaves)), dim3(256), 0, st, h->X, n, h->d, Qc,
+                           m, p.ld, S);
+        AMDR_HIP(hipGetLastError());
+        return AMDR_OK;
+      }
+      if (f.scores == PassForm::Panel) {
+        DensePanelPlan pp;
+        dense_panel_plan(n, h->d, m, &pp);
+        return dense_panel_launch_scores(pp, h->X, n, h->d, Qc, m, p.ld, S, st);
+      }
+      return dense_mfma_launch_scores(p, h->X, n, h->d, Qc, m, S, st);
+    });
+    if (rc) return rc;
+    if (f.select_fuse) {
+      if ((rc = dense_select_fuse_launch(*tail, q0, S, p.ld, n, m, k, p.cap, os, oi, st))) return rc;
+      continue;
+    }
+    if ((rc = topk_pass(p, S, n, m, k, h->part[ws], os, oi, st))) return rc;
+    if (tail && (rc = dense_fuse_plain_launch(*tail, q0, m, k, os, oi, st))) return rc;
   }
   return AMDR_OK;
 }
@@ -741,16 +813,8 @@ int two_level_pass(amdr_dense* h, int ws, const float* Qc, int m, int k, float* 
   int* list = reinterpret_cast<int*>(aux + (size_t)m * k * (sizeof(int64_t) + sizeof(float)));
   int* count = list + (size_t)m * k;
   int rc;
-  const bool prof = h->prof_on && (size_t)(h->prof_used + 2) <= h->prof_ev.size();
   // 1. tile maxima (the scan: this is the launch the profiling events bracket)
-  if (prof) AMDR_HIP(hipEventRecord(h->prof_ev[h->prof_used], st));
-  DenseMfmaPlan scan = t.scan;
-  scan.ld = t.tk1.ld;
-  if ((rc = dense_mfma_launch_scores(scan, h->X, (long)h->n, h->d, Qc, m, M, st, 1))) return rc;
-  if (prof) {
-    AMDR_HIP(hipEventRecord(h->prof_ev[h->prof_used + 1], st));
-    h->prof_used += 2;
-  }
+  if ((rc = profiled(h, st, [&] { return dense_mfma_launch_scores(t.scan, h->X, (long)h->n, h->d, Qc, m, M, st, 1); }))) return rc;
   // 2. k candidate tiles per query, their sorted union
   if ((rc = topk_pass(t.tk1, M, t.tiles, m, k, h->part[ws], tile_max, tile_ids, st))) return rc;
   if ((rc = dense_tiles_unique_launch(tile_ids, m * k, t.tiles, list, count, st))) return rc;
@@ -763,8 +827,7 @@ int two_level_pass(amdr_dense* h, int ws, const float* Qc, int m, int k, float* 
 
 // One pass (<= 4 query tiles) of the round-4 tail: see dense_hi.hip.  Launches: sample, tau, one scan per query tile,
 // select, [gated: exact tile maxima, exact select], re-scoring, final top-k.
-int hi2_pass(amdr_dense* h, int ws, const float* Qc, int m, int k, int kc, float* out_scores, int64_t* out_ids, hipStream_t st,
-             int* flag) {
+int hi2_pass(amdr_dense* h, int ws, const float* Qc, int m, int k, int kc, float* out_scores, int64_t* out_ids, hipStream_t st) {
   Hi2Plan p;
   hi2_plan(h, m, k, kc, &p);
   unsigned char* sm = reinterpret_cast<unsigned char*>(h->smat[ws].p);
@@ -778,6 +841,7 @@ int hi2_pass(amdr_dense* h, int ws, const float* Qc, int m, int k, int kc, float
   int* unres = reinterpret_cast<int*>(ax + p.off_unres);
   float* tau = reinterpret_cast<float*>(ax + p.off_tau);
   unsigned int* qcount = reinterpret_cast<unsigned int*>(ax + p.off_qcount);
+  int* flag = reinterpret_cast<int*>(ax + p.off_flag);  // (reset by this pass's own tau kernel)
   unsigned int* stats = h->stats.as<unsigned int>();
   int rc;
   if ((rc = dense_hi2_launch_sample(h->X, (long)h->n, h->d, Qc, m, p.qtiles, MT, st, h->x_scale))) return rc;
@@ -789,15 +853,11 @@ int hi2_pass(amdr_dense* h, int ws, const float* Qc, int m, int k, int kc, float
     const int qt = dense_hi_max_queries(h->d);
     for (int y = 0; y < (split ? p.qtiles : 1); ++y) {
       const int q0 = y * qt, mq = split ? (m - q0 < qt ? m - q0 : qt) : m;
-      const bool prof = h->prof_on && (size_t)(h->prof_used + 2) <= h->prof_ev.size();
-      if (prof) AMDR_HIP(hipEventRecord(h->prof_ev[h->prof_used], st));
-      if ((rc = dense_hi2_launch_emit(h->X, (long)h->n, h->d, Qc + (size_t)q0 * h->d, mq, tau + q0, qlist + (size_t)q0 * p.qcap,
-                                      qcount + q0, p.qcap, st, h->x_scale, split ? 1 : p.qtiles)))
-        return rc;
-      if (prof) {
-        AMDR_HIP(hipEventRecord(h->prof_ev[h->prof_used + 1], st));
-        h->prof_used += 2;
-      }
+      rc = profiled(h, st, [&] {
+        return dense_hi2_launch_emit(h->X, (long)h->n, h->d, Qc + (size_t)q0 * h->d, mq, tau + q0, qlist + (size_t)q0 * p.qcap,
+                                     qcount + q0, p.qcap, st, h->x_scale, split ? 1 : p.qtiles);
+      });
+      if (rc) return rc;
     }
   }
   h->hi_queries += m;
@@ -812,30 +872,24 @@ int hi2_pass(amdr_dense* h, int ws, const float* Qc, int m, int k, int kc, float
   return dense_final_topk_launch(S2, p.ldS2, list, count, kc, kc, (long)h->n, m, k, out_scores, out_ids, st);
 }
 
-int run_search_two_level(amdr_dense* h, int ws, const float* Q_dev, int nq, int k, float* scores_dev, int64_t* ids_dev,
-                         hipStream_t st) {
-  int rc = two_level_ensure(h, ws, nq, k);
-  if (rc) return rc;
-  const bool hi = hi_applies(h, nq, k);
+// Forms TwoLevel and Hi.
+int run_search_two_level(amdr_dense* h, int ws, const DensePins& pins, Route r, const float* Q_dev, int nq, int k,
+                         float* scores_dev, int64_t* ids_dev, hipStream_t st) {
   hipStreamCaptureStatus cap_st = hipStreamCaptureStatusNone;
   (void)hipStreamIsCapturing(st, &cap_st);
   const bool capturing = cap_st != hipStreamCaptureStatusNone;
-  if (hi && !capturing) hi_adapt(h);
-  // a handle that gave the fp16 pass up runs the exact passes, ungated
-  const int kc_hi = hi && !h->hi_off ? hi_kc(k, hi_level_of(h)) : 0;
-  const int chunk = kc_hi ? hi2_chunk(h, nq) : two_level_chunk(nq, k);
-  // the gate flag: behind the largest list layout of this call (two_level_ensure sized aux for it)
-  int* flag = reinterpret_cast<int*>(reinterpret_cast<unsigned char*>(h->aux[ws].p) + h->aux[ws].cap - 256);
-  for (int q0 = 0; q0 < nq; q0 += chunk) {
-    const int m = nq - q0 < chunk ? nq - q0 : chunk;
+  if (r.hi && !capturing && hi_adapt(h, pins)) r = dense_route(h, pins, nq, k);  // a wider cut, or the pass given up
+  const bool hi = r.form == Form::Hi;
+  int rc;
+  for (int q0 = 0; q0 < nq; q0 += r.chunk) {
+    const int m = nq - q0 < r.chunk ? nq - q0 : r.chunk;
     const float* Qc = Q_dev + (size_t)q0 * h->d;
     float* os = scores_dev + (size_t)q0 * k;
     int64_t* oi = ids_dev + (size_t)q0 * k;
-    // (the flag is reset by the fp16 pass's own tau kernel)
-    rc = kc_hi ? hi2_pass(h, ws, Qc, m, k, kc_hi, os, oi, st, flag) : two_level_pass(h, ws, Qc, m, k, os, oi, st);
+    rc = hi ? hi2_pass(h, ws, Qc, m, k, r.kc, os, oi, st) : two_level_pass(h, ws, Qc, m, k, os, oi, st);
     if (rc) return rc;
   }
-  if (kc_hi && h->hi_host && !capturing && !h->hi_copy_pending) {  // what hi_adapt reads before a later search
+  if (hi && h->hi_host && !capturing && !h->hi_copy_pending) {  // what hi_adapt reads before a later search
     AMDR_HIP(hipMemcpyAsync(h->hi_host, h->stats.as<unsigned int>() + 2, 3 * sizeof(unsigned int), hipMemcpyDeviceToHost, st));
     AMDR_HIP(hipEventRecord(h->hi_ev, st));
     h->hi_copy_pending = true;
@@ -843,44 +897,47 @@ int run_search_two_level(amdr_dense* h, int ws, const float* Q_dev, int nq, int 
   return AMDR_OK;
 }
 
-int run_search(amdr_dense* h, int ws, const float* Q_dev, int nq, int k, float* scores_dev, int64_t* ids_dev,
-               hipStream_t st) {
-  if (hi_applies(h, nq, k) || two_level_applies(h, nq, k))
-    return run_search_two_level(h, ws, Q_dev, nq, k, scores_dev, ids_dev, st);
-  if (nq >= kBatchedMin && h->n > 0 && dense_mfma_supported(h->d))
-    return run_search_batched(h, ws, Q_dev, nq, k, scores_dev, ids_dev, st);
-  if (h->n > 0 && h->n <= kRowWavesMax) return run_search_batched(h, ws, Q_dev, nq, k, scores_dev, ids_dev, st, true);
+// Form Scan.
+int run_search_scan(amdr_dense* h, int ws, const float* Q_dev, int nq, int k, float* scores_dev, int64_t* ids_dev,
+                    hipStream_t st) {
   ScanPlan p;
   make_plan(h->n, h->d, nq, k, &p);
-  int rc = h->part[ws].ensure(p.part_bytes);
-  if (rc) return rc;
   C32* part = h->part[ws].as<C32>();
-  const bool prof = h->prof_on && (size_t)(h->prof_used + 2) <= h->prof_ev.size() && h->n > 0;
-  if (prof) AMDR_HIP(hipEventRecord(h->prof_ev[h->prof_used], st));
-  const bool direct = h->n > 0 && p.grid_x == 1;
+  const bool direct = h->n > 0 && p.grid_x == 1;  // single slab: its list is the answer
   float* fs = direct ? scores_dev : nullptr;
   int64_t* fi = direct ? ids_dev : nullptr;
   if (h->n > 0) {
-    switch (p.nq_per_block) {
-      case 1: rc = launch_scan_ch<1>(p, h, Q_dev, nq, k, part, fs, fi, st); break;
-      case 2: rc = launch_scan_ch<2>(p, h, Q_dev, nq, k, part, fs, fi, st); break;
-      case 4: rc = launch_scan_ch<4>(p, h, Q_dev, nq, k, part, fs, fi, st); break;
-      default: rc = launch_scan_ch<8>(p, h, Q_dev, nq, k, part, fs, fi, st); break;
-    }
+    const int rc = profiled(h, st, [&] {
+      switch (p.nq_per_block) {
+        case 1: return launch_scan_ch<1>(p, h, Q_dev, nq, k, part, fs, fi, st);
+        case 2: return launch_scan_ch<2>(p, h, Q_dev, nq, k, part, fs, fi, st);
+        case 4: return launch_scan_ch<4>(p, h, Q_dev, nq, k, part, fs, fi, st);
+        default: return launch_scan_ch<8>(p, h, Q_dev, nq, k, part, fs, fi, st);
+      }
+    });
     if (rc) return rc;
-    AMDR_HIP(hipGetLastError());
-  }
-  if (prof) {
-    AMDR_HIP(hipEventRecord(h->prof_ev[h->prof_used + 1], st));
-    h->prof_used += 2;
   }
   if (direct) return AMDR_OK;
-  int nparts = h->n > 0 ? p.grid_x : 0;
-  size_t lds = (size_t)kWaves * p.cap * sizeof(C32) + kWaves * sizeof(int);
-  hipLaunchKernelGGL(dense_merge_kernel, dim3(nq), dim3(256), lds, st, part, nparts, nq, k, p.cap, scores_dev,
-                     (long long*)ids_dev);
-  AMDR_HIP(hipGetLastError());
-  return AMDR_OK;
+  return launch_merge(part, h->n > 0 ? p.grid_x : 0, nq, k, p.cap, scores_dev, ids_dev, st);  // (an empty index: padding)
+}
+
+// One search on workspace `ws`; with a tail (amdr_dense_search_fuse_device), the fusion behind it — pass by pass in the
+// Batched form, one plain launch over the finished lists behind the others.
+int run_search(amdr_dense* h, int ws, const float* Q_dev, int nq, int k, float* scores_dev, int64_t* ids_dev,
+               hipStream_t st, const FuseTail* tail = nullptr) {
+  const DensePins pins = read_pins();
+  const Route r = dense_route(h, pins, nq, k);
+  int rc = ensure_need(h, ws, call_need(h, r, nq, k));
+  if (rc) return rc;
+  switch (r.form) {
+    case Form::Batched: return run_search_batched(h, ws, pins, r, Q_dev, nq, k, scores_dev, ids_dev, st, tail);
+    case Form::RowWaves: rc = run_search_batched(h, ws, pins, r, Q_dev, nq, k, scores_dev, ids_dev, st, nullptr); break;
+    case Form::TwoLevel:
+    case Form::Hi: rc = run_search_two_level(h, ws, pins, r, Q_dev, nq, k, scores_dev, ids_dev, st); break;
+    case Form::Scan: rc = run_search_scan(h, ws, Q_dev, nq, k, scores_dev, ids_dev, st); break;
+  }
+  if (rc || !tail) return rc;
+  return dense_fuse_plain_launch(*tail, 0, nq, k, scores_dev, ids_dev, st);
 }
 
 int check_search_args(const amdr_dense* h, const void* Q, int nq, int k, const void* s, const void* i) {
@@ -922,14 +979,13 @@ int update_stats(amdr_dense* h, int64_t row0, int64_t rows) {
 
 namespace amdr {
 int dense_small_raw(amdr_dense_t* h, int nq, DenseRaw* out) {
-  const long ld = ((long)h->n + 31) / 32 * 32;
-  int rc = h->smat[0].ensure((size_t)nq * (size_t)ld * sizeof(float));
+  int rc = h->smat[0].ensure(score_rows_bytes(h, nq));
   if (rc) return rc;
   out->X = h->X;
   out->n = (long)h->n;
   out->d = h->d;
   out->S = h->smat[0].as<float>();
-  out->ld = ld;
+  out->ld = ((long)h->n + 31) / 32 * 32;
   return AMDR_OK;
 }
 std::mutex& dense_mutex(amdr_dense_t* h) { return h->mu; }
@@ -1061,36 +1117,13 @@ int amdr_dense_reserve(amdr_dense_t* h, int32_t nq_max, int32_t k_max) {
   AMDR_REQUIRE(nq_max >= 1 && k_max >= 1 && k_max <= AMDR_MAX_K, "dense_reserve: bad sizes");
   std::lock_guard<std::mutex> g(h->mu);
   AMDR_HIP(hipSetDevice(h->device));
-  ScanPlan p;
-  make_plan(h->n, h->d, nq_max, k_max, &p);
-  int rc = h->part[0].ensure(p.part_bytes);
+  const DensePins pins = read_pins();
+  int rc = ensure_need(h, 0, reserve_need(h, pins, nq_max, k_max));
   if (rc) return rc;
-  // batches on a large matrix take the two-level form (every batch size <= nq_max and depth <= k_max that does is
-  // covered, see two_level_ensure); longer ones the panel kernel + score matrix
-  if ((rc = two_level_ensure(h, 0, nq_max, k_max, true))) return rc;
-  if (hi_applies(h, nq_max, k_max) || two_level_applies(h, nq_max, k_max)) {
-  } else if (nq_max >= kBatchedMin && h->n > 0 && dense_mfma_supported(h->d)) {
-    DenseMfmaPlan mp;
-    const int cmax = batched_chunk(h, nq_max);
-    dense_mfma_plan((long)h->n, h->d, cmax, k_max, &mp);
-    if ((rc = h->smat[0].ensure(mp.s_bytes))) return rc;
-    size_t part_need = 0;  // every pass size a call within nq_max can have (slab lists: not monotone in the size)
-    for (int m = 1; m <= cmax; ++m) {
-      dense_mfma_plan((long)h->n, h->d, m, k_max, &mp);
-      part_need = mp.part_bytes > part_need ? mp.part_bytes : part_need;
-    }
-    if ((rc = h->part[0].ensure(part_need))) return rc;
-  }
-  if (h->n > 0 && h->n <= kRowWavesMax) {  // the 1-4 query call on a short corpus also goes through S
-    DenseMfmaPlan mp;
-    dense_mfma_plan((long)h->n, h->d, nq_max < kBatchedMin ? nq_max : kBatchedMin - 1, k_max, &mp);
-    if ((rc = h->smat[0].ensure(mp.s_bytes))) return rc;
-    if ((rc = h->part[0].ensure(mp.part_bytes))) return rc;
-  }
   if ((rc = h->qbuf.ensure((size_t)nq_max * h->d * sizeof(float)))) return rc;
   if ((rc = h->sbuf.ensure((size_t)nq_max * k_max * sizeof(float)))) return rc;
-  if (small_hi_shape(h, nq_max, k_max < 12 ? k_max : 12, 0))  // (so that a later capture finds the two-pass form's buffers)
-    (void)small_hi_ready(h, batched_chunk(h, nq_max) < nq_max ? batched_chunk(h, nq_max) : nq_max, nullptr);
+  if (small_hi_shape(h, pins, nq_max, k_max < 12 ? k_max : 12, 0))  // (so that a later capture finds the two-pass form's buffers)
+    (void)small_hi_ready(h, batched_chunk(h, nq_max), nullptr);
   return h->ibuf.ensure((size_t)nq_max * k_max * sizeof(int64_t));
 }
 
@@ -1118,13 +1151,8 @@ int amdr_dense_search_fuse_device(amdr_dense_t* h, const float* Q_dev, int32_t n
   if (nq == 0) return AMDR_OK;
   std::lock_guard<std::mutex> g(h->mu);
   AMDR_HIP(hipSetDevice(h->device));
-  hipStream_t st = (hipStream_t)stream;
   FuseTail tail{p, dense_row2uid, bm25_ids, bm25_scores, kb, bm25_row2uid, out_ids, out_vals, out_mask, out_count};
-  if (!hi_applies(h, nq, k) && !two_level_applies(h, nq, k) && nq >= kBatchedMin && h->n > 0 &&
-      dense_mfma_supported(h->d))
-    return run_search_batched(h, 0, Q_dev, nq, k, dense_scores_dev, dense_ids_dev, st, false, &tail);
-  if ((rc = run_search(h, 0, Q_dev, nq, k, dense_scores_dev, dense_ids_dev, st))) return rc;
-  return dense_fuse_plain_launch(tail, 0, nq, k, dense_scores_dev, dense_ids_dev, st);
+  return run_search(h, 0, Q_dev, nq, k, dense_scores_dev, dense_ids_dev, (hipStream_t)stream, &tail);
 }
 
 int amdr_dense_search(amdr_dense_t* h, const float* Q_host, int32_t nq, int32_t k, float* scores_host,
@@ -1180,98 +1208,62 @@ int amdr_dense_read_rows(const amdr_dense_t* h, int64_t row0, int64_t nrows, flo
   return AMDR_OK;
 }
 
-int amdr_dense_workspace_plan(int64_t n, int32_t d, int32_t nq, int32_t k, int64_t* out6) {
+int amdr_dense_workspace_plan(int64_t n, int32_t d, int32_t nq_max, int32_t k_max, int32_t nq, int32_t k, int64_t* out6) {
   AMDR_REQUIRE(out6 != nullptr, "dense_workspace_plan: null");
   AMDR_REQUIRE(n >= 1 && n < (1ll << 32) && d >= 4 && d <= AMDR_MAX_DIM && d % 4 == 0, "dense_workspace_plan: bad shape");
-  AMDR_REQUIRE(nq >= 1 && k >= 1 && k <= AMDR_MAX_K, "dense_workspace_plan: bad sizes");
+  AMDR_REQUIRE(nq_max >= 1 && k_max >= 1 && k_max <= AMDR_MAX_K && nq >= 1 && k >= 1 && k <= AMDR_MAX_K,
+               "dense_workspace_plan: bad sizes");
   amdr_dense h;  // shape only: no device is touched
   h.n = n;
   h.d = d;
-  for (int i = 0; i < 6; ++i) out6[i] = 0;
-  auto mx = [](int64_t& a, size_t b) { a = (int64_t)b > a ? (int64_t)b : a; };
   h.hi_ok = dense_hi_supported(d);  // shape only: the statistics of a real matrix can only take the fp16 first pass away
-  if (hi_applies(&h, nq, k) || two_level_applies(&h, nq, k)) {
-    TwoLevelNeed need, used;
-    two_level_need(&h, nq, k, &need);
-    out6[0] = (int64_t)need.smat, out6[1] = (int64_t)need.part, out6[2] = (int64_t)need.aux;
-    if (hi_applies(&h, nq, k)) {  // passes of up to four query tiles, any of the three widths
-      const int c2 = hi2_chunk(&h, nq);
-      for (int q0 = 0; q0 < nq; q0 += c2)
-        for (int l = 0; l < kHiLevels; ++l) {
-          Hi2Plan p;
-          hi2_plan(&h, nq - q0 < c2 ? nq - q0 : c2, k, hi_kc(k, l), &p);
-          used.smat = p.smat_bytes > used.smat ? p.smat_bytes : used.smat;
-          used.aux = p.aux_bytes + 256 > used.aux ? p.aux_bytes + 256 : used.aux;
-        }
-    }
-    const int chunk = two_level_chunk(nq, k);
-    for (int q0 = 0; q0 < nq; q0 += chunk) {  // the exact passes (a handle that gave the fp16 pass up runs them too)
-      TwoLevelPlan t;
-      two_level_plan(&h, nq - q0 < chunk ? nq - q0 : chunk, k, &t);
-      used.add(t);
-    }
-    out6[3] = (int64_t)used.smat, out6[4] = (int64_t)used.part, out6[5] = (int64_t)used.aux;
-  } else if (nq >= kBatchedMin && dense_mfma_supported(d)) {
-    const int chunk = batched_chunk(&h, nq);
-    DenseMfmaPlan p;
-    dense_mfma_plan((long)n, d, chunk, k, &p);
-    out6[0] = (int64_t)p.s_bytes, out6[1] = (int64_t)batched_part_need(&h, nq, k);
-    for (int q0 = 0; q0 < nq; q0 += chunk) {
-      dense_mfma_plan((long)n, d, nq - q0 < chunk ? nq - q0 : chunk, k, &p);
-      mx(out6[3], p.s_bytes), mx(out6[4], p.part_bytes);
-    }
-  }
+  const DensePins pins = read_pins();
+  const Need res = reserve_need(&h, pins, nq_max, k_max), used = call_need(&h, dense_route(&h, pins, nq, k), nq, k);
+  out6[0] = (int64_t)res.smat, out6[1] = (int64_t)res.part, out6[2] = (int64_t)res.aux;
+  out6[3] = (int64_t)used.smat, out6[4] = (int64_t)used.part, out6[5] = (int64_t)used.aux;
   return AMDR_OK;
 }
 
 int amdr_dense_plan_info(const amdr_dense_t* h, int32_t nq, int32_t k, char* buf, int32_t buf_len) {
   AMDR_REQUIRE(h && buf && buf_len > 0, "dense_plan_info: null");
   AMDR_REQUIRE(nq >= 1 && k >= 1 && k <= AMDR_MAX_K, "dense_plan_info: bad sizes");
+  const DensePins pins = read_pins();
+  const Route r = dense_route(h, pins, nq, k);
+  const int m = r.chunk;
   if (h->n <= 0) {
     snprintf(buf, buf_len, "empty index");
-    return AMDR_OK;
-  }
-  if (hi_applies(h, nq, k) && !h->hi_off) {
-    const int m = hi2_chunk(h, nq), kc = hi_kc(k, hi_level_of(h));
+  } else if (r.form == Form::Hi) {
     Hi2Plan p;
-    hi2_plan(h, m, k, kc, &p);
+    hi2_plan(h, m, k, r.kc, &p);
     snprintf(buf, buf_len,
              "dense_hi_tilemax_kernel fp16 first pass queries_per_launch=%d scans_per_launch=%d (%d per scan, one tail): per-query lists of the "
              "approximate tile maxima above a sampled threshold (every %ld-th tile, width level %d) -> top-%d + rounding-bound "
              "check + exact re-scoring of each query's tiles at or above its cut (<= %d each) + top-k: 4 launches behind the "
              "scan(s), the exact first pass behind a device flag in 2",
              m, p.qtiles, m < dense_hi_max_queries(h->d) ? m : dense_hi_max_queries(h->d),
-             dense_hi2_sample_stride((long)h->n, p.qtiles), hi_level_of(h), kc, kc);
-    return AMDR_OK;
-  }
-  if (hi_applies(h, nq, k) || two_level_applies(h, nq, k)) {  // (hi_applies: the handle gave the fp16 pass up)
+             dense_hi2_sample_stride((long)h->n, p.qtiles), r.hi_level, r.kc, r.kc);
+  } else if (r.form == Form::TwoLevel) {
     TwoLevelPlan t;
-    const int m = two_level_chunk(nq, k);
     two_level_plan(h, m, k, &t);
     snprintf(buf, buf_len,
              "dense_mfma_scores_kernel tile-maxima grid=%dx%d queries_per_launch=%d two-level: top-%d of %ld tile maxima "
              "+ re-scoring of <= %d candidate tiles + top-k%s",
              t.scan.grid_x, t.scan.grid_y, m, k, t.tiles, m * k,
-             hi_applies(h, nq, k) ? " (fp16 first pass given up: too many unresolved queries)" : "");
-    return AMDR_OK;
-  }
-  const bool batched = nq >= kBatchedMin && dense_mfma_supported(h->d);
-  if (batched || h->n <= kRowWavesMax) {
-    const int m = batched_chunk(h, nq);
+             r.hi ? " (fp16 first pass given up: too many unresolved queries)" : "");
+  } else if (r.form != Form::Scan) {
     DenseMfmaPlan p;
     dense_mfma_plan((long)h->n, h->d, m, k, &p);
-    if (batched && p.slabs == 1 && small_hi_shape(h, m < nq ? m : nq, k, 0) && !h->small_failed) {
+    const PassForm f = batched_pass_form(h, pins, r, p, m, k, nullptr);
+    const char* tail = p.slabs == 1 ? "scores_slab_topk_kernel" : "scores_slab_topk_kernel + dense_merge_kernel";
+    if (f.small_hi && !h->small_failed) {
       snprintf(buf, buf_len,
                "dsh_scores_kernel fp16 first pass queries_per_launch=%d (dsh_split_queries_kernel + v_mfma_f32_32x32x16_f16 on "
                "fp16 roundings of both operands, proven per-query bound) + dense_hi_select_fuse_kernel (rows inside 2 eps of the "
                "k-th best re-scored exactly, top-k, fusion); exact form: dense_panel_scores_kernel",
-               m < nq ? m : nq);
-      return AMDR_OK;
-    }
-    const char* tail = p.slabs == 1 ? "scores_slab_topk_kernel" : "scores_slab_topk_kernel + dense_merge_kernel";
-    if (!batched) {
+               m);
+    } else if (f.scores == PassForm::RowWaves) {
       snprintf(buf, buf_len, "dense_all_scores_kernel (one wave per query x row) + %s", tail);
-    } else if (dense_panel_supported((long)h->n, h->d, m)) {
+    } else if (f.scores == PassForm::Panel) {
       DensePanelPlan pp;
       dense_panel_plan((long)h->n, h->d, m, &pp);
       snprintf(buf, buf_len, "dense_panel_scores_kernel nb=%d parts=%d blocks=%d queries_per_launch=%d + %s", pp.nb,
@@ -1280,12 +1272,12 @@ int amdr_dense_plan_info(const amdr_dense_t* h, int32_t nq, int32_t k, char* buf
       snprintf(buf, buf_len, "dense_mfma_scores_kernel query-tiles-in-LDS grid=%dx%d queries_per_launch=%d + %s",
                p.grid_x, p.grid_y, m, tail);
     }
-    return AMDR_OK;
+  } else {
+    ScanPlan p;
+    make_plan(h->n, h->d, nq, k, &p);
+    snprintf(buf, buf_len, "dense_scan_topk_kernel<NQ=%d> grid=%dx%d%s", p.nq_per_block, p.grid_x, p.grid_y,
+             p.grid_x == 1 ? "" : " + dense_merge_kernel");
   }
-  ScanPlan p;
-  make_plan(h->n, h->d, nq, k, &p);
-  snprintf(buf, buf_len, "dense_scan_topk_kernel<NQ=%d> grid=%dx%d%s", p.nq_per_block, p.grid_x, p.grid_y,
-           p.grid_x == 1 ? "" : " + dense_merge_kernel");
   return AMDR_OK;
 }
 
@@ -1302,7 +1294,8 @@ int amdr_dense_hi_counters(amdr_dense_t* h, int64_t* out6) {
     out6[1] = (int64_t)c[0];
     out6[5] = (int64_t)c[1];
   }
-  out6[2] = hi_level_of(h);
+  const DensePins pins = read_pins();
+  out6[2] = pins.hi_level >= 0 ? pins.hi_level : h->hi_level;
   out6[3] = h->hi_ok && !h->hi_off ? 1 : 0;
   out6[4] = h->hi_passes;
   return AMDR_OK;

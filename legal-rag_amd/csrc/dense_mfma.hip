@@ -770,11 +770,11 @@ static long plan_slabs(long tiles, long q_tiles, int waves) {
   return gx;
 }
 
-void dense_mfma_plan(long n, int d, int nq, int k, DenseMfmaPlan* p) {
+void dense_mfma_plan(long n, int d, int nq, int k, DenseMfmaPlan* p, bool grid) {
   const int kBW = scores_waves(d);
   p->q_tiles = ceil_div(nq, 32);
   const long tiles = (n + 31) / 32;
-  const long gx = plan_slabs(tiles, p->q_tiles, kBW);
+  const long gx = grid ? plan_slabs(tiles, p->q_tiles, kBW) : 1;
   long tiles_per_block = (tiles + gx - 1) / gx;
   tiles_per_block = ((tiles_per_block + kBW - 1) / kBW) * kBW;
   p->rows_per_block = tiles_per_block * 32;

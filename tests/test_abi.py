@@ -99,7 +99,7 @@ def test_dense_workspace_covers_every_pass(monkeypatch):
     for n in (13_000_000, 12_345_678, 20_000_000, 40_000_000, 3_000_000, 600_000):
         for k in (1, 10, 80, 256):
             for nq in (5, 37, 95, 96, 97, 100, 131, 185, 191, 192, 193, 250, 1000):
-                res, used = _native.dense_workspace_plan(n, 768, nq, k)
+                res, used = _native.dense_workspace_plan(n, 768, nq, k, nq, k)
                 assert all(u <= r for u, r in zip(used, res)), (n, k, nq, res, used)
                 checked += 1
                 two_level += int(res[2] > 0)
@@ -107,7 +107,7 @@ def test_dense_workspace_covers_every_pass(monkeypatch):
     # the advisor's worked example, pinned: remainder 89 needs more list space than the chunk of 96
     monkeypatch.setenv("AMDR_DENSE_TWO_LEVEL", "1")
     monkeypatch.setenv("AMDR_DENSE_HI", "0")  # the exact first pass (32-query tiles, chunks of 96)
-    res, used = _native.dense_workspace_plan(13_000_000, 768, 185, 10)
+    res, used = _native.dense_workspace_plan(13_000_000, 768, 185, 10, 185, 10)
     assert used[1] == 170880 and res[1] >= used[1]
     # the fp16 first pass (chunks of 64, k + 23 candidate tiles per query) and the exact chain behind its flag
     for hi in ("0", "1"):
@@ -116,7 +116,7 @@ def test_dense_workspace_covers_every_pass(monkeypatch):
             for d in (128, 384, 768, 896, 1024):
                 for k in (1, 10, 80, 127, 128):
                     for nq in (5, 37, 64, 65, 100, 129):
-                        res, used = _native.dense_workspace_plan(n, d, nq, k)
+                        res, used = _native.dense_workspace_plan(n, d, nq, k, nq, k)
                         assert all(u <= r for u, r in zip(used, res)), (hi, n, d, k, nq, res, used)
 
 
@@ -149,6 +149,56 @@ def test_bm25_reserve_covers_every_call():
     from legal_rag_amd import _native
     for n in (1, 591, 1260, 2048, 2049, 4097, 5000, 100_000, 10_000_000):
         assert _reserve_sweep(lambda a, b, c, d: _native.bm25_workspace_plan(n, a, b, c, d)) > 10_000, n
+
+
+# the dense sweep is thinner than SWEEP_NQ x SWEEP_K (a reserve of a batch on a large matrix evaluates tens of thousands of
+# plans: ~1.5 ms): the batch sizes at which the form or the pass size changes, the depths at which topk_cap (64 | 65,
+# 192 | 193), the fp16 pass's limit (127 | 128) and its candidate widths step
+DENSE_NQ = (1, 2, 3, 4, 5, 6, 7, 8, 9, 63, 64, 65, 95, 96, 97, 191, 192, 193, 255, 256, 257)
+DENSE_NQ_LONG = (4095, 4096, 37_376)  # the short matrices: around the fp16 two-pass form, the largest serving batch
+DENSE_K = tuple(range(1, 21)) + (63, 64, 65, 127, 128, 191, 192, 193, 255, 256)
+DENSE_PINS = ({}, {"AMDR_DENSE_TWO_LEVEL": "1", "AMDR_DENSE_HI": "0"}, {"AMDR_DENSE_TWO_LEVEL": "1", "AMDR_DENSE_HI": "1"})
+
+
+def test_dense_reserve_covers_every_call(monkeypatch):
+    """amdr_dense_reserve(nq_max, k_max) sizes smat, part and aux for every "_device" call with nq <= nq_max, k <= k_max,
+    whichever form the call takes.  The scan's slab lists grid_x(nq, k) * nq * k * 8 are monotone in neither argument:
+    20 000 rows, (4, 192) takes 625 row slabs = 3 840 000 B where (4, 256) takes 313 = 2 564 096 B; 200 000 x 100 (a
+    dimension outside the MFMA forms: every batch scans), (8, 10) 1 231 360 B where (9, 10) takes 720 000 B.
+    Host-only arithmetic (amdr_dense_workspace_plan): no device."""
+    import numpy as np
+    from legal_rag_amd import _native
+
+    def sweep(n, d, nqs, ks):
+        R = np.zeros((len(nqs), len(ks), 3), dtype=np.int64)
+        U = np.zeros_like(R)
+        for a, nq in enumerate(nqs):
+            for b, k in enumerate(ks):
+                R[a, b], U[a, b] = _native.dense_workspace_plan(n, d, nq, k, nq, k)
+        need = np.maximum.accumulate(np.maximum.accumulate(U, axis=0), axis=1)
+        bad = np.argwhere(need > R)  # separately for smat, part and aux
+        assert bad.size == 0, (n, d, [(nqs[a], ks[b], ("smat", "part", "aux")[c], int(R[a, b, c]), int(need[a, b, c]))
+                                      for a, b, c in bad[:8]])
+        return bool(np.any(need > U))  # some smaller call uses more than the call at (nq_max, k_max) itself
+
+    non_monotone = 0
+    for n, d in ((20_000, 128), (20_000, 768), (200_000, 100)):
+        non_monotone += sweep(n, d, DENSE_NQ, DENSE_K)
+    for n, d in ((600, 768), (1024, 768)):
+        non_monotone += sweep(n, d, DENSE_NQ + DENSE_NQ_LONG, DENSE_K)
+    for pins in DENSE_PINS:
+        for key, v in pins.items():
+            monkeypatch.setenv(key, v)
+        non_monotone += sweep(600_000, 768, DENSE_NQ, DENSE_K)
+        for d in (768, 1024):
+            non_monotone += sweep(13_000_000, d, DENSE_NQ, DENSE_K)
+    assert non_monotone >= 3
+    # the two worked examples: the smaller call needs more than the call at the bounds, and the reserve covers it
+    for n, d, nq_max, k_max, nq, k, part in ((20_000, 128, 4, 256, 4, 192, 3_840_000), (20_000, 768, 4, 256, 4, 192, 3_840_000),
+                                             (200_000, 100, 9, 10, 8, 10, 1_231_360)):
+        res, used = _native.dense_workspace_plan(n, d, nq_max, k_max, nq, k)
+        assert used[1] == part and res[1] >= part, (n, d, res, used)
+        assert _native.dense_workspace_plan(n, d, nq_max, k_max, nq_max, k_max)[1][1] < part
 
 
 @pytest.mark.parametrize("n, k_max, ks", [(100_000, 17, range(9, 17)), (5000, 18, range(13, 18)),

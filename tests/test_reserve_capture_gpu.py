@@ -101,7 +101,7 @@ def check_topk(S64, s, i, k, gap=TOL):
 
 # ---- dense -------------------------------------------------------------------------------------------------------------
 DENSE_CASES = {
-    # name: (n, d, nq_max, k_max, env, {nq range: plan_info substring})
+    # name: (n, d, nq_max, k_max, env, {nq range: plan_info substring}[, depths beside k_grid(k_max)])
     "row-waves-tile-panel": (600, 768, 128, 64, {}, [((1, 4), "dense_all_scores_kernel"),
                                                      ((5, 95), "query-tiles-in-LDS"),
                                                      ((96, 128), "dense_panel_scores_kernel")]),
@@ -113,13 +113,19 @@ DENSE_CASES = {
                                                        ((5, 95), "query-tiles-in-LDS"),
                                                        ((96, 4095), "dense_panel_scores_kernel"),
                                                        ((4096, 4096), "dsh_scores_kernel")]),
+    # the scan's slab lists grid_x(nq, k) * nq * k * 8 are monotone in neither argument: a dimension outside the MFMA
+    # forms (every batch scans; 8 queries take 1 231 360 B, 9 take 720 000), and k = 192 against 256 (half the staging
+    # capacity: four queries share a block, 625 row slabs against 313)
+    "scan-only-dim": (200_000, 100, 9, 10, {}, [((1, 9), "dense_scan_topk_kernel")]),
+    "scan-deep-k": (20_000, 128, 4, 256, {}, [((1, 4), "dense_scan_topk_kernel")], (191, 192, 193)),
 }
 
 
 @pytest.mark.parametrize("case", list(DENSE_CASES))
 def test_dense_reserve_then_capture(case, monkeypatch):
     nat = _nat()
-    n, d, nq_max, k_max, env, forms = DENSE_CASES[case]
+    n, d, nq_max, k_max, env, forms = DENSE_CASES[case][:6]
+    ks = sorted(set(k_grid(k_max)).union(*DENSE_CASES[case][6:]))
     for key, v in env.items():
         monkeypatch.setenv(key, v)
     rng = np.random.default_rng(len(case) * 31 + n)
@@ -132,7 +138,7 @@ def test_dense_reserve_then_capture(case, monkeypatch):
     Qd = torch.from_numpy(Qall).to(DEV)
     seen = set()
     for nq in nq_grid(nq_max):
-        for k in k_grid(k_max):
+        for k in ks:
             plan = idx.plan_info(nq, k)
             want = [f for (lo, hi), f in forms if lo <= nq <= hi]
             assert len(want) == 1 and want[0] in plan, (case, nq, k, plan)
