@@ -37,7 +37,7 @@ struct amdr_bm25 {
   hipStream_t stream = nullptr;
   std::mutex mu;
   DevBuf part[2], qterms, qptr, sbuf, ibuf, full;  // part[0]: "_device" calls, part[1]: host-pointer calls (see dense.hip)
-  DevBuf ticket;  // 64 zeroed ints: arrival counters of the one-launch serving step (fuse.hip), self-resetting
+  DevBuf ticket;  // 64 zeroed ints: arrival counters of the one-launch serving step (dense_tail.hip), self-resetting
 };
 
 namespace {

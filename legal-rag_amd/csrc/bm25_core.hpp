@@ -1,5 +1,5 @@
 // Device code of the BM25 channel (see bm25.hip for the design notes): scoring of one (query, slab) + ranking, shared by
-// bm25.hip's kernels and the one-launch serving step in fuse.hip.  Both translation units are compiled with
+// bm25.hip's kernels and the one-launch serving step in dense_tail.hip.  Both translation units are compiled with
 // -ffp-contract=off (fp64, operand for operand what rank_bm25's numpy expression evaluates).
 #pragma once
 #include "common.hpp"
@@ -262,7 +262,7 @@ __device__ __forceinline__ int bm25_rank_slab(const double* sc, int m, int k, lo
 // kernel with every bucket inside carried the 32-register variant's VGPR count, 105, at every corpus size).
 // One (query, slab) of the BM25 channel by the WAVES waves that call it (threadIdx.x < WAVES * 64; WAVES = 1: a single
 // wave, no block barrier inside) — the body of bm25_score_topk_kernel, callable from the one-launch serving step of
-// fuse.hip (hybrid_small_kernel) as well: the same instructions, hence the same bits.
+// dense_tail.hip (hybrid_small_kernel) as well: the same instructions, hence the same bits.
 template <int WAVES, int NVT>
 __device__ __forceinline__ void bm25_block_query(
     const long long* __restrict__ term_ptr, const int* __restrict__ post_doc, const double* __restrict__ post_w,

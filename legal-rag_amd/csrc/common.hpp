@@ -126,7 +126,7 @@ int dense_final_topk_launch(const float* S, long ldS, const int* list, const int
                             long n_real, int m, int k, float* fin_scores, int64_t* fin_ids, hipStream_t st);
 
 
-// ---- dense top-k + fusion in one call (fuse.hip; dense.hip amdr_dense_search_fuse_device) ----
+// ---- dense top-k + fusion in one call (dense_tail.hip; dense.hip amdr_dense_search_fuse_device) ----
 struct FuseTail {  // the fusion that follows the dense channel: parameters, the BM25 lists, the outputs (device pointers)
   const amdr_fuse_params_t* p;
   const int64_t* dense_row2uid;
@@ -143,7 +143,7 @@ struct FuseTail {  // the fusion that follows the dense channel: parameters, the
 int dense_small_create_from(int device, const float* X, int64_t n, int d, amdr_dense_small_t** out);
 int dense_small_reserve(amdr_dense_small_t* h, int nq_max);
 bool dense_small_usable(const amdr_dense_small_t* h);
-// second pass of the two-pass long-batch form (fuse.hip dense_hi_select_fuse_kernel): candidates inside the proven margin
+// second pass of the two-pass long-batch form (dense_tail.hip dense_hi_select_fuse_kernel): candidates inside the proven margin
 // of the approximate scores in S, exact dots, top-k (+ the fusion when t != nullptr)
 int dense_hi_select_launch(const FuseTail* t, int q0, const float* S, long ldS, long n, int m, int kd, const float* X,
                            const float* Q, int d, const float* eps, float* fin_scores, int64_t* fin_ids,
@@ -157,7 +157,7 @@ int dense_select_fuse_launch(const FuseTail& t, int q0, const float* S, long ldS
 int dense_fuse_plain_launch(const FuseTail& t, int q0, int m, int kd, const float* dense_scores, const int64_t* dense_ids,
                             hipStream_t st);
 
-// ---- the one-launch serving step (fuse.hip hybrid_small_kernel): what it needs from the two handles --------------
+// ---- the one-launch serving step (dense_tail.hip hybrid_small_kernel): what it needs from the two handles --------------
 struct DenseRaw {
   const float* X;
   long n;

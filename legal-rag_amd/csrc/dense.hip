@@ -286,7 +286,7 @@ struct amdr_dense {
   hipEvent_t hi_ev = nullptr;       // recorded behind that copy: hi_adapt reads hi_host only once it has completed
   bool hi_copy_pending = false;
   unsigned int hi_seen[3] = {0u, 0u, 0u};  // the last completed copy
-  // two-pass long-batch form on a short corpus (dense_small_hi.hip + fuse.hip dense_hi_select_fuse_kernel): the fp16 image
+  // two-pass long-batch form on a short corpus (dense_small_hi.hip + dense_tail.hip dense_hi_select_fuse_kernel): the fp16 image
   // of X, made on first use (not while a stream is capturing) and dropped by add(); the per-query bounds; how many queries
   // re-scored their whole row inside the second pass
   amdr_dense_small_t* small = nullptr;
@@ -509,7 +509,7 @@ bool small_hi_shape(const amdr_dense* h, const DensePins& pins, int m, int k, in
 struct PassForm {
   enum Scores { RowWaves, Panel, Tiles } scores;  // the exact kernels
   bool small_hi;     // the fp16 two-pass form applies instead of `scores` and the ranking below
-  bool select_fuse;  // ranking of the rows and the fusion with the BM25 lists in one kernel (fuse.hip dense_select_fuse_kernel);
+  bool select_fuse;  // ranking of the rows and the fusion with the BM25 lists in one kernel (dense_tail.hip dense_select_fuse_kernel);
                      // else slab top-k (+ merge when there are several slabs), then the plain fusion if a tail follows
 };
 PassForm batched_pass_form(const amdr_dense* h, const DensePins& pins, const Route& r, const DenseMfmaPlan& p, int m, int k,

@@ -1,6 +1,6 @@
 // The GEMV form of a dense score: one wave per (query, row), lane l holds the float4 pieces at columns 4 l + 256 c, the
 // 64 partial sums folded by six DPP row operations.  Shared by dense.hip (dense_scan_topk_kernel, dense_all_scores_kernel,
-// dense_score_rows_kernel) and the one-launch serving step of fuse.hip: the same instruction sequence, hence the same bits.
+// dense_score_rows_kernel) and the one-launch serving step of dense_tail.hip: the same instruction sequence, hence the same bits.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -669,18 +669,7 @@ __global__ __launch_bounds__(256) void dense_hi_exact_select_kernel(const float*
   const float* row = M + (size_t)q * ldM;
   WaveTopK<C32> tk;
   tk.init(lists + (size_t)wave * tcap, tcap, k);
-  for (long base = (long)wave * 256; base < n_tiles; base += 4 * 256) {  // ldM is a multiple of 32 floats: whole float4s
-    const long r0 = base + 4 * lane;
-    const hi4f z = {0.f, 0.f, 0.f, 0.f};
-    const hi4f x = r0 < n_tiles ? *reinterpret_cast<const hi4f*>(row + r0) : z;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const long r = r0 + e;
-      const bool v = r < n_tiles;
-      tk.push_lanes(v ? C32::make(x[e], (u32)r) : C32::pad(), v, lane);
-    }
-  }
-  tk.finalize(lane);
+  wave_topk_sweep4<false>(tk, row, 0, n_tiles, wave, 4, lane);  // ldM is a multiple of 32 floats: whole float4s
   block_combine_topk(tk, lists, tcap, 4, wave, lane, cnts);
   if (wave != 0) return;
   const int keep = tk.cnt;

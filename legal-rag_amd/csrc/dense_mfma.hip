@@ -345,51 +345,19 @@ __global__ __launch_bounds__(WAVES * 64) void scores_slab_topk_kernel(const floa
   tk.init(lists + (size_t)wave * cap, cap, k);
   bool done = false;
   if (WAVES == 1 && k <= 64 && hi - lo <= kSelectRowsMax) {
-    // short row: register selector (topk.hpp); scratch = the upper half of the staging buffer.
-    // V = keys per lane, sized to the row (a UCC-en row of 591 scores needs 10, a
-    // Civil-Code-zh row of 1 260 needs 20).
-    int got;
-    if (hi - lo <= 256)
-      got = select_row<4>(row, lo, hi, k, lane, tk.buf);
-    else if (hi - lo <= 640)
-      got = select_row<10>(row, lo, hi, k, lane, tk.buf);
-    else if (hi - lo <= 1024)
-      got = select_row<16>(row, lo, hi, k, lane, tk.buf);
-    else if (hi - lo <= 1280)
-      got = select_row<20>(row, lo, hi, k, lane, tk.buf);
-    else
-      got = select_row<32>(row, lo, hi, k, lane, tk.buf);
+    // short row: register selector (topk.hpp); scratch = the upper half of the staging buffer
+    const int got = select_row_any(row, lo, hi, k, lane, tk.buf);
     if (got >= 0) {
       tk.cnt = got;
       done = true;
     }
   }
-  if (!done) {
-    // S is read exactly once: 16-byte non-temporal loads, four consecutive rows per lane (slabs start
-    // on multiples of 64 rows and S rows on 128-byte lines, so every float4 below `hi` rounded up to 4
-    // lies inside the padded row)
-    for (long base = lo + (long)wave * 256; base < hi; base += (long)WAVES * 256) {
-      const long r0 = base + 4 * lane;
-      const v4f z = {0.f, 0.f, 0.f, 0.f};
-      const v4f x = (r0 < hi) ? __builtin_nontemporal_load(reinterpret_cast<const v4f*>(row + r0)) : z;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const long r = r0 + e;
-        const bool v = r < hi;
-        tk.push_lanes(v ? C32::make(x[e], (u32)r) : C32::pad(), v, lane);
-      }
-    }
-    tk.finalize(lane);
-  }
+  // S is read exactly once: non-temporal (slabs start on multiples of 64 rows and S rows on 128-byte lines)
+  if (!done) wave_topk_sweep4<true>(tk, row, lo, hi, wave, WAVES, lane);
   if (WAVES > 1) block_combine_topk(tk, lists, cap, WAVES, wave, lane, cnts);
   if (wave == 0) {
     if (fin_ids) {
-      for (int j = lane; j < k; j += 64) {
-        const bool v = j < tk.cnt;
-        const C32 c = v ? tk.buf[j] : C32::pad();
-        fin_scores[(size_t)qi * k + j] = v ? c.score() : -FLT_MAX;
-        fin_ids[(size_t)qi * k + j] = v ? c.id() : -1ll;
-      }
+      topk_store(tk.buf, tk.cnt, k, lane, fin_scores + (size_t)qi * k, fin_ids + (size_t)qi * k);
     } else {
       C32* dst = part + ((size_t)blockIdx.x * nq + qi) * k;
       for (int j = lane; j < k; j += 64) dst[j] = (j < tk.cnt) ? tk.buf[j] : C32::pad();
@@ -406,37 +374,10 @@ __global__ __launch_bounds__(64) void scores_pair_topk_kernel(const float* __res
   const int q = 2 * blockIdx.x + (lane >> 5);
   const bool has_q = q < nq;
   C32 out = C32::pad();
-  const int got = select_row_pair_any(S, ldS, n, q, has_q, k, lane, buf, out);
-  if (got >= 0) {
-    const int j = lane & 31;
-    if (has_q && j < k) {
-      const bool v = j < got;
-      fin_scores[(size_t)q * k + j] = v ? out.score() : -FLT_MAX;
-      fin_ids[(size_t)q * k + j] = v ? out.id() : -1ll;
-    }
-    return;
-  }
-  // mass ties at the cut in one of the two rows: the general selector, one row after the other
-  for (int h = 0; h < 2; ++h) {
-    const int qq = 2 * blockIdx.x + h;
-    if (qq >= nq) break;
-    const float* row = S + (size_t)qq * ldS;
-    WaveTopK<C32> tk;
-    tk.init(buf, cap, k);
-    for (long base = 0; base < n; base += 64) {
-      const long r = base + lane;
-      const bool v = r < n;
-      tk.push_lanes(v ? C32::make(row[r], (u32)r) : C32::pad(), v, lane);
-    }
-    tk.finalize(lane);
-    for (int j = lane; j < k; j += 64) {
-      const bool v = j < tk.cnt;
-      const C32 c = v ? tk.buf[j] : C32::pad();
-      fin_scores[(size_t)qq * k + j] = v ? c.score() : -FLT_MAX;
-      fin_ids[(size_t)qq * k + j] = v ? c.id() : -1ll;
-    }
-    wave_lds_fence();
-  }
+  int got = select_row_pair_any(S, ldS, n, q, has_q, k, lane, buf, out);
+  if (got < 0) pair_rows_staged(S, ldS, n, 2 * blockIdx.x, nq, k, cap, buf, lane, true, out, got);  // mass ties at the cut
+  const int j = lane & 31;
+  if (has_q && j < k) topk_store(out, j < got, j, fin_scores + (size_t)q * k, fin_ids + (size_t)q * k);
 }
 
 // Two-level top-k of a large scan, step 2: the <= 8 192 candidate tile ids (k per query, -1 = none) -> ascending
@@ -705,20 +646,7 @@ __global__ __launch_bounds__(WAVES * 64) void dense_final_topk_kernel(const floa
       done = true;
     }
   }
-  if (!done) {
-    for (long base = (long)wave * 256; base < hi; base += (long)WAVES * 256) {
-      const long r0 = base + 4 * lane;
-      const v4f z = {0.f, 0.f, 0.f, 0.f};
-      const v4f x = (r0 < hi) ? *reinterpret_cast<const v4f*>(row + r0) : z;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const long r = r0 + e;
-        const bool v = r < hi;
-        tk.push_lanes(v ? C32::make(x[e], (u32)r) : C32::pad(), v, lane);
-      }
-    }
-    tk.finalize(lane);
-  }
+  if (!done) wave_topk_sweep4<false>(tk, row, 0, hi, wave, WAVES, lane);
   if (WAVES > 1) block_combine_topk(tk, lists, cap, WAVES, wave, lane, cnts);
   if (wave == 0) {
     for (int j = lane; j < k; j += 64) {

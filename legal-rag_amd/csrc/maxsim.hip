@@ -864,12 +864,7 @@ __global__ __launch_bounds__(64) void maxsim_select_kernel(const float* __restri
   if (got >= 0) {
     tk.cnt = got;
   } else {
-    for (long base = 0; base < n_docs; base += 64) {
-      const long d = base + lane;
-      const bool v = d < n_docs;
-      tk.push_lanes(v ? C32::make(row[d], (u32)d) : C32::pad(), v, lane);
-    }
-    tk.finalize(lane);
+    wave_topk_sweep(tk, row, 0, n_docs, lane);
   }
   wave_lds_fence();
   const float T = tk.cnt >= k ? tk.buf[k - 1].score() : -FLT_MAX;  // fewer than k documents: every one is a candidate
@@ -1156,14 +1151,7 @@ __global__ __launch_bounds__(256) void rowscores_topk_kernel(const float* __rest
   }
   tk.finalize(lane);
   block_combine_topk(tk, lists, cap, kMsWaves, wave, lane, cnts);
-  if (wave == 0) {
-    for (int j = lane; j < k; j += 64) {
-      bool v = j < tk.cnt;
-      C32 c = v ? tk.buf[j] : C32::pad();
-      out_scores[(size_t)qi * k + j] = v ? c.score() : -FLT_MAX;
-      out_ids[(size_t)qi * k + j] = v ? c.id() : -1ll;
-    }
-  }
+  if (wave == 0) topk_store(tk.buf, tk.cnt, k, lane, out_scores + (size_t)qi * k, out_ids + (size_t)qi * k);
 }
 
 // The two-pass top-k's last step, one wave per query: only a query's candidates (<= cap, 64 for k <= 32) carry a
@@ -1190,11 +1178,7 @@ __global__ __launch_bounds__(256) void maxsim_final_topk_kernel(const float* __r
       c = C32::make(row[d], (u32)d);
     }
     c = wave_sort64_desc(c, lane);
-    if (lane < k) {
-      const bool v = lane < n;
-      out_scores[(size_t)q * k + lane] = v ? c.score() : -FLT_MAX;
-      out_ids[(size_t)q * k + lane] = v ? c.id() : -1ll;
-    }
+    if (lane < k) topk_store(c, lane < n, lane, out_scores + (size_t)q * k, out_ids + (size_t)q * k);
     return;
   }
   WaveTopK<C32> tk;
@@ -1208,12 +1192,7 @@ __global__ __launch_bounds__(256) void maxsim_final_topk_kernel(const float* __r
     tk.push_lanes(v ? C32::make(row[d], (u32)d) : C32::pad(), v, lane);
   }
   tk.finalize(lane);
-  for (int j = lane; j < k; j += 64) {
-    const bool v = j < tk.cnt;
-    const C32 c = v ? tk.buf[j] : C32::pad();
-    out_scores[(size_t)q * k + j] = v ? c.score() : -FLT_MAX;
-    out_ids[(size_t)q * k + j] = v ? c.id() : -1ll;
-  }
+  topk_store(tk.buf, tk.cnt, k, lane, out_scores + (size_t)q * k, out_ids + (size_t)q * k);
 }
 
 }  // namespace amdr

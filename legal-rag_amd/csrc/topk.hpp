@@ -11,6 +11,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cfloat>
 #include <cstdint>
 
 namespace amdr {
@@ -542,6 +543,79 @@ __device__ __forceinline__ int select_row_pair_any(const float* __restrict__ S, 
   if (n <= 512) return select_row_pair<16>(S, ldS, n, q, has_q, k, lane, scratch, out);
   if (n <= 640) return select_row_pair<20>(S, ldS, n, q, has_q, k, lane, scratch, out);
   return select_row_pair<32>(S, ldS, n, q, has_q, k, lane, scratch, out);
+}
+
+// ---- the steps every row top-k shares ---------------------------------------------------------------------------------
+// rows [lo, hi) of `row` through the staged selector, 64 per step, by one wave; the list is final afterwards
+__device__ __forceinline__ void wave_topk_sweep(WaveTopK<C32>& tk, const float* __restrict__ row, long lo, long hi, int lane) {
+  for (long base = lo; base < hi; base += 64) {
+    const long r = base + lane;
+    const bool v = r < hi;
+    tk.push_lanes(v ? C32::make(row[r], (u32)r) : C32::pad(), v, lane);
+  }
+  tk.finalize(lane);
+}
+// The same with 16-byte loads, four consecutive rows per lane, wave `wave` of `nwaves` taking every nwaves-th piece of
+// 256 rows (lo a multiple of 4 and the row padded so that every float4 below `hi` rounded up to 4 lies inside it).
+// NT: the row is read exactly once — non-temporal loads.
+template <bool NT>
+__device__ __forceinline__ void wave_topk_sweep4(WaveTopK<C32>& tk, const float* __restrict__ row, long lo, long hi, int wave,
+                                                 int nwaves, int lane) {
+  for (long base = lo + (long)wave * 256; base < hi; base += (long)nwaves * 256) {
+    const long r0 = base + 4 * lane;
+    tk_v4f x = {0.f, 0.f, 0.f, 0.f};
+    if (r0 < hi) x = NT ? __builtin_nontemporal_load(reinterpret_cast<const tk_v4f*>(row + r0)) : *reinterpret_cast<const tk_v4f*>(row + r0);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const long r = r0 + e;
+      const bool v = r < hi;
+      tk.push_lanes(v ? C32::make(x[e], (u32)r) : C32::pad(), v, lane);
+    }
+  }
+  tk.finalize(lane);
+}
+// select_row with V = keys per lane sized to the row (a UCC-en row of 591 scores needs 10, a Civil-Code-zh row of 1 260
+// needs 20); hi - lo <= kSelectRowsMax
+__device__ __forceinline__ int select_row_any(const float* __restrict__ row, long lo, long hi, int k, int lane, C32* buf) {
+  if (hi - lo <= 256) return select_row<4>(row, lo, hi, k, lane, buf);
+  if (hi - lo <= 640) return select_row<10>(row, lo, hi, k, lane, buf);
+  if (hi - lo <= 1024) return select_row<16>(row, lo, hi, k, lane, buf);
+  if (hi - lo <= 1280) return select_row<20>(row, lo, hi, k, lane, buf);
+  return select_row<32>(row, lo, hi, k, lane, buf);
+}
+// Mass ties at the cut of a pair selector: rows q_pair0 and q_pair0 + 1 of S, one after the other, through the staged
+// selector (buf: cap entries); each half whose lanes ask for it (want_half, uniform in the half) keeps its own list in
+// its lanes — lane j of the half = list position j — and its length in `got`.
+__device__ __forceinline__ void pair_rows_staged(const float* __restrict__ S, long ldS, long n, int q_pair0, int nq, int k,
+                                                 int cap, C32* buf, int lane, bool want_half, C32& out, int& got) {
+  const u64 want = __ballot(want_half);
+  for (int hh = 0; hh < 2; ++hh) {
+    if (q_pair0 + hh >= nq || !((want >> (32 * hh)) & 1ull)) continue;
+    WaveTopK<C32> tk;
+    tk.init(buf, cap, k);
+    wave_topk_sweep(tk, S + (size_t)(q_pair0 + hh) * ldS, 0, n, lane);
+    if ((lane >> 5) == hh) {
+      got = tk.cnt;
+      out = (lane & 31) < tk.cnt ? tk.buf[lane & 31] : C32::pad();
+    }
+    wave_lds_fence();
+  }
+}
+// One row of a (scores, ids) result: -FLT_MAX / -1 behind the hits.  From a finished list in LDS ...
+__device__ __forceinline__ void topk_store(const C32* list, int cnt, int k, int lane, float* __restrict__ scores,
+                                           long long* __restrict__ ids) {
+  for (int j = lane; j < k; j += 64) {
+    const bool v = j < cnt;
+    const C32 c = v ? list[j] : C32::pad();
+    scores[j] = v ? c.score() : -FLT_MAX;
+    ids[j] = v ? c.id() : -1ll;
+  }
+}
+// ... or position j of it, held by this lane
+__device__ __forceinline__ void topk_store(const C32& c, bool valid, int j, float* __restrict__ scores,
+                                           long long* __restrict__ ids) {
+  scores[j] = valid ? c.score() : -FLT_MAX;
+  ids[j] = valid ? c.id() : -1ll;
 }
 
 // Merge the finalized lists of all waves of a block into wave 0's list.

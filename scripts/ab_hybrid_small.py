@@ -1,5 +1,5 @@
 """A/B of the serving call (dense + BM25 + fusion of ONE query on a serving corpus): the separate launches
-(AMDR_HYBRID_SMALL=0) against the one-launch step (csrc/fuse.hip hybrid_small_kernel).  Per corpus shape: eager p50 / p90
+(AMDR_HYBRID_SMALL=0) against the one-launch step (csrc/dense_tail.hip hybrid_small_kernel).  Per corpus shape: eager p50 / p90
 of HybridEngine.search_batch at 1, 2 and 4 queries (host call + device time, synchronised per call) and the same step
 replayed from a hipGraph.  AMDR_HYBRID_SMALL_ROWS (chunk rows per dense block) is read once per process."""
 import json

@@ -1,4 +1,4 @@
-"""One-off stress of the one-launch serving step (csrc/fuse.hip hybrid_small_kernel): random corpus shapes, depths, query
+"""One-off stress of the one-launch serving step (csrc/dense_tail.hip hybrid_small_kernel): random corpus shapes, depths, query
 counts and token lists, every output compared bit for bit with the separate launches; repeated back-to-back launches on
 one engine (the arrival counters reset themselves) and launches interleaved over two engines.  python scripts/stress_hybrid_small.py [cases]"""
 import os

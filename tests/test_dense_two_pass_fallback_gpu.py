@@ -1,4 +1,4 @@
-"""The whole-row exact fallback of the two-pass long-batch form (fuse.hip dense_hi_select_fuse_kernel) re-scores a query's
+"""The whole-row exact fallback of the two-pass long-batch form (dense_tail.hip dense_hi_select_fuse_kernel) re-scores a query's
 row over that query's own row of the approximate score matrix instead of a per-block LDS buffer.  Checked here: the
 fallback's exact scores are the bits the candidate re-scoring computes for the same rows; mass ties among exact scores
 (the staged selector reading the row back); a pair whose two halves take different paths; an odd batch whose last pair

@@ -1,5 +1,5 @@
 """The two-pass form of a long batch on a short corpus (round 4: dense_small_hi.hip first pass on the fp16 matrix
-instructions + fuse.hip dense_hi_select_fuse_kernel: the rows inside the proven margin re-scored exactly) against the
+instructions + dense_tail.hip dense_hi_select_fuse_kernel: the rows inside the proven margin re-scored exactly) against the
 exact form (AMDR_DENSE_SMALL_HI=0: dense_panel_scores_kernel + select) and the CPU oracle: same ids, scores within fp32
 summation-order noise, the fusion's outputs the same — with the in-kernel exact fallback forced, on near-duplicate rows
 (more than 32 rows inside the margin) and on queries without a bound (NaN / zero / huge)."""

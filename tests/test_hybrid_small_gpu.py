@@ -1,4 +1,4 @@
-"""The serving call as ONE launch (amdr_hybrid_small_device, csrc/fuse.hip hybrid_small_kernel): BM25 top-k + dense top-k +
+"""The serving call as ONE launch (amdr_hybrid_small_device, csrc/dense_tail.hip hybrid_small_kernel): BM25 top-k + dense top-k +
 fusion of 1-4 queries on a corpus of <= 2 048 chunks.  Checked against (a) the separate launches (AMDR_HYBRID_SMALL=0:
 amdr_bm25_search_device + amdr_dense_search_fuse_device) — bit for bit, every output — and (b) the oracle directly
 (oracle/dense.py, oracle/bm25.py, oracle/fuse.py: the reference's hybrid_retriever.py:181-209 + :389-551)."""
@@ -57,12 +57,20 @@ def _same(a, b, what):
         assert np.array_equal(x.view(np.uint8), y.view(np.uint8)), (what, f)
 
 
-@pytest.mark.parametrize("n,d", [(591, 384), (1260, 768), (2048, 64), (33, 384), (257, 1024), (1, 8)])
-def test_one_launch_equals_the_separate_launches(n, d):
+# ties: rows 100-179 are one row and query 0 IS that row — the 80 tied rows are its 80 best scores and sit at the cut for
+# every k below: each of the 64 lanes holds a tied key, the k-th lane best is the tie score, 80 > 64 keys survive, the
+# register selector gives up and the kernel's staged selector ranks the row (random queries meet the block at the cut
+# about once in fifty).
+@pytest.mark.parametrize("n,d,ties", [pytest.param(n, d, t, id=f"{n}-{d}" + ("-ties" if t else "")) for n, d, t in
+                                      [(591, 384, False), (1260, 768, False), (2048, 64, False), (33, 384, False),
+                                       (257, 1024, False), (1, 8, False), (591, 384, True)]])
+def test_one_launch_equals_the_separate_launches(n, d, ties):
     import torch
     from legal_rag_amd import _native
     rng = np.random.default_rng(n * 7 + d)
     X, ob, csr = _corpus(rng, n, d, 150)
+    if ties:
+        X[100:180] = X[100]
     eng = _engine(X, ob, csr)
     dev = torch.device("cuda", 0)
     V = len(csr["vocab"])
@@ -72,6 +80,8 @@ def test_one_launch_equals_the_separate_launches(n, d):
                 continue
             q = rng.standard_normal((nq, d)).astype(np.float32)
             q /= np.linalg.norm(q, axis=1, keepdims=True)
+            if ties:
+                q[0] = X[100]
             toks = [[int(t) for t in rng.integers(-2, V, size=int(rng.integers(0, 24)))] for _ in range(nq)]
             qt_h, qp_h = _native.BM25Index.pack_queries(toks)
             Q = torch.from_numpy(q).to(dev)
@@ -84,6 +94,8 @@ def test_one_launch_equals_the_separate_launches(n, d):
                 b = _run(eng, params, k, Q, qt, qp, False)
                 _same(a, b, (n, d, nq, k, method, mf))
                 _same(a2, b, (n, d, nq, k, method, mf, "second launch"))
+                if ties:  # equal scores: the lower id first
+                    assert a["dense_ids"][0].tolist() == list(range(100, 100 + k)), (nq, k, a["dense_ids"][0])
 
 
 def test_one_launch_against_the_oracle_directly():
