@@ -127,7 +127,7 @@ int amdr_dense_destroy(amdr_dense_t* h);
  * with duplicates counted, so scores are bit-identical to rank_bm25's numpy
  * expression.  Ties -> lower doc id; zero-score docs ARE returned.
  * term_ptr[n_terms+1] indexes post_doc/post_tf (ascending doc id per term);
- * idf already has rank_bm25's epsilon floor applied. */
+ * idf already has rank_bm25's epsilon floor applied; every idf must be finite (AMDR_EINVAL otherwise). */
 int amdr_bm25_create(const int64_t* term_ptr, const int32_t* post_doc, const int32_t* post_tf,
                      const double* idf, const int32_t* doc_len, int64_t n_terms, int64_t n_docs,
                      double avgdl, double k1, double b, int32_t device, amdr_bm25_t** out);

@@ -188,6 +188,9 @@ int amdr_bm25_create(const int64_t* term_ptr, const int32_t* post_doc, const int
   AMDR_REQUIRE(term_ptr[0] == 0, "bm25_create: term_ptr[0] != 0");
   for (int64_t t = 0; t < n_terms; ++t)
     AMDR_REQUIRE(term_ptr[t + 1] >= term_ptr[t], "bm25_create: term_ptr not monotone at %lld", (long long)t);
+  // rank_bm25 never produces a non-finite idf; the rankings use -inf as "no document" and order NaN by convention
+  for (int64_t t = 0; t < n_terms; ++t)
+    AMDR_REQUIRE(std::isfinite(idf[t]), "bm25_create: idf of term %lld is not finite", (long long)t);
   const int64_t nnz = term_ptr[n_terms];
   AMDR_REQUIRE(nnz == 0 || (post_doc && post_tf), "bm25_create: null postings");
   for (int64_t t = 0; t < n_terms; ++t)

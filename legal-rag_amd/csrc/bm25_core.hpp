@@ -95,9 +95,11 @@ __device__ __forceinline__ int bm25_argmax_rounds(const double* sc, int m, int k
 // top k; all documents whose image reaches the cut take part (the threshold test looks at the
 // score half of the key only).  After the survivors are sorted by (image desc, doc asc) the
 // order can differ from the exact (score desc, doc asc) order only inside a run of equal
-// images: if any neighbouring pair up to the cut has equal images but different fp64 scores the
-// function gives up (-1) and the caller runs the exact arg-max rounds.  More than 64 survivors
-// (mass ties at the cut: e.g. every document at score 0) -> -1 as well.
+// images: if any neighbouring pair through the run that reaches the cut has equal images but
+// different fp64 scores the function gives up (-1) and the caller runs the exact arg-max rounds.
+// The run that holds position k - 1 may go on past it, and a member beyond the cut with a larger
+// exact score (a higher id) belongs in the top k: pairs (j, j + 1) with j < k alone miss it.
+// More than 64 survivors (mass ties at the cut: e.g. every document at score 0) -> -1 as well.
 template <int NV>
 __device__ __forceinline__ int bm25_select_f32(const double* sc, int m, int k, long lo, int lane, C32* scratch,
                                                double* xs /* [64] exact scores of the survivors */, C64* out) {
@@ -207,16 +209,18 @@ __device__ __forceinline__ int bm25_select_f32(const double* sc, int m, int k, l
     c = wave_sortN_desc<C32, 32>(c, lane);
   else
     c = wave_sortN_desc<C32, 64>(c, lane);
-  // exact scores of the survivors, and the check of every neighbouring pair up to the cut
+  // exact scores of the survivors, and the check of every neighbouring pair through the run that reaches the cut
+  // (every survivor whose image is at least the image at position min(k, cnt) - 1)
   const u32 low = (u32)c.c;
   const int doc = (lane < cnt) ? (int)(0xffffu - (low >> 8)) : 0;
   const double x = xs[(lane < cnt) ? (int)(low & 63u) : 0];
   const u32 im = (u32)(c.c >> 32);
   const u32 im_n = (u32)__shfl_down((int)im, 1);
   const double x_n = __shfl_down(x, 1);
-  const bool undecided = lane < k && lane + 1 < cnt && im == im_n && x != x_n;
-  if (__ballot(undecided)) return -1;
   const int got = cnt < k ? cnt : k;
+  const u32 im_cut = (u32)__builtin_amdgcn_readlane((int)im, got > 0 ? got - 1 : 0);
+  const bool undecided = im >= im_cut && lane + 1 < cnt && im == im_n && x != x_n;
+  if (__ballot(undecided)) return -1;
   if (lane < got) out[lane] = C64::make(x, lo + doc);
   return got;
 }
