@@ -218,7 +218,10 @@ int amdr_maxsim_plan_info(const amdr_maxsim_t* h, int32_t nq, char* buf, int32_t
 int amdr_maxsim_reserve(amdr_maxsim_t* h, int32_t nq_max, int32_t k_max);
 /* Host-only: the same for MaxSim on n_docs documents, split_image = 1 when the store has its split-fp16 images (every
  * finite store; the two-pass top-k needs them): out2[0] = the workspace bytes amdr_maxsim_reserve(nq_max, k_max) sizes,
- * out2[1] = the bytes amdr_maxsim_search_device(nq, k) uses (both follow AMDR_MAXSIM_F16X3 / AMDR_MAXSIM_TWOPASS). */
+ * out2[1] = the bytes amdr_maxsim_search_device(nq, k) uses (both follow AMDR_MAXSIM_F16X3 / AMDR_MAXSIM_TWOPASS).
+ * A one-pass call uses its score rows [nq, n_docs], rounded up to 256 bytes; for a two-pass call out2[1] is the exact
+ * end of the layout the call runs in (a multiple of 256), not an upper bound, and the call checks it against the
+ * workspace it is given. */
 int amdr_maxsim_workspace_plan(int64_t n_docs, int32_t split_image, int32_t nq_max, int32_t k_max, int32_t nq, int32_t k,
                                int64_t* out2);
 int amdr_maxsim_search(amdr_maxsim_t* h, const float* Q_host, int32_t nq, int32_t q_len, int32_t k,

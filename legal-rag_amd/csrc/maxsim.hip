@@ -357,8 +357,8 @@ __device__ __forceinline__ int ms_tile_off(int row, int slot) { return row * 512
 
 __global__ __launch_bounds__(kMsQ * 64) void maxsim_scores_blocked_kernel(const float* __restrict__ D,
                                                                            const long long* __restrict__ doc_ptr,
-                                                                           long n_docs, long n_tokens,
-                                                                           const float* __restrict__ Q, int nq, int q_len,
+                                                                           long n_docs, const float* __restrict__ Q,
+                                                                           int nq, int q_len,
                                                                            float* __restrict__ scores /*[nq, n_docs]*/) {
   __shared__ __attribute__((aligned(16))) unsigned char tile[2][32 * 512];
   typedef float v4f __attribute__((ext_vector_type(4)));
@@ -401,7 +401,6 @@ __global__ __launch_bounds__(kMsQ * 64) void maxsim_scores_blocked_kernel(const 
   __syncthreads();
   int buf = 0;
   float best[2] = {-FLT_MAX, -FLT_MAX};
-  (void)n_tokens;
   while (true) {
     // coordinates of the next tile (wave-uniform)
     long ndoc = doc;
@@ -468,6 +467,76 @@ __global__ __launch_bounds__(kMsQ * 64) void maxsim_scores_blocked_kernel(const 
 // other's MFMAs.  Tried on the way (same-box A/B, scripts/ab_maxsim.py): 2 / 3 / 4 / 6 stages 2.55 / 2.31 / 2.24 /
 // 2.44 ms per 1 168 UCC-en queries; 8 / 16 / 32 / 64 documents per block 2.27 / 2.23 / 2.24 / 2.37; a second fragment
 // register set filled one tile ahead (254 VGPRs) +- 0.
+//
+// The pieces of the ring that its three kernels share.  A stage is 16 pieces of 1 KiB, one piece = one DMA request of a
+// wave (64 lanes x 16 B) = 1024 / ROWB whole token rows of ROWB bytes (512: the [hi | lo] image, 256: the hi-only image).
+// Per-lane source offsets of pieces piece0 .. piece0 + PIECES - 1 inside a tile: lane l of a piece: its row l / (ROWB / 16),
+// PHYSICAL slot l % (ROWB / 16), which holds logical slot ^ (row & 15).  Rows past the end of a document read on into the
+// next document's tokens (the images are padded by one tile at their end) and are masked after the MFMAs.
+template <int PIECES, int ROWB>
+__device__ __forceinline__ void ms_piece_offs(int piece0, int lane, long (&poff)[PIECES]) {
+  constexpr int kSlots = ROWB / 16, kRows = 1024 / ROWB;
+#pragma unroll
+  for (int u = 0; u < PIECES; ++u) {
+    const int prow = kRows * (piece0 + u) + lane / kSlots;
+    poff[u] = (long)prow * ROWB + (((lane & (kSlots - 1)) ^ (prow & 15)) << 4);
+  }
+}
+// this wave's pieces of the tile at `src` (wave-uniform) into `dst` = the stage + piece0 KiB
+template <int PIECES>
+__device__ __forceinline__ void ms_issue_tile(const unsigned char* src, const long (&poff)[PIECES], unsigned char* dst) {
+#pragma unroll
+  for (int u = 0; u < PIECES; ++u)
+    __builtin_amdgcn_global_load_lds(AMDR_MS_GPTR(src + poff[u]), AMDR_MS_LPTR(dst + u * 1024), 16, 0, 0);
+}
+// A position in a block's tile sequence (wave-uniform): tiles of TOK tokens of documents d0 .. d1 - 1.
+template <int TOK>
+struct MsDocCursor {
+  long doc, t_lo;
+  int len, tok0;
+  __device__ __forceinline__ void first(const long long* __restrict__ doc_ptr, long d0) {
+    doc = d0;
+    t_lo = doc_ptr[d0];
+    len = (int)(doc_ptr[d0 + 1] - t_lo);
+    tok0 = 0;
+  }
+  __device__ __forceinline__ void advance(const long long* __restrict__ doc_ptr, long d1) {
+    tok0 += TOK;
+    if (tok0 >= len) {
+      doc += 1;
+      tok0 = 0;
+      if (doc < d1) {
+        t_lo = doc_ptr[doc];
+        len = (int)(doc_ptr[doc + 1] - t_lo);
+      }
+    }
+  }
+};
+// The waits.  simm16 on gfx9: vmcnt [3:0] (+ [15:14]), expcnt [6:4] (7 = none), lgkmcnt [11:8] (15 = none).
+constexpr int ms_vmcnt_imm(int n) { return 0x0F70 | (n & 15) | ((n >> 4) << 14); }
+constexpr int kMsLgkm0 = 0xC07F;  // lgkmcnt(0) alone
+// This wave's pieces of a tile have landed once at most PIECES x (tiles issued behind it) requests are outstanding:
+// vmcnt(PIECES x min(behind, CAP)) (fewer than the truth only makes the wait stricter; other loads issued meanwhile
+// likewise).  lgkmcnt(0) on every path as ONE unconditional instruction (inside the branches the wait-count pass still
+// re-waited in front of the MFMAs).
+template <int PIECES, int CAP, int B = CAP>
+__device__ __forceinline__ void ms_wait_vm(int behind) {
+  static_assert(PIECES * CAP < 64, "vmcnt has 6 bits");
+  if constexpr (B == 0) {
+    __builtin_amdgcn_s_waitcnt(ms_vmcnt_imm(0));
+  } else {
+    if (B == CAP ? behind >= B : behind == B)
+      __builtin_amdgcn_s_waitcnt(ms_vmcnt_imm(PIECES * B));
+    else
+      ms_wait_vm<PIECES, CAP, B - 1>(behind);
+  }
+}
+template <int PIECES, int CAP>
+__device__ __forceinline__ void ms_wait_tile(int behind) {
+  __builtin_amdgcn_s_waitcnt(kMsLgkm0);
+  ms_wait_vm<PIECES, CAP>(behind);
+}
+
 template <int NBUF>
 __global__ __launch_bounds__(kMsQ * 64) __attribute__((amdgpu_waves_per_eu(4, 4))) void maxsim_scores_ring_kernel(const unsigned char* __restrict__ img,
                                                                         const long long* __restrict__ doc_ptr,
@@ -491,82 +560,33 @@ __global__ __launch_bounds__(kMsQ * 64) __attribute__((amdgpu_waves_per_eu(4, 4)
   ms_load_query_h(Q + (size_t)(live ? qi : 0) * q_len * kDim, q_len, live, r32, h, qh, ql, unscale);
   unscale *= unscale_d;
 
-  // DMA role: piece u (0, 1) of this wave covers stage bytes [(2 wave + u) * 1024, + 1024) = tile rows
-  // 2 (2 wave + u) and + 1; lane l: row + (l >> 5), PHYSICAL slot l & 31, which holds logical slot ^ (row & 15).
-  // poff: the piece's per-lane byte offset inside a tile; rows past the end of a document read on into the next
-  // document's tokens (the image is padded by one tile at its end) and are masked after the MFMAs.
+  // DMA role: pieces 2 wave, 2 wave + 1 of a tile (two token rows of 512 B each)
   long poff[2];
-#pragma unroll
-  for (int u = 0; u < 2; ++u) {
-    const int prow = 2 * (2 * wave + u) + (lane >> 5);
-    poff[u] = (long)prow * 512 + (((lane & 31) ^ (prow & 15)) << 4);
-  }
+  ms_piece_offs<2, 512>(2 * wave, lane, poff);
   // fragment read addresses: row r32, chunk 2 s + h (the lo part sits 256 B behind the hi part: slots c and 16 + c
   // differ in bit 4, which the XOR with row & 15 leaves alone)
   int foff[8];
 #pragma unroll
   for (int st = 0; st < 8; ++st) foff[st] = ms_tile_off(r32, 2 * st + h);
 
-  struct Cur {  // a position in the block's tile sequence (wave-uniform)
-    long doc, t_lo;
-    int len, tok0;
-  };
-  auto advance = [&](Cur& c) {
-    c.tok0 += 32;
-    if (c.tok0 >= c.len) {
-      c.doc += 1;
-      c.tok0 = 0;
-      if (c.doc < d1) {
-        c.t_lo = doc_ptr[c.doc];
-        c.len = (int)(doc_ptr[c.doc + 1] - c.t_lo);
-      }
-    }
-  };
-  auto issue = [&](const Cur& c, int stage) {
-    const unsigned char* src = img + (size_t)(c.t_lo + c.tok0) * 512;  // wave-uniform
-#pragma unroll
-    for (int u = 0; u < 2; ++u)
-      __builtin_amdgcn_global_load_lds(AMDR_MS_GPTR(src + poff[u]),
-                                       AMDR_MS_LPTR(ring + stage * kStage + (2 * wave + u) * 1024), 16, 0, 0);
-  };
-  Cur prod, cur;
-  prod.doc = d0;
-  prod.t_lo = doc_ptr[d0];
-  prod.len = (int)(doc_ptr[d0 + 1] - prod.t_lo);
-  prod.tok0 = 0;
+  MsDocCursor<32> prod, cur;
+  prod.first(doc_ptr, d0);
   cur = prod;
   int issued = 0, done = 0;
+  auto produce = [&]() {
+    if (prod.doc >= d1) return;
+    ms_issue_tile<2>(img + (size_t)(prod.t_lo + prod.tok0) * 512, poff, ring + (issued % NBUF) * kStage + 2 * wave * 1024);
+    ++issued;
+    prod.advance(doc_ptr, d1);
+  };
 #pragma unroll
-  for (int i = 0; i < NBUF - 1; ++i) {
-    if (prod.doc < d1) {
-      issue(prod, issued % NBUF);
-      ++issued;
-      advance(prod);
-    }
-  }
+  for (int i = 0; i < NBUF - 1; ++i) produce();
   float best = -FLT_MAX;
   while (cur.doc < d1) {
-    // simm16 on gfx9: vmcnt [3:0] (+ [15:14]), expcnt [6:4] (7 = none), lgkmcnt [11:8].  lgkmcnt(0) on every path as
-    // ONE unconditional instruction (inside the branches below the pass still re-waited in front of the MFMAs);
-    // this wave's pieces of tile `done` have landed once at most 2 x (tiles issued after it) loads are outstanding.
-    __builtin_amdgcn_s_waitcnt(0xC07F);
-    const int behind = issued - done - 1;
-    if (behind >= 3) {
-      __builtin_amdgcn_s_waitcnt(0x0F76);  // vmcnt(6)
-    } else if (behind == 2) {
-      __builtin_amdgcn_s_waitcnt(0x0F74);
-    } else if (behind == 1) {
-      __builtin_amdgcn_s_waitcnt(0x0F72);
-    } else {
-      __builtin_amdgcn_s_waitcnt(0x0F70);
-    }
+    ms_wait_tile<2, NBUF - 1>(issued - done - 1);  // this wave's pieces of tile `done`
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
-    if (prod.doc < d1) {
-      issue(prod, issued % NBUF);
-      ++issued;
-      advance(prod);
-    }
+    produce();  // into the stage of tile done - 1
     const unsigned char* tile = ring + (done % NBUF) * kStage;
     ms8h ah[8], al[8];
 #pragma unroll
@@ -583,7 +603,7 @@ __global__ __launch_bounds__(kMsQ * 64) __attribute__((amdgpu_waves_per_eu(4, 4)
       best = -FLT_MAX;
     }
     ++done;
-    advance(cur);
+    cur.advance(doc_ptr, d1);
   }
 }
 
@@ -650,73 +670,31 @@ __global__ __launch_bounds__(kMsQ2 * 64) __attribute__((amdgpu_waves_per_eu(3, N
   const float unscale_a = unscale_q[live_a ? qa : 0] * unscale_d;
   const float unscale_b = unscale_q[live_b ? qb : 0] * unscale_d;
 
-  // DMA role: pieces 4 wave .. 4 wave + 3 of the tile's 16 (1 KiB = 4 rows of 256 B each); lane l: row + (l >> 4),
-  // PHYSICAL slot l & 15, which holds logical slot ^ (row & 15)
+  // DMA role: pieces 4 wave .. 4 wave + 3 of the tile's 16 (1 KiB = 4 token rows of 256 B each)
   long poff[4];
-#pragma unroll
-  for (int u = 0; u < 4; ++u) {
-    const int prow = 4 * (4 * wave + u) + (lane >> 4);
-    poff[u] = (long)prow * 256 + (((lane & 15) ^ (prow & 15)) << 4);
-  }
+  ms_piece_offs<4, 256>(4 * wave, lane, poff);
   int foff[8];
 #pragma unroll
   for (int st = 0; st < 8; ++st) foff[st] = ms_hi_off(r32, 2 * st + h);
 
-  struct Cur {
-    long doc, t_lo;
-    int len, tok0;
-  };
-  auto advance = [&](Cur& c) {
-    c.tok0 += 64;
-    if (c.tok0 >= c.len) {
-      c.doc += 1;
-      c.tok0 = 0;
-      if (c.doc < d1) {
-        c.t_lo = doc_ptr[c.doc];
-        c.len = (int)(doc_ptr[c.doc + 1] - c.t_lo);
-      }
-    }
-  };
-  auto issue = [&](const Cur& c, int stage) {
-    const unsigned char* src = img_hi + (size_t)(c.t_lo + c.tok0) * 256;  // wave-uniform
-#pragma unroll
-    for (int u = 0; u < 4; ++u)
-      __builtin_amdgcn_global_load_lds(AMDR_MS_GPTR(src + poff[u]),
-                                       AMDR_MS_LPTR(ring + stage * kStage + (4 * wave + u) * 1024), 16, 0, 0);
-  };
-  Cur prod, cur;
-  prod.doc = d0;
-  prod.t_lo = doc_ptr[d0];
-  prod.len = (int)(doc_ptr[d0 + 1] - prod.t_lo);
-  prod.tok0 = 0;
+  MsDocCursor<64> prod, cur;
+  prod.first(doc_ptr, d0);
   cur = prod;
   int issued = 0, done = 0;
+  auto produce = [&]() {
+    if (prod.doc >= d1) return;
+    ms_issue_tile<4>(img_hi + (size_t)(prod.t_lo + prod.tok0) * 256, poff, ring + (issued % NBUF) * kStage + 4 * wave * 1024);
+    ++issued;
+    prod.advance(doc_ptr, d1);
+  };
 #pragma unroll
-  for (int i = 0; i < NBUF - 1; ++i) {
-    if (prod.doc < d1) {
-      issue(prod, issued % NBUF);
-      ++issued;
-      advance(prod);
-    }
-  }
+  for (int i = 0; i < NBUF - 1; ++i) produce();
   float best_a = -FLT_MAX, best_b = -FLT_MAX;
   while (cur.doc < d1) {
-    __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0); then this wave's 4 pieces of tile `done` (4 loads per tile in flight behind it)
-    const int behind = issued - done - 1;
-    if (behind >= 2) {
-      __builtin_amdgcn_s_waitcnt(0x0F78);  // vmcnt(8)
-    } else if (behind == 1) {
-      __builtin_amdgcn_s_waitcnt(0x0F74);  // vmcnt(4)
-    } else {
-      __builtin_amdgcn_s_waitcnt(0x0F70);
-    }
+    ms_wait_tile<4, NBUF - 1>(issued - done - 1);  // this wave's 4 pieces of tile `done`
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
-    if (prod.doc < d1) {
-      issue(prod, issued % NBUF);
-      ++issued;
-      advance(prod);
-    }
+    produce();  // into the stage of tile done - 1
     const unsigned char* tile = ring + (done % NBUF) * kStage;
     const int remain = cur.len - cur.tok0;
 #pragma unroll
@@ -764,7 +742,7 @@ __global__ __launch_bounds__(kMsQ2 * 64) __attribute__((amdgpu_waves_per_eu(3, N
       best_a = best_b = -FLT_MAX;
     }
     ++done;
-    advance(cur);
+    cur.advance(doc_ptr, d1);
   }
 }
 
@@ -912,22 +890,15 @@ __device__ __forceinline__ float ms_exact_doc_lds(const unsigned char* __restric
   const int r32 = lane & 31, h = lane >> 5;
   const long t_lo = doc_ptr[doc];
   const int len = (int)(doc_ptr[doc + 1] - t_lo);
-  long poff[16];  // piece u: tile rows 2 u and 2 u + 1; lane: row + (l >> 5), PHYSICAL slot l & 31 <- logical slot ^ (row & 15)
-#pragma unroll
-  for (int u = 0; u < 16; ++u) {
-    const int prow = 2 * u + (lane >> 5);
-    poff[u] = (long)prow * 512 + (((lane & 31) ^ (prow & 15)) << 4);
-  }
+  long poff[16];  // the whole tile is this wave's
+  ms_piece_offs<16, 512>(0, lane, poff);
   int foff[8];
 #pragma unroll
   for (int st = 0; st < 8; ++st) foff[st] = ms_tile_off(r32, 2 * st + h);
   float best = -FLT_MAX;
   for (int tok0 = 0; tok0 < len; tok0 += 32) {
-    const unsigned char* src = img + (size_t)(t_lo + tok0) * 512;
-    __builtin_amdgcn_s_waitcnt(0xC07F);  // the fragment reads of the previous tile are done: the stage may be refilled
-#pragma unroll
-    for (int u = 0; u < 16; ++u)
-      __builtin_amdgcn_global_load_lds(AMDR_MS_GPTR(src + poff[u]), AMDR_MS_LPTR(stage + u * 1024), 16, 0, 0);
+    __builtin_amdgcn_s_waitcnt(kMsLgkm0);  // the fragment reads of the previous tile are done: the stage may be refilled
+    ms_issue_tile<16>(img + (size_t)(t_lo + tok0) * 512, poff, stage);
     __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): the tile has landed (the other waves of the CU cover the wait)
     asm volatile("" ::: "memory");
     ms8h ah[8], al[8];
@@ -1021,11 +992,7 @@ __global__ __launch_bounds__(kMsQ * 64) __attribute__((amdgpu_waves_per_eu(4, 4)
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int r32 = lane & 31, h = lane >> 5;
   long poff[2];  // DMA role of this wave: pieces 2 wave, 2 wave + 1 of a tile (maxsim_scores_ring_kernel)
-#pragma unroll
-  for (int u = 0; u < 2; ++u) {
-    const int prow = 2 * (2 * wave + u) + (lane >> 5);
-    poff[u] = (long)prow * 512 + (((lane & 31) ^ (prow & 15)) << 4);
-  }
+  ms_piece_offs<2, 512>(2 * wave, lane, poff);
   int foff[8];
 #pragma unroll
   for (int st = 0; st < 8; ++st) foff[st] = ms_tile_off(r32, 2 * st + h);
@@ -1049,11 +1016,7 @@ __global__ __launch_bounds__(kMsQ * 64) __attribute__((amdgpu_waves_per_eu(4, 4)
       p_tile = 0;
     }
     if (p_item >= items) return;
-    const unsigned char* src = img + (size_t)(p_cur.t_lo + 32 * p_tile) * 512;
-#pragma unroll
-    for (int u = 0; u < 2; ++u)
-      __builtin_amdgcn_global_load_lds(AMDR_MS_GPTR(src + poff[u]),
-                                       AMDR_MS_LPTR(ring + (issued % NBUF) * kStage + (2 * wave + u) * 1024), 16, 0, 0);
+    ms_issue_tile<2>(img + (size_t)(p_cur.t_lo + 32 * p_tile) * 512, poff, ring + (issued % NBUF) * kStage + 2 * wave * 1024);
     ++issued;
     ++p_tile;
   };
@@ -1073,21 +1036,8 @@ __global__ __launch_bounds__(kMsQ * 64) __attribute__((amdgpu_waves_per_eu(4, 4)
     const int qi_n = wave < c_nxt.cnt ? dlist[(size_t)c_nxt.doc * nq + c_nxt.p0 + wave] : 0;
     float best = -FLT_MAX;
     for (int t = 0; t < ntiles; ++t) {
-      __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): the fragment reads of the previous tile
-      if (done >= safe) {
-        // this wave's pieces of tile `done`: landed once at most 2 x (tiles issued behind it) requests are outstanding
-        // (other loads issued meanwhile only make the wait stricter)
-        const int behind = issued - done - 1;
-        if (behind >= 3) {
-          __builtin_amdgcn_s_waitcnt(0x0F76);  // vmcnt(6)
-        } else if (behind == 2) {
-          __builtin_amdgcn_s_waitcnt(0x0F74);
-        } else if (behind == 1) {
-          __builtin_amdgcn_s_waitcnt(0x0F72);
-        } else {
-          __builtin_amdgcn_s_waitcnt(0x0F70);
-        }
-      }
+      __builtin_amdgcn_s_waitcnt(kMsLgkm0);  // lgkmcnt(0): the fragment reads of the previous tile
+      if (done >= safe) ms_wait_vm<2, 3>(issued - done - 1);  // this wave's pieces of tile `done`
       __builtin_amdgcn_s_barrier();  // everybody's pieces of tile `done` are in; tile done - 1 has been read by all
       asm volatile("" ::: "memory");
       produce();                     // into the stage of tile done - 1
@@ -1201,13 +1151,14 @@ using namespace amdr;
 
 struct amdr_maxsim {
   int device = 0;
-  int64_t n_docs = 0, n_tokens = 0;
+  int64_t n_docs = 0;
   float* D = nullptr;
   unsigned char* img = nullptr;  // [hi 128 x fp16 | lo 128 x fp16] per token, scaled by d_scale (split-fp16 form)
   unsigned char* img_hi = nullptr;  // [hi 128 x fp16] per token: first pass of the two-pass top-k
   float d_scale = 1.f;           // power of two; img == nullptr: the store is not finite -> fp32-input form only
   float d_norm_max = 0.f;        // largest token L2 norm (error bound of the first pass)
   long long* doc_ptr = nullptr;
+  int cus = 0;  // compute units of `device` (the re-scoring pass's grid)
   hipStream_t stream = nullptr;
   std::mutex mu;
   DevBuf full[2], qbuf, sbuf, ibuf;  // full[0]: "_device" calls, full[1]: host-pointer calls (see dense.hip)
@@ -1223,35 +1174,97 @@ struct MsShape {
 };
 MsShape ms_shape(const amdr_maxsim* h) { return MsShape{h->n_docs, h->img != nullptr, h->img_hi != nullptr}; }
 
-bool ms_half(const MsShape& s) {
-  const char* pin = getenv("AMDR_MAXSIM_F16X3");
-  return s.img && !(pin && pin[0] == '0');  // split-fp16 MFMA form (default) / fp32-input form
+// ---- the route: which form a call takes, decided once ---------------------------------------------------------------------
+// Everything about a call that is fixed before its first launch.  The three pins are read here, once per call (tests set
+// them between calls of one process: nothing is kept from one call to the next): AMDR_MAXSIM_F16X3=0 the fp32-input
+// forms, AMDR_MAXSIM_TWOPASS=0 one pass, AMDR_MAXSIM_DOCS the documents per block of the ring kernels.
+enum class MsForm {
+  TwoPass,   // top-k only: hi-only pass 1 over every document, candidates re-scored in full, top-k over the candidates
+  Ring,      // maxsim_scores_ring_kernel: split-fp16 tiles shared by 8 queries through the LDS ring
+  Blocked,   // maxsim_scores_blocked_kernel: fp32-input tiles shared by 8 queries
+  PairHalf,  // maxsim_scores_h_kernel: one wave per (query, document), split-fp16
+  PairF32,   // maxsim_scores_kernel: one wave per (query, document), fp32-input
+};
+struct MsRoute {
+  MsForm form;
+  int docs;  // documents per block of the pass that walks them (TwoPass: pass 1; the pair forms: one per wave), with
+             // the grid limit of 65 535 blocks in y applied
+};
+// Ring depths and blocks per CU: constants of the route (template arguments of the kernels; amdr_maxsim_create sizes
+// the kernels' dynamic LDS from them).
+constexpr int kRing = 4;   // one-pass ring: LDS stages (2 / 3 / 4 / 6 measured; best: 4)
+constexpr int kRing1 = 3;  // pass 1: three blocks per CU
+// Pass 2 (same process, interleaved, 1 168 UCC-en queries, whole channel):
+// 4 stages x 2 blocks per CU (64 KB of LDS each: 4 waves per SIMD) 0.8916 ms; 3 x 3: 0.8903; 2 x 4 (8 waves per SIMD):
+// 0.8837; 2 stages with 6 / 8 blocks per CU in the grid (the items then outnumber the blocks by little: the hardware
+// deals them) 0.8815 / 0.8793.  What the deeper ring bought inside a block, twice the resident waves buy across
+// blocks: the per-item latencies (descriptor -> query list -> query fragments -> first tile) overlap another
+// block's products.  Civil-Code-zh: 1.1017 -> 1.0947.
+constexpr int kRing2 = 2, kBlocks2 = 8;
+constexpr int kPairLds = kMsWaves * 16384;  // maxsim_overflow_kernel: a 16-KiB stage per wave
+// Documents per block.  One-pass ring: 16 (measured best).  Pass 1 (round 4, scripts/ab_maxsim_env.py — variants
+// interleaved in one process, channel ms): UCC-en 16 / 24 / 29 / 32: 0.891 / 0.884 / 0.897 / 0.903, Civil-Code-zh 16 / 24 /
+// 32 / 48 / 64: 1.161 / 1.161 / 1.163 / 1.101* / 1.095* (*another box: 32 = 1.090).  Whole rounds of the chip's block slots
+// (29 documents: 3 066 blocks = 3.99 rounds of 768, against 3.6 at 32) bought nothing, nor did 2 or 4 ring stages (5 or
+// 2 blocks per CU instead of 3: -0.5 % / +2 %): the pass sits on a plateau that scheduling does not move.
+constexpr int kDocsRing = 16, kDocsPass1 = 24;
+
+MsRoute ms_route(const MsShape& s, int nq, int k, bool want_topk) {
+  auto off = [](const char* name) { const char* e = getenv(name); return e && e[0] == '0'; };
+  const bool half = s.img && !off("AMDR_MAXSIM_F16X3");  // split-fp16 MFMA form (default) / fp32-input form
+  const bool batch = nq >= kMsQ;                         // batches: document tiles shared by 8 queries through LDS
+  const char* dpb = getenv("AMDR_MAXSIM_DOCS");
+  auto docs = [&](long d) {
+    if (dpb && atoi(dpb) > 0) d = atoi(dpb);
+    while (ceil_div(s.n_docs, d) > 65535) d *= 2;
+    return (int)d;
+  };
+  // the two-pass top-k: batches on the split-fp16 form, k small against the corpus
+  if (want_topk && half && batch && s.img_hi && (int64_t)4 * k <= s.n_docs && !off("AMDR_MAXSIM_TWOPASS"))
+    return MsRoute{MsForm::TwoPass, docs(kDocsPass1)};
+  if (batch && half) return MsRoute{MsForm::Ring, docs(kDocsRing)};
+  if (batch && ceil_div(s.n_docs, kMsDocs) <= 65535) return MsRoute{MsForm::Blocked, kMsDocs};
+  return MsRoute{half ? MsForm::PairHalf : MsForm::PairF32, kMsWaves};
 }
-bool ms_half(const amdr_maxsim* h) { return ms_half(ms_shape(h)); }
-// the two-pass top-k: batches on the split-fp16 form, k small against the corpus (AMDR_MAXSIM_TWOPASS=0 pins one pass)
-bool ms_two_pass(const MsShape& s, int nq, int k, bool want_topk) {
-  const char* pin = getenv("AMDR_MAXSIM_TWOPASS");
-  if (pin && pin[0] == '0') return false;
-  return want_topk && ms_half(s) && nq >= kMsQ && s.img_hi && (int64_t)4 * k <= s.n_docs;
-}
-bool ms_two_pass(const amdr_maxsim* h, int nq, int k, bool want_topk) { return ms_two_pass(ms_shape(h), nq, k, want_topk); }
+
 int ms_cand_cap(int k) {
   const int c = next_pow2(2 * k);
   return c < 64 ? 64 : c;
 }
-// workspace of one call: the score rows [nq, n_docs]; two-pass: the first-pass rows, the re-scored rows, the candidate lists
-size_t ms_workspace_bytes(const MsShape& s, int nq, int k, bool want_topk) {
-  const size_t rows = ((size_t)nq * s.n_docs * sizeof(float) + 255) / 256 * 256;
-  if (!ms_two_pass(s, nq, k, want_topk)) return rows;
-  // three row blocks (first-pass scores, re-scored scores, the per-document query lists of the re-scoring pass) + the
-  // candidate lists [nq * cap], counters, the item table (<= n_docs + pairs / 8 descriptors of 32 bytes); an upper bound
-  return 3 * rows + ((size_t)nq * ms_cand_cap(k) + 2 * (size_t)nq) * sizeof(int) + 256 +  // (3rd: dlist [n_docs][nq])
-         ((size_t)nq * ms_cand_cap(k) + 4 * (size_t)s.n_docs + 8) * sizeof(int) +
-         ((size_t)s.n_docs + (size_t)nq * ms_cand_cap(k) / kMsQ + 8) * sizeof(MsItem) +
-         (size_t)nq * (32 * 512 + 2 * sizeof(float)) + 512;  // + the split image of the queries, their scales, norm sums
+
+// ---- the workspace ---------------------------------------------------------------------------------------------------------
+constexpr size_t kMsAlign = 256;  // of the row blocks and of the total
+size_t ms_rows_bytes(int64_t n_docs, int nq) {  // the score rows [nq, n_docs]: all a one-pass call uses
+  return ((size_t)nq * n_docs * sizeof(float) + kMsAlign - 1) / kMsAlign * kMsAlign;
 }
-size_t ms_workspace_bytes(const amdr_maxsim* h, int nq, int k, bool want_topk) {
-  return ms_workspace_bytes(ms_shape(h), nq, k, want_topk);
+// The two-pass workspace: the byte offset of every region, in the order ms_run's kernels meet them, and the end.  ms_run
+// takes its pointers from here, amdr_maxsim_reserve / amdr_maxsim_workspace_plan their sizes: there is no second sum.
+struct MsLayout {
+  size_t approx, exact, dlist, cand, cnt, ovf, dcnt, n_items, items, img_q, unscale_q, nsum_q, bytes;
+};
+MsLayout ms_layout(int64_t n_docs, int nq, int k) {
+  MsLayout L;
+  size_t at = 0;
+  auto take = [&](size_t bytes, size_t align) { const size_t o = (at + align - 1) / align * align; at = o + bytes; return o; };
+  const size_t n = (size_t)n_docs, q = (size_t)nq, cap = (size_t)ms_cand_cap(k), row = q * n * sizeof(float);
+  L.approx = take(row, kMsAlign);                  // float [nq, n_docs]: first-pass scores
+  L.exact = take(row, kMsAlign);                   // float [nq, n_docs]: re-scored scores
+  L.dlist = take(row, kMsAlign);                   // int [n_docs][nq]: the queries a document is a candidate of
+  L.cand = take(q * cap * sizeof(int), kMsAlign);  // int [nq, cap]: a query's candidates
+  L.cnt = take(q * sizeof(int), sizeof(int));      // int [nq]: their number (0: the list overflowed)
+  L.ovf = take(q * sizeof(int), sizeof(int));      // int [nq]: the list overflowed
+  L.dcnt = take(n * sizeof(int), sizeof(int));     // int [n_docs]: candidates per document
+  L.n_items = take(sizeof(int), sizeof(int));      // items of the re-scoring pass
+  // 32-byte descriptors: a document that c queries take has ceil(c / 8) <= c / 8 + 1 items, nq * cap pairs at most
+  L.items = take((n + q * cap / kMsQ) * sizeof(MsItem), sizeof(MsItem));
+  L.img_q = take(q * 32 * 512, kMsAlign);  // the queries' split images (16-byte fragment loads)
+  L.unscale_q = take(q * sizeof(float), sizeof(float));  // float [nq]: their power-of-two scales
+  L.nsum_q = take(q * sizeof(float), sizeof(float));     // float [nq]: the sums of their token norms
+  L.bytes = take(0, kMsAlign);
+  return L;
+}
+size_t ms_workspace_bytes(const MsShape& s, const MsRoute& r, int nq, int k) {
+  return r.form == MsForm::TwoPass ? ms_layout(s.n_docs, nq, k).bytes : ms_rows_bytes(s.n_docs, nq);
 }
 // what amdr_maxsim_reserve(nq_max, k_max) sizes: the maximum over every call within it.  The form depends on k (a call
 // with 4 k <= n_docs takes the two-pass layout, three row blocks + the query images, a deeper one the one-pass rows), so
@@ -1260,110 +1273,75 @@ size_t ms_workspace_bytes(const amdr_maxsim* h, int nq, int k, bool want_topk) {
 size_t ms_reserve_bytes(const MsShape& s, int nq_max, int k_max) {
   size_t need = 0;
   for (int k = 1; k <= k_max; ++k) {
-    const size_t b = ms_workspace_bytes(s, nq_max, k, true);
+    const size_t b = ms_workspace_bytes(s, ms_route(s, nq_max, k, true), nq_max, k);
     need = b > need ? b : need;
   }
   return need;
 }
 
-int ms_run(amdr_maxsim* h, const float* Q_dev, int nq, int q_len, int k, float* full_dev, float* scores_dev,
-           int64_t* ids_dev, hipStream_t st) {
-  const bool half = ms_half(h);
+#define AMDR_MS_LAUNCH(...) do { hipLaunchKernelGGL(__VA_ARGS__); AMDR_HIP(hipGetLastError()); } while (0)
+
+int ms_run_two_pass(amdr_maxsim* h, const MsRoute& r, const float* Q_dev, int nq, int q_len, int k, const DevBuf& ws,
+                    float* scores_dev, int64_t* ids_dev, hipStream_t st) {
   const float unscale_d = 1.f / h->d_scale;
-  const bool batch = nq >= kMsQ;  // batches: document tiles shared by 8 queries through LDS
-  if (ms_two_pass(h, nq, k, scores_dev != nullptr)) {
-    const size_t rows = ((size_t)nq * h->n_docs * sizeof(float) + 255) / 256 * 256;
-    unsigned char* wsb = reinterpret_cast<unsigned char*>(full_dev);
-    float* approx = full_dev;
-    float* exact = reinterpret_cast<float*>(wsb + rows);
-    const int cap = ms_cand_cap(k);
-    int* dlist = reinterpret_cast<int*>(wsb + 2 * rows);  // [n_docs][nq] the queries a document is a candidate of
-    int* cand = reinterpret_cast<int*>(wsb + 3 * rows);
-    int* cnt = cand + (size_t)nq * cap;
-    int* ovf = cnt + nq;
-    const int cap_sel = topk_cap(k);
-    int* dcnt = ovf + nq;                     // [n_docs] candidates per document
-    int* ioff = dcnt + h->n_docs;             // [1] items of the re-scoring pass
-    MsItem* items = reinterpret_cast<MsItem*>(((uintptr_t)(ioff + 1) + 31) & ~(uintptr_t)31);
-    unsigned char* img_q = reinterpret_cast<unsigned char*>(
-        ((uintptr_t)(items + h->n_docs + (size_t)nq * cap / kMsQ + 8) + 255) & ~(uintptr_t)255);
-    float* unscale_q = reinterpret_cast<float*>(img_q + (size_t)nq * 32 * 512);
-    float* nsum_q = unscale_q + nq;
-    // documents per block of pass 1 (round 4, scripts/ab_maxsim_env.py — variants interleaved in one process, channel ms):
-    // UCC-en 16 / 24 / 29 / 32: 0.891 / 0.884 / 0.897 / 0.903, Civil-Code-zh 16 / 24 / 32 / 48 / 64: 1.161 / 1.161 / 1.163 /
-    // 1.101* / 1.095* (*another box: 32 = 1.090).  Whole rounds of the chip's block slots (29 documents: 3 066 blocks = 3.99
-    // rounds of 768, against 3.6 at 32) bought nothing, nor did 2 or 4 ring stages (5 or 2 blocks per CU instead of 3:
-    // -0.5 % / +2 %): the pass sits on a plateau that scheduling does not move.
-    const char* dpb = getenv("AMDR_MAXSIM_DOCS");
-    long docs = dpb && atoi(dpb) > 0 ? atoi(dpb) : 24;
-    while (ceil_div(h->n_docs, docs) > 65535) docs *= 2;
-    hipLaunchKernelGGL(maxsim_split_queries_kernel, dim3(ceil_div(nq, 4)), dim3(256), 0, st, Q_dev, nq, q_len, img_q,
-                       unscale_q, nsum_q);
-    constexpr int kRing1 = 3;  // LDS stages of pass 1: three blocks per CU
-    AMDR_HIP(hipFuncSetAttribute((const void*)maxsim_hi2_ring_kernel<kRing1>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 kRing1 * 16384));
-    hipLaunchKernelGGL((maxsim_hi2_ring_kernel<kRing1>), dim3(ceil_div(nq, 2 * kMsQ2), ceil_div(h->n_docs, docs)),
-                       dim3(kMsQ2 * 64), kRing1 * 16384, st, h->img_hi, h->doc_ptr, (long)h->n_docs, (int)docs, nq, q_len,
-                       approx, unscale_d, img_q, unscale_q);
-    AMDR_HIP(hipMemsetAsync(dcnt, 0, (size_t)h->n_docs * sizeof(int), st));
-    hipLaunchKernelGGL(maxsim_select_kernel, dim3(nq), dim3(64), (size_t)cap_sel * sizeof(C32), st, approx,
-                       (long)h->n_docs, q_len, k, cap_sel, h->d_norm_max, unscale_d, cap, cand, cnt, ovf, dcnt, dlist, nq,
-                       nsum_q, unscale_q);
-    constexpr int kPairLds = kMsWaves * 16384;
-    AMDR_HIP(hipFuncSetAttribute((const void*)maxsim_overflow_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kPairLds));
-    int dev = 0, cus = 256;
-    AMDR_HIP(hipGetDevice(&dev));
-    AMDR_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    hipLaunchKernelGGL(maxsim_items_kernel, dim3(1), dim3(256), 0, st, dcnt, (long)h->n_docs, h->doc_ptr, ioff, items);
-    // Ring depth and blocks per CU of the re-scoring pass (same process, interleaved, 1 168 UCC-en queries, whole channel):
-    // 4 stages x 2 blocks per CU (64 KB of LDS each: 4 waves per SIMD) 0.8916 ms; 3 x 3: 0.8903; 2 x 4 (8 waves per SIMD):
-    // 0.8837; 2 stages with 6 / 8 blocks per CU in the grid (the items then outnumber the blocks by little: the hardware
-    // deals them) 0.8815 / 0.8793.  What the deeper ring bought inside a block, twice the resident waves buy across
-    // blocks: the per-item latencies (descriptor -> query list -> query fragments -> first tile) overlap another
-    // block's products.  Civil-Code-zh: 1.1017 -> 1.0947.
-    constexpr int kRing2 = 2, kBlocks2 = 8;
-    AMDR_HIP(hipFuncSetAttribute((const void*)maxsim_rescore_ring_kernel<kRing2>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 kRing2 * 16384));
-    hipLaunchKernelGGL((maxsim_rescore_ring_kernel<kRing2>), dim3(kBlocks2 * cus), dim3(kMsQ * 64), kRing2 * 16384, st, h->img,
-                       (long)h->n_docs, img_q, unscale_q, q_len, unscale_d, items, ioff, dlist, nq, exact);
-    hipLaunchKernelGGL(maxsim_overflow_kernel, dim3(nq), dim3(256), kPairLds, st, h->img, h->doc_ptr, (long)h->n_docs,
-                       Q_dev, q_len, unscale_d, ovf, exact);
-    AMDR_HIP(hipGetLastError());
-    hipLaunchKernelGGL(maxsim_final_topk_kernel, dim3(ceil_div(nq, 4)), dim3(256), (size_t)4 * cap_sel * sizeof(C32), st,
-                       exact, (long)h->n_docs, nq, cand, cnt, ovf, cap, k, cap_sel, scores_dev, (long long*)ids_dev);
-    AMDR_HIP(hipGetLastError());
-    return AMDR_OK;
+  const long n = (long)h->n_docs;
+  const MsLayout L = ms_layout(h->n_docs, nq, k);
+  unsigned char *w = ws.as<unsigned char>(), *img_q = w + L.img_q;
+  float *approx = (float*)(w + L.approx), *exact = (float*)(w + L.exact), *unscale_q = (float*)(w + L.unscale_q);
+  float* nsum_q = (float*)(w + L.nsum_q);
+  int *dlist = (int*)(w + L.dlist), *cand = (int*)(w + L.cand), *cnt = (int*)(w + L.cnt), *ovf = (int*)(w + L.ovf);
+  int *dcnt = (int*)(w + L.dcnt), *n_items = (int*)(w + L.n_items);
+  MsItem* items = (MsItem*)(w + L.items);
+  const int cap = ms_cand_cap(k), cap_sel = topk_cap(k);
+  AMDR_MS_LAUNCH(maxsim_split_queries_kernel, dim3(ceil_div(nq, 4)), dim3(256), 0, st, Q_dev, nq, q_len, img_q, unscale_q,
+                 nsum_q);
+  AMDR_MS_LAUNCH((maxsim_hi2_ring_kernel<kRing1>), dim3(ceil_div(nq, 2 * kMsQ2), ceil_div(n, r.docs)), dim3(kMsQ2 * 64),
+                 kRing1 * 16384, st, h->img_hi, h->doc_ptr, n, r.docs, nq, q_len, approx, unscale_d, img_q, unscale_q);
+  AMDR_HIP(hipMemsetAsync(dcnt, 0, (size_t)n * sizeof(int), st));
+  AMDR_MS_LAUNCH(maxsim_select_kernel, dim3(nq), dim3(64), (size_t)cap_sel * sizeof(C32), st, approx, n, q_len, k, cap_sel,
+                 h->d_norm_max, unscale_d, cap, cand, cnt, ovf, dcnt, dlist, nq, nsum_q, unscale_q);
+  AMDR_MS_LAUNCH(maxsim_items_kernel, dim3(1), dim3(256), 0, st, dcnt, n, h->doc_ptr, n_items, items);
+  AMDR_MS_LAUNCH((maxsim_rescore_ring_kernel<kRing2>), dim3(kBlocks2 * h->cus), dim3(kMsQ * 64), kRing2 * 16384, st, h->img,
+                 n, img_q, unscale_q, q_len, unscale_d, items, n_items, dlist, nq, exact);
+  AMDR_MS_LAUNCH(maxsim_overflow_kernel, dim3(nq), dim3(256), kPairLds, st, h->img, h->doc_ptr, n, Q_dev, q_len, unscale_d,
+                 ovf, exact);
+  AMDR_MS_LAUNCH(maxsim_final_topk_kernel, dim3(ceil_div(nq, 4)), dim3(256), (size_t)4 * cap_sel * sizeof(C32), st, exact, n,
+                 nq, cand, cnt, ovf, cap, k, cap_sel, scores_dev, (long long*)ids_dev);
+  return AMDR_OK;
+}
+
+// The launches of one call on route r, in workspace ws (sized by ms_workspace_bytes for the same route).
+int ms_run(amdr_maxsim* h, const MsRoute& r, const float* Q_dev, int nq, int q_len, int k, const DevBuf& ws,
+           float* scores_dev, int64_t* ids_dev, hipStream_t st) {
+  const size_t need = ms_workspace_bytes(ms_shape(h), r, nq, k);
+  AMDR_REQUIRE(need <= ws.cap, "maxsim: a call of %zu bytes in a workspace of %zu", need, ws.cap);
+  const float unscale_d = 1.f / h->d_scale;
+  const long n = (long)h->n_docs;
+  float* full_dev = ws.as<float>();
+  switch (r.form) {
+    case MsForm::Ring:
+      AMDR_MS_LAUNCH((maxsim_scores_ring_kernel<kRing>), dim3(ceil_div(nq, kMsQ), ceil_div(n, r.docs)), dim3(kMsQ * 64),
+                     kRing * 16384, st, h->img, h->doc_ptr, n, r.docs, Q_dev, nq, q_len, full_dev, unscale_d);
+      break;
+    case MsForm::Blocked:
+      AMDR_MS_LAUNCH(maxsim_scores_blocked_kernel, dim3(ceil_div(nq, kMsQ), ceil_div(n, r.docs)), dim3(kMsQ * 64), 0, st, h->D,
+                     h->doc_ptr, n, Q_dev, nq, q_len, full_dev);
+      break;
+    case MsForm::PairHalf:
+      AMDR_MS_LAUNCH(maxsim_scores_h_kernel, dim3(ceil_div(n, r.docs), nq), dim3(256), 0, st, h->img, h->doc_ptr, n, Q_dev,
+                     q_len, full_dev, unscale_d);
+      break;
+    case MsForm::PairF32:
+      AMDR_MS_LAUNCH(maxsim_scores_kernel, dim3(ceil_div(n, r.docs), nq), dim3(256), 0, st, h->D, h->doc_ptr, n, Q_dev, q_len,
+                     full_dev);
+      break;
+    case MsForm::TwoPass:
+      return ms_run_two_pass(h, r, Q_dev, nq, q_len, k, ws, scores_dev, ids_dev, st);
   }
-  if (batch && half) {
-    constexpr int kRing = 4;  // LDS stages (2 / 3 / 4 / 6 measured; best: 4)
-    const char* dpb = getenv("AMDR_MAXSIM_DOCS");  // documents per block (measured best: 16)
-    long docs = dpb && atoi(dpb) > 0 ? atoi(dpb) : 16;
-    while (ceil_div(h->n_docs, docs) > 65535) docs *= 2;
-    AMDR_HIP(hipFuncSetAttribute((const void*)maxsim_scores_ring_kernel<kRing>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 kRing * 16384));
-    hipLaunchKernelGGL((maxsim_scores_ring_kernel<kRing>), dim3(ceil_div(nq, kMsQ), ceil_div(h->n_docs, docs)),
-                       dim3(kMsQ * 64), kRing * 16384, st, h->img, h->doc_ptr, (long)h->n_docs, (int)docs, Q_dev, nq, q_len,
-                       full_dev, unscale_d);
-  } else if (batch && ceil_div(h->n_docs, kMsDocs) <= 65535) {
-    dim3 grid(ceil_div(nq, kMsQ), ceil_div(h->n_docs, kMsDocs));
-    hipLaunchKernelGGL(maxsim_scores_blocked_kernel, grid, dim3(kMsQ * 64), 0, st, h->D, h->doc_ptr, (long)h->n_docs,
-                       (long)h->n_tokens, Q_dev, nq, q_len, full_dev);
-  } else {
-    dim3 grid(ceil_div(h->n_docs, kMsWaves), nq);
-    if (half)
-      hipLaunchKernelGGL(maxsim_scores_h_kernel, grid, dim3(256), 0, st, h->img, h->doc_ptr, (long)h->n_docs, Q_dev,
-                         q_len, full_dev, unscale_d);
-    else
-      hipLaunchKernelGGL(maxsim_scores_kernel, grid, dim3(256), 0, st, h->D, h->doc_ptr, (long)h->n_docs, Q_dev, q_len,
-                         full_dev);
-  }
-  AMDR_HIP(hipGetLastError());
   if (scores_dev) {
-    int cap = topk_cap(k);
-    size_t lds = (size_t)kMsWaves * cap * sizeof(C32) + kMsWaves * sizeof(int);
-    hipLaunchKernelGGL(rowscores_topk_kernel, dim3(nq), dim3(256), lds, st, full_dev, (long)h->n_docs, k, cap,
-                       scores_dev, (long long*)ids_dev);
-    AMDR_HIP(hipGetLastError());
+    const int cap = topk_cap(k);
+    AMDR_MS_LAUNCH(rowscores_topk_kernel, dim3(nq), dim3(256), (size_t)kMsWaves * cap * sizeof(C32) + kMsWaves * sizeof(int),
+                   st, full_dev, n, k, cap, scores_dev, (long long*)ids_dev);
   }
   return AMDR_OK;
 }
@@ -1398,13 +1376,19 @@ int amdr_maxsim_create(const float* D_host, const int64_t* doc_ptr, int64_t n_do
   if (!h) return fail(AMDR_ENOMEM, "maxsim_create: host alloc");
   h->device = device;
   h->n_docs = n_docs;
-  h->n_tokens = nt;
   hipError_t e = hipMalloc((void**)&h->D, (size_t)nt * dim * sizeof(float));
   if (e == hipSuccess) e = hipMemcpy(h->D, D_host, (size_t)nt * dim * sizeof(float), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMalloc((void**)&h->doc_ptr, (size_t)(n_docs + 1) * sizeof(long long));
   if (e == hipSuccess)
     e = hipMemcpy(h->doc_ptr, doc_ptr, (size_t)(n_docs + 1) * sizeof(long long), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
+  // once per handle (it is bound to this device): the CU count, the dynamic-LDS limits of the ring and overflow kernels
+  if (e == hipSuccess) e = hipDeviceGetAttribute(&h->cus, hipDeviceAttributeMultiprocessorCount, device);
+  auto lds = [&](const void* f, int b) { if (e == hipSuccess) e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, b); };
+  lds((const void*)maxsim_scores_ring_kernel<kRing>, kRing * 16384);
+  lds((const void*)maxsim_hi2_ring_kernel<kRing1>, kRing1 * 16384);
+  lds((const void*)maxsim_rescore_ring_kernel<kRing2>, kRing2 * 16384);
+  lds((const void*)maxsim_overflow_kernel, kPairLds);
   // the split-fp16 image: the store's largest |component| fixes a power-of-two scale into [0.5, 1), then every
   // token row is split once (a store with a NaN / infinity keeps the fp32-input form only)
   unsigned int* mx = nullptr;
@@ -1457,23 +1441,23 @@ int amdr_maxsim_ndocs(const amdr_maxsim_t* h, int64_t* n) {
 int amdr_maxsim_plan_info(const amdr_maxsim_t* h, int32_t nq, char* buf, int32_t buf_len) {
   AMDR_REQUIRE(h && buf && buf_len > 0, "maxsim_plan_info: null");
   AMDR_REQUIRE(nq >= 1, "maxsim_plan_info: nq=%d", nq);
-  const MsShape s = ms_shape(h);
-  const bool half = ms_half(s);
-  const bool batch = nq >= kMsQ;
-  // the ABI has no k: the two-pass form as ms_run takes it at the shallowest depth
-  if (ms_two_pass(s, nq, 1, true))
-    snprintf(buf, buf_len,
-             "maxsim_hi2_ring_kernel split-fp16 two-pass top-k (k <= n_docs / 4): maxsim_split_queries_kernel + pass 1 hi "
-             "parts only (1 x v_mfma_f32_32x32x16_f16 per block, two queries per wave) + maxsim_select_kernel + "
-             "maxsim_rescore_ring_kernel<2> (pairs grouped by document: a block = one document x 8 of its queries; 8 blocks "
-             "per CU) (hi + lo/2048, 3 MFMAs per block, candidates only) + maxsim_final_topk_kernel (the candidates only); "
-             "full score rows: maxsim_scores_ring_kernel");
-  else if (half)
-    snprintf(buf, buf_len, "%s split-fp16 (hi + lo/2048, 3 x v_mfma_f32_32x32x16_f16 per block) + rowscores_topk_kernel",
-             batch ? "maxsim_scores_ring_kernel" : "maxsim_scores_h_kernel");
-  else
-    snprintf(buf, buf_len, "%s fp32-input (v_mfma_f32_16x16x4_f32) + rowscores_topk_kernel",
-             batch ? "maxsim_scores_blocked_kernel" : "maxsim_scores_kernel");
+  static const char* const half = "%s split-fp16 (hi + lo/2048, 3 x v_mfma_f32_32x32x16_f16 per block) + rowscores_topk_kernel";
+  static const char* const f32 = "%s fp32-input (v_mfma_f32_16x16x4_f32) + rowscores_topk_kernel";
+  switch (ms_route(ms_shape(h), nq, 1, true).form) {  // the ABI has no k: the route at the shallowest depth
+    case MsForm::TwoPass:
+      snprintf(buf, buf_len,
+               "maxsim_hi2_ring_kernel split-fp16 two-pass top-k (k <= n_docs / 4): maxsim_split_queries_kernel + pass 1 hi "
+               "parts only (1 x v_mfma_f32_32x32x16_f16 per block, two queries per wave) + maxsim_select_kernel + "
+               "maxsim_rescore_ring_kernel<%d> (pairs grouped by document: a block = one document x %d of its queries; %d "
+               "blocks per CU) (hi + lo/2048, 3 MFMAs per block, candidates only) + maxsim_final_topk_kernel (the candidates "
+               "only); full score rows: maxsim_scores_ring_kernel",
+               kRing2, kMsQ, kBlocks2);
+      break;
+    case MsForm::Ring: snprintf(buf, buf_len, half, "maxsim_scores_ring_kernel"); break;
+    case MsForm::PairHalf: snprintf(buf, buf_len, half, "maxsim_scores_h_kernel"); break;
+    case MsForm::Blocked: snprintf(buf, buf_len, f32, "maxsim_scores_blocked_kernel"); break;
+    case MsForm::PairF32: snprintf(buf, buf_len, f32, "maxsim_scores_kernel"); break;
+  }
   return AMDR_OK;
 }
 
@@ -1498,7 +1482,7 @@ int amdr_maxsim_workspace_plan(int64_t n_docs, int32_t split_image, int32_t nq_m
                "maxsim_workspace_plan: bad sizes");
   const MsShape s{n_docs, split_image != 0, split_image != 0};  // create() makes both images or neither
   out2[0] = (int64_t)ms_reserve_bytes(s, nq_max, k_max);
-  out2[1] = (int64_t)ms_workspace_bytes(s, nq, k, true);
+  out2[1] = (int64_t)ms_workspace_bytes(s, ms_route(s, nq, k, true), nq, k);
   return AMDR_OK;
 }
 
@@ -1510,8 +1494,9 @@ int amdr_maxsim_search_device(amdr_maxsim_t* h, const float* Q_dev, int32_t nq, 
   if (nq == 0) return AMDR_OK;
   std::lock_guard<std::mutex> g(h->mu);
   AMDR_HIP(hipSetDevice(h->device));
-  if ((rc = h->full[0].ensure(ms_workspace_bytes(h, nq, k, true)))) return rc;
-  return ms_run(h, Q_dev, nq, q_len, k, h->full[0].as<float>(), scores_dev, ids_dev, (hipStream_t)stream);
+  const MsRoute r = ms_route(ms_shape(h), nq, k, true);
+  if ((rc = h->full[0].ensure(ms_workspace_bytes(ms_shape(h), r, nq, k)))) return rc;
+  return ms_run(h, r, Q_dev, nq, q_len, k, h->full[0], scores_dev, ids_dev, (hipStream_t)stream);
 }
 
 int amdr_maxsim_search(amdr_maxsim_t* h, const float* Q_host, int32_t nq, int32_t q_len, int32_t k,
@@ -1524,12 +1509,12 @@ int amdr_maxsim_search(amdr_maxsim_t* h, const float* Q_host, int32_t nq, int32_
   AMDR_HIP(hipSetDevice(h->device));
   size_t qbytes = (size_t)nq * q_len * kDim * sizeof(float);
   if ((rc = h->qbuf.ensure(qbytes))) return rc;
-  if ((rc = h->full[1].ensure(ms_workspace_bytes(h, nq, k, true)))) return rc;
+  const MsRoute r = ms_route(ms_shape(h), nq, k, true);
+  if ((rc = h->full[1].ensure(ms_workspace_bytes(ms_shape(h), r, nq, k)))) return rc;
   if ((rc = h->sbuf.ensure((size_t)nq * k * sizeof(float)))) return rc;
   if ((rc = h->ibuf.ensure((size_t)nq * k * sizeof(int64_t)))) return rc;
   AMDR_HIP(hipMemcpyAsync(h->qbuf.p, Q_host, qbytes, hipMemcpyHostToDevice, h->stream));
-  rc = ms_run(h, h->qbuf.as<float>(), nq, q_len, k, h->full[1].as<float>(), h->sbuf.as<float>(), h->ibuf.as<int64_t>(),
-              h->stream);
+  rc = ms_run(h, r, h->qbuf.as<float>(), nq, q_len, k, h->full[1], h->sbuf.as<float>(), h->ibuf.as<int64_t>(), h->stream);
   if (rc) return rc;
   AMDR_HIP(hipMemcpyAsync(scores_host, h->sbuf.p, (size_t)nq * k * sizeof(float), hipMemcpyDeviceToHost, h->stream));
   AMDR_HIP(hipMemcpyAsync(ids_host, h->ibuf.p, (size_t)nq * k * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
@@ -1546,9 +1531,10 @@ int amdr_maxsim_scores(amdr_maxsim_t* h, const float* Q_host, int32_t nq, int32_
   AMDR_HIP(hipSetDevice(h->device));
   size_t qbytes = (size_t)nq * q_len * kDim * sizeof(float);
   if ((rc = h->qbuf.ensure(qbytes))) return rc;
-  if ((rc = h->full[1].ensure((size_t)nq * h->n_docs * sizeof(float)))) return rc;
+  const MsRoute r = ms_route(ms_shape(h), nq, 1, false);  // every score: one pass
+  if ((rc = h->full[1].ensure(ms_workspace_bytes(ms_shape(h), r, nq, 1)))) return rc;
   AMDR_HIP(hipMemcpyAsync(h->qbuf.p, Q_host, qbytes, hipMemcpyHostToDevice, h->stream));
-  rc = ms_run(h, h->qbuf.as<float>(), nq, q_len, 1, h->full[1].as<float>(), nullptr, nullptr, h->stream);
+  rc = ms_run(h, r, h->qbuf.as<float>(), nq, q_len, 1, h->full[1], nullptr, nullptr, h->stream);
   if (rc) return rc;
   AMDR_HIP(hipMemcpyAsync(scores_host, h->full[1].p, (size_t)nq * h->n_docs * sizeof(float), hipMemcpyDeviceToHost,
                           h->stream));

@@ -222,6 +222,23 @@ def test_maxsim_reserve_covers_every_call(monkeypatch):
     for split in (True, False):
         for n in (1, 7, 8, 9, 40, 74, 158, 200, 591, 1260):
             assert _reserve_sweep(lambda a, b, c, d: _native.maxsim_workspace_plan(n, split, a, b, c, d)) > 10_000
+    # the two-pass figure is the end of the layout the call runs in: aligned like its row blocks, three of them and more;
+    # at a fixed depth no region shrinks with the batch
+    two_pass = 0
+    for n in (8, 40, 74, 591, 1260):
+        for k in (1, 2, 10, 18, 147, 256):
+            last = 0
+            for nq in SWEEP_NQ:
+                used = _native.maxsim_workspace_plan(n, True, nq, k, nq, k)[1]
+                rows = (nq * n * 4 + 255) // 256 * 256
+                assert used >= last, (n, k, nq, used, last)
+                last = used
+                if nq >= 8 and 4 * k <= n:
+                    assert used % 256 == 0 and used > 3 * rows, (n, k, nq, used, rows)
+                    two_pass += 1
+                else:
+                    assert used == rows, (n, k, nq, used, rows)
+    assert two_pass >= 100
     # without the image (a store with a NaN / infinity) or with the two-pass form pinned off: one-pass rows only
     rows = (64 * 74 * 4 + 255) // 256 * 256
     assert _native.maxsim_workspace_plan(74, False, 64, 80, 64, 10) == (rows, rows)
