@@ -25,27 +25,6 @@ FUSE_METHODS = {"rrf_norm_blend": 0, "rrf": 1, "wrrf": 2, "weighted_sum": 3}
 FV = dict(score=0, rrf_norm=1, weighted_sum=2, dense_norm=3, bm25_norm=4, colbert_norm=5,
           contrib_dense=6, contrib_bm25=7, contrib_colbert=8)
 
-# every symbol include/amdretrieval.h declares (checked by tests/test_abi.py)
-EXPORTS = (
-    "amdr_last_error", "amdr_version", "amdr_device_count", "amdr_device_name", "amdr_workspace_growths",
-    "amdr_dense_create", "amdr_dense_create_from_device", "amdr_dense_add", "amdr_dense_ntotal", "amdr_dense_dim",
-    "amdr_dense_reserve", "amdr_dense_search", "amdr_dense_search_device", "amdr_dense_search_fuse_device", "amdr_hybrid_small_device", "amdr_dense_small_create", "amdr_dense_small_approx_device", "amdr_dense_small_destroy", "amdr_dense_two_pass_fallbacks", "amdr_dense_read_rows", "amdr_dense_score_rows",
-    "amdr_dense_plan_info", "amdr_dense_workspace_plan", "amdr_dense_hi_counters", "amdr_dense_profile_begin", "amdr_dense_profile_end", "amdr_dense_destroy",
-    "amdr_bm25_create", "amdr_bm25_ndocs", "amdr_bm25_reserve", "amdr_bm25_workspace_plan", "amdr_bm25_plan_info", "amdr_bm25_search", "amdr_bm25_search_device",
-    "amdr_bm25_scores", "amdr_bm25_destroy",
-    "amdr_tokenizer_create", "amdr_tokenizer_encode", "amdr_tokenizer_encode_joined", "amdr_tokenizer_encode_ptrs", "amdr_tokenizer_spans", "amdr_tokenizer_destroy",
-    "amdr_tokenizer_pack", "amdr_tokenizer_device_create", "amdr_tokenizer_device_reserve", "amdr_tokenizer_encode_device",
-    "amdr_tokenizer_device_destroy",
-    "amdr_maxsim_create", "amdr_maxsim_ndocs", "amdr_maxsim_plan_info", "amdr_maxsim_reserve", "amdr_maxsim_workspace_plan", "amdr_maxsim_search",
-    "amdr_maxsim_search_device", "amdr_maxsim_scores", "amdr_maxsim_destroy",
-    "amdr_fuse", "amdr_fuse_device", "amdr_rerank_blend", "amdr_rerank_blend_device", "amdr_fuse_compact_device",
-    "amdr_merge_topk_f32_device", "amdr_merge_topk_f64_device",
-    "amdr_shard_row_words", "amdr_shard_pack_device", "amdr_shard_merge_device",
-    "amdr_graph_create", "amdr_graph_reserve", "amdr_graph_walk", "amdr_graph_search", "amdr_graph_search_device",
-    "amdr_graph_destroy",
-)
-
-
 # argument kinds of every export, in header order: P = pointer (host or device, or an opaque handle /
 # handle out-parameter / hipStream_t passed as void*), i = int32_t, l = int64_t, d = double.
 # tests/test_abi.py parses include/amdretrieval.h and checks this table against the prototypes, so a
@@ -75,6 +54,7 @@ SIGNATURES = {
     "amdr_graph_search": "PPPPPiiiiP" + "P" * 7, "amdr_graph_search_device": "PPPPPPiiiiP" + "P" * 8,
     "amdr_graph_destroy": "P",
 }
+EXPORTS = tuple(SIGNATURES)  # every symbol include/amdretrieval.h declares (checked by tests/test_abi.py)
 _KIND = {"P": C.c_void_p, "i": C.c_int32, "l": C.c_int64, "d": C.c_double}
 
 
@@ -237,10 +217,34 @@ def _c(a, dtype) -> np.ndarray:
     return np.ascontiguousarray(a, dtype=dtype)
 
 
+class _Handle:
+    """An opaque library handle `_h`, released by close() or garbage collection through the export `_destroy` names
+    (tolerant of a missing `_h`: a constructor can raise before it exists)."""
+    _destroy = ""
+
+    def close(self) -> None:
+        if getattr(self, "_h", None) and self._h.value:
+            getattr(load(), self._destroy)(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+    def _plan_info(self, name: str, *dims: int) -> str:
+        """The text an amdr_*_plan_info export writes for these dimensions (no device work)."""
+        buf = C.create_string_buffer(1024)
+        _check(getattr(load(), name)(self._h, *(C.c_int32(x) for x in dims), buf, C.c_int32(len(buf))), name)
+        return buf.value.decode()
+
+
 # ---------------------------------------------------------------------------
-class DenseIndex:
+class DenseIndex(_Handle):
     """Exact inner-product index resident in HBM (replaces faiss IndexFlatIP /
     IndexHNSWFlat behind `index.search`, dense_retriever.py:42)."""
+    _destroy = "amdr_dense_destroy"
 
     def __init__(self, X: Optional[np.ndarray] = None, *, device: int = 0, dim: Optional[int] = None,
                  device_ptr: Optional[int] = None, n: Optional[int] = None, keepalive=None):
@@ -332,10 +336,7 @@ class DenseIndex:
 
     def plan_info(self, nq: int, k: int) -> str:
         """Kernels a search of nq queries at depth k launches on this index, and the cut of the work."""
-        buf = C.create_string_buffer(1024)
-        _check(load().amdr_dense_plan_info(self._h, C.c_int32(nq), C.c_int32(k), buf, C.c_int32(len(buf))),
-               "amdr_dense_plan_info")
-        return buf.value.decode()
+        return self._plan_info("amdr_dense_plan_info", nq, k)
 
     def hi_counters(self) -> Tuple[int, int, int, bool, int, int]:
         """(queries that took the fp16 first pass of large scans, those it could not resolve, current width level 0-2,
@@ -352,22 +353,12 @@ class DenseIndex:
         _check(load().amdr_dense_profile_end(self._h, C.byref(ms), C.byref(n)), "amdr_dense_profile_end")
         return float(ms.value), int(n.value)
 
-    def close(self) -> None:
-        if getattr(self, "_h", None) and self._h.value:
-            load().amdr_dense_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 # ---------------------------------------------------------------------------
-class BM25Index:
+class BM25Index(_Handle):
     """Okapi BM25 over term-major CSR postings (replaces BM25Okapi.get_scores +
     the Python sort, bm25_retriever.py:74-75)."""
+    _destroy = "amdr_bm25_destroy"
 
     def __init__(self, term_ptr, post_doc, post_tf, idf, doc_len, avgdl: float, k1: float = 1.5, b: float = 0.75,
                  *, device: int = 0):
@@ -410,10 +401,7 @@ class BM25Index:
 
     def plan_info(self, nq: int, k: int) -> str:
         """Which kernels a search of nq queries at depth k would launch, and the slabs (no device work)."""
-        buf = C.create_string_buffer(1024)
-        _check(load().amdr_bm25_plan_info(self._h, C.c_int32(nq), C.c_int32(k), buf, C.c_int32(len(buf))),
-               "amdr_bm25_plan_info")
-        return buf.value.decode()
+        return self._plan_info("amdr_bm25_plan_info", nq, k)
 
     def search_device(self, q_terms_ptr: int, q_ptr_ptr: int, nq: int, k: int, scores_ptr: int, ids_ptr: int,
                       stream: int = 0) -> None:
@@ -428,22 +416,12 @@ class BM25Index:
                                        _p(out, C.c_double)), "amdr_bm25_scores")
         return out
 
-    def close(self) -> None:
-        if getattr(self, "_h", None) and self._h.value:
-            load().amdr_bm25_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 # ---------------------------------------------------------------------------
-class Tokenizer:
+class Tokenizer(_Handle):
     """Batched native query tokeniser + vocabulary lookup (include/amdretrieval.h, csrc/tokenize.cpp): the jieba.cut
     rule for text without Han characters, then term ids — one call per batch, GIL released."""
+    _destroy = "amdr_tokenizer_destroy"
 
     def __init__(self, vocab: Sequence[str]):
         enc = [w.encode("utf-8") for w in vocab]
@@ -507,17 +485,6 @@ class Tokenizer:
             return None
         return [b[int(a):int(e)].decode("utf-8") for a, e in zip(st[: n.value], en[: n.value])]
 
-    def close(self) -> None:
-        if self._h:
-            load().amdr_tokenizer_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001
-            pass
-
 
 def utf8_views(texts: Sequence[Optional[str]]):
     """(ptrs i64 [n], lens i64 [n], total bytes, maybe_han bool [n], keepalive) of a list of str: the UTF-8 bytes where
@@ -558,11 +525,12 @@ def pack_texts(texts: Sequence[Optional[str]]) -> Tuple[np.ndarray, np.ndarray]:
     return blob[:total], offs
 
 
-class DeviceTokenizer:
+class DeviceTokenizer(_Handle):
     """The batched query tokeniser on the device (amdr_tokenizer_*_device, csrc/tokenize.hip): a copy of a host
     Tokenizer's vocabulary in HBM; encode_device turns a UTF-8 blob + offsets already on the device into the term-id
     CSR amdr_bm25_search_device takes, byte for byte what Tokenizer.encode gives for the same bytes.  Enqueue only;
     capturable after reserve()."""
+    _destroy = "amdr_tokenizer_device_destroy"
 
     def __init__(self, tok: "Tokenizer", *, device: int = 0):
         self.device = int(device)
@@ -600,20 +568,10 @@ class DeviceTokenizer:
         self.encode_device_ptrs(blob.data_ptr(), offs.data_ptr(), nq, n_bytes, term_ids.data_ptr(), int(term_ids.numel()),
                                 q_ptr.data_ptr(), needs_segmenter.data_ptr(), stream)
 
-    def close(self) -> None:
-        if getattr(self, "_h", None) and self._h.value:
-            load().amdr_tokenizer_device_destroy(self._h)
-            self._h = C.c_void_p()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001
-            pass
-
-
-class MaxSimIndex:
+class MaxSimIndex(_Handle):
     """Exhaustive ColBERT late interaction over fp32 token embeddings."""
+    _destroy = "amdr_maxsim_destroy"
 
     def __init__(self, D: np.ndarray, doc_ptr: np.ndarray, *, device: int = 0):
         D = _c(D, np.float32)
@@ -632,9 +590,7 @@ class MaxSimIndex:
 
     def plan_info(self, nq: int) -> str:
         """Kernels and arithmetic form a search of nq queries launches (no device work)."""
-        buf = C.create_string_buffer(1024)
-        _check(load().amdr_maxsim_plan_info(self._h, C.c_int32(nq), buf, C.c_int32(len(buf))), "amdr_maxsim_plan_info")
-        return buf.value.decode()
+        return self._plan_info("amdr_maxsim_plan_info", nq)
 
     def reserve(self, nq_max: int, k_max: int) -> None:
         _check(load().amdr_maxsim_reserve(self._h, C.c_int32(nq_max), C.c_int32(k_max)), "amdr_maxsim_reserve")
@@ -670,23 +626,13 @@ class MaxSimIndex:
                                          _p(out, C.c_float)), "amdr_maxsim_scores")
         return out
 
-    def close(self) -> None:
-        if getattr(self, "_h", None) and self._h.value:
-            load().amdr_maxsim_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 # ---------------------------------------------------------------------------
-class GraphIndex:
+class GraphIndex(_Handle):
     """The law graph in HBM for the graph channel (amdr_graph_*, csrc/graph.hip): CSR adjacency over interned article
     ids plus the node <-> chunk-row maps; walk + re-scoring + top-k of a whole batch against a DenseIndex's matrix
     (replaces LawGraphStore.walk + GraphRetriever.search per query, graph_store.py:89-169, graph_retriever.py:82-219)."""
+    _destroy = "amdr_graph_destroy"
 
     def __init__(self, node_ptr, edge_dst, edge_rel, edge_conf_raw, edge_conf_eff, edge_has_evidence, node_present,
                  node_row, row_node, row_norm, row_lang=None, *, n_rel: int, device: int = 0):
@@ -766,17 +712,6 @@ class GraphIndex:
                                                C.byref(params), *(_vp(o) for o in outs), _vp(stream)),
                "amdr_graph_search_device")
 
-    def close(self) -> None:
-        if getattr(self, "_h", None) and self._h.value:
-            load().amdr_graph_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001
-            pass
-
 
 # ---------------------------------------------------------------------------
 def make_fuse_params(*, method: str = "rrf_norm_blend", rrf_k: int = 60, alpha: float = 0.5, w_dense: float = 0.6,
@@ -855,10 +790,11 @@ def rerank_blend_device(nq: int, max_out: int, count: int, ids: int, vals: int, 
            "amdr_rerank_blend_device")
 
 
-class DenseSmallApprox:
+class DenseSmallApprox(_Handle):
     """The fp16 first pass over a short corpus on its own (amdr_dense_small_*; tests and measurements — the search calls
     run it inside): approximate scores of every (query, row) with a proven per-query bound on their distance from the
     exact dot product."""
+    _destroy = "amdr_dense_small_destroy"
 
     def __init__(self, dense: "DenseIndex"):
         self._h = C.c_void_p()
@@ -868,17 +804,6 @@ class DenseSmallApprox:
     def approx_device(self, q_ptr: int, nq: int, s_ptr: int, ld: int, eps_ptr: int = 0, stream: int = 0) -> None:
         _check(load().amdr_dense_small_approx_device(self._h, _vp(q_ptr), C.c_int32(nq), _vp(s_ptr), C.c_int64(ld), _vp(eps_ptr),
                                                      _vp(stream)), "amdr_dense_small_approx_device")
-
-    def close(self) -> None:
-        if self._h:
-            load().amdr_dense_small_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001
-            pass
 
 
 def hybrid_small_plan(dense: "DenseIndex", bm25: "BM25Index", nq: int, kd: int, kb: int, dense_row2uid: int,

@@ -11,15 +11,70 @@ and bench.py sit on top of it; the single-query API uses the same kernels.
 """
 from __future__ import annotations
 
+import os
 from dataclasses import dataclass
 from typing import Optional
-
-import os
 
 import numpy as np
 import torch
 
 from .. import _native
+
+NV = _native.FUSE_NVALS
+
+
+def packed_layout(nq: int, w: int, nvals: int = NV):
+    """Byte offsets (o1, o2, o3, total) of a packed fused record: ids i64 [nq, w] | vals f64 [nq, w, nvals] | mask i32
+    [nq, w] | count i32 [nq].  nvals = FUSE_NVALS: the full record (fuse); nvals = 1: the lean one of one score per hit
+    (compact_to_host).  The ONE place the layout is computed."""
+    o1 = nq * w * 8
+    o2 = o1 + nq * w * nvals * 8
+    o3 = o2 + nq * w * 4
+    return o1, o2, o3, o3 + nq * 4
+
+
+def packed_views(h: np.ndarray, nq: int, w: int, nvals: int = NV):
+    """(ids, vals, mask, count) as numpy views of a packed record on the host (u8 array of at least `total` bytes);
+    the lean record's vals are [nq, w]."""
+    o1, o2, o3, tot = packed_layout(nq, w, nvals)
+    return (h[:o1].view("int64").reshape(nq, w), h[o1:o2].view("float64").reshape((nq, w, nvals) if nvals > 1 else (nq, w)),
+            h[o2:o3].view("int32").reshape(nq, w), h[o3:tot].view("int32"))
+
+
+# The forms of one hybrid step (step_form):
+ONE_LAUNCH = "one_launch"            # both channels and the fusion in one launch (_hybrid_small)
+BM25_THEN_FUSED = "bm25_then_fused"  # BM25, then the dense channel and the fusion as one native call
+CHANNELS = "channels"                # the channels one after the other on the caller's stream, then the fusion
+CHANNELS_SIDE = "channels_side"      # dense / BM25 on the side stream beside MaxSim, then the fusion
+# The one-launch form is asked for up to this many queries and fused candidates per query (the serving call).
+# amdr_hybrid_small_device decides again natively (corpus size, AMDR_HYBRID_SMALL) and falls back by itself to the
+# launches of BM25_THEN_FUSED, so this test only has to be no narrower than the native one.
+SMALL_NQ, SMALL_CANDS = 4, 32
+
+
+def step_form(has_dense: bool, has_bm25: bool, has_colbert: bool, sharded: bool, nq: int, k: int, overlap: bool):
+    """(form, exchange) of a step: which channels have an index AND an operand, whether the indexes are row shards,
+    the batch, the depth and whether the side stream is allowed (AMDR_ENGINE_OVERLAP).  exchange: the per-shard lists
+    are all-gathered and merged before the fusion.  Pure: search_batch switches on it."""
+    if has_dense and has_bm25 and not has_colbert and not sharded:
+        # dense + BM25 on one GPU, the serving hybrid without ColBERT
+        return (ONE_LAUNCH if nq <= SMALL_NQ and 2 * k <= SMALL_CANDS else BM25_THEN_FUSED), False
+    # The dense and BM25 channels of a batch are a few short launches that do not fill the chip; MaxSim's first pass is
+    # ~0.8 ms on the matrix pipe.  They depend on nothing of each other until the fusion.
+    side = has_colbert and overlap and (has_dense or has_bm25)
+    return (CHANNELS_SIDE if side else CHANNELS), bool(sharded)
+
+
+def _check_emb(q_emb: torch.Tensor) -> None:
+    assert q_emb.is_cuda and q_emb.dtype == torch.float32 and q_emb.is_contiguous(), "q_emb: contiguous f32 on the device"
+
+
+def _check_tok(q_tok: torch.Tensor) -> None:
+    assert q_tok.is_cuda and q_tok.dtype == torch.float32 and q_tok.is_contiguous(), "q_tok: contiguous f32 on the device"
+
+
+def _check_csr(q_terms: torch.Tensor, q_ptr: torch.Tensor) -> None:
+    assert q_terms.dtype == torch.int32 and q_ptr.dtype == torch.int64 and q_terms.is_cuda and q_ptr.is_cuda, "BM25 CSR"
 
 
 @dataclass
@@ -44,13 +99,7 @@ class BatchResult:
         waits for the kernels; three more copies of a single query's few hundred bytes cost ~10 us each)."""
         if self.packed is None:
             return (self.ids.cpu().numpy(), self.vals.cpu().numpy(), self.mask.cpu().numpy(), self.count.cpu().numpy())
-        nq, mo = self.ids.shape
-        h = self.packed.cpu().numpy()
-        o1 = nq * mo * 8
-        o2 = o1 + nq * mo * _native.FUSE_NVALS * 8
-        o3 = o2 + nq * mo * 4
-        return (h[:o1].view("int64").reshape(nq, mo), h[o1:o2].view("float64").reshape(nq, mo, _native.FUSE_NVALS),
-                h[o2:o3].view("int32").reshape(nq, mo), h[o3:o3 + nq * 4].view("int32"))
+        return packed_views(self.packed.cpu().numpy(), *self.ids.shape)
 
 
 def _stream() -> int:
@@ -83,6 +132,7 @@ class HybridEngine:
         self.graph_params: Optional[_native.GraphParams] = None
         self.graph_limit = 0
         self._graph_key = None
+        self._side_stream: Optional[torch.cuda.Stream] = None  # made by the first CHANNELS_SIDE step
 
     def _buf(self, name, shape, dtype):
         key = (name, tuple(shape), dtype)
@@ -131,7 +181,6 @@ class HybridEngine:
         on the current stream.  Back-to-back batches may be enqueued without synchronising: the staging is a ring of two
         (pinned, device) pairs fenced by events (_staging), so the returned tensors hold this batch's CSR until two more
         upload_csr calls have been made; work that reads them must be enqueued before then on the same stream."""
-        import numpy as np
         qp8, qt8 = q_ptr.view(np.uint8), q_terms.view(np.uint8)
         n1, n2 = qp8.size, qt8.size
         host, dev, ev = self._staging("csr", n1 + n2)
@@ -178,10 +227,7 @@ class HybridEngine:
         compacted by ONE kernel (amdr_fuse_compact_device), ONE copy into pinned memory, one synchronise."""
         nq, mo = res.ids.shape
         w = max(1, min(int(w), int(mo)))
-        o1 = nq * w * 8
-        o2 = o1 + nq * w * 8
-        o3 = o2 + nq * w * 4
-        tot = o3 + nq * 4
+        o1, o2, o3, tot = packed_layout(nq, w, 1)
         pk = self._buf("cpk", (tot,), torch.uint8)
         base = pk.data_ptr()
         _native.fuse_compact_device(nq, mo, w, res.ids.data_ptr(), res.vals.data_ptr(), res.mask.data_ptr(),
@@ -190,9 +236,7 @@ class HybridEngine:
         host = self._pinned("cpkh", tot)
         host[:tot].copy_(pk, non_blocking=True)
         torch.cuda.current_stream(self.tdev).synchronize()
-        h = host.numpy()
-        return (h[:o1].view("int64").reshape(nq, w).copy(), h[o1:o2].view("float64").reshape(nq, w).copy(),
-                h[o2:o3].view("int32").reshape(nq, w).copy(), h[o3:tot].view("int32").copy())
+        return tuple(v.copy() for v in packed_views(host.numpy(), nq, w, 1))
 
     def reserve(self, nq: int, k: int, total_terms: int = 0, bytes_max: int = 0) -> None:
         """bytes_max > 0: text-in steps of up to that many bytes of query text (q_text); BM25 then takes up to bytes_max
@@ -213,7 +257,6 @@ class HybridEngine:
     def set_graph(self, graph: _native.GraphIndex, params: dict, lang: int = -1) -> None:
         """The graph channel of this engine: the GraphIndex and one call's parameters (graph_retriever.graph_call_params);
         the parameter tables go up to the device once per distinct parameter set."""
-        import numpy as np
         key = (id(graph), int(params["limit"]), int(params["default_depth"]), float(params["min_conf"]), int(lang),
                params["rel_max_depth"].tobytes(), params["rel_allowed"].tobytes(), params["rel_weight"].tobytes(),
                params["decay"].tobytes())
@@ -236,7 +279,7 @@ class HybridEngine:
         if self.graph is None or self.graph_params is None:
             raise RuntimeError("graph_topk: this engine has no graph channel (set_graph)")
         assert seeds.is_cuda and seeds.dtype == torch.int64 and seeds.is_contiguous() and seed_count.dtype == torch.int32
-        assert q_emb.is_cuda and q_emb.dtype == torch.float32 and q_emb.is_contiguous()
+        _check_emb(q_emb)
         ld = int(seeds.shape[1])
         ng = int(qsel.numel()) if qsel is not None else int(seeds.shape[0])
         if qsel is not None:
@@ -252,7 +295,7 @@ class HybridEngine:
     # -- channels (device in, device out) -----------------------------------
     def dense_topk(self, q_emb: torch.Tensor, k: int):
         nq = q_emb.shape[0]
-        assert q_emb.is_cuda and q_emb.dtype == torch.float32 and q_emb.is_contiguous()
+        _check_emb(q_emb)
         s = self._buf("ds", (nq, k), torch.float32)
         i = self._buf("di", (nq, k), torch.int64)
         self.dense.search_device(q_emb.data_ptr(), nq, k, s.data_ptr(), i.data_ptr(), _stream())
@@ -260,7 +303,7 @@ class HybridEngine:
 
     def bm25_topk(self, q_terms: torch.Tensor, q_ptr: torch.Tensor, k: int):
         nq = q_ptr.shape[0] - 1
-        assert q_terms.dtype == torch.int32 and q_ptr.dtype == torch.int64 and q_terms.is_cuda and q_ptr.is_cuda
+        _check_csr(q_terms, q_ptr)
         s = self._buf("bs", (nq, k), torch.float64)
         i = self._buf("bi", (nq, k), torch.int64)
         self.bm25.search_device(q_terms.data_ptr(), q_ptr.data_ptr(), nq, k, s.data_ptr(), i.data_ptr(), _stream())
@@ -268,7 +311,7 @@ class HybridEngine:
 
     def colbert_topk(self, q_tok: torch.Tensor, k: int):
         nq, q_len = q_tok.shape[0], q_tok.shape[1]
-        assert q_tok.is_cuda and q_tok.dtype == torch.float32 and q_tok.is_contiguous()
+        _check_tok(q_tok)
         s = self._buf("cs", (nq, k), torch.float32)
         i = self._buf("ci", (nq, k), torch.int64)
         self.maxsim.search_device(q_tok.data_ptr(), nq, q_len, k, s.data_ptr(), i.data_ptr(), _stream())
@@ -291,18 +334,16 @@ class HybridEngine:
         return BatchResult(ids=ids, vals=vals, mask=mask, count=count, packed=pk)
 
     def _fused_outputs(self, nq: int, mo: int):
-        o1 = nq * mo * 8
-        o2 = o1 + nq * mo * _native.FUSE_NVALS * 8
-        o3 = o2 + nq * mo * 4
-        pk = self._buf("fpk", (o3 + nq * 4,), torch.uint8)  # the four outputs side by side: one D2H serves the host API
-        return (pk, pk[:o1].view(torch.int64).view(nq, mo), pk[o1:o2].view(torch.float64).view(nq, mo, _native.FUSE_NVALS),
+        o1, o2, o3, tot = packed_layout(nq, mo)
+        pk = self._buf("fpk", (tot,), torch.uint8)  # the four outputs side by side: one D2H serves the host API
+        return (pk, pk[:o1].view(torch.int64).view(nq, mo), pk[o1:o2].view(torch.float64).view(nq, mo, NV),
                 pk[o2:o3].view(torch.int32).view(nq, mo), pk[o3:].view(torch.int32))
 
     def dense_topk_fuse(self, params: _native.FuseParams, q_emb: torch.Tensor, k: int, bm25):
         """Dense top-k + fusion with the finished BM25 lists as ONE native call (amdr_dense_search_fuse_device: for the
         serving corpora under a batch one kernel ranks the score rows and fuses).  Same results as dense_topk + fuse."""
         nq = q_emb.shape[0]
-        assert q_emb.is_cuda and q_emb.dtype == torch.float32 and q_emb.is_contiguous()
+        _check_emb(q_emb)
         bs, bi = bm25
         kb = int(bi.shape[1])
         s = self._buf("ds", (nq, k), torch.float32)
@@ -316,12 +357,13 @@ class HybridEngine:
         return (s, i), BatchResult(ids=ids, vals=vals, mask=mask, count=count, packed=pk)
 
     def _hybrid_small(self, params: _native.FuseParams, q_emb: torch.Tensor, q_terms: torch.Tensor, q_ptr: torch.Tensor,
-                      k: int) -> BatchResult:
-        """bm25_topk + dense_topk_fuse through amdr_hybrid_small_device (one launch on a serving corpus).  Issued once
-        per query by search(): output tensors and the call's argument block are built once per (nq, k)."""
+                      k: int):
+        """bm25_topk + dense_topk_fuse through amdr_hybrid_small_device (one launch on a serving corpus): (dense lists,
+        BM25 lists, result).  Issued once per query by search(): output tensors and the call's argument block are built
+        once per (nq, k)."""
         nq = int(q_emb.shape[0])
-        assert q_emb.is_cuda and q_emb.dtype == torch.float32 and q_emb.is_contiguous()
-        assert q_terms.dtype == torch.int32 and q_ptr.dtype == torch.int64 and q_terms.is_cuda and q_ptr.is_cuda
+        _check_emb(q_emb)
+        _check_csr(q_terms, q_ptr)
         assert q_ptr.shape[0] - 1 == nq
         ent = self._xcache.get(("hs", nq, k))
         if ent is None:
@@ -339,10 +381,7 @@ class HybridEngine:
             self._xcache[("hs", nq, k)] = ent
         plan, (ids, vals, mask, count, pk), (ds, di, bs, bi) = ent
         _native.hybrid_small_device(plan, params, q_emb.data_ptr(), q_terms.data_ptr(), q_ptr.data_ptr(), _stream())
-        res = BatchResult(ids=ids, vals=vals, mask=mask, count=count, packed=pk)
-        res.dense_scores, res.dense_ids = ds, di
-        res.bm25_scores, res.bm25_ids = bs, bi
-        return res
+        return (ds, di), (bs, bi), BatchResult(ids=ids, vals=vals, mask=mask, count=count, packed=pk)
 
     def rerank_blend(self, res: BatchResult, ce_raw: torch.Tensor, beta: float) -> BatchResult:
         nq, mo = res.ids.shape
@@ -361,71 +400,57 @@ class HybridEngine:
         """dense + bm25 (+ colbert) top-k -> fuse -> min_final filter, all on device.
         q_text = (blob u8, offs i64 [nq + 1]) device tensors: the BM25 query side as text, tokenised on the device
         (tokenize_device) in the same stream, instead of q_terms / q_ptr."""
+        flags = None
         if q_text is not None:
             if q_terms is not None or q_ptr is not None:
                 raise ValueError("search_batch: pass q_text or q_terms / q_ptr, not both")
             q_terms, q_ptr, flags = self.tokenize_device(*q_text)
-            res = self.search_batch(params, k, q_emb=q_emb, q_terms=q_terms, q_ptr=q_ptr, q_tok=q_tok)
-            res.needs_segmenter = flags
-            return res
+        # a channel runs when it has both an index and an operand
+        d_on = self.dense is not None and q_emb is not None
+        b_on = self.bm25 is not None and q_ptr is not None
+        c_on = self.maxsim is not None and q_tok is not None
+        nq = int(q_tok.shape[0] if c_on else q_ptr.shape[0] - 1 if b_on else q_emb.shape[0])
+        form, exchange = step_form(d_on, b_on, c_on, self.shard_offset is not None, nq, k,
+                                   c_on and os.environ.get("AMDR_ENGINE_OVERLAP", "1") != "0")
         d = b = c = None
-        nq = None
-        if (self.dense is not None and q_emb is not None and self.bm25 is not None and q_ptr is not None
-                and not (self.maxsim is not None and q_tok is not None) and self.shard_offset is None):
-            # dense + BM25 on one GPU, the serving hybrid without ColBERT: BM25 first, then the dense channel and the
-            # fusion in one native call
-            nq = int(q_emb.shape[0])
-            if nq <= 4 and 2 * k <= 32:
-                # the serving call (search(): one query at a time): both channels and the fusion in ONE launch
-                return self._hybrid_small(params, q_emb, q_terms, q_ptr, k)
+        if form == ONE_LAUNCH:  # the serving call (search(): one query at a time)
+            d, b, res = self._hybrid_small(params, q_emb, q_terms, q_ptr, k)
+        elif form == BM25_THEN_FUSED:
             b = self.bm25_topk(q_terms, q_ptr, k)
             d, res = self.dense_topk_fuse(params, q_emb, k, b)
-            res.dense_scores, res.dense_ids = d
-            res.bm25_scores, res.bm25_ids = b
-            return res
-        with_col = self.maxsim is not None and q_tok is not None
-        overlap = (with_col and os.environ.get("AMDR_ENGINE_OVERLAP", "1") != "0"
-                   and ((self.dense is not None and q_emb is not None) or (self.bm25 is not None and q_ptr is not None)))
-        if overlap:
-            # The dense and BM25 channels of a batch are a few short launches that do not fill the chip; MaxSim's first pass is
-            # ~0.8 ms on the matrix pipe.  They depend on nothing of each other until the fusion: the two short channels go to
-            # a side stream (forked from and joined to the caller's: inside a hipGraph capture the fork / join become edges).
-            main = torch.cuda.current_stream(self.tdev)
-            side = self.__dict__.get("_side_stream")
-            if side is None:
-                side = self.__dict__["_side_stream"] = torch.cuda.Stream(device=self.tdev)
-            side.wait_stream(main)
-            with torch.cuda.stream(side):
-                if self.dense is not None and q_emb is not None:
-                    d = self.dense_topk(q_emb, k)
-                if self.bm25 is not None and q_ptr is not None:
-                    b = self.bm25_topk(q_terms, q_ptr, k)
-            c = self.colbert_topk(q_tok, k)
-            main.wait_stream(side)
-            nq = q_tok.shape[0]
         else:
-            if self.dense is not None and q_emb is not None:
-                d = self.dense_topk(q_emb, k)
-                nq = q_emb.shape[0]
-            if self.bm25 is not None and q_ptr is not None:
-                b = self.bm25_topk(q_terms, q_ptr, k)
-                nq = q_ptr.shape[0] - 1
-            if with_col:
+            side = None
+            if form == CHANNELS_SIDE:
+                # the two short channels on a side stream, forked from and joined to the caller's: inside a hipGraph
+                # capture the fork / join become edges
+                main = torch.cuda.current_stream(self.tdev)
+                if self._side_stream is None:
+                    self._side_stream = torch.cuda.Stream(device=self.tdev)
+                side = self._side_stream
+                side.wait_stream(main)
+            with torch.cuda.stream(side):  # (None: the caller's stream)
+                if d_on:
+                    d = self.dense_topk(q_emb, k)
+                if b_on:
+                    b = self.bm25_topk(q_terms, q_ptr, k)
+            if c_on:
                 c = self.colbert_topk(q_tok, k)
-                nq = q_tok.shape[0]
-        if self.shard_offset is not None:
-            from . import sharding
-            chans = [x for x in (d, b, c) if x is not None]
-            merged = iter(sharding.exchange_topk(chans, int(self.shard_offset), group=self.shard_group, buf=self._buf,
-                                                 cache=self._xcache))
-            d, b, c = (next(merged) if x is not None else None for x in (d, b, c))
-        res = self.fuse(params, nq, d, b, c)
+            if side is not None:
+                main.wait_stream(side)
+            if exchange:
+                from . import sharding
+                chans = [x for x in (d, b, c) if x is not None]
+                merged = iter(sharding.exchange_topk(chans, int(self.shard_offset), group=self.shard_group, buf=self._buf,
+                                                     cache=self._xcache))
+                d, b, c = (next(merged) if x is not None else None for x in (d, b, c))
+            res = self.fuse(params, nq, d, b, c)
         if d is not None:
             res.dense_scores, res.dense_ids = d
         if b is not None:
             res.bm25_scores, res.bm25_ids = b
         if c is not None:
             res.colbert_scores, res.colbert_ids = c
+        res.needs_segmenter = flags
         return res
 
     # -- hipGraph form -----------------------------------------------------------

@@ -123,6 +123,30 @@ def _is_graph_mode(mode: Any) -> bool:
     return bool(mode) and (str(mode).upper().endswith("GRAPH_AUGMENTED") or str(mode) == "RoutingMode.GRAPH_AUGMENTED")
 
 
+class _NativeStage:
+    """State of a retriever's device-resident stage: the compatibility key of the loaded indexes and its verdict
+    (_native_channels), the engines by "with ColBERT" (rebuilt when the key changes) and the lock of one batch at a time."""
+
+    def __init__(self) -> None:
+        self.key, self.ok, self.engines, self.lock = None, False, {}, threading.Lock()
+
+
+@dataclass
+class _Prepared:
+    """One batch ready for the device (HybridRetriever._prepare)."""
+    native: Any    # (dense store, BM25 retriever, ColBERT retriever | None: channel off or its query encoder failed)
+    q_emb: Any     # f32 [n, d] query embeddings on the device
+    csr: Any       # the BM25 side as (q_terms i32, q_ptr i64) numpy arrays, or None when `text` is set
+    text: Any      # ... or the UTF-8 views of a text batch (BM25Retriever.device_text_batch)
+    exact: Any     # bool [n]: tokenised exactly (zh_exact)
+    q_tok: Any     # the ColBERT query tokens (device tensor or numpy batch), or None
+    stamps: Any    # (t_after_dense_prep, t_after_bm25_prep, t_after_colbert_prep) for search()'s log line
+
+
+def _fetch_full(eng, res):  # ONE synchronise and ONE device-to-host copy (the four outputs share an allocation)
+    return res.to_host()
+
+
 @dataclass
 class HybridRetriever:
     cfg: Any
@@ -240,8 +264,12 @@ class HybridRetriever:
 
     # -------------------------------------------------------------- fusion
     def _fuse(self, *, dense_hits: List[RetrievalHit], bm25_hits: List[RetrievalHit],
-              colbert_hits: List[RetrievalHit], _min_final: float = -math.inf,
-              _return_native: bool = False):
+              colbert_hits: List[RetrievalHit]) -> List[RetrievalHit]:
+        return self._fuse_kept(dense_hits, bm25_hits, colbert_hits, -math.inf)[0]
+
+    def _fuse_kept(self, dense_hits: List[RetrievalHit], bm25_hits: List[RetrievalHit],
+                   colbert_hits: List[RetrievalHit], min_final: float):
+        """(every fused hit, how many of them score >= min_final: the list is sorted, so they are a prefix)."""
         kn = self._knobs()
         lists = {"dense": dense_hits, "bm25": bm25_hits, "colbert": colbert_hits}
         for name, hs in lists.items():
@@ -258,7 +286,7 @@ class HybridRetriever:
                 uid_of[h.chunk.id] = len(chunk_of)
                 chunk_of.append(h.chunk)
         if not chunk_of:
-            return ([], None) if _return_native else []
+            return [], 0
 
         def arr(hs: List[RetrievalHit]):
             # a repeated id inside one channel keeps its first (best-ranked) entry
@@ -275,15 +303,13 @@ class HybridRetriever:
                 return None
             return np.asarray([ids], dtype=np.int64), np.asarray([sc], dtype=np.float64)
 
-        ids, vals, mask, count = _native.fuse(self._params(kn, _min_final), 1, arr(dense_hits), arr(bm25_hits),
+        ids, vals, mask, count = _native.fuse(self._params(kn, min_final), 1, arr(dense_hits), arr(bm25_hits),
                                               arr(colbert_hits))
         hits = self._hits_from_native(ids[0], vals[0], mask[0], ids.shape[1], kn, chunk_of)
         if any((h.score_breakdown or {}).get("zh_exact") is False for h in bm25_hits):
             for h in hits:  # the stand-in tokenizer's mark survives fusion (text.py)
                 h.score_breakdown["zh_exact"] = False
-        if _return_native:
-            return hits, (ids, vals, mask, count)
-        return hits
+        return hits, int(count[0])
 
     @staticmethod
     def _hits_from_native(ids, vals, mask, n, kn, chunk_of) -> List[RetrievalHit]:
@@ -347,9 +373,8 @@ class HybridRetriever:
             # stream, ONE synchronise, one set of copies back (the kernels and results are those of the
             # per-channel path below; tests pin the two against each other)
             t0 = time.time()
-            outs, stamps = self._batch_native([question], eff_top_k, native, min_final)
+            outs, (t1, t2, t3), _ = self._hit_lists([question], eff_top_k, native, min_final)
             fused = outs[0]
-            t1, t2, t3 = stamps
             t4 = time.time()
         else:
             t0 = time.time()
@@ -360,10 +385,8 @@ class HybridRetriever:
             colbert_hits = self.search_colbert(question, eff_top_k)
             t3 = time.time()
 
-            all_fused, nat = self._fuse(dense_hits=dense_hits, bm25_hits=bm25_hits, colbert_hits=colbert_hits,
-                                        _min_final=min_final, _return_native=True)
-            kept = int(nat[3][0]) if nat is not None else 0
-            fused = all_fused[:kept]  # hits with score >= min_final_score (sorted, so a prefix)
+            all_fused, kept = self._fuse_kept(dense_hits, bm25_hits, colbert_hits, min_final)
+            fused = all_fused[:kept]  # hits with score >= min_final_score
             t4 = time.time()
 
         t_graph = None
@@ -501,6 +524,16 @@ class HybridRetriever:
         return outs
 
     # ------------------------------------------------- device-resident stage
+    def _stage(self) -> "_NativeStage":
+        """The ONE home of the native stage's state, made on first use (retrievers built with __new__ have no
+        __post_init__; setdefault: two threads' first calls agree on one object)."""
+        return self.__dict__.get("_native_stage") or self.__dict__.setdefault("_native_stage", _NativeStage())
+
+    def native_engine(self, with_colbert: bool = False):
+        """The HybridEngine of the device-resident stage with / without the ColBERT channel; None until a search has
+        built it (and again after the indexes were reloaded)."""
+        return self._stage().engines.get(bool(with_colbert))
+
     def _native_channels(self, eff: int):
         """(dense store, bm25 retriever, colbert retriever | None) when every channel is this
         package's own retriever over the SAME chunk list, so that one row number means one chunk in
@@ -525,19 +558,15 @@ class HybridRetriever:
         store = self.dense.store
         key = (id(store.index), id(self.bm25.bm25), id(col._searcher) if col is not None else None,
                id(col._pid2chunk) if col is not None else None)
-        cached = self.__dict__.get("_native_key")
-        if cached != key:
+        st = self._stage()
+        if st.key != key:
             a, b = store.chunks, self.bm25.chunks
             same = len(a) == len(b) and all(x.id == y.id for x, y in zip(a, b))
             if same and col is not None:
                 same = len(col._pid2chunk) == len(a) and all(
                     (col._pid2chunk.get(i) is not None and col._pid2chunk[i].id == c.id) for i, c in enumerate(a))
-            self.__dict__["_native_key"] = key
-            self.__dict__["_native_ok"] = bool(same) and getattr(store.index, "native", None) is not None
-            self.__dict__["_native_engine"] = None
-        if not self.__dict__.get("_native_ok"):
-            return None
-        return store, self.bm25, col
+            st.key, st.ok, st.engines = key, bool(same) and getattr(store.index, "native", None) is not None, {}
+        return (store, self.bm25, col) if st.ok else None
 
     @staticmethod
     def _make_engine(store, bm, col, dev: int):
@@ -556,40 +585,22 @@ class HybridRetriever:
         return HybridEngine(store.index.native, bm.gpu_index(), col._searcher if col is not None else None,
                             device=dev, shard_offset=offset, shard_group=shard.group if shard is not None else None)
 
-    def _batch_native(self, questions: Sequence[str], eff: int, native, min_final: float, arrays: bool = False,
-                      q_emb=None, compact_w: int = 0, device_tok: bool = False, graph_stage: Optional[Dict[str, Any]] = None):
-        """Embed / tokenise on the host, then dense + BM25 (+ MaxSim) top-k -> fuse -> min_final
-        count for the whole batch on torch's current stream, one synchronise, results built once.
-        device_tok (cfg.retrieval.query_tokenizer = "device"): a batch the device rule decides
-        (BM25Retriever.device_text_batch) goes up as UTF-8 text and is tokenised on the GPU in the same stream
-        (HybridEngine.tokenize_device); any other batch takes the host tokeniser as before.
-        graph_stage: {"fn": callable(engine, BatchResult)} run on the device result inside the batch lock (the graph
-        channel of graph_channel = "device"); what it returns goes to graph_stage["out"].
-        Returns ([fused hits with score >= min_final per question], (t_after_dense_prep, t_after_bm25_prep,
-        t_after_colbert_prep))."""
-        import torch
-        from .engine import HybridEngine
+    def _engine(self, store, bm, col):
+        """The stage's engine with / without ColBERT, built on first use (caller holds the stage lock)."""
+        engines = self._stage().engines
+        eng = engines.get(col is not None)
+        if eng is None:
+            eng = engines[col is not None] = self._make_engine(store, bm, col, int(getattr(self.cfg.retrieval, "device", 0)))
+        return eng
 
+    def _prepare(self, questions: Sequence[str], native, q_emb=None, device_tok: bool = False) -> "_Prepared":
+        """Step 1, outside the lock: embed / tokenise / encode the batch on the host side.
+        device_tok (cfg.retrieval.query_tokenizer = "device"): a batch the device rule decides
+        (BM25Retriever.device_text_batch) goes up as UTF-8 text and is tokenised on the GPU (_run); any other batch
+        takes the host tokeniser."""
+        import torch
         store, bm, col = native
-        if col is not None and any(not (q or "").strip() for q in questions):
-            # an empty question switches the ColBERT channel off for that question (colbert_retriever.py:147-149)
-            blank = [i for i, q in enumerate(questions) if not (q or "").strip()]
-            rest = [i for i in range(len(questions)) if i not in set(blank)]
-            out = [None] * len(questions)
-            stamps = (time.time(),) * 3
-            if arrays:
-                raise ValueError("search_batch_arrays: empty questions are not supported in the columnar form")
-            if graph_stage is not None:
-                raise ValueError("graph_channel='device': empty questions are not supported with the ColBERT channel on")
-            for idxs, nat in ((blank, (store, bm, None)), (rest, native)):
-                if idxs:
-                    part, stamps = self._batch_native([questions[i] for i in idxs], eff, nat, min_final,
-                                                      q_emb=None if q_emb is None else q_emb[idxs], device_tok=device_tok)
-                    for i, h in zip(idxs, part):
-                        out[i] = h
-            return out, stamps
-        dev = int(getattr(self.cfg.retrieval, "device", 0))
-        tdev = torch.device("cuda", dev)
+        tdev = torch.device("cuda", int(getattr(self.cfg.retrieval, "device", 0)))
         if q_emb is None:
             q_emb = store.embed_device(list(questions), is_query=True)  # encoder output stays in HBM
         else:  # the caller's own encoder output (numpy or a device tensor), one row per question
@@ -598,15 +609,16 @@ class HybridRetriever:
             if q_emb.shape != (len(questions), store.index.d):
                 raise ValueError(f"q_emb must be [{len(questions)}, {store.index.d}], got {tuple(q_emb.shape)}")
         t1 = time.time()
-        txt = bm.device_text_batch(questions) if device_tok else None
+        csr, txt = None, bm.device_text_batch(questions) if device_tok else None
         if txt is None:
             qt, qp, exact = bm.term_ids_batch(questions)  # native batched tokeniser + vocabulary lookup
             if qt.size == 0:
                 qt = np.zeros(1, dtype=np.int32)  # pack_queries' convention for "no term at all"
+            csr = (qt, qp)
         else:
             exact = np.ones(len(questions), dtype=bool)  # text without Han characters: tokenised exactly
         t2 = time.time()
-        q_tok_h = None
+        q_tok = None
         if col is not None:
             try:
                 # the ColBERT query side of the whole batch in ONE encoder call: a device tensor when the encoder can hand
@@ -614,71 +626,122 @@ class HybridRetriever:
                 stripped = [(q or "").strip() for q in questions]
                 enc = col._encoder
                 if hasattr(enc, "encode_queries_tensor"):
-                    q_tok_h = enc.encode_queries_tensor(stripped)
+                    q_tok = enc.encode_queries_tensor(stripped)
                 elif hasattr(enc, "encode_queries"):
-                    q_tok_h = np.ascontiguousarray(enc.encode_queries(stripped), dtype=np.float32)
+                    q_tok = np.ascontiguousarray(enc.encode_queries(stripped), dtype=np.float32)
                 else:
-                    q_tok_h = np.stack([np.asarray(enc.encode_query(q), dtype=np.float32) for q in stripped])
+                    q_tok = np.stack([np.asarray(enc.encode_query(q), dtype=np.float32) for q in stripped])
             except Exception:  # noqa: BLE001 - the reference swallows ColBERT channel errors (:244-245)
                 if getattr(store.index, "spec", None) is not None:
                     # row-sharded: dropping the channel is a rank-LOCAL decision inside an SPMD exchange — the other ranks
                     # would all-gather three packed channels against this rank's two (hang, or garbage).  Fail loudly.
                     raise
-                col, q_tok_h = None, None
-        t3 = time.time()
-        kn = self._knobs()
-        lock = self.__dict__.setdefault("_native_lock", threading.Lock())
-        with lock:  # one batch at a time through the handles' "_device" workspace (include/amdretrieval.h)
-            engines = self.__dict__.get("_native_engine") or {}
-            eng = engines.get(col is not None)
-            if eng is None:
-                eng = self._make_engine(store, bm, col, dev)
-                engines[col is not None] = eng
-                self.__dict__["_native_engine"] = engines
-            if txt is None:
+                col, q_tok = None, None
+        return _Prepared((store, bm, col), q_emb, csr, txt, np.asarray(exact, dtype=bool), q_tok, (t1, t2, time.time()))
+
+    def _run(self, prep: "_Prepared", params: "_native.FuseParams", eff: int, fetch, after=None):
+        """Step 2, under the stage lock (one batch at a time through the handles' "_device" workspace,
+        include/amdretrieval.h): engine, upload, eng.search_batch on torch's current stream, the ColBERT fallback,
+        `after(engine, result)` (the device graph stage), then `fetch(engine, result)` — the ONE synchronise and
+        device-to-host copy of the form the caller decodes.  Returns (what fetch returned, what after returned)."""
+        import torch
+        (store, bm, col), tdev = prep.native, prep.q_emb.device
+        with self._stage().lock:
+            eng = self._engine(store, bm, col)
+            if prep.text is None:
                 # BM25 query CSR in ONE host-to-device copy through pinned staging: q_ptr (i64) then q_terms (i32)
-                q_ptr_d, q_terms_d = eng.upload_csr(np.ascontiguousarray(qp, dtype=np.int64),
-                                                    np.ascontiguousarray(qt, dtype=np.int32))
+                q_ptr_d, q_terms_d = eng.upload_csr(np.ascontiguousarray(prep.csr[1], dtype=np.int64),
+                                                    np.ascontiguousarray(prep.csr[0], dtype=np.int32))
             else:
                 # the query texts in ONE host-to-device copy (packed into pinned staging), the CSR made on the device
-                eng.tokenizer = bm.device_tokenizer()
-                blob_d, offs_d = eng.upload_text(txt[0], txt[1], txt[2])
+                if eng.tokenizer is None:  # (a reloaded BM25 index changes the compatibility key: new engines)
+                    eng.tokenizer = bm.device_tokenizer()
+                blob_d, offs_d = eng.upload_text(*prep.text[:3])
                 q_terms_d, q_ptr_d, _ = eng.tokenize_device(blob_d, offs_d)
-                del txt
+            q_tok = prep.q_tok
+            if q_tok is not None:
+                q_tok = (q_tok.to(tdev, dtype=torch.float32).contiguous() if torch.is_tensor(q_tok)
+                         else torch.from_numpy(q_tok).to(tdev, non_blocking=True))
             try:
-                res = eng.search_batch(self._params(kn, min_final), eff, q_emb=q_emb, q_terms=q_terms_d, q_ptr=q_ptr_d,
-                                       q_tok=None if q_tok_h is None else
-                                       (q_tok_h.to(tdev, dtype=torch.float32).contiguous() if torch.is_tensor(q_tok_h)
-                                        else torch.from_numpy(q_tok_h).to(tdev, non_blocking=True)))
+                res = eng.search_batch(params, eff, q_emb=prep.q_emb, q_terms=q_terms_d, q_ptr=q_ptr_d, q_tok=q_tok)
             except _native.NativeError:
                 if col is None or eng.shard_offset is not None:
-                    raise  # (row-sharded: a rank must not leave the common exchange on its own, see above)
+                    raise  # (row-sharded: a rank must not leave the common exchange on its own, see _prepare)
                 # a failing ColBERT stage (e.g. out of memory) empties that channel, it does not fail the query
                 # (hybrid_retriever.py:244-245, colbert_retriever.py:171-181); a dense / BM25 failure raises again here
-                eng = engines.get(False)
-                if eng is None:
-                    eng = engines[False] = self._make_engine(store, bm, None, dev)
-                res = eng.search_batch(self._params(kn, min_final), eff, q_emb=q_emb, q_terms=q_terms_d, q_ptr=q_ptr_d)
-            if graph_stage is not None:
-                graph_stage["out"] = graph_stage["fn"](eng, res)
-            if arrays and compact_w:
-                # the lean columnar form: rows / scores / masks of the first compact_w hits, compacted on the device
-                rows, scores, cmask, cnt = eng.compact_to_host(res, compact_w)
-                return (rows, scores, cmask, cnt, np.asarray(exact, dtype=bool)), (t1, t2, t3)
-            # ONE synchronise and ONE device-to-host copy (the four outputs share an allocation)
-            ids, vals, mask, cnt = res.to_host()
-        if arrays:
-            return (ids, vals, mask, cnt, np.asarray(exact, dtype=bool)), (t1, t2, t3)
-        chunks = store.chunks
+                eng = self._engine(store, bm, None)
+                res = eng.search_batch(params, eff, q_emb=prep.q_emb, q_terms=q_terms_d, q_ptr=q_ptr_d)
+            extra = after(eng, res) if after is not None else None
+            return fetch(eng, res), extra
+
+    # Step 3, the decoders: host arrays of ONE fetch -> the caller's form.
+    def _decode_hits(self, host, exact, kn, chunks) -> List[List[RetrievalHit]]:
+        ids, vals, mask, cnt = host
         out = []
-        for qi in range(len(questions)):
+        for qi in range(len(cnt)):
             # only the hits that survive min_final_score are ever used (hybrid_retriever.py:309-310)
             hits = self._hits_from_native(ids[qi], vals[qi], mask[qi], int(cnt[qi]), kn, chunks)
             if not exact[qi]:
                 for h in hits:
                     h.score_breakdown["zh_exact"] = False
             out.append(hits)
-        return out, (t1, t2, t3)
+        return out
+
+    @staticmethod
+    def _decode_columns(host, exact, top_k: int, chunks) -> Dict[str, Any]:
+        """The full columnar dict from BatchResult.to_host(): the first top_k columns and every fused value."""
+        ids, vals, mask, cnt = host
+        w = min(top_k, ids.shape[1])
+        keep = np.arange(w)[None, :] < np.minimum(cnt, w)[:, None]
+        return {"rows": np.where(keep, ids[:, :w], -1), "scores": np.where(keep, vals[:, :w, _native.FV["score"]], 0.0),
+                "count": np.minimum(cnt, w).astype(np.int32), "channel_mask": np.where(keep, mask[:, :w], 0),
+                "values": vals[:, :w], "value_names": dict(_native.FV), "zh_exact": exact, "chunks": chunks}
+
+    @staticmethod
+    def _decode_lean(host, exact, chunks) -> Dict[str, Any]:
+        """The lean columnar dict from HybridEngine.compact_to_host(result, top_k): rows / scores / count / channel_mask
+        only, cut to top_k on the device — 20 bytes per hit over PCIe instead of the full fused record (9 doubles for
+        every candidate of every channel: 1.6 KB per query)."""
+        rows, scores, cmask, cnt = host
+        return {"rows": rows, "scores": scores, "count": cnt, "channel_mask": cmask, "zh_exact": exact, "chunks": chunks}
+
+    def _hit_lists(self, questions: Sequence[str], eff: int, native, min_final: float, q_emb=None,
+                   device_tok: bool = False, after=None):
+        """prepare -> run -> hit lists: ([fused hits with score >= min_final per question], (t_after_dense_prep,
+        t_after_bm25_prep, t_after_colbert_prep), what `after` returned).  An empty question switches the ColBERT
+        channel off for that question (colbert_retriever.py:147-149): the blank questions go as one batch without the
+        channel, the rest as another."""
+        store, bm, col = native
+        kn = self._knobs()
+        params = self._params(kn, min_final)
+
+        def batch(qs, nat, emb, after):
+            prep = self._prepare(qs, nat, emb, device_tok)
+            host, extra = self._run(prep, params, eff, _fetch_full, after)
+            return self._decode_hits(host, prep.exact, kn, store.chunks), prep.stamps, extra
+        blank = [i for i, q in enumerate(questions) if not (q or "").strip()] if col is not None else []
+        if not blank:
+            return batch(questions, native, q_emb, after)
+        if after is not None:
+            raise ValueError("graph_channel='device': empty questions are not supported with the ColBERT channel on")
+        rest = [i for i in range(len(questions)) if i not in set(blank)]
+        out, stamps = [None] * len(questions), (time.time(),) * 3
+        for idxs, nat in ((blank, (store, bm, None)), (rest, native)):
+            if idxs:
+                part, stamps, _ = batch([questions[i] for i in idxs], nat, None if q_emb is None else q_emb[idxs], None)
+                for i, h in zip(idxs, part):
+                    out[i] = h
+        return out, stamps, None
+
+    def _graph_selection(self, decisions, n: int, top_k: int, who: str):
+        """(sel, seed_n): the questions whose decision asks for the graph channel (none unless cfg.retrieval.enable_graph)
+        and how many fused hits seed the walk."""
+        if decisions is not None and len(decisions) != n:
+            raise ValueError(f"{who}: decisions must have one entry per question")
+        rcfg = self.cfg.retrieval
+        on = decisions is not None and getattr(rcfg, "enable_graph", False)
+        sel = [i for i, dec in enumerate(decisions) if _is_graph_mode(getattr(dec, "mode", None))] if on else []
+        return sel, int(getattr(rcfg, "graph_seed_k", max(10, top_k * 3)))
 
     # ----------------------------------------------------------- batch form
     def search_batch(self, questions: Sequence[str], top_k: int = 10, llm: Any = None,
@@ -690,44 +753,41 @@ class HybridRetriever:
         rcfg = self.cfg.retrieval
         top_k = max(1, int(top_k))
         questions = list(questions)
-        if decisions is not None and len(decisions) != len(questions):
-            raise ValueError("search_batch: decisions must have one entry per question")
+        sel, seed_n = self._graph_selection(decisions, len(questions), top_k, "search_batch")
         eff = self._eff_depth(top_k, "search_batch")
         native = self._native_channels(eff)
         if native is None:
             raise RuntimeError("search_batch requires this package's own dense / BM25 (/ ColBERT) retrievers built "
                                "over the same chunk list")
-        graph_on = getattr(rcfg, "enable_graph", False) and decisions is not None
-        seed_n = int(getattr(rcfg, "graph_seed_k", max(10, top_k * 3)))
-        sel = [i for i, dec in enumerate(decisions) if _is_graph_mode(getattr(dec, "mode", None))] if graph_on else []
-        stage = None
+        # The graph walks at the per-channel depth `eff`.  With the device channel off or no graph loaded the stage
+        # falls back to the host search_graph per query (which, without a graph, still cuts the list to the seeds).
+        after = gp = None
         if sel and self.graph is not None and graph_channel_mode(self.cfg) == "device":
-            stage = self._graph_device_stage(questions, sel, eff, seed_n, native)
-        outs, _ = self._batch_native(questions, eff, native, float(getattr(rcfg, "min_final_score", 0.0)), q_emb=q_emb,
-                                     device_tok=query_tokenizer_mode(self.cfg) == "device", graph_stage=stage)
-        if stage is not None:
-            # one device call served every graph-mode query; the same relabelling as search_graph
-            gout, gp = stage["out"], stage["params"]
-            for j, i in enumerate(sel):
+            after, gp = self._graph_device_stage(questions, sel, eff, seed_n, native)
+        outs, _, gout = self._hit_lists(questions, eff, native, float(getattr(rcfg, "min_final_score", 0.0)), q_emb,
+                                        query_tokenizer_mode(self.cfg) == "device", after)
+        for j, i in enumerate(sel):
+            seeds = outs[i][:seed_n]
+            if after is not None:
+                # one device call served every graph-mode query; the same relabelling as search_graph
                 hits = self.graph.hits_from_device(gout, j, gp)
                 for h in hits:
                     h.source = "retriever"
                     h.score_breakdown["channel"] = ["graph"]
-                outs[i] = outs[i][:seed_n] + hits
-        else:
-            for i in sel:
-                seeds = outs[i][:seed_n]
-                outs[i] = seeds + self.search_graph(questions[i], eff, decision=decisions[i], seeds=seeds)
+            else:
+                hits = self.search_graph(questions[i], eff, decision=decisions[i], seeds=seeds)
+            outs[i] = seeds + hits
         if getattr(rcfg, "enable_rerank", False):
             outs = self._rerank_stage(questions, outs, llm, top_k)
         return [_dedup_keep_best(hits)[:top_k] for hits in outs]
 
     def _graph_device_stage(self, questions: Sequence[str], sel: Sequence[int], k: int, seed_n: int, native,
-                            lang: Optional[str] = None) -> Dict[str, Any]:
+                            lang: Optional[str] = None):
         """The graph channel of a batch on the device (graph_channel = "device"): the graph-mode questions embedded once
         (non-query form, as GraphRetriever's store._embed(question)), then ONE amdr_graph_search_device call over the
-        fused lists of the batch, seeds = the first graph_seed_k fused hits.  Row-sharded indexes and parameters outside
-        the kernel's limits raise ValueError (no silent host path)."""
+        fused lists of the batch, seeds = the first graph_seed_k fused hits.  Returns (after, params): `after(engine,
+        BatchResult)` is the stage for _run (its outputs as host arrays), params what hits_from_device takes.
+        Row-sharded indexes and parameters outside the kernel's limits raise ValueError (no silent host path)."""
         import torch
         store = native[0]
         if getattr(store.index, "spec", None) is not None:
@@ -740,7 +800,7 @@ class HybridRetriever:
         sel = list(sel)
         emb = store.embed_device([questions[i] for i in sel], is_query=False)
 
-        def fn(eng, res):
+        def after(eng, res):
             eng.set_graph(g, params, lang_id)
             nq = int(res.ids.shape[0])
             q_full = eng._buf("gq", (nq, int(emb.shape[1])), torch.float32)
@@ -749,7 +809,7 @@ class HybridRetriever:
             eng.graph.reserve(len(sel), k, eng.graph_limit)
             outs = eng.graph_topk(res.ids, res.count, q_full, k, seed_n, qsel=qsel)
             return {n: v.cpu().numpy() for n, v in outs.items()}
-        return {"fn": fn, "params": params}
+        return after, params
 
     def search_batch_arrays(self, questions: Sequence[str], top_k: int = 10, q_emb=None, values: bool = True,
                             decisions: Optional[Sequence[Any]] = None) -> Dict[str, Any]:
@@ -758,6 +818,7 @@ class HybridRetriever:
         offline scoring).  rows[q, j] indexes `self.dense.store.chunks`; entries j >= count[q] are -1 / 0.
         `q_emb` ([n, d] numpy array or device tensor): query embeddings the caller's encoder already produced
         (a deployment batches its BERT forward itself); default: this store's encoder.
+        `values=False`: rows / scores / count / channel_mask only (_decode_lean) instead of the full record.
         The rows of one index are distinct chunks, so the dedup step of search() has nothing to merge.
         `decisions` (one per question): the graph channel runs on the device for the GRAPH_AUGMENTED ones (when
         cfg.retrieval.enable_graph and a graph is loaded) and the result gains graph_rows / graph_scores (final) /
@@ -769,15 +830,23 @@ class HybridRetriever:
         native = self._native_channels(eff)
         if native is None:
             raise RuntimeError("search_batch_arrays requires this package's own retrievers built over the same chunk list")
-        if decisions is not None and len(decisions) != len(questions):
-            raise ValueError("search_batch_arrays: decisions must have one entry per question")
+        questions = list(questions)
+        sel, seed_n = self._graph_selection(decisions, len(questions), top_k, "search_batch_arrays")
+        # The graph walks at depth `top_k`, always on the device; with no graph loaded `decisions` are ignored.
         graph_on = decisions is not None and getattr(rcfg, "enable_graph", False) and self.graph is not None
-        sel = [i for i, dec in enumerate(decisions) if _is_graph_mode(getattr(dec, "mode", None))] if graph_on else []
-        stage = (self._graph_device_stage(list(questions), sel, top_k,
-                                          int(getattr(rcfg, "graph_seed_k", max(10, top_k * 3))), native) if sel else None)
-        out = self._search_batch_arrays(questions, top_k, eff, native, q_emb, values, stage)
+        after = self._graph_device_stage(questions, sel, top_k, seed_n, native)[0] if graph_on and sel else None
+        if native[2] is not None and any(not (q or "").strip() for q in questions):
+            raise ValueError("search_batch_arrays: empty questions are not supported in the columnar form")
+        prep = self._prepare(questions, native, q_emb, query_tokenizer_mode(self.cfg) == "device")
+        params = self._params(self._knobs(), float(getattr(rcfg, "min_final_score", 0.0)))
+        if values:
+            host, g = self._run(prep, params, eff, _fetch_full, after)
+            out = self._decode_columns(host, prep.exact, top_k, native[0].chunks)
+        else:
+            host, g = self._run(prep, params, eff, lambda eng, res: eng.compact_to_host(res, top_k), after)
+            out = self._decode_lean(host, prep.exact, native[0].chunks)
         if graph_on:
-            n, g = len(questions), (stage or {}).get("out")
+            n = len(questions)
             for col, name, dt, fill in (("rows", "rows", np.int64, -1), ("scores", "final", np.float64, 0.0),
                                         ("semantic", "semantic", np.float32, 0.0), ("depth", "depth", np.int32, 0),
                                         ("relation", "relation", np.int32, -1), ("edge_conf", "edge_conf", np.float64, 0.0)):
@@ -790,25 +859,3 @@ class HybridRetriever:
                 out["graph_count"][sel] = g["count"]
             out["graph_relation_names"] = list(self.graph.device_graph()[1].rel_names)
         return out
-
-    def _search_batch_arrays(self, questions, top_k: int, eff: int, native, q_emb, values: bool, stage):
-        rcfg = self.cfg.retrieval
-        if not values:
-            # `values=False`: rows / scores / count / channel_mask only, cut to top_k on the device — 20 bytes per hit over
-            # PCIe instead of the full fused record (9 doubles for every candidate of every channel: 1.6 KB per query)
-            (rows, scores, cmask, cnt, exact), _ = self._batch_native(
-                list(questions), eff, native, float(getattr(rcfg, "min_final_score", 0.0)), arrays=True, q_emb=q_emb,
-                compact_w=top_k, device_tok=query_tokenizer_mode(self.cfg) == "device", graph_stage=stage)
-            return {"rows": rows, "scores": scores, "count": cnt, "channel_mask": cmask, "zh_exact": exact,
-                    "chunks": native[0].chunks}
-        (ids, vals, mask, cnt, exact), _ = self._batch_native(list(questions), eff, native,
-                                                                float(getattr(rcfg, "min_final_score", 0.0)), arrays=True,
-                                                                q_emb=q_emb,
-                                                                device_tok=query_tokenizer_mode(self.cfg) == "device",
-                                                                graph_stage=stage)
-        w = min(top_k, ids.shape[1])
-        keep = np.arange(w)[None, :] < np.minimum(cnt, w)[:, None]
-        return {"rows": np.where(keep, ids[:, :w], -1), "scores": np.where(keep, vals[:, :w, _native.FV["score"]], 0.0),
-                "count": np.minimum(cnt, w).astype(np.int32), "channel_mask": np.where(keep, mask[:, :w], 0),
-                "values": vals[:, :w], "value_names": dict(_native.FV), "zh_exact": exact,
-                "chunks": native[0].chunks}

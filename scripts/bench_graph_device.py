@@ -84,7 +84,7 @@ def main() -> None:
     arrays_s = (time.perf_counter() - t0) / args.reps
 
     # the device graph stage alone, on the engine's last fused result
-    eng = hr.__dict__["_native_engine"][False]
+    eng = hr.native_engine(with_colbert=False)
     store = hr.dense.store
     q_graph = store.embed_device(qs, is_query=False)
     q_emb = store.embed_device(qs, is_query=True)

@@ -74,7 +74,7 @@ def test_side_stream_channels_equal_the_one_stream_batch_eager_and_captured(monk
         for q in range(one[0].shape[0]):
             c = int(one[2][q])
             assert (one[0][q, :c] == two[0][q, :c]).all() and (one[1][q, :c].view("uint64") == two[1][q, :c].view("uint64")).all(), q  # (vals: f64 [.., 9])
-    assert R.eng.__dict__.get("_side_stream") is not None
+    assert R.eng._side_stream is not None
     # captured: the fork / join become edges of the graph; replay after the inputs changed and were restored
     cap = torch.cuda.Stream()
     cap.wait_stream(torch.cuda.current_stream())

@@ -250,7 +250,7 @@ def test_captured_step_with_graph_stage_replays_like_eager(tmp_path):
     qs = [q for q, _, _ in synthetic_queries(chunks, seed=0)][:48]
     decisions = [types.SimpleNamespace(mode="GRAPH_AUGMENTED")] * len(qs)
     hr.search_batch(qs, top_k=10, decisions=decisions)  # builds the engine and its graph channel
-    eng = hr.__dict__["_native_engine"][False]
+    eng = hr.native_engine(with_colbert=False)
     assert eng.graph is not None
     store, bm = hr.dense.store, hr.bm25
     dev = torch.device("cuda", 0)
