@@ -87,17 +87,11 @@ struct DenseMfmaPlan {
 bool dense_mfma_supported(int d);
 // grid = false: the top-k half and the sizes only (the search for the scores grid costs ~10 us on a large matrix)
 void dense_mfma_plan(long n, int d, int nq, int k, DenseMfmaPlan* p, bool grid = true);
-// mode 0: every row's score; 1: per-tile maxima; 2: re-scoring of the tiles in tile_list (dense_mfma.hip)
+// tile_max false: S[query][row], every row's score; true: S[query][tile], the maximum over each 32-row tile
 // `gate` (nullable device int): the launch does nothing unless *gate != 0 — the exact first pass behind the fp16 one
 // (dense_hi.hip) is enqueued unconditionally and decides on the device whether it runs
 int dense_mfma_launch_scores(const DenseMfmaPlan& p, const float* X, long n, int d, const float* Q, int nq, float* S,
-                             hipStream_t st, int mode = 0, const int* tile_list = nullptr,
-                             const int* tile_count = nullptr, long n_real = 0, const int* gate = nullptr);
-// two-level top-k helpers: sorted unique list of the candidate tiles (a bitmap in LDS up to kUniqueBitmapTilesMax tiles,
-// any number of candidates; beyond, a one-wave sort of <= 8 192 candidates); column -> row id of the final hits
-constexpr int kUniqueBitmapTilesMax = 1 << 20;
-int dense_tiles_unique_launch(const int64_t* tile_ids, int n_in, long n_tiles, int* list, int* count, hipStream_t st);
-int dense_tiles_remap_launch(int64_t* ids, int total, const int* list, const int* count, long n_real, hipStream_t st);
+                             hipStream_t st, bool tile_max = false, const int* gate = nullptr);
 int dense_mfma_launch_topk(const DenseMfmaPlan& p, const float* S, long n, int nq, int k, void* part,
                            float* fin_scores, int64_t* fin_ids, hipStream_t st);
 
@@ -118,8 +112,11 @@ int dense_hi2_launch_emit(const float* X, long n, int d, const float* Q, int nq,
 int dense_hi2_launch_select(const void* qlist, const unsigned int* qcount, size_t qcap, int m, int kc, int k, const float* Q,
                             int d, float row_norm_max, float x_scale, long n_tiles, int* list, int* count, int* unres,
                             int* flag, unsigned int* unresolved, hipStream_t st);
-int dense_hi2_launch_exact_select(const float* M, long ldM, long n_tiles, int m, int k, int list_stride, int* list, int* count,
-                                  const int* unres, const int* gate, hipStream_t st);
+// the exact tail behind the tile maxima M (dense_mfma.hip): each query's k best tiles, ascending, into list[q][..] (gate,
+// unres: nullable device pointers — null = always, every query; chosen, nullable: the tiles picked already, [m][k] best
+// first, to be ordered only) -> the exact scores of their rows -> the final top-k
+int dense_exact_select_launch(const float* M, long ldM, long n_tiles, int m, int k, int list_stride, int* list, int* count,
+                              const int* unres, const int* gate, const int64_t* chosen, hipStream_t st);
 int dense_rescore_tiles_launch(const float* X, long n_real, int d, const float* Q, int m, const int* list, const int* count,
                                int list_stride, int max_tiles, long ldS, float* S, hipStream_t st);
 int dense_final_topk_launch(const float* S, long ldS, const int* list, const int* count, int list_stride, int max_tiles,

@@ -268,7 +268,7 @@ struct amdr_dense {
   // synchronised before the mutex is released).  A service thread in amdr_dense_search can
   // therefore never scribble over the score matrix of a search_batch still in flight on another
   // stream.  "_device" calls on ONE handle from SEVERAL streams remain the caller's to order.
-  DevBuf part[2], smat[2], aux[2], qbuf, sbuf, ibuf;  // aux: candidate tiles of the two-level top-k
+  DevBuf part[2], smat[2], aux[2], qbuf, sbuf, ibuf;  // aux: the per-query tile lists of the two-level top-k
   // matrix statistics for the fp16 first pass of large scans (dense_hi.hip): kept up to date by create / add
   DevBuf stats;
   float x_scale = 1.f;       // power of two: |x| * x_scale < 1 for every component
@@ -385,15 +385,17 @@ int batched_chunk(const amdr_dense* h, int nq) {
 // plain two-pass form is 4 B x queries per row — 1.28 GB per 32 queries on 10 M rows, written and read back once, and
 // its stores interleave with the read stream at the HBM (timing-only build without them: 5.80 -> 5.10 ms).  Here:
 //   1. the tile kernel keeps, per 32-row tile and query, only the MAXIMUM  (n/32 x queries floats: 40 MB);
-//   2. top-k of each query's tile maxima -> k candidate tiles; their union, sorted, without duplicates;
-//   3. the tile kernel re-scores the candidate tiles (same loads, same MFMA k order: the same bits as a full pass);
-//   4. top-k of the re-scored columns, columns -> row ids.
+//   2. top-k of each query's tile maxima (slab lists + merge) -> its k candidate tiles, ascending, in its own list;
+//   3. one wave per (query, tile) re-scores them (same loads, same MFMA k order: the same bits as a full pass);
+//   4. top-k of each query's re-scored columns, columns -> row ids.
 // Exact: at most k - 1 tiles hold a score above a query's k-th best s_k, so the k-th largest tile maximum T <= s_k
 // and every tile that holds one of the top k has a maximum >= T; among tiles AT T the lower tile ids are kept, which
-// is where the lower row ids of equal scores live.  queries x k <= 8 192 candidate tiles per pass.
-constexpr int kTwoLevelTilesMax = 8192;  // candidate tiles per pass (queries x k): one wave sorts them in 64 KiB of LDS
+// is where the lower row ids of equal scores live.  Steps 2-4 are exact_tail below (kernels: dense_mfma.hip).
+// Queries per pass: 8 192 / k in whole 32-query tiles, at most 96.  Nothing in the tail bounds it any more (the value
+// once kept the pass's candidate tiles within one wave's sort); it is kept so that the scan launches of every call
+// stay what they were.
 int two_level_chunk(int nq, int k) {
-  int c = (kTwoLevelTilesMax / k) / 32 * 32;  // >= 32 for every k <= AMDR_MAX_K = 256
+  int c = (8192 / k) / 32 * 32;  // >= 32 for every k <= AMDR_MAX_K = 256
   if (c < 32) c = 32;
   if (c > 96) c = 96;
   return nq < c ? nq : c;
@@ -405,8 +407,8 @@ int two_level_chunk(int nq, int k) {
 // max(k, 22) + 1 tiles with the largest a(t) are re-scored, and the answer is exact if the kc-th largest a(t) lies below
 // T_k - 2 eps_q (T_k = the k-th largest): the k tiles on top have exact maxima >= T_k - eps, hence s_k >= T_k - eps,
 // and a tile holding a row >= s_k has a(t) >= s_k - eps >= T_k - 2 eps — it is among the first kc - 1.  Steps 3-4 are
-// exact: same ids, same score bits.  A query the bound does not separate raises a device flag; the exact first pass is
-// enqueued behind, gated on that flag (no host round trip), and gives that query its k tiles.
+// exact: same ids, same score bits.  A query the bound does not separate raises a device flag; exact steps 1-2 are
+// enqueued behind, gated on that flag (no host round trip), and give that query its k tiles.
 // Extra candidates: the tiles expected within 2 eps below the cut grow with k (about 0.4 k on unit-norm Gaussian rows)
 // and with how tightly the matrix clusters around a query's best rows, which only the data knows: three widths.
 constexpr int kHiLevels = 3;
@@ -558,58 +560,49 @@ bool hi_adapt(amdr_dense* h, const DensePins& pins) {
 }
 
 // ---- workspaces -----------------------------------------------------------------------------------------------------
-// Workspace of one pass of the round-4 tail.  smat: exact tile maxima M [m][ldM] (written only when the flag goes up) |
-// re-scored columns S2 [m][32 kc] | sample maxima MT [qtiles][items][64] | per-query candidate lists [m][qcap];
-// aux: list [m][kc] | count, unres [m] | tau [m] | qcount [m] | the gate flag.
-struct Hi2Plan {
+// Workspace of one pass of the two-level forms.  Both use
+//   smat: tile maxima M [m][ldM] | re-scored columns S2 [m][32 kc];   aux: list [m][kc] | count [m];
+// the exact form (kc = k) adds
+//   part: the slab lists of the top-k over M   (the k tiles it picks per query, ids [m][k] | maxima [m][k], pass through
+//         the head of S2, 12 of its 128 bytes per (query, tile): read by the ordering step before the re-scoring writes S2);
+// the fp16 form (kc = its candidate cut; M written only when the flag goes up) adds, behind them,
+//   smat: sample maxima MT [qtiles][items][64] | per-query candidate lists [m][qcap];   aux: unres [m] | tau [m] | qcount [m] | the gate flag.
+struct TwoLevelLayout {
   int qtiles, kc;
   long tiles, ldM, ldS2;
   size_t qcap;
-  DenseMfmaPlan scan;
+  DenseMfmaPlan scan, tk1;  // the tile-maxima scan; exact form: the top-k over its output (columns = tiles)
   size_t off_S2, off_MT, off_qlist, smat_bytes;
-  size_t off_count, off_unres, off_tau, off_qcount, off_flag, aux_bytes;
+  size_t off_count, off_unres, off_tau, off_qcount, off_flag, aux_bytes, part_bytes;
 };
-void hi2_plan(const amdr_dense* h, int m, int k, int kc, Hi2Plan* p, bool grids = true) {
+void two_level_layout(const amdr_dense* h, int m, int k, int kc, bool hi, TwoLevelLayout* p, bool grids = true) {
   auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+  *p = TwoLevelLayout{};
   const int qt = dense_hi_max_queries(h->d);
   p->qtiles = (m + qt - 1) / qt;
   p->kc = kc;
   p->tiles = ((long)h->n + 31) / 32;
   dense_mfma_plan((long)h->n, h->d, m, k, &p->scan, grids);
   p->ldM = (p->tiles + 31) / 32 * 32;
-  p->scan.ld = p->ldM;
+  p->scan.ld = p->ldM;  // (the tile-maxima scan writes one float per tile)
   p->ldS2 = (long)kc * 32;
-  p->qcap = dense_hi2_qcap((long)h->n, p->qtiles, kc);
   p->off_S2 = up((size_t)m * p->ldM * sizeof(float));
   p->off_MT = p->off_S2 + up((size_t)m * p->ldS2 * sizeof(float));
+  p->smat_bytes = p->off_MT;
+  p->off_count = up((size_t)m * kc * sizeof(int));
+  p->off_unres = p->aux_bytes = p->off_count + up((size_t)m * sizeof(int));
+  if (!hi) {
+    dense_mfma_plan(p->tiles, h->d, m, k, &p->tk1, false);  // only its top-k half is used (tk1.ld == ldM)
+    p->part_bytes = p->tk1.part_bytes;
+    return;
+  }
+  p->qcap = dense_hi2_qcap((long)h->n, p->qtiles, kc);
   p->off_qlist = p->off_MT + up((size_t)(2048 + 64 * kHi2Tiles) * 64 * sizeof(float));  // [queries][items rounded up to 64]
   p->smat_bytes = p->off_qlist + up((size_t)m * p->qcap * sizeof(C32));
-  p->off_count = up((size_t)m * kc * sizeof(int));
-  p->off_unres = p->off_count + up((size_t)m * sizeof(int));
   p->off_tau = p->off_unres + up((size_t)m * sizeof(int));
   p->off_qcount = p->off_tau + up((size_t)m * sizeof(float));
   p->off_flag = p->off_qcount + up((size_t)m * sizeof(unsigned int));
   p->aux_bytes = p->off_flag + 256;
-}
-
-struct TwoLevelPlan {
-  DenseMfmaPlan scan, tk1, pass2;  // full scan (mode 1), top-k over the tile maxima, candidate re-scoring + its top-k
-  long tiles, cand_rows;
-  size_t m_bytes, s2_bytes, aux_bytes, part_bytes;
-};
-// the exact form: every query of the pass against the UNION of their k candidate tiles each (one list)
-void two_level_plan(const amdr_dense* h, int m, int k, TwoLevelPlan* t, bool grids = true) {
-  t->tiles = ((long)h->n + 31) / 32;
-  dense_mfma_plan((long)h->n, h->d, m, k, &t->scan, grids);
-  dense_mfma_plan(t->tiles, h->d, m, k, &t->tk1, false);  // only its top-k half is used: columns = tiles
-  t->scan.ld = t->tk1.ld;                                 // (mode 1 writes one maximum per tile)
-  t->cand_rows = (long)m * k * 32;
-  dense_mfma_plan(t->cand_rows, h->d, m, k, &t->pass2, grids);
-  t->m_bytes = ((size_t)m * t->tk1.ld * sizeof(float) + 255) / 256 * 256;
-  t->s2_bytes = ((size_t)m * t->pass2.ld * sizeof(float) + 255) / 256 * 256;
-  // tile ids + maxima, union + count; + 256 that nothing addresses (where the fp16 pass's flag once sat: sizes as before)
-  t->aux_bytes = (size_t)m * k * (sizeof(int64_t) + sizeof(float)) + (size_t)(m * k + 64) * sizeof(int) + 256 + 256;
-  t->part_bytes = t->tk1.part_bytes > t->pass2.part_bytes ? t->tk1.part_bytes : t->pass2.part_bytes;
 }
 
 struct Need {  // bytes of smat / part / aux
@@ -627,15 +620,10 @@ Need pass_need(const amdr_dense* h, Form form, int m, int k) {
     make_plan(h->n, h->d, m, k, &p);
     return {0, p.part_bytes, 0};
   }
-  if (form == Form::TwoLevel) {
-    TwoLevelPlan t;
-    two_level_plan(h, m, k, &t, false);
-    return {t.m_bytes + t.s2_bytes, t.part_bytes, t.aux_bytes};
-  }
-  if (form == Form::Hi) {
-    Hi2Plan p;
-    hi2_plan(h, m, k, hi_kc_max(k), &p, false);
-    return {p.smat_bytes, 0, p.aux_bytes};
+  if (form == Form::TwoLevel || form == Form::Hi) {
+    TwoLevelLayout p;
+    two_level_layout(h, m, k, form == Form::Hi ? hi_kc_max(k) : k, form == Form::Hi, &p, false);
+    return {p.smat_bytes, p.part_bytes, p.aux_bytes};
   }
   DenseMfmaPlan p;  // RowWaves, Batched
   dense_mfma_plan((long)h->n, h->d, m, k, &p, false);
@@ -644,7 +632,8 @@ Need pass_need(const amdr_dense* h, Form form, int m, int k) {
 // One call: the maximum over every pass its loop will run — the full chunk AND the remainder, planned for its own size
 // (a shorter pass can need MORE slab-list space: slabs(m) * m is not monotone in m).  Where the fp16 first pass applies,
 // its passes and the exact ones: a handle gives the pass up (and add() gives it back) between a reserve and a call.
-// (Hi2Plan grows with m in every term — the sample stride, hence qcap, with the number of query tiles: no remainder.)
+// (The fp16 form of TwoLevelLayout has no slab lists and grows with m in every term — m rows of M, S2 and the lists at
+// strides that do not depend on m; the sample stride, hence qcap, with the number of query tiles: no remainder.)
 Need call_need(const amdr_dense* h, const Route& r, int nq, int k) {
   const Form form = r.hi ? Form::TwoLevel : r.form;
   const int chunk = r.hi ? two_level_chunk(nq, k) : r.chunk;
@@ -800,40 +789,49 @@ int run_search_batched(amdr_dense* h, int ws, const DensePins& pins, const Route
   return AMDR_OK;
 }
 
-// One pass of <= two_level_chunk queries of the exact form.
-int two_level_pass(amdr_dense* h, int ws, const float* Qc, int m, int k, float* out_scores, int64_t* out_ids,
-                   hipStream_t st) {
-  TwoLevelPlan t;
-  two_level_plan(h, m, k, &t);
-  float* M = h->smat[ws].as<float>();
-  float* S2 = reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(h->smat[ws].p) + t.m_bytes);
-  unsigned char* aux = reinterpret_cast<unsigned char*>(h->aux[ws].p);
-  int64_t* tile_ids = reinterpret_cast<int64_t*>(aux);
-  float* tile_max = reinterpret_cast<float*>(aux + (size_t)m * k * sizeof(int64_t));
-  int* list = reinterpret_cast<int*>(aux + (size_t)m * k * (sizeof(int64_t) + sizeof(float)));
-  int* count = list + (size_t)m * k;
-  int rc;
-  // 1. tile maxima (the scan: this is the launch the profiling events bracket)
-  if ((rc = profiled(h, st, [&] { return dense_mfma_launch_scores(t.scan, h->X, (long)h->n, h->d, Qc, m, M, st, 1); }))) return rc;
-  // 2. k candidate tiles per query, their sorted union
-  if ((rc = topk_pass(t.tk1, M, t.tiles, m, k, h->part[ws], tile_max, tile_ids, st))) return rc;
-  if ((rc = dense_tiles_unique_launch(tile_ids, m * k, t.tiles, list, count, st))) return rc;
-  // 3. exact scores of the candidate tiles' rows
-  if ((rc = dense_mfma_launch_scores(t.pass2, h->X, t.cand_rows, h->d, Qc, m, S2, st, 2, list, count, (long)h->n))) return rc;
-  // 4. top-k of the candidates, columns -> row ids
-  if ((rc = topk_pass(t.pass2, S2, t.cand_rows, m, k, h->part[ws], out_scores, out_ids, st))) return rc;
-  return dense_tiles_remap_launch(out_ids, m * k, list, count, (long)h->n, st);
-}
-
-// One pass (<= 4 query tiles) of the round-4 tail: see dense_hi.hip.  Launches: sample, tau, one scan per query tile,
-// select, [gated: exact tile maxima, exact select], re-scoring, final top-k.
-int hi2_pass(amdr_dense* h, int ws, const float* Qc, int m, int k, int kc, float* out_scores, int64_t* out_ids, hipStream_t st) {
-  Hi2Plan p;
-  hi2_plan(h, m, k, kc, &p);
+// Steps 1-4 of the exact two-level form for the m queries of a pass laid out by p: tile maxima M -> each query's k best
+// tiles, ascending, in list [m][p.kc] -> the exact scores of their rows -> final top-k.  gate, unres (device, nullable):
+// behind the fp16 first pass steps 1-2 run only when *gate != 0, step 2 only for queries with unres[q] != 0 (one block
+// sweeps a query's row of M), and steps 3-4 take the other queries' lists (<= p.kc tiles) as the fp16 pass left them;
+// null = always, every query: the k tiles then come from the slab top-k (+ merge) and step 2 only orders them.
+int exact_tail(amdr_dense* h, int ws, const TwoLevelLayout& p, const float* Qc, int m, int k, const int* unres, const int* gate,
+               float* out_scores, int64_t* out_ids, hipStream_t st) {
   unsigned char* sm = reinterpret_cast<unsigned char*>(h->smat[ws].p);
   unsigned char* ax = reinterpret_cast<unsigned char*>(h->aux[ws].p);
   float* M = reinterpret_cast<float*>(sm);
   float* S2 = reinterpret_cast<float*>(sm + p.off_S2);
+  int* list = reinterpret_cast<int*>(ax);
+  int* count = reinterpret_cast<int*>(ax + p.off_count);
+  const long n = (long)h->n;
+  // ungated, the scan is the launch the profiling events bracket (behind the fp16 pass that pass's own scan is)
+  auto scan = [&] { return dense_mfma_launch_scores(p.scan, h->X, n, h->d, Qc, m, M, st, true, gate); };
+  int rc = gate ? scan() : profiled(h, st, scan);
+  if (rc) return rc;
+  int64_t* chosen = nullptr;
+  if (!gate) {
+    chosen = reinterpret_cast<int64_t*>(S2);  // (see TwoLevelLayout)
+    if ((rc = topk_pass(p.tk1, M, p.tiles, m, k, h->part[ws], reinterpret_cast<float*>(chosen + (size_t)m * k), chosen, st))) return rc;
+  }
+  if ((rc = dense_exact_select_launch(M, p.ldM, p.tiles, m, k, p.kc, list, count, unres, gate, chosen, st))) return rc;
+  if ((rc = dense_rescore_tiles_launch(h->X, n, h->d, Qc, m, list, count, p.kc, p.kc, p.ldS2, S2, st))) return rc;
+  return dense_final_topk_launch(S2, p.ldS2, list, count, p.kc, p.kc, n, m, k, out_scores, out_ids, st);
+}
+
+// One pass of <= two_level_chunk queries of the exact form.
+int two_level_pass(amdr_dense* h, int ws, const float* Qc, int m, int k, float* out_scores, int64_t* out_ids,
+                   hipStream_t st) {
+  TwoLevelLayout p;
+  two_level_layout(h, m, k, k, false, &p);
+  return exact_tail(h, ws, p, Qc, m, k, nullptr, nullptr, out_scores, out_ids, st);
+}
+
+// One pass (<= 4 query tiles) of the round-4 tail: see dense_hi.hip.  Launches: sample, tau, one scan per query tile,
+// select, then exact_tail behind the flag: [gated: exact tile maxima, exact select], re-scoring, final top-k.
+int hi2_pass(amdr_dense* h, int ws, const float* Qc, int m, int k, int kc, float* out_scores, int64_t* out_ids, hipStream_t st) {
+  TwoLevelLayout p;
+  two_level_layout(h, m, k, kc, true, &p);
+  unsigned char* sm = reinterpret_cast<unsigned char*>(h->smat[ws].p);
+  unsigned char* ax = reinterpret_cast<unsigned char*>(h->aux[ws].p);
   float* MT = reinterpret_cast<float*>(sm + p.off_MT);
   C32* qlist = reinterpret_cast<C32*>(sm + p.off_qlist);
   int* list = reinterpret_cast<int*>(ax);
@@ -866,10 +864,7 @@ int hi2_pass(amdr_dense* h, int ws, const float* Qc, int m, int k, int kc, float
                                     count, unres, flag, stats + 2, st)))
     return rc;
   // behind the flag: the exact first pass of the batch and, for the queries the bound did not resolve, their k tiles
-  if ((rc = dense_mfma_launch_scores(p.scan, h->X, (long)h->n, h->d, Qc, m, M, st, 1, nullptr, nullptr, 0, flag))) return rc;
-  if ((rc = dense_hi2_launch_exact_select(M, p.ldM, p.tiles, m, k, kc, list, count, unres, flag, st))) return rc;
-  if ((rc = dense_rescore_tiles_launch(h->X, (long)h->n, h->d, Qc, m, list, count, kc, kc, p.ldS2, S2, st))) return rc;
-  return dense_final_topk_launch(S2, p.ldS2, list, count, kc, kc, (long)h->n, m, k, out_scores, out_ids, st);
+  return exact_tail(h, ws, p, Qc, m, k, unres, flag, out_scores, out_ids, st);
 }
 
 // Forms TwoLevel and Hi.
@@ -1233,8 +1228,8 @@ int amdr_dense_plan_info(const amdr_dense_t* h, int32_t nq, int32_t k, char* buf
   if (h->n <= 0) {
     snprintf(buf, buf_len, "empty index");
   } else if (r.form == Form::Hi) {
-    Hi2Plan p;
-    hi2_plan(h, m, k, r.kc, &p);
+    TwoLevelLayout p;
+    two_level_layout(h, m, k, r.kc, true, &p);
     snprintf(buf, buf_len,
              "dense_hi_tilemax_kernel fp16 first pass queries_per_launch=%d scans_per_launch=%d (%d per scan, one tail): per-query lists of the "
              "approximate tile maxima above a sampled threshold (every %ld-th tile, width level %d) -> top-%d + rounding-bound "
@@ -1243,12 +1238,12 @@ int amdr_dense_plan_info(const amdr_dense_t* h, int32_t nq, int32_t k, char* buf
              m, p.qtiles, m < dense_hi_max_queries(h->d) ? m : dense_hi_max_queries(h->d),
              dense_hi2_sample_stride((long)h->n, p.qtiles), r.hi_level, r.kc, r.kc);
   } else if (r.form == Form::TwoLevel) {
-    TwoLevelPlan t;
-    two_level_plan(h, m, k, &t);
+    TwoLevelLayout t;
+    two_level_layout(h, m, k, k, false, &t);
     snprintf(buf, buf_len,
              "dense_mfma_scores_kernel tile-maxima grid=%dx%d queries_per_launch=%d two-level: top-%d of %ld tile maxima "
-             "+ re-scoring of <= %d candidate tiles + top-k%s",
-             t.scan.grid_x, t.scan.grid_y, m, k, t.tiles, m * k,
+             "+ <= %d tiles per query re-scored + top-k%s",
+             t.scan.grid_x, t.scan.grid_y, m, k, t.tiles, k,
              r.hi ? " (fp16 first pass given up: too many unresolved queries)" : "");
   } else if (r.form != Form::Scan) {
     DenseMfmaPlan p;

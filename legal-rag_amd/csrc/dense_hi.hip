@@ -652,36 +652,6 @@ __global__ __launch_bounds__(256) void dense_hi_select_kernel(const C32* __restr
   }
 }
 
-// Gated (the flag of the pass) and per query (unres[q]): the k tiles with the largest EXACT maxima M[q][tile] (fp32 matrix
-// instructions, dense_mfma.hip mode 1) — step 2 of the exact two-level form — ascending into the query's list.  The exact
-// re-scoring and the final top-k then treat every query of the batch alike.
-__global__ __launch_bounds__(256) void dense_hi_exact_select_kernel(const float* __restrict__ M, long ldM, long n_tiles, int k,
-                                                                    int tcap, int list_stride, int* __restrict__ list,
-                                                                    int* __restrict__ count, const int* __restrict__ unres,
-                                                                    const int* __restrict__ gate) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  if (*gate == 0) return;
-  const int q = blockIdx.x;
-  if (unres[q] == 0) return;
-  C32* lists = reinterpret_cast<C32*>(smem);
-  int* cnts = reinterpret_cast<int*>(lists + (size_t)4 * tcap);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const float* row = M + (size_t)q * ldM;
-  WaveTopK<C32> tk;
-  tk.init(lists + (size_t)wave * tcap, tcap, k);
-  wave_topk_sweep4<false>(tk, row, 0, n_tiles, wave, 4, lane);  // ldM is a multiple of 32 floats: whole float4s
-  block_combine_topk(tk, lists, tcap, 4, wave, lane, cnts);
-  if (wave != 0) return;
-  const int keep = tk.cnt;
-  for (int j = lane; j < keep; j += 64) {
-    const long long t = tk.buf[j].id();
-    int rank = 0;
-    for (int i = 0; i < keep; ++i) rank += tk.buf[i].id() < t ? 1 : 0;
-    list[(size_t)q * list_stride + rank] = (int)t;
-  }
-  if (lane == 0) count[q] = keep;
-}
-
 // ---- host side of the round-4 tail -------------------------------------------------------------------------------------
 // the sample of a search with `qtiles` query tiles: 2 048 / qtiles items per tile (one item per wave of the grid, all
 // tiles in ONE launch)
@@ -744,15 +714,6 @@ int dense_hi2_launch_select(const void* qlist, const unsigned int* qcount, size_
   hipLaunchKernelGGL(dense_hi_select_kernel, dim3(m), dim3(256), lds, st, (const C32*)qlist, qcount, (unsigned int)qcap, kc, k,
                      tcap, Q, d, row_norm_max, x_scale, x_exp, n_tiles, list, count, unres, flag, unresolved,
                      (m + hi_query_tile(d) - 1) / hi_query_tile(d));
-  AMDR_HIP(hipGetLastError());
-  return AMDR_OK;
-}
-int dense_hi2_launch_exact_select(const float* M, long ldM, long n_tiles, int m, int k, int list_stride, int* list, int* count,
-                                  const int* unres, const int* gate, hipStream_t st) {
-  const int tcap = topk_cap(k);
-  const size_t lds = (size_t)4 * tcap * sizeof(C32) + 4 * sizeof(int);
-  hipLaunchKernelGGL(dense_hi_exact_select_kernel, dim3(m), dim3(256), lds, st, M, ldM, n_tiles, k, tcap, list_stride, list,
-                     count, unres, gate);
   AMDR_HIP(hipGetLastError());
   return AMDR_OK;
 }

@@ -112,17 +112,12 @@ template <int D8, int WAVES, bool NTL>  // NTL: non-temporal loads of the stream
 __global__ __launch_bounds__(WAVES * 64) void dense_mfma_scores_kernel(const float* __restrict__ X, long n,
                                                                  const float* __restrict__ Q, int nq,
                                                                  long rows_per_block, int gx, int gy, long ldS,
-                                                                 float* __restrict__ S /*[queries][ldS]*/, int mode,
-                                                                 const int* __restrict__ tile_list,
-                                                                 const int* __restrict__ tile_count, long n_real,
+                                                                 float* __restrict__ S /*[queries][ldS]*/, int tile_max,
                                                                  const int* __restrict__ gate) {
-  if (gate != nullptr && *gate == 0) return;  // a gated launch (dense_hi.hip): decided on the device, block-uniform
-  // mode 0: S[query][row] for every row.
-  // mode 1: S[query][tile] = MAXIMUM of the query's scores over the 32-row tile (first pass of the two-level
-  //         top-k of a large scan: dense.hip run_search_two_level).
-  // mode 2: `n` counts VIRTUAL rows, 32 per entry of tile_list; virtual tile t reads chunk tile tile_list[t]
-  //         (t < *tile_count, else it is filled with -FLT_MAX) and writes S[query][32 t ..]: the exact re-scoring of
-  //         the candidate tiles — same loads, same MFMA k order, the same bits as mode 0.
+  if (gate != nullptr && *gate == 0) return;  // a gated launch (dense.hip hi2_pass): decided on the device, block-uniform
+  // tile_max == 0: S[query][row] for every row.
+  // tile_max != 0: S[query][tile] = MAXIMUM of the query's scores over the 32-row tile (first pass of the two-level
+  //                top-k of a large scan: dense.hip exact_tail).
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int d = D8 * 8;
   constexpr int NCH = d / kKC;  // chunks per row: 12 / 24 / 32 (always even: d % 64 == 0)
@@ -202,32 +197,13 @@ __global__ __launch_bounds__(WAVES * 64) void dense_mfma_scores_kernel(const flo
   // loader role of this lane inside a 1-KiB piece: 8 rows x 8 slots
   const int lrow = lane >> 3, lslot = lane & 7;
 
-  const int n_list = mode == 2 ? *tile_count : 0;
   for (long r0 = row_lo + (long)wave * 32; r0 < row_hi; r0 += (long)WAVES * 32) {
-    long src0 = r0, src_hi = row_hi;  // rows actually read
-    if (mode == 2) {
-      const int t = (int)(r0 >> 5);
-      if (t >= n_list) {  // beyond the candidate list: columns that can never win
-#pragma unroll
-        for (int bi = 0; bi < 2; ++bi) {
-          const int q = q0 + 16 * bi + i16;
-          if (q < nq) {
-            float* srow = S + (size_t)q * ldS + r0 + 4 * kq;
-#pragma unroll
-            for (int bj = 0; bj < 2; ++bj) *reinterpret_cast<f32x4*>(srow + 16 * bj) = f32x4{-FLT_MAX, -FLT_MAX, -FLT_MAX, -FLT_MAX};
-          }
-        }
-        continue;
-      }
-      src0 = (long)tile_list[t] * 32;
-      src_hi = n_real;
-    }
     // global pointers of the 8 pieces (rows 4p + lrow), clamped at the slab end
     const float* gp[kPieces];
 #pragma unroll
     for (int p = 0; p < kPieces; ++p) {
-      long r = src0 + 8 * p + lrow;
-      if (r >= src_hi) r = src_hi - 1;
+      long r = r0 + 8 * p + lrow;
+      if (r >= row_hi) r = row_hi - 1;
       gp[p] = X + (size_t)r * d + lslot * 4;
     }
     // Software pipeline; every index below is a compile-time constant once the chunk loop is
@@ -285,7 +261,7 @@ __global__ __launch_bounds__(WAVES * 64) void dense_mfma_scores_kernel(const flo
     // = 4 % of the bytes cost 12 % of the time: they interleave with the read stream at the HBM), non-temporal
     // stores 6.01 -> 6.10 ms.)  Rows past n inside the last 32-row tile repeat row n - 1 and land in the
     // padding of S (ldS is a multiple of 32); slab boundaries are multiples of 32 rows.
-    if (mode == 1) {
+    if (tile_max) {
       // tile maxima: 7 v_max per query block in the lane, two exchanges over the four kq groups (rows past the end
       // of the matrix repeat its last row: no effect on a maximum)
 #pragma unroll
@@ -308,15 +284,7 @@ __global__ __launch_bounds__(WAVES * 64) void dense_mfma_scores_kernel(const flo
         if (acc[bi][0][0] == 12345.f) srow[0] = acc[bi][1][1];
 #else
 #pragma unroll
-        for (int bj = 0; bj < 2; ++bj) {
-          f32x4 v = acc[bi][bj];
-          if (mode == 2) {  // rows past the end of the matrix inside the last tile are no candidates
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-              if (src0 + 16 * bj + 4 * kq + r >= n_real) v[r] = -FLT_MAX;
-          }
-          *reinterpret_cast<f32x4*>(srow + 16 * bj) = v;
-        }
+        for (int bj = 0; bj < 2; ++bj) *reinterpret_cast<f32x4*>(srow + 16 * bj) = acc[bi][bj];
 #endif
       }
     }
@@ -380,141 +348,63 @@ __global__ __launch_bounds__(64) void scores_pair_topk_kernel(const float* __res
   if (has_q && j < k) topk_store(out, j < got, j, fin_scores + (size_t)q * k, fin_ids + (size_t)q * k);
 }
 
-// Two-level top-k of a large scan, step 2: the <= 8 192 candidate tile ids (k per query, -1 = none) -> ascending
-// list without duplicates + its length.  One wave; bitonic sort in LDS (descending on id + 1, so that "none" sorts
-// last), neighbour compare, one prefix sum.
-__global__ __launch_bounds__(64) void tiles_unique_kernel(const long long* __restrict__ tile_ids, int n_in, int cap,
-                                                          int* __restrict__ list, int* __restrict__ count) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  C32* buf = reinterpret_cast<C32*>(smem);
-  const int lane = threadIdx.x;
-  for (int i = lane; i < cap; i += 64) {
-    const long long v = i < n_in ? tile_ids[i] : -1ll;
-    buf[i].c = v >= 0 ? (u64)(v + 1) : 0ull;
-  }
-  wave_bitonic_sort_desc(buf, cap, lane);
-  const int per = cap / 64;  // cap is a power of two >= 64
-  int mine = 0;
-  for (int j = 0; j < per; ++j) {
-    const int i = lane * per + j;
-    const u64 x = buf[i].c, prev = i ? buf[i - 1].c : ~0ull;
-    mine += (x != 0ull && x != prev) ? 1 : 0;
-  }
-  int incl = mine;
-#pragma unroll
-  for (int s2 = 1; s2 < 64; s2 <<= 1) {
-    const int o = __shfl_up(incl, s2);
-    incl += (lane >= s2) ? o : 0;
-  }
-  const int total = __builtin_amdgcn_readlane(incl, 63);
-  int pos = incl - mine;
-  for (int j = 0; j < per; ++j) {
-    const int i = lane * per + j;
-    const u64 x = buf[i].c, prev = i ? buf[i - 1].c : ~0ull;
-    if (x != 0ull && x != prev) list[total - 1 - pos++] = (int)(x - 1);  // descending order in, ascending out
-  }
-  if (lane == 0) *count = total;
-}
-
-// The same list from a bitmap of the tiles in LDS (one block of 1 024 threads, up to 2^20 tiles = 128 KiB of bits):
-// mark, popcount prefix sum over the words, emit ascending.  The one-wave sort above takes 0.3 ms for the 2 112
-// candidates of a 64-query pass behind the fp16 first pass — more than every other step after the scan together.
-__global__ __launch_bounds__(1024) void tiles_unique_bitmap_kernel(const long long* __restrict__ tile_ids, int n_in,
-                                                                   int n_tiles, int* __restrict__ list,
-                                                                   int* __restrict__ count) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const int words = (n_tiles + 31) >> 5;
-  unsigned int* bm = reinterpret_cast<unsigned int*>(smem);
-  int* wsum = reinterpret_cast<int*>(bm + words);  // 16 wave totals
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  for (int i = tid; i < words; i += 1024) bm[i] = 0u;
-  __syncthreads();
-  for (int i = tid; i < n_in; i += 1024) {
-    const long long v = tile_ids[i];
-    if (v >= 0 && v < n_tiles) atomicOr(&bm[v >> 5], 1u << (v & 31));
-  }
-  __syncthreads();
-  const int per = (words + 1023) / 1024, w0 = tid * per;
-  int mine = 0;
-  for (int j = 0; j < per; ++j)
-    if (w0 + j < words) mine += __popc(bm[w0 + j]);
-  int incl = mine;
-#pragma unroll
-  for (int s2 = 1; s2 < 64; s2 <<= 1) {
-    const int o = __shfl_up(incl, s2);
-    incl += (lane >= s2) ? o : 0;
-  }
-  if (lane == 63) wsum[wave] = incl;
-  __syncthreads();
-  int base = 0, total = 0;
-  for (int w = 0; w < 16; ++w) {
-    const int x = wsum[w];
-    base += w < wave ? x : 0;
-    total += x;
-  }
-  int pos = base + incl - mine;
-  for (int j = 0; j < per; ++j) {
-    if (w0 + j >= words) break;
-    unsigned int x = bm[w0 + j];
-    while (x) {
-      const int b = __ffs((int)x) - 1;
-      list[pos++] = (w0 + j) * 32 + b;
-      x &= x - 1;
-    }
-  }
-  if (tid == 0) *count = total;
-}
-
-// step 4: the final hits carry COLUMNS of the re-scored candidate matrix (32 per list entry); columns ascend with the
-// row ids (the list is ascending), so ties were already broken towards the lower id.
-__global__ __launch_bounds__(256) void tiles_remap_ids_kernel(long long* __restrict__ ids, int total,
-                                                              const int* __restrict__ list,
-                                                              const int* __restrict__ count, long n_real) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i < total) {
-    const long long c = ids[i];
-    if (c >= 0) {
-      // a filler column (beyond the candidate list, or past the end of the matrix inside the last tile: score
-      // -FLT_MAX) reaches the final list only when fewer than k candidate rows have a real (non-NaN) score: it is
-      // padding, id -1 (the faiss convention for "fewer than k results"), never a read of an unwritten list entry
-      const long long t = c >> 5;
-      const long long r = t < *count ? (long long)list[t] * 32 + (c & 31) : -1;
-      ids[i] = r < n_real ? r : -1;
-    }
-  }
-}
-
-int dense_tiles_unique_launch(const int64_t* tile_ids, int n_in, long n_tiles, int* list, int* count, hipStream_t st) {
-  if (n_tiles > 0 && n_tiles <= kUniqueBitmapTilesMax && n_in >= 512) {
-    const size_t lds = (size_t)((n_tiles + 31) / 32) * 4 + 64;
-    AMDR_HIP(hipFuncSetAttribute((const void*)tiles_unique_bitmap_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 128 * 1024 + 64));
-    hipLaunchKernelGGL(tiles_unique_bitmap_kernel, dim3(1), dim3(1024), lds, st, (const long long*)tile_ids, n_in,
-                       (int)n_tiles, list, count);
-    AMDR_HIP(hipGetLastError());
-    return AMDR_OK;
-  }
-  int cap = 64;
-  while (cap < n_in) cap <<= 1;
-  hipLaunchKernelGGL(tiles_unique_kernel, dim3(1), dim3(64), (size_t)cap * sizeof(C32), st, (const long long*)tile_ids, n_in,
-                     cap, list, count);
-  AMDR_HIP(hipGetLastError());
-  return AMDR_OK;
-}
-int dense_tiles_remap_launch(int64_t* ids, int total, const int* list, const int* count, long n_real, hipStream_t st) {
-  hipLaunchKernelGGL(tiles_remap_ids_kernel, dim3(ceil_div(total, 256)), dim3(256), 0, st, (long long*)ids, total, list,
-                     count, n_real);
-  AMDR_HIP(hipGetLastError());
-  return AMDR_OK;
-}
-
 // ---------------------------------------------------------------------------------------------------------------------
-// Round 4: exact scores of every query's OWN candidate tiles behind the fp16 first pass, lean form.  A retired mode 3 of
+// The exact tail of a large scan behind the tile maxima M[q][tile] (tile_max above): each query's k best tiles, the exact
+// scores of their rows, the final top-k.  The exact two-level form runs it for every query of a pass; the fp16 first
+// pass (dense_hi.hip) behind its device flag, for the queries its rounding bound did not resolve (dense.hip exact_tail).
+
+// Step 2: the k tiles with the largest maxima, ascending by tile id, into the query's list; lower tile ids win among
+// equal maxima.  `gate` (nullable): nothing runs unless *gate != 0.  `unres` (nullable): only queries with unres[q] != 0.
+// One block sweeps its query's whole row of M: right for the few unresolved queries behind the fp16 pass.  For every
+// query of a pass on a 10 M-row matrix (312 500 maxima per query, a handful of blocks) the sweep is bound by the
+// latency of its own loads, so the ungated call picks the tiles with the slab top-k (+ merge) that spreads a row over
+// many blocks and passes them in `chosen` ([queries][k] tile ids, best first, -1 behind the last; one wave per
+// query): only the ordering is left to do here.
+__global__ __launch_bounds__(256) void dense_hi_exact_select_kernel(const float* __restrict__ M, long ldM, long n_tiles, int k,
+                                                                    int tcap, int list_stride, int* __restrict__ list,
+                                                                    int* __restrict__ count, const int* __restrict__ unres,
+                                                                    const int* __restrict__ gate,
+                                                                    const long long* __restrict__ chosen) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  if (gate != nullptr && *gate == 0) return;
+  const int q = blockIdx.x;
+  if (unres != nullptr && unres[q] == 0) return;
+  C32* lists = reinterpret_cast<C32*>(smem);
+  int* cnts = reinterpret_cast<int*>(lists + (size_t)4 * tcap);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  WaveTopK<C32> tk;
+  tk.init(lists + (size_t)wave * tcap, tcap, k);
+  if (chosen != nullptr) {
+    int got = 0;
+    for (int j0 = 0; j0 < k; j0 += 64) {
+      const int j = j0 + lane;
+      const long long t = j < k ? chosen[(size_t)q * k + j] : -1ll;
+      if (t >= 0) tk.buf[j] = C32::make(0.f, (u32)t);
+      got += __popcll(__ballot(t >= 0));
+    }
+    tk.cnt = got;
+    wave_lds_fence();
+  } else {
+    wave_topk_sweep4<false>(tk, M + (size_t)q * ldM, 0, n_tiles, wave, 4, lane);  // ldM is a multiple of 32 floats: whole float4s
+    block_combine_topk(tk, lists, tcap, 4, wave, lane, cnts);
+    if (wave != 0) return;
+  }
+  const int keep = tk.cnt;
+  for (int j = lane; j < keep; j += 64) {
+    const long long t = tk.buf[j].id();
+    int rank = 0;
+    for (int i = 0; i < keep; ++i) rank += tk.buf[i].id() < t ? 1 : 0;
+    list[(size_t)q * list_stride + rank] = (int)t;
+  }
+  if (lane == 0) count[q] = keep;
+}
+
+// Step 3: exact scores of every query's OWN candidate tiles, lean form.  A retired mode 3 of
 // the tile kernel above did this with a whole 32-query LDS tile per block (96 KiB staged, 31 of 32 MFMA columns idle, one block
 // per CU: 38 us per 64 queries).  Here a wave scores ONE (query, tile): the tile's rows stream through the wave's 4-KiB
 // stage exactly as above (same loads, same fragments), the B operand is the query's own components broadcast to all 16
 // columns, and only the two row blocks are multiplied: 16 MFMAs per chunk instead of 32, the k-steps in the SAME order —
-// acc[bj] sees the sequence the tile kernel's acc[bi][bj] sees, hence the same bits (tested against modes 0 / 2).
+// acc[bj] sees the sequence the tile kernel's acc[bi][bj] sees, hence the same bits (tested against the full score matrix).
 // 20 KiB of LDS per 4-wave block: the candidate tiles of a batch spread over every CU.
 // grid: (queries, ceil(max tiles per query / WPB)).
 template <int D8, int WPB>
@@ -650,9 +540,8 @@ __global__ __launch_bounds__(WAVES * 64) void dense_final_topk_kernel(const floa
   if (WAVES > 1) block_combine_topk(tk, lists, cap, WAVES, wave, lane, cnts);
   if (wave == 0) {
     for (int j = lane; j < k; j += 64) {
-      // A NaN score (key 1: it sorts behind every real score) is no hit: the exact two-level form ranks its filler
-      // columns (-FLT_MAX, id -1) above NaN rows, so a query or rows that score NaN come back as padding there — the
-      // same here (tests/test_dense_hi_gpu.py: the exact two-level form decides what a NaN query returns).
+      // A NaN score (key 1: it sorts behind every real score) is no hit: a query or rows that score NaN come back as
+      // padding (id -1, -FLT_MAX), whichever other queries share the pass (tests/test_kernels_gpu.py, test_dense_hi_gpu.py).
       const bool v = j < tk.cnt && (u32)(tk.buf[j].c >> 32) != 1u;
       const C32 c = v ? tk.buf[j] : C32::pad();
       long long id = -1ll;
@@ -728,8 +617,7 @@ void dense_mfma_plan(long n, int d, int nq, int k, DenseMfmaPlan* p, bool grid) 
 
 template <int D8, int WAVES, bool NTL>
 static int launch_scores(const DenseMfmaPlan& p, const float* X, long n, const float* Q, int nq, float* S,
-                         hipStream_t st, int mode, const int* tile_list, const int* tile_count, long n_real,
-                         const int* gate) {
+                         hipStream_t st, bool tile_max, const int* gate) {
   // 128-160 KiB of dynamic LDS needs the opt-in.  The attribute belongs to the (function, device)
   // pair, the C ABI takes a device ordinal, and setting it is cheap: set on every launch for the
   // current device rather than remembering "done" per process.
@@ -737,21 +625,19 @@ static int launch_scores(const DenseMfmaPlan& p, const float* X, long n, const f
                                hipFuncAttributeMaxDynamicSharedMemorySize,
                                D8 * 8 * 32 * (int)sizeof(float) + WAVES * kStageBufs * kStageBytes));
   hipLaunchKernelGGL((dense_mfma_scores_kernel<D8, WAVES, NTL>), dim3(p.grid_x * p.grid_y), dim3(WAVES * 64),
-                     p.lds_scores, st, X, n, Q, nq, p.rows_per_block, p.grid_x, p.grid_y, p.ld, S, mode, tile_list, tile_count,
-                     n_real, gate);
+                     p.lds_scores, st, X, n, Q, nq, p.rows_per_block, p.grid_x, p.grid_y, p.ld, S, (int)tile_max, gate);
   return AMDR_OK;
 }
 
 int dense_mfma_launch_scores(const DenseMfmaPlan& p, const float* X, long n, int d, const float* Q, int nq, float* S,
-                             hipStream_t st, int mode, const int* tile_list, const int* tile_count, long n_real,
-                             const int* gate) {
+                             hipStream_t st, bool tile_max, const int* gate) {
   int rc = AMDR_OK;
-  const bool nt = dense_stream_nontemporal(mode >= 2 ? n_real : n, d) && mode < 2;  // candidate tiles are re-read: cacheable
+  const bool nt = dense_stream_nontemporal(n, d);
   switch (d) {
 #define AMDR_CASE(D)                                                          \
   case D:                                                                     \
-    rc = nt ? launch_scores<D / 8, scores_waves(D), true>(p, X, n, Q, nq, S, st, mode, tile_list, tile_count, n_real, gate)   \
-            : launch_scores<D / 8, scores_waves(D), false>(p, X, n, Q, nq, S, st, mode, tile_list, tile_count, n_real, gate); \
+    rc = nt ? launch_scores<D / 8, scores_waves(D), true>(p, X, n, Q, nq, S, st, tile_max, gate)   \
+            : launch_scores<D / 8, scores_waves(D), false>(p, X, n, Q, nq, S, st, tile_max, gate); \
     break;
     AMDR_CASE(64) AMDR_CASE(128) AMDR_CASE(192) AMDR_CASE(256) AMDR_CASE(320) AMDR_CASE(384)
     AMDR_CASE(448) AMDR_CASE(512) AMDR_CASE(576) AMDR_CASE(640) AMDR_CASE(704) AMDR_CASE(768)
@@ -786,6 +672,18 @@ int dense_mfma_launch_topk(const DenseMfmaPlan& p, const float* S, long n, int n
   return AMDR_OK;
 }
 
+
+// list[q][0 .. count[q]) = the k tiles of query q with the largest M[q][tile], ascending (gate, unres, chosen: see the
+// kernel)
+int dense_exact_select_launch(const float* M, long ldM, long n_tiles, int m, int k, int list_stride, int* list, int* count,
+                              const int* unres, const int* gate, const int64_t* chosen, hipStream_t st) {
+  const int tcap = topk_cap(k);
+  const size_t lds = (size_t)4 * tcap * sizeof(C32) + 4 * sizeof(int);
+  hipLaunchKernelGGL(dense_hi_exact_select_kernel, dim3(m), dim3(chosen ? 64 : 256), lds, st, M, ldM, n_tiles, k, tcap,
+                     list_stride, list, count, unres, gate, (const long long*)chosen);
+  AMDR_HIP(hipGetLastError());
+  return AMDR_OK;
+}
 
 template <int D8>
 static int launch_rescore(const float* X, long n_real, const float* Q, int m, const int* list, const int* count,

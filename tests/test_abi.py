@@ -91,9 +91,9 @@ def test_no_cpu_fallback_in_product():
 
 def test_dense_workspace_covers_every_pass(monkeypatch):
     """A batched dense search reserves its workspace once and then runs passes of the full chunk and a remainder:
-    the slab-list space slabs(m) * m * k * 8 is NOT monotone in the pass size m (13 M rows, k = 10: 96 queries take
-    22 slabs = 168 960 B, the 89-query remainder 24 slabs = 170 880 B), so the reservation must be the maximum over
-    the passes.  Host-only arithmetic (amdr_dense_workspace_plan): no device."""
+    the slab-list space slabs(m) * m * k * 8 is NOT monotone in the pass size m (10 M rows through the full score
+    matrix, k = 10: 96 queries take 22 slabs = 168 960 B, the 89-query remainder 24 slabs = 170 880 B), so the
+    reservation must be the maximum over the passes.  Host-only arithmetic (amdr_dense_workspace_plan): no device."""
     from legal_rag_amd import _native
     checked = two_level = 0
     for n in (13_000_000, 12_345_678, 20_000_000, 40_000_000, 3_000_000, 600_000):
@@ -104,11 +104,47 @@ def test_dense_workspace_covers_every_pass(monkeypatch):
                 checked += 1
                 two_level += int(res[2] > 0)
     assert checked > 300 and two_level > 50
-    # the advisor's worked example, pinned: remainder 89 needs more list space than the chunk of 96
-    monkeypatch.setenv("AMDR_DENSE_TWO_LEVEL", "1")
-    monkeypatch.setenv("AMDR_DENSE_HI", "0")  # the exact first pass (32-query tiles, chunks of 96)
-    res, used = _native.dense_workspace_plan(13_000_000, 768, 185, 10, 185, 10)
+    # the advisor's worked example, pinned, on the form that has slab lists (the full score matrix, chunks of 96 on
+    # 10 M rows): remainder 89 needs more list space than the chunk of 96
+    monkeypatch.setenv("AMDR_DENSE_TWO_LEVEL", "0")
+    res, used = _native.dense_workspace_plan(10_000_000, 768, 185, 10, 185, 10)
     assert used[1] == 170880 and res[1] >= used[1]
+    assert _native.dense_workspace_plan(10_000_000, 768, 96, 10, 96, 10)[1][1] == 168960
+    assert _native.dense_workspace_plan(10_000_000, 768, 89, 10, 89, 10)[1][1] == 170880
+    # the exact two-level form (32-query tiles, chunks of 96): M [m][ldM] | S2 [m][32 k] in smat, list [m][k] | count [m]
+    # in aux, each rounded up to 256 B, and in part the slab lists of the top-k over the n / 32 tile maxima alone.  Never
+    # more than the form it replaced needed, which re-scored the UNION of the pass's m * k candidate tiles for every
+    # query (S2 [m][32 m k], and its slab lists; aux: tile ids + maxima m * k * 12 B, the union (m * k + 64) * 4 B, 512 B
+    # of padding)
+    monkeypatch.setenv("AMDR_DENSE_TWO_LEVEL", "1")
+    monkeypatch.setenv("AMDR_DENSE_HI", "0")
+    up = lambda b: (b + 255) // 256 * 256  # noqa: E731
+    chunk = lambda nq, k: min(nq, min(96, max(32, 8192 // k // 32 * 32)))  # noqa: E731
+    ld_m = lambda n: ((n + 31) // 32 + 31) // 32 * 32  # noqa: E731
+
+    def now(n, m, k):
+        return up(m * ld_m(n) * 4) + up(m * 32 * k * 4), up(m * k * 4) + up(m * 4)
+
+    def lists(cols, m, k):  # slab lists of a top-k pass over m rows of `cols` scores
+        if m == 0:
+            return 0
+        sl = max(1, min(-(-2048 // m), -(-cols // 16384)))
+        per = (-(-cols // sl) + 63) // 64 * 64
+        return -(-cols // per) * m * k * 8
+
+    def before(n, m, k):
+        return up(m * ld_m(n) * 4) + up(m * 32 * m * k * 4), m * k * 12 + (m * k + 64) * 4 + 512
+
+    for n in (13_000_000, 12_345_678, 20_000_000, 40_000_000, 3_000_000, 600_000):
+        for k in (1, 10, 80, 256):
+            for nq in (5, 37, 95, 96, 97, 100, 131, 185, 191, 192, 193, 250, 1000):
+                res, used = _native.dense_workspace_plan(n, 768, nq, k, nq, k)
+                assert (used[0], used[2]) == now(n, chunk(nq, k), k), (n, k, nq, used)
+                assert used[1] == max(lists((n + 31) // 32, m, k) for m in {chunk(nq, k), nq % chunk(nq, k)}), (n, k, nq, used)
+                old_used = before(n, chunk(nq, k), k)
+                old_res = [max(before(n, chunk(nq, kk), kk)[c] for kk in range(1, k + 1)) for c in (0, 1)]
+                assert used[0] <= old_used[0] and used[2] <= old_used[1], (n, k, nq, used, old_used)
+                assert res[0] <= old_res[0] and res[2] <= old_res[1], (n, k, nq, res, old_res)
     # the fp16 first pass (chunks of 64, k + 23 candidate tiles per query) and the exact chain behind its flag
     for hi in ("0", "1"):
         monkeypatch.setenv("AMDR_DENSE_HI", hi)

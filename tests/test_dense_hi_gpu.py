@@ -147,8 +147,15 @@ def test_hi_first_pass_nan_rows_and_nan_queries(nat, monkeypatch):
     idx = nat.DenseIndex(Xc)
     ex = idx.search(Q, 10)
     idx.close()
-    assert np.array_equal(hi[1], ex[1])  # the exact two-level form decides what a NaN / infinite query returns
+    assert np.array_equal(hi[1], ex[1])
     assert np.array_equal(hi[0].view(np.uint32), ex[0].view(np.uint32))
+    # both pins end in one exact tail, so what a NaN / infinite query returns is stated outright (recorded from the exact
+    # two-level form when it still re-scored the union of the batch's tiles): a NaN query is padding; an infinite
+    # component makes every row with a positive component there score +inf, lowest ids first
+    for s, i in (hi, ex):
+        assert (i[5] == -1).all() and (s[5] == -np.finfo(np.float32).max).all()
+        assert i[6].tolist() == [1, 2, 5, 6, 8, 11, 13, 16, 19, 20] == np.nonzero(Xc[:, 0] > 0)[0][:10].tolist()
+        assert (s[6] == np.inf).all()
     # an infinite component in the matrix: the statistics are not finite, the pass is not taken at all
     Xi = Xc.copy()
     Xi[100, 5] = np.inf

@@ -215,6 +215,64 @@ def test_dense_two_level_topk_equals_full_score_matrix(nat, monkeypatch):
 
 
 
+def _two_level_and_full(nat, monkeypatch, X, Q, k):
+    """(scores, ids) of the exact two-level form ("1") and of the full score matrix ("0")."""
+    monkeypatch.setenv("AMDR_DENSE_HI", "0")
+    out = {}
+    for flag in ("1", "0"):
+        monkeypatch.setenv("AMDR_DENSE_TWO_LEVEL", flag)
+        idx = nat.DenseIndex(X)
+        assert ("two-level" in idx.plan_info(len(Q), k)) == (flag == "1")
+        out[flag] = idx.search(Q, k)
+        idx.close()
+    return out
+
+
+@pytest.mark.parametrize("n, nq, k", [(2100, 100, 10), (20000, 7, 256)], ids=["remainder-pass-of-4", "k-256"])
+def test_dense_two_level_per_query_tile_lists(nat, monkeypatch, n, nq, k):
+    """Each query re-scores its OWN k tiles: a pass of 96 queries and a remainder of 4 (below the batch minimum of 5);
+    lists of 256 tiles, more than a tile has rows, ranked by the four-wave final top-k.  Same ids, same score bits as
+    the full score matrix."""
+    rng = np.random.default_rng(93)
+    X, Q = unit_rows(rng, n, 64), unit_rows(rng, nq, 64)
+    out = _two_level_and_full(nat, monkeypatch, X, Q, k)
+    assert np.array_equal(out["1"][1], out["0"][1])
+    assert np.array_equal(out["1"][0].view(np.uint32), out["0"][0].view(np.uint32))
+    assert (out["1"][1] >= 0).all()
+
+
+def test_dense_two_level_ragged_last_tile_wins(nat, monkeypatch):
+    """n = 64 k + 1: the last tile holds ONE row and every query equals it.  The tile kernels read the 31 rows past
+    the end as copies of that row: none of them may come back."""
+    rng = np.random.default_rng(94)
+    k, n = 3, 64 * 3 + 1
+    X = unit_rows(rng, n, 64)
+    Q = np.repeat(X[n - 1:n], 5, axis=0)
+    out = _two_level_and_full(nat, monkeypatch, X, Q, k)
+    s, i = out["1"]
+    assert (i[:, 0] == n - 1).all() and ((i >= 0) & (i < n)).all()
+    assert all(len(set(row.tolist())) == k for row in i)
+    assert np.array_equal(i, out["0"][1]) and np.array_equal(s.view(np.uint32), out["0"][0].view(np.uint32))
+
+
+def test_dense_two_level_nan_query_is_padding_whatever_the_batch(nat, monkeypatch):
+    """An all-NaN query comes back as padding (id -1, -FLT_MAX) also when the candidate tiles of the pass are pairwise
+    distinct and n is a multiple of 32 (5 tiles, k = 1, five queries with a tile each): what a query returns does not
+    depend on the other queries of its batch."""
+    rng = np.random.default_rng(95)
+    monkeypatch.setenv("AMDR_DENSE_TWO_LEVEL", "1")
+    monkeypatch.setenv("AMDR_DENSE_HI", "0")
+    X = unit_rows(rng, 160, 64)
+    rows = [40, 70, 100, 130]  # tiles 1-4
+    Q = np.concatenate([X[rows], np.full((1, 64), np.nan, dtype=np.float32)])
+    idx = nat.DenseIndex(X)
+    assert "two-level" in idx.plan_info(5, 1)
+    s, i = idx.search(Q, 1)
+    idx.close()
+    assert i[:4, 0].tolist() == rows and np.allclose(s[:4, 0], 1.0, atol=TOL)
+    assert i[4, 0] == -1 and s[4, 0] == -np.finfo(np.float32).max
+
+
 def test_dense_two_level_and_full_form_with_nan_scores(nat, monkeypatch):
     """NaN scores (a NaN in a chunk row) sort LAST in the full form (they still fill the tail of a top-k that has
     fewer than k real scores); the two-level form never returns them — a maximum drops NaN, so an all-NaN tile is no
