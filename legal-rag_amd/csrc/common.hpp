@@ -98,7 +98,7 @@ int dense_mfma_launch_topk(const DenseMfmaPlan& p, const float* S, long n, int n
 // ---- fp16 first pass of the two-level top-k on large matrices: dense_hi.hip ----
 bool dense_hi_supported(int d);
 int dense_hi_max_queries(int d);  // queries per scan: 64, 48 at d = 1 024
-int dense_stats_launch(const float* X, long n, int d, unsigned int* out2, hipStream_t st);
+int dense_stats_launch(const float* X, long n, int d, unsigned int* words, hipStream_t st);  // (words: dense_fp16.hpp)
 // round 4: the tail of a large search in four launches + two gated ones (dense_hi.hip, dense_mfma.hip)
 long dense_hi2_sample_stride(long n, int qtiles);
 long dense_hi2_sample_items(long n, int qtiles);
@@ -136,10 +136,11 @@ struct FuseTail {  // the fusion that follows the dense channel: parameters, the
   int32_t* out_mask;
   int32_t* out_count;
 };
-// first pass of the two-pass long-batch form (dense_small_hi.hip): the fp16 image and statistics of a short chunk matrix
-int dense_small_create_from(int device, const float* X, int64_t n, int d, amdr_dense_small_t** out);
+// first pass of the two-pass long-batch form (dense_small_hi.hip): the fp16 image of a short chunk matrix (stats: dense_fp16.hpp)
+struct DenseFp16Stats;
+int dense_small_create_from(int device, const float* X, int64_t n, int d, const DenseFp16Stats& stats,
+                            amdr_dense_small_t** out);
 int dense_small_reserve(amdr_dense_small_t* h, int nq_max);
-bool dense_small_usable(const amdr_dense_small_t* h);
 // second pass of the two-pass long-batch form (dense_tail.hip dense_hi_select_fuse_kernel): candidates inside the proven margin
 // of the approximate scores in S, exact dots, top-k (+ the fusion when t != nullptr)
 int dense_hi_select_launch(const FuseTail* t, int q0, const float* S, long ldS, long n, int m, int kd, const float* X,
@@ -181,6 +182,7 @@ std::mutex& bm25_mutex(amdr_bm25_t* h);
 int dense_device_of(const amdr_dense_t* h);
 // the resident chunk matrix of a dense handle (graph.hip re-scores walked articles against it)
 void dense_matrix(const amdr_dense_t* h, const float** X, long* n, int* d);
+const DenseFp16Stats& dense_fp16_stats_of(const amdr_dense_t* h);  // its statistics of that matrix
 
 // ---- long-batch dense path: dense_panel.hip (panel of chunk rows shared by a block through LDS) ----
 struct DensePanelPlan {

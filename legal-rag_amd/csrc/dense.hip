@@ -11,6 +11,7 @@
 // = n*d*4 per pass, flops = 2*n*d*NQ.
 #include "common.hpp"
 #include "dense_dot.hpp"
+#include "dense_fp16.hpp"
 #include "topk.hpp"
 
 #include <algorithm>
@@ -269,11 +270,10 @@ struct amdr_dense {
   // therefore never scribble over the score matrix of a search_batch still in flight on another
   // stream.  "_device" calls on ONE handle from SEVERAL streams remain the caller's to order.
   DevBuf part[2], smat[2], aux[2], qbuf, sbuf, ibuf;  // aux: the per-query tile lists of the two-level top-k
-  // matrix statistics for the fp16 first pass of large scans (dense_hi.hip): kept up to date by create / add
+  // matrix statistics for both fp16 first passes (dense_fp16.hpp: the device words, among them the large scan's counters,
+  // and the record; finite only if d is supported): kept up to date by create / add
   DevBuf stats;
-  float x_scale = 1.f;       // power of two: |x| * x_scale < 1 for every component
-  float row_norm_max = 0.f;  // largest row L2 norm
-  bool hi_ok = false;        // d supported and both statistics finite
+  DenseFp16Stats fp16;
   int64_t hi_queries = 0;    // queries that went through the fp16 first pass (amdr_dense_hi_counters)
   // adaptive width of the candidate cut: level l re-scores k + max(k, kHiExtra[l]) + 1 tiles per query; a handle whose
   // queries the rounding bound keeps failing to resolve moves up a level, and at the top level gives the pass up
@@ -473,7 +473,7 @@ Route dense_route(const amdr_dense* h, const DensePins& pins, int nq, int k) {
     const long tiles = (n + 31) / 32;
     const int kc_max = hi_kc_max(k);
     // kc_max <= AMDR_MAX_K: k <= 127; tiles < 2^26: (query, tile) packed in 32 bits of a candidate entry
-    r.hi = pins.hi != '0' && h->hi_ok && kc_max <= AMDR_MAX_K && tiles < (1l << 26) &&
+    r.hi = pins.hi != '0' && h->fp16.large_scan_ok() && kc_max <= AMDR_MAX_K && tiles < (1l << 26) &&
            (pins.hi == '1' ? tiles >= 2L * kc_max : dense_stream_nontemporal(n, h->d) && tiles >= 64L * kc_max);
     if (r.hi && !h->hi_off) {
       r.form = Form::Hi;
@@ -503,7 +503,7 @@ bool small_hi_shape(const amdr_dense* h, const DensePins& pins, int m, int k, in
   // overflow on most queries and the query re-scores its whole row (37 376 queries on 1 024 x 768: k = 12 230 against 517 us
   // for the exact form, k = 14 465 against 536, k = 20 2 099 against 619)
   return pins.small_hi && m >= pins.small_hi_min && h->n >= 1 && h->n <= 1024 && h->d >= 128 && h->d <= 1024 &&
-         h->d % 128 == 0 && k >= 1 && k <= 12 && k + kb <= 32;
+         h->d % 128 == 0 && k >= 1 && k <= 12 && k + kb <= 32 && h->fp16.short_corpus_ok();
 }
 // One pass of m queries of the forms that go through a score matrix S[q][row] (Batched, RowWaves; p = its plan): who
 // writes S, who ranks it.  What depends on run-time state (small_hi_ready: image present, stream capturing) is decided
@@ -717,16 +717,16 @@ int topk_pass(const DenseMfmaPlan& p, const float* S, long cols, int m, int k, D
   return launch_merge(partb.as<C32>(), p.slabs, m, k, p.cap, out_scores, out_ids, st);
 }
 
-// the image and the workspaces of the fp16 two-pass form; false: not available now (creation failed before, non-finite
-// matrix, or a stream is capturing and nothing was reserved) — the caller takes the exact form
+// the image and the workspaces of the fp16 two-pass form; false: not available now (allocating the image failed before, or
+// a stream is capturing and nothing was reserved) — the caller takes the exact form
 bool small_hi_ready(amdr_dense* h, int m, hipStream_t st) {
   if (h->small_failed) return false;
   hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
   const bool capturing = st && hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
   if (!h->small) {
     if (capturing) return false;
-    if (dense_small_create_from(h->device, h->X, h->n, h->d, &h->small) != AMDR_OK || !dense_small_usable(h->small)) {
-      h->small_failed = true;  // (a matrix the fp16 scale range cannot hold stays on the exact form)
+    if (dense_small_create_from(h->device, h->X, h->n, h->d, h->fp16, &h->small) != AMDR_OK) {
+      h->small_failed = true;
       return false;
     }
   }
@@ -842,7 +842,7 @@ int hi2_pass(amdr_dense* h, int ws, const float* Qc, int m, int k, int kc, float
   int* flag = reinterpret_cast<int*>(ax + p.off_flag);  // (reset by this pass's own tau kernel)
   unsigned int* stats = h->stats.as<unsigned int>();
   int rc;
-  if ((rc = dense_hi2_launch_sample(h->X, (long)h->n, h->d, Qc, m, p.qtiles, MT, st, h->x_scale))) return rc;
+  if ((rc = dense_hi2_launch_sample(h->X, (long)h->n, h->d, Qc, m, p.qtiles, MT, st, h->fp16.x_scale))) return rc;
   if ((rc = dense_hi2_launch_tau(MT, (long)h->n, h->d, m, p.qtiles, kc, tau, qcount, flag, stats, st))) return rc;
   {  // the scan: ONE launch over all query tiles of the pass (the launch the profiling events bracket);
      // AMDR_DENSE_HI_SCANS=split: one launch per query tile (A/B, tests)
@@ -853,14 +853,14 @@ int hi2_pass(amdr_dense* h, int ws, const float* Qc, int m, int k, int kc, float
       const int q0 = y * qt, mq = split ? (m - q0 < qt ? m - q0 : qt) : m;
       rc = profiled(h, st, [&] {
         return dense_hi2_launch_emit(h->X, (long)h->n, h->d, Qc + (size_t)q0 * h->d, mq, tau + q0, qlist + (size_t)q0 * p.qcap,
-                                     qcount + q0, p.qcap, st, h->x_scale, split ? 1 : p.qtiles);
+                                     qcount + q0, p.qcap, st, h->fp16.x_scale, split ? 1 : p.qtiles);
       });
       if (rc) return rc;
     }
   }
   h->hi_queries += m;
   h->hi_passes += p.qtiles;
-  if ((rc = dense_hi2_launch_select(qlist, qcount, p.qcap, m, kc, k, Qc, h->d, h->row_norm_max, h->x_scale, p.tiles, list,
+  if ((rc = dense_hi2_launch_select(qlist, qcount, p.qcap, m, kc, k, Qc, h->d, h->fp16.row_norm_max, h->fp16.x_scale, p.tiles, list,
                                     count, unres, flag, stats + 2, st)))
     return rc;
   // behind the flag: the exact first pass of the batch and, for the queries the bound did not resolve, their k tiles
@@ -943,15 +943,14 @@ int check_search_args(const amdr_dense* h, const void* Q, int nq, int k, const v
   return AMDR_OK;
 }
 
-// Statistics of rows [row0, row0 + rows) folded into the handle's (max |component|, max row norm): what the fp16 first
-// pass of large scans scales by and bounds its error with.  Synchronous (create / add are).
+// Statistics of rows [row0, row0 + rows) folded into the handle's: what the fp16 first passes scale by and bound their
+// error with.  Synchronous (create / add are).
 int update_stats(amdr_dense* h, int64_t row0, int64_t rows) {
-  h->hi_ok = false;
+  h->fp16 = DenseFp16Stats();
   if (!dense_hi_supported(h->d)) return AMDR_OK;
-  // max |x|, max row norm, then the counters: unresolved queries, flagged passes, passes, pad
-  int rc = h->stats.ensure(8 * sizeof(unsigned int));
+  int rc = h->stats.ensure(kDenseStatWords * sizeof(unsigned int));
   if (rc) return rc;
-  if (row0 == 0) AMDR_HIP(hipMemsetAsync(h->stats.p, 0, 8 * sizeof(unsigned int), h->stream));
+  if (row0 == 0) AMDR_HIP(hipMemsetAsync(h->stats.p, 0, kDenseStatWords * sizeof(unsigned int), h->stream));
   if (!h->hi_host) {
     AMDR_HIP(hipHostMalloc((void**)&h->hi_host, 4 * sizeof(unsigned int), hipHostMallocDefault));
     h->hi_host[0] = h->hi_host[1] = h->hi_host[2] = 0u;
@@ -959,14 +958,10 @@ int update_stats(amdr_dense* h, int64_t row0, int64_t rows) {
   }
   if ((rc = dense_stats_launch(h->X + (size_t)row0 * h->d, (long)rows, h->d, h->stats.as<unsigned int>(), h->stream)))
     return rc;
-  float st[2] = {0.f, 0.f};
-  AMDR_HIP(hipMemcpyAsync(st, h->stats.p, sizeof(st), hipMemcpyDeviceToHost, h->stream));
+  unsigned int words[kDenseStatWords] = {};
+  AMDR_HIP(hipMemcpyAsync(words, h->stats.p, sizeof(words), hipMemcpyDeviceToHost, h->stream));
   AMDR_HIP(hipStreamSynchronize(h->stream));
-  int e = 0;
-  if (st[0] > 0.f && st[0] <= FLT_MAX) (void)frexpf(st[0], &e);
-  h->x_scale = ldexpf(1.f, -e);
-  h->row_norm_max = st[1];
-  h->hi_ok = st[0] <= FLT_MAX && st[1] <= FLT_MAX && e > -100 && e < 100;
+  h->fp16 = dense_fp16_stats(words);
   return AMDR_OK;
 }
 
@@ -985,6 +980,7 @@ int dense_small_raw(amdr_dense_t* h, int nq, DenseRaw* out) {
 }
 std::mutex& dense_mutex(amdr_dense_t* h) { return h->mu; }
 int dense_device_of(const amdr_dense_t* h) { return h->device; }
+const DenseFp16Stats& dense_fp16_stats_of(const amdr_dense_t* h) { return h->fp16; }
 void dense_matrix(const amdr_dense_t* h, const float** X, long* n, int* d) {
   *X = h->X;
   *n = (long)h->n;
@@ -1211,7 +1207,7 @@ int amdr_dense_workspace_plan(int64_t n, int32_t d, int32_t nq_max, int32_t k_ma
   amdr_dense h;  // shape only: no device is touched
   h.n = n;
   h.d = d;
-  h.hi_ok = dense_hi_supported(d);  // shape only: the statistics of a real matrix can only take the fp16 first pass away
+  h.fp16.finite = dense_hi_supported(d);  // shape only: the statistics of a real matrix can only take the fp16 first pass away
   const DensePins pins = read_pins();
   const Need res = reserve_need(&h, pins, nq_max, k_max), used = call_need(&h, dense_route(&h, pins, nq, k), nq, k);
   out6[0] = (int64_t)res.smat, out6[1] = (int64_t)res.part, out6[2] = (int64_t)res.aux;
@@ -1291,7 +1287,7 @@ int amdr_dense_hi_counters(amdr_dense_t* h, int64_t* out6) {
   }
   const DensePins pins = read_pins();
   out6[2] = pins.hi_level >= 0 ? pins.hi_level : h->hi_level;
-  out6[3] = h->hi_ok && !h->hi_off ? 1 : 0;
+  out6[3] = h->fp16.large_scan_ok() && !h->hi_off ? 1 : 0;
   out6[4] = h->hi_passes;
   return AMDR_OK;
 }

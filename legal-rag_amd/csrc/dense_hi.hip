@@ -6,7 +6,7 @@
 // peak and cannot hold more than 32 queries (a 96-KiB fp32 query tile in LDS).  The first pass only has to find
 // candidate tiles, and the second pass is exact — so here it runs on v_mfma_f32_32x32x16_f16 with fp16 ROUNDINGS of
 // both operands (hi parts, csrc/maxsim.hip): 16x the matrix rate, a 96-KiB tile now holds 64 queries, the scan is
-// bound by HBM alone.  Every approximate tile maximum lies within a proven eps of the exact one (dense_hi_select_kernel
+// bound by HBM alone.  Every approximate tile maximum lies within a proven eps of the exact one (dense_fp16.hpp
 // states the bound), the candidate cut is widened by it (dense.hip hi2_pass), the re-scoring is exact fp32 in the same
 // MFMA k order: ids and score bits are those of the exact forms.  A query whose
 // cut the bound does not separate (mass near-ties) raises a device flag and the exact first pass runs for that batch
@@ -22,6 +22,7 @@
 // lets only the maxima that reach the threshold leave the kernel, as entries of per-query candidate lists.  Writing all
 // 20 M maxima of a 10 M-row scan cost 0.3-0.9 ms of 5 whatever the layout.
 #include "common.hpp"
+#include "dense_fp16.hpp"
 #include "topk.hpp"
 
 #include <cfloat>
@@ -158,9 +159,7 @@ __device__ __forceinline__ void hi_tilemax_pass(const float* __restrict__ X, lon
         m = fmaxf(m, __uint_as_float(lane_xor<8>(__float_as_uint(m))));
         m = fmaxf(m, __uint_as_float(lane_xor<16>(__float_as_uint(m))));
         m = fmaxf(m, __uint_as_float(lane_xor<32>(__float_as_uint(m))));
-        int e = 0;
-        if (m > 0.f && m <= FLT_MAX) (void)frexpf(m, &e);
-        const float sc = ldexpf(1.f, -e);
+        const float sc = dense_fp16_scale(dense_fp16_exp(m));  // (the scale dense_hi_select_kernel states the bound in)
         if (qi < QT) {
 #pragma unroll
           for (int it = 0; it < ITS; ++it) {
@@ -345,16 +344,19 @@ __global__ __launch_bounds__(kHiWaves * 64) void dense_hi_tilemax_kernel(const f
   }
 }
 
-// largest |component| and largest row L2 norm of a matrix (float bits; both are non-negative)
+// the statistics of a matrix folded into the words of dense_fp16.hpp (float bits: both maxima are non-negative; fmaxf
+// drops NaN components and the norms of rows that hold one — the third word says that there was one)
 __global__ __launch_bounds__(256) void dense_stats_kernel(const float* __restrict__ X, long n, int d,
-                                                          unsigned int* __restrict__ out2) {
+                                                          unsigned int* __restrict__ words) {
   const int lane = threadIdx.x & 63;
   const long wv = ((long)blockIdx.x * 256 + threadIdx.x) >> 6, nw = (long)gridDim.x * 4;
   float amax = 0.f, nmax = 0.f;
+  bool nan = false;
   for (long r = wv; r < n; r += nw) {
     float ss = 0.f;
     for (int k = lane; k < d; k += 64) {
       const float x = X[(size_t)r * d + k];
+      nan |= x != x;
       amax = fmaxf(amax, fabsf(x));
       ss += x * x;
     }
@@ -364,9 +366,11 @@ __global__ __launch_bounds__(256) void dense_stats_kernel(const float* __restric
   }
 #pragma unroll
   for (int sft = 1; sft < 64; sft <<= 1) amax = fmaxf(amax, __shfl_xor(amax, sft));
+  nan = __any(nan);
   if (lane == 0) {
-    atomicMax(out2, __float_as_uint(amax != amax ? INFINITY : amax));
-    atomicMax(out2 + 1, __float_as_uint(nmax != nmax ? INFINITY : nmax));
+    atomicMax(words, __float_as_uint(amax));
+    atomicMax(words + 1, __float_as_uint(nmax));
+    if (nan) atomicOr(words + kDenseStatNan, 1u);
   }
 }
 
@@ -436,12 +440,12 @@ static int launch_hi_d(const float* X, long n, int d, const float* Q, int nq, fl
   }
 }
 
-// max |component| and max row norm of X[row0 .. row0 + n): out2 must hold two zeroed unsigned ints
-int dense_stats_launch(const float* X, long n, int d, unsigned int* out2, hipStream_t st) {
+// the statistics of X's n rows folded into `words` (kDenseStatWords of them, zeroed before the first rows)
+int dense_stats_launch(const float* X, long n, int d, unsigned int* words, hipStream_t st) {
   if (n <= 0) return AMDR_OK;
   long blocks = (n + 3) / 4;  // a wave per row and round
   if (blocks > 2048) blocks = 2048;
-  hipLaunchKernelGGL(dense_stats_kernel, dim3((unsigned)blocks), dim3(256), 0, st, X, n, d, out2);
+  hipLaunchKernelGGL(dense_stats_kernel, dim3((unsigned)blocks), dim3(256), 0, st, X, n, d, words);
   AMDR_HIP(hipGetLastError());
   return AMDR_OK;
 }
@@ -527,13 +531,7 @@ __device__ __forceinline__ int select_list(const C32* __restrict__ src, unsigned
 // (T_k = the k-th largest approximate maximum): the k tiles on top have exact maxima >= T_k - eps, so the k-th best
 // score s_k >= T_k - eps, and a tile holding a row >= s_k has an approximate maximum >= T_k - 2 eps.
 //
-// eps_q, in scaled units (x' = x * 2^-ex, |x'| < 1; q' = q * 2^-eq, |q'| < 1): per component the fp16 rounding is
-// |dx'| <= 2^-11 |x'| + 2^-25 (the second term covers fp16's subnormal range), the same for q'.  Hence
-//   |x^ . q^ - x' . q'| <= (2^-10 + 2^-22) |x'| |q'| + 2^-25 (|q'|_1 + |x'|_1) (1 + 2^-11) <= ... + d 2^-24 (1 + 2^-11)
-// (the products of two fp16 values are exact in the MFMA's fp32, the accumulation of d of them adds d 2^-24 |x'| |q'|;
-// so does the accumulation inside the exact kernel this pass is compared with).  |x'| <= R * 2^-ex with R the largest
-// row norm.  The comparison only holds if the exact fp32 scores neither overflow nor sink into fp32's subnormal
-// range: |ex + eq| <= 100 is required, else the flag is raised.
+// eps_q and the scale range |ex + eq| <= 100 it holds in (else the flag is raised): dense_fp16.hpp.
 __global__ __launch_bounds__(256) void dense_hi_select_kernel(const C32* __restrict__ qlist,
                                                               const unsigned int* __restrict__ qcount, unsigned int qcap,
                                                               int kc1, int k, int tcap, const float* __restrict__ Q, int d,
@@ -592,7 +590,7 @@ __global__ __launch_bounds__(256) void dense_hi_select_kernel(const C32* __restr
     block_combine_topk(tk, lists, tcap, 4, wave, lane, cnts);
     if (wave != 0) return;
   }
-  // ---- the rounding bound of this query (stated above the kernel)
+  // ---- the rounding bound of this query (dense_fp16.hpp)
   float amax = 0.f;
   bool nan = false;
   for (int j = lane; j < d; j += 64) {
@@ -603,9 +601,8 @@ __global__ __launch_bounds__(256) void dense_hi_select_kernel(const C32* __restr
 #pragma unroll
   for (int sft = 1; sft < 64; sft <<= 1) amax = fmaxf(amax, __uint_as_float(lane_xor_sw(__float_as_uint(amax), sft)));
   nan = __any(nan);
-  int e = 0;
-  if (amax > 0.f && amax <= FLT_MAX) (void)frexpf(amax, &e);
-  const float sc = ldexpf(1.f, -e);
+  const int e = dense_fp16_exp(amax);
+  const float sc = dense_fp16_scale(e);
   float ss = 0.f;
   for (int j = lane; j < d; j += 64) {
     const float x = Q[(size_t)q * d + j] * sc;
@@ -613,9 +610,8 @@ __global__ __launch_bounds__(256) void dense_hi_select_kernel(const C32* __restr
   }
 #pragma unroll
   for (int sft = 1; sft < 64; sft <<= 1) ss += __uint_as_float(lane_xor_sw(__float_as_uint(ss), sft));
-  const float rel = 1.125f * (9.765625e-4f + 2.4e-7f + 2.f * (float)(d + 8) * 5.9604645e-8f);
-  const float eps = rel * sqrtf(ss) * (row_norm_max * x_scale) + 1.125f * (float)d * 5.9604645e-8f;
-  const bool bad = nan || !(amax <= FLT_MAX) || !(eps == eps) || e + x_exp > 100 || e + x_exp < -100;
+  const float eps = dense_fp16_eps_scaled(d, sqrtf(ss), row_norm_max * x_scale);
+  const bool bad = nan || !(amax <= FLT_MAX) || !(eps == eps) || !dense_fp16_range_large_scan(x_exp, e);
   const int cnt = tk.cnt;
   const long want = n_tiles < kc1 ? n_tiles : (long)kc1;
   bool raise = bad || have > qcap || cnt < want;  // an overflowed list or too few candidates (NaN threshold): the exact chain decides
@@ -706,9 +702,7 @@ int dense_hi2_launch_emit(const float* X, long n, int d, const float* Q, int nq,
 int dense_hi2_launch_select(const void* qlist, const unsigned int* qcount, size_t qcap, int m, int kc, int k, const float* Q,
                             int d, float row_norm_max, float x_scale, long n_tiles, int* list, int* count, int* unres,
                             int* flag, unsigned int* unresolved, hipStream_t st) {
-  int x_exp = 0;
-  (void)frexpf(x_scale, &x_exp);  // x_scale = 2^-ex = 0.5 * 2^(1 - ex)
-  x_exp = 1 - x_exp;
+  const int x_exp = 1 - dense_fp16_exp(x_scale);  // x_scale = 2^-ex = 0.5 * 2^(1 - ex)
   const int tcap = topk_cap(kc);
   const size_t lds = (size_t)4 * tcap * sizeof(C32) + 4 * sizeof(int);
   hipLaunchKernelGGL(dense_hi_select_kernel, dim3(m), dim3(256), lds, st, (const C32*)qlist, qcount, (unsigned int)qcap, kc, k,

@@ -5,8 +5,8 @@
 // the chunks within 2 eps of a query's k-th best (dense_tail.hip dense_hi_select_fuse_kernel; dense.hip run_search_batched takes
 // the pair from 4 096 queries per launch).
 //
-//   amdr_dense_small_create        statistics of the chunk matrix (largest component -> power-of-two scale, largest row
-//                                  norm) and its fp16 image  Xh[K slice][row][128 halves]  (rows padded to 32, zero)
+//   amdr_dense_small_create        the fp16 image of the chunk matrix  Xh[K slice][row][128 halves]  (rows padded to 32,
+//                                  zero), scaled by the dense handle's statistics of it (DenseFp16Stats)
 //   dsh_split_queries_kernel       per query: power-of-two scale, the proven bound, fp16 image in MFMA FRAGMENT order
 //                                  Qh[query tile of 32][K slice][k step][lane][8 halves] — one coalesced 1-KiB load per
 //                                  fragment in the scores kernel
@@ -16,15 +16,13 @@
 //                                  fragments per slice (64 VGPRs) and keeps 4 x 2 accumulator tiles (128 VGPRs) across
 //                                  the 6 slices of d = 768 — 32 queries x 768 dims of fragments (192 VGPRs for ONE
 //                                  tile) do not fit a wave, which is what makes this shape different from MaxSim's.
-// Error bound (dense_hi.hip, same arithmetic: fp16 roundings of both scaled operands, exact products, fp32 accumulation):
-//   |approx - exact| <= eps_q = [1.125 (2^-10 + 2^-22 + 2 (d + 8) 2^-24) |q'| R' + 1.125 d 2^-24] / (x_scale q_scale)
-// in the units of the exact score (q' = q q_scale, R' = largest row norm x x_scale).
+// The error bound eps_q (the large scan's: the same arithmetic), the scales and the statistics: dense_fp16.hpp.
 #include "common.hpp"
+#include "dense_fp16.hpp"
 
 #include <cfloat>
 #include <cmath>
 #include <cstdlib>
-#include <cstring>
 #include <new>
 
 namespace amdr {
@@ -40,35 +38,6 @@ constexpr int kDsG = 4;      // 32-row chunk tiles per block
 constexpr int kDsStage = 32 * 256;
 
 __device__ __forceinline__ int ds_hi_off(int row, int slot) { return row * 256 + ((slot ^ (row & 15)) << 4); }
-
-// ---- statistics of the chunk matrix: out[0] = largest |component|, out[1] = largest row norm (as uint bit patterns of
-// non-negative floats: ordered like the floats; a NaN poisons both through 0x7fc00000 > every finite pattern)
-__global__ __launch_bounds__(256) void dsh_stats_kernel(const float* __restrict__ X, long n, int d, unsigned int* __restrict__ out) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const long row = (long)blockIdx.x * 4 + wave;
-  if (row >= n) return;
-  float amax = 0.f, ss = 0.f;
-  bool nan = false;
-  for (int j = lane * 4; j < d; j += 256) {
-    const ds4f v = *reinterpret_cast<const ds4f*>(X + (size_t)row * d + j);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      nan |= v[e] != v[e];
-      amax = fmaxf(amax, fabsf(v[e]));
-      ss += v[e] * v[e];
-    }
-  }
-#pragma unroll
-  for (int sft = 1; sft < 64; sft <<= 1) {
-    amax = fmaxf(amax, __shfl_xor(amax, sft));
-    ss += __shfl_xor(ss, sft);
-  }
-  nan = __any(nan);
-  if (lane == 0) {
-    atomicMax(out, nan ? 0x7fc00000u : __float_as_uint(amax));
-    atomicMax(out + 1, nan ? 0x7fc00000u : __float_as_uint(sqrtf(ss)));
-  }
-}
 
 // ---- the chunk image: Xh[slice][row][slot of 8 halves] = fp16(x * x_scale), one thread per (row, 8 components)
 __global__ __launch_bounds__(256) void dsh_image_kernel(const float* __restrict__ X, long n, int d, float x_scale,
@@ -126,9 +95,8 @@ __global__ __launch_bounds__(256) void dsh_split_queries_kernel(const float* __r
     amax = fmaxf(amax, __shfl_xor(amax, sft));
     nan |= __shfl_xor((int)nan, sft) != 0;
   }
-  int e2 = 0;
-  if (amax > 0.f && amax <= FLT_MAX) (void)frexpf(amax, &e2);  // amax = f 2^e2, f in [0.5, 1)
-  const float sc = ldexpf(1.f, -e2);
+  const int e2 = dense_fp16_exp(amax);
+  const float sc = dense_fp16_scale(e2);
   float ss = 0.f;
 #pragma unroll
   for (int i = 0; i < 16; ++i)
@@ -152,11 +120,10 @@ __global__ __launch_bounds__(256) void dsh_split_queries_kernel(const float* __r
     *reinterpret_cast<ds8h*>(Qh + ((((size_t)tile * ks + kc) * 8 + st) * 64 + (r32 + 32 * hh)) * 16) = y;
   }
   if (sub == 0) {
-    const bool bad = nan || !(amax <= FLT_MAX) || e2 > 100 || e2 < -100;
+    const bool bad = nan || !(amax <= FLT_MAX) || !dense_fp16_range_short_corpus(e2);
     const float us = ldexpf(1.f, e2);
     q_unscale[q] = us;
-    const float rel = 1.125f * (9.765625e-4f + 2.4e-7f + 2.f * (float)(d + 8) * 5.9604645e-8f);
-    const float e_q = (rel * sqrtf(ss) * r_scaled + 1.125f * (float)d * 5.9604645e-8f) * x_unscale * us;
+    const float e_q = dense_fp16_eps_scaled(d, sqrtf(ss), r_scaled) * x_unscale * us;  // (the bound: dense_fp16.hpp)
     if (eps) eps[q] = bad ? __uint_as_float(0x7fc00000u) : e_q;  // NaN: no bound for this query
   }
 }
@@ -297,8 +264,7 @@ struct amdr_dense_small {
   const float* X = nullptr;
   int64_t n = 0, n_pad = 0;
   int d = 0;
-  float x_scale = 1.f, row_norm_max = 0.f;
-  bool ok = false;
+  DenseFp16Stats stats;  // the dense handle's, of X as it was at creation
   DevBuf img, ws;
   std::mutex mu;
 };
@@ -313,43 +279,26 @@ int dense_small_reserve(amdr_dense_small_t* h, int nq_max) {
   std::lock_guard<std::mutex> g(h->mu);
   return h->ws.ensure(dsh_ws_bytes(h->d, nq_max, nullptr));
 }
-bool dense_small_usable(const amdr_dense_small_t* h) { return h && h->ok; }
-// (the caller has set the device; X stays the caller's)
-int dense_small_create_from(int device, const float* X, int64_t n, int d, amdr_dense_small_t** out) {
+// (the caller has set the device; X stays the caller's; stats: of X)
+int dense_small_create_from(int device, const float* X, int64_t n, int d, const DenseFp16Stats& stats,
+                            amdr_dense_small_t** out) {
   *out = nullptr;
   AMDR_REQUIRE(n >= 1 && d >= 128 && d <= 1024 && d % 128 == 0,
                "dense_small_create: needs >= 1 row and d a multiple of 128 in [128, 1024] (d=%d)", d);
   amdr_dense_small* h = new (std::nothrow) amdr_dense_small();
   if (!h) return fail(AMDR_ENOMEM, "dense_small_create: host alloc");
-  int rc = AMDR_OK;
   h->device = device;
   h->X = X;
   h->n = n;
   h->d = d;
   h->n_pad = (n + 31) / 32 * 32;
-  unsigned int* st = nullptr;
-  unsigned int host[2] = {0u, 0u};
+  h->stats = stats;
   const size_t img_bytes = (size_t)(h->d / 128) * h->n_pad * 256;
-  rc = h->img.ensure(img_bytes);
-  if (!rc && hipMalloc((void**)&st, 2 * sizeof(unsigned int)) != hipSuccess) rc = fail(AMDR_EHIP, "dense_small_create: alloc");
+  int rc = h->img.ensure(img_bytes);
   if (!rc) {
-    (void)hipMemset(st, 0, 2 * sizeof(unsigned int));
-    hipLaunchKernelGGL(dsh_stats_kernel, dim3(ceil_div(h->n, 4)), dim3(256), 0, nullptr, h->X, (long)h->n, h->d, st);
-    if (hipMemcpy(host, st, sizeof(host), hipMemcpyDeviceToHost) != hipSuccess) rc = fail(AMDR_EHIP, "dense_small_create: stats");
-  }
-  if (st) (void)hipFree(st);
-  if (!rc) {
-    float amax, rmax;
-    memcpy(&amax, &host[0], 4);
-    memcpy(&rmax, &host[1], 4);
-    int e = 0;
-    if (amax > 0.f && amax <= FLT_MAX) (void)frexpf(amax, &e);
-    h->x_scale = ldexpf(1.f, -e);
-    h->row_norm_max = rmax;
-    h->ok = amax <= FLT_MAX && rmax <= FLT_MAX && e > -100 && e < 100;  // (NaN compares false)
     (void)hipMemset(h->img.p, 0, img_bytes);
     hipLaunchKernelGGL(dsh_image_kernel, dim3(ceil_div(h->n * (h->d / 8), 256)), dim3(256), 0, nullptr, h->X, (long)h->n, h->d,
-                       h->x_scale, h->img.as<unsigned char>(), (long)h->n_pad);
+                       h->stats.x_scale, h->img.as<unsigned char>(), (long)h->n_pad);
     if (hipDeviceSynchronize() != hipSuccess || hipGetLastError() != hipSuccess) rc = fail(AMDR_EHIP, "dense_small_create: image");
   }
   if (rc) {
@@ -367,12 +316,13 @@ extern "C" {
 int amdr_dense_small_create(amdr_dense_t* dense, amdr_dense_small_t** out) {
   AMDR_REQUIRE(dense && out, "dense_small_create: null");
   *out = nullptr;
-  DenseRaw raw;
-  int rc;
+  const float* X;
+  long n;
+  int d;
   std::lock_guard<std::mutex> g(dense_mutex(dense));
   AMDR_HIP(hipSetDevice(dense_device_of(dense)));
-  if ((rc = dense_small_raw(dense, 1, &raw))) return rc;
-  return dense_small_create_from(dense_device_of(dense), raw.X, raw.n, raw.d, out);
+  dense_matrix(dense, &X, &n, &d);
+  return dense_small_create_from(dense_device_of(dense), X, n, d, dense_fp16_stats_of(dense), out);
 }
 
 int amdr_dense_small_destroy(amdr_dense_small_t* h) {
@@ -392,7 +342,7 @@ int amdr_dense_small_approx_device(amdr_dense_small_t* h, const float* Q_dev, in
   AMDR_REQUIRE(Q_dev && S_dev, "dense_small_approx: null buffer");
   AMDR_REQUIRE(ldS >= h->n_pad && ldS % 4 == 0, "dense_small_approx: ldS=%lld must be a multiple of 4 and >= %lld (rows padded to 32)",
                (long long)ldS, (long long)h->n_pad);
-  AMDR_REQUIRE(h->ok, "dense_small_approx: the chunk matrix holds non-finite values or is out of the fp16 scale range");
+  AMDR_REQUIRE(h->stats.short_corpus_ok(), "dense_small_approx: the chunk matrix holds non-finite values or is out of the fp16 scale range");
   std::lock_guard<std::mutex> g(h->mu);
   AMDR_HIP(hipSetDevice(h->device));
   hipStream_t st = (hipStream_t)stream;
@@ -403,13 +353,13 @@ int amdr_dense_small_approx_device(amdr_dense_small_t* h, const float* Q_dev, in
   unsigned char* Qh = h->ws.as<unsigned char>();
   float* q_unscale = reinterpret_cast<float*>(Qh + qh_bytes);
   hipLaunchKernelGGL(dsh_split_queries_kernel, dim3(ceil_div(nq, 32)), dim3(256), 0, st, Q_dev, nq, h->d, Qh, q_unscale,
-                     h->row_norm_max * h->x_scale, 1.f / h->x_scale, eps_dev);
+                     h->stats.row_norm_max * h->stats.x_scale, 1.f / h->stats.x_scale, eps_dev);
   constexpr int NBUF = 4;
   AMDR_HIP(hipFuncSetAttribute((const void*)dsh_scores_kernel<NBUF>, hipFuncAttributeMaxDynamicSharedMemorySize, NBUF * kDsStage));
   const int qgroups8 = ceil_div(ceil_div(n_qtiles, 2 * kDsWaves), 8) * 8;
   hipLaunchKernelGGL((dsh_scores_kernel<NBUF>), dim3(qgroups8 * ceil_div(n_tiles, kDsG)), dim3(kDsWaves * 64),
                      NBUF * kDsStage, st, h->img.as<unsigned char>(), (long)h->n_pad, n_tiles, ks, Qh, nq, q_unscale,
-                     1.f / h->x_scale, S_dev, (long)ldS);
+                     1.f / h->stats.x_scale, S_dev, (long)ldS);
   AMDR_HIP(hipGetLastError());
   return AMDR_OK;
 }

@@ -1,8 +1,8 @@
 """Worst-case rounding inputs for the fp16 first passes, and a CPU model of what those passes compute.
 
 Three first passes pick candidates on fp16 roundings of power-of-two-scaled operands and trust a proven per-query bound
-eps to decide what to re-score exactly (csrc/dense_small_hi.hip dsh_split_queries_kernel, csrc/dense_hi.hip
-dense_hi_check_kernel / dense_hi_select_kernel, csrc/maxsim.hip maxsim_select_kernel).  Gaussian test vectors round
+eps to decide what to re-score exactly (the dense bound of csrc/dense_fp16.hpp, called by csrc/dense_small_hi.hip
+dsh_split_queries_kernel and csrc/dense_hi.hip dense_hi_select_kernel; csrc/maxsim.hip maxsim_select_kernel).  Gaussian test vectors round
 like a random walk and sit far below those bounds; the data built here rounds every component by >= 0.45 fp16 ulp in a
 chosen direction, so that the first-pass error comes within a constant factor of eps and a bound that is too small (a
 dropped factor, a flushed subnormal, a truncating conversion) changes what the kernels return.
@@ -25,7 +25,7 @@ OFF_Q = 4096        # rounding offsets are multiples of 1/4096 ulp: the scaled v
 # scales and bounds, restated from the kernels (fp64)
 
 def pow2_scale(amax) -> np.ndarray:
-    """2^-e with amax = f 2^e, f in [0.5, 1) (frexpf); 1 for amax == 0 — dsh_split_queries_kernel / dense_stats."""
+    """2^-e with amax = f 2^e, f in [0.5, 1) (frexpf); 1 for amax == 0 — dense_fp16.hpp dense_fp16_exp / dense_fp16_scale."""
     amax = np.asarray(amax, dtype=np.float64)
     _, e = np.frexp(np.where(amax > 0, amax, 1.0))
     return np.where(amax > 0, np.ldexp(1.0, -e), 1.0)
@@ -41,7 +41,7 @@ def dense_scales(X: np.ndarray, Q: np.ndarray):
 
 
 def dense_rel(d: int) -> float:
-    """The relative factor of dsh_split_queries_kernel / dense_hi_check_kernel / dense_hi_select_kernel."""
+    """The relative factor of dense_fp16.hpp dense_fp16_eps_scaled, restated (this module is the independent oracle)."""
     return 1.125 * (9.765625e-4 + 2.4e-7 + 2.0 * (d + 8) * 5.9604645e-8)
 
 

@@ -7,7 +7,7 @@ instead of the random-walk ~1/5 that Gaussian vectors give.
   components that round away from zero are where a truncating conversion leaves the model; cases with
   fp16-subnormal operands (one outlier row setting the matrix scale among them) show whether the matrix instruction
   honours subnormal inputs — a flushing MFMA exceeds eps there at d >= 768 and leaves the model at every d.
-- The two-pass long-batch step, the dense_hi large scan (both tails, i.e. both copies of the bound) and the MaxSim
+- The two-pass long-batch step, the dense_hi large scan (both callers of the one bound, csrc/dense_fp16.hpp) and the MaxSim
   two-pass top-k (every pass-1 variant, eps from norm_sum or computed by maxsim_select_kernel) on inversion corpora: the
   fp16 pass ranks competitors above the exact top-k, only the bound keeps the latter among the candidates; ids must
   equal the fp64 oracle's and the exact forms' (ids and score bits), with the fast paths — not a fallback — deciding."""
