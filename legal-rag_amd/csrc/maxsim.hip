@@ -228,14 +228,16 @@ __global__ __launch_bounds__(256) void ms_split_store_kernel(const float* __rest
   *reinterpret_cast<ms8h*>(img_hi + tok * 256 + 16 * g) = hi;
 }
 
-// largest token L2 norm of the store, as float bits (error bound of the first pass of the two-pass top-k)
-__global__ __launch_bounds__(256) void ms_tokmax_kernel(const float* __restrict__ D, long n_tokens,
+// largest token L2 norm of the SCALED store (rows x `scale`, the store's power of two: components in [-1, 1], so no
+// square underflows to nothing or overflows whatever the store's magnitude), as float bits (error bound of the first
+// pass of the two-pass top-k)
+__global__ __launch_bounds__(256) void ms_tokmax_kernel(const float* __restrict__ D, long n_tokens, float scale,
                                                         unsigned int* __restrict__ out) {
   const int lane = threadIdx.x & 63;
   const long wv = ((long)blockIdx.x * 256 + threadIdx.x) >> 6, nw = (long)gridDim.x * 4;
   float m = 0.f;
   for (long t = wv; t < n_tokens; t += nw) {
-    const float a = D[t * kDim + lane], b = D[t * kDim + 64 + lane];
+    const float a = D[t * kDim + lane] * scale, b = D[t * kDim + 64 + lane] * scale;
     float ss = a * a + b * b;
 #pragma unroll
     for (int sft = 1; sft < 64; sft <<= 1) ss += __shfl_xor(ss, sft);
@@ -612,8 +614,16 @@ __global__ __launch_bounds__(kMsQ * 64) __attribute__((amdgpu_waves_per_eu(4, 4)
 // (ONE fp16 MFMA per block instead of three, a 256-byte-per-token image instead of 512: a third of the matrix cycles and
 // half the bytes).  |a_hi . b_hi - a . b| <= (2^-10 + 2^-22) |a| |b| (each fp16 rounding is 2^-11 relative, per
 // component), so a document's first-pass score is within
-//     eps_q = 1.5 * 2^-10 * (sum_i |q_i|) * max_token |d|  (+ the subnormal term)
-// of its full-form score (the 1.5 covers the fp32 accumulation and the full form's own 2e-6).  If T is the k-th best
+//     eps_q = [1.5 * 2^-10 * (sum_i |q'_i|) * max_token |d'| * 1.0001 + q_len * 256 * 2^-25] * unscale_q * unscale_d
+// of its full-form score: q' = q * scale_q and d' = d * scale_d are the SCALED operands (largest |component| in
+// [0.5, 1)), which is what fp16 rounds and what both norms are taken on (ms_split_query_wave, ms_tokmax_kernel) — the
+// bracket is in scaled units and the two unscales carry it to the units of the scores exactly, as they carry the scores.
+// (The 1.5 covers the fp32 accumulation and the full form's own 2e-6, the 1.0001 the fp32 rounding of the norms, the
+// second term operands in fp16's subnormal range.)  The bound has NO scale range of its own: it holds wherever
+// unscale_q * unscale_d is a normal fp32 number, i.e. wherever the scores are; outside (and for a query holding a NaN
+// or an infinity) maxsim_select_kernel makes every document a candidate, which is the one-pass form.  (Until the norms
+// were taken on the scaled operands, a store or a query below ~2^-75 squared to 0 and lost every true top-k document,
+// and one above ~2^63 squared to infinity.)  If T is the k-th best
 // first-pass score, every document that can be among the k best full-form scores — ties at the cut included — has a
 // first-pass score >= T - 2 eps_q (at most k - 1 documents score above the k-th best s_k, hence T <= s_k + eps, and a
 // top-k document has a >= s_k - eps >= T - 2 eps).  Pass 2 re-scores exactly those documents with the full form
@@ -750,8 +760,11 @@ __global__ __launch_bounds__(kMsQ2 * 64) __attribute__((amdgpu_waves_per_eu(3, N
 // zero) and stores its power-of-two unscale — the scale rule and ms_split of ms_load_query_h: identical fragments.  The
 // re-scoring pass takes a query's fragments for every (document, query) item it serves, 15 k times per UCC-en batch:
 // splitting them in the scoring wave each time cost ~500 vector instructions per item and wave.
-// `norm_sum`: the sum of the token rows' Euclidean norms, which the candidate margin of the two-pass top-k is built on
-// (maxsim_select_kernel) — the rows are in this wave's registers anyway.
+// `norm_sum`: the sum of the SCALED token rows' Euclidean norms (rows x the query's power of two, as ms_split takes them:
+// squares of raw components underflow to 0 for a query below ~2^-75 and overflow above ~2^63), which the candidate margin
+// of the two-pass top-k is built on (maxsim_select_kernel) — the rows are in this wave's registers anyway.  A NaN or an
+// infinity in the query makes it NaN or infinite (the scale of such a query is 1), which the select kernel reads as "no
+// bound".
 __device__ __forceinline__ void ms_split_query_wave(const float* __restrict__ Qq, int q_len, int lane,
                                                     unsigned char* __restrict__ img, float* __restrict__ unscale,
                                                     float* __restrict__ norm_sum) {
@@ -761,7 +774,6 @@ __device__ __forceinline__ void ms_split_query_wave(const float* __restrict__ Qq
 #pragma unroll
   for (int it = 0; it < 8; ++it) {
     const int g = lane + 64 * it, row = g >> 4, grp = g & 15;
-    float ss = 0.f;
     if (row < q_len) {
       const ms4f v0 = *reinterpret_cast<const ms4f*>(Qq + (size_t)row * kDim + 8 * grp);
       const ms4f v1 = *reinterpret_cast<const ms4f*>(Qq + (size_t)row * kDim + 8 * grp + 4);
@@ -772,21 +784,27 @@ __device__ __forceinline__ void ms_split_query_wave(const float* __restrict__ Qq
       for (int j = 0; j < 8; ++j) x[it][j] = 0.f;
     }
 #pragma unroll
+    for (int j = 0; j < 8; ++j) m = fmaxf(m, fabsf(x[it][j]));
+  }
+#pragma unroll
+  for (int sft = 1; sft < 64; sft <<= 1) m = fmaxf(m, __shfl_xor(m, sft));
+  int e = 0;
+  if (m > 0.f && m <= FLT_MAX) (void)frexpf(m, &e);
+  const float sc = ldexpf(1.f, -e);
+#pragma unroll
+  for (int it = 0; it < 8; ++it) {
+    float ss = 0.f;
+#pragma unroll
     for (int j = 0; j < 8; ++j) {
-      m = fmaxf(m, fabsf(x[it][j]));
-      ss += x[it][j] * x[it][j];
+      const float v = x[it][j] * sc;  // what ms_split rounds
+      ss += v * v;
     }
 #pragma unroll
     for (int sft = 1; sft < 16; sft <<= 1) ss += __shfl_xor(ss, sft);  // the row's 16 lanes
     nsum += sqrtf(ss);  // (every lane of the row holds it; counted once below)
   }
-#pragma unroll
-  for (int sft = 1; sft < 64; sft <<= 1) m = fmaxf(m, __shfl_xor(m, sft));
   nsum += __shfl_xor(nsum, 16);  // the four rows of a step sit in the four 16-lane groups
   nsum += __shfl_xor(nsum, 32);
-  int e = 0;
-  if (m > 0.f && m <= FLT_MAX) (void)frexpf(m, &e);
-  const float sc = ldexpf(1.f, -e);
   if (lane == 0) {
     *unscale = ldexpf(1.f, e);
     *norm_sum = nsum;
@@ -816,7 +834,8 @@ __global__ __launch_bounds__(256) void maxsim_split_queries_kernel(const float* 
 // Between the passes, one wave per query: T = the k-th best first-pass score, eps from the query's token norms, the
 // list of documents with a first-pass score >= T - 2 eps (ascending ids, at most cap; more -> overflow).
 __global__ __launch_bounds__(64) void maxsim_select_kernel(const float* __restrict__ approx, long n_docs, int q_len, int k,
-                                                           int cap_sel, float d_norm_max, float unscale_d, int cap,
+                                                           int cap_sel, float d_norm_max /* of the scaled store */,
+                                                           float unscale_d, int cap,
                                                            int* __restrict__ cand /*[nq, cap]*/, int* __restrict__ cnt,
                                                            int* __restrict__ overflow, int* __restrict__ dcnt,
                                                            int* __restrict__ dlist /*[n_docs][nq]*/, int nq,
@@ -847,11 +866,17 @@ __global__ __launch_bounds__(64) void maxsim_select_kernel(const float* __restri
   wave_lds_fence();
   const float T = tk.cnt >= k ? tk.buf[k - 1].score() : -FLT_MAX;  // fewer than k documents: every one is a candidate
   wave_lds_fence();
-  // eps: token norms and the query's power-of-two scale, as the scoring kernels take it (maxsim_split_queries_kernel)
-  const float nsum = norm_sum[q], unscale_q = unscale_in[q];
-  const float eps = 1.5f * 9.765625e-4f * nsum * d_norm_max * 1.0001f +
-                    (float)q_len * 256.f * 2.98023224e-8f * unscale_q * unscale_d;  // + operands in fp16's subnormal range
-  const float thr = (T == -FLT_MAX) ? -FLT_MAX : T - 2.f * eps;
+  // eps in SCALED units (norms of the scaled operands: nsum <= 32 sqrt(128), d_norm_max <= sqrt(128), whatever the
+  // magnitudes of store and query), then times the two unscales — the powers of two that the scoring kernels undo on the
+  // scores themselves (maxsim_split_queries_kernel).  No bound — every document is a candidate, the overflow path or the
+  // items re-score them all and the result is the one-pass form's — where the arithmetic gives none: a NaN or an infinity
+  // in the query (nsum NaN / infinite), or unscales whose product is no normal fp32 number (then the scores themselves
+  // have left fp32's range).
+  const float nsum = norm_sum[q], unscale = unscale_in[q] * unscale_d;
+  const float eps = (1.5f * 9.765625e-4f * nsum * d_norm_max * 1.0001f +
+                     (float)q_len * 256.f * 2.98023224e-8f /* operands in fp16's subnormal range */) * unscale;
+  const bool bound = unscale >= FLT_MIN && eps <= FLT_MAX;  // (false on NaN)
+  const float thr = (T == -FLT_MAX || !bound) ? -FLT_MAX : T - 2.f * eps;
   int n = 0;
   for (long base = 0; base < n_docs; base += 64) {
     const long d = base + lane;
@@ -1156,7 +1181,7 @@ struct amdr_maxsim {
   unsigned char* img = nullptr;  // [hi 128 x fp16 | lo 128 x fp16] per token, scaled by d_scale (split-fp16 form)
   unsigned char* img_hi = nullptr;  // [hi 128 x fp16] per token: first pass of the two-pass top-k
   float d_scale = 1.f;           // power of two; img == nullptr: the store is not finite -> fp32-input form only
-  float d_norm_max = 0.f;        // largest token L2 norm (error bound of the first pass)
+  float d_norm_max = 0.f;        // largest token L2 norm of the store x d_scale (error bound of the first pass)
   long long* doc_ptr = nullptr;
   int cus = 0;  // compute units of `device` (the re-scoring pass's grid)
   hipStream_t stream = nullptr;
@@ -1417,7 +1442,7 @@ int amdr_maxsim_create(const float* D_host, const int64_t* doc_ptr, int64_t n_do
     if (e == hipSuccess) {
       hipLaunchKernelGGL(ms_split_store_kernel, dim3(ceil_div(nt * 16, 256)), dim3(256), 0, 0, h->D, (long)nt, h->d_scale,
                          h->img, h->img_hi);
-      hipLaunchKernelGGL(ms_tokmax_kernel, dim3(1024), dim3(256), 0, 0, h->D, (long)nt, nm);
+      hipLaunchKernelGGL(ms_tokmax_kernel, dim3(1024), dim3(256), 0, 0, h->D, (long)nt, h->d_scale, nm);
       e = hipMemcpy(&nbits, nm, sizeof(unsigned int), hipMemcpyDeviceToHost);
       memcpy(&h->d_norm_max, &nbits, sizeof(float));
     }

@@ -61,12 +61,41 @@ def maxsim_scales(Q: np.ndarray, D: np.ndarray):
 
 
 def maxsim_eps(Q: np.ndarray, D: np.ndarray) -> np.ndarray:
-    """maxsim_select_kernel: 1.5 2^-10 sum_i |q_i| max_t |d_t| 1.0001 + q_len 256 2^-25 unscale_q unscale_d."""
+    """maxsim_select_kernel, restated in fp64 (this module is the independent oracle): in SCALED units — q' = q q_scale,
+    d' = d d_scale, largest |component| in [0.5, 1) —
+        [1.5 2^-10 (sum_i |q'_i|) max_t |d'_t| 1.0001 + q_len 256 2^-25] unscale_q unscale_d,
+    the bracket times the two unscales 1 / q_scale, 1 / d_scale.  The kernels take both norms on the scaled operands, so
+    the bound has no scale range of its own: it holds wherever unscale_q unscale_d is a normal fp32 number."""
     d_scale, q_scale = maxsim_scales(Q, D)
     q_len = Q.shape[1]
-    nsum = np.linalg.norm(np.asarray(Q, np.float64), axis=2).sum(axis=1)
-    dmax = float(np.linalg.norm(np.asarray(D, np.float64), axis=1).max())
-    return 1.5 * 9.765625e-4 * nsum * dmax * 1.0001 + q_len * 256.0 * 2.98023224e-8 / (q_scale * d_scale)
+    nsum = np.linalg.norm(np.asarray(Q, np.float64) * q_scale[:, None, None], axis=2).sum(axis=1)
+    dmax = float(np.linalg.norm(np.asarray(D, np.float64) * d_scale, axis=1).max())
+    return (1.5 * 9.765625e-4 * nsum * dmax * 1.0001 + q_len * 256.0 * 2.98023224e-8) / (q_scale * d_scale)
+
+
+def maxsim_eps_subnormal_term(Q: np.ndarray, D: np.ndarray) -> np.ndarray:
+    """The second term of maxsim_eps alone: what is left of the bound when a norm collapses to 0 (norms taken on raw fp32
+    components square to 0 below ~2^-75)."""
+    d_scale, q_scale = maxsim_scales(Q, D)
+    return Q.shape[1] * 256.0 * 2.98023224e-8 / (q_scale * d_scale)
+
+
+def maxsim_eps_f32(Q: np.ndarray, D: np.ndarray, scaled: bool = True) -> np.ndarray:
+    """The bound in the kernels' fp32 arithmetic (ms_tokmax_kernel, ms_split_query_wave, maxsim_select_kernel; the
+    summation order inside a row is numpy's, not the lanes').  scaled=False: the norms on the raw components, as the
+    kernels took them before — 0, inf or NaN (0 x inf) outside ~2^-75 .. 2^63."""
+    f = np.float32
+    d_scale, q_scale = maxsim_scales(Q, D)
+    ds, qs = f(d_scale), q_scale.astype(f)
+    Dx = np.asarray(D, f) * (ds if scaled else f(1))
+    Qx = np.asarray(Q, f) * (qs[:, None, None] if scaled else f(1))
+    with np.errstate(over="ignore", under="ignore", invalid="ignore"):
+        dmax = np.sqrt((Dx * Dx).sum(axis=1, dtype=f)).max()
+        nsum = np.sqrt((Qx * Qx).sum(axis=2, dtype=f)).sum(axis=1, dtype=f)
+        first = f(1.5) * f(9.765625e-4) * nsum * dmax * f(1.0001)
+        second = f(Q.shape[1]) * f(256.0) * f(2.98023224e-8)
+        un = (f(1) / qs) * (f(1) / ds)
+        return ((first + second) * un if scaled else first + second * un).astype(np.float64)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -416,3 +445,198 @@ def ms_cand_cap(k: int) -> int:
     while c < 2 * k:
         c *= 2
     return max(64, c)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the scale range of the MaxSim bound: a case times exact powers of two
+
+# (store exponent, query exponent); the exact scores of maxsim_inversion stay inside fp32's normal range for all of them
+MAXSIM_SCALE_PAIRS = [(0, 0), (-90, 0), (0, -90), (-75, 0), (-45, -45), (70, 0), (0, 70), (45, 45)]
+
+
+def maxsim_scaled(c: dict, sd: int, sq: int) -> dict:
+    """The case with (D 2^sd, Q 2^sq), exactly (no component leaves fp32's normal range): the fp16 images of the scaled
+    operands, the first-pass errors relative to the scores and the oracle's order are those of the unscaled case."""
+    out = dict(c)
+    for name, e in (("D", sd), ("Q", sq)):
+        x = np.ldexp(np.asarray(c[name], np.float64), e)
+        x32 = x.astype(np.float32)
+        nz = x != 0
+        assert np.array_equal(x32.astype(np.float64), x) and np.all(np.abs(x[nz]) >= 2.0 ** -126), (name, e)
+        out[name] = x32
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# shape edges of the MaxSim two-pass top-k (random unit rows)
+
+def unit_rows(rng, n: int, d: int = 128) -> np.ndarray:
+    x = rng.standard_normal((n, d)).astype(np.float32)
+    x /= np.linalg.norm(x, axis=1, keepdims=True)
+    return x
+
+
+def topk_exact(exact: np.ndarray, k: int):
+    """(scores, ids) [nq, k] of an fp64 score matrix: descending, ties -> lower id."""
+    ids = np.stack([np.lexsort((np.arange(exact.shape[1]), -row))[:k] for row in exact])
+    return np.take_along_axis(exact, ids, axis=1), ids
+
+
+MS_LONG_LENS = (513, 1000, 481, 511, 512, 640)  # more than 15 tiles of 32 tokens each (maxsim_items_kernel's last class)
+
+
+def maxsim_long_docs(rng, nq: int, q_len: int):
+    """80 documents: lengths 1, 448, 449, 480 (14 and 15 tiles: below and on the items kernel's clamp) and the six of
+    MS_LONG_LENS (16 .. 32 tiles) first, in the middle and last — the last document has 513 tokens, one token in its
+    final tile, so that tile reads on into the images' padding — the rest 1 .. 60.  Query b's first three tokens are
+    planted (noisy copies, renormalised) in long document b mod 6 at tokens b, len / 2 + b and len - 1 - b (query 0: the
+    very last token of the store).  Returns dict(D, doc_ptr, Q, long = ids of the documents with more than 15 tiles)."""
+    n = 80
+    lens = rng.integers(1, 61, size=n)
+    place = {0: 1000, 1: 448, 2: 1, 3: 481, 38: 449, 39: 480, 40: 511, 41: 640, 78: 512, 79: 513}
+    for i, v in place.items():
+        lens[i] = v
+    doc_ptr = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    D = unit_rows(rng, int(doc_ptr[-1]))
+    Q = unit_rows(rng, nq * q_len).reshape(nq, q_len, 128)
+    long_of = {v: i for i, v in place.items()}
+    for b in range(nq):
+        d = long_of[MS_LONG_LENS[b % len(MS_LONG_LENS)]]
+        ln = int(lens[d])
+        for j, pos in enumerate((b, ln // 2 + b, ln - 1 - b)[:min(3, q_len)]):
+            v = Q[b, j] + 0.3 * unit_rows(rng, 1)[0]
+            D[doc_ptr[d] + pos] = v / np.linalg.norm(v)
+    long_ids = np.nonzero((lens + 31) // 32 > 15)[0]
+    return dict(D=D, doc_ptr=doc_ptr, Q=Q, long=long_ids)
+
+
+def maxsim_short_docs(rng, n_docs: int, nq: int, q_len: int = 32):
+    """n_docs documents of 1 .. 12 random unit tokens (the first four: 1, 12, 1, 12).  A prefix of the store is a store:
+    doc_ptr[:m + 1] and D[:doc_ptr[m]], and the exact scores of the prefix are the first m columns."""
+    lens = rng.integers(1, 13, size=n_docs)
+    lens[:4] = [1, 12, 1, 12]
+    doc_ptr = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    return dict(D=unit_rows(rng, int(doc_ptr[-1])), doc_ptr=doc_ptr, Q=unit_rows(rng, nq * q_len).reshape(nq, q_len, 128))
+
+
+def maxsim_depth_docs(rng, nq: int, q_len: int = 32):
+    """1 100 documents for depths up to 256: 850 of 1 .. 6 tokens and 250 of 12 .. 80, shuffled (under 15 k tokens).  A
+    score grows with the length, so the 256 best are the long documents spread over ~2.5 — with equal lengths the top
+    quarter of 1 100 random scores sits within ~1 and one rank position in seven is a near-tie at 1e-4."""
+    lens = rng.permutation(np.concatenate([rng.integers(1, 7, size=850), rng.integers(12, 81, size=250)]))
+    doc_ptr = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    return dict(D=unit_rows(rng, int(doc_ptr[-1])), doc_ptr=doc_ptr, Q=unit_rows(rng, nq * q_len).reshape(nq, q_len, 128))
+
+
+def maxsim_prefix(c: dict, m: int):
+    return c["D"][: int(c["doc_ptr"][m])], c["doc_ptr"][: m + 1]
+
+
+def maxsim_mixed_overflow(rng):
+    """300 documents: 200 near-duplicates of one 40-token document (differing in the 4th decimal), interleaved with 100
+    random ones of 30 .. 100 tokens; 16 queries: the even ones aimed at the cluster (20 noisy copies of its tokens + 12
+    random tokens: the 200 duplicates tie inside the margin, far more than the candidate list holds), the odd ones random
+    (the cluster scores like any 40-token document: below their cut).  An aimed and a random query share every pass-1 wave.
+    Returns dict(D, doc_ptr, Q, aimed = query ids, cluster = document ids)."""
+    base = unit_rows(rng, 40)
+    docs, cluster = [], []
+    for i in range(300):
+        if i % 3 != 2:
+            cluster.append(i)
+            docs.append(base + 1e-4 * rng.standard_normal(base.shape).astype(np.float32))
+        else:
+            docs.append(unit_rows(rng, int(rng.integers(30, 101))))
+    D = np.concatenate(docs).astype(np.float32)
+    D /= np.linalg.norm(D, axis=1, keepdims=True)
+    doc_ptr = np.concatenate([[0], np.cumsum([len(x) for x in docs])]).astype(np.int64)
+    Q = unit_rows(rng, 16 * 32).reshape(16, 32, 128)
+    aimed = np.arange(0, 16, 2)
+    for b in aimed:
+        Q[b, :20] = base[:20] + 0.05 * rng.standard_normal((20, 128)).astype(np.float32)
+    Q /= np.linalg.norm(Q, axis=2, keepdims=True)
+    return dict(D=D, doc_ptr=doc_ptr, Q=Q.astype(np.float32), aimed=aimed, cluster=np.array(cluster))
+
+
+MS_SHARED_DOC = 100  # the planted document of maxsim_shared
+
+
+def maxsim_shared(rng):
+    """201 documents of 1 .. 12 random unit tokens, but document MS_SHARED_DOC: 70 tokens (3 tiles), noisy copies of the
+    tokens of query 0 at norm 0.35 — the best document of query 0 by far (~10 against ~5), and for any other query a
+    document of short tokens far below its cut (~2.5).  In a batch that holds query 0 c times, document MS_SHARED_DOC is a
+    candidate of exactly c queries.  Returns dict(D, doc_ptr, pool [30, 32, 128]): pool[0] is query 0, the rest random."""
+    c = maxsim_short_docs(rng, 201, 30)
+    lens = np.diff(c["doc_ptr"])
+    lens[MS_SHARED_DOC] = 70
+    doc_ptr = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    D = unit_rows(rng, int(doc_ptr[-1]))
+    q0 = c["Q"][0]
+    v = q0[np.arange(70) % 32] + 0.3 * unit_rows(rng, 70)
+    D[doc_ptr[MS_SHARED_DOC]: doc_ptr[MS_SHARED_DOC + 1]] = 0.35 * v / np.linalg.norm(v, axis=1, keepdims=True)
+    return dict(D=D, doc_ptr=doc_ptr, pool=c["Q"])
+
+
+def maxsim_shared_batch(pool: np.ndarray, copies: int, nq: int = 24) -> np.ndarray:
+    """`copies` times query 0, then nq - copies others of the pool."""
+    return np.concatenate([np.repeat(pool[:1], copies, axis=0), pool[1: 1 + nq - copies]]).astype(np.float32)
+
+
+def candidate_status(approx_row: np.ndarray, eps: float, k: int, slack: float) -> np.ndarray:
+    """+1: a candidate by more than `slack`, -1: none by more than `slack`, 0: too close to the threshold for a model
+    whose sums are not the kernel's fp32 sums to say."""
+    thr = np.sort(approx_row)[::-1][k - 1] - 2.0 * eps
+    return np.where(approx_row >= thr + slack, 1, np.where(approx_row < thr - slack, -1, 0))
+
+
+def oracle_rank_mask(es: np.ndarray, tol: float) -> np.ndarray:
+    """Positions of a descending oracle score row whose neighbours are both more than 2 tol away: where ranks are compared."""
+    ok = np.abs(np.diff(es)) > 2 * tol
+    return np.concatenate([[True], ok]) & np.concatenate([ok, [True]])
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the GPU tests' driver of the MaxSim forms (needs the native library: `nat` is legal_rag_amd._native, loaded)
+
+# documents per block of pass 1: the default, one, and seven (blocks that end inside the store's groups)
+MS_VARIANTS = [{}, {"AMDR_MAXSIM_DOCS": "1"}, {"AMDR_MAXSIM_DOCS": "7"}]
+
+
+def ms_forms(nat, monkeypatch, D, doc_ptr, Q, k, variants, ref_ids=None, rows=None, two_pass=None):
+    """(scores, ids) of the one-pass form (AMDR_MAXSIM_TWOPASS=0), which equal ref_ids where given; every variant of the
+    two-pass form — asserted to BE the two-pass form — returns the same ids and the same score bits.  rows: the queries
+    compared (default: all); two_pass: a list that receives every variant's (scores, ids)."""
+    rows = slice(None) if rows is None else rows
+    monkeypatch.setenv("AMDR_MAXSIM_TWOPASS", "0")
+    idx = nat.MaxSimIndex(D, doc_ptr)
+    s1, i1 = idx.search(Q, k)
+    idx.close()
+    monkeypatch.delenv("AMDR_MAXSIM_TWOPASS")
+    if ref_ids is not None:
+        assert np.array_equal(i1, ref_ids)
+    n_docs, nq = len(doc_ptr) - 1, len(Q)
+    for env in variants:
+        for n_, v in env.items():
+            monkeypatch.setenv(n_, v)
+        idx = nat.MaxSimIndex(D, doc_ptr)
+        assert "two-pass" in idx.plan_info(nq), idx.plan_info(nq)
+        assert nat.maxsim_workspace_plan(n_docs, True, nq, k, nq, k)[1] > (nq * n_docs * 4 + 255) // 256 * 256, (n_docs, nq, k)
+        s2, i2 = idx.search(Q, k)
+        idx.close()
+        for n_ in env:
+            monkeypatch.delenv(n_)
+        if two_pass is not None:
+            two_pass.append((s2, i2))
+        if ref_ids is not None:
+            assert np.array_equal(i2, ref_ids), env
+        assert np.array_equal(i2[rows], i1[rows]), env
+        assert np.array_equal(s2[rows].view(np.uint32), s1[rows].view(np.uint32)), env
+    return s1, i1
+
+
+def ms_check(nat, monkeypatch, D, doc_ptr, Q, k, top, variants):
+    """ms_forms against the fp64 oracle's ids (oracle/maxsim.py), which are `top` where the construction fixes them."""
+    from oracle import maxsim as OM
+    _, ref_ids = OM.maxsim_topk(Q, D, doc_ptr, k)
+    if top is not None:
+        assert np.array_equal(ref_ids, top)
+    return ms_forms(nat, monkeypatch, D, doc_ptr, Q, k, variants, ref_ids)

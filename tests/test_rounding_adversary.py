@@ -183,3 +183,134 @@ def test_maxsim_subnormal_queries_need_honoured_subnormals():
         assert set(top.tolist()) <= set(RA.candidates(ok[b], eps[b], k).tolist())
         lost += not set(top.tolist()) <= set(RA.candidates(ftz[b], eps[b], k).tolist())
     assert lost >= len(Q) // 2
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the scale range of the MaxSim bound
+
+@pytest.fixture(scope="module", params=[(1, 4), (10, 12)], ids=["k1", "k10"])
+def ms_inversion_case(request):
+    k, nc = request.param
+    return k, RA.maxsim_inversion(np.random.default_rng(910), 16, k, groups=8, reps=2, nc=nc)
+
+
+@pytest.mark.parametrize("sd,sq", RA.MAXSIM_SCALE_PAIRS)
+def test_maxsim_scale_range(ms_inversion_case, sd, sq):
+    """The inversion store times exact powers of two: the oracle's top-k and the candidate rule under the restated
+    bound are those of the unscaled case, the scores stay in fp32's normal range — and what is left of the bound when a
+    norm collapses to 0 (its subnormal term) loses a target of EVERY query, at every scale, so a kernel whose norms
+    underflow returns other ids.  The bound in the kernels' fp32 arithmetic on the scaled operands follows the fp64
+    restatement at every pair; on the raw components it is 0-normed, infinite or NaN outside ~2^-75 .. 2^63."""
+    k, base = ms_inversion_case
+    c = RA.maxsim_scaled(base, sd, sq)
+    Q, D, ptr, top = c["Q"], c["D"], c["doc_ptr"], c["top"]
+    exact = RA.exact_maxsim(Q, D, ptr)
+    assert np.all(np.abs(exact) >= 2.0 ** -126) and np.all(np.abs(exact) < 2.0 ** 127)
+    assert np.array_equal(RA.topk_exact(exact, k)[1], top)  # 1
+    approx, eps, sub = RA.model_maxsim_hi(Q, D, ptr), RA.maxsim_eps(Q, D), RA.maxsim_eps_subnormal_term(Q, D)
+    # the scaling is exact: scores, model and bound are the unscaled ones times 2^(sd + sq)
+    f = 2.0 ** (sd + sq)
+    assert np.array_equal(exact, RA.exact_maxsim(base["Q"], base["D"], ptr) * f)
+    assert np.array_equal(approx, RA.model_maxsim_hi(base["Q"], base["D"], ptr) * f)
+    assert np.allclose(eps, RA.maxsim_eps(base["Q"], base["D"]) * f, rtol=1e-12, atol=0)
+    for b in range(len(Q)):
+        assert set(top[b].tolist()) <= set(RA.candidates(approx[b], eps[b], k).tolist())  # 2
+        assert not set(top[b].tolist()) <= set(RA.candidates(approx[b], sub[b], k).tolist())  # 3
+    # fp32, scaled operands: the 1.0001 of the bound covers the rounding of the norms (never below the fp64 bound without it)
+    e32 = RA.maxsim_eps_f32(Q, D)
+    assert np.all(np.isfinite(e32)) and np.all(e32 >= eps / 1.0001) and np.allclose(e32, eps, rtol=1e-5, atol=0)
+    raw = RA.maxsim_eps_f32(Q, D, scaled=False)
+    if min(sd, sq) <= -75:
+        assert np.allclose(raw, sub, rtol=1e-6, atol=0)  # a norm is exactly 0
+    elif max(sd, sq) >= 70:
+        assert np.all(np.isinf(raw))
+    else:
+        assert np.allclose(raw, eps, rtol=1e-5, atol=0)
+
+
+def test_maxsim_zero_query_on_a_huge_store_has_a_bound():
+    """0 x inf: an all-zero query on the store x 2^70 — raw norms give eps = NaN (no document passes a NaN threshold),
+    scaled norms the subnormal term."""
+    c = RA.maxsim_scaled(RA.maxsim_inversion(np.random.default_rng(911), 16, 1, groups=2, reps=1, nc=4), 70, 0)
+    Q = c["Q"].copy()
+    Q[1] = 0.0
+    assert np.isnan(RA.maxsim_eps_f32(Q, c["D"], scaled=False)[1])
+    e = RA.maxsim_eps_f32(Q, c["D"])[1]
+    assert np.isfinite(e) and np.isclose(e, RA.maxsim_eps_subnormal_term(Q, c["D"])[1], rtol=1e-6)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# shape edges of the MaxSim two-pass top-k: the data is what tests/test_maxsim_two_pass_edges_gpu.py says it is
+
+TOL = 1e-4
+
+
+def _skipped(exact, k):
+    es, _ = RA.topk_exact(exact, k)
+    return float(np.mean([~RA.oracle_rank_mask(row, TOL) for row in es]))
+
+
+@pytest.mark.parametrize("nq,q_len", [(9, 32), (16, 17)])
+def test_maxsim_long_docs_reach_the_top(nq, q_len):
+    c = RA.maxsim_long_docs(np.random.default_rng(1000 + nq), nq, q_len)
+    ptr, lens = c["doc_ptr"], np.diff(c["doc_ptr"])
+    assert len(lens) == 80 and lens[-1] == 513 and set((1, 448, 449, 480, 481, 511, 512, 513, 640, 1000)) <= set(lens.tolist())
+    assert sorted(lens[c["long"]].tolist()) == sorted(RA.MS_LONG_LENS) and {0, 79} <= set(c["long"].tolist())
+    exact = RA.exact_maxsim(c["Q"], c["D"], ptr)
+    _, ids = RA.topk_exact(exact, 5)
+    assert len(set(ids.ravel().tolist()) & set(c["long"].tolist())) >= 5
+    assert ids[0, 0] == 79  # query 0's planted tokens: the last token of the store among them
+    assert _skipped(exact, 5) <= 0.10
+    # the long documents are candidates of the first pass too (not only of the oracle)
+    approx, eps = RA.model_maxsim_hi(c["Q"], c["D"], ptr), RA.maxsim_eps(c["Q"], c["D"])
+    cand = set().union(*[set(RA.candidates(approx[b], eps[b], 5).tolist()) for b in range(nq)])
+    assert len(cand & set(c["long"].tolist())) >= 5
+
+
+def test_maxsim_short_docs_rank_gaps():
+    """Random unit rows at the selector and depth shapes: at most 10 % of the compared rank positions sit in a near-tie."""
+    c = RA.maxsim_short_docs(np.random.default_rng(2100), 2100, 24)
+    exact = RA.exact_maxsim(c["Q"], c["D"], c["doc_ptr"])
+    assert _skipped(exact[:, :640], 10) <= 0.10 and _skipped(exact[8:16, :640], 33) <= 0.10  # the handle-reuse calls
+    assert c["doc_ptr"][-1] <= 15000
+    for n in (40, 640, 641, 1280, 1281, 2048, 2049, 2100):
+        for k in (1, 10):
+            assert _skipped(exact[:8, :n], k) <= 0.10, (n, k)
+    assert _skipped(exact[:, :40], 11) <= 0.10
+    c = RA.maxsim_depth_docs(np.random.default_rng(1100), 9)
+    assert len(c["doc_ptr"]) == 1101 and c["doc_ptr"][-1] <= 15000
+    exact = RA.exact_maxsim(c["Q"], c["D"], c["doc_ptr"])
+    for k in (32, 33, 64, 65, 128, 256):
+        print(k, _skipped(exact, k))
+        assert _skipped(exact, k) <= 0.10, k
+
+
+def test_maxsim_mixed_overflow_case():
+    k = 10
+    c = RA.maxsim_mixed_overflow(np.random.default_rng(77))
+    Q, D, ptr = c["Q"], c["D"], c["doc_ptr"]
+    approx, eps = RA.model_maxsim_hi(Q, D, ptr), RA.maxsim_eps(Q, D)
+    cap = RA.ms_cand_cap(k)
+    for b in range(16):
+        n = len(RA.candidates(approx[b], eps[b], k))
+        if b in c["aimed"]:
+            assert n > 2 * cap, (b, n)
+        else:
+            assert n < cap / 2, (b, n)
+    assert sorted(c["aimed"].tolist()) == list(range(0, 16, 2))  # one of each kind in every pass-1 wave (queries 2 w, 2 w + 1)
+
+
+@pytest.mark.parametrize("copies", [1, 8, 9, 16, 17, 24])
+def test_maxsim_shared_document_is_a_candidate_of_exactly_the_copies(copies):
+    k = 10
+    c = RA.maxsim_shared(np.random.default_rng(24))
+    Q = RA.maxsim_shared_batch(c["pool"], copies)
+    assert Q.shape == (24, 32, 128)
+    approx, eps = RA.model_maxsim_hi(Q, c["D"], c["doc_ptr"]), RA.maxsim_eps(Q, c["D"])
+    st = np.array([RA.candidate_status(approx[b], eps[b], k, 1e-2)[RA.MS_SHARED_DOC] for b in range(24)])
+    assert np.all(st[:copies] == 1) and np.all(st[copies:] == -1), st  # by a margin 1 000 x the fp32 summation noise
+    exact = RA.exact_maxsim(Q, c["D"], c["doc_ptr"])
+    assert np.all(np.argmax(exact[:copies], axis=1) == RA.MS_SHARED_DOC)
+    assert np.diff(c["doc_ptr"])[RA.MS_SHARED_DOC] == 70 and 4 * k <= len(c["doc_ptr"]) - 1
+    if copies == 1:
+        assert _skipped(exact, k) <= 0.10

@@ -203,32 +203,10 @@ def test_dense_hi_large_scan_on_the_inversion_corpus(nat, monkeypatch, d, nq):
         assert np.array_equal(out["hi"][0].view(np.uint32), out[other][0].view(np.uint32)), other
 
 
-# documents per block of pass 1: the default, one, and seven (blocks that end inside the store's groups)
-_MS_VARIANTS = [{}, {"AMDR_MAXSIM_DOCS": "1"}, {"AMDR_MAXSIM_DOCS": "7"}]
-
-
-def _ms_check(nat, monkeypatch, D, doc_ptr, Q, k, top, variants):
-    from oracle import maxsim as OM
-    _, ref_ids = OM.maxsim_topk(Q, D, doc_ptr, k)
-    if top is not None:
-        assert np.array_equal(ref_ids, top)
-    monkeypatch.setenv("AMDR_MAXSIM_TWOPASS", "0")
-    idx = nat.MaxSimIndex(D, doc_ptr)
-    s1, i1 = idx.search(Q, k)
-    idx.close()
-    monkeypatch.delenv("AMDR_MAXSIM_TWOPASS")
-    assert np.array_equal(i1, ref_ids)
-    for env in variants:
-        for n_, v in env.items():
-            monkeypatch.setenv(n_, v)
-        idx = nat.MaxSimIndex(D, doc_ptr)
-        assert "two-pass" in idx.plan_info(len(Q)), idx.plan_info(len(Q))
-        s2, i2 = idx.search(Q, k)
-        idx.close()
-        for n_ in env:
-            monkeypatch.delenv(n_)
-        assert np.array_equal(i2, ref_ids), env
-        assert np.array_equal(s2.view(np.uint32), s1.view(np.uint32)), env
+# the driver of the MaxSim forms (one-pass ids == oracle ids; every two-pass variant: the same ids, the same score bits)
+# lives beside the data: tests/test_maxsim_two_pass_edges_gpu.py runs it too
+_MS_VARIANTS = RA.MS_VARIANTS
+_ms_check = RA.ms_check
 
 
 @pytest.mark.parametrize("k,nc", [(1, 4), (10, 12)])
