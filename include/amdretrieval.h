@@ -50,6 +50,7 @@ typedef struct amdr_maxsim amdr_maxsim_t;
 typedef struct amdr_tokenizer amdr_tokenizer_t;
 typedef struct amdr_tokenizer_device amdr_tokenizer_device_t;
 typedef struct amdr_graph amdr_graph_t;
+typedef struct amdr_scope amdr_scope_t;
 
 /* ---- library ---------------------------------------------------------- */
 const char* amdr_last_error(void);
@@ -417,6 +418,61 @@ int amdr_graph_search_device(amdr_graph_t* h, amdr_dense_t* dense, const float* 
                              int64_t* out_rows, double* out_final, float* out_semantic, int32_t* out_depth,
                              int32_t* out_rel, double* out_conf, void* stream);
 int amdr_graph_destroy(amdr_graph_t* h);
+
+/* ---- scoped search: the top-k of a query's OWN rows in the dense, BM25 and ColBERT channels ------------------------
+ * No reference counterpart: HybridRetriever.search (legalrag/retrieval/hybrid_retriever.py:282-384) ranks the whole corpus
+ * and has no scope argument; a caller who asks "within this chapter" over-fetches and filters on the host.  csrc/scope.hip.
+ * A scope is an ascending list of rows of ONE channel's row space (dense rows, BM25 documents and ColBERT documents each
+ * have their own).  The table travels with each call: scope_ptr i64 [n_scopes + 1] indexes rows i64 [...], qscope i32 [nq]
+ * names each query's scope, rows_max = the longest scope of the call (the grid is sized from it; rows past it are not
+ * ranked).  Per query the top k <= AMDR_MAX_K of its scope's rows, by the score the unscoped channel gives each row — bit
+ * for bit (dense: amdr_dense_score_rows; BM25: amdr_bm25_scores, idf and avgdl of the WHOLE index; MaxSim: the split-fp16
+ * pair form of amdr_maxsim_scores, the store's scale) — with the channel's own order: score descending, ties -> lower id,
+ * NaN last, -0.0 as +0.0, BM25 zero-score documents returned; padding id -1 / -FLT_MAX (-DBL_MAX) behind a scope shorter
+ * than k.  An empty scope or a qscope outside [0, n_scopes) gives an all-padding list and reads nothing; a row outside
+ * [0, n) is skipped and never dereferenced.  Work is proportional to the scopes, not to the corpus.
+ * amdr_scope_t is a workspace holder and owns no table: one region of slab lists per channel, so the three "_device"
+ * calls of a step need no ordering among themselves (calls of the SAME channel on one handle share its region: order
+ * them).  reserve: the largest call (queries, depth, longest scope); a scope inside one slab of rows needs no workspace.
+ * AMDR_SCOPE_SLAB=<rows> pins the slab length of all three channels (<= 1 024; read per call and by reserve /
+ * workspace_plan: set it before the reserve).
+ * The "_device" calls take the channel's handle, the query operand in the channel's own device form and the table as
+ * device pointers; they only enqueue on `stream` (one launch, plus the merge when a scope spans slabs), allocate nothing
+ * and return AMDR_EINVAL, enqueueing nothing, when the call exceeds the reserve.  amdr_scope_maxsim_* return AMDR_EINVAL
+ * for a store without its split-fp16 image and under AMDR_MAXSIM_F16X3=0.
+ * The host-pointer twins validate the table (AMDR_EINVAL: scope_ptr not monotone, a scope's rows not strictly ascending
+ * or outside [0, n)), stage it, run on the scope handle's own stream and return after the lists are in the host buffers. */
+int amdr_scope_create(int32_t device, amdr_scope_t** out);
+int amdr_scope_reserve(amdr_scope_t* h, int32_t nq_max, int32_t k_max, int64_t rows_max);
+/* Host-only (no device is touched): out6[0..2] = the bytes amdr_scope_reserve(nq_max, k_max, rows_max_reserve) sizes for
+ * the dense / BM25 / MaxSim region, out6[3..5] = the bytes a "_device" call (nq, k, rows_max) uses of each.  A test holds
+ * out6[3+i] <= out6[i] for every nq <= nq_max, k <= k_max, rows_max <= rows_max_reserve (tests/test_scope.py). */
+int amdr_scope_workspace_plan(int32_t nq_max, int32_t k_max, int64_t rows_max_reserve, int32_t nq, int32_t k,
+                              int64_t rows_max, int64_t* out6);
+/* which kernels the three scoped calls of (nq, k, rows_max) would launch and how a scope is cut into slabs
+ * (NUL-terminated; no device work) */
+int amdr_scope_plan_info(const amdr_scope_t* h, int32_t nq, int32_t k, int64_t rows_max, char* buf, int32_t buf_len);
+int amdr_scope_dense_search_device(amdr_scope_t* h, amdr_dense_t* dense, const float* Q_dev, const int64_t* scope_ptr_dev,
+                                   const int64_t* rows_dev, const int32_t* qscope_dev, int32_t n_scopes, int64_t rows_max,
+                                   int32_t nq, int32_t k, float* scores_dev, int64_t* ids_dev, void* stream);
+int amdr_scope_bm25_search_device(amdr_scope_t* h, amdr_bm25_t* bm25, const int32_t* q_terms_dev, const int64_t* q_ptr_dev,
+                                  const int64_t* scope_ptr_dev, const int64_t* rows_dev, const int32_t* qscope_dev,
+                                  int32_t n_scopes, int64_t rows_max, int32_t nq, int32_t k, double* scores_dev,
+                                  int64_t* ids_dev, void* stream);
+int amdr_scope_maxsim_search_device(amdr_scope_t* h, amdr_maxsim_t* maxsim, const float* Q_dev, int32_t q_len,
+                                    const int64_t* scope_ptr_dev, const int64_t* rows_dev, const int32_t* qscope_dev,
+                                    int32_t n_scopes, int64_t rows_max, int32_t nq, int32_t k, float* scores_dev,
+                                    int64_t* ids_dev, void* stream);
+int amdr_scope_dense_search(amdr_scope_t* h, amdr_dense_t* dense, const float* Q_host, const int64_t* scope_ptr,
+                            const int64_t* rows, const int32_t* qscope, int32_t n_scopes, int32_t nq, int32_t k,
+                            float* scores_host, int64_t* ids_host);
+int amdr_scope_bm25_search(amdr_scope_t* h, amdr_bm25_t* bm25, const int32_t* q_terms, const int64_t* q_ptr,
+                           const int64_t* scope_ptr, const int64_t* rows, const int32_t* qscope, int32_t n_scopes,
+                           int32_t nq, int32_t k, double* scores_host, int64_t* ids_host);
+int amdr_scope_maxsim_search(amdr_scope_t* h, amdr_maxsim_t* maxsim, const float* Q_host, int32_t q_len,
+                             const int64_t* scope_ptr, const int64_t* rows, const int32_t* qscope, int32_t n_scopes,
+                             int32_t nq, int32_t k, float* scores_host, int64_t* ids_host);
+int amdr_scope_destroy(amdr_scope_t* h);
 
 /* ---- multi-GPU: merge per-shard top-k after the RCCL all-gather --------
  * No reference counterpart (the reference is single-process).

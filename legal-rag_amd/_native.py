@@ -53,6 +53,10 @@ SIGNATURES = {
     "amdr_graph_create": "P" * 11 + "illiiP", "amdr_graph_reserve": "Piii", "amdr_graph_walk": "PPPiiiP" + "P" * 7,
     "amdr_graph_search": "PPPPPiiiiP" + "P" * 7, "amdr_graph_search_device": "PPPPPPiiiiP" + "P" * 8,
     "amdr_graph_destroy": "P",
+    "amdr_scope_create": "iP", "amdr_scope_reserve": "Piil", "amdr_scope_workspace_plan": "iiliilP", "amdr_scope_plan_info": "PiilPi",
+    "amdr_scope_dense_search_device": "PPPPPPiliiPPP", "amdr_scope_bm25_search_device": "PPPPPPPiliiPPP",
+    "amdr_scope_maxsim_search_device": "PPPiPPPiliiPPP", "amdr_scope_dense_search": "PPPPPPiiiPP",
+    "amdr_scope_bm25_search": "PPPPPPPiiiPP", "amdr_scope_maxsim_search": "PPPiPPPiiiPP", "amdr_scope_destroy": "P",
 }
 EXPORTS = tuple(SIGNATURES)  # every symbol include/amdretrieval.h declares (checked by tests/test_abi.py)
 _KIND = {"P": C.c_void_p, "i": C.c_int32, "l": C.c_int64, "d": C.c_double}
@@ -714,6 +718,123 @@ class GraphIndex(_Handle):
 
 
 # ---------------------------------------------------------------------------
+def scope_workspace_plan(nq_max: int, k_max: int, rows_max_reserve: int, nq: int, k: int,
+                         rows_max: int) -> Tuple[Tuple[int, int, int], Tuple[int, int, int]]:
+    """(bytes ScopeWorkspace.reserve(nq_max, k_max, rows_max_reserve) sizes, bytes the scoped "_device" calls of
+    (nq, k, rows_max) use), each as (dense, BM25, MaxSim region) — host-only arithmetic."""
+    out = (C.c_int64 * 6)()
+    _check(load().amdr_scope_workspace_plan(C.c_int32(nq_max), C.c_int32(k_max), C.c_int64(rows_max_reserve), C.c_int32(nq),
+                                            C.c_int32(k), C.c_int64(rows_max), out), "amdr_scope_workspace_plan")
+    v = [int(x) for x in out]
+    return tuple(v[:3]), tuple(v[3:])
+
+
+def check_scope_table(scope_ptr, rows, qscope) -> Tuple[np.ndarray, np.ndarray, np.ndarray, int]:
+    """(scope_ptr i64 [n_scopes + 1], rows i64, qscope i32 [nq], rows_max) as contiguous arrays of the ABI's types."""
+    scope_ptr, rows, qscope = _c(scope_ptr, np.int64).ravel(), _c(rows, np.int64).ravel(), _c(qscope, np.int32).ravel()
+    if scope_ptr.size < 1:
+        raise ValueError("scope table: scope_ptr needs at least one entry")
+    if int(scope_ptr.min()) < 0 or int(scope_ptr.max()) > rows.size:
+        raise ValueError("scope table: scope_ptr points outside rows")
+    rows_max = int(np.diff(scope_ptr).max()) if scope_ptr.size > 1 else 0
+    return scope_ptr, rows, qscope, max(rows_max, 0)
+
+
+class ScopeWorkspace(_Handle):
+    """Workspace of the scoped channel searches (amdr_scope_t, csrc/scope.hip): the top-k of each query's OWN rows — a
+    scope table (scope_ptr, rows, qscope) travels with every call — in the dense, BM25 and ColBERT channels, with the
+    score bits and the order of the unscoped channel.  Owns no table; one slab-list region per channel."""
+    _destroy = "amdr_scope_destroy"
+
+    def __init__(self, *, device: int = 0):
+        self._h = C.c_void_p()
+        self.device = int(device)
+        self.nq_max = self.k_max = self.rows_max = 0
+        _check(load().amdr_scope_create(C.c_int32(device), C.byref(self._h)), "amdr_scope_create")
+
+    def reserve(self, nq_max: int, k_max: int, rows_max: int) -> None:
+        _check(load().amdr_scope_reserve(self._h, C.c_int32(nq_max), C.c_int32(k_max), C.c_int64(rows_max)),
+               "amdr_scope_reserve")
+        self.nq_max, self.k_max, self.rows_max = int(nq_max), int(k_max), int(rows_max)
+
+    def plan_info(self, nq: int, k: int, rows_max: int) -> str:
+        buf = C.create_string_buffer(1024)
+        _check(load().amdr_scope_plan_info(self._h, C.c_int32(nq), C.c_int32(k), C.c_int64(rows_max), buf,
+                                           C.c_int32(len(buf))), "amdr_scope_plan_info")
+        return buf.value.decode()
+
+    # -- host-pointer twins: (scores [nq, k], ids i64 [nq, k]), -1 padded -------------------------------------------
+    def dense_search(self, dense: "DenseIndex", Q: np.ndarray, scope_ptr, rows, qscope, k: int):
+        Q = _c(Q, np.float32)
+        if Q.ndim == 1:
+            Q = Q[None, :]
+        if Q.shape[1] != dense.d:
+            raise ValueError(f"dense_search: query dim {Q.shape[1]} != index dim {dense.d}")
+        scope_ptr, rows, qscope, _ = check_scope_table(scope_ptr, rows, qscope)
+        nq = Q.shape[0]
+        if qscope.size != nq:
+            raise ValueError("dense_search: one qscope entry per query")
+        scores = np.empty((nq, k), dtype=np.float32)
+        ids = np.empty((nq, k), dtype=np.int64)
+        _check(load().amdr_scope_dense_search(self._h, dense._h, _p(Q, C.c_float), _p(scope_ptr, C.c_int64),
+                                              _p(rows, C.c_int64), _p(qscope, C.c_int32), C.c_int32(scope_ptr.size - 1),
+                                              C.c_int32(nq), C.c_int32(k), _p(scores, C.c_float), _p(ids, C.c_int64)),
+               "amdr_scope_dense_search")
+        return scores, ids
+
+    def bm25_search(self, bm25: "BM25Index", queries: Sequence[Sequence[int]], scope_ptr, rows, qscope, k: int):
+        q_terms, q_ptr = BM25Index.pack_queries(queries)
+        scope_ptr, rows, qscope, _ = check_scope_table(scope_ptr, rows, qscope)
+        nq = len(queries)
+        if qscope.size != nq:
+            raise ValueError("bm25_search: one qscope entry per query")
+        scores = np.empty((nq, k), dtype=np.float64)
+        ids = np.empty((nq, k), dtype=np.int64)
+        _check(load().amdr_scope_bm25_search(self._h, bm25._h, _p(q_terms, C.c_int32), _p(q_ptr, C.c_int64),
+                                             _p(scope_ptr, C.c_int64), _p(rows, C.c_int64), _p(qscope, C.c_int32),
+                                             C.c_int32(scope_ptr.size - 1), C.c_int32(nq), C.c_int32(k),
+                                             _p(scores, C.c_double), _p(ids, C.c_int64)), "amdr_scope_bm25_search")
+        return scores, ids
+
+    def maxsim_search(self, maxsim: "MaxSimIndex", Q: np.ndarray, scope_ptr, rows, qscope, k: int):
+        Q = maxsim._q(Q)
+        scope_ptr, rows, qscope, _ = check_scope_table(scope_ptr, rows, qscope)
+        nq = Q.shape[0]
+        if qscope.size != nq:
+            raise ValueError("maxsim_search: one qscope entry per query")
+        scores = np.empty((nq, k), dtype=np.float32)
+        ids = np.empty((nq, k), dtype=np.int64)
+        _check(load().amdr_scope_maxsim_search(self._h, maxsim._h, _p(Q, C.c_float), C.c_int32(Q.shape[1]),
+                                               _p(scope_ptr, C.c_int64), _p(rows, C.c_int64), _p(qscope, C.c_int32),
+                                               C.c_int32(scope_ptr.size - 1), C.c_int32(nq), C.c_int32(k),
+                                               _p(scores, C.c_float), _p(ids, C.c_int64)), "amdr_scope_maxsim_search")
+        return scores, ids
+
+    # -- "_device" forms: pointers in, enqueue only; table = (scope_ptr, rows, qscope, n_scopes, rows_max) ----------
+    def dense_search_device(self, dense: "DenseIndex", q_ptr: int, table, nq: int, k: int, scores_ptr: int, ids_ptr: int,
+                            stream: int = 0) -> None:
+        sp, rw, qs, ns, rmax = table
+        _check(load().amdr_scope_dense_search_device(self._h, dense._h, _vp(q_ptr), _vp(sp), _vp(rw), _vp(qs), C.c_int32(ns),
+                                                     C.c_int64(rmax), C.c_int32(nq), C.c_int32(k), _vp(scores_ptr),
+                                                     _vp(ids_ptr), _vp(stream)), "amdr_scope_dense_search_device")
+
+    def bm25_search_device(self, bm25: "BM25Index", q_terms_ptr: int, q_ptr_ptr: int, table, nq: int, k: int,
+                           scores_ptr: int, ids_ptr: int, stream: int = 0) -> None:
+        sp, rw, qs, ns, rmax = table
+        _check(load().amdr_scope_bm25_search_device(self._h, bm25._h, _vp(q_terms_ptr), _vp(q_ptr_ptr), _vp(sp), _vp(rw),
+                                                    _vp(qs), C.c_int32(ns), C.c_int64(rmax), C.c_int32(nq), C.c_int32(k),
+                                                    _vp(scores_ptr), _vp(ids_ptr), _vp(stream)),
+               "amdr_scope_bm25_search_device")
+
+    def maxsim_search_device(self, maxsim: "MaxSimIndex", q_ptr: int, q_len: int, table, nq: int, k: int, scores_ptr: int,
+                             ids_ptr: int, stream: int = 0) -> None:
+        sp, rw, qs, ns, rmax = table
+        _check(load().amdr_scope_maxsim_search_device(self._h, maxsim._h, _vp(q_ptr), C.c_int32(q_len), _vp(sp), _vp(rw),
+                                                      _vp(qs), C.c_int32(ns), C.c_int64(rmax), C.c_int32(nq), C.c_int32(k),
+                                                      _vp(scores_ptr), _vp(ids_ptr), _vp(stream)),
+               "amdr_scope_maxsim_search_device")
+
+
 def make_fuse_params(*, method: str = "rrf_norm_blend", rrf_k: int = 60, alpha: float = 0.5, w_dense: float = 0.6,
                      w_bm25: float = 0.4, w_colbert: float = 0.35, min_final_score: float = -math.inf) -> FuseParams:
     m = FUSE_METHODS.get(str(method).lower(), 0)  # unknown strings fall to the blend, like the reference's `else`

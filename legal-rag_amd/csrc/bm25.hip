@@ -161,6 +161,7 @@ int bm25_small_raw(amdr_bm25_t* h, int nq, int k, Bm25Raw* out) {
   return AMDR_OK;
 }
 std::mutex& bm25_mutex(amdr_bm25_t* h) { return h->mu; }
+int bm25_device_of(const amdr_bm25_t* h) { return h->device; }
 }  // namespace amdr
 namespace {
 

@@ -177,6 +177,21 @@ struct Bm25Raw {
   bool argmax, select_on;
 };
 int bm25_small_raw(amdr_bm25_t* h, int nq, int k, Bm25Raw* out);  // (bm25.hip)
+// the split-fp16 token image of a MaxSim store (scope.hip scores a scope's documents against it); img == nullptr: the
+// store holds a NaN / infinity and has no image
+struct MaxsimRaw {
+  const unsigned char* img;
+  const long long* doc_ptr;
+  long n_docs;
+  float unscale_d;  // 1 / the store's power-of-two scale
+  int device;
+};
+int maxsim_raw(amdr_maxsim_t* h, MaxsimRaw* out);  // (maxsim.hip)
+int bm25_device_of(const amdr_bm25_t* h);
+// [n_parts, nq, k_in] (score, id) lists -> [nq, k_out], score descending, ties -> lower id; id < 0 = padding (dense.hip)
+template <class T>
+int launch_merge_parts(const T* scores, const int64_t* ids, int nparts, int nq, int k_in, int k_out, T* out_scores,
+                       int64_t* out_ids, hipStream_t st);
 std::mutex& dense_mutex(amdr_dense_t* h);
 std::mutex& bm25_mutex(amdr_bm25_t* h);
 int dense_device_of(const amdr_dense_t* h);

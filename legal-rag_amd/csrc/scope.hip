@@ -1,0 +1,626 @@
+// Scoped search: the top-k of a query's OWN rows in the dense, BM25 and ColBERT channels.
+//
+// No reference counterpart: the reference ranks the whole corpus and a caller who asks "within Book III" over-fetches and
+// filters on the host (legalrag/retrieval/hybrid_retriever.py:282-384 has no scope argument).  Here a scope is a short,
+// ascending list of rows of ONE channel's row space and the work is proportional to it: grid = (slabs of a scope, query),
+// a block scores its slab's rows with the channel's own device functions — dense_row_dot (dense_dot.hpp), the BM25
+// expression in query order (bm25_core.hpp), the split-fp16 pair form (maxsim_core.hpp) — so every score has the bits
+// the unscoped channel gives that row, and ranks them with the selector of topk.hpp (score descending, ties -> lower id,
+// NaN last, -0.0 as +0.0).  Corpus statistics stay global (idf, avgdl, the MaxSim store's scale).  One slab: the final
+// lists are written directly; several: per-slab lists, merged by launch_merge_parts.  No existing kernel, route or
+// workspace is touched: the handle below owns the slab lists, one region per channel, so the three calls of a step need
+// no ordering among themselves.
+#include "common.hpp"
+#include "topk.hpp"
+
+#include <cfloat>
+#include <cmath>
+#include <cstdlib>
+#include <mutex>
+#include <new>
+
+#include "bm25_core.hpp"
+#include "dense_dot.hpp"
+#include "maxsim_core.hpp"
+
+using namespace amdr;
+
+struct amdr_scope {
+  int device = 0;
+  hipStream_t stream = nullptr;
+  std::mutex mu;
+  // the reserve of the "_device" calls: its sizes and the byte offset / length of each channel's region in ws[0]
+  int nq_max = 0, k_max = 0;
+  int64_t rows_max = 0;
+  size_t off[3] = {0, 0, 0}, len[3] = {0, 0, 0};
+  DevBuf ws[2];  // [0]: "_device" calls, [1]: host-pointer calls (see dense.hip)
+  DevBuf stage;  // host-pointer calls: the table, the query operand and the result lists
+};
+
+namespace {
+
+constexpr int kScWaves = 4;
+constexpr int kScSlabMax = 1024;  // rows per block at most (BM25: 8 KiB of fp64 scores in LDS beside the lists)
+constexpr size_t kScAlign = 256;
+enum { kDense = 0, kBm25 = 1, kMaxsim = 2 };
+
+size_t align_up(size_t b) { return (b + kScAlign - 1) / kScAlign * kScAlign; }
+
+// Rows per block.  Dense: a row is one wave's GEMV step, 64 rows per wave keep a 28-row section in one block and one
+// launch.  BM25: a row is one thread's walk over the query's tokens.  MaxSim: a document is 24 matrix instructions per
+// 32 tokens, 16 documents per wave.  AMDR_SCOPE_SLAB (read per call, and by reserve / workspace_plan) pins the length
+// for all three so that tests reach the multi-slab path at small sizes.
+int scope_slab(int chan) {
+  const char* e = getenv("AMDR_SCOPE_SLAB");
+  if (e && atoi(e) > 0) return atoi(e) < kScSlabMax ? atoi(e) : kScSlabMax;
+  return chan == kDense ? 256 : chan == kBm25 ? 1024 : 64;
+}
+int scope_slabs(int chan, int64_t rows_max) {
+  const int64_t s = scope_slab(chan);
+  const int64_t n = (rows_max + s - 1) / s;
+  return n < 1 ? 1 : (int)n;
+}
+// bytes of a channel's slab lists: scores [slabs, nq, k] then ids [slabs, nq, k]; a single slab writes the final lists
+size_t scope_score_bytes(int chan, int slabs, int nq, int k) {
+  return align_up((size_t)slabs * nq * k * (chan == kBm25 ? sizeof(double) : sizeof(float)));
+}
+size_t scope_region_bytes(int chan, int nq, int k, int64_t rows_max) {
+  const int slabs = scope_slabs(chan, rows_max);
+  if (slabs <= 1) return 0;
+  return scope_score_bytes(chan, slabs, nq, k) + align_up((size_t)slabs * nq * k * sizeof(int64_t));
+}
+
+// this block's piece [lo, hi) of the row list: the slab blockIdx.x of the scope of query q; empty for a qscope outside
+// [0, n_scopes) and for a slab beyond the scope
+__device__ __forceinline__ void scope_piece(const long long* __restrict__ scope_ptr, const int* __restrict__ qscope,
+                                            int n_scopes, int slab, int q, long& lo, long& hi) {
+  lo = hi = 0;
+  const int s = qscope[q];
+  if (s < 0 || s >= n_scopes) return;
+  const long b = scope_ptr[s], e = scope_ptr[s + 1];
+  lo = b + (long)blockIdx.x * slab;
+  hi = lo + slab < e ? lo + slab : e;
+  if (hi < lo) hi = lo;
+}
+
+// ---- dense: one wave per scope row (dense_row_dot), lane 63's score into the wave's list ---------------------------------
+// grid: (x = slabs, y = queries).  LDS: C32 lists[kScWaves][cap] + int cnts[kScWaves]
+__global__ __launch_bounds__(kScWaves * 64) void scope_dense_kernel(
+    const float* __restrict__ X, long n, int d, const float* __restrict__ Q, const long long* __restrict__ scope_ptr,
+    const long long* __restrict__ rows, const int* __restrict__ qscope, int n_scopes, int slab, int nq, int k, int cap,
+    float* __restrict__ part_scores, long long* __restrict__ part_ids, float* __restrict__ fin_scores,
+    long long* __restrict__ fin_ids) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  C32* lists = reinterpret_cast<C32*>(smem);
+  int* cnts = reinterpret_cast<int*>(lists + (size_t)kScWaves * cap);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int q = blockIdx.y;
+  long lo, hi;
+  scope_piece(scope_ptr, qscope, n_scopes, slab, q, lo, hi);
+  WaveTopK<C32> tk;
+  tk.init(lists + (size_t)wave * cap, cap, k);
+  const float* qr = Q + (size_t)q * d;
+  for (long i = lo + wave; i < hi; i += kScWaves) {
+    const long r = uniform_i64(rows[i]);
+    if (r < 0 || r >= n) continue;  // never dereferenced
+    const float acc = dense_row_dot(X + (size_t)r * d, qr, d, lane);
+    const float s = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(acc), 63));
+    tk.push_uniform(C32::make(s, (u32)r), lane);
+  }
+  tk.finalize(lane);
+  block_combine_topk(tk, lists, cap, kScWaves, wave, lane, cnts);
+  if (wave != 0) return;
+  const size_t row = fin_ids ? (size_t)q : (size_t)blockIdx.x * nq + q;
+  topk_store(tk.buf, tk.cnt, k, lane, (fin_ids ? fin_scores : part_scores) + row * k, (fin_ids ? fin_ids : part_ids) + row * k);
+}
+
+// ---- BM25: the slab's fp64 scores in LDS, one thread per scope document, tokens in query order ---------------------------
+// A document's posting in a term's list is found by binary search (scopes are short next to posting lists); a hit adds
+// idf[term] * post_w[p] — a multiply, then an add (this file is built with -ffp-contract=off) — in the order
+// bm25_block_query's scatter gives the same document, duplicates counted, unknown terms skipped: the same bits.
+// grid: (x = slabs, y = queries).  LDS: double sc[slab] + C64 lists[kScWaves][cap] + int cnts[kScWaves] + token table
+__global__ __launch_bounds__(kScWaves * 64) void scope_bm25_kernel(
+    const long long* __restrict__ term_ptr, const int* __restrict__ post_doc, const double* __restrict__ post_w,
+    const double* __restrict__ idf, long n_terms, long n_docs, const int* __restrict__ q_terms,
+    const long long* __restrict__ q_ptr, const long long* __restrict__ scope_ptr, const long long* __restrict__ rows,
+    const int* __restrict__ qscope, int n_scopes, int slab, int nq, int k, int cap, double* __restrict__ part_scores,
+    long long* __restrict__ part_ids, double* __restrict__ fin_scores, long long* __restrict__ fin_ids) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  double* sc = reinterpret_cast<double*>(smem);
+  C64* lists = reinterpret_cast<C64*>(sc + slab);
+  int* cnts = reinterpret_cast<int*>(lists + (size_t)kScWaves * cap);
+  long* tk_ps = reinterpret_cast<long*>(cnts + kScWaves);  // posting range + idf of up to kBmTok query tokens at a time
+  long* tk_pe = tk_ps + kBmTok;
+  double* tk_w = reinterpret_cast<double*>(tk_pe + kBmTok);
+  int* tk_n = reinterpret_cast<int*>(tk_w + kBmTok);
+  constexpr int NT = kScWaves * 64;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int q = blockIdx.y;
+  long lo, hi;
+  scope_piece(scope_ptr, qscope, n_scopes, slab, q, lo, hi);
+  const int m = (int)(hi - lo);
+  for (int i = tid; i < m; i += NT) sc[i] = 0.0;
+  __syncthreads();
+  if (m > 0) {  // block-uniform; an empty piece reads nothing
+    const long t0 = q_ptr[q], t1 = q_ptr[q + 1];
+    for (long tb = t0; tb < t1; tb += kBmTok) {
+      const int nt_all = (int)((t1 - tb) < kBmTok ? (t1 - tb) : kBmTok);
+      if (tid < 64) {
+        long ps = 0, pe = 0;
+        double w = 0.0;
+        if (tid < nt_all) {
+          const int term = q_terms[tb + tid];
+          if (term >= 0 && term < n_terms) {  // unknown token: skipped
+            ps = term_ptr[term];
+            pe = term_ptr[term + 1];
+            w = idf[term];
+          }
+        }
+        const bool keep = pe > ps;  // kept in query order
+        const unsigned long long km = __ballot(keep);
+        const unsigned long long below = (tid == 0) ? 0ull : (km & (~0ull >> (64 - tid)));
+        if (keep) {
+          const int at = __popcll(below);
+          tk_ps[at] = ps;
+          tk_pe[at] = pe;
+          tk_w[at] = w;
+        }
+        if (tid == 0) *tk_n = __popcll(km);
+      }
+      __syncthreads();
+      const int nt = *tk_n;
+      for (int i = tid; i < m; i += NT) {
+        const long doc = rows[lo + i];
+        if (doc < 0 || doc >= n_docs) continue;
+        double s = sc[i];
+        for (int t = 0; t < nt; ++t) {
+          const long pe = tk_pe[t];
+          const long p = lower_bound_i32(post_doc, tk_ps[t], pe, (int)doc);
+          if (p < pe && post_doc[p] == (int)doc) s += tk_w[t] * post_w[p];
+        }
+        sc[i] = s;
+      }
+      __syncthreads();  // the table is rewritten by the next group
+    }
+  }
+  WaveTopK<C64> tk;
+  tk.init(lists + (size_t)wave * cap, cap, k);
+  for (int base = wave * 64; base < m; base += NT) {
+    const int i = base + lane;
+    const long doc = i < m ? rows[lo + i] : -1;
+    const bool v = doc >= 0 && doc < n_docs;  // zero-score documents ARE ranked
+    tk.push_lanes(v ? C64::make(sc[i], doc) : C64::pad(), v, lane);
+  }
+  tk.finalize(lane);
+  block_combine_topk(tk, lists, cap, kScWaves, wave, lane, cnts);
+  if (wave != 0) return;
+  const size_t row = fin_ids ? (size_t)q : (size_t)blockIdx.x * nq + q;
+  double* so = (fin_ids ? fin_scores : part_scores) + row * k;
+  long long* io = (fin_ids ? fin_ids : part_ids) + row * k;
+  for (int j = lane; j < k; j += 64) {
+    const bool v = j < tk.cnt;
+    so[j] = v ? unord64(tk.buf[j].key) : -DBL_MAX;
+    io[j] = v ? tk.buf[j].idv : -1ll;
+  }
+}
+
+// ---- MaxSim: one wave per (query, scope document), the pair form of maxsim_scores_h_kernel -------------------------------
+// grid: (x = slabs, y = queries).  LDS: C32 lists[kScWaves][cap] + int cnts[kScWaves]
+__global__ __launch_bounds__(kScWaves * 64) void scope_maxsim_kernel(
+    const unsigned char* __restrict__ img, const long long* __restrict__ doc_ptr, long n_docs, const float* __restrict__ Q,
+    int q_len, float unscale_d, const long long* __restrict__ scope_ptr, const long long* __restrict__ rows,
+    const int* __restrict__ qscope, int n_scopes, int slab, int nq, int k, int cap, float* __restrict__ part_scores,
+    long long* __restrict__ part_ids, float* __restrict__ fin_scores, long long* __restrict__ fin_ids) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  C32* lists = reinterpret_cast<C32*>(smem);
+  int* cnts = reinterpret_cast<int*>(lists + (size_t)kScWaves * cap);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int q = blockIdx.y;
+  const int r32 = lane & 31, h = lane >> 5;
+  long lo, hi;
+  scope_piece(scope_ptr, qscope, n_scopes, slab, q, lo, hi);
+  WaveTopK<C32> tk;
+  tk.init(lists + (size_t)wave * cap, cap, k);
+  if (lo + wave < hi) {  // wave-uniform: a wave without a document does not read its query
+    ms8h qh[8], ql[8];
+    float unscale;
+    ms_load_query_h(Q + (size_t)q * q_len * kDim, q_len, true, r32, h, qh, ql, unscale);
+    unscale *= unscale_d;
+    for (long i = lo + wave; i < hi; i += kScWaves) {
+      const long doc = uniform_i64(rows[i]);
+      if (doc < 0 || doc >= n_docs) continue;
+      const long t_lo = doc_ptr[doc];
+      const int len = (int)(doc_ptr[doc + 1] - t_lo);
+      const float total = ms_pair_doc_h(img, t_lo, len, qh, ql, r32, h, q_len, unscale);
+      tk.push_uniform(C32::make(total, (u32)doc), lane);
+    }
+  }
+  tk.finalize(lane);
+  block_combine_topk(tk, lists, cap, kScWaves, wave, lane, cnts);
+  if (wave != 0) return;
+  const size_t row = fin_ids ? (size_t)q : (size_t)blockIdx.x * nq + q;
+  topk_store(tk.buf, tk.cnt, k, lane, (fin_ids ? fin_scores : part_scores) + row * k, (fin_ids ? fin_ids : part_ids) + row * k);
+}
+
+// ---- host side --------------------------------------------------------------------------------------------------------------
+struct ScTable {  // device pointers
+  const long long* scope_ptr;
+  const long long* rows;
+  const int* qscope;
+  int n_scopes;
+  int64_t rows_max;
+};
+
+int sc_check_table(const char* who, const void* scope_ptr, const void* rows, const void* qscope, int n_scopes,
+                   int64_t rows_max, int nq, int k) {
+  AMDR_REQUIRE(nq >= 0, "%s: nq=%d", who, nq);
+  AMDR_REQUIRE(k >= 1 && k <= AMDR_MAX_K, "%s: k=%d outside [1,%d]", who, k, AMDR_MAX_K);
+  AMDR_REQUIRE(n_scopes >= 0 && rows_max >= 0, "%s: bad table sizes", who);
+  AMDR_REQUIRE(nq == 0 || (scope_ptr && qscope), "%s: null table", who);
+  AMDR_REQUIRE(rows_max == 0 || rows, "%s: null rows", who);
+  return AMDR_OK;
+}
+
+// where a "_device" call of this channel keeps its slab lists: inside the reserve, or AMDR_EINVAL
+int sc_device_region(amdr_scope* s, int chan, int nq, int k, int64_t rows_max, unsigned char** base) {
+  AMDR_REQUIRE(nq <= s->nq_max && k <= s->k_max && rows_max <= s->rows_max,
+               "scope: a call of nq=%d k=%d rows_max=%lld beyond the reserve (%d, %d, %lld)", nq, k, (long long)rows_max,
+               s->nq_max, s->k_max, (long long)s->rows_max);
+  const size_t need = scope_region_bytes(chan, nq, k, rows_max);
+  AMDR_REQUIRE(need <= s->len[chan], "scope: slab lists of %zu bytes in a region of %zu (AMDR_SCOPE_SLAB changed since the reserve?)",
+               need, s->len[chan]);
+  *base = s->ws[0].as<unsigned char>() + s->off[chan];
+  return AMDR_OK;
+}
+
+// Launches of one channel: the grid's y holds at most 65 535 queries, longer batches go in pieces.  launch(q0, m, slabs,
+// part_scores, part_ids, direct) enqueues the scoring kernel of queries [q0, q0 + m).
+template <class T, class Launch>
+int sc_run(int chan, int nq, int k, int64_t rows_max, unsigned char* region, T* scores_dev, int64_t* ids_dev, hipStream_t st,
+           Launch&& launch) {
+  const int slab = scope_slab(chan), slabs = scope_slabs(chan, rows_max);
+  const int cap = topk_cap(k);
+  for (int q0 = 0; q0 < nq; q0 += 65535) {
+    const int m = nq - q0 < 65535 ? nq - q0 : 65535;
+    T* ps = nullptr;
+    int64_t* pi = nullptr;
+    if (slabs > 1) {
+      ps = reinterpret_cast<T*>(region);
+      pi = reinterpret_cast<int64_t*>(region + scope_score_bytes(chan, slabs, nq, k));
+    }
+    launch(q0, m, slab, slabs, cap, ps, pi);
+    AMDR_HIP(hipGetLastError());
+    if (slabs > 1) {
+      int rc = launch_merge_parts<T>(ps, pi, slabs, m, k, k, scores_dev + (size_t)q0 * k, ids_dev + (size_t)q0 * k, st);
+      if (rc) return rc;
+    }
+  }
+  return AMDR_OK;
+}
+
+int sc_dense_run(amdr_dense_t* dense, const float* Q, const ScTable& t, int nq, int k, unsigned char* region,
+                 float* scores_dev, int64_t* ids_dev, hipStream_t st) {
+  const float* X;
+  long n;
+  int d;
+  dense_matrix(dense, &X, &n, &d);
+  return sc_run<float>(kDense, nq, k, t.rows_max, region, scores_dev, ids_dev, st,
+                       [&](int q0, int m, int slab, int slabs, int cap, float* ps, int64_t* pi) {
+                         const size_t lds = (size_t)kScWaves * cap * sizeof(C32) + kScWaves * sizeof(int);
+                         const bool direct = slabs == 1;
+                         hipLaunchKernelGGL(scope_dense_kernel, dim3(slabs, m), dim3(kScWaves * 64), lds, st, X, n, d,
+                                            Q + (size_t)q0 * d, t.scope_ptr, t.rows, t.qscope + q0, t.n_scopes, slab, m, k, cap,
+                                            ps, (long long*)pi, direct ? scores_dev + (size_t)q0 * k : nullptr,
+                                            direct ? (long long*)ids_dev + (size_t)q0 * k : nullptr);
+                       });
+}
+
+int sc_bm25_run(const Bm25Raw& b, const int* q_terms, const long long* q_ptr, const ScTable& t, int nq, int k,
+                unsigned char* region, double* scores_dev, int64_t* ids_dev, hipStream_t st) {
+  return sc_run<double>(kBm25, nq, k, t.rows_max, region, scores_dev, ids_dev, st,
+                        [&](int q0, int m, int slab, int slabs, int cap, double* ps, int64_t* pi) {
+                          const size_t lds = (size_t)slab * sizeof(double) + (size_t)kScWaves * cap * sizeof(C64) +
+                                             kScWaves * sizeof(int) + 3 * kBmTok * sizeof(long) + 8;
+                          const bool direct = slabs == 1;
+                          hipLaunchKernelGGL(scope_bm25_kernel, dim3(slabs, m), dim3(kScWaves * 64), lds, st, b.term_ptr,
+                                             b.post_doc, b.post_w, b.idf, b.n_terms, b.n_docs, q_terms, q_ptr + q0, t.scope_ptr,
+                                             t.rows, t.qscope + q0, t.n_scopes, slab, m, k, cap, ps, (long long*)pi,
+                                             direct ? scores_dev + (size_t)q0 * k : nullptr,
+                                             direct ? (long long*)ids_dev + (size_t)q0 * k : nullptr);
+                        });
+}
+
+int sc_maxsim_run(const MaxsimRaw& r, const float* Q, int q_len, const ScTable& t, int nq, int k, unsigned char* region,
+                  float* scores_dev, int64_t* ids_dev, hipStream_t st) {
+  return sc_run<float>(kMaxsim, nq, k, t.rows_max, region, scores_dev, ids_dev, st,
+                       [&](int q0, int m, int slab, int slabs, int cap, float* ps, int64_t* pi) {
+                         const size_t lds = (size_t)kScWaves * cap * sizeof(C32) + kScWaves * sizeof(int);
+                         const bool direct = slabs == 1;
+                         hipLaunchKernelGGL(scope_maxsim_kernel, dim3(slabs, m), dim3(kScWaves * 64), lds, st, r.img, r.doc_ptr,
+                                            r.n_docs, Q + (size_t)q0 * q_len * kDim, q_len, r.unscale_d, t.scope_ptr, t.rows,
+                                            t.qscope + q0, t.n_scopes, slab, m, k, cap, ps, (long long*)pi,
+                                            direct ? scores_dev + (size_t)q0 * k : nullptr,
+                                            direct ? (long long*)ids_dev + (size_t)q0 * k : nullptr);
+                       });
+}
+
+// the split-fp16 image a scoped MaxSim call needs (the pair form of maxsim_scores_h_kernel); AMDR_MAXSIM_F16X3=0 pins
+// the fp32-input forms of the unscoped channel, which have no scoped counterpart
+int sc_maxsim_raw(amdr_maxsim_t* h, int q_len, MaxsimRaw* r) {
+  AMDR_REQUIRE(h != nullptr, "scope_maxsim: null handle");
+  AMDR_REQUIRE(q_len >= 1 && q_len <= AMDR_MAXSIM_QLEN, "scope_maxsim: q_len=%d outside [1,%d]", q_len, AMDR_MAXSIM_QLEN);
+  int rc = maxsim_raw(h, r);
+  if (rc) return rc;
+  const char* e = getenv("AMDR_MAXSIM_F16X3");
+  AMDR_REQUIRE(!(e && e[0] == '0'), "scope_maxsim: AMDR_MAXSIM_F16X3=0 pins the fp32-input form; the scoped search has the split-fp16 form only");
+  AMDR_REQUIRE(r->img != nullptr, "scope_maxsim: the store has no split-fp16 image (it holds a NaN or an infinity)");
+  AMDR_REQUIRE(r->n_docs < (1ll << 32), "scope_maxsim: too many documents");
+  return AMDR_OK;
+}
+
+// Host table -> device (stage buffer of the handle, on its stream), validated: scope_ptr monotone from >= 0, every
+// scope's rows strictly ascending inside [0, n).  qscope may hold any value (outside [0, n_scopes): all padding).
+// Layout of the stage buffer: scope_ptr | rows | qscope | operand bytes | scores | ids, each aligned.
+struct ScStage {
+  ScTable t;
+  unsigned char* operand;
+  unsigned char* scores;
+  int64_t* ids;
+};
+int sc_stage(amdr_scope* s, const char* who, const int64_t* scope_ptr, const int64_t* rows, const int32_t* qscope,
+             int n_scopes, int64_t n, int nq, int k, size_t operand_bytes, size_t score_size, ScStage* out) {
+  AMDR_REQUIRE(scope_ptr[0] >= 0, "%s: scope_ptr[0] < 0", who);
+  int64_t rows_max = 0;
+  for (int i = 0; i < n_scopes; ++i) {
+    AMDR_REQUIRE(scope_ptr[i + 1] >= scope_ptr[i], "%s: scope_ptr not monotone at %d", who, i);
+    const int64_t len = scope_ptr[i + 1] - scope_ptr[i];
+    rows_max = len > rows_max ? len : rows_max;
+  }
+  const int64_t total = scope_ptr[n_scopes];
+  AMDR_REQUIRE(total == 0 || rows, "%s: null rows", who);
+  for (int i = 0; i < n_scopes; ++i)
+    for (int64_t j = scope_ptr[i]; j < scope_ptr[i + 1]; ++j) {
+      AMDR_REQUIRE(rows[j] >= 0 && rows[j] < n, "%s: row %lld of scope %d outside [0,%lld)", who, (long long)rows[j], i,
+                   (long long)n);
+      AMDR_REQUIRE(j == scope_ptr[i] || rows[j] > rows[j - 1], "%s: rows of scope %d not strictly ascending", who, i);
+    }
+  const size_t b_ptr = align_up((size_t)(n_scopes + 1) * sizeof(int64_t)), b_rows = align_up((size_t)total * sizeof(int64_t)),
+               b_qs = align_up((size_t)nq * sizeof(int32_t)), b_op = align_up(operand_bytes),
+               b_sc = align_up((size_t)nq * k * score_size), b_id = align_up((size_t)nq * k * sizeof(int64_t));
+  int rc = s->stage.ensure(b_ptr + b_rows + b_qs + b_op + b_sc + b_id);
+  if (rc) return rc;
+  unsigned char* p = s->stage.as<unsigned char>();
+  AMDR_HIP(hipMemcpyAsync(p, scope_ptr, (size_t)(n_scopes + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s->stream));
+  if (total) AMDR_HIP(hipMemcpyAsync(p + b_ptr, rows, (size_t)total * sizeof(int64_t), hipMemcpyHostToDevice, s->stream));
+  AMDR_HIP(hipMemcpyAsync(p + b_ptr + b_rows, qscope, (size_t)nq * sizeof(int32_t), hipMemcpyHostToDevice, s->stream));
+  out->t = ScTable{reinterpret_cast<const long long*>(p), reinterpret_cast<const long long*>(p + b_ptr),
+                   reinterpret_cast<const int*>(p + b_ptr + b_rows), n_scopes, rows_max};
+  out->operand = p + b_ptr + b_rows + b_qs;
+  out->scores = out->operand + b_op;
+  out->ids = reinterpret_cast<int64_t*>(out->scores + b_sc);
+  return AMDR_OK;
+}
+int sc_unstage(amdr_scope* s, const ScStage& g, int nq, int k, size_t score_size, void* scores_host, int64_t* ids_host) {
+  AMDR_HIP(hipMemcpyAsync(scores_host, g.scores, (size_t)nq * k * score_size, hipMemcpyDeviceToHost, s->stream));
+  AMDR_HIP(hipMemcpyAsync(ids_host, g.ids, (size_t)nq * k * sizeof(int64_t), hipMemcpyDeviceToHost, s->stream));
+  AMDR_HIP(hipStreamSynchronize(s->stream));
+  return AMDR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int amdr_scope_create(int32_t device, amdr_scope_t** out) {
+  AMDR_REQUIRE(out != nullptr, "scope_create: out is null");
+  *out = nullptr;
+  int rc = check_device(device);
+  if (rc) return rc;
+  amdr_scope* s = new (std::nothrow) amdr_scope();
+  if (!s) return fail(AMDR_ENOMEM, "scope_create: host alloc");
+  s->device = device;
+  if (hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess) {
+    delete s;
+    return fail(AMDR_EHIP, "scope_create: stream");
+  }
+  *out = s;
+  return AMDR_OK;
+}
+
+int amdr_scope_reserve(amdr_scope_t* s, int32_t nq_max, int32_t k_max, int64_t rows_max) {
+  AMDR_REQUIRE(s != nullptr, "scope_reserve: null handle");
+  AMDR_REQUIRE(nq_max >= 1 && k_max >= 1 && k_max <= AMDR_MAX_K && rows_max >= 0, "scope_reserve: bad sizes");
+  std::lock_guard<std::mutex> g(s->mu);
+  AMDR_HIP(hipSetDevice(s->device));
+  size_t off[3], len[3], total = 0;
+  for (int c = 0; c < 3; ++c) {
+    off[c] = total;
+    len[c] = scope_region_bytes(c, nq_max, k_max, rows_max);
+    total += len[c];
+  }
+  int rc = s->ws[0].ensure(total);
+  if (rc) return rc;
+  for (int c = 0; c < 3; ++c) s->off[c] = off[c], s->len[c] = len[c];
+  s->nq_max = nq_max;
+  s->k_max = k_max;
+  s->rows_max = rows_max;
+  return AMDR_OK;
+}
+
+int amdr_scope_workspace_plan(int32_t nq_max, int32_t k_max, int64_t rows_max_reserve, int32_t nq, int32_t k,
+                              int64_t rows_max, int64_t* out6) {
+  AMDR_REQUIRE(out6 != nullptr, "scope_workspace_plan: null");
+  AMDR_REQUIRE(nq_max >= 1 && k_max >= 1 && k_max <= AMDR_MAX_K && nq >= 1 && k >= 1 && k <= AMDR_MAX_K &&
+                   rows_max_reserve >= 0 && rows_max >= 0,
+               "scope_workspace_plan: bad sizes");
+  for (int c = 0; c < 3; ++c) {
+    out6[c] = (int64_t)scope_region_bytes(c, nq_max, k_max, rows_max_reserve);
+    out6[3 + c] = (int64_t)scope_region_bytes(c, nq, k, rows_max);
+  }
+  return AMDR_OK;
+}
+
+int amdr_scope_plan_info(const amdr_scope_t* s, int32_t nq, int32_t k, int64_t rows_max, char* buf, int32_t buf_len) {
+  AMDR_REQUIRE(s && buf && buf_len > 0, "scope_plan_info: null");
+  AMDR_REQUIRE(nq >= 1 && k >= 1 && k <= AMDR_MAX_K && rows_max >= 0, "scope_plan_info: bad sizes");
+  const int sd = scope_slabs(kDense, rows_max), sb = scope_slabs(kBm25, rows_max), sm = scope_slabs(kMaxsim, rows_max);
+  snprintf(buf, buf_len,
+           "scope_dense_kernel slabs=%d of <= %d rows%s; scope_bm25_kernel slabs=%d of <= %d%s; scope_maxsim_kernel slabs=%d of <= %d%s",
+           sd, scope_slab(kDense), sd == 1 ? " (direct)" : " + merge_parts_kernel", sb, scope_slab(kBm25),
+           sb == 1 ? " (direct)" : " + merge_parts_kernel", sm, scope_slab(kMaxsim),
+           sm == 1 ? " (direct)" : " + merge_parts_kernel");
+  return AMDR_OK;
+}
+
+int amdr_scope_dense_search_device(amdr_scope_t* s, amdr_dense_t* dense, const float* Q_dev, const int64_t* scope_ptr_dev,
+                                   const int64_t* rows_dev, const int32_t* qscope_dev, int32_t n_scopes, int64_t rows_max,
+                                   int32_t nq, int32_t k, float* scores_dev, int64_t* ids_dev, void* stream) {
+  AMDR_REQUIRE(s && dense, "scope_dense: null handle");
+  int rc = sc_check_table("scope_dense", scope_ptr_dev, rows_dev, qscope_dev, n_scopes, rows_max, nq, k);
+  if (rc) return rc;
+  AMDR_REQUIRE(nq == 0 || (Q_dev && scores_dev && ids_dev), "scope_dense: null buffer");
+  AMDR_REQUIRE(dense_device_of(dense) == s->device, "scope_dense: handles on different devices");
+  if (nq == 0) return AMDR_OK;
+  std::lock_guard<std::mutex> g(s->mu);
+  unsigned char* region;
+  if ((rc = sc_device_region(s, kDense, nq, k, rows_max, &region))) return rc;
+  AMDR_HIP(hipSetDevice(s->device));
+  const ScTable t{(const long long*)scope_ptr_dev, (const long long*)rows_dev, qscope_dev, n_scopes, rows_max};
+  return sc_dense_run(dense, Q_dev, t, nq, k, region, scores_dev, ids_dev, (hipStream_t)stream);
+}
+
+int amdr_scope_bm25_search_device(amdr_scope_t* s, amdr_bm25_t* bm25, const int32_t* q_terms_dev, const int64_t* q_ptr_dev,
+                                  const int64_t* scope_ptr_dev, const int64_t* rows_dev, const int32_t* qscope_dev,
+                                  int32_t n_scopes, int64_t rows_max, int32_t nq, int32_t k, double* scores_dev,
+                                  int64_t* ids_dev, void* stream) {
+  AMDR_REQUIRE(s && bm25, "scope_bm25: null handle");
+  int rc = sc_check_table("scope_bm25", scope_ptr_dev, rows_dev, qscope_dev, n_scopes, rows_max, nq, k);
+  if (rc) return rc;
+  AMDR_REQUIRE(nq == 0 || (q_ptr_dev && scores_dev && ids_dev), "scope_bm25: null buffer");
+  AMDR_REQUIRE(bm25_device_of(bm25) == s->device, "scope_bm25: handles on different devices");
+  if (nq == 0) return AMDR_OK;
+  std::lock_guard<std::mutex> g(s->mu);
+  unsigned char* region;
+  if ((rc = sc_device_region(s, kBm25, nq, k, rows_max, &region))) return rc;
+  Bm25Raw b;
+  if ((rc = bm25_small_raw(bm25, nq, k, &b))) return rc;
+  AMDR_HIP(hipSetDevice(s->device));
+  const ScTable t{(const long long*)scope_ptr_dev, (const long long*)rows_dev, qscope_dev, n_scopes, rows_max};
+  return sc_bm25_run(b, q_terms_dev, (const long long*)q_ptr_dev, t, nq, k, region, scores_dev, ids_dev, (hipStream_t)stream);
+}
+
+int amdr_scope_maxsim_search_device(amdr_scope_t* s, amdr_maxsim_t* maxsim, const float* Q_dev, int32_t q_len,
+                                    const int64_t* scope_ptr_dev, const int64_t* rows_dev, const int32_t* qscope_dev,
+                                    int32_t n_scopes, int64_t rows_max, int32_t nq, int32_t k, float* scores_dev,
+                                    int64_t* ids_dev, void* stream) {
+  AMDR_REQUIRE(s != nullptr, "scope_maxsim: null handle");
+  MaxsimRaw r;
+  int rc = sc_maxsim_raw(maxsim, q_len, &r);
+  if (rc) return rc;
+  if ((rc = sc_check_table("scope_maxsim", scope_ptr_dev, rows_dev, qscope_dev, n_scopes, rows_max, nq, k))) return rc;
+  AMDR_REQUIRE(nq == 0 || (Q_dev && scores_dev && ids_dev), "scope_maxsim: null buffer");
+  AMDR_REQUIRE(r.device == s->device, "scope_maxsim: handles on different devices");
+  if (nq == 0) return AMDR_OK;
+  std::lock_guard<std::mutex> g(s->mu);
+  unsigned char* region;
+  if ((rc = sc_device_region(s, kMaxsim, nq, k, rows_max, &region))) return rc;
+  AMDR_HIP(hipSetDevice(s->device));
+  const ScTable t{(const long long*)scope_ptr_dev, (const long long*)rows_dev, qscope_dev, n_scopes, rows_max};
+  return sc_maxsim_run(r, Q_dev, q_len, t, nq, k, region, scores_dev, ids_dev, (hipStream_t)stream);
+}
+
+int amdr_scope_dense_search(amdr_scope_t* s, amdr_dense_t* dense, const float* Q_host, const int64_t* scope_ptr,
+                            const int64_t* rows, const int32_t* qscope, int32_t n_scopes, int32_t nq, int32_t k,
+                            float* scores_host, int64_t* ids_host) {
+  AMDR_REQUIRE(s && dense, "scope_dense: null handle");
+  int rc = sc_check_table("scope_dense", scope_ptr, rows, qscope, n_scopes, 0, nq, k);
+  if (rc) return rc;
+  AMDR_REQUIRE(nq == 0 || (Q_host && scores_host && ids_host), "scope_dense: null buffer");
+  AMDR_REQUIRE(dense_device_of(dense) == s->device, "scope_dense: handles on different devices");
+  if (nq == 0) return AMDR_OK;
+  const float* X;
+  long n;
+  int d;
+  dense_matrix(dense, &X, &n, &d);
+  std::lock_guard<std::mutex> g(s->mu);
+  AMDR_HIP(hipSetDevice(s->device));
+  ScStage st;
+  const size_t qb = (size_t)nq * d * sizeof(float);
+  if ((rc = sc_stage(s, "scope_dense", scope_ptr, rows, qscope, n_scopes, n, nq, k, qb, sizeof(float), &st))) return rc;
+  if ((rc = s->ws[1].ensure(scope_region_bytes(kDense, nq, k, st.t.rows_max)))) return rc;
+  AMDR_HIP(hipMemcpyAsync(st.operand, Q_host, qb, hipMemcpyHostToDevice, s->stream));
+  rc = sc_dense_run(dense, reinterpret_cast<const float*>(st.operand), st.t, nq, k, s->ws[1].as<unsigned char>(),
+                    reinterpret_cast<float*>(st.scores), st.ids, s->stream);
+  if (rc) return rc;
+  return sc_unstage(s, st, nq, k, sizeof(float), scores_host, ids_host);
+}
+
+int amdr_scope_bm25_search(amdr_scope_t* s, amdr_bm25_t* bm25, const int32_t* q_terms, const int64_t* q_ptr,
+                           const int64_t* scope_ptr, const int64_t* rows, const int32_t* qscope, int32_t n_scopes,
+                           int32_t nq, int32_t k, double* scores_host, int64_t* ids_host) {
+  AMDR_REQUIRE(s && bm25, "scope_bm25: null handle");
+  int rc = sc_check_table("scope_bm25", scope_ptr, rows, qscope, n_scopes, 0, nq, k);
+  if (rc) return rc;
+  AMDR_REQUIRE(nq == 0 || (q_ptr && scores_host && ids_host), "scope_bm25: null buffer");
+  AMDR_REQUIRE(bm25_device_of(bm25) == s->device, "scope_bm25: handles on different devices");
+  if (nq == 0) return AMDR_OK;
+  AMDR_REQUIRE(q_ptr[0] == 0, "scope_bm25: q_ptr[0] != 0");
+  for (int i = 0; i < nq; ++i) AMDR_REQUIRE(q_ptr[i + 1] >= q_ptr[i], "scope_bm25: q_ptr not monotone");
+  const int64_t tot = q_ptr[nq];
+  AMDR_REQUIRE(tot == 0 || q_terms, "scope_bm25: null q_terms");
+  std::lock_guard<std::mutex> g(s->mu);
+  Bm25Raw b;
+  if ((rc = bm25_small_raw(bm25, nq, k, &b))) return rc;
+  AMDR_HIP(hipSetDevice(s->device));
+  ScStage st;
+  const size_t pb = align_up((size_t)(nq + 1) * sizeof(int64_t)), tb = (size_t)(tot + 1) * sizeof(int32_t);
+  if ((rc = sc_stage(s, "scope_bm25", scope_ptr, rows, qscope, n_scopes, b.n_docs, nq, k, pb + tb, sizeof(double), &st)))
+    return rc;
+  if ((rc = s->ws[1].ensure(scope_region_bytes(kBm25, nq, k, st.t.rows_max)))) return rc;
+  AMDR_HIP(hipMemcpyAsync(st.operand, q_ptr, (size_t)(nq + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s->stream));
+  if (tot) AMDR_HIP(hipMemcpyAsync(st.operand + pb, q_terms, (size_t)tot * sizeof(int32_t), hipMemcpyHostToDevice, s->stream));
+  rc = sc_bm25_run(b, reinterpret_cast<const int*>(st.operand + pb), reinterpret_cast<const long long*>(st.operand), st.t, nq,
+                   k, s->ws[1].as<unsigned char>(), reinterpret_cast<double*>(st.scores), st.ids, s->stream);
+  if (rc) return rc;
+  return sc_unstage(s, st, nq, k, sizeof(double), scores_host, ids_host);
+}
+
+int amdr_scope_maxsim_search(amdr_scope_t* s, amdr_maxsim_t* maxsim, const float* Q_host, int32_t q_len,
+                             const int64_t* scope_ptr, const int64_t* rows, const int32_t* qscope, int32_t n_scopes,
+                             int32_t nq, int32_t k, float* scores_host, int64_t* ids_host) {
+  AMDR_REQUIRE(s != nullptr, "scope_maxsim: null handle");
+  MaxsimRaw r;
+  int rc = sc_maxsim_raw(maxsim, q_len, &r);
+  if (rc) return rc;
+  if ((rc = sc_check_table("scope_maxsim", scope_ptr, rows, qscope, n_scopes, 0, nq, k))) return rc;
+  AMDR_REQUIRE(nq == 0 || (Q_host && scores_host && ids_host), "scope_maxsim: null buffer");
+  AMDR_REQUIRE(r.device == s->device, "scope_maxsim: handles on different devices");
+  if (nq == 0) return AMDR_OK;
+  std::lock_guard<std::mutex> g(s->mu);
+  AMDR_HIP(hipSetDevice(s->device));
+  ScStage st;
+  const size_t qb = (size_t)nq * q_len * kDim * sizeof(float);
+  if ((rc = sc_stage(s, "scope_maxsim", scope_ptr, rows, qscope, n_scopes, r.n_docs, nq, k, qb, sizeof(float), &st))) return rc;
+  if ((rc = s->ws[1].ensure(scope_region_bytes(kMaxsim, nq, k, st.t.rows_max)))) return rc;
+  AMDR_HIP(hipMemcpyAsync(st.operand, Q_host, qb, hipMemcpyHostToDevice, s->stream));
+  rc = sc_maxsim_run(r, reinterpret_cast<const float*>(st.operand), q_len, st.t, nq, k, s->ws[1].as<unsigned char>(),
+                     reinterpret_cast<float*>(st.scores), st.ids, s->stream);
+  if (rc) return rc;
+  return sc_unstage(s, st, nq, k, sizeof(float), scores_host, ids_host);
+}
+
+int amdr_scope_destroy(amdr_scope_t* s) {
+  if (!s) return AMDR_OK;
+  (void)hipSetDevice(s->device);
+  if (s->stream) {
+    (void)hipStreamSynchronize(s->stream);
+    (void)hipStreamDestroy(s->stream);
+  }
+  s->ws[0].release();
+  s->ws[1].release();
+  s->stage.release();
+  delete s;
+  return AMDR_OK;
+}
+
+}  // extern "C"

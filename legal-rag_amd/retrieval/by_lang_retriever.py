@@ -31,5 +31,9 @@ class ByLangRetriever:
                 self._retrievers[lang] = HybridRetriever(self._retriever_cfgs[lang])
             return self._retrievers[lang]
 
-    def search(self, question: str, llm=None, top_k: int = 10, decision=None):
-        return self._for_lang(detect_lang(question)).search(question, llm=llm, top_k=top_k, decision=decision)
+    def search(self, question: str, llm=None, top_k: int = 10, decision=None, *, scope=None):
+        """`scope` (retrieval/scope.py Scope): passed through to the language's retriever; None: the whole corpus."""
+        retriever = self._for_lang(detect_lang(question))
+        if scope is None:
+            return retriever.search(question, llm=llm, top_k=top_k, decision=decision)
+        return retriever.search(question, llm=llm, top_k=top_k, decision=decision, scope=scope)

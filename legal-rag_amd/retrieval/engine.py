@@ -46,6 +46,7 @@ ONE_LAUNCH = "one_launch"            # both channels and the fusion in one launc
 BM25_THEN_FUSED = "bm25_then_fused"  # BM25, then the dense channel and the fusion as one native call
 CHANNELS = "channels"                # the channels one after the other on the caller's stream, then the fusion
 CHANNELS_SIDE = "channels_side"      # dense / BM25 on the side stream beside MaxSim, then the fusion
+SCOPED = "scoped"                    # every channel ranks each query's own rows (search_batch(scopes=)), then the fusion
 # The one-launch form is asked for up to this many queries and fused candidates per query (the serving call).
 # amdr_hybrid_small_device decides again natively (corpus size, AMDR_HYBRID_SMALL) and falls back by itself to the
 # launches of BM25_THEN_FUSED, so this test only has to be no narrower than the native one.
@@ -133,6 +134,7 @@ class HybridEngine:
         self.graph_limit = 0
         self._graph_key = None
         self._side_stream: Optional[torch.cuda.Stream] = None  # made by the first CHANNELS_SIDE step
+        self.scope: Optional[_native.ScopeWorkspace] = None  # made by the first scoped call / reserve(rows_max=)
 
     def _buf(self, name, shape, dtype):
         key = (name, tuple(shape), dtype)
@@ -190,6 +192,25 @@ class HybridEngine:
         self._send(host, dev, ev, n1 + n2)
         return dev[:n1].view(torch.int64), dev[n1:n1 + n2].view(torch.int32)
 
+    def upload_scopes(self, scope_ptr, rows, qscope, channel: int = 0):
+        """A scope table (numpy: scope_ptr int64 [n_scopes + 1], rows int64, qscope int32 [nq]; retrieval/scope.py
+        ScopeResolver.table) -> the device table the scoped channels take, (scope_ptr, rows, qscope, n_scopes, rows_max),
+        through ONE pinned staging copy enqueued on the current stream.  The same contract as upload_csr: a ring of two
+        staging pairs fenced by events, so the table holds until two more upload_scopes calls of the same `channel`; work
+        that reads it must be enqueued before then on the same stream.  channel (0 dense, 1 BM25, 2 ColBERT): one ring
+        each, so that the three tables of a step whose channels have different row spaces are live together."""
+        scope_ptr, rows, qscope, rows_max = _native.check_scope_table(scope_ptr, rows, qscope)
+        sp8, rw8, qs8 = scope_ptr.view(np.uint8), rows.view(np.uint8), qscope.view(np.uint8)
+        n1, n2, n3 = sp8.size, rw8.size, qs8.size
+        host, dev, ev = self._staging(f"scp{int(channel)}_", n1 + n2 + n3)
+        hv = host.numpy()
+        hv[:n1] = sp8
+        hv[n1:n1 + n2] = rw8
+        hv[n1 + n2:n1 + n2 + n3] = qs8
+        self._send(host, dev, ev, n1 + n2 + n3)
+        return (dev[:n1].view(torch.int64), dev[n1:n1 + n2].view(torch.int64), dev[n1 + n2:n1 + n2 + n3].view(torch.int32),
+                int(scope_ptr.size) - 1, rows_max)
+
     def upload_text(self, ptrs, lens, total: int):
         """Query texts (UTF-8 pointer / length arrays, _native.utf8_views) -> (blob u8 [total], offs i64 [n + 1]) on the
         device: packed straight into pinned staging (amdr_tokenizer_pack: offsets first, then the bytes) and sent up
@@ -238,9 +259,12 @@ class HybridEngine:
         torch.cuda.current_stream(self.tdev).synchronize()
         return tuple(v.copy() for v in packed_views(host.numpy(), nq, w, 1))
 
-    def reserve(self, nq: int, k: int, total_terms: int = 0, bytes_max: int = 0) -> None:
+    def reserve(self, nq: int, k: int, total_terms: int = 0, bytes_max: int = 0, rows_max: int = 0) -> None:
         """bytes_max > 0: text-in steps of up to that many bytes of query text (q_text); BM25 then takes up to bytes_max
-        terms (tokens <= bytes)."""
+        terms (tokens <= bytes).  rows_max > 0: scoped steps (search_batch(scopes=)) whose longest scope has up to that
+        many rows."""
+        if rows_max > 0:
+            self._scope_reserve(nq, k, rows_max)
         if bytes_max > 0 and self.tokenizer is not None:
             self.tokenizer.reserve(nq, bytes_max)
             total_terms = max(total_terms, bytes_max)
@@ -315,6 +339,58 @@ class HybridEngine:
         s = self._buf("cs", (nq, k), torch.float32)
         i = self._buf("ci", (nq, k), torch.int64)
         self.maxsim.search_device(q_tok.data_ptr(), nq, q_len, k, s.data_ptr(), i.data_ptr(), _stream())
+        return s, i
+
+    # -- scoped channels: each query's top-k among its OWN rows (table: upload_scopes) ---------------------------------
+    def _scope_ws(self) -> "_native.ScopeWorkspace":
+        if self.shard_offset is not None:
+            raise ValueError("scoped search does not run on a row-sharded index (a scope's rows are global)")
+        if self.scope is None:
+            self.scope = _native.ScopeWorkspace(device=self.device)
+        return self.scope
+
+    def _scope_reserve(self, nq: int, k: int, rows_max: int) -> "_native.ScopeWorkspace":
+        """The workspace with a reserve that covers (nq, k, rows_max) and everything reserved before (never shrinks)."""
+        ws = self._scope_ws()
+        if nq > ws.nq_max or k > ws.k_max or rows_max > ws.rows_max:
+            ws.reserve(max(nq, ws.nq_max), max(k, ws.k_max), max(rows_max, ws.rows_max))
+        return ws
+
+    def _scope_call(self, table, nq: int, k: int):
+        """The workspace, grown eagerly when the call exceeds its reserve (capture() reserves first), and the table as
+        the pointers the native call takes."""
+        sp, rw, qs, n_scopes, rows_max = table
+        assert sp.is_cuda and sp.dtype == torch.int64 and rw.dtype == torch.int64 and qs.dtype == torch.int32, "scope table"
+        assert int(qs.numel()) == nq, "scope table: one qscope entry per query"
+        ws = self._scope_reserve(nq, k, rows_max)
+        return ws, (sp.data_ptr(), rw.data_ptr(), qs.data_ptr(), int(n_scopes), int(rows_max))
+
+    def dense_topk_scoped(self, q_emb: torch.Tensor, k: int, table):
+        nq = q_emb.shape[0]
+        _check_emb(q_emb)
+        ws, tb = self._scope_call(table, nq, k)
+        s = self._buf("sds", (nq, k), torch.float32)
+        i = self._buf("sdi", (nq, k), torch.int64)
+        ws.dense_search_device(self.dense, q_emb.data_ptr(), tb, nq, k, s.data_ptr(), i.data_ptr(), _stream())
+        return s, i
+
+    def bm25_topk_scoped(self, q_terms: torch.Tensor, q_ptr: torch.Tensor, k: int, table):
+        nq = q_ptr.shape[0] - 1
+        _check_csr(q_terms, q_ptr)
+        ws, tb = self._scope_call(table, nq, k)
+        s = self._buf("sbs", (nq, k), torch.float64)
+        i = self._buf("sbi", (nq, k), torch.int64)
+        ws.bm25_search_device(self.bm25, q_terms.data_ptr(), q_ptr.data_ptr(), tb, nq, k, s.data_ptr(), i.data_ptr(),
+                              _stream())
+        return s, i
+
+    def colbert_topk_scoped(self, q_tok: torch.Tensor, k: int, table):
+        nq, q_len = q_tok.shape[0], q_tok.shape[1]
+        _check_tok(q_tok)
+        ws, tb = self._scope_call(table, nq, k)
+        s = self._buf("scs", (nq, k), torch.float32)
+        i = self._buf("sci", (nq, k), torch.int64)
+        ws.maxsim_search_device(self.maxsim, q_tok.data_ptr(), q_len, tb, nq, k, s.data_ptr(), i.data_ptr(), _stream())
         return s, i
 
     # -- fusion ---------------------------------------------------------------
@@ -396,10 +472,13 @@ class HybridEngine:
     # -- whole pipeline ---------------------------------------------------------
     def search_batch(self, params: _native.FuseParams, k: int, *, q_emb: Optional[torch.Tensor] = None,
                      q_terms: Optional[torch.Tensor] = None, q_ptr: Optional[torch.Tensor] = None,
-                     q_tok: Optional[torch.Tensor] = None, q_text=None) -> BatchResult:
+                     q_tok: Optional[torch.Tensor] = None, q_text=None, scopes=None) -> BatchResult:
         """dense + bm25 (+ colbert) top-k -> fuse -> min_final filter, all on device.
         q_text = (blob u8, offs i64 [nq + 1]) device tensors: the BM25 query side as text, tokenised on the device
-        (tokenize_device) in the same stream, instead of q_terms / q_ptr."""
+        (tokenize_device) in the same stream, instead of q_terms / q_ptr.
+        scopes = (dense table, BM25 table, ColBERT table) (upload_scopes; one per channel's row space, None for a
+        channel that is off): every channel ranks each query's own rows and the fusion — its normalisation included —
+        runs over those lists (the SCOPED form).  Not on a row-sharded engine (ValueError)."""
         flags = None
         if q_text is not None:
             if q_terms is not None or q_ptr is not None:
@@ -413,7 +492,22 @@ class HybridEngine:
         form, exchange = step_form(d_on, b_on, c_on, self.shard_offset is not None, nq, k,
                                    c_on and os.environ.get("AMDR_ENGINE_OVERLAP", "1") != "0")
         d = b = c = None
-        if form == ONE_LAUNCH:  # the serving call (search(): one query at a time)
+        if scopes is not None:
+            if self.shard_offset is not None:
+                raise ValueError("search_batch(scopes=): scoped search does not run on a row-sharded engine")
+            form = SCOPED
+            for on, tb, who in zip((d_on, b_on, c_on), scopes, ("dense", "BM25", "ColBERT")):
+                if on and tb is None:
+                    raise ValueError(f"search_batch(scopes=): the {who} channel runs but has no scope table")
+        if form == SCOPED:  # three short launches on the caller's stream (regions of one workspace: no ordering needed)
+            if d_on:
+                d = self.dense_topk_scoped(q_emb, k, scopes[0])
+            if b_on:
+                b = self.bm25_topk_scoped(q_terms, q_ptr, k, scopes[1])
+            if c_on:
+                c = self.colbert_topk_scoped(q_tok, k, scopes[2])
+            res = self.fuse(params, nq, d, b, c)
+        elif form == ONE_LAUNCH:  # the serving call (search(): one query at a time)
             d, b, res = self._hybrid_small(params, q_emb, q_terms, q_ptr, k)
         elif form == BM25_THEN_FUSED:
             b = self.bm25_topk(q_terms, q_ptr, k)
@@ -456,7 +550,7 @@ class HybridEngine:
     # -- hipGraph form -----------------------------------------------------------
     def capture(self, params: _native.FuseParams, k: int, *, q_emb: Optional[torch.Tensor] = None,
                 q_terms: Optional[torch.Tensor] = None, q_ptr: Optional[torch.Tensor] = None,
-                q_tok: Optional[torch.Tensor] = None, q_text=None, graph: Optional[dict] = None):
+                q_tok: Optional[torch.Tensor] = None, q_text=None, graph: Optional[dict] = None, scopes=None):
         """Record one search_batch over the given tensors into a hipGraph.
 
         Returns (graph, result): `graph.replay()` re-runs the whole step — every kernel of every
@@ -471,6 +565,8 @@ class HybridEngine:
         text written into the same two tensors (same nq, at most blob.numel() bytes, offs[nq] <= that).
         graph = dict(q_emb=, k=, seed_n=, qsel=None): the step ends with graph_topk over the fused list (set_graph
         first); its outputs are result.graph.
+        scopes: the scoped step (search_batch); a replay takes new tables written INTO the same table tensors (same
+        nq; every scope at most the tables' rows_max rows, scope_ptr / rows within the tensors' lengths).
         """
         if self.shard_offset is not None:
             raise RuntimeError("capture: a sharded step contains a collective; it is not recorded into a hipGraph")
@@ -480,13 +576,16 @@ class HybridEngine:
         else:
             nq = (q_emb.shape[0] if q_emb is not None else q_ptr.shape[0] - 1 if q_ptr is not None else q_tok.shape[0])
             self.reserve(int(nq), int(k), int(q_terms.numel()) if q_terms is not None else 0)
+        if scopes is not None:
+            self._scope_reserve(int(nq), int(k), max(1, max(int(tb[4]) for tb in scopes if tb is not None)))
         gstage = graph
         if gstage is not None:
             ng = int(gstage["qsel"].numel()) if gstage.get("qsel") is not None else int(nq)
             self.graph.reserve(ng, int(gstage["k"]), self.graph_limit)
 
         def step():
-            r = self.search_batch(params, k, q_emb=q_emb, q_terms=q_terms, q_ptr=q_ptr, q_tok=q_tok, q_text=q_text)
+            r = self.search_batch(params, k, q_emb=q_emb, q_terms=q_terms, q_ptr=q_ptr, q_tok=q_tok, q_text=q_text,
+                                  scopes=scopes)
             if gstage is not None:
                 r.graph = self.graph_topk(r.ids, r.count, gstage["q_emb"], gstage["k"], gstage["seed_n"],
                                           qsel=gstage.get("qsel"))

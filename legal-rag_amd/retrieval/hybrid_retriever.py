@@ -39,6 +39,7 @@ from .colbert_retriever import ColBERTRetriever
 from .dense_retriever import DenseRetriever
 from .graph_retriever import GraphRetriever
 from .rerankers import RerankerFactory, _to_doc_text
+from .scope import Scope, resolver_for
 
 logger = logging.getLogger("legalrag.retrieval.hybrid_retriever")
 
@@ -186,9 +187,38 @@ class HybridRetriever:
                                         w_bm25=w["bm25"], w_colbert=w["colbert"], min_final_score=min_final)
 
     # ------------------------------------------------------- per-channel APIs
-    def search_dense(self, question: str, top_k: int = 10) -> List[RetrievalHit]:
+    def _scope_workspace(self, device: int) -> "_native.ScopeWorkspace":
+        """The workspace of the per-channel scoped searches (host-pointer calls: serialised inside the handle)."""
+        held = self.__dict__.setdefault("_scope_ws", {})
+        ws = held.get(int(device))
+        if ws is None:
+            ws = held[int(device)] = _native.ScopeWorkspace(device=int(device))
+        return ws
+
+    @staticmethod
+    def _scope_depth(top_k: int, who: str) -> int:
+        if top_k > _native.MAX_K:
+            raise ValueError(f"{who}: a scoped search ranks at most {_native.MAX_K} hits per channel, got top_k={top_k}")
+        return top_k
+
+    def _search_dense_scoped(self, question: str, top_k: int, scope: Scope) -> List[RetrievalHit]:
+        store = self.dense.store
+        store.load()
+        rows = resolver_for(store.chunks).rows(scope)
+        if rows.size == 0:
+            return []  # a scope that matches nothing: no launch
+        index = getattr(store.index, "native", None)
+        if index is None or getattr(store.index, "spec", None) is not None:
+            raise ValueError("search_dense(scope=): needs this package's own, unsharded dense index")
+        scores, ids = self._scope_workspace(index.device).dense_search(
+            index, store._embed([question], is_query=True), [0, rows.size], rows, [0], self._scope_depth(top_k, "search_dense"))
+        return [RetrievalHit(chunk=store.chunks[r], score=float(s), rank=j, source="retriever", semantic_score=float(s))
+                for j, (r, s) in enumerate(zip(ids[0].tolist(), scores[0].tolist()), start=1) if r >= 0]
+
+    def search_dense(self, question: str, top_k: int = 10, *, scope: Optional[Scope] = None) -> List[RetrievalHit]:
+        """`scope`: rank only that part of the corpus (retrieval/scope.py); None: the whole corpus."""
         top_k = max(1, int(top_k))
-        hits = self.dense.search(question, top_k)
+        hits = self.dense.search(question, top_k) if scope is None else self._search_dense_scoped(question, top_k, scope)
         hits.sort(key=lambda h: float(h.score), reverse=True)
         for i, h in enumerate(hits, start=1):
             h.rank = i
@@ -196,11 +226,34 @@ class HybridRetriever:
             h.score_breakdown = {"channel": ["dense"], "dense_raw": float(h.score)}
         return hits
 
-    def search_bm25(self, question: str, top_k: int = 10, tokens: Optional[Sequence[str]] = None) -> List[RetrievalHit]:
-        """`tokens`: the caller's own segmentation of `question` (exact path without jieba)."""
+    def _search_bm25_scoped(self, question: str, top_k: int, tokens: Optional[Sequence[str]], scope: Scope):
+        bm = self.bm25
+        bm.load()
+        rows = resolver_for(bm.chunks).rows(scope)
+        if rows.size == 0:
+            return []
+        if getattr(bm, "shard", None) is not None:
+            raise ValueError("search_bm25(scope=): scoped search does not run on a row-sharded index")
+        if tokens is not None:
+            tokens = list(tokens)
+            bm._tls.exact = True
+        else:
+            tokens = bm.tokenize_query(question)
+        index = bm.gpu_index()
+        scores, ids = self._scope_workspace(bm.device_index).bm25_search(
+            index, [bm.bm25.term_ids(tokens)], [0, rows.size], rows, [0], self._scope_depth(top_k, "search_bm25"))
+        return [(bm.chunks[r], float(s)) for r, s in zip(ids[0].tolist(), scores[0].tolist()) if r >= 0]
+
+    def search_bm25(self, question: str, top_k: int = 10, tokens: Optional[Sequence[str]] = None, *,
+                    scope: Optional[Scope] = None) -> List[RetrievalHit]:
+        """`tokens`: the caller's own segmentation of `question` (exact path without jieba).  `scope`: rank only that
+        part of the corpus (idf and avgdl stay those of the whole index)."""
         top_k = max(1, int(top_k))
         # (a duck-typed retriever with the reference's two-argument search() is still accepted)
-        pairs = self.bm25.search(question, top_k, tokens=tokens) if tokens is not None else self.bm25.search(question, top_k)
+        if scope is not None:
+            pairs = self._search_bm25_scoped(question, top_k, tokens, scope)
+        else:
+            pairs = self.bm25.search(question, top_k, tokens=tokens) if tokens is not None else self.bm25.search(question, top_k)
         hits = [RetrievalHit(chunk=c, score=float(s), rank=i, source="retriever",
                              score_breakdown={"channel": ["bm25"], "bm25_raw": float(s)})
                 for i, (c, s) in enumerate(pairs, start=1)]
@@ -212,13 +265,37 @@ class HybridRetriever:
                 h.score_breakdown["zh_exact"] = False
         return hits
 
-    def search_colbert(self, question: str, top_k: int = 10) -> List[RetrievalHit]:
+    def _search_colbert_scoped(self, question: str, top_k: int, scope: Scope):
+        col = self.colbert
+        if not col.enabled:
+            return []
+        col._load_meta_and_collection()
+        question = (question or "").strip()
+        if not question:
+            return []
+        held = self.__dict__.get("_colbert_chunks")
+        if held is None or held[0] is not col._pid2chunk:  # the ColBERT row space as a list: pid -> chunk (None: no such pid)
+            held = self.__dict__["_colbert_chunks"] = (col._pid2chunk,
+                                                       [col._pid2chunk.get(i) for i in range(max(col._pid2chunk) + 1)])
+        chunks = held[1]
+        rows = resolver_for(chunks).rows(scope)
+        if rows.size == 0:
+            return []
+        if getattr(col, "shard", None) is not None:
+            raise ValueError("search_colbert(scope=): scoped search does not run on a row-sharded index")
+        q_tokens = np.asarray(col._encoder.encode_query(question), dtype=np.float32)[None]
+        scores, ids = self._scope_workspace(col.device_index).maxsim_search(
+            col._searcher, q_tokens, [0, rows.size], rows, [0], self._scope_depth(top_k, "search_colbert"))
+        return [(chunks[r], float(s)) for r, s in zip(ids[0].tolist(), scores[0].tolist()) if r >= 0 and chunks[r] is not None]
+
+    def search_colbert(self, question: str, top_k: int = 10, *, scope: Optional[Scope] = None) -> List[RetrievalHit]:
         top_k = max(1, int(top_k))
         if self.colbert is None:
             return []
         try:
             hits: List[RetrievalHit] = []
-            for item in self.colbert.search(question, top_k):
+            for item in (self.colbert.search(question, top_k) if scope is None
+                         else self._search_colbert_scoped(question, top_k, scope)):
                 if isinstance(item, RetrievalHit):
                     hits.append(item)
                 else:
@@ -359,7 +436,13 @@ class HybridRetriever:
         return eff
 
     # ---------------------------------------------------------- main search
-    def search(self, question: str, llm: Any = None, top_k: int = 10, decision: Any = None) -> List[RetrievalHit]:
+    def search(self, question: str, llm: Any = None, top_k: int = 10, decision: Any = None, *,
+               scope: Optional[Scope] = None) -> List[RetrievalHit]:
+        """`scope` (retrieval/scope.py): every channel ranks only that part of the corpus and the fusion normalises over
+        those lists — the one-question form of search_batch(scopes=).  None: the whole corpus."""
+        if scope is not None:
+            return self.search_batch([question], top_k=top_k, llm=llm, decisions=None if decision is None else [decision],
+                                     scopes=[scope])[0]
         rcfg = self.cfg.retrieval
         top_k = max(1, int(top_k))
         has_gpu = _native.device_count() > 0
@@ -639,11 +722,13 @@ class HybridRetriever:
                 col, q_tok = None, None
         return _Prepared((store, bm, col), q_emb, csr, txt, np.asarray(exact, dtype=bool), q_tok, (t1, t2, time.time()))
 
-    def _run(self, prep: "_Prepared", params: "_native.FuseParams", eff: int, fetch, after=None):
+    def _run(self, prep: "_Prepared", params: "_native.FuseParams", eff: int, fetch, after=None, scope_table=None):
         """Step 2, under the stage lock (one batch at a time through the handles' "_device" workspace,
         include/amdretrieval.h): engine, upload, eng.search_batch on torch's current stream, the ColBERT fallback,
         `after(engine, result)` (the device graph stage), then `fetch(engine, result)` — the ONE synchronise and
-        device-to-host copy of the form the caller decodes.  Returns (what fetch returned, what after returned)."""
+        device-to-host copy of the form the caller decodes.  Returns (what fetch returned, what after returned).
+        scope_table (ScopeResolver.table of the batch): the scoped step — the three channels share one chunk list here
+        (_native_channels), so one table serves them all."""
         import torch
         (store, bm, col), tdev = prep.native, prep.q_emb.device
         with self._stage().lock:
@@ -662,15 +747,22 @@ class HybridRetriever:
             if q_tok is not None:
                 q_tok = (q_tok.to(tdev, dtype=torch.float32).contiguous() if torch.is_tensor(q_tok)
                          else torch.from_numpy(q_tok).to(tdev, non_blocking=True))
+
+            def scoped(e, with_col):
+                if scope_table is None:
+                    return {}
+                tb = e.upload_scopes(*scope_table[:3])
+                return {"scopes": (tb, tb, tb if with_col else None)}
             try:
-                res = eng.search_batch(params, eff, q_emb=prep.q_emb, q_terms=q_terms_d, q_ptr=q_ptr_d, q_tok=q_tok)
+                res = eng.search_batch(params, eff, q_emb=prep.q_emb, q_terms=q_terms_d, q_ptr=q_ptr_d, q_tok=q_tok,
+                                       **scoped(eng, q_tok is not None))
             except _native.NativeError:
                 if col is None or eng.shard_offset is not None:
                     raise  # (row-sharded: a rank must not leave the common exchange on its own, see _prepare)
                 # a failing ColBERT stage (e.g. out of memory) empties that channel, it does not fail the query
                 # (hybrid_retriever.py:244-245, colbert_retriever.py:171-181); a dense / BM25 failure raises again here
                 eng = self._engine(store, bm, None)
-                res = eng.search_batch(params, eff, q_emb=prep.q_emb, q_terms=q_terms_d, q_ptr=q_ptr_d)
+                res = eng.search_batch(params, eff, q_emb=prep.q_emb, q_terms=q_terms_d, q_ptr=q_ptr_d, **scoped(eng, False))
             extra = after(eng, res) if after is not None else None
             return fetch(eng, res), extra
 
@@ -706,29 +798,31 @@ class HybridRetriever:
         return {"rows": rows, "scores": scores, "count": cnt, "channel_mask": cmask, "zh_exact": exact, "chunks": chunks}
 
     def _hit_lists(self, questions: Sequence[str], eff: int, native, min_final: float, q_emb=None,
-                   device_tok: bool = False, after=None):
+                   device_tok: bool = False, after=None, scopes: Optional[Sequence[Scope]] = None):
         """prepare -> run -> hit lists: ([fused hits with score >= min_final per question], (t_after_dense_prep,
         t_after_bm25_prep, t_after_colbert_prep), what `after` returned).  An empty question switches the ColBERT
         channel off for that question (colbert_retriever.py:147-149): the blank questions go as one batch without the
-        channel, the rest as another."""
+        channel, the rest as another.  scopes (one Scope per question, none of them None): the scoped step."""
         store, bm, col = native
         kn = self._knobs()
         params = self._params(kn, min_final)
 
-        def batch(qs, nat, emb, after):
+        def batch(qs, nat, emb, after, sc=None):
             prep = self._prepare(qs, nat, emb, device_tok)
-            host, extra = self._run(prep, params, eff, _fetch_full, after)
+            table = resolver_for(store.chunks).table(sc) if sc is not None else None
+            host, extra = self._run(prep, params, eff, _fetch_full, after, table)
             return self._decode_hits(host, prep.exact, kn, store.chunks), prep.stamps, extra
         blank = [i for i, q in enumerate(questions) if not (q or "").strip()] if col is not None else []
         if not blank:
-            return batch(questions, native, q_emb, after)
+            return batch(questions, native, q_emb, after, scopes)
         if after is not None:
             raise ValueError("graph_channel='device': empty questions are not supported with the ColBERT channel on")
         rest = [i for i in range(len(questions)) if i not in set(blank)]
         out, stamps = [None] * len(questions), (time.time(),) * 3
         for idxs, nat in ((blank, (store, bm, None)), (rest, native)):
             if idxs:
-                part, stamps, _ = batch([questions[i] for i in idxs], nat, None if q_emb is None else q_emb[idxs], None)
+                part, stamps, _ = batch([questions[i] for i in idxs], nat, None if q_emb is None else q_emb[idxs], None,
+                                        None if scopes is None else [scopes[i] for i in idxs])
                 for i, h in zip(idxs, part):
                     out[i] = h
         return out, stamps, None
@@ -744,15 +838,69 @@ class HybridRetriever:
         return sel, int(getattr(rcfg, "graph_seed_k", max(10, top_k * 3)))
 
     # ----------------------------------------------------------- batch form
+    def _split_scopes(self, n: int, scopes, decisions, chunks, who: str):
+        """(plain, scoped, empty): the questions without a scope, with one that names rows of `chunks`, with one that
+        matches nothing.  A graph-mode decision together with a scope raises: the graph channel follows cross-references
+        out of any scope by design."""
+        if len(scopes) != n:
+            raise ValueError(f"{who}: scopes must have one entry per question")
+        if decisions is not None and len(decisions) != n:
+            raise ValueError(f"{who}: decisions must have one entry per question")
+        res = resolver_for(chunks)
+        plain, scoped, empty = [], [], []
+        for i, s in enumerate(scopes):
+            if s is None:
+                plain.append(i)
+                continue
+            if not isinstance(s, Scope):
+                raise TypeError(f"{who}: scopes[{i}] is not a Scope")
+            if decisions is not None and _is_graph_mode(getattr(decisions[i], "mode", None)):
+                raise ValueError(f"{who}: question {i} has a graph-mode decision and a scope; the graph channel follows "
+                                 f"cross-references out of any scope")
+            (scoped if res.rows(s).size else empty).append(i)
+        return plain, scoped, empty
+
+    def _search_batch_scoped(self, questions: List[str], top_k: int, llm: Any, decisions, q_emb, scopes):
+        rcfg = self.cfg.retrieval
+        eff = self._eff_depth(top_k, "search_batch")
+        native = self._native_channels(eff)
+        if native is None:
+            raise RuntimeError("search_batch requires this package's own dense / BM25 (/ ColBERT) retrievers built "
+                               "over the same chunk list")
+        plain, scoped, empty = self._split_scopes(len(questions), scopes, decisions, native[0].chunks, "search_batch")
+        outs: List[Any] = [[] for _ in questions]  # a scope that matches nothing: [] without a launch
+        if plain:  # the unscoped step, as a sub-batch
+            sub = self.search_batch([questions[i] for i in plain], top_k, llm,
+                                    None if decisions is None else [decisions[i] for i in plain],
+                                    None if q_emb is None else q_emb[plain])
+            for i, hits in zip(plain, sub):
+                outs[i] = hits
+        if scoped:
+            qs = [questions[i] for i in scoped]
+            lists, _, _ = self._hit_lists(qs, eff, native, float(getattr(rcfg, "min_final_score", 0.0)),
+                                          None if q_emb is None else q_emb[scoped],
+                                          query_tokenizer_mode(self.cfg) == "device", None, [scopes[i] for i in scoped])
+            if getattr(rcfg, "enable_rerank", False):
+                lists = self._rerank_stage(qs, lists, llm, top_k)
+            for i, hits in zip(scoped, lists):
+                outs[i] = _dedup_keep_best(hits)[:top_k]
+        return outs
+
     def search_batch(self, questions: Sequence[str], top_k: int = 10, llm: Any = None,
-                     decisions: Optional[Sequence[Any]] = None, q_emb=None) -> List[List[RetrievalHit]]:
+                     decisions: Optional[Sequence[Any]] = None, q_emb=None, *,
+                     scopes: Optional[Sequence[Optional[Scope]]] = None) -> List[List[RetrievalHit]]:
         """Throughput form: `search_batch(qs)[i]` == `search(qs[i])` for every stage the configuration enables
         (hybrid_retriever.py:282-384) — one kernel pipeline for the whole batch (dense + BM25 (+ ColBERT) -> fuse
         -> filter), the graph stage per query whose `decisions[i]` asks for it, the rerank stage with the
-        cross-encoder fed in full batches over all queries' candidates and ONE blend launch, dedup, cut."""
+        cross-encoder fed in full batches over all queries' candidates and ONE blend launch, dedup, cut.
+        `scopes` (one Scope or None per question, retrieval/scope.py): a scoped question's channels rank only its part of
+        the corpus and its fusion normalises over those lists; the questions with None run as a sub-batch through the
+        unscoped step; a scope that matches nothing yields [].  A graph-mode decision with a scope raises ValueError."""
         rcfg = self.cfg.retrieval
         top_k = max(1, int(top_k))
         questions = list(questions)
+        if scopes is not None and any(s is not None for s in scopes):
+            return self._search_batch_scoped(questions, top_k, llm, decisions, q_emb, list(scopes))
         sel, seed_n = self._graph_selection(decisions, len(questions), top_k, "search_batch")
         eff = self._eff_depth(top_k, "search_batch")
         native = self._native_channels(eff)
@@ -811,8 +959,54 @@ class HybridRetriever:
             return {n: v.cpu().numpy() for n, v in outs.items()}
         return after, params
 
+    def _arrays_scoped(self, questions: List[str], top_k: int, q_emb, values: bool, decisions, scopes) -> Dict[str, Any]:
+        """search_batch_arrays with scopes: the unscoped questions as one sub-batch, the scoped ones as another (the
+        scoped step), the columns re-interleaved on the host; a scope that matches nothing: count 0."""
+        rcfg = self.cfg.retrieval
+        eff = self._eff_depth(top_k, "search_batch_arrays")
+        native = self._native_channels(eff)
+        if native is None:
+            raise RuntimeError("search_batch_arrays requires this package's own retrievers built over the same chunk list")
+        n = len(questions)
+        plain, scoped, _ = self._split_scopes(n, scopes, decisions, native[0].chunks, "search_batch_arrays")
+        parts = []
+        if plain:
+            parts.append((plain, self.search_batch_arrays([questions[i] for i in plain], top_k,
+                                                          None if q_emb is None else q_emb[plain], values,
+                                                          None if decisions is None else [decisions[i] for i in plain])))
+        if scoped:
+            qs = [questions[i] for i in scoped]
+            if native[2] is not None and any(not (q or "").strip() for q in qs):
+                raise ValueError("search_batch_arrays: empty questions are not supported in the columnar form")
+            prep = self._prepare(qs, native, None if q_emb is None else q_emb[scoped], query_tokenizer_mode(self.cfg) == "device")
+            params = self._params(self._knobs(), float(getattr(rcfg, "min_final_score", 0.0)))
+            table = resolver_for(native[0].chunks).table([scopes[i] for i in scoped])
+            if values:
+                host, _ = self._run(prep, params, eff, _fetch_full, None, table)
+                parts.append((scoped, self._decode_columns(host, prep.exact, top_k, native[0].chunks)))
+            else:
+                host, _ = self._run(prep, params, eff, lambda eng, res: eng.compact_to_host(res, top_k), None, table)
+                parts.append((scoped, self._decode_lean(host, prep.exact, native[0].chunks)))
+        out: Dict[str, Any] = {"rows": np.full((n, top_k), -1, dtype=np.int64), "scores": np.zeros((n, top_k)),
+                               "count": np.zeros(n, dtype=np.int32), "channel_mask": np.zeros((n, top_k), dtype=np.int32),
+                               "zh_exact": np.ones(n, dtype=bool), "chunks": native[0].chunks}
+        if values:
+            out["values"], out["value_names"] = np.zeros((n, top_k, _native.FUSE_NVALS)), dict(_native.FV)
+        for idxs, part in parts:
+            for key, val in part.items():
+                if not (isinstance(val, np.ndarray) and val.shape[:1] == (len(idxs),)):
+                    out.setdefault(key, val)  # value_names, chunks, graph_relation_names
+                    continue
+                if key not in out or out[key].shape[1:] != val.shape[1:] or out[key].dtype != val.dtype:
+                    # (a graph_* column of the unscoped part, or a width below top_k: the same for every part)
+                    fill = -1 if key in ("rows", "graph_rows", "graph_relation") else 0
+                    out[key] = np.full((n,) + val.shape[1:], fill, dtype=val.dtype)
+                out[key][idxs] = val
+        return out
+
     def search_batch_arrays(self, questions: Sequence[str], top_k: int = 10, q_emb=None, values: bool = True,
-                            decisions: Optional[Sequence[Any]] = None) -> Dict[str, Any]:
+                            decisions: Optional[Sequence[Any]] = None, *,
+                            scopes: Optional[Sequence[Optional[Scope]]] = None) -> Dict[str, Any]:
         """`search_batch` without building RetrievalHit objects (pydantic construction, not the GPU, bounds
         `search_batch` at a few thousand queries/s): columnar results for bulk callers (evaluation sweeps,
         offline scoring).  rows[q, j] indexes `self.dense.store.chunks`; entries j >= count[q] are -1 / 0.
@@ -823,9 +1017,12 @@ class HybridRetriever:
         `decisions` (one per question): the graph channel runs on the device for the GRAPH_AUGMENTED ones (when
         cfg.retrieval.enable_graph and a graph is loaded) and the result gains graph_rows / graph_scores (final) /
         graph_semantic / graph_depth / graph_relation (index into graph_relation_names) / graph_edge_conf [n, top_k] and
-        graph_count [n] (0 for the other queries)."""
+        graph_count [n] (0 for the other queries).
+        `scopes`: as search_batch — one Scope or None per question; a scope that matches nothing gives count 0."""
         rcfg = self.cfg.retrieval
         top_k = max(1, int(top_k))
+        if scopes is not None and any(s is not None for s in scopes):
+            return self._arrays_scoped(list(questions), top_k, q_emb, values, decisions, list(scopes))
         eff = self._eff_depth(top_k, "search_batch_arrays")
         native = self._native_channels(eff)
         if native is None:
