@@ -113,6 +113,23 @@ int amdr_dense_workspace_plan(int64_t n, int32_t d, int32_t nq_max, int32_t k_ma
  * Synchronises the device.  The matrix wrapped by amdr_dense_create_from_device must not change while the handle
  * lives (its largest component and row norm are measured at creation). */
 int amdr_dense_hi_counters(amdr_dense_t* h, int64_t* out6);
+/* Optional resident fp16 image of the matrix for the fp16 first pass of large scans (`index.search`,
+ * legalrag/retrieval/dense_retriever.py:42): for every 32-row tile and 64-component chunk the halves fp16(x * 2^-e) that the
+ * pass otherwise rounds from the fp32 matrix in registers, in the order its kernel reads them — the pass then streams half
+ * the bytes and computes the same tile maxima bit for bit, so every id and score bit of a search is what it is without the
+ * image (the exact re-scoring still reads the fp32 matrix, which stays).  Memory: ceil(n / 32) * 32 * d * 2 bytes, owned
+ * by the handle, not workspace (amdr_dense_workspace_plan / amdr_workspace_growths do not count it).
+ * build: synchronous (allocates, converts, waits); a no-op on a handle whose image is current; AMDR_EINVAL for a width
+ * the fp16 first pass does not support (d % 128 != 0 or d < 128), an empty index, or a matrix whose statistics are not
+ * finite (an infinite component or row norm, or a largest component outside 2^+-99); allowed on handles from
+ * amdr_dense_create_from_device.  No search ever builds or allocates it.  amdr_dense_add keeps a present image current: it
+ * converts the new rows, or the whole matrix when the add changes the matrix's power-of-two scale or the image has no
+ * room; if the add leaves the statistics non-finite the image is dropped.  AMDR_DENSE_HI_IMAGE=0 makes searches ignore it.
+ * drop: frees it (waits for the device).  info: out4[0] = 1 if present, out4[1] = bytes allocated, out4[2] = rows covered,
+ * out4[3] = e of the scale 2^-e it was converted with. */
+int amdr_dense_image_build(amdr_dense_t* h);
+int amdr_dense_image_drop(amdr_dense_t* h);
+int amdr_dense_image_info(amdr_dense_t* h, int64_t* out4);
 /* HIP-event bracket around the scan kernel alone (not the merge), recorded on
  * the stream each search is launched on; used by bench.py for the roofline.
  * begin() arms up to max_launches event pairs, end() returns the summed scan

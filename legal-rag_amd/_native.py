@@ -34,7 +34,7 @@ SIGNATURES = {
     "amdr_dense_create": "PliiP", "amdr_dense_create_from_device": "PliiP", "amdr_dense_add": "PPl",
     "amdr_dense_ntotal": "PP", "amdr_dense_dim": "PP", "amdr_dense_reserve": "Pii", "amdr_dense_search": "PPiiPP",
     "amdr_dense_search_device": "PPiiPPP", "amdr_dense_search_fuse_device": "PPiiPPPPiPPPPPPPP", "amdr_hybrid_small_device": "PPPPPiiiPPPPPPPPPPPP", "amdr_dense_small_create": "PP", "amdr_dense_small_approx_device": "PPiPlPP", "amdr_dense_small_destroy": "P", "amdr_dense_two_pass_fallbacks": "PP", "amdr_dense_read_rows": "PllP", "amdr_dense_score_rows": "PPiPiP",
-    "amdr_dense_plan_info": "PiiPi", "amdr_dense_workspace_plan": "liiiiiP", "amdr_dense_hi_counters": "PP", "amdr_dense_profile_begin": "Pi", "amdr_dense_profile_end": "PPP", "amdr_dense_destroy": "P",
+    "amdr_dense_plan_info": "PiiPi", "amdr_dense_workspace_plan": "liiiiiP", "amdr_dense_hi_counters": "PP", "amdr_dense_image_build": "P", "amdr_dense_image_drop": "P", "amdr_dense_image_info": "PP", "amdr_dense_profile_begin": "Pi", "amdr_dense_profile_end": "PPP", "amdr_dense_destroy": "P",
     "amdr_bm25_create": "PPPPPlldddiP", "amdr_bm25_ndocs": "PP", "amdr_bm25_reserve": "Piil", "amdr_bm25_workspace_plan": "liiiiP", "amdr_bm25_plan_info": "PiiPi",
     "amdr_bm25_search": "PPPiiPP", "amdr_bm25_search_device": "PPPiiPPP", "amdr_bm25_scores": "PPPiP",
     "amdr_bm25_destroy": "P",
@@ -156,6 +156,11 @@ def _check(rc: int, what: str) -> None:
     if rc != 0:
         msg = load().amdr_last_error()
         raise NativeError(f"{what} failed (status {rc}): {msg.decode('utf-8', 'replace') if msg else ''}")
+
+
+def dense_hi_supported(d: int) -> bool:
+    """Widths the fp16 first pass of large dense scans (and its resident image) supports: csrc/dense_hi.hip."""
+    return 128 <= int(d) <= 1024 and int(d) % 128 == 0
 
 
 def device_count() -> int:
@@ -348,6 +353,21 @@ class DenseIndex(_Handle):
         out = (C.c_int64 * 6)()
         _check(load().amdr_dense_hi_counters(self._h, out), "amdr_dense_hi_counters")
         return int(out[0]), int(out[1]), int(out[2]), bool(out[3]), int(out[4]), int(out[5])
+
+    def build_image(self) -> None:
+        """Resident fp16 image for the fp16 first pass of large scans (amdr_dense_image_build): synchronous, idempotent,
+        +50 % memory, no returned bit changes.  NativeError for a width the pass does not support or a matrix whose
+        statistics are not finite."""
+        _check(load().amdr_dense_image_build(self._h), "amdr_dense_image_build")
+
+    def drop_image(self) -> None:
+        _check(load().amdr_dense_image_drop(self._h), "amdr_dense_image_drop")
+
+    def image_info(self) -> Tuple[bool, int, int, int]:
+        """(present, bytes, rows covered, e of the scale 2^-e)."""
+        out = (C.c_int64 * 4)()
+        _check(load().amdr_dense_image_info(self._h, out), "amdr_dense_image_info")
+        return bool(out[0]), int(out[1]), int(out[2]), int(out[3])
 
     def profile_begin(self, max_launches: int) -> None:
         _check(load().amdr_dense_profile_begin(self._h, C.c_int32(max_launches)), "amdr_dense_profile_begin")

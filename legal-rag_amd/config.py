@@ -86,10 +86,14 @@ class RetrievalConfig:
     graph_channel: str = "host"          # graph stage of search_batch for GRAPH_AUGMENTED decisions: "host" (walk and
                                          # re-scoring per query, graph_retriever.py) | "device" (one csrc/graph.hip
                                          # call for all graph-mode queries of the batch)
+    dense_image: str = "none"            # resident half-precision copy of the chunk matrix for the fp16 first pass of
+                                         # large dense scans: "none" | "fp16" (+ ceil(n/32)*32*d*2 bytes of HBM; the
+                                         # exact re-scoring keeps every id and score bit, csrc/dense_hi_image.hpp)
 
     def __post_init__(self) -> None:
         query_tokenizer_mode(self)
         graph_channel_mode(self)
+        dense_image_mode(self)
 
 
 QUERY_TOKENIZERS = ("host", "device")
@@ -117,6 +121,20 @@ def graph_channel_mode(cfg) -> str:
     m = "host" if m is None else m
     if m not in GRAPH_CHANNELS:
         raise ValueError(f"retrieval.graph_channel must be one of {GRAPH_CHANNELS}, got {m!r}")
+    return m
+
+
+DENSE_IMAGES = ("none", "fp16")
+
+
+def dense_image_mode(cfg) -> str:
+    """`dense_image` of a RetrievalConfig (or of `cfg.retrieval`): "none" by default; ValueError for any other value
+    than "none" / "fp16"."""
+    r = getattr(cfg, "retrieval", cfg)
+    m = getattr(r, "dense_image", None)
+    m = "none" if m is None else m
+    if m not in DENSE_IMAGES:
+        raise ValueError(f"retrieval.dense_image must be one of {DENSE_IMAGES}, got {m!r}")
     return m
 
 

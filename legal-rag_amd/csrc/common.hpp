@@ -103,15 +103,18 @@ int dense_stats_launch(const float* X, long n, int d, unsigned int* words, hipSt
 long dense_hi2_sample_stride(long n, int qtiles);
 long dense_hi2_sample_items(long n, int qtiles);
 size_t dense_hi2_qcap(long n, int qtiles, int kc);
-int dense_hi2_launch_sample(const float* X, long n, int d, const float* Q, int nq, int qtiles, float* MT, hipStream_t st,
-                            float x_scale);
+// image (nullable): the resident fp16 image of X (dense_hi_image.hpp) — sample and scan then read it instead of X
+int dense_hi2_launch_sample(const float* X, const void* image, long n, int d, const float* Q, int nq, int qtiles, float* MT,
+                            hipStream_t st, float x_scale);
 int dense_hi2_launch_tau(const float* MT, long n, int d, int nq, int qtiles, int kc, float* tau, unsigned int* qcount,
                          int* flag, unsigned int* stats, hipStream_t st);
-int dense_hi2_launch_emit(const float* X, long n, int d, const float* Q, int nq, const float* tau, void* qlist,
+int dense_hi2_launch_emit(const float* X, const void* image, long n, int d, const float* Q, int nq, const float* tau, void* qlist,
                           unsigned int* qcount, size_t qcap, hipStream_t st, float x_scale, int qtiles);
 int dense_hi2_launch_select(const void* qlist, const unsigned int* qcount, size_t qcap, int m, int kc, int k, const float* Q,
                             int d, float row_norm_max, float x_scale, long n_tiles, int* list, int* count, int* unres,
                             int* flag, unsigned int* unresolved, hipStream_t st);
+// rows [row0, n) of X into the image, from the tile that holds row0 on (dense_hi_image.hip)
+int dense_hi_image_launch(const float* X, long row0, long n, int d, float x_scale, void* image, hipStream_t st);
 // the exact tail behind the tile maxima M (dense_mfma.hip): each query's k best tiles, ascending, into list[q][..] (gate,
 // unres: nullable device pointers — null = always, every query; chosen, nullable: the tiles picked already, [m][k] best
 // first, to be ordered only) -> the exact scores of their rows -> the final top-k

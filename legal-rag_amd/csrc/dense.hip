@@ -12,6 +12,7 @@
 #include "common.hpp"
 #include "dense_dot.hpp"
 #include "dense_fp16.hpp"
+#include "dense_hi_image.hpp"
 #include "topk.hpp"
 
 #include <algorithm>
@@ -292,6 +293,12 @@ struct amdr_dense {
   amdr_dense_small_t* small = nullptr;
   bool small_failed = false;
   DevBuf small_eps, small_fb;
+  // optional resident fp16 image of X for the large scan's first pass (dense_hi_image.hpp): made by amdr_dense_image_build
+  // only, kept current by add (image_sync), never touched by a search; not workspace.  Present = it holds img_rows == n
+  // rows converted with img_scale == fp16.x_scale
+  void* img = nullptr;
+  int64_t img_cap_rows = 0, img_rows = 0;
+  float img_scale = 0.f;
   // optional HIP-event ring bracketing the scan kernel alone (bench.py roofline)
   std::vector<hipEvent_t> prof_ev;
   int prof_used = 0;
@@ -430,6 +437,7 @@ struct DensePins {
   int hi_level = -1;           // set, but not a level: the handle keeps the width it has
   bool small_hi = true;        // AMDR_DENSE_SMALL_HI=0 pins the exact form of long batches on a short corpus
   int small_hi_min = 4096;     // AMDR_DENSE_SMALL_HI_MIN: the batch size its fp16 two-pass form starts at
+  bool hi_image = true;        // AMDR_DENSE_HI_IMAGE=0: the fp16 first pass of large scans ignores the handle's image (tests, A/B)
 };
 DensePins read_pins() {
   auto pin = [](const char* name) { const char* e = getenv(name); return e && (e[0] == '0' || e[0] == '1') ? e[0] : '\0'; };
@@ -442,6 +450,7 @@ DensePins read_pins() {
   p.small_hi = pin("AMDR_DENSE_SMALL_HI") != '0';
   const char* mn = getenv("AMDR_DENSE_SMALL_HI_MIN");
   if (mn && atoi(mn) > 0) p.small_hi_min = atoi(mn);
+  p.hi_image = pin("AMDR_DENSE_HI_IMAGE") != '0';
   return p;
 }
 
@@ -825,9 +834,16 @@ int two_level_pass(amdr_dense* h, int ws, const float* Qc, int m, int k, float* 
   return exact_tail(h, ws, p, Qc, m, k, nullptr, nullptr, out_scores, out_ids, st);
 }
 
+// The image the fp16 first pass reads, or null: the fp32 matrix.
+const void* hi_image_of(const amdr_dense* h, const DensePins& pins) {
+  return pins.hi_image && h->img && h->img_rows == h->n && h->img_scale == h->fp16.x_scale ? h->img : nullptr;
+}
+
 // One pass (<= 4 query tiles) of the round-4 tail: see dense_hi.hip.  Launches: sample, tau, one scan per query tile,
 // select, then exact_tail behind the flag: [gated: exact tile maxima, exact select], re-scoring, final top-k.
-int hi2_pass(amdr_dense* h, int ws, const float* Qc, int m, int k, int kc, float* out_scores, int64_t* out_ids, hipStream_t st) {
+// `image` (nullable): the handle's fp16 image — sample and scan read it instead of X; everything behind them is the same.
+int hi2_pass(amdr_dense* h, int ws, const void* image, const float* Qc, int m, int k, int kc, float* out_scores,
+             int64_t* out_ids, hipStream_t st) {
   TwoLevelLayout p;
   two_level_layout(h, m, k, kc, true, &p);
   unsigned char* sm = reinterpret_cast<unsigned char*>(h->smat[ws].p);
@@ -842,7 +858,7 @@ int hi2_pass(amdr_dense* h, int ws, const float* Qc, int m, int k, int kc, float
   int* flag = reinterpret_cast<int*>(ax + p.off_flag);  // (reset by this pass's own tau kernel)
   unsigned int* stats = h->stats.as<unsigned int>();
   int rc;
-  if ((rc = dense_hi2_launch_sample(h->X, (long)h->n, h->d, Qc, m, p.qtiles, MT, st, h->fp16.x_scale))) return rc;
+  if ((rc = dense_hi2_launch_sample(h->X, image, (long)h->n, h->d, Qc, m, p.qtiles, MT, st, h->fp16.x_scale))) return rc;
   if ((rc = dense_hi2_launch_tau(MT, (long)h->n, h->d, m, p.qtiles, kc, tau, qcount, flag, stats, st))) return rc;
   {  // the scan: ONE launch over all query tiles of the pass (the launch the profiling events bracket);
      // AMDR_DENSE_HI_SCANS=split: one launch per query tile (A/B, tests)
@@ -852,7 +868,7 @@ int hi2_pass(amdr_dense* h, int ws, const float* Qc, int m, int k, int kc, float
     for (int y = 0; y < (split ? p.qtiles : 1); ++y) {
       const int q0 = y * qt, mq = split ? (m - q0 < qt ? m - q0 : qt) : m;
       rc = profiled(h, st, [&] {
-        return dense_hi2_launch_emit(h->X, (long)h->n, h->d, Qc + (size_t)q0 * h->d, mq, tau + q0, qlist + (size_t)q0 * p.qcap,
+        return dense_hi2_launch_emit(h->X, image, (long)h->n, h->d, Qc + (size_t)q0 * h->d, mq, tau + q0, qlist + (size_t)q0 * p.qcap,
                                      qcount + q0, p.qcap, st, h->fp16.x_scale, split ? 1 : p.qtiles);
       });
       if (rc) return rc;
@@ -875,13 +891,14 @@ int run_search_two_level(amdr_dense* h, int ws, const DensePins& pins, Route r, 
   const bool capturing = cap_st != hipStreamCaptureStatusNone;
   if (r.hi && !capturing && hi_adapt(h, pins)) r = dense_route(h, pins, nq, k);  // a wider cut, or the pass given up
   const bool hi = r.form == Form::Hi;
+  const void* image = hi_image_of(h, pins);
   int rc;
   for (int q0 = 0; q0 < nq; q0 += r.chunk) {
     const int m = nq - q0 < r.chunk ? nq - q0 : r.chunk;
     const float* Qc = Q_dev + (size_t)q0 * h->d;
     float* os = scores_dev + (size_t)q0 * k;
     int64_t* oi = ids_dev + (size_t)q0 * k;
-    rc = hi ? hi2_pass(h, ws, Qc, m, k, r.kc, os, oi, st) : two_level_pass(h, ws, Qc, m, k, os, oi, st);
+    rc = hi ? hi2_pass(h, ws, image, Qc, m, k, r.kc, os, oi, st) : two_level_pass(h, ws, Qc, m, k, os, oi, st);
     if (rc) return rc;
   }
   if (hi && h->hi_host && !capturing && !h->hi_copy_pending) {  // what hi_adapt reads before a later search
@@ -962,6 +979,36 @@ int update_stats(amdr_dense* h, int64_t row0, int64_t rows) {
   AMDR_HIP(hipMemcpyAsync(words, h->stats.p, sizeof(words), hipMemcpyDeviceToHost, h->stream));
   AMDR_HIP(hipStreamSynchronize(h->stream));
   h->fp16 = dense_fp16_stats(words);
+  return AMDR_OK;
+}
+
+void image_drop(amdr_dense* h) {
+  if (h->img) (void)hipFree(h->img);  // (waits for the device: no scan is reading it any more)
+  h->img = nullptr;
+  h->img_cap_rows = h->img_rows = 0;
+  h->img_scale = 0.f;
+}
+
+// Brings the image up to the matrix: rows [row0, n) converted if the image has room and its scale is still the
+// matrix's, else all of it again in a new allocation (sized like the matrix's own, so that adds within the matrix's
+// capacity find room here too).  The callers have checked that the matrix has rows and finite statistics.  Synchronous
+// on the handle's stream.
+int image_sync(amdr_dense* h, int64_t row0) {
+  if (!h->img || h->img_scale != h->fp16.x_scale || h->n > h->img_cap_rows || row0 > h->img_rows) {
+    image_drop(h);
+    const int64_t cap = h->cap_rows > h->n ? h->cap_rows : h->n;
+    AMDR_HIP(hipMalloc(&h->img, hi_image_bytes((long)cap, h->d)));
+    h->img_cap_rows = hi_image_tiles((long)cap) * kHiTileRows;
+    row0 = 0;
+  }
+  int rc = dense_hi_image_launch(h->X, (long)row0, (long)h->n, h->d, h->fp16.x_scale, h->img, h->stream);
+  if (rc == AMDR_OK && hipStreamSynchronize(h->stream) != hipSuccess) rc = fail(AMDR_EHIP, "dense_image: build failed");
+  if (rc) {
+    image_drop(h);
+    return rc;
+  }
+  h->img_rows = h->n;
+  h->img_scale = h->fp16.x_scale;
   return AMDR_OK;
 }
 
@@ -1089,7 +1136,44 @@ int amdr_dense_add(amdr_dense_t* h, const float* X_host, int64_t n_add) {
   }
   h->lvl_f0 = h->hi_seen[1];
   h->lvl_p0 = (int64_t)h->hi_seen[2];
-  return update_stats(h, row0, n_add);
+  int rc = update_stats(h, row0, n_add);
+  // a handle with an fp16 image keeps it current: the new rows, or all of it when the scale changed or it has no room
+  if (rc == AMDR_OK && h->img) {
+    if (h->fp16.large_scan_ok())
+      rc = image_sync(h, row0);
+    else
+      image_drop(h);  // (no first pass is left to read it)
+  }
+  return rc;
+}
+
+int amdr_dense_image_build(amdr_dense_t* h) {
+  AMDR_REQUIRE(h != nullptr, "dense_image_build: null handle");
+  std::lock_guard<std::mutex> g(h->mu);
+  AMDR_HIP(hipSetDevice(h->device));
+  AMDR_REQUIRE(dense_hi_supported(h->d), "dense_image_build: the fp16 first pass does not support d=%d", h->d);
+  AMDR_REQUIRE(h->n > 0, "dense_image_build: empty index");
+  AMDR_REQUIRE(h->fp16.large_scan_ok(), "dense_image_build: the matrix's statistics are not finite");
+  if (h->img && h->img_rows == h->n && h->img_scale == h->fp16.x_scale) return AMDR_OK;
+  return image_sync(h, 0);
+}
+
+int amdr_dense_image_drop(amdr_dense_t* h) {
+  AMDR_REQUIRE(h != nullptr, "dense_image_drop: null handle");
+  std::lock_guard<std::mutex> g(h->mu);
+  AMDR_HIP(hipSetDevice(h->device));
+  image_drop(h);
+  return AMDR_OK;
+}
+
+int amdr_dense_image_info(amdr_dense_t* h, int64_t* out4) {
+  AMDR_REQUIRE(h && out4, "dense_image_info: null");
+  std::lock_guard<std::mutex> g(h->mu);
+  out4[0] = h->img ? 1 : 0;
+  out4[1] = h->img ? (int64_t)hi_image_bytes((long)h->img_cap_rows, h->d) : 0;
+  out4[2] = h->img ? h->img_rows : 0;
+  out4[3] = h->img ? 1 - dense_fp16_exp(h->img_scale) : 0;  // img_scale = 2^-e = 0.5 * 2^(1 - e)
+  return AMDR_OK;
 }
 
 int amdr_dense_ntotal(const amdr_dense_t* h, int64_t* n) {
@@ -1227,11 +1311,12 @@ int amdr_dense_plan_info(const amdr_dense_t* h, int32_t nq, int32_t k, char* buf
     TwoLevelLayout p;
     two_level_layout(h, m, k, r.kc, true, &p);
     snprintf(buf, buf_len,
-             "dense_hi_tilemax_kernel fp16 first pass queries_per_launch=%d scans_per_launch=%d (%d per scan, one tail): per-query lists of the "
+             "%s fp16 first pass queries_per_launch=%d scans_per_launch=%d (%d per scan, one tail): per-query lists of the "
              "approximate tile maxima above a sampled threshold (every %ld-th tile, width level %d) -> top-%d + rounding-bound "
              "check + exact re-scoring of each query's tiles at or above its cut (<= %d each) + top-k: 4 launches behind the "
              "scan(s), the exact first pass behind a device flag in 2",
-             m, p.qtiles, m < dense_hi_max_queries(h->d) ? m : dense_hi_max_queries(h->d),
+             hi_image_of(h, pins) ? "dense_hi_image_tilemax_kernel (resident fp16 image)" : "dense_hi_tilemax_kernel", m, p.qtiles,
+             m < dense_hi_max_queries(h->d) ? m : dense_hi_max_queries(h->d),
              dense_hi2_sample_stride((long)h->n, p.qtiles), r.hi_level, r.kc, r.kc);
   } else if (r.form == Form::TwoLevel) {
     TwoLevelLayout t;
@@ -1345,6 +1430,7 @@ int amdr_dense_destroy(amdr_dense_t* h) {
     (void)hipStreamDestroy(h->stream);
   }
   if (h->owns && h->X) (void)hipFree(h->X);
+  image_drop(h);
   for (int w = 0; w < 2; ++w) {
     h->part[w].release();
     h->smat[w].release();

@@ -23,11 +23,13 @@
 // 20 M maxima of a 10 M-row scan cost 0.3-0.9 ms of 5 whatever the layout.
 #include "common.hpp"
 #include "dense_fp16.hpp"
+#include "dense_hi_image.hpp"
 #include "topk.hpp"
 
 #include <cfloat>
 #include <cmath>
 #include <cstdlib>
+#include <type_traits>
 
 namespace amdr {
 
@@ -37,12 +39,9 @@ typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 typedef _Float16 h4 __attribute__((ext_vector_type(4)));
 
 constexpr int kHiWaves = 8;
-constexpr int kHiKC = 64;              // floats of every row per chunk
-constexpr int kHiStageBytes = 32 * 128;  // 32 rows x 64 halves
 constexpr int kHiWbufMax = 384;          // entries of a wave's staging buffer at most (hi_wbuf_entries)
 
-// stage: row r (0..31) at byte r*128, its 16-B slot s (0..7) at s ^ ((r >> 1) & 7) (the image of dense_mfma.hip's stage)
-__device__ __forceinline__ int hi_stage_off(int row, int slot) { return row * 128 + ((slot ^ ((row >> 1) & 7)) << 4); }
+// (the stage's byte order, hi_stage_off, and the chunk and stage sizes: dense_hi_image.hpp)
 // query tile: row q (0..63) at byte q * (d * 2), its 16-B chunk c at c ^ (q & 15) (rows alias on the banks: d * 2 % 256 == 0)
 __device__ __forceinline__ int hi_q_off(int q, int chunk, int d) { return q * (d * 2) + ((chunk ^ (q & 15)) << 4); }
 __host__ __device__ constexpr int hi_query_tile(int d) { return d > 896 ? 48 : 64; }
@@ -71,8 +70,13 @@ struct HiEmit {
 };
 constexpr int kHiQShift = 26;  // tiles < 2^26
 
-template <int D64, bool EMIT>  // d / 64
-__device__ __forceinline__ void hi_tilemax_pass(const float* __restrict__ X, long n, const float* __restrict__ Q, int nq,
+// IMG: the rows come from the resident fp16 image (dense_hi_image.hpp) instead of the fp32 matrix — X is the image, and a
+// (tile, chunk) piece is four 16-B loads per lane that go to the stage as they are (the conversion and the stage's byte
+// order were applied by the builder).  Everything behind the stage is the same code: the same fragments, the same MFMAs in
+// the same order, the same maxima bit for bit.
+template <int D64, bool EMIT, bool IMG>  // d / 64
+__device__ __forceinline__ void hi_tilemax_pass(const std::conditional_t<IMG, h8, float>* __restrict__ X, long n,
+                                                const float* __restrict__ Q, int nq,
                                                 float* __restrict__ MT /*[queries][ldMT]*/, long ldMT, float x_scale,
                                                 long tile_stride, long n_items, const HiEmit& em, unsigned char* smem,
                                                 int qoff /* first query of this pass in tau / qlist / qcount */) {
@@ -99,23 +103,32 @@ __device__ __forceinline__ void hi_tilemax_pass(const float* __restrict__ X, lon
   const long gw = (long)blockIdx.x * kHiWaves + wave, nw = (long)gridDim.x * kHiWaves;
   const long t_lo = n_items * gw / nw, t_hi = n_items * (gw + 1) / nw;  // this wave's run of items
   // loader role inside a 1-KiB piece: 4 rows x 256 B; lane: row l >> 4, 16-B piece l & 15 (4 floats)
+  // (IMG: a 1-KiB piece of the image is 8 rows x 128 B in stage order; lane l loads and stores its 16-B unit l)
   const int lrow = lane >> 4, lpiece = lane & 15;
-  auto row_ptr = [&](long item, int p) {
-    long r = item * tile_stride * 32 + 4 * p + lrow;
-    if (r >= n) r = n - 1;  // rows past the end repeat the last row: no effect on a maximum
-    return X + (size_t)r * d + lpiece * 4;
+  constexpr int NP = IMG ? 4 : 8;                    // 16-B loads per lane and chunk
+  constexpr int CSTEP = IMG ? kHiStageBytes / 16 : kHiKC;  // a row pointer's step from chunk to chunk, in elements of X
+  using GV = std::conditional_t<IMG, h8, hi4f>;
+  using XP = const std::conditional_t<IMG, h8, float>*;
+  auto row_ptr = [&](long item, int p) -> XP {
+    if constexpr (IMG) {
+      return X + ((size_t)(item * tile_stride) * NCH * (kHiStageBytes / 16) + p * 64 + lane);
+    } else {
+      long r = item * tile_stride * 32 + 4 * p + lrow;
+      if (r >= n) r = n - 1;  // rows past the end repeat the last row: no effect on a maximum
+      return X + (size_t)r * d + lpiece * 4;
+    }
   };
-  hi4f G[2][8];
-  const float* gpn[8];
+  GV G[2][NP];
+  XP gpn[NP];
   if (t_lo < t_hi) {
 #pragma unroll
-    for (int p = 0; p < 8; ++p) gpn[p] = row_ptr(t_lo, p);
+    for (int p = 0; p < NP; ++p) gpn[p] = row_ptr(t_lo, p);
     // issue order = the steady state's (chunk 0's loads, then chunk 1's): the loop header's vmcnt waits are the
     // minimum over this entry and the back edge, an interleaved order here would drain the queue at every tile start
 #pragma unroll
     for (int c = 0; c < 2; ++c) {
 #pragma unroll
-      for (int p = 0; p < 8; ++p) G[c][p] = __builtin_nontemporal_load(reinterpret_cast<const hi4f*>(gpn[p] + c * kHiKC));
+      for (int p = 0; p < NP; ++p) G[c][p] = __builtin_nontemporal_load(reinterpret_cast<const GV*>(gpn[p] + c * CSTEP));
       __builtin_amdgcn_sched_barrier(0);
     }
   }
@@ -200,9 +213,9 @@ __device__ __forceinline__ void hi_tilemax_pass(const float* __restrict__ X, lon
   };
   for (long t = t_lo; t < t_hi; ++t) {
     const bool has_next = t + 1 < t_hi;
-    const float* gp[8];
+    XP gp[NP];
 #pragma unroll
-    for (int p = 0; p < 8; ++p) {
+    for (int p = 0; p < NP; ++p) {
       gp[p] = gpn[p];
       gpn[p] = row_ptr(has_next ? t + 1 : t, p);
     }
@@ -215,26 +228,31 @@ __device__ __forceinline__ void hi_tilemax_pass(const float* __restrict__ X, lon
     for (int c = 0; c < NCH; ++c) {
       // chunk c: fp32 -> fp16 (4 floats -> 8 bytes per piece), into the stage: row 4 p + lrow, 8-byte half (lpiece & 1) of
       // 16-B slot lpiece >> 1
+      // (IMG: the piece's four 1-KiB parts as they are, lane-linear)
 #pragma unroll
-      for (int p = 0; p < 8; ++p) {
-        const hi4f x = G[c & 1][p];
-        h4 y;
+      for (int p = 0; p < NP; ++p) {
+        if constexpr (IMG) {
+          *reinterpret_cast<h8*>(stage + p * 1024 + lane * 16) = G[c & 1][p];
+        } else {
+          const hi4f x = G[c & 1][p];
+          h4 y;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) y[e] = (_Float16)(x[e] * x_scale);
-        *reinterpret_cast<h4*>(stage + hi_stage_off(4 * p + lrow, lpiece >> 1) + (lpiece & 1) * 8) = y;
+          for (int e = 0; e < 4; ++e) y[e] = hi_half(x[e], x_scale);
+          *reinterpret_cast<h4*>(stage + hi_stage_off(4 * p + lrow, lpiece >> 1) + (lpiece & 1) * 8) = y;
+        }
       }
       // the refill is issued HERE, two chunks ahead of its use (hipcc otherwise sinks the loads towards their first use
       // and the wave waits a full memory latency per chunk: sched_barrier pins them)
       __builtin_amdgcn_sched_barrier(0);
       if (c + 2 < NCH) {
 #pragma unroll
-        for (int p = 0; p < 8; ++p)
-          G[c & 1][p] = __builtin_nontemporal_load(reinterpret_cast<const hi4f*>(gp[p] + (c + 2) * kHiKC));
+        for (int p = 0; p < NP; ++p)
+          G[c & 1][p] = __builtin_nontemporal_load(reinterpret_cast<const GV*>(gp[p] + (c + 2) * CSTEP));
       } else {  // NCH is even: chunk c + 2 - NCH of the next tile lands in the buffer of its parity.  Unconditional (the
                 // run's last tile re-reads its own first chunks): behind a branch hipcc drains vmcnt to 0 at every tile end
 #pragma unroll
-        for (int p = 0; p < 8; ++p)
-          G[c & 1][p] = __builtin_nontemporal_load(reinterpret_cast<const hi4f*>(gpn[p] + (c + 2 - NCH) * kHiKC));
+        for (int p = 0; p < NP; ++p)
+          G[c & 1][p] = __builtin_nontemporal_load(reinterpret_cast<const GV*>(gpn[p] + (c + 2 - NCH) * CSTEP));
       }
       __builtin_amdgcn_sched_barrier(0);
       wave_lds_fence();
@@ -338,9 +356,31 @@ __global__ __launch_bounds__(kHiWaves * 64) void dense_hi_tilemax_kernel(const f
       nq_y = nq - y * QT;
       nq_y = nq_y > QT ? QT : nq_y;
     }
-    hi_tilemax_pass<D64, EMIT>(X, n, Q + (size_t)y * QT * (D64 * 64), nq_y, MT, ldMT, x_scale, tile_stride, n_items, em, smem,
-                               y * QT);
+    hi_tilemax_pass<D64, EMIT, false>(X, n, Q + (size_t)y * QT * (D64 * 64), nq_y, MT, ldMT, x_scale, tile_stride, n_items, em,
+                                      smem, y * QT);
     if (y + 1 < tiles) __syncthreads();  // every wave is done with this tile's queries and lists before the next is converted
+  }
+}
+// The same kernel over the resident fp16 image of X (dense_hi_image.hpp; IMG above): half the bytes, no conversion.
+template <int D64, bool EMIT>
+__global__ __launch_bounds__(kHiWaves * 64) void dense_hi_image_tilemax_kernel(const h8* __restrict__ image, long n,
+                                                                               const float* __restrict__ Q, int nq,
+                                                                               float* __restrict__ MT /*[queries][ldMT]*/,
+                                                                               long ldMT, long tile_stride, long n_items,
+                                                                               HiEmit em) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  constexpr int QT = hi_query_tile(D64 * 64);
+  const int tiles = (EMIT && em.n_qtiles > 1) ? em.n_qtiles : 1;
+#pragma unroll 1
+  for (int y = 0; y < tiles; ++y) {
+    int nq_y = nq;
+    if (tiles > 1) {
+      nq_y = nq - y * QT;
+      nq_y = nq_y > QT ? QT : nq_y;
+    }
+    hi_tilemax_pass<D64, EMIT, true>(image, n, Q + (size_t)y * QT * (D64 * 64), nq_y, MT, ldMT, 1.f, tile_stride, n_items, em,
+                                     smem, y * QT);
+    if (y + 1 < tiles) __syncthreads();
   }
 }
 
@@ -397,20 +437,28 @@ static size_t dense_hi_lds(int d, bool emit) {
          (emit ? (size_t)kHiWaves * hi_wbuf_entries(d) * sizeof(C32) + 128 * sizeof(int) : 0);
 }
 
+// image != nullptr: the scan over the fp16 image of X
 template <int D64, bool EMIT>
-static int launch_hi(const float* X, long n, const float* Q, int nq, int grid, float* MT, long ldMT, float x_scale,
-                     long tile_stride, long n_items, const HiEmit& em, hipStream_t st, int grid_y) {
+static int launch_hi(const float* X, const void* image, long n, const float* Q, int nq, int grid, float* MT, long ldMT,
+                     float x_scale, long tile_stride, long n_items, const HiEmit& em, hipStream_t st, int grid_y) {
   const size_t lds = dense_hi_lds(D64 * 64, EMIT);
-  AMDR_HIP(hipFuncSetAttribute((const void*)dense_hi_tilemax_kernel<D64, EMIT>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)lds));
-  hipLaunchKernelGGL((dense_hi_tilemax_kernel<D64, EMIT>), dim3(grid, grid_y), dim3(kHiWaves * 64), lds, st, X, n, Q, nq, MT,
-                     ldMT, x_scale, tile_stride, n_items, em);
+  if (image) {
+    AMDR_HIP(hipFuncSetAttribute((const void*)dense_hi_image_tilemax_kernel<D64, EMIT>,
+                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL((dense_hi_image_tilemax_kernel<D64, EMIT>), dim3(grid, grid_y), dim3(kHiWaves * 64), lds, st,
+                       (const h8*)image, n, Q, nq, MT, ldMT, tile_stride, n_items, em);
+  } else {
+    AMDR_HIP(hipFuncSetAttribute((const void*)dense_hi_tilemax_kernel<D64, EMIT>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                 (int)lds));
+    hipLaunchKernelGGL((dense_hi_tilemax_kernel<D64, EMIT>), dim3(grid, grid_y), dim3(kHiWaves * 64), lds, st, X, n, Q, nq, MT,
+                       ldMT, x_scale, tile_stride, n_items, em);
+  }
   AMDR_HIP(hipGetLastError());
   return AMDR_OK;
 }
 
 template <bool EMIT>
-static int launch_hi_d(const float* X, long n, int d, const float* Q, int nq, float* MT, long ldMT, float x_scale,
+static int launch_hi_d(const float* X, const void* image, long n, int d, const float* Q, int nq, float* MT, long ldMT, float x_scale,
                        long tile_stride, const HiEmit& em, hipStream_t st, int grid_y, int scan_tiles) {
   if (!dense_hi_supported(d) || nq < 1 || nq > grid_y * scan_tiles * hi_query_tile(d))
     return fail(AMDR_EINVAL, "dense (fp16 first pass): d=%d nq=%d", d, nq);
@@ -428,14 +476,14 @@ static int launch_hi_d(const float* X, long n, int d, const float* Q, int nq, fl
   if (blocks < 1) blocks = 1;
   const int grid = (int)blocks;
   switch (d / 64) {
-    case 2: return launch_hi<2, EMIT>(X, n, Q, nq, grid, MT, ldMT, x_scale, tile_stride, n_items, em, st, grid_y);
-    case 4: return launch_hi<4, EMIT>(X, n, Q, nq, grid, MT, ldMT, x_scale, tile_stride, n_items, em, st, grid_y);
-    case 6: return launch_hi<6, EMIT>(X, n, Q, nq, grid, MT, ldMT, x_scale, tile_stride, n_items, em, st, grid_y);
-    case 8: return launch_hi<8, EMIT>(X, n, Q, nq, grid, MT, ldMT, x_scale, tile_stride, n_items, em, st, grid_y);
-    case 10: return launch_hi<10, EMIT>(X, n, Q, nq, grid, MT, ldMT, x_scale, tile_stride, n_items, em, st, grid_y);
-    case 12: return launch_hi<12, EMIT>(X, n, Q, nq, grid, MT, ldMT, x_scale, tile_stride, n_items, em, st, grid_y);
-    case 14: return launch_hi<14, EMIT>(X, n, Q, nq, grid, MT, ldMT, x_scale, tile_stride, n_items, em, st, grid_y);
-    case 16: return launch_hi<16, EMIT>(X, n, Q, nq, grid, MT, ldMT, x_scale, tile_stride, n_items, em, st, grid_y);
+    case 2: return launch_hi<2, EMIT>(X, image, n, Q, nq, grid, MT, ldMT, x_scale, tile_stride, n_items, em, st, grid_y);
+    case 4: return launch_hi<4, EMIT>(X, image, n, Q, nq, grid, MT, ldMT, x_scale, tile_stride, n_items, em, st, grid_y);
+    case 6: return launch_hi<6, EMIT>(X, image, n, Q, nq, grid, MT, ldMT, x_scale, tile_stride, n_items, em, st, grid_y);
+    case 8: return launch_hi<8, EMIT>(X, image, n, Q, nq, grid, MT, ldMT, x_scale, tile_stride, n_items, em, st, grid_y);
+    case 10: return launch_hi<10, EMIT>(X, image, n, Q, nq, grid, MT, ldMT, x_scale, tile_stride, n_items, em, st, grid_y);
+    case 12: return launch_hi<12, EMIT>(X, image, n, Q, nq, grid, MT, ldMT, x_scale, tile_stride, n_items, em, st, grid_y);
+    case 14: return launch_hi<14, EMIT>(X, image, n, Q, nq, grid, MT, ldMT, x_scale, tile_stride, n_items, em, st, grid_y);
+    case 16: return launch_hi<16, EMIT>(X, image, n, Q, nq, grid, MT, ldMT, x_scale, tile_stride, n_items, em, st, grid_y);
     default: return fail(AMDR_EINVAL, "dense (fp16 first pass): unsupported dim %d", d);
   }
 }
@@ -678,9 +726,9 @@ size_t dense_hi2_qcap(long n, int qtiles, int kc) {
   return e < all ? e : all;
 }
 long dense_hi2_sample_ld(long n, int qtiles) { return (dense_hi2_sample_items(n, qtiles) + 63) / 64 * 64; }
-int dense_hi2_launch_sample(const float* X, long n, int d, const float* Q, int nq, int qtiles, float* MT, hipStream_t st,
-                            float x_scale) {
-  return launch_hi_d<false>(X, n, d, Q, nq, MT, dense_hi2_sample_ld(n, qtiles), x_scale, dense_hi2_sample_stride(n, qtiles),
+int dense_hi2_launch_sample(const float* X, const void* image, long n, int d, const float* Q, int nq, int qtiles, float* MT,
+                            hipStream_t st, float x_scale) {
+  return launch_hi_d<false>(X, image, n, d, Q, nq, MT, dense_hi2_sample_ld(n, qtiles), x_scale, dense_hi2_sample_stride(n, qtiles),
                             HiEmit{}, st, qtiles, 1);
 }
 int dense_hi2_launch_tau(const float* MT, long n, int d, int nq, int qtiles, int kc, float* tau, unsigned int* qcount,
@@ -693,11 +741,11 @@ int dense_hi2_launch_tau(const float* MT, long n, int d, int nq, int qtiles, int
   return AMDR_OK;
 }
 // the scan of ONE query tile: maxima >= tau[q] into the per-query lists
-int dense_hi2_launch_emit(const float* X, long n, int d, const float* Q, int nq, const float* tau, void* qlist,
+int dense_hi2_launch_emit(const float* X, const void* image, long n, int d, const float* Q, int nq, const float* tau, void* qlist,
                           unsigned int* qcount, size_t qcap, hipStream_t st, float x_scale, int qtiles) {
   if ((n + 31) / 32 >= (1l << kHiQShift)) return fail(AMDR_EINVAL, "dense (fp16 first pass): too many tiles");
   const HiEmit em{tau, hi_wbuf_entries(d), (C32*)qlist, qcount, (unsigned int)qcap, qtiles};
-  return launch_hi_d<true>(X, n, d, Q, nq, nullptr, 0, x_scale, 1, em, st, 1, qtiles);
+  return launch_hi_d<true>(X, image, n, d, Q, nq, nullptr, 0, x_scale, 1, em, st, 1, qtiles);
 }
 int dense_hi2_launch_select(const void* qlist, const unsigned int* qcount, size_t qcap, int m, int kc, int k, const float* Q,
                             int d, float row_norm_max, float x_scale, long n_tiles, int* list, int* count, int* unres,

@@ -14,6 +14,7 @@ and ignored because the scan is exact.
 """
 from __future__ import annotations
 
+import logging
 import threading
 from pathlib import Path
 from typing import ClassVar, Dict, List, Tuple
@@ -21,16 +22,43 @@ from typing import ClassVar, Dict, List, Tuple
 import numpy as np
 
 from .. import _native, artifacts, encoders
+from ..config import DENSE_IMAGES, dense_image_mode
 from ..schemas import LawChunk
+
+logger = logging.getLogger(__name__)
+_image_width_logged = False
 
 
 class FlatIPIndex:
     """faiss.Index-shaped facade over _native.DenseIndex."""
 
-    def __init__(self, X: np.ndarray, device: int = 0):
+    def __init__(self, X: np.ndarray, device: int = 0, dense_image: str = "none"):
+        if dense_image not in DENSE_IMAGES:
+            raise ValueError(f"dense_image must be one of {DENSE_IMAGES}, got {dense_image!r}")
         self._idx = _native.DenseIndex(X, device=device)
         self.d = int(X.shape[1])
         self.metric_type = artifacts.METRIC_INNER_PRODUCT
+        self.dense_image = dense_image
+        if dense_image == "fp16":
+            self._build_image()
+
+    def _build_image(self) -> None:
+        """The resident fp16 image for the first pass of large scans (amdr_dense_image_build; `add` keeps it current
+        natively).  A width the pass does not support logs once and serves without it; an empty index has nothing to
+        image."""
+        global _image_width_logged
+        if not _native.dense_hi_supported(self.d):
+            if not _image_width_logged:
+                _image_width_logged = True
+                logger.warning("dense_image=fp16: the fp16 first pass does not support d=%d (a multiple of 128 in "
+                               "[128, 1024]); serving without the image", self.d)
+            return
+        if self._idx.ntotal > 0:
+            self._idx.build_image()
+
+    def image_info(self):
+        """(present, bytes, rows covered, e of the scale 2^-e) of this process's resident fp16 image."""
+        return self._idx.image_info()
 
     @property
     def ntotal(self) -> int:
@@ -62,6 +90,8 @@ class FlatIPIndex:
 
     def add(self, x: np.ndarray) -> None:
         self._idx.add(x)
+        if self.dense_image == "fp16" and not self._idx.image_info()[0]:  # (the index was empty when it was created)
+            self._build_image()
 
     def reconstruct_n(self, i0: int, n: int) -> np.ndarray:
         return self._idx.read_rows(int(i0), int(n))
@@ -77,11 +107,11 @@ class ShardedFlatIPIndex(FlatIPIndex):
     (retrieval/sharding.py) — identical on every rank.  `ntotal` is the global row count; `native` is the local
     index (rows lo .. hi-1 at local ids 0 .. hi-lo-1, `row_offset` = lo)."""
 
-    def __init__(self, X: np.ndarray, spec, device: int = 0):
+    def __init__(self, X: np.ndarray, spec, device: int = 0, dense_image: str = "none"):
         self.spec = spec
         self.n_global = int(X.shape[0])
         self.row_offset, self.row_end = spec.bounds(self.n_global)
-        super().__init__(np.ascontiguousarray(X[self.row_offset:self.row_end]), device=device)
+        super().__init__(np.ascontiguousarray(X[self.row_offset:self.row_end]), device=device, dense_image=dense_image)
         self._device = int(device)
 
     @property
@@ -132,7 +162,8 @@ class VectorStore:
     def from_config(cls, cfg) -> "VectorStore":
         rcfg = cfg.retrieval
         key = (str(rcfg.embedding_model), str(rcfg.faiss_index_file), str(rcfg.faiss_meta_file),
-               f"cuda:{int(getattr(rcfg, 'device', 0))}", str(getattr(rcfg, "shard", None) or "none"))
+               f"cuda:{int(getattr(rcfg, 'device', 0))}", str(getattr(rcfg, "shard", None) or "none"),
+               dense_image_mode(cfg))
         with cls._lock:
             inst = cls._instances_by_key.get(key)
             if inst is None:
@@ -158,8 +189,9 @@ class VectorStore:
             spec = sharding.active_shard(self.cfg.retrieval)
             # row-sharded deployment: only this rank's row block goes to HBM; the chunk list (host) stays whole,
             # global row id == position in it
-            self.index = (ShardedFlatIPIndex(X, spec, device=self.device_index) if spec is not None
-                          else FlatIPIndex(X, device=self.device_index))
+            mode = dense_image_mode(self.cfg)  # "fp16": the image is built right behind the index (each rank its block)
+            self.index = (ShardedFlatIPIndex(X, spec, device=self.device_index, dense_image=mode) if spec is not None
+                          else FlatIPIndex(X, device=self.device_index, dense_image=mode))
             self.chunks = chunks
             self._index_mtime = index_mtime
             self._meta_mtime = meta_mtime
