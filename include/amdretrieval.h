@@ -466,7 +466,8 @@ int amdr_scope_reserve(amdr_scope_t* h, int32_t nq_max, int32_t k_max, int64_t r
  * out6[3+i] <= out6[i] for every nq <= nq_max, k <= k_max, rows_max <= rows_max_reserve (tests/test_scope.py). */
 int amdr_scope_workspace_plan(int32_t nq_max, int32_t k_max, int64_t rows_max_reserve, int32_t nq, int32_t k,
                               int64_t rows_max, int64_t* out6);
-/* which kernels the three scoped calls of (nq, k, rows_max) would launch and how a scope is cut into slabs
+/* which kernels the three scoped calls of (nq, k, rows_max) would launch, how a scope is cut into slabs, and whether the
+ * step of dense + BM25 at depth k each (amdr_hybrid_scope_device) is the one launch of scope_hybrid_kernel
  * (NUL-terminated; no device work) */
 int amdr_scope_plan_info(const amdr_scope_t* h, int32_t nq, int32_t k, int64_t rows_max, char* buf, int32_t buf_len);
 int amdr_scope_dense_search_device(amdr_scope_t* h, amdr_dense_t* dense, const float* Q_dev, const int64_t* scope_ptr_dev,
@@ -480,6 +481,34 @@ int amdr_scope_maxsim_search_device(amdr_scope_t* h, amdr_maxsim_t* maxsim, cons
                                     const int64_t* scope_ptr_dev, const int64_t* rows_dev, const int32_t* qscope_dev,
                                     int32_t n_scopes, int64_t rows_max, int32_t nq, int32_t k, float* scores_dev,
                                     int64_t* ids_dev, void* stream);
+/* The scoped STEP — dense + BM25 top-k of each query's own rows, then the fusion — as one call.  No reference counterpart
+ * (legalrag/retrieval/hybrid_retriever.py:282-384 has no scope argument); it computes what amdr_scope_dense_search_device,
+ * amdr_scope_bm25_search_device and amdr_fuse_device compute from the same arguments, bit for bit: the two channel lists
+ * (dense_scores f32 / dense_ids [nq, kd], bm25_scores f64 / bm25_ids [nq, kb]) and the fused record (out_ids [nq, mo],
+ * out_vals [nq, mo, AMDR_FUSE_NVALS], out_mask [nq, mo], out_count [nq], mo = kd + kb + kc).  The dense and the BM25 scope
+ * come from their own tables (d_* / b_*: their row spaces differ); ids are mapped through each channel's row2uid
+ * (nullable) by the fusion.  Optional ColBERT channel: colbert_ids / colbert_scores [nq, kc] are finished lists, written
+ * by amdr_scope_maxsim_search_device (or anything else) EARLIER on the same stream; kc = 0: none.
+ * When both tables' rows_max fit one slab of their channel (dense 256 rows, BM25 1 024, or the AMDR_SCOPE_SLAB pin) and
+ * kd + kb + kc <= 32 this is ONE launch (scope_hybrid_kernel: one block per query from its first row to its fused hits;
+ * no workspace, no reserve needed, no state in any handle between launches; AMDR_SCOPE_OVERLAP=0 pins its sequential
+ * phase order, same results).  Every other shape, and AMDR_SCOPE_FUSED=0,
+ * runs the three calls named above inside: they need the reserve and return AMDR_EINVAL beyond it.  Either way the call
+ * only enqueues on `stream` and allocates nothing (capturable).  All three handles on one device (AMDR_EINVAL). */
+int amdr_hybrid_scope_device(amdr_scope_t* h, amdr_dense_t* dense, amdr_bm25_t* bm25, const float* Q_dev,
+                             const int32_t* q_terms_dev, const int64_t* q_ptr_dev, const int64_t* d_scope_ptr_dev,
+                             const int64_t* d_rows_dev, const int32_t* d_qscope_dev, int32_t d_n_scopes, int64_t d_rows_max,
+                             const int64_t* b_scope_ptr_dev, const int64_t* b_rows_dev, const int32_t* b_qscope_dev,
+                             int32_t b_n_scopes, int64_t b_rows_max, int32_t nq, int32_t kd, int32_t kb,
+                             const amdr_fuse_params_t* params, const int64_t* dense_row2uid, const int64_t* bm25_row2uid,
+                             const int64_t* colbert_ids, const float* colbert_scores, int32_t kc,
+                             const int64_t* colbert_row2uid, float* dense_scores, int64_t* dense_ids, double* bm25_scores,
+                             int64_t* bm25_ids, int64_t* out_ids, double* out_vals, int32_t* out_mask, int32_t* out_count,
+                             void* stream);
+/* Host-only (no device is touched): *fused = 1 when amdr_hybrid_scope_device of these sizes takes the one-launch form
+ * (AMDR_SCOPE_FUSED and AMDR_SCOPE_SLAB are read per call), *lds_bytes = the dynamic LDS of that launch (0 otherwise). */
+int amdr_hybrid_scope_plan(int32_t nq, int32_t kd, int32_t kb, int32_t kc, int64_t rows_max_dense, int64_t rows_max_bm25,
+                           int32_t* fused, int64_t* lds_bytes);
 int amdr_scope_dense_search(amdr_scope_t* h, amdr_dense_t* dense, const float* Q_host, const int64_t* scope_ptr,
                             const int64_t* rows, const int32_t* qscope, int32_t n_scopes, int32_t nq, int32_t k,
                             float* scores_host, int64_t* ids_host);

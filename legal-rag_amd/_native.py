@@ -57,6 +57,8 @@ SIGNATURES = {
     "amdr_scope_dense_search_device": "PPPPPPiliiPPP", "amdr_scope_bm25_search_device": "PPPPPPPiliiPPP",
     "amdr_scope_maxsim_search_device": "PPPiPPPiliiPPP", "amdr_scope_dense_search": "PPPPPPiiiPP",
     "amdr_scope_bm25_search": "PPPPPPPiiiPP", "amdr_scope_maxsim_search": "PPPiPPPiiiPP", "amdr_scope_destroy": "P",
+    "amdr_hybrid_scope_device": "PPPPPP" + "PPPil" * 2 + "iii" + "PPP" + "PPiP" + "PPPP" + "PPPP" + "P",
+    "amdr_hybrid_scope_plan": "iiiillPP",
 }
 EXPORTS = tuple(SIGNATURES)  # every symbol include/amdretrieval.h declares (checked by tests/test_abi.py)
 _KIND = {"P": C.c_void_p, "i": C.c_int32, "l": C.c_int64, "d": C.c_double}
@@ -749,6 +751,15 @@ def scope_workspace_plan(nq_max: int, k_max: int, rows_max_reserve: int, nq: int
     return tuple(v[:3]), tuple(v[3:])
 
 
+def hybrid_scope_plan(nq: int, kd: int, kb: int, kc: int, rows_max_dense: int, rows_max_bm25: int) -> Tuple[bool, int]:
+    """(whether ScopeWorkspace.hybrid of these sizes is the one launch of scope_hybrid_kernel, its dynamic LDS bytes) —
+    host-only; AMDR_SCOPE_FUSED=0 and AMDR_SCOPE_SLAB are read per call."""
+    fused, lds = C.c_int32(0), C.c_int64(0)
+    _check(load().amdr_hybrid_scope_plan(C.c_int32(nq), C.c_int32(kd), C.c_int32(kb), C.c_int32(kc), C.c_int64(rows_max_dense),
+                                         C.c_int64(rows_max_bm25), C.byref(fused), C.byref(lds)), "amdr_hybrid_scope_plan")
+    return bool(fused.value), int(lds.value)
+
+
 def check_scope_table(scope_ptr, rows, qscope) -> Tuple[np.ndarray, np.ndarray, np.ndarray, int]:
     """(scope_ptr i64 [n_scopes + 1], rows i64, qscope i32 [nq], rows_max) as contiguous arrays of the ABI's types."""
     scope_ptr, rows, qscope = _c(scope_ptr, np.int64).ravel(), _c(rows, np.int64).ravel(), _c(qscope, np.int32).ravel()
@@ -853,6 +864,23 @@ class ScopeWorkspace(_Handle):
                                                       _vp(qs), C.c_int32(ns), C.c_int64(rmax), C.c_int32(nq), C.c_int32(k),
                                                       _vp(scores_ptr), _vp(ids_ptr), _vp(stream)),
                "amdr_scope_maxsim_search_device")
+
+    def hybrid(self, dense: "DenseIndex", bm25: "BM25Index", params: "FuseParams", q_ptr: int, q_terms_ptr: int,
+               q_ptr_ptr: int, dense_table, bm25_table, nq: int, kd: int, kb: int, maps, colbert, lists, outs,
+               stream: int = 0) -> None:
+        """The scoped step as one call (amdr_hybrid_scope_device): the dense and the BM25 top-k of each query's own rows
+        and their fusion — one launch when both scopes fit a slab and kd + kb + kc <= 32, the separate calls inside
+        otherwise.  maps = (dense, BM25, ColBERT) row -> uid pointers (0: none); colbert = (ids, scores, kc) of lists
+        finished earlier on the stream, or None; lists = (dense scores, dense ids, BM25 scores, BM25 ids) and outs =
+        (ids, vals, mask, count): output pointers."""
+        dsp, drw, dqs, dns, drm = dense_table
+        bsp, brw, bqs, bns, brm = bm25_table
+        ci, cs, kc = colbert if colbert is not None else (0, 0, 0)
+        _check(load().amdr_hybrid_scope_device(
+            self._h, dense._h, bm25._h, _vp(q_ptr), _vp(q_terms_ptr), _vp(q_ptr_ptr), _vp(dsp), _vp(drw), _vp(dqs),
+            C.c_int32(dns), C.c_int64(drm), _vp(bsp), _vp(brw), _vp(bqs), C.c_int32(bns), C.c_int64(brm), C.c_int32(nq),
+            C.c_int32(kd), C.c_int32(kb), C.byref(params), _vp(maps[0]), _vp(maps[1]), _vp(ci), _vp(cs), C.c_int32(kc),
+            _vp(maps[2]), *(_vp(x) for x in lists), *(_vp(x) for x in outs), _vp(stream)), "amdr_hybrid_scope_device")
 
 
 def make_fuse_params(*, method: str = "rrf_norm_blend", rrf_k: int = 60, alpha: float = 0.5, w_dense: float = 0.6,

@@ -128,6 +128,10 @@ struct FusePre {
     id[0] = valid ? c.id() : -1ll;
     s[0] = valid ? (double)c.score() : 0.0;
   }
+  __device__ __forceinline__ void bm25(const C64& c, bool valid) {  // the BM25 list (ord64 keys) likewise
+    id[1] = valid ? c.idv : -1ll;
+    s[1] = valid ? unord64(c.key) : 0.0;
+  }
 };
 template <int W, bool PRE>
 __device__ __forceinline__ void fuse_packed_body(const amdr_fuse_params_t& P, const ChanIn& c0, const ChanIn& c1,

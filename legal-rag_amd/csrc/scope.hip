@@ -10,6 +10,9 @@
 // lists are written directly; several: per-slab lists, merged by launch_merge_parts.  No existing kernel, route or
 // workspace is touched: the handle below owns the slab lists, one region per channel, so the three calls of a step need
 // no ordering among themselves.
+// The scoped STEP (dense + BM25 top-k + fusion) of scopes that fit one slab is one launch, scope_hybrid_kernel: a block
+// owns a query from its first row to its fused hits and runs the two channels' own pieces below, so it needs no
+// workspace, no counters and no ordering between blocks.
 #include "common.hpp"
 #include "topk.hpp"
 
@@ -21,6 +24,7 @@
 
 #include "bm25_core.hpp"
 #include "dense_dot.hpp"
+#include "fuse_core.hpp"
 #include "maxsim_core.hpp"
 
 using namespace amdr;
@@ -70,21 +74,42 @@ size_t scope_region_bytes(int chan, int nq, int k, int64_t rows_max) {
   return scope_score_bytes(chan, slabs, nq, k) + align_up((size_t)slabs * nq * k * sizeof(int64_t));
 }
 
-// this block's piece [lo, hi) of the row list: the slab blockIdx.x of the scope of query q; empty for a qscope outside
+// a block's piece [lo, hi) of the row list: the slab `at` of the scope of query q; empty for a qscope outside
 // [0, n_scopes) and for a slab beyond the scope
 __device__ __forceinline__ void scope_piece(const long long* __restrict__ scope_ptr, const int* __restrict__ qscope,
-                                            int n_scopes, int slab, int q, long& lo, long& hi) {
+                                            int n_scopes, int slab, unsigned at, int q, long& lo, long& hi) {
   lo = hi = 0;
   const int s = qscope[q];
   if (s < 0 || s >= n_scopes) return;
   const long b = scope_ptr[s], e = scope_ptr[s + 1];
-  lo = b + (long)blockIdx.x * slab;
+  lo = b + (long)at * slab;
   hi = lo + slab < e ? lo + slab : e;
   if (hi < lo) hi = lo;
 }
 
 // ---- dense: one wave per scope row (dense_row_dot), lane 63's score into the wave's list ---------------------------------
-// grid: (x = slabs, y = queries).  LDS: C32 lists[kScWaves][cap] + int cnts[kScWaves]
+// The piece [lo, hi) of the row list against query row qr: every wave's list, combined into wave 0's (tk of wave 0 holds
+// the block's top-k afterwards).  Called by all four waves; two block barriers (block_combine_topk).
+// LDS: C32 lists[kScWaves][cap] + int cnts[kScWaves]
+// This wave takes rows lo + first, lo + first + step, ... (the channel kernel: first = wave, step = 4).
+__device__ __forceinline__ void scope_dense_piece(const float* __restrict__ X, long n, int d, const float* __restrict__ qr,
+                                                  const long long* __restrict__ rows, long lo, long hi, int first, int step,
+                                                  int k, int cap, C32* lists, int* cnts, int wave, int lane,
+                                                  WaveTopK<C32>& tk) {
+  tk.init(lists + (size_t)wave * cap, cap, k);
+  for (long i = lo + first; i < hi; i += step) {
+    const long r = uniform_i64(rows[i]);
+    if (r < 0 || r >= n) continue;  // never dereferenced
+    const float acc = dense_row_dot(X + (size_t)r * d, qr, d, lane);
+    const float s = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(acc), 63));
+    tk.push_uniform(C32::make(s, (u32)r), lane);
+  }
+  tk.finalize(lane);
+  block_combine_topk(tk, lists, cap, kScWaves, wave, lane, cnts);
+}
+__host__ __device__ inline size_t scope_dense_lds(int cap) { return (size_t)kScWaves * cap * sizeof(C32) + kScWaves * sizeof(int); }
+
+// grid: (x = slabs, y = queries)
 __global__ __launch_bounds__(kScWaves * 64) void scope_dense_kernel(
     const float* __restrict__ X, long n, int d, const float* __restrict__ Q, const long long* __restrict__ scope_ptr,
     const long long* __restrict__ rows, const int* __restrict__ qscope, int n_scopes, int slab, int nq, int k, int cap,
@@ -96,19 +121,9 @@ __global__ __launch_bounds__(kScWaves * 64) void scope_dense_kernel(
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int q = blockIdx.y;
   long lo, hi;
-  scope_piece(scope_ptr, qscope, n_scopes, slab, q, lo, hi);
+  scope_piece(scope_ptr, qscope, n_scopes, slab, blockIdx.x, q, lo, hi);
   WaveTopK<C32> tk;
-  tk.init(lists + (size_t)wave * cap, cap, k);
-  const float* qr = Q + (size_t)q * d;
-  for (long i = lo + wave; i < hi; i += kScWaves) {
-    const long r = uniform_i64(rows[i]);
-    if (r < 0 || r >= n) continue;  // never dereferenced
-    const float acc = dense_row_dot(X + (size_t)r * d, qr, d, lane);
-    const float s = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(acc), 63));
-    tk.push_uniform(C32::make(s, (u32)r), lane);
-  }
-  tk.finalize(lane);
-  block_combine_topk(tk, lists, cap, kScWaves, wave, lane, cnts);
+  scope_dense_piece(X, n, d, Q + (size_t)q * d, rows, lo, hi, wave, kScWaves, k, cap, lists, cnts, wave, lane, tk);
   if (wave != 0) return;
   const size_t row = fin_ids ? (size_t)q : (size_t)blockIdx.x * nq + q;
   topk_store(tk.buf, tk.cnt, k, lane, (fin_ids ? fin_scores : part_scores) + row * k, (fin_ids ? fin_ids : part_ids) + row * k);
@@ -118,14 +133,29 @@ __global__ __launch_bounds__(kScWaves * 64) void scope_dense_kernel(
 // A document's posting in a term's list is found by binary search (scopes are short next to posting lists); a hit adds
 // idf[term] * post_w[p] — a multiply, then an add (this file is built with -ffp-contract=off) — in the order
 // bm25_block_query's scatter gives the same document, duplicates counted, unknown terms skipped: the same bits.
-// grid: (x = slabs, y = queries).  LDS: double sc[slab] + C64 lists[kScWaves][cap] + int cnts[kScWaves] + token table
-__global__ __launch_bounds__(kScWaves * 64) void scope_bm25_kernel(
-    const long long* __restrict__ term_ptr, const int* __restrict__ post_doc, const double* __restrict__ post_w,
-    const double* __restrict__ idf, long n_terms, long n_docs, const int* __restrict__ q_terms,
-    const long long* __restrict__ q_ptr, const long long* __restrict__ scope_ptr, const long long* __restrict__ rows,
-    const int* __restrict__ qscope, int n_scopes, int slab, int nq, int k, int cap, double* __restrict__ part_scores,
-    long long* __restrict__ part_ids, double* __restrict__ fin_scores, long long* __restrict__ fin_ids) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+// The piece [lo, hi) of the document list for query q, scored and ranked: wave 0's tk holds the block's top-k afterwards.
+// Called by all four waves; every barrier is under a block-uniform condition.  ONE_WAVE: called by wave 0 alone for a
+// piece of <= 64 documents — in the four-wave form the other three waves have no document of such a piece and only
+// keep the barriers company — with wave-level fences for the block barriers and no combine: the same scores, the same
+// list, no block barrier.
+// LDS (smem): double sc[slab] + C64 lists[kScWaves][cap] + int cnts[kScWaves] + token table
+struct ScBm25 {  // the index side of the BM25 piece (device pointers)
+  const long long* term_ptr;
+  const int* post_doc;
+  const double* post_w;
+  const double* idf;
+  long n_terms, n_docs;
+};
+template <bool ONE_WAVE>
+__device__ __forceinline__ void scope_bm25_piece(const ScBm25& B, const int* __restrict__ q_terms,
+                                                 const long long* __restrict__ q_ptr, int q,
+                                                 const long long* __restrict__ rows, long lo, long hi, int slab, int k,
+                                                 int cap, unsigned char* smem, WaveTopK<C64>& tk) {
+  const long long* __restrict__ term_ptr = B.term_ptr;
+  const int* __restrict__ post_doc = B.post_doc;
+  const double* __restrict__ post_w = B.post_w;
+  const double* __restrict__ idf = B.idf;
+  const long n_terms = B.n_terms, n_docs = B.n_docs;
   double* sc = reinterpret_cast<double*>(smem);
   C64* lists = reinterpret_cast<C64*>(sc + slab);
   int* cnts = reinterpret_cast<int*>(lists + (size_t)kScWaves * cap);
@@ -133,14 +163,12 @@ __global__ __launch_bounds__(kScWaves * 64) void scope_bm25_kernel(
   long* tk_pe = tk_ps + kBmTok;
   double* tk_w = reinterpret_cast<double*>(tk_pe + kBmTok);
   int* tk_n = reinterpret_cast<int*>(tk_w + kBmTok);
-  constexpr int NT = kScWaves * 64;
+  constexpr int NT = ONE_WAVE ? 64 : kScWaves * 64;
+  constexpr int SYNC = ONE_WAVE ? 1 : kScWaves;  // block_sync<1>: a wave-level fence
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int q = blockIdx.y;
-  long lo, hi;
-  scope_piece(scope_ptr, qscope, n_scopes, slab, q, lo, hi);
   const int m = (int)(hi - lo);
   for (int i = tid; i < m; i += NT) sc[i] = 0.0;
-  __syncthreads();
+  block_sync<SYNC>();
   if (m > 0) {  // block-uniform; an empty piece reads nothing
     const long t0 = q_ptr[q], t1 = q_ptr[q + 1];
     for (long tb = t0; tb < t1; tb += kBmTok) {
@@ -167,7 +195,7 @@ __global__ __launch_bounds__(kScWaves * 64) void scope_bm25_kernel(
         }
         if (tid == 0) *tk_n = __popcll(km);
       }
-      __syncthreads();
+      block_sync<SYNC>();
       const int nt = *tk_n;
       for (int i = tid; i < m; i += NT) {
         const long doc = rows[lo + i];
@@ -180,10 +208,9 @@ __global__ __launch_bounds__(kScWaves * 64) void scope_bm25_kernel(
         }
         sc[i] = s;
       }
-      __syncthreads();  // the table is rewritten by the next group
+      block_sync<SYNC>();  // the table is rewritten by the next group
     }
   }
-  WaveTopK<C64> tk;
   tk.init(lists + (size_t)wave * cap, cap, k);
   for (int base = wave * 64; base < m; base += NT) {
     const int i = base + lane;
@@ -192,16 +219,131 @@ __global__ __launch_bounds__(kScWaves * 64) void scope_bm25_kernel(
     tk.push_lanes(v ? C64::make(sc[i], doc) : C64::pad(), v, lane);
   }
   tk.finalize(lane);
-  block_combine_topk(tk, lists, cap, kScWaves, wave, lane, cnts);
-  if (wave != 0) return;
-  const size_t row = fin_ids ? (size_t)q : (size_t)blockIdx.x * nq + q;
-  double* so = (fin_ids ? fin_scores : part_scores) + row * k;
-  long long* io = (fin_ids ? fin_ids : part_ids) + row * k;
+  if (!ONE_WAVE) block_combine_topk(tk, lists, cap, kScWaves, wave, lane, cnts);
+}
+__host__ __device__ inline size_t scope_bm25_lds(int slab, int cap) {
+  return (size_t)slab * sizeof(double) + (size_t)kScWaves * cap * sizeof(C64) + kScWaves * sizeof(int) +
+         3 * kBmTok * sizeof(long) + 8;
+}
+// wave 0: one row of a (scores, ids) result from its finished list, -DBL_MAX / -1 behind the hits
+__device__ __forceinline__ void scope_bm25_store(const WaveTopK<C64>& tk, int k, int lane, double* __restrict__ so,
+                                                 long long* __restrict__ io) {
   for (int j = lane; j < k; j += 64) {
     const bool v = j < tk.cnt;
     so[j] = v ? unord64(tk.buf[j].key) : -DBL_MAX;
     io[j] = v ? tk.buf[j].idv : -1ll;
   }
+}
+
+// grid: (x = slabs, y = queries)
+__global__ __launch_bounds__(kScWaves * 64) void scope_bm25_kernel(ScBm25 B, const int* __restrict__ q_terms,
+    const long long* __restrict__ q_ptr, const long long* __restrict__ scope_ptr, const long long* __restrict__ rows,
+    const int* __restrict__ qscope, int n_scopes, int slab, int nq, int k, int cap, double* __restrict__ part_scores,
+    long long* __restrict__ part_ids, double* __restrict__ fin_scores, long long* __restrict__ fin_ids) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int q = blockIdx.y;
+  long lo, hi;
+  scope_piece(scope_ptr, qscope, n_scopes, slab, blockIdx.x, q, lo, hi);
+  WaveTopK<C64> tk;
+  scope_bm25_piece<false>(B, q_terms, q_ptr, q, rows, lo, hi, slab, k, cap, smem, tk);
+  if (wave != 0) return;
+  const size_t row = fin_ids ? (size_t)q : (size_t)blockIdx.x * nq + q;
+  scope_bm25_store(tk, k, lane, (fin_ids ? fin_scores : part_scores) + row * k, (fin_ids ? fin_ids : part_ids) + row * k);
+}
+
+// ---- the scoped step in one launch: dense piece, BM25 piece, fusion -----------------------------------------------------
+// grid = one block per query, 256 threads, no workspace: both scopes of the query fit one slab of their channel, so the
+// block runs the two pieces above one after the other (all four waves each; the same floating-point sequence per row /
+// document as the two kernels above, hence the same bits).  Wave 0 writes each finished list to the caller's [nq, kd] /
+// [nq, kb] as its piece ends, keeps the dense list in registers across the BM25 piece, takes the BM25 list from LDS and
+// fuses with fuse_packed_body, the packed fusion's own code (W = 16 / 32 lanes per query as launch_fuse picks them; lanes
+// past W carry no query).  Both lists reach the fusion through FusePre, not from global memory; the optional ColBERT
+// list c2 was written by an earlier launch on the stream and is read from memory.  The dense and the BM25 scope come
+// from their own tables (their row spaces differ).  Every barrier (two in each block_combine_topk, one + two per token
+// group in the BM25 piece) sits under block-uniform conditions and is reached by all four waves; waves 1-3 leave only
+// after the last of them.  An empty scope or a qscope outside the table reads nothing and fuses nothing (count 0).
+// A BM25 scope of <= 64 documents takes the overlapped order instead (below; AMDR_SCOPE_OVERLAP=0 pins the sequential
+// one): measured 37.7 against 46.1 us for one query with a 28-row section, the same bits.
+// LDS: the dense lists (scope_dense_lds) followed by the BM25 piece's region (scope_bm25_lds) — separate, so no barrier
+// is needed between the pieces — + the packed fusion's 3.3 KB of static arrays.
+struct ScTab {  // one channel's scope table (device pointers)
+  const long long* scope_ptr;
+  const long long* rows;
+  const int* qscope;
+  int n_scopes;
+};
+struct ScFuse {  // what only the fusion at the end needs
+  amdr_fuse_params_t P;
+  const long long* d_row2uid;  // (both lists go in through FusePre: the row -> uid maps are all the fusion takes of them)
+  const long long* b_row2uid;
+  ChanIn c2;
+  int max_out;
+  long long* out_ids;
+  double* out_vals;
+  int* out_mask;
+  int* out_count;
+};
+__host__ __device__ inline size_t scope_hybrid_dense_lds(int cap_d) { return (scope_dense_lds(cap_d) + 15) / 16 * 16; }
+// F_at_0 must stay the FIRST parameter: wave 0 reads it from offset 0 of the kernel-argument segment when it gets to
+// the fusion.  As an ordinary argument its 33 scalar registers are loaded at the kernel's start and parked across both
+// channel pieces, which need 56 and 66 of their own: the compiler then spills 14 of them (to lanes of a vector register).
+template <int W>
+__global__ __launch_bounds__(kScWaves * 64) void scope_hybrid_kernel(
+    ScFuse F_at_0, const float* __restrict__ X, long n, int d, const float* __restrict__ Q, ScBm25 B,
+    const int* __restrict__ q_terms, const long long* __restrict__ q_ptr, ScTab td, ScTab tb, int slab_d, int slab_b, int kd,
+    int kb, int cap_d, int cap_b, int overlap_docs, float* __restrict__ d_scores, long long* __restrict__ d_ids,
+    double* __restrict__ b_scores, long long* __restrict__ b_ids) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  C32* lists = reinterpret_cast<C32*>(smem);
+  int* cnts = reinterpret_cast<int*>(lists + (size_t)kScWaves * cap_d);
+  unsigned char* smem_b = smem + scope_hybrid_dense_lds(cap_d);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int q = blockIdx.x;
+  long lo, hi, lo_b, hi_b;
+  scope_piece(td.scope_ptr, td.qscope, td.n_scopes, slab_d, 0, q, lo, hi);
+  scope_piece(tb.scope_ptr, tb.qscope, tb.n_scopes, slab_b, 0, q, lo_b, hi_b);
+  // list position sl of query q in lanes 0 .. W-1 (segment 0 of the packed fusion; the other segments have no query:
+  // the limit handed in is q + 1)
+  const int sl = lane % W;
+  const bool seg0 = lane < W;
+  FusePre pre;
+  pre.have[0] = pre.have[1] = true;
+  pre.have[2] = false;
+  WaveTopK<C32> tkd;
+  WaveTopK<C64> tkb;
+  if (hi_b - lo_b <= overlap_docs) {  // block-uniform
+    // A BM25 piece of <= 64 documents is one wave's work and the longest chain of the block (per token a binary search
+    // of dependent loads): wave 0 runs it alone, without a block barrier, while waves 1-3 take the dense rows; the two
+    // meet at the dense combine.  The same lists as the sequential form: the selectors' order is total.
+    if (wave == 0) scope_bm25_piece<true>(B, q_terms, q_ptr, q, tb.rows, lo_b, hi_b, slab_b, kb, cap_b, smem_b, tkb);
+    scope_dense_piece(X, n, d, Q + (size_t)q * d, td.rows, wave == 0 ? hi : lo, hi, wave == 0 ? 0 : wave - 1, kScWaves - 1,
+                      kd, cap_d, lists, cnts, wave, lane, tkd);  // (wave 0: no row, an empty list into the combine)
+    if (wave != 0) return;  // (behind the last block-wide exchange)
+    topk_store(tkd.buf, tkd.cnt, kd, lane, d_scores + (size_t)q * kd, d_ids + (size_t)q * kd);
+    const bool vd = seg0 && sl < tkd.cnt;
+    pre.dense(vd ? tkd.buf[sl] : C32::pad(), vd);
+  } else {
+    scope_dense_piece(X, n, d, Q + (size_t)q * d, td.rows, lo, hi, wave, kScWaves, kd, cap_d, lists, cnts, wave, lane, tkd);
+    if (wave == 0) {  // the dense list: out, and into wave 0's registers for the fusion (the BM25 piece has its own LDS)
+      topk_store(tkd.buf, tkd.cnt, kd, lane, d_scores + (size_t)q * kd, d_ids + (size_t)q * kd);
+      const bool vd = seg0 && sl < tkd.cnt;
+      pre.dense(vd ? tkd.buf[sl] : C32::pad(), vd);
+    }
+    scope_bm25_piece<false>(B, q_terms, q_ptr, q, tb.rows, lo_b, hi_b, slab_b, kb, cap_b, smem_b, tkb);
+    if (wave != 0) return;  // (behind the last block-wide exchange)
+  }
+  scope_bm25_store(tkb, kb, lane, b_scores + (size_t)q * kb, b_ids + (size_t)q * kb);
+  const bool vb = seg0 && sl < tkb.cnt;
+  pre.bm25(vb ? tkb.buf[sl] : C64::pad(), vb);
+  typedef const ScFuse __attribute__((address_space(4))) * KernArg;  // (constant address space: scalar loads)
+  KernArg f = (KernArg)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(f));  // read here, not before
+  const ScFuse F{{f->P.method, f->P.rrf_k, f->P.alpha, f->P.w_dense, f->P.w_bm25, f->P.w_colbert, f->P.min_final_score},
+                 f->d_row2uid, f->b_row2uid, ChanIn{f->c2.ids, f->c2.scores, f->c2.row2uid, f->c2.k, f->c2.is_f64},
+                 f->max_out, f->out_ids, f->out_vals, f->out_mask, f->out_count};
+  const ChanIn c0{nullptr, nullptr, F.d_row2uid, kd, 0}, c1{nullptr, nullptr, F.b_row2uid, kb, 1};
+  fuse_packed_body<W, true>(F.P, c0, c1, F.c2, q + 1, F.max_out, F.out_ids, F.out_vals, F.out_mask, F.out_count, pre, q);
 }
 
 // ---- MaxSim: one wave per (query, scope document), the pair form of maxsim_scores_h_kernel -------------------------------
@@ -218,7 +360,7 @@ __global__ __launch_bounds__(kScWaves * 64) void scope_maxsim_kernel(
   const int q = blockIdx.y;
   const int r32 = lane & 31, h = lane >> 5;
   long lo, hi;
-  scope_piece(scope_ptr, qscope, n_scopes, slab, q, lo, hi);
+  scope_piece(scope_ptr, qscope, n_scopes, slab, blockIdx.x, q, lo, hi);
   WaveTopK<C32> tk;
   tk.init(lists + (size_t)wave * cap, cap, k);
   if (lo + wave < hi) {  // wave-uniform: a wave without a document does not read its query
@@ -306,7 +448,7 @@ int sc_dense_run(amdr_dense_t* dense, const float* Q, const ScTable& t, int nq, 
   dense_matrix(dense, &X, &n, &d);
   return sc_run<float>(kDense, nq, k, t.rows_max, region, scores_dev, ids_dev, st,
                        [&](int q0, int m, int slab, int slabs, int cap, float* ps, int64_t* pi) {
-                         const size_t lds = (size_t)kScWaves * cap * sizeof(C32) + kScWaves * sizeof(int);
+                         const size_t lds = scope_dense_lds(cap);
                          const bool direct = slabs == 1;
                          hipLaunchKernelGGL(scope_dense_kernel, dim3(slabs, m), dim3(kScWaves * 64), lds, st, X, n, d,
                                             Q + (size_t)q0 * d, t.scope_ptr, t.rows, t.qscope + q0, t.n_scopes, slab, m, k, cap,
@@ -319,11 +461,11 @@ int sc_bm25_run(const Bm25Raw& b, const int* q_terms, const long long* q_ptr, co
                 unsigned char* region, double* scores_dev, int64_t* ids_dev, hipStream_t st) {
   return sc_run<double>(kBm25, nq, k, t.rows_max, region, scores_dev, ids_dev, st,
                         [&](int q0, int m, int slab, int slabs, int cap, double* ps, int64_t* pi) {
-                          const size_t lds = (size_t)slab * sizeof(double) + (size_t)kScWaves * cap * sizeof(C64) +
-                                             kScWaves * sizeof(int) + 3 * kBmTok * sizeof(long) + 8;
+                          const size_t lds = scope_bm25_lds(slab, cap);
                           const bool direct = slabs == 1;
-                          hipLaunchKernelGGL(scope_bm25_kernel, dim3(slabs, m), dim3(kScWaves * 64), lds, st, b.term_ptr,
-                                             b.post_doc, b.post_w, b.idf, b.n_terms, b.n_docs, q_terms, q_ptr + q0, t.scope_ptr,
+                          const ScBm25 B{b.term_ptr, b.post_doc, b.post_w, b.idf, b.n_terms, b.n_docs};
+                          hipLaunchKernelGGL(scope_bm25_kernel, dim3(slabs, m), dim3(kScWaves * 64), lds, st, B, q_terms,
+                                             q_ptr + q0, t.scope_ptr,
                                              t.rows, t.qscope + q0, t.n_scopes, slab, m, k, cap, ps, (long long*)pi,
                                              direct ? scores_dev + (size_t)q0 * k : nullptr,
                                              direct ? (long long*)ids_dev + (size_t)q0 * k : nullptr);
@@ -342,6 +484,59 @@ int sc_maxsim_run(const MaxsimRaw& r, const float* Q, int q_len, const ScTable& 
                                             direct ? scores_dev + (size_t)q0 * k : nullptr,
                                             direct ? (long long*)ids_dev + (size_t)q0 * k : nullptr);
                        });
+}
+
+// ---- the one-launch step -------------------------------------------------------------------------------------------------
+// AMDR_SCOPE_FUSED=0 pins the separate launches (A/B and tests).  Otherwise: both scopes inside one slab of their channel
+// and all candidates of a query inside the packed fusion's 32 lanes.
+bool scope_hybrid_applies(int nq, int kd, int kb, int kc, int64_t rows_max_dense, int64_t rows_max_bm25) {
+  const char* e = getenv("AMDR_SCOPE_FUSED");
+  if (e && e[0] == '0') return false;
+  return nq >= 1 && kd >= 1 && kb >= 1 && kc >= 0 && kd + kb + kc <= 32 && rows_max_dense >= 0 && rows_max_bm25 >= 0 &&
+         rows_max_dense <= scope_slab(kDense) && rows_max_bm25 <= scope_slab(kBm25);
+}
+size_t scope_hybrid_lds(int kd, int kb) {
+  return scope_hybrid_dense_lds(topk_cap(kd)) + scope_bm25_lds(scope_slab(kBm25), topk_cap(kb));
+}
+
+struct ScHybridOut {  // device pointers: the two channel lists and the fused record
+  float* dense_scores;
+  int64_t* dense_ids;
+  double* bm25_scores;
+  int64_t* bm25_ids;
+  int64_t* ids;
+  double* vals;
+  int32_t* mask;
+  int32_t* count;
+};
+int sc_hybrid_run(amdr_dense_t* dense, const Bm25Raw& b, const float* Q, const int* q_terms, const long long* q_ptr,
+                  const ScTable& td, const ScTable& tb, int nq, int kd, int kb, const amdr_fuse_params_t& P,
+                  const int64_t* dense_row2uid, const int64_t* bm25_row2uid, const ChanIn& c2, const ScHybridOut& o,
+                  hipStream_t st) {
+  const float* X;
+  long n;
+  int d;
+  dense_matrix(dense, &X, &n, &d);
+  const int cap_d = topk_cap(kd), cap_b = topk_cap(kb), mo = kd + kb + c2.k;
+  const size_t lds = scope_hybrid_lds(kd, kb);
+  const ScBm25 B{b.term_ptr, b.post_doc, b.post_w, b.idf, b.n_terms, b.n_docs};
+  const ScTab d_tab{td.scope_ptr, td.rows, td.qscope, td.n_scopes}, b_tab{tb.scope_ptr, tb.rows, tb.qscope, tb.n_scopes};
+  const char* ov = getenv("AMDR_SCOPE_OVERLAP");  // "0" pins the sequential form (A/B and tests)
+  const int overlap_docs = (ov && ov[0] == '0') ? -1 : 64;
+  const ScFuse F{P, (const long long*)dense_row2uid, (const long long*)bm25_row2uid, c2, mo, (long long*)o.ids, o.vals, o.mask,
+                 o.count};
+#define AMDR_SCH_LAUNCH(W)                                                                                               \
+  hipLaunchKernelGGL((scope_hybrid_kernel<W>), dim3(nq), dim3(kScWaves * 64), lds, st, F, X, n, d, Q, B, q_terms, q_ptr, \
+                     d_tab, b_tab, scope_slab(kDense), scope_slab(kBm25), kd, kb, cap_d, cap_b, overlap_docs,          \
+                     o.dense_scores,                                                                                    \
+                     (long long*)o.dense_ids, o.bm25_scores, (long long*)o.bm25_ids)
+  if (mo <= 16)  // (launch_fuse's choice: the same instantiation of the packed body as the separate fusion launch)
+    AMDR_SCH_LAUNCH(16);
+  else
+    AMDR_SCH_LAUNCH(32);
+#undef AMDR_SCH_LAUNCH
+  AMDR_HIP(hipGetLastError());
+  return AMDR_OK;
 }
 
 // the split-fp16 image a scoped MaxSim call needs (the pair form of maxsim_scores_h_kernel); AMDR_MAXSIM_F16X3=0 pins
@@ -464,11 +659,17 @@ int amdr_scope_plan_info(const amdr_scope_t* s, int32_t nq, int32_t k, int64_t r
   AMDR_REQUIRE(s && buf && buf_len > 0, "scope_plan_info: null");
   AMDR_REQUIRE(nq >= 1 && k >= 1 && k <= AMDR_MAX_K && rows_max >= 0, "scope_plan_info: bad sizes");
   const int sd = scope_slabs(kDense, rows_max), sb = scope_slabs(kBm25, rows_max), sm = scope_slabs(kMaxsim, rows_max);
+  // the step of dense + BM25 at depth k each (amdr_hybrid_scope_device), without and with a ColBERT list of depth k
+  const bool f2 = scope_hybrid_applies(nq, k, k, 0, rows_max, rows_max), f3 = scope_hybrid_applies(nq, k, k, k, rows_max, rows_max);
   snprintf(buf, buf_len,
-           "scope_dense_kernel slabs=%d of <= %d rows%s; scope_bm25_kernel slabs=%d of <= %d%s; scope_maxsim_kernel slabs=%d of <= %d%s",
+           "scope_dense_kernel slabs=%d of <= %d rows%s; scope_bm25_kernel slabs=%d of <= %d%s; scope_maxsim_kernel slabs=%d of <= %d%s; "
+           "step dense + bm25 + fusion: %s",
            sd, scope_slab(kDense), sd == 1 ? " (direct)" : " + merge_parts_kernel", sb, scope_slab(kBm25),
            sb == 1 ? " (direct)" : " + merge_parts_kernel", sm, scope_slab(kMaxsim),
-           sm == 1 ? " (direct)" : " + merge_parts_kernel");
+           sm == 1 ? " (direct)" : " + merge_parts_kernel",
+           f3   ? "scope_hybrid_kernel (one launch; also behind a ColBERT list of depth k)"
+           : f2 ? "scope_hybrid_kernel (one launch; separate launches with a ColBERT list of depth k)"
+                : "separate launches");
   return AMDR_OK;
 }
 
@@ -507,6 +708,65 @@ int amdr_scope_bm25_search_device(amdr_scope_t* s, amdr_bm25_t* bm25, const int3
   AMDR_HIP(hipSetDevice(s->device));
   const ScTable t{(const long long*)scope_ptr_dev, (const long long*)rows_dev, qscope_dev, n_scopes, rows_max};
   return sc_bm25_run(b, q_terms_dev, (const long long*)q_ptr_dev, t, nq, k, region, scores_dev, ids_dev, (hipStream_t)stream);
+}
+
+int amdr_hybrid_scope_plan(int32_t nq, int32_t kd, int32_t kb, int32_t kc, int64_t rows_max_dense, int64_t rows_max_bm25,
+                           int32_t* fused, int64_t* lds_bytes) {
+  AMDR_REQUIRE(fused && lds_bytes, "hybrid_scope_plan: null");
+  AMDR_REQUIRE(nq >= 1 && kd >= 1 && kd <= AMDR_MAX_K && kb >= 1 && kb <= AMDR_MAX_K && kc >= 0 && kc <= AMDR_MAX_K &&
+                   rows_max_dense >= 0 && rows_max_bm25 >= 0,
+               "hybrid_scope_plan: bad sizes");
+  *fused = scope_hybrid_applies(nq, kd, kb, kc, rows_max_dense, rows_max_bm25) ? 1 : 0;
+  *lds_bytes = *fused ? (int64_t)scope_hybrid_lds(kd, kb) : 0;
+  return AMDR_OK;
+}
+
+int amdr_hybrid_scope_device(amdr_scope_t* s, amdr_dense_t* dense, amdr_bm25_t* bm25, const float* Q_dev,
+                             const int32_t* q_terms_dev, const int64_t* q_ptr_dev, const int64_t* d_scope_ptr_dev,
+                             const int64_t* d_rows_dev, const int32_t* d_qscope_dev, int32_t d_n_scopes, int64_t d_rows_max,
+                             const int64_t* b_scope_ptr_dev, const int64_t* b_rows_dev, const int32_t* b_qscope_dev,
+                             int32_t b_n_scopes, int64_t b_rows_max, int32_t nq, int32_t kd, int32_t kb,
+                             const amdr_fuse_params_t* p, const int64_t* dense_row2uid, const int64_t* bm25_row2uid,
+                             const int64_t* colbert_ids, const float* colbert_scores, int32_t kc,
+                             const int64_t* colbert_row2uid, float* dense_scores, int64_t* dense_ids, double* bm25_scores,
+                             int64_t* bm25_ids, int64_t* out_ids, double* out_vals, int32_t* out_mask, int32_t* out_count,
+                             void* stream) {
+  AMDR_REQUIRE(s && dense && bm25, "hybrid_scope: null handle");
+  AMDR_REQUIRE(p != nullptr, "hybrid_scope: null params");
+  AMDR_REQUIRE(p->method >= 0 && p->method <= 3, "hybrid_scope: unknown method %d", p->method);
+  AMDR_REQUIRE(kc >= 0 && kc <= AMDR_MAX_K, "hybrid_scope: kc=%d outside [0,%d]", kc, AMDR_MAX_K);
+  int rc = sc_check_table("hybrid_scope (dense)", d_scope_ptr_dev, d_rows_dev, d_qscope_dev, d_n_scopes, d_rows_max, nq, kd);
+  if (rc) return rc;
+  if ((rc = sc_check_table("hybrid_scope (bm25)", b_scope_ptr_dev, b_rows_dev, b_qscope_dev, b_n_scopes, b_rows_max, nq, kb)))
+    return rc;
+  AMDR_REQUIRE(nq == 0 || (Q_dev && q_ptr_dev && dense_scores && dense_ids && bm25_scores && bm25_ids), "hybrid_scope: null buffer");
+  AMDR_REQUIRE(nq == 0 || kc == 0 || (colbert_ids && colbert_scores), "hybrid_scope: null ColBERT list");
+  AMDR_REQUIRE(nq == 0 || (out_ids && out_vals && out_mask && out_count), "hybrid_scope: null output");
+  AMDR_REQUIRE(dense_device_of(dense) == s->device && bm25_device_of(bm25) == s->device,
+               "hybrid_scope: handles on different devices");
+  if (nq == 0) return AMDR_OK;
+  if (!scope_hybrid_applies(nq, kd, kb, kc, d_rows_max, b_rows_max)) {
+    // every other shape: today's calls, in their own regions of the reserve (AMDR_EINVAL beyond it), then the fusion
+    if ((rc = amdr_scope_dense_search_device(s, dense, Q_dev, d_scope_ptr_dev, d_rows_dev, d_qscope_dev, d_n_scopes, d_rows_max,
+                                             nq, kd, dense_scores, dense_ids, stream)))
+      return rc;
+    if ((rc = amdr_scope_bm25_search_device(s, bm25, q_terms_dev, q_ptr_dev, b_scope_ptr_dev, b_rows_dev, b_qscope_dev,
+                                            b_n_scopes, b_rows_max, nq, kb, bm25_scores, bm25_ids, stream)))
+      return rc;
+    return amdr_fuse_device(p, nq, dense_ids, dense_scores, kd, dense_row2uid, bm25_ids, bm25_scores, kb, bm25_row2uid,
+                            colbert_ids, colbert_scores, kc, colbert_row2uid, out_ids, out_vals, out_mask, out_count,
+                            s->device, stream);
+  }
+  Bm25Raw b;
+  if ((rc = bm25_small_raw(bm25, nq, kb, &b))) return rc;
+  AMDR_HIP(hipSetDevice(s->device));
+  const ScTable td{(const long long*)d_scope_ptr_dev, (const long long*)d_rows_dev, d_qscope_dev, d_n_scopes, d_rows_max};
+  const ScTable tb{(const long long*)b_scope_ptr_dev, (const long long*)b_rows_dev, b_qscope_dev, b_n_scopes, b_rows_max};
+  const ChanIn c2 = kc ? ChanIn{(const long long*)colbert_ids, colbert_scores, (const long long*)colbert_row2uid, kc, 0}
+                       : ChanIn::none();
+  const ScHybridOut o{dense_scores, dense_ids, bm25_scores, bm25_ids, out_ids, out_vals, out_mask, out_count};
+  return sc_hybrid_run(dense, b, Q_dev, q_terms_dev, (const long long*)q_ptr_dev, td, tb, nq, kd, kb, *p, dense_row2uid,
+                       bm25_row2uid, c2, o, (hipStream_t)stream);
 }
 
 int amdr_scope_maxsim_search_device(amdr_scope_t* s, amdr_maxsim_t* maxsim, const float* Q_dev, int32_t q_len,

@@ -393,6 +393,31 @@ class HybridEngine:
         ws.maxsim_search_device(self.maxsim, q_tok.data_ptr(), q_len, tb, nq, k, s.data_ptr(), i.data_ptr(), _stream())
         return s, i
 
+    def hybrid_scoped(self, params: _native.FuseParams, q_emb: torch.Tensor, q_terms: torch.Tensor, q_ptr: torch.Tensor,
+                      k: int, dense_table, bm25_table, colbert=None):
+        """dense_topk_scoped + bm25_topk_scoped + fuse as ONE native call (amdr_hybrid_scope_device: one launch when both
+        tables' scopes fit a slab of their channel and all candidates of a query fit the packed fusion; the separate
+        calls inside otherwise): (dense lists, BM25 lists, result).  colbert = the finished lists of colbert_topk_scoped,
+        enqueued earlier on the stream.  Same results as the separate calls, bit for bit."""
+        nq = int(q_emb.shape[0])
+        _check_emb(q_emb)
+        _check_csr(q_terms, q_ptr)
+        assert q_ptr.shape[0] - 1 == nq
+        ws, td = self._scope_call(dense_table, nq, k)
+        ws, tb = self._scope_call(bm25_table, nq, k)
+        ds = self._buf("sds", (nq, k), torch.float32)
+        di = self._buf("sdi", (nq, k), torch.int64)
+        bs = self._buf("sbs", (nq, k), torch.float64)
+        bi = self._buf("sbi", (nq, k), torch.int64)
+        kc = int(colbert[1].shape[1]) if colbert is not None else 0
+        pk, ids, vals, mask, count = self._fused_outputs(nq, 2 * k + kc)
+        maps = tuple(m.data_ptr() if m is not None else 0 for m in self.maps[:3])
+        ws.hybrid(self.dense, self.bm25, params, q_emb.data_ptr(), q_terms.data_ptr(), q_ptr.data_ptr(), td, tb, nq, k, k,
+                  maps, (colbert[1].data_ptr(), colbert[0].data_ptr(), kc) if colbert is not None else None,
+                  (ds.data_ptr(), di.data_ptr(), bs.data_ptr(), bi.data_ptr()),
+                  (ids.data_ptr(), vals.data_ptr(), mask.data_ptr(), count.data_ptr()), _stream())
+        return (ds, di), (bs, bi), BatchResult(ids=ids, vals=vals, mask=mask, count=count, packed=pk)
+
     # -- fusion ---------------------------------------------------------------
     def fuse(self, params: _native.FuseParams, nq: int, dense=None, bm25=None, colbert=None) -> BatchResult:
         def chan(c, m):
@@ -499,7 +524,11 @@ class HybridEngine:
             for on, tb, who in zip((d_on, b_on, c_on), scopes, ("dense", "BM25", "ColBERT")):
                 if on and tb is None:
                     raise ValueError(f"search_batch(scopes=): the {who} channel runs but has no scope table")
-        if form == SCOPED:  # three short launches on the caller's stream (regions of one workspace: no ordering needed)
+        if form == SCOPED and d_on and b_on:  # one call: dense + BM25 + fusion behind the ColBERT lists, if any
+            if c_on:
+                c = self.colbert_topk_scoped(q_tok, k, scopes[2])
+            d, b, res = self.hybrid_scoped(params, q_emb, q_terms, q_ptr, k, scopes[0], scopes[1], c)
+        elif form == SCOPED:  # short launches on the caller's stream (regions of one workspace: no ordering needed)
             if d_on:
                 d = self.dense_topk_scoped(q_emb, k, scopes[0])
             if b_on:
