@@ -13,6 +13,7 @@
 // Algorithmic bytes per query: sum_t df(t)*12 (posting doc id + precomputed fp64 factor).
 #include "common.hpp"
 #include "topk.hpp"
+#include "topk_merge.hpp"
 
 #include <cfloat>
 #include <cmath>
@@ -56,7 +57,7 @@ void bm_plan(int64_t n_docs, int nq, int k, BmPlan* p) {
   // slabs of <= 2 048 documents ranked by the register arg-max (<= 32 scores per lane), its k
   // winners parked in a short list; otherwise slabs of <= 4 096 ranked by the staged selector.
   // Slabs are balanced (3 000 documents = 2 x 1 536, not 2 048 + 952) and merged by
-  // bm25_merge_kernel.
+  // merge_parts_kernel (topk_merge.hip).
   const int64_t n = n_docs > 0 ? n_docs : 1;
   auto balanced = [&](int slab_max) {
     p->nslabs = (int)((n + slab_max - 1) / slab_max);
@@ -70,7 +71,7 @@ void bm_plan(int64_t n_docs, int nq, int k, BmPlan* p) {
   p->waves = 1;
   p->cap_merge = topk_cap(k);
   p->cap = argmax ? (k <= 16 ? 16 : kBmArgmaxK) : p->cap_merge;
-  p->lds = (size_t)p->slab * sizeof(double) + (size_t)p->waves * p->cap * sizeof(C64) + 4 * sizeof(int) +
+  p->lds = (size_t)p->slab * sizeof(double) + TopkLds<C64>::bytes(p->waves, p->cap, kBmCnts) +
            128 * sizeof(long) + 8;  // token table (3 x kBmTok x 8 B) / ranking scratch (2 x 64 x 8 B)
   p->part_bytes = (size_t)p->nslabs * nq * k * sizeof(C64);
 }
@@ -129,12 +130,7 @@ int bm_run(amdr_bm25* h, int ws, const int* q_terms_dev, const long long* q_ptr_
   else AMDR_BM_LAUNCH(32);
 #undef AMDR_BM_LAUNCH
   AMDR_HIP(hipGetLastError());
-  if (scores_dev && !direct) {
-    size_t lds = (size_t)kBmWaves * p.cap_merge * sizeof(C64) + kBmWaves * sizeof(int);
-    hipLaunchKernelGGL(bm25_merge_kernel, dim3(nq), dim3(256), lds, st, part, p.nslabs, nq, k, p.cap_merge, scores_dev,
-                       (long long*)ids_dev);
-    AMDR_HIP(hipGetLastError());
-  }
+  if (scores_dev && !direct) return launch_merge_packed(part, p.nslabs, nq, k, p.cap_merge, scores_dev, ids_dev, st);
   return AMDR_OK;
 }
 
@@ -276,7 +272,7 @@ int amdr_bm25_plan_info(const amdr_bm25_t* h, int32_t nq, int32_t k, char* buf, 
   bm_plan(h->n_docs, nq, k, &p);
   snprintf(buf, buf_len, "bm25_score_topk_kernel slabs=%d of <= %d documents, ranked by %s%s", p.nslabs, p.slab,
            bm_use_argmax(k, p.slab) ? "the register arg-max rounds" : "the staged selector",
-           p.nslabs == 1 ? " (one slab: direct)" : " + bm25_merge_kernel");
+           p.nslabs == 1 ? " (one slab: direct)" : " + merge_parts_kernel");
   return AMDR_OK;
 }
 

@@ -10,7 +10,7 @@
 
 namespace amdr {
 
-constexpr int kBmWaves = 4;
+constexpr int kBmCnts = 4;  // count slots behind the lists whatever WAVES is: the token table after them stays 8-byte aligned
 constexpr int kBmArgmaxK = 96;  // deepest k ever ranked by arg-max rounds (one round per result)
 // Arg-max rounds cost ~ k x (scores per lane); the staged selector is nearly flat in k.  Measured
 // crossover (scripts/sweep_bm25.py, 591 and 1 260 documents, k = 10 ... 80): k x ceil(slab / 64) ~ 480.
@@ -257,7 +257,7 @@ __device__ __forceinline__ int bm25_rank_slab(const double* sc, int m, int k, lo
   return got;
 }
 
-// grid: (x = doc slabs, y = queries).  LDS: double sc[slab] + C64 lists[WAVES][cap] + int cnts[4] + token table [64]
+// grid: (x = doc slabs, y = queries).  LDS: double sc[slab] + TopkLds<C64>(WAVES lists, kBmCnts counts) + token table [64]
 // The host launches WAVES = 1 only (one wave per (query, slab): no block barriers, no list
 // combine) — the 4-wave form the template still allows lost at every corpus size measured
 // (bm_plan).  With a single slab the final (scores, ids) are written directly and the merge
@@ -276,12 +276,11 @@ __device__ __forceinline__ void bm25_block_query(
     double* __restrict__ fin_scores /* nullable [nq,k]: single slab */, long long* __restrict__ fin_ids,
     int qi_arg, int slab_ix, unsigned char* smem) {
   double* sc = reinterpret_cast<double*>(smem);
-  C64* lists = reinterpret_cast<C64*>(sc + slab);
-  int* cnts = reinterpret_cast<int*>(lists + (size_t)WAVES * cap);
+  const TopkLds<C64> L(sc + slab, WAVES, cap);
   // Token table: posting range + idf of up to kBmTok query tokens at a time (32: a UCC-en query has 19 tokens; the
   // 1 KiB region is reused by the ranking — 64 survivor keys + 64 exact scores — and a 64-token table made it
   // 1.5 KiB: 25 -> 27 resident waves per CU at UCC-en size).
-  long* tk_ps = reinterpret_cast<long*>(cnts + 4);
+  long* tk_ps = reinterpret_cast<long*>(L.cnts + kBmCnts);
   long* tk_pe = tk_ps + kBmTok;
   double* tk_w = reinterpret_cast<double*>(tk_pe + kBmTok);
   int* tk_n = reinterpret_cast<int*>(tk_ps + 128);  // tokens of the current group that have postings in this slab
@@ -422,7 +421,7 @@ __device__ __forceinline__ void bm25_block_query(
 #endif
 
   WaveTopK<C64> tk;
-  tk.init(lists + (size_t)wave * cap, cap, k);
+  tk.init(L.list(wave), cap, k);
   // Short slab and shallow k (bm_use_argmax; the serving shape is 591 docs, k = 10): bm25_argmax_rounds.
   bool done = false;
   if (WAVES == 1 && bm_use_argmax(k, slab)) {
@@ -441,19 +440,8 @@ __device__ __forceinline__ void bm25_block_query(
     }
     tk.finalize(lane);
   }
-  if (WAVES > 1) block_combine_topk(tk, lists, cap, WAVES, wave, lane, cnts);
-  if (wave == 0) {
-    if (fin_ids) {
-      for (int j = lane; j < k; j += 64) {
-        bool v = j < tk.cnt;
-        fin_scores[(size_t)qi * k + j] = v ? unord64(tk.buf[j].key) : -DBL_MAX;
-        fin_ids[(size_t)qi * k + j] = v ? tk.buf[j].idv : -1ll;
-      }
-    } else {
-      C64* dst = part + ((size_t)slab_ix * nq + qi) * k;
-      for (int j = lane; j < k; j += 64) dst[j] = (j < tk.cnt) ? tk.buf[j] : C64::pad();
-    }
-  }
+  if (WAVES > 1) block_combine_topk(tk, L, WAVES, wave, lane);
+  if (wave == 0) topk_emit(tk.buf, tk.cnt, k, lane, fin_scores, fin_ids, (size_t)qi, part, (size_t)slab_ix * nq + qi);
 }
 
 template <int WAVES, int NVT>
@@ -466,40 +454,6 @@ __global__ __launch_bounds__(WAVES * 64) void bm25_score_topk_kernel(
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   bm25_block_query<WAVES, NVT>(term_ptr, post_doc, post_w, idf, n_terms, n_docs, q_terms, q_ptr, nq, k, cap, slab, use_select, scores_out, part, fin_scores, fin_ids,
                                (int)blockIdx.y, (int)blockIdx.x, smem);
-}
-
-static __global__ __launch_bounds__(256) void bm25_merge_kernel(const C64* __restrict__ part, int nparts, int nq, int k,
-                                                          int cap, double* __restrict__ out_scores,
-                                                          long long* __restrict__ out_ids) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  C64* lists = reinterpret_cast<C64*>(smem);
-  int* cnts = reinterpret_cast<int*>(lists + (size_t)kBmWaves * cap);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int qi = blockIdx.x;
-  WaveTopK<C64> tk;
-  tk.init(lists + (size_t)wave * cap, cap, k);
-  const long total = (long)nparts * k;
-  for (long base = (long)wave * 64; base < total; base += (long)kBmWaves * 64) {
-    long i = base + lane;
-    bool v = i < total;
-    C64 c = C64::pad();
-    if (v) {
-      long p = i / k, j = i - p * k;
-      c = part[((size_t)p * nq + qi) * k + j];
-      v = !c.is_pad();
-    }
-    tk.push_lanes(c, v, lane);
-  }
-  tk.finalize(lane);
-  block_combine_topk(tk, lists, cap, kBmWaves, wave, lane, cnts);
-  if (wave == 0) {
-    for (int j = lane; j < k; j += 64) {
-      bool v = j < tk.cnt;
-      C64 c = v ? tk.buf[j] : C64::pad();
-      out_scores[(size_t)qi * k + j] = v ? unord64(c.key) : -DBL_MAX;
-      out_ids[(size_t)qi * k + j] = v ? c.idv : -1ll;
-    }
-  }
 }
 
 }  // namespace amdr

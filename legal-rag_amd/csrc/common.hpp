@@ -191,10 +191,6 @@ struct MaxsimRaw {
 };
 int maxsim_raw(amdr_maxsim_t* h, MaxsimRaw* out);  // (maxsim.hip)
 int bm25_device_of(const amdr_bm25_t* h);
-// [n_parts, nq, k_in] (score, id) lists -> [nq, k_out], score descending, ties -> lower id; id < 0 = padding (dense.hip)
-template <class T>
-int launch_merge_parts(const T* scores, const int64_t* ids, int nparts, int nq, int k_in, int k_out, T* out_scores,
-                       int64_t* out_ids, hipStream_t st);
 std::mutex& dense_mutex(amdr_dense_t* h);
 std::mutex& bm25_mutex(amdr_bm25_t* h);
 int dense_device_of(const amdr_dense_t* h);

@@ -14,6 +14,7 @@
 #include "dense_fp16.hpp"
 #include "dense_hi_image.hpp"
 #include "topk.hpp"
+#include "topk_merge.hpp"
 
 #include <algorithm>
 #include <cfloat>
@@ -25,7 +26,8 @@ namespace amdr {
 
 constexpr int kWaves = 4;  // 256-thread blocks
 
-// grid: (x = row slabs, y = query groups of NQ).  LDS: kWaves*NQ*cap C32 + ints.
+// grid: (x = row slabs, y = query groups of NQ).  LDS: TopkLds of kWaves*NQ lists (query b's group: lists b*kWaves ...)
+// over one set of kWaves counts.
 // NT: the chunk matrix is read with the non-temporal cache policy.  A matrix that does not fit the
 // 256 MiB Infinity Cache is read once per scan and gains nothing from being kept: measured on
 // 10 M x 768 (30.7 GB), one query per scan 4.85-4.96 -> 4.44-4.58 ms (6.3 -> 6.7-6.9 TB/s), four queries
@@ -38,8 +40,7 @@ __global__ __launch_bounds__(256) void dense_scan_topk_kernel(const float* __res
                                                                float* __restrict__ fin_scores /* single slab */,
                                                                long long* __restrict__ fin_ids) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  C32* lists = reinterpret_cast<C32*>(smem);
-  int* cnts = reinterpret_cast<int*>(lists + (size_t)kWaves * NQ * cap);
+  const TopkLds<C32> L(smem, kWaves * NQ, cap);
 
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
@@ -58,7 +59,7 @@ __global__ __launch_bounds__(256) void dense_scan_topk_kernel(const float* __res
 
   WaveTopK<C32> tk[NQ];
 #pragma unroll
-  for (int b = 0; b < NQ; ++b) tk[b].init(lists + ((size_t)b * kWaves + wave) * cap, cap, k);
+  for (int b = 0; b < NQ; ++b) tk[b].init(L.list(b * kWaves + wave), cap, k);
 
   const long row_lo = (long)blockIdx.x * rows_per_block;
   long row_hi = row_lo + rows_per_block;
@@ -103,20 +104,10 @@ __global__ __launch_bounds__(256) void dense_scan_topk_kernel(const float* __res
   for (int b = 0; b < NQ; ++b) tk[b].finalize(lane);
 #pragma unroll
   for (int b = 0; b < NQ; ++b) {
-    block_combine_topk(tk[b], lists + (size_t)b * kWaves * cap, cap, kWaves, wave, lane, cnts);
-    if (wave == 0 && qbase + b < nq_total) {
-      if (fin_ids) {  // single slab: this list is the final answer, no merge launch follows
-        for (int j = lane; j < k; j += 64) {
-          const bool v = j < tk[b].cnt;
-          const C32 c = v ? tk[b].buf[j] : C32::pad();
-          fin_scores[(size_t)(qbase + b) * k + j] = v ? c.score() : -FLT_MAX;
-          fin_ids[(size_t)(qbase + b) * k + j] = v ? c.id() : -1ll;
-        }
-      } else {
-        C32* dst = part + ((size_t)blockIdx.x * nq_total + (qbase + b)) * k;
-        for (int j = lane; j < k; j += 64) dst[j] = (j < tk[b].cnt) ? tk[b].buf[j] : C32::pad();
-      }
-    }
+    block_combine_topk(tk[b], L.list(b * kWaves), cap, kWaves, wave, lane, L.cnts);
+    if (wave == 0 && qbase + b < nq_total)
+      topk_emit(tk[b].buf, tk[b].cnt, k, lane, fin_scores, fin_ids, (size_t)(qbase + b), part,
+                (size_t)blockIdx.x * nq_total + (qbase + b));
     __syncthreads();
   }
 }
@@ -157,100 +148,6 @@ __global__ __launch_bounds__(256) void dense_all_scores_kernel(const float* __re
   const float acc = dense_row_dot(X + (size_t)r * d, Q + (size_t)qi * d, d, lane);
   if (lane == 63) S[(size_t)qi * ldS + r] = acc;
 }
-
-// One block per query: stream the per-block lists, keep the best k, decode.
-__global__ __launch_bounds__(256) void dense_merge_kernel(const C32* __restrict__ part, int nparts, int nq, int k,
-                                                           int cap, float* __restrict__ out_scores,
-                                                           long long* __restrict__ out_ids) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  C32* lists = reinterpret_cast<C32*>(smem);
-  int* cnts = reinterpret_cast<int*>(lists + (size_t)kWaves * cap);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int qi = blockIdx.x;
-  WaveTopK<C32> tk;
-  tk.init(lists + (size_t)wave * cap, cap, k);
-  const long total = (long)nparts * k;
-  for (long base = (long)wave * 64; base < total; base += (long)kWaves * 64) {
-    long i = base + lane;
-    bool v = i < total;
-    C32 c = C32::pad();
-    if (v) {
-      long p = i / k, j = i - p * k;
-      c = part[((size_t)p * nq + qi) * k + j];
-      v = !c.is_pad();
-    }
-    tk.push_lanes(c, v, lane);
-  }
-  tk.finalize(lane);
-  block_combine_topk(tk, lists, cap, kWaves, wave, lane, cnts);
-  if (wave == 0) {
-    for (int j = lane; j < k; j += 64) {
-      bool v = j < tk.cnt;
-      C32 c = v ? tk.buf[j] : C32::pad();
-      out_scores[(size_t)qi * k + j] = v ? c.score() : -FLT_MAX;
-      out_ids[(size_t)qi * k + j] = v ? c.id() : -1ll;
-    }
-  }
-}
-
-// Generic [n_parts, nq, k_in] (score, global id) merge used after the RCCL
-// all-gather of per-shard results.  T = float or double.
-template <class T>
-__global__ __launch_bounds__(256) void merge_parts_kernel(const T* __restrict__ scores,
-                                                           const long long* __restrict__ ids, int nparts, int nq,
-                                                           int k_in, int k_out, int cap, T* __restrict__ out_scores,
-                                                           long long* __restrict__ out_ids) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  C64* lists = reinterpret_cast<C64*>(smem);
-  int* cnts = reinterpret_cast<int*>(lists + (size_t)kWaves * cap);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int qi = blockIdx.x;
-  WaveTopK<C64> tk;
-  tk.init(lists + (size_t)wave * cap, cap, k_out);
-  const long total = (long)nparts * k_in;
-  for (long base = (long)wave * 64; base < total; base += (long)kWaves * 64) {
-    long i = base + lane;
-    bool v = i < total;
-    C64 c = C64::pad();
-    if (v) {
-      long p = i / k_in, j = i - p * k_in;
-      size_t off = ((size_t)p * nq + qi) * k_in + j;
-      long long id = ids[off];
-      v = id >= 0;
-      if (v) c = sizeof(T) == 8 ? C64::make((double)scores[off], id) : C64::make32((float)scores[off], id);
-    }
-    tk.push_lanes(c, v, lane);
-  }
-  tk.finalize(lane);
-  block_combine_topk(tk, lists, cap, kWaves, wave, lane, cnts);
-  if (wave == 0) {
-    for (int j = lane; j < k_out; j += 64) {
-      bool v = j < tk.cnt;
-      C64 c = v ? tk.buf[j] : C64::pad();
-      T s;
-      if (sizeof(T) == 8)
-        s = v ? (T)unord64(c.key) : (T)(-DBL_MAX);
-      else
-        s = v ? (T)unord32((u32)c.key) : (T)(-FLT_MAX);
-      out_scores[(size_t)qi * k_out + j] = s;
-      out_ids[(size_t)qi * k_out + j] = v ? c.idv : -1ll;
-    }
-  }
-}
-
-template <class T>
-int launch_merge_parts(const T* scores, const int64_t* ids, int nparts, int nq, int k_in, int k_out, T* out_scores,
-                       int64_t* out_ids, hipStream_t st) {
-  int cap = topk_cap(k_out);
-  size_t lds = (size_t)kWaves * cap * sizeof(C64) + kWaves * sizeof(int);
-  hipLaunchKernelGGL((merge_parts_kernel<T>), dim3(nq), dim3(256), lds, st, scores, (const long long*)ids, nparts, nq,
-                     k_in, k_out, cap, out_scores, (long long*)out_ids);
-  AMDR_HIP(hipGetLastError());
-  return AMDR_OK;
-}
-template int launch_merge_parts<float>(const float*, const int64_t*, int, int, int, int, float*, int64_t*, hipStream_t);
-template int launch_merge_parts<double>(const double*, const int64_t*, int, int, int, int, double*, int64_t*,
-                                        hipStream_t);
 
 }  // namespace amdr
 
@@ -345,7 +242,7 @@ int make_plan(int64_t n, int d, int nq, int k, ScanPlan* p) {
   p->grid_x = (int)((n + p->rows_per_block - 1) / p->rows_per_block);
   if (p->grid_x < 1) p->grid_x = 1;
   p->grid_y = ceil_div(nq, nqb);
-  p->lds = (size_t)kWaves * nqb * p->cap * sizeof(C32) + kWaves * sizeof(int);
+  p->lds = TopkLds<C32>::bytes(kWaves * nqb, p->cap, kWaves);
   p->part_bytes = (size_t)p->grid_x * nq * k * sizeof(C32);
   return AMDR_OK;
 }
@@ -710,20 +607,13 @@ int profiled(amdr_dense* h, hipStream_t st, F&& launch) {
   return AMDR_OK;
 }
 
-// the nparts slab lists of each of nq queries -> its top k
-int launch_merge(const C32* part, int nparts, int nq, int k, int cap, float* out_scores, int64_t* out_ids, hipStream_t st) {
-  const size_t lds = (size_t)kWaves * cap * sizeof(C32) + kWaves * sizeof(int);
-  hipLaunchKernelGGL(dense_merge_kernel, dim3(nq), dim3(256), lds, st, part, nparts, nq, k, cap, out_scores, (long long*)out_ids);
-  AMDR_HIP(hipGetLastError());
-  return AMDR_OK;
-}
 // one top-k pass over a [m][ld] score matrix with `cols` valid columns (slab lists + merge, or direct)
 int topk_pass(const DenseMfmaPlan& p, const float* S, long cols, int m, int k, DevBuf& partb, float* out_scores,
               int64_t* out_ids, hipStream_t st) {
   const bool direct = p.slabs == 1;  // one slab: its list is the answer, no merge launch
   int rc = dense_mfma_launch_topk(p, S, cols, m, k, partb.p, direct ? out_scores : nullptr, direct ? out_ids : nullptr, st);
   if (rc || direct) return rc;
-  return launch_merge(partb.as<C32>(), p.slabs, m, k, p.cap, out_scores, out_ids, st);
+  return launch_merge_packed(partb.as<C32>(), p.slabs, m, k, p.cap, out_scores, out_ids, st);
 }
 
 // the image and the workspaces of the fp16 two-pass form; false: not available now (allocating the image failed before, or
@@ -930,7 +820,7 @@ int run_search_scan(amdr_dense* h, int ws, const float* Q_dev, int nq, int k, fl
     if (rc) return rc;
   }
   if (direct) return AMDR_OK;
-  return launch_merge(part, h->n > 0 ? p.grid_x : 0, nq, k, p.cap, scores_dev, ids_dev, st);  // (an empty index: padding)
+  return launch_merge_packed(part, h->n > 0 ? p.grid_x : 0, nq, k, p.cap, scores_dev, ids_dev, st);  // (an empty index: padding)
 }
 
 // One search on workspace `ws`; with a tail (amdr_dense_search_fuse_device), the fusion behind it — pass by pass in the
@@ -1330,7 +1220,7 @@ int amdr_dense_plan_info(const amdr_dense_t* h, int32_t nq, int32_t k, char* buf
     DenseMfmaPlan p;
     dense_mfma_plan((long)h->n, h->d, m, k, &p);
     const PassForm f = batched_pass_form(h, pins, r, p, m, k, nullptr);
-    const char* tail = p.slabs == 1 ? "scores_slab_topk_kernel" : "scores_slab_topk_kernel + dense_merge_kernel";
+    const char* tail = p.slabs == 1 ? "scores_slab_topk_kernel" : "scores_slab_topk_kernel + merge_parts_kernel";
     if (f.small_hi && !h->small_failed) {
       snprintf(buf, buf_len,
                "dsh_scores_kernel fp16 first pass queries_per_launch=%d (dsh_split_queries_kernel + v_mfma_f32_32x32x16_f16 on "
@@ -1352,7 +1242,7 @@ int amdr_dense_plan_info(const amdr_dense_t* h, int32_t nq, int32_t k, char* buf
     ScanPlan p;
     make_plan(h->n, h->d, nq, k, &p);
     snprintf(buf, buf_len, "dense_scan_topk_kernel<NQ=%d> grid=%dx%d%s", p.nq_per_block, p.grid_x, p.grid_y,
-             p.grid_x == 1 ? "" : " + dense_merge_kernel");
+             p.grid_x == 1 ? "" : " + merge_parts_kernel");
   }
   return AMDR_OK;
 }
@@ -1447,21 +1337,6 @@ int amdr_dense_destroy(amdr_dense_t* h) {
   if (h->hi_ev) (void)hipEventDestroy(h->hi_ev);
   delete h;
   return AMDR_OK;
-}
-
-int amdr_merge_topk_f32_device(const float* scores, const int64_t* ids, int32_t n_parts, int32_t nq, int32_t k_in,
-                               int32_t k_out, float* out_scores, int64_t* out_ids, int32_t device, void* stream) {
-  AMDR_REQUIRE(scores && ids && out_scores && out_ids, "merge_topk: null buffer");
-  AMDR_REQUIRE(n_parts >= 1 && nq >= 1 && k_in >= 1 && k_out >= 1 && k_out <= AMDR_MAX_K, "merge_topk: bad sizes");
-  AMDR_HIP(hipSetDevice(device));
-  return launch_merge_parts<float>(scores, ids, n_parts, nq, k_in, k_out, out_scores, out_ids, (hipStream_t)stream);
-}
-int amdr_merge_topk_f64_device(const double* scores, const int64_t* ids, int32_t n_parts, int32_t nq, int32_t k_in,
-                               int32_t k_out, double* out_scores, int64_t* out_ids, int32_t device, void* stream) {
-  AMDR_REQUIRE(scores && ids && out_scores && out_ids, "merge_topk: null buffer");
-  AMDR_REQUIRE(n_parts >= 1 && nq >= 1 && k_in >= 1 && k_out >= 1 && k_out <= AMDR_MAX_K, "merge_topk: bad sizes");
-  AMDR_HIP(hipSetDevice(device));
-  return launch_merge_parts<double>(scores, ids, n_parts, nq, k_in, k_out, out_scores, out_ids, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -588,15 +588,14 @@ __global__ __launch_bounds__(256) void dense_hi_select_kernel(const C32* __restr
                                                               int* __restrict__ unres, int* __restrict__ flag,
                                                               unsigned int* __restrict__ unresolved, int qtiles) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  C32* lists = reinterpret_cast<C32*>(smem);
-  int* cnts = reinterpret_cast<int*>(lists + (size_t)4 * tcap);
+  const TopkLds<C32> L(smem, 4, tcap);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int q = blockIdx.x;
   const unsigned int have = qcount[q];
   const unsigned int n = have < qcap ? have : qcap;
   const C32* src = qlist + (size_t)q * qcap;
   WaveTopK<C32> tk;
-  tk.init(lists + (size_t)wave * tcap, tcap, kc1);
+  tk.init(L.list(wave), tcap, kc1);
   // Short lists (the usual case: ~kc x sample stride entries) are ranked by ONE wave in registers (topk.hpp
   // wave_select_small: lane bests, their kc-th as the cut, the few survivors sorted) — the staged selector's LDS sorts
   // (two or three per wave, then three merges) were 25 of this kernel's 32 us.  Mass ties at the cut (> 64 survivors),
@@ -635,7 +634,7 @@ __global__ __launch_bounds__(256) void dense_hi_select_kernel(const C32* __restr
       for (int u = 0; u < UN; ++u) tk.push_lanes(e[u], !e[u].is_pad(), lane);
     }
     tk.finalize(lane);
-    block_combine_topk(tk, lists, tcap, 4, wave, lane, cnts);
+    block_combine_topk(tk, L, 4, wave, lane);
     if (wave != 0) return;
   }
   // ---- the rounding bound of this query (dense_fp16.hpp)
@@ -752,7 +751,7 @@ int dense_hi2_launch_select(const void* qlist, const unsigned int* qcount, size_
                             int* flag, unsigned int* unresolved, hipStream_t st) {
   const int x_exp = 1 - dense_fp16_exp(x_scale);  // x_scale = 2^-ex = 0.5 * 2^(1 - ex)
   const int tcap = topk_cap(kc);
-  const size_t lds = (size_t)4 * tcap * sizeof(C32) + 4 * sizeof(int);
+  const size_t lds = TopkLds<C32>::bytes(4, tcap);
   hipLaunchKernelGGL(dense_hi_select_kernel, dim3(m), dim3(256), lds, st, (const C32*)qlist, qcount, (unsigned int)qcap, kc, k,
                      tcap, Q, d, row_norm_max, x_scale, x_exp, n_tiles, list, count, unres, flag, unresolved,
                      (m + hi_query_tile(d) - 1) / hi_query_tile(d));

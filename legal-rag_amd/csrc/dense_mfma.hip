@@ -301,8 +301,7 @@ __global__ __launch_bounds__(WAVES * 64) void scores_slab_topk_kernel(const floa
                                                                        float* __restrict__ fin_scores,
                                                                        long long* __restrict__ fin_ids) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  C32* lists = reinterpret_cast<C32*>(smem);
-  int* cnts = reinterpret_cast<int*>(lists + (size_t)WAVES * cap);
+  const TopkLds<C32> L(smem, WAVES, cap);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int qi = blockIdx.y;
   const long lo = (long)blockIdx.x * rows_per_slab;
@@ -310,7 +309,7 @@ __global__ __launch_bounds__(WAVES * 64) void scores_slab_topk_kernel(const floa
   if (hi > n) hi = n;
   const float* row = S + (size_t)qi * ldS;
   WaveTopK<C32> tk;
-  tk.init(lists + (size_t)wave * cap, cap, k);
+  tk.init(L.list(wave), cap, k);
   bool done = false;
   if (WAVES == 1 && k <= 64 && hi - lo <= kSelectRowsMax) {
     // short row: register selector (topk.hpp); scratch = the upper half of the staging buffer
@@ -322,15 +321,8 @@ __global__ __launch_bounds__(WAVES * 64) void scores_slab_topk_kernel(const floa
   }
   // S is read exactly once: non-temporal (slabs start on multiples of 64 rows and S rows on 128-byte lines)
   if (!done) wave_topk_sweep4<true>(tk, row, lo, hi, wave, WAVES, lane);
-  if (WAVES > 1) block_combine_topk(tk, lists, cap, WAVES, wave, lane, cnts);
-  if (wave == 0) {
-    if (fin_ids) {
-      topk_store(tk.buf, tk.cnt, k, lane, fin_scores + (size_t)qi * k, fin_ids + (size_t)qi * k);
-    } else {
-      C32* dst = part + ((size_t)blockIdx.x * nq + qi) * k;
-      for (int j = lane; j < k; j += 64) dst[j] = (j < tk.cnt) ? tk.buf[j] : C32::pad();
-    }
-  }
+  if (WAVES > 1) block_combine_topk(tk, L, WAVES, wave, lane);
+  if (wave == 0) topk_emit(tk.buf, tk.cnt, k, lane, fin_scores, fin_ids, (size_t)qi, part, (size_t)blockIdx.x * nq + qi);
 }
 
 __global__ __launch_bounds__(64) void scores_pair_topk_kernel(const float* __restrict__ S, long ldS, long n, int nq,
@@ -369,11 +361,10 @@ __global__ __launch_bounds__(256) void dense_hi_exact_select_kernel(const float*
   if (gate != nullptr && *gate == 0) return;
   const int q = blockIdx.x;
   if (unres != nullptr && unres[q] == 0) return;
-  C32* lists = reinterpret_cast<C32*>(smem);
-  int* cnts = reinterpret_cast<int*>(lists + (size_t)4 * tcap);
+  const TopkLds<C32> L(smem, 4, tcap);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   WaveTopK<C32> tk;
-  tk.init(lists + (size_t)wave * tcap, tcap, k);
+  tk.init(L.list(wave), tcap, k);
   if (chosen != nullptr) {
     int got = 0;
     for (int j0 = 0; j0 < k; j0 += 64) {
@@ -386,7 +377,7 @@ __global__ __launch_bounds__(256) void dense_hi_exact_select_kernel(const float*
     wave_lds_fence();
   } else {
     wave_topk_sweep4<false>(tk, M + (size_t)q * ldM, 0, n_tiles, wave, 4, lane);  // ldM is a multiple of 32 floats: whole float4s
-    block_combine_topk(tk, lists, tcap, 4, wave, lane, cnts);
+    block_combine_topk(tk, L, 4, wave, lane);
     if (wave != 0) return;
   }
   const int keep = tk.cnt;
@@ -514,14 +505,13 @@ __global__ __launch_bounds__(WAVES * 64) void dense_final_topk_kernel(const floa
                                                                       float* __restrict__ fin_scores,
                                                                       long long* __restrict__ fin_ids) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  C32* lists = reinterpret_cast<C32*>(smem);
-  int* cnts = reinterpret_cast<int*>(lists + (size_t)WAVES * cap);
+  const TopkLds<C32> L(smem, WAVES, cap);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int qi = blockIdx.x;
   const long hi = (long)count[qi] * 32;
   const float* row = S + (size_t)qi * ldS;
   WaveTopK<C32> tk;
-  tk.init(lists + (size_t)wave * cap, cap, k);
+  tk.init(L.list(wave), cap, k);
   bool done = false;
   if (WAVES == 1 && k <= 64 && hi <= kSelectRowsMax) {
     int got;
@@ -537,7 +527,7 @@ __global__ __launch_bounds__(WAVES * 64) void dense_final_topk_kernel(const floa
     }
   }
   if (!done) wave_topk_sweep4<false>(tk, row, 0, hi, wave, WAVES, lane);
-  if (WAVES > 1) block_combine_topk(tk, lists, cap, WAVES, wave, lane, cnts);
+  if (WAVES > 1) block_combine_topk(tk, L, WAVES, wave, lane);
   if (wave == 0) {
     for (int j = lane; j < k; j += 64) {
       // A NaN score (key 1: it sorts behind every real score) is no hit: a query or rows that score NaN come back as
@@ -653,7 +643,7 @@ int dense_mfma_launch_scores(const DenseMfmaPlan& p, const float* X, long n, int
 int dense_mfma_launch_topk(const DenseMfmaPlan& p, const float* S, long n, int nq, int k, void* part,
                            float* fin_scores, int64_t* fin_ids, hipStream_t st) {
   const int waves = p.rows_per_slab <= kSelectRowsMax ? 1 : kBW;
-  size_t lds = (size_t)waves * p.cap * sizeof(C32) + waves * sizeof(int);
+  const size_t lds = TopkLds<C32>::bytes(waves, p.cap);
   const char* pair_env = getenv("AMDR_TOPK_PAIR");  // "0" pins one query per wave (A/B, tests)
   const bool pair_off = pair_env && pair_env[0] == '0';
   if (fin_ids && p.slabs == 1 && n <= 1024 && k <= 32 && nq >= 2 && !pair_off) {
@@ -678,7 +668,7 @@ int dense_mfma_launch_topk(const DenseMfmaPlan& p, const float* S, long n, int n
 int dense_exact_select_launch(const float* M, long ldM, long n_tiles, int m, int k, int list_stride, int* list, int* count,
                               const int* unres, const int* gate, const int64_t* chosen, hipStream_t st) {
   const int tcap = topk_cap(k);
-  const size_t lds = (size_t)4 * tcap * sizeof(C32) + 4 * sizeof(int);
+  const size_t lds = TopkLds<C32>::bytes(4, tcap);
   hipLaunchKernelGGL(dense_hi_exact_select_kernel, dim3(m), dim3(chosen ? 64 : 256), lds, st, M, ldM, n_tiles, k, tcap,
                      list_stride, list, count, unres, gate, (const long long*)chosen);
   AMDR_HIP(hipGetLastError());
@@ -717,7 +707,7 @@ int dense_final_topk_launch(const float* S, long ldS, const int* list, const int
   const int cap = topk_cap(k);
   const bool one = (long)max_tiles * 32 <= kSelectRowsMax && k <= 64;
   const int waves = one ? 1 : kBW;
-  const size_t lds = (size_t)waves * cap * sizeof(C32) + waves * sizeof(int);
+  const size_t lds = TopkLds<C32>::bytes(waves, cap);
   if (one)
     hipLaunchKernelGGL(dense_final_topk_kernel<1>, dim3(m), dim3(64), lds, st, S, ldS, list, count, list_stride, n_real, k, cap,
                        fin_scores, (long long*)fin_ids);

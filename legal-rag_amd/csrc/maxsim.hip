@@ -970,13 +970,12 @@ __global__ __launch_bounds__(256) void rowscores_topk_kernel(const float* __rest
                                                               float* __restrict__ out_scores,
                                                               long long* __restrict__ out_ids) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  C32* lists = reinterpret_cast<C32*>(smem);
-  int* cnts = reinterpret_cast<int*>(lists + (size_t)kMsWaves * cap);
+  const TopkLds<C32> L(smem, kMsWaves, cap);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int qi = blockIdx.x;
   const float* row = scores + (size_t)qi * n;
   WaveTopK<C32> tk;
-  tk.init(lists + (size_t)wave * cap, cap, k);
+  tk.init(L.list(wave), cap, k);
   for (long base = (long)wave * 64; base < n; base += (long)kMsWaves * 64) {
     long i = base + lane;
     bool v = i < n;
@@ -984,7 +983,7 @@ __global__ __launch_bounds__(256) void rowscores_topk_kernel(const float* __rest
     tk.push_lanes(c, v, lane);
   }
   tk.finalize(lane);
-  block_combine_topk(tk, lists, cap, kMsWaves, wave, lane, cnts);
+  block_combine_topk(tk, L, kMsWaves, wave, lane);
   if (wave == 0) topk_store(tk.buf, tk.cnt, k, lane, out_scores + (size_t)qi * k, out_ids + (size_t)qi * k);
 }
 
@@ -1234,7 +1233,7 @@ int ms_run(amdr_maxsim* h, const MsRoute& r, const float* Q_dev, int nq, int q_l
   }
   if (scores_dev) {
     const int cap = topk_cap(k);
-    AMDR_MS_LAUNCH(rowscores_topk_kernel, dim3(nq), dim3(256), (size_t)kMsWaves * cap * sizeof(C32) + kMsWaves * sizeof(int),
+    AMDR_MS_LAUNCH(rowscores_topk_kernel, dim3(nq), dim3(256), TopkLds<C32>::bytes(kMsWaves, cap),
                    st, full_dev, n, k, cap, scores_dev, (long long*)ids_dev);
   }
   return AMDR_OK;

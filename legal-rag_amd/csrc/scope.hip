@@ -15,6 +15,7 @@
 // workspace, no counters and no ordering between blocks.
 #include "common.hpp"
 #include "topk.hpp"
+#include "topk_merge.hpp"
 
 #include <cfloat>
 #include <cmath>
@@ -90,13 +91,12 @@ __device__ __forceinline__ void scope_piece(const long long* __restrict__ scope_
 // ---- dense: one wave per scope row (dense_row_dot), lane 63's score into the wave's list ---------------------------------
 // The piece [lo, hi) of the row list against query row qr: every wave's list, combined into wave 0's (tk of wave 0 holds
 // the block's top-k afterwards).  Called by all four waves; two block barriers (block_combine_topk).
-// LDS: C32 lists[kScWaves][cap] + int cnts[kScWaves]
+// LDS: TopkLds<C32>(kScWaves, cap)
 // This wave takes rows lo + first, lo + first + step, ... (the channel kernel: first = wave, step = 4).
 __device__ __forceinline__ void scope_dense_piece(const float* __restrict__ X, long n, int d, const float* __restrict__ qr,
                                                   const long long* __restrict__ rows, long lo, long hi, int first, int step,
-                                                  int k, int cap, C32* lists, int* cnts, int wave, int lane,
-                                                  WaveTopK<C32>& tk) {
-  tk.init(lists + (size_t)wave * cap, cap, k);
+                                                  int k, const TopkLds<C32>& L, int wave, int lane, WaveTopK<C32>& tk) {
+  tk.init(L.list(wave), L.cap, k);
   for (long i = lo + first; i < hi; i += step) {
     const long r = uniform_i64(rows[i]);
     if (r < 0 || r >= n) continue;  // never dereferenced
@@ -105,28 +105,27 @@ __device__ __forceinline__ void scope_dense_piece(const float* __restrict__ X, l
     tk.push_uniform(C32::make(s, (u32)r), lane);
   }
   tk.finalize(lane);
-  block_combine_topk(tk, lists, cap, kScWaves, wave, lane, cnts);
+  block_combine_topk(tk, L, kScWaves, wave, lane);
 }
-__host__ __device__ inline size_t scope_dense_lds(int cap) { return (size_t)kScWaves * cap * sizeof(C32) + kScWaves * sizeof(int); }
 
+// The three channel kernels write row blockIdx.x * nq + q of (out_scores, out_ids): the slab lists, or — a single slab,
+// blockIdx.x = 0 — the final result itself (sc_run hands in the one or the other).
 // grid: (x = slabs, y = queries)
 __global__ __launch_bounds__(kScWaves * 64) void scope_dense_kernel(
     const float* __restrict__ X, long n, int d, const float* __restrict__ Q, const long long* __restrict__ scope_ptr,
     const long long* __restrict__ rows, const int* __restrict__ qscope, int n_scopes, int slab, int nq, int k, int cap,
-    float* __restrict__ part_scores, long long* __restrict__ part_ids, float* __restrict__ fin_scores,
-    long long* __restrict__ fin_ids) {
+    float* __restrict__ out_scores, long long* __restrict__ out_ids) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  C32* lists = reinterpret_cast<C32*>(smem);
-  int* cnts = reinterpret_cast<int*>(lists + (size_t)kScWaves * cap);
+  const TopkLds<C32> L(smem, kScWaves, cap);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int q = blockIdx.y;
   long lo, hi;
   scope_piece(scope_ptr, qscope, n_scopes, slab, blockIdx.x, q, lo, hi);
   WaveTopK<C32> tk;
-  scope_dense_piece(X, n, d, Q + (size_t)q * d, rows, lo, hi, wave, kScWaves, k, cap, lists, cnts, wave, lane, tk);
+  scope_dense_piece(X, n, d, Q + (size_t)q * d, rows, lo, hi, wave, kScWaves, k, L, wave, lane, tk);
   if (wave != 0) return;
-  const size_t row = fin_ids ? (size_t)q : (size_t)blockIdx.x * nq + q;
-  topk_store(tk.buf, tk.cnt, k, lane, (fin_ids ? fin_scores : part_scores) + row * k, (fin_ids ? fin_ids : part_ids) + row * k);
+  const size_t row = (size_t)blockIdx.x * nq + q;
+  topk_store(tk.buf, tk.cnt, k, lane, out_scores + row * k, out_ids + row * k);
 }
 
 // ---- BM25: the slab's fp64 scores in LDS, one thread per scope document, tokens in query order ---------------------------
@@ -138,7 +137,7 @@ __global__ __launch_bounds__(kScWaves * 64) void scope_dense_kernel(
 // piece of <= 64 documents — in the four-wave form the other three waves have no document of such a piece and only
 // keep the barriers company — with wave-level fences for the block barriers and no combine: the same scores, the same
 // list, no block barrier.
-// LDS (smem): double sc[slab] + C64 lists[kScWaves][cap] + int cnts[kScWaves] + token table
+// LDS (smem): double sc[slab] + TopkLds<C64>(kScWaves, cap) + token table
 struct ScBm25 {  // the index side of the BM25 piece (device pointers)
   const long long* term_ptr;
   const int* post_doc;
@@ -157,9 +156,8 @@ __device__ __forceinline__ void scope_bm25_piece(const ScBm25& B, const int* __r
   const double* __restrict__ idf = B.idf;
   const long n_terms = B.n_terms, n_docs = B.n_docs;
   double* sc = reinterpret_cast<double*>(smem);
-  C64* lists = reinterpret_cast<C64*>(sc + slab);
-  int* cnts = reinterpret_cast<int*>(lists + (size_t)kScWaves * cap);
-  long* tk_ps = reinterpret_cast<long*>(cnts + kScWaves);  // posting range + idf of up to kBmTok query tokens at a time
+  const TopkLds<C64> L(sc + slab, kScWaves, cap);
+  long* tk_ps = reinterpret_cast<long*>(L.cnts + kScWaves);  // posting range + idf of up to kBmTok query tokens at a time
   long* tk_pe = tk_ps + kBmTok;
   double* tk_w = reinterpret_cast<double*>(tk_pe + kBmTok);
   int* tk_n = reinterpret_cast<int*>(tk_w + kBmTok);
@@ -211,7 +209,7 @@ __device__ __forceinline__ void scope_bm25_piece(const ScBm25& B, const int* __r
       block_sync<SYNC>();  // the table is rewritten by the next group
     }
   }
-  tk.init(lists + (size_t)wave * cap, cap, k);
+  tk.init(L.list(wave), cap, k);
   for (int base = wave * 64; base < m; base += NT) {
     const int i = base + lane;
     const long doc = i < m ? rows[lo + i] : -1;
@@ -219,27 +217,17 @@ __device__ __forceinline__ void scope_bm25_piece(const ScBm25& B, const int* __r
     tk.push_lanes(v ? C64::make(sc[i], doc) : C64::pad(), v, lane);
   }
   tk.finalize(lane);
-  if (!ONE_WAVE) block_combine_topk(tk, lists, cap, kScWaves, wave, lane, cnts);
+  if (!ONE_WAVE) block_combine_topk(tk, L, kScWaves, wave, lane);
 }
 __host__ __device__ inline size_t scope_bm25_lds(int slab, int cap) {
-  return (size_t)slab * sizeof(double) + (size_t)kScWaves * cap * sizeof(C64) + kScWaves * sizeof(int) +
-         3 * kBmTok * sizeof(long) + 8;
-}
-// wave 0: one row of a (scores, ids) result from its finished list, -DBL_MAX / -1 behind the hits
-__device__ __forceinline__ void scope_bm25_store(const WaveTopK<C64>& tk, int k, int lane, double* __restrict__ so,
-                                                 long long* __restrict__ io) {
-  for (int j = lane; j < k; j += 64) {
-    const bool v = j < tk.cnt;
-    so[j] = v ? unord64(tk.buf[j].key) : -DBL_MAX;
-    io[j] = v ? tk.buf[j].idv : -1ll;
-  }
+  return (size_t)slab * sizeof(double) + TopkLds<C64>::bytes(kScWaves, cap) + 3 * kBmTok * sizeof(long) + 8;
 }
 
 // grid: (x = slabs, y = queries)
 __global__ __launch_bounds__(kScWaves * 64) void scope_bm25_kernel(ScBm25 B, const int* __restrict__ q_terms,
     const long long* __restrict__ q_ptr, const long long* __restrict__ scope_ptr, const long long* __restrict__ rows,
-    const int* __restrict__ qscope, int n_scopes, int slab, int nq, int k, int cap, double* __restrict__ part_scores,
-    long long* __restrict__ part_ids, double* __restrict__ fin_scores, long long* __restrict__ fin_ids) {
+    const int* __restrict__ qscope, int n_scopes, int slab, int nq, int k, int cap, double* __restrict__ out_scores,
+    long long* __restrict__ out_ids) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int q = blockIdx.y;
@@ -248,8 +236,8 @@ __global__ __launch_bounds__(kScWaves * 64) void scope_bm25_kernel(ScBm25 B, con
   WaveTopK<C64> tk;
   scope_bm25_piece<false>(B, q_terms, q_ptr, q, rows, lo, hi, slab, k, cap, smem, tk);
   if (wave != 0) return;
-  const size_t row = fin_ids ? (size_t)q : (size_t)blockIdx.x * nq + q;
-  scope_bm25_store(tk, k, lane, (fin_ids ? fin_scores : part_scores) + row * k, (fin_ids ? fin_ids : part_ids) + row * k);
+  const size_t row = (size_t)blockIdx.x * nq + q;
+  topk_store(tk.buf, tk.cnt, k, lane, out_scores + row * k, out_ids + row * k);
 }
 
 // ---- the scoped step in one launch: dense piece, BM25 piece, fusion -----------------------------------------------------
@@ -265,7 +253,7 @@ __global__ __launch_bounds__(kScWaves * 64) void scope_bm25_kernel(ScBm25 B, con
 // after the last of them.  An empty scope or a qscope outside the table reads nothing and fuses nothing (count 0).
 // A BM25 scope of <= 64 documents takes the overlapped order instead (below; AMDR_SCOPE_OVERLAP=0 pins the sequential
 // one): measured 37.7 against 46.1 us for one query with a 28-row section, the same bits.
-// LDS: the dense lists (scope_dense_lds) followed by the BM25 piece's region (scope_bm25_lds) — separate, so no barrier
+// LDS: the dense lists (TopkLds<C32>) followed by the BM25 piece's region (scope_bm25_lds) — separate, so no barrier
 // is needed between the pieces — + the packed fusion's 3.3 KB of static arrays.
 struct ScTab {  // one channel's scope table (device pointers)
   const long long* scope_ptr;
@@ -284,7 +272,7 @@ struct ScFuse {  // what only the fusion at the end needs
   int* out_mask;
   int* out_count;
 };
-__host__ __device__ inline size_t scope_hybrid_dense_lds(int cap_d) { return (scope_dense_lds(cap_d) + 15) / 16 * 16; }
+__host__ __device__ inline size_t scope_hybrid_dense_lds(int cap_d) { return (TopkLds<C32>::bytes(kScWaves, cap_d) + 15) / 16 * 16; }
 // F_at_0 must stay the FIRST parameter: wave 0 reads it from offset 0 of the kernel-argument segment when it gets to
 // the fusion.  As an ordinary argument its 33 scalar registers are loaded at the kernel's start and parked across both
 // channel pieces, which need 56 and 66 of their own: the compiler then spills 14 of them (to lanes of a vector register).
@@ -295,8 +283,7 @@ __global__ __launch_bounds__(kScWaves * 64) void scope_hybrid_kernel(
     int kb, int cap_d, int cap_b, int overlap_docs, float* __restrict__ d_scores, long long* __restrict__ d_ids,
     double* __restrict__ b_scores, long long* __restrict__ b_ids) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  C32* lists = reinterpret_cast<C32*>(smem);
-  int* cnts = reinterpret_cast<int*>(lists + (size_t)kScWaves * cap_d);
+  const TopkLds<C32> L(smem, kScWaves, cap_d);
   unsigned char* smem_b = smem + scope_hybrid_dense_lds(cap_d);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int q = blockIdx.x;
@@ -318,13 +305,13 @@ __global__ __launch_bounds__(kScWaves * 64) void scope_hybrid_kernel(
     // meet at the dense combine.  The same lists as the sequential form: the selectors' order is total.
     if (wave == 0) scope_bm25_piece<true>(B, q_terms, q_ptr, q, tb.rows, lo_b, hi_b, slab_b, kb, cap_b, smem_b, tkb);
     scope_dense_piece(X, n, d, Q + (size_t)q * d, td.rows, wave == 0 ? hi : lo, hi, wave == 0 ? 0 : wave - 1, kScWaves - 1,
-                      kd, cap_d, lists, cnts, wave, lane, tkd);  // (wave 0: no row, an empty list into the combine)
+                      kd, L, wave, lane, tkd);  // (wave 0: no row, an empty list into the combine)
     if (wave != 0) return;  // (behind the last block-wide exchange)
     topk_store(tkd.buf, tkd.cnt, kd, lane, d_scores + (size_t)q * kd, d_ids + (size_t)q * kd);
     const bool vd = seg0 && sl < tkd.cnt;
     pre.dense(vd ? tkd.buf[sl] : C32::pad(), vd);
   } else {
-    scope_dense_piece(X, n, d, Q + (size_t)q * d, td.rows, lo, hi, wave, kScWaves, kd, cap_d, lists, cnts, wave, lane, tkd);
+    scope_dense_piece(X, n, d, Q + (size_t)q * d, td.rows, lo, hi, wave, kScWaves, kd, L, wave, lane, tkd);
     if (wave == 0) {  // the dense list: out, and into wave 0's registers for the fusion (the BM25 piece has its own LDS)
       topk_store(tkd.buf, tkd.cnt, kd, lane, d_scores + (size_t)q * kd, d_ids + (size_t)q * kd);
       const bool vd = seg0 && sl < tkd.cnt;
@@ -333,7 +320,7 @@ __global__ __launch_bounds__(kScWaves * 64) void scope_hybrid_kernel(
     scope_bm25_piece<false>(B, q_terms, q_ptr, q, tb.rows, lo_b, hi_b, slab_b, kb, cap_b, smem_b, tkb);
     if (wave != 0) return;  // (behind the last block-wide exchange)
   }
-  scope_bm25_store(tkb, kb, lane, b_scores + (size_t)q * kb, b_ids + (size_t)q * kb);
+  topk_store(tkb.buf, tkb.cnt, kb, lane, b_scores + (size_t)q * kb, b_ids + (size_t)q * kb);
   const bool vb = seg0 && sl < tkb.cnt;
   pre.bm25(vb ? tkb.buf[sl] : C64::pad(), vb);
   typedef const ScFuse __attribute__((address_space(4))) * KernArg;  // (constant address space: scalar loads)
@@ -347,22 +334,21 @@ __global__ __launch_bounds__(kScWaves * 64) void scope_hybrid_kernel(
 }
 
 // ---- MaxSim: one wave per (query, scope document), the pair form of maxsim_scores_h_kernel -------------------------------
-// grid: (x = slabs, y = queries).  LDS: C32 lists[kScWaves][cap] + int cnts[kScWaves]
+// grid: (x = slabs, y = queries).  LDS: TopkLds<C32>(kScWaves, cap)
 __global__ __launch_bounds__(kScWaves * 64) void scope_maxsim_kernel(
     const unsigned char* __restrict__ img, const long long* __restrict__ doc_ptr, long n_docs, const float* __restrict__ Q,
     int q_len, float unscale_d, const long long* __restrict__ scope_ptr, const long long* __restrict__ rows,
-    const int* __restrict__ qscope, int n_scopes, int slab, int nq, int k, int cap, float* __restrict__ part_scores,
-    long long* __restrict__ part_ids, float* __restrict__ fin_scores, long long* __restrict__ fin_ids) {
+    const int* __restrict__ qscope, int n_scopes, int slab, int nq, int k, int cap, float* __restrict__ out_scores,
+    long long* __restrict__ out_ids) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  C32* lists = reinterpret_cast<C32*>(smem);
-  int* cnts = reinterpret_cast<int*>(lists + (size_t)kScWaves * cap);
+  const TopkLds<C32> L(smem, kScWaves, cap);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int q = blockIdx.y;
   const int r32 = lane & 31, h = lane >> 5;
   long lo, hi;
   scope_piece(scope_ptr, qscope, n_scopes, slab, blockIdx.x, q, lo, hi);
   WaveTopK<C32> tk;
-  tk.init(lists + (size_t)wave * cap, cap, k);
+  tk.init(L.list(wave), cap, k);
   if (lo + wave < hi) {  // wave-uniform: a wave without a document does not read its query
     ms8h qh[8], ql[8];
     float unscale;
@@ -378,10 +364,10 @@ __global__ __launch_bounds__(kScWaves * 64) void scope_maxsim_kernel(
     }
   }
   tk.finalize(lane);
-  block_combine_topk(tk, lists, cap, kScWaves, wave, lane, cnts);
+  block_combine_topk(tk, L, kScWaves, wave, lane);
   if (wave != 0) return;
-  const size_t row = fin_ids ? (size_t)q : (size_t)blockIdx.x * nq + q;
-  topk_store(tk.buf, tk.cnt, k, lane, (fin_ids ? fin_scores : part_scores) + row * k, (fin_ids ? fin_ids : part_ids) + row * k);
+  const size_t row = (size_t)blockIdx.x * nq + q;
+  topk_store(tk.buf, tk.cnt, k, lane, out_scores + row * k, out_ids + row * k);
 }
 
 // ---- host side --------------------------------------------------------------------------------------------------------------
@@ -415,8 +401,9 @@ int sc_device_region(amdr_scope* s, int chan, int nq, int k, int64_t rows_max, u
   return AMDR_OK;
 }
 
-// Launches of one channel: the grid's y holds at most 65 535 queries, longer batches go in pieces.  launch(q0, m, slabs,
-// part_scores, part_ids, direct) enqueues the scoring kernel of queries [q0, q0 + m).
+// Launches of one channel: the grid's y holds at most 65 535 queries, longer batches go in pieces.  launch(q0, m, slab,
+// slabs, cap, out_scores, out_ids) enqueues the scoring kernel of queries [q0, q0 + m); out: where its lists go — the
+// slab lists in `region`, merged behind it, or, with a single slab, the queries' rows of the result.
 template <class T, class Launch>
 int sc_run(int chan, int nq, int k, int64_t rows_max, unsigned char* region, T* scores_dev, int64_t* ids_dev, hipStream_t st,
            Launch&& launch) {
@@ -424,16 +411,14 @@ int sc_run(int chan, int nq, int k, int64_t rows_max, unsigned char* region, T* 
   const int cap = topk_cap(k);
   for (int q0 = 0; q0 < nq; q0 += 65535) {
     const int m = nq - q0 < 65535 ? nq - q0 : 65535;
-    T* ps = nullptr;
-    int64_t* pi = nullptr;
-    if (slabs > 1) {
-      ps = reinterpret_cast<T*>(region);
-      pi = reinterpret_cast<int64_t*>(region + scope_score_bytes(chan, slabs, nq, k));
-    }
-    launch(q0, m, slab, slabs, cap, ps, pi);
+    T* fs = scores_dev + (size_t)q0 * k;
+    int64_t* fi = ids_dev + (size_t)q0 * k;
+    T* ps = slabs > 1 ? reinterpret_cast<T*>(region) : fs;
+    int64_t* pi = slabs > 1 ? reinterpret_cast<int64_t*>(region + scope_score_bytes(chan, slabs, nq, k)) : fi;
+    launch(q0, m, slab, slabs, cap, ps, (long long*)pi);
     AMDR_HIP(hipGetLastError());
     if (slabs > 1) {
-      int rc = launch_merge_parts<T>(ps, pi, slabs, m, k, k, scores_dev + (size_t)q0 * k, ids_dev + (size_t)q0 * k, st);
+      int rc = launch_merge_parts<T>(ps, pi, slabs, m, k, k, fs, fi, st);
       if (rc) return rc;
     }
   }
@@ -447,42 +432,32 @@ int sc_dense_run(amdr_dense_t* dense, const float* Q, const ScTable& t, int nq, 
   int d;
   dense_matrix(dense, &X, &n, &d);
   return sc_run<float>(kDense, nq, k, t.rows_max, region, scores_dev, ids_dev, st,
-                       [&](int q0, int m, int slab, int slabs, int cap, float* ps, int64_t* pi) {
-                         const size_t lds = scope_dense_lds(cap);
-                         const bool direct = slabs == 1;
-                         hipLaunchKernelGGL(scope_dense_kernel, dim3(slabs, m), dim3(kScWaves * 64), lds, st, X, n, d,
-                                            Q + (size_t)q0 * d, t.scope_ptr, t.rows, t.qscope + q0, t.n_scopes, slab, m, k, cap,
-                                            ps, (long long*)pi, direct ? scores_dev + (size_t)q0 * k : nullptr,
-                                            direct ? (long long*)ids_dev + (size_t)q0 * k : nullptr);
+                       [&](int q0, int m, int slab, int slabs, int cap, float* os, long long* oi) {
+                         hipLaunchKernelGGL(scope_dense_kernel, dim3(slabs, m), dim3(kScWaves * 64),
+                                            TopkLds<C32>::bytes(kScWaves, cap), st, X, n, d, Q + (size_t)q0 * d, t.scope_ptr,
+                                            t.rows, t.qscope + q0, t.n_scopes, slab, m, k, cap, os, oi);
                        });
 }
 
 int sc_bm25_run(const Bm25Raw& b, const int* q_terms, const long long* q_ptr, const ScTable& t, int nq, int k,
                 unsigned char* region, double* scores_dev, int64_t* ids_dev, hipStream_t st) {
   return sc_run<double>(kBm25, nq, k, t.rows_max, region, scores_dev, ids_dev, st,
-                        [&](int q0, int m, int slab, int slabs, int cap, double* ps, int64_t* pi) {
-                          const size_t lds = scope_bm25_lds(slab, cap);
-                          const bool direct = slabs == 1;
+                        [&](int q0, int m, int slab, int slabs, int cap, double* os, long long* oi) {
                           const ScBm25 B{b.term_ptr, b.post_doc, b.post_w, b.idf, b.n_terms, b.n_docs};
-                          hipLaunchKernelGGL(scope_bm25_kernel, dim3(slabs, m), dim3(kScWaves * 64), lds, st, B, q_terms,
-                                             q_ptr + q0, t.scope_ptr,
-                                             t.rows, t.qscope + q0, t.n_scopes, slab, m, k, cap, ps, (long long*)pi,
-                                             direct ? scores_dev + (size_t)q0 * k : nullptr,
-                                             direct ? (long long*)ids_dev + (size_t)q0 * k : nullptr);
+                          hipLaunchKernelGGL(scope_bm25_kernel, dim3(slabs, m), dim3(kScWaves * 64), scope_bm25_lds(slab, cap),
+                                             st, B, q_terms, q_ptr + q0, t.scope_ptr, t.rows, t.qscope + q0, t.n_scopes, slab, m,
+                                             k, cap, os, oi);
                         });
 }
 
 int sc_maxsim_run(const MaxsimRaw& r, const float* Q, int q_len, const ScTable& t, int nq, int k, unsigned char* region,
                   float* scores_dev, int64_t* ids_dev, hipStream_t st) {
   return sc_run<float>(kMaxsim, nq, k, t.rows_max, region, scores_dev, ids_dev, st,
-                       [&](int q0, int m, int slab, int slabs, int cap, float* ps, int64_t* pi) {
-                         const size_t lds = (size_t)kScWaves * cap * sizeof(C32) + kScWaves * sizeof(int);
-                         const bool direct = slabs == 1;
-                         hipLaunchKernelGGL(scope_maxsim_kernel, dim3(slabs, m), dim3(kScWaves * 64), lds, st, r.img, r.doc_ptr,
-                                            r.n_docs, Q + (size_t)q0 * q_len * kDim, q_len, r.unscale_d, t.scope_ptr, t.rows,
-                                            t.qscope + q0, t.n_scopes, slab, m, k, cap, ps, (long long*)pi,
-                                            direct ? scores_dev + (size_t)q0 * k : nullptr,
-                                            direct ? (long long*)ids_dev + (size_t)q0 * k : nullptr);
+                       [&](int q0, int m, int slab, int slabs, int cap, float* os, long long* oi) {
+                         hipLaunchKernelGGL(scope_maxsim_kernel, dim3(slabs, m), dim3(kScWaves * 64),
+                                            TopkLds<C32>::bytes(kScWaves, cap), st, r.img, r.doc_ptr, r.n_docs,
+                                            Q + (size_t)q0 * q_len * kDim, q_len, r.unscale_d, t.scope_ptr, t.rows,
+                                            t.qscope + q0, t.n_scopes, slab, m, k, cap, os, oi);
                        });
 }
 

@@ -601,22 +601,23 @@ __device__ __forceinline__ void pair_rows_staged(const float* __restrict__ S, lo
     wave_lds_fence();
   }
 }
-// One row of a (scores, ids) result: -FLT_MAX / -1 behind the hits.  From a finished list in LDS ...
-__device__ __forceinline__ void topk_store(const C32* list, int cnt, int k, int lane, float* __restrict__ scores,
-                                           long long* __restrict__ ids) {
-  for (int j = lane; j < k; j += 64) {
-    const bool v = j < cnt;
-    const C32 c = v ? list[j] : C32::pad();
-    scores[j] = v ? c.score() : -FLT_MAX;
-    ids[j] = v ? c.id() : -1ll;
+// ---- the frame around the selector: the block's LDS, the combine, the result stores ---------------------------------
+// LDS of a block that ranks with WaveTopK: C lists[nlists][cap], then int cnts[ncnts].  One list and one count per wave
+// (ncnts = 0: as many counts as lists); dense_scan_topk_kernel keeps NQ groups of lists over one set of counts, BM25's
+// one-wave form four counts (the token table behind them stays 8-byte aligned).  Launchers take bytes(), kernels carve
+// smem with the same arguments: the two cannot disagree.
+template <class C>
+struct TopkLds {
+  C* lists;
+  int* cnts;
+  int cap;
+  __host__ __device__ static constexpr size_t bytes(int nlists, int cap, int ncnts = 0) {
+    return (size_t)nlists * cap * sizeof(C) + (size_t)(ncnts ? ncnts : nlists) * sizeof(int);
   }
-}
-// ... or position j of it, held by this lane
-__device__ __forceinline__ void topk_store(const C32& c, bool valid, int j, float* __restrict__ scores,
-                                           long long* __restrict__ ids) {
-  scores[j] = valid ? c.score() : -FLT_MAX;
-  ids[j] = valid ? c.id() : -1ll;
-}
+  __device__ __forceinline__ TopkLds(void* smem, int nlists, int cap_)
+      : lists(reinterpret_cast<C*>(smem)), cnts(reinterpret_cast<int*>(lists + (size_t)nlists * cap_)), cap(cap_) {}
+  __device__ __forceinline__ C* list(int i) const { return lists + (size_t)i * cap; }
+};
 
 // Merge the finalized lists of all waves of a block into wave 0's list.
 // Call with all threads; contains block barriers.  lists: [nwaves][stride]
@@ -639,6 +640,63 @@ __device__ inline void block_combine_topk(WaveTopK<C>& tk, C* lists, int stride,
     tk.finalize(lane);
   }
   __syncthreads();
+}
+template <class C>
+__device__ __forceinline__ void block_combine_topk(WaveTopK<C>& tk, const TopkLds<C>& L, int nwaves, int wave, int lane) {
+  block_combine_topk(tk, L.lists, L.cap, nwaves, wave, lane, L.cnts);
+}
+
+// One row of a (scores, ids) result from a finished list in LDS, by one wave: -FLT_MAX / -1 behind the hits ...
+__device__ __forceinline__ void topk_store(const C32* list, int cnt, int k, int lane, float* __restrict__ scores,
+                                           long long* __restrict__ ids) {
+  for (int j = lane; j < k; j += 64) {
+    const bool v = j < cnt;
+    const C32 c = v ? list[j] : C32::pad();
+    scores[j] = v ? c.score() : -FLT_MAX;
+    ids[j] = v ? c.id() : -1ll;
+  }
+}
+// ... fp64 keys (C64::make): -DBL_MAX / -1 ...
+__device__ __forceinline__ void topk_store(const C64* list, int cnt, int k, int lane, double* __restrict__ scores,
+                                           long long* __restrict__ ids) {
+  for (int j = lane; j < k; j += 64) {
+    const bool v = j < cnt;
+    const C64 c = v ? list[j] : C64::pad();
+    scores[j] = v ? unord64(c.key) : -DBL_MAX;
+    ids[j] = v ? c.idv : -1ll;
+  }
+}
+// ... 32-bit keys with 64-bit ids (C64::make32)
+__device__ __forceinline__ void topk_store(const C64* list, int cnt, int k, int lane, float* __restrict__ scores,
+                                           long long* __restrict__ ids) {
+  for (int j = lane; j < k; j += 64) {
+    const bool v = j < cnt;
+    const C64 c = v ? list[j] : C64::pad();
+    scores[j] = v ? unord32((u32)c.key) : -FLT_MAX;
+    ids[j] = v ? c.idv : -1ll;
+  }
+}
+// position j of a list, held by this lane
+__device__ __forceinline__ void topk_store(const C32& c, bool valid, int j, float* __restrict__ scores,
+                                           long long* __restrict__ ids) {
+  scores[j] = valid ? c.score() : -FLT_MAX;
+  ids[j] = valid ? c.id() : -1ll;
+}
+// one row of a packed slab list (merged later: topk_merge.hip): C::pad() behind the hits
+template <class C>
+__device__ __forceinline__ void topk_store_part(const C* list, int cnt, int k, int lane, C* __restrict__ dst) {
+  for (int j = lane; j < k; j += 64) dst[j] = (j < cnt) ? list[j] : C::pad();
+}
+// What a slab kernel does with its finished list: row `fin_row` of the final result when fin_ids is given (a single slab:
+// no merge follows), else row `part_row` of the packed slab lists.
+template <class C, class T>
+__device__ __forceinline__ void topk_emit(const C* list, int cnt, int k, int lane, T* __restrict__ fin_scores,
+                                          long long* __restrict__ fin_ids, size_t fin_row, C* __restrict__ part,
+                                          size_t part_row) {
+  if (fin_ids)
+    topk_store(list, cnt, k, lane, fin_scores + fin_row * k, fin_ids + fin_row * k);
+  else
+    topk_store_part(list, cnt, k, lane, part + part_row * k);
 }
 
 }  // namespace amdr

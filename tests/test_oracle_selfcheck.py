@@ -29,6 +29,23 @@ def test_topk_ties_and_padding():
     assert mi[0].tolist() == [2, 7, 8] and ms[0].tolist() == [0.9, 0.9, 0.7]
 
 
+def test_merge_topk_orders_nan_signed_zero_and_padding():
+    """What tests/test_topk_merge_gpu.py relies on: a NaN ranks behind every real score and ahead of padding, -0.0 and
+    +0.0 tie (the lower id first, either way round), padding (id -1) never surfaces whatever score it carries, and the
+    scores come back with the bits they went in with."""
+    for dt in (np.float32, np.float64):
+        nan = np.array([np.nan], dtype=dt)[0]
+        s0 = np.array([[-0.0, nan, 9e9, -1e30]], dtype=dt)
+        s1 = np.array([[0.0, 0.0, 7.0, -0.0]], dtype=dt)
+        i0 = np.array([[5, 1, -1, (1 << 33) + 2]], dtype=np.int64)
+        i1 = np.array([[3, 8, -1, 9]], dtype=np.int64)
+        s, i = OD.merge_topk([s0, s1], [i0, i1], 8)
+        assert i[0].tolist() == [3, 5, 8, 9, (1 << 33) + 2, 1, -1, -1]
+        assert np.signbit(s[0, :4]).tolist() == [False, True, False, True] and np.all(s[0, :4] == 0)
+        assert s[0, 4] == dt(-1e30) and np.isnan(s[0, 5])
+        assert np.all(s[0, 6:] == (-np.finfo(np.float32).max if dt == np.float32 else -np.inf))
+
+
 def test_bm25_toy_golden_and_hand_check():
     g = load_golden("bm25_toy.json")
     bm = OB.BM25Okapi([OB.tokenize_en(t) for t in g["docs"]])
