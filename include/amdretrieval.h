@@ -92,7 +92,8 @@ int amdr_dense_score_rows(amdr_dense_t* h, const float* Q_host, int32_t nq, cons
  * the oracle on exactly the matrix that is resident in HBM) */
 int amdr_dense_read_rows(const amdr_dense_t* h, int64_t row0, int64_t nrows, float* out_host);
 /* Which kernels a search of nq queries at depth k would launch on this index, and how the work
- * is cut (e.g. "dense_panel_scores_kernel nb=6 parts=7 blocks=2044 + scores_slab_topk_kernel"):
+ * is cut (e.g. "dense_panel_scores_kernel nb=6 parts=7 blocks=2044 + scores_pair_topk_kernel";
+ * the top-k kernel named is the one the launch picks):
  * written NUL-terminated into buf.  No device work.  bench.py names its roofline kernel with it. */
 int amdr_dense_plan_info(const amdr_dense_t* h, int32_t nq, int32_t k, char* buf, int32_t buf_len);
 /* Host-only (no device is touched): on an [n, d] matrix, out6[0..2] = the bytes amdr_dense_reserve(nq_max, k_max) sizes

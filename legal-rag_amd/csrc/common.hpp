@@ -94,6 +94,8 @@ int dense_mfma_launch_scores(const DenseMfmaPlan& p, const float* X, long n, int
                              hipStream_t st, bool tile_max = false, const int* gate = nullptr);
 int dense_mfma_launch_topk(const DenseMfmaPlan& p, const float* S, long n, int nq, int k, void* part,
                            float* fin_scores, int64_t* fin_ids, hipStream_t st);
+// the launch above ranks two queries per wave (scores_pair_topk_kernel) instead of one per block (scores_slab_topk_kernel)
+bool dense_topk_pair_applies(const DenseMfmaPlan& p, long n, int nq, int k);
 
 // ---- fp16 first pass of the two-level top-k on large matrices: dense_hi.hip ----
 bool dense_hi_supported(int d);

@@ -1220,7 +1220,9 @@ int amdr_dense_plan_info(const amdr_dense_t* h, int32_t nq, int32_t k, char* buf
     DenseMfmaPlan p;
     dense_mfma_plan((long)h->n, h->d, m, k, &p);
     const PassForm f = batched_pass_form(h, pins, r, p, m, k, nullptr);
-    const char* tail = p.slabs == 1 ? "scores_slab_topk_kernel" : "scores_slab_topk_kernel + merge_parts_kernel";
+    const char* tail = dense_topk_pair_applies(p, (long)h->n, m, k) ? "scores_pair_topk_kernel"
+                       : p.slabs == 1                              ? "scores_slab_topk_kernel"
+                                                                   : "scores_slab_topk_kernel + merge_parts_kernel";
     if (f.small_hi && !h->small_failed) {
       snprintf(buf, buf_len,
                "dsh_scores_kernel fp16 first pass queries_per_launch=%d (dsh_split_queries_kernel + v_mfma_f32_32x32x16_f16 on "

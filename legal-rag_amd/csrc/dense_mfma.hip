@@ -640,13 +640,19 @@ int dense_mfma_launch_scores(const DenseMfmaPlan& p, const float* X, long n, int
   return AMDR_OK;
 }
 
+// The top-k pass of nq queries over n columns ranks two queries per wave (scores_pair_topk_kernel): a single slab — its
+// list is the answer —, a row the pair selector holds in registers, a list of one half-wave, a pair to share the wave.
+bool dense_topk_pair_applies(const DenseMfmaPlan& p, long n, int nq, int k) {
+  const char* pair_env = getenv("AMDR_TOPK_PAIR");  // "0" pins one query per wave (A/B, tests)
+  if (pair_env && pair_env[0] == '0') return false;
+  return p.slabs == 1 && n <= 1024 && k <= 32 && nq >= 2;
+}
+
 int dense_mfma_launch_topk(const DenseMfmaPlan& p, const float* S, long n, int nq, int k, void* part,
                            float* fin_scores, int64_t* fin_ids, hipStream_t st) {
   const int waves = p.rows_per_slab <= kSelectRowsMax ? 1 : kBW;
   const size_t lds = TopkLds<C32>::bytes(waves, p.cap);
-  const char* pair_env = getenv("AMDR_TOPK_PAIR");  // "0" pins one query per wave (A/B, tests)
-  const bool pair_off = pair_env && pair_env[0] == '0';
-  if (fin_ids && p.slabs == 1 && n <= 1024 && k <= 32 && nq >= 2 && !pair_off) {
+  if (fin_ids && dense_topk_pair_applies(p, n, nq, k)) {
     hipLaunchKernelGGL(scores_pair_topk_kernel, dim3((nq + 1) / 2), dim3(64), (size_t)p.cap * sizeof(C32), st, S, p.ld,
                        n, nq, k, p.cap, fin_scores, (long long*)fin_ids);
     AMDR_HIP(hipGetLastError());
