@@ -39,6 +39,7 @@ SIGNATURES = {
     "amdr_bm25_search": "PPPiiPP", "amdr_bm25_search_device": "PPPiiPPP", "amdr_bm25_scores": "PPPiP",
     "amdr_bm25_destroy": "P",
     "amdr_tokenizer_create": "PPlP", "amdr_tokenizer_encode": "PPPiPlPP", "amdr_tokenizer_encode_joined": "PPliPlPP", "amdr_tokenizer_encode_ptrs": "PPPiPlPP", "amdr_tokenizer_spans": "PlPPiP",
+    "amdr_tokenizer_set_han": "PiPPPPld", "amdr_tokenizer_han_mode": "PP", "amdr_tokenizer_spans_han": "PPlPPiP",
     "amdr_tokenizer_destroy": "P",
     "amdr_tokenizer_pack": "PPiPlP", "amdr_tokenizer_device_create": "PiP", "amdr_tokenizer_device_reserve": "Pil",
     "amdr_tokenizer_encode_device": "PPPilPlPPP", "amdr_tokenizer_device_destroy": "P",
@@ -446,10 +447,13 @@ class BM25Index(_Handle):
 # ---------------------------------------------------------------------------
 class Tokenizer(_Handle):
     """Batched native query tokeniser + vocabulary lookup (include/amdretrieval.h, csrc/tokenize.cpp): the jieba.cut
-    rule for text without Han characters, then term ids — one call per batch, GIL released."""
+    rule for text without Han characters, then term ids — one call per batch, GIL released.
+    han: what a query holding a Han character gets (amdr_tokenizer_set_han) — "flag" (the default: needs_segmenter, no
+    terms), "char" (text.jieba_cut_restated: one Han character per token) or a text.HanDict (text.dict_cut over it)."""
     _destroy = "amdr_tokenizer_destroy"
+    HAN_MODES = {"flag": 0, "char": 1, "dict": 2}
 
-    def __init__(self, vocab: Sequence[str]):
+    def __init__(self, vocab: Sequence[str], han="flag"):
         enc = [w.encode("utf-8") for w in vocab]
         blob = b"".join(enc)
         offs = np.zeros(len(enc) + 1, dtype=np.int64)
@@ -457,10 +461,53 @@ class Tokenizer(_Handle):
         self._h = C.c_void_p()
         _check(load().amdr_tokenizer_create(C.c_char_p(blob), _p(offs, C.c_int64), C.c_int64(len(enc)), C.byref(self._h)),
                "amdr_tokenizer_create")
+        self.han = "flag"
+        if isinstance(han, str):
+            if han not in ("flag", "char"):
+                raise ValueError(f"Tokenizer: han must be 'flag', 'char' or a text.HanDict, got {han!r}")
+            if han == "char":
+                self.set_han(1)
+                self.han = "char"
+        else:
+            keys, logw, word, unknown = han.native_tables()
+            self.set_han(2, keys, logw, word, unknown)
+            self.han = "dict"
+
+    def set_han(self, mode: int, keys: Sequence[str] = (), logw=None, is_word=None, logw_unknown: float = 0.0) -> None:
+        """amdr_tokenizer_set_han as it is (before any encode and before a DeviceTokenizer is made of this handle)."""
+        enc = [k.encode("utf-8") for k in keys]
+        blob = b"".join(enc)
+        offs = np.zeros(len(enc) + 1, dtype=np.int64)
+        np.cumsum([len(e) for e in enc], out=offs[1:])
+        logw = np.ascontiguousarray(logw if logw is not None else np.zeros(len(enc)), dtype=np.float64)
+        word = np.ascontiguousarray(is_word if is_word is not None else np.zeros(len(enc)), dtype=np.uint8)
+        if logw.shape != (len(enc),) or word.shape != (len(enc),):
+            raise ValueError("set_han: logw and is_word take one entry per key")
+        _check(load().amdr_tokenizer_set_han(self._h, C.c_int32(mode), C.c_char_p(blob), _p(offs, C.c_int64),
+                                             _p(logw, C.c_double), _p(word, C.c_uint8), C.c_int64(len(enc)),
+                                             C.c_double(logw_unknown)), "amdr_tokenizer_set_han")
+
+    @property
+    def han_mode(self) -> int:
+        m = C.c_int32(-1)
+        _check(load().amdr_tokenizer_han_mode(self._h, C.byref(m)), "amdr_tokenizer_han_mode")
+        return int(m.value)
+
+    def cut_han(self, text: str) -> Optional[list]:
+        """Token strings of one text under this handle's Han mode (None: Han text in the "flag" mode)."""
+        b = text.encode("utf-8")
+        cap = max(len(b), 1)
+        st, en = np.empty(cap, dtype=np.int32), np.empty(cap, dtype=np.int32)
+        n = C.c_int32(0)
+        _check(load().amdr_tokenizer_spans_han(self._h, C.c_char_p(b), C.c_int64(len(b)), _p(st, C.c_int32),
+                                               _p(en, C.c_int32), C.c_int32(cap), C.byref(n)), "amdr_tokenizer_spans_han")
+        if n.value < 0:
+            return None
+        return [b[int(a):int(e)].decode("utf-8") for a, e in zip(st[: n.value], en[: n.value])]
 
     def encode(self, texts: Sequence[str]) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """(term_ids i32 [total], q_ptr i64 [n+1], needs_segmenter bool [n]) — the CSR BM25Index.search takes.
-        Queries flagged needs_segmenter hold a Han character and got NO terms here.  The batch crosses into native code
+        Queries flagged needs_segmenter hold a Han character and got NO terms here (han="flag" only).  The batch crosses into native code
         as ONE blob: the queries joined by NUL bytes and encoded once (two C-level operations however long the batch);
         a batch that itself contains a NUL takes the per-query offsets form."""
         n = len(texts)

@@ -79,7 +79,10 @@ class RetrievalConfig:
     shard: Optional[str] = None          # "rows": this process holds the row block of its torch.distributed rank in
                                          # HBM and every search all-gathers the per-shard top-k (retrieval/sharding.py)
     zh_tokenizer: str = "jieba"          # "jieba" (raises if Han text meets no segmenter) | "char" (explicit
-                                         # opt-in to the inexact one-character stand-in, text.py)
+                                         # opt-in to the inexact one-character stand-in, text.py) | "dict" (explicit
+                                         # opt-in to the dictionary segmenter over zh_dict_file, text.dict_cut)
+    zh_dict_file: Optional[str] = None   # zh_tokenizer = "dict": a dictionary in jieba's dict.txt format
+                                         # ("word freq [tag]" per line), e.g. jieba's own dict.txt
     query_tokenizer: str = "host"        # BM25 query side of search_batch / search_batch_arrays: "host" (native
                                          # tokeniser on CPU threads) | "device" (tokenised on the GPU, csrc/tokenize.hip,
                                          # for batches whose text the device rule decides; any other batch: host)

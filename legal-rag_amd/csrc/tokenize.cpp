@@ -11,11 +11,15 @@
 //      [a-zA-Z0-9]+(?:\.\d+)?%? are one token each and each maximal run of the remaining characters is one token;
 //      the five ASCII multi-character entries of jieba's dictionary (AT&T, C++, c++, C#, c#) are tokens wherever
 //      they start, the text between them is cut as above.
-// A query that holds a Han character is NOT tokenised here (it needs jieba's dictionary): it is flagged and the
-// caller takes the Python path (which raises unless a segmenter or the explicit stand-in is configured).
+// A query that holds a Han character is, by default, NOT tokenised here (it needs jieba's dictionary): it is flagged and
+// the caller takes the Python path (which raises unless a segmenter or an explicit stand-in is configured).  With
+// amdr_tokenizer_set_han the handle cuts such a query itself, by one of the two stand-ins of text.py: one Han character
+// per token (AMDR_HAN_CHAR, text.jieba_cut_restated) or jieba's default cut over the caller's dictionary without the HMM
+// (AMDR_HAN_DICT, text.dict_cut); the flag is then 0 and the terms are written.  tokenize_rule.hpp holds both.
 // Queries are NOT lower-cased (the reference does not, bm25_retriever.py:73).  One call handles a whole batch and
 // writes the term-id CSR amdr_bm25_search takes; ctypes releases the GIL for its duration.
 #include <atomic>
+#include <cmath>
 #include <condition_variable>
 #include <cstdint>
 #include <cstring>
@@ -73,6 +77,70 @@ int amdr_tokenizer_create(const char* vocab_blob, const int64_t* vocab_offsets, 
     }
   }
   *out = t;
+  return AMDR_OK;
+}
+
+int amdr_tokenizer_set_han(amdr_tokenizer_t* t, int32_t mode, const char* key_blob, const int64_t* key_offsets,
+                           const double* logw, const uint8_t* is_word, int64_t n_keys, double logw_unknown) {
+  AMDR_REQUIRE(t != nullptr, "tokenizer_set_han: null handle");
+  AMDR_REQUIRE(mode == AMDR_HAN_FLAG || mode == AMDR_HAN_CHAR || mode == AMDR_HAN_DICT, "tokenizer_set_han: bad mode %d",
+               mode);
+  if (mode != AMDR_HAN_DICT) n_keys = 0;  // the other modes consult no dictionary
+  AMDR_REQUIRE(mode != AMDR_HAN_DICT || (n_keys > 0 && n_keys < (1ll << 28) && key_blob && key_offsets && logw && is_word),
+               "tokenizer_set_han: the dictionary mode needs keys");
+  AMDR_REQUIRE(mode != AMDR_HAN_DICT || std::isfinite(logw_unknown), "tokenizer_set_han: logw_unknown is not finite");
+  for (int64_t i = 0; i < n_keys; ++i) {
+    AMDR_REQUIRE(key_offsets[i + 1] > key_offsets[i], "tokenizer_set_han: key %lld is empty or its offsets descend",
+                 (long long)i);
+    AMDR_REQUIRE(std::isfinite(logw[i]), "tokenizer_set_han: logw of key %lld is not finite", (long long)i);
+  }
+  AMDR_REQUIRE(n_keys == 0 || key_offsets[n_keys] - key_offsets[0] < (1ll << 31), "tokenizer_set_han: keys too long");
+  amdr_tok::HanRule han;
+  han.mode = mode;
+  t->han_blob.clear();
+  t->han_offs.clear();
+  t->han_slots.clear();
+  t->han_logw.clear();
+  t->han_word.clear();
+  if (n_keys) {
+    const int64_t base = key_offsets[0];
+    t->han_blob.assign(key_blob + base, (size_t)(key_offsets[n_keys] - base));
+    t->han_offs.resize((size_t)n_keys + 1);
+    for (int64_t i = 0; i <= n_keys; ++i) t->han_offs[(size_t)i] = (int32_t)(key_offsets[i] - base);
+    t->han_logw.assign(logw, logw + n_keys);
+    t->han_word.resize((size_t)n_keys);
+    for (int64_t i = 0; i < n_keys; ++i) t->han_word[(size_t)i] = is_word[i] ? 1 : 0;
+    size_t cap = 16;
+    while (cap < (size_t)n_keys * 2) cap <<= 1;
+    t->han_slots.assign(cap, -1);
+    han.mask = (uint32_t)(cap - 1);
+    han.slots = t->han_slots.data();
+    han.offs = t->han_offs.data();
+    han.blob = reinterpret_cast<const unsigned char*>(t->han_blob.data());
+    han.logw = t->han_logw.data();
+    han.is_word = t->han_word.data();
+    han.logw_unknown = logw_unknown;
+    for (int64_t i = 0; i < n_keys; ++i) {
+      const int32_t len = t->han_offs[(size_t)i + 1] - t->han_offs[(size_t)i];
+      if (len > han.max_key) han.max_key = len;
+    }
+    for (int64_t i = 0; i < n_keys; ++i) {  // first entry of a repeated key wins
+      const unsigned char* p = han.blob + t->han_offs[(size_t)i];
+      const int32_t len = t->han_offs[(size_t)i + 1] - t->han_offs[(size_t)i];
+      const uint32_t h = amdr_tok::hash(p, len);
+      if (amdr_tok::han_find(han, p, len, h) >= 0) continue;
+      uint32_t j = h & han.mask;
+      while (t->han_slots[j] >= 0) j = (j + 1) & han.mask;
+      t->han_slots[j] = (int32_t)i;
+    }
+  }
+  t->han = han;
+  return AMDR_OK;
+}
+
+int amdr_tokenizer_han_mode(const amdr_tokenizer_t* t, int32_t* mode) {
+  AMDR_REQUIRE(t != nullptr && mode != nullptr, "tokenizer_han_mode: null argument");
+  *mode = t->han.mode;
   return AMDR_OK;
 }
 
@@ -189,6 +257,9 @@ int encode_core(const amdr_tokenizer* t, const unsigned char* const* ptrs, const
     int64_t bytes = 0;
     for (int32_t q = lo; q < hi; ++q) bytes += lens[q] > 0 ? lens[q] : 0;
     out.reserve((size_t)(bytes / 2 + 16));
+    const amdr_tok::HanRule han = t->han;
+    std::vector<double> rv;  // this worker's route scratch (dictionary mode), grown to its longest query
+    std::vector<int32_t> rx;
     for (int32_t q = lo; q < hi; ++q) {
       const int64_t n = lens[q];
       if (n < 0 || n >= (1ll << 31) || (n > 0 && !ptrs[q])) {
@@ -197,7 +268,12 @@ int encode_core(const amdr_tokenizer* t, const unsigned char* const* ptrs, const
       }
       const unsigned char* s = ptrs[q];
       const size_t start = out.size();
-      const bool ok = tokenize(s, (int)n, [&](int x, int y) { out.push_back(t->find(s + x, (size_t)(y - x))); });
+      if (han.mode == AMDR_HAN_DICT && (size_t)n > rv.size()) {
+        rv.resize((size_t)n);
+        rx.resize((size_t)n);
+      }
+      const bool ok = tokenize(s, (int)n, han, rv.data(), rx.data(),
+                               [&](int x, int y) { out.push_back(t->find(s + x, (size_t)(y - x))); });
       if (!ok) out.resize(start);
       needs_segmenter[q] = ok ? 0 : 1;
       q_ptr[q + 1] = (int64_t)(out.size() - start);  // the count; turned into the offset below
@@ -321,6 +397,35 @@ int amdr_tokenizer_spans(const char* text, int64_t n_bytes, int32_t* starts, int
   });
   AMDR_REQUIRE(!overflow, "tokenizer_spans: span buffers too small");
   *n_tokens = ok ? n : -1;  // -1: the text holds a Han character and needs a segmenter
+  return AMDR_OK;
+}
+
+int amdr_tokenizer_spans_han(const amdr_tokenizer_t* t, const char* text, int64_t n_bytes, int32_t* starts, int32_t* ends,
+                             int32_t capacity, int32_t* n_tokens) {
+  AMDR_REQUIRE(t != nullptr, "tokenizer_spans_han: null handle");
+  AMDR_REQUIRE(n_tokens != nullptr && n_bytes >= 0 && n_bytes < (1ll << 31), "tokenizer_spans_han: bad arguments");
+  AMDR_REQUIRE(n_bytes == 0 || text, "tokenizer_spans_han: null text");
+  AMDR_REQUIRE(capacity >= 0 && (capacity == 0 || (starts && ends)), "tokenizer_spans_han: null span buffers");
+  std::vector<double> rv;
+  std::vector<int32_t> rx;
+  if (t->han.mode == AMDR_HAN_DICT) {
+    rv.resize((size_t)n_bytes);
+    rx.resize((size_t)n_bytes);
+  }
+  int32_t n = 0;
+  bool overflow = false;
+  const bool ok = tokenize(reinterpret_cast<const unsigned char*>(text), (int)n_bytes, t->han, rv.data(), rx.data(),
+                           [&](int a, int b) {
+                             if (n >= capacity) {
+                               overflow = true;
+                               return;
+                             }
+                             starts[n] = a;
+                             ends[n] = b;
+                             ++n;
+                           });
+  AMDR_REQUIRE(!overflow, "tokenizer_spans_han: span buffers too small");
+  *n_tokens = ok ? n : -1;  // -1: Han text under AMDR_HAN_FLAG
   return AMDR_OK;
 }
 

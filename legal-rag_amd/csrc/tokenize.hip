@@ -4,7 +4,11 @@
 // Replaces, as the host form in tokenize.cpp does, `tokens = list(jieba.cut(query))` + the term lookup of rank_bm25's
 // get_scores (legalrag/retrieval/bm25_retriever.py:73-74) for text without Han characters.  The rule is
 // tokenize_rule.hpp, the same source the host form compiles, and the vocabulary is a copy of a host amdr_tokenizer_t's
-// open-addressing table: the output is amdr_tokenizer_encode's, byte for byte.
+// open-addressing table: the output is amdr_tokenizer_encode's, byte for byte.  That holds for Han text too: the copy
+// takes the host handle's Han mode (amdr_tokenizer_set_han) and, in the dictionary mode, its key table, and
+// tok_count_kernel calls the same tokenize().  The table is read from HBM where it lies (a few hundred KB at most, so
+// L2-resident); the route of a query (one double and one int32 per byte) lives in the query's own byte range of two more
+// workspace arrays, so no lane holds an array sized by its query and nothing goes to scratch.
 //
 // Four launches, all enqueued on the caller's stream, no allocation (the workspace is sized by reserve):
 //   1. tok_count_kernel   one lane per query, the block's bytes staged in LDS by coalesced loads (when they fit in
@@ -37,9 +41,16 @@ struct amdr_tokenizer_device {
   int64_t* offs = nullptr;         // [n_terms + 1]: term i = blob[offs[i] .. offs[i + 1])
   unsigned char* blob = nullptr;   // the terms' bytes
   int32_t* single = nullptr;       // [256]: id of each one-byte term
+  amdr_tok::HanRule han;           // the host handle's Han mode; its table pointers are the device copies below
+  int32_t* han_slots = nullptr;
+  int32_t* han_offs = nullptr;
+  unsigned char* han_blob = nullptr;
+  double* han_logw = nullptr;
+  unsigned char* han_word = nullptr;
   int32_t nq_max = 0;
   int64_t bytes_max = -1;          // -1: reserve not called yet
   DevBuf spans, cspans, bsum;      // per-query span slots, compacted spans, block totals
+  DevBuf route_v, route_x;         // dictionary mode: the route, per byte of text (double, int32)
   std::mutex mu;
 };
 
@@ -69,7 +80,9 @@ __device__ inline long long block_scan_incl(long long v, long long* s) {
 __global__ __launch_bounds__(kTokBlock) void tok_count_kernel(const unsigned char* __restrict__ text,
                                                               const int64_t* __restrict__ offs, int nq, int64_t n_bytes,
                                                               uint2* __restrict__ spans, int64_t* __restrict__ q_ptr,
-                                                              int32_t* __restrict__ flags, long long* __restrict__ bsum) {
+                                                              int32_t* __restrict__ flags, long long* __restrict__ bsum,
+                                                              const amdr_tok::HanRule han, double* __restrict__ route_v,
+                                                              int32_t* __restrict__ route_x) {
   __shared__ long long s[kTokBlock];
   __shared__ unsigned char stage[kTokStage];
   const int q = blockIdx.x * kTokBlock + threadIdx.x;
@@ -93,9 +106,9 @@ __global__ __launch_bounds__(kTokBlock) void tok_count_kernel(const unsigned cha
     // (offsets that are not ascending can leave a query outside the staged range: it is read from the blob)
     bool ok;
     if (staged && lo >= blo && hi <= bhi)
-      ok = amdr_tok::tokenize(stage + (lo - blo), (int)(hi - lo), emit);
+      ok = amdr_tok::tokenize(stage + (lo - blo), (int)(hi - lo), han, route_v + lo, route_x + lo, emit);
     else
-      ok = amdr_tok::tokenize(text + lo, (int)(hi - lo), emit);
+      ok = amdr_tok::tokenize(text + lo, (int)(hi - lo), han, route_v + lo, route_x + lo, emit);
     flags[q] = ok ? 0 : 1;
     c = ok ? n_tok : 0;
     q_ptr[q + 1] = c;  // the count; tok_place_kernel turns it into the offset
@@ -202,6 +215,17 @@ int amdr_tokenizer_device_create(const amdr_tokenizer_t* host, int32_t device, a
   if (!rc) rc = upload(&h->offs, host->offs.data(), host->offs.size());
   if (!rc) rc = upload(&h->blob, reinterpret_cast<const unsigned char*>(host->blob.data()), host->blob.size());
   if (!rc) rc = upload(&h->single, host->single, 256);
+  h->han = host->han;
+  if (!rc) rc = upload(&h->han_slots, host->han_slots.data(), host->han_slots.size());
+  if (!rc) rc = upload(&h->han_offs, host->han_offs.data(), host->han_offs.size());
+  if (!rc) rc = upload(&h->han_blob, reinterpret_cast<const unsigned char*>(host->han_blob.data()), host->han_blob.size());
+  if (!rc) rc = upload(&h->han_logw, host->han_logw.data(), host->han_logw.size());
+  if (!rc) rc = upload(&h->han_word, host->han_word.data(), host->han_word.size());
+  h->han.slots = h->han_slots;
+  h->han.offs = h->han_offs;
+  h->han.blob = h->han_blob;
+  h->han.logw = h->han_logw;
+  h->han.is_word = h->han_word;
   if (rc) {
     amdr_tokenizer_device_destroy(h);
     return rc;
@@ -219,6 +243,10 @@ int amdr_tokenizer_device_reserve(amdr_tokenizer_device_t* h, int32_t nq_max, in
   int rc = h->spans.ensure((size_t)(bytes_max + 1) * sizeof(uint2));
   if (!rc) rc = h->cspans.ensure((size_t)(bytes_max + 1) * sizeof(uint2));
   if (!rc) rc = h->bsum.ensure(nb * sizeof(long long));
+  if (h->han.mode == AMDR_HAN_DICT) {
+    if (!rc) rc = h->route_v.ensure((size_t)(bytes_max + 1) * sizeof(double));
+    if (!rc) rc = h->route_x.ensure((size_t)(bytes_max + 1) * sizeof(int32_t));
+  }
   if (rc) return rc;
   if (nq_max > h->nq_max) h->nq_max = nq_max;
   if (bytes_max > h->bytes_max) h->bytes_max = bytes_max;
@@ -251,7 +279,8 @@ int amdr_tokenizer_encode_device(amdr_tokenizer_device_t* h, const char* text_de
   uint2* spans = h->spans.as<uint2>();
   uint2* cspans = h->cspans.as<uint2>();
   long long* bsum = h->bsum.as<long long>();
-  tok_count_kernel<<<nb, kTokBlock, 0, st>>>(text, offs_dev, nq, n_bytes, spans, q_ptr_dev, needs_segmenter_dev, bsum);
+  tok_count_kernel<<<nb, kTokBlock, 0, st>>>(text, offs_dev, nq, n_bytes, spans, q_ptr_dev, needs_segmenter_dev, bsum, h->han,
+                                             h->route_v.as<double>(), h->route_x.as<int32_t>());
   tok_scan_kernel<<<1, kTokBlock, 0, st>>>(bsum, nb);
   tok_place_kernel<<<nb, kTokBlock, 0, st>>>(offs_dev, nq, n_bytes, spans, cspans, q_ptr_dev, bsum);
   // tokens <= n_bytes: a grid for that many lanes, capped (the lanes stride over the rest)
@@ -271,9 +300,16 @@ int amdr_tokenizer_device_destroy(amdr_tokenizer_device_t* h) {
   if (h->offs) (void)hipFree(h->offs);
   if (h->blob) (void)hipFree(h->blob);
   if (h->single) (void)hipFree(h->single);
+  if (h->han_slots) (void)hipFree(h->han_slots);
+  if (h->han_offs) (void)hipFree(h->han_offs);
+  if (h->han_blob) (void)hipFree(h->han_blob);
+  if (h->han_logw) (void)hipFree(h->han_logw);
+  if (h->han_word) (void)hipFree(h->han_word);
   h->spans.release();
   h->cspans.release();
   h->bsum.release();
+  h->route_v.release();
+  h->route_x.release();
   delete h;
   return AMDR_OK;
 }

@@ -10,10 +10,12 @@ expression.
 
 Tokenisation is never silently inexact (text.py): a Han query without a
 segmenter raises `text.ZhTokenizerUnavailable` unless cfg.retrieval.zh_tokenizer
-= "char" opts in (then `zh_exact` is False and the hybrid layer stamps it into
-score_breakdown); `search(..., tokens=)` takes the caller's own tokens; an index
-whose recorded tokenizer is "char" is queried in the same mode so that index and
-query tokens stay consistent."""
+= "char" (or "dict", with zh_dict_file) opts in (then `zh_exact` is False and the
+hybrid layer stamps it into score_breakdown); `search(..., tokens=)` takes the
+caller's own tokens; an index whose recorded tokenizer is "char" or "dict" is
+queried in the same mode so that index and query tokens stay consistent — and,
+when neither jieba nor a registered segmenter exists, its Han queries are cut by
+the native batched tokenisers (host and device) in that mode."""
 from __future__ import annotations
 
 import threading
@@ -27,6 +29,8 @@ from ..schemas import LawChunk
 
 
 logger = logging.getLogger(__name__)
+
+STAND_INS = ("char", "dict")  # recorded tokenizer ids of the declared inexact Han segmenters (text.py)
 
 
 class BM25Retriever:
@@ -63,9 +67,10 @@ class BM25Retriever:
             self.bm25 = bm25
             self.chunks = chunks
             self.index_tokenizer = bm25.__dict__.get("_tokenizer_id")
-            if self.index_tokenizer == "char":
-                logger.warning("[BM25] %s was built with the one-character stand-in tokenizer: results differ "
-                               "from a jieba-built index (zh_exact=False)", self.bm25_path)
+            if self.index_tokenizer in STAND_INS:
+                logger.warning("[BM25] %s was built with the %s stand-in tokenizer: results differ "
+                               "from a jieba-built index (zh_exact=False)", self.bm25_path,
+                               "one-character" if self.index_tokenizer == "char" else "dictionary")
             self._loaded = True
             self._bm25_mtime = current_mtime
 
@@ -75,21 +80,36 @@ class BM25Retriever:
         return self.bm25.gpu(self.device_index, rows=self.shard.bounds(self.bm25.corpus_size) if self.shard else None)
 
     def tokenize_query(self, query: str) -> List[str]:
-        """bm25_retriever.py:73 — jieba.cut, not lower-cased.  Mode "char" when the index was built
+        """bm25_retriever.py:73 — jieba.cut, not lower-cased.  Mode "char" / "dict" when the index was built
         that way or the config opts in; otherwise a Han query without a segmenter raises."""
-        mode = "char" if self.index_tokenizer == "char" else text.cfg_mode(self.cfg)
-        if self.index_tokenizer == "char" and text.contains_han(query):
-            toks = text.jieba_cut_restated(query)  # same stand-in as the index, whatever is installed
+        standin = self.index_tokenizer in STAND_INS
+        mode = self.index_tokenizer if standin else text.cfg_mode(self.cfg)
+        if standin and text.contains_han(query):
+            # same stand-in as the index, whatever is installed
+            toks = text.han_cut(query, mode, self._han_dict() if mode == "dict" else None)
         else:
-            toks = text.jieba_cut(query, mode)
-        self._tls.exact = not (text.contains_han(query) and (self.index_tokenizer == "char" or not text.zh_exact()))
+            toks = text.jieba_cut(query, mode, text.cfg_dict_file(self.cfg))
+        self._tls.exact = not (text.contains_han(query) and (standin or not text.zh_exact()))
         return toks
+
+    def _han_dict(self):
+        """The dictionary of cfg.retrieval.zh_dict_file (ValueError without one)."""
+        return text.han_dict_for(text.cfg_dict_file(self.cfg))
+
+    def han_mode(self):
+        """What the native tokenisers do with a query that holds a Han character (_native.Tokenizer(han=)): "char" or
+        the text.HanDict on an index recorded as built that way, when neither a registered segmenter nor jieba exists —
+        tokenize_query's own result for such a query; "flag" otherwise (the query takes tokenize_query)."""
+        if text._custom_cut is not None or text.HAVE_JIEBA or self.index_tokenizer not in STAND_INS:
+            return "flag"
+        return "char" if self.index_tokenizer == "char" else self._han_dict()
 
     def term_ids_batch(self, questions: Sequence[str]):
         """Tokenise + look up a whole batch: (q_terms i32, q_ptr i64 [n+1], exact bool [n]) — the query CSR of
         amdr_bm25_search.  Text without Han characters goes through the native batched tokeniser (one call, GIL
         released: amdr_tokenizer_encode, token for token what text.jieba_cut returns for it); a query holding Han
-        characters — and every query when jieba or a registered segmenter is present — takes tokenize_query()."""
+        characters takes tokenize_query() — unless han_mode() names a stand-in: the native call then cuts it too and
+        exact is False for exactly those queries — and so does every query when a registered segmenter is present."""
         import numpy as np
         from .. import _native
         self.load()
@@ -111,6 +131,8 @@ class BM25Retriever:
             # text without Han characters is tokenised exactly whatever the index was built with (tokenize_query's rule:
             # only a Han query on a char-built index, or without jieba, is a stand-in result)
             exact = np.ones(n, dtype=bool)
+            if self.han_mode() != "flag":  # a stand-in cut the Han queries natively: those, and only those, are inexact
+                exact = self._not_han(questions, _native.utf8_views(questions)[3])
             if not hard.any():
                 return terms, q_ptr, exact
         else:
@@ -134,44 +156,66 @@ class BM25Retriever:
     def native_tokenizer(self):
         """The batched native tokeniser (_native.Tokenizer) over this index's vocabulary, built once per loaded index."""
         from .. import _native
+        han = self.han_mode()
         tok = self.__dict__.get("_native_tok")
-        if tok is None or tok[0] is not self.bm25:
-            tok = (self.bm25, _native.Tokenizer(list(self.bm25.vocab().keys())))
+        if tok is None or tok[0] is not self.bm25 or tok[2] != han:  # (han: a str, or the cached HanDict itself)
+            tok = (self.bm25, _native.Tokenizer(list(self.bm25.vocab().keys()), han=han), han)
             self.__dict__["_native_tok"] = tok
         return tok[1]
+
+    def han_key(self):
+        """Hashable identity of han_mode() (part of the hybrid stage's compatibility key)."""
+        han = self.han_mode()
+        return han if isinstance(han, str) else ("dict", id(han))
+
+    @staticmethod
+    def _not_han(questions, maybe_han):
+        """bool [n]: True where the query holds no Han character (maybe_han: utf8_views' O(1) pre-test)."""
+        import numpy as np
+        exact = np.ones(len(questions), dtype=bool)
+        idx = np.flatnonzero(maybe_han).tolist()
+        if idx:
+            search = text._RE_HAN_ANY.search  # (contains_han's test)
+            exact[idx] = [search(questions[i] or "") is None for i in idx]
+        return exact
 
     def device_tokenizer(self):
         """The same tokeniser on this retriever's GPU (_native.DeviceTokenizer: a copy of native_tokenizer()'s table)."""
         from .. import _native
         self.load()
         ent = self.__dict__.get("_device_tok")
-        if ent is None or ent[0] is not self.bm25 or ent[1] != self.device_index:
-            ent = (self.bm25, self.device_index, _native.DeviceTokenizer(self.native_tokenizer(), device=self.device_index))
+        host = self.native_tokenizer()
+        if ent is None or ent[0] is not host or ent[1] != self.device_index:
+            ent = (host, self.device_index, _native.DeviceTokenizer(host, device=self.device_index))
             self.__dict__["_device_tok"] = ent
         return ent[2]
 
     def device_text_batch(self, questions: Sequence[str]):
-        """The batch's UTF-8 views (_native.utf8_views: ptrs, lens, total bytes, keepalive) when the device tokeniser
-        decides EVERY query exactly as term_ids_batch would, else None (the caller takes term_ids_batch): no registered
-        segmenter, no Han character (an O(1) test of each string's storage kind first; only strings that could hold one
-        are searched) and, when jieba is importable, none of its ASCII dictionary entries — term_ids_batch's routing.
-        Every query of such a batch is tokenised exactly (zh_exact)."""
+        """The batch's UTF-8 views and exactness (_native.utf8_views: ptrs, lens, total bytes, keepalive; then exact
+        bool [n]) when the device tokeniser decides EVERY query as term_ids_batch would, else None (the caller takes
+        term_ids_batch): no registered segmenter, no Han character (an O(1) test of each string's storage kind first;
+        only strings that could hold one are searched) unless han_mode() names a stand-in the device copy cuts them by
+        and, when jieba is importable, none of its ASCII dictionary entries — term_ids_batch's routing.  exact is False
+        for exactly the queries a stand-in cut (zh_exact)."""
         import numpy as np
         from .. import _native
         if text._custom_cut is not None:
             return None
         ptrs, lens, total, maybe_han, keep = _native.utf8_views(questions)
-        if maybe_han.any() and any(text.contains_han(questions[i] or "") for i in np.flatnonzero(maybe_han)):
-            return None
+        exact = np.ones(len(questions), dtype=bool)
+        if maybe_han.any():
+            exact = self._not_han(questions, maybe_han)
+            if not exact.all() and self.han_mode() == "flag":
+                return None
         if text.HAVE_JIEBA and any(w in "\0".join(q or "" for q in questions) for w in text._ASCII_DICT_WORDS):
             return None
-        return ptrs, lens, total, keep
+        return ptrs, lens, total, keep, exact
 
     @property
     def zh_exact(self) -> bool:
         """False when this thread's last query (or the index itself) went through the
         one-character stand-in instead of jieba."""
-        return self.index_tokenizer != "char" and getattr(self._tls, "exact", True)
+        return self.index_tokenizer not in STAND_INS and getattr(self._tls, "exact", True)
 
     def search(self, query: str, top_k: int, tokens: Optional[Sequence[str]] = None) -> List[Tuple[LawChunk, float]]:
         self.load()

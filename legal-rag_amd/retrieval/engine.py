@@ -229,7 +229,8 @@ class HybridEngine:
         """BM25 query side of a text-in step on the device: (q_terms i32, q_ptr i64 [nq + 1], needs_segmenter i32 [nq])
         from the UTF-8 blob and its offsets (device tensors; nq = offs.numel() - 1, n_bytes = blob.numel()).  q_terms
         is the whole term buffer (sized from the reserve: tokens <= bytes); q_ptr says which part is used.  A query that
-        holds a Han character gets needs_segmenter = 1 and no terms (the caller decides what to do with it)."""
+        holds a Han character gets needs_segmenter = 1 and no terms (the caller decides what to do with it) — unless the
+        tokeniser is a copy of a host tokeniser in a Han mode (_native.Tokenizer(han=)), which cuts it: flag 0, terms."""
         if self.tokenizer is None:
             raise RuntimeError("tokenize_device: this engine has no device tokeniser (HybridEngine(..., tokenizer=))")
         assert blob.is_cuda and blob.element_size() == 1 and offs.is_cuda and offs.dtype == torch.int64

@@ -639,8 +639,9 @@ class HybridRetriever:
         except Exception:  # noqa: BLE001 - the per-channel path raises the reference's own errors
             return None
         store = self.dense.store
+        # (the BM25 retriever's Han mode: an engine's device tokeniser is a copy of the host tokeniser in that mode)
         key = (id(store.index), id(self.bm25.bm25), id(col._searcher) if col is not None else None,
-               id(col._pid2chunk) if col is not None else None)
+               id(col._pid2chunk) if col is not None else None, self.bm25.han_key())
         st = self._stage()
         if st.key != key:
             a, b = store.chunks, self.bm25.chunks
@@ -699,7 +700,7 @@ class HybridRetriever:
                 qt = np.zeros(1, dtype=np.int32)  # pack_queries' convention for "no term at all"
             csr = (qt, qp)
         else:
-            exact = np.ones(len(questions), dtype=bool)  # text without Han characters: tokenised exactly
+            exact = txt[4]  # False where a stand-in cuts a Han query (BM25Retriever.device_text_batch)
         t2 = time.time()
         q_tok = None
         if col is not None:

@@ -12,6 +12,19 @@ and whether the device CSR and the fused ids equal the host path's.  Kernel time
 `rocprofv3 --kernel-trace --stats` with --steps small (a run of its own; tracing slows the host).
 
     python scripts/bench_device_tokenizer.py [--steps 20] [--windows 5] [--repeat 32]
+
+--han MODE ("char" | "dict") measures the Han query side instead: ONE batch of 4 096 Han queries
+(sentences of tests/golden/corpus/law_zh.jsonl) on a BM25 index of that corpus built in MODE, from the list of str to
+the finished CSR in HBM, median over --reps repetitions after --warmup:
+  host_text_to_csr    BM25Retriever.term_ids_batch + ONE pinned H2D copy of the CSR (the native host tokeniser; on a
+                      commit without the Han modes this is the per-query Python route of every Han query)
+  device_text_to_csr  pointer views + amdr_tokenizer_pack + ONE H2D of the text + the device tokeniser (when the
+                      retriever has the Han modes)
+and whether the two CSRs are equal.  "dict" takes the corpus' own 400 most frequent 2-4-character n-grams as dictionary.
+Uses only what a commit before the Han modes also has, so that the same file measures that commit's route: one process per
+commit.
+
+    python scripts/bench_device_tokenizer.py --han char [--reps 20] [--warmup 3] [--queries 4096]
 """
 from __future__ import annotations
 
@@ -27,13 +40,106 @@ ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
 
 
+def han_dictionary_lines(texts, top=400):
+    import re
+    from collections import Counter
+    counts = Counter()
+    for t in texts:
+        for run in re.findall("[\u4E00-\u9FD5]+", t):
+            for n in (2, 3, 4):
+                counts.update(run[i:i + n] for i in range(len(run) - n + 1))
+    return [f"{w} {c}" for w, c in sorted(counts.items(), key=lambda kv: (-kv[1], kv[0]))[:top]]
+
+
+def han(a) -> None:
+    import re
+    import statistics
+    import tempfile
+
+    import torch
+
+    from legal_rag_amd import _native, text
+    from legal_rag_amd.config import AppConfig
+    from legal_rag_amd.retrieval.bm25_retriever import BM25Retriever
+    from legal_rag_amd.retrieval.builders.bm25_builder import build_bm25_index
+    from legal_rag_amd.retrieval.corpus_loader import load_chunks_from_dir
+    from legal_rag_amd.retrieval.engine import HybridEngine
+
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_device_tokenizer: no GPU (this script measures the device path; nothing to fall back to)")
+    if text.zh_exact():
+        raise SystemExit("bench_device_tokenizer --han: jieba or a registered segmenter is present; the stand-ins do not run")
+    chunks = load_chunks_from_dir(str(ROOT / "tests" / "golden" / "corpus"), "law_zh.jsonl")
+    sents = [s for c in chunks for s in re.split("(?<=[。；：])", c.text) if 4 <= len(s) <= 120]
+    rng = np.random.default_rng(0)
+    qs = [sents[int(i)] for i in rng.integers(0, len(sents), size=a.queries)]
+    with tempfile.TemporaryDirectory() as tmp:
+        cfg = AppConfig.for_data_dir(tmp, "zh")
+        cfg.retrieval.zh_tokenizer = a.han
+        if a.han == "dict":
+            cfg.retrieval.zh_dict_file = str(Path(tmp) / "dict.txt")
+            Path(cfg.retrieval.zh_dict_file).write_text("\n".join(han_dictionary_lines([c.text for c in chunks])),
+                                                        encoding="utf-8")
+        build_bm25_index(cfg, chunks)
+        bm = BM25Retriever(cfg)
+        bm.load()
+        native = hasattr(bm, "han_mode")
+        eng = HybridEngine(None, bm.gpu_index(), None, device=0)
+        out = {"workload": f"law_zh Han queries, zh_tokenizer={a.han}: list of str -> CSR in HBM", "queries": len(qs),
+               "blob_bytes": sum(len(q.encode()) for q in qs), "native_han_modes": native}
+        last = {}
+
+        def host_route():
+            qt, qp, exact = bm.term_ids_batch(qs)
+            last["host"] = (qt, qp, exact)
+            last["host_dev"] = eng.upload_csr(qp, qt if qt.size else np.zeros(1, np.int32))
+            torch.cuda.synchronize()
+
+        def device_route():
+            txt = bm.device_text_batch(qs)
+            blob_d, offs_d = eng.upload_text(*txt[:3])
+            last["dev"] = eng.tokenize_device(blob_d, offs_d)
+            torch.cuda.synchronize()
+
+        def median_ms(fn):
+            for _ in range(a.warmup):
+                fn()
+            ts = []
+            for _ in range(a.reps):
+                t0 = time.perf_counter()
+                fn()
+                ts.append((time.perf_counter() - t0) * 1e3)
+            return {"median": statistics.median(ts), "min": min(ts), "max": max(ts), "reps": len(ts)}
+
+        out["host_text_to_csr"] = median_ms(host_route)
+        out["exact_any"] = bool(last["host"][2].any())
+        out["terms"] = int(last["host"][1][-1])
+        if native and bm.han_mode() != "flag":
+            eng.tokenizer = bm.device_tokenizer()
+            out["device_text_to_csr"] = median_ms(device_route)
+            tt, tp, tf = last["dev"]
+            qt, qp, _ = last["host"]
+            out["device_csr_equals_host"] = bool(np.array_equal(tp.cpu().numpy(), qp)
+                                                 and np.array_equal(tt[: len(qt)].cpu().numpy(), qt)
+                                                 and not tf.cpu().numpy().any())
+        out["medians_ms"] = {k: v["median"] for k, v in out.items() if isinstance(v, dict)}
+        print(json.dumps(out, ensure_ascii=False))
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
+    ap.add_argument("--han", choices=("char", "dict"), default=None)
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--queries", type=int, default=4096)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--windows", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=12)
     ap.add_argument("--repeat", type=int, default=32)
     a = ap.parse_args()
+    if a.han:
+        if a.warmup == 12:
+            a.warmup = 3
+        return han(a)
 
     import torch
 
