@@ -83,7 +83,10 @@ def channel_hits(pairs: Sequence[Tuple[str, float]], channel: str) -> List[dict]
 
 
 def fuse(dense: Sequence[Tuple[str, float]], bm25: Sequence[Tuple[str, float]],
-         colbert: Sequence[Tuple[str, float]], knobs: Optional[dict] = None) -> List[dict]:
+         colbert: Sequence[Tuple[str, float]], knobs: Optional[dict] = None, *, keep_order: bool = False) -> List[dict]:
+    """keep_order=True skips the stable re-sort of the channel lists: a list is taken as it stands, so rank is list
+    position and min / max come from min() / max() (what the kernels compute for a list that is not descending).  For a
+    descending list both settings give the same hits."""
     kn = dict(DEFAULTS)
     kn.update(knobs or {})
     method = str(kn["fusion_method"]).lower()
@@ -92,7 +95,8 @@ def fuse(dense: Sequence[Tuple[str, float]], bm25: Sequence[Tuple[str, float]],
     weights = {"dense": float(kn["dense_weight"]), "bm25": float(kn["bm25_weight"]),
                "colbert": float(kn["colbert_weight"])}
 
-    lists = {"dense": _stable_desc(dense), "bm25": _stable_desc(bm25), "colbert": _stable_desc(colbert)}
+    order = list if keep_order else _stable_desc
+    lists = {"dense": order(dense), "bm25": order(bm25), "colbert": order(colbert)}
     rank_lists = {ch: [i for i, _ in lists[ch]] for ch in CHANNELS}
 
     channels_by_id: Dict[str, List[str]] = {}

@@ -969,7 +969,10 @@ def test_dense_search_fuse_equals_the_two_launches(nat, monkeypatch):
     params = nat.make_fuse_params(min_final_score=0.2)
     cases = [(591, 768, 130, 10, 10), (591, 768, 37, 10, 10), (37, 64, 5, 10, 10), (1024, 128, 33, 16, 16), (1, 64, 6, 10, 10),
              (1300, 64, 40, 10, 10), (591, 64, 257, 20, 20), (20000, 64, 9, 10, 10), (200, 64, 3, 10, 10), (640, 320, 96, 1, 31),
-             (591, 128, 64, 10, 0)]
+             (591, 128, 64, 10, 0),
+             # the dense tail's packed fusion with 4 queries per wave (k + kb <= 16), an odd batch and a BM25 list beside it;
+             # the separate-launch side of these is held to the oracle by tests/test_fusion_adversary_gpu.py
+             (37, 64, 7, 8, 8), (200, 64, 5, 4, 3)]
     for n, d, nq, k, kb in cases:
         X, Q = unit_rows(rng, n, d), unit_rows(rng, nq, d)
         if n == 591 and d == 768:  # mass ties: blocks of identical rows -> more than 32 keys at the cut for some queries
