@@ -148,6 +148,21 @@ def _fetch_full(eng, res):  # ONE synchronise and ONE device-to-host copy (the f
     return res.to_host()
 
 
+# The columns of search_batch_arrays: (name, dtype, fill where a question or a hit has no result, shape of one hit's entry
+# | None: one entry per question).  Whatever allocates a column (_column: the graph columns, the scatter of a split batch)
+# reads this table.
+COLUMNS = (
+    ("rows", np.int64, -1, ()), ("scores", np.float64, 0.0, ()), ("count", np.int32, 0, None),
+    ("channel_mask", np.int32, 0, ()), ("zh_exact", np.bool_, True, None), ("values", np.float64, 0.0, (_native.FUSE_NVALS,)),
+    ("graph_rows", np.int64, -1, ()), ("graph_scores", np.float64, 0.0, ()), ("graph_semantic", np.float32, 0.0, ()),
+    ("graph_depth", np.int32, 0, ()), ("graph_relation", np.int32, -1, ()), ("graph_edge_conf", np.float64, 0.0, ()),
+    ("graph_count", np.int32, 0, None))
+
+
+def _column(n: int, top_k: int, dtype, fill, hit) -> np.ndarray:
+    return np.full((n,) if hit is None else (n, top_k) + hit, fill, dtype=dtype)
+
+
 @dataclass
 class HybridRetriever:
     cfg: Any
@@ -195,25 +210,32 @@ class HybridRetriever:
             ws = held[int(device)] = _native.ScopeWorkspace(device=int(device))
         return ws
 
-    @staticmethod
-    def _scope_depth(top_k: int, who: str) -> int:
+    def _search_scoped(self, who: str, chunks, scope: Scope, top_k: int, refusal: Optional[str], device, twin: str, operands):
+        """The common sequence of the per-channel scoped searches: [(chunk, score)] of the channel's top_k among the rows of
+        `chunks` the scope names.  A scope that matches nothing returns [] without a launch, even where the index would be
+        refused; `refusal`: the channel's error text when its index cannot take a scope, else None; `twin`: the channel's
+        host twin (a ScopeWorkspace method), called on a one-scope table with what `operands()` returns: (index, queries)."""
+        rows = resolver_for(chunks).rows(scope)
+        if rows.size == 0:
+            return []
+        if refusal is not None:
+            raise ValueError(refusal)
         if top_k > _native.MAX_K:
             raise ValueError(f"{who}: a scoped search ranks at most {_native.MAX_K} hits per channel, got top_k={top_k}")
-        return top_k
+        scores, ids = getattr(self._scope_workspace(device), twin)(*operands(), [0, rows.size], rows, [0], top_k)
+        return [(chunks[r], float(s)) for r, s in zip(ids[0].tolist(), scores[0].tolist()) if r >= 0 and chunks[r] is not None]
 
     def _search_dense_scoped(self, question: str, top_k: int, scope: Scope) -> List[RetrievalHit]:
         store = self.dense.store
         store.load()
-        rows = resolver_for(store.chunks).rows(scope)
-        if rows.size == 0:
-            return []  # a scope that matches nothing: no launch
         index = getattr(store.index, "native", None)
-        if index is None or getattr(store.index, "spec", None) is not None:
-            raise ValueError("search_dense(scope=): needs this package's own, unsharded dense index")
-        scores, ids = self._scope_workspace(index.device).dense_search(
-            index, store._embed([question], is_query=True), [0, rows.size], rows, [0], self._scope_depth(top_k, "search_dense"))
-        return [RetrievalHit(chunk=store.chunks[r], score=float(s), rank=j, source="retriever", semantic_score=float(s))
-                for j, (r, s) in enumerate(zip(ids[0].tolist(), scores[0].tolist()), start=1) if r >= 0]
+        pairs = self._search_scoped(
+            "search_dense", store.chunks, scope, top_k,
+            "search_dense(scope=): needs this package's own, unsharded dense index"
+            if index is None or getattr(store.index, "spec", None) is not None else None,
+            getattr(index, "device", 0), "dense_search", lambda: (index, store._embed([question], is_query=True)))
+        return [RetrievalHit(chunk=c, score=s, rank=j, source="retriever", semantic_score=s)
+                for j, (c, s) in enumerate(pairs, start=1)]
 
     def search_dense(self, question: str, top_k: int = 10, *, scope: Optional[Scope] = None) -> List[RetrievalHit]:
         """`scope`: rank only that part of the corpus (retrieval/scope.py); None: the whole corpus."""
@@ -229,20 +251,18 @@ class HybridRetriever:
     def _search_bm25_scoped(self, question: str, top_k: int, tokens: Optional[Sequence[str]], scope: Scope):
         bm = self.bm25
         bm.load()
-        rows = resolver_for(bm.chunks).rows(scope)
-        if rows.size == 0:
-            return []
-        if getattr(bm, "shard", None) is not None:
-            raise ValueError("search_bm25(scope=): scoped search does not run on a row-sharded index")
-        if tokens is not None:
-            tokens = list(tokens)
-            bm._tls.exact = True
-        else:
-            tokens = bm.tokenize_query(question)
-        index = bm.gpu_index()
-        scores, ids = self._scope_workspace(bm.device_index).bm25_search(
-            index, [bm.bm25.term_ids(tokens)], [0, rows.size], rows, [0], self._scope_depth(top_k, "search_bm25"))
-        return [(bm.chunks[r], float(s)) for r, s in zip(ids[0].tolist(), scores[0].tolist()) if r >= 0]
+
+        def operands():
+            if tokens is not None:
+                terms = list(tokens)
+                bm._tls.exact = True
+            else:
+                terms = bm.tokenize_query(question)
+            return bm.gpu_index(), [bm.bm25.term_ids(terms)]
+        return self._search_scoped(
+            "search_bm25", bm.chunks, scope, top_k,
+            "search_bm25(scope=): scoped search does not run on a row-sharded index" if getattr(bm, "shard", None) is not None
+            else None, bm.device_index, "bm25_search", operands)
 
     def search_bm25(self, question: str, top_k: int = 10, tokens: Optional[Sequence[str]] = None, *,
                     scope: Optional[Scope] = None) -> List[RetrievalHit]:
@@ -277,16 +297,11 @@ class HybridRetriever:
         if held is None or held[0] is not col._pid2chunk:  # the ColBERT row space as a list: pid -> chunk (None: no such pid)
             held = self.__dict__["_colbert_chunks"] = (col._pid2chunk,
                                                        [col._pid2chunk.get(i) for i in range(max(col._pid2chunk) + 1)])
-        chunks = held[1]
-        rows = resolver_for(chunks).rows(scope)
-        if rows.size == 0:
-            return []
-        if getattr(col, "shard", None) is not None:
-            raise ValueError("search_colbert(scope=): scoped search does not run on a row-sharded index")
-        q_tokens = np.asarray(col._encoder.encode_query(question), dtype=np.float32)[None]
-        scores, ids = self._scope_workspace(col.device_index).maxsim_search(
-            col._searcher, q_tokens, [0, rows.size], rows, [0], self._scope_depth(top_k, "search_colbert"))
-        return [(chunks[r], float(s)) for r, s in zip(ids[0].tolist(), scores[0].tolist()) if r >= 0 and chunks[r] is not None]
+        return self._search_scoped(
+            "search_colbert", held[1], scope, top_k,
+            "search_colbert(scope=): scoped search does not run on a row-sharded index" if getattr(col, "shard", None) is not None
+            else None, col.device_index, "maxsim_search",
+            lambda: (col._searcher, np.asarray(col._encoder.encode_query(question), dtype=np.float32)[None]))
 
     def search_colbert(self, question: str, top_k: int = 10, *, scope: Optional[Scope] = None) -> List[RetrievalHit]:
         top_k = max(1, int(top_k))
@@ -456,7 +471,8 @@ class HybridRetriever:
             # stream, ONE synchronise, one set of copies back (the kernels and results are those of the
             # per-channel path below; tests pin the two against each other)
             t0 = time.time()
-            outs, (t1, t2, t3), _ = self._hit_lists([question], eff_top_k, native, min_final)
+            parts, _ = self._partition([question], None, None, native[0].chunks, native[2] is not None, "search")
+            outs, (t1, t2, t3), _ = self._hit_lists([question], parts, eff_top_k, native, min_final)
             fused = outs[0]
             t4 = time.time()
         else:
@@ -798,94 +814,89 @@ class HybridRetriever:
         rows, scores, cmask, cnt = host
         return {"rows": rows, "scores": scores, "count": cnt, "channel_mask": cmask, "zh_exact": exact, "chunks": chunks}
 
-    def _hit_lists(self, questions: Sequence[str], eff: int, native, min_final: float, q_emb=None,
-                   device_tok: bool = False, after=None, scopes: Optional[Sequence[Scope]] = None):
-        """prepare -> run -> hit lists: ([fused hits with score >= min_final per question], (t_after_dense_prep,
-        t_after_bm25_prep, t_after_colbert_prep), what `after` returned).  An empty question switches the ColBERT
-        channel off for that question (colbert_retriever.py:147-149): the blank questions go as one batch without the
-        channel, the rest as another.  scopes (one Scope per question, none of them None): the scoped step."""
-        store, bm, col = native
-        kn = self._knobs()
-        params = self._params(kn, min_final)
-
-        def batch(qs, nat, emb, after, sc=None):
-            prep = self._prepare(qs, nat, emb, device_tok)
-            table = resolver_for(store.chunks).table(sc) if sc is not None else None
-            host, extra = self._run(prep, params, eff, _fetch_full, after, table)
-            return self._decode_hits(host, prep.exact, kn, store.chunks), prep.stamps, extra
-        blank = [i for i, q in enumerate(questions) if not (q or "").strip()] if col is not None else []
-        if not blank:
-            return batch(questions, native, q_emb, after, scopes)
-        if after is not None:
-            raise ValueError("graph_channel='device': empty questions are not supported with the ColBERT channel on")
-        rest = [i for i in range(len(questions)) if i not in set(blank)]
-        out, stamps = [None] * len(questions), (time.time(),) * 3
-        for idxs, nat in ((blank, (store, bm, None)), (rest, native)):
-            if idxs:
-                part, stamps, _ = batch([questions[i] for i in idxs], nat, None if q_emb is None else q_emb[idxs], None,
-                                        None if scopes is None else [scopes[i] for i in idxs])
-                for i, h in zip(idxs, part):
-                    out[i] = h
-        return out, stamps, None
-
-    def _graph_selection(self, decisions, n: int, top_k: int, who: str):
-        """(sel, seed_n): the questions whose decision asks for the graph channel (none unless cfg.retrieval.enable_graph)
-        and how many fused hits seed the walk."""
-        if decisions is not None and len(decisions) != n:
-            raise ValueError(f"{who}: decisions must have one entry per question")
-        rcfg = self.cfg.retrieval
-        on = decisions is not None and getattr(rcfg, "enable_graph", False)
-        sel = [i for i, dec in enumerate(decisions) if _is_graph_mode(getattr(dec, "mode", None))] if on else []
-        return sel, int(getattr(rcfg, "graph_seed_k", max(10, top_k * 3)))
-
     # ----------------------------------------------------------- batch form
-    def _split_scopes(self, n: int, scopes, decisions, chunks, who: str):
-        """(plain, scoped, empty): the questions without a scope, with one that names rows of `chunks`, with one that
-        matches nothing.  A graph-mode decision together with a scope raises: the graph channel follows cross-references
-        out of any scope by design."""
-        if len(scopes) != n:
+    @staticmethod
+    def _partition(questions: Sequence[str], scopes, decisions, chunks, colbert: bool, who: str):
+        """(parts, empty) of a batch; needs neither device nor torch.  A part is (indices, scoped, ColBERT on): questions
+        that share one engine run.  The order is fixed — plain-blank, plain, scoped-blank, scoped — and a part without an
+        index is left out.  A blank question switches the ColBERT channel off for itself (colbert_retriever.py:147-149), so
+        with the channel on (`colbert`) the blank ones run apart, without it; with the channel off nothing is split.
+        `empty`: the questions whose scope names no row of `chunks` (no launch is made for them).  A graph-mode decision
+        together with a scope raises: the graph channel follows cross-references out of any scope by design."""
+        n = len(questions)
+        if scopes is not None and len(scopes) != n:
             raise ValueError(f"{who}: scopes must have one entry per question")
         if decisions is not None and len(decisions) != n:
             raise ValueError(f"{who}: decisions must have one entry per question")
-        res = resolver_for(chunks)
-        plain, scoped, empty = [], [], []
-        for i, s in enumerate(scopes):
+        plain, scoped, empty = range(n), [], []
+        for i, s in enumerate(scopes if scopes is not None else ()):
             if s is None:
-                plain.append(i)
                 continue
             if not isinstance(s, Scope):
                 raise TypeError(f"{who}: scopes[{i}] is not a Scope")
             if decisions is not None and _is_graph_mode(getattr(decisions[i], "mode", None)):
                 raise ValueError(f"{who}: question {i} has a graph-mode decision and a scope; the graph channel follows "
                                  f"cross-references out of any scope")
-            (scoped if res.rows(s).size else empty).append(i)
-        return plain, scoped, empty
+            (scoped if resolver_for(chunks).rows(s).size else empty).append(i)
+        if scoped or empty:
+            out = set(scoped).union(empty)
+            plain = [i for i in plain if i not in out]
+        parts = []
+        for idxs, sc in ((plain, False), (scoped, True)):
+            blank = [i for i in idxs if not (questions[i] or "").strip()] if colbert else []
+            if blank:
+                parts.append((blank, sc, False))
+                drop = set(blank)
+                idxs = [i for i in idxs if i not in drop]
+            parts.append((idxs, sc, colbert))
+        return [p for p in parts if len(p[0])], empty
 
-    def _search_batch_scoped(self, questions: List[str], top_k: int, llm: Any, decisions, q_emb, scopes):
-        rcfg = self.cfg.retrieval
-        eff = self._eff_depth(top_k, "search_batch")
-        native = self._native_channels(eff)
-        if native is None:
-            raise RuntimeError("search_batch requires this package's own dense / BM25 (/ ColBERT) retrievers built "
-                               "over the same chunk list")
-        plain, scoped, empty = self._split_scopes(len(questions), scopes, decisions, native[0].chunks, "search_batch")
-        outs: List[Any] = [[] for _ in questions]  # a scope that matches nothing: [] without a launch
-        if plain:  # the unscoped step, as a sub-batch
-            sub = self.search_batch([questions[i] for i in plain], top_k, llm,
-                                    None if decisions is None else [decisions[i] for i in plain],
-                                    None if q_emb is None else q_emb[plain])
-            for i, hits in zip(plain, sub):
+    def _split_scopes(self, n: int, scopes, decisions, chunks, who: str):
+        """(plain, scoped, empty) of _partition with the ColBERT channel left aside."""
+        parts, empty = self._partition([None] * n, scopes, decisions, chunks, False, who)
+        by = {sc: list(idxs) for idxs, sc, _ in parts}
+        return by.get(False, []), by.get(True, []), empty
+
+    def _run_part(self, part, questions, scopes, q_emb, native, device_tok: bool, params, eff: int, fetch, decode, graph=None):
+        """One part of a batch in one engine run: _prepare -> the scope table of a scoped part -> _run -> `decode(host
+        arrays, exact)`; `graph` (what _graph_device_stage returned) rides the part it names.  Returns (what decode
+        returned, the _Prepared's time stamps, what the graph stage returned).  A part that is the whole batch takes the
+        caller's questions and q_emb as they are."""
+        idxs, scoped, with_col = part
+        store, bm, col = native
+        after = graph[2] if graph is not None and part is graph[0] else None
+        if len(idxs) < len(questions):
+            questions = [questions[i] for i in idxs]
+            q_emb = None if q_emb is None else q_emb[idxs]
+        prep = self._prepare(questions, (store, bm, col if with_col else None), q_emb, device_tok)
+        table = resolver_for(store.chunks).table([scopes[i] for i in idxs]) if scoped else None
+        host, extra = self._run(prep, params, eff, fetch, after, table)
+        return decode(host, prep.exact), prep.stamps, extra
+
+    def _hit_lists(self, questions: Sequence[str], parts, eff: int, native, min_final: float, q_emb=None,
+                   device_tok: bool = False, scopes=None, graph=None):
+        """The parts of a batch as hit lists: ([fused hits with score >= min_final per question; [] for a question no part
+        holds: its scope matches nothing], (t_after_dense_prep, t_after_bm25_prep, t_after_colbert_prep) of the last part,
+        what the graph stage `graph` (_graph_device_stage) returned)."""
+        kn = self._knobs()
+        params = self._params(kn, min_final)
+        chunks = native[0].chunks
+        outs, stamps, gout = [[] for _ in questions], (time.time(),) * 3, None
+        for part in parts:
+            lists, stamps, g = self._run_part(part, questions, scopes, q_emb, native, device_tok, params, eff, _fetch_full,
+                                              lambda host, exact: self._decode_hits(host, exact, kn, chunks), graph)
+            gout = gout if g is None else g
+            for i, hits in zip(part[0], lists):
                 outs[i] = hits
-        if scoped:
-            qs = [questions[i] for i in scoped]
-            lists, _, _ = self._hit_lists(qs, eff, native, float(getattr(rcfg, "min_final_score", 0.0)),
-                                          None if q_emb is None else q_emb[scoped],
-                                          query_tokenizer_mode(self.cfg) == "device", None, [scopes[i] for i in scoped])
-            if getattr(rcfg, "enable_rerank", False):
-                lists = self._rerank_stage(qs, lists, llm, top_k)
-            for i, hits in zip(scoped, lists):
-                outs[i] = _dedup_keep_best(hits)[:top_k]
-        return outs
+        return outs, stamps, gout
+
+    def _graph_selection(self, decisions, top_k: int):
+        """(sel, seed_n): the questions whose decision asks for the graph channel (none unless cfg.retrieval.enable_graph)
+        and how many fused hits seed the walk."""
+        rcfg = self.cfg.retrieval
+        on = decisions is not None and getattr(rcfg, "enable_graph", False)
+        sel = [i for i, dec in enumerate(decisions) if _is_graph_mode(getattr(dec, "mode", None))] if on else []
+        return sel, int(getattr(rcfg, "graph_seed_k", max(10, top_k * 3)))
 
     def search_batch(self, questions: Sequence[str], top_k: int = 10, llm: Any = None,
                      decisions: Optional[Sequence[Any]] = None, q_emb=None, *,
@@ -895,50 +906,56 @@ class HybridRetriever:
         -> filter), the graph stage per query whose `decisions[i]` asks for it, the rerank stage with the
         cross-encoder fed in full batches over all queries' candidates and ONE blend launch, dedup, cut.
         `scopes` (one Scope or None per question, retrieval/scope.py): a scoped question's channels rank only its part of
-        the corpus and its fusion normalises over those lists; the questions with None run as a sub-batch through the
-        unscoped step; a scope that matches nothing yields [].  A graph-mode decision with a scope raises ValueError."""
+        the corpus and its fusion normalises over those lists; the questions with None run as one part through the
+        unscoped step, the scoped ones as another; a scope that matches nothing yields [].  A graph-mode decision with a
+        scope raises ValueError."""
         rcfg = self.cfg.retrieval
         top_k = max(1, int(top_k))
         questions = list(questions)
-        if scopes is not None and any(s is not None for s in scopes):
-            return self._search_batch_scoped(questions, top_k, llm, decisions, q_emb, list(scopes))
-        sel, seed_n = self._graph_selection(decisions, len(questions), top_k, "search_batch")
         eff = self._eff_depth(top_k, "search_batch")
         native = self._native_channels(eff)
         if native is None:
             raise RuntimeError("search_batch requires this package's own dense / BM25 (/ ColBERT) retrievers built "
                                "over the same chunk list")
+        parts, _ = self._partition(questions, scopes, decisions, native[0].chunks, native[2] is not None, "search_batch")
+        sel, seed_n = self._graph_selection(decisions, top_k)
         # The graph walks at the per-channel depth `eff`.  With the device channel off or no graph loaded the stage
         # falls back to the host search_graph per query (which, without a graph, still cuts the list to the seeds).
-        after = gp = None
+        graph = None
         if sel and self.graph is not None and graph_channel_mode(self.cfg) == "device":
-            after, gp = self._graph_device_stage(questions, sel, eff, seed_n, native)
-        outs, _, gout = self._hit_lists(questions, eff, native, float(getattr(rcfg, "min_final_score", 0.0)), q_emb,
-                                        query_tokenizer_mode(self.cfg) == "device", after)
+            graph = self._graph_device_stage(parts, questions, sel, eff, seed_n, native)
+        outs, _, gout = self._hit_lists(questions, parts, eff, native, float(getattr(rcfg, "min_final_score", 0.0)), q_emb,
+                                        query_tokenizer_mode(self.cfg) == "device", scopes, graph)
         for j, i in enumerate(sel):
             seeds = outs[i][:seed_n]
-            if after is not None:
+            if graph is not None:
                 # one device call served every graph-mode query; the same relabelling as search_graph
-                hits = self.graph.hits_from_device(gout, j, gp)
+                hits = self.graph.hits_from_device(gout, j, graph[3])
                 for h in hits:
                     h.source = "retriever"
                     h.score_breakdown["channel"] = ["graph"]
             else:
                 hits = self.search_graph(questions[i], eff, decision=decisions[i], seeds=seeds)
             outs[i] = seeds + hits
+        # rerank, dedup and cut run once, over the whole batch (a question whose scope matches nothing has no candidate)
         if getattr(rcfg, "enable_rerank", False):
             outs = self._rerank_stage(questions, outs, llm, top_k)
         return [_dedup_keep_best(hits)[:top_k] for hits in outs]
 
-    def _graph_device_stage(self, questions: Sequence[str], sel: Sequence[int], k: int, seed_n: int, native,
+    def _graph_device_stage(self, parts, questions: Sequence[str], sel: Sequence[int], k: int, seed_n: int, native,
                             lang: Optional[str] = None):
-        """The graph channel of a batch on the device (graph_channel = "device"): the graph-mode questions embedded once
-        (non-query form, as GraphRetriever's store._embed(question)), then ONE amdr_graph_search_device call over the
-        fused lists of the batch, seeds = the first graph_seed_k fused hits.  Returns (after, params): `after(engine,
-        BatchResult)` is the stage for _run (its outputs as host arrays), params what hits_from_device takes.
-        Row-sharded indexes and parameters outside the kernel's limits raise ValueError (no silent host path)."""
+        """The graph channel of a batch on the device (graph_channel = "device"): the graph-mode questions `sel` embedded
+        once (non-query form, as GraphRetriever's store._embed(question)), then ONE amdr_graph_search_device call over the
+        fused lists of their part, seeds = the first graph_seed_k fused hits.  _partition has refused graph mode with a
+        scope, so `sel` lies in the plain questions; they must share one engine run.  Returns (that part, sel as indices
+        inside it, after, params): `after(engine, BatchResult)` is the stage for _run (its outputs as host arrays, one row
+        per question of sel), params what hits_from_device takes.  Row-sharded indexes and parameters outside the kernel's
+        limits raise ValueError (no silent host path)."""
         import torch
         store = native[0]
+        plain = [p for p in parts if not p[1]]
+        if len(plain) != 1 or plain[0][2] != (native[2] is not None):
+            raise ValueError("graph_channel='device': empty questions are not supported with the ColBERT channel on")
         if getattr(store.index, "spec", None) is not None:
             raise ValueError("graph_channel='device' does not run on a row-sharded index (cfg.retrieval.shard); "
                              "use graph_channel='host'")
@@ -946,8 +963,9 @@ class HybridRetriever:
         params, lang_id = self.graph.device_params(k, lang)
         if k > _native.MAX_K:
             raise ValueError(f"graph_channel='device': depth {k} exceeds {_native.MAX_K}")
-        sel = list(sel)
         emb = store.embed_device([questions[i] for i in sel], is_query=False)
+        at = {i: j for j, i in enumerate(plain[0][0])} if len(plain[0][0]) < len(questions) else None
+        sel = list(sel) if at is None else [at[i] for i in sel]
 
         def after(eng, res):
             eng.set_graph(g, params, lang_id)
@@ -958,51 +976,39 @@ class HybridRetriever:
             eng.graph.reserve(len(sel), k, eng.graph_limit)
             outs = eng.graph_topk(res.ids, res.count, q_full, k, seed_n, qsel=qsel)
             return {n: v.cpu().numpy() for n, v in outs.items()}
-        return after, params
+        return plain[0], sel, after, params
 
-    def _arrays_scoped(self, questions: List[str], top_k: int, q_emb, values: bool, decisions, scopes) -> Dict[str, Any]:
-        """search_batch_arrays with scopes: the unscoped questions as one sub-batch, the scoped ones as another (the
-        scoped step), the columns re-interleaved on the host; a scope that matches nothing: count 0."""
-        rcfg = self.cfg.retrieval
-        eff = self._eff_depth(top_k, "search_batch_arrays")
-        native = self._native_channels(eff)
-        if native is None:
-            raise RuntimeError("search_batch_arrays requires this package's own retrievers built over the same chunk list")
-        n = len(questions)
-        plain, scoped, _ = self._split_scopes(n, scopes, decisions, native[0].chunks, "search_batch_arrays")
-        parts = []
-        if plain:
-            parts.append((plain, self.search_batch_arrays([questions[i] for i in plain], top_k,
-                                                          None if q_emb is None else q_emb[plain], values,
-                                                          None if decisions is None else [decisions[i] for i in plain])))
-        if scoped:
-            qs = [questions[i] for i in scoped]
-            if native[2] is not None and any(not (q or "").strip() for q in qs):
-                raise ValueError("search_batch_arrays: empty questions are not supported in the columnar form")
-            prep = self._prepare(qs, native, None if q_emb is None else q_emb[scoped], query_tokenizer_mode(self.cfg) == "device")
-            params = self._params(self._knobs(), float(getattr(rcfg, "min_final_score", 0.0)))
-            table = resolver_for(native[0].chunks).table([scopes[i] for i in scoped])
-            if values:
-                host, _ = self._run(prep, params, eff, _fetch_full, None, table)
-                parts.append((scoped, self._decode_columns(host, prep.exact, top_k, native[0].chunks)))
-            else:
-                host, _ = self._run(prep, params, eff, lambda eng, res: eng.compact_to_host(res, top_k), None, table)
-                parts.append((scoped, self._decode_lean(host, prep.exact, native[0].chunks)))
-        out: Dict[str, Any] = {"rows": np.full((n, top_k), -1, dtype=np.int64), "scores": np.zeros((n, top_k)),
-                               "count": np.zeros(n, dtype=np.int32), "channel_mask": np.zeros((n, top_k), dtype=np.int32),
-                               "zh_exact": np.ones(n, dtype=bool), "chunks": native[0].chunks}
+    def _graph_columns(self, cols: Dict[str, Any], g, sel: Sequence[int], top_k: int) -> None:
+        """The graph_* columns of a part's columnar dict: what the device stage returned (`g`, one row per question of
+        `sel`; None: no graph-mode question) at the rows `sel`, the schema's fill everywhere else."""
+        n = len(cols["count"])
+        for name, dt, fill, hit in COLUMNS:
+            if name.startswith("graph_"):
+                cols[name] = _column(n, top_k, dt, fill, hit)
+                if g is not None:
+                    cols[name][sel] = g["final" if name == "graph_scores" else name[len("graph_"):]]
+        cols["graph_relation_names"] = list(self.graph.device_graph()[1].rel_names)
+
+    @staticmethod
+    def _scatter_columns(n: int, top_k: int, values: bool, chunks, parts) -> Dict[str, Any]:
+        """The columnar dict of n questions from the decoded parts [(indices, columnar dict)].  A part's rows land at its
+        indices; a question no part holds (its scope matches nothing) and a column a part does not carry (graph_* beside
+        a scoped part) keep the schema's fill.  What is no column (value_names, chunks, graph_relation_names) passes
+        through.  ONE part holding every question is returned as it is."""
+        if len(parts) == 1 and len(parts[0][0]) == n:
+            return parts[0][1]
+        out: Dict[str, Any] = {"chunks": chunks}
         if values:
-            out["values"], out["value_names"] = np.zeros((n, top_k, _native.FUSE_NVALS)), dict(_native.FV)
-        for idxs, part in parts:
-            for key, val in part.items():
-                if not (isinstance(val, np.ndarray) and val.shape[:1] == (len(idxs),)):
-                    out.setdefault(key, val)  # value_names, chunks, graph_relation_names
-                    continue
-                if key not in out or out[key].shape[1:] != val.shape[1:] or out[key].dtype != val.dtype:
-                    # (a graph_* column of the unscoped part, or a width below top_k: the same for every part)
-                    fill = -1 if key in ("rows", "graph_rows", "graph_relation") else 0
-                    out[key] = np.full((n,) + val.shape[1:], fill, dtype=val.dtype)
-                out[key][idxs] = val
+            out["value_names"] = dict(_native.FV)
+        for name, dt, fill, hit in COLUMNS:
+            if any(name in cols for _, cols in parts) or not (name.startswith("graph_") or (name == "values" and not values)):
+                out[name] = _column(n, top_k, dt, fill, hit)
+                for idxs, cols in parts:
+                    if name in cols:
+                        out[name][idxs] = cols[name]
+        for _, cols in parts:
+            for key, val in cols.items():
+                out.setdefault(key, val)
         return out
 
     def search_batch_arrays(self, questions: Sequence[str], top_k: int = 10, q_emb=None, values: bool = True,
@@ -1019,41 +1025,33 @@ class HybridRetriever:
         cfg.retrieval.enable_graph and a graph is loaded) and the result gains graph_rows / graph_scores (final) /
         graph_semantic / graph_depth / graph_relation (index into graph_relation_names) / graph_edge_conf [n, top_k] and
         graph_count [n] (0 for the other queries).
-        `scopes`: as search_batch — one Scope or None per question; a scope that matches nothing gives count 0."""
+        `scopes`: as search_batch — one Scope or None per question; a scope that matches nothing gives count 0.
+        COLUMNS holds every column's dtype and the fill of a question or hit without a result."""
         rcfg = self.cfg.retrieval
         top_k = max(1, int(top_k))
-        if scopes is not None and any(s is not None for s in scopes):
-            return self._arrays_scoped(list(questions), top_k, q_emb, values, decisions, list(scopes))
         eff = self._eff_depth(top_k, "search_batch_arrays")
         native = self._native_channels(eff)
         if native is None:
             raise RuntimeError("search_batch_arrays requires this package's own retrievers built over the same chunk list")
-        questions = list(questions)
-        sel, seed_n = self._graph_selection(decisions, len(questions), top_k, "search_batch_arrays")
+        questions, chunks = list(questions), native[0].chunks
+        parts, _ = self._partition(questions, scopes, decisions, chunks, native[2] is not None, "search_batch_arrays")
+        if native[2] is not None and not all(with_col for _, _, with_col in parts):
+            raise ValueError("search_batch_arrays: empty questions are not supported in the columnar form")
+        sel, seed_n = self._graph_selection(decisions, top_k)
         # The graph walks at depth `top_k`, always on the device; with no graph loaded `decisions` are ignored.
         graph_on = decisions is not None and getattr(rcfg, "enable_graph", False) and self.graph is not None
-        after = self._graph_device_stage(questions, sel, top_k, seed_n, native)[0] if graph_on and sel else None
-        if native[2] is not None and any(not (q or "").strip() for q in questions):
-            raise ValueError("search_batch_arrays: empty questions are not supported in the columnar form")
-        prep = self._prepare(questions, native, q_emb, query_tokenizer_mode(self.cfg) == "device")
+        graph = self._graph_device_stage(parts, questions, sel, top_k, seed_n, native) if graph_on and sel else None
         params = self._params(self._knobs(), float(getattr(rcfg, "min_final_score", 0.0)))
         if values:
-            host, g = self._run(prep, params, eff, _fetch_full, after)
-            out = self._decode_columns(host, prep.exact, top_k, native[0].chunks)
+            fetch, decode = _fetch_full, lambda host, exact: self._decode_columns(host, exact, top_k, chunks)
         else:
-            host, g = self._run(prep, params, eff, lambda eng, res: eng.compact_to_host(res, top_k), after)
-            out = self._decode_lean(host, prep.exact, native[0].chunks)
-        if graph_on:
-            n = len(questions)
-            for col, name, dt, fill in (("rows", "rows", np.int64, -1), ("scores", "final", np.float64, 0.0),
-                                        ("semantic", "semantic", np.float32, 0.0), ("depth", "depth", np.int32, 0),
-                                        ("relation", "relation", np.int32, -1), ("edge_conf", "edge_conf", np.float64, 0.0)):
-                a = np.full((n, top_k), fill, dtype=dt)
-                if g is not None:
-                    a[sel] = g[name]
-                out["graph_" + col] = a
-            out["graph_count"] = np.zeros(n, dtype=np.int32)
-            if g is not None:
-                out["graph_count"][sel] = g["count"]
-            out["graph_relation_names"] = list(self.graph.device_graph()[1].rel_names)
-        return out
+            fetch, decode = (lambda eng, res: eng.compact_to_host(res, top_k),
+                             lambda host, exact: self._decode_lean(host, exact, chunks))
+        done = []
+        for part in parts:
+            cols, _, g = self._run_part(part, questions, scopes, q_emb, native, query_tokenizer_mode(self.cfg) == "device",
+                                        params, eff, fetch, decode, graph)
+            if graph_on and not part[1]:
+                self._graph_columns(cols, g, graph[1] if graph is not None else [], top_k)
+            done.append((part[0], cols))
+        return self._scatter_columns(len(questions), top_k, values, chunks, done)

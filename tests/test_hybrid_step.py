@@ -1,9 +1,11 @@
 """The host side of one hybrid step, without a GPU: the engine's route (engine.step_form), the ONE layout of the packed
-fused record (engine.packed_layout / packed_views, both record forms) and the two columnar decoders of
-HybridRetriever.search_batch_arrays."""
+fused record (engine.packed_layout / packed_views, both record forms), the two columnar decoders of
+HybridRetriever.search_batch_arrays, and the two ends of a split batch: its partition and the scatter of its columns."""
 import itertools
+from types import SimpleNamespace
 
 import numpy as np
+import pytest
 import torch
 
 from legal_rag_amd import _native
@@ -90,3 +92,84 @@ def test_lean_columns_equal_the_first_top_k_of_the_full_columns():
         assert lean["zh_exact"] is exact and full["zh_exact"] is exact and lean["chunks"] is chunks
         assert full["values"].shape == (nq, w, _native.FUSE_NVALS) and full["value_names"] == _native.FV
         assert (full["values"] == vals[:, :w]).all()
+
+
+# ---- a split batch: the partition and the scatter ------------------------------------------------------------------------
+def listed(parts):
+    return [(list(idxs), scoped, colbert) for idxs, scoped, colbert in parts]
+
+
+def test_partition_has_a_fixed_order_and_places_every_question_once():
+    from legal_rag_amd.retrieval.scope import Scope
+    chunks = [SimpleNamespace(id=f"c{i}", section="A" if i < 3 else "B") for i in range(5)]
+    a, b, miss = Scope(section="A"), Scope(section="B"), Scope(section="no such section")
+    # {no scope, a scope with rows, a scope that matches nothing} x {blank, not blank}, two of the six twice
+    scopes = [b, None, miss, None, b, miss, None, a]
+    qs = ["q0", "  ", "q2", "q3", "", None, "q6", "q7"]
+    part = HybridRetriever._partition
+    for colbert, exp in ((True, [([1], False, False), ([3, 6], False, True), ([4], True, False), ([0, 7], True, True)]),
+                         (False, [([1, 3, 6], False, False), ([0, 4, 7], True, False)])):  # channel off: no blank split
+        parts, empty = part(qs, scopes, None, chunks, colbert, "search_batch")
+        assert listed(parts) == exp and empty == [2, 5]
+        assert sorted(i for idxs, _, _ in parts for i in idxs) + empty == [0, 1, 3, 4, 6, 7, 2, 5]  # each index once
+        # decisions that ask for no graph change nothing
+        assert listed(part(qs, scopes, [SimpleNamespace(mode="RAG")] * 8, chunks, colbert, "search_batch")[0]) == exp
+    # no scope and no blank question: ONE part, the whole batch, with and without the list of Nones
+    for sc in (None, [None] * 3):
+        for colbert in (False, True):
+            assert listed(part(["x", "y", "z"], sc, None, chunks, colbert, "search")[0]) == [([0, 1, 2], False, colbert)]
+    assert listed(part(["x", " "], None, None, chunks, False, "search")[0]) == [([0, 1], False, False)]
+    assert part(["x"], [miss], None, chunks, True, "search") == ([], [0])  # parts without an index are left out
+    graph = SimpleNamespace(mode="GRAPH_AUGMENTED")
+    assert listed(part(["x", "y"], [None, a], [graph, None], chunks, False, "search_batch")[0]) == \
+        [([0], False, False), ([1], True, False)]
+    with pytest.raises(ValueError, match="search_batch: scopes must have one entry per question"):
+        part(["x", "y"], [None], None, chunks, False, "search_batch")
+    with pytest.raises(ValueError, match="search_batch_arrays: decisions must have one entry per question"):
+        part(["x", "y"], None, [None], chunks, False, "search_batch_arrays")
+    with pytest.raises(TypeError, match=r"scopes\[1\] is not a Scope"):
+        part(["x", "y"], [None, "A"], None, chunks, False, "search_batch")
+    with pytest.raises(ValueError, match="question 1 has a graph-mode decision and a scope.*graph"):
+        part(["x", "y"], [None, miss], [None, graph], chunks, False, "search_batch")
+
+
+@pytest.mark.parametrize("graph", [False, True], ids=["no-graph-columns", "graph-columns"])
+@pytest.mark.parametrize("values", [True, False], ids=["full", "lean"])
+@pytest.mark.parametrize("top_k", [1, 10])
+def test_scatter_places_the_parts_and_fills_the_rest_from_the_schema(top_k, values, graph):
+    from legal_rag_amd.retrieval.hybrid_retriever import COLUMNS
+    chunks, rng = [object()], np.random.default_rng(top_k)
+    n, at = 6, ([0, 3, 5], [4, 1])  # a plain part of 3, a scoped part of 2; question 2: a scope that matches nothing
+    parts = []
+    for seed, idxs in enumerate(at):
+        rec = synthetic_record(len(idxs), 20, _native.FUSE_NVALS, 50 + seed)
+        exact = rng.integers(0, 2, size=len(idxs)).astype(bool)
+        parts.append((idxs, HybridRetriever._decode_columns(rec, exact, top_k, chunks) if values
+                      else HybridRetriever._decode_lean(compact(*rec, top_k), exact, chunks)))
+    names = ["rows", "scores", "count", "channel_mask", "zh_exact"] + ["values"] * values
+    if graph:  # the plain part carries the graph columns, the scoped part does not
+        for name, dt, _, hit in COLUMNS:
+            if name.startswith("graph_"):
+                parts[0][1][name] = rng.integers(-1, 50, size=(3,) if hit is None else (3, top_k) + hit).astype(dt)
+                names.append(name)
+        parts[0][1]["graph_relation_names"] = ["cite", "next"]
+    out = HybridRetriever._scatter_columns(n, top_k, values, chunks, parts)
+    assert set(out) == set(names) | {"chunks"} | ({"value_names"} if values else set()) | \
+        ({"graph_relation_names"} if graph else set())
+    assert out["chunks"] is chunks and (not values or out["value_names"] == _native.FV)
+    assert not graph or out["graph_relation_names"] == ["cite", "next"]
+    schema = {name: rest for name, *rest in COLUMNS}
+    assert len(schema) == 13 and set(names) <= set(schema)
+    for name in names:
+        dt, fill, hit = schema[name]
+        assert out[name].dtype == dt and out[name].shape == ((n,) if hit is None else (n, top_k) + hit), name
+        rest = np.ones(n, dtype=bool)
+        for idxs, cols in parts:
+            if name in cols:
+                assert cols[name].dtype == dt and out[name][idxs].tobytes() == cols[name].tobytes(), name  # bit for bit
+                rest[idxs] = False
+        assert rest[2] and (rest[[4, 1]].all() if name.startswith("graph_") else rest.sum() == 1)
+        assert (out[name][rest] == fill).all(), name
+    # ONE part that holds every question is the result as it is (no copy on the path of a batch that is not split)
+    whole = parts[0][1]
+    assert HybridRetriever._scatter_columns(3, top_k, values, chunks, [(range(3), whole)]) is whole

@@ -615,3 +615,72 @@ def test_mixed_batch_is_re_interleaved(ucc_index):
         assert np.all(arr["rows"][j, len(hits):] == -1)
     lean = r.search_batch_arrays(qs, top_k=10, scopes=scopes, values=False)
     assert np.array_equal(lean["rows"], arr["rows"]) and np.array_equal(lean["count"], arr["count"])
+
+
+def test_mixed_batch_reranks_once_and_equals_each_question_alone(ucc_index, monkeypatch):
+    from legal_rag_amd.retrieval.hybrid_retriever import HybridRetriever
+    from legal_rag_amd.retrieval.scope import Scope
+    cfg, chunks = ucc_index
+    cfg2 = copy.deepcopy(cfg)
+    cfg2.retrieval.enable_rerank = True
+    cfg2.retrieval.rerank_ce_model = "hashing"  # the stand-in cross-encoder
+    r = HybridRetriever(cfg2)
+    s1, s2 = Scope(section=chunks[10].section), Scope(section=chunks[150].section)
+    scopes = [None, s1, None, Scope(section="no such section"), s2, s1]
+    qs = [QUESTIONS[j % len(QUESTIONS)] for j in range(len(scopes))]
+    calls, stage = [], HybridRetriever._rerank_stage
+
+    def counted(self, questions, *args, **kw):
+        calls.append(len(questions))
+        return stage(self, questions, *args, **kw)
+    monkeypatch.setattr(HybridRetriever, "_rerank_stage", counted)
+    out = r.search_batch(qs, top_k=10, scopes=scopes)
+    assert calls == [len(qs)]  # ONE stage over the whole batch: one pass through the cross-encoder, one blend launch
+    assert out[3] == []
+    for j, hits in enumerate(out):
+        exp = r.search(qs[j], top_k=10, scope=scopes[j])
+        assert [dump(h) for h in hits] == [dump(h) for h in exp], j
+        assert j == 3 or any(h.source == "rerank" for h in hits)
+
+
+def test_blank_questions_run_apart_with_and_without_a_scope(ucc_index):
+    from legal_rag_amd.retrieval.hybrid_retriever import HybridRetriever
+    from legal_rag_amd.retrieval.scope import Scope
+    cfg, chunks = ucc_index
+    r = HybridRetriever(cfg)
+    assert r.colbert is not None and r.colbert.enabled
+    s1 = Scope(section=chunks[10].section)
+    qs, scopes = ["", "  ", QUESTIONS[0], QUESTIONS[3]], [None, s1, None, s1]
+    out = r.search_batch(qs, top_k=10, scopes=scopes)
+    for j, hits in enumerate(out):
+        exp = r.search(qs[j], top_k=10, scope=scopes[j])
+        assert [dump(h) for h in hits] == [dump(h) for h in exp], j
+    assert all("colbert" in h.score_breakdown["channel"] for h in out[3][:1]) and out[2] and out[3]
+    assert not any("colbert" in h.score_breakdown["channel"] for j in (0, 1) for h in out[j])
+    for values in (True, False):
+        with pytest.raises(ValueError, match="empty questions are not supported in the columnar form"):
+            r.search_batch_arrays(qs, top_k=10, scopes=scopes, values=values)
+
+
+def test_graph_and_scopes_in_one_columnar_call(tmp_path):
+    from legal_rag_amd.retrieval.hybrid_retriever import COLUMNS
+    from legal_rag_amd.retrieval.scope import Scope
+    from test_graph_device_gpu import ucc_retriever
+    hr, chunks = ucc_retriever(tmp_path, "device")
+    s1, s2 = Scope(section=chunks[10].section), Scope(section=chunks[150].section)
+    graph, other = SimpleNamespace(mode="GRAPH_AUGMENTED"), SimpleNamespace(mode="HYBRID")
+    qs = QUESTIONS + QUESTIONS[:2]
+    scopes = [None, s1, None, s2, None, None]
+    decisions = [graph, None, other, None, graph, None]
+    for values in (True, False):
+        arr = hr.search_batch_arrays(qs, top_k=10, values=values, decisions=decisions, scopes=scopes)
+        alone = hr.search_batch_arrays([qs[0], qs[4]], top_k=10, values=values, decisions=[graph, graph])
+        assert int(alone["graph_count"].min()) > 0 and arr["count"][1] > 0 and arr["count"][3] > 0
+        assert arr["graph_relation_names"] == alone["graph_relation_names"]
+        for name, dt, fill, hit in COLUMNS:
+            if name.startswith("graph_"):
+                assert arr[name].dtype == alone[name].dtype == dt
+                assert arr[name].shape == ((6,) if hit is None else (6, 10))
+                assert np.array_equal(arr[name][[0, 4]], alone[name]), name
+                assert (arr[name][[1, 2, 3, 5]] == fill).all(), name
+        assert arr["graph_count"][[1, 2, 3, 5]].tolist() == [0, 0, 0, 0]
