@@ -30,7 +30,7 @@ static int check_bijection(long n, int d) {
           }
           seen[(size_t)u] = 1;
           // a (tile, chunk) piece is 4 KiB of its own, in the stage's byte order
-          if (u / (kHiStageBytes / 16) != t * nch + c || (u % (kHiStageBytes / 16)) * 16 != hi_stage_off(r, s)) return 1;
+          if (u / (kHiStageBytes / 16) != t * nch + c || (u % (kHiStageBytes / 16)) * 16 != stage_off(r, s)) return 1;
         }
   for (long u = 0; u < units; ++u)
     if (!seen[(size_t)u]) return 1;

@@ -76,8 +76,7 @@ __global__ __launch_bounds__(256) void dense_scan_topk_kernel(const float* __res
       for (int c = 0; c < CH; ++c) {
         int col = c * 256 + lane * 4;
         if (NT) {
-          typedef float nt4 __attribute__((ext_vector_type(4)));
-          const nt4 t_ = (col < d) ? __builtin_nontemporal_load(reinterpret_cast<const nt4*>(xr + col)) : nt4{0, 0, 0, 0};
+          const f32x4 t_ = (col < d) ? __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(xr + col)) : f32x4{0, 0, 0, 0};
           x[u][c] = make_float4(t_.x, t_.y, t_.z, t_.w);
         } else {
           x[u][c] = (col < d) ? *reinterpret_cast<const float4*>(xr + col) : make_float4(0, 0, 0, 0);
@@ -1062,7 +1061,7 @@ int amdr_dense_image_info(amdr_dense_t* h, int64_t* out4) {
   out4[0] = h->img ? 1 : 0;
   out4[1] = h->img ? (int64_t)hi_image_bytes((long)h->img_cap_rows, h->d) : 0;
   out4[2] = h->img ? h->img_rows : 0;
-  out4[3] = h->img ? 1 - dense_fp16_exp(h->img_scale) : 0;  // img_scale = 2^-e = 0.5 * 2^(1 - e)
+  out4[3] = h->img ? 1 - pow2_exp(h->img_scale) : 0;  // img_scale = 2^-e = 0.5 * 2^(1 - e)
   return AMDR_OK;
 }
 

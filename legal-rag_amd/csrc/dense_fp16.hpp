@@ -1,23 +1,15 @@
 // What the exactness of the dense channel's two fp16 first passes rests on — the large scan (dense_hi.hip) and the long
 // batch on a short corpus (dense_small_hi.hip + dense_tail.hip dense_hi_select_fuse_kernel) — stated once: the power-of-two
-// scale of a vector, the rounding bound, the scale range it holds in, the statistics of the chunk matrix that feed it.
+// scale of a vector (pow2_exp / pow2_scale of tile_swizzle.hpp, which MaxSim shares), the rounding bound, the scale range
+// it holds in, the statistics of the chunk matrix that feed it.
 #pragma once
-#include <hip/hip_runtime.h>
+#include "tile_swizzle.hpp"
 
 #include <cfloat>
 #include <cmath>
 #include <cstring>
 
 namespace amdr {
-
-// e with amax = f 2^e, f in [0.5, 1), for a vector's largest |component| amax (0 when amax is 0, infinite or NaN), and
-// the scale 2^-e that brings every |component| below 1
-__host__ __device__ inline int dense_fp16_exp(float amax) {
-  int e = 0;
-  if (amax > 0.f && amax <= FLT_MAX) (void)frexpf(amax, &e);
-  return e;
-}
-__host__ __device__ inline float dense_fp16_scale(int e) { return ldexpf(1.f, -e); }
 
 // The bound.  Both passes compute x^ . q^: fp16 roundings of x' = x 2^-ex and q' = q 2^-eq, exact products, fp32 sums.
 // Per component the fp16 rounding is |dx'| <= 2^-11 |x'| + 2^-25 (the second term covers fp16's subnormal range), the
@@ -57,8 +49,8 @@ inline DenseFp16Stats dense_fp16_stats(const unsigned int* words) {
   float amax, rmax;
   memcpy(&amax, words, 4);
   memcpy(&rmax, words + 1, 4);
-  const int e = dense_fp16_exp(amax);
-  return {dense_fp16_scale(e), rmax, amax <= FLT_MAX && rmax <= FLT_MAX && e > -100 && e < 100, words[kDenseStatNan] != 0u};
+  const int e = pow2_exp(amax);
+  return {pow2_scale(e), rmax, amax <= FLT_MAX && rmax <= FLT_MAX && e > -100 && e < 100, words[kDenseStatNan] != 0u};
 }
 
 }  // namespace amdr

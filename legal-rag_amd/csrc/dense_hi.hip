@@ -33,15 +33,10 @@
 
 namespace amdr {
 
-typedef float hi4f __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-
 constexpr int kHiWaves = 8;
 constexpr int kHiWbufMax = 384;          // entries of a wave's staging buffer at most (hi_wbuf_entries)
 
-// (the stage's byte order, hi_stage_off, and the chunk and stage sizes: dense_hi_image.hpp)
+// (the stage's byte order, stage_off: tile_swizzle.hpp; the chunk and stage sizes: dense_hi_image.hpp)
 // query tile: row q (0..63) at byte q * (d * 2), its 16-B chunk c at c ^ (q & 15) (rows alias on the banks: d * 2 % 256 == 0)
 __device__ __forceinline__ int hi_q_off(int q, int chunk, int d) { return q * (d * 2) + ((chunk ^ (q & 15)) << 4); }
 __host__ __device__ constexpr int hi_query_tile(int d) { return d > 896 ? 48 : 64; }
@@ -107,7 +102,7 @@ __device__ __forceinline__ void hi_tilemax_pass(const std::conditional_t<IMG, h8
   const int lrow = lane >> 4, lpiece = lane & 15;
   constexpr int NP = IMG ? 4 : 8;                    // 16-B loads per lane and chunk
   constexpr int CSTEP = IMG ? kHiStageBytes / 16 : kHiKC;  // a row pointer's step from chunk to chunk, in elements of X
-  using GV = std::conditional_t<IMG, h8, hi4f>;
+  using GV = std::conditional_t<IMG, h8, f32x4>;
   using XP = const std::conditional_t<IMG, h8, float>*;
   auto row_ptr = [&](long item, int p) -> XP {
     if constexpr (IMG) {
@@ -140,7 +135,7 @@ __device__ __forceinline__ void hi_tilemax_pass(const std::conditional_t<IMG, h8
     constexpr int CPQ = d / 8, ITS = (CPQ + 63) / 64;
 #pragma unroll
     for (int g = 0; g < 2; ++g) {
-      hi4f v[4][ITS][2];
+      f32x4 v[4][ITS][2];
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const int qi = wave * 8 + g * 4 + j;
@@ -150,9 +145,9 @@ __device__ __forceinline__ void hi_tilemax_pass(const std::conditional_t<IMG, h8
           const int c = lane + 64 * it;
           const bool ok = live && c < CPQ;
           const float* src = Q + (size_t)(ok ? qi : 0) * d + (ok ? c : 0) * 8;
-          const hi4f z = {0.f, 0.f, 0.f, 0.f};
-          v[j][it][0] = ok ? *reinterpret_cast<const hi4f*>(src) : z;
-          v[j][it][1] = ok ? *reinterpret_cast<const hi4f*>(src + 4) : z;
+          const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+          v[j][it][0] = ok ? *reinterpret_cast<const f32x4*>(src) : z;
+          v[j][it][1] = ok ? *reinterpret_cast<const f32x4*>(src + 4) : z;
         }
       }
 #pragma unroll
@@ -172,7 +167,7 @@ __device__ __forceinline__ void hi_tilemax_pass(const std::conditional_t<IMG, h8
         m = fmaxf(m, __uint_as_float(lane_xor<8>(__float_as_uint(m))));
         m = fmaxf(m, __uint_as_float(lane_xor<16>(__float_as_uint(m))));
         m = fmaxf(m, __uint_as_float(lane_xor<32>(__float_as_uint(m))));
-        const float sc = dense_fp16_scale(dense_fp16_exp(m));  // (the scale dense_hi_select_kernel states the bound in)
+        const float sc = pow2_scale(pow2_exp(m));  // (the scale dense_hi_select_kernel states the bound in)
         if (qi < QT) {
 #pragma unroll
           for (int it = 0; it < ITS; ++it) {
@@ -234,11 +229,11 @@ __device__ __forceinline__ void hi_tilemax_pass(const std::conditional_t<IMG, h8
         if constexpr (IMG) {
           *reinterpret_cast<h8*>(stage + p * 1024 + lane * 16) = G[c & 1][p];
         } else {
-          const hi4f x = G[c & 1][p];
+          const f32x4 x = G[c & 1][p];
           h4 y;
 #pragma unroll
           for (int e = 0; e < 4; ++e) y[e] = hi_half(x[e], x_scale);
-          *reinterpret_cast<h4*>(stage + hi_stage_off(4 * p + lrow, lpiece >> 1) + (lpiece & 1) * 8) = y;
+          *reinterpret_cast<h4*>(stage + stage_off(4 * p + lrow, lpiece >> 1) + (lpiece & 1) * 8) = y;
         }
       }
       // the refill is issued HERE, two chunks ahead of its use (hipcc otherwise sinks the loads towards their first use
@@ -259,7 +254,7 @@ __device__ __forceinline__ void hi_tilemax_pass(const std::conditional_t<IMG, h8
       // fragments: A = row r32, chunks 2 s + h (s = 0..3) of the stage; B = query r32 (+ 32), chunks 8 c + 2 s + h of its row
 #pragma unroll
       for (int s = 0; s < 4; ++s) {
-        const h8 a = *reinterpret_cast<const h8*>(stage + hi_stage_off(r32, 2 * s + h));
+        const h8 a = *reinterpret_cast<const h8*>(stage + stage_off(r32, 2 * s + h));
 #pragma unroll
         for (int b = 0; b < 2; ++b) {
           // (a 48-query tile has no rows 48..63: the second block's upper columns re-read rows 32..47 and are never used)
@@ -648,8 +643,8 @@ __global__ __launch_bounds__(256) void dense_hi_select_kernel(const C32* __restr
 #pragma unroll
   for (int sft = 1; sft < 64; sft <<= 1) amax = fmaxf(amax, __uint_as_float(lane_xor_sw(__float_as_uint(amax), sft)));
   nan = __any(nan);
-  const int e = dense_fp16_exp(amax);
-  const float sc = dense_fp16_scale(e);
+  const int e = pow2_exp(amax);
+  const float sc = pow2_scale(e);
   float ss = 0.f;
   for (int j = lane; j < d; j += 64) {
     const float x = Q[(size_t)q * d + j] * sc;
@@ -749,7 +744,7 @@ int dense_hi2_launch_emit(const float* X, const void* image, long n, int d, cons
 int dense_hi2_launch_select(const void* qlist, const unsigned int* qcount, size_t qcap, int m, int kc, int k, const float* Q,
                             int d, float row_norm_max, float x_scale, long n_tiles, int* list, int* count, int* unres,
                             int* flag, unsigned int* unresolved, hipStream_t st) {
-  const int x_exp = 1 - dense_fp16_exp(x_scale);  // x_scale = 2^-ex = 0.5 * 2^(1 - ex)
+  const int x_exp = 1 - pow2_exp(x_scale);  // x_scale = 2^-ex = 0.5 * 2^(1 - ex)
   const int tcap = topk_cap(kc);
   const size_t lds = TopkLds<C32>::bytes(4, tcap);
   hipLaunchKernelGGL(dense_hi_select_kernel, dim3(m), dim3(256), lds, st, (const C32*)qlist, qcount, (unsigned int)qcap, kc, k,

@@ -6,14 +6,11 @@
 
 namespace amdr {
 
-typedef float img4f __attribute__((ext_vector_type(4)));
-typedef _Float16 img8h __attribute__((ext_vector_type(8)));
-
 // One thread per 16-byte unit of the image, enumerated in the order of the SOURCE (row by row, 8 components each: a
 // wave reads 2 KiB of a row contiguously); the unit's place in the image permutes the 8 units of a row's 128-byte
 // segment, so the stores still fill whole segments.  Rows past n repeat row n - 1 (the scan's row clamp).
 __global__ __launch_bounds__(256) void dense_hi_image_kernel(const float* __restrict__ X, long tile0, long n, int d,
-                                                             float x_scale, img8h* __restrict__ image) {
+                                                             float x_scale, h8* __restrict__ image) {
   const int upr = d / 8, nch = d / kHiKC;  // units per row
   const long units = (hi_image_tiles(n) - tile0) * kHiTileRows * upr;
   for (long u = (long)blockIdx.x * 256 + threadIdx.x; u < units; u += (long)gridDim.x * 256) {
@@ -24,8 +21,8 @@ __global__ __launch_bounds__(256) void dense_hi_image_kernel(const float* __rest
     long r = tile * kHiTileRows + row;
     if (r >= n) r = n - 1;
     const float* src = X + (size_t)r * d + c8 * 8;
-    const img4f a = *reinterpret_cast<const img4f*>(src), b = *reinterpret_cast<const img4f*>(src + 4);
-    img8h y;
+    const f32x4 a = *reinterpret_cast<const f32x4*>(src), b = *reinterpret_cast<const f32x4*>(src + 4);
+    h8 y;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       y[e] = hi_half(a[e], x_scale);
@@ -43,7 +40,7 @@ int dense_hi_image_launch(const float* X, long row0, long n, int d, float x_scal
   long blocks = (units + 255) / 256;
   if (blocks > 8192) blocks = 8192;
   hipLaunchKernelGGL(dense_hi_image_kernel, dim3((unsigned)blocks), dim3(256), 0, st, X, tile0, n, d, x_scale,
-                     reinterpret_cast<img8h*>(image));
+                     reinterpret_cast<h8*>(image));
   AMDR_HIP(hipGetLastError());
   return AMDR_OK;
 }

@@ -24,15 +24,13 @@
 // second, slab-parallel pass over S (+8 % traffic at d = 768: 128 B written and read per
 // 3072-B row per 32 queries).
 #include "common.hpp"
+#include "tile_swizzle.hpp"
 #include "topk.hpp"
 
 #include <cfloat>
 #include <cstdlib>
 
 namespace amdr {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float v4f __attribute__((ext_vector_type(4)));  // native vector: stays in registers (HIP's float4 struct did not)
 
 constexpr int kBW = 4;          // waves per block
 constexpr int kKC = 32;         // floats of every row per staged chunk (128 B = 8 slots of 16 B)
@@ -47,18 +45,13 @@ constexpr int kStageBufs = AMDR_STAGE_BUFS;
 constexpr int kPieces = kStageBytes / 1024;  // 1-KiB wave loads per chunk (4): 8 rows x 128 B each
 constexpr int kDepth = 4;                      // chunks in flight from HBM per wave (16 KiB)
 
-// LDS image of a staged chunk: row r (0..31) at byte r*128 — two rows share one 256-B bank
-// row — with its logical 16-B slot s (0..7) at physical slot s ^ ((r >> 1) & 7).  A
-// ds_read_b128 lane group covers 16 different rows at the same logical slot: 8 distinct
-// physical slots x the 2 halves of the bank row = conflict-free; a ds_write_b128 lane group
-// (8 contiguous lanes) writes the 8 slots of one row.
-__device__ __forceinline__ int stage_off(int row, int slot) { return row * 128 + ((slot ^ ((row >> 1) & 7)) << 4); }
+// LDS image of a staged chunk: 32 rows of 128 B in the byte order of stage_off (tile_swizzle.hpp).
 
 // The three pipeline steps are macros, not functions: passing the register arrays by
 // reference made hipcc (ROCm 7.2) keep them in scratch memory.
 #define AMDR_STAGE_CHUNK(ST, G)                                                                   \
   _Pragma("unroll") for (int p_ = 0; p_ < kPieces; ++p_)                                          \
-      *reinterpret_cast<v4f*>((ST) + stage_off(8 * p_ + lrow, lslot)) = G[p_];
+      *reinterpret_cast<f32x4*>((ST) + stage_off(8 * p_ + lrow, lslot)) = G[p_];
 // Fragments of one 32-float chunk.  v_mfma_f32_16x16x4_f32 takes A[row l&15][k = l>>4] and
 // B[k = l>>4][col l&15], one float per lane, so a lane (i16 = l & 15, kq = l >> 4) owns, for each
 // of the two 16-row blocks b of the tile, the 16-B slots 4u + kq (u = 0, 1) of row 16b + i16: the
@@ -70,7 +63,7 @@ __device__ __forceinline__ int stage_off(int row, int slot) { return row * 128 +
 #define AMDR_READ_FRAGS(ST, C, FX, FQ)                                                            \
   _Pragma("unroll") for (int b_ = 0; b_ < 2; ++b_) {                                              \
     _Pragma("unroll") for (int u_ = 0; u_ < 2; ++u_) {                                            \
-      FX[b_][u_] = *reinterpret_cast<const v4f*>((ST) + b_ * 2048 + xoff[u_]);                    \
+      FX[b_][u_] = *reinterpret_cast<const f32x4*>((ST) + b_ * 2048 + xoff[u_]);                    \
       FQ[b_][u_] = qrow[b_ * 16 * (d / 4) + ((C) >> 1) * 16 + qlow[(C) & 1][u_]];                 \
     }                                                                                             \
   }
@@ -98,10 +91,10 @@ __device__ __forceinline__ int stage_off(int row, int slot) { return row * 128 +
 #define AMDR_INTERLEAVE()
 
 #if defined(AMDR_ABLATE) && AMDR_ABLATE == 2  // timing-only build: no X traffic (registers filled from an address hash)
-#define AMDR_LDX(PTR) ([&] { v4f z_; z_.x = z_.y = z_.z = z_.w = (float)(((size_t)(PTR)) & 1023) * 1e-3f; return z_; }())
+#define AMDR_LDX(PTR) ([&] { f32x4 z_; z_.x = z_.y = z_.z = z_.w = (float)(((size_t)(PTR)) & 1023) * 1e-3f; return z_; }())
 #else
 // NTL (template constant): non-temporal policy for a matrix beyond the Infinity Cache (common.hpp)
-#define AMDR_LDX(PTR) (NTL ? __builtin_nontemporal_load(reinterpret_cast<const v4f*>(PTR)) : *reinterpret_cast<const v4f*>(PTR))
+#define AMDR_LDX(PTR) (NTL ? __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(PTR)) : *reinterpret_cast<const f32x4*>(PTR))
 #endif
 
 // grid: (x = row slabs, y = 32-query tiles).
@@ -122,7 +115,7 @@ __global__ __launch_bounds__(WAVES * 64) void dense_mfma_scores_kernel(const flo
   constexpr int d = D8 * 8;
   constexpr int NCH = d / kKC;  // chunks per row: 12 / 24 / 32 (always even: d % 64 == 0)
   static_assert(d % kKC == 0, "dim must be a multiple of 64");
-  const v4f* qsv = reinterpret_cast<const v4f*>(smem);
+  const f32x4* qsv = reinterpret_cast<const f32x4*>(smem);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   unsigned char* stage = smem + (size_t)d * 128 + (size_t)wave * kStageBufs * kStageBytes;
   const int i16 = lane & 15, kq = lane >> 4;  // MFMA fragment roles
@@ -137,7 +130,7 @@ __global__ __launch_bounds__(WAVES * 64) void dense_mfma_scores_kernel(const flo
     qlow[0][u] = (4 * u + kq) ^ i16;
     qlow[1][u] = (8 + 4 * u + kq) ^ i16;
   }
-  const v4f* qrow = qsv + i16 * (d / 4);
+  const f32x4* qrow = qsv + i16 * (d / 4);
   // Block id -> (slab bx of the streamed operand, tile by of the LDS operand).  The grid is 1-D and
   // remapped so that each XCD (blocks with equal id % 8 share one; 8 XCDs, each with its own L2)
   // owns a CONTIGUOUS range of the slab-major order: the `gy` blocks that stream the same slab
@@ -168,14 +161,14 @@ __global__ __launch_bounds__(WAVES * 64) void dense_mfma_scores_kernel(const flo
     constexpr int NT = WAVES * 64, TOTAL = 32 * (d / 4), PER = (TOTAL + NT - 1) / NT, BATCH = 16;
 #pragma unroll
     for (int j0 = 0; j0 < PER; j0 += BATCH) {
-      v4f tmp[BATCH];
+      f32x4 tmp[BATCH];
 #pragma unroll
       for (int j = 0; j < BATCH; ++j) {
         if (j0 + j < PER) {
           const int idx = threadIdx.x + (j0 + j) * NT;
           const int qi_ = idx / (d / 4), k4 = idx - qi_ * (d / 4);
-          v4f z = {0.f, 0.f, 0.f, 0.f};
-          tmp[j] = (idx < TOTAL && q0 + qi_ < nq) ? *reinterpret_cast<const v4f*>(Q + (size_t)(q0 + qi_) * d + 4 * k4)
+          f32x4 z = {0.f, 0.f, 0.f, 0.f};
+          tmp[j] = (idx < TOTAL && q0 + qi_ < nq) ? *reinterpret_cast<const f32x4*>(Q + (size_t)(q0 + qi_) * d + 4 * k4)
                                                   : z;
         }
       }
@@ -184,7 +177,7 @@ __global__ __launch_bounds__(WAVES * 64) void dense_mfma_scores_kernel(const flo
         if (j0 + j < PER) {
           const int idx = threadIdx.x + (j0 + j) * NT;
           const int qi_ = idx / (d / 4), k4 = idx - qi_ * (d / 4);
-          if (idx < TOTAL) reinterpret_cast<v4f*>(smem)[qi_ * (d / 4) + (k4 ^ (qi_ & 15))] = tmp[j];
+          if (idx < TOTAL) reinterpret_cast<f32x4*>(smem)[qi_ * (d / 4) + (k4 ^ (qi_ & 15))] = tmp[j];
         }
       }
     }
@@ -212,7 +205,7 @@ __global__ __launch_bounds__(WAVES * 64) void dense_mfma_scores_kernel(const flo
     //   stage[c & 1]   this wave's LDS image of chunk c (swizzled, double-buffered)
     //   FX/FQ[c & 1]   MFMA fragments of chunk c, read from LDS one chunk AHEAD of their use so
     //                  the dependent MFMA chain never waits on an LDS round trip.
-    v4f G[kDepth][kPieces], FX[2][2][2], FQ[2][2][2];
+    f32x4 G[kDepth][kPieces], FX[2][2][2], FQ[2][2][2];
 #pragma unroll
     for (int j = 0; j < kDepth; ++j) {
       if (j < NCH) {
@@ -417,8 +410,8 @@ __global__ __launch_bounds__(WPB * 64) void dense_rescore_tiles_kernel(const flo
   const int q = blockIdx.x;
   const int cnt = count[q];
   if ((int)blockIdx.y * WPB >= cnt) return;  // block-uniform: nothing of this query's list falls to the block
-  v4f* qv = reinterpret_cast<v4f*>(smem);
-  for (int i = threadIdx.x; i < d / 4; i += WPB * 64) qv[i] = *reinterpret_cast<const v4f*>(Q + (size_t)q * d + 4 * i);
+  f32x4* qv = reinterpret_cast<f32x4*>(smem);
+  for (int i = threadIdx.x; i < d / 4; i += WPB * 64) qv[i] = *reinterpret_cast<const f32x4*>(Q + (size_t)q * d + 4 * i);
   __syncthreads();
   const int t = blockIdx.y * WPB + wave;
   if (t >= cnt) return;
@@ -436,18 +429,18 @@ __global__ __launch_bounds__(WPB * 64) void dense_rescore_tiles_kernel(const flo
     if (r >= n_real) r = n_real - 1;
     gp[p] = X + (size_t)r * d + lslot * 4;
   }
-  v4f G[kRsDepth][kPieces], FX[2][2][2], FQ[2][2];
+  f32x4 G[kRsDepth][kPieces], FX[2][2][2], FQ[2][2];
 #pragma unroll
   for (int j = 0; j < kRsDepth; ++j) {
     if (j < NCH) {
 #pragma unroll
-      for (int p = 0; p < kPieces; ++p) G[j][p] = *reinterpret_cast<const v4f*>(gp[p] + j * kKC);
+      for (int p = 0; p < kPieces; ++p) G[j][p] = *reinterpret_cast<const f32x4*>(gp[p] + j * kKC);
     }
   }
 #define AMDR_RS_FRAGS(ST, C, FX_, FQ_)                                                     \
   _Pragma("unroll") for (int u_ = 0; u_ < 2; ++u_) {                                       \
-    FX_[0][u_] = *reinterpret_cast<const v4f*>((ST) + xoff[u_]);                           \
-    FX_[1][u_] = *reinterpret_cast<const v4f*>((ST) + 2048 + xoff[u_]);                    \
+    FX_[0][u_] = *reinterpret_cast<const f32x4*>((ST) + xoff[u_]);                           \
+    FX_[1][u_] = *reinterpret_cast<const f32x4*>((ST) + 2048 + xoff[u_]);                    \
     FQ_[u_] = qv[8 * (C) + 4 * u_ + kq];                                                   \
   }
 #define AMDR_RS_KSTEP(FX_, FQ_, U, COMP)                                                              \
@@ -456,7 +449,7 @@ __global__ __launch_bounds__(WPB * 64) void dense_rescore_tiles_kernel(const flo
   AMDR_STAGE_CHUNK(stage, G[0])
   if (kRsDepth < NCH) {
 #pragma unroll
-    for (int p = 0; p < kPieces; ++p) G[0][p] = *reinterpret_cast<const v4f*>(gp[p] + kRsDepth * kKC);
+    for (int p = 0; p < kPieces; ++p) G[0][p] = *reinterpret_cast<const f32x4*>(gp[p] + kRsDepth * kKC);
   }
   wave_lds_fence();
   AMDR_RS_FRAGS(stage, 0, FX[0], FQ[0])
@@ -469,7 +462,7 @@ __global__ __launch_bounds__(WPB * 64) void dense_rescore_tiles_kernel(const flo
       AMDR_STAGE_CHUNK(stage, G[(c + 1) % kRsDepth])
       if (c + 1 + kRsDepth < NCH) {
 #pragma unroll
-        for (int p = 0; p < kPieces; ++p) G[(c + 1) % kRsDepth][p] = *reinterpret_cast<const v4f*>(gp[p] + (c + 1 + kRsDepth) * kKC);
+        for (int p = 0; p < kPieces; ++p) G[(c + 1) % kRsDepth][p] = *reinterpret_cast<const f32x4*>(gp[p] + (c + 1 + kRsDepth) * kKC);
       }
       AMDR_RS_FRAGS(stage, c + 1, FX[(c + 1) & 1], FQ[(c + 1) & 1])
     }

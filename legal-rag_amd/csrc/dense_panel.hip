@@ -27,21 +27,17 @@
 // Pipeline: two LDS buffers; the DMA of chunk c+1 is issued before the fragment reads of chunk
 // c and retired (vmcnt(0)) at the block barrier that ends chunk c.
 #include "common.hpp"
+#include "lds_ring.hpp"
 
 #include <atomic>
 #include <cstdlib>
 
 namespace amdr {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-#define AMDR_GPTR(p) ((const __attribute__((address_space(1))) void*)(p))
-#define AMDR_LPTR(p) ((__attribute__((address_space(3))) void*)(p))
-
+// (lds_ring.hpp: the casts of an LDS-DMA only — the loop below is a double buffer, not its ring; tile_swizzle.hpp:
+// stage_off / stage_slot, the byte offset of logical 16-B slot `slot` of row `row` in a [rows][128 B] image)
 constexpr int kPanelKC = 32;  // floats of K per chunk: 128 B = 8 slots of 16 B per row
 
-// byte offset of logical 16-B slot `slot` of row `row` in a [rows][128 B] image
-__device__ __forceinline__ int panel_off(int row, int slot) { return row * 128 + ((slot ^ ((row >> 1) & 7)) << 4); }
 
 // One (32 queries per wave) x (NBP x 16 rows) tile.  NBE = row blocks the panel buffers are
 // sized and filled for (NBP rounded up so that every wave issues the same number of DMA
@@ -71,7 +67,7 @@ __device__ __forceinline__ void panel_tile(const float* __restrict__ X, long n, 
     const int r = 8 * (wave + WAVES * j) + prow;  // row in the panel
     long gr = row0 + r;
     if (gr > n - 1) gr = n - 1;
-    xp[j] = X + (size_t)gr * d + ((pslot ^ ((r >> 1) & 7)) << 2);
+    xp[j] = X + (size_t)gr * d + (stage_slot(r, pslot) << 2);
   }
   const float* qp[4];
 #pragma unroll
@@ -79,12 +75,12 @@ __device__ __forceinline__ void panel_tile(const float* __restrict__ X, long n, 
     const int r = 8 * j + prow;
     int gq = q0w + r;
     if (gq > nq - 1) gq = nq - 1;
-    qp[j] = Q + (size_t)gq * d + ((pslot ^ ((r >> 1) & 7)) << 2);
+    qp[j] = Q + (size_t)gq * d + (stage_slot(r, pslot) << 2);
   }
   // lane-dependent part of the fragment read addresses (slot 4u + kq of row i16 of a block)
   int foff[2];
 #pragma unroll
-  for (int u = 0; u < 2; ++u) foff[u] = panel_off(i16, 4 * u + kq);
+  for (int u = 0; u < 2; ++u) foff[u] = stage_off(i16, 4 * u + kq);
 
   f32x4 acc[NBP][2];
 #pragma unroll

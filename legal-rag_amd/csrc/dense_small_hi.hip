@@ -16,9 +16,10 @@
 //                                  fragments per slice (64 VGPRs) and keeps 4 x 2 accumulator tiles (128 VGPRs) across
 //                                  the 6 slices of d = 768 — 32 queries x 768 dims of fragments (192 VGPRs for ONE
 //                                  tile) do not fit a wave, which is what makes this shape different from MaxSim's.
-// The error bound eps_q (the large scan's: the same arithmetic), the scales and the statistics: dense_fp16.hpp.
+// The error bound eps_q (the large scan's: the same arithmetic), the scales, the statistics: dense_fp16.hpp; the ring: lds_ring.hpp.
 #include "common.hpp"
 #include "dense_fp16.hpp"
+#include "lds_ring.hpp"
 
 #include <cfloat>
 #include <cmath>
@@ -27,17 +28,9 @@
 
 namespace amdr {
 
-#define AMDR_DS_GPTR(p) ((const __attribute__((address_space(1))) void*)(p))
-#define AMDR_DS_LPTR(p) ((__attribute__((address_space(3))) void*)(p))
-typedef _Float16 ds8h __attribute__((ext_vector_type(8)));
-typedef float ds4f __attribute__((ext_vector_type(4)));
-typedef float dsf16 __attribute__((ext_vector_type(16)));
-
 constexpr int kDsWaves = 4;  // waves per block, two 32-query tiles each
 constexpr int kDsG = 4;      // 32-row chunk tiles per block
 constexpr int kDsStage = 32 * 256;
-
-__device__ __forceinline__ int ds_hi_off(int row, int slot) { return row * 256 + ((slot ^ (row & 15)) << 4); }
 
 // ---- the chunk image: Xh[slice][row][slot of 8 halves] = fp16(x * x_scale), one thread per (row, 8 components)
 __global__ __launch_bounds__(256) void dsh_image_kernel(const float* __restrict__ X, long n, int d, float x_scale,
@@ -47,15 +40,15 @@ __global__ __launch_bounds__(256) void dsh_image_kernel(const float* __restrict_
   if (idx >= n * groups) return;
   const long row = idx / groups;
   const int g = (int)(idx - row * groups);
-  const ds4f v0 = *reinterpret_cast<const ds4f*>(X + (size_t)row * d + 8 * g);
-  const ds4f v1 = *reinterpret_cast<const ds4f*>(X + (size_t)row * d + 8 * g + 4);
-  ds8h y;
+  const f32x4 v0 = *reinterpret_cast<const f32x4*>(X + (size_t)row * d + 8 * g);
+  const f32x4 v1 = *reinterpret_cast<const f32x4*>(X + (size_t)row * d + 8 * g + 4);
+  h8 y;
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
     y[e] = (_Float16)(v0[e] * x_scale);
     y[4 + e] = (_Float16)(v1[e] * x_scale);
   }
-  *reinterpret_cast<ds8h*>(Xh + ((size_t)(g >> 4) * n_pad + row) * 256 + (size_t)(g & 15) * 16) = y;
+  *reinterpret_cast<h8*>(Xh + ((size_t)(g >> 4) * n_pad + row) * 256 + (size_t)(g & 15) * 16) = y;
 }
 
 // ---- the queries: a wave takes EIGHT consecutive queries, eight lanes each (lane = 8 j + s: query j, groups s, s + 8, ...
@@ -76,8 +69,8 @@ __global__ __launch_bounds__(256) void dsh_split_queries_kernel(const float* __r
   for (int i = 0; i < 16; ++i) {
     if (i < per && live) {
       const float* p = Q + (size_t)q * d + 8 * (sub + 8 * i);
-      const ds4f v0 = *reinterpret_cast<const ds4f*>(p);
-      const ds4f v1 = *reinterpret_cast<const ds4f*>(p + 4);
+      const f32x4 v0 = *reinterpret_cast<const f32x4*>(p);
+      const f32x4 v1 = *reinterpret_cast<const f32x4*>(p + 4);
 #pragma unroll
       for (int e = 0; e < 4; ++e) x[i][e] = v0[e], x[i][4 + e] = v1[e];
     } else {
@@ -95,8 +88,8 @@ __global__ __launch_bounds__(256) void dsh_split_queries_kernel(const float* __r
     amax = fmaxf(amax, __shfl_xor(amax, sft));
     nan |= __shfl_xor((int)nan, sft) != 0;
   }
-  const int e2 = dense_fp16_exp(amax);
-  const float sc = dense_fp16_scale(e2);
+  const int e2 = pow2_exp(amax);
+  const float sc = pow2_scale(e2);
   float ss = 0.f;
 #pragma unroll
   for (int i = 0; i < 16; ++i)
@@ -114,10 +107,10 @@ __global__ __launch_bounds__(256) void dsh_split_queries_kernel(const float* __r
     if (i >= per) continue;
     const int g = sub + 8 * i;
     const int kc = g >> 4, slot = g & 15, st = slot >> 1, hh = slot & 1;
-    ds8h y;
+    h8 y;
 #pragma unroll
     for (int e = 0; e < 8; ++e) y[e] = (_Float16)(x[i][e] * sc);
-    *reinterpret_cast<ds8h*>(Qh + ((((size_t)tile * ks + kc) * 8 + st) * 64 + (r32 + 32 * hh)) * 16) = y;
+    *reinterpret_cast<h8*>(Qh + ((((size_t)tile * ks + kc) * 8 + st) * 64 + (r32 + 32 * hh)) * 16) = y;
   }
   if (sub == 0) {
     const bool bad = nan || !(amax <= FLT_MAX) || !dense_fp16_range_short_corpus(e2);
@@ -151,26 +144,19 @@ __global__ __launch_bounds__(kDsWaves * 64) __attribute__((amdgpu_waves_per_eu(2
   const int t0 = yg * kDsG;
   const int g = n_tiles - t0 < kDsG ? n_tiles - t0 : kDsG;  // block-uniform, >= 1
 
-  // DMA role: pieces 2 wave, 2 wave + 1 of a tile's 8 (1 KiB = 4 rows of 256 B); lane l: row + (l >> 4), PHYSICAL slot
-  // l & 15, which holds logical slot ^ (row & 15) (maxsim.hip, the hi-only ring)
+  // DMA role in the ring (lds_ring.hpp): pieces 2 wave, 2 wave + 1 of a tile's 8 (1 KiB = 4 rows of 256 B)
   long poff[2];
 #pragma unroll
-  for (int u = 0; u < 2; ++u) {
-    const int prow = 4 * (2 * wave + u) + (lane >> 4);
-    poff[u] = (long)prow * 256 + (((lane & 15) ^ (prow & 15)) << 4);
-  }
+  for (int u = 0; u < 2; ++u) poff[u] = piece_off<256>(2 * wave + u, lane);
   int foff[8];
 #pragma unroll
-  for (int st = 0; st < 8; ++st) foff[st] = ds_hi_off(r32, 2 * st + h);
+  for (int st = 0; st < 8; ++st) foff[st] = tile_off<256>(r32, 2 * st + h);
 
   // the stream of tiles through the ring: K slice major, the block's g chunk tiles inside
   int p_kc = 0, p_j = 0;  // producer cursor
   auto issue = [&](int stage) {
     const unsigned char* src = Xh + ((size_t)p_kc * n_pad + (size_t)32 * (t0 + p_j)) * 256;  // wave-uniform
-#pragma unroll
-    for (int u = 0; u < 2; ++u)
-      __builtin_amdgcn_global_load_lds(AMDR_DS_GPTR(src + poff[u]),
-                                       AMDR_DS_LPTR(ring + stage * kDsStage + (2 * wave + u) * 1024), 16, 0, 0);
+    ring_issue_tile<2>(src, poff, ring + stage * kDsStage + 2 * wave * 1024);
     if (++p_j == g) p_j = 0, ++p_kc;
   };
   int issued = 0, done = 0;
@@ -181,7 +167,7 @@ __global__ __launch_bounds__(kDsWaves * 64) __attribute__((amdgpu_waves_per_eu(2
       ++issued;
     }
   }
-  dsf16 acc[kDsG][2];
+  f32x16 acc[kDsG][2];
 #pragma unroll
   for (int j = 0; j < kDsG; ++j)
 #pragma unroll
@@ -190,30 +176,20 @@ __global__ __launch_bounds__(kDsWaves * 64) __attribute__((amdgpu_waves_per_eu(2
   for (int kc = 0; kc < ks; ++kc) {
     // this slice's query fragments: 2 x 8 coalesced 1-KiB loads; drained at once (they are needed now), which also lands
     // every tile issued so far
-    ds8h qa[8], qb[8];
+    h8 qa[8], qb[8];
     const unsigned char* pa = Qh + (((size_t)la * ks + kc) * 8) * 1024 + (size_t)lane * 16;
     const unsigned char* pb = Qh + (((size_t)lb * ks + kc) * 8) * 1024 + (size_t)lane * 16;
 #pragma unroll
     for (int st = 0; st < 8; ++st) {
-      qa[st] = *reinterpret_cast<const ds8h*>(pa + st * 1024);
-      qb[st] = *reinterpret_cast<const ds8h*>(pb + st * 1024);
+      qa[st] = *reinterpret_cast<const h8*>(pa + st * 1024);
+      qb[st] = *reinterpret_cast<const h8*>(pb + st * 1024);
     }
-    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
+    wait_vm0();
     asm volatile("" ::: "memory");
 #pragma unroll
     for (int j = 0; j < kDsG; ++j) {
       if (j < g) {  // block-uniform
-        __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): the fragment reads of the previous tile
-        const int behind = issued - done - 1;  // tiles issued behind this one: 2 loads each may still be in flight
-        if (behind >= 3) {
-          __builtin_amdgcn_s_waitcnt(0x0F76);
-        } else if (behind == 2) {
-          __builtin_amdgcn_s_waitcnt(0x0F74);
-        } else if (behind == 1) {
-          __builtin_amdgcn_s_waitcnt(0x0F72);
-        } else {
-          __builtin_amdgcn_s_waitcnt(0x0F70);
-        }
+        wait_tile<2, 3>(issued - done - 1);  // the fragment reads of the previous tile; this wave's pieces of tile `done`
         __builtin_amdgcn_s_barrier();  // everybody's pieces of tile `done` are in; tile done - 1 has been read by all
         asm volatile("" ::: "memory");
         if (p_kc < ks) {
@@ -221,9 +197,9 @@ __global__ __launch_bounds__(kDsWaves * 64) __attribute__((amdgpu_waves_per_eu(2
           ++issued;
         }
         const unsigned char* tile = ring + (done % NBUF) * kDsStage;
-        ds8h a[8];
+        h8 a[8];
 #pragma unroll
-        for (int st = 0; st < 8; ++st) a[st] = *reinterpret_cast<const ds8h*>(tile + foff[st]);
+        for (int st = 0; st < 8; ++st) a[st] = *reinterpret_cast<const h8*>(tile + foff[st]);
 #pragma unroll
         for (int st = 0; st < 8; ++st) {
           acc[j][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[st], qa[st], acc[j][0], 0, 0, 0);
@@ -233,7 +209,7 @@ __global__ __launch_bounds__(kDsWaves * 64) __attribute__((amdgpu_waves_per_eu(2
       }
     }
   }
-  // accumulator element i of lane (r32, h): chunk row 32 (t0 + j) + (i & 3) + 8 (i >> 2) + 4 h, query 32 tile + r32
+  // accumulator element i of lane (r32, h): chunk row 32 (t0 + j) + mfma32_row(i, h) (4 m + e: 8 m + 4 h + e), query 32 tile + r32
 #pragma unroll
   for (int ab = 0; ab < 2; ++ab) {
     const int tq = ab == 0 ? ta : tb;
@@ -246,10 +222,10 @@ __global__ __launch_bounds__(kDsWaves * 64) __attribute__((amdgpu_waves_per_eu(2
       if (j >= g) continue;
 #pragma unroll
       for (int m = 0; m < 4; ++m) {
-        ds4f v;
+        f32x4 v;
 #pragma unroll
         for (int e = 0; e < 4; ++e) v[e] = acc[j][ab][4 * m + e] * us;
-        *reinterpret_cast<ds4f*>(row + 32 * j + 8 * m) = v;
+        *reinterpret_cast<f32x4*>(row + 32 * j + 8 * m) = v;
       }
     }
   }

@@ -58,12 +58,12 @@ __device__ __forceinline__ int select_row_pair_margin(const float* __restrict__ 
                                                       float margin, int lane, C32* scratch, C32& out, int& need) {
   const float* row = S + (size_t)q * ldS;
   const int j = lane & 31;
-  tk_v4f blk[V / 4];
+  f32x4 blk[V / 4];
 #pragma unroll
   for (int u = 0; u < V / 4; ++u) {
     const long c0 = 128L * u + 4 * j;
-    const tk_v4f z = {0.f, 0.f, 0.f, 0.f};
-    blk[u] = (has_q && c0 < ldS) ? __builtin_nontemporal_load(reinterpret_cast<const tk_v4f*>(row + c0)) : z;  // read once
+    const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+    blk[u] = (has_q && c0 < ldS) ? __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(row + c0)) : z;  // read once
   }
   u32 sk[V];
 #pragma unroll
@@ -171,11 +171,11 @@ __global__ __launch_bounds__(64) void dense_hi_select_fuse_kernel(amdr_fuse_para
   const float margin = 2.f * e_q * margin_scale;
   bool exact_all = has_q && !(margin == margin && margin <= FLT_MAX);  // no bound for this query
   // this half's query, spread over its 32 lanes: lane sl holds components 128 u + 4 sl .. + 3
-  tk_v4f qv[D128];
+  f32x4 qv[D128];
 #pragma unroll
   for (int u = 0; u < D128; ++u) {
-    const tk_v4f z = {0.f, 0.f, 0.f, 0.f};
-    qv[u] = has_q ? __builtin_nontemporal_load(reinterpret_cast<const tk_v4f*>(Q + (size_t)q * d + 128 * u + 4 * sl)) : z;  // (the
+    const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+    qv[u] = has_q ? __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(Q + (size_t)q * d + 128 * u + 4 * sl)) : z;  // (the
     // streamed score rows and queries are read once: non-temporal, so that the chunk rows the candidates re-read stay in L2)
   }
   // the sum of a value over the 32 lanes of each half, in every lane of the half: five DPP row operations leave the halves'
@@ -191,12 +191,12 @@ __global__ __launch_bounds__(64) void dense_hi_select_fuse_kernel(amdr_fuse_para
     const float s1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
     return half ? s1 : s0;
   };
-  auto row_load = [&](long r, tk_v4f (&xv)[D128]) {
+  auto row_load = [&](long r, f32x4 (&xv)[D128]) {
     const float* xr = X + (size_t)r * d + 4 * sl;
 #pragma unroll
-    for (int u = 0; u < D128; ++u) xv[u] = *reinterpret_cast<const tk_v4f*>(xr + 128 * u);
+    for (int u = 0; u < D128; ++u) xv[u] = *reinterpret_cast<const f32x4*>(xr + 128 * u);
   };
-  auto row_fma = [&](const tk_v4f (&xv)[D128]) -> float {
+  auto row_fma = [&](const f32x4 (&xv)[D128]) -> float {
     float acc = 0.f;
 #pragma unroll
     for (int u = 0; u < D128; ++u)
@@ -205,7 +205,7 @@ __global__ __launch_bounds__(64) void dense_hi_select_fuse_kernel(amdr_fuse_para
     return half_sum(acc);
   };
   auto row_dot = [&](long r) -> float {  // every lane of the half returns <Q[q], X[r]> (r: uniform in the half)
-    tk_v4f xv[D128];
+    f32x4 xv[D128];
     row_load(r, xv);
     return row_fma(xv);
   };
@@ -269,7 +269,7 @@ __global__ __launch_bounds__(64) void dense_hi_select_fuse_kernel(amdr_fuse_para
     const int ra0 = __builtin_amdgcn_readlane(my_id, c), ra1 = __builtin_amdgcn_readlane(my_id, 32 + c);
     const int rb0 = __builtin_amdgcn_readlane(my_id, c1), rb1 = __builtin_amdgcn_readlane(my_id, 32 + c1);
     const bool la = c < need, lb = c + 1 < need;
-    tk_v4f xa[D128], xb[D128];
+    f32x4 xa[D128], xb[D128];
     row_load(la ? (long)(half ? ra1 : ra0) : 0, xa);
     row_load(lb ? (long)(half ? rb1 : rb0) : 0, xb);
     const float va = row_fma(xa), vb = row_fma(xb);

@@ -15,6 +15,7 @@
 // (First built on v_mfma_f32_32x32x2_f32; the 16x16 form holds a higher clock, see dense_mfma.hip.)
 // Algorithmic bytes per (query, shard): sum_docs len*128*4; flops 2*32*128*sum len.
 #include "common.hpp"
+#include "lds_ring.hpp"
 #include "maxsim_core.hpp"
 #include "topk.hpp"
 
@@ -26,8 +27,6 @@
 
 namespace amdr {
 
-
-
 // One 32x32 tile: 8 slots x 4 components x (2 x 2 accumulator blocks) = 128 MFMAs of 32 cycles.
 // a[bi][t] / q[bj][t]: the lane's 16-B slot 4t + kq of document-token row 16 bi + i16 / query-token
 // row 16 bj + i16.  Returns, per query-token block bj, the maximum over this lane's 8 document
@@ -37,7 +36,7 @@ namespace amdr {
 // same results, and documents are short (Civil-Code articles: 77 tokens on average, 17 % of the
 // 32-token tile slots were padding).
 template <int NBI>
-__device__ __forceinline__ void ms_tile(const ms4f (&a)[2][8], const ms4f (&q)[2][8], int kq, int remain,
+__device__ __forceinline__ void ms_tile(const f32x4 (&a)[2][8], const f32x4 (&q)[2][8], int kq, int remain,
                                         float (&best)[2]) {
   f32x4 acc[NBI][2];
 #pragma unroll
@@ -87,15 +86,15 @@ __global__ __launch_bounds__(256) void ms_split_store_kernel(const float* __rest
   const long tok = i >> 4;
   const int g = (int)(i & 15);
   float x[8];
-  const ms4f v0 = *reinterpret_cast<const ms4f*>(D + tok * kDim + 8 * g);
-  const ms4f v1 = *reinterpret_cast<const ms4f*>(D + tok * kDim + 8 * g + 4);
+  const f32x4 v0 = *reinterpret_cast<const f32x4*>(D + tok * kDim + 8 * g);
+  const f32x4 v1 = *reinterpret_cast<const f32x4*>(D + tok * kDim + 8 * g + 4);
 #pragma unroll
   for (int j = 0; j < 4; ++j) x[j] = v0[j], x[4 + j] = v1[j];
-  ms8h hi, lo;
+  h8 hi, lo;
   ms_split(x, scale, hi, lo);
-  *reinterpret_cast<ms8h*>(img + tok * 512 + 16 * g) = hi;
-  *reinterpret_cast<ms8h*>(img + tok * 512 + 256 + 16 * g) = lo;
-  *reinterpret_cast<ms8h*>(img_hi + tok * 256 + 16 * g) = hi;
+  *reinterpret_cast<h8*>(img + tok * 512 + 16 * g) = hi;
+  *reinterpret_cast<h8*>(img + tok * 512 + 256 + 16 * g) = lo;
+  *reinterpret_cast<h8*>(img_hi + tok * 256 + 16 * g) = hi;
 }
 
 // largest token L2 norm of the SCALED store (rows x `scale`, the store's power of two: components in [-1, 1], so no
@@ -130,7 +129,7 @@ __global__ __launch_bounds__(256) void ms_absmax_kernel(const float* __restrict_
 // The lane's fragment of a 32-row x 128-float operand in global memory: rows row0 + 16 b + i16
 // (clamped to row_max), 16-B slots 4t + kq.
 __device__ __forceinline__ void ms_load_frag(const float* __restrict__ base, long row0, long row_max, int i16, int kq,
-                                             bool zero, ms4f (&f)[2][8]) {
+                                             bool zero, f32x4 (&f)[2][8]) {
 #pragma unroll
   for (int b = 0; b < 2; ++b) {
     long row = row0 + 16 * b + i16;
@@ -139,8 +138,8 @@ __device__ __forceinline__ void ms_load_frag(const float* __restrict__ base, lon
     const float* p = base + (size_t)row * kDim + kq * 4;
 #pragma unroll
     for (int t = 0; t < 8; ++t) {
-      const ms4f v = *reinterpret_cast<const ms4f*>(p + 16 * t);
-      f[b][t] = out ? ms4f{0.f, 0.f, 0.f, 0.f} : v;
+      const f32x4 v = *reinterpret_cast<const f32x4*>(p + 16 * t);
+      f[b][t] = out ? f32x4{0.f, 0.f, 0.f, 0.f} : v;
     }
   }
 }
@@ -156,14 +155,14 @@ __global__ __launch_bounds__(256) void maxsim_scores_kernel(const float* __restr
   const int qi = blockIdx.y;
   const int i16 = lane & 15, kq = lane >> 4;
 
-  ms4f qf[2][8];  // query tokens past q_len are zero rows
+  f32x4 qf[2][8];  // query tokens past q_len are zero rows
   ms_load_frag(Q + (size_t)qi * q_len * kDim, 0, q_len - 1, i16, kq, true, qf);
 
   const long t_lo = doc_ptr[doc], t_hi = doc_ptr[doc + 1];
   const int len = (int)(t_hi - t_lo);
   float best[2] = {-FLT_MAX, -FLT_MAX};
   for (int tok0 = 0; tok0 < len; tok0 += 32) {
-    ms4f af[2][8];  // rows past the document end are clamped here and masked in ms_tile
+    f32x4 af[2][8];  // rows past the document end are clamped here and masked in ms_tile
     ms_load_frag(D, t_lo + tok0, t_hi - 1, i16, kq, false, af);
     if (len - tok0 <= 16)
       ms_tile<1>(af, qf, kq, len - tok0, best);
@@ -186,7 +185,7 @@ __global__ __launch_bounds__(256) void maxsim_scores_h_kernel(const unsigned cha
   if (doc >= n_docs) return;
   const int qi = blockIdx.y;
   const int r32 = lane & 31, h = lane >> 5;
-  ms8h qh[8], ql[8];
+  h8 qh[8], ql[8];
   float unscale;
   ms_load_query_h(Q + (size_t)qi * q_len * kDim, q_len, true, r32, h, qh, ql, unscale);
   unscale *= unscale_d;
@@ -210,19 +209,14 @@ __global__ __launch_bounds__(256) void maxsim_scores_h_kernel(const unsigned cha
 constexpr int kMsQ = 8;     // queries (waves) per block
 constexpr int kMsDocs = 8;  // documents per block
 
-// LDS tile: token row j (0..31) at byte j*512, its 16-B slot s (0..31) at s ^ (j & 15).  A
-// ds_read_b128 lane group holds 16 distinct rows, eight reading slot 4t + kq and eight
-// 4t + (kq ^ 1): the XOR maps those two sets onto disjoint bank quads (conflict-free); a
-// staging write of one row (32 consecutive threads) covers the row's 512 B.
-__device__ __forceinline__ int ms_tile_off(int row, int slot) { return row * 512 + ((slot ^ (row & 15)) << 4); }
-
+// LDS tile: token row j (0..31) at byte j*512, swizzled by tile_off<512> (a ds_read_b128 lane group reads slots 4t + kq
+// and 4t + (kq ^ 1) of 16 distinct rows); a staging write of one row (32 consecutive threads) covers the row's 512 B.
 __global__ __launch_bounds__(kMsQ * 64) void maxsim_scores_blocked_kernel(const float* __restrict__ D,
                                                                            const long long* __restrict__ doc_ptr,
                                                                            long n_docs, const float* __restrict__ Q,
                                                                            int nq, int q_len,
                                                                            float* __restrict__ scores /*[nq, n_docs]*/) {
   __shared__ __attribute__((aligned(16))) unsigned char tile[2][32 * 512];
-  typedef float v4f __attribute__((ext_vector_type(4)));
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int i16 = lane & 15, kq = lane >> 4;
   const int qi = blockIdx.x * kMsQ + wave;
@@ -231,14 +225,14 @@ __global__ __launch_bounds__(kMsQ * 64) void maxsim_scores_blocked_kernel(const 
   long d1 = d0 + kMsDocs;
   if (d1 > n_docs) d1 = n_docs;
 
-  ms4f qf[2][8];
+  f32x4 qf[2][8];
   if (live) {
     ms_load_frag(Q + (size_t)qi * q_len * kDim, 0, q_len - 1, i16, kq, true, qf);
   } else {
 #pragma unroll
     for (int b = 0; b < 2; ++b)
 #pragma unroll
-      for (int t = 0; t < 8; ++t) qf[b][t] = ms4f{0.f, 0.f, 0.f, 0.f};
+      for (int t = 0; t < 8; ++t) qf[b][t] = f32x4{0.f, 0.f, 0.f, 0.f};
   }
 
   // loader role: two 16-B pieces per thread and tile (elements tid and tid + 512 of 1024)
@@ -247,16 +241,16 @@ __global__ __launch_bounds__(kMsQ * 64) void maxsim_scores_blocked_kernel(const 
   long t_lo = doc_ptr[doc];
   int len = (int)(doc_ptr[doc + 1] - t_lo);
   int tok0 = 0;
-  v4f g[2];
+  f32x4 g[2];
 #define AMDR_MS_LOAD(TLO, LEN, TOK0)                                                                   \
   _Pragma("unroll") for (int u = 0; u < 2; ++u) {                                                      \
     int j_ = (TOK0) + lrow0 + 16 * u;                                                                  \
     if (j_ >= (LEN)) j_ = (LEN)-1; /* rows past the document end are masked after the MFMAs */         \
-    g[u] = *reinterpret_cast<const v4f*>(D + (size_t)((TLO) + j_) * kDim + lslot * 4);                 \
+    g[u] = *reinterpret_cast<const f32x4*>(D + (size_t)((TLO) + j_) * kDim + lslot * 4);                 \
   }
 #define AMDR_MS_STAGE(BUF)                                                                             \
   _Pragma("unroll") for (int u = 0; u < 2; ++u)                                                        \
-      *reinterpret_cast<v4f*>(tile[BUF] + ms_tile_off(lrow0 + 16 * u, lslot)) = g[u];
+      *reinterpret_cast<f32x4*>(tile[BUF] + tile_off<512>(lrow0 + 16 * u, lslot)) = g[u];
   AMDR_MS_LOAD(t_lo, len, tok0)
   AMDR_MS_STAGE(0)
   __syncthreads();
@@ -279,18 +273,18 @@ __global__ __launch_bounds__(kMsQ * 64) void maxsim_scores_blocked_kernel(const 
     const bool has_next = ndoc < d1;
     if (has_next) { AMDR_MS_LOAD(nt_lo, nlen, ntok) }
 
-    ms4f af[2][8];
+    f32x4 af[2][8];
     if (len - tok0 <= 16) {  // wave-uniform: the tail of a document fits one 16-token row block
 #pragma unroll
       for (int t = 0; t < 8; ++t)
-        af[0][t] = *reinterpret_cast<const ms4f*>(tile[buf] + ms_tile_off(i16, 4 * t + kq));
+        af[0][t] = *reinterpret_cast<const f32x4*>(tile[buf] + tile_off<512>(i16, 4 * t + kq));
       ms_tile<1>(af, qf, kq, len - tok0, best);
     } else {
 #pragma unroll
       for (int b = 0; b < 2; ++b)
 #pragma unroll
         for (int t = 0; t < 8; ++t)
-          af[b][t] = *reinterpret_cast<const ms4f*>(tile[buf] + ms_tile_off(16 * b + i16, 4 * t + kq));
+          af[b][t] = *reinterpret_cast<const f32x4*>(tile[buf] + tile_off<512>(16 * b + i16, 4 * t + kq));
       ms_tile<2>(af, qf, kq, len - tok0, best);
     }
     if (ntok == 0) {  // last tile of this document
@@ -314,42 +308,14 @@ __global__ __launch_bounds__(kMsQ * 64) void maxsim_scores_blocked_kernel(const 
 // ---- ring form of the blocked kernel (split-fp16 tiles) ---------------------------------------------------------
 // A wave's 24 MFMAs of a split-fp16 tile take 768 cycles — less than one trip to L2 / the Infinity Cache — so the
 // one-tile-ahead, register-staged pipeline of the kernel above cannot feed them.  Here the document tiles go through
-// a RING of NBUF 16-KiB LDS stages filled by LDS-DMA (global_load_lds_dwordx4: no staging registers, no ds_write),
-// NBUF - 1 tiles ahead of the one being multiplied:
-//   step s:  s_waitcnt lgkmcnt(0) vmcnt(2 x tiles in flight behind tile s)   this wave's pieces of tile s have landed
-//            s_barrier                                                       ... everybody's; tile s - 1 has been read
-//            DMA of tile s + NBUF - 1 into the stage of tile s - 1
-//            ds_reads of tile s; 24 MFMAs; per-lane maxima; (last tile of a document) the score
-// One raw barrier per tile and no vmcnt(0) in the loop (a __syncthreads() would drain the DMAs in flight); the waits
-// are the s_waitcnt BUILTIN, not inline asm: hipcc's own wait-count pass must see them, or it re-waits in front of
-// the MFMAs.  A DMA lands lane-linear (stage base + lane * 16): the XOR swizzle that makes the ds_read_b128 fragment
-// reads conflict-free is applied to the per-lane SOURCE address (dense_panel.hip does the same).  128 VGPRs and
+// the LDS-DMA ring of lds_ring.hpp (protocol, waits and their reasons: there) with NBUF 16-KiB stages.  128 VGPRs and
 // NBUF x 16 KiB of LDS: two blocks = four waves per SIMD per CU, so one block's barrier / DMA wait runs under the
 // other's MFMAs.  Tried on the way (same-box A/B, scripts/ab_maxsim.py): 2 / 3 / 4 / 6 stages 2.55 / 2.31 / 2.24 /
 // 2.44 ms per 1 168 UCC-en queries; 8 / 16 / 32 / 64 documents per block 2.27 / 2.23 / 2.24 / 2.37; a second fragment
 // register set filled one tile ahead (254 VGPRs) +- 0.
-//
-// The pieces of the ring that its three kernels share.  A stage is 16 pieces of 1 KiB, one piece = one DMA request of a
-// wave (64 lanes x 16 B) = 1024 / ROWB whole token rows of ROWB bytes (512: the [hi | lo] image, 256: the hi-only image).
-// Per-lane source offsets of pieces piece0 .. piece0 + PIECES - 1 inside a tile: lane l of a piece: its row l / (ROWB / 16),
-// PHYSICAL slot l % (ROWB / 16), which holds logical slot ^ (row & 15).  Rows past the end of a document read on into the
-// next document's tokens (the images are padded by one tile at their end) and are masked after the MFMAs.
-template <int PIECES, int ROWB>
-__device__ __forceinline__ void ms_piece_offs(int piece0, int lane, long (&poff)[PIECES]) {
-  constexpr int kSlots = ROWB / 16, kRows = 1024 / ROWB;
-#pragma unroll
-  for (int u = 0; u < PIECES; ++u) {
-    const int prow = kRows * (piece0 + u) + lane / kSlots;
-    poff[u] = (long)prow * ROWB + (((lane & (kSlots - 1)) ^ (prow & 15)) << 4);
-  }
-}
-// this wave's pieces of the tile at `src` (wave-uniform) into `dst` = the stage + piece0 KiB
-template <int PIECES>
-__device__ __forceinline__ void ms_issue_tile(const unsigned char* src, const long (&poff)[PIECES], unsigned char* dst) {
-#pragma unroll
-  for (int u = 0; u < PIECES; ++u)
-    __builtin_amdgcn_global_load_lds(AMDR_MS_GPTR(src + poff[u]), AMDR_MS_LPTR(dst + u * 1024), 16, 0, 0);
-}
+// A stage is 16 pieces of 1 KiB (piece_offs, tile_swizzle.hpp) of whole token rows (512 B: the [hi | lo] image, 256: the
+// hi-only image).  Rows past the end of a document read on into the next document's tokens (the images are padded by
+// one tile at their end) and are masked after the MFMAs.
 // A position in a block's tile sequence (wave-uniform): tiles of TOK tokens of documents d0 .. d1 - 1.
 template <int TOK>
 struct MsDocCursor {
@@ -373,30 +339,6 @@ struct MsDocCursor {
     }
   }
 };
-// The waits.  simm16 on gfx9: vmcnt [3:0] (+ [15:14]), expcnt [6:4] (7 = none), lgkmcnt [11:8] (15 = none).
-constexpr int ms_vmcnt_imm(int n) { return 0x0F70 | (n & 15) | ((n >> 4) << 14); }
-constexpr int kMsLgkm0 = 0xC07F;  // lgkmcnt(0) alone
-// This wave's pieces of a tile have landed once at most PIECES x (tiles issued behind it) requests are outstanding:
-// vmcnt(PIECES x min(behind, CAP)) (fewer than the truth only makes the wait stricter; other loads issued meanwhile
-// likewise).  lgkmcnt(0) on every path as ONE unconditional instruction (inside the branches the wait-count pass still
-// re-waited in front of the MFMAs).
-template <int PIECES, int CAP, int B = CAP>
-__device__ __forceinline__ void ms_wait_vm(int behind) {
-  static_assert(PIECES * CAP < 64, "vmcnt has 6 bits");
-  if constexpr (B == 0) {
-    __builtin_amdgcn_s_waitcnt(ms_vmcnt_imm(0));
-  } else {
-    if (B == CAP ? behind >= B : behind == B)
-      __builtin_amdgcn_s_waitcnt(ms_vmcnt_imm(PIECES * B));
-    else
-      ms_wait_vm<PIECES, CAP, B - 1>(behind);
-  }
-}
-template <int PIECES, int CAP>
-__device__ __forceinline__ void ms_wait_tile(int behind) {
-  __builtin_amdgcn_s_waitcnt(kMsLgkm0);
-  ms_wait_vm<PIECES, CAP>(behind);
-}
 
 template <int NBUF>
 __global__ __launch_bounds__(kMsQ * 64) __attribute__((amdgpu_waves_per_eu(4, 4))) void maxsim_scores_ring_kernel(const unsigned char* __restrict__ img,
@@ -416,19 +358,19 @@ __global__ __launch_bounds__(kMsQ * 64) __attribute__((amdgpu_waves_per_eu(4, 4)
   long d1 = d0 + docs_per_block;
   if (d1 > n_docs) d1 = n_docs;
 
-  ms8h qh[8], ql[8];
+  h8 qh[8], ql[8];
   float unscale;
   ms_load_query_h(Q + (size_t)(live ? qi : 0) * q_len * kDim, q_len, live, r32, h, qh, ql, unscale);
   unscale *= unscale_d;
 
   // DMA role: pieces 2 wave, 2 wave + 1 of a tile (two token rows of 512 B each)
   long poff[2];
-  ms_piece_offs<2, 512>(2 * wave, lane, poff);
+  piece_offs<2, 512>(2 * wave, lane, poff);
   // fragment read addresses: row r32, chunk 2 s + h (the lo part sits 256 B behind the hi part: slots c and 16 + c
   // differ in bit 4, which the XOR with row & 15 leaves alone)
   int foff[8];
 #pragma unroll
-  for (int st = 0; st < 8; ++st) foff[st] = ms_tile_off(r32, 2 * st + h);
+  for (int st = 0; st < 8; ++st) foff[st] = tile_off<512>(r32, 2 * st + h);
 
   MsDocCursor<32> prod, cur;
   prod.first(doc_ptr, d0);
@@ -436,7 +378,7 @@ __global__ __launch_bounds__(kMsQ * 64) __attribute__((amdgpu_waves_per_eu(4, 4)
   int issued = 0, done = 0;
   auto produce = [&]() {
     if (prod.doc >= d1) return;
-    ms_issue_tile<2>(img + (size_t)(prod.t_lo + prod.tok0) * 512, poff, ring + (issued % NBUF) * kStage + 2 * wave * 1024);
+    ring_issue_tile<2>(img + (size_t)(prod.t_lo + prod.tok0) * 512, poff, ring + (issued % NBUF) * kStage + 2 * wave * 1024);
     ++issued;
     prod.advance(doc_ptr, d1);
   };
@@ -444,17 +386,17 @@ __global__ __launch_bounds__(kMsQ * 64) __attribute__((amdgpu_waves_per_eu(4, 4)
   for (int i = 0; i < NBUF - 1; ++i) produce();
   float best = -FLT_MAX;
   while (cur.doc < d1) {
-    ms_wait_tile<2, NBUF - 1>(issued - done - 1);  // this wave's pieces of tile `done`
+    wait_tile<2, NBUF - 1>(issued - done - 1);  // this wave's pieces of tile `done`
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
     produce();  // into the stage of tile done - 1
     const unsigned char* tile = ring + (done % NBUF) * kStage;
-    ms8h ah[8], al[8];
+    h8 ah[8], al[8];
 #pragma unroll
     for (int st = 0; st < 8; ++st) {
       const unsigned char* fp = tile + foff[st];
-      ah[st] = *reinterpret_cast<const ms8h*>(fp);
-      al[st] = *reinterpret_cast<const ms8h*>(fp + 256);
+      ah[st] = *reinterpret_cast<const h8*>(fp);
+      al[st] = *reinterpret_cast<const h8*>(fp + 256);
     }
     const int remain = cur.len - cur.tok0;
     ms_tile_h(ah, al, qh, ql, h, remain, best);
@@ -492,7 +434,6 @@ __global__ __launch_bounds__(kMsQ * 64) __attribute__((amdgpu_waves_per_eu(4, 4)
 // `cap` candidates (mass near-ties) re-scores every document instead (maxsim_overflow_kernel).
 // Pass 1: a ring kernel like the one above with 64-token tiles of the hi-only image (16-KiB stages again, half the
 // barriers per document), no fma in the epilogue.
-__device__ __forceinline__ int ms_hi_off(int row, int slot) { return row * 256 + ((slot ^ (row & 15)) << 4); }
 
 // Pass 1, two queries per wave.  PMC / arithmetic on the first form of pass 1 (one query per wave, 16 MFMAs and 16
 // ds_read_b128 per tile; retired): a wave reads the whole 16-KiB tile from LDS for 16 MFMAs of 32 cycles — 16 waves per CU x 16 KiB per 2 048 pipe cycles = 125 B per clock, the LDS's whole bandwidth: it
@@ -502,10 +443,10 @@ __device__ __forceinline__ int ms_hi_off(int row, int slot) { return row * 256 +
 constexpr int kMsQ2 = 4;  // waves per block; 2 queries each
 
 __device__ __forceinline__ void ms_load_query_img_hi(const unsigned char* __restrict__ img_q, int qi, int r32, int h,
-                                                     ms8h (&qh)[8]) {
+                                                     h8 (&qh)[8]) {
   const unsigned char* p = img_q + ((size_t)qi * 32 + r32) * 512 + 16 * h;
 #pragma unroll
-  for (int st = 0; st < 8; ++st) qh[st] = *reinterpret_cast<const ms8h*>(p + 32 * st);
+  for (int st = 0; st < 8; ++st) qh[st] = *reinterpret_cast<const h8*>(p + 32 * st);
 }
 
 __device__ __forceinline__ float ms_max3(float a, float b, float c) {  // max(a, b, c) in one instruction (no NaNs reach it)
@@ -533,7 +474,7 @@ __global__ __launch_bounds__(kMsQ2 * 64) __attribute__((amdgpu_waves_per_eu(3, N
 
   // the fragments as maxsim_split_queries_kernel left them (a query is scored by n_docs / docs_per_block blocks: splitting
   // it in each of them was 10-20 % of this kernel's vector instructions); a dead wave takes query 0's
-  ms8h qha[8], qhb[8];
+  h8 qha[8], qhb[8];
   ms_load_query_img_hi(img_q, live_a ? qa : 0, r32, h, qha);
   ms_load_query_img_hi(img_q, live_b ? qb : 0, r32, h, qhb);
   const float unscale_a = unscale_q[live_a ? qa : 0] * unscale_d;
@@ -541,10 +482,10 @@ __global__ __launch_bounds__(kMsQ2 * 64) __attribute__((amdgpu_waves_per_eu(3, N
 
   // DMA role: pieces 4 wave .. 4 wave + 3 of the tile's 16 (1 KiB = 4 token rows of 256 B each)
   long poff[4];
-  ms_piece_offs<4, 256>(4 * wave, lane, poff);
+  piece_offs<4, 256>(4 * wave, lane, poff);
   int foff[8];
 #pragma unroll
-  for (int st = 0; st < 8; ++st) foff[st] = ms_hi_off(r32, 2 * st + h);
+  for (int st = 0; st < 8; ++st) foff[st] = tile_off<256>(r32, 2 * st + h);
 
   MsDocCursor<64> prod, cur;
   prod.first(doc_ptr, d0);
@@ -552,7 +493,7 @@ __global__ __launch_bounds__(kMsQ2 * 64) __attribute__((amdgpu_waves_per_eu(3, N
   int issued = 0, done = 0;
   auto produce = [&]() {
     if (prod.doc >= d1) return;
-    ms_issue_tile<4>(img_hi + (size_t)(prod.t_lo + prod.tok0) * 256, poff, ring + (issued % NBUF) * kStage + 4 * wave * 1024);
+    ring_issue_tile<4>(img_hi + (size_t)(prod.t_lo + prod.tok0) * 256, poff, ring + (issued % NBUF) * kStage + 4 * wave * 1024);
     ++issued;
     prod.advance(doc_ptr, d1);
   };
@@ -560,7 +501,7 @@ __global__ __launch_bounds__(kMsQ2 * 64) __attribute__((amdgpu_waves_per_eu(3, N
   for (int i = 0; i < NBUF - 1; ++i) produce();
   float best_a = -FLT_MAX, best_b = -FLT_MAX;
   while (cur.doc < d1) {
-    ms_wait_tile<4, NBUF - 1>(issued - done - 1);  // this wave's 4 pieces of tile `done`
+    wait_tile<4, NBUF - 1>(issued - done - 1);  // this wave's 4 pieces of tile `done`
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
     produce();  // into the stage of tile done - 1
@@ -569,9 +510,9 @@ __global__ __launch_bounds__(kMsQ2 * 64) __attribute__((amdgpu_waves_per_eu(3, N
 #pragma unroll
     for (int blk = 0; blk < 2; ++blk) {
       if (blk == 1 && remain <= 32) break;  // wave-uniform: the second 32-token row block holds no token of this document
-      ms8h a[8];
+      h8 a[8];
 #pragma unroll
-      for (int st = 0; st < 8; ++st) a[st] = *reinterpret_cast<const ms8h*>(tile + blk * (32 * 256) + foff[st]);
+      for (int st = 0; st < 8; ++st) a[st] = *reinterpret_cast<const h8*>(tile + blk * (32 * 256) + foff[st]);
       f32x16 ca, cb;
 #pragma unroll
       for (int j = 0; j < 16; ++j) ca[j] = cb[j] = 0.f;
@@ -584,7 +525,7 @@ __global__ __launch_bounds__(kMsQ2 * 64) __attribute__((amdgpu_waves_per_eu(3, N
         asm volatile("" ::: "memory");
 #pragma unroll
         for (int j = 0; j < 16; ++j)
-          if (32 * blk + (j & 3) + 8 * (j >> 2) + 4 * h >= remain) ca[j] = cb[j] = -FLT_MAX;
+          if (32 * blk + mfma32_row(j, h) >= remain) ca[j] = cb[j] = -FLT_MAX;
       }
       // 16 values -> 1 per query and row block as EIGHT v_max3_f32 (hipcc fused only a quarter of the fmaxf pairs: 56
       // v_max per 32 MFMAs; the pass issued ~5 other vector instructions per MFMA with its matrix pipe busy half the
@@ -634,8 +575,8 @@ __device__ __forceinline__ void ms_split_query_wave(const float* __restrict__ Qq
   for (int it = 0; it < 8; ++it) {
     const int g = lane + 64 * it, row = g >> 4, grp = g & 15;
     if (row < q_len) {
-      const ms4f v0 = *reinterpret_cast<const ms4f*>(Qq + (size_t)row * kDim + 8 * grp);
-      const ms4f v1 = *reinterpret_cast<const ms4f*>(Qq + (size_t)row * kDim + 8 * grp + 4);
+      const f32x4 v0 = *reinterpret_cast<const f32x4*>(Qq + (size_t)row * kDim + 8 * grp);
+      const f32x4 v1 = *reinterpret_cast<const f32x4*>(Qq + (size_t)row * kDim + 8 * grp + 4);
 #pragma unroll
       for (int j = 0; j < 4; ++j) x[it][j] = v0[j], x[it][4 + j] = v1[j];
     } else {
@@ -647,9 +588,8 @@ __device__ __forceinline__ void ms_split_query_wave(const float* __restrict__ Qq
   }
 #pragma unroll
   for (int sft = 1; sft < 64; sft <<= 1) m = fmaxf(m, __shfl_xor(m, sft));
-  int e = 0;
-  if (m > 0.f && m <= FLT_MAX) (void)frexpf(m, &e);
-  const float sc = ldexpf(1.f, -e);
+  const int e = pow2_exp(m);
+  const float sc = pow2_scale(e);
 #pragma unroll
   for (int it = 0; it < 8; ++it) {
     float ss = 0.f;
@@ -665,17 +605,17 @@ __device__ __forceinline__ void ms_split_query_wave(const float* __restrict__ Qq
   nsum += __shfl_xor(nsum, 16);  // the four rows of a step sit in the four 16-lane groups
   nsum += __shfl_xor(nsum, 32);
   if (lane == 0) {
-    *unscale = ldexpf(1.f, e);
+    *unscale = pow2_scale(-e);
     *norm_sum = nsum;
   }
 #pragma unroll
   for (int it = 0; it < 8; ++it) {
     const int g = lane + 64 * it, row = g >> 4, grp = g & 15;
-    ms8h hi, lo;
+    h8 hi, lo;
     ms_split(x[it], sc, hi, lo);
     unsigned char* dst = img + (size_t)row * 512 + 16 * grp;
-    *reinterpret_cast<ms8h*>(dst) = hi;
-    *reinterpret_cast<ms8h*>(dst + 256) = lo;
+    *reinterpret_cast<h8*>(dst) = hi;
+    *reinterpret_cast<h8*>(dst + 256) = lo;
   }
 }
 
@@ -768,29 +708,29 @@ __global__ __launch_bounds__(64) void maxsim_select_kernel(const float* __restri
 // pieces of 32 different rows per load instruction — 15 k candidate pairs per launch then moved ~8x their bytes through
 // the L1s and pass 2 took as long as pass 1 (0.98 ms).  Same tile function, same operands: the same bits.
 __device__ __forceinline__ float ms_exact_doc_lds(const unsigned char* __restrict__ img,
-                                                  const long long* __restrict__ doc_ptr, long doc, const ms8h (&qh)[8],
-                                                  const ms8h (&ql)[8], int lane, int q_len, float unscale,
+                                                  const long long* __restrict__ doc_ptr, long doc, const h8 (&qh)[8],
+                                                  const h8 (&ql)[8], int lane, int q_len, float unscale,
                                                   unsigned char* stage /* this wave's 16 KiB */) {
   const int r32 = lane & 31, h = lane >> 5;
   const long t_lo = doc_ptr[doc];
   const int len = (int)(doc_ptr[doc + 1] - t_lo);
   long poff[16];  // the whole tile is this wave's
-  ms_piece_offs<16, 512>(0, lane, poff);
+  piece_offs<16, 512>(0, lane, poff);
   int foff[8];
 #pragma unroll
-  for (int st = 0; st < 8; ++st) foff[st] = ms_tile_off(r32, 2 * st + h);
+  for (int st = 0; st < 8; ++st) foff[st] = tile_off<512>(r32, 2 * st + h);
   float best = -FLT_MAX;
   for (int tok0 = 0; tok0 < len; tok0 += 32) {
-    __builtin_amdgcn_s_waitcnt(kMsLgkm0);  // the fragment reads of the previous tile are done: the stage may be refilled
-    ms_issue_tile<16>(img + (size_t)(t_lo + tok0) * 512, poff, stage);
-    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): the tile has landed (the other waves of the CU cover the wait)
+    wait_lgkm0();  // the fragment reads of the previous tile are done: the stage may be refilled
+    ring_issue_tile<16>(img + (size_t)(t_lo + tok0) * 512, poff, stage);
+    wait_vm0();  // the tile has landed (the other waves of the CU cover the wait)
     asm volatile("" ::: "memory");
-    ms8h ah[8], al[8];
+    h8 ah[8], al[8];
 #pragma unroll
     for (int st = 0; st < 8; ++st) {
       const unsigned char* fp = stage + foff[st];
-      ah[st] = *reinterpret_cast<const ms8h*>(fp);
-      al[st] = *reinterpret_cast<const ms8h*>(fp + 256);
+      ah[st] = *reinterpret_cast<const h8*>(fp);
+      al[st] = *reinterpret_cast<const h8*>(fp + 256);
     }
     ms_tile_h(ah, al, qh, ql, h, len - tok0, best);
   }
@@ -798,12 +738,12 @@ __device__ __forceinline__ float ms_exact_doc_lds(const unsigned char* __restric
 }
 
 __device__ __forceinline__ void ms_load_query_img(const unsigned char* __restrict__ img_q, int qi, int r32, int h,
-                                                  ms8h (&qh)[8], ms8h (&ql)[8]) {
+                                                  h8 (&qh)[8], h8 (&ql)[8]) {
   const unsigned char* p = img_q + ((size_t)qi * 32 + r32) * 512 + 16 * h;
 #pragma unroll
   for (int st = 0; st < 8; ++st) {
-    qh[st] = *reinterpret_cast<const ms8h*>(p + 32 * st);
-    ql[st] = *reinterpret_cast<const ms8h*>(p + 256 + 32 * st);
+    qh[st] = *reinterpret_cast<const h8*>(p + 32 * st);
+    ql[st] = *reinterpret_cast<const h8*>(p + 256 + 32 * st);
   }
 }
 
@@ -876,10 +816,10 @@ __global__ __launch_bounds__(kMsQ * 64) __attribute__((amdgpu_waves_per_eu(4, 4)
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int r32 = lane & 31, h = lane >> 5;
   long poff[2];  // DMA role of this wave: pieces 2 wave, 2 wave + 1 of a tile (maxsim_scores_ring_kernel)
-  ms_piece_offs<2, 512>(2 * wave, lane, poff);
+  piece_offs<2, 512>(2 * wave, lane, poff);
   int foff[8];
 #pragma unroll
-  for (int st = 0; st < 8; ++st) foff[st] = ms_tile_off(r32, 2 * st + h);
+  for (int st = 0; st < 8; ++st) foff[st] = tile_off<512>(r32, 2 * st + h);
   const int items = *n_items;
   const int stride = (int)gridDim.x;
   auto desc_of = [&](int it) { return it < items ? item_tab[it] : MsItem{0, 0, 0, 0, 0, 0}; };
@@ -900,7 +840,7 @@ __global__ __launch_bounds__(kMsQ * 64) __attribute__((amdgpu_waves_per_eu(4, 4)
       p_tile = 0;
     }
     if (p_item >= items) return;
-    ms_issue_tile<2>(img + (size_t)(p_cur.t_lo + 32 * p_tile) * 512, poff, ring + (issued % NBUF) * kStage + 2 * wave * 1024);
+    ring_issue_tile<2>(img + (size_t)(p_cur.t_lo + 32 * p_tile) * 512, poff, ring + (issued % NBUF) * kStage + 2 * wave * 1024);
     ++issued;
     ++p_tile;
   };
@@ -909,30 +849,30 @@ __global__ __launch_bounds__(kMsQ * 64) __attribute__((amdgpu_waves_per_eu(4, 4)
   for (int item = blockIdx.x; item < items; item += stride) {
     const bool live = wave < c_cur.cnt;
     const int qi = qi_c, len = c_cur.len, ntiles = (c_cur.len + 31) >> 5;
-    ms8h qh[8], ql[8];
+    h8 qh[8], ql[8];
     ms_load_query_img(img_q, qi, r32, h, qh, ql);  // (a dead wave reads query 0's: its result is never stored)
     const float unscale = unscale_q[qi] * unscale_d;
     // vmcnt counts in issue order: with the fragments (the youngest requests) in, every DMA issued so far has landed
-    __builtin_amdgcn_s_waitcnt(0x0F70);
+    wait_vm0();
     asm volatile("" ::: "memory");
     const int safe = issued;  // tiles below this index need no further wait by this wave
     const MsItem nn = desc_of(item + 2 * stride);
     const int qi_n = wave < c_nxt.cnt ? dlist[(size_t)c_nxt.doc * nq + c_nxt.p0 + wave] : 0;
     float best = -FLT_MAX;
     for (int t = 0; t < ntiles; ++t) {
-      __builtin_amdgcn_s_waitcnt(kMsLgkm0);  // lgkmcnt(0): the fragment reads of the previous tile
-      if (done >= safe) ms_wait_vm<2, 3>(issued - done - 1);  // this wave's pieces of tile `done`
+      wait_lgkm0();  // the fragment reads of the previous tile
+      if (done >= safe) wait_vm<2, 3>(issued - done - 1);  // this wave's pieces of tile `done`
       __builtin_amdgcn_s_barrier();  // everybody's pieces of tile `done` are in; tile done - 1 has been read by all
       asm volatile("" ::: "memory");
       produce();                     // into the stage of tile done - 1
       if (live) {  // wave-uniform: a wave without a query of this item (a document's last, partly filled item) only moves tiles
         const unsigned char* tile = ring + (done % NBUF) * kStage;
-        ms8h ah[8], al[8];
+        h8 ah[8], al[8];
 #pragma unroll
         for (int st = 0; st < 8; ++st) {
           const unsigned char* fp = tile + foff[st];
-          ah[st] = *reinterpret_cast<const ms8h*>(fp);
-          al[st] = *reinterpret_cast<const ms8h*>(fp + 256);
+          ah[st] = *reinterpret_cast<const h8*>(fp);
+          al[st] = *reinterpret_cast<const h8*>(fp + 256);
         }
         ms_tile_h(ah, al, qh, ql, h, len - 32 * t, best);
       }
@@ -956,7 +896,7 @@ __global__ __launch_bounds__(256) void maxsim_overflow_kernel(const unsigned cha
   if (!overflow[q]) return;
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  ms8h qh[8], ql[8];
+  h8 qh[8], ql[8];
   float unscale;
   ms_load_query_h(Q + (size_t)q * q_len * kDim, q_len, true, lane & 31, lane >> 5, qh, ql, unscale);
   for (long doc = wave; doc < n_docs; doc += kMsWaves) {
@@ -1296,9 +1236,7 @@ int amdr_maxsim_create(const float* D_host, const int64_t* doc_ptr, int64_t n_do
   if (e == hipSuccess && mbits < 0x7f800000u) {
     float m;
     memcpy(&m, &mbits, sizeof(float));
-    int ex = 0;
-    if (m > 0.f) (void)frexpf(m, &ex);
-    h->d_scale = ldexpf(1.f, -ex);
+    h->d_scale = pow2_scale(pow2_exp(m));
     e = hipMalloc((void**)&h->img, (size_t)(nt + 32) * 512);  // + one tile: the last tile of the last document reads on
     if (e == hipSuccess) e = hipMemset(h->img + (size_t)nt * 512, 0, (size_t)32 * 512);
     if (e == hipSuccess) e = hipMalloc((void**)&h->img_hi, (size_t)(nt + 64) * 256);  // + one 64-token tile

@@ -3,15 +3,13 @@
 // search of scope.hip: the same instruction sequence, hence the same bits.
 #pragma once
 #include "common.hpp"
+#include "tile_swizzle.hpp"
 #include "topk.hpp"
 
 #include <cfloat>
 #include <cmath>
 
 namespace amdr {
-
-#define AMDR_MS_GPTR(p) ((const __attribute__((address_space(1))) void*)(p))
-#define AMDR_MS_LPTR(p) ((__attribute__((address_space(3))) void*)(p))
 
 constexpr int kMsWaves = 4;
 constexpr int kDim = AMDR_MAXSIM_DIM;  // 128
@@ -31,9 +29,6 @@ __device__ __forceinline__ float ms_wave_sum(float v) {  // total in lane 63
   return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
 }
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float ms4f __attribute__((ext_vector_type(4)));
-
 // ---- split-fp16 form ("f16x3") -------------------------------------------------------------------------------
 // The same tile on the fp16 matrix instructions (v_mfma_f32_32x32x16_f16: 16x the rate of the fp32-input form).
 // fp16 alone (11 significant bits) would miss the 1e-4 bar, so every operand x (scaled by a power of two into
@@ -52,7 +47,7 @@ typedef float ms4f __attribute__((ext_vector_type(4)));
 // and are undone exactly on the per-token maxima.  AMDR_MAXSIM_F16X3=0 pins the fp32-input form.
 //
 // Shape: one 32x32x16 accumulator (16 registers) has the query token on the lane (l & 31) and 16 document tokens in
-// the lane's registers: rows (reg & 3) + 8 (reg >> 2) + 4 (l >> 5).
+// the lane's registers: rows mfma32_row(reg, l >> 5) (tile_swizzle.hpp).
 //   A (32 doc tokens x 16):   lane (r = l & 31, h = l >> 5) holds row r, k = 16 s + 8 h .. + 7 = 16-B chunk 2 s + h
 //   B (16 x 32 query tokens): the same of query-token row r.
 // An MFMA holds its SIMD's vector issue for 8 cycles whatever its shape (MI355X_MICROARCH.md): 8 of 16 for a
@@ -63,11 +58,9 @@ typedef float ms4f __attribute__((ext_vector_type(4)));
 // the chip holds 1.70 GHz (GRBM_GUI_ACTIVE; 2.11 GHz under the fp32-input dense kernel), the matrix pipe is busy 67 %
 // of those cycles (77 % with DMA and barriers taken out in a timing-only build, which runs 2.10 ms); at the held
 // clock the MFMAs alone need 1.63 ms.
-typedef _Float16 ms8h __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 constexpr float kMsLoScale = 2048.f, kMsLoInv = 1.f / 2048.f;
 
-__device__ __forceinline__ void ms_split(const float (&x)[8], float s, ms8h& hi, ms8h& lo) {
+__device__ __forceinline__ void ms_split(const float (&x)[8], float s, h8& hi, h8& lo) {
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
     const float v = x[j] * s;
@@ -80,17 +73,17 @@ __device__ __forceinline__ void ms_split(const float (&x)[8], float s, ms8h& hi,
 // A query's fragments, split (lane (r, h): token row r, chunks 2 s + h); rows past q_len are zero; the wave's
 // power-of-two scale comes back in `unscale` (1 / scale, exact).
 __device__ __forceinline__ void ms_load_query_h(const float* __restrict__ Qq, int q_len, bool live, int r, int h,
-                                                ms8h (&qh)[8], ms8h (&ql)[8], float& unscale) {
+                                                h8 (&qh)[8], h8 (&ql)[8], float& unscale) {
   float x[8][8];
   float m = 0.f;
   const bool out = !live || r >= q_len;
   const float* p = Qq + (size_t)(r < q_len ? r : q_len - 1) * kDim + 8 * h;
 #pragma unroll
   for (int st = 0; st < 8; ++st) {
-    ms4f v0 = ms4f{0.f, 0.f, 0.f, 0.f}, v1 = v0;
+    f32x4 v0 = f32x4{0.f, 0.f, 0.f, 0.f}, v1 = v0;
     if (live) {
-      v0 = *reinterpret_cast<const ms4f*>(p + 16 * st);
-      v1 = *reinterpret_cast<const ms4f*>(p + 16 * st + 4);
+      v0 = *reinterpret_cast<const f32x4*>(p + 16 * st);
+      v1 = *reinterpret_cast<const f32x4*>(p + 16 * st + 4);
     }
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -101,10 +94,9 @@ __device__ __forceinline__ void ms_load_query_h(const float* __restrict__ Qq, in
   }
 #pragma unroll
   for (int sft = 1; sft < 64; sft <<= 1) m = fmaxf(m, __shfl_xor(m, sft));
-  int e = 0;
-  if (m > 0.f && m <= FLT_MAX) (void)frexpf(m, &e);  // m = f * 2^e, f in [0.5, 1)
-  const float sc = ldexpf(1.f, -e);
-  unscale = ldexpf(1.f, e);
+  const int e = pow2_exp(m);  // m = f * 2^e, f in [0.5, 1)
+  const float sc = pow2_scale(e);
+  unscale = pow2_scale(-e);
 #pragma unroll
   for (int st = 0; st < 8; ++st) ms_split(x[st], sc, qh[st], ql[st]);
 }
@@ -112,8 +104,8 @@ __device__ __forceinline__ void ms_load_query_h(const float* __restrict__ Qq, in
 // One 32 x 32 tile: 24 MFMAs, then the lane's maximum over its 16 document tokens (rows >= remain are no tokens of
 // the document: masked on the last tile of a document only — a real, wave-uniform branch: if-converted, the 32
 // compare / select pairs ran on every tile).  Both kernels of this form call it: identical bits.
-__device__ __forceinline__ void ms_tile_h(const ms8h (&ah)[8], const ms8h (&al)[8], const ms8h (&qh)[8],
-                                          const ms8h (&ql)[8], int h, int remain, float& best) {
+__device__ __forceinline__ void ms_tile_h(const h8 (&ah)[8], const h8 (&al)[8], const h8 (&qh)[8],
+                                          const h8 (&ql)[8], int h, int remain, float& best) {
   f32x16 am, ac;
 #pragma unroll
   for (int j = 0; j < 16; ++j) am[j] = ac[j] = 0.f;
@@ -130,7 +122,7 @@ __device__ __forceinline__ void ms_tile_h(const ms8h (&ah)[8], const ms8h (&al)[
     asm volatile("" ::: "memory");
 #pragma unroll
     for (int j = 0; j < 16; ++j)
-      if (((j & 3) + 8 * (j >> 2) + 4 * h) >= remain) v[j] = -FLT_MAX;
+      if (mfma32_row(j, h) >= remain) v[j] = -FLT_MAX;
   }
 #pragma unroll
   for (int j = 0; j < 16; j += 2) best = fmaxf(best, fmaxf(v[j], v[j + 1]));
@@ -148,16 +140,16 @@ __device__ __forceinline__ float ms_finish_h(float best, int r, int h, int q_len
 // by one tile — and are masked by ms_tile_h).  unscale: the query's power of two times the store's.  The score comes
 // back in every lane.  The body of maxsim_scores_h_kernel; scope.hip runs it over a query's scope documents.
 __device__ __forceinline__ float ms_pair_doc_h(const unsigned char* img, long t_lo, int len,
-                                               const ms8h (&qh)[8], const ms8h (&ql)[8], int r32, int h, int q_len,
+                                               const h8 (&qh)[8], const h8 (&ql)[8], int r32, int h, int q_len,
                                                float unscale) {
   float best = -FLT_MAX;
   for (int tok0 = 0; tok0 < len; tok0 += 32) {
     const unsigned char* p = img + (size_t)(t_lo + tok0 + r32) * 512 + h * 16;
-    ms8h ah[8], al[8];
+    h8 ah[8], al[8];
 #pragma unroll
     for (int st = 0; st < 8; ++st) {
-      ah[st] = *reinterpret_cast<const ms8h*>(p + 32 * st);
-      al[st] = *reinterpret_cast<const ms8h*>(p + 256 + 32 * st);
+      ah[st] = *reinterpret_cast<const h8*>(p + 32 * st);
+      al[st] = *reinterpret_cast<const h8*>(p + 256 + 32 * st);
     }
     ms_tile_h(ah, al, qh, ql, h, len - tok0, best);
   }

@@ -350,7 +350,7 @@ __global__ __launch_bounds__(kScWaves * 64) void scope_maxsim_kernel(
   WaveTopK<C32> tk;
   tk.init(L.list(wave), cap, k);
   if (lo + wave < hi) {  // wave-uniform: a wave without a document does not read its query
-    ms8h qh[8], ql[8];
+    h8 qh[8], ql[8];
     float unscale;
     ms_load_query_h(Q + (size_t)q * q_len * kDim, q_len, true, r32, h, qh, ql, unscale);
     unscale *= unscale_d;

@@ -9,7 +9,7 @@
 // Selection is exact for any input order (the data only changes how often a
 // wave compacts) and deterministic: candidates are totally ordered.
 #pragma once
-#include <hip/hip_runtime.h>
+#include "tile_swizzle.hpp"
 
 #include <cfloat>
 #include <cstdint>
@@ -504,7 +504,6 @@ __device__ __forceinline__ int select_row(const float* __restrict__ row, long lo
   return wave_select_small<C32, V>(keys, k, buf + 64, lane, buf);
 }
 
-typedef float tk_v4f __attribute__((ext_vector_type(4)));
 
 // Two queries per wave (lanes 0-31 / 32-63), for rows of <= 1024 scores at k <= 32 when there is a
 // single slab — the serving corpora under a long batch.  grid.x = ceil(nq / 2); a wave whose
@@ -518,12 +517,12 @@ __device__ __forceinline__ int select_row_pair(const float* __restrict__ S, long
   // 16-byte loads (a half-wave covers 512 B of its row per instruction): the kernel waits on memory
   // for two thirds of its life, so fewer, wider requests in flight earlier is what shortens it.
   // Rows are padded to ldS (a multiple of 32 floats), so a whole float4 below ldS is inside the row.
-  tk_v4f blk[V / 4];
+  f32x4 blk[V / 4];
 #pragma unroll
   for (int u = 0; u < V / 4; ++u) {
     const long c0 = 128L * u + 4 * j;
-    const tk_v4f z = {0.f, 0.f, 0.f, 0.f};
-    blk[u] = (has_q && c0 < ldS) ? __builtin_nontemporal_load(reinterpret_cast<const tk_v4f*>(row + c0)) : z;  // read once
+    const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+    blk[u] = (has_q && c0 < ldS) ? __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(row + c0)) : z;  // read once
   }
   u32 sk[V];  // score keys only; ids (128 u + 4 j + e) are attached to the survivors (wave_select_small_pair32)
 #pragma unroll
@@ -563,8 +562,8 @@ __device__ __forceinline__ void wave_topk_sweep4(WaveTopK<C32>& tk, const float*
                                                  int nwaves, int lane) {
   for (long base = lo + (long)wave * 256; base < hi; base += (long)nwaves * 256) {
     const long r0 = base + 4 * lane;
-    tk_v4f x = {0.f, 0.f, 0.f, 0.f};
-    if (r0 < hi) x = NT ? __builtin_nontemporal_load(reinterpret_cast<const tk_v4f*>(row + r0)) : *reinterpret_cast<const tk_v4f*>(row + r0);
+    f32x4 x = {0.f, 0.f, 0.f, 0.f};
+    if (r0 < hi) x = NT ? __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(row + r0)) : *reinterpret_cast<const f32x4*>(row + r0);
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const long r = r0 + e;

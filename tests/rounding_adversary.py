@@ -25,7 +25,7 @@ OFF_Q = 4096        # rounding offsets are multiples of 1/4096 ulp: the scaled v
 # scales and bounds, restated from the kernels (fp64)
 
 def pow2_scale(amax) -> np.ndarray:
-    """2^-e with amax = f 2^e, f in [0.5, 1) (frexpf); 1 for amax == 0 — dense_fp16.hpp dense_fp16_exp / dense_fp16_scale."""
+    """2^-e with amax = f 2^e, f in [0.5, 1) (frexpf); 1 for amax == 0 — tile_swizzle.hpp pow2_exp / pow2_scale."""
     amax = np.asarray(amax, dtype=np.float64)
     _, e = np.frexp(np.where(amax > 0, amax, 1.0))
     return np.where(amax > 0, np.ldexp(1.0, -e), 1.0)
