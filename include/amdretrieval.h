@@ -260,6 +260,32 @@ int amdr_tokenizer_device_destroy(amdr_tokenizer_device_t* h);
  * holding a NaN / infinity, or AMDR_MAXSIM_F16X3=0, takes the exact fp32-input matrix form (csrc/maxsim.hip). */
 int amdr_maxsim_create(const float* D_host, const int64_t* doc_ptr, int64_t n_docs, int32_t dim,
                        int32_t device, amdr_maxsim_t** out);
+/* Append n_add documents (replaces re-running the indexer over the whole corpus, legalrag/retrieval/builders/
+ * colbert_builder.py:131-132, for an ingest): D_host fp32 [doc_ptr_add[n_add], 128], doc_ptr_add[0] == 0, strictly ascending
+ * (every document >= 1 token); new pids are n_docs .. n_docs + n_add - 1.  Afterwards the handle is what
+ * amdr_maxsim_create makes of the concatenated store: the same scale, first-pass bound and image bytes, hence the same
+ * ids and score bits from every entry point.  The new rows' largest |component| joins the store's; the images of the
+ * old rows stay as they are unless that raises the store's power-of-two scale (then the whole store is converted
+ * again); new rows holding a NaN / infinity drop the images (fp32-input form from then on, as after such a create).
+ * Storage doubles, or grows to fit.  AMDR_EINVAL: null handle, n_add < 0, null pointers with n_add > 0,
+ * doc_ptr_add[0] != 0, an empty document, n_docs + n_add >= 2^32; n_add == 0 is a no-op.  A failed add (AMDR_ENOMEM,
+ * AMDR_EHIP) leaves the handle as it was and searchable.  The price of that: an add that has to grow the storage, or
+ * to convert the store again, holds the old and the new copy of what it replaces (D, img and img_hi: 4 + 4 + 2 bytes
+ * per component) until it has succeeded — up to twice the steady state for the length of the call, so it can return
+ * AMDR_ENOMEM on a device where the store itself fits; an add within the capacity at an unchanged scale allocates nothing.
+ * Runs inside the handle's mutex: host-pointer searches from other threads serialise against it.  It is a mutation in
+ * the sense of the rule at the top of this file: "_device" work of the handle still in flight is the caller's to finish
+ * first (buffers it reads may be freed).  Workspaces are sized per call from n_docs: an eager "_device" call after an add
+ * grows its workspace if it has to (amdr_workspace_growths shows it); a captured graph holds the old buffers and sizes
+ * and must be re-reserved (amdr_maxsim_reserve) and captured again. */
+int amdr_maxsim_add(amdr_maxsim_t* h, const float* D_host, const int64_t* doc_ptr_add, int64_t n_add);
+/* out6: [0] n_docs, [1] n_tokens, [2] token capacity, [3] e of d_scale = 2^e, [4] 1 if the split-fp16 images exist,
+ *       [5] whole-store conversions so far (amdr_maxsim_create of a finite store counts 1) */
+int amdr_maxsim_info(amdr_maxsim_t* h, int64_t* out6);
+/* The two numbers of the store that the bound of the two-pass top-k's first pass is built on: out2[0] = d_scale (a power
+ * of two; 1 for a store without images), out2[1] = d_norm_max, the largest token L2 norm of the store x d_scale (0 without
+ * images).  After any sequence of adds both have the bits amdr_maxsim_create gives them on the concatenated store. */
+int amdr_maxsim_stats(amdr_maxsim_t* h, float* out2);
 int amdr_maxsim_ndocs(const amdr_maxsim_t* h, int64_t* n);
 /* which kernels a search of nq queries would launch and in which arithmetic form (NUL-terminated; no device work) */
 int amdr_maxsim_plan_info(const amdr_maxsim_t* h, int32_t nq, char* buf, int32_t buf_len);

@@ -43,7 +43,7 @@ SIGNATURES = {
     "amdr_tokenizer_destroy": "P",
     "amdr_tokenizer_pack": "PPiPlP", "amdr_tokenizer_device_create": "PiP", "amdr_tokenizer_device_reserve": "Pil",
     "amdr_tokenizer_encode_device": "PPPilPlPPP", "amdr_tokenizer_device_destroy": "P",
-    "amdr_maxsim_create": "PPliiP", "amdr_maxsim_ndocs": "PP", "amdr_maxsim_plan_info": "PiPi", "amdr_maxsim_reserve": "Pii", "amdr_maxsim_workspace_plan": "liiiiiP",
+    "amdr_maxsim_create": "PPliiP", "amdr_maxsim_add": "PPPl", "amdr_maxsim_info": "PP", "amdr_maxsim_stats": "PP", "amdr_maxsim_ndocs": "PP", "amdr_maxsim_plan_info": "PiPi", "amdr_maxsim_reserve": "Pii", "amdr_maxsim_workspace_plan": "liiiiiP",
     "amdr_maxsim_search": "PPiiiPP", "amdr_maxsim_search_device": "PPiiiPPP", "amdr_maxsim_scores": "PPiiP",
     "amdr_maxsim_destroy": "P",
     "amdr_fuse": "Pi" + "PPi" * 3 + "PPPP", "amdr_fuse_device": "Pi" + "PPiP" * 3 + "PPPP" + "iP",
@@ -660,6 +660,34 @@ class MaxSimIndex(_Handle):
         _check(load().amdr_maxsim_create(_p(D, C.c_float), _p(doc_ptr, C.c_int64), C.c_int64(self.n_docs),
                                          C.c_int32(self.dim), C.c_int32(device), C.byref(self._h)),
                "amdr_maxsim_create")
+
+    def add(self, D: np.ndarray, doc_ptr: np.ndarray) -> None:
+        """Append documents (doc_ptr: their own offsets, from 0); new pids follow the store's.  The handle is then what
+        MaxSimIndex makes of the concatenated store, bit for bit (amdr_maxsim_add)."""
+        D = _c(D, np.float32)
+        doc_ptr = _c(doc_ptr, np.int64)
+        if D.ndim != 2 or D.shape[1] != self.dim:
+            raise ValueError(f"add: D must be [tokens, {self.dim}]")
+        if doc_ptr.ndim != 1 or doc_ptr.shape[0] < 1:
+            raise ValueError("add: doc_ptr must be [n_add + 1]")
+        if int(doc_ptr[-1]) != D.shape[0]:
+            raise ValueError("doc_ptr[-1] != number of token rows")
+        _check(load().amdr_maxsim_add(self._h, _p(D, C.c_float), _p(doc_ptr, C.c_int64), C.c_int64(doc_ptr.shape[0] - 1)),
+               "amdr_maxsim_add")
+        self.n_docs = self.info()[0]
+
+    def info(self) -> Tuple[int, int, int, int, int, int]:
+        """(n_docs, n_tokens, token capacity, e of the store's scale 2^e, 1 if the split-fp16 images exist, whole-store
+        conversions so far)."""
+        out = (C.c_int64 * 6)()
+        _check(load().amdr_maxsim_info(self._h, out), "amdr_maxsim_info")
+        return tuple(int(x) for x in out)
+
+    def stats(self) -> Tuple[float, float]:
+        """(d_scale, d_norm_max): the store's power-of-two scale and its largest scaled token norm (amdr_maxsim_stats)."""
+        out = (C.c_float * 2)()
+        _check(load().amdr_maxsim_stats(self._h, out), "amdr_maxsim_stats")
+        return float(out[0]), float(out[1])
 
     def plan_info(self, nq: int) -> str:
         """Kernels and arithmetic form a search of nq queries launches (no device work)."""

@@ -317,6 +317,31 @@ def read_token_store(dirpath: Path) -> Tuple[np.ndarray, np.ndarray]:
                        f"Run build_colbert_index() first.")
 
 
+def token_store_ndocs(dirpath: Path) -> int:
+    """Documents in the store read_token_store finds in `dirpath` (this build's file: only doc_ptr is read)."""
+    p = Path(dirpath) / "amdr_tokens.npz"
+    if p.exists():
+        with np.load(p) as z:
+            return int(z["doc_ptr"].shape[0]) - 1
+    return int(read_token_store(dirpath)[1].shape[0]) - 1
+
+
+def append_token_store(dirpath: Path, D_add: np.ndarray, doc_ptr_add: np.ndarray) -> Path:
+    """Append documents (doc_ptr_add: their own offsets, from 0) to the store read_token_store finds in `dirpath` and
+    write the result as this build's own file, atomically.  On a colbert-ai (PLAID) directory without one that is the
+    decompressed store plus the new rows, which read_token_store prefers from then on."""
+    D, doc_ptr = read_token_store(dirpath)
+    D_add = np.ascontiguousarray(D_add, dtype=np.float32)
+    doc_ptr_add = np.ascontiguousarray(doc_ptr_add, dtype=np.int64)
+    if D_add.ndim != 2 or D_add.shape[1] != D.shape[1]:
+        raise ValueError(f"append_token_store: D_add must be [tokens, {D.shape[1]}]")
+    if doc_ptr_add.ndim != 1 or doc_ptr_add.shape[0] < 1 or doc_ptr_add[0] != 0 or doc_ptr_add[-1] != D_add.shape[0] \
+            or np.any(np.diff(doc_ptr_add) < 1):
+        raise ValueError("append_token_store: doc_ptr_add must run from 0 to the number of new token rows, ascending")
+    return write_token_store(dirpath, np.concatenate([np.asarray(D, dtype=np.float32), D_add], axis=0),
+                             np.concatenate([np.asarray(doc_ptr, dtype=np.int64), doc_ptr_add[1:] + int(doc_ptr[-1])]))
+
+
 # ---------------------------------------------------------------------------
 # colbert-ai (PLAID) index directory  [upstream layout, from memory — verify]
 #   metadata.json            {"config": {"nbits", "dim", ...}, "num_chunks", "num_partitions", "num_embeddings", ...}

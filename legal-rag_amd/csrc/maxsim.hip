@@ -975,11 +975,15 @@ using namespace amdr;
 struct amdr_maxsim {
   int device = 0;
   int64_t n_docs = 0;
+  int64_t n_tokens = 0;                  // doc_ptr[n_docs]
+  int64_t cap_tokens = 0, cap_docs = 0;  // rows that D / img / img_hi and entries (+ 1) that doc_ptr have room for (amdr_maxsim_add)
   float* D = nullptr;
   unsigned char* img = nullptr;  // [hi 128 x fp16 | lo 128 x fp16] per token, scaled by d_scale (split-fp16 form)
   unsigned char* img_hi = nullptr;  // [hi 128 x fp16] per token: first pass of the two-pass top-k
   float d_scale = 1.f;           // power of two; img == nullptr: the store is not finite -> fp32-input form only
   float d_norm_max = 0.f;        // largest token L2 norm of the store x d_scale (error bound of the first pass)
+  unsigned int amax_bits = 0;    // largest |component| of the store as float bits (what d_scale was taken from)
+  int64_t conversions = 0;       // whole-store conversions to the images so far (amdr_maxsim_info)
   long long* doc_ptr = nullptr;
   int cus = 0;  // compute units of `device` (the re-scoring pass's grid)
   hipStream_t stream = nullptr;
@@ -1179,6 +1183,58 @@ int ms_run(amdr_maxsim* h, const MsRoute& r, const float* Q_dev, int nq, int q_l
   return AMDR_OK;
 }
 
+// ---- the store's statistics and images, over a range of token rows (amdr_maxsim_create: all of them; amdr_maxsim_add:
+// the new ones).  Synchronous, on the null stream. -------------------------------------------------------------------
+// largest |component| of token rows [t0, t1) as float bits (>= 0x7f800000: the range holds a NaN or an infinity)
+hipError_t ms_absmax(const float* D, int64_t t0, int64_t t1, unsigned int* bits) {
+  unsigned int* mx = nullptr;
+  hipError_t e = hipMalloc((void**)&mx, sizeof(unsigned int));
+  if (e == hipSuccess) e = hipMemset(mx, 0, sizeof(unsigned int));
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(ms_absmax_kernel, dim3(1024), dim3(256), 0, 0, D + (size_t)t0 * kDim, (long)((t1 - t0) * kDim), mx);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpy(bits, mx, sizeof(unsigned int), hipMemcpyDeviceToHost);
+  if (mx) (void)hipFree(mx);
+  return e;
+}
+// Token rows [t0, t1) of D -> both images at `scale`, t1 being the store's end: the zero tile behind it (32 tokens of
+// img, 64 of img_hi) is written too.  *norm_max = the largest L2 norm of the scaled rows of the range.
+hipError_t ms_convert(const float* D, int64_t t0, int64_t t1, float scale, unsigned char* img, unsigned char* img_hi,
+                      float* norm_max) {
+  unsigned int* nm = nullptr;
+  unsigned int nbits = 0;
+  hipError_t e = hipMemset(img + (size_t)t1 * 512, 0, (size_t)32 * 512);
+  if (e == hipSuccess) e = hipMemset(img_hi + (size_t)t1 * 256, 0, (size_t)64 * 256);
+  if (e == hipSuccess) e = hipMalloc((void**)&nm, sizeof(unsigned int));
+  if (e == hipSuccess) e = hipMemset(nm, 0, sizeof(unsigned int));
+  if (e == hipSuccess) {
+    const int64_t nt = t1 - t0;
+    hipLaunchKernelGGL(ms_split_store_kernel, dim3(ceil_div(nt * 16, 256)), dim3(256), 0, 0, D + (size_t)t0 * kDim, (long)nt,
+                       scale, img + (size_t)t0 * 512, img_hi + (size_t)t0 * 256);
+    e = hipGetLastError();
+    if (e == hipSuccess) {
+      hipLaunchKernelGGL(ms_tokmax_kernel, dim3(1024), dim3(256), 0, 0, D + (size_t)t0 * kDim, (long)nt, scale, nm);
+      e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpy(&nbits, nm, sizeof(unsigned int), hipMemcpyDeviceToHost);
+    memcpy(norm_max, &nbits, sizeof(float));
+  }
+  if (nm) (void)hipFree(nm);
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  return e;
+}
+hipError_t ms_alloc_images(int64_t cap_tokens, unsigned char** img, unsigned char** img_hi) {
+  hipError_t e = hipMalloc((void**)img, (size_t)(cap_tokens + 32) * 512);  // + one tile: the last tile of the last document reads on
+  if (e == hipSuccess) e = hipMalloc((void**)img_hi, (size_t)(cap_tokens + 64) * 256);  // + one 64-token tile
+  return e;
+}
+float ms_scale_of(unsigned int amax_bits) {
+  float m;
+  memcpy(&m, &amax_bits, sizeof(float));
+  return pow2_scale(pow2_exp(m));
+}
+
 int ms_check(const amdr_maxsim* h, const void* Q, int nq, int q_len, int k) {
   AMDR_REQUIRE(h != nullptr, "maxsim: null handle");
   AMDR_REQUIRE(nq >= 0, "maxsim: nq=%d", nq);
@@ -1208,7 +1264,8 @@ int amdr_maxsim_create(const float* D_host, const int64_t* doc_ptr, int64_t n_do
   amdr_maxsim* h = new (std::nothrow) amdr_maxsim();
   if (!h) return fail(AMDR_ENOMEM, "maxsim_create: host alloc");
   h->device = device;
-  h->n_docs = n_docs;
+  h->n_docs = h->cap_docs = n_docs;
+  h->n_tokens = h->cap_tokens = nt;
   hipError_t e = hipMalloc((void**)&h->D, (size_t)nt * dim * sizeof(float));
   if (e == hipSuccess) e = hipMemcpy(h->D, D_host, (size_t)nt * dim * sizeof(float), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMalloc((void**)&h->doc_ptr, (size_t)(n_docs + 1) * sizeof(long long));
@@ -1224,42 +1281,144 @@ int amdr_maxsim_create(const float* D_host, const int64_t* doc_ptr, int64_t n_do
   lds((const void*)maxsim_overflow_kernel, kPairLds);
   // the split-fp16 image: the store's largest |component| fixes a power-of-two scale into [0.5, 1), then every
   // token row is split once (a store with a NaN / infinity keeps the fp32-input form only)
-  unsigned int* mx = nullptr;
-  unsigned int mbits = 0;
-  if (e == hipSuccess) e = hipMalloc((void**)&mx, sizeof(unsigned int));
-  if (e == hipSuccess) e = hipMemset(mx, 0, sizeof(unsigned int));
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(ms_absmax_kernel, dim3(1024), dim3(256), 0, 0, h->D, (long)(nt * dim), mx);
-    e = hipMemcpy(&mbits, mx, sizeof(unsigned int), hipMemcpyDeviceToHost);
-  }
-  if (mx) (void)hipFree(mx);
-  if (e == hipSuccess && mbits < 0x7f800000u) {
-    float m;
-    memcpy(&m, &mbits, sizeof(float));
-    h->d_scale = pow2_scale(pow2_exp(m));
-    e = hipMalloc((void**)&h->img, (size_t)(nt + 32) * 512);  // + one tile: the last tile of the last document reads on
-    if (e == hipSuccess) e = hipMemset(h->img + (size_t)nt * 512, 0, (size_t)32 * 512);
-    if (e == hipSuccess) e = hipMalloc((void**)&h->img_hi, (size_t)(nt + 64) * 256);  // + one 64-token tile
-    if (e == hipSuccess) e = hipMemset(h->img_hi + (size_t)nt * 256, 0, (size_t)64 * 256);
-    unsigned int* nm = nullptr;
-    unsigned int nbits = 0;
-    if (e == hipSuccess) e = hipMalloc((void**)&nm, sizeof(unsigned int));
-    if (e == hipSuccess) e = hipMemset(nm, 0, sizeof(unsigned int));
-    if (e == hipSuccess) {
-      hipLaunchKernelGGL(ms_split_store_kernel, dim3(ceil_div(nt * 16, 256)), dim3(256), 0, 0, h->D, (long)nt, h->d_scale,
-                         h->img, h->img_hi);
-      hipLaunchKernelGGL(ms_tokmax_kernel, dim3(1024), dim3(256), 0, 0, h->D, (long)nt, h->d_scale, nm);
-      e = hipMemcpy(&nbits, nm, sizeof(unsigned int), hipMemcpyDeviceToHost);
-      memcpy(&h->d_norm_max, &nbits, sizeof(float));
-    }
-    if (nm) (void)hipFree(nm);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e == hipSuccess) e = ms_absmax(h->D, 0, nt, &h->amax_bits);
+  if (e == hipSuccess && h->amax_bits < 0x7f800000u) {
+    h->d_scale = ms_scale_of(h->amax_bits);
+    e = ms_alloc_images(nt, &h->img, &h->img_hi);
+    if (e == hipSuccess) e = ms_convert(h->D, 0, nt, h->d_scale, h->img, h->img_hi, &h->d_norm_max);
+    h->conversions = 1;
   }
   if (e != hipSuccess) {
     amdr_maxsim_destroy(h);
     return fail(e == hipErrorOutOfMemory ? AMDR_ENOMEM : AMDR_EHIP, "maxsim_create: %s", hipGetErrorString(e));
   }
   *out = h;
+  return AMDR_OK;
+}
+
+int amdr_maxsim_info(amdr_maxsim_t* h, int64_t* out6) {
+  AMDR_REQUIRE(h && out6, "maxsim_info: null");
+  std::lock_guard<std::mutex> g(h->mu);
+  out6[0] = h->n_docs;
+  out6[1] = h->n_tokens;
+  out6[2] = h->cap_tokens;
+  out6[3] = pow2_exp(h->d_scale) - 1;  // d_scale = 2^e = 0.5 * 2^(e + 1)
+  out6[4] = h->img ? 1 : 0;
+  out6[5] = h->conversions;
+  return AMDR_OK;
+}
+
+int amdr_maxsim_stats(amdr_maxsim_t* h, float* out2) {
+  AMDR_REQUIRE(h && out2, "maxsim_stats: null");
+  std::lock_guard<std::mutex> g(h->mu);
+  out2[0] = h->d_scale;
+  out2[1] = h->d_norm_max;
+  return AMDR_OK;
+}
+
+// Append documents.  Everything that can fail — allocations, copies, the conversion kernels — runs on buffers or buffer
+// tails that no search reads (rows behind n_tokens, entries behind n_docs + 1); the handle's fields change together at
+// the end, so a failed add leaves the store it had.  What create() does for a whole store, on the new rows: their largest
+// |component| joins the store's, and only when that raises the store's power-of-two scale are the images made again from
+// D — otherwise the old rows' image bytes are already what create() would write for the concatenated store.
+int amdr_maxsim_add(amdr_maxsim_t* h, const float* D_host, const int64_t* doc_ptr_add, int64_t n_add) {
+  AMDR_REQUIRE(h != nullptr, "maxsim_add: null handle");
+  AMDR_REQUIRE(n_add >= 0, "maxsim_add: n_add=%lld", (long long)n_add);
+  if (n_add == 0) return AMDR_OK;
+  AMDR_REQUIRE(D_host && doc_ptr_add, "maxsim_add: null D / doc_ptr");
+  std::lock_guard<std::mutex> g(h->mu);
+  AMDR_REQUIRE(n_add < (1ll << 32) && h->n_docs + n_add < (1ll << 32), "maxsim_add: too many documents");  // (before doc_ptr_add is walked)
+  AMDR_REQUIRE(doc_ptr_add[0] == 0, "maxsim_add: doc_ptr[0] != 0");
+  for (int64_t i = 0; i < n_add; ++i)
+    AMDR_REQUIRE(doc_ptr_add[i + 1] > doc_ptr_add[i], "maxsim_add: document %lld has no tokens", (long long)i);
+  AMDR_HIP(hipSetDevice(h->device));
+  const int64_t t0 = h->n_tokens, t1 = t0 + doc_ptr_add[n_add], nd0 = h->n_docs, nd1 = nd0 + n_add;
+  long long* ptr_host = new (std::nothrow) long long[(size_t)n_add];
+  if (!ptr_host) return fail(AMDR_ENOMEM, "maxsim_add: host alloc");
+  for (int64_t i = 0; i < n_add; ++i) ptr_host[i] = (long long)(t0 + doc_ptr_add[i + 1]);
+
+  // the buffers the grown store lives in: the handle's own where there is room, otherwise new ones (double, or to fit)
+  const bool grow_t = t1 > h->cap_tokens, grow_d = nd1 > h->cap_docs;
+  const int64_t cap_t = !grow_t ? h->cap_tokens : (h->cap_tokens * 2 > t1 ? h->cap_tokens * 2 : t1);
+  const int64_t cap_d = !grow_d ? h->cap_docs : (h->cap_docs * 2 > nd1 ? h->cap_docs * 2 : nd1);
+  float* D = h->D;
+  long long* dp = h->doc_ptr;
+  unsigned char *img = h->img, *img_hi = h->img_hi;
+  hipError_t e = hipSuccess;
+  if (grow_t) {
+    D = nullptr;
+    e = hipMalloc((void**)&D, (size_t)cap_t * kDim * sizeof(float));
+    if (e == hipSuccess) e = hipMemcpy(D, h->D, (size_t)t0 * kDim * sizeof(float), hipMemcpyDeviceToDevice);
+  }
+  if (e == hipSuccess && grow_d) {
+    dp = nullptr;
+    e = hipMalloc((void**)&dp, (size_t)(cap_d + 1) * sizeof(long long));
+    if (e == hipSuccess) e = hipMemcpy(dp, h->doc_ptr, (size_t)(nd0 + 1) * sizeof(long long), hipMemcpyDeviceToDevice);
+  }
+  if (e == hipSuccess) e = hipMemcpy(D + (size_t)t0 * kDim, D_host, (size_t)(t1 - t0) * kDim * sizeof(float), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(dp + nd0 + 1, ptr_host, (size_t)n_add * sizeof(long long), hipMemcpyHostToDevice);
+  delete[] ptr_host;
+
+  // statistics from the new rows; the images follow them
+  unsigned int amax = h->amax_bits;
+  float scale = h->d_scale, norm_max = h->d_norm_max;
+  int64_t conversions = h->conversions;
+  bool keep_img = h->img != nullptr;
+  if (e == hipSuccess) {
+    unsigned int add_bits = 0;
+    e = ms_absmax(D, t0, t1, &add_bits);
+    amax = add_bits > amax ? add_bits : amax;  // (float bits of non-negative values order like the values; NaN on top)
+  }
+  if (e == hipSuccess && keep_img) {
+    if (amax >= 0x7f800000u) {  // the store is no longer finite: the fp32-input forms serve, as after such a create()
+      keep_img = false;
+      img = img_hi = nullptr;
+      scale = 1.f;
+      norm_max = 0.f;
+    } else {
+      const bool rescale = ms_scale_of(amax) != scale;  // the exponent can only rise
+      scale = ms_scale_of(amax);
+      if (grow_t || rescale) {  // (a re-split goes to new images too: the old ones serve until it has succeeded)
+        img = img_hi = nullptr;
+        e = ms_alloc_images(cap_t, &img, &img_hi);
+        if (e == hipSuccess && !rescale) e = hipMemcpy(img, h->img, (size_t)t0 * 512, hipMemcpyDeviceToDevice);
+        if (e == hipSuccess && !rescale) e = hipMemcpy(img_hi, h->img_hi, (size_t)t0 * 256, hipMemcpyDeviceToDevice);
+      }
+      float nm = 0.f;
+      if (e == hipSuccess) e = ms_convert(D, rescale ? 0 : t0, t1, scale, img, img_hi, &nm);
+      norm_max = rescale ? nm : (nm > norm_max ? nm : norm_max);
+      conversions += rescale ? 1 : 0;
+    }
+  }
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e != hipSuccess) {
+    if (D != h->D) (void)hipFree(D);
+    if (dp != h->doc_ptr) (void)hipFree(dp);
+    if (img && img != h->img) (void)hipFree(img);
+    if (img_hi && img_hi != h->img_hi) (void)hipFree(img_hi);
+    if (keep_img && img == h->img) {  // the tail written behind the old end becomes the zero tile again (masked either way)
+      (void)hipMemset(h->img + (size_t)t0 * 512, 0, (size_t)32 * 512);
+      (void)hipMemset(h->img_hi + (size_t)t0 * 256, 0, (size_t)64 * 256);
+    }
+    return fail(e == hipErrorOutOfMemory ? AMDR_ENOMEM : AMDR_EHIP, "maxsim_add: %s", hipGetErrorString(e));
+  }
+  // the swap (hipFree waits for the device: host-pointer searches are behind h->mu, "_device" work is the caller's to order)
+  if (D != h->D) (void)hipFree(h->D);
+  if (dp != h->doc_ptr) (void)hipFree(h->doc_ptr);
+  if (img != h->img && h->img) (void)hipFree(h->img);
+  if (img_hi != h->img_hi && h->img_hi) (void)hipFree(h->img_hi);
+  h->D = D;
+  h->doc_ptr = dp;
+  h->img = img;
+  h->img_hi = img_hi;
+  h->cap_tokens = cap_t;
+  h->cap_docs = cap_d;
+  h->n_tokens = t1;
+  h->n_docs = nd1;
+  h->amax_bits = amax;
+  h->d_scale = scale;
+  h->d_norm_max = norm_max;
+  h->conversions = conversions;
   return AMDR_OK;
 }
 

@@ -1,0 +1,80 @@
+"""Incremental ColBERT add: the sibling of IncrementalDenseBuilder for the token store (the reference has none — its
+only way to index a new document is Indexer.index() over the whole collection,
+legalrag/retrieval/builders/colbert_builder.py:131-132).
+
+Under the lock build_colbert_index takes (`<index_path>/.colbert_build.lock`): read colbert_meta.jsonl, keep only ids
+it does not hold yet, encode THOSE chunks, append their meta lines (pid = next row) BEFORE the token store is rewritten
+(a reader must never see a pid without its chunk), then append the token rows to the store.  Before anything is
+written the meta file and the store must agree (pids 0 .. n - 1, n documents); if they do not, it asks for a rebuild.
+If a ColBERTRetriever of this index identity is live in the process and holds the store that was appended to, the same
+rows go behind its resident store in HBM (`amdr_maxsim_add`) and it remembers the files' mtimes, so it does not reload
+what this process wrote — under the retriever's registry lock from the check to the add, so that no search thread
+reloads the file in between; any other reader finds the store changed and reloads it."""
+from __future__ import annotations
+
+import json
+import logging
+from pathlib import Path
+
+import numpy as np
+from filelock import FileLock
+
+from ... import artifacts
+from ..colbert_retriever import ColBERTRetriever, _identity, get_token_encoder
+from ._incremental import incoming_chunks, unseen
+
+logger = logging.getLogger(__name__)
+
+
+class IncrementalColBERTBuilder:
+    def __init__(self, cfg):
+        self.cfg = cfg
+
+    def add_jsonl(self, jsonl_path) -> int:
+        rcfg = self.cfg.retrieval
+        if not bool(getattr(rcfg, "enable_colbert", False)):
+            raise RuntimeError("ColBERT is disabled: set cfg.retrieval.enable_colbert=True")
+        if getattr(rcfg, "shard", None):
+            raise RuntimeError("incremental add on a row-sharded index is not supported: rebuild and reload")
+        batch = incoming_chunks(jsonl_path, logger, "colbert")
+        if not batch:
+            return 0
+        index_path, index_name, model_name, meta_file, experiment, _ = _identity(rcfg)
+        meta_file = Path(meta_file)
+        out_dir = artifacts.colbert_index_dir(index_path, experiment, index_name)
+        if not meta_file.exists() or not ((out_dir / "amdr_tokens.npz").exists() or artifacts.is_plaid_index(out_dir)):
+            raise RuntimeError(f"ColBERT index not found ({meta_file}, {out_dir}). Run build_colbert_index() first.")
+        with FileLock(str(Path(index_path) / ".colbert_build.lock")):
+            by_pid = artifacts.read_colbert_meta(meta_file)
+            fresh = unseen(batch, {c.id for c in by_pid.values()})
+            logger.info("[colbert] dedup done: incoming=%d added=%d", len(batch), len(fresh))
+            if not fresh:
+                return 0
+            # pid == row of the token store: the meta file must hold pids 0 .. n - 1 and the store n documents (an add
+            # that died between its two writes leaves ids without token rows, and every later pid would be off by them)
+            first = len(by_pid)
+            n_store = artifacts.token_store_ndocs(out_dir)
+            if sorted(by_pid) != list(range(first)) or n_store != first:
+                raise RuntimeError(f"ColBERT index is inconsistent: {meta_file} holds {first} chunks (pids up to "
+                                   f"{max(by_pid) if by_pid else -1}), the token store in {out_dir} {n_store} documents. "
+                                   f"Rebuild it: build_colbert_index(cfg, chunks, override=True).")
+            enc = get_token_encoder(model_name, str(getattr(rcfg, "encoder_backend", "auto")),
+                                    int(getattr(rcfg, "colbert_doc_maxlen", 220)),
+                                    device=f"cuda:{int(getattr(rcfg, 'device', 0))}")
+            mats = [np.asarray(enc.encode_doc((getattr(c, "text", "") or "").strip()), dtype=np.float32) for c in fresh]
+            tokens = np.concatenate(mats, axis=0)
+            doc_ptr = np.concatenate([[0], np.cumsum([m.shape[0] for m in mats])]).astype(np.int64)
+            live = ColBERTRetriever._instances_by_key.get(_identity(rcfg) + ("none",))
+            # The retriever's lock is held from the question "is the resident store the one on disk" until the rows are
+            # behind it: a search thread that sees the new mtime in between would otherwise reload the file — new rows
+            # included — and the add below would put them there a second time.
+            with ColBERTRetriever._registry_lock:
+                in_place = live is not None and live.store_is_current()
+                with meta_file.open("a", encoding="utf-8") as meta:
+                    meta.writelines(json.dumps({"pid": first + i, "chunk": c.model_dump()}, ensure_ascii=False) + "\n"
+                                    for i, c in enumerate(fresh))
+                artifacts.append_token_store(out_dir, tokens, doc_ptr)
+                if in_place:
+                    live.note_appended(tokens, doc_ptr, first)
+        logger.info("[colbert] incremental add done: added=%d jsonl=%s", len(fresh), jsonl_path)
+        return len(fresh)

@@ -54,7 +54,8 @@ def _identity(rcfg) -> Tuple[str, str, str, str, str, int]:
 
 class ColBERTRetriever:
     _instances_by_key: ClassVar[Dict[tuple, "ColBERTRetriever"]] = {}
-    _searcher_cache: ClassVar[Dict[tuple, Tuple["_native.MaxSimIndex", int]]] = {}  # (index, first pid of the shard)
+    # (index, first pid of the shard, mtime of the token store it was read from)
+    _searcher_cache: ClassVar[Dict[tuple, Tuple["_native.MaxSimIndex", int, Optional[float]]]] = {}
     # from_config() constructs an instance (which fills the searcher cache) while holding the
     # registry lock: re-entrant on purpose
     _registry_lock: ClassVar[threading.RLock] = threading.RLock()
@@ -69,6 +70,8 @@ class ColBERTRetriever:
         self._pid2chunk: Dict[int, LawChunk] = {}
         self._collection: List[str] = []
         self._meta_mtime: Optional[float] = None
+        self._store_mtime: Optional[float] = None  # of the token store self._searcher holds
+        self._searcher_key: Optional[tuple] = None
         self._searcher: Optional[_native.MaxSimIndex] = None
         self.shard, self.row_offset = None, 0  # sharding.ShardSpec / first pid of this rank's block
         self._encoder = None
@@ -84,20 +87,42 @@ class ColBERTRetriever:
                 cls._instances_by_key[key] = cls(cfg)
             return cls._instances_by_key[key]
 
-    # pid -> chunk map, refreshed when the meta file changes on disk
+    # pid -> chunk map and resident token store, each refreshed when its file changes on disk
     def _load_meta_and_collection(self) -> None:
         if not self.meta_file.exists():
             raise RuntimeError(f"ColBERT meta file not found: {self.meta_file}. Run build_colbert_index() first.")
         stamp = self.meta_file.stat().st_mtime
-        if stamp == self._meta_mtime:
-            return
-        by_pid = artifacts.read_colbert_meta(self.meta_file)
-        if not by_pid:
-            raise RuntimeError(f"ColBERT meta file is empty: {self.meta_file}")
-        texts = [""] * (max(by_pid) + 1)
-        for pid, chunk in by_pid.items():
-            texts[pid] = (chunk.text or "").strip()
-        self._pid2chunk, self._collection, self._meta_mtime = by_pid, texts, stamp
+        if stamp != self._meta_mtime:
+            by_pid = artifacts.read_colbert_meta(self.meta_file)
+            if not by_pid:
+                raise RuntimeError(f"ColBERT meta file is empty: {self.meta_file}")
+            texts = [""] * (max(by_pid) + 1)
+            for pid, chunk in by_pid.items():
+                texts[pid] = (chunk.text or "").strip()
+            self._pid2chunk, self._collection, self._meta_mtime = by_pid, texts, stamp
+        if self._searcher is not None and self._store_stamp() != self._store_mtime:
+            self._reload_searcher()
+
+    def index_dir(self) -> Path:
+        return artifacts.colbert_index_dir(str(self.index_path), self.experiment, self.index_name)
+
+    def _store_stamp(self) -> Optional[float]:
+        """mtime of this build's token store (None: a colbert-ai directory without one, which nothing here rewrites)."""
+        try:
+            return (self.index_dir() / "amdr_tokens.npz").stat().st_mtime
+        except OSError:
+            return None
+
+    def _open_store(self) -> Tuple["_native.MaxSimIndex", int, Optional[float]]:
+        stamp = self._store_stamp()  # before the read: a store replaced meanwhile is found changed again
+        tokens, doc_ptr = artifacts.read_token_store(self.index_dir())
+        lo = 0
+        if self.shard is not None:
+            # row-sharded deployment: the token vectors of this rank's documents only (pid = lo + local id)
+            lo, hi = self.shard.bounds(len(doc_ptr) - 1)
+            tokens = np.ascontiguousarray(tokens[int(doc_ptr[lo]):int(doc_ptr[hi])])
+            doc_ptr = np.ascontiguousarray(doc_ptr[lo:hi + 1] - doc_ptr[lo])
+        return _native.MaxSimIndex(tokens, doc_ptr, device=self.device_index), lo, stamp
 
     # token store -> HBM (one MaxSim index per index identity and process)
     def _init_searcher(self) -> None:
@@ -107,20 +132,48 @@ class ColBERTRetriever:
                                           device=f"cuda:{self.device_index}")
         from . import sharding
         self.shard = sharding.active_shard(rcfg)
-        key = (str(self.index_path), self.index_name, str(self.model_name), self.experiment, self.nranks,
-               self.shard.key if self.shard else None)
+        key = self._searcher_key = (str(self.index_path), self.index_name, str(self.model_name), self.experiment,
+                                    self.nranks, self.shard.key if self.shard else None)
         with type(self)._registry_lock:
             if key not in type(self)._searcher_cache:
-                tokens, doc_ptr = artifacts.read_token_store(
-                    artifacts.colbert_index_dir(str(self.index_path), self.experiment, self.index_name))
-                lo = 0
-                if self.shard is not None:
-                    # row-sharded deployment: the token vectors of this rank's documents only (pid = lo + local id)
-                    lo, hi = self.shard.bounds(len(doc_ptr) - 1)
-                    tokens = np.ascontiguousarray(tokens[int(doc_ptr[lo]):int(doc_ptr[hi])])
-                    doc_ptr = np.ascontiguousarray(doc_ptr[lo:hi + 1] - doc_ptr[lo])
-                type(self)._searcher_cache[key] = (_native.MaxSimIndex(tokens, doc_ptr, device=self.device_index), lo)
-            self._searcher, self.row_offset = type(self)._searcher_cache[key]
+                type(self)._searcher_cache[key] = self._open_store()
+            self._searcher, self.row_offset, self._store_mtime = type(self)._searcher_cache[key]
+
+    def _reload_searcher(self) -> None:
+        """Another process rewrote the token store: a new MaxSim index from the file replaces the resident one (a full
+        reload — right whatever the writer did; the in-process builder appends to the resident store instead and stamps
+        `_store_mtime`: store_is_current / note_appended)."""
+        cls = type(self)
+        with cls._registry_lock:
+            held = cls._searcher_cache.get(self._searcher_key)
+            if held is None or held[2] != self._store_stamp():  # (else: an instance sharing the index already has it)
+                held = cls._searcher_cache[self._searcher_key] = self._open_store()
+            self._searcher, self.row_offset, self._store_mtime = held
+
+    def store_is_current(self) -> bool:
+        """The resident store is the token store on disk (asked by the builder BEFORE it writes, under the build lock and
+        `_registry_lock`, which it keeps until note_appended has returned)."""
+        return self._searcher is not None and self._store_stamp() == self._store_mtime
+
+    def note_appended(self, tokens: np.ndarray, doc_ptr: np.ndarray, first_pid: int) -> None:
+        """IncrementalColBERTBuilder, after it has written `tokens` / `doc_ptr` (the new documents' own offsets, pids from
+        `first_pid`) behind a store that was current (store_is_current) and their lines behind the meta file: the same rows
+        go behind the resident store (amdr_maxsim_add), the pid map is read again, and the files' mtimes are remembered —
+        what this process wrote IS the resident state, so nothing is reloaded.  The caller holds `_registry_lock` across
+        the check, the write and this call: a search that sees the new mtime meanwhile waits in _reload_searcher and then
+        finds the cache entry current.  Should the resident store still not end where the new rows begin (a caller that
+        did not hold the lock), it is read from the file instead of being added to twice."""
+        cls = type(self)
+        with cls._registry_lock:
+            if self._searcher is not None and self._searcher.info()[0] == int(first_pid) - self.row_offset:
+                self._searcher.add(tokens, doc_ptr)
+                self._store_mtime = self._store_stamp()
+                cls._searcher_cache[self._searcher_key] = (self._searcher, self.row_offset, self._store_mtime)
+            else:
+                held = cls._searcher_cache[self._searcher_key] = self._open_store()
+                self._searcher, self.row_offset, self._store_mtime = held
+            self._meta_mtime = None
+            self._load_meta_and_collection()
 
     def search(self, query: str, top_k: int = 5) -> List[Tuple[LawChunk, float]]:
         if not self.enabled:
