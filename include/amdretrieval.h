@@ -448,7 +448,9 @@ int amdr_fuse_compact_device(int32_t nq, int32_t max_out, int32_t w, const int64
  *   final    = ((double)semantic * decay[depth]) * weight[rel] * conf_eff
  * and the top k <= AMDR_MAX_K by final are written, ties -> earlier walk position: out_count [n], out_rows i64,
  * out_final f64, out_semantic f32, out_depth i32, out_rel i32, out_conf f64 (conf_eff) [n, k] (past out_count: -1 /
- * 0).  The only difference from the host path: numpy computes |q| with BLAS in its own summation order.
+ * 0).  Non-finite scores: a NaN final ranks behind every number (-inf included), NaN entries in walk order among
+ * themselves; +-inf order as numbers.  Every valid found node appears exactly once and out_count = min(valid, k).
+ * The only difference from the host path: numpy computes |q| with BLAS in its own summation order.
  * The dense handle gives the resident chunk matrix (same device; its rows are the chunk rows above). */
 typedef struct amdr_graph_params {
   int32_t limit;

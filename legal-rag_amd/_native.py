@@ -785,14 +785,15 @@ class GraphIndex(_Handle):
                   float(conf[q, i])) for i in range(int(oc[q]))] for q in range(nq)]
 
     def search(self, dense: "DenseIndex", Q: np.ndarray, seeds: np.ndarray, seed_count: np.ndarray, seed_n: int, k: int,
-               params: GraphParams):
+               params: GraphParams, out=None):
         """Host-pointer search: Q f32 [nq, d], seeds i64 chunk rows [nq, ld], seed_count i32 [nq] -> dict of
-        count [nq] and rows / final / semantic / depth / relation / edge_conf [nq, k]."""
+        count [nq] and rows / final / semantic / depth / relation / edge_conf [nq, k] (`out`: the caller's arrays of
+        _outputs(nq, k), written in place)."""
         Q = _c(Q, np.float32).reshape(-1, dense.d)
         nq = Q.shape[0]
         seeds = _c(seeds, np.int64).reshape(nq, -1)
         seed_count = _c(seed_count, np.int32).reshape(nq)
-        out = self._outputs(nq, k)
+        out = self._outputs(nq, k) if out is None else out
         _check(load().amdr_graph_search(self._h, dense._h, Q.ctypes.data, seeds.ctypes.data, seed_count.ctypes.data,
                                         seeds.shape[1], int(seed_n), nq, int(k), C.byref(params),
                                         *(out[n].ctypes.data for n in self.OUTS)), "amdr_graph_search")

@@ -17,7 +17,9 @@
 //                              semantic = dot / (qn * rn + 1e-9f) in fp32 with dot = dense_row_dot (the instruction
 //                              sequence of amdr_dense_score_rows), final = ((double)semantic * decay[depth]) *
 //                              relw[rel] * conf in fp64; then the top-k by final, ties -> earlier walk position
-//                              (Python's stable sort), by rank counting over the <= limit entries in LDS.
+//                              (Python's stable sort), by rank counting over the <= limit entries in LDS.  A NaN
+//                              final ranks behind every number, NaN entries in walk order ("NaN last", as the
+//                              other channels).
 //
 // The one difference from the host path: qn = sqrtf(<q, q>) here, numpy's norm (BLAS, its own summation order) there —
 // the semantic term may differ in the last bit.  Built with -ffp-contract=off (Makefile EXACT): qn * rn + 1e-9f and
@@ -40,6 +42,8 @@ constexpr int kGraphMaxSeeds = 1024;    // seed rows per query
 constexpr int kWalkThreads = 256;
 constexpr int kScoreThreads = 512;
 constexpr unsigned kEpochMax = 0xFFFFFFF0u;
+constexpr size_t kLdsDefault = 65536;   // LDS a launch gets without hipFuncAttributeMaxDynamicSharedMemorySize
+constexpr size_t kStaticLdsMax = 64;    // bound on the __shared__ scalars of either kernel, which count against it
 
 struct GraphTables {  // device copies of the handle's tables
   const long long* node_ptr;
@@ -348,7 +352,9 @@ __global__ __launch_bounds__(kScoreThreads) void graph_score_select_kernel(Graph
     }
   }
   __syncthreads();
-  // rank = entries ahead of i: larger final, or equal final and earlier in the walk
+  // rank = entries ahead of i: larger final, or equal final and earlier in the walk.  A NaN final compares false both
+  // ways: it ranks behind every number (-inf included), NaN entries among themselves in walk order, so that every
+  // valid entry has a rank of its own.
   const size_t o = (size_t)gq * a.k;
   for (int i = tid; i < F; i += kScoreThreads) {
     const int r = srow[i];
@@ -356,9 +362,16 @@ __global__ __launch_bounds__(kScoreThreads) void graph_score_select_kernel(Graph
     atomicAdd(&s_valid, 1);
     const double fi = sfin[i];
     int rank = 0;
-    for (int j = 0; j < F; ++j) {
-      const double fj = sfin[j];
-      rank += (srow[j] >= 0) & ((fj > fi) | ((fj == fi) & (j < i)));
+    if (fi == fi) {  // a number: a NaN fj is never ahead of it
+      for (int j = 0; j < F; ++j) {
+        const double fj = sfin[j];
+        rank += (srow[j] >= 0) & ((fj > fi) | ((fj == fi) & (j < i)));
+      }
+    } else {  // NaN: every number is ahead, and the NaN entries before it
+      for (int j = 0; j < F; ++j) {
+        const double fj = sfin[j];
+        rank += (srow[j] >= 0) & ((fj == fj) | (j < i));
+      }
     }
     if (rank < a.k) {
       const int e = f_edge[i];
@@ -494,7 +507,7 @@ int launch_walk(amdr_graph* h, int w, const amdr_graph_params_t* p, const int* r
   a.f_count = W.f_count.as<int>();
   const size_t lds = ((size_t)2 * a.fcap + seed_n + (a.lds_claims ? h->n_nodes : 0)) * sizeof(int);
   const int grid = a.lds_claims ? ng : (ng < W.blocks ? ng : W.blocks);
-  if (lds > 65536)
+  if (lds + kStaticLdsMax > kLdsDefault)
     AMDR_HIP(hipFuncSetAttribute((const void*)graph_walk_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   hipLaunchKernelGGL(graph_walk_kernel, dim3(grid), dim3(kWalkThreads), lds, st, tables_of(h), a);
   AMDR_HIP(hipGetLastError());
@@ -529,7 +542,7 @@ int launch_score(amdr_graph* h, int w, const float* X, long n_dense, int d, cons
   a.out_rel = out_rel;
   a.out_conf = out_conf;
   const size_t lds = (size_t)limit * (sizeof(double) + sizeof(float) + sizeof(int));
-  if (lds > 65536)
+  if (lds + kStaticLdsMax > kLdsDefault)  // limit 4096: 65 536 B dynamic + the static words
     AMDR_HIP(hipFuncSetAttribute((const void*)graph_score_select_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                  (int)lds));
   hipLaunchKernelGGL(graph_score_select_kernel, dim3(ng), dim3(kScoreThreads), lds, st, tables_of(h), a);

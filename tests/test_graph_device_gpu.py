@@ -8,6 +8,7 @@ import types
 import numpy as np
 import pytest
 
+from graph_adversary import random_graph
 from test_graph import G, HostStore, make_cfg, node_view
 
 pytestmark = pytest.mark.gpu
@@ -71,33 +72,6 @@ def test_device_walk_matches_reference(case):
     got = device_walk_views(gs, g, t, [starts], **a)[0]
     assert got == case["nodes"]
     g.close()
-
-
-def random_graph(rng, n, path):
-    rels = ["next", "prev", "cite", "defined_by", "ref", "amend", "neighbor", "x"]
-    with open(path, "w", encoding="utf-8") as f:
-        for i in range(n):
-            nbs, dl = [], []
-            for _ in range(rng.choice([0, 0, 1, 2, 3, 5, 8])):
-                r = rng.random()
-                if r < 0.08:
-                    dst = str(i)                          # self edge
-                elif r < 0.16:
-                    dst = f"absent{rng.randrange(n)}"     # destination that is no stored node
-                elif r < 0.22 and dl:
-                    dst = rng.choice(dl)                  # duplicate edge
-                else:
-                    dst = str(rng.randrange(n))
-                dl.append(dst)
-                if rng.random() < 0.15:
-                    nbs.append(dst)                      # bare string: relation "neighbor", conf 1.0
-                else:
-                    e = {"id": dst, "relation": rng.choice(rels), "conf": rng.choice([0, 0.2, 0.5, 0.7, 0.9, 1.0, None])}
-                    if rng.random() < 0.3:
-                        e["evidence"] = {"span": "ev"}
-                    nbs.append(e)
-            meta = {"_edge_conf": rng.choice([0.3, 0.8])} if rng.random() < 0.2 else {}
-            f.write(json.dumps({"article_id": str(i), "neighbors": nbs, "meta": meta}) + "\n")
 
 
 def test_device_walk_equals_host_walk_on_random_graphs(tmp_path):

@@ -1147,3 +1147,22 @@ def test_dense_score_rows_and_edges(nat):
     assert sorted(i[0, :3].tolist()) == [0, 1, 2] and np.all(i[0, 3:] == -1)
     s0, i0 = idx.search(np.zeros((0, 768), np.float32), 5)
     assert s0.shape == (0, 5) and i0.shape == (0, 5)
+
+
+@pytest.mark.parametrize("d", [4, 252, 256, 260, 1024])
+def test_dense_score_rows_at_the_edges_of_the_row_dot(nat, d):
+    """dense_row_dot takes 256 columns per pass, four per lane: one lane only (d = 4), a partial single pass (252), one
+    full pass (256), a second pass of one lane (260), four full passes (1024)."""
+    rng = np.random.default_rng(d)
+    n, nq = 300, 3
+    X, Q = unit_rows(rng, n, d), unit_rows(rng, nq, d)
+    idx = nat.DenseIndex(X)
+    rows = rng.integers(0, n, size=(nq, 41))
+    rows[:, 0], rows[:, 1], rows[:, 2], rows[:, 3] = -1, n, 0, n - 1
+    got = idx.score_rows(Q, rows)
+    ref = Q.astype(np.float64) @ X.astype(np.float64).T
+    inside = (rows >= 0) & (rows < n)
+    assert inside.sum() == nq * 39
+    exp = np.take_along_axis(ref, np.where(inside, rows, 0), 1)
+    assert np.max(np.abs(got.astype(np.float64) - exp)[inside]) <= TOL
+    assert np.all(got[~inside] == -np.finfo(np.float32).max)
