@@ -146,11 +146,48 @@ int amdr_dense_destroy(amdr_dense_t* h);
  * with duplicates counted, so scores are bit-identical to rank_bm25's numpy
  * expression.  Ties -> lower doc id; zero-score docs ARE returned.
  * term_ptr[n_terms+1] indexes post_doc/post_tf (ascending doc id per term);
- * idf already has rank_bm25's epsilon floor applied; every idf must be finite (AMDR_EINVAL otherwise). */
+ * idf already has rank_bm25's epsilon floor applied; every idf must be finite (AMDR_EINVAL otherwise).
+ * Resident per posting: doc id (4 B) + fp64 factor (8 B), which the searches read, + tf (4 B); per document: its length
+ * (4 B).  tf and the lengths are kept only for amdr_bm25_add, which recomputes every factor from them: 16 B per posting
+ * of HBM instead of 12, + 4 B per document. */
 int amdr_bm25_create(const int64_t* term_ptr, const int32_t* post_doc, const int32_t* post_tf,
                      const double* idf, const int32_t* doc_len, int64_t n_terms, int64_t n_docs,
                      double avgdl, double k1, double b, int32_t device, amdr_bm25_t** out);
 int amdr_bm25_ndocs(const amdr_bm25_t* h, int64_t* n);
+/* Append n_add documents (replaces the full re-fit + reload of an ingest, legalrag/retrieval/builders/
+ * incremental_bm25_builder.py:70-79 followed by bm25_retriever.py:44-56).  n_terms >= the handle's: old term ids keep
+ * their meaning, new terms take the ids behind them.  term_ptr_add[n_terms+1] / post_doc_add / post_tf_add: the added
+ * documents' own term-major CSR over the NEW term table, post_doc_add holding local ids 0 .. n_add-1, strictly ascending
+ * per term; doc_len_add[n_add]; idf[n_terms]: the whole new vector, floor applied, computed by the caller as for create
+ * (native code takes no logarithm); avgdl: the caller's new value.  New document ids are n_docs .. n_docs+n_add-1.
+ * Afterwards the handle is what amdr_bm25_create makes of the concatenated index: term_ptr, post_doc, post_w and idf are
+ * the same bytes, hence the same ids and score bits from every entry point.  N and avgdl are corpus-global, so every
+ * factor changes: the call is one device pass over ALL resident postings (each term's list grows at its tail, each factor
+ * is recomputed with the new avgdl) plus host work proportional to the add — it validates the add's arrays only.
+ * AMDR_EINVAL: null handle, n_add < 0, null arrays with n_add > 0, n_terms below the handle's, term_ptr_add[0] != 0 or
+ * not monotone, a post_doc_add outside [0, n_add) or not strictly ascending within a term, a non-finite idf, a
+ * non-finite or non-positive avgdl, n_docs + n_add >= 2^31; n_add == 0 is a no-op that reads nothing.  A failed add
+ * (AMDR_EINVAL, AMDR_ENOMEM, AMDR_EHIP) leaves the handle as it was and searchable.  The price of that: the new arrays
+ * are built beside the old ones and swapped in after the handle's stream has finished, so for the length of the call
+ * the device holds a second copy of the index (16 B per posting, 4 B per document, 16 B per term) and the call can
+ * return AMDR_ENOMEM where the index itself fits.  Runs inside the handle's mutex: host-pointer searches from other
+ * threads serialise against it.  It is a mutation in the sense of the rule at the top of this file: "_device" work of
+ * the handle still in flight is the caller's to finish first (the arrays it reads are freed); workspaces are sized per
+ * call from n_docs, so an eager "_device" call after an add grows its workspace if it has to (amdr_workspace_growths
+ * shows it), and a captured graph holds the old arrays and sizes and must be re-reserved (amdr_bm25_reserve) and
+ * captured again.  The arrival counters of the one-launch serving step stay as they are. */
+int amdr_bm25_add(amdr_bm25_t* h, const int64_t* term_ptr_add, const int32_t* post_doc_add, const int32_t* post_tf_add,
+                  const double* idf, const int32_t* doc_len_add, int64_t n_terms, int64_t n_add, double avgdl);
+/* out6: [0] n_docs, [1] n_terms, [2] nnz (postings), [3] adds so far, [4] the merge kernel's tile length in postings,
+ *       [5] 0 (reserved) */
+int amdr_bm25_info(amdr_bm25_t* h, int64_t* out6);
+/* Device time of the merge kernel of the last successful amdr_bm25_add, in ms between two events on the handle's stream
+ * (scripts/bench_bm25_add.py sets it against the kernel's algorithmic bytes); -1 before the first add. */
+int amdr_bm25_add_kernel_ms(amdr_bm25_t* h, double* ms);
+/* Copies the resident arrays to the host: term_ptr[n_terms+1], post_doc / post_tf / post_w[nnz], idf[n_terms],
+ * doc_len[n_docs] (sizes from amdr_bm25_info); any pointer may be null.  The only way to see what a handle holds. */
+int amdr_bm25_read(amdr_bm25_t* h, int64_t* term_ptr, int32_t* post_doc, int32_t* post_tf, double* post_w, double* idf,
+                   int32_t* doc_len);
 int amdr_bm25_reserve(amdr_bm25_t* h, int32_t nq_max, int32_t k_max, int64_t total_terms_max);
 /* Host-only (no device is touched): on a corpus of n_docs documents, out2[0] = the slab-list bytes amdr_bm25_reserve
  * (nq_max, k_max) sizes for the "_device" calls, out2[1] = the bytes amdr_bm25_search_device(nq, k) uses.  A test holds

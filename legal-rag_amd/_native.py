@@ -35,7 +35,7 @@ SIGNATURES = {
     "amdr_dense_ntotal": "PP", "amdr_dense_dim": "PP", "amdr_dense_reserve": "Pii", "amdr_dense_search": "PPiiPP",
     "amdr_dense_search_device": "PPiiPPP", "amdr_dense_search_fuse_device": "PPiiPPPPiPPPPPPPP", "amdr_hybrid_small_device": "PPPPPiiiPPPPPPPPPPPP", "amdr_dense_small_create": "PP", "amdr_dense_small_approx_device": "PPiPlPP", "amdr_dense_small_destroy": "P", "amdr_dense_two_pass_fallbacks": "PP", "amdr_dense_read_rows": "PllP", "amdr_dense_score_rows": "PPiPiP",
     "amdr_dense_plan_info": "PiiPi", "amdr_dense_workspace_plan": "liiiiiP", "amdr_dense_hi_counters": "PP", "amdr_dense_image_build": "P", "amdr_dense_image_drop": "P", "amdr_dense_image_info": "PP", "amdr_dense_profile_begin": "Pi", "amdr_dense_profile_end": "PPP", "amdr_dense_destroy": "P",
-    "amdr_bm25_create": "PPPPPlldddiP", "amdr_bm25_ndocs": "PP", "amdr_bm25_reserve": "Piil", "amdr_bm25_workspace_plan": "liiiiP", "amdr_bm25_plan_info": "PiiPi",
+    "amdr_bm25_create": "PPPPPlldddiP", "amdr_bm25_ndocs": "PP", "amdr_bm25_add": "PPPPPPlld", "amdr_bm25_info": "PP", "amdr_bm25_add_kernel_ms": "PP", "amdr_bm25_read": "PPPPPPP", "amdr_bm25_reserve": "Piil", "amdr_bm25_workspace_plan": "liiiiP", "amdr_bm25_plan_info": "PiiPi",
     "amdr_bm25_search": "PPPiiPP", "amdr_bm25_search_device": "PPPiiPPP", "amdr_bm25_scores": "PPPiP",
     "amdr_bm25_destroy": "P",
     "amdr_tokenizer_create": "PPlP", "amdr_tokenizer_encode": "PPPiPlPP", "amdr_tokenizer_encode_joined": "PPliPlPP", "amdr_tokenizer_encode_ptrs": "PPPiPlPP", "amdr_tokenizer_spans": "PlPPiP",
@@ -402,6 +402,44 @@ class BM25Index(_Handle):
                                     C.c_double(avgdl), C.c_double(k1), C.c_double(b), C.c_int32(device),
                                     C.byref(self._h)), "amdr_bm25_create")
         self._arrs = None  # the library holds its own device copy
+
+    def add(self, term_ptr_add, post_doc_add, post_tf_add, idf, doc_len_add, avgdl: float) -> None:
+        """Append documents (amdr_bm25_add): the added documents' own term-major CSR over the new term table (local
+        document ids from 0; len(term_ptr_add) - 1 = the new number of terms >= n_terms), their lengths, the WHOLE new
+        idf vector and the new avgdl.  Afterwards the index is what BM25Index makes of the concatenated arrays, bit for
+        bit.  A "_device" caller finishes its work first and reserves again."""
+        tp, pd, pt = _c(term_ptr_add, np.int64), _c(post_doc_add, np.int32), _c(post_tf_add, np.int32)
+        idf_, dl = _c(idf, np.float64), _c(doc_len_add, np.int32)
+        if tp.ndim != 1 or tp.shape[0] < 1 or idf_.shape != (tp.shape[0] - 1,) or pd.shape != pt.shape:
+            raise ValueError("add: term_ptr_add [V + 1], idf [V], post_doc_add and post_tf_add of one length")
+        if dl.shape[0] and (pd.shape[0] < int(tp[-1])):
+            raise ValueError("add: term_ptr_add points past the postings")
+        _check(load().amdr_bm25_add(self._h, _p(tp, C.c_int64), _p(pd, C.c_int32), _p(pt, C.c_int32), _p(idf_, C.c_double),
+                                    _p(dl, C.c_int32), C.c_int64(tp.shape[0] - 1), C.c_int64(dl.shape[0]),
+                                    C.c_double(avgdl)), "amdr_bm25_add")
+        self.n_docs, self.n_terms = self.info()[:2]
+
+    def info(self) -> Tuple[int, int, int, int, int, int]:
+        """(n_docs, n_terms, postings, adds so far, the merge kernel's tile length in postings, 0)."""
+        out = (C.c_int64 * 6)()
+        _check(load().amdr_bm25_info(self._h, out), "amdr_bm25_info")
+        return tuple(int(x) for x in out)
+
+    def add_kernel_ms(self) -> float:
+        """Device time of the last add's merge kernel in ms (-1 before the first add)."""
+        ms = C.c_double(-1.0)
+        _check(load().amdr_bm25_add_kernel_ms(self._h, C.byref(ms)), "amdr_bm25_add_kernel_ms")
+        return float(ms.value)
+
+    def read(self):
+        """The resident arrays, copied to the host: (term_ptr, post_doc, post_tf, post_w, idf, doc_len)."""
+        n, V, nnz = self.info()[:3]
+        out = (np.empty(V + 1, np.int64), np.empty(nnz, np.int32), np.empty(nnz, np.int32), np.empty(nnz, np.float64),
+               np.empty(V, np.float64), np.empty(n, np.int32))
+        _check(load().amdr_bm25_read(self._h, _p(out[0], C.c_int64), _p(out[1], C.c_int32), _p(out[2], C.c_int32),
+                                     _p(out[3], C.c_double), _p(out[4], C.c_double), _p(out[5], C.c_int32)),
+               "amdr_bm25_read")
+        return out
 
     @staticmethod
     def pack_queries(queries: Sequence[Sequence[int]]) -> Tuple[np.ndarray, np.ndarray]:

@@ -13,6 +13,7 @@ Scoring runs on the GPU (csrc/bm25.hip) — there is no host scoring path.
 from __future__ import annotations
 
 import math
+from itertools import chain, islice
 from typing import Dict, List, Optional, Sequence
 
 import numpy as np
@@ -31,6 +32,29 @@ def shard_csr(term_ptr, post_doc, post_tf, doc_len, lo: int, hi: int):
     np.add.at(cnt, term_of[keep] + 1, 1)
     return (np.cumsum(cnt).astype(np.int64), (post_doc[keep] - lo).astype(np.int32), np.ascontiguousarray(post_tf[keep]),
             np.ascontiguousarray(doc_len[lo:hi]))
+
+
+def docs_csr(doc_freqs: Sequence[Dict[str, int]], vocab: Dict[str, int]):
+    """Term-major CSR (term_ptr [V + 1], post_doc, post_tf) of documents given as {word: tf} dicts, local ids from 0,
+    ascending per term — to_csr()'s arrays for these documents, built by numpy (a stable sort by term of the
+    document-major postings) without a per-posting interpreter loop."""
+    V = len(vocab)
+    nnz = sum(map(len, doc_freqs))
+    terms = np.fromiter(map(vocab.__getitem__, chain.from_iterable(doc_freqs)), dtype=np.int64, count=nnz)
+    tfs = np.fromiter(chain.from_iterable(map(dict.values, doc_freqs)), dtype=np.int32, count=nnz)
+    docs = np.repeat(np.arange(len(doc_freqs), dtype=np.int32), np.fromiter(map(len, doc_freqs), dtype=np.int64,
+                                                                          count=len(doc_freqs)))
+    order = np.argsort(terms, kind="stable")
+    term_ptr = np.zeros(V + 1, dtype=np.int64)
+    np.cumsum(np.bincount(terms, minlength=V), out=term_ptr[1:])
+    return term_ptr, np.ascontiguousarray(docs[order]), np.ascontiguousarray(tfs[order])
+
+
+def concat_term_ptr(old_ptr, add_ptr):
+    """term_ptr of the concatenated index: both tables are prefix sums over the same term ids, the old one extended by
+    its last value over the new terms (csrc/bm25_add_rule.hpp computes the same on the device)."""
+    old_ptr, add_ptr = np.asarray(old_ptr, dtype=np.int64), np.asarray(add_ptr, dtype=np.int64)
+    return old_ptr[np.minimum(np.arange(len(add_ptr)), len(old_ptr) - 1)] + add_ptr
 
 
 class BM25Okapi:
@@ -76,7 +100,7 @@ class BM25Okapi:
     # -- device side --------------------------------------------------------
     def __getstate__(self):
         st = dict(self.__dict__)
-        for k in ("_vocab", "_gpu", "_gpu_device", "_tokenizer_id"):
+        for k in ("_vocab", "_gpu", "_gpu_device", "_tokenizer_id", "_nd", "_total"):
             st.pop(k, None)
         return st
 
@@ -86,6 +110,84 @@ class BM25Okapi:
             v = {w: t for t, w in enumerate(self.idf.keys())}
             self.__dict__["_vocab"] = v
         return v
+
+    def _doc_frequencies(self) -> Dict[str, int]:
+        """{word: number of documents holding it} in vocabulary order — __init__'s `nd`, rebuilt once from doc_freqs
+        (one pass over the postings) and then kept up to date by add_documents; not pickled."""
+        nd = self.__dict__.get("_nd")
+        if nd is None:
+            nd = dict.fromkeys(self.idf, 0)
+            for freqs in self.doc_freqs:
+                for word in freqs:
+                    nd[word] += 1
+            self.__dict__["_nd"] = nd
+            self.__dict__["_total"] = sum(self.doc_len)
+        return nd
+
+    def add_documents(self, corpus: Sequence[Sequence[str]]) -> int:
+        """Append tokenised documents; afterwards this object equals BM25Okapi(old corpus + corpus): the idf dict in the
+        same key order with the same bits (math.log per term and a sequential sum in vocabulary order, as __init__),
+        avgdl, average_idf, doc_len, doc_freqs, corpus_size.  O(V + added tokens) after the one-time document-frequency
+        cache.  A resident unsharded index (gpu()) takes the same documents in place (BM25Index.add: the added documents'
+        CSR, the new idf vector and avgdl); a row shard is dropped and uploaded again on its next use — the in-place
+        append on a row-sharded index is not supported."""
+        corpus = list(corpus)
+        if not corpus:
+            return 0
+        if self.corpus_size == 0:
+            raise ValueError("add_documents: fit the index on a corpus first")
+        nd = self._doc_frequencies()
+        n_terms_old = len(nd)
+        total = self.__dict__["_total"]
+        added: List[Dict[str, int]] = []
+        for document in corpus:
+            self.doc_len.append(len(document))
+            total += len(document)
+            freqs: Dict[str, int] = {}
+            for word in document:
+                freqs[word] = freqs.get(word, 0) + 1
+            added.append(freqs)
+            for word in freqs:
+                nd[word] = nd.get(word, 0) + 1
+        self.doc_freqs.extend(added)
+        self.corpus_size += len(corpus)
+        self.__dict__["_total"] = total
+        self.avgdl = total / self.corpus_size
+        idf: Dict[str, float] = {}
+        idf_sum = 0
+        negative = []
+        for word, freq in nd.items():
+            v = math.log(self.corpus_size - freq + 0.5) - math.log(freq + 0.5)
+            idf[word] = v
+            idf_sum += v
+            if v < 0:
+                negative.append(word)
+        self.average_idf = idf_sum / len(idf)
+        eps = self.epsilon * self.average_idf
+        for word in negative:
+            idf[word] = eps
+        self.idf = idf
+        vocab = self.__dict__.get("_vocab")
+        if vocab is not None and len(vocab) == n_terms_old:  # new terms take the ids behind the old ones
+            for word in islice(nd, n_terms_old, None):
+                vocab[word] = len(vocab)
+        else:
+            self.__dict__.pop("_vocab", None)
+        g = self.__dict__.get("_gpu")
+        if g is not None:
+            if self.__dict__.get("_gpu_device", (None, None))[1] is None:
+                term_ptr, post_doc, post_tf = docs_csr(added, self.vocab())
+                try:
+                    g.add(term_ptr, post_doc, post_tf, np.fromiter(idf.values(), dtype=np.float64, count=len(idf)),
+                          np.asarray(self.doc_len[-len(corpus):], dtype=np.int32), float(self.avgdl))
+                except Exception:  # the resident index is unchanged and now behind this object: upload again on next use
+                    self.__dict__.pop("_gpu", None)
+                    self.__dict__.pop("_gpu_device", None)
+                    raise
+            else:
+                self.__dict__.pop("_gpu", None)
+                self.__dict__.pop("_gpu_device", None)
+        return len(corpus)
 
     def to_csr(self):
         vocab = self.vocab()

@@ -11,6 +11,12 @@
 // slab is then ranked in place (score desc, ties -> lower doc id, zero-score
 // docs included) with the wave-level selector of topk.hpp.
 // Algorithmic bytes per query: sum_t df(t)*12 (posting doc id + precomputed fp64 factor).
+//
+// amdr_bm25_add appends documents.  N and avgdl are corpus-global, so every factor changes: the add is ONE pass over the
+// resident postings (bm25_merge_kernel) that interleaves each term's old list with the added documents' list behind it
+// and recomputes post_w with the new avgdl, next to the data.  post_tf and doc_len stay resident for that (16 B per
+// posting instead of 12, + 4 B per document).  The new arrays are built beside the old ones and swapped in after the
+// stream has finished: a failed add leaves the handle as it was.
 #include "common.hpp"
 #include "topk.hpp"
 #include "topk_merge.hpp"
@@ -20,21 +26,26 @@
 #include <cstdlib>
 #include <mutex>
 #include <new>
+#include <type_traits>
 #include <vector>
 
 
+#include "bm25_add_rule.hpp"
 #include "bm25_core.hpp"
 
 using namespace amdr;
 
 struct amdr_bm25 {
   int device = 0;
-  int64_t n_terms = 0, n_docs = 0, nnz = 0;
+  int64_t n_terms = 0, n_docs = 0, nnz = 0, adds = 0;
   double avgdl = 0, k1 = 1.5, b = 0.75;
+  double add_kernel_ms = -1;  // event time of the last add's merge kernel (amdr_bm25_add_kernel_ms)
   long long* term_ptr = nullptr;
   int* post_doc = nullptr;
   double* post_w = nullptr;  // tf*(k1+1) / (tf + k1*(1 - b + b*len/avgdl)) per posting, fp64
   double* idf = nullptr;
+  int* post_tf = nullptr;  // resident for amdr_bm25_add: the factors are recomputed from (tf, doc_len, avgdl)
+  int* doc_len = nullptr;
   hipStream_t stream = nullptr;
   std::mutex mu;
   DevBuf part[2], qterms, qptr, sbuf, ibuf, full;  // part[0]: "_device" calls, part[1]: host-pointer calls (see dense.hip)
@@ -170,6 +181,81 @@ int upload(T** dst, const T* src, size_t count) {
   return AMDR_OK;
 }
 
+// ---- amdr_bm25_add: term table and merge ------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void bm25_term_ptr_sum_kernel(const long long* __restrict__ old_ptr, long n_terms_old,
+                                                                const long long* __restrict__ add_ptr, long n_terms_new,
+                                                                long long* __restrict__ new_ptr) {
+  const long t = (long)blockIdx.x * 256 + threadIdx.x;
+  if (t <= n_terms_new) new_ptr[t] = bm_add_term_ptr(old_ptr, n_terms_old, add_ptr, t);
+}
+
+// One block = kBmAddTile consecutive OUTPUT postings (work is divided by postings, not by terms: a Zipfian head term holds
+// every document and a wave per term would serialise on it).  Thread 0 finds the terms of the tile's first and last
+// posting by binary search in the new term table; the table entries between them go to LDS (a tile holds at most
+// kBmAddTile terms that have postings; a window widened by terms WITHOUT postings beyond the LDS room is searched in
+// global memory instead), and every posting finds its term there.  A posting reads 8 B (doc, tf) from the old list or
+// the add's, gathers 4 B of doc_len, and writes 16 B (doc, tf, factor).  No atomics: the result is deterministic.
+__global__ __launch_bounds__(kBmAddThreads) void bm25_merge_kernel(
+    const long long* __restrict__ new_ptr, long n_terms_new, const long long* __restrict__ old_ptr, long n_terms_old,
+    const int* __restrict__ old_doc, const int* __restrict__ old_tf, const long long* __restrict__ add_ptr,
+    const int* __restrict__ add_doc, const int* __restrict__ add_tf, const int* __restrict__ doc_len /* new */,
+    int n_docs_old, long long nnz_new, double avgdl, double k1, double b, int* __restrict__ out_doc,
+    int* __restrict__ out_tf, double* __restrict__ out_w) {
+  __shared__ long long win[kBmAddTile + 2];
+  __shared__ long t_first, t_last;
+  const int tid = threadIdx.x;
+  const long long p0 = (long long)blockIdx.x * kBmAddTile;
+  long long p1 = p0 + kBmAddTile;  // exclusive
+  if (p1 > nnz_new) p1 = nnz_new;
+  if (p0 >= p1) return;
+  if (tid == 0) {
+    long a, z;
+    bm_add_tile_terms(new_ptr, n_terms_new, p0, p1, &a, &z);
+    t_first = a;
+    t_last = z;
+  }
+  __syncthreads();
+  const long t0 = t_first, t1 = t_last;
+  const bool in_lds = bm_add_window_fits(t0, t1);
+  if (in_lds) {
+    for (long i = tid; i <= t1 - t0 + 1; i += kBmAddThreads) win[i] = new_ptr[t0 + i];
+    __syncthreads();
+  }
+  const long long* tab = in_lds ? win : new_ptr;
+  const long base = in_lds ? t0 : 0;
+#pragma unroll
+  for (int u = 0; u < kBmAddPerThread; ++u) {
+    const long long p = p0 + (long long)u * kBmAddThreads + tid;
+    if (p < p1) {
+      const long t = bm_add_term_of(tab, base, t0, t1, p);
+      bool from_add;
+      const long long src = bm_add_source(p, tab[t - base], t, old_ptr, n_terms_old, add_ptr, &from_add);
+      const int doc = from_add ? add_doc[src] + n_docs_old : old_doc[src];
+      const int tf = from_add ? add_tf[src] : old_tf[src];
+      out_doc[p] = doc;
+      out_tf[p] = tf;
+      out_w[p] = bm25_factor(tf, doc_len[doc], avgdl, k1, b);
+    }
+  }
+}
+
+// device arrays of an add in the making: freed unless they were handed to the handle
+struct BmAddBufs {
+  void* p[9] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  ~BmAddBufs() {
+    for (void* q : p)
+      if (q) (void)hipFree(q);
+  }
+  int alloc(int i, size_t bytes) {
+    if (hipMalloc(&p[i], bytes) != hipSuccess) {
+      (void)hipGetLastError();
+      p[i] = nullptr;
+      return fail(AMDR_ENOMEM, "bm25_add: device allocation of %zu B failed", bytes);
+    }
+    return AMDR_OK;
+  }
+};
+
 }  // namespace
 
 extern "C" {
@@ -211,19 +297,13 @@ int amdr_bm25_create(const int64_t* term_ptr, const int32_t* post_doc, const int
   // (this translation unit is built with -ffp-contract=off; IEEE fp64 mul/add/div are
   // correctly rounded on the host as on the device, so the value is the one numpy computes).
   std::vector<double> pw((size_t)nnz);
-  {
-    const double k1p1 = k1 + 1, one_minus_b = 1 - b;
-    for (int64_t p = 0; p < nnz; ++p) {
-      const double qf = (double)post_tf[p];
-      const double dl = (double)doc_len[post_doc[p]];
-      const double denom = qf + k1 * (one_minus_b + b * dl / avgdl);
-      pw[(size_t)p] = qf * k1p1 / denom;
-    }
-  }
+  for (int64_t p = 0; p < nnz; ++p) pw[(size_t)p] = bm25_factor(post_tf[p], doc_len[post_doc[p]], avgdl, k1, b);
   rc = upload(&h->term_ptr, (const long long*)term_ptr, (size_t)n_terms + 1);
   if (!rc) rc = upload(&h->post_doc, post_doc, (size_t)nnz);
   if (!rc) rc = upload(&h->post_w, pw.data(), (size_t)nnz);
   if (!rc) rc = upload(&h->idf, idf, (size_t)n_terms);
+  if (!rc) rc = upload(&h->post_tf, post_tf, (size_t)nnz);
+  if (!rc) rc = upload(&h->doc_len, doc_len, (size_t)n_docs);
   if (!rc && hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess)
     rc = fail(AMDR_EHIP, "bm25_create: stream");
   if (!rc) rc = h->ticket.ensure(64 * sizeof(int));  // arrival counters of the one-launch serving step: zero between launches
@@ -347,6 +427,126 @@ int amdr_bm25_scores(amdr_bm25_t* h, const int32_t* q_terms, const int64_t* q_pt
   return AMDR_OK;
 }
 
+int amdr_bm25_add(amdr_bm25_t* h, const int64_t* term_ptr_add, const int32_t* post_doc_add, const int32_t* post_tf_add,
+                  const double* idf, const int32_t* doc_len_add, int64_t n_terms, int64_t n_add, double avgdl) {
+  AMDR_REQUIRE(h != nullptr, "bm25_add: null handle");
+  AMDR_REQUIRE(n_add >= 0, "bm25_add: n_add=%lld", (long long)n_add);
+  if (n_add == 0) return AMDR_OK;
+  std::lock_guard<std::mutex> g(h->mu);
+  const int bad = bm_add_validate(term_ptr_add, post_doc_add, post_tf_add, idf, doc_len_add, n_terms, n_add, avgdl,
+                                  h->n_terms, h->n_docs);
+  AMDR_REQUIRE(bad == kBmAddOk, "bm25_add: %s", bm_add_error_text(bad));
+  AMDR_HIP(hipSetDevice(h->device));
+  const int64_t nnz_add = term_ptr_add[n_terms], nnz_new = h->nnz + nnz_add, n_docs_new = h->n_docs + n_add;
+  // The new arrays beside the old ones (one padding element each, as upload() leaves: the scoring kernel's clamped
+  // prefetch may touch [count]); 6..8: the add's own CSR on the device, freed when the call returns.
+  enum { TP, PD, PT, PW, IDF, DL, ATP, APD, APT };
+  BmAddBufs nb;
+  int rc = nb.alloc(TP, (size_t)(n_terms + 2) * sizeof(long long));
+  if (!rc) rc = nb.alloc(PD, (size_t)(nnz_new + 1) * sizeof(int));
+  if (!rc) rc = nb.alloc(PT, (size_t)(nnz_new + 1) * sizeof(int));
+  if (!rc) rc = nb.alloc(PW, (size_t)(nnz_new + 1) * sizeof(double));
+  if (!rc) rc = nb.alloc(IDF, (size_t)(n_terms + 1) * sizeof(double));
+  if (!rc) rc = nb.alloc(DL, (size_t)(n_docs_new + 1) * sizeof(int));
+  if (!rc) rc = nb.alloc(ATP, (size_t)(n_terms + 1) * sizeof(long long));
+  if (!rc) rc = nb.alloc(APD, (size_t)(nnz_add + 1) * sizeof(int));
+  if (!rc) rc = nb.alloc(APT, (size_t)(nnz_add + 1) * sizeof(int));
+  if (rc) return rc;
+  hipStream_t st = h->stream;
+  AMDR_HIP(hipMemcpyAsync(nb.p[ATP], term_ptr_add, (size_t)(n_terms + 1) * sizeof(long long), hipMemcpyHostToDevice, st));
+  if (nnz_add) {
+    AMDR_HIP(hipMemcpyAsync(nb.p[APD], post_doc_add, (size_t)nnz_add * sizeof(int), hipMemcpyHostToDevice, st));
+    AMDR_HIP(hipMemcpyAsync(nb.p[APT], post_tf_add, (size_t)nnz_add * sizeof(int), hipMemcpyHostToDevice, st));
+  }
+  if (n_terms) AMDR_HIP(hipMemcpyAsync(nb.p[IDF], idf, (size_t)n_terms * sizeof(double), hipMemcpyHostToDevice, st));
+  AMDR_HIP(hipMemcpyAsync(nb.p[DL], h->doc_len, (size_t)h->n_docs * sizeof(int), hipMemcpyDeviceToDevice, st));
+  AMDR_HIP(hipMemcpyAsync((int*)nb.p[DL] + h->n_docs, doc_len_add, (size_t)n_add * sizeof(int), hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(bm25_term_ptr_sum_kernel, dim3((unsigned)((n_terms + 1 + 255) / 256)), dim3(256), 0, st, h->term_ptr,
+                     (long)h->n_terms, (const long long*)nb.p[ATP], (long)n_terms, (long long*)nb.p[TP]);
+  AMDR_HIP(hipGetLastError());
+  // the merge kernel between two events (amdr_bm25_add_kernel_ms); an event that cannot be made only loses the time
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  struct EvGuard {
+    hipEvent_t* e;
+    ~EvGuard() {
+      for (int i = 0; i < 2; ++i)
+        if (e[i]) (void)hipEventDestroy(e[i]);
+    }
+  } ev_guard{ev};
+  if (hipEventCreate(&ev[0]) != hipSuccess || hipEventCreate(&ev[1]) != hipSuccess) {
+    (void)hipGetLastError();
+    if (ev[0]) (void)hipEventDestroy(ev[0]);
+    ev[0] = ev[1] = nullptr;
+  }
+  if (nnz_new > 0) {
+    const long long blocks = (nnz_new + kBmAddTile - 1) / kBmAddTile;
+    AMDR_REQUIRE(blocks < (1ll << 31), "bm25_add: %lld postings exceed the merge grid", (long long)nnz_new);
+    if (ev[0]) AMDR_HIP(hipEventRecord(ev[0], st));
+    hipLaunchKernelGGL(bm25_merge_kernel, dim3((unsigned)blocks), dim3(kBmAddThreads), 0, st, (const long long*)nb.p[TP],
+                       (long)n_terms, h->term_ptr, (long)h->n_terms, h->post_doc, h->post_tf, (const long long*)nb.p[ATP],
+                       (const int*)nb.p[APD], (const int*)nb.p[APT], (const int*)nb.p[DL], (int)h->n_docs,
+                       (long long)nnz_new, avgdl, h->k1, h->b, (int*)nb.p[PD], (int*)nb.p[PT], (double*)nb.p[PW]);
+    AMDR_HIP(hipGetLastError());
+    if (ev[0]) AMDR_HIP(hipEventRecord(ev[1], st));
+  }
+  AMDR_HIP(hipStreamSynchronize(st));
+  float ms = -1.f;
+  if (!(nnz_new > 0 && ev[0] && hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess)) ms = -1.f;
+  h->add_kernel_ms = (double)ms;
+  // the swap: from here on nothing can fail (the old arrays take the new ones' places in nb and are freed with it)
+  auto swap_in = [&](auto*& held, int i) {
+    void* old = (void*)held;
+    held = reinterpret_cast<std::remove_reference_t<decltype(held)>>(nb.p[i]);
+    nb.p[i] = old;
+  };
+  swap_in(h->term_ptr, TP);
+  swap_in(h->post_doc, PD);
+  swap_in(h->post_tf, PT);
+  swap_in(h->post_w, PW);
+  swap_in(h->idf, IDF);
+  swap_in(h->doc_len, DL);
+  h->n_terms = n_terms;
+  h->n_docs = n_docs_new;
+  h->nnz = nnz_new;
+  h->avgdl = avgdl;
+  ++h->adds;
+  return AMDR_OK;
+}
+
+int amdr_bm25_info(amdr_bm25_t* h, int64_t* out6) {
+  AMDR_REQUIRE(h && out6, "bm25_info: null");
+  std::lock_guard<std::mutex> g(h->mu);
+  out6[0] = h->n_docs;
+  out6[1] = h->n_terms;
+  out6[2] = h->nnz;
+  out6[3] = h->adds;
+  out6[4] = kBmAddTile;
+  out6[5] = 0;
+  return AMDR_OK;
+}
+
+int amdr_bm25_add_kernel_ms(amdr_bm25_t* h, double* ms) {
+  AMDR_REQUIRE(h && ms, "bm25_add_kernel_ms: null");
+  std::lock_guard<std::mutex> g(h->mu);
+  *ms = h->add_kernel_ms;
+  return AMDR_OK;
+}
+
+int amdr_bm25_read(amdr_bm25_t* h, int64_t* term_ptr, int32_t* post_doc, int32_t* post_tf, double* post_w, double* idf,
+                   int32_t* doc_len) {
+  AMDR_REQUIRE(h != nullptr, "bm25_read: null handle");
+  std::lock_guard<std::mutex> g(h->mu);
+  AMDR_HIP(hipSetDevice(h->device));
+  const size_t V = (size_t)h->n_terms, nnz = (size_t)h->nnz, n = (size_t)h->n_docs;
+  if (term_ptr) AMDR_HIP(hipMemcpy(term_ptr, h->term_ptr, (V + 1) * sizeof(long long), hipMemcpyDeviceToHost));
+  if (post_doc && nnz) AMDR_HIP(hipMemcpy(post_doc, h->post_doc, nnz * sizeof(int), hipMemcpyDeviceToHost));
+  if (post_tf && nnz) AMDR_HIP(hipMemcpy(post_tf, h->post_tf, nnz * sizeof(int), hipMemcpyDeviceToHost));
+  if (post_w && nnz) AMDR_HIP(hipMemcpy(post_w, h->post_w, nnz * sizeof(double), hipMemcpyDeviceToHost));
+  if (idf && V) AMDR_HIP(hipMemcpy(idf, h->idf, V * sizeof(double), hipMemcpyDeviceToHost));
+  if (doc_len && n) AMDR_HIP(hipMemcpy(doc_len, h->doc_len, n * sizeof(int), hipMemcpyDeviceToHost));
+  return AMDR_OK;
+}
+
 int amdr_bm25_destroy(amdr_bm25_t* h) {
   if (!h) return AMDR_OK;
   (void)hipSetDevice(h->device);
@@ -358,6 +558,8 @@ int amdr_bm25_destroy(amdr_bm25_t* h) {
   if (h->post_doc) (void)hipFree(h->post_doc);
   if (h->post_w) (void)hipFree(h->post_w);
   if (h->idf) (void)hipFree(h->idf);
+  if (h->post_tf) (void)hipFree(h->post_tf);
+  if (h->doc_len) (void)hipFree(h->doc_len);
   h->part[0].release();
   h->part[1].release();
   h->qterms.release();

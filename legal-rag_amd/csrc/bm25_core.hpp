@@ -17,6 +17,17 @@ constexpr int kBmArgmaxK = 96;  // deepest k ever ranked by arg-max rounds (one 
 __host__ __device__ inline bool bm_use_argmax(int k, int slab) {
   return slab <= 2048 && (k <= 16 || (k <= kBmArgmaxK && k * ((slab + 63) >> 6) <= 480));
 }
+// Per-posting factor of rank_bm25's expression, tf*(k1+1) / (tf + k1*(1 - b + b*len/avgdl)), operand for operand in
+// numpy's order.  The one source of amdr_bm25_create's host loop and of the merge kernel of amdr_bm25_add (both built
+// with -ffp-contract=off; IEEE fp64 mul/add/div are correctly rounded on the host as on the device, so the value is the
+// one numpy computes).
+__host__ __device__ inline double bm25_factor(int tf, int doc_len, double avgdl, double k1, double b) {
+  const double k1p1 = k1 + 1, one_minus_b = 1 - b;
+  const double qf = (double)tf;
+  const double dl = (double)doc_len;
+  const double denom = qf + k1 * (one_minus_b + b * dl / avgdl);
+  return qf * k1p1 / denom;
+}
 constexpr int kBmTok = 32;  // query tokens resolved per group (lanes fetch them in parallel)
 constexpr int kBmOneWaveDocs = 2048;  // slabs up to this size are scored and ranked by ONE wave (<= 32 scores per lane)
 

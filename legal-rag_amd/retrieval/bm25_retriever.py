@@ -15,13 +15,20 @@ hybrid layer stamps it into score_breakdown); `search(..., tokens=)` takes the
 caller's own tokens; an index whose recorded tokenizer is "char" or "dict" is
 queried in the same mode so that index and query tokens stay consistent — and,
 when neither jieba nor a registered segmenter exists, its Han queries are cut by
-the native batched tokenisers (host and device) in that mode."""
+the native batched tokenisers (host and device) in that mode.
+
+Loaded retrievers are kept in a process-wide weak registry, keyed by resolved index file and device
+(`BM25Retriever.live`): IncrementalBM25Builder finds the live retriever of the file it has rewritten there and appends
+the new documents behind its resident postings (`append_in_place`, amdr_bm25_add) instead of leaving it to reload the
+whole index.  Not on a row-sharded index (cfg.retrieval.shard = "rows"): that one reloads as before."""
 from __future__ import annotations
 
 import threading
+import weakref
+from itertools import islice
 from pathlib import Path
 import logging
-from typing import List, Optional, Sequence, Tuple
+from typing import ClassVar, List, Optional, Sequence, Tuple
 
 from .. import artifacts, text
 from ..bm25_model import BM25Okapi
@@ -34,6 +41,10 @@ STAND_INS = ("char", "dict")  # recorded tokenizer ids of the declared inexact H
 
 
 class BM25Retriever:
+    # loaded instances by (resolved index file, device); weak: a retriever nobody holds any more is not kept alive
+    _live: ClassVar["weakref.WeakValueDictionary"] = weakref.WeakValueDictionary()
+    _live_lock: ClassVar[threading.Lock] = threading.Lock()
+
     def __init__(self, cfg):
         self.cfg = cfg
         rcfg = cfg.retrieval
@@ -47,6 +58,17 @@ class BM25Retriever:
         self.index_tokenizer: Optional[str] = None  # id recorded in bm25.pkl (None: reference-built)
         self._tls = threading.local()                 # per-thread: did the last query use the stand-in?
         self.shard = None                             # sharding.ShardSpec in a row-sharded deployment
+        self.appends = 0                              # in-place appends so far (part of the hybrid stage's key)
+
+    @staticmethod
+    def _live_key(path, device: int) -> tuple:
+        return str(Path(path).resolve()), int(device)
+
+    @classmethod
+    def live(cls, path, device: int) -> Optional["BM25Retriever"]:
+        """The loaded retriever of this index file on this device in the process, if one is alive."""
+        with cls._live_lock:
+            return cls._live.get(cls._live_key(path, device))
 
     def load(self) -> None:
         if not self.bm25_path.exists():
@@ -73,6 +95,52 @@ class BM25Retriever:
                                "one-character" if self.index_tokenizer == "char" else "dictionary")
             self._loaded = True
             self._bm25_mtime = current_mtime
+            with type(self)._live_lock:
+                type(self)._live[self._live_key(self.bm25_path, self.device_index)] = self
+
+    def state_is_current(self) -> bool:
+        """The loaded state is the index file on disk, and the index is unsharded — asked by the builder BEFORE it
+        replaces the file, under `_lock`, which it keeps until append_in_place has returned: a search thread that sees the
+        new mtime in between waits in load() and then finds the state current."""
+        try:
+            return (self._loaded and self.shard is None and self.bm25 is not None
+                    and self.bm25_path.stat().st_mtime == self._bm25_mtime)
+        except OSError:
+            return False
+
+    def append_in_place(self, refit: BM25Okapi, corpus: Sequence[LawChunk], new_tokens: Sequence[Sequence[str]],
+                        tokenizer: Optional[str]) -> bool:
+        """IncrementalBM25Builder, after it has replaced a file that was current (state_is_current, the caller holds
+        `_lock`) by `refit` over `corpus` = the old chunks + len(new_tokens) new ones: when the re-fit's first n documents
+        and first V vocabulary keys are the live object's — the old chunks were tokenised as the live index was; an index
+        built with the English regex rule is not — the new documents go behind the live object and its resident postings
+        (BM25Okapi.add_documents, amdr_bm25_add), the file's mtime is remembered and True is returned: what this process
+        wrote IS the resident state.  Otherwise nothing is touched and the next load() reloads the file.
+        The append is a mutation of the native handle (include/amdretrieval.h): device work already enqueued is waited
+        for here; searches on the device-resident stage must not be STARTED from other threads while an ingest runs."""
+        live = self.bm25
+        n, v = live.corpus_size, len(live.idf)
+        if (tokenizer != self.index_tokenizer or refit.corpus_size != n + len(new_tokens) or len(corpus) != refit.corpus_size
+                or len(self.chunks) != n or refit.doc_freqs[:n] != live.doc_freqs
+                or list(islice(refit.idf, v)) != list(live.idf)):
+            return False
+        stamp = self.bm25_path.stat().st_mtime
+        if live.__dict__.get("_gpu") is not None:
+            import torch
+            if torch.cuda.is_available():
+                torch.cuda.synchronize(self.device_index)
+        try:
+            live.add_documents(new_tokens)
+        except Exception as exc:  # noqa: BLE001 - e.g. no room for the transient second copy: the file is reloaded instead
+            logger.warning("[BM25] in-place append failed (%s): %s is reloaded on the next load()", exc, self.bm25_path)
+            return False
+        self.chunks = list(corpus)
+        # the native tokenisers hold the vocabulary table: rebuilt for the grown one on their next use
+        self.__dict__.pop("_native_tok", None)
+        self.__dict__.pop("_device_tok", None)
+        self.appends += 1
+        self._bm25_mtime = stamp
+        return True
 
     def gpu_index(self):
         """The _native.BM25Index this retriever scores with (this rank's row block in a sharded deployment)."""
