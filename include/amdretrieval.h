@@ -8,7 +8,7 @@
  * 0 on success or a negative AMDR_E* code, with a thread-local message available
  * from amdr_last_error(); the caller allocates all outputs; opaque handles are
  * safe for concurrent read-only searches (internally serialised per handle),
- * mutation (add/destroy) must not race with searches on the same handle.
+ * mutation (add/remove/destroy) must not race with searches on the same handle.
  *
  * "_device" variants take DEVICE pointers and a hipStream_t passed as void*
  * (0 = the null stream); they enqueue work and return without synchronising,
@@ -148,7 +148,7 @@ int amdr_dense_destroy(amdr_dense_t* h);
  * term_ptr[n_terms+1] indexes post_doc/post_tf (ascending doc id per term);
  * idf already has rank_bm25's epsilon floor applied; every idf must be finite (AMDR_EINVAL otherwise).
  * Resident per posting: doc id (4 B) + fp64 factor (8 B), which the searches read, + tf (4 B); per document: its length
- * (4 B).  tf and the lengths are kept only for amdr_bm25_add, which recomputes every factor from them: 16 B per posting
+ * (4 B).  tf and the lengths are kept only for amdr_bm25_add / amdr_bm25_remove, which recompute every factor from them: 16 B per posting
  * of HBM instead of 12, + 4 B per document. */
 int amdr_bm25_create(const int64_t* term_ptr, const int32_t* post_doc, const int32_t* post_tf,
                      const double* idf, const int32_t* doc_len, int64_t n_terms, int64_t n_docs,
@@ -178,8 +178,39 @@ int amdr_bm25_ndocs(const amdr_bm25_t* h, int64_t* n);
  * captured again.  The arrival counters of the one-launch serving step stay as they are. */
 int amdr_bm25_add(amdr_bm25_t* h, const int64_t* term_ptr_add, const int32_t* post_doc_add, const int32_t* post_tf_add,
                   const double* idf, const int32_t* doc_len_add, int64_t n_terms, int64_t n_add, double avgdl);
-/* out6: [0] n_docs, [1] n_terms, [2] nnz (postings), [3] adds so far, [4] the merge kernel's tile length in postings,
- *       [5] 0 (reserved) */
+/* Remove n_remove documents (the reference has no removal: a corpus that shrinks takes the full re-fit + reload of
+ * legalrag/retrieval/builders/incremental_bm25_builder.py:70-79 followed by bm25_retriever.py:44-56, which this call
+ * replaces).  remove_ids[n_remove]: old document ids, strictly ascending, in [0, n_docs); n_remove < n_docs (an index
+ * keeps a document, as create demands).  The surviving documents are renumbered 0 .. n_docs-n_remove-1 in their old order
+ * (ids close up: the faiss remove_ids convention of flat indexes).  term_map[n_terms]: the new id of each old term or -1,
+ * the ids >= 0 a bijection onto [0, n_terms_new) — a re-fit of the survivors drops the terms whose documents are all gone
+ * and may order the rest differently; null is the identity: n_terms_new == n_terms and an emptied term keeps its id with
+ * an empty list.  idf[n_terms_new]: the whole new vector, floor applied, computed by the caller as for create (native
+ * code takes no logarithm); avgdl: the caller's new value.
+ * Afterwards the handle is what amdr_bm25_create makes of the surviving documents' index with the terms renumbered by
+ * the map, each list ascending: term_ptr, post_doc, post_tf, post_w, idf and doc_len are the same bytes (amdr_bm25_read),
+ * hence the same ids and score bits from every entry point.  N, avgdl and every idf are corpus-global, so every factor
+ * changes: the call is two device passes over ALL resident postings (count, then scatter with the factor recomputed; the
+ * tiles of 2 048 old postings and the short scans between them are described in csrc/bm25.hip) plus host work
+ * proportional to n_terms + n_remove — it validates the call's arrays only.  No atomics: the result is deterministic.
+ * AMDR_EINVAL: null handle, n_remove < 0, null remove_ids or (n_terms_new > 0) null idf, n_remove >= n_docs, an id outside
+ * [0, n_docs), ids not strictly ascending, n_terms_new outside [0, n_terms], a null map with n_terms_new != n_terms, a map
+ * value below -1 or >= n_terms_new, two terms on one new id, a new id no term maps to, a non-finite idf, a non-finite or
+ * non-positive avgdl — and a term mapped to -1 that still has a surviving posting, which only the device sees: the
+ * counting passes raise a flag that is read before the swap.  n_remove == 0 is a no-op that reads nothing.  A failed
+ * remove (AMDR_EINVAL, AMDR_ENOMEM, AMDR_EHIP) leaves the handle as it was and searchable; the price is the add's: the
+ * new arrays are built beside the old ones and swapped in after the handle's stream has finished (for the length of the
+ * call the device also holds 2 B per old posting, 4 B per old document and 8 B per term of scratch).  Runs inside the
+ * handle's mutex.  It is a mutation in the sense of the rule at the top of this file, and the rules for in-flight
+ * "_device" work, for workspaces and for captured graphs are those of amdr_bm25_add: finish the work first, reserve and
+ * capture again.  The arrival counters of the one-launch serving step stay as they are. */
+int amdr_bm25_remove(amdr_bm25_t* h, const int64_t* remove_ids, int64_t n_remove, const int32_t* term_map,
+                     int64_t n_terms_new, const double* idf, double avgdl);
+/* Summed device time of the passes of the last successful amdr_bm25_remove, in ms between events on the handle's stream
+ * (scripts/bench_bm25_remove.py sets it against the passes' algorithmic bytes); -1 before the first remove. */
+int amdr_bm25_remove_kernel_ms(amdr_bm25_t* h, double* ms);
+/* out6: [0] n_docs, [1] n_terms, [2] nnz (postings), [3] adds so far, [4] the tile length in postings of the merge
+ *       kernel and of the remove's passes, [5] removes so far (an add does not touch [5], a remove does not touch [3]) */
 int amdr_bm25_info(amdr_bm25_t* h, int64_t* out6);
 /* Device time of the merge kernel of the last successful amdr_bm25_add, in ms between two events on the handle's stream
  * (scripts/bench_bm25_add.py sets it against the kernel's algorithmic bytes); -1 before the first add. */

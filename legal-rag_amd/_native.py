@@ -35,7 +35,7 @@ SIGNATURES = {
     "amdr_dense_ntotal": "PP", "amdr_dense_dim": "PP", "amdr_dense_reserve": "Pii", "amdr_dense_search": "PPiiPP",
     "amdr_dense_search_device": "PPiiPPP", "amdr_dense_search_fuse_device": "PPiiPPPPiPPPPPPPP", "amdr_hybrid_small_device": "PPPPPiiiPPPPPPPPPPPP", "amdr_dense_small_create": "PP", "amdr_dense_small_approx_device": "PPiPlPP", "amdr_dense_small_destroy": "P", "amdr_dense_two_pass_fallbacks": "PP", "amdr_dense_read_rows": "PllP", "amdr_dense_score_rows": "PPiPiP",
     "amdr_dense_plan_info": "PiiPi", "amdr_dense_workspace_plan": "liiiiiP", "amdr_dense_hi_counters": "PP", "amdr_dense_image_build": "P", "amdr_dense_image_drop": "P", "amdr_dense_image_info": "PP", "amdr_dense_profile_begin": "Pi", "amdr_dense_profile_end": "PPP", "amdr_dense_destroy": "P",
-    "amdr_bm25_create": "PPPPPlldddiP", "amdr_bm25_ndocs": "PP", "amdr_bm25_add": "PPPPPPlld", "amdr_bm25_info": "PP", "amdr_bm25_add_kernel_ms": "PP", "amdr_bm25_read": "PPPPPPP", "amdr_bm25_reserve": "Piil", "amdr_bm25_workspace_plan": "liiiiP", "amdr_bm25_plan_info": "PiiPi",
+    "amdr_bm25_create": "PPPPPlldddiP", "amdr_bm25_ndocs": "PP", "amdr_bm25_add": "PPPPPPlld", "amdr_bm25_info": "PP", "amdr_bm25_add_kernel_ms": "PP", "amdr_bm25_remove": "PPlPlPd", "amdr_bm25_remove_kernel_ms": "PP", "amdr_bm25_read": "PPPPPPP", "amdr_bm25_reserve": "Piil", "amdr_bm25_workspace_plan": "liiiiP", "amdr_bm25_plan_info": "PiiPi",
     "amdr_bm25_search": "PPPiiPP", "amdr_bm25_search_device": "PPPiiPPP", "amdr_bm25_scores": "PPPiP",
     "amdr_bm25_destroy": "P",
     "amdr_tokenizer_create": "PPlP", "amdr_tokenizer_encode": "PPPiPlPP", "amdr_tokenizer_encode_joined": "PPliPlPP", "amdr_tokenizer_encode_ptrs": "PPPiPlPP", "amdr_tokenizer_spans": "PlPPiP",
@@ -419,8 +419,30 @@ class BM25Index(_Handle):
                                     C.c_double(avgdl)), "amdr_bm25_add")
         self.n_docs, self.n_terms = self.info()[:2]
 
+    def remove(self, remove_ids, idf, avgdl: float, term_map=None) -> None:
+        """Remove documents (amdr_bm25_remove): remove_ids strictly ascending old ids (not all of them); the survivors are
+        renumbered 0 .. n-1 in their old order.  term_map[n_terms]: the new id of each old term or -1, a bijection onto
+        [0, len(idf)) (None: the identity, len(idf) == n_terms); idf: the WHOLE new vector; avgdl: the new value.
+        Afterwards the index is what BM25Index makes of the survivors' arrays, bit for bit.  A "_device" caller finishes
+        its work first and reserves again."""
+        ids, idf_ = _c(remove_ids, np.int64), _c(idf, np.float64)
+        tm = None if term_map is None else _c(term_map, np.int32)
+        if ids.ndim != 1 or idf_.ndim != 1 or (tm is not None and tm.shape != (self.n_terms,)):
+            raise ValueError("remove: remove_ids [n_remove], idf [n_terms_new], term_map [n_terms] or None")
+        _check(load().amdr_bm25_remove(self._h, _p(ids, C.c_int64), C.c_int64(ids.shape[0]),
+                                       None if tm is None else _p(tm, C.c_int32), C.c_int64(idf_.shape[0]),
+                                       _p(idf_, C.c_double), C.c_double(avgdl)), "amdr_bm25_remove")
+        self.n_docs, self.n_terms = self.info()[:2]
+
+    def remove_kernel_ms(self) -> float:
+        """Summed device time of the last remove's passes in ms (-1 before the first remove)."""
+        ms = C.c_double(-1.0)
+        _check(load().amdr_bm25_remove_kernel_ms(self._h, C.byref(ms)), "amdr_bm25_remove_kernel_ms")
+        return float(ms.value)
+
     def info(self) -> Tuple[int, int, int, int, int, int]:
-        """(n_docs, n_terms, postings, adds so far, the merge kernel's tile length in postings, 0)."""
+        """(n_docs, n_terms, postings, adds so far, the tile length in postings of the add's and the remove's kernels,
+        removes so far)."""
         out = (C.c_int64 * 6)()
         _check(load().amdr_bm25_info(self._h, out), "amdr_bm25_info")
         return tuple(int(x) for x in out)

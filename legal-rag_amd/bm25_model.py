@@ -189,6 +189,75 @@ class BM25Okapi:
                 self.__dict__.pop("_gpu_device", None)
         return len(corpus)
 
+    def remove_documents(self, doc_ids: Sequence[int]) -> int:
+        """Remove documents by id (duplicates and order do not matter); afterwards this object equals
+        BM25Okapi(the surviving documents' tokens), the survivors renumbered 0 .. n-1 in their old order: the idf dict in
+        the re-fit's key order — the first-seen order of the SURVIVORS, which drops the terms whose documents are all gone
+        and can order the rest differently — with the same bits (math.log per term and a sequential sum in that order, as
+        __init__), avgdl, average_idf, doc_len, doc_freqs, corpus_size.  O(V + the survivors' postings, at C speed) after
+        the one-time document-frequency cache.  ValueError for an id out of range and for removing every document; the
+        object is unchanged then.  A resident unsharded index (gpu()) takes the removal in place (BM25Index.remove: the
+        ids, the map old term id -> new term id, the new idf vector and avgdl); a row shard is dropped and uploaded
+        again on its next use.  Returns the number of documents removed."""
+        ids = sorted({int(i) for i in doc_ids})
+        if not ids:
+            return 0
+        if ids[0] < 0 or ids[-1] >= self.corpus_size:
+            raise ValueError(f"remove_documents: ids must lie in [0, {self.corpus_size})")
+        if len(ids) >= self.corpus_size:
+            raise ValueError("remove_documents: an index keeps at least one document")
+        nd_old = self._doc_frequencies()
+        total = self.__dict__["_total"]
+        gone = set(ids)
+        doc_freqs = [f for d, f in enumerate(self.doc_freqs) if d not in gone]
+        doc_len = [n for d, n in enumerate(self.doc_len) if d not in gone]
+        lost: Dict[str, int] = {}
+        for d in ids:
+            total -= self.doc_len[d]
+            for word in self.doc_freqs[d]:
+                lost[word] = lost.get(word, 0) + 1
+        # the re-fit's vocabulary order: a word's place is its first appearance in the surviving documents
+        nd = dict.fromkeys(chain.from_iterable(doc_freqs))
+        for word in nd:
+            nd[word] = nd_old[word] - lost.get(word, 0)
+        corpus_size = len(doc_freqs)
+        idf: Dict[str, float] = {}
+        idf_sum = 0
+        negative = []
+        for word, freq in nd.items():
+            v = math.log(corpus_size - freq + 0.5) - math.log(freq + 0.5)
+            idf[word] = v
+            idf_sum += v
+            if v < 0:
+                negative.append(word)
+        average_idf = idf_sum / len(idf)
+        eps = self.epsilon * average_idf
+        for word in negative:
+            idf[word] = eps
+        g = self.__dict__.get("_gpu")
+        in_place = g is not None and self.__dict__.get("_gpu_device", (None, None))[1] is None
+        if in_place:  # old term id -> new term id, -1 for a term that is gone
+            old_vocab = self.vocab()
+            term_map = np.full(len(old_vocab), -1, dtype=np.int32)
+            term_map[np.fromiter(map(old_vocab.__getitem__, nd), dtype=np.int64, count=len(nd))] = np.arange(len(nd), dtype=np.int32)
+        self.doc_freqs, self.doc_len, self.corpus_size = doc_freqs, doc_len, corpus_size
+        self.avgdl = total / corpus_size
+        self.idf, self.average_idf = idf, average_idf
+        self.__dict__["_nd"], self.__dict__["_total"] = nd, total
+        self.__dict__.pop("_vocab", None)
+        if in_place:
+            try:
+                g.remove(np.asarray(ids, dtype=np.int64), np.fromiter(idf.values(), dtype=np.float64, count=len(idf)),
+                         float(self.avgdl), term_map=term_map)
+            except Exception:  # the resident index is unchanged and now ahead of this object: upload again on next use
+                self.__dict__.pop("_gpu", None)
+                self.__dict__.pop("_gpu_device", None)
+                raise
+        elif g is not None:
+            self.__dict__.pop("_gpu", None)
+            self.__dict__.pop("_gpu_device", None)
+        return len(ids)
+
     def to_csr(self):
         vocab = self.vocab()
         V = len(vocab)

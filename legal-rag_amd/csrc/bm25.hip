@@ -17,6 +17,20 @@
 // and recomputes post_w with the new avgdl, next to the data.  post_tf and doc_len stay resident for that (16 B per
 // posting instead of 12, + 4 B per document).  The new arrays are built beside the old ones and swapped in after the
 // stream has finished: a failed add leaves the handle as it was.
+//
+// amdr_bm25_remove takes documents out, with the same contract (the handle is what create makes of the survivors' index)
+// and the same build-beside-and-swap.  It is a stream compaction of the postings in two passes over them, divided by
+// tiles of kBmAddTile OLD postings, with no atomics (compact.hpp, bm25_remove_rule.hpp):
+//   bm25_rm_docmap_kernel   doc_new[d] = -1 or d minus the remove ids below d; doc_len compacted through it
+//   bm25_rm_count_kernel    per tile: the keep flags scanned in LDS -> each posting's rank inside its tile (2 B) + the
+//                           tile's count                                         reads 4 B + a 4 B gather, writes 2 B
+//   compact_scan_i64_kernel tile counts -> tile bases (the last one is nnz_new)
+//   bm25_rm_terms_kernel    per old term: rank of its first posting (rank_at), surviving count -> df_new[term_map[t]];
+//                           a term mapped to -1 with a surviving posting raises the error flag
+//   compact_scan_i64_kernel df_new -> the new term_ptr
+//   (the host reads nnz_new and the flag here, and allocates the new posting arrays at their exact size)
+//   bm25_rm_scatter_kernel  per tile: a kept posting of term t goes to new_ptr[term_map[t]] + rank - rank_at[t] with its
+//                           mapped document, its tf and the recomputed factor    reads 10 B + two 4 B gathers, writes 16 B
 #include "common.hpp"
 #include "topk.hpp"
 #include "topk_merge.hpp"
@@ -32,14 +46,17 @@
 
 #include "bm25_add_rule.hpp"
 #include "bm25_core.hpp"
+#include "bm25_remove_rule.hpp"
+#include "compact.hpp"
 
 using namespace amdr;
 
 struct amdr_bm25 {
   int device = 0;
-  int64_t n_terms = 0, n_docs = 0, nnz = 0, adds = 0;
+  int64_t n_terms = 0, n_docs = 0, nnz = 0, adds = 0, removes = 0;
   double avgdl = 0, k1 = 1.5, b = 0.75;
-  double add_kernel_ms = -1;  // event time of the last add's merge kernel (amdr_bm25_add_kernel_ms)
+  double add_kernel_ms = -1;     // event time of the last add's merge kernel (amdr_bm25_add_kernel_ms)
+  double remove_kernel_ms = -1;  // summed event time of the last remove's passes (amdr_bm25_remove_kernel_ms)
   long long* term_ptr = nullptr;
   int* post_doc = nullptr;
   double* post_w = nullptr;  // tf*(k1+1) / (tf + k1*(1 - b + b*len/avgdl)) per posting, fp64
@@ -239,9 +256,106 @@ __global__ __launch_bounds__(kBmAddThreads) void bm25_merge_kernel(
   }
 }
 
-// device arrays of an add in the making: freed unless they were handed to the handle
+// ---- amdr_bm25_remove: document map, tile ranks, term table, scatter -------------------------------------------------
+__global__ __launch_bounds__(256) void bm25_rm_docmap_kernel(const long long* __restrict__ remove_ids, long n_remove,
+                                                             const int* __restrict__ doc_len_old, long n_docs_old,
+                                                             int* __restrict__ doc_new, int* __restrict__ doc_len_new) {
+  const long d = (long)blockIdx.x * 256 + threadIdx.x;
+  if (d >= n_docs_old) return;
+  const int nd = bm_rm_doc_new(remove_ids, n_remove, d);
+  doc_new[d] = nd;
+  if (nd >= 0) doc_len_new[nd] = doc_len_old[d];
+}
+
+// One block = one tile of kBmAddTile consecutive OLD postings (thread tid owns postings tid, tid + 256, ...): which of
+// them survive, each one's rank among the tile's survivors (compact_tile_scan) and the tile's count.
+__global__ __launch_bounds__(kBmAddThreads) void bm25_rm_count_kernel(const int* __restrict__ old_doc, long long nnz_old,
+                                                                      const int* __restrict__ doc_new,
+                                                                      unsigned short* __restrict__ tile_rank,
+                                                                      long long* __restrict__ tile_cnt) {
+  __shared__ int lds[kBmAddTile + kBmAddThreads / 64 + 1];
+  const int tid = threadIdx.x;
+  const long long p0 = (long long)blockIdx.x * kBmAddTile;
+  unsigned keep = 0;
+#pragma unroll
+  for (int u = 0; u < kBmAddPerThread; ++u) {
+    const long long p = p0 + (long long)u * kBmAddThreads + tid;
+    if (p < nnz_old && doc_new[old_doc[p]] >= 0) keep |= 1u << u;
+  }
+  int rank[kBmAddPerThread];
+  const int total = compact_tile_scan<kBmAddThreads, kBmAddPerThread>(keep, lds, rank);
+#pragma unroll
+  for (int u = 0; u < kBmAddPerThread; ++u) {
+    const long long p = p0 + (long long)u * kBmAddThreads + tid;
+    if (p < nnz_old) tile_rank[p] = (unsigned short)rank[u];
+  }
+  if (tid == 0) tile_cnt[blockIdx.x] = total;
+}
+
+__global__ __launch_bounds__(256) void bm25_rm_terms_kernel(const long long* __restrict__ old_ptr, long n_terms_old,
+                                                            long long nnz_old, const long long* __restrict__ tile_base,
+                                                            const unsigned short* __restrict__ tile_rank,
+                                                            const int* __restrict__ term_map, long long* __restrict__ rank_at,
+                                                            long long* __restrict__ df_new, int* __restrict__ bad) {
+  const long t = (long)blockIdx.x * 256 + threadIdx.x;
+  if (t <= n_terms_old) bm_rm_term_entry(t, n_terms_old, old_ptr, nnz_old, tile_base, tile_rank, term_map, rank_at, df_new, bad);
+}
+
+// One block = one tile of OLD postings again.  The tile's terms are found as in bm25_merge_kernel, in the OLD term table
+// (a window of it in LDS; a window widened beyond the LDS room by terms without postings is searched in global memory).
+// A surviving posting reads 8 B (doc, tf) + 2 B of rank, gathers doc_new and doc_len (4 B each) and the few table entries
+// of its term, and writes 16 B (doc, tf, factor) at bm_rm_dest.  Every destination is a sum of counts: no atomics.
+__global__ __launch_bounds__(kBmAddThreads) void bm25_rm_scatter_kernel(
+    const long long* __restrict__ old_ptr, long n_terms_old, const int* __restrict__ old_doc, const int* __restrict__ old_tf,
+    long long nnz_old, const int* __restrict__ doc_new, const int* __restrict__ doc_len /* new */,
+    const long long* __restrict__ tile_base, const unsigned short* __restrict__ tile_rank,
+    const long long* __restrict__ rank_at, const long long* __restrict__ new_ptr, const int* __restrict__ term_map,
+    long long nnz_new, double avgdl, double k1, double b, int* __restrict__ out_doc, int* __restrict__ out_tf,
+    double* __restrict__ out_w) {
+  __shared__ long long win[kBmAddTile + 2];
+  __shared__ long t_first, t_last;
+  const int tid = threadIdx.x;
+  const long long p0 = (long long)blockIdx.x * kBmAddTile;
+  long long p1 = p0 + kBmAddTile;  // exclusive
+  if (p1 > nnz_old) p1 = nnz_old;
+  if (p0 >= p1) return;
+  if (tid == 0) {
+    long a, z;
+    bm_add_tile_terms(old_ptr, n_terms_old, p0, p1, &a, &z);
+    t_first = a;
+    t_last = z;
+  }
+  __syncthreads();
+  const long t0 = t_first, t1 = t_last;
+  const bool in_lds = bm_add_window_fits(t0, t1);
+  if (in_lds) {
+    for (long i = tid; i <= t1 - t0 + 1; i += kBmAddThreads) win[i] = old_ptr[t0 + i];
+    __syncthreads();
+  }
+  const long long* tab = in_lds ? win : old_ptr;
+  const long base = in_lds ? t0 : 0;
+#pragma unroll
+  for (int u = 0; u < kBmAddPerThread; ++u) {
+    const long long p = p0 + (long long)u * kBmAddThreads + tid;
+    if (p < p1) {
+      const int doc = doc_new[old_doc[p]];
+      if (doc >= 0) {
+        const long t = bm_add_term_of(tab, base, t0, t1, p);
+        const long long dst = bm_rm_dest(p, t, nnz_old, tile_base, tile_rank, rank_at, new_ptr, term_map);
+        if (dst >= 0 && dst < nnz_new) {  // (always, after the host's checks and the terms kernel's flag)
+          const int tf = old_tf[p];
+          out_doc[dst] = doc;
+          out_tf[dst] = tf;
+          out_w[dst] = bm25_factor(tf, doc_len[doc], avgdl, k1, b);
+        }
+      }
+    }
+  }
+}
+
+// device arrays of an add or a remove in the making: freed unless they were handed to the handle
 struct BmAddBufs {
-  void* p[9] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  void* p[16] = {};
   ~BmAddBufs() {
     for (void* q : p)
       if (q) (void)hipFree(q);
@@ -513,6 +627,134 @@ int amdr_bm25_add(amdr_bm25_t* h, const int64_t* term_ptr_add, const int32_t* po
   return AMDR_OK;
 }
 
+int amdr_bm25_remove(amdr_bm25_t* h, const int64_t* remove_ids, int64_t n_remove, const int32_t* term_map,
+                     int64_t n_terms_new, const double* idf, double avgdl) {
+  AMDR_REQUIRE(h != nullptr, "bm25_remove: null handle");
+  AMDR_REQUIRE(n_remove >= 0, "bm25_remove: n_remove=%lld", (long long)n_remove);
+  if (n_remove == 0) return AMDR_OK;
+  std::lock_guard<std::mutex> g(h->mu);
+  const int bad = bm_rm_validate(remove_ids, n_remove, term_map, n_terms_new, idf, avgdl, h->n_terms, h->n_docs);
+  if (bad == kBmRmNoMem) return fail(AMDR_ENOMEM, "bm25_remove: %s", bm_rm_error_text(bad));
+  AMDR_REQUIRE(bad == kBmRmOk, "bm25_remove: %s", bm_rm_error_text(bad));
+  AMDR_HIP(hipSetDevice(h->device));
+  const int64_t V_old = h->n_terms, V_new = n_terms_new, nnz_old = h->nnz, n_old = h->n_docs, n_new = n_old - n_remove;
+  const long long tiles = (nnz_old + kBmAddTile - 1) / kBmAddTile;
+  AMDR_REQUIRE(tiles < (1ll << 31), "bm25_remove: %lld postings exceed the grid", (long long)nnz_old);
+  // 0..5: the new arrays (one padding element each, as upload() leaves); the rest is freed when the call returns
+  enum { TP, PD, PT, PW, IDF, DL, RID, DNEW, TRANK, TCNT, TBASE, RANKAT, DF, MAP, FLAG };
+  BmAddBufs nb;
+  int rc = nb.alloc(TP, (size_t)(V_new + 2) * sizeof(long long));
+  if (!rc) rc = nb.alloc(IDF, (size_t)(V_new + 1) * sizeof(double));
+  if (!rc) rc = nb.alloc(DL, (size_t)(n_new + 1) * sizeof(int));
+  if (!rc) rc = nb.alloc(RID, (size_t)n_remove * sizeof(long long));
+  if (!rc) rc = nb.alloc(DNEW, (size_t)n_old * sizeof(int));
+  if (!rc) rc = nb.alloc(TRANK, (size_t)(nnz_old + 1) * sizeof(unsigned short));
+  if (!rc) rc = nb.alloc(TCNT, (size_t)(tiles + 1) * sizeof(long long));
+  if (!rc) rc = nb.alloc(TBASE, (size_t)(tiles + 1) * sizeof(long long));
+  if (!rc) rc = nb.alloc(RANKAT, (size_t)(V_old + 1) * sizeof(long long));
+  if (!rc) rc = nb.alloc(DF, (size_t)(V_new + 1) * sizeof(long long));
+  if (!rc && term_map) rc = nb.alloc(MAP, (size_t)(V_old + 1) * sizeof(int));
+  if (!rc) rc = nb.alloc(FLAG, sizeof(int));
+  if (rc) return rc;
+  hipStream_t st = h->stream;
+  AMDR_HIP(hipMemcpyAsync(nb.p[RID], remove_ids, (size_t)n_remove * sizeof(long long), hipMemcpyHostToDevice, st));
+  if (term_map && V_old) AMDR_HIP(hipMemcpyAsync(nb.p[MAP], term_map, (size_t)V_old * sizeof(int), hipMemcpyHostToDevice, st));
+  if (V_new) AMDR_HIP(hipMemcpyAsync(nb.p[IDF], idf, (size_t)V_new * sizeof(double), hipMemcpyHostToDevice, st));
+  AMDR_HIP(hipMemsetAsync(nb.p[FLAG], 0, sizeof(int), st));
+  // the passes between events, in two stretches with the host's look at nnz_new between them
+  // (amdr_bm25_remove_kernel_ms); an event that cannot be made only loses the time
+  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  struct EvGuard {
+    hipEvent_t* e;
+    ~EvGuard() {
+      for (int i = 0; i < 4; ++i)
+        if (e[i]) (void)hipEventDestroy(e[i]);
+    }
+  } ev_guard{ev};
+  bool timed = true;
+  for (int i = 0; i < 4 && timed; ++i)
+    if (hipEventCreate(&ev[i]) != hipSuccess) {
+      (void)hipGetLastError();
+      ev[i] = nullptr;
+      timed = false;
+    }
+  const int* map_dev = term_map ? (const int*)nb.p[MAP] : nullptr;
+  if (timed) AMDR_HIP(hipEventRecord(ev[0], st));
+  hipLaunchKernelGGL(bm25_rm_docmap_kernel, dim3((unsigned)((n_old + 255) / 256)), dim3(256), 0, st,
+                     (const long long*)nb.p[RID], (long)n_remove, h->doc_len, (long)n_old, (int*)nb.p[DNEW], (int*)nb.p[DL]);
+  AMDR_HIP(hipGetLastError());
+  if (tiles > 0) {
+    hipLaunchKernelGGL(bm25_rm_count_kernel, dim3((unsigned)tiles), dim3(kBmAddThreads), 0, st, h->post_doc,
+                       (long long)nnz_old, (const int*)nb.p[DNEW], (unsigned short*)nb.p[TRANK], (long long*)nb.p[TCNT]);
+    AMDR_HIP(hipGetLastError());
+  }
+  hipLaunchKernelGGL(compact_scan_i64_kernel, dim3(1), dim3(kCompactScanThreads), 0, st, (const long long*)nb.p[TCNT],
+                     (long)tiles, (long long*)nb.p[TBASE]);
+  AMDR_HIP(hipGetLastError());
+  hipLaunchKernelGGL(bm25_rm_terms_kernel, dim3((unsigned)((V_old + 1 + 255) / 256)), dim3(256), 0, st, h->term_ptr,
+                     (long)V_old, (long long)nnz_old, (const long long*)nb.p[TBASE], (const unsigned short*)nb.p[TRANK],
+                     map_dev, (long long*)nb.p[RANKAT], (long long*)nb.p[DF], (int*)nb.p[FLAG]);
+  AMDR_HIP(hipGetLastError());
+  hipLaunchKernelGGL(compact_scan_i64_kernel, dim3(1), dim3(kCompactScanThreads), 0, st, (const long long*)nb.p[DF],
+                     (long)V_new, (long long*)nb.p[TP]);
+  AMDR_HIP(hipGetLastError());
+  if (timed) AMDR_HIP(hipEventRecord(ev[1], st));
+  long long nnz_new = 0;
+  int flag = 0;
+  AMDR_HIP(hipMemcpyAsync(&nnz_new, (const long long*)nb.p[TBASE] + tiles, sizeof(long long), hipMemcpyDeviceToHost, st));
+  AMDR_HIP(hipMemcpyAsync(&flag, nb.p[FLAG], sizeof(int), hipMemcpyDeviceToHost, st));
+  AMDR_HIP(hipStreamSynchronize(st));
+  AMDR_REQUIRE(flag == 0, "bm25_remove: a term mapped to -1 still has a surviving posting");
+  if (nnz_new < 0 || nnz_new > nnz_old) return fail(AMDR_EHIP, "bm25_remove: counted %lld of %lld postings", nnz_new, (long long)nnz_old);
+  rc = nb.alloc(PD, (size_t)(nnz_new + 1) * sizeof(int));
+  if (!rc) rc = nb.alloc(PT, (size_t)(nnz_new + 1) * sizeof(int));
+  if (!rc) rc = nb.alloc(PW, (size_t)(nnz_new + 1) * sizeof(double));
+  if (rc) return rc;
+  if (timed) AMDR_HIP(hipEventRecord(ev[2], st));
+  if (tiles > 0 && nnz_new > 0) {
+    hipLaunchKernelGGL(bm25_rm_scatter_kernel, dim3((unsigned)tiles), dim3(kBmAddThreads), 0, st, h->term_ptr, (long)V_old,
+                       h->post_doc, h->post_tf, (long long)nnz_old, (const int*)nb.p[DNEW], (const int*)nb.p[DL],
+                       (const long long*)nb.p[TBASE], (const unsigned short*)nb.p[TRANK], (const long long*)nb.p[RANKAT],
+                       (const long long*)nb.p[TP], map_dev, nnz_new, avgdl, h->k1, h->b, (int*)nb.p[PD], (int*)nb.p[PT],
+                       (double*)nb.p[PW]);
+    AMDR_HIP(hipGetLastError());
+  }
+  if (timed) AMDR_HIP(hipEventRecord(ev[3], st));
+  AMDR_HIP(hipStreamSynchronize(st));
+  float ms0 = -1.f, ms1 = -1.f;
+  if (!(timed && hipEventElapsedTime(&ms0, ev[0], ev[1]) == hipSuccess && hipEventElapsedTime(&ms1, ev[2], ev[3]) == hipSuccess)) {
+    (void)hipGetLastError();
+    ms0 = -1.f;
+    ms1 = 0.f;
+  }
+  h->remove_kernel_ms = (double)ms0 + (double)ms1;
+  // the swap: from here on nothing can fail (the old arrays take the new ones' places in nb and are freed with it)
+  auto swap_in = [&](auto*& held, int i) {
+    void* old = (void*)held;
+    held = reinterpret_cast<std::remove_reference_t<decltype(held)>>(nb.p[i]);
+    nb.p[i] = old;
+  };
+  swap_in(h->term_ptr, TP);
+  swap_in(h->post_doc, PD);
+  swap_in(h->post_tf, PT);
+  swap_in(h->post_w, PW);
+  swap_in(h->idf, IDF);
+  swap_in(h->doc_len, DL);
+  h->n_terms = V_new;
+  h->n_docs = n_new;
+  h->nnz = nnz_new;
+  h->avgdl = avgdl;
+  ++h->removes;
+  return AMDR_OK;
+}
+
+int amdr_bm25_remove_kernel_ms(amdr_bm25_t* h, double* ms) {
+  AMDR_REQUIRE(h && ms, "bm25_remove_kernel_ms: null");
+  std::lock_guard<std::mutex> g(h->mu);
+  *ms = h->remove_kernel_ms;
+  return AMDR_OK;
+}
+
 int amdr_bm25_info(amdr_bm25_t* h, int64_t* out6) {
   AMDR_REQUIRE(h && out6, "bm25_info: null");
   std::lock_guard<std::mutex> g(h->mu);
@@ -521,7 +763,7 @@ int amdr_bm25_info(amdr_bm25_t* h, int64_t* out6) {
   out6[2] = h->nnz;
   out6[3] = h->adds;
   out6[4] = kBmAddTile;
-  out6[5] = 0;
+  out6[5] = h->removes;
   return AMDR_OK;
 }
 

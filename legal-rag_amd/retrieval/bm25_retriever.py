@@ -20,7 +20,8 @@ the native batched tokenisers (host and device) in that mode.
 Loaded retrievers are kept in a process-wide weak registry, keyed by resolved index file and device
 (`BM25Retriever.live`): IncrementalBM25Builder finds the live retriever of the file it has rewritten there and appends
 the new documents behind its resident postings (`append_in_place`, amdr_bm25_add) instead of leaving it to reload the
-whole index.  Not on a row-sharded index (cfg.retrieval.shard = "rows"): that one reloads as before."""
+whole index, and takes removed documents out of them the same way (`remove_in_place`, amdr_bm25_remove).  Not on a
+row-sharded index (cfg.retrieval.shard = "rows"): that one reloads as before."""
 from __future__ import annotations
 
 import threading
@@ -58,7 +59,8 @@ class BM25Retriever:
         self.index_tokenizer: Optional[str] = None  # id recorded in bm25.pkl (None: reference-built)
         self._tls = threading.local()                 # per-thread: did the last query use the stand-in?
         self.shard = None                             # sharding.ShardSpec in a row-sharded deployment
-        self.appends = 0                              # in-place appends so far (part of the hybrid stage's key)
+        self.appends = 0                              # in-place mutations (appends and removals) so far: part of the
+                                                      # hybrid stage's key
 
     @staticmethod
     def _live_key(path, device: int) -> tuple:
@@ -136,6 +138,39 @@ class BM25Retriever:
             return False
         self.chunks = list(corpus)
         # the native tokenisers hold the vocabulary table: rebuilt for the grown one on their next use
+        self.__dict__.pop("_native_tok", None)
+        self.__dict__.pop("_device_tok", None)
+        self.appends += 1
+        self._bm25_mtime = stamp
+        return True
+
+    def remove_in_place(self, rows: Sequence[int], corpus_after: Sequence[LawChunk]) -> bool:
+        """IncrementalBM25Builder.remove_ids, after it has replaced a file that was current (state_is_current, the caller
+        holds `_lock`) by the same index without the documents at `rows` (positions in the replaced file's chunk list),
+        whose chunks are now `corpus_after`: when the live chunks' ids and corpus_size are the replaced file's — the live
+        chunks without `rows` are corpus_after, id for id — the documents leave the live object and its resident postings
+        (BM25Okapi.remove_documents, amdr_bm25_remove), the file's mtime is remembered and True is returned.  Otherwise,
+        or when the removal fails, False: the next load() reloads the file.  A mutation of the native handle, as
+        append_in_place: device work already enqueued is waited for here; searches on the device-resident stage must not
+        be STARTED from other threads meanwhile."""
+        live = self.bm25
+        gone = {int(r) for r in rows}
+        n = live.corpus_size
+        if (not gone or min(gone) < 0 or max(gone) >= n or len(self.chunks) != n or len(corpus_after) != n - len(gone)
+                or [c.id for d, c in enumerate(self.chunks) if d not in gone] != [c.id for c in corpus_after]):
+            return False
+        stamp = self.bm25_path.stat().st_mtime
+        if live.__dict__.get("_gpu") is not None:
+            import torch
+            if torch.cuda.is_available():
+                torch.cuda.synchronize(self.device_index)
+        try:
+            live.remove_documents(sorted(gone))
+        except Exception as exc:  # noqa: BLE001 - e.g. no room for the transient second copy: the file is reloaded instead
+            logger.warning("[BM25] in-place removal failed (%s): %s is reloaded on the next load()", exc, self.bm25_path)
+            return False
+        self.chunks = list(corpus_after)
+        # the native tokenisers hold the vocabulary table: rebuilt for the renumbered one on their next use
         self.__dict__.pop("_native_tok", None)
         self.__dict__.pop("_device_tok", None)
         self.appends += 1

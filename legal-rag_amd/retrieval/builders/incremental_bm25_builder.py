@@ -13,13 +13,15 @@ resident postings, amdr_bm25_add: one device pass instead of unpickling, to_csr(
 old documents and vocabulary are the live object's (BM25Retriever.append_in_place; an index built with the English regex
 rule of build_bm25_index is tokenised differently here, fails that check and reloads: correct, not an error).  The
 retriever's lock is held from the question "is the loaded state the file" until the append is done, so that no search
-thread reloads the new file in between.  A row-sharded retriever (cfg.retrieval.shard = "rows") always reloads."""
+thread reloads the new file in between.  A row-sharded retriever (cfg.retrieval.shard = "rows") always reloads.
+
+remove_ids takes chunks out again (the reference has no removal at all): a replaced article is remove_ids + add_jsonl."""
 from __future__ import annotations
 
 import contextlib
 import logging
 from pathlib import Path
-from typing import List
+from typing import Iterable, List
 
 from ... import artifacts, text
 from ...bm25_model import BM25Okapi
@@ -66,3 +68,41 @@ class IncrementalBM25Builder:
                     "none" if live is None else "reloads on its next load()")
         logger.info("[bm25] incremental add done: added=%d total=%d", len(fresh), len(corpus))
         return len(fresh)
+
+    def remove_ids(self, chunk_ids: Iterable[str]) -> int:
+        """Remove the chunks with these ids from the index; returns how many were there.  No reference counterpart: the
+        reference's builder only appends, so a corpus that shrinks is re-fitted from scratch there.  The model in the
+        current pickle is brought to the re-fit of the surviving documents by BM25Okapi.remove_documents — no text is
+        tokenised again: doc_freqs are in the file — and written back with the tokenizer id the file records.  None of the
+        ids present: 0; all of them: ValueError (an index keeps a document); the file is untouched in both cases.  A live
+        BM25Retriever whose loaded state was the replaced file then takes the removal in place (remove_in_place,
+        amdr_bm25_remove), under the same lock discipline as add_jsonl; otherwise, and always when row-sharded, it
+        reloads on its next load()."""
+        wanted = {str(i) for i in chunk_ids}
+        path = Path(self.cfg.retrieval.bm25_index_file)
+        if not wanted or not path.exists():
+            return 0
+        bm25, chunks = artifacts.read_bm25_pickle(path)
+        rows = [d for d, c in enumerate(chunks) if c.id in wanted]
+        if not rows:
+            logger.info("[bm25] none of %d ids is in the index", len(wanted))
+            return 0
+        if len(rows) >= len(chunks):
+            raise ValueError("remove_ids: this would empty the index")
+        if bm25.corpus_size != len(chunks):
+            raise RuntimeError(f"[BM25] {path}: {bm25.corpus_size} documents but {len(chunks)} chunks")
+        tokenizer = bm25.__dict__.get("_tokenizer_id")
+        bm25.remove_documents(rows)
+        gone = set(rows)
+        corpus = [c for d, c in enumerate(chunks) if d not in gone]
+        from ..bm25_retriever import BM25Retriever
+        live = BM25Retriever.live(path, int(getattr(self.cfg.retrieval, "device", 0)))
+        with live._lock if live is not None else contextlib.nullcontext():
+            in_place = live is not None and live.state_is_current()
+            artifacts.write_bm25_pickle(path, bm25, corpus, tokenizer=tokenizer)
+            if in_place:
+                in_place = live.remove_in_place(rows, corpus)
+        logger.info("[bm25] live retriever: %s", "removed in place" if in_place else
+                    "none" if live is None else "reloads on its next load()")
+        logger.info("[bm25] incremental remove done: removed=%d total=%d", len(rows), len(corpus))
+        return len(rows)

@@ -656,7 +656,8 @@ class HybridRetriever:
             return None
         store = self.dense.store
         # (the BM25 retriever's Han mode: an engine's device tokeniser is a copy of the host tokeniser in that mode)
-        # (appends: an in-place BM25 append keeps the object and grows n_docs: engines and reserves are made again)
+        # (appends counts in-place mutations: an in-place BM25 append or removal keeps the object and changes n_docs and
+        # the term ids: engines and reserves are made again)
         key = (id(store.index), id(self.bm25.bm25), getattr(self.bm25, "appends", 0), id(col._searcher) if col is not None else None,
                id(col._pid2chunk) if col is not None else None, self.bm25.han_key())
         st = self._stage()
