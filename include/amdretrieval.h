@@ -191,7 +191,7 @@ int amdr_bm25_add(amdr_bm25_t* h, const int64_t* term_ptr_add, const int32_t* po
  * the map, each list ascending: term_ptr, post_doc, post_tf, post_w, idf and doc_len are the same bytes (amdr_bm25_read),
  * hence the same ids and score bits from every entry point.  N, avgdl and every idf are corpus-global, so every factor
  * changes: the call is two device passes over ALL resident postings (count, then scatter with the factor recomputed; the
- * tiles of 2 048 old postings and the short scans between them are described in csrc/bm25.hip) plus host work
+ * tiles of 2 048 old postings and the short scans between them are described in csrc/bm25_update.hip) plus host work
  * proportional to n_terms + n_remove — it validates the call's arrays only.  No atomics: the result is deterministic.
  * AMDR_EINVAL: null handle, n_remove < 0, null remove_ids or (n_terms_new > 0) null idf, n_remove >= n_docs, an id outside
  * [0, n_docs), ids not strictly ascending, n_terms_new outside [0, n_terms], a null map with n_terms_new != n_terms, a map

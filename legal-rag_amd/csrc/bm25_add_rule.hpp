@@ -1,22 +1,14 @@
-// The rules of amdr_bm25_add (bm25.hip) that are plain C++: the host validation of an add's own arrays, the term table of
-// the concatenation, and where output posting p of the merged index comes from.  The merge kernel and the host check
-// (check_bm25_add.cpp, which merges on the CPU with the same functions) share this one source, in the style of
-// tokenize_rule.hpp.  No HIP header is needed: AMDR_HD is empty for a plain host compiler.
+// The rules of amdr_bm25_add (bm25_update.hip) that are plain C++: the host validation of an add's own arrays, the term
+// table of the concatenation, and where output posting p of the merged index comes from.  The merge kernel and the host
+// check (check_bm25_add.cpp, which merges on the CPU with the same functions) share this one source, in the style of
+// tokenize_rule.hpp.  The tile (kBmTile consecutive OUTPUT postings per block) and the term search are those of
+// bm25_tile_rule.hpp.
 #pragma once
-#include <cmath>
 #include <cstdint>
 
-#if defined(__HIPCC__)
-#define AMDR_HD __host__ __device__
-#else
-#define AMDR_HD
-#endif
+#include "bm25_tile_rule.hpp"
 
 namespace amdr {
-
-constexpr int kBmAddThreads = 256;
-constexpr int kBmAddPerThread = 8;
-constexpr int kBmAddTile = kBmAddThreads * kBmAddPerThread;  // consecutive output postings per block of the merge kernel
 
 // Why an add is refused (0 = it is accepted).  Reads the add's arrays only: O(V + added postings).
 enum BmAddError {
@@ -52,12 +44,11 @@ inline int bm_add_validate(const int64_t* term_ptr_add, const int32_t* post_doc_
                            int64_t n_terms_old, int64_t n_docs_old) {
   if (n_add < 0 || n_terms < n_terms_old || n_terms >= (1ll << 31) || n_docs_old + n_add >= (1ll << 31)) return kBmAddSizes;
   if (!term_ptr_add || !doc_len_add || (n_terms > 0 && !idf)) return kBmAddNull;
-  if (!std::isfinite(avgdl) || !(avgdl > 0.0)) return kBmAddAvgdl;
+  if (!bm_avgdl_ok(avgdl)) return kBmAddAvgdl;
   if (term_ptr_add[0] != 0) return kBmAddPtrStart;
   for (int64_t t = 0; t < n_terms; ++t)
     if (term_ptr_add[t + 1] < term_ptr_add[t]) return kBmAddPtrOrder;
-  for (int64_t t = 0; t < n_terms; ++t)
-    if (!std::isfinite(idf[t])) return kBmAddIdf;
+  if (!bm_idf_all_finite(idf, n_terms)) return kBmAddIdf;
   if (term_ptr_add[n_terms] > 0 && (!post_doc_add || !post_tf_add)) return kBmAddNull;
   for (int64_t t = 0; t < n_terms; ++t)
     for (int64_t p = term_ptr_add[t]; p < term_ptr_add[t + 1]; ++p) {
@@ -72,28 +63,6 @@ inline int bm_add_validate(const int64_t* term_ptr_add, const int32_t* post_doc_
 AMDR_HD inline long long bm_add_term_ptr(const long long* old_ptr, long n_terms_old, const long long* add_ptr, long t) {
   return old_ptr[t < n_terms_old ? t : n_terms_old] + add_ptr[t];
 }
-
-// The term of output posting p: the largest t in [lo, hi] with ptr[t] <= p, where ptr[lo] <= p < ptr[hi + 1] (terms
-// without postings are stepped over: the largest such t is the one whose list holds p).  `ptr` may be a window of the
-// table: ptr[i] is the entry of term base + i.
-AMDR_HD inline long bm_add_term_of(const long long* ptr, long base, long lo, long hi, long long p) {
-  while (lo < hi) {
-    const long mid = lo + ((hi - lo + 1) >> 1);
-    if (ptr[mid - base] <= p)
-      lo = mid;
-    else
-      hi = mid - 1;
-  }
-  return lo;
-}
-
-// The terms of a tile's first and last posting, [p0, p1) not empty and inside [0, ptr[n_terms]); and whether the table
-// entries t0 .. t1 + 1 fit the kernel's LDS window (always, unless terms without postings widen the range).
-AMDR_HD inline void bm_add_tile_terms(const long long* ptr, long n_terms, long long p0, long long p1, long* t0, long* t1) {
-  *t0 = bm_add_term_of(ptr, 0, 0, n_terms - 1, p0);
-  *t1 = bm_add_term_of(ptr, 0, *t0, n_terms - 1, p1 - 1);
-}
-AMDR_HD inline bool bm_add_window_fits(long t0, long t1) { return t1 - t0 + 2 <= (long)(kBmAddTile + 2); }
 
 // Output posting p of term t (new_start = the term's first output position): its first old_df entries are the old
 // list, the rest the add's.  Returns the source index and sets *from_add.

@@ -1,0 +1,90 @@
+// The BM25 handle, shared by bm25.hip (create, plan, score, search, destroy) and bm25_update.hip (add, remove, info, read).
+#pragma once
+#include "common.hpp"
+
+#include <mutex>
+#include <utility>
+
+namespace amdr {
+
+// count elements of T on the device (count may be 0); a failure names the entry point `who`
+template <class T>
+int bm_dev_alloc(T** dst, size_t count, const char* who) {
+  *dst = nullptr;
+  const size_t bytes = count * sizeof(T);
+  if (hipMalloc((void**)dst, bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    *dst = nullptr;
+    return fail(AMDR_ENOMEM, "%s: device allocation of %zu B failed", who, bytes);
+  }
+  return AMDR_OK;
+}
+
+// The resident index: term-major CSR postings, the per-posting factors, idf and the document lengths.  Every array
+// carries ONE padding element behind its `count` values — the scoring kernel's clamped prefetch may touch [count] — and
+// alloc() is the only place that knows it: amdr_bm25_create's upload and the updates allocate through it.
+struct BmIndex {
+  long long* term_ptr = nullptr;  // [n_terms + 1]
+  int* post_doc = nullptr;        // [nnz]
+  int* post_tf = nullptr;         // [nnz] resident for the updates: the factors are recomputed from (tf, doc_len, avgdl)
+  double* post_w = nullptr;       // [nnz] tf*(k1+1) / (tf + k1*(1 - b + b*len/avgdl)) per posting, fp64
+  double* idf = nullptr;          // [n_terms]
+  int* doc_len = nullptr;         // [n_docs]
+  int64_t n_terms = 0, n_docs = 0, nnz = 0;
+  double avgdl = 0;
+
+  template <class T>
+  static int alloc(T** dst, size_t count, const char* who) {
+    return bm_dev_alloc(dst, count + 1, who);
+  }
+  // the tables of n_terms terms and n_docs documents; the postings, once their number is known
+  int alloc_tables(int64_t V, int64_t n, double avg, const char* who) {
+    n_terms = V, n_docs = n, avgdl = avg;
+    int rc = alloc(&term_ptr, (size_t)V + 1, who);
+    if (!rc) rc = alloc(&idf, (size_t)V, who);
+    if (!rc) rc = alloc(&doc_len, (size_t)n, who);
+    return rc;
+  }
+  int alloc_postings(int64_t count, const char* who) {
+    nnz = count;
+    int rc = alloc(&post_doc, (size_t)count, who);
+    if (!rc) rc = alloc(&post_tf, (size_t)count, who);
+    if (!rc) rc = alloc(&post_w, (size_t)count, who);
+    return rc;
+  }
+  void free() {
+    for (void* q : {(void*)term_ptr, (void*)post_doc, (void*)post_tf, (void*)post_w, (void*)idf, (void*)doc_len})
+      if (q) (void)hipFree(q);
+    *this = BmIndex();
+  }
+};
+
+// An index in the making, beside the live one (amdr_bm25_add, amdr_bm25_remove).  commit() is the whole update: the two
+// values change places, so this one's destructor frees the OLD arrays after a commit and the half-built ones after a
+// failure — a failed update leaves the handle as it was.
+struct BmStagedIndex : BmIndex {
+  BmStagedIndex() = default;
+  BmStagedIndex(const BmStagedIndex&) = delete;
+  BmStagedIndex& operator=(const BmStagedIndex&) = delete;
+  ~BmStagedIndex() { free(); }
+  void commit(BmIndex& live, int64_t& updates) {
+    std::swap(live, static_cast<BmIndex&>(*this));
+    ++updates;
+  }
+};
+
+}  // namespace amdr
+
+struct amdr_bm25 {
+  int device = 0;
+  amdr::BmIndex ix;
+  int64_t adds = 0, removes = 0;
+  double k1 = 1.5, b = 0.75;
+  double add_kernel_ms = -1;     // event time of the last add's merge kernel (amdr_bm25_add_kernel_ms)
+  double remove_kernel_ms = -1;  // summed event time of the last remove's passes (amdr_bm25_remove_kernel_ms)
+  hipStream_t stream = nullptr;
+  std::mutex mu;
+  // part[0]: "_device" calls, part[1]: host-pointer calls (see dense.hip)
+  amdr::DevBuf part[2], qterms, qptr, sbuf, ibuf, full;
+  amdr::DevBuf ticket;  // 64 zeroed ints: arrival counters of the one-launch serving step (dense_tail.hip), self-resetting
+};

@@ -1,19 +1,18 @@
-// The rules of amdr_bm25_remove (bm25.hip) that are plain C++: the host validation of the call's own arrays, the new id of
+// The rules of amdr_bm25_remove (bm25_update.hip) that are plain C++: the host validation of the call's own arrays, the new id of
 // an old document, the rank of an old posting among the surviving ones, a term's surviving count and where a surviving
 // posting goes.  The kernels and the host check (check_bm25_remove.cpp, which compacts on the CPU with the same
-// functions) share this one source, in the style of bm25_add_rule.hpp, whose tile length and term search are used here
-// too: a tile is kBmAddTile consecutive OLD postings.
+// functions) share this one source, in the style of bm25_add_rule.hpp.  The tile (here kBmTile consecutive OLD postings)
+// and the term search are those of bm25_tile_rule.hpp.
 #pragma once
-#include <cmath>
 #include <cstdint>
 #include <memory>
 #include <new>
 
-#include "bm25_add_rule.hpp"
+#include "bm25_tile_rule.hpp"
 
 namespace amdr {
 
-static_assert(kBmAddTile <= 65536, "a posting's rank inside its tile is kept in 16 bits");
+static_assert(kBmTile <= 65536, "a posting's rank inside its tile is kept in 16 bits");
 
 // Why a remove is refused (0 = it is accepted).  Reads the call's arrays only: O(V + n_remove).
 enum BmRemoveError {
@@ -57,9 +56,8 @@ inline int bm_rm_validate(const int64_t* remove_ids, int64_t n_remove, const int
     if (remove_ids[i] < 0 || remove_ids[i] >= n_docs_old) return kBmRmIdRange;
     if (i > 0 && remove_ids[i] <= remove_ids[i - 1]) return kBmRmIdOrder;
   }
-  if (!std::isfinite(avgdl) || !(avgdl > 0.0)) return kBmRmAvgdl;
-  for (int64_t t = 0; t < n_terms_new; ++t)
-    if (!std::isfinite(idf[t])) return kBmRmIdf;
+  if (!bm_avgdl_ok(avgdl)) return kBmRmAvgdl;
+  if (!bm_idf_all_finite(idf, n_terms_new)) return kBmRmIdf;
   if (term_map) {
     std::unique_ptr<unsigned char[]> seen(new (std::nothrow) unsigned char[(size_t)n_terms_new + 1]());
     if (!seen) return kBmRmNoMem;
@@ -95,8 +93,8 @@ AMDR_HD inline int bm_rm_doc_new(const long long* remove_ids, long n_remove, lon
 // The number of surviving postings before old posting q, q in [0, nnz_old]: the base of q's tile (the exclusive scan of
 // the tile counts, tile_base[n_tiles] being the total) plus q's rank inside the tile.
 AMDR_HD inline long long bm_rm_rank(long long q, long long nnz_old, const long long* tile_base, const unsigned short* tile_rank) {
-  if (q >= nnz_old) return tile_base[(nnz_old + kBmAddTile - 1) / kBmAddTile];
-  return tile_base[q / kBmAddTile] + (long long)tile_rank[q];
+  if (q >= nnz_old) return tile_base[(nnz_old + kBmTile - 1) / kBmTile];
+  return tile_base[q / kBmTile] + (long long)tile_rank[q];
 }
 
 // The new id of old term t (a null map is the identity).

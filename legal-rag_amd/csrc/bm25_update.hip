@@ -1,0 +1,443 @@
+// BM25 channel: updates of the resident index (bm25_handle.hpp) — amdr_bm25_add, amdr_bm25_remove — and what reads it
+// back (amdr_bm25_info, amdr_bm25_read).  After any sequence of updates the handle is what amdr_bm25_create (bm25.hip)
+// makes of the resulting index, byte for byte: built with -ffp-contract=off, as bm25.hip is, so that bm25_factor gives the
+// bits of create's host loop.
+//
+// Both updates build a second BmIndex beside the live one and commit it by one swap after the stream has finished: a
+// failed update leaves the handle as it was.  Both divide the work by tiles of kBmTile postings, not by terms (a Zipfian
+// head term holds every document and a wave per term would serialise on it); a block finds the terms of its tile with
+// bm_tile_window.  No atomics anywhere: the result is deterministic.
+//
+// amdr_bm25_add appends documents.  N and avgdl are corpus-global, so every factor changes: the add is ONE pass over the
+// resident postings (bm25_merge_kernel) that interleaves each term's old list with the added documents' list behind it
+// and recomputes post_w with the new avgdl, next to the data.  post_tf and doc_len stay resident for that (16 B per
+// posting instead of 12, + 4 B per document).
+//
+// amdr_bm25_remove takes documents out.  It is a stream compaction of the postings in two passes over them, divided by
+// tiles of kBmTile OLD postings (compact.hpp, bm25_remove_rule.hpp):
+//   bm25_rm_docmap_kernel   doc_new[d] = -1 or d minus the remove ids below d; doc_len compacted through it
+//   bm25_rm_count_kernel    per tile: the keep flags scanned in LDS -> each posting's rank inside its tile (2 B) + the
+//                           tile's count                                         reads 4 B + a 4 B gather, writes 2 B
+//   compact_scan_i64_kernel tile counts -> tile bases (the last one is nnz_new)
+//   bm25_rm_terms_kernel    per old term: rank of its first posting (rank_at), surviving count -> df_new[term_map[t]];
+//                           a term mapped to -1 with a surviving posting raises the error flag
+//   compact_scan_i64_kernel df_new -> the new term_ptr
+//   (the host reads nnz_new and the flag here, and allocates the new posting arrays at their exact size)
+//   bm25_rm_scatter_kernel  per tile: a kept posting of term t goes to new_ptr[term_map[t]] + rank - rank_at[t] with its
+//                           mapped document, its tf and the recomputed factor    reads 10 B + two 4 B gathers, writes 16 B
+#include "common.hpp"
+
+#include <mutex>
+
+#include "bm25_add_rule.hpp"
+#include "bm25_core.hpp"
+#include "bm25_handle.hpp"
+#include "bm25_remove_rule.hpp"
+#include "compact.hpp"
+
+using namespace amdr;
+
+namespace {
+
+// ---- the tile walk of the update kernels -----------------------------------------------------------------------------
+// Thread tid of a block owns postings p0 + u * kBmTileThreads + tid of its tile, u = 0 .. kBmTilePerThread - 1.  (That loop
+// stays written out in the three kernels: with its body passed as a functor they compile to other code, 29 for 35 VGPRs
+// in the merge kernel.)
+// Where the postings of a tile find their terms: tab[t - base] is the table entry of term t, for t in [t0, t1 + 1].
+struct BmTileWindow {
+  const long long* tab;
+  long base, t0, t1;
+  __device__ long term_of(long long p) const { return bm_tile_term_of(tab, base, t0, t1, p); }
+  __device__ long long start_of(long t) const { return tab[t - base]; }
+};
+
+// The terms of tile [p0, p1) (not empty) in the table `ptr` of n_terms terms; every thread of the block calls this.
+// Thread 0 finds the terms of the tile's first and last posting by binary search in the table; the entries between them
+// go to `win` (LDS, kBmTile + 2 entries: a tile holds at most kBmTile terms that have postings).  A window widened by
+// terms WITHOUT postings beyond that room is searched in global memory instead.
+__device__ __forceinline__ BmTileWindow bm_tile_window(const long long* __restrict__ ptr, long n_terms, long long p0,
+                                                       long long p1, long long* win) {
+  __shared__ long t_first, t_last;
+  const int tid = threadIdx.x;
+  if (tid == 0) {
+    long a, z;
+    bm_tile_terms(ptr, n_terms, p0, p1, &a, &z);
+    t_first = a;
+    t_last = z;
+  }
+  __syncthreads();
+  const long t0 = t_first, t1 = t_last;
+  const bool in_lds = bm_tile_window_fits(t0, t1);
+  if (in_lds) {
+    for (long i = tid; i <= t1 - t0 + 1; i += kBmTileThreads) win[i] = ptr[t0 + i];
+    __syncthreads();
+  }
+  return {in_lds ? win : ptr, in_lds ? t0 : 0, t0, t1};
+}
+
+// ---- amdr_bm25_add: term table and merge ------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void bm25_term_ptr_sum_kernel(const long long* __restrict__ old_ptr, long n_terms_old,
+                                                                const long long* __restrict__ add_ptr, long n_terms_new,
+                                                                long long* __restrict__ new_ptr) {
+  const long t = (long)blockIdx.x * 256 + threadIdx.x;
+  if (t <= n_terms_new) new_ptr[t] = bm_add_term_ptr(old_ptr, n_terms_old, add_ptr, t);
+}
+
+// One block = kBmTile consecutive OUTPUT postings, their terms found in the NEW term table.  A posting reads 8 B (doc, tf)
+// from the old list or the add's, gathers 4 B of doc_len, and writes 16 B (doc, tf, factor).
+__global__ __launch_bounds__(kBmTileThreads) void bm25_merge_kernel(
+    const long long* __restrict__ new_ptr, long n_terms_new, const long long* __restrict__ old_ptr, long n_terms_old,
+    const int* __restrict__ old_doc, const int* __restrict__ old_tf, const long long* __restrict__ add_ptr,
+    const int* __restrict__ add_doc, const int* __restrict__ add_tf, const int* __restrict__ doc_len /* new */,
+    int n_docs_old, long long nnz_new, double avgdl, double k1, double b, int* __restrict__ out_doc,
+    int* __restrict__ out_tf, double* __restrict__ out_w) {
+  __shared__ long long win[kBmTile + 2];
+  const long long p0 = (long long)blockIdx.x * kBmTile;
+  long long p1 = p0 + kBmTile;  // exclusive
+  if (p1 > nnz_new) p1 = nnz_new;
+  if (p0 >= p1) return;
+  const BmTileWindow w = bm_tile_window(new_ptr, n_terms_new, p0, p1, win);
+  const int tid = threadIdx.x;
+#pragma unroll
+  for (int u = 0; u < kBmTilePerThread; ++u) {
+    const long long p = p0 + (long long)u * kBmTileThreads + tid;
+    if (p < p1) {
+      const long t = w.term_of(p);
+      bool from_add;
+      const long long src = bm_add_source(p, w.start_of(t), t, old_ptr, n_terms_old, add_ptr, &from_add);
+      const int doc = from_add ? add_doc[src] + n_docs_old : old_doc[src];
+      const int tf = from_add ? add_tf[src] : old_tf[src];
+      out_doc[p] = doc;
+      out_tf[p] = tf;
+      out_w[p] = bm25_factor(tf, doc_len[doc], avgdl, k1, b);
+    }
+  }
+}
+
+// ---- amdr_bm25_remove: document map, tile ranks, term table, scatter -------------------------------------------------
+__global__ __launch_bounds__(256) void bm25_rm_docmap_kernel(const long long* __restrict__ remove_ids, long n_remove,
+                                                             const int* __restrict__ doc_len_old, long n_docs_old,
+                                                             int* __restrict__ doc_new, int* __restrict__ doc_len_new) {
+  const long d = (long)blockIdx.x * 256 + threadIdx.x;
+  if (d >= n_docs_old) return;
+  const int nd = bm_rm_doc_new(remove_ids, n_remove, d);
+  doc_new[d] = nd;
+  if (nd >= 0) doc_len_new[nd] = doc_len_old[d];
+}
+
+// One block = one tile of kBmTile consecutive OLD postings: which of them survive, each one's rank among the tile's
+// survivors (compact_tile_scan) and the tile's count.
+__global__ __launch_bounds__(kBmTileThreads) void bm25_rm_count_kernel(const int* __restrict__ old_doc, long long nnz_old,
+                                                                       const int* __restrict__ doc_new,
+                                                                       unsigned short* __restrict__ tile_rank,
+                                                                       long long* __restrict__ tile_cnt) {
+  __shared__ int lds[kBmTile + kBmTileThreads / 64 + 1];
+  const long long p0 = (long long)blockIdx.x * kBmTile;
+  const int tid = threadIdx.x;
+  unsigned keep = 0;
+#pragma unroll
+  for (int u = 0; u < kBmTilePerThread; ++u) {
+    const long long p = p0 + (long long)u * kBmTileThreads + tid;
+    if (p < nnz_old && doc_new[old_doc[p]] >= 0) keep |= 1u << u;
+  }
+  int rank[kBmTilePerThread];
+  const int total = compact_tile_scan<kBmTileThreads, kBmTilePerThread>(keep, lds, rank);
+#pragma unroll
+  for (int u = 0; u < kBmTilePerThread; ++u) {
+    const long long p = p0 + (long long)u * kBmTileThreads + tid;
+    if (p < nnz_old) tile_rank[p] = (unsigned short)rank[u];
+  }
+  if (tid == 0) tile_cnt[blockIdx.x] = total;
+}
+
+__global__ __launch_bounds__(256) void bm25_rm_terms_kernel(const long long* __restrict__ old_ptr, long n_terms_old,
+                                                            long long nnz_old, const long long* __restrict__ tile_base,
+                                                            const unsigned short* __restrict__ tile_rank,
+                                                            const int* __restrict__ term_map, long long* __restrict__ rank_at,
+                                                            long long* __restrict__ df_new, int* __restrict__ bad) {
+  const long t = (long)blockIdx.x * 256 + threadIdx.x;
+  if (t <= n_terms_old) bm_rm_term_entry(t, n_terms_old, old_ptr, nnz_old, tile_base, tile_rank, term_map, rank_at, df_new, bad);
+}
+
+// One block = one tile of OLD postings again, their terms found in the OLD term table.  A surviving posting reads 8 B
+// (doc, tf) + 2 B of rank, gathers doc_new and doc_len (4 B each) and the few table entries of its term, and writes 16 B
+// (doc, tf, factor) at bm_rm_dest.  Every destination is a sum of counts.
+__global__ __launch_bounds__(kBmTileThreads) void bm25_rm_scatter_kernel(
+    const long long* __restrict__ old_ptr, long n_terms_old, const int* __restrict__ old_doc, const int* __restrict__ old_tf,
+    long long nnz_old, const int* __restrict__ doc_new, const int* __restrict__ doc_len /* new */,
+    const long long* __restrict__ tile_base, const unsigned short* __restrict__ tile_rank,
+    const long long* __restrict__ rank_at, const long long* __restrict__ new_ptr, const int* __restrict__ term_map,
+    long long nnz_new, double avgdl, double k1, double b, int* __restrict__ out_doc, int* __restrict__ out_tf,
+    double* __restrict__ out_w) {
+  __shared__ long long win[kBmTile + 2];
+  const long long p0 = (long long)blockIdx.x * kBmTile;
+  long long p1 = p0 + kBmTile;  // exclusive
+  if (p1 > nnz_old) p1 = nnz_old;
+  if (p0 >= p1) return;
+  const BmTileWindow w = bm_tile_window(old_ptr, n_terms_old, p0, p1, win);
+  const int tid = threadIdx.x;
+#pragma unroll
+  for (int u = 0; u < kBmTilePerThread; ++u) {
+    const long long p = p0 + (long long)u * kBmTileThreads + tid;
+    if (p < p1) {
+      const int doc = doc_new[old_doc[p]];
+      if (doc >= 0) {
+        const long long dst = bm_rm_dest(p, w.term_of(p), nnz_old, tile_base, tile_rank, rank_at, new_ptr, term_map);
+        if (dst >= 0 && dst < nnz_new) {  // (always, after the host's checks and the terms kernel's flag)
+          const int tf = old_tf[p];
+          out_doc[dst] = doc;
+          out_tf[dst] = tf;
+          out_w[dst] = bm25_factor(tf, doc_len[doc], avgdl, k1, b);
+        }
+      }
+    }
+  }
+}
+
+// ---- host: per-call scratch and the kernel timer ---------------------------------------------------------------------
+// Typed device arrays that live for one call: freed on return.  (Not DevBuf: a call's scratch is no workspace growth.)
+struct BmScratch {
+  void* held[12] = {};
+  int n = 0;
+  BmScratch() = default;
+  BmScratch(const BmScratch&) = delete;
+  BmScratch& operator=(const BmScratch&) = delete;
+  ~BmScratch() {
+    for (int i = 0; i < n; ++i) (void)hipFree(held[i]);
+  }
+  template <class T>
+  int alloc(T** p, size_t count, const char* who) {
+    *p = nullptr;
+    if (n == (int)(sizeof(held) / sizeof(held[0]))) return fail(AMDR_EINVAL, "%s: too many scratch arrays", who);
+    const int rc = bm_dev_alloc(p, count, who);
+    if (!rc && *p) held[n++] = (void*)*p;
+    return rc;
+  }
+};
+
+// Device time of up to two stretches of a stream between events.  Events that cannot be made only lose the time: the
+// spans then record nothing and ms() is -1.
+struct BmSpans {
+  hipEvent_t ev[4] = {};
+  int spans, recorded = 0;
+  bool ok = true;
+  explicit BmSpans(int spans_) : spans(spans_) {
+    for (int i = 0; i < 2 * spans && ok; ++i)
+      if (hipEventCreate(&ev[i]) != hipSuccess) {
+        (void)hipGetLastError();
+        ev[i] = nullptr;
+        ok = false;
+      }
+  }
+  BmSpans(const BmSpans&) = delete;
+  BmSpans& operator=(const BmSpans&) = delete;
+  ~BmSpans() {
+    for (hipEvent_t e : ev)
+      if (e) (void)hipEventDestroy(e);
+  }
+  int begin(int i, hipStream_t st) {
+    if (ok) AMDR_HIP(hipEventRecord(ev[2 * i], st));
+    return AMDR_OK;
+  }
+  int end(int i, hipStream_t st) {
+    if (ok) AMDR_HIP(hipEventRecord(ev[2 * i + 1], st));
+    ++recorded;
+    return AMDR_OK;
+  }
+  // the summed milliseconds of the recorded spans, once the stream has finished; exactly -1.0 when there is no time
+  double ms() const {
+    if (!ok || recorded == 0) return -1.0;
+    double sum = 0;
+    for (int i = 0; i < recorded; ++i) {
+      float t = 0.f;
+      if (hipEventElapsedTime(&t, ev[2 * i], ev[2 * i + 1]) != hipSuccess) {
+        (void)hipGetLastError();
+        return -1.0;
+      }
+      sum += (double)t;
+    }
+    return sum;
+  }
+};
+
+#define AMDR_TRY(expr)         \
+  do {                         \
+    const int _rc = (expr);    \
+    if (_rc) return _rc;       \
+  } while (0)
+
+}  // namespace
+
+extern "C" {
+
+int amdr_bm25_add(amdr_bm25_t* h, const int64_t* term_ptr_add, const int32_t* post_doc_add, const int32_t* post_tf_add,
+                  const double* idf, const int32_t* doc_len_add, int64_t n_terms, int64_t n_add, double avgdl) {
+  static const char* const who = "bm25_add";
+  AMDR_REQUIRE(h != nullptr, "bm25_add: null handle");
+  AMDR_REQUIRE(n_add >= 0, "bm25_add: n_add=%lld", (long long)n_add);
+  if (n_add == 0) return AMDR_OK;
+  std::lock_guard<std::mutex> g(h->mu);
+  const BmIndex& old = h->ix;
+  const int bad = bm_add_validate(term_ptr_add, post_doc_add, post_tf_add, idf, doc_len_add, n_terms, n_add, avgdl,
+                                  old.n_terms, old.n_docs);
+  AMDR_REQUIRE(bad == kBmAddOk, "bm25_add: %s", bm_add_error_text(bad));
+  AMDR_HIP(hipSetDevice(h->device));
+  const int64_t nnz_add = term_ptr_add[n_terms], nnz_new = old.nnz + nnz_add;
+  BmStagedIndex nx;
+  AMDR_TRY(nx.alloc_tables(n_terms, old.n_docs + n_add, avgdl, who));
+  AMDR_TRY(nx.alloc_postings(nnz_new, who));
+  // the add's own CSR on the device (never an empty allocation)
+  BmScratch tmp;
+  long long* add_ptr;
+  int *add_doc, *add_tf;
+  AMDR_TRY(tmp.alloc(&add_ptr, (size_t)n_terms + 1, who));
+  AMDR_TRY(tmp.alloc(&add_doc, (size_t)nnz_add + 1, who));
+  AMDR_TRY(tmp.alloc(&add_tf, (size_t)nnz_add + 1, who));
+  hipStream_t st = h->stream;
+  AMDR_HIP(hipMemcpyAsync(add_ptr, term_ptr_add, (size_t)(n_terms + 1) * sizeof(long long), hipMemcpyHostToDevice, st));
+  if (nnz_add) {
+    AMDR_HIP(hipMemcpyAsync(add_doc, post_doc_add, (size_t)nnz_add * sizeof(int), hipMemcpyHostToDevice, st));
+    AMDR_HIP(hipMemcpyAsync(add_tf, post_tf_add, (size_t)nnz_add * sizeof(int), hipMemcpyHostToDevice, st));
+  }
+  if (n_terms) AMDR_HIP(hipMemcpyAsync(nx.idf, idf, (size_t)n_terms * sizeof(double), hipMemcpyHostToDevice, st));
+  AMDR_HIP(hipMemcpyAsync(nx.doc_len, old.doc_len, (size_t)old.n_docs * sizeof(int), hipMemcpyDeviceToDevice, st));
+  AMDR_HIP(hipMemcpyAsync(nx.doc_len + old.n_docs, doc_len_add, (size_t)n_add * sizeof(int), hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(bm25_term_ptr_sum_kernel, dim3((unsigned)((n_terms + 1 + 255) / 256)), dim3(256), 0, st, old.term_ptr,
+                     (long)old.n_terms, add_ptr, (long)n_terms, nx.term_ptr);
+  AMDR_HIP(hipGetLastError());
+  BmSpans timer(1);  // the merge kernel (amdr_bm25_add_kernel_ms)
+  if (nnz_new > 0) {
+    const long long blocks = (nnz_new + kBmTile - 1) / kBmTile;
+    AMDR_REQUIRE(blocks < (1ll << 31), "bm25_add: %lld postings exceed the merge grid", (long long)nnz_new);
+    AMDR_TRY(timer.begin(0, st));
+    hipLaunchKernelGGL(bm25_merge_kernel, dim3((unsigned)blocks), dim3(kBmTileThreads), 0, st, nx.term_ptr, (long)n_terms,
+                       old.term_ptr, (long)old.n_terms, old.post_doc, old.post_tf, add_ptr, add_doc, add_tf, nx.doc_len,
+                       (int)old.n_docs, (long long)nnz_new, avgdl, h->k1, h->b, nx.post_doc, nx.post_tf, nx.post_w);
+    AMDR_HIP(hipGetLastError());
+    AMDR_TRY(timer.end(0, st));
+  }
+  AMDR_HIP(hipStreamSynchronize(st));
+  h->add_kernel_ms = timer.ms();
+  nx.commit(h->ix, h->adds);  // from here on nothing can fail
+  return AMDR_OK;
+}
+
+int amdr_bm25_remove(amdr_bm25_t* h, const int64_t* remove_ids, int64_t n_remove, const int32_t* term_map,
+                     int64_t n_terms_new, const double* idf, double avgdl) {
+  static const char* const who = "bm25_remove";
+  AMDR_REQUIRE(h != nullptr, "bm25_remove: null handle");
+  AMDR_REQUIRE(n_remove >= 0, "bm25_remove: n_remove=%lld", (long long)n_remove);
+  if (n_remove == 0) return AMDR_OK;
+  std::lock_guard<std::mutex> g(h->mu);
+  const BmIndex& old = h->ix;
+  const int bad = bm_rm_validate(remove_ids, n_remove, term_map, n_terms_new, idf, avgdl, old.n_terms, old.n_docs);
+  if (bad == kBmRmNoMem) return fail(AMDR_ENOMEM, "bm25_remove: %s", bm_rm_error_text(bad));
+  AMDR_REQUIRE(bad == kBmRmOk, "bm25_remove: %s", bm_rm_error_text(bad));
+  AMDR_HIP(hipSetDevice(h->device));
+  const int64_t V_old = old.n_terms, V_new = n_terms_new, nnz_old = old.nnz, n_old = old.n_docs;
+  const long long tiles = (nnz_old + kBmTile - 1) / kBmTile;
+  AMDR_REQUIRE(tiles < (1ll << 31), "bm25_remove: %lld postings exceed the grid", (long long)nnz_old);
+  BmStagedIndex nx;
+  AMDR_TRY(nx.alloc_tables(V_new, n_old - n_remove, avgdl, who));
+  BmScratch tmp;
+  long long *rm_ids, *tile_cnt, *tile_base, *rank_at, *df_new;
+  int *doc_new, *map_dev = nullptr, *flag_dev;
+  unsigned short* tile_rank;
+  AMDR_TRY(tmp.alloc(&rm_ids, (size_t)n_remove, who));
+  AMDR_TRY(tmp.alloc(&doc_new, (size_t)n_old, who));
+  AMDR_TRY(tmp.alloc(&tile_rank, (size_t)nnz_old + 1, who));  // (+ 1: never an empty allocation)
+  AMDR_TRY(tmp.alloc(&tile_cnt, (size_t)tiles + 1, who));
+  AMDR_TRY(tmp.alloc(&tile_base, (size_t)tiles + 1, who));
+  AMDR_TRY(tmp.alloc(&rank_at, (size_t)V_old + 1, who));
+  AMDR_TRY(tmp.alloc(&df_new, (size_t)V_new + 1, who));
+  if (term_map) AMDR_TRY(tmp.alloc(&map_dev, (size_t)V_old + 1, who));
+  AMDR_TRY(tmp.alloc(&flag_dev, 1, who));
+  hipStream_t st = h->stream;
+  AMDR_HIP(hipMemcpyAsync(rm_ids, remove_ids, (size_t)n_remove * sizeof(long long), hipMemcpyHostToDevice, st));
+  if (term_map && V_old) AMDR_HIP(hipMemcpyAsync(map_dev, term_map, (size_t)V_old * sizeof(int), hipMemcpyHostToDevice, st));
+  if (V_new) AMDR_HIP(hipMemcpyAsync(nx.idf, idf, (size_t)V_new * sizeof(double), hipMemcpyHostToDevice, st));
+  AMDR_HIP(hipMemsetAsync(flag_dev, 0, sizeof(int), st));
+  // the passes in two stretches, with the host's look at nnz_new between them (amdr_bm25_remove_kernel_ms)
+  BmSpans timer(2);
+  AMDR_TRY(timer.begin(0, st));
+  hipLaunchKernelGGL(bm25_rm_docmap_kernel, dim3((unsigned)((n_old + 255) / 256)), dim3(256), 0, st, rm_ids, (long)n_remove,
+                     old.doc_len, (long)n_old, doc_new, nx.doc_len);
+  AMDR_HIP(hipGetLastError());
+  if (tiles > 0) {
+    hipLaunchKernelGGL(bm25_rm_count_kernel, dim3((unsigned)tiles), dim3(kBmTileThreads), 0, st, old.post_doc,
+                       (long long)nnz_old, doc_new, tile_rank, tile_cnt);
+    AMDR_HIP(hipGetLastError());
+  }
+  hipLaunchKernelGGL(compact_scan_i64_kernel, dim3(1), dim3(kCompactScanThreads), 0, st, tile_cnt, (long)tiles, tile_base);
+  AMDR_HIP(hipGetLastError());
+  hipLaunchKernelGGL(bm25_rm_terms_kernel, dim3((unsigned)((V_old + 1 + 255) / 256)), dim3(256), 0, st, old.term_ptr,
+                     (long)V_old, (long long)nnz_old, tile_base, tile_rank, map_dev, rank_at, df_new, flag_dev);
+  AMDR_HIP(hipGetLastError());
+  hipLaunchKernelGGL(compact_scan_i64_kernel, dim3(1), dim3(kCompactScanThreads), 0, st, df_new, (long)V_new, nx.term_ptr);
+  AMDR_HIP(hipGetLastError());
+  AMDR_TRY(timer.end(0, st));
+  long long nnz_new = 0;
+  int flag = 0;
+  AMDR_HIP(hipMemcpyAsync(&nnz_new, tile_base + tiles, sizeof(long long), hipMemcpyDeviceToHost, st));
+  AMDR_HIP(hipMemcpyAsync(&flag, flag_dev, sizeof(int), hipMemcpyDeviceToHost, st));
+  AMDR_HIP(hipStreamSynchronize(st));
+  AMDR_REQUIRE(flag == 0, "bm25_remove: a term mapped to -1 still has a surviving posting");
+  if (nnz_new < 0 || nnz_new > nnz_old) return fail(AMDR_EHIP, "bm25_remove: counted %lld of %lld postings", nnz_new, (long long)nnz_old);
+  AMDR_TRY(nx.alloc_postings(nnz_new, who));
+  AMDR_TRY(timer.begin(1, st));
+  if (tiles > 0 && nnz_new > 0) {
+    hipLaunchKernelGGL(bm25_rm_scatter_kernel, dim3((unsigned)tiles), dim3(kBmTileThreads), 0, st, old.term_ptr, (long)V_old,
+                       old.post_doc, old.post_tf, (long long)nnz_old, doc_new, nx.doc_len, tile_base, tile_rank, rank_at,
+                       nx.term_ptr, map_dev, nnz_new, avgdl, h->k1, h->b, nx.post_doc, nx.post_tf, nx.post_w);
+    AMDR_HIP(hipGetLastError());
+  }
+  AMDR_TRY(timer.end(1, st));
+  AMDR_HIP(hipStreamSynchronize(st));
+  h->remove_kernel_ms = timer.ms();
+  nx.commit(h->ix, h->removes);  // from here on nothing can fail
+  return AMDR_OK;
+}
+
+int amdr_bm25_add_kernel_ms(amdr_bm25_t* h, double* ms) {
+  AMDR_REQUIRE(h && ms, "bm25_add_kernel_ms: null");
+  std::lock_guard<std::mutex> g(h->mu);
+  *ms = h->add_kernel_ms;
+  return AMDR_OK;
+}
+
+int amdr_bm25_remove_kernel_ms(amdr_bm25_t* h, double* ms) {
+  AMDR_REQUIRE(h && ms, "bm25_remove_kernel_ms: null");
+  std::lock_guard<std::mutex> g(h->mu);
+  *ms = h->remove_kernel_ms;
+  return AMDR_OK;
+}
+
+int amdr_bm25_info(amdr_bm25_t* h, int64_t* out6) {
+  AMDR_REQUIRE(h && out6, "bm25_info: null");
+  std::lock_guard<std::mutex> g(h->mu);
+  out6[0] = h->ix.n_docs;
+  out6[1] = h->ix.n_terms;
+  out6[2] = h->ix.nnz;
+  out6[3] = h->adds;
+  out6[4] = kBmTile;
+  out6[5] = h->removes;
+  return AMDR_OK;
+}
+
+int amdr_bm25_read(amdr_bm25_t* h, int64_t* term_ptr, int32_t* post_doc, int32_t* post_tf, double* post_w, double* idf,
+                   int32_t* doc_len) {
+  AMDR_REQUIRE(h != nullptr, "bm25_read: null handle");
+  std::lock_guard<std::mutex> g(h->mu);
+  AMDR_HIP(hipSetDevice(h->device));
+  const BmIndex& ix = h->ix;
+  const size_t V = (size_t)ix.n_terms, nnz = (size_t)ix.nnz, n = (size_t)ix.n_docs;
+  if (term_ptr) AMDR_HIP(hipMemcpy(term_ptr, ix.term_ptr, (V + 1) * sizeof(long long), hipMemcpyDeviceToHost));
+  if (post_doc && nnz) AMDR_HIP(hipMemcpy(post_doc, ix.post_doc, nnz * sizeof(int), hipMemcpyDeviceToHost));
+  if (post_tf && nnz) AMDR_HIP(hipMemcpy(post_tf, ix.post_tf, nnz * sizeof(int), hipMemcpyDeviceToHost));
+  if (post_w && nnz) AMDR_HIP(hipMemcpy(post_w, ix.post_w, nnz * sizeof(double), hipMemcpyDeviceToHost));
+  if (idf && V) AMDR_HIP(hipMemcpy(idf, ix.idf, V * sizeof(double), hipMemcpyDeviceToHost));
+  if (doc_len && n) AMDR_HIP(hipMemcpy(doc_len, ix.doc_len, n * sizeof(int), hipMemcpyDeviceToHost));
+  return AMDR_OK;
+}
+
+}  // extern "C"

@@ -1,11 +1,13 @@
-// Host check of the rules of amdr_bm25_add (bm25_add_rule.hpp), a program of its own (never part of the library):
+// Host check of the rules of amdr_bm25_add (bm25_add_rule.hpp, bm25_tile_rule.hpp), a program of its own (never part of
+// the library):
 //   check_bm25_add
 // It builds random term-major indexes and adds (Zipfian lists, terms without postings, new terms, a total that is an
-// exact multiple of the merge tile and one more), merges them on the CPU the way bm25_merge_kernel does — tile by tile,
-// the tile's terms by bm_add_tile_terms, a window of the term table copied out exactly as the kernel's LDS window, every
-// posting by bm_add_term_of + bm_add_source — and compares the result with a plain per-term concatenation.  Every array
-// is a std::vector of exactly the size the ABI promises, so with the host sanitizers (tests/test_bm25_add_rule_host.py)
-// an access outside one is a failure.  Then every refusal of bm_add_validate is provoked once, on arrays of exact size.
+// exact multiple of the merge tile and one more), merges them on the CPU the way bm25_merge_kernel does — tile by tile
+// (host_tile_walk, check_bm25_common.hpp), the tile's terms by bm_tile_terms, a window of the term table copied out
+// exactly as the kernel's LDS window, every posting by bm_tile_term_of + bm_add_source — and compares the result with a
+// plain per-term concatenation.  Every array is a std::vector of exactly the size the ABI promises, so with the host
+// sanitizers (tests/test_bm25_add_rule_host.py) an access outside one is a failure.  Then every refusal of
+// bm_add_validate is provoked once, on arrays of exact size.
 // Build: c++ -std=c++17 check_bm25_add.cpp (plain host code; no HIP header is read).
 #include <cstdint>
 #include <cstdio>
@@ -14,53 +16,14 @@
 #include <vector>
 
 #include "bm25_add_rule.hpp"
+#include "check_bm25_common.hpp"
 
 using namespace amdr;
 
 namespace {
 
-uint64_t rng_state = 0x9e3779b97f4a7c15ull;
-uint32_t rnd() {
-  rng_state = rng_state * 6364136223846793005ull + 1442695040888963407ull;
-  return (uint32_t)(rng_state >> 33);
-}
-
-struct Csr {
-  std::vector<int64_t> ptr;
-  std::vector<int32_t> doc, tf;
-};
-
-// n_terms lists over n_docs documents: term 0 holds every document, list lengths fall off, every `hole`-th term is empty
-Csr make_csr(long n_terms, long n_docs, long hole) {
-  Csr c;
-  c.ptr.assign(1, 0);
-  for (long t = 0; t < n_terms; ++t) {
-    long df = t == 0 ? n_docs : (long)(n_docs / (t + 1)) + (long)(rnd() % 2);
-    if (df > n_docs) df = n_docs;
-    if (hole && t % hole == hole - 1) df = 0;
-    // df documents in ascending order: a random start and stride 1
-    const long first = df < n_docs ? (long)(rnd() % (uint32_t)(n_docs - df + 1)) : 0;
-    for (long j = 0; j < df; ++j) {
-      c.doc.push_back((int32_t)(first + j));
-      c.tf.push_back((int32_t)(1 + rnd() % 9));
-    }
-    c.ptr.push_back((int64_t)c.doc.size());
-  }
-  return c;
-}
-
-int failures = 0;
-#define CHECK(cond, ...)            \
-  do {                              \
-    if (!(cond)) {                  \
-      ++failures;                   \
-      std::printf("FAIL: " __VA_ARGS__); \
-      std::printf("\n");            \
-    }                               \
-  } while (0)
-
 void merge_case(long v_old, long n_old, long v_new, long n_add, long hole, long long pad_to) {
-  Csr o = make_csr(v_old, n_old, hole), a = make_csr(v_new, n_add, hole);
+  Csr o = make_csr(v_old, n_old, hole, 0, 0), a = make_csr(v_new, n_add, hole, 0, 0);
   // pad_to: further new terms behind the add's table, each holding up to every added document, until the index has
   // exactly pad_to postings
   for (long long total = o.ptr.back() + a.ptr.back(); total < pad_to; ++v_new) {
@@ -69,49 +32,35 @@ void merge_case(long v_old, long n_old, long v_new, long n_add, long hole, long 
       a.doc.push_back((int32_t)j);
       a.tf.push_back(1);
     }
-    a.ptr.push_back((int64_t)a.doc.size());
+    a.ptr.push_back((long long)a.doc.size());
     total += df;
   }
   std::vector<double> idf((size_t)v_new, 1.0);
   std::vector<int32_t> dl((size_t)n_add, 3);
-  const int bad = bm_add_validate(a.ptr.data(), a.doc.data(), a.tf.data(), idf.data(), dl.data(), v_new, n_add, 7.5, v_old, n_old);
+  const int bad = bm_add_validate((const int64_t*)a.ptr.data(), a.doc.data(), a.tf.data(), idf.data(), dl.data(), v_new, n_add, 7.5, v_old, n_old);
   CHECK(bad == kBmAddOk, "a generated add is refused: %s", bm_add_error_text(bad));
-  std::vector<long long> optr(o.ptr.begin(), o.ptr.end()), aptr(a.ptr.begin(), a.ptr.end());
   std::vector<long long> nptr((size_t)v_new + 1);
-  for (long t = 0; t <= v_new; ++t) nptr[(size_t)t] = bm_add_term_ptr(optr.data(), v_old, aptr.data(), t);
+  for (long t = 0; t <= v_new; ++t) nptr[(size_t)t] = bm_add_term_ptr(o.ptr.data(), v_old, a.ptr.data(), t);
   // expected: per term, the old list, then the add's with n_old added
   std::vector<int32_t> ed, et;
   for (long t = 0; t < v_new; ++t) {
     CHECK(nptr[(size_t)t] == (long long)ed.size(), "term_ptr[%ld] = %lld, expected %zu", t, nptr[(size_t)t], ed.size());
     if (t < v_old)
-      for (int64_t p = o.ptr[t]; p < o.ptr[t + 1]; ++p) ed.push_back(o.doc[(size_t)p]), et.push_back(o.tf[(size_t)p]);
-    for (int64_t p = a.ptr[t]; p < a.ptr[t + 1]; ++p) ed.push_back(a.doc[(size_t)p] + (int32_t)n_old), et.push_back(a.tf[(size_t)p]);
+      for (long long p = o.ptr[t]; p < o.ptr[t + 1]; ++p) ed.push_back(o.doc[(size_t)p]), et.push_back(o.tf[(size_t)p]);
+    for (long long p = a.ptr[t]; p < a.ptr[t + 1]; ++p) ed.push_back(a.doc[(size_t)p] + (int32_t)n_old), et.push_back(a.tf[(size_t)p]);
   }
   const long long nnz = nptr[(size_t)v_new];
   CHECK(nnz == (long long)ed.size(), "nnz %lld, expected %zu", nnz, ed.size());
   if (pad_to > 0) CHECK(nnz == pad_to, "case did not reach %lld postings (%lld)", pad_to, nnz);
   std::vector<int32_t> gd((size_t)nnz, -1), gt((size_t)nnz, -1);
-  long windows_global = 0;
-  for (long long p0 = 0; p0 < nnz; p0 += kBmAddTile) {
-    const long long p1 = p0 + kBmAddTile < nnz ? p0 + kBmAddTile : nnz;
-    long t0, t1;
-    bm_add_tile_terms(nptr.data(), v_new, p0, p1, &t0, &t1);
-    const bool fits = bm_add_window_fits(t0, t1);
-    std::vector<long long> win;  // exactly the entries the kernel copies to LDS
-    if (fits) win.assign(nptr.begin() + t0, nptr.begin() + t1 + 2);
-    CHECK(!fits || win.size() <= (size_t)kBmAddTile + 2, "window of %zu entries", win.size());
-    windows_global += fits ? 0 : 1;
-    const long long* tab = fits ? win.data() : nptr.data();
-    const long base = fits ? t0 : 0;
-    for (long long p = p0; p < p1; ++p) {
-      const long t = bm_add_term_of(tab, base, t0, t1, p);
-      CHECK(nptr[(size_t)t] <= p && p < nptr[(size_t)t + 1], "posting %lld put in term %ld", p, t);
-      bool from_add;
-      const long long src = bm_add_source(p, tab[t - base], t, optr.data(), v_old, aptr.data(), &from_add);
-      gd[(size_t)p] = from_add ? a.doc.at((size_t)src) + (int32_t)n_old : o.doc.at((size_t)src);
-      gt[(size_t)p] = from_add ? a.tf.at((size_t)src) : o.tf.at((size_t)src);
-    }
-  }
+  const long windows_global = host_tile_walk(nptr, v_new, [&](long long p, const HostTileWindow& w) {
+    const long t = w.term_of(p);
+    CHECK(nptr[(size_t)t] <= p && p < nptr[(size_t)t + 1], "posting %lld put in term %ld", p, t);
+    bool from_add;
+    const long long src = bm_add_source(p, w.start_of(t), t, o.ptr.data(), v_old, a.ptr.data(), &from_add);
+    gd[(size_t)p] = from_add ? a.doc.at((size_t)src) + (int32_t)n_old : o.doc.at((size_t)src);
+    gt[(size_t)p] = from_add ? a.tf.at((size_t)src) : o.tf.at((size_t)src);
+  });
   CHECK(gd == ed && gt == et, "merged postings differ (v_old %ld n_old %ld v_new %ld n_add %ld hole %ld)", v_old, n_old, v_new, n_add, hole);
   std::printf("merge ok: %ld+%ld docs, %ld->%ld terms, %lld postings, %ld window(s) searched in the table itself\n", n_old,
               n_add, v_old, v_new, nnz, windows_global);
@@ -157,20 +106,20 @@ int main() {
   merge_case(400, 1500, 420, 600, 0, 0);
   merge_case(400, 64, 420, 37, 7, 0);                       // terms without postings
   merge_case(5000, 3, 9000, 2, 2, 0);                       // mostly short lists: many terms per tile
-  merge_case(3, 40, 3 * kBmAddTile, 50, 0, 0);              // new terms, almost all without postings ...
-  merge_case(40, 2000, 60, 2000, 0, 10ll * kBmAddTile);      // exactly a multiple of the tile
-  merge_case(40, 2000, 60, 2000, 0, 10ll * kBmAddTile + 1);  // and one more
+  merge_case(3, 40, 3 * kBmTile, 50, 0, 0);              // new terms, almost all without postings ...
+  merge_case(40, 2000, 60, 2000, 0, 10ll * kBmTile);      // exactly a multiple of the tile
+  merge_case(40, 2000, 60, 2000, 0, 10ll * kBmTile + 1);  // and one more
   {  // a window that does not fit: one posting, then > tile terms without any, then one posting
-    const long v = kBmAddTile + 50;
+    const long v = kBmTile + 50;
     std::vector<long long> optr((size_t)3, 0), aptr((size_t)v + 1, 0);
     optr[1] = optr[2] = 1;  // old: term 0 has one posting, term 1 none
     aptr[(size_t)v] = 1;    // add: the last term has one
     std::vector<long long> nptr((size_t)v + 1);
     for (long t = 0; t <= v; ++t) nptr[(size_t)t] = bm_add_term_ptr(optr.data(), 2, aptr.data(), t);
     long t0, t1;
-    bm_add_tile_terms(nptr.data(), v, 0, 2, &t0, &t1);
-    CHECK(t0 == 0 && t1 == v - 1 && !bm_add_window_fits(t0, t1), "wide window: terms %ld .. %ld", t0, t1);
-    CHECK(bm_add_term_of(nptr.data(), 0, t0, t1, 0) == 0 && bm_add_term_of(nptr.data(), 0, t0, t1, 1) == v - 1, "wide window search");
+    bm_tile_terms(nptr.data(), v, 0, 2, &t0, &t1);
+    CHECK(t0 == 0 && t1 == v - 1 && !bm_tile_window_fits(t0, t1), "wide window: terms %ld .. %ld", t0, t1);
+    CHECK(bm_tile_term_of(nptr.data(), 0, t0, t1, 0) == 0 && bm_tile_term_of(nptr.data(), 0, t0, t1, 1) == v - 1, "wide window search");
     bool fa;
     CHECK(bm_add_source(1, nptr[(size_t)v - 1], v - 1, optr.data(), 2, aptr.data(), &fa) == 0 && fa, "wide window source");
   }

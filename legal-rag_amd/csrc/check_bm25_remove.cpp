@@ -1,16 +1,16 @@
-// Host check of the rules of amdr_bm25_remove (bm25_remove_rule.hpp, compact.hpp), a program of its own (never part of
-// the library):
+// Host check of the rules of amdr_bm25_remove (bm25_remove_rule.hpp, bm25_tile_rule.hpp, compact.hpp), a program of its
+// own (never part of the library):
 //   check_bm25_remove
 // It builds random term-major indexes (Zipfian lists, terms without postings, a total that is an exact multiple of the
 // tile and one more), removes documents and compacts on the CPU the way the kernels do — the document map by
 // bm_rm_doc_new, tile by tile the keep flags and their ranks (compact_tile_scan_host), the tile bases and the new term
-// table by compact_scan_host, every term by bm_rm_term_entry, then tile by tile again the tile's terms by
-// bm_add_tile_terms, a window of the OLD term table copied out exactly as the kernel's LDS window, every surviving
-// posting by bm_add_term_of + bm_rm_dest — and compares the result with a plain per-term filter followed by a stable
-// reorder by new term id.  Every array is a std::vector of exactly the size the call allocates, so with the host
-// sanitizers (tests/test_bm25_remove_rule_host.py) an access outside one is a failure.  Then every refusal of
-// bm_rm_validate is provoked once, on arrays of exact size, and the device-side flag (a term mapped to -1 with a
-// surviving posting) once.
+// table by compact_scan_host, every term by bm_rm_term_entry, then tile by tile again (host_tile_walk,
+// check_bm25_common.hpp) the tile's terms by bm_tile_terms, a window of the OLD term table copied out exactly as the
+// kernel's LDS window, every surviving posting by bm_tile_term_of + bm_rm_dest — and compares the result with a plain
+// per-term filter followed by a stable reorder by new term id.  Every array is a std::vector of exactly the size the call
+// allocates, so with the host sanitizers (tests/test_bm25_remove_rule_host.py) an access outside one is a failure.  Then
+// every refusal of bm_rm_validate is provoked once, on arrays of exact size, and the device-side flag (a term mapped to -1
+// with a surviving posting) once.
 // Build: c++ -std=c++17 check_bm25_remove.cpp (plain host code; no HIP header is needed).
 #include <algorithm>
 #include <cstdint>
@@ -21,62 +21,12 @@
 
 #define AMDR_COMPACT_HOST_ONLY 1  // the host forms alone: this program has no device code
 #include "bm25_remove_rule.hpp"
+#include "check_bm25_common.hpp"
 #include "compact.hpp"
 
 using namespace amdr;
 
 namespace {
-
-uint64_t rng_state = 0x9e3779b97f4a7c15ull;
-uint32_t rnd() {
-  rng_state = rng_state * 6364136223846793005ull + 1442695040888963407ull;
-  return (uint32_t)(rng_state >> 33);
-}
-
-struct Csr {
-  std::vector<long long> ptr;
-  std::vector<int32_t> doc, tf;
-};
-
-// n_terms lists over n_docs documents: term 0 holds every document, list lengths fall off, every `hole`-th term is
-// empty; `empty_run` terms without postings follow term 1; further full lists pad the index to exactly pad_to postings
-Csr make_csr(long n_terms, long n_docs, long hole, long empty_run, long long pad_to) {
-  Csr c;
-  c.ptr.assign(1, 0);
-  for (long t = 0; t < n_terms; ++t) {
-    long df = t == 0 ? n_docs : (long)(n_docs / (t + 1)) + (long)(rnd() % 2);
-    if (df > n_docs) df = n_docs;
-    if (hole && t % hole == hole - 1) df = 0;
-    const long first = df < n_docs ? (long)(rnd() % (uint32_t)(n_docs - df + 1)) : 0;
-    for (long j = 0; j < df; ++j) {
-      c.doc.push_back((int32_t)(first + j));
-      c.tf.push_back((int32_t)(1 + rnd() % 9));
-    }
-    c.ptr.push_back((long long)c.doc.size());
-    if (t == 1)
-      for (long e = 0; e < empty_run; ++e) c.ptr.push_back((long long)c.doc.size());
-  }
-  while ((long long)c.doc.size() < pad_to) {
-    const long long rest = pad_to - (long long)c.doc.size();
-    const long df = rest < n_docs ? (long)rest : n_docs;
-    for (long j = 0; j < df; ++j) {
-      c.doc.push_back((int32_t)j);
-      c.tf.push_back(1);
-    }
-    c.ptr.push_back((long long)c.doc.size());
-  }
-  return c;
-}
-
-int failures = 0;
-#define CHECK(cond, ...)                 \
-  do {                                   \
-    if (!(cond)) {                       \
-      ++failures;                        \
-      std::printf("FAIL: " __VA_ARGS__); \
-      std::printf("\n");                 \
-    }                                    \
-  } while (0)
 
 // What the device computes up to the host's look at the total and the flag, on arrays of the call's sizes.
 struct Counted {
@@ -89,14 +39,14 @@ struct Counted {
 Counted count_passes(const Csr& o, long v_old, long n_old, const std::vector<long long>& rm, const int* map, long v_new) {
   Counted c;
   const long long nnz = o.ptr.back();
-  const long tiles = (long)((nnz + kBmAddTile - 1) / kBmAddTile);
+  const long tiles = (long)((nnz + kBmTile - 1) / kBmTile);
   c.doc_new.resize((size_t)n_old);
   for (long d = 0; d < n_old; ++d) c.doc_new[(size_t)d] = bm_rm_doc_new(rm.data(), (long)rm.size(), d);
   c.tile_rank.resize((size_t)nnz);
   std::vector<long long> tile_cnt((size_t)tiles);
   for (long tile = 0; tile < tiles; ++tile) {
-    const long long p0 = (long long)tile * kBmAddTile;
-    const int n = (int)std::min<long long>(kBmAddTile, nnz - p0);
+    const long long p0 = (long long)tile * kBmTile;
+    const int n = (int)std::min<long long>(kBmTile, nnz - p0);
     std::vector<unsigned char> keep((size_t)n);
     for (int i = 0; i < n; ++i) keep[(size_t)i] = c.doc_new.at((size_t)o.doc[(size_t)(p0 + i)]) >= 0;
     tile_cnt[(size_t)tile] = compact_tile_scan_host(keep.data(), n, c.tile_rank.data() + p0);
@@ -190,30 +140,18 @@ void compact_case(const char* what, long v, long n_old, long hole, long empty_ru
   CHECK(nnz_new == (long long)ed.size(), "%s: nnz_new %lld, expected %zu", what, nnz_new, ed.size());
   if (nnz_new_want > 0) CHECK(nnz_new == nnz_new_want, "%s: case did not leave %lld postings (%lld)", what, nnz_new_want, nnz_new);
   std::vector<int32_t> gd((size_t)nnz_new, -1), gt((size_t)nnz_new, -1);
-  long windows_global = 0, zero_tiles = 0;
-  for (long long p0 = 0; p0 < nnz; p0 += kBmAddTile) {
-    const long long p1 = std::min<long long>(p0 + kBmAddTile, nnz);
-    zero_tiles += c.tile_base[(size_t)(p0 / kBmAddTile) + 1] == c.tile_base[(size_t)(p0 / kBmAddTile)];
-    long t0, t1;
-    bm_add_tile_terms(o.ptr.data(), v_old, p0, p1, &t0, &t1);
-    const bool fits = bm_add_window_fits(t0, t1);
-    std::vector<long long> win;  // exactly the entries the kernel copies to LDS
-    if (fits) win.assign(o.ptr.begin() + t0, o.ptr.begin() + t1 + 2);
-    CHECK(!fits || win.size() <= (size_t)kBmAddTile + 2, "window of %zu entries", win.size());
-    windows_global += fits ? 0 : 1;
-    const long long* tab = fits ? win.data() : o.ptr.data();
-    const long base = fits ? t0 : 0;
-    for (long long p = p0; p < p1; ++p) {
-      const int doc = c.doc_new.at((size_t)o.doc[(size_t)p]);
-      if (doc < 0) continue;
-      const long t = bm_add_term_of(tab, base, t0, t1, p);
-      CHECK(o.ptr[(size_t)t] <= p && p < o.ptr[(size_t)t + 1], "posting %lld put in term %ld", p, t);
-      const long long dst = bm_rm_dest(p, t, nnz, c.tile_base.data(), c.tile_rank.data(), c.rank_at.data(), c.new_ptr.data(), map_arg);
-      CHECK(dst >= 0 && dst < nnz_new && gd.at((size_t)dst) == -1, "posting %lld goes to %lld", p, dst);
-      gd.at((size_t)dst) = doc;
-      gt.at((size_t)dst) = o.tf[(size_t)p];
-    }
-  }
+  long zero_tiles = 0;
+  for (size_t tile = 0; tile + 1 < c.tile_base.size(); ++tile) zero_tiles += c.tile_base[tile + 1] == c.tile_base[tile];
+  const long windows_global = host_tile_walk(o.ptr, v_old, [&](long long p, const HostTileWindow& w) {
+    const int doc = c.doc_new.at((size_t)o.doc[(size_t)p]);
+    if (doc < 0) return;
+    const long t = w.term_of(p);
+    CHECK(o.ptr[(size_t)t] <= p && p < o.ptr[(size_t)t + 1], "posting %lld put in term %ld", p, t);
+    const long long dst = bm_rm_dest(p, t, nnz, c.tile_base.data(), c.tile_rank.data(), c.rank_at.data(), c.new_ptr.data(), map_arg);
+    CHECK(dst >= 0 && dst < nnz_new && gd.at((size_t)dst) == -1, "posting %lld goes to %lld", p, dst);
+    gd.at((size_t)dst) = doc;
+    gt.at((size_t)dst) = o.tf[(size_t)p];
+  });
   CHECK(gd == ed && gt == et, "%s: compacted postings differ", what);
   bool monotone = true;
   long last = -1;
@@ -271,7 +209,7 @@ void validate_cases() {
 }  // namespace
 
 int main() {
-  const long long T = kBmAddTile;
+  const long long T = kBmTile;
   compact_case("smallest index", 1, 2, 0, 0, 0, 0, 1, 1, 2);
   compact_case("every other document, null map", 400, 1500, 0, 0, 0, 0, 2, 0, 0);
   compact_case("every third kept, terms dropped and reversed", 400, 1500, 0, 0, 0, 0, 3, 0, 1);
@@ -282,8 +220,8 @@ int main() {
   compact_case("3 tiles exactly", 10, 2000, 0, 0, 3 * T, 0, 2, 0, 1);
   compact_case("3 tiles and one more", 10, 2000, 0, 0, 3 * T + 1, 0, 2, 0, 0);
   compact_case("2 tiles survive exactly", 1, T, 0, 0, 4 * T, 2 * T, 1, 1, 1);
-  compact_case("a wide run of empty terms", 12, 300, 0, kBmAddTile + 50, 0, 0, 2, 0, 1);
-  compact_case("a wide run of empty terms, null map", 12, 300, 0, kBmAddTile + 50, 0, 0, 4, 10, 0);
+  compact_case("a wide run of empty terms", 12, 300, 0, kBmTile + 50, 0, 0, 2, 0, 1);
+  compact_case("a wide run of empty terms, null map", 12, 300, 0, kBmTile + 50, 0, 0, 4, 10, 0);
   validate_cases();
   if (failures) {
     std::printf("%d failure(s)\n", failures);

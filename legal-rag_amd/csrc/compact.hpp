@@ -1,5 +1,5 @@
-// Stream compaction pieces shared by the removals (amdr_bm25_remove, bm25.hip; the dense and token-store removals are to
-// reuse them): where a kept element goes is its rank among the kept ones, and a rank is
+// Stream compaction pieces shared by the removals (amdr_bm25_remove, bm25_update.hip; the dense and token-store removals are
+// to reuse them): where a kept element goes is its rank among the kept ones, and a rank is
 //   the exclusive scan of the per-tile counts (compact_scan_i64_kernel)  +  the exclusive scan of the keep flags inside
 //   the element's tile (compact_tile_scan, in LDS).
 // No atomics: every position is a sum of counts, so the result is deterministic.  The host forms (compact_scan_host,
@@ -115,8 +115,9 @@ __device__ inline int compact_tile_scan(unsigned keep_bits, int* lds, int* rank)
 // out[0 .. n] = exclusive prefix sums of in[0 .. n-1], out[n] the total: ONE block of kCompactScanThreads threads walks the
 // array in rounds of kCompactScanThreads * kCompactScanPerThread values and carries the running sum.  Meant for the short
 // arrays of a compaction (one value per tile, one per term), not for the elements themselves.  in and out may not overlap.
-__global__ __launch_bounds__(kCompactScanThreads) void compact_scan_i64_kernel(const long long* __restrict__ in, long n,
-                                                                               long long* __restrict__ out) {
+// Internal linkage: every translation unit that includes this header gets a kernel of its own, and two of them link.
+static __global__ __launch_bounds__(kCompactScanThreads) void compact_scan_i64_kernel(const long long* __restrict__ in, long n,
+                                                                                      long long* __restrict__ out) {
   __shared__ long long wsum[kCompactScanThreads / 64 + 1];
   constexpr long kRound = (long)kCompactScanThreads * kCompactScanPerThread;
   long long carry = 0;

@@ -1,43 +1,17 @@
 """amdr_bm25_add: after any sequence of adds a BM25 handle is what amdr_bm25_create makes of the concatenated index — the
-six resident arrays byte for byte, hence the same ids and score BITS from every entry point (csrc/bm25.hip).  `grown` is
-created from the first part and added to, `fresh` from the concatenation.  The add's arrays come from the re-fit's own
-to_csr() cut by shard_csr, not from the code that add_documents uses; one test goes through add_documents itself."""
+six resident arrays byte for byte, hence the same ids and score BITS from every entry point (csrc/bm25_update.hip).
+`grown` is created from the first part and added to, `fresh` from the concatenation.  The add's arrays come from the
+re-fit's own to_csr() cut by shard_csr, not from the code that add_documents uses; one test goes through add_documents
+itself."""
 import ctypes as C
 
 import numpy as np
 import pytest
-import torch
+
+from bm25_update_cases import (LENS, assert_same_results, assert_same_serving_step, fit, index_of, make_docs, nat,  # noqa: F401
+                               queries_for, same_arrays, same_pair)
 
 pytestmark = pytest.mark.gpu
-
-DEV = torch.device("cuda", 0)
-LENS = (1, 2, 5, 17, 40, 90)
-SEARCHES = ((1, 1), (7, 10), (9, 17), (24, 80))  # (nq, k)
-N_ZIPF = 400
-
-
-@pytest.fixture(scope="module")
-def nat():
-    from legal_rag_amd import _native
-    _native.load()
-    assert _native.device_count() >= 1, "no GPU visible"
-    assert _native.device_name(0).startswith("gfx950"), _native.device_name(0)
-    return _native
-
-
-def make_docs(rng, n, lead):
-    """n token lists: "all" in every one, Zipfian terms z0 .. z399 with tf 1-9, lengths from LENS; lead(i) -> the tokens
-    that follow "all" in document i (terms of one side of the seam only)."""
-    docs = []
-    for i in range(n):
-        head = ["all"] + list(lead(i))
-        want = max(int(rng.choice(LENS)), len(head))
-        doc = list(head)
-        while len(doc) < want:
-            z = min(int(rng.zipf(1.3)) - 1, N_ZIPF - 1)
-            doc.extend([f"z{z}"] * int(rng.integers(1, 10)))
-        docs.append(doc[:want])
-    return docs
 
 
 def old_lead(i):
@@ -51,16 +25,6 @@ def add_lead(i):
 def parts_of(seed, n_base, adds):
     rng = np.random.default_rng(seed)
     return [make_docs(rng, n_base, old_lead)] + [make_docs(rng, n, add_lead) for n in adds]
-
-
-def fit(docs):
-    from legal_rag_amd.bm25_model import BM25Okapi
-    return BM25Okapi(docs)
-
-
-def index_of(nat, model):
-    term_ptr, post_doc, post_tf, idf, doc_len = model.to_csr()
-    return nat.BM25Index(term_ptr, post_doc, post_tf, idf, doc_len, float(model.avgdl), float(model.k1), float(model.b))
 
 
 def grow(nat, parts):
@@ -80,88 +44,11 @@ def grow(nat, parts):
     return g, index_of(nat, model), model
 
 
-def same_arrays(a, b):
-    assert len(a) == len(b)
-    for j, (x, y) in enumerate(zip(a, b)):
-        assert x.dtype == y.dtype and x.shape == y.shape and x.tobytes() == y.tobytes(), f"array {j} differs"
-
-
 def assert_same_state(g, f, adds):
     gi, fi = g.info(), f.info()
     assert gi[:3] == fi[:3] and gi[4] == fi[4] and gi[5] == fi[5] == 0 and gi[3] == adds and fi[3] == 0, (gi, fi)
     assert (g.n_docs, g.n_terms) == (f.n_docs, f.n_terms) == gi[:2]
     same_arrays(g.read(), f.read())
-
-
-def queries_for(rng, V, n=24):
-    """Term-id queries: unknown ids, repeats, the term of every document (id 0) and the newest terms among them."""
-    qs = [[int(t) for t in rng.integers(-1, V, size=int(rng.integers(0, 13)))] for _ in range(n)]
-    qs[0] = [0, V - 1, 0, -1, V - 2]
-    qs[1] = []
-    qs[2] = [V - 1]
-    return qs
-
-
-def same_pair(a, b, what):
-    (sa, ia), (sb, ib) = a, b
-    assert np.array_equal(ia, ib), what
-    assert sa.tobytes() == sb.tobytes(), what
-
-
-def assert_same_results(nat, g, f, qs, seam):
-    n = g.n_docs
-    for nq, k in SEARCHES:
-        same_pair(g.search(qs[:nq], k), f.search(qs[:nq], k), ("search", nq, k))
-    assert g.get_scores(qs).tobytes() == f.get_scores(qs).tobytes()
-    # "_device" search inside a reserve: no workspace grows
-    qt_h, qp_h = nat.BM25Index.pack_queries(qs)
-    qt, qp = torch.from_numpy(qt_h).to(DEV), torch.from_numpy(qp_h).to(DEV)
-    out = []
-    for h in (g, f):
-        h.reserve(24, 80, int(qt_h.size))
-        for nq, k in SEARCHES:
-            s = torch.empty((nq, k), dtype=torch.float64, device=DEV)
-            i = torch.empty((nq, k), dtype=torch.int64, device=DEV)
-            g0 = nat.workspace_growths()
-            h.search_device(qt.data_ptr(), qp.data_ptr(), nq, k, s.data_ptr(), i.data_ptr(),
-                            torch.cuda.current_stream().cuda_stream)
-            assert nat.workspace_growths() == g0, ("search_device grew a workspace", nq, k)
-            torch.cuda.synchronize()
-            out.append((s.cpu().numpy(), i.cpu().numpy()))
-    half = len(out) // 2
-    for j in range(half):
-        same_pair(out[j], out[half + j], ("search_device", SEARCHES[j]))
-        same_pair(out[j], g.search(qs[:SEARCHES[j][0]], SEARCHES[j][1]), ("search_device against search", SEARCHES[j]))
-    # scoped search: a scope with documents of both sides of the seam
-    rows = np.asarray(sorted({0, max(seam - 2, 0), seam - 1, seam, min(seam + 1, n - 1), n - 1}), dtype=np.int64)
-    ws = nat.ScopeWorkspace()
-    table = (np.asarray([0, rows.size], dtype=np.int64), rows, [0] * 7)
-    a, b = (ws.bm25_search(h, qs[:7], *table, 4) for h in (g, f))
-    ws.close()
-    same_pair(a, b, "scoped search")
-    assert set(a[1][0].tolist()) - {-1} <= set(rows.tolist())
-
-
-def assert_same_serving_step(nat, g, f, qs, d=64):
-    """HybridEngine.search_batch of 1-4 queries (amdr_hybrid_small_device on <= 2 048 documents: ONE launch)."""
-    from test_hybrid_small_gpu import _run, _same
-    from legal_rag_amd.retrieval.engine import HybridEngine
-    rng = np.random.default_rng(g.n_docs)
-    X = rng.standard_normal((g.n_docs, d)).astype(np.float32)
-    X /= np.linalg.norm(X, axis=1, keepdims=True)
-    eg, ef = (HybridEngine(nat.DenseIndex(X), h, None) for h in (g, f))
-    params = nat.make_fuse_params(method="weighted_sum", min_final_score=0.0)
-    for nq, k in ((1, 10), (3, 5)):
-        if k > g.n_docs:
-            k = g.n_docs
-        q = rng.standard_normal((nq, d)).astype(np.float32)
-        qt_h, qp_h = nat.BM25Index.pack_queries(qs[:nq])
-        Q = torch.from_numpy(q).to(DEV)
-        qt = torch.from_numpy(np.concatenate([qt_h, np.zeros(1, np.int32)])).to(DEV)
-        qp = torch.from_numpy(qp_h).to(DEV)
-        a, b = _run(eg, params, k, Q, qt, qp, True), _run(ef, params, k, Q, qt, qp, True)
-        _same(a, b, ("serving step", nq, k))
-        same_pair((a["bm25_scores"], a["bm25_ids"]), g.search(qs[:nq], k), ("serving step against search", nq, k))
 
 
 # base documents, adds: the smallest index; one arg-max slab of 2 048 becomes two; two adds in a row over that edge; the
@@ -180,7 +67,7 @@ def test_grown_equals_fresh(nat, n_base, adds):
     assert tp[vocab["single"] + 1] - tp[vocab["single"]] == len(adds)  # one posting per add
     assert g.read()[1][tp[vocab["oldonly"]]:tp[vocab["oldonly"] + 1]].max() < n_base
     qs = queries_for(np.random.default_rng(1), len(vocab))
-    assert_same_results(nat, g, f, qs, seam=n_base)
+    assert_same_results(nat, g, f, qs, n_base)  # the seam
     assert_same_serving_step(nat, g, f, qs)
     g.close()
     f.close()
@@ -299,6 +186,7 @@ def test_bad_arguments_leave_the_handle_unchanged(nat):
     old = random_lists(rng, 50, [50, 20, 3])
     g = nat.BM25Index(old[0], old[1], old[2], np.asarray([0.3, 1.0, 2.5]), np.full(50, 7, np.int32), 7.0)
     before = g.read()
+    assert g.add_kernel_ms() == -1.0  # no add yet
     ptr = np.asarray([0, 2, 2, 3, 4], np.int64)
     doc = np.asarray([0, 1, 1, 0], np.int32)
     tf = np.asarray([1, 2, 3, 1], np.int32)
@@ -334,11 +222,11 @@ def test_bad_arguments_leave_the_handle_unchanged(nat):
     # n_add == 0 reads nothing
     assert call(ptr=None, doc=None, tf=None, idf=None, dl=None, n_add=0) == 0
     same_arrays(g.read(), before)
-    assert g.info()[:4] == (50, 3, 73, 0)
+    assert g.info()[:4] == (50, 3, 73, 0) and g.add_kernel_ms() == -1.0
     s0 = g.search([[0, 1, 2]], 5)
     # and the good add goes through afterwards: the handle was left searchable
     assert call() == 0
-    assert g.info()[:4] == (52, 4, 77, 1)
+    assert g.info()[:4] == (52, 4, 77, 1) and g.add_kernel_ms() > 0
     whole = concat_csr(old, (ptr, doc, tf), 50)
     f = nat.BM25Index(whole[0], whole[1], whole[2], idf, np.concatenate([np.full(50, 7, np.int32), dl]), 6.5)
     same_arrays(g.read(), f.read())

@@ -1,59 +1,22 @@
 """amdr_bm25_remove: after any sequence of adds and removes a BM25 handle is what amdr_bm25_create makes of the surviving
 documents' index — the six resident arrays byte for byte, hence the same ids and score BITS from every entry point
-(csrc/bm25.hip).  `shrunk` is created from the whole corpus and removed from, `fresh` from the survivors' re-fit.  The
-remove's arguments come from the re-fit itself (its idf vector, avgdl and the map old vocabulary -> its vocabulary), not
-from the code that remove_documents uses; one test goes through remove_documents itself."""
+(csrc/bm25_update.hip).  `shrunk` is created from the whole corpus and removed from, `fresh` from the survivors' re-fit.
+The remove's arguments come from the re-fit itself (its idf vector, avgdl and the map old vocabulary -> its vocabulary),
+not from the code that remove_documents uses; one test goes through remove_documents itself."""
 import ctypes as C
 
 import numpy as np
 import pytest
-import torch
+
+from bm25_update_cases import (LENS, assert_same_results, assert_same_serving_step, fit, index_of, make_docs, nat,  # noqa: F401
+                               queries_for, same_arrays, same_pair)
 
 pytestmark = pytest.mark.gpu
-
-DEV = torch.device("cuda", 0)
-LENS = (1, 2, 5, 17, 40, 90)
-SEARCHES = ((1, 1), (7, 10), (9, 17), (24, 80))  # (nq, k)
-N_ZIPF = 400
-
-
-@pytest.fixture(scope="module")
-def nat():
-    from legal_rag_amd import _native
-    _native.load()
-    assert _native.device_count() >= 1, "no GPU visible"
-    assert _native.device_name(0).startswith("gfx950"), _native.device_name(0)
-    return _native
-
-
-def make_docs(rng, n, lead=lambda i: ()):
-    """n token lists: "all" in every one (the first term: its list is postings 0 .. n-1), Zipfian terms z0 .. z399 with
-    tf 1-9, lengths from LENS; lead(i) -> the tokens that follow "all" in document i."""
-    docs = []
-    for i in range(n):
-        head = ["all"] + list(lead(i))
-        want = max(int(rng.choice(LENS)), len(head))
-        doc = list(head)
-        while len(doc) < want:
-            z = min(int(rng.zipf(1.3)) - 1, N_ZIPF - 1)
-            doc.extend([f"z{z}"] * int(rng.integers(1, 10)))
-        docs.append(doc[:want])
-    return docs
 
 
 def only_lead(i):
     """Terms that live in one document each (they vanish with it), and one in every 40th."""
     return ([f"only{i}"] if i % 7 == 0 else []) + (["forty"] if i % 40 == 0 else [])
-
-
-def fit(docs):
-    from legal_rag_amd.bm25_model import BM25Okapi
-    return BM25Okapi(docs)
-
-
-def index_of(nat, model):
-    term_ptr, post_doc, post_tf, idf, doc_len = model.to_csr()
-    return nat.BM25Index(term_ptr, post_doc, post_tf, idf, doc_len, float(model.avgdl), float(model.k1), float(model.b))
 
 
 def survivors(docs, ids):
@@ -86,12 +49,6 @@ def shrink(nat, docs, ids):
     return g, index_of(nat, model), model, tm
 
 
-def same_arrays(a, b):
-    assert len(a) == len(b)
-    for j, (x, y) in enumerate(zip(a, b)):
-        assert x.dtype == y.dtype and x.shape == y.shape and x.tobytes() == y.tobytes(), f"array {j} differs"
-
-
 def assert_same_state(g, f, removes, adds=0):
     gi, fi = g.info(), f.info()
     assert gi[:3] == fi[:3] and gi[4] == fi[4] and gi[5] == removes and fi[5] == 0 and gi[3] == adds and fi[3] == 0, (gi, fi)
@@ -100,79 +57,6 @@ def assert_same_state(g, f, removes, adds=0):
     tp, pd = g.read()[:2]
     for t in range(len(tp) - 1):  # each list ascending
         assert np.all(np.diff(pd[tp[t]:tp[t + 1]]) > 0), t
-
-
-def queries_for(rng, V, n=24):
-    """Term-id queries: unknown ids, repeats, the term of every document (id 0) and the last terms among them."""
-    qs = [[int(t) for t in rng.integers(-1, V, size=int(rng.integers(0, 13)))] for _ in range(n)]
-    qs[0] = [0, V - 1, 0, -1, max(V - 2, 0)]
-    qs[1] = []
-    qs[2] = [V - 1]
-    return qs
-
-
-def same_pair(a, b, what):
-    (sa, ia), (sb, ib) = a, b
-    assert np.array_equal(ia, ib), what
-    assert sa.tobytes() == sb.tobytes(), what
-
-
-def assert_same_results(nat, g, f, qs, gap):
-    """gap: the new id of the first survivor behind a removed document (the scope reaches across the closed gap)."""
-    n = g.n_docs
-    for nq, k in SEARCHES:
-        same_pair(g.search(qs[:nq], k), f.search(qs[:nq], k), ("search", nq, k))
-    assert g.get_scores(qs).tobytes() == f.get_scores(qs).tobytes()
-    # "_device" search inside a reserve: no workspace grows
-    qt_h, qp_h = nat.BM25Index.pack_queries(qs)
-    qt, qp = torch.from_numpy(qt_h).to(DEV), torch.from_numpy(qp_h).to(DEV)
-    out = []
-    for h in (g, f):
-        h.reserve(24, 80, int(qt_h.size))
-        for nq, k in SEARCHES:
-            s = torch.empty((nq, k), dtype=torch.float64, device=DEV)
-            i = torch.empty((nq, k), dtype=torch.int64, device=DEV)
-            g0 = nat.workspace_growths()
-            h.search_device(qt.data_ptr(), qp.data_ptr(), nq, k, s.data_ptr(), i.data_ptr(),
-                            torch.cuda.current_stream().cuda_stream)
-            assert nat.workspace_growths() == g0, ("search_device grew a workspace", nq, k)
-            torch.cuda.synchronize()
-            out.append((s.cpu().numpy(), i.cpu().numpy()))
-    half = len(out) // 2
-    for j in range(half):
-        same_pair(out[j], out[half + j], ("search_device", SEARCHES[j]))
-        same_pair(out[j], g.search(qs[:SEARCHES[j][0]], SEARCHES[j][1]), ("search_device against search", SEARCHES[j]))
-    # scoped search: a scope with documents of both sides of a closed gap
-    gap = min(max(gap, 0), n - 1)
-    rows = np.asarray(sorted({0, max(gap - 2, 0), max(gap - 1, 0), gap, min(gap + 1, n - 1), n - 1}), dtype=np.int64)
-    ws = nat.ScopeWorkspace()
-    table = (np.asarray([0, rows.size], dtype=np.int64), rows, [0] * 7)
-    a, b = (ws.bm25_search(h, qs[:7], *table, 4) for h in (g, f))
-    ws.close()
-    same_pair(a, b, "scoped search")
-    assert set(a[1][0].tolist()) - {-1} <= set(rows.tolist())
-
-
-def assert_same_serving_step(nat, g, f, qs, d=64):
-    """HybridEngine.search_batch of 1-4 queries (amdr_hybrid_small_device on <= 2 048 documents: ONE launch)."""
-    from test_hybrid_small_gpu import _run, _same
-    from legal_rag_amd.retrieval.engine import HybridEngine
-    rng = np.random.default_rng(g.n_docs)
-    X = rng.standard_normal((g.n_docs, d)).astype(np.float32)
-    X /= np.linalg.norm(X, axis=1, keepdims=True)
-    eg, ef = (HybridEngine(nat.DenseIndex(X), h, None) for h in (g, f))
-    params = nat.make_fuse_params(method="weighted_sum", min_final_score=0.0)
-    for nq, k in ((1, 10), (3, 5)):
-        if k > g.n_docs:
-            k = g.n_docs
-        q = rng.standard_normal((nq, d)).astype(np.float32)
-        qt_h, qp_h = nat.BM25Index.pack_queries(qs[:nq])
-        Q = torch.from_numpy(q).to(DEV)
-        qt = torch.from_numpy(np.concatenate([qt_h, np.zeros(1, np.int32)])).to(DEV)
-        qp = torch.from_numpy(qp_h).to(DEV)
-        a, b = _run(eg, params, k, Q, qt, qp, True), _run(ef, params, k, Q, qt, qp, True)
-        _same(a, b, ("serving step", nq, k))
-        same_pair((a["bm25_scores"], a["bm25_ids"]), g.search(qs[:nq], k), ("serving step against search", nq, k))
 
 
 def first_gap(ids):

@@ -4,28 +4,16 @@ scans) through csrc/check_bm25_remove.cpp: a program of its own, compiled for th
 undefined-behaviour sanitizers (host flags only: no device code is built) and run as a child process (no GPU, nothing
 loaded into Python).  It compacts generated indexes tile by tile as the kernels do, on arrays of exactly the promised
 sizes, and compares with a plain per-term filter plus a stable reorder by new term id."""
-import os
-import shutil
 import subprocess
-from pathlib import Path
 
 import pytest
 
-ROOT = Path(__file__).resolve().parent.parent
-CSRC = ROOT / "legal-rag_amd" / "csrc"
+from bm25_update_cases import build_check_program
 
 
 @pytest.fixture(scope="module")
 def program(tmp_path_factory):
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    if not (Path(hipcc).exists() or shutil.which(hipcc)):
-        pytest.fail(f"{hipcc} not found: the host check is compiled with the compiler that builds the library")
-    exe = tmp_path_factory.mktemp("bm25_remove_rule") / "check_bm25_remove"
-    subprocess.run([hipcc, "-x", "hip", "--offload-host-only", "-std=c++17", "-O1", "-g", "-ffp-contract=off",
-                    "-Xarch_host", "-fsanitize=address", "-Xarch_host", "-fsanitize=undefined",
-                    "-Xarch_host", "-fno-sanitize-recover=all", str(CSRC / "check_bm25_remove.cpp"), "-o", str(exe)],
-                   check=True, cwd=str(CSRC))
-    return exe
+    return build_check_program(tmp_path_factory, "check_bm25_remove")
 
 
 def test_compaction_rule_and_validation(program):
