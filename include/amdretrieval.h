@@ -666,6 +666,12 @@ int amdr_merge_topk_f64_device(const double* scores, const int64_t* ids, int32_t
  * amdr_shard_merge_device: gathered [world, nq, row] (the all-gather's output, read in place) -> per channel the global
  *                          top-k_c: out scores [nq, k_c] (fp32 / fp64 as flagged), out ids [nq, k_c]; score descending,
  *                          ties -> lower global id, -1 / -FLT_MAX (-DBL_MAX) padding.  Identical on every rank.
+ * Ids and values: ANY negative id is "no entry" — the pack writes it to the wire unchanged (only ids >= 0 take the
+ * offset), the merge skips it whatever its score word holds and pads its own output with -1 alone.  The id decides, never
+ * the score: a valid hit may score -FLT_MAX / -DBL_MAX or -inf.  -0.0 ties with +0.0 (the lower id first) and comes back
+ * as +0.0; a NaN ranks behind -inf and ahead of padding, and comes back as the NaN 0xfffffffe (fp32 channel) /
+ * 0xfffffffffffffffe (fp64 channel) whatever payload went in — the bits amdr_merge_topk_*_device returns too.  Every
+ * other hit returns the bits that went in.  id_offset >= 0; global ids use all 63 bits.
  * Both only enqueue on `stream` (graph-capturable); up to 4 channels, k_c <= AMDR_MAX_K. */
 typedef struct amdr_shard_chan {
   void* scores;   /* pack: const input lists; merge: output */

@@ -91,6 +91,10 @@ __device__ __forceinline__ void shard_bitonic_merge64_desc(u64& key, long long& 
   for (int stride = 32; stride > 0; stride >>= 1) cx64(key, idv, stride, (lane & stride) == 0);
 }
 
+// The score of a ranked key in an fp32 channel.  Key 1 (any NaN) decodes to unord32's NaN, the one merge_parts_kernel
+// returns for an fp32 list: narrowing unord64's NaN gives another payload (0xffffffff, not 0xfffffffe).
+__device__ __forceinline__ float shard_score32(u64 key) { return key == 1ull ? unord32(1u) : (float)unord64(key); }
+
 template <bool STAGED>
 __global__ __launch_bounds__(256) void shard_merge_kernel(ShardLayout L, int world, int nq,
                                                           const long long* __restrict__ g, int cap) {
@@ -142,7 +146,7 @@ __global__ __launch_bounds__(256) void shard_merge_kernel(ShardLayout L, int wor
       if (f64)
         reinterpret_cast<double*>(osp)[(size_t)q * k + j] = v ? unord64(c.key) : -DBL_MAX;
       else
-        reinterpret_cast<float*>(osp)[(size_t)q * k + j] = v ? (float)unord64(c.key) : -FLT_MAX;
+        reinterpret_cast<float*>(osp)[(size_t)q * k + j] = v ? shard_score32(c.key) : -FLT_MAX;
       oip[(size_t)q * k + j] = v ? c.idv : -1ll;
     }
     return;
@@ -152,7 +156,7 @@ __global__ __launch_bounds__(256) void shard_merge_kernel(ShardLayout L, int wor
     if (f64)
       reinterpret_cast<double*>(osp)[(size_t)q * k + lane] = v ? unord64(bkey) : -DBL_MAX;
     else
-      reinterpret_cast<float*>(osp)[(size_t)q * k + lane] = v ? (float)unord64(bkey) : -FLT_MAX;
+      reinterpret_cast<float*>(osp)[(size_t)q * k + lane] = v ? shard_score32(bkey) : -FLT_MAX;
     oip[(size_t)q * k + lane] = v ? bid : -1ll;
   }
 }
