@@ -75,6 +75,34 @@ int amdr_dense_create(const float* X_host, int64_t n, int32_t d, int32_t device,
  * any stream and was enqueued before the call is complete; the matrix must not change while the handle lives. */
 int amdr_dense_create_from_device(const float* X_dev, int64_t n, int32_t d, int32_t device, amdr_dense_t** out);
 int amdr_dense_add(amdr_dense_t* h, const float* X_host, int64_t n_add);
+/* Remove n_remove rows (the reference has no removal: a corpus that shrinks takes `index.add` over everything again,
+ * legalrag/retrieval/builders/faiss_builder.py:91, and then the reload of legalrag/retrieval/vector_store.py, which this
+ * call replaces).  remove_ids[n_remove]: old row ids, strictly ascending, in [0, n); the surviving rows are renumbered
+ * 0 .. n-n_remove-1 in their old order (ids close up: the faiss remove_ids convention of flat indexes, as
+ * amdr_bm25_remove).  Removing every row is allowed and leaves the empty index (create accepts n = 0).
+ * Afterwards the handle is what amdr_dense_create makes of the surviving rows: the same matrix bytes (amdr_dense_read_rows)
+ * and the statistics of the fp16 first passes taken from zero over them — under add the largest component and row norm
+ * only grow, here they can fall — hence the same ids and score bits from every entry point.  The short-corpus fp16 image
+ * is dropped (made again on demand), the adaptation of the large scan's fp16 pass and its counters
+ * (amdr_dense_hi_counters) start over, and a resident fp16 image (amdr_dense_image_build) is made again from the
+ * compacted matrix — its 32-row tiles hold other rows now — or dropped when the index is empty or its statistics are no
+ * longer finite.  The work is one ordered compaction of the matrix at HBM speed into a NEW buffer (csrc/rows_compact.hip:
+ * every surviving byte read once and written once; no atomics, deterministic) and the statistics pass; host work is
+ * proportional to n_remove.  Capacity afterwards equals the survivors; a later add grows as it does today.
+ * AMDR_EINVAL: null handle, a handle from amdr_dense_create_from_device, n_remove < 0, null remove_ids, an id outside
+ * [0, n), ids not strictly ascending.  n_remove == 0 is a no-op that reads nothing.  A failed remove (AMDR_EINVAL,
+ * AMDR_ENOMEM, AMDR_EHIP) leaves the handle as it was and searchable.  The price of that: the old and the new matrix
+ * (and 8 B per removed id) are resident for the length of the call, so it can return AMDR_ENOMEM on a device where the
+ * matrix itself fits.  Runs inside the handle's mutex.  It is a mutation in the sense of the rule at the top of this
+ * file: "_device" work of the handle still in flight is the caller's to finish first (the matrix it reads is freed),
+ * captured graphs hold the old buffer and sizes and must be reserved and captured again, workspaces are never shrunk.
+ * Row ids held by others — the graph tables node_row / row_node / row_norm of amdr_graph_create, scope tables, row2uid
+ * maps of the fusion calls — name the old rows and are the caller's to rebuild. */
+int amdr_dense_remove(amdr_dense_t* h, const int64_t* remove_ids, int64_t n_remove);
+/* Device time of the compaction kernel of the last successful amdr_dense_remove, in ms between two events on the
+ * handle's stream (scripts/bench_store_remove.py sets it against the kernel's algorithmic bytes); -1 before the first
+ * remove. */
+int amdr_dense_remove_kernel_ms(amdr_dense_t* h, double* ms);
 int amdr_dense_ntotal(const amdr_dense_t* h, int64_t* n);
 int amdr_dense_dim(const amdr_dense_t* h, int32_t* d);
 int amdr_dense_reserve(amdr_dense_t* h, int32_t nq_max, int32_t k_max);
@@ -347,6 +375,34 @@ int amdr_maxsim_create(const float* D_host, const int64_t* doc_ptr, int64_t n_do
  * grows its workspace if it has to (amdr_workspace_growths shows it); a captured graph holds the old buffers and sizes
  * and must be re-reserved (amdr_maxsim_reserve) and captured again. */
 int amdr_maxsim_add(amdr_maxsim_t* h, const float* D_host, const int64_t* doc_ptr_add, int64_t n_add);
+/* Remove n_remove documents (the reference has no removal: a corpus that shrinks takes the indexer over everything
+ * again, legalrag/retrieval/builders/colbert_builder.py:131-132, and then the reload of
+ * legalrag/retrieval/colbert_retriever.py, which this call replaces).  remove_ids[n_remove]: old pids, strictly
+ * ascending, in [0, n_docs); n_remove < n_docs (a store keeps a document, as create demands).  The surviving documents
+ * are renumbered 0 .. n_docs-n_remove-1 in their old order and their token rows close up.
+ * Afterwards the handle is what amdr_maxsim_create makes of the surviving store: D and doc_ptr are the same bytes
+ * (amdr_maxsim_read), and create's own sequence runs on the new D — largest |component|, power-of-two scale, both images
+ * converted again from D (fewer bytes per token than copying them, and create's bytes by construction), d_norm_max —
+ * hence the same ids and score bits from every entry point.  Unlike under add the scale and d_norm_max can FALL; a store
+ * that had no images gets them when its last NaN / infinity is removed; info[5] goes up by one per remove of a store
+ * that is finite afterwards.  The work: two small kernels rebuild doc_ptr, one ordered compaction moves the 512-byte
+ * token rows at HBM speed into a NEW buffer (csrc/rows_compact.hip; no atomics, deterministic), then the conversion.
+ * Capacity afterwards equals the survivors; a later add grows as it does today.
+ * AMDR_EINVAL: null handle, n_remove < 0, null remove_ids, n_remove >= n_docs, an id outside [0, n_docs), ids not
+ * strictly ascending.  n_remove == 0 is a no-op that reads nothing.  A failed remove (AMDR_EINVAL, AMDR_ENOMEM, AMDR_EHIP)
+ * leaves the handle as it was and searchable.  The price of that: the old and the new copy of D, doc_ptr and both images
+ * (4 + 4 + 2 bytes per component) plus 16 B per surviving document and 8 B per removed id of scratch are resident for the
+ * length of the call, so it can return AMDR_ENOMEM on a device where the store itself fits.  Runs inside the handle's
+ * mutex.  It is a mutation in the sense of the rule at the top of this file, and the rules for in-flight "_device" work,
+ * for workspaces (never shrunk) and for captured graphs are those of amdr_maxsim_add: finish the work first, reserve and
+ * capture again.  Pids held by others (scope tables, pid -> chunk maps) are the caller's to rebuild. */
+int amdr_maxsim_remove(amdr_maxsim_t* h, const int64_t* remove_ids, int64_t n_remove);
+/* Summed device time of the doc_ptr rebuild and the compaction kernel of the last successful amdr_maxsim_remove, in ms
+ * between events on the handle's stream (scripts/bench_store_remove.py); -1 before the first remove. */
+int amdr_maxsim_remove_kernel_ms(amdr_maxsim_t* h, double* ms);
+/* Copies the resident store to the host: D [n_tokens, 128], doc_ptr [n_docs + 1] (sizes from amdr_maxsim_info); either
+ * pointer may be null.  Synchronous, inside the handle's mutex.  The only way to see what a handle holds. */
+int amdr_maxsim_read(amdr_maxsim_t* h, float* D_host, int64_t* doc_ptr_host);
 /* out6: [0] n_docs, [1] n_tokens, [2] token capacity, [3] e of d_scale = 2^e, [4] 1 if the split-fp16 images exist,
  *       [5] whole-store conversions so far (amdr_maxsim_create of a finite store counts 1) */
 int amdr_maxsim_info(amdr_maxsim_t* h, int64_t* out6);

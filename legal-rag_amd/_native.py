@@ -31,7 +31,7 @@ FV = dict(score=0, rrf_norm=1, weighted_sum=2, dense_norm=3, bm25_norm=4, colber
 # wrapper can no longer pass a Python int where the ABI wants 64 bits (or the reverse) unnoticed.
 SIGNATURES = {
     "amdr_last_error": "", "amdr_version": "", "amdr_device_count": "P", "amdr_device_name": "iPi", "amdr_workspace_growths": "P",
-    "amdr_dense_create": "PliiP", "amdr_dense_create_from_device": "PliiP", "amdr_dense_add": "PPl",
+    "amdr_dense_create": "PliiP", "amdr_dense_create_from_device": "PliiP", "amdr_dense_add": "PPl", "amdr_dense_remove": "PPl", "amdr_dense_remove_kernel_ms": "PP",
     "amdr_dense_ntotal": "PP", "amdr_dense_dim": "PP", "amdr_dense_reserve": "Pii", "amdr_dense_search": "PPiiPP",
     "amdr_dense_search_device": "PPiiPPP", "amdr_dense_search_fuse_device": "PPiiPPPPiPPPPPPPP", "amdr_hybrid_small_device": "PPPPPiiiPPPPPPPPPPPP", "amdr_dense_small_create": "PP", "amdr_dense_small_approx_device": "PPiPlPP", "amdr_dense_small_destroy": "P", "amdr_dense_two_pass_fallbacks": "PP", "amdr_dense_read_rows": "PllP", "amdr_dense_score_rows": "PPiPiP",
     "amdr_dense_plan_info": "PiiPi", "amdr_dense_workspace_plan": "liiiiiP", "amdr_dense_hi_counters": "PP", "amdr_dense_image_build": "P", "amdr_dense_image_drop": "P", "amdr_dense_image_info": "PP", "amdr_dense_profile_begin": "Pi", "amdr_dense_profile_end": "PPP", "amdr_dense_destroy": "P",
@@ -43,7 +43,7 @@ SIGNATURES = {
     "amdr_tokenizer_destroy": "P",
     "amdr_tokenizer_pack": "PPiPlP", "amdr_tokenizer_device_create": "PiP", "amdr_tokenizer_device_reserve": "Pil",
     "amdr_tokenizer_encode_device": "PPPilPlPPP", "amdr_tokenizer_device_destroy": "P",
-    "amdr_maxsim_create": "PPliiP", "amdr_maxsim_add": "PPPl", "amdr_maxsim_info": "PP", "amdr_maxsim_stats": "PP", "amdr_maxsim_ndocs": "PP", "amdr_maxsim_plan_info": "PiPi", "amdr_maxsim_reserve": "Pii", "amdr_maxsim_workspace_plan": "liiiiiP",
+    "amdr_maxsim_create": "PPliiP", "amdr_maxsim_add": "PPPl", "amdr_maxsim_remove": "PPl", "amdr_maxsim_remove_kernel_ms": "PP", "amdr_maxsim_read": "PPP", "amdr_maxsim_info": "PP", "amdr_maxsim_stats": "PP", "amdr_maxsim_ndocs": "PP", "amdr_maxsim_plan_info": "PiPi", "amdr_maxsim_reserve": "Pii", "amdr_maxsim_workspace_plan": "liiiiiP",
     "amdr_maxsim_search": "PPiiiPP", "amdr_maxsim_search_device": "PPiiiPPP", "amdr_maxsim_scores": "PPiiP",
     "amdr_maxsim_destroy": "P",
     "amdr_fuse": "Pi" + "PPi" * 3 + "PPPP", "amdr_fuse_device": "Pi" + "PPiP" * 3 + "PPPP" + "iP",
@@ -291,6 +291,19 @@ class DenseIndex(_Handle):
         if X.ndim != 2 or X.shape[1] != self.d:
             raise ValueError(f"add: expected [*, {self.d}]")
         _check(load().amdr_dense_add(self._h, _p(X, C.c_float), C.c_int64(X.shape[0])), "amdr_dense_add")
+
+    def remove(self, ids) -> None:
+        """Remove rows (amdr_dense_remove): ids strictly ascending old row ids; the survivors are renumbered
+        0 .. n-1 in their old order and the handle is then what DenseIndex makes of them, bit for bit.  Row ids held
+        elsewhere (graph tables, scope tables, row2uid maps) name the old rows and are the caller's to rebuild."""
+        ids = _c(np.asarray(ids, dtype=np.int64).reshape(-1), np.int64)
+        _check(load().amdr_dense_remove(self._h, _p(ids, C.c_int64), C.c_int64(ids.shape[0])), "amdr_dense_remove")
+
+    def remove_kernel_ms(self) -> float:
+        """Device time of the last remove's compaction kernel, in ms (-1.0 before the first remove)."""
+        ms = C.c_double(0)
+        _check(load().amdr_dense_remove_kernel_ms(self._h, C.byref(ms)), "amdr_dense_remove_kernel_ms")
+        return float(ms.value)
 
     def reserve(self, nq_max: int, k_max: int) -> None:
         _check(load().amdr_dense_reserve(self._h, C.c_int32(nq_max), C.c_int32(k_max)), "amdr_dense_reserve")
@@ -735,6 +748,28 @@ class MaxSimIndex(_Handle):
         _check(load().amdr_maxsim_add(self._h, _p(D, C.c_float), _p(doc_ptr, C.c_int64), C.c_int64(doc_ptr.shape[0] - 1)),
                "amdr_maxsim_add")
         self.n_docs = self.info()[0]
+
+    def remove(self, ids) -> None:
+        """Remove documents (amdr_maxsim_remove): ids strictly ascending old pids (not all of them); the survivors are
+        renumbered 0 .. n-1 in their old order and the handle is then what MaxSimIndex makes of the surviving store,
+        bit for bit — its scale and first-pass bound can fall."""
+        ids = _c(np.asarray(ids, dtype=np.int64).reshape(-1), np.int64)
+        _check(load().amdr_maxsim_remove(self._h, _p(ids, C.c_int64), C.c_int64(ids.shape[0])), "amdr_maxsim_remove")
+        self.n_docs = self.info()[0]
+
+    def remove_kernel_ms(self) -> float:
+        """Device time of the last remove's doc_ptr rebuild and compaction kernel, in ms (-1.0 before the first remove)."""
+        ms = C.c_double(0)
+        _check(load().amdr_maxsim_remove_kernel_ms(self._h, C.byref(ms)), "amdr_maxsim_remove_kernel_ms")
+        return float(ms.value)
+
+    def read(self) -> Tuple[np.ndarray, np.ndarray]:
+        """(D f32[n_tokens, dim], doc_ptr i64[n_docs + 1]): the resident store copied to the host (amdr_maxsim_read)."""
+        info = self.info()
+        D = np.empty((info[1], self.dim), dtype=np.float32)
+        doc_ptr = np.empty(info[0] + 1, dtype=np.int64)
+        _check(load().amdr_maxsim_read(self._h, _p(D, C.c_float), _p(doc_ptr, C.c_int64)), "amdr_maxsim_read")
+        return D, doc_ptr
 
     def info(self) -> Tuple[int, int, int, int, int, int]:
         """(n_docs, n_tokens, token capacity, e of the store's scale 2^e, 1 if the split-fp16 images exist, whole-store

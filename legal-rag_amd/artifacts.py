@@ -342,6 +342,26 @@ def append_token_store(dirpath: Path, D_add: np.ndarray, doc_ptr_add: np.ndarray
                              np.concatenate([np.asarray(doc_ptr, dtype=np.int64), doc_ptr_add[1:] + int(doc_ptr[-1])]))
 
 
+def remove_from_token_store(dirpath: Path, doc_rows) -> Path:
+    """Take documents `doc_rows` (distinct pids; not all of them) out of the store read_token_store finds in `dirpath`:
+    the surviving documents close up in their old order, and the result is written as this build's own file,
+    atomically.  On a colbert-ai (PLAID) directory without one that is the decompressed store minus those documents,
+    which read_token_store prefers from then on."""
+    D, doc_ptr = read_token_store(dirpath)
+    doc_ptr = np.asarray(doc_ptr, dtype=np.int64)
+    n = int(doc_ptr.shape[0]) - 1
+    rows = np.unique(np.asarray(list(doc_rows), dtype=np.int64).reshape(-1))
+    if rows.size and (rows[0] < 0 or rows[-1] >= n):
+        raise ValueError(f"remove_from_token_store: document rows must lie in [0, {n})")
+    if rows.size >= n:
+        raise ValueError("remove_from_token_store: this would empty the store")
+    keep = np.ones(n, dtype=bool)
+    keep[rows] = False
+    lens = np.diff(doc_ptr)
+    return write_token_store(dirpath, np.asarray(D, dtype=np.float32)[np.repeat(keep, lens)],
+                             np.concatenate([[0], np.cumsum(lens[keep])]).astype(np.int64))
+
+
 # ---------------------------------------------------------------------------
 # colbert-ai (PLAID) index directory  [upstream layout, from memory — verify]
 #   metadata.json            {"config": {"nbits", "dim", ...}, "num_chunks", "num_partitions", "num_embeddings", ...}

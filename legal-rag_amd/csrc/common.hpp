@@ -200,6 +200,19 @@ int dense_device_of(const amdr_dense_t* h);
 void dense_matrix(const amdr_dense_t* h, const float** X, long* n, int* d);
 const DenseFp16Stats& dense_fp16_stats_of(const amdr_dense_t* h);  // its statistics of that matrix
 
+// ---- ordered row compaction into a new buffer: rows_compact.hip (amdr_dense_remove, amdr_maxsim_remove; the map is
+// rows_compact.hpp's; remove_ids is a DEVICE copy of a validated list) ----
+// new row j of n_new, row_bytes each (a multiple of 16) <- old row src(j)
+int rows_compact_launch(const void* src, long long n_new, long row_bytes, const long long* remove_ids, long n_remove,
+                        void* dst, hipStream_t st);
+// the doc_ptr rebuild: len / start [n_docs_new] scratch (a new document's length, the old row its rows start at),
+// new_ptr [n_docs_new + 1] the exclusive scan of len
+int segments_ptr_launch(const long long* doc_ptr, long n_docs_new, const long long* remove_ids, long n_remove,
+                        long long* len, long long* start, long long* new_ptr, hipStream_t st);
+// the 512-byte token rows of the surviving documents, rows_new = new_ptr[n_docs_new] of them
+int segments_compact_launch(const void* src, long long rows_new, const long long* new_ptr, const long long* start,
+                            long n_docs_new, void* dst, hipStream_t st);
+
 // ---- long-batch dense path: dense_panel.hip (panel of chunk rows shared by a block through LDS) ----
 struct DensePanelPlan {
   int parts, base, rem, nb, m_tiles, gm, waves;

@@ -1,5 +1,6 @@
-// Stream compaction pieces shared by the removals (amdr_bm25_remove, bm25_update.hip; the dense and token-store removals are
-// to reuse them): where a kept element goes is its rank among the kept ones, and a rank is
+// Stream compaction pieces shared by the removals (amdr_bm25_remove, bm25_update.hip; the token-store removal of
+// rows_compact.hip scans its document lengths with compact_scan_i64_kernel): where a kept element goes is its rank among the
+// kept ones, and a rank is
 //   the exclusive scan of the per-tile counts (compact_scan_i64_kernel)  +  the exclusive scan of the keep flags inside
 //   the element's tile (compact_tile_scan, in LDS).
 // No atomics: every position is a sum of counts, so the result is deterministic.  The host forms (compact_scan_host,

@@ -13,6 +13,7 @@
 #include "dense_dot.hpp"
 #include "dense_fp16.hpp"
 #include "dense_hi_image.hpp"
+#include "rows_compact.hpp"
 #include "topk.hpp"
 #include "topk_merge.hpp"
 
@@ -195,6 +196,7 @@ struct amdr_dense {
   void* img = nullptr;
   int64_t img_cap_rows = 0, img_rows = 0;
   float img_scale = 0.f;
+  double remove_kernel_ms = -1.0;  // device time of the compaction kernel of the last successful amdr_dense_remove
   // optional HIP-event ring bracketing the scan kernel alone (bench.py roofline)
   std::vector<hipEvent_t> prof_ev;
   int prof_used = 0;
@@ -1034,6 +1036,85 @@ int amdr_dense_add(amdr_dense_t* h, const float* X_host, int64_t n_add) {
       image_drop(h);  // (no first pass is left to read it)
   }
   return rc;
+}
+
+// Remove rows.  Everything that can run out of memory or be refused — the device copy of the list, the new matrix, the
+// compaction kernel (rows_compact.hip) — happens beside the old matrix; the handle's fields change only after the device
+// has finished.  Then what create() does on the new matrix: the statistics from zero, and a present image made again.
+int amdr_dense_remove(amdr_dense_t* h, const int64_t* remove_ids, int64_t n_remove) {
+  AMDR_REQUIRE(h != nullptr, "dense_remove: null handle");
+  AMDR_REQUIRE(h->owns, "dense_remove: handle wraps caller-owned memory");
+  AMDR_REQUIRE(n_remove >= 0, "dense_remove: n_remove=%lld", (long long)n_remove);
+  if (n_remove == 0) return AMDR_OK;
+  std::lock_guard<std::mutex> g(h->mu);
+  const int bad = rc_validate(remove_ids, n_remove, h->n);
+  AMDR_REQUIRE(bad == kRcOk, "dense_remove: %s", rc_error_text(bad));
+  AMDR_HIP(hipSetDevice(h->device));
+  const int64_t n_new = h->n - n_remove;
+  float* nx = nullptr;
+  long long* rm = nullptr;
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  float ms = 0.f;
+  int rc = AMDR_OK;
+  hipError_t e = hipSuccess;
+  if (n_new > 0) {
+    e = hipMalloc((void**)&rm, (size_t)n_remove * sizeof(long long));
+    if (e == hipSuccess) e = hipMalloc((void**)&nx, (size_t)n_new * h->d * sizeof(float));
+    if (e == hipSuccess) e = hipMemcpyAsync(rm, remove_ids, (size_t)n_remove * sizeof(long long), hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipEventCreate(&ev[0]);
+    if (e == hipSuccess) e = hipEventCreate(&ev[1]);
+    if (e == hipSuccess) e = hipEventRecord(ev[0], h->stream);
+    if (e == hipSuccess)
+      rc = rows_compact_launch(h->X, (long long)n_new, (long)h->d * (long)sizeof(float), rm, (long)n_remove, nx, h->stream);
+    if (e == hipSuccess && rc == AMDR_OK) e = hipEventRecord(ev[1], h->stream);
+    if (e == hipSuccess && rc == AMDR_OK) e = hipStreamSynchronize(h->stream);
+    if (e == hipSuccess && rc == AMDR_OK) e = hipEventElapsedTime(&ms, ev[0], ev[1]);
+    for (hipEvent_t v : ev)
+      if (v) (void)hipEventDestroy(v);
+    if (rm) (void)hipFree(rm);
+    if (e != hipSuccess || rc != AMDR_OK) {
+      if (nx) (void)hipFree(nx);
+      if (rc != AMDR_OK) return rc;
+      return fail(e == hipErrorOutOfMemory ? AMDR_ENOMEM : AMDR_EHIP, "dense_remove: %s", hipGetErrorString(e));
+    }
+  }
+  // the swap (hipFree waits for the device: host-pointer searches are behind h->mu, "_device" work is the caller's to order)
+  if (h->small) {  // the short-corpus fp16 image is of the old matrix: made again on demand
+    (void)hipDeviceSynchronize();
+    (void)amdr_dense_small_destroy(h->small);
+    h->small = nullptr;
+  }
+  h->small_failed = false;
+  if (h->X) (void)hipFree(h->X);
+  h->X = nx;
+  h->n = h->cap_rows = n_new;
+  h->remove_kernel_ms = (double)ms;
+  // the matrix changed: what the fp16 first pass learnt about it starts over, as in amdr_dense_add — and since the
+  // statistics words are made again from zero, the device's counters and the host's view of them start from zero too
+  h->hi_level = 0;
+  h->hi_off = false;
+  if (h->hi_copy_pending) {
+    (void)hipEventSynchronize(h->hi_ev);
+    h->hi_copy_pending = false;
+  }
+  for (int i = 0; i < 3; ++i) h->hi_seen[i] = 0u;
+  h->lvl_f0 = 0u;
+  h->lvl_p0 = 0;
+  h->hi_queries = h->hi_passes = 0;
+  rc = update_stats(h, 0, n_new);
+  // a handle with an fp16 image keeps one: of the compacted matrix, whose rows sit in other 32-row tiles now
+  if (h->img) {
+    image_drop(h);  // (a new allocation, sized like the new matrix's own; none for an empty index or unusable statistics)
+    if (rc == AMDR_OK && n_new > 0 && h->fp16.large_scan_ok()) rc = image_sync(h, 0);
+  }
+  return rc;
+}
+
+int amdr_dense_remove_kernel_ms(amdr_dense_t* h, double* ms) {
+  AMDR_REQUIRE(h && ms, "dense_remove_kernel_ms: null");
+  std::lock_guard<std::mutex> g(h->mu);
+  *ms = h->remove_kernel_ms;
+  return AMDR_OK;
 }
 
 int amdr_dense_image_build(amdr_dense_t* h) {

@@ -17,6 +17,7 @@
 #include "common.hpp"
 #include "lds_ring.hpp"
 #include "maxsim_core.hpp"
+#include "rows_compact.hpp"
 #include "topk.hpp"
 
 #include <cfloat>
@@ -984,6 +985,7 @@ struct amdr_maxsim {
   float d_norm_max = 0.f;        // largest token L2 norm of the store x d_scale (error bound of the first pass)
   unsigned int amax_bits = 0;    // largest |component| of the store as float bits (what d_scale was taken from)
   int64_t conversions = 0;       // whole-store conversions to the images so far (amdr_maxsim_info)
+  double remove_kernel_ms = -1.0;  // device time of the doc_ptr rebuild + the compaction of the last successful amdr_maxsim_remove
   long long* doc_ptr = nullptr;
   int cus = 0;  // compute units of `device` (the re-scoring pass's grid)
   hipStream_t stream = nullptr;
@@ -1419,6 +1421,112 @@ int amdr_maxsim_add(amdr_maxsim_t* h, const float* D_host, const int64_t* doc_pt
   h->d_scale = scale;
   h->d_norm_max = norm_max;
   h->conversions = conversions;
+  return AMDR_OK;
+}
+
+// Remove documents.  The new doc_ptr and the compacted D (rows_compact.hip) are built in new buffers, then create()'s own
+// sequence runs on the new D — largest |component|, scale, new images converted from it, d_norm_max — so the scale and
+// the bound can FALL here and a store whose last NaN / infinity goes gets its images.  The handle's fields change together
+// at the end; until then every search reads the old store.
+int amdr_maxsim_remove(amdr_maxsim_t* h, const int64_t* remove_ids, int64_t n_remove) {
+  AMDR_REQUIRE(h != nullptr, "maxsim_remove: null handle");
+  AMDR_REQUIRE(n_remove >= 0, "maxsim_remove: n_remove=%lld", (long long)n_remove);
+  if (n_remove == 0) return AMDR_OK;
+  std::lock_guard<std::mutex> g(h->mu);
+  const int bad = rc_validate(remove_ids, n_remove, h->n_docs);
+  AMDR_REQUIRE(bad == kRcOk, "maxsim_remove: %s", rc_error_text(bad));
+  AMDR_REQUIRE(n_remove < h->n_docs, "maxsim_remove: n_remove=%lld would leave no document of %lld", (long long)n_remove,
+               (long long)h->n_docs);
+  AMDR_HIP(hipSetDevice(h->device));
+  const int64_t nd1 = h->n_docs - n_remove;
+  long long *rm = nullptr, *len = nullptr, *start = nullptr, *dp = nullptr;
+  float* D = nullptr;
+  unsigned char *img = nullptr, *img_hi = nullptr;
+  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  long long t1 = 0;
+  int rc = AMDR_OK;
+  hipStream_t st = h->stream;
+  hipError_t e = hipMalloc((void**)&rm, (size_t)n_remove * sizeof(long long));
+  if (e == hipSuccess) e = hipMalloc((void**)&len, (size_t)nd1 * sizeof(long long));
+  if (e == hipSuccess) e = hipMalloc((void**)&start, (size_t)nd1 * sizeof(long long));
+  if (e == hipSuccess) e = hipMalloc((void**)&dp, (size_t)(nd1 + 1) * sizeof(long long));
+  for (int i = 0; i < 4 && e == hipSuccess; ++i) e = hipEventCreate(&ev[i]);
+  if (e == hipSuccess) e = hipMemcpyAsync(rm, remove_ids, (size_t)n_remove * sizeof(long long), hipMemcpyHostToDevice, st);
+  // the doc_ptr rebuild, then the host's look at the new token count
+  if (e == hipSuccess) e = hipEventRecord(ev[0], st);
+  if (e == hipSuccess) rc = segments_ptr_launch(h->doc_ptr, (long)nd1, rm, (long)n_remove, len, start, dp, st);
+  if (e == hipSuccess && rc == AMDR_OK) e = hipEventRecord(ev[1], st);
+  if (e == hipSuccess && rc == AMDR_OK) e = hipMemcpyAsync(&t1, dp + nd1, sizeof(long long), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess && rc == AMDR_OK) e = hipStreamSynchronize(st);
+  if (e == hipSuccess && rc == AMDR_OK && (t1 < nd1 || t1 >= h->n_tokens))
+    rc = fail(AMDR_EHIP, "maxsim_remove: counted %lld of %lld token rows", t1, (long long)h->n_tokens);
+  // the token rows
+  if (e == hipSuccess && rc == AMDR_OK) e = hipMalloc((void**)&D, (size_t)t1 * kDim * sizeof(float));
+  if (e == hipSuccess && rc == AMDR_OK) e = hipEventRecord(ev[2], st);
+  if (e == hipSuccess && rc == AMDR_OK) rc = segments_compact_launch(h->D, t1, dp, start, (long)nd1, D, st);
+  if (e == hipSuccess && rc == AMDR_OK) e = hipEventRecord(ev[3], st);
+  if (e == hipSuccess && rc == AMDR_OK) e = hipStreamSynchronize(st);
+  float ms0 = 0.f, ms1 = 0.f;
+  if (e == hipSuccess && rc == AMDR_OK) e = hipEventElapsedTime(&ms0, ev[0], ev[1]);
+  if (e == hipSuccess && rc == AMDR_OK) e = hipEventElapsedTime(&ms1, ev[2], ev[3]);
+  // exactly create()'s sequence on the new D
+  unsigned int amax = 0;
+  float scale = 1.f, norm_max = 0.f;
+  int64_t conversions = h->conversions;
+  if (e == hipSuccess && rc == AMDR_OK) e = ms_absmax(D, 0, t1, &amax);
+  if (e == hipSuccess && rc == AMDR_OK && amax < 0x7f800000u) {
+    scale = ms_scale_of(amax);
+    e = ms_alloc_images(t1, &img, &img_hi);
+    if (e == hipSuccess) e = ms_convert(D, 0, t1, scale, img, img_hi, &norm_max);
+    ++conversions;
+  }
+  if (e == hipSuccess && rc == AMDR_OK) e = hipDeviceSynchronize();
+  for (hipEvent_t v : ev)
+    if (v) (void)hipEventDestroy(v);
+  if (rm) (void)hipFree(rm);
+  if (len) (void)hipFree(len);
+  if (start) (void)hipFree(start);
+  if (e != hipSuccess || rc != AMDR_OK) {
+    if (dp) (void)hipFree(dp);
+    if (D) (void)hipFree(D);
+    if (img) (void)hipFree(img);
+    if (img_hi) (void)hipFree(img_hi);
+    if (rc != AMDR_OK) return rc;
+    return fail(e == hipErrorOutOfMemory ? AMDR_ENOMEM : AMDR_EHIP, "maxsim_remove: %s", hipGetErrorString(e));
+  }
+  // the swap (hipFree waits for the device: host-pointer searches are behind h->mu, "_device" work is the caller's to order)
+  (void)hipFree(h->D);
+  (void)hipFree(h->doc_ptr);
+  if (h->img) (void)hipFree(h->img);
+  if (h->img_hi) (void)hipFree(h->img_hi);
+  h->D = D;
+  h->doc_ptr = dp;
+  h->img = img;
+  h->img_hi = img_hi;
+  h->cap_tokens = h->n_tokens = t1;
+  h->cap_docs = h->n_docs = nd1;
+  h->amax_bits = amax;
+  h->d_scale = scale;
+  h->d_norm_max = norm_max;
+  h->conversions = conversions;
+  h->remove_kernel_ms = (double)ms0 + (double)ms1;
+  return AMDR_OK;
+}
+
+int amdr_maxsim_remove_kernel_ms(amdr_maxsim_t* h, double* ms) {
+  AMDR_REQUIRE(h && ms, "maxsim_remove_kernel_ms: null");
+  std::lock_guard<std::mutex> g(h->mu);
+  *ms = h->remove_kernel_ms;
+  return AMDR_OK;
+}
+
+int amdr_maxsim_read(amdr_maxsim_t* h, float* D_host, int64_t* doc_ptr_host) {
+  AMDR_REQUIRE(h != nullptr, "maxsim_read: null handle");
+  std::lock_guard<std::mutex> g(h->mu);
+  AMDR_HIP(hipSetDevice(h->device));
+  if (D_host) AMDR_HIP(hipMemcpy(D_host, h->D, (size_t)h->n_tokens * kDim * sizeof(float), hipMemcpyDeviceToHost));
+  if (doc_ptr_host)
+    AMDR_HIP(hipMemcpy(doc_ptr_host, h->doc_ptr, (size_t)(h->n_docs + 1) * sizeof(long long), hipMemcpyDeviceToHost));
   return AMDR_OK;
 }
 

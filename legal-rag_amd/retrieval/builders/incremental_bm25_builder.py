@@ -15,7 +15,9 @@ rule of build_bm25_index is tokenised differently here, fails that check and rel
 retriever's lock is held from the question "is the loaded state the file" until the append is done, so that no search
 thread reloads the new file in between.  A row-sharded retriever (cfg.retrieval.shard = "rows") always reloads.
 
-remove_ids takes chunks out again (the reference has no removal at all): a replaced article is remove_ids + add_jsonl."""
+remove_ids takes chunks out again (the reference has no removal at all) — out of THIS channel.  A retriever that runs the
+hybrid holds the chunk in its dense and ColBERT channels too: a replaced article is builders/remove.py
+`remove_chunk_ids(cfg, ids)`, which calls the three builders' remove_ids, followed by the three add_jsonl."""
 from __future__ import annotations
 
 import contextlib

@@ -9,12 +9,18 @@ written the meta file and the store must agree (pids 0 .. n - 1, n documents); i
 If a ColBERTRetriever of this index identity is live in the process and holds the store that was appended to, the same
 rows go behind its resident store in HBM (`amdr_maxsim_add`) and it remembers the files' mtimes, so it does not reload
 what this process wrote — under the retriever's registry lock from the check to the add, so that no search thread
-reloads the file in between; any other reader finds the store changed and reloads it."""
+reloads the file in between; any other reader finds the store changed and reloads it.
+
+remove_ids takes chunks out again under the same lock and the same consistency check: the meta file is rewritten with
+the pids renumbered 0 .. n - 1, the token store without the documents, and a live retriever that held the store takes
+the removal in place (`amdr_maxsim_remove`, ColBERTRetriever.note_removed)."""
 from __future__ import annotations
 
 import json
 import logging
+import os
 from pathlib import Path
+from typing import Iterable
 
 import numpy as np
 from filelock import FileLock
@@ -78,3 +84,50 @@ class IncrementalColBERTBuilder:
                     live.note_appended(tokens, doc_ptr, first)
         logger.info("[colbert] incremental add done: added=%d jsonl=%s", len(fresh), jsonl_path)
         return len(fresh)
+
+    def remove_ids(self, chunk_ids: Iterable[str]) -> int:
+        """Remove the chunks with these ids; returns how many were there.  None of the ids present: 0; all of them:
+        ValueError (a store keeps a document); the files are untouched in both cases.  The meta file (pids renumbered
+        0 .. n - 1, through a temporary and os.replace) is written BEFORE the token store, as in add_jsonl."""
+        rcfg = self.cfg.retrieval
+        if not bool(getattr(rcfg, "enable_colbert", False)):
+            raise RuntimeError("ColBERT is disabled: set cfg.retrieval.enable_colbert=True")
+        if getattr(rcfg, "shard", None):
+            raise RuntimeError("removal on a row-sharded index is not supported: rebuild and reload")
+        wanted = {str(i) for i in chunk_ids}
+        if not wanted:
+            return 0
+        index_path, index_name, _model, meta_file, experiment, _ = _identity(rcfg)
+        meta_file = Path(meta_file)
+        out_dir = artifacts.colbert_index_dir(index_path, experiment, index_name)
+        if not meta_file.exists() or not ((out_dir / "amdr_tokens.npz").exists() or artifacts.is_plaid_index(out_dir)):
+            raise RuntimeError(f"ColBERT index not found ({meta_file}, {out_dir}). Run build_colbert_index() first.")
+        with FileLock(str(Path(index_path) / ".colbert_build.lock")):
+            by_pid = artifacts.read_colbert_meta(meta_file)
+            rows = sorted(pid for pid, c in by_pid.items() if c.id in wanted)
+            if not rows:
+                logger.info("[colbert] none of %d ids is in the index", len(wanted))
+                return 0
+            n = len(by_pid)
+            n_store = artifacts.token_store_ndocs(out_dir)
+            if sorted(by_pid) != list(range(n)) or n_store != n:
+                raise RuntimeError(f"ColBERT index is inconsistent: {meta_file} holds {n} chunks (pids up to "
+                                   f"{max(by_pid) if by_pid else -1}), the token store in {out_dir} {n_store} documents. "
+                                   f"Rebuild it: build_colbert_index(cfg, chunks, override=True).")
+            if len(rows) >= n:
+                raise ValueError("remove_ids: this would empty the index")
+            gone = set(rows)
+            kept = [by_pid[pid] for pid in range(n) if pid not in gone]
+            live = ColBERTRetriever._instances_by_key.get(_identity(rcfg) + ("none",))
+            # the retriever's lock from the question "is the resident store the one on disk" until the documents have
+            # left it: see add_jsonl
+            with ColBERTRetriever._registry_lock:
+                in_place = live is not None and live.store_is_current()
+                tmp = meta_file.with_suffix(meta_file.suffix + ".tmp")
+                artifacts.write_colbert_meta(tmp, kept)
+                os.replace(tmp, meta_file)
+                artifacts.remove_from_token_store(out_dir, rows)
+                if in_place:
+                    live.note_removed(rows)
+        logger.info("[colbert] incremental remove done: removed=%d total=%d", len(rows), len(kept))
+        return len(rows)

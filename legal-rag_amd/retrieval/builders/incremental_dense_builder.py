@@ -6,11 +6,17 @@ the reference's name): reload the store, keep only ids it does not hold yet,
 embed them as passages, append the rows to the matrix resident in HBM
 (`amdr_dense_add` is serialised against concurrent searches inside the library),
 append the meta lines BEFORE rewriting the index file (a reader must never see
-an index row without its chunk), then persist the index."""
+an index row without its chunk), then persist the index.
+
+remove_ids takes chunks out again (the reference has no removal: a corpus that shrinks takes `index.add` over everything,
+faiss_builder.py:91, and the reload of vector_store.py): the rows leave the resident matrix in place (`amdr_dense_remove`)
+and both files are rewritten.  builders/remove.py does it for every channel of the hybrid."""
 from __future__ import annotations
 
 import logging
+import os
 from pathlib import Path
+from typing import Iterable
 
 from filelock import FileLock
 
@@ -48,3 +54,39 @@ class IncrementalDenseBuilder:
             vs._meta_mtime = vs.meta_path.stat().st_mtime
         logger.info("[index] incremental add done: added=%d jsonl=%s", len(fresh), jsonl_path)
         return len(fresh)
+
+    def remove_ids(self, chunk_ids: Iterable[str]) -> int:
+        """Remove the chunks with these ids; returns how many were there.  Under the index file lock: reload the store,
+        find their rows, take the rows out of the matrix resident in HBM (FlatIPIndex.remove_ids: the survivors close up
+        in their old order, faiss's convention), then rewrite the meta file and the index file, each through a temporary
+        and os.replace, in add_jsonl's order and with its stamping of the mtimes, so that this process does not reload
+        what it wrote.  None of the ids present: 0, all of them: ValueError (an index keeps a chunk); the files are
+        untouched in both cases.  Row ids held elsewhere name the old rows: a GraphRetriever of this store finds
+        `rows_epoch` changed and binds its row map, norms and device tables again."""
+        wanted = {str(i) for i in chunk_ids}
+        if not wanted:
+            return 0
+        vs = self.vs
+        with FileLock(str(Path(self.cfg.retrieval.faiss_index_file).with_suffix(".lock"))):
+            vs.load()
+            rows = [r for r, c in enumerate(vs.chunks) if c.id in wanted]
+            if not rows:
+                logger.info("[index] none of %d ids is in the index", len(wanted))
+                return 0
+            if len(rows) >= len(vs.chunks):
+                raise ValueError("remove_ids: this would empty the index")
+            if vs.index.ntotal != len(vs.chunks):
+                raise RuntimeError(f"[index] {vs.index_path}: {vs.index.ntotal} rows but {len(vs.chunks)} chunks")
+            vs.index.remove_ids(rows)
+            gone = set(rows)
+            kept = [c for r, c in enumerate(vs.chunks) if r not in gone]
+            tmp = vs.meta_path.with_suffix(vs.meta_path.suffix + ".tmp")
+            artifacts.write_faiss_meta(tmp, kept)
+            os.replace(tmp, vs.meta_path)
+            vs.chunks = kept
+            artifacts.write_faiss_flat_ip(vs.index_path, vs.index.reconstruct_n(0, vs.index.ntotal))
+            # what this process just wrote IS the resident state: no mtime-triggered reload
+            vs._index_mtime = vs.index_path.stat().st_mtime
+            vs._meta_mtime = vs.meta_path.stat().st_mtime
+        logger.info("[index] incremental remove done: removed=%d total=%d", len(rows), len(kept))
+        return len(rows)

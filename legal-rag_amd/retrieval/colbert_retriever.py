@@ -175,6 +175,28 @@ class ColBERTRetriever:
             self._meta_mtime = None
             self._load_meta_and_collection()
 
+    def note_removed(self, rows) -> None:
+        """IncrementalColBERTBuilder, after it has rewritten the meta file (pids renumbered 0 .. n - 1) and the token store
+        without documents `rows` (ascending pids of a store that was current: store_is_current): the same documents leave
+        the resident store (amdr_maxsim_remove), the pid map is read again, and the files' mtimes are remembered — what
+        this process wrote IS the resident state, so nothing is reloaded.  The lock discipline is note_appended's: the
+        caller holds `_registry_lock` across the check, the writes and this call.  Should the resident store not be the
+        written one plus these documents (a caller that did not hold the lock), or be a shard's block, it is read from
+        the file instead."""
+        cls = type(self)
+        rows = [int(r) for r in rows]
+        with cls._registry_lock:
+            on_disk = artifacts.token_store_ndocs(self.index_dir())
+            if self._searcher is not None and self.shard is None and self._searcher.info()[0] == on_disk + len(rows):
+                self._searcher.remove(rows)
+                self._store_mtime = self._store_stamp()
+                cls._searcher_cache[self._searcher_key] = (self._searcher, self.row_offset, self._store_mtime)
+            else:
+                held = cls._searcher_cache[self._searcher_key] = self._open_store()
+                self._searcher, self.row_offset, self._store_mtime = held
+            self._meta_mtime = None
+            self._load_meta_and_collection()
+
     def search(self, query: str, top_k: int = 5) -> List[Tuple[LawChunk, float]]:
         if not self.enabled:
             return []

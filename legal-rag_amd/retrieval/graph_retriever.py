@@ -130,6 +130,11 @@ def build_graph_tables(graph: LawGraphStore, chunks: Sequence[LawChunk]) -> Grap
                        node_row=node_row, row_node=row_node, row_lang=row_lang)
 
 
+def _rows_epoch(index: Any) -> int:
+    """How often rows of `index` were removed in place (vector_store.FlatIPIndex.rows_epoch; 0 for an index without)."""
+    return int(getattr(index, "rows_epoch", 0) or 0)
+
+
 def _depth_bound(v: Any) -> int:
     """dist >= v for an integer dist, as an integer bound."""
     return int(max(-(2 ** 31), min(2 ** 31 - 1, math.ceil(float(v)))))
@@ -187,12 +192,15 @@ class GraphRetriever:
                 self._row_of[key] = row
         self._norms: Optional[np.ndarray] = None
         self._bound_index = getattr(self.store, "index", None)
+        self._bound_epoch = _rows_epoch(self._bound_index)
 
     def _row_norms(self) -> Optional[np.ndarray]:
         index = getattr(self.store, "index", None)
         if index is None or not hasattr(index, "native"):
             return None
-        if index is not self._bound_index:  # store reloaded (mtime guard): rows may have moved
+        # store reloaded (mtime guard), or rows removed in place (FlatIPIndex.remove_ids renumbers the survivors): rows
+        # may have moved.  The count of removals, not the row count: a removal followed by an add of equal size moves them too
+        if index is not self._bound_index or _rows_epoch(index) != self._bound_epoch:
             self._bind_rows()
         if self._norms is None:
             # a row-sharded index (vector_store.ShardedFlatIPIndex) holds rows [r0, r1) only: the norms of the other
@@ -217,7 +225,7 @@ class GraphRetriever:
             raise ValueError("graph_channel='device' does not run on a row-sharded index (cfg.retrieval.shard); "
                              "use graph_channel='host'")
         cached = self.__dict__.get("_dev_graph")
-        if cached is not None and cached[0] is index:
+        if cached is not None and cached[0] is index and cached[3] == _rows_epoch(index):
             return cached[1], cached[2]
         t = build_graph_tables(self.graph, list(getattr(self.store, "chunks", []) or []))
         if len(t.row_node) != int(index.ntotal):
@@ -225,7 +233,7 @@ class GraphRetriever:
         g = _native.GraphIndex(t.node_ptr, t.edge_dst, t.edge_rel, t.conf_raw, t.conf_eff, t.evidence, t.present,
                                t.node_row, t.row_node, norms, t.row_lang, n_rel=len(t.rel_names),
                                device=int(getattr(index, "_device", getattr(self.cfg.retrieval, "device", 0)) or 0))
-        self.__dict__["_dev_graph"] = (index, g, t)
+        self.__dict__["_dev_graph"] = (index, g, t, _rows_epoch(index))
         return g, t
 
     def device_params(self, top_k: int, lang: Optional[str] = None):

@@ -39,6 +39,9 @@ class FlatIPIndex:
         self.d = int(X.shape[1])
         self.metric_type = artifacts.METRIC_INNER_PRODUCT
         self.dense_image = dense_image
+        # bumped by remove_ids: the surviving rows are renumbered in place, so whoever holds row ids of this index
+        # (GraphRetriever's row map, norms and device tables) tells by it that they name the old rows
+        self.rows_epoch = 0
         if dense_image == "fp16":
             self._build_image()
 
@@ -93,6 +96,20 @@ class FlatIPIndex:
         if self.dense_image == "fp16" and not self._idx.image_info()[0]:  # (the index was empty when it was created)
             self._build_image()
 
+    def remove_ids(self, ids) -> int:
+        """faiss `index.remove_ids` of a flat index: the rows `ids` go, the survivors close up in their old order
+        (amdr_dense_remove: one ordered compaction of the resident matrix; the handle is then what a fresh index of the
+        surviving rows is, bit for bit).  Returns the number removed.  ids: distinct rows in [0, ntotal)."""
+        rows = np.unique(np.asarray(list(ids) if not isinstance(ids, np.ndarray) else ids, dtype=np.int64).reshape(-1))
+        if rows.size == 0:
+            return 0
+        self._idx.remove(rows)
+        self.rows_epoch += 1
+        # the native remove makes a present image again; under "fp16" an index that had none yet gets it, as in add
+        if self.dense_image == "fp16" and not self._idx.image_info()[0]:
+            self._build_image()
+        return int(rows.size)
+
     def reconstruct_n(self, i0: int, n: int) -> np.ndarray:
         return self._idx.read_rows(int(i0), int(n))
 
@@ -129,6 +146,9 @@ class ShardedFlatIPIndex(FlatIPIndex):
 
     def add(self, x: np.ndarray) -> None:
         raise RuntimeError("incremental add on a row-sharded index is not supported: rebuild and reload")
+
+    def remove_ids(self, ids) -> int:
+        raise RuntimeError("removal on a row-sharded index is not supported: rebuild and reload")
 
     def reconstruct_n(self, i0: int, n: int) -> np.ndarray:
         """rows by GLOBAL id; only this rank's block is resident"""
