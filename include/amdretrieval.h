@@ -8,7 +8,7 @@
  * 0 on success or a negative AMDR_E* code, with a thread-local message available
  * from amdr_last_error(); the caller allocates all outputs; opaque handles are
  * safe for concurrent read-only searches (internally serialised per handle),
- * mutation (add/remove/destroy) must not race with searches on the same handle.
+ * mutation (add/remove/replace/destroy) must not race with searches on the same handle.
  *
  * "_device" variants take DEVICE pointers and a hipStream_t passed as void*
  * (0 = the null stream); they enqueue work and return without synchronising,
@@ -103,6 +103,33 @@ int amdr_dense_remove(amdr_dense_t* h, const int64_t* remove_ids, int64_t n_remo
  * handle's stream (scripts/bench_store_remove.py sets it against the kernel's algorithmic bytes); -1 before the first
  * remove. */
 int amdr_dense_remove_kernel_ms(amdr_dense_t* h, double* ms);
+/* Replace n_rep rows under their ids: an amended article keeps its row (the reference has no update: its builders skip a
+ * chunk id they have seen, legalrag/retrieval/builders/incremental_dense_builder.py:50-51, so an amendment takes a
+ * rebuild).
+ * replace_ids[n_rep]: old row ids, strictly ascending, in [0, n); row replace_ids[i] takes X_host[i, :].  No id moves, so
+ * row ids held by others (graph tables, scope tables, row2uid maps) still name the same chunks — only what is derived
+ * from a row's VALUES (the graph's row_norm) is the caller's to refresh.
+ * Afterwards the handle is what amdr_dense_create makes of the edited matrix: the same matrix bytes
+ * (amdr_dense_read_rows) and the statistics of the fp16 first passes taken again from zero over all rows — the largest
+ * component and row norm can fall, as under remove — hence the same ids and score bits from every entry point.  The
+ * short-corpus fp16 image is dropped (made again on demand), the adaptation of the large scan's fp16 pass and its
+ * counters start over as in amdr_dense_remove, and a resident fp16 image stays current: converted again from the first
+ * touched 32-row tile on, all of it when the power-of-two scale changed, dropped when the statistics are no longer
+ * finite.  The work: the new rows and ids are staged on the device, then one scatter kernel in 16-byte units writes the
+ * matrix IN PLACE (csrc/rows_compact.hip: every replaced byte read once and written once, nothing else moves; no atomics,
+ * deterministic), then the statistics pass over the matrix.
+ * AMDR_EINVAL: null handle, a handle from amdr_dense_create_from_device, n_rep < 0, null replace_ids or X_host,
+ * n_rep > n, an id outside [0, n), ids not strictly ascending.  n_rep == 0 is a no-op that reads nothing.  Everything that
+ * can fail happens before the scatter is enqueued, so a failed replace (AMDR_EINVAL, AMDR_ENOMEM, AMDR_EHIP) leaves the
+ * handle as it was and searchable.  Transient memory: the staged rows and ids (4 d + 8 bytes per replaced row) for the
+ * length of the call; no second matrix.  Runs inside the handle's mutex.  It is a mutation in the sense of the rule at
+ * the top of this file: "_device" work of the handle still in flight is the caller's to finish first (it would read a
+ * half-written matrix), and captured graphs must be reserved and captured again (the statistics they were routed by
+ * changed).  The row count does not change, so no workspace grows. */
+int amdr_dense_replace(amdr_dense_t* h, const int64_t* replace_ids, const float* X_host, int64_t n_rep);
+/* Device time of the scatter kernel of the last successful amdr_dense_replace, in ms between two events on the handle's
+ * stream (scripts/bench_replace.py); -1 before the first replace. */
+int amdr_dense_replace_kernel_ms(amdr_dense_t* h, double* ms);
 int amdr_dense_ntotal(const amdr_dense_t* h, int64_t* n);
 int amdr_dense_dim(const amdr_dense_t* h, int32_t* d);
 int amdr_dense_reserve(amdr_dense_t* h, int32_t nq_max, int32_t k_max);
@@ -176,7 +203,7 @@ int amdr_dense_destroy(amdr_dense_t* h);
  * term_ptr[n_terms+1] indexes post_doc/post_tf (ascending doc id per term);
  * idf already has rank_bm25's epsilon floor applied; every idf must be finite (AMDR_EINVAL otherwise).
  * Resident per posting: doc id (4 B) + fp64 factor (8 B), which the searches read, + tf (4 B); per document: its length
- * (4 B).  tf and the lengths are kept only for amdr_bm25_add / amdr_bm25_remove, which recompute every factor from them: 16 B per posting
+ * (4 B).  tf and the lengths are kept only for amdr_bm25_add / amdr_bm25_remove / amdr_bm25_replace, which recompute every factor from them: 16 B per posting
  * of HBM instead of 12, + 4 B per document. */
 int amdr_bm25_create(const int64_t* term_ptr, const int32_t* post_doc, const int32_t* post_tf,
                      const double* idf, const int32_t* doc_len, int64_t n_terms, int64_t n_docs,
@@ -237,6 +264,46 @@ int amdr_bm25_remove(amdr_bm25_t* h, const int64_t* remove_ids, int64_t n_remove
 /* Summed device time of the passes of the last successful amdr_bm25_remove, in ms between events on the handle's stream
  * (scripts/bench_bm25_remove.py sets it against the passes' algorithmic bytes); -1 before the first remove. */
 int amdr_bm25_remove_kernel_ms(amdr_bm25_t* h, double* ms);
+/* Replace n_rep documents under their ids: an amended article keeps its id (the reference has no update: its builder
+ * skips a chunk id it has seen, legalrag/retrieval/builders/incremental_bm25_builder.py:56-57, so an amendment takes the
+ * full re-fit + reload).  replace_ids[n_rep]: old document ids, strictly ascending, in [0, n_docs); n_rep <= n_docs.  The new
+ * documents come as their own term-major CSR over the NEW term table, as in amdr_bm25_add: term_ptr_add[n_terms_new + 1] /
+ * post_doc_add / post_tf_add, post_doc_add holding local ids 0 .. n_rep-1, strictly ascending per term, local i being
+ * document replace_ids[i]; doc_len_add[n_rep].  term_map[n_terms]: the new id of each old term or -1, injective, as in
+ * amdr_bm25_remove — a re-fit of the edited corpus drops the terms whose last document lost them and may order the rest
+ * differently; null is the identity on the old terms with the new terms behind them (n_terms_new >= n_terms; an emptied
+ * term keeps its id with an empty list).  New ids that no old term maps to are NEW terms: their lists come from the add
+ * alone.  idf[n_terms_new] and avgdl are the caller's values, as in both other updates (native code takes no logarithm).
+ * Afterwards every new term's list is the merge by document id of its old term's surviving postings (the documents not
+ * in replace_ids) and the add's postings at replace_ids[local]; doc_len[replace_ids[i]] = doc_len_add[i]; every factor
+ * is recomputed.  The handle is what amdr_bm25_create makes of the edited index: term_ptr, post_doc, post_tf, post_w, idf
+ * and doc_len are the same bytes (amdr_bm25_read), hence the same ids and score bits from every entry point.  No
+ * document id moves, so tables that name documents stay valid.
+ * The work: one count and one scatter over ALL resident postings (the remove's tiles of 2 048 old postings and its
+ * counting pass) plus one pass over the add's postings — one pass fewer than a remove followed by an add — and host work
+ * proportional to n_terms + n_rep + the add's postings: it validates the call's arrays only.  A posting's place is a sum
+ * of counts and one binary search in the other source's list (csrc/bm25_replace_rule.hpp): no atomics, deterministic.
+ * AMDR_EINVAL: null handle, n_rep < 0, a null array the sizes say is read, n_rep > n_docs, an id outside [0, n_docs), ids
+ * not strictly ascending, n_terms_new outside [0, 2^31), a null map with n_terms_new < n_terms, a map value below -1 or
+ * >= n_terms_new, two terms on one new id, term_ptr_add[0] != 0 or not monotone, a post_doc_add outside [0, n_rep) or
+ * not strictly ascending within a term, a non-finite idf, a non-finite or non-positive avgdl — and a term mapped to -1
+ * that still has a surviving posting, which only the device sees: the counting passes raise a flag that is read before
+ * the swap.  n_rep == 0 is a no-op that reads nothing.  A failed replace (AMDR_EINVAL, AMDR_ENOMEM, AMDR_EHIP) leaves the
+ * handle as it was and searchable.  Transient memory: the new arrays are built beside the old ones and swapped in after
+ * the handle's stream has finished (a second copy of the index: 16 B per posting, 4 B per document, 16 B per term), plus
+ * the scratch of the remove (2 B per old posting, 4 B per document, 8 B per old term), the add's CSR (8 B per added
+ * posting, 8 B per new term), 12 B per new term and 12 B per replaced document.  Runs inside the handle's mutex.  It is
+ * a mutation in the sense of the rule at the top of this file, and the rules for in-flight "_device" work and for
+ * captured graphs are those of amdr_bm25_add: finish the work first, reserve and capture again.  n_docs does not change,
+ * so no workspace grows.  The arrival counters of the one-launch serving step stay as they are. */
+int amdr_bm25_replace(amdr_bm25_t* h, const int64_t* replace_ids, int64_t n_rep, const int64_t* term_ptr_add,
+                      const int32_t* post_doc_add, const int32_t* post_tf_add, const int32_t* doc_len_add,
+                      const int32_t* term_map, int64_t n_terms_new, const double* idf, double avgdl);
+/* Summed device time of the passes of the last successful amdr_bm25_replace, in ms between events on the handle's stream
+ * (scripts/bench_replace.py sets it against the passes' algorithmic bytes); -1 before the first replace. */
+int amdr_bm25_replace_kernel_ms(amdr_bm25_t* h, double* ms);
+/* Replaces so far (amdr_bm25_info keeps its six words: a replace touches neither [3] nor [5]). */
+int amdr_bm25_replaces(amdr_bm25_t* h, int64_t* n);
 /* out6: [0] n_docs, [1] n_terms, [2] nnz (postings), [3] adds so far, [4] the tile length in postings of the merge
  *       kernel and of the remove's passes, [5] removes so far (an add does not touch [5], a remove does not touch [3]) */
 int amdr_bm25_info(amdr_bm25_t* h, int64_t* out6);
@@ -400,6 +467,31 @@ int amdr_maxsim_remove(amdr_maxsim_t* h, const int64_t* remove_ids, int64_t n_re
 /* Summed device time of the doc_ptr rebuild and the compaction kernel of the last successful amdr_maxsim_remove, in ms
  * between events on the handle's stream (scripts/bench_store_remove.py); -1 before the first remove. */
 int amdr_maxsim_remove_kernel_ms(amdr_maxsim_t* h, double* ms);
+/* Replace n_rep documents under their pids (the reference has no update: an amended passage takes the indexer over
+ * everything again, legalrag/retrieval/builders/colbert_builder.py:131-132).  replace_ids[n_rep]: old pids, strictly
+ * ascending, in [0, n_docs); document replace_ids[i] takes the token rows D_host[doc_ptr_add[i] .. doc_ptr_add[i + 1])
+ * (doc_ptr_add[0] == 0, every document has >= 1 token; a document may grow, shrink or keep its length).  No pid moves.
+ * Afterwards the handle is what amdr_maxsim_create makes of the edited store: D and doc_ptr are the same bytes
+ * (amdr_maxsim_read), and create's own sequence has run on the new D — largest |component|, power-of-two scale, both
+ * images converted again, d_norm_max — hence the same ids and score bits from every entry point.  As under remove the
+ * scale and d_norm_max can FALL, a store whose last NaN / infinity is replaced away gets its images, and info[5] goes up
+ * by one per replace of a store that is finite afterwards.  The work: the new rows, their doc_ptr and the ids are staged
+ * on the device, two small kernels rebuild doc_ptr (lengths, then the scan), one ordered splice writes the 512-byte token
+ * rows in 16-byte units into a NEW buffer, each from the old D or from the staged rows (csrc/rows_compact.hip; no
+ * atomics, deterministic), then the conversion.  Capacity afterwards equals the store.
+ * AMDR_EINVAL: null handle, n_rep < 0, null replace_ids / D_host / doc_ptr_add, n_rep > n_docs, an id outside
+ * [0, n_docs), ids not strictly ascending, doc_ptr_add[0] != 0, a document without tokens.  n_rep == 0 is a no-op that
+ * reads nothing.  A failed replace (AMDR_EINVAL, AMDR_ENOMEM, AMDR_EHIP) leaves the handle as it was and searchable.
+ * Transient memory: the old and the new copy of D, doc_ptr and both images (4 + 4 + 2 bytes per component), the staged
+ * rows (512 B per new token, 8 B per replaced document) and 16 B per document of scratch are resident for the length of
+ * the call, so it can return AMDR_ENOMEM on a device where the store itself fits.  Runs inside the handle's mutex.  It is
+ * a mutation in the sense of the rule at the top of this file, and the rules for in-flight "_device" work and for
+ * captured graphs are those of amdr_maxsim_add: finish the work first, reserve and capture again. */
+int amdr_maxsim_replace(amdr_maxsim_t* h, const int64_t* replace_ids, const float* D_host, const int64_t* doc_ptr_add,
+                        int64_t n_rep);
+/* Summed device time of the doc_ptr rebuild and the splice kernel of the last successful amdr_maxsim_replace, in ms
+ * between events on the handle's stream (scripts/bench_replace.py); -1 before the first replace. */
+int amdr_maxsim_replace_kernel_ms(amdr_maxsim_t* h, double* ms);
 /* Copies the resident store to the host: D [n_tokens, 128], doc_ptr [n_docs + 1] (sizes from amdr_maxsim_info); either
  * pointer may be null.  Synchronous, inside the handle's mutex.  The only way to see what a handle holds. */
 int amdr_maxsim_read(amdr_maxsim_t* h, float* D_host, int64_t* doc_ptr_host);

@@ -31,11 +31,11 @@ FV = dict(score=0, rrf_norm=1, weighted_sum=2, dense_norm=3, bm25_norm=4, colber
 # wrapper can no longer pass a Python int where the ABI wants 64 bits (or the reverse) unnoticed.
 SIGNATURES = {
     "amdr_last_error": "", "amdr_version": "", "amdr_device_count": "P", "amdr_device_name": "iPi", "amdr_workspace_growths": "P",
-    "amdr_dense_create": "PliiP", "amdr_dense_create_from_device": "PliiP", "amdr_dense_add": "PPl", "amdr_dense_remove": "PPl", "amdr_dense_remove_kernel_ms": "PP",
+    "amdr_dense_create": "PliiP", "amdr_dense_create_from_device": "PliiP", "amdr_dense_add": "PPl", "amdr_dense_remove": "PPl", "amdr_dense_remove_kernel_ms": "PP", "amdr_dense_replace": "PPPl", "amdr_dense_replace_kernel_ms": "PP",
     "amdr_dense_ntotal": "PP", "amdr_dense_dim": "PP", "amdr_dense_reserve": "Pii", "amdr_dense_search": "PPiiPP",
     "amdr_dense_search_device": "PPiiPPP", "amdr_dense_search_fuse_device": "PPiiPPPPiPPPPPPPP", "amdr_hybrid_small_device": "PPPPPiiiPPPPPPPPPPPP", "amdr_dense_small_create": "PP", "amdr_dense_small_approx_device": "PPiPlPP", "amdr_dense_small_destroy": "P", "amdr_dense_two_pass_fallbacks": "PP", "amdr_dense_read_rows": "PllP", "amdr_dense_score_rows": "PPiPiP",
     "amdr_dense_plan_info": "PiiPi", "amdr_dense_workspace_plan": "liiiiiP", "amdr_dense_hi_counters": "PP", "amdr_dense_image_build": "P", "amdr_dense_image_drop": "P", "amdr_dense_image_info": "PP", "amdr_dense_profile_begin": "Pi", "amdr_dense_profile_end": "PPP", "amdr_dense_destroy": "P",
-    "amdr_bm25_create": "PPPPPlldddiP", "amdr_bm25_ndocs": "PP", "amdr_bm25_add": "PPPPPPlld", "amdr_bm25_info": "PP", "amdr_bm25_add_kernel_ms": "PP", "amdr_bm25_remove": "PPlPlPd", "amdr_bm25_remove_kernel_ms": "PP", "amdr_bm25_read": "PPPPPPP", "amdr_bm25_reserve": "Piil", "amdr_bm25_workspace_plan": "liiiiP", "amdr_bm25_plan_info": "PiiPi",
+    "amdr_bm25_create": "PPPPPlldddiP", "amdr_bm25_ndocs": "PP", "amdr_bm25_add": "PPPPPPlld", "amdr_bm25_info": "PP", "amdr_bm25_add_kernel_ms": "PP", "amdr_bm25_remove": "PPlPlPd", "amdr_bm25_remove_kernel_ms": "PP", "amdr_bm25_replace": "PPlPPPPPlPd", "amdr_bm25_replace_kernel_ms": "PP", "amdr_bm25_replaces": "PP", "amdr_bm25_read": "PPPPPPP", "amdr_bm25_reserve": "Piil", "amdr_bm25_workspace_plan": "liiiiP", "amdr_bm25_plan_info": "PiiPi",
     "amdr_bm25_search": "PPPiiPP", "amdr_bm25_search_device": "PPPiiPPP", "amdr_bm25_scores": "PPPiP",
     "amdr_bm25_destroy": "P",
     "amdr_tokenizer_create": "PPlP", "amdr_tokenizer_encode": "PPPiPlPP", "amdr_tokenizer_encode_joined": "PPliPlPP", "amdr_tokenizer_encode_ptrs": "PPPiPlPP", "amdr_tokenizer_spans": "PlPPiP",
@@ -43,7 +43,7 @@ SIGNATURES = {
     "amdr_tokenizer_destroy": "P",
     "amdr_tokenizer_pack": "PPiPlP", "amdr_tokenizer_device_create": "PiP", "amdr_tokenizer_device_reserve": "Pil",
     "amdr_tokenizer_encode_device": "PPPilPlPPP", "amdr_tokenizer_device_destroy": "P",
-    "amdr_maxsim_create": "PPliiP", "amdr_maxsim_add": "PPPl", "amdr_maxsim_remove": "PPl", "amdr_maxsim_remove_kernel_ms": "PP", "amdr_maxsim_read": "PPP", "amdr_maxsim_info": "PP", "amdr_maxsim_stats": "PP", "amdr_maxsim_ndocs": "PP", "amdr_maxsim_plan_info": "PiPi", "amdr_maxsim_reserve": "Pii", "amdr_maxsim_workspace_plan": "liiiiiP",
+    "amdr_maxsim_create": "PPliiP", "amdr_maxsim_add": "PPPl", "amdr_maxsim_remove": "PPl", "amdr_maxsim_remove_kernel_ms": "PP", "amdr_maxsim_replace": "PPPPl", "amdr_maxsim_replace_kernel_ms": "PP", "amdr_maxsim_read": "PPP", "amdr_maxsim_info": "PP", "amdr_maxsim_stats": "PP", "amdr_maxsim_ndocs": "PP", "amdr_maxsim_plan_info": "PiPi", "amdr_maxsim_reserve": "Pii", "amdr_maxsim_workspace_plan": "liiiiiP",
     "amdr_maxsim_search": "PPiiiPP", "amdr_maxsim_search_device": "PPiiiPPP", "amdr_maxsim_scores": "PPiiP",
     "amdr_maxsim_destroy": "P",
     "amdr_fuse": "Pi" + "PPi" * 3 + "PPPP", "amdr_fuse_device": "Pi" + "PPiP" * 3 + "PPPP" + "iP",
@@ -305,6 +305,22 @@ class DenseIndex(_Handle):
         _check(load().amdr_dense_remove_kernel_ms(self._h, C.byref(ms)), "amdr_dense_remove_kernel_ms")
         return float(ms.value)
 
+    def replace(self, ids, X: np.ndarray) -> None:
+        """Replace rows under their ids (amdr_dense_replace): ids strictly ascending row ids, row ids[i] takes X[i].  No
+        row moves; the handle is then what DenseIndex makes of the edited matrix, bit for bit."""
+        ids = _c(np.asarray(ids, dtype=np.int64).reshape(-1), np.int64)
+        X = _c(X, np.float32)
+        if X.ndim != 2 or X.shape[1] != self.d or X.shape[0] != ids.shape[0]:
+            raise ValueError(f"replace: expected [{ids.shape[0]}, {self.d}]")
+        _check(load().amdr_dense_replace(self._h, _p(ids, C.c_int64), _p(X, C.c_float), C.c_int64(ids.shape[0])),
+               "amdr_dense_replace")
+
+    def replace_kernel_ms(self) -> float:
+        """Device time of the last replace's scatter kernel, in ms (-1.0 before the first replace)."""
+        ms = C.c_double(0)
+        _check(load().amdr_dense_replace_kernel_ms(self._h, C.byref(ms)), "amdr_dense_replace_kernel_ms")
+        return float(ms.value)
+
     def reserve(self, nq_max: int, k_max: int) -> None:
         _check(load().amdr_dense_reserve(self._h, C.c_int32(nq_max), C.c_int32(k_max)), "amdr_dense_reserve")
 
@@ -452,6 +468,42 @@ class BM25Index(_Handle):
         ms = C.c_double(-1.0)
         _check(load().amdr_bm25_remove_kernel_ms(self._h, C.byref(ms)), "amdr_bm25_remove_kernel_ms")
         return float(ms.value)
+
+    def replace(self, replace_ids, term_ptr_add, post_doc_add, post_tf_add, doc_len_add, idf, avgdl: float,
+                term_map=None) -> None:
+        """Replace documents under their ids (amdr_bm25_replace): replace_ids strictly ascending; the new documents' own
+        term-major CSR over the NEW term table (local id i = document replace_ids[i]) and their lengths; term_map[n_terms]:
+        the new id of each old term or -1, injective (None: the identity, new terms behind the old); new ids no old term
+        maps to are new terms; idf: the WHOLE new vector; avgdl: the new value.  No document id moves.  Afterwards the
+        index is what BM25Index makes of the edited arrays, bit for bit.  A "_device" caller finishes its work first and
+        reserves again."""
+        ids = _c(replace_ids, np.int64)
+        tp, pd, pt = _c(term_ptr_add, np.int64), _c(post_doc_add, np.int32), _c(post_tf_add, np.int32)
+        idf_, dl = _c(idf, np.float64), _c(doc_len_add, np.int32)
+        tm = None if term_map is None else _c(term_map, np.int32)
+        if (ids.ndim != 1 or tp.ndim != 1 or tp.shape[0] < 1 or idf_.shape != (tp.shape[0] - 1,) or pd.shape != pt.shape
+                or dl.shape != ids.shape or (tm is not None and tm.shape != (self.n_terms,))):
+            raise ValueError("replace: replace_ids and doc_len_add [n_rep], term_ptr_add [V + 1], idf [V], post_doc_add and "
+                             "post_tf_add of one length, term_map [n_terms] or None")
+        if ids.shape[0] and pd.shape[0] < int(tp[-1]):
+            raise ValueError("replace: term_ptr_add points past the postings")
+        _check(load().amdr_bm25_replace(self._h, _p(ids, C.c_int64), C.c_int64(ids.shape[0]), _p(tp, C.c_int64),
+                                        _p(pd, C.c_int32), _p(pt, C.c_int32), _p(dl, C.c_int32),
+                                        None if tm is None else _p(tm, C.c_int32), C.c_int64(idf_.shape[0]),
+                                        _p(idf_, C.c_double), C.c_double(avgdl)), "amdr_bm25_replace")
+        self.n_docs, self.n_terms = self.info()[:2]
+
+    def replace_kernel_ms(self) -> float:
+        """Summed device time of the last replace's passes in ms (-1 before the first replace)."""
+        ms = C.c_double(-1.0)
+        _check(load().amdr_bm25_replace_kernel_ms(self._h, C.byref(ms)), "amdr_bm25_replace_kernel_ms")
+        return float(ms.value)
+
+    def replaces(self) -> int:
+        """Replaces so far (amdr_bm25_replaces)."""
+        n = C.c_int64(0)
+        _check(load().amdr_bm25_replaces(self._h, C.byref(n)), "amdr_bm25_replaces")
+        return int(n.value)
 
     def info(self) -> Tuple[int, int, int, int, int, int]:
         """(n_docs, n_terms, postings, adds so far, the tile length in postings of the add's and the remove's kernels,
@@ -761,6 +813,28 @@ class MaxSimIndex(_Handle):
         """Device time of the last remove's doc_ptr rebuild and compaction kernel, in ms (-1.0 before the first remove)."""
         ms = C.c_double(0)
         _check(load().amdr_maxsim_remove_kernel_ms(self._h, C.byref(ms)), "amdr_maxsim_remove_kernel_ms")
+        return float(ms.value)
+
+    def replace(self, ids, D: np.ndarray, doc_ptr: np.ndarray) -> None:
+        """Replace documents under their pids (amdr_maxsim_replace): ids strictly ascending pids, document ids[i] takes
+        the token rows D[doc_ptr[i]:doc_ptr[i + 1]] (doc_ptr: their own offsets, from 0).  No pid moves; the handle is then
+        what MaxSimIndex makes of the edited store, bit for bit — its scale and first-pass bound can fall."""
+        ids = _c(np.asarray(ids, dtype=np.int64).reshape(-1), np.int64)
+        D = _c(D, np.float32)
+        doc_ptr = _c(doc_ptr, np.int64)
+        if D.ndim != 2 or D.shape[1] != self.dim:
+            raise ValueError(f"replace: D must be [tokens, {self.dim}]")
+        if doc_ptr.ndim != 1 or doc_ptr.shape[0] != ids.shape[0] + 1:
+            raise ValueError("replace: doc_ptr must be [len(ids) + 1]")
+        if int(doc_ptr[-1]) != D.shape[0]:
+            raise ValueError("doc_ptr[-1] != number of token rows")
+        _check(load().amdr_maxsim_replace(self._h, _p(ids, C.c_int64), _p(D, C.c_float), _p(doc_ptr, C.c_int64),
+                                          C.c_int64(ids.shape[0])), "amdr_maxsim_replace")
+
+    def replace_kernel_ms(self) -> float:
+        """Device time of the last replace's doc_ptr rebuild and splice kernel, in ms (-1.0 before the first replace)."""
+        ms = C.c_double(0)
+        _check(load().amdr_maxsim_replace_kernel_ms(self._h, C.byref(ms)), "amdr_maxsim_replace_kernel_ms")
         return float(ms.value)
 
     def read(self) -> Tuple[np.ndarray, np.ndarray]:

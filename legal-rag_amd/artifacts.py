@@ -362,6 +362,33 @@ def remove_from_token_store(dirpath: Path, doc_rows) -> Path:
                              np.concatenate([[0], np.cumsum(lens[keep])]).astype(np.int64))
 
 
+def replace_in_token_store(dirpath: Path, doc_rows, D_new: np.ndarray, doc_ptr_new: np.ndarray) -> Path:
+    """Documents `doc_rows` (distinct pids) of the store read_token_store finds in `dirpath` take the token rows
+    D_new[doc_ptr_new[i]:doc_ptr_new[i + 1]] (doc_ptr_new: their own offsets, from 0; a document may grow, shrink or keep
+    its length); no document moves.  The result is written as this build's own file, atomically.  On a colbert-ai
+    (PLAID) directory without one that is the decompressed, edited store, which read_token_store prefers from then on."""
+    D, doc_ptr = read_token_store(dirpath)
+    D = np.asarray(D, dtype=np.float32)
+    doc_ptr = np.asarray(doc_ptr, dtype=np.int64)
+    n = int(doc_ptr.shape[0]) - 1
+    rows = np.asarray(list(doc_rows), dtype=np.int64).reshape(-1)
+    D_new = np.ascontiguousarray(D_new, dtype=np.float32)
+    doc_ptr_new = np.ascontiguousarray(doc_ptr_new, dtype=np.int64)
+    if rows.size and (rows.min() < 0 or rows.max() >= n or np.unique(rows).size != rows.size):
+        raise ValueError(f"replace_in_token_store: document rows must be distinct and lie in [0, {n})")
+    if D_new.ndim != 2 or D_new.shape[1] != D.shape[1]:
+        raise ValueError(f"replace_in_token_store: D_new must be [tokens, {D.shape[1]}]")
+    if doc_ptr_new.ndim != 1 or doc_ptr_new.shape[0] != rows.size + 1 or doc_ptr_new[0] != 0 \
+            or doc_ptr_new[-1] != D_new.shape[0] or np.any(np.diff(doc_ptr_new) < 1):
+        raise ValueError("replace_in_token_store: doc_ptr_new must run from 0 to the number of new token rows, ascending, "
+                         "one document per row id")
+    new_of = {int(r): i for i, r in enumerate(rows)}
+    parts = [D_new[doc_ptr_new[new_of[j]]:doc_ptr_new[new_of[j] + 1]] if j in new_of else D[doc_ptr[j]:doc_ptr[j + 1]]
+             for j in range(n)]
+    return write_token_store(dirpath, np.concatenate(parts, axis=0) if parts else D,
+                             np.concatenate([[0], np.cumsum([p.shape[0] for p in parts])]).astype(np.int64))
+
+
 # ---------------------------------------------------------------------------
 # colbert-ai (PLAID) index directory  [upstream layout, from memory — verify]
 #   metadata.json            {"config": {"nbits", "dim", ...}, "num_chunks", "num_partitions", "num_embeddings", ...}

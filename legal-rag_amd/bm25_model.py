@@ -258,6 +258,92 @@ class BM25Okapi:
             self.__dict__.pop("_gpu_device", None)
         return len(ids)
 
+    def replace_documents(self, doc_ids: Sequence[int], corpus: Sequence[Sequence[str]]) -> int:
+        """Replace documents under their ids: document doc_ids[i] takes the tokens corpus[i] (any order; an id given twice
+        is a ValueError) and no document moves.  Afterwards this object equals BM25Okapi(the edited corpus in its original
+        order): the idf dict in the re-fit's key order — the first-seen order of the EDITED corpus, which drops a term
+        whose last document lost it, takes in new terms where they first appear and moves a word whose first appearance
+        moved — with the same bits (math.log per term and a sequential sum in that order, as __init__), avgdl,
+        average_idf, doc_len, doc_freqs.  O(V + the postings, at C speed) after the one-time document-frequency cache.
+        ValueError for an id out of range or a length mismatch; the object is unchanged then.  A resident unsharded index
+        (gpu()) takes the replacement in place (BM25Index.replace: the ids, the new documents' CSR over the new term
+        table, the map old term id -> new term id, the new idf vector and avgdl); a row shard is dropped and uploaded
+        again on its next use.  Returns the number of documents replaced."""
+        corpus = list(corpus)
+        ids = [int(i) for i in doc_ids]
+        if len(ids) != len(corpus):
+            raise ValueError(f"replace_documents: {len(ids)} ids for {len(corpus)} documents")
+        if not ids:
+            return 0
+        order = sorted(range(len(ids)), key=ids.__getitem__)
+        ids = [ids[i] for i in order]
+        corpus = [corpus[i] for i in order]
+        if ids[0] < 0 or ids[-1] >= self.corpus_size:
+            raise ValueError(f"replace_documents: ids must lie in [0, {self.corpus_size})")
+        if any(a == b for a, b in zip(ids, ids[1:])):
+            raise ValueError("replace_documents: an id is given twice")
+        nd_old = self._doc_frequencies()
+        total = self.__dict__["_total"]
+        change: Dict[str, int] = {}  # document frequency: lost by the old documents, gained by the new ones
+        added: List[Dict[str, int]] = []
+        for d, document in zip(ids, corpus):
+            total += len(document) - self.doc_len[d]
+            for word in self.doc_freqs[d]:
+                change[word] = change.get(word, 0) - 1
+            freqs: Dict[str, int] = {}
+            for word in document:
+                freqs[word] = freqs.get(word, 0) + 1
+            added.append(freqs)
+            for word in freqs:
+                change[word] = change.get(word, 0) + 1
+        doc_freqs = list(self.doc_freqs)
+        doc_len = list(self.doc_len)
+        for d, document, freqs in zip(ids, corpus, added):
+            doc_freqs[d] = freqs
+            doc_len[d] = len(document)
+        # the re-fit's vocabulary order: a word's place is its first appearance in the edited corpus
+        nd = dict.fromkeys(chain.from_iterable(doc_freqs))
+        for word in nd:
+            nd[word] = nd_old.get(word, 0) + change.get(word, 0)
+        corpus_size = self.corpus_size
+        idf: Dict[str, float] = {}
+        idf_sum = 0
+        negative = []
+        for word, freq in nd.items():
+            v = math.log(corpus_size - freq + 0.5) - math.log(freq + 0.5)
+            idf[word] = v
+            idf_sum += v
+            if v < 0:
+                negative.append(word)
+        average_idf = idf_sum / len(idf)
+        eps = self.epsilon * average_idf
+        for word in negative:
+            idf[word] = eps
+        g = self.__dict__.get("_gpu")
+        in_place = g is not None and self.__dict__.get("_gpu_device", (None, None))[1] is None
+        if in_place:  # old term id -> new term id, -1 for a term that is gone; the new documents over the new term table
+            new_vocab = {w: t for t, w in enumerate(nd)}
+            term_map = np.fromiter((new_vocab.get(w, -1) for w in self.vocab()), dtype=np.int32, count=len(self.vocab()))
+            add_csr = docs_csr(added, new_vocab)
+        self.doc_freqs, self.doc_len = doc_freqs, doc_len
+        self.avgdl = total / corpus_size
+        self.idf, self.average_idf = idf, average_idf
+        self.__dict__["_nd"], self.__dict__["_total"] = nd, total
+        self.__dict__.pop("_vocab", None)
+        if in_place:
+            self.__dict__["_vocab"] = new_vocab
+            try:
+                g.replace(np.asarray(ids, dtype=np.int64), *add_csr, np.asarray([doc_len[d] for d in ids], dtype=np.int32),
+                          np.fromiter(idf.values(), dtype=np.float64, count=len(idf)), float(self.avgdl), term_map=term_map)
+            except Exception:  # the resident index is unchanged and now behind this object: upload again on next use
+                self.__dict__.pop("_gpu", None)
+                self.__dict__.pop("_gpu_device", None)
+                raise
+        elif g is not None:
+            self.__dict__.pop("_gpu", None)
+            self.__dict__.pop("_gpu_device", None)
+        return len(ids)
+
     def to_csr(self):
         vocab = self.vocab()
         V = len(vocab)

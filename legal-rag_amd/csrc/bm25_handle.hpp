@@ -78,10 +78,11 @@ struct BmStagedIndex : BmIndex {
 struct amdr_bm25 {
   int device = 0;
   amdr::BmIndex ix;
-  int64_t adds = 0, removes = 0;
+  int64_t adds = 0, removes = 0, replaces = 0;
   double k1 = 1.5, b = 0.75;
   double add_kernel_ms = -1;     // event time of the last add's merge kernel (amdr_bm25_add_kernel_ms)
   double remove_kernel_ms = -1;  // summed event time of the last remove's passes (amdr_bm25_remove_kernel_ms)
+  double replace_kernel_ms = -1;  // summed event time of the last replace's passes (amdr_bm25_replace_kernel_ms)
   hipStream_t stream = nullptr;
   std::mutex mu;
   // part[0]: "_device" calls, part[1]: host-pointer calls (see dense.hip)

@@ -1,10 +1,10 @@
-// BM25 channel: updates of the resident index (bm25_handle.hpp) — amdr_bm25_add, amdr_bm25_remove — and what reads it
-// back (amdr_bm25_info, amdr_bm25_read).  After any sequence of updates the handle is what amdr_bm25_create (bm25.hip)
+// BM25 channel: updates of the resident index (bm25_handle.hpp) — amdr_bm25_add, amdr_bm25_remove, amdr_bm25_replace — and
+// what reads it back (amdr_bm25_info, amdr_bm25_read).  After any sequence of updates the handle is what amdr_bm25_create (bm25.hip)
 // makes of the resulting index, byte for byte: built with -ffp-contract=off, as bm25.hip is, so that bm25_factor gives the
 // bits of create's host loop.
 //
-// Both updates build a second BmIndex beside the live one and commit it by one swap after the stream has finished: a
-// failed update leaves the handle as it was.  Both divide the work by tiles of kBmTile postings, not by terms (a Zipfian
+// Every update builds a second BmIndex beside the live one and commits it by one swap after the stream has finished: a
+// failed update leaves the handle as it was.  All divide the work by tiles of kBmTile postings, not by terms (a Zipfian
 // head term holds every document and a wave per term would serialise on it); a block finds the terms of its tile with
 // bm_tile_window.  No atomics anywhere: the result is deterministic.
 //
@@ -25,14 +25,28 @@
 //   (the host reads nnz_new and the flag here, and allocates the new posting arrays at their exact size)
 //   bm25_rm_scatter_kernel  per tile: a kept posting of term t goes to new_ptr[term_map[t]] + rank - rank_at[t] with its
 //                           mapped document, its tf and the recomputed factor    reads 10 B + two 4 B gathers, writes 16 B
+//
+// amdr_bm25_replace exchanges documents under their ids: the remove's document map, counting pass and scans, then two
+// scatters that MERGE, per new term, the surviving old postings with the new documents' postings by document id
+// (bm25_replace_rule.hpp) — one pass over the postings fewer than a remove followed by an add, and no id moves:
+//   bm25_rp_docmap_kernel       doc_keep[d] = d or -1 (replaced); doc_len[d] = the old or the new length
+//   bm25_rm_count_kernel        as in the remove, over doc_keep
+//   bm25_rp_terms_kernel        rank_at per old term, the flag, and df_new[u] = survivors of the old term of u + add count
+//   bm25_rp_scatter_old_kernel  per tile of old postings: a kept posting goes behind the kept ones before it and the add
+//                               postings of its new list with a smaller document (one search in that list, mostly empty)
+//   bm25_rp_scatter_add_kernel  per tile of the add's postings: behind the add postings before it and the kept old
+//                               postings with a smaller document (one search in the old list + the tile rank tables)
 #include "common.hpp"
 
+#include <memory>
 #include <mutex>
+#include <new>
 
 #include "bm25_add_rule.hpp"
 #include "bm25_core.hpp"
 #include "bm25_handle.hpp"
 #include "bm25_remove_rule.hpp"
+#include "bm25_replace_rule.hpp"
 #include "compact.hpp"
 
 using namespace amdr;
@@ -194,10 +208,104 @@ __global__ __launch_bounds__(kBmTileThreads) void bm25_rm_scatter_kernel(
   }
 }
 
+// ---- amdr_bm25_replace: document map, the remove's tile ranks, term table, two scatters ---------------------------------
+__global__ __launch_bounds__(256) void bm25_rp_docmap_kernel(const long long* __restrict__ replace_ids, long n_rep,
+                                                             const int* __restrict__ doc_len_old,
+                                                             const int* __restrict__ doc_len_add, long n_docs,
+                                                             int* __restrict__ doc_keep, int* __restrict__ doc_len_new) {
+  const long d = (long)blockIdx.x * 256 + threadIdx.x;
+  if (d < n_docs) bm_rp_doc_entry(replace_ids, n_rep, doc_len_old, doc_len_add, d, doc_keep, doc_len_new);
+}
+
+__global__ __launch_bounds__(256) void bm25_rp_terms_kernel(const long long* __restrict__ old_ptr, long n_terms_old,
+                                                            long n_terms_new, long long nnz_old,
+                                                            const long long* __restrict__ tile_base,
+                                                            const unsigned short* __restrict__ tile_rank,
+                                                            const int* __restrict__ term_map, const int* __restrict__ inv,
+                                                            const long long* __restrict__ add_ptr,
+                                                            long long* __restrict__ rank_at, long long* __restrict__ df_new,
+                                                            int* __restrict__ bad) {
+  const long e = (long)blockIdx.x * 256 + threadIdx.x;
+  bm_rp_term_entry(e, n_terms_old, n_terms_new, old_ptr, nnz_old, tile_base, tile_rank, term_map, inv, add_ptr, rank_at,
+                   df_new, bad);
+}
+
+// One block = one tile of OLD postings, their terms found in the OLD term table: bm25_rm_scatter_kernel with the add
+// postings of the term's new list counted in (one binary search in that list, skipped where it is empty).  A surviving
+// posting reads 8 B (doc, tf) + 2 B of rank, gathers doc_keep and doc_len, and writes 16 B at bm_rp_dest_old.
+__global__ __launch_bounds__(kBmTileThreads) void bm25_rp_scatter_old_kernel(
+    const long long* __restrict__ old_ptr, long n_terms_old, const int* __restrict__ old_doc, const int* __restrict__ old_tf,
+    long long nnz_old, const int* __restrict__ doc_keep, const int* __restrict__ doc_len /* new */,
+    const long long* __restrict__ tile_base, const unsigned short* __restrict__ tile_rank,
+    const long long* __restrict__ rank_at, const long long* __restrict__ new_ptr, const int* __restrict__ term_map,
+    const long long* __restrict__ add_ptr, const int* __restrict__ add_doc, const long long* __restrict__ replace_ids,
+    long long nnz_new, double avgdl, double k1, double b, int* __restrict__ out_doc, int* __restrict__ out_tf,
+    double* __restrict__ out_w) {
+  __shared__ long long win[kBmTile + 2];
+  const long long p0 = (long long)blockIdx.x * kBmTile;
+  long long p1 = p0 + kBmTile;  // exclusive
+  if (p1 > nnz_old) p1 = nnz_old;
+  if (p0 >= p1) return;
+  const BmTileWindow w = bm_tile_window(old_ptr, n_terms_old, p0, p1, win);
+  const int tid = threadIdx.x;
+#pragma unroll
+  for (int u = 0; u < kBmTilePerThread; ++u) {
+    const long long p = p0 + (long long)u * kBmTileThreads + tid;
+    if (p < p1) {
+      const int doc = doc_keep[old_doc[p]];
+      if (doc >= 0) {
+        const long long dst = bm_rp_dest_old(p, doc, w.term_of(p), nnz_old, tile_base, tile_rank, rank_at, new_ptr, term_map,
+                                             add_ptr, add_doc, replace_ids);
+        if (dst >= 0 && dst < nnz_new) {  // (always, after the host's checks and the terms kernel's flag)
+          const int tf = old_tf[p];
+          out_doc[dst] = doc;
+          out_tf[dst] = tf;
+          out_w[dst] = bm25_factor(tf, doc_len[doc], avgdl, k1, b);
+        }
+      }
+    }
+  }
+}
+
+// One block = one tile of the ADD's postings, their terms found in the add's own term table (over the new ids).  A posting
+// reads 8 B (local doc, tf) and its document id, searches its term's OLD list for that document (bm_rp_dest_add) and
+// writes 16 B.
+__global__ __launch_bounds__(kBmTileThreads) void bm25_rp_scatter_add_kernel(
+    const long long* __restrict__ add_ptr, long n_terms_new, const int* __restrict__ add_doc, const int* __restrict__ add_tf,
+    long long nnz_add, const long long* __restrict__ replace_ids, const int* __restrict__ inv,
+    const long long* __restrict__ old_ptr, const int* __restrict__ old_doc, long long nnz_old,
+    const long long* __restrict__ tile_base, const unsigned short* __restrict__ tile_rank,
+    const long long* __restrict__ rank_at, const long long* __restrict__ new_ptr, const int* __restrict__ doc_len /* new */,
+    long long nnz_new, double avgdl, double k1, double b, int* __restrict__ out_doc, int* __restrict__ out_tf,
+    double* __restrict__ out_w) {
+  __shared__ long long win[kBmTile + 2];
+  const long long p0 = (long long)blockIdx.x * kBmTile;
+  long long p1 = p0 + kBmTile;  // exclusive
+  if (p1 > nnz_add) p1 = nnz_add;
+  if (p0 >= p1) return;
+  const BmTileWindow w = bm_tile_window(add_ptr, n_terms_new, p0, p1, win);
+  const int tid = threadIdx.x;
+#pragma unroll
+  for (int u = 0; u < kBmTilePerThread; ++u) {
+    const long long q = p0 + (long long)u * kBmTileThreads + tid;
+    if (q < p1) {
+      const long long doc = replace_ids[add_doc[q]];
+      const long long dst = bm_rp_dest_add(q, doc, w.term_of(q), inv, old_ptr, old_doc, nnz_old, tile_base, tile_rank, rank_at,
+                                           new_ptr, add_ptr);
+      if (dst >= 0 && dst < nnz_new) {  // (always, after the host's checks)
+        const int tf = add_tf[q];
+        out_doc[dst] = (int)doc;
+        out_tf[dst] = tf;
+        out_w[dst] = bm25_factor(tf, doc_len[doc], avgdl, k1, b);
+      }
+    }
+  }
+}
+
 // ---- host: per-call scratch and the kernel timer ---------------------------------------------------------------------
 // Typed device arrays that live for one call: freed on return.  (Not DevBuf: a call's scratch is no workspace growth.)
 struct BmScratch {
-  void* held[12] = {};
+  void* held[16] = {};
   int n = 0;
   BmScratch() = default;
   BmScratch(const BmScratch&) = delete;
@@ -395,6 +503,126 @@ int amdr_bm25_remove(amdr_bm25_t* h, const int64_t* remove_ids, int64_t n_remove
   AMDR_HIP(hipStreamSynchronize(st));
   h->remove_kernel_ms = timer.ms();
   nx.commit(h->ix, h->removes);  // from here on nothing can fail
+  return AMDR_OK;
+}
+
+int amdr_bm25_replace(amdr_bm25_t* h, const int64_t* replace_ids, int64_t n_rep, const int64_t* term_ptr_add,
+                      const int32_t* post_doc_add, const int32_t* post_tf_add, const int32_t* doc_len_add,
+                      const int32_t* term_map, int64_t n_terms_new, const double* idf, double avgdl) {
+  static const char* const who = "bm25_replace";
+  AMDR_REQUIRE(h != nullptr, "bm25_replace: null handle");
+  AMDR_REQUIRE(n_rep >= 0, "bm25_replace: n_rep=%lld", (long long)n_rep);
+  if (n_rep == 0) return AMDR_OK;
+  std::lock_guard<std::mutex> g(h->mu);
+  const BmIndex& old = h->ix;
+  AMDR_REQUIRE(n_terms_new >= 0 && n_terms_new < (1ll << 31), "bm25_replace: n_terms_new=%lld", (long long)n_terms_new);
+  std::unique_ptr<int32_t[]> inv(new (std::nothrow) int32_t[(size_t)n_terms_new + 1]);
+  if (!inv) return fail(AMDR_ENOMEM, "bm25_replace: no host memory for the inverse term map");
+  const int bad = bm_rp_validate(replace_ids, n_rep, term_ptr_add, post_doc_add, post_tf_add, doc_len_add, term_map,
+                                 n_terms_new, idf, avgdl, old.n_terms, old.n_docs, inv.get());
+  AMDR_REQUIRE(bad == kBmRpOk, "bm25_replace: %s", bm_rp_error_text(bad));
+  AMDR_HIP(hipSetDevice(h->device));
+  const int64_t V_old = old.n_terms, V_new = n_terms_new, nnz_old = old.nnz, n = old.n_docs, nnz_add = term_ptr_add[V_new];
+  const long long tiles = (nnz_old + kBmTile - 1) / kBmTile, add_tiles = (nnz_add + kBmTile - 1) / kBmTile;
+  AMDR_REQUIRE(tiles < (1ll << 31) && add_tiles < (1ll << 31), "bm25_replace: %lld + %lld postings exceed the grid",
+               (long long)nnz_old, (long long)nnz_add);
+  BmStagedIndex nx;
+  AMDR_TRY(nx.alloc_tables(V_new, n, avgdl, who));
+  BmScratch tmp;
+  long long *rp_ids, *tile_cnt, *tile_base, *rank_at, *df_new, *add_ptr;
+  int *doc_keep, *map_dev = nullptr, *inv_dev, *flag_dev, *add_doc, *add_tf, *add_len;
+  unsigned short* tile_rank;
+  AMDR_TRY(tmp.alloc(&rp_ids, (size_t)n_rep, who));
+  AMDR_TRY(tmp.alloc(&doc_keep, (size_t)n, who));
+  AMDR_TRY(tmp.alloc(&tile_rank, (size_t)nnz_old + 1, who));  // (+ 1: never an empty allocation)
+  AMDR_TRY(tmp.alloc(&tile_cnt, (size_t)tiles + 1, who));
+  AMDR_TRY(tmp.alloc(&tile_base, (size_t)tiles + 1, who));
+  AMDR_TRY(tmp.alloc(&rank_at, (size_t)V_old + 1, who));
+  AMDR_TRY(tmp.alloc(&df_new, (size_t)V_new + 1, who));
+  if (term_map) AMDR_TRY(tmp.alloc(&map_dev, (size_t)V_old + 1, who));
+  AMDR_TRY(tmp.alloc(&inv_dev, (size_t)V_new + 1, who));
+  AMDR_TRY(tmp.alloc(&flag_dev, 1, who));
+  AMDR_TRY(tmp.alloc(&add_ptr, (size_t)V_new + 1, who));
+  AMDR_TRY(tmp.alloc(&add_doc, (size_t)nnz_add + 1, who));
+  AMDR_TRY(tmp.alloc(&add_tf, (size_t)nnz_add + 1, who));
+  AMDR_TRY(tmp.alloc(&add_len, (size_t)n_rep, who));
+  hipStream_t st = h->stream;
+  AMDR_HIP(hipMemcpyAsync(rp_ids, replace_ids, (size_t)n_rep * sizeof(long long), hipMemcpyHostToDevice, st));
+  AMDR_HIP(hipMemcpyAsync(add_len, doc_len_add, (size_t)n_rep * sizeof(int), hipMemcpyHostToDevice, st));
+  AMDR_HIP(hipMemcpyAsync(add_ptr, term_ptr_add, (size_t)(V_new + 1) * sizeof(long long), hipMemcpyHostToDevice, st));
+  if (nnz_add) {
+    AMDR_HIP(hipMemcpyAsync(add_doc, post_doc_add, (size_t)nnz_add * sizeof(int), hipMemcpyHostToDevice, st));
+    AMDR_HIP(hipMemcpyAsync(add_tf, post_tf_add, (size_t)nnz_add * sizeof(int), hipMemcpyHostToDevice, st));
+  }
+  if (term_map && V_old) AMDR_HIP(hipMemcpyAsync(map_dev, term_map, (size_t)V_old * sizeof(int), hipMemcpyHostToDevice, st));
+  if (V_new) {
+    AMDR_HIP(hipMemcpyAsync(inv_dev, inv.get(), (size_t)V_new * sizeof(int), hipMemcpyHostToDevice, st));
+    AMDR_HIP(hipMemcpyAsync(nx.idf, idf, (size_t)V_new * sizeof(double), hipMemcpyHostToDevice, st));
+  }
+  AMDR_HIP(hipMemsetAsync(flag_dev, 0, sizeof(int), st));
+  // the passes in two stretches, with the host's look at nnz_new between them (amdr_bm25_replace_kernel_ms)
+  BmSpans timer(2);
+  AMDR_TRY(timer.begin(0, st));
+  hipLaunchKernelGGL(bm25_rp_docmap_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, rp_ids, (long)n_rep,
+                     old.doc_len, add_len, (long)n, doc_keep, nx.doc_len);
+  AMDR_HIP(hipGetLastError());
+  if (tiles > 0) {  // the remove's counting pass: doc_keep is its document map
+    hipLaunchKernelGGL(bm25_rm_count_kernel, dim3((unsigned)tiles), dim3(kBmTileThreads), 0, st, old.post_doc,
+                       (long long)nnz_old, doc_keep, tile_rank, tile_cnt);
+    AMDR_HIP(hipGetLastError());
+  }
+  hipLaunchKernelGGL(compact_scan_i64_kernel, dim3(1), dim3(kCompactScanThreads), 0, st, tile_cnt, (long)tiles, tile_base);
+  AMDR_HIP(hipGetLastError());
+  const int64_t entries = V_old + 1 > V_new ? V_old + 1 : V_new;
+  hipLaunchKernelGGL(bm25_rp_terms_kernel, dim3((unsigned)((entries + 255) / 256)), dim3(256), 0, st, old.term_ptr,
+                     (long)V_old, (long)V_new, (long long)nnz_old, tile_base, tile_rank, map_dev, inv_dev, add_ptr, rank_at,
+                     df_new, flag_dev);
+  AMDR_HIP(hipGetLastError());
+  hipLaunchKernelGGL(compact_scan_i64_kernel, dim3(1), dim3(kCompactScanThreads), 0, st, df_new, (long)V_new, nx.term_ptr);
+  AMDR_HIP(hipGetLastError());
+  AMDR_TRY(timer.end(0, st));
+  long long kept = 0;
+  int flag = 0;
+  AMDR_HIP(hipMemcpyAsync(&kept, tile_base + tiles, sizeof(long long), hipMemcpyDeviceToHost, st));
+  AMDR_HIP(hipMemcpyAsync(&flag, flag_dev, sizeof(int), hipMemcpyDeviceToHost, st));
+  AMDR_HIP(hipStreamSynchronize(st));
+  AMDR_REQUIRE(flag == 0, "bm25_replace: a term mapped to -1 still has a surviving posting");
+  if (kept < 0 || kept > nnz_old) return fail(AMDR_EHIP, "bm25_replace: counted %lld of %lld postings", kept, (long long)nnz_old);
+  const long long nnz_new = kept + nnz_add;
+  AMDR_TRY(nx.alloc_postings(nnz_new, who));
+  AMDR_TRY(timer.begin(1, st));
+  if (tiles > 0 && kept > 0) {
+    hipLaunchKernelGGL(bm25_rp_scatter_old_kernel, dim3((unsigned)tiles), dim3(kBmTileThreads), 0, st, old.term_ptr,
+                       (long)V_old, old.post_doc, old.post_tf, (long long)nnz_old, doc_keep, nx.doc_len, tile_base, tile_rank,
+                       rank_at, nx.term_ptr, map_dev, add_ptr, add_doc, rp_ids, nnz_new, avgdl, h->k1, h->b, nx.post_doc,
+                       nx.post_tf, nx.post_w);
+    AMDR_HIP(hipGetLastError());
+  }
+  if (add_tiles > 0) {
+    hipLaunchKernelGGL(bm25_rp_scatter_add_kernel, dim3((unsigned)add_tiles), dim3(kBmTileThreads), 0, st, add_ptr,
+                       (long)V_new, add_doc, add_tf, (long long)nnz_add, rp_ids, inv_dev, old.term_ptr, old.post_doc,
+                       (long long)nnz_old, tile_base, tile_rank, rank_at, nx.term_ptr, nx.doc_len, nnz_new, avgdl, h->k1,
+                       h->b, nx.post_doc, nx.post_tf, nx.post_w);
+    AMDR_HIP(hipGetLastError());
+  }
+  AMDR_TRY(timer.end(1, st));
+  AMDR_HIP(hipStreamSynchronize(st));
+  h->replace_kernel_ms = timer.ms();
+  nx.commit(h->ix, h->replaces);  // from here on nothing can fail
+  return AMDR_OK;
+}
+
+int amdr_bm25_replace_kernel_ms(amdr_bm25_t* h, double* ms) {
+  AMDR_REQUIRE(h && ms, "bm25_replace_kernel_ms: null");
+  std::lock_guard<std::mutex> g(h->mu);
+  *ms = h->replace_kernel_ms;
+  return AMDR_OK;
+}
+
+int amdr_bm25_replaces(amdr_bm25_t* h, int64_t* n) {
+  AMDR_REQUIRE(h && n, "bm25_replaces: null");
+  std::lock_guard<std::mutex> g(h->mu);
+  *n = h->replaces;
   return AMDR_OK;
 }
 

@@ -212,6 +212,17 @@ int segments_ptr_launch(const long long* doc_ptr, long n_docs_new, const long lo
 // the 512-byte token rows of the surviving documents, rows_new = new_ptr[n_docs_new] of them
 int segments_compact_launch(const void* src, long long rows_new, const long long* new_ptr, const long long* start,
                             long n_docs_new, void* dst, hipStream_t st);
+// the replaces (amdr_dense_replace, amdr_maxsim_replace; replace_ids / add_ptr are DEVICE copies of validated lists):
+// staged row i of n_rep -> row replace_ids[i] of dst, in place
+int rows_scatter_launch(const void* rows, long long n_rep, long row_bytes, const long long* replace_ids, void* dst,
+                        hipStream_t st);
+// the doc_ptr of the edited store: len / start [n_docs] scratch (start signed: >= 0 an old row, < 0 staged row ~start),
+// new_ptr [n_docs + 1] the exclusive scan of len
+int splice_ptr_launch(const long long* doc_ptr, long n_docs, const long long* add_ptr, const long long* replace_ids,
+                      long n_rep, long long* len, long long* start, long long* new_ptr, hipStream_t st);
+// the 512-byte token rows of the edited store, each from old_rows or add_rows
+int segments_splice_launch(const void* old_rows, const void* add_rows, long long rows_new, const long long* new_ptr,
+                           const long long* start, long n_docs, void* dst, hipStream_t st);
 
 // ---- long-batch dense path: dense_panel.hip (panel of chunk rows shared by a block through LDS) ----
 struct DensePanelPlan {

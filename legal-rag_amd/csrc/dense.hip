@@ -197,6 +197,7 @@ struct amdr_dense {
   int64_t img_cap_rows = 0, img_rows = 0;
   float img_scale = 0.f;
   double remove_kernel_ms = -1.0;  // device time of the compaction kernel of the last successful amdr_dense_remove
+  double replace_kernel_ms = -1.0;  // device time of the scatter kernel of the last successful amdr_dense_replace
   // optional HIP-event ring bracketing the scan kernel alone (bench.py roofline)
   std::vector<hipEvent_t> prof_ev;
   int prof_used = 0;
@@ -873,6 +874,29 @@ int update_stats(amdr_dense* h, int64_t row0, int64_t rows) {
   return AMDR_OK;
 }
 
+// Rows were removed or replaced, so the statistics are about to be taken again from zero (the largest component and row
+// norm can fall): the short-corpus fp16 image is of the old matrix and is made again on demand; what the fp16 first pass
+// learnt starts over, as in amdr_dense_add — and since the statistics words are made again from zero, the device's
+// counters and the host's view of them start from zero too.
+void first_pass_start_over(amdr_dense* h) {
+  if (h->small) {
+    (void)hipDeviceSynchronize();
+    (void)amdr_dense_small_destroy(h->small);
+    h->small = nullptr;
+  }
+  h->small_failed = false;
+  h->hi_level = 0;
+  h->hi_off = false;
+  if (h->hi_copy_pending) {
+    (void)hipEventSynchronize(h->hi_ev);
+    h->hi_copy_pending = false;
+  }
+  for (int i = 0; i < 3; ++i) h->hi_seen[i] = 0u;
+  h->lvl_f0 = 0u;
+  h->lvl_p0 = 0;
+  h->hi_queries = h->hi_passes = 0;
+}
+
 void image_drop(amdr_dense* h) {
   if (h->img) (void)hipFree(h->img);  // (waits for the device: no scan is reading it any more)
   h->img = nullptr;
@@ -1079,28 +1103,11 @@ int amdr_dense_remove(amdr_dense_t* h, const int64_t* remove_ids, int64_t n_remo
     }
   }
   // the swap (hipFree waits for the device: host-pointer searches are behind h->mu, "_device" work is the caller's to order)
-  if (h->small) {  // the short-corpus fp16 image is of the old matrix: made again on demand
-    (void)hipDeviceSynchronize();
-    (void)amdr_dense_small_destroy(h->small);
-    h->small = nullptr;
-  }
-  h->small_failed = false;
+  first_pass_start_over(h);
   if (h->X) (void)hipFree(h->X);
   h->X = nx;
   h->n = h->cap_rows = n_new;
   h->remove_kernel_ms = (double)ms;
-  // the matrix changed: what the fp16 first pass learnt about it starts over, as in amdr_dense_add — and since the
-  // statistics words are made again from zero, the device's counters and the host's view of them start from zero too
-  h->hi_level = 0;
-  h->hi_off = false;
-  if (h->hi_copy_pending) {
-    (void)hipEventSynchronize(h->hi_ev);
-    h->hi_copy_pending = false;
-  }
-  for (int i = 0; i < 3; ++i) h->hi_seen[i] = 0u;
-  h->lvl_f0 = 0u;
-  h->lvl_p0 = 0;
-  h->hi_queries = h->hi_passes = 0;
   rc = update_stats(h, 0, n_new);
   // a handle with an fp16 image keeps one: of the compacted matrix, whose rows sit in other 32-row tiles now
   if (h->img) {
@@ -1114,6 +1121,73 @@ int amdr_dense_remove_kernel_ms(amdr_dense_t* h, double* ms) {
   AMDR_REQUIRE(h && ms, "dense_remove_kernel_ms: null");
   std::lock_guard<std::mutex> g(h->mu);
   *ms = h->remove_kernel_ms;
+  return AMDR_OK;
+}
+
+// Replace rows in place.  Everything that can run out of memory or be refused — the staged rows and ids, their copies,
+// the events — has happened and has been waited for before the scatter kernel (rows_compact.hip) is enqueued; until then
+// the matrix is untouched.  Then what remove does after its swap: the statistics from zero, and a present image brought
+// up to the matrix from the first touched 32-row tile on (image_sync converts all of it when the scale changed).
+int amdr_dense_replace(amdr_dense_t* h, const int64_t* replace_ids, const float* X_host, int64_t n_rep) {
+  AMDR_REQUIRE(h != nullptr, "dense_replace: null handle");
+  AMDR_REQUIRE(h->owns, "dense_replace: handle wraps caller-owned memory");
+  AMDR_REQUIRE(n_rep >= 0, "dense_replace: n_rep=%lld", (long long)n_rep);
+  if (n_rep == 0) return AMDR_OK;
+  AMDR_REQUIRE(X_host != nullptr, "dense_replace: X is null");
+  std::lock_guard<std::mutex> g(h->mu);
+  const int bad = rc_validate(replace_ids, n_rep, h->n);
+  AMDR_REQUIRE(bad == kRcOk, "dense_replace: %s", rs_error_text(bad));
+  AMDR_HIP(hipSetDevice(h->device));
+  const size_t row_bytes = (size_t)h->d * sizeof(float);
+  float* rows = nullptr;
+  long long* ids = nullptr;
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  hipError_t e = hipMalloc((void**)&ids, (size_t)n_rep * sizeof(long long));
+  if (e == hipSuccess) e = hipMalloc((void**)&rows, (size_t)n_rep * row_bytes);
+  if (e == hipSuccess) e = hipMemcpyAsync(ids, replace_ids, (size_t)n_rep * sizeof(long long), hipMemcpyHostToDevice, h->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(rows, X_host, (size_t)n_rep * row_bytes, hipMemcpyHostToDevice, h->stream);
+  if (e == hipSuccess) e = hipEventCreate(&ev[0]);
+  if (e == hipSuccess) e = hipEventCreate(&ev[1]);
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);  // the staged copies are whole; the matrix is still the old one
+  auto release = [&]() {
+    for (hipEvent_t v : ev)
+      if (v) (void)hipEventDestroy(v);
+    if (ids) (void)hipFree(ids);
+    if (rows) (void)hipFree(rows);
+  };
+  if (e != hipSuccess) {
+    release();
+    return fail(e == hipErrorOutOfMemory ? AMDR_ENOMEM : AMDR_EHIP, "dense_replace: %s", hipGetErrorString(e));
+  }
+  float ms = 0.f;
+  e = hipEventRecord(ev[0], h->stream);
+  int rc = e == hipSuccess ? rows_scatter_launch(rows, (long long)n_rep, (long)row_bytes, ids, h->X, h->stream) : AMDR_OK;
+  if (e != hipSuccess || rc != AMDR_OK) {  // (nothing was enqueued: the launcher checks its arguments before it launches)
+    release();
+    return rc != AMDR_OK ? rc : fail(AMDR_EHIP, "dense_replace: %s", hipGetErrorString(e));
+  }
+  // from here on the matrix is the edited one; a device error below is reported, and the handle describes that matrix
+  e = hipEventRecord(ev[1], h->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+  if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev[0], ev[1]);
+  release();
+  first_pass_start_over(h);
+  h->replace_kernel_ms = e == hipSuccess ? (double)ms : -1.0;
+  rc = update_stats(h, 0, h->n);
+  if (h->img) {
+    if (rc == AMDR_OK && e == hipSuccess && h->fp16.large_scan_ok())
+      rc = image_sync(h, replace_ids[0] / kHiTileRows * kHiTileRows);
+    else
+      image_drop(h);  // (no first pass is left to read it)
+  }
+  if (rc == AMDR_OK && e != hipSuccess) rc = fail(AMDR_EHIP, "dense_replace: %s", hipGetErrorString(e));
+  return rc;
+}
+
+int amdr_dense_replace_kernel_ms(amdr_dense_t* h, double* ms) {
+  AMDR_REQUIRE(h && ms, "dense_replace_kernel_ms: null");
+  std::lock_guard<std::mutex> g(h->mu);
+  *ms = h->replace_kernel_ms;
   return AMDR_OK;
 }
 

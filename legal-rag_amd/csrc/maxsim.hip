@@ -986,6 +986,7 @@ struct amdr_maxsim {
   unsigned int amax_bits = 0;    // largest |component| of the store as float bits (what d_scale was taken from)
   int64_t conversions = 0;       // whole-store conversions to the images so far (amdr_maxsim_info)
   double remove_kernel_ms = -1.0;  // device time of the doc_ptr rebuild + the compaction of the last successful amdr_maxsim_remove
+  double replace_kernel_ms = -1.0;  // device time of the doc_ptr rebuild + the splice of the last successful amdr_maxsim_replace
   long long* doc_ptr = nullptr;
   int cus = 0;  // compute units of `device` (the re-scoring pass's grid)
   hipStream_t stream = nullptr;
@@ -1517,6 +1518,111 @@ int amdr_maxsim_remove_kernel_ms(amdr_maxsim_t* h, double* ms) {
   AMDR_REQUIRE(h && ms, "maxsim_remove_kernel_ms: null");
   std::lock_guard<std::mutex> g(h->mu);
   *ms = h->remove_kernel_ms;
+  return AMDR_OK;
+}
+
+// Replace documents under their pids.  amdr_maxsim_remove with a second source: the new token rows and their doc_ptr are
+// staged on the device, the new doc_ptr and the spliced D (rows_compact.hip) are built in new buffers, then create()'s own
+// sequence runs on the new D.  The handle's fields change together at the end; until then every search reads the old store.
+int amdr_maxsim_replace(amdr_maxsim_t* h, const int64_t* replace_ids, const float* D_host, const int64_t* doc_ptr_add,
+                        int64_t n_rep) {
+  AMDR_REQUIRE(h != nullptr, "maxsim_replace: null handle");
+  AMDR_REQUIRE(n_rep >= 0, "maxsim_replace: n_rep=%lld", (long long)n_rep);
+  if (n_rep == 0) return AMDR_OK;
+  AMDR_REQUIRE(D_host && doc_ptr_add, "maxsim_replace: null D / doc_ptr");
+  std::lock_guard<std::mutex> g(h->mu);
+  const int bad = rc_validate(replace_ids, n_rep, h->n_docs);  // (n_rep <= n_docs, before doc_ptr_add is walked)
+  AMDR_REQUIRE(bad == kRcOk, "maxsim_replace: %s", rs_error_text(bad));
+  AMDR_REQUIRE(doc_ptr_add[0] == 0, "maxsim_replace: doc_ptr[0] != 0");
+  for (int64_t i = 0; i < n_rep; ++i)
+    AMDR_REQUIRE(doc_ptr_add[i + 1] > doc_ptr_add[i], "maxsim_replace: document %lld has no tokens", (long long)i);
+  AMDR_HIP(hipSetDevice(h->device));
+  const int64_t nd = h->n_docs, t_add = doc_ptr_add[n_rep];
+  long long *ids = nullptr, *add_ptr = nullptr, *len = nullptr, *start = nullptr, *dp = nullptr;
+  float *add_rows = nullptr, *D = nullptr;
+  unsigned char *img = nullptr, *img_hi = nullptr;
+  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  long long t1 = 0;
+  int rc = AMDR_OK;
+  hipStream_t st = h->stream;
+  hipError_t e = hipMalloc((void**)&ids, (size_t)n_rep * sizeof(long long));
+  if (e == hipSuccess) e = hipMalloc((void**)&add_ptr, (size_t)(n_rep + 1) * sizeof(long long));
+  if (e == hipSuccess) e = hipMalloc((void**)&add_rows, (size_t)t_add * kDim * sizeof(float));
+  if (e == hipSuccess) e = hipMalloc((void**)&len, (size_t)nd * sizeof(long long));
+  if (e == hipSuccess) e = hipMalloc((void**)&start, (size_t)nd * sizeof(long long));
+  if (e == hipSuccess) e = hipMalloc((void**)&dp, (size_t)(nd + 1) * sizeof(long long));
+  for (int i = 0; i < 4 && e == hipSuccess; ++i) e = hipEventCreate(&ev[i]);
+  if (e == hipSuccess) e = hipMemcpyAsync(ids, replace_ids, (size_t)n_rep * sizeof(long long), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(add_ptr, doc_ptr_add, (size_t)(n_rep + 1) * sizeof(long long), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(add_rows, D_host, (size_t)t_add * kDim * sizeof(float), hipMemcpyHostToDevice, st);
+  // the doc_ptr rebuild, then the host's look at the new token count
+  if (e == hipSuccess) e = hipEventRecord(ev[0], st);
+  if (e == hipSuccess) rc = splice_ptr_launch(h->doc_ptr, (long)nd, add_ptr, ids, (long)n_rep, len, start, dp, st);
+  if (e == hipSuccess && rc == AMDR_OK) e = hipEventRecord(ev[1], st);
+  if (e == hipSuccess && rc == AMDR_OK) e = hipMemcpyAsync(&t1, dp + nd, sizeof(long long), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess && rc == AMDR_OK) e = hipStreamSynchronize(st);
+  if (e == hipSuccess && rc == AMDR_OK && (t1 < nd || t1 < t_add || t1 - t_add > h->n_tokens - n_rep))
+    rc = fail(AMDR_EHIP, "maxsim_replace: counted %lld token rows from %lld old and %lld new", t1, (long long)h->n_tokens,
+              (long long)t_add);
+  // the token rows
+  if (e == hipSuccess && rc == AMDR_OK) e = hipMalloc((void**)&D, (size_t)t1 * kDim * sizeof(float));
+  if (e == hipSuccess && rc == AMDR_OK) e = hipEventRecord(ev[2], st);
+  if (e == hipSuccess && rc == AMDR_OK) rc = segments_splice_launch(h->D, add_rows, t1, dp, start, (long)nd, D, st);
+  if (e == hipSuccess && rc == AMDR_OK) e = hipEventRecord(ev[3], st);
+  if (e == hipSuccess && rc == AMDR_OK) e = hipStreamSynchronize(st);
+  float ms0 = 0.f, ms1 = 0.f;
+  if (e == hipSuccess && rc == AMDR_OK) e = hipEventElapsedTime(&ms0, ev[0], ev[1]);
+  if (e == hipSuccess && rc == AMDR_OK) e = hipEventElapsedTime(&ms1, ev[2], ev[3]);
+  // exactly create()'s sequence on the new D
+  unsigned int amax = 0;
+  float scale = 1.f, norm_max = 0.f;
+  int64_t conversions = h->conversions;
+  if (e == hipSuccess && rc == AMDR_OK) e = ms_absmax(D, 0, t1, &amax);
+  if (e == hipSuccess && rc == AMDR_OK && amax < 0x7f800000u) {
+    scale = ms_scale_of(amax);
+    e = ms_alloc_images(t1, &img, &img_hi);
+    if (e == hipSuccess) e = ms_convert(D, 0, t1, scale, img, img_hi, &norm_max);
+    ++conversions;
+  }
+  if (e == hipSuccess && rc == AMDR_OK) e = hipDeviceSynchronize();
+  for (hipEvent_t v : ev)
+    if (v) (void)hipEventDestroy(v);
+  if (ids) (void)hipFree(ids);
+  if (add_ptr) (void)hipFree(add_ptr);
+  if (add_rows) (void)hipFree(add_rows);
+  if (len) (void)hipFree(len);
+  if (start) (void)hipFree(start);
+  if (e != hipSuccess || rc != AMDR_OK) {
+    if (dp) (void)hipFree(dp);
+    if (D) (void)hipFree(D);
+    if (img) (void)hipFree(img);
+    if (img_hi) (void)hipFree(img_hi);
+    if (rc != AMDR_OK) return rc;
+    return fail(e == hipErrorOutOfMemory ? AMDR_ENOMEM : AMDR_EHIP, "maxsim_replace: %s", hipGetErrorString(e));
+  }
+  // the swap (hipFree waits for the device: host-pointer searches are behind h->mu, "_device" work is the caller's to order)
+  (void)hipFree(h->D);
+  (void)hipFree(h->doc_ptr);
+  if (h->img) (void)hipFree(h->img);
+  if (h->img_hi) (void)hipFree(h->img_hi);
+  h->D = D;
+  h->doc_ptr = dp;
+  h->img = img;
+  h->img_hi = img_hi;
+  h->cap_tokens = h->n_tokens = t1;
+  h->cap_docs = nd;
+  h->amax_bits = amax;
+  h->d_scale = scale;
+  h->d_norm_max = norm_max;
+  h->conversions = conversions;
+  h->replace_kernel_ms = (double)ms0 + (double)ms1;
+  return AMDR_OK;
+}
+
+int amdr_maxsim_replace_kernel_ms(amdr_maxsim_t* h, double* ms) {
+  AMDR_REQUIRE(h && ms, "maxsim_replace_kernel_ms: null");
+  std::lock_guard<std::mutex> g(h->mu);
+  *ms = h->replace_kernel_ms;
   return AMDR_OK;
 }
 

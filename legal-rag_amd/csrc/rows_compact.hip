@@ -6,6 +6,10 @@
 //   segments_len_kernel      new document j -> its length and the old row its rows start at        } the doc_ptr rebuild
 //   compact_scan_i64_kernel  (compact.hpp) the exclusive scan of the lengths = the new doc_ptr     }
 //   segments_compact_kernel  token rows of 512 B under the segmented map (the MaxSim store)
+// and of the replaces (documents keep their ids; the rule is rows_compact.hpp's rs_*):
+//   rows_scatter_kernel      staged rows written over rows replace_ids[i] of the dense matrix, in place
+//   splice_len_kernel        document j -> its length afterwards and its signed source row        } + the same scan
+//   segments_splice_kernel   token rows of 512 B, each from the old store or from the staged rows, into a new buffer
 //
 // Both copy kernels move 16-byte units.  A block owns a slab of kRcSlabUnits consecutive NEW units (whole rows: 32 KiB or
 // a little less), first writes the old row of each of the slab's rows into LDS — every thread a run of consecutive rows:
@@ -95,6 +99,64 @@ __global__ __launch_bounds__(kRcThreads) void segments_compact_kernel(const uint
   }
 }
 
+// ---- replace: rows exchanged under unchanged ids (amdr_dense_replace, amdr_maxsim_replace) ----------------------------
+// The dense form writes IN PLACE: staged row i goes to row replace_ids[i] of the matrix, nothing else moves.  Unit u of
+// the staged rows (consecutive, so a wave loads 1 KiB per instruction) has one destination and one writer — the ids are
+// strictly ascending — so there is nothing to order.  Traffic: every replaced byte read once and written once + 8 B an id.
+__global__ __launch_bounds__(kRcThreads) void rows_scatter_kernel(const uint4* __restrict__ rows, long long units,
+                                                                  int units_per_row,
+                                                                  const long long* __restrict__ replace_ids,
+                                                                  uint4* __restrict__ dst) {
+  const long long step = (long long)gridDim.x * kRcThreads;
+#pragma unroll 1
+  for (long long u = (long long)blockIdx.x * kRcThreads + threadIdx.x; u < units; u += step) {
+    const long long i = u / units_per_row;
+    dst[replace_ids[i] * units_per_row + (u - i * units_per_row)] = rows[u];
+  }
+}
+
+// Document j of n_docs (the count does not change): its length afterwards and the signed source row its rows start at.
+__global__ __launch_bounds__(256) void splice_len_kernel(const long long* __restrict__ doc_ptr, long n_docs,
+                                                         const long long* __restrict__ add_ptr,
+                                                         const long long* __restrict__ replace_ids, long n_rep,
+                                                         long long* __restrict__ len, long long* __restrict__ start) {
+  const long j = (long)blockIdx.x * 256 + threadIdx.x;
+  if (j >= n_docs) return;
+  rs_seg_entry(doc_ptr, add_ptr, replace_ids, n_rep, j, &len[j], &start[j]);
+}
+
+// The ordered splice of 512-byte token rows into a NEW buffer: segments_compact_kernel with two sources.  A slab's rows
+// get their signed source row in LDS (rs_seg_src), then every unit is loaded from the old store or from the staged rows
+// and stored to its consecutive destination, one unit per thread and step as in rc_copy_slab.
+__global__ __launch_bounds__(kRcThreads) void segments_splice_kernel(const uint4* __restrict__ old_rows,
+                                                                     const uint4* __restrict__ add_rows, long long rows_new,
+                                                                     long long slabs, const long long* __restrict__ new_ptr,
+                                                                     const long long* __restrict__ start, long n_docs,
+                                                                     uint4* __restrict__ dst) {
+  __shared__ long long row_src[kSegSlabRows];
+  for (long long slab = blockIdx.x; slab < slabs; slab += gridDim.x) {
+    const long long t0 = slab * kSegSlabRows;
+    const int rows = (int)(rows_new - t0 < kSegSlabRows ? rows_new - t0 : kSegSlabRows);
+    const int a = (int)threadIdx.x * kSegRun;
+    if (a < rows) {
+      long j = rc_seg_doc(new_ptr, n_docs, t0 + a);
+      for (int i = 0; i < kSegRun && a + i < rows; ++i) {
+        j = rc_seg_walk(new_ptr, n_docs, j, t0 + a + i);
+        row_src[a + i] = rs_seg_src(new_ptr, start, j, t0 + a + i);
+      }
+    }
+    __syncthreads();
+#pragma unroll 1
+    for (int u = (int)threadIdx.x; u < rows * kSegRowUnits; u += kRcThreads) {
+      const int row = u / kSegRowUnits;
+      const long long s = row_src[row];
+      const uint4* from = s >= 0 ? old_rows + s * kSegRowUnits : add_rows + ~s * kSegRowUnits;
+      dst[t0 * kSegRowUnits + u] = from[u - row * kSegRowUnits];
+    }
+    __syncthreads();
+  }
+}
+
 unsigned rc_grid(long long slabs) { return (unsigned)(slabs < kRcMaxBlocks ? slabs : kRcMaxBlocks); }
 
 }  // namespace
@@ -135,6 +197,44 @@ int segments_compact_launch(const void* src, long long rows_new, const long long
   const long long slabs = (rows_new + kSegSlabRows - 1) / kSegSlabRows;
   hipLaunchKernelGGL(segments_compact_kernel, dim3(rc_grid(slabs)), dim3(kRcThreads), 0, st, (const uint4*)src, rows_new,
                      slabs, new_ptr, start, n_docs_new, (uint4*)dst);
+  AMDR_HIP(hipGetLastError());
+  return AMDR_OK;
+}
+
+int rows_scatter_launch(const void* rows, long long n_rep, long row_bytes, const long long* replace_ids, void* dst,
+                        hipStream_t st) {
+  AMDR_REQUIRE(row_bytes > 0 && row_bytes % 16 == 0, "rows_scatter: row_bytes=%ld must be a multiple of 16", row_bytes);
+  AMDR_REQUIRE(n_rep >= 1 && rows && replace_ids && dst, "rows_scatter: bad arguments");
+  AMDR_REQUIRE((((uintptr_t)rows | (uintptr_t)dst) & 15) == 0, "rows_scatter: buffers must be 16-byte aligned");
+  const int upr = (int)(row_bytes / 16);
+  const long long units = n_rep * upr;
+  hipLaunchKernelGGL(rows_scatter_kernel, dim3(rc_grid((units + kRcThreads - 1) / kRcThreads)), dim3(kRcThreads), 0, st,
+                     (const uint4*)rows, units, upr, replace_ids, (uint4*)dst);
+  AMDR_HIP(hipGetLastError());
+  return AMDR_OK;
+}
+
+int splice_ptr_launch(const long long* doc_ptr, long n_docs, const long long* add_ptr, const long long* replace_ids,
+                      long n_rep, long long* len, long long* start, long long* new_ptr, hipStream_t st) {
+  AMDR_REQUIRE(n_docs >= 1 && n_rep >= 1, "splice_ptr: bad sizes");
+  AMDR_REQUIRE(doc_ptr && add_ptr && replace_ids && len && start && new_ptr, "splice_ptr: null");
+  hipLaunchKernelGGL(splice_len_kernel, dim3((unsigned)((n_docs + 255) / 256)), dim3(256), 0, st, doc_ptr, n_docs, add_ptr,
+                     replace_ids, n_rep, len, start);
+  AMDR_HIP(hipGetLastError());
+  hipLaunchKernelGGL(compact_scan_i64_kernel, dim3(1), dim3(kCompactScanThreads), 0, st, len, n_docs, new_ptr);
+  AMDR_HIP(hipGetLastError());
+  return AMDR_OK;
+}
+
+int segments_splice_launch(const void* old_rows, const void* add_rows, long long rows_new, const long long* new_ptr,
+                           const long long* start, long n_docs, void* dst, hipStream_t st) {
+  AMDR_REQUIRE(rows_new >= 1 && n_docs >= 1, "segments_splice: bad sizes");
+  AMDR_REQUIRE(old_rows && add_rows && dst && new_ptr && start, "segments_splice: null");
+  AMDR_REQUIRE((((uintptr_t)old_rows | (uintptr_t)add_rows | (uintptr_t)dst) & 15) == 0,
+               "segments_splice: buffers must be 16-byte aligned");
+  const long long slabs = (rows_new + kSegSlabRows - 1) / kSegSlabRows;
+  hipLaunchKernelGGL(segments_splice_kernel, dim3(rc_grid(slabs)), dim3(kRcThreads), 0, st, (const uint4*)old_rows,
+                     (const uint4*)add_rows, rows_new, slabs, new_ptr, start, n_docs, (uint4*)dst);
   AMDR_HIP(hipGetLastError());
   return AMDR_OK;
 }

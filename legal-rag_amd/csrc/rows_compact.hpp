@@ -1,6 +1,7 @@
 // The rules of amdr_dense_remove and amdr_maxsim_remove (rows_compact.hip) that are plain C++: the host validation of the
 // removal list, the old row a new row comes from, the walk that carries that answer along a range of new rows, and the
-// segmented form (documents are removed, their token rows move).  The kernels and the host check (check_rows_compact.cpp,
+// segmented form (documents are removed, their token rows move), and the replace form behind them (rs_*: documents keep
+// their ids and take new rows from a second, staged buffer).  The kernels and the host check (check_rows_compact.cpp,
 // which compacts on the CPU with the same functions) share this one source, in the style of bm25_remove_rule.hpp.
 //
 // The map.  remove_ids[n_remove] is strictly ascending in [0, n); the survivors close up in their old order (the faiss
@@ -115,6 +116,52 @@ AMDR_RC_HD inline long rc_seg_walk(const long long* new_ptr, long n_docs_new, lo
 // The old row of new row t of new document j.
 AMDR_RC_HD inline long long rc_seg_src(const long long* new_ptr, const long long* start, long j, long long t) {
   return start[j] + (t - new_ptr[j]);
+}
+
+// ---- the replace form (amdr_dense_replace, amdr_maxsim_replace): documents keep their ids, their rows are exchanged -----
+// replace_ids[n_rep] is strictly ascending in [0, n) (rc_validate); the new rows of replace_ids[i] are staged rows
+// add_ptr[i] .. add_ptr[i + 1] of a second buffer (add_ptr[0] == 0, every document has a row).  A source row is named by
+// one signed number: s >= 0 is row s of the old store, s < 0 is row ~s of the staged rows.
+inline const char* rs_error_text(int e) {
+  switch (e) {
+    case kRcNull: return "null replace_ids";
+    case kRcSizes: return "n_rep is negative or above the number of rows";
+    case kRcIdRange: return "a replace id is outside [0, n)";
+    case kRcIdOrder: return "replace ids are not strictly ascending";
+    default: return "ok";
+  }
+}
+
+// The position of document j in replace_ids, or -1 when it is not replaced.
+AMDR_RC_HD inline long rs_find(const long long* replace_ids, long n_rep, long long j) {
+  long lo = 0, hi = n_rep;  // lower_bound
+  while (lo < hi) {
+    const long mid = lo + ((hi - lo) >> 1);
+    if (replace_ids[mid] < j)
+      lo = mid + 1;
+    else
+      hi = mid;
+  }
+  return lo < n_rep && replace_ids[lo] == j ? lo : -1;
+}
+
+// Document j afterwards: its length and the (signed) source row its rows start at.  The new doc_ptr is the exclusive
+// scan of len, as in the remove form.
+AMDR_RC_HD inline void rs_seg_entry(const long long* doc_ptr, const long long* add_ptr, const long long* replace_ids,
+                                    long n_rep, long long j, long long* len, long long* start) {
+  const long i = rs_find(replace_ids, n_rep, j);
+  if (i < 0) {
+    rc_seg_entry(doc_ptr, j, len, start);
+  } else {
+    *start = ~add_ptr[i];
+    *len = add_ptr[i + 1] - add_ptr[i];
+  }
+}
+
+// The (signed) source row of new row t of document j: rows of a document are consecutive in either source.
+AMDR_RC_HD inline long long rs_seg_src(const long long* new_ptr, const long long* start, long j, long long t) {
+  const long long s = start[j], off = t - new_ptr[j];
+  return s >= 0 ? s + off : s - off;  // ~(~s + off)
 }
 
 }  // namespace amdr

@@ -59,7 +59,7 @@ class BM25Retriever:
         self.index_tokenizer: Optional[str] = None  # id recorded in bm25.pkl (None: reference-built)
         self._tls = threading.local()                 # per-thread: did the last query use the stand-in?
         self.shard = None                             # sharding.ShardSpec in a row-sharded deployment
-        self.appends = 0                              # in-place mutations (appends and removals) so far: part of the
+        self.appends = 0                              # in-place mutations (appends, removals, replacements) so far: part of the
                                                       # hybrid stage's key
 
     @staticmethod
@@ -168,6 +168,41 @@ class BM25Retriever:
             live.remove_documents(sorted(gone))
         except Exception as exc:  # noqa: BLE001 - e.g. no room for the transient second copy: the file is reloaded instead
             logger.warning("[BM25] in-place removal failed (%s): %s is reloaded on the next load()", exc, self.bm25_path)
+            return False
+        self.chunks = list(corpus_after)
+        # the native tokenisers hold the vocabulary table: rebuilt for the renumbered one on their next use
+        self.__dict__.pop("_native_tok", None)
+        self.__dict__.pop("_device_tok", None)
+        self.appends += 1
+        self._bm25_mtime = stamp
+        return True
+
+    def replace_in_place(self, rows: Sequence[int], new_tokens: Sequence[Sequence[str]],
+                         corpus_after: Sequence[LawChunk]) -> bool:
+        """IncrementalBM25Builder.replace_jsonl, after it has replaced a file that was current (state_is_current, the
+        caller holds `_lock`) by the same index with the documents at `rows` (positions in the chunk list) re-fitted from
+        `new_tokens`, whose chunks are now `corpus_after`: when the live chunks are the replaced file's — as many, and
+        id for id corpus_after, a replaced chunk keeps its id — the documents are replaced in the live object and its
+        resident postings (BM25Okapi.replace_documents, amdr_bm25_replace), the file's mtime is remembered and True is
+        returned.  Otherwise, or when the replacement fails, False: the next load() reloads the file.  A mutation of the
+        native handle, as append_in_place: device work already enqueued is waited for here; searches on the
+        device-resident stage must not be STARTED from other threads meanwhile."""
+        live = self.bm25
+        rows = [int(r) for r in rows]
+        n = live.corpus_size
+        if (not rows or len(rows) != len(new_tokens) or len(set(rows)) != len(rows) or min(rows) < 0 or max(rows) >= n
+                or len(self.chunks) != n or len(corpus_after) != n
+                or [c.id for c in self.chunks] != [c.id for c in corpus_after]):
+            return False
+        stamp = self.bm25_path.stat().st_mtime
+        if live.__dict__.get("_gpu") is not None:
+            import torch
+            if torch.cuda.is_available():
+                torch.cuda.synchronize(self.device_index)
+        try:
+            live.replace_documents(rows, new_tokens)
+        except Exception as exc:  # noqa: BLE001 - e.g. no room for the transient second copy: the file is reloaded instead
+            logger.warning("[BM25] in-place replacement failed (%s): %s is reloaded on the next load()", exc, self.bm25_path)
             return False
         self.chunks = list(corpus_after)
         # the native tokenisers hold the vocabulary table: rebuilt for the renumbered one on their next use

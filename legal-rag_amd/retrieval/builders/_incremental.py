@@ -2,7 +2,7 @@
 from __future__ import annotations
 
 from pathlib import Path
-from typing import Iterable, List, Set
+from typing import Dict, Iterable, List, Sequence, Set
 
 from ...schemas import LawChunk
 from ..corpus_loader import read_jsonl_chunks
@@ -29,3 +29,16 @@ def unseen(chunks: Iterable[LawChunk], known_ids: Set[str]) -> List[LawChunk]:
             seen.add(c.id)
             fresh.append(c)
     return fresh
+
+
+def amended(chunks: Iterable[LawChunk], current_ids: Sequence[str]) -> Dict[int, LawChunk]:
+    """{row: chunk} for the incoming chunks whose id is in the index, `current_ids[row]` being the id at that row; rows
+    ascending; of two incoming chunks with one id the later one counts (it amends the earlier).  Ids the index does not
+    hold are left out: adding them is add_jsonl's job."""
+    row_of = {cid: r for r, cid in enumerate(current_ids)}
+    found: Dict[int, LawChunk] = {}
+    for c in chunks:
+        r = row_of.get(c.id)
+        if r is not None:
+            found[r] = c
+    return dict(sorted(found.items()))

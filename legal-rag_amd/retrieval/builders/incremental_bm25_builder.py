@@ -16,8 +16,12 @@ retriever's lock is held from the question "is the loaded state the file" until 
 thread reloads the new file in between.  A row-sharded retriever (cfg.retrieval.shard = "rows") always reloads.
 
 remove_ids takes chunks out again (the reference has no removal at all) — out of THIS channel.  A retriever that runs the
-hybrid holds the chunk in its dense and ColBERT channels too: a replaced article is builders/remove.py
-`remove_chunk_ids(cfg, ids)`, which calls the three builders' remove_ids, followed by the three add_jsonl."""
+hybrid holds the chunk in its dense and ColBERT channels too: builders/remove.py `remove_chunk_ids(cfg, ids)` calls the
+three builders' remove_ids.
+
+replace_jsonl exchanges chunks under their ids — an AMENDED article: add_jsonl skips an id the index holds (and says how
+many it skipped).  The chunk keeps its row, so every table that names rows stays valid and ties break as in a fresh
+build of the amended corpus; builders/replace.py `replace_chunks(cfg, jsonl_path)` does it for every channel."""
 from __future__ import annotations
 
 import contextlib
@@ -28,7 +32,7 @@ from typing import Iterable, List
 from ... import artifacts, text
 from ...bm25_model import BM25Okapi
 from ...schemas import LawChunk
-from ._incremental import incoming_chunks
+from ._incremental import amended, incoming_chunks
 
 logger = logging.getLogger(__name__)
 
@@ -50,6 +54,9 @@ class IncrementalBM25Builder:
             return 0
         kept = self._current_chunks()
         fresh = [c for c in batch if c.id not in {k.id for k in kept}]
+        if len(fresh) < len(batch):
+            logger.info("[bm25] skipped %d incoming chunks whose id is in the index already; replace_jsonl ingests "
+                        "amended chunks", len(batch) - len(fresh))
         if not fresh:
             logger.info("[bm25] no new chunks to add: incoming=%d", len(batch))
             return 0
@@ -107,4 +114,50 @@ class IncrementalBM25Builder:
         logger.info("[bm25] live retriever: %s", "removed in place" if in_place else
                     "none" if live is None else "reloads on its next load()")
         logger.info("[bm25] incremental remove done: removed=%d total=%d", len(rows), len(corpus))
+        return len(rows)
+
+    def replace_jsonl(self, jsonl_path) -> int:
+        """Incoming chunks whose id IS in the index replace that chunk at its row; returns how many.  Ids the index does
+        not hold are left alone (add_jsonl adds them).  The model in the current pickle is brought to the re-fit of the
+        amended corpus, in its original order, by BM25Okapi.replace_documents — only the incoming texts are tokenised,
+        with add_jsonl's rule (jieba.cut); the other documents keep the tokens the file holds — and written back with the
+        tokenizer id the file records, which must be this configuration's.  A live BM25Retriever whose loaded state was
+        the replaced file then takes the replacement in place (replace_in_place, amdr_bm25_replace), under the same lock
+        discipline as add_jsonl; otherwise it reloads on its next load()."""
+        if getattr(self.cfg.retrieval, "shard", None):
+            raise RuntimeError("replacement on a row-sharded index is not supported: rebuild and reload")
+        batch = incoming_chunks(jsonl_path, logger, "bm25")
+        path = Path(self.cfg.retrieval.bm25_index_file)
+        if not batch or not path.exists():
+            return 0
+        bm25, chunks = artifacts.read_bm25_pickle(path)
+        found = amended(batch, [c.id for c in chunks])
+        if not found:
+            logger.info("[bm25] none of %d incoming ids is in the index", len(batch))
+            return 0
+        if bm25.corpus_size != len(chunks):
+            raise RuntimeError(f"[BM25] {path}: {bm25.corpus_size} documents but {len(chunks)} chunks")
+        mode, dict_file = text.cfg_mode(self.cfg), text.cfg_dict_file(self.cfg)
+        text.require_dict(mode, dict_file)
+        tokenizer = bm25.__dict__.get("_tokenizer_id")
+        if tokenizer != text.tokenizer_id(mode):
+            raise RuntimeError(f"[BM25] {path} was tokenised by {tokenizer!r}, this configuration tokenises by "
+                               f"{text.tokenizer_id(mode)!r}: an amended chunk would be cut differently from the rest. "
+                               f"Rebuild the index.")
+        rows = list(found)
+        tokens = [text.jieba_cut(c.text, mode, dict_file) for c in found.values()]
+        bm25.replace_documents(rows, tokens)
+        corpus = list(chunks)
+        for r, c in found.items():
+            corpus[r] = c
+        from ..bm25_retriever import BM25Retriever
+        live = BM25Retriever.live(path, int(getattr(self.cfg.retrieval, "device", 0)))
+        with live._lock if live is not None else contextlib.nullcontext():
+            in_place = live is not None and live.state_is_current()
+            artifacts.write_bm25_pickle(path, bm25, corpus, tokenizer=tokenizer)
+            if in_place:
+                in_place = live.replace_in_place(rows, tokens, corpus)
+        logger.info("[bm25] live retriever: %s", "replaced in place" if in_place else
+                    "none" if live is None else "reloads on its next load()")
+        logger.info("[bm25] incremental replace done: replaced=%d total=%d", len(rows), len(corpus))
         return len(rows)

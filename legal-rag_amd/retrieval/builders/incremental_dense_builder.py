@@ -10,7 +10,11 @@ an index row without its chunk), then persist the index.
 
 remove_ids takes chunks out again (the reference has no removal: a corpus that shrinks takes `index.add` over everything,
 faiss_builder.py:91, and the reload of vector_store.py): the rows leave the resident matrix in place (`amdr_dense_remove`)
-and both files are rewritten.  builders/remove.py does it for every channel of the hybrid."""
+and both files are rewritten.  builders/remove.py does it for every channel of the hybrid.
+
+replace_jsonl exchanges chunks under their ids — an amended article, which add_jsonl skips: the new embeddings are
+written over the chunks' rows of the resident matrix (`amdr_dense_replace`), no row moves, and both files are rewritten.
+builders/replace.py does it for every channel."""
 from __future__ import annotations
 
 import logging
@@ -22,7 +26,7 @@ from filelock import FileLock
 
 from ... import artifacts
 from ..vector_store import VectorStore
-from ._incremental import incoming_chunks, unseen
+from ._incremental import amended, incoming_chunks, unseen
 
 logger = logging.getLogger(__name__)
 
@@ -41,6 +45,9 @@ class IncrementalDenseBuilder:
             vs.load()
             fresh = unseen(batch, {c.id for c in vs.chunks})
             logger.info("[index] dedup done: incoming=%d added=%d", len(batch), len(fresh))
+            if len(fresh) < len(batch):
+                logger.info("[index] skipped %d incoming chunks whose id is in the index already; replace_jsonl ingests "
+                            "amended chunks", len(batch) - len(fresh))
             if not fresh:
                 return 0
             vs.index.add(vs._embed([c.text for c in fresh]).astype("float32"))
@@ -90,3 +97,37 @@ class IncrementalDenseBuilder:
             vs._meta_mtime = vs.meta_path.stat().st_mtime
         logger.info("[index] incremental remove done: removed=%d total=%d", len(rows), len(kept))
         return len(rows)
+
+    def replace_jsonl(self, jsonl_path) -> int:
+        """Incoming chunks whose id IS in the index replace that chunk at its row; returns how many.  Ids the index does
+        not hold are left alone (add_jsonl adds them).  Under the index file lock: reload the store, embed the incoming
+        texts as passages, write them over their rows of the matrix resident in HBM (FlatIPIndex.replace_rows: no row
+        moves), then rewrite the meta file and the index file as remove_ids does: each through a temporary and
+        os.replace, the mtimes stamped so that this process does not reload what it wrote.  A GraphRetriever of this
+        store finds `rows_epoch` changed and binds its norms and device tables again."""
+        batch = incoming_chunks(jsonl_path, logger, "index")
+        if not batch:
+            return 0
+        vs = self.vs
+        with FileLock(str(Path(self.cfg.retrieval.faiss_index_file).with_suffix(".lock"))):
+            vs.load()
+            found = amended(batch, [c.id for c in vs.chunks])
+            if not found:
+                logger.info("[index] none of %d incoming ids is in the index", len(batch))
+                return 0
+            if vs.index.ntotal != len(vs.chunks):
+                raise RuntimeError(f"[index] {vs.index_path}: {vs.index.ntotal} rows but {len(vs.chunks)} chunks")
+            vs.index.replace_rows(list(found), vs._embed([c.text for c in found.values()]).astype("float32"))
+            chunks = list(vs.chunks)
+            for r, c in found.items():
+                chunks[r] = c
+            tmp = vs.meta_path.with_suffix(vs.meta_path.suffix + ".tmp")
+            artifacts.write_faiss_meta(tmp, chunks)
+            os.replace(tmp, vs.meta_path)
+            vs.chunks = chunks
+            artifacts.write_faiss_flat_ip(vs.index_path, vs.index.reconstruct_n(0, vs.index.ntotal))
+            # what this process just wrote IS the resident state: no mtime-triggered reload
+            vs._index_mtime = vs.index_path.stat().st_mtime
+            vs._meta_mtime = vs.meta_path.stat().st_mtime
+        logger.info("[index] incremental replace done: replaced=%d total=%d", len(found), len(chunks))
+        return len(found)

@@ -197,6 +197,28 @@ class ColBERTRetriever:
             self._meta_mtime = None
             self._load_meta_and_collection()
 
+    def note_replaced(self, rows, tokens: np.ndarray, doc_ptr: np.ndarray) -> None:
+        """IncrementalColBERTBuilder, after it has rewritten the meta file (the chunks of pids `rows` exchanged) and the
+        token store with the token rows of those documents exchanged for `tokens` / `doc_ptr` (the new documents' own
+        offsets; `rows` ascending pids of a store that was current: store_is_current): the same documents are replaced
+        in the resident store (amdr_maxsim_replace), the pid map is read again, and the files' mtimes are remembered —
+        what this process wrote IS the resident state, so nothing is reloaded.  The lock discipline is note_appended's.
+        Should the resident store not hold as many documents as the written one (a caller that did not hold the lock),
+        or be a shard's block, it is read from the file instead."""
+        cls = type(self)
+        rows = [int(r) for r in rows]
+        with cls._registry_lock:
+            on_disk = artifacts.token_store_ndocs(self.index_dir())
+            if self._searcher is not None and self.shard is None and self._searcher.info()[0] == on_disk:
+                self._searcher.replace(rows, tokens, doc_ptr)
+                self._store_mtime = self._store_stamp()
+                cls._searcher_cache[self._searcher_key] = (self._searcher, self.row_offset, self._store_mtime)
+            else:
+                held = cls._searcher_cache[self._searcher_key] = self._open_store()
+                self._searcher, self.row_offset, self._store_mtime = held
+            self._meta_mtime = None
+            self._load_meta_and_collection()
+
     def search(self, query: str, top_k: int = 5) -> List[Tuple[LawChunk, float]]:
         if not self.enabled:
             return []

@@ -131,7 +131,8 @@ def build_graph_tables(graph: LawGraphStore, chunks: Sequence[LawChunk]) -> Grap
 
 
 def _rows_epoch(index: Any) -> int:
-    """How often rows of `index` were removed in place (vector_store.FlatIPIndex.rows_epoch; 0 for an index without)."""
+    """How often rows of `index` were removed or replaced in place (vector_store.FlatIPIndex.rows_epoch; 0 for an index
+    without)."""
     return int(getattr(index, "rows_epoch", 0) or 0)
 
 

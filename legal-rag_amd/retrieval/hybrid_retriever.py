@@ -658,7 +658,8 @@ class HybridRetriever:
         # (the BM25 retriever's Han mode: an engine's device tokeniser is a copy of the host tokeniser in that mode)
         # (appends counts in-place mutations: an in-place BM25 append or removal keeps the object and changes n_docs and
         # the term ids: engines and reserves are made again)
-        # (rows_epoch counts the dense index's in-place removals, FlatIPIndex.remove_ids: the object stays, its rows move)
+        # (rows_epoch counts the dense index's in-place removals and replacements, FlatIPIndex.remove_ids / replace_rows: the
+        # object stays, its rows move or change)
         key = (id(store.index), getattr(store.index, "rows_epoch", 0), id(self.bm25.bm25), getattr(self.bm25, "appends", 0),
                id(col._searcher) if col is not None else None, id(col._pid2chunk) if col is not None else None,
                self.bm25.han_key())

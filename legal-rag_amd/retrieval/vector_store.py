@@ -39,8 +39,9 @@ class FlatIPIndex:
         self.d = int(X.shape[1])
         self.metric_type = artifacts.METRIC_INNER_PRODUCT
         self.dense_image = dense_image
-        # bumped by remove_ids: the surviving rows are renumbered in place, so whoever holds row ids of this index
-        # (GraphRetriever's row map, norms and device tables) tells by it that they name the old rows
+        # bumped by remove_ids and replace_rows: rows were renumbered or rewritten in place, so whoever holds row ids of
+        # this index or values derived from its rows (GraphRetriever's row map, norms and device tables) tells by it
+        # that they describe the old rows
         self.rows_epoch = 0
         if dense_image == "fp16":
             self._build_image()
@@ -110,6 +111,26 @@ class FlatIPIndex:
             self._build_image()
         return int(rows.size)
 
+    def replace_rows(self, ids, x: np.ndarray) -> int:
+        """Rows `ids` (distinct, in [0, ntotal)) take the rows of `x`, ids[i] <- x[i]; no row moves (amdr_dense_replace:
+        one scatter into the resident matrix; the handle is then what a fresh index of the edited matrix is, bit for
+        bit).  Returns the number replaced.  `rows_epoch` goes up: a replaced row's norm and chunk may have changed, so
+        a GraphRetriever of this store binds its norms and device tables again."""
+        rows = np.asarray(list(ids) if not isinstance(ids, np.ndarray) else ids, dtype=np.int64).reshape(-1)
+        x = np.ascontiguousarray(x, dtype=np.float32).reshape(-1, self.d)
+        if rows.size != x.shape[0] or np.unique(rows).size != rows.size:
+            raise ValueError("replace_rows: one row of x for every id, every id once")
+        if rows.size == 0:
+            return 0
+        order = np.argsort(rows, kind="stable")
+        self._idx.replace(rows[order], x[order])
+        self.rows_epoch += 1
+        # the native replace keeps a present image current and drops it while the matrix is not finite; under "fp16" an
+        # index without one gets it as soon as it can have one, as in add
+        if self.dense_image == "fp16" and not self._idx.image_info()[0]:
+            self._build_image()
+        return int(rows.size)
+
     def reconstruct_n(self, i0: int, n: int) -> np.ndarray:
         return self._idx.read_rows(int(i0), int(n))
 
@@ -149,6 +170,9 @@ class ShardedFlatIPIndex(FlatIPIndex):
 
     def remove_ids(self, ids) -> int:
         raise RuntimeError("removal on a row-sharded index is not supported: rebuild and reload")
+
+    def replace_rows(self, ids, x: np.ndarray) -> int:
+        raise RuntimeError("replacement on a row-sharded index is not supported: rebuild and reload")
 
     def reconstruct_n(self, i0: int, n: int) -> np.ndarray:
         """rows by GLOBAL id; only this rank's block is resident"""
