@@ -420,7 +420,17 @@ int amdr_tokenizer_device_destroy(amdr_tokenizer_device_t* h);
  * Arithmetic: every operand is split exactly into fp16 hi + lo / 2048 (22 significant bits) and a product is
  * hi*hi + (hi*lo + lo*hi) / 2048 on the fp16 matrix instructions with fp32 accumulation — scores within ~3e-6 of
  * the fp64 definition on unit-norm tokens (north_star's bar: 1e-4), scale-free for any finite input; a store
- * holding a NaN / infinity, or AMDR_MAXSIM_F16X3=0, takes the exact fp32-input matrix form (csrc/maxsim.hip). */
+ * holding a NaN / infinity, or AMDR_MAXSIM_F16X3=0, takes the exact fp32-input matrix form (csrc/maxsim.hip).
+ * Non-finite stores (fp32-input form; scores, search and search_device alike): a similarity <q_i, d_j> follows IEEE
+ * arithmetic (a NaN component, inf x 0 or inf - inf make it NaN).  The maximum over a document's tokens starts at
+ * -FLT_MAX and ignores a NaN similarity, so a -inf similarity never wins either and a +inf one does: a query token whose
+ * similarities with a document are all NaN or -inf contributes -FLT_MAX, one with a +inf similarity +inf.  The
+ * contributions are added in fp32: -FLT_MAX absorbs finite addends, two of them overflow to -inf.  Hence a NaN token
+ * in a longer document drops out of it, a document of NaN tokens only scores -FLT_MAX (q_len == 1) or -inf, and no
+ * score is ever NaN — the fp64 definition says NaN where this rule says a number.  (Only a document holding both
+ * a +inf contribution and two -FLT_MAX ones has no defined score: inf - inf.)  In the top-k +inf ranks first and -inf
+ * last, ahead of the -1 / -FLT_MAX padding, ties -> lower id as everywhere.  Every other document keeps the bits it
+ * has in the same store with the non-finite token replaced by zeros.  Tested in tests/test_maxsim_adversary_gpu.py. */
 int amdr_maxsim_create(const float* D_host, const int64_t* doc_ptr, int64_t n_docs, int32_t dim,
                        int32_t device, amdr_maxsim_t** out);
 /* Append n_add documents (replaces re-running the indexer over the whole corpus, legalrag/retrieval/builders/

@@ -754,19 +754,23 @@ def test_maxsim_two_pass_topk_equals_one_pass(nat, monkeypatch):
     base = unit_rows(rng, 40, 128)
     docs = [base + 1e-4 * rng.standard_normal(base.shape).astype(np.float32) for _ in range(200)]
     docs += [unit_rows(rng, int(rng.integers(5, 80)), 128) for _ in range(100)]
+    Q = np.stack([np.concatenate([base[:20] + 0.05 * rng.standard_normal((20, 128)).astype(np.float32),
+                                  unit_rows(rng, 12, 128)]) for _ in range(8)]).astype(np.float32)
+    Q /= np.linalg.norm(Q, axis=2, keepdims=True)
+    # documents 3, 7 and 150 are one document: a member of the cluster plus the 12 random tokens of every query, which only
+    # it matches exactly (+ ~8 on a score of ~25) — the three lead every list, tied
+    docs[3] = np.concatenate([docs[3], Q[:, 20:].reshape(-1, 128)])
     docs[7] = docs[3].copy()
     docs[150] = docs[3].copy()
     D = np.concatenate(docs).astype(np.float32)
     D /= np.linalg.norm(D, axis=1, keepdims=True)
     doc_ptr = np.concatenate([[0], np.cumsum([len(x) for x in docs])]).astype(np.int64)
-    Q = np.stack([np.concatenate([base[:20] + 0.05 * rng.standard_normal((20, 128)).astype(np.float32),
-                                  unit_rows(rng, 12, 128)]) for _ in range(8)]).astype(np.float32)
-    Q /= np.linalg.norm(Q, axis=2, keepdims=True)
     s, i = run(D, doc_ptr, Q, 10)
     for b in range(8):
         pos = {int(d): j for j, d in enumerate(i[b])}
-        if 3 in pos and 7 in pos and 150 in pos:
-            assert pos[3] < pos[7] < pos[150] and s[b, pos[3]] == s[b, pos[7]] == s[b, pos[150]]
+        assert 3 in pos and 7 in pos and 150 in pos
+        assert pos[3] < pos[7] < pos[150] and s[b, pos[3]] == s[b, pos[7]] == s[b, pos[150]]
+        assert (pos[3], pos[7], pos[150]) == (0, 1, 2)
     # token norms over three orders of magnitude, a scaled store and tiny queries: the bound follows the norms
     w = np.exp2(-rng.integers(0, 10, size=D.shape[0])).astype(np.float32)[:, None]
     run((D * w * np.float32(12.5)).astype(np.float32), doc_ptr, (Q * np.float32(3e-3)).astype(np.float32), 10)
