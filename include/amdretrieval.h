@@ -22,6 +22,12 @@
  * the handle's mutex and return after the results are in the host buffers: they
  * are safe to call from any number of threads, also while "_device" work of the
  * same handle is still in flight on another stream (different workspace).
+ *
+ * Batch size: every batched call serves any nq an int32 holds, memory permitting
+ * (outputs and workspaces grow with nq; a failed allocation is AMDR_ENOMEM).  No
+ * launch limit bounds it: a launch that carries the batch in the grid's y goes in
+ * pieces of 65 535 queries on the same stream, so no grid dimension exceeds what
+ * every HIP runtime accepts.
  */
 #ifndef AMDRETRIEVAL_H
 #define AMDRETRIEVAL_H

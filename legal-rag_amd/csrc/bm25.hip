@@ -106,19 +106,27 @@ int bm_run(amdr_bm25* h, int ws, const int* q_terms_dev, const long long* q_ptr_
     return fail(AMDR_EINVAL, "bm25: slab needs %zu B of LDS", p.lds);
   }
   const BmIndex& ix = h->ix;
-#define AMDR_BM_LAUNCH(NVT)                                                                                          \
-  hipLaunchKernelGGL((bm25_score_topk_kernel<1, NVT>), dim3(p.nslabs, nq), dim3(64), p.lds, st, ix.term_ptr,         \
-                     ix.post_doc, ix.post_w, ix.idf, (long)ix.n_terms, (long)ix.n_docs, q_terms_dev, q_ptr_dev, nq, k, \
-                     p.cap, p.slab, bm_select_enabled() ? 1 : 0, full_dev, part, fs, fi)
+  // The batch is the grid's y: pieces (grid_y_pieces).  A piece is handed the call's nq and its own rows of q_ptr, of the
+  // outputs and of every slab's list ([slab][nq][k] + q0 * k), so the pieces fill one set of lists and one merge reads it.
+#define AMDR_BM_LAUNCH(NVT)                                                                                            \
+  hipLaunchKernelGGL((bm25_score_topk_kernel<1, NVT>), dim3(p.nslabs, m), dim3(64), p.lds, st, ix.term_ptr,            \
+                     ix.post_doc, ix.post_w, ix.idf, (long)ix.n_terms, (long)ix.n_docs, q_terms_dev, q_ptr_dev + q0,   \
+                     nq, k, p.cap, p.slab, bm_select_enabled() ? 1 : 0,                                                \
+                     full_dev ? full_dev + (size_t)q0 * ix.n_docs : nullptr, part ? part + (size_t)q0 * k : nullptr,  \
+                     fs ? fs + (size_t)q0 * k : nullptr, fi ? fi + (size_t)q0 * k : nullptr)
   const int nv = bm_use_argmax(k, p.slab) ? (p.slab + 63) / 64 : 1;  // the staged selector needs no register bucket
-  if (nv <= 4) AMDR_BM_LAUNCH(4);
-  else if (nv <= 8) AMDR_BM_LAUNCH(8);
-  else if (nv <= 10) AMDR_BM_LAUNCH(10);
-  else if (nv <= 16) AMDR_BM_LAUNCH(16);
-  else if (nv <= 20) AMDR_BM_LAUNCH(20);
-  else AMDR_BM_LAUNCH(32);
+  const int rc = grid_y_pieces(nq, [&](int q0, int m) -> int {
+    if (nv <= 4) AMDR_BM_LAUNCH(4);
+    else if (nv <= 8) AMDR_BM_LAUNCH(8);
+    else if (nv <= 10) AMDR_BM_LAUNCH(10);
+    else if (nv <= 16) AMDR_BM_LAUNCH(16);
+    else if (nv <= 20) AMDR_BM_LAUNCH(20);
+    else AMDR_BM_LAUNCH(32);
+    AMDR_HIP(hipGetLastError());
+    return AMDR_OK;
+  });
 #undef AMDR_BM_LAUNCH
-  AMDR_HIP(hipGetLastError());
+  if (rc) return rc;
   if (scores_dev && !direct) return launch_merge_packed(part, p.nslabs, nq, k, p.cap_merge, scores_dev, ids_dev, st);
   return AMDR_OK;
 }

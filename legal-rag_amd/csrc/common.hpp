@@ -70,6 +70,21 @@ inline int topk_cap(int k) { return next_pow2(k + 64) < 128 ? 128 : next_pow2(k 
 
 int check_device(int device);
 
+// A grid's y (and z) is sure to hold 65 535 blocks: hipDeviceProp_t::maxGridSize of the MI355X reports 65 536 for both.  (Its
+// ROCm runtime took the unsplit launches of 65 541 queries as well, with the same results; nothing here relies on that.)  A
+// launch that carries the batch in y goes in pieces of at most that many queries, one after the other on the caller's
+// stream: piece(q0, m) enqueues queries [q0, q0 + m) and returns a status.  A batch of up to 65 535 queries is one piece,
+// piece(0, nq): the launch it always was.
+constexpr int kGridYMax = 65535;
+template <class Piece>
+int grid_y_pieces(int nq, Piece&& piece) {
+  for (int q0 = 0; q0 < nq; q0 += kGridYMax) {
+    const int rc = piece(q0, nq - q0 < kGridYMax ? nq - q0 : kGridYMax);
+    if (rc) return rc;
+  }
+  return AMDR_OK;
+}
+
 // A chunk matrix larger than the 256 MiB Infinity Cache is streamed with the non-temporal policy
 // (read once per scan; nothing to keep on-die).  AMDR_DENSE_NT=0|1 pins the choice.
 inline bool dense_stream_nontemporal(long n, int d) {

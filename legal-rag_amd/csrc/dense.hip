@@ -372,7 +372,7 @@ constexpr int64_t kRowWavesMax = 16384;  // rows up to which fewer queries take 
 // yields to the panel kernel (the fp16 first pass does not).  Below kBatchedMin, and for a dimension outside the MFMA
 // forms, k does not enter.  reserve_need enumerates on these two facts.
 Route dense_route(const amdr_dense* h, const DensePins& pins, int nq, int k) {
-  Route r{Form::Scan, nq, false, 0, 0};
+  Route r{Form::Scan, nq < kGridYMax ? nq : kGridYMax, false, 0, 0};  // (a pass's query groups are the scan's grid y)
   const long n = (long)h->n;
   if (nq >= kBatchedMin && n > 0 && dense_mfma_supported(h->d)) {
     r.form = Form::Batched;
@@ -801,9 +801,9 @@ int run_search_two_level(amdr_dense* h, int ws, const DensePins& pins, Route r, 
   return AMDR_OK;
 }
 
-// Form Scan.
-int run_search_scan(amdr_dense* h, int ws, const float* Q_dev, int nq, int k, float* scores_dev, int64_t* ids_dev,
-                    hipStream_t st) {
+// One pass of form Scan: m <= kGridYMax queries, so the ceil(m / queries per block) query groups fit the grid's y.
+int scan_pass(amdr_dense* h, int ws, const float* Q_dev, int nq, int k, float* scores_dev, int64_t* ids_dev,
+              hipStream_t st) {
   ScanPlan p;
   make_plan(h->n, h->d, nq, k, &p);
   C32* part = h->part[ws].as<C32>();
@@ -825,6 +825,17 @@ int run_search_scan(amdr_dense* h, int ws, const float* Q_dev, int nq, int k, fl
   return launch_merge_packed(part, h->n > 0 ? p.grid_x : 0, nq, k, p.cap, scores_dev, ids_dev, st);  // (an empty index: padding)
 }
 
+// Form Scan: passes of r.chunk queries, each with its own plan; they share the slab lists one after the other on the stream.
+int run_search_scan(amdr_dense* h, int ws, const Route& r, const float* Q_dev, int nq, int k, float* scores_dev,
+                    int64_t* ids_dev, hipStream_t st) {
+  for (int q0 = 0; q0 < nq; q0 += r.chunk) {
+    const int m = nq - q0 < r.chunk ? nq - q0 : r.chunk;
+    const int rc = scan_pass(h, ws, Q_dev + (size_t)q0 * h->d, m, k, scores_dev + (size_t)q0 * k, ids_dev + (size_t)q0 * k, st);
+    if (rc) return rc;
+  }
+  return AMDR_OK;
+}
+
 // One search on workspace `ws`; with a tail (amdr_dense_search_fuse_device), the fusion behind it — pass by pass in the
 // Batched form, one plain launch over the finished lists behind the others.
 int run_search(amdr_dense* h, int ws, const float* Q_dev, int nq, int k, float* scores_dev, int64_t* ids_dev,
@@ -838,7 +849,7 @@ int run_search(amdr_dense* h, int ws, const float* Q_dev, int nq, int k, float* 
     case Form::RowWaves: rc = run_search_batched(h, ws, pins, r, Q_dev, nq, k, scores_dev, ids_dev, st, nullptr); break;
     case Form::TwoLevel:
     case Form::Hi: rc = run_search_two_level(h, ws, pins, r, Q_dev, nq, k, scores_dev, ids_dev, st); break;
-    case Form::Scan: rc = run_search_scan(h, ws, Q_dev, nq, k, scores_dev, ids_dev, st); break;
+    case Form::Scan: rc = run_search_scan(h, ws, r, Q_dev, nq, k, scores_dev, ids_dev, st); break;
   }
   if (rc || !tail) return rc;
   return dense_fuse_plain_launch(*tail, 0, nq, k, scores_dev, ids_dev, st);
@@ -1396,7 +1407,7 @@ int amdr_dense_plan_info(const amdr_dense_t* h, int32_t nq, int32_t k, char* buf
     }
   } else {
     ScanPlan p;
-    make_plan(h->n, h->d, nq, k, &p);
+    make_plan(h->n, h->d, m, k, &p);  // (a pass: the whole batch up to kGridYMax queries)
     snprintf(buf, buf_len, "dense_scan_topk_kernel<NQ=%d> grid=%dx%d%s", p.nq_per_block, p.grid_x, p.grid_y,
              p.grid_x == 1 ? "" : " + merge_parts_kernel");
   }

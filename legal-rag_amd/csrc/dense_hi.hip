@@ -437,6 +437,7 @@ template <int D64, bool EMIT>
 static int launch_hi(const float* X, const void* image, long n, const float* Q, int nq, int grid, float* MT, long ldMT,
                      float x_scale, long tile_stride, long n_items, const HiEmit& em, hipStream_t st, int grid_y) {
   const size_t lds = dense_hi_lds(D64 * 64, EMIT);
+  // grid y: the query tiles of one pass, <= 4 (dense.hip kHi2Tiles)
   if (image) {
     AMDR_HIP(hipFuncSetAttribute((const void*)dense_hi_image_tilemax_kernel<D64, EMIT>,
                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));

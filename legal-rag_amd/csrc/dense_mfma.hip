@@ -651,14 +651,22 @@ int dense_mfma_launch_topk(const DenseMfmaPlan& p, const float* S, long n, int n
     AMDR_HIP(hipGetLastError());
     return AMDR_OK;
   }
-  if (waves == 1)
-    hipLaunchKernelGGL(scores_slab_topk_kernel<1>, dim3(p.slabs, nq), dim3(64), lds, st, S, p.ld, n, nq, k, p.cap,
-                       p.rows_per_slab, (C32*)part, fin_scores, (long long*)fin_ids);
-  else
-    hipLaunchKernelGGL(scores_slab_topk_kernel<kBW>, dim3(p.slabs, nq), dim3(256), lds, st, S, p.ld, n, nq, k, p.cap,
-                       p.rows_per_slab, (C32*)part, fin_scores, (long long*)fin_ids);
-  AMDR_HIP(hipGetLastError());
-  return AMDR_OK;
+  // The batch is the grid's y: pieces (grid_y_pieces).  A piece is handed the pass's nq and its own rows of S, of the result
+  // and of every slab's list ([slab][nq][k] + q0 * k), so the pieces fill the one set of lists that the caller's merge reads.
+  return grid_y_pieces(nq, [&](int q0, int m) -> int {
+    const float* Sp = S + (size_t)q0 * p.ld;
+    C32* pp = part ? (C32*)part + (size_t)q0 * k : nullptr;
+    float* fs = fin_scores ? fin_scores + (size_t)q0 * k : nullptr;
+    long long* fi = fin_ids ? (long long*)fin_ids + (size_t)q0 * k : nullptr;
+    if (waves == 1)
+      hipLaunchKernelGGL(scores_slab_topk_kernel<1>, dim3(p.slabs, m), dim3(64), lds, st, Sp, p.ld, n, nq, k, p.cap,
+                         p.rows_per_slab, pp, fs, fi);
+    else
+      hipLaunchKernelGGL(scores_slab_topk_kernel<kBW>, dim3(p.slabs, m), dim3(256), lds, st, Sp, p.ld, n, nq, k, p.cap,
+                         p.rows_per_slab, pp, fs, fi);
+    AMDR_HIP(hipGetLastError());
+    return AMDR_OK;
+  });
 }
 
 
@@ -679,6 +687,7 @@ static int launch_rescore(const float* X, long n_real, const float* Q, int m, co
                           int list_stride, int max_tiles, long ldS, float* S, hipStream_t st) {
   constexpr int WPB = 4;
   const size_t lds = (size_t)D8 * 8 * sizeof(float) + (size_t)WPB * kStageBytes;
+  // grid y: tiles of one query's list, <= AMDR_MAX_K / WPB
   hipLaunchKernelGGL((dense_rescore_tiles_kernel<D8, WPB>), dim3(m, (max_tiles + WPB - 1) / WPB), dim3(WPB * 64), lds, st, X,
                      n_real, Q, list, count, list_stride, ldS, S);
   return AMDR_OK;

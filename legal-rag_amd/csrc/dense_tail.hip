@@ -538,6 +538,7 @@ int hybrid_small_launch(const DenseRaw& dr, const Bm25Raw& br, const float* Q, c
   const int mo = kd + kb;
   ChanIn c0{nullptr, nullptr, (const long long*)dense_row2uid, kd, 0};
   ChanIn c1{(const long long*)bm25_ids, (const void*)bm25_scores, (const long long*)bm25_row2uid, kb, 1};
+  // grid y: the one-launch step serves nq <= 4 (hybrid_small_applies)
 #define AMDR_HS_LAUNCH(NVT)                                                                                        \
   hipLaunchKernelGGL((hybrid_small_kernel<NVT>), dim3(A.blocks_per_query, nq), dim3(256), lds, st, A, P, c0, c1, nq, mo, \
                      (long long*)out_ids, out_vals, out_mask, out_count)

@@ -1158,7 +1158,7 @@ int ms_run(amdr_maxsim* h, const MsRoute& r, const float* Q_dev, int nq, int q_l
   const float unscale_d = 1.f / h->d_scale;
   const long n = (long)h->n_docs;
   float* full_dev = ws.as<float>();
-  switch (r.form) {
+  switch (r.form) {  // (ring, blocked and two-pass forms: the batch in the grid's x, <= 65 535 document blocks in y by ms_route)
     case MsForm::Ring:
       AMDR_MS_LAUNCH((maxsim_scores_ring_kernel<kRing>), dim3(ceil_div(nq, kMsQ), ceil_div(n, r.docs)), dim3(kMsQ * 64),
                      kRing * 16384, st, h->img, h->doc_ptr, n, r.docs, Q_dev, nq, q_len, full_dev, unscale_d);
@@ -1167,14 +1167,22 @@ int ms_run(amdr_maxsim* h, const MsRoute& r, const float* Q_dev, int nq, int q_l
       AMDR_MS_LAUNCH(maxsim_scores_blocked_kernel, dim3(ceil_div(nq, kMsQ), ceil_div(n, r.docs)), dim3(kMsQ * 64), 0, st, h->D,
                      h->doc_ptr, n, Q_dev, nq, q_len, full_dev);
       break;
-    case MsForm::PairHalf:
-      AMDR_MS_LAUNCH(maxsim_scores_h_kernel, dim3(ceil_div(n, r.docs), nq), dim3(256), 0, st, h->img, h->doc_ptr, n, Q_dev,
-                     q_len, full_dev, unscale_d);
+    case MsForm::PairHalf:  // the pair forms carry the batch in the grid's y: pieces (grid_y_pieces)
+    case MsForm::PairF32: {
+      const int rc = grid_y_pieces(nq, [&](int q0, int m) -> int {
+        const float* Qp = Q_dev + (size_t)q0 * q_len * kDim;
+        float* out = full_dev + (size_t)q0 * n;
+        if (r.form == MsForm::PairHalf)
+          AMDR_MS_LAUNCH(maxsim_scores_h_kernel, dim3(ceil_div(n, r.docs), m), dim3(256), 0, st, h->img, h->doc_ptr, n, Qp,
+                         q_len, out, unscale_d);
+        else
+          AMDR_MS_LAUNCH(maxsim_scores_kernel, dim3(ceil_div(n, r.docs), m), dim3(256), 0, st, h->D, h->doc_ptr, n, Qp, q_len,
+                         out);
+        return AMDR_OK;
+      });
+      if (rc) return rc;
       break;
-    case MsForm::PairF32:
-      AMDR_MS_LAUNCH(maxsim_scores_kernel, dim3(ceil_div(n, r.docs), nq), dim3(256), 0, st, h->D, h->doc_ptr, n, Q_dev, q_len,
-                     full_dev);
-      break;
+    }
     case MsForm::TwoPass:
       return ms_run_two_pass(h, r, Q_dev, nq, q_len, k, ws, scores_dev, ids_dev, st);
   }

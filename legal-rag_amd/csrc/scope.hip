@@ -401,7 +401,7 @@ int sc_device_region(amdr_scope* s, int chan, int nq, int k, int64_t rows_max, u
   return AMDR_OK;
 }
 
-// Launches of one channel: the grid's y holds at most 65 535 queries, longer batches go in pieces.  launch(q0, m, slab,
+// Launches of one channel: the batch is the grid's y, so it goes in pieces (grid_y_pieces).  launch(q0, m, slab,
 // slabs, cap, out_scores, out_ids) enqueues the scoring kernel of queries [q0, q0 + m); out: where its lists go — the
 // slab lists in `region`, merged behind it, or, with a single slab, the queries' rows of the result.
 template <class T, class Launch>
@@ -409,20 +409,15 @@ int sc_run(int chan, int nq, int k, int64_t rows_max, unsigned char* region, T* 
            Launch&& launch) {
   const int slab = scope_slab(chan), slabs = scope_slabs(chan, rows_max);
   const int cap = topk_cap(k);
-  for (int q0 = 0; q0 < nq; q0 += 65535) {
-    const int m = nq - q0 < 65535 ? nq - q0 : 65535;
+  return grid_y_pieces(nq, [&](int q0, int m) -> int {
     T* fs = scores_dev + (size_t)q0 * k;
     int64_t* fi = ids_dev + (size_t)q0 * k;
     T* ps = slabs > 1 ? reinterpret_cast<T*>(region) : fs;
     int64_t* pi = slabs > 1 ? reinterpret_cast<int64_t*>(region + scope_score_bytes(chan, slabs, nq, k)) : fi;
     launch(q0, m, slab, slabs, cap, ps, (long long*)pi);
     AMDR_HIP(hipGetLastError());
-    if (slabs > 1) {
-      int rc = launch_merge_parts<T>(ps, pi, slabs, m, k, k, fs, fi, st);
-      if (rc) return rc;
-    }
-  }
-  return AMDR_OK;
+    return slabs > 1 ? launch_merge_parts<T>(ps, pi, slabs, m, k, k, fs, fi, st) : AMDR_OK;
+  });
 }
 
 int sc_dense_run(amdr_dense_t* dense, const float* Q, const ScTable& t, int nq, int k, unsigned char* region,
