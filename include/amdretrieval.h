@@ -654,6 +654,36 @@ int amdr_fuse_compact_device(int32_t nq, int32_t max_out, int32_t w, const int64
                              const int32_t* mask, const int32_t* count, int64_t* out_rows, double* out_scores,
                              int32_t* out_mask, int32_t* out_count, int32_t device, void* stream);
 
+/* ---- diversification: maximal-marginal-relevance (MMR) selection over the resident chunk matrix -------------------
+ * Picks k_sel of a query's first `pool` fused hits, trading relevance against similarity to the hits already picked
+ * (Carbonell & Goldstein 1998).  The reference has no such stage and no call site for it: this is the project's own, as
+ * scoped search is.  One block per query; no workspace, no atomics, deterministic (csrc/mmr.hip).
+ *
+ * Per query q:  m = min(max(count[q], 0), pool);  rows[q][0..m) are rows of `dense` in fused-rank order
+ * (rows + q*ld_rows);  rel[q][i] is the double at rel + q*rel_ld + i*rel_stride (a packed fused result: rel_stride =
+ * AMDR_FUSE_NVALS, rel_ld = max_out*AMDR_FUSE_NVALS, rel pointing at AMDR_FV_SCORE; a plain matrix: 1, ld).
+ *   Gram:    G[i][j] = the fp32 inner product of X[rows[i]] and X[rows[j]] (summation order unspecified); ONE value
+ *            serves (i, j) and (j, i).  A candidate whose row is < 0 or >= n has no vector: its G row and column are 0.
+ *   cosine:  cos[i][j] = (double)G[i][j] / sqrt((double)G[i][i] * (double)G[j][j]) in fp64, no contraction; 0 when the
+ *            denominator is not finite and > 0, or G[i][j] is not finite.
+ *   greedy:  min(k_sel, m) steps.  maxsim[i] = the maximum of cos[i][j] over the j selected so far, 0.0 while there is
+ *            none;  mmr[i] = lambda * rel[i] - (1.0 - lambda) * maxsim[i] (two fp64 products, one subtraction).  A step
+ *            selects the unselected i of the largest mmr[i]; ties go to the lower i; a NaN ranks behind every number
+ *            (-inf included) and NaNs keep position order.
+ * Outputs [nq, k_sel], in selection order: out_pos (the position i; -1 past out_count[q]), out_mmr (the winning value;
+ * 0.0), out_maxsim (its maxsim when it was selected; 0.0); out_count [nq] = min(k_sel, m).
+ * Errors (AMDR_EINVAL): a null pointer, pool outside [1, AMDR_MMR_MAX_POOL], k_sel outside [1, pool], lambda outside
+ * [0, 1] or NaN, ld_rows < pool, nq < 0, rel_stride < 1 or rel_ld < 0.  nq == 0 succeeds and does nothing.
+ * amdr_mmr_device only enqueues on `stream` (capturable, no reserve call); amdr_mmr takes host pointers, runs on the
+ * handle's own stream under its mutex and synchronises. */
+#define AMDR_MMR_MAX_POOL 64
+int amdr_mmr_device(amdr_dense_t* dense, const int64_t* rows_dev, int32_t ld_rows, const double* rel_dev,
+                    int64_t rel_stride, int64_t rel_ld, const int32_t* count_dev, int32_t nq, int32_t pool, int32_t k_sel,
+                    double lambda, int32_t* out_pos, double* out_mmr, double* out_maxsim, int32_t* out_count, void* stream);
+int amdr_mmr(amdr_dense_t* dense, const int64_t* rows_host, int32_t ld_rows, const double* rel_host, int64_t rel_stride,
+             int64_t rel_ld, const int32_t* count_host, int32_t nq, int32_t pool, int32_t k_sel, double lambda,
+             int32_t* out_pos, double* out_mmr, double* out_maxsim, int32_t* out_count);
+
 /* ---- graph channel: law-graph walk + re-scoring of the walked articles --------------------------------------------
  * Replaces, for a whole batch, the per-query host stage HybridRetriever.search runs for a GRAPH_AUGMENTED decision
  * (legalrag/retrieval/hybrid_retriever.py:312-322): LawGraphStore.walk (graph_store.py:89-169, a Python BFS over up to

@@ -17,6 +17,7 @@ import numpy as np
 
 LIB_NAME = "libamdretrieval.so"
 MAX_K = 256
+MMR_MAX_POOL = 64  # AMDR_MMR_MAX_POOL
 MAX_DIM = 1024
 MAXSIM_DIM = 128
 MAXSIM_QLEN = 32
@@ -49,6 +50,7 @@ SIGNATURES = {
     "amdr_fuse": "Pi" + "PPi" * 3 + "PPPP", "amdr_fuse_device": "Pi" + "PPiP" * 3 + "PPPP" + "iP",
     "amdr_rerank_blend": "iiPPPPPidP", "amdr_rerank_blend_device": "iiPPPPPidPiP",
     "amdr_fuse_compact_device": "iiiPPPPPPPPiP",
+    "amdr_mmr_device": "PPiPllPiiidPPPPP", "amdr_mmr": "PPiPllPiiidPPPP",
     "amdr_merge_topk_f32_device": "PPiiiiPPiP", "amdr_merge_topk_f64_device": "PPiiiiPPiP",
     "amdr_shard_row_words": "PiP", "amdr_shard_pack_device": "PiilPiP", "amdr_shard_merge_device": "PiiPiiP",
     "amdr_graph_create": "P" * 11 + "illiiP", "amdr_graph_reserve": "Piii", "amdr_graph_walk": "PPPiiiP" + "P" * 7,
@@ -368,6 +370,57 @@ class DenseIndex(_Handle):
         _check(load().amdr_dense_score_rows(self._h, _p(Q, C.c_float), C.c_int32(Q.shape[0]), _p(rows, C.c_int64),
                                             C.c_int32(rows.shape[1]), _p(out, C.c_float)), "amdr_dense_score_rows")
         return out
+
+    def mmr(self, rows: np.ndarray, rel: np.ndarray, count: np.ndarray, pool: int, k_sel: int,
+            lam: float) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+        """Maximal-marginal-relevance selection (amdr_mmr; the definition is in include/amdretrieval.h): rows [nq, >= pool]
+        int64 rows of this index in rank order, rel [nq, >= pool] float64 (a strided view, such as the score column of a
+        packed fused result, is read in place), count [nq].  -> (pos, mmr, maxsim) [nq, k_sel] and count [nq]."""
+        rows = np.asarray(rows, dtype=np.int64)
+        if rows.ndim != 2 or rows.shape[0] and (rows.strides[1] != 8 or rows.strides[0] % 8 or rows.strides[0] < 0):
+            rows = _c(rows, np.int64).reshape(len(rows), -1)
+        nq = rows.shape[0]
+        rel = np.asarray(rel, dtype=np.float64)
+        if rel.ndim != 2 or nq and (rel.strides[1] % 8 or rel.strides[1] < 8 or rel.strides[0] % 8 or rel.strides[0] < 0):
+            rel = _c(rel, np.float64).reshape(nq, -1)
+        count = _c(count, np.int32).reshape(-1)
+        if rel.shape[0] != nq or count.shape[0] != nq:
+            raise ValueError(f"mmr: rows, rel and count disagree on the batch ({nq}, {rel.shape[0]}, {count.shape[0]})")
+        if nq and rel.shape[1] < min(int(pool), rows.shape[1]):
+            raise ValueError(f"mmr: rel holds {rel.shape[1]} columns, fewer than the pool of {pool}")
+        ks = max(int(k_sel), 0)
+        pos = np.empty((nq, ks), dtype=np.int32)
+        val = np.empty((nq, ks), dtype=np.float64)
+        sim = np.empty((nq, ks), dtype=np.float64)
+        cnt = np.empty(nq, dtype=np.int32)
+        ld_rows = rows.strides[0] // 8 if nq > 1 else rows.shape[1]
+        rel_stride, rel_ld = (rel.strides[1] // 8, rel.strides[0] // 8) if nq else (1, 0)
+        _check(load().amdr_mmr(self._h, _p(rows, C.c_int64), C.c_int32(ld_rows), _p(rel, C.c_double), C.c_int64(rel_stride),
+                               C.c_int64(rel_ld), _p(count, C.c_int32), C.c_int32(nq), C.c_int32(pool), C.c_int32(k_sel),
+                               C.c_double(lam), _p(pos, C.c_int32), _p(val, C.c_double), _p(sim, C.c_double),
+                               _p(cnt, C.c_int32)), "amdr_mmr")
+        return pos, val, sim, cnt
+
+    def mmr_device(self, rows, rel, count, nq: int, pool: int, k_sel: int, lam: float, out_pos, out_mmr, out_maxsim,
+                   out_count, *, ld_rows: Optional[int] = None, rel_stride: Optional[int] = None,
+                   rel_ld: Optional[int] = None, stream: int = 0) -> None:
+        """amdr_mmr_device: enqueue only, no workspace.  Every buffer is a torch tensor on this index's device or a device
+        address; the strides (in elements) default to those of the tensors `rows` [nq, ld] and `rel` [nq, pool] (a view)."""
+        def addr(t):
+            return int(t.data_ptr()) if hasattr(t, "data_ptr") else int(t or 0)
+
+        def stride(t, axis, given, what):
+            if given is not None:
+                return int(given)
+            if not hasattr(t, "stride"):
+                raise ValueError(f"mmr_device: {what} is needed when a device address is passed")
+            return int(t.stride(axis))
+        _check(load().amdr_mmr_device(self._h, _vp(addr(rows)), C.c_int32(stride(rows, 0, ld_rows, "ld_rows")), _vp(addr(rel)),
+                                      C.c_int64(stride(rel, 1, rel_stride, "rel_stride")),
+                                      C.c_int64(stride(rel, 0, rel_ld, "rel_ld")), _vp(addr(count)), C.c_int32(nq),
+                                      C.c_int32(pool), C.c_int32(k_sel), C.c_double(lam), _vp(addr(out_pos)),
+                                      _vp(addr(out_mmr)), _vp(addr(out_maxsim)), _vp(addr(out_count)), _vp(stream)),
+               "amdr_mmr_device")
 
     def read_rows(self, row0: int, nrows: int) -> np.ndarray:
         out = np.empty((nrows, self.d), dtype=np.float32)

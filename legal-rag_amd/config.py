@@ -92,14 +92,25 @@ class RetrievalConfig:
     dense_image: str = "none"            # resident half-precision copy of the chunk matrix for the fp16 first pass of
                                          # large dense scans: "none" | "fp16" (+ ceil(n/32)*32*d*2 bytes of HBM; the
                                          # exact re-scoring keeps every id and score bit, csrc/dense_hi_image.hpp)
+    diversity_lambda: Optional[float] = None  # MMR selection over the fused hits (retrieval/diversity.py) as the default
+                                         # of every search: the weight of the relevance in [0, 1]; None: off
+    diversity_pool: int = 0              # its candidates per question, at most 64; 0: min(64, max(3 * top_k, 10))
 
     def __post_init__(self) -> None:
         query_tokenizer_mode(self)
         graph_channel_mode(self)
         dense_image_mode(self)
+        diversity_default(self)
 
 
 QUERY_TOKENIZERS = ("host", "device")
+
+
+def diversity_default(cfg):
+    """`diversity_lambda` / `diversity_pool` of a RetrievalConfig (or of `cfg.retrieval`) as a retrieval.diversity.Diversity,
+    None while diversity_lambda is None; ValueError / TypeError for values a Diversity refuses."""
+    from .retrieval.diversity import configured
+    return configured(getattr(cfg, "retrieval", cfg))
 
 
 def query_tokenizer_mode(cfg) -> str:

@@ -214,6 +214,9 @@ int dense_device_of(const amdr_dense_t* h);
 // the resident chunk matrix of a dense handle (graph.hip re-scores walked articles against it)
 void dense_matrix(const amdr_dense_t* h, const float** X, long* n, int* d);
 const DenseFp16Stats& dense_fp16_stats_of(const amdr_dense_t* h);  // its statistics of that matrix
+// the staging buffer (>= bytes) and the stream of a dense handle's host-pointer entry points; the caller holds
+// dense_mutex(h) until it has synchronised that stream (mmr.hip amdr_mmr)
+int dense_host_stage(amdr_dense_t* h, size_t bytes, void** dev, hipStream_t* st);
 
 // ---- ordered row compaction into a new buffer: rows_compact.hip (amdr_dense_remove, amdr_maxsim_remove; the map is
 // rows_compact.hpp's; remove_ids is a DEVICE copy of a validated list) ----

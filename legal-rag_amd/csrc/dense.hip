@@ -954,6 +954,13 @@ int dense_small_raw(amdr_dense_t* h, int nq, DenseRaw* out) {
 std::mutex& dense_mutex(amdr_dense_t* h) { return h->mu; }
 int dense_device_of(const amdr_dense_t* h) { return h->device; }
 const DenseFp16Stats& dense_fp16_stats_of(const amdr_dense_t* h) { return h->fp16; }
+int dense_host_stage(amdr_dense_t* h, size_t bytes, void** dev, hipStream_t* st) {
+  const int rc = h->sbuf.ensure(bytes);
+  if (rc) return rc;
+  *dev = h->sbuf.p;
+  *st = h->stream;
+  return AMDR_OK;
+}
 void dense_matrix(const amdr_dense_t* h, const float** X, long* n, int* d) {
   *X = h->X;
   *n = (long)h->n;

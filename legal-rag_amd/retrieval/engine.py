@@ -11,6 +11,7 @@ and bench.py sit on top of it; the single-query API uses the same kernels.
 """
 from __future__ import annotations
 
+import math
 import os
 from dataclasses import dataclass
 from typing import Optional
@@ -94,6 +95,11 @@ class BatchResult:
     packed: Optional[torch.Tensor] = None  # u8: ids | vals | mask | count in ONE allocation (one D2H for the host API)
     needs_segmenter: Optional[torch.Tensor] = None  # i32 [nq] of a text-in step (q_text): 1 = Han query, no BM25 terms
     graph: Optional[dict] = None  # graph_topk outputs of a captured step that ends with the graph stage
+    # after diversify(): per selected hit its position in the fused list it was picked from, the winning MMR value and
+    # its largest cosine to the hits picked before it (i32 / f64 / f64 [nq, k_sel])
+    mmr_pos: Optional[torch.Tensor] = None
+    mmr: Optional[torch.Tensor] = None
+    mmr_max_sim: Optional[torch.Tensor] = None
 
     def to_host(self):
         """(ids, vals, mask, count) as numpy arrays through ONE device-to-host copy (the first `.cpu()` of a result
@@ -495,17 +501,72 @@ class HybridEngine:
         res.rerank = out
         return res
 
+    # -- diversification ------------------------------------------------------
+    def check_diversify(self) -> None:
+        """ValueError unless diversify() can run on this engine; launches nothing."""
+        if self.shard_offset is not None:
+            raise ValueError("diversify: MMR selection does not run on a row-sharded index (the candidate rows are global)")
+        if self.maps[0] is not None:
+            raise ValueError("diversify: this engine maps dense rows to ids (dense_row2uid); the fused ids are then no "
+                             "rows of the chunk matrix")
+        if self.dense is None:
+            raise ValueError("diversify: MMR selection needs the dense index (the cosine is taken between its rows)")
+
+    def diversify(self, res: BatchResult, k_sel: int, lam: float, pool: int) -> BatchResult:
+        """MMR selection over the first `pool` fused hits of every query (amdr_mmr_device on the current stream, after the
+        optional rerank blend): a new result of width k_sel that holds the selected hits in selection order — ids / vals /
+        mask (/ rerank) gathered by position, count = min(k_sel, count, pool), -1 / 0 past it — with mmr_pos / mmr /
+        mmr_max_sim beside it.  The fused ids are rows of the dense matrix (no dense_row2uid map, not row-sharded:
+        ValueError).  Needs no reserve; capturable."""
+        self.check_diversify()
+        nq, mo = (int(x) for x in res.ids.shape)
+        pool = max(1, min(int(pool), mo, _native.MMR_MAX_POOL))
+        k_sel = max(1, min(int(k_sel), pool))
+        o1, o2, o3, tot = packed_layout(nq, k_sel)
+        pk = self._buf("mpk", (tot,), torch.uint8)
+        ids, vals = pk[:o1].view(torch.int64).view(nq, k_sel), pk[o1:o2].view(torch.float64).view(nq, k_sel, NV)
+        mask, count = pk[o2:o3].view(torch.int32).view(nq, k_sel), pk[o3:].view(torch.int32)
+        pos = self._buf("mpos", (nq, k_sel), torch.int32)
+        val = self._buf("mval", (nq, k_sel), torch.float64)
+        sim = self._buf("msim", (nq, k_sel), torch.float64)
+        self.dense.mmr_device(res.ids, res.vals[:, :, _native.FV["score"]], res.count, nq, pool, k_sel, float(lam), pos, val,
+                              sim, count, ld_rows=mo, stream=_stream())
+        # the reorder: gathers on the same stream (a fused reorder kernel is not part of this stage)
+        none = self._buf("mnone", (nq, k_sel), torch.bool)
+        torch.lt(pos, 0, out=none)
+        at = self._buf("mat", (nq, k_sel), torch.int64)
+        at.copy_(pos)
+        at.clamp_(min=0)
+        torch.gather(res.ids, 1, at, out=ids)
+        ids.masked_fill_(none, -1)
+        torch.gather(res.mask, 1, at, out=mask)
+        mask.masked_fill_(none, 0)
+        torch.gather(res.vals, 1, at[:, :, None].expand(nq, k_sel, NV), out=vals)
+        vals.masked_fill_(none[:, :, None], 0.0)
+        out = BatchResult(ids=ids, vals=vals, mask=mask, count=count, packed=pk, mmr_pos=pos, mmr=val, mmr_max_sim=sim)
+        for name in ("dense_ids", "dense_scores", "bm25_ids", "bm25_scores", "colbert_ids", "colbert_scores",
+                     "needs_segmenter", "graph"):
+            setattr(out, name, getattr(res, name))
+        if res.rerank is not None:
+            out.rerank = self._buf("mrr", (nq, k_sel, 2), torch.float64)
+            torch.gather(res.rerank, 1, at[:, :, None].expand(nq, k_sel, 2), out=out.rerank)
+            out.rerank.masked_fill_(none[:, :, None], math.nan)
+        return out
+
     # -- whole pipeline ---------------------------------------------------------
     def search_batch(self, params: _native.FuseParams, k: int, *, q_emb: Optional[torch.Tensor] = None,
                      q_terms: Optional[torch.Tensor] = None, q_ptr: Optional[torch.Tensor] = None,
-                     q_tok: Optional[torch.Tensor] = None, q_text=None, scopes=None) -> BatchResult:
+                     q_tok: Optional[torch.Tensor] = None, q_text=None, scopes=None, diversity=None) -> BatchResult:
         """dense + bm25 (+ colbert) top-k -> fuse -> min_final filter, all on device.
         q_text = (blob u8, offs i64 [nq + 1]) device tensors: the BM25 query side as text, tokenised on the device
         (tokenize_device) in the same stream, instead of q_terms / q_ptr.
         scopes = (dense table, BM25 table, ColBERT table) (upload_scopes; one per channel's row space, None for a
         channel that is off): every channel ranks each query's own rows and the fusion — its normalisation included —
-        runs over those lists (the SCOPED form).  Not on a row-sharded engine (ValueError)."""
+        runs over those lists (the SCOPED form).  Not on a row-sharded engine (ValueError).
+        diversity = (k_sel, lam, pool): the step ends with diversify(); None: the same launches as ever."""
         flags = None
+        if diversity is not None:
+            self.check_diversify()  # (before any launch)
         if q_text is not None:
             if q_terms is not None or q_ptr is not None:
                 raise ValueError("search_batch: pass q_text or q_terms / q_ptr, not both")
@@ -575,12 +636,13 @@ class HybridEngine:
         if c is not None:
             res.colbert_scores, res.colbert_ids = c
         res.needs_segmenter = flags
-        return res
+        return res if diversity is None else self.diversify(res, *diversity)
 
     # -- hipGraph form -----------------------------------------------------------
     def capture(self, params: _native.FuseParams, k: int, *, q_emb: Optional[torch.Tensor] = None,
                 q_terms: Optional[torch.Tensor] = None, q_ptr: Optional[torch.Tensor] = None,
-                q_tok: Optional[torch.Tensor] = None, q_text=None, graph: Optional[dict] = None, scopes=None):
+                q_tok: Optional[torch.Tensor] = None, q_text=None, graph: Optional[dict] = None, scopes=None,
+                diversity=None):
         """Record one search_batch over the given tensors into a hipGraph.
 
         Returns (graph, result): `graph.replay()` re-runs the whole step — every kernel of every
@@ -597,6 +659,8 @@ class HybridEngine:
         first); its outputs are result.graph.
         scopes: the scoped step (search_batch); a replay takes new tables written INTO the same table tensors (same
         nq; every scope at most the tables' rows_max rows, scope_ptr / rows within the tensors' lengths).
+        diversity = (k_sel, lam, pool): the step ends with diversify() — behind the graph stage, whose seeds are the
+        fused list as it was ranked; the MMR kernel has no workspace, so nothing more is reserved.
         """
         if self.shard_offset is not None:
             raise RuntimeError("capture: a sharded step contains a collective; it is not recorded into a hipGraph")
@@ -619,7 +683,7 @@ class HybridEngine:
             if gstage is not None:
                 r.graph = self.graph_topk(r.ids, r.count, gstage["q_emb"], gstage["k"], gstage["seed_n"],
                                           qsel=gstage.get("qsel"))
-            return r
+            return r if diversity is None else self.diversify(r, *diversity)
         side = torch.cuda.Stream(device=self.tdev)
         side.wait_stream(torch.cuda.current_stream(self.tdev))
         with torch.cuda.stream(side):  # eager warm-up sizes every lazily grown buffer outside the capture

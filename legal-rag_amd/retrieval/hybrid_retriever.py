@@ -37,6 +37,7 @@ from ..schemas import RetrievalHit
 from .bm25_retriever import BM25Retriever
 from .colbert_retriever import ColBERTRetriever
 from .dense_retriever import DenseRetriever
+from .diversity import Diversity, resolve as _resolve_diversity
 from .graph_retriever import GraphRetriever
 from .rerankers import RerankerFactory, _to_doc_text
 from .scope import Scope, resolver_for
@@ -157,6 +158,11 @@ COLUMNS = (
     ("graph_rows", np.int64, -1, ()), ("graph_scores", np.float64, 0.0, ()), ("graph_semantic", np.float32, 0.0, ()),
     ("graph_depth", np.int32, 0, ()), ("graph_relation", np.int32, -1, ()), ("graph_edge_conf", np.float64, 0.0, ()),
     ("graph_count", np.int32, 0, None))
+
+
+# ... and the two more of a diversified call with values=True (diversity=): per selected hit the winning MMR value and its
+# largest cosine to the hits selected before it.
+MMR_COLUMNS = (("mmr", np.float64, 0.0, ()), ("mmr_max_sim", np.float64, 0.0, ()))
 
 
 def _column(n: int, top_k: int, dtype, fill, hit) -> np.ndarray:
@@ -452,14 +458,17 @@ class HybridRetriever:
 
     # ---------------------------------------------------------- main search
     def search(self, question: str, llm: Any = None, top_k: int = 10, decision: Any = None, *,
-               scope: Optional[Scope] = None) -> List[RetrievalHit]:
+               scope: Optional[Scope] = None, diversity: Any = None) -> List[RetrievalHit]:
         """`scope` (retrieval/scope.py): every channel ranks only that part of the corpus and the fusion normalises over
-        those lists — the one-question form of search_batch(scopes=).  None: the whole corpus."""
+        those lists — the one-question form of search_batch(scopes=).  None: the whole corpus.
+        `diversity` (retrieval/diversity.py): a Diversity makes MMR selection the last stage, None takes the configured
+        default (cfg.retrieval.diversity_lambda), False switches it off."""
         if scope is not None:
             return self.search_batch([question], top_k=top_k, llm=llm, decisions=None if decision is None else [decision],
-                                     scopes=[scope])[0]
+                                     scopes=[scope], diversity=diversity)[0]
         rcfg = self.cfg.retrieval
         top_k = max(1, int(top_k))
+        mmr = self._diversity(diversity, top_k, "search")
         has_gpu = _native.device_count() > 0
         t_start = time.time()
         eff_top_k = self._eff_depth(top_k, "search")
@@ -502,6 +511,8 @@ class HybridRetriever:
             t_rerank = time.time()
 
         fused = _dedup_keep_best(fused)
+        if mmr is not None:
+            fused = self._mmr_stage([fused], top_k, *mmr)[0]
         t_end = time.time()
 
         def ms(a, b):
@@ -513,6 +524,64 @@ class HybridRetriever:
             ms((t_graph or t4), t_rerank) if t_rerank else 0, ms(t_start, t_end),
             int(bool(getattr(rcfg, "enable_graph", False))), int(self.colbert is not None), int(has_gpu))
         return fused[:top_k]
+
+    # ------------------------------------------------------- diversification
+    def _diversity(self, diversity: Any, top_k: int, who: str):
+        """(Diversity, pool) of a call, or None when the stage is off — and every refusal, before anything is launched:
+        top_k beyond the kernel's pool, a row-sharded index, no dense index of this package's own on the GPU."""
+        div = _resolve_diversity(diversity, self.cfg.retrieval)
+        if div is None:
+            return None
+        try:
+            pool = div.pool_for(top_k)
+        except ValueError as e:
+            raise ValueError(f"HybridRetriever.{who}: {e}") from None
+        index = None
+        store = getattr(self.dense, "store", None)
+        if store is not None:
+            try:
+                store.load()
+                index = getattr(store, "index", None)
+            except Exception:  # noqa: BLE001 - reported as "no index" below
+                index = None
+        if index is not None and getattr(index, "spec", None) is not None:
+            raise ValueError(f"HybridRetriever.{who}: diversity (MMR selection) does not run on a row-sharded index "
+                             f"(the candidate rows are global)")
+        if index is None or getattr(index, "native", None) is None:
+            raise ValueError(f"HybridRetriever.{who}: diversity (MMR selection) needs this package's own dense index "
+                             f"resident on the GPU: the cosine is taken between its rows, and there is no CPU path")
+        return div, pool
+
+    def _mmr_stage(self, lists: List[List[RetrievalHit]], top_k: int, div: Diversity, pool: int) -> List[List[RetrievalHit]]:
+        """The last stage of the hit-object paths, behind _dedup_keep_best (which re-sorts by score): MMR selection over the
+        first `pool` hits of every list in ONE batched call (amdr_mmr).  relevance = hit.score, candidate row = the chunk's
+        row of the dense store (-1: a chunk the store does not hold has no vector and is similar to nothing).  Returns the
+        selected hits in selection order, cut to top_k: rank renumbered, score untouched, score_breakdown gains "mmr" and
+        "mmr_max_sim"."""
+        nq = len(lists)
+        if nq == 0:
+            return lists
+        store = self.dense.store
+        row_of = resolver_for(store.chunks).row_of
+        rows = np.full((nq, pool), -1, dtype=np.int64)
+        rel = np.zeros((nq, pool), dtype=np.float64)
+        count = np.zeros(nq, dtype=np.int32)
+        for q, hits in enumerate(lists):
+            m = count[q] = min(len(hits), pool)
+            rows[q, :m] = [row_of(h.chunk.id) for h in hits[:m]]
+            rel[q, :m] = [float(h.score) for h in hits[:m]]
+        pos, val, sim, cnt = store.index.native.mmr(rows, rel, count, pool, min(top_k, pool), div.lam)
+        outs = []
+        for q, hits in enumerate(lists):
+            out = []
+            for j in range(int(cnt[q])):
+                h = hits[int(pos[q, j])]
+                sb = h.score_breakdown or {}
+                sb["mmr"], sb["mmr_max_sim"] = float(val[q, j]), float(sim[q, j])
+                h.score_breakdown, h.rank = sb, j + 1
+                out.append(h)
+            outs.append(out)
+        return outs
 
     @staticmethod
     def _hit_text(h: Any) -> str:
@@ -744,13 +813,14 @@ class HybridRetriever:
                 col, q_tok = None, None
         return _Prepared((store, bm, col), q_emb, csr, txt, np.asarray(exact, dtype=bool), q_tok, (t1, t2, time.time()))
 
-    def _run(self, prep: "_Prepared", params: "_native.FuseParams", eff: int, fetch, after=None, scope_table=None):
+    def _run(self, prep: "_Prepared", params: "_native.FuseParams", eff: int, fetch, after=None, scope_table=None, mmr=None):
         """Step 2, under the stage lock (one batch at a time through the handles' "_device" workspace,
         include/amdretrieval.h): engine, upload, eng.search_batch on torch's current stream, the ColBERT fallback,
         `after(engine, result)` (the device graph stage), then `fetch(engine, result)` — the ONE synchronise and
         device-to-host copy of the form the caller decodes.  Returns (what fetch returned, what after returned).
         scope_table (ScopeResolver.table of the batch): the scoped step — the three channels share one chunk list here
-        (_native_channels), so one table serves them all."""
+        (_native_channels), so one table serves them all.  mmr = (k_sel, lam, pool): the result is diversified on the device
+        (HybridEngine.diversify) behind `after`, whose seeds are the fused list as ranked, and in front of `fetch`."""
         import torch
         (store, bm, col), tdev = prep.native, prep.q_emb.device
         with self._stage().lock:
@@ -786,6 +856,8 @@ class HybridRetriever:
                 eng = self._engine(store, bm, None)
                 res = eng.search_batch(params, eff, q_emb=prep.q_emb, q_terms=q_terms_d, q_ptr=q_ptr_d, **scoped(eng, False))
             extra = after(eng, res) if after is not None else None
+            if mmr is not None:
+                res = eng.diversify(res, *mmr)
             return fetch(eng, res), extra
 
     # Step 3, the decoders: host arrays of ONE fetch -> the caller's form.
@@ -862,7 +934,8 @@ class HybridRetriever:
         by = {sc: list(idxs) for idxs, sc, _ in parts}
         return by.get(False, []), by.get(True, []), empty
 
-    def _run_part(self, part, questions, scopes, q_emb, native, device_tok: bool, params, eff: int, fetch, decode, graph=None):
+    def _run_part(self, part, questions, scopes, q_emb, native, device_tok: bool, params, eff: int, fetch, decode, graph=None,
+                  mmr=None):
         """One part of a batch in one engine run: _prepare -> the scope table of a scoped part -> _run -> `decode(host
         arrays, exact)`; `graph` (what _graph_device_stage returned) rides the part it names.  Returns (what decode
         returned, the _Prepared's time stamps, what the graph stage returned).  A part that is the whole batch takes the
@@ -875,7 +948,7 @@ class HybridRetriever:
             q_emb = None if q_emb is None else q_emb[idxs]
         prep = self._prepare(questions, (store, bm, col if with_col else None), q_emb, device_tok)
         table = resolver_for(store.chunks).table([scopes[i] for i in idxs]) if scoped else None
-        host, extra = self._run(prep, params, eff, fetch, after, table)
+        host, extra = self._run(prep, params, eff, fetch, after, table, mmr)
         return decode(host, prep.exact), prep.stamps, extra
 
     def _hit_lists(self, questions: Sequence[str], parts, eff: int, native, min_final: float, q_emb=None,
@@ -905,7 +978,7 @@ class HybridRetriever:
 
     def search_batch(self, questions: Sequence[str], top_k: int = 10, llm: Any = None,
                      decisions: Optional[Sequence[Any]] = None, q_emb=None, *,
-                     scopes: Optional[Sequence[Optional[Scope]]] = None) -> List[List[RetrievalHit]]:
+                     scopes: Optional[Sequence[Optional[Scope]]] = None, diversity: Any = None) -> List[List[RetrievalHit]]:
         """Throughput form: `search_batch(qs)[i]` == `search(qs[i])` for every stage the configuration enables
         (hybrid_retriever.py:282-384) — one kernel pipeline for the whole batch (dense + BM25 (+ ColBERT) -> fuse
         -> filter), the graph stage per query whose `decisions[i]` asks for it, the rerank stage with the
@@ -913,10 +986,12 @@ class HybridRetriever:
         `scopes` (one Scope or None per question, retrieval/scope.py): a scoped question's channels rank only its part of
         the corpus and its fusion normalises over those lists; the questions with None run as one part through the
         unscoped step, the scoped ones as another; a scope that matches nothing yields [].  A graph-mode decision with a
-        scope raises ValueError."""
+        scope raises ValueError.
+        `diversity`: as search — MMR selection as the last stage, ONE batched call for all questions."""
         rcfg = self.cfg.retrieval
         top_k = max(1, int(top_k))
         questions = list(questions)
+        mmr = self._diversity(diversity, top_k, "search_batch")
         eff = self._eff_depth(top_k, "search_batch")
         native = self._native_channels(eff)
         if native is None:
@@ -945,7 +1020,10 @@ class HybridRetriever:
         # rerank, dedup and cut run once, over the whole batch (a question whose scope matches nothing has no candidate)
         if getattr(rcfg, "enable_rerank", False):
             outs = self._rerank_stage(questions, outs, llm, top_k)
-        return [_dedup_keep_best(hits)[:top_k] for hits in outs]
+        outs = [_dedup_keep_best(hits) for hits in outs]
+        if mmr is not None:
+            outs = self._mmr_stage(outs, top_k, *mmr)
+        return [hits[:top_k] for hits in outs]
 
     def _graph_device_stage(self, parts, questions: Sequence[str], sel: Sequence[int], k: int, seed_n: int, native,
                             lang: Optional[str] = None):
@@ -1005,8 +1083,9 @@ class HybridRetriever:
         out: Dict[str, Any] = {"chunks": chunks}
         if values:
             out["value_names"] = dict(_native.FV)
-        for name, dt, fill, hit in COLUMNS:
-            if any(name in cols for _, cols in parts) or not (name.startswith("graph_") or (name == "values" and not values)):
+        for name, dt, fill, hit in COLUMNS + MMR_COLUMNS:
+            if any(name in cols for _, cols in parts) or not (name.startswith(("graph_", "mmr")) or
+                                                              (name == "values" and not values)):
                 out[name] = _column(n, top_k, dt, fill, hit)
                 for idxs, cols in parts:
                     if name in cols:
@@ -1018,7 +1097,7 @@ class HybridRetriever:
 
     def search_batch_arrays(self, questions: Sequence[str], top_k: int = 10, q_emb=None, values: bool = True,
                             decisions: Optional[Sequence[Any]] = None, *,
-                            scopes: Optional[Sequence[Optional[Scope]]] = None) -> Dict[str, Any]:
+                            scopes: Optional[Sequence[Optional[Scope]]] = None, diversity: Any = None) -> Dict[str, Any]:
         """`search_batch` without building RetrievalHit objects (pydantic construction, not the GPU, bounds
         `search_batch` at a few thousand queries/s): columnar results for bulk callers (evaluation sweeps,
         offline scoring).  rows[q, j] indexes `self.dense.store.chunks`; entries j >= count[q] are -1 / 0.
@@ -1031,9 +1110,14 @@ class HybridRetriever:
         graph_semantic / graph_depth / graph_relation (index into graph_relation_names) / graph_edge_conf [n, top_k] and
         graph_count [n] (0 for the other queries).
         `scopes`: as search_batch — one Scope or None per question; a scope that matches nothing gives count 0.
+        `diversity`: as search — the selection runs on the device inside the stage (HybridEngine.diversify) over the
+        fused list of every part, scoped ones included; the columns hold the selected hits in selection order and, with
+        values=True, `mmr` and `mmr_max_sim` [n, top_k] beside them (MMR_COLUMNS).
         COLUMNS holds every column's dtype and the fill of a question or hit without a result."""
         rcfg = self.cfg.retrieval
         top_k = max(1, int(top_k))
+        mmr = self._diversity(diversity, top_k, "search_batch_arrays")
+        mmr = None if mmr is None else (top_k, mmr[0].lam, mmr[1])
         eff = self._eff_depth(top_k, "search_batch_arrays")
         native = self._native_channels(eff)
         if native is None:
@@ -1047,7 +1131,15 @@ class HybridRetriever:
         graph_on = decisions is not None and getattr(rcfg, "enable_graph", False) and self.graph is not None
         graph = self._graph_device_stage(parts, questions, sel, top_k, seed_n, native) if graph_on and sel else None
         params = self._params(self._knobs(), float(getattr(rcfg, "min_final_score", 0.0)))
-        if values:
+        if values and mmr is not None:
+            def fetch(eng, res):
+                return res.to_host(), res.mmr.cpu().numpy(), res.mmr_max_sim.cpu().numpy()
+
+            def decode(host, exact):
+                cols = self._decode_columns(host[0], exact, top_k, chunks)
+                cols["mmr"], cols["mmr_max_sim"] = host[1], host[2]
+                return cols
+        elif values:
             fetch, decode = _fetch_full, lambda host, exact: self._decode_columns(host, exact, top_k, chunks)
         else:
             fetch, decode = (lambda eng, res: eng.compact_to_host(res, top_k),
@@ -1055,7 +1147,7 @@ class HybridRetriever:
         done = []
         for part in parts:
             cols, _, g = self._run_part(part, questions, scopes, q_emb, native, query_tokenizer_mode(self.cfg) == "device",
-                                        params, eff, fetch, decode, graph)
+                                        params, eff, fetch, decode, graph, mmr)
             if graph_on and not part[1]:
                 self._graph_columns(cols, g, graph[1] if graph is not None else [], top_k)
             done.append((part[0], cols))

@@ -66,6 +66,11 @@ class ScopeResolver:
             return np.zeros(0, dtype=np.int64)
         return np.unique(np.concatenate([np.asarray(p, dtype=np.int64) for p in parts]))
 
+    def row_of(self, chunk_id: Any) -> int:
+        """The (first) row of the chunk with this id, -1 when the list holds none."""
+        rows = self._by["id"].get(str(chunk_id))
+        return int(rows[0]) if rows else -1
+
     def rows(self, scope: Scope) -> np.ndarray:
         got = self._cache.get(scope)
         if got is not None:
