@@ -840,6 +840,54 @@ int amdr_scope_maxsim_search(amdr_scope_t* h, amdr_maxsim_t* maxsim, const float
                              int32_t nq, int32_t k, float* scores_host, int64_t* ids_host);
 int amdr_scope_destroy(amdr_scope_t* h);
 
+/* ---- required and excluded terms: Boolean term constraints resolved into a scope table on the device ---------------
+ * No reference counterpart: the reference's BM25 channel only prefers a query's terms (legalrag/retrieval/
+ * bm25_retriever.py:74-75) and HybridRetriever.search has no filter argument; a caller who wants "articles that contain
+ * seller and goods but not buyer" over-fetches and filters on the host.  csrc/term_scope.hip, csrc/term_scope_rule.hpp.
+ * A constraint is a list of groups; a group is a non-empty list of term ids with a kind: 0 MUST, 1 ANY, 2 NOT.  The id -1
+ * (any id outside [0, n_terms)) is a token the vocabulary does not hold: present in no document.  A document satisfies a
+ * group when it has a posting for EVERY term of the group — a conjunction, NOT a phrase match: the postings hold no
+ * positions.  It qualifies when it satisfies every MUST group, at least one ANY group (or there is none), no NOT group,
+ * and lies in the constraint's base scope, if it has one.
+ * Operands: grp_ptr i64 [n_cons + 1] indexes the groups of each constraint, grp_kind i32 [n_groups], grp_term_ptr i64
+ * [n_groups + 1] indexes grp_terms i32; base_ptr i64 [n_base + 1] indexes base_rows i64 (each base scope strictly
+ * ascending rows of [0, n_docs), as a scope table holds them), cons_base i32 [n_cons] names each constraint's base scope,
+ * -1: the whole corpus.
+ * Output: a scope table in the format of the scoped searches above — out_scope_ptr i64 [n_cons + 1], out_rows i64
+ * [rows_cap], each constraint's qualifying documents strictly ascending — to be handed unchanged, with rows_max =
+ * cand_max, to amdr_scope_*_search_device / amdr_hybrid_scope_device on the same stream (BM25 documents; the dense and
+ * the ColBERT channel take it where they share the BM25 index's chunk list).  Scores do not change: idf and avgdl stay
+ * those of the whole index.  out_status i32 [n_cons]: 0; 1 = the constraint's driver is longer than cand_max, its scope
+ * is left empty; 2 = rows of the constraint lay at positions >= rows_cap and were dropped (scope_ptr is clamped to
+ * rows_cap).  The other constraints of the call are exact either way.
+ * The driver of a constraint — its candidates — is the shortest of { its base scope, the posting list of each term of
+ * its MUST groups }, ties -> the first in that order; an unknown term among the MUST terms makes it empty without
+ * reading anything; with no MUST term and no base scope the candidates are the documents 0 .. n_docs-1 themselves and the
+ * work is proportional to the corpus.  Otherwise work is |driver| x the sum of log2(df) of the other terms: proportional
+ * to the constraint.  cand_max >= the longest driver and rows_cap >= the sum of the drivers always suffice.
+ * Three launches (count, scan, write; grid = constraints x tiles of 1 024 candidates), no atomics, deterministic.
+ * amdr_term_scope_plan is host-only arithmetic: the workspace bytes of a call (16 B + 1 KiB per constraint and tile).
+ * amdr_term_scope_device only enqueues on `stream` and allocates nothing (capturable); AMDR_EINVAL, enqueueing nothing,
+ * for a null handle or array, a negative size, cand_max beyond 65 535 tiles, or work_bytes below the plan.  The handle
+ * itself has no notion of a row shard: a deployment whose BM25 handle holds one rank's rows refuses a term constraint
+ * above this call (retrieval/engine.py), since the base rows and the table would be global.  It does not validate the
+ * operands' contents: terms outside the vocabulary and base rows outside [0, n_docs) are never dereferenced.
+ * amdr_term_scope is the host-pointer twin: it validates (AMDR_EINVAL: a pointer array that does not start at 0 or is not
+ * monotone, grp_ptr not ending at n_groups, an empty group, a kind outside 0 .. 2, base rows not strictly ascending or
+ * outside [0, n_docs), cons_base outside [-1, n_base)), stages the operands, runs on the BM25 handle's own stream under
+ * its mutex and returns the table (out_rows holds rows_cap values; the first out_scope_ptr[n_cons] are written) and the
+ * status array in the host buffers. */
+int amdr_term_scope_plan(int64_t n_cons, int64_t cand_max, int64_t* work_bytes);
+int amdr_term_scope_device(amdr_bm25_t* bm25, const int64_t* grp_ptr_dev, const int32_t* grp_kind_dev,
+                           const int64_t* grp_term_ptr_dev, const int32_t* grp_terms_dev, const int64_t* base_ptr_dev,
+                           const int64_t* base_rows_dev, const int32_t* cons_base_dev, int64_t n_base, int64_t n_cons,
+                           int64_t n_groups, int64_t cand_max, int64_t rows_cap, int64_t* out_scope_ptr_dev,
+                           int64_t* out_rows_dev, int32_t* out_status_dev, void* work_dev, int64_t work_bytes, void* stream);
+int amdr_term_scope(amdr_bm25_t* bm25, const int64_t* grp_ptr, const int32_t* grp_kind, const int64_t* grp_term_ptr,
+                    const int32_t* grp_terms, const int64_t* base_ptr, const int64_t* base_rows, const int32_t* cons_base,
+                    int64_t n_base, int64_t n_cons, int64_t n_groups, int64_t cand_max, int64_t rows_cap,
+                    int64_t* out_scope_ptr, int64_t* out_rows, int32_t* out_status);
+
 /* ---- multi-GPU: merge per-shard top-k after the RCCL all-gather --------
  * No reference counterpart (the reference is single-process).
  * parts: [n_parts, nq, k_in] scores + GLOBAL ids (-1 padding); output

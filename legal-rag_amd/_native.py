@@ -62,6 +62,8 @@ SIGNATURES = {
     "amdr_scope_bm25_search": "PPPPPPPiiiPP", "amdr_scope_maxsim_search": "PPPiPPPiiiPP", "amdr_scope_destroy": "P",
     "amdr_hybrid_scope_device": "PPPPPP" + "PPPil" * 2 + "iii" + "PPP" + "PPiP" + "PPPP" + "PPPP" + "P",
     "amdr_hybrid_scope_plan": "iiiillPP",
+    "amdr_term_scope_plan": "llP", "amdr_term_scope_device": "P" + "P" * 7 + "l" * 5 + "PPP" + "PlP",
+    "amdr_term_scope": "P" + "P" * 7 + "l" * 5 + "PPP",
 }
 EXPORTS = tuple(SIGNATURES)  # every symbol include/amdretrieval.h declares (checked by tests/test_abi.py)
 _KIND = {"P": C.c_void_p, "i": C.c_int32, "l": C.c_int64, "d": C.c_double}
@@ -197,6 +199,16 @@ def bm25_workspace_plan(n_docs: int, nq_max: int, k_max: int, nq: int, k: int) -
     _check(load().amdr_bm25_workspace_plan(C.c_int64(n_docs), C.c_int32(nq_max), C.c_int32(k_max), C.c_int32(nq),
                                            C.c_int32(k), out), "amdr_bm25_workspace_plan")
     return int(out[0]), int(out[1])
+
+
+TERM_SCOPE_TILE = 1024  # candidates per block of amdr_term_scope (kTsTile)
+
+
+def term_scope_plan(n_cons: int, cand_max: int) -> int:
+    """Workspace bytes of BM25Index.term_scope_device(n_cons constraints, longest driver cand_max) — host-only arithmetic."""
+    out = C.c_int64(0)
+    _check(load().amdr_term_scope_plan(C.c_int64(n_cons), C.c_int64(cand_max), C.byref(out)), "amdr_term_scope_plan")
+    return int(out.value)
 
 
 def maxsim_workspace_plan(n_docs: int, split_image: bool, nq_max: int, k_max: int, nq: int, k: int) -> Tuple[int, int]:
@@ -612,6 +624,38 @@ class BM25Index(_Handle):
                       stream: int = 0) -> None:
         _check(load().amdr_bm25_search_device(self._h, _vp(q_terms_ptr), _vp(q_ptr_ptr), C.c_int32(nq), C.c_int32(k),
                                               _vp(scores_ptr), _vp(ids_ptr), _vp(stream)), "amdr_bm25_search_device")
+
+    # -- term constraints -> scope table (amdr_term_scope, csrc/term_scope.hip) ---------------------------------------
+    # operands, in the ABI's order: (grp_ptr i64, grp_kind i32, grp_term_ptr i64, grp_terms i32, base_ptr i64,
+    # base_rows i64, cons_base i32); retrieval/terms.py pack() makes them
+    TERM_OPS = (np.int64, np.int32, np.int64, np.int32, np.int64, np.int64, np.int32)
+
+    def term_scope(self, ops, cand_max: int, rows_cap: int):
+        """The host twin: (scope_ptr i64 [n_cons + 1], rows i64 [scope_ptr[-1]], status i32 [n_cons]) of the constraints
+        `ops` — validated, staged, resolved on the handle's own stream.  status: 0, 1 (driver longer than cand_max: scope
+        empty), 2 (rows beyond rows_cap dropped)."""
+        a = [_c(x, t).ravel() for x, t in zip(ops, self.TERM_OPS)]
+        n_cons, n_groups, n_base = a[6].size, a[1].size, max(a[4].size - 1, 0)
+        if a[0].size != n_cons + 1 or a[2].size != n_groups + 1:
+            raise ValueError("term_scope: grp_ptr [n_cons + 1], grp_term_ptr [n_groups + 1]")
+        sp = np.zeros(n_cons + 1, dtype=np.int64)
+        rows = np.full(max(int(rows_cap), 1), -1, dtype=np.int64)
+        status = np.zeros(max(n_cons, 1), dtype=np.int32)
+        _check(load().amdr_term_scope(self._h, *(_p(x, C.c_int64 if t is np.int64 else C.c_int32)
+                                                 for x, t in zip(a, self.TERM_OPS)),
+                                      C.c_int64(n_base), C.c_int64(n_cons), C.c_int64(n_groups), C.c_int64(cand_max),
+                                      C.c_int64(rows_cap), _p(sp, C.c_int64), _p(rows, C.c_int64), _p(status, C.c_int32)),
+               "amdr_term_scope")
+        return sp, rows[:int(sp[-1])], status[:n_cons]
+
+    def term_scope_device(self, op_ptrs: Sequence[int], n_base: int, n_cons: int, n_groups: int, cand_max: int, rows_cap: int,
+                          scope_ptr_ptr: int, rows_ptr: int, status_ptr: int, work_ptr: int, work_bytes: int,
+                          stream: int = 0) -> None:
+        """The "_device" form: the seven operand arrays and the outputs as device pointers; enqueues only."""
+        _check(load().amdr_term_scope_device(self._h, *(_vp(x) for x in op_ptrs), C.c_int64(n_base), C.c_int64(n_cons),
+                                             C.c_int64(n_groups), C.c_int64(cand_max), C.c_int64(rows_cap),
+                                             _vp(scope_ptr_ptr), _vp(rows_ptr), _vp(status_ptr), _vp(work_ptr),
+                                             C.c_int64(work_bytes), _vp(stream)), "amdr_term_scope_device")
 
     def get_scores(self, queries: Sequence[Sequence[int]]) -> np.ndarray:
         q_terms, q_ptr = self.pack_queries(queries)

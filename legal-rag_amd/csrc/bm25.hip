@@ -353,6 +353,7 @@ int amdr_bm25_destroy(amdr_bm25_t* h) {
   h->sbuf.release();
   h->ibuf.release();
   h->full.release();
+  h->tscope.release();
   h->ticket.release();
   delete h;
   return AMDR_OK;

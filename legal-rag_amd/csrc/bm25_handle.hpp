@@ -87,5 +87,6 @@ struct amdr_bm25 {
   std::mutex mu;
   // part[0]: "_device" calls, part[1]: host-pointer calls (see dense.hip)
   amdr::DevBuf part[2], qterms, qptr, sbuf, ibuf, full;
+  amdr::DevBuf tscope;  // amdr_term_scope (term_scope.hip): its staged operands, outputs and workspace
   amdr::DevBuf ticket;  // 64 zeroed ints: arrival counters of the one-launch serving step (dense_tail.hip), self-resetting
 };

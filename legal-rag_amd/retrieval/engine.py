@@ -217,6 +217,58 @@ class HybridEngine:
         return (dev[:n1].view(torch.int64), dev[n1:n1 + n2].view(torch.int64), dev[n1 + n2:n1 + n2 + n3].view(torch.int32),
                 int(scope_ptr.size) - 1, rows_max)
 
+    def _grown(self, name: str, nbytes: int) -> torch.Tensor:
+        """A device byte buffer of at least nbytes under `name` (grown geometrically, reused)."""
+        t = self._bufs.get(("grow", name))
+        if t is None or t.numel() < nbytes:
+            t = torch.empty((max(int(nbytes), 2 * (t.numel() if t is not None else 0), 4096),), dtype=torch.uint8,
+                            device=self.tdev)
+            self._bufs[("grow", name)] = t
+        return t
+
+    def check_term_scopes(self) -> None:
+        """ValueError unless term_scopes() can run on this engine; launches nothing."""
+        if self.shard_offset is not None:
+            raise ValueError("term constraints do not run on a row-sharded engine (base rows and the table are global)")
+        if self.bm25 is None:
+            raise ValueError("term constraints need the BM25 index (they are resolved on its resident postings)")
+
+    def term_scopes(self, table):
+        """Term constraints -> the scope table of the scoped channels, on the device (amdr_term_scope_device, three
+        launches on the current stream, no host synchronise).  table: retrieval/terms.py pack() — the operand arrays,
+        each question's constraint and the host bounds.  The operands go up through ONE pinned staging copy (the ring of
+        upload_scopes: they hold until two more term_scopes calls).  Returns ((scope_ptr, rows, qscope, n_scopes,
+        rows_max), status): the 5-tuple upload_scopes returns — n_scopes = the constraint count, rows_max = cand_max —
+        which search_batch(scopes=) and capture take as they take an uploaded table (the channels must share the BM25
+        index's chunk list), and the status tensor i32 [n_cons] (0; 1 / 2: cand_max / rows_cap exceeded — never with
+        pack()'s bounds on the index they were computed from).  The outputs are this engine's buffers: they hold until the
+        next term_scopes call."""
+        self.check_term_scopes()
+        n_cons, cand_max, rows_cap = int(table.n_cons), int(table.cand_max), int(table.rows_cap)
+        order = (0, 2, 4, 5, 1, 3, 6)  # the i64 arrays first: every one starts on a multiple of its item size
+        parts = [(i, np.ascontiguousarray(table.ops[i], dtype=t).view(np.uint8))
+                 for i, t in ((i, _native.BM25Index.TERM_OPS[i]) for i in order)]
+        parts.append((7, np.ascontiguousarray(table.qscope, dtype=np.int32).view(np.uint8)))
+        total = sum(p.size for _, p in parts)
+        host, dev, ev = self._staging("tsc", max(total, 8))
+        hv, at, where = host.numpy(), 0, {}
+        for i, p in parts:
+            hv[at:at + p.size] = p
+            where[i] = (at, p.size)
+            at += p.size
+        self._send(host, dev, ev, max(total, 8))
+        base = dev.data_ptr()
+        o_rows, o_status = 8 * (n_cons + 1), 8 * (n_cons + 1) + 8 * rows_cap
+        out = self._grown("tso", o_status + 4 * n_cons + 8)
+        work_bytes = _native.term_scope_plan(n_cons, cand_max)
+        work = self._grown("tsw", work_bytes)
+        self.bm25.term_scope_device([base + where[i][0] for i in range(7)], int(table.n_base), n_cons, int(table.n_groups),
+                                    cand_max, rows_cap, out.data_ptr(), out.data_ptr() + o_rows, out.data_ptr() + o_status,
+                                    work.data_ptr(), work_bytes, _stream())
+        q0, qn = where[7]
+        return ((out[:o_rows].view(torch.int64), out[o_rows:o_status].view(torch.int64), dev[q0:q0 + qn].view(torch.int32),
+                 n_cons, cand_max), out[o_status:o_status + 4 * n_cons].view(torch.int32))
+
     def upload_text(self, ptrs, lens, total: int):
         """Query texts (UTF-8 pointer / length arrays, _native.utf8_views) -> (blob u8 [total], offs i64 [n + 1]) on the
         device: packed straight into pinned staging (amdr_tokenizer_pack: offsets first, then the bytes) and sent up

@@ -41,6 +41,7 @@ from .diversity import Diversity, resolve as _resolve_diversity
 from .graph_retriever import GraphRetriever
 from .rerankers import RerankerFactory, _to_doc_text
 from .scope import Scope, resolver_for
+from .terms import Terms, pack as _pack_terms
 
 logger = logging.getLogger("legalrag.retrieval.hybrid_retriever")
 
@@ -216,12 +217,40 @@ class HybridRetriever:
             ws = held[int(device)] = _native.ScopeWorkspace(device=int(device))
         return ws
 
-    def _search_scoped(self, who: str, chunks, scope: Scope, top_k: int, refusal: Optional[str], device, twin: str, operands):
+    def _term_rows(self, who: str, chunks, scope: Optional[Scope], terms: Terms) -> np.ndarray:
+        """The ascending rows of `chunks` that satisfy `terms` inside `scope` (None: the whole list), resolved on the GPU from
+        the BM25 index's resident postings (amdr_term_scope, the host twin).  `chunks` must be the BM25 index's own chunk
+        list or one with the same ids in the same order — a BM25 document id is then a row of it — and the index unsharded:
+        ValueError otherwise, before any launch."""
+        bm = self.bm25
+        if not isinstance(bm, BM25Retriever):
+            raise ValueError(f"{who}(terms=): term constraints need this package's own BM25 retriever")
+        bm.load()
+        if getattr(bm, "shard", None) is not None:
+            raise ValueError(f"{who}(terms=): term constraints do not run on a row-sharded index")
+        if chunks is not bm.chunks and not (len(chunks) == len(bm.chunks) and all(
+                a is not None and a.id == b.id for a, b in zip(chunks, bm.chunks))):
+            raise ValueError(f"{who}(terms=): this channel's chunk list is not the BM25 index's (a BM25 document id must "
+                             f"be a row of the channel)")
+        model = bm.bm25
+        tt = _pack_terms([(scope, terms)], model.vocab(), model._doc_frequencies(), int(model.corpus_size),
+                         resolver_for(bm.chunks).rows)
+        if tt.cand_max == 0:
+            return np.zeros(0, dtype=np.int64)
+        _, rows, status = bm.gpu_index().term_scope(tt.ops, tt.cand_max, tt.rows_cap)
+        if int(status[0]) != 0:
+            raise RuntimeError(f"{who}(terms=): the term constraint overflowed its bound (status {int(status[0])}); the "
+                               f"host model and the resident BM25 index disagree")
+        return rows
+
+    def _search_scoped(self, who: str, chunks, scope: Optional[Scope], top_k: int, refusal: Optional[str], device, twin: str,
+                       operands, terms: Optional[Terms] = None):
         """The common sequence of the per-channel scoped searches: [(chunk, score)] of the channel's top_k among the rows of
         `chunks` the scope names.  A scope that matches nothing returns [] without a launch, even where the index would be
         refused; `refusal`: the channel's error text when its index cannot take a scope, else None; `twin`: the channel's
-        host twin (a ScopeWorkspace method), called on a one-scope table with what `operands()` returns: (index, queries)."""
-        rows = resolver_for(chunks).rows(scope)
+        host twin (a ScopeWorkspace method), called on a one-scope table with what `operands()` returns: (index, queries).
+        `terms`: the rows are those of `scope` (None: all) that satisfy the term constraint (_term_rows)."""
+        rows = resolver_for(chunks).rows(scope) if terms is None else self._term_rows(who, chunks, scope, terms)
         if rows.size == 0:
             return []
         if refusal is not None:
@@ -231,7 +260,8 @@ class HybridRetriever:
         scores, ids = getattr(self._scope_workspace(device), twin)(*operands(), [0, rows.size], rows, [0], top_k)
         return [(chunks[r], float(s)) for r, s in zip(ids[0].tolist(), scores[0].tolist()) if r >= 0 and chunks[r] is not None]
 
-    def _search_dense_scoped(self, question: str, top_k: int, scope: Scope) -> List[RetrievalHit]:
+    def _search_dense_scoped(self, question: str, top_k: int, scope: Optional[Scope],
+                             terms: Optional[Terms] = None) -> List[RetrievalHit]:
         store = self.dense.store
         store.load()
         index = getattr(store.index, "native", None)
@@ -239,14 +269,18 @@ class HybridRetriever:
             "search_dense", store.chunks, scope, top_k,
             "search_dense(scope=): needs this package's own, unsharded dense index"
             if index is None or getattr(store.index, "spec", None) is not None else None,
-            getattr(index, "device", 0), "dense_search", lambda: (index, store._embed([question], is_query=True)))
+            getattr(index, "device", 0), "dense_search", lambda: (index, store._embed([question], is_query=True)), terms)
         return [RetrievalHit(chunk=c, score=s, rank=j, source="retriever", semantic_score=s)
                 for j, (c, s) in enumerate(pairs, start=1)]
 
-    def search_dense(self, question: str, top_k: int = 10, *, scope: Optional[Scope] = None) -> List[RetrievalHit]:
-        """`scope`: rank only that part of the corpus (retrieval/scope.py); None: the whole corpus."""
+    def search_dense(self, question: str, top_k: int = 10, *, scope: Optional[Scope] = None,
+                     terms: Optional[Terms] = None) -> List[RetrievalHit]:
+        """`scope`: rank only that part of the corpus (retrieval/scope.py); None: the whole corpus.  `terms`: rank only the
+        chunks that satisfy the term constraint (retrieval/terms.py), inside `scope` if both are given."""
         top_k = max(1, int(top_k))
-        hits = self.dense.search(question, top_k) if scope is None else self._search_dense_scoped(question, top_k, scope)
+        terms = None if self._no_terms(None if terms is None else [terms], "search_dense") else terms
+        hits = (self.dense.search(question, top_k) if scope is None and terms is None
+                else self._search_dense_scoped(question, top_k, scope, terms))
         hits.sort(key=lambda h: float(h.score), reverse=True)
         for i, h in enumerate(hits, start=1):
             h.rank = i
@@ -254,7 +288,8 @@ class HybridRetriever:
             h.score_breakdown = {"channel": ["dense"], "dense_raw": float(h.score)}
         return hits
 
-    def _search_bm25_scoped(self, question: str, top_k: int, tokens: Optional[Sequence[str]], scope: Scope):
+    def _search_bm25_scoped(self, question: str, top_k: int, tokens: Optional[Sequence[str]], scope: Optional[Scope],
+                            terms: Optional[Terms] = None):
         bm = self.bm25
         bm.load()
 
@@ -268,16 +303,18 @@ class HybridRetriever:
         return self._search_scoped(
             "search_bm25", bm.chunks, scope, top_k,
             "search_bm25(scope=): scoped search does not run on a row-sharded index" if getattr(bm, "shard", None) is not None
-            else None, bm.device_index, "bm25_search", operands)
+            else None, bm.device_index, "bm25_search", operands, terms)
 
     def search_bm25(self, question: str, top_k: int = 10, tokens: Optional[Sequence[str]] = None, *,
-                    scope: Optional[Scope] = None) -> List[RetrievalHit]:
+                    scope: Optional[Scope] = None, terms: Optional[Terms] = None) -> List[RetrievalHit]:
         """`tokens`: the caller's own segmentation of `question` (exact path without jieba).  `scope`: rank only that
-        part of the corpus (idf and avgdl stay those of the whole index)."""
+        part of the corpus (idf and avgdl stay those of the whole index).  `terms`: rank only the chunks that satisfy the
+        term constraint (retrieval/terms.py), inside `scope` if both are given; the scores do not change."""
         top_k = max(1, int(top_k))
+        terms = None if self._no_terms(None if terms is None else [terms], "search_bm25") else terms
         # (a duck-typed retriever with the reference's two-argument search() is still accepted)
-        if scope is not None:
-            pairs = self._search_bm25_scoped(question, top_k, tokens, scope)
+        if scope is not None or terms is not None:
+            pairs = self._search_bm25_scoped(question, top_k, tokens, scope, terms)
         else:
             pairs = self.bm25.search(question, top_k, tokens=tokens) if tokens is not None else self.bm25.search(question, top_k)
         hits = [RetrievalHit(chunk=c, score=float(s), rank=i, source="retriever",
@@ -291,7 +328,7 @@ class HybridRetriever:
                 h.score_breakdown["zh_exact"] = False
         return hits
 
-    def _search_colbert_scoped(self, question: str, top_k: int, scope: Scope):
+    def _search_colbert_scoped(self, question: str, top_k: int, scope: Optional[Scope], terms: Optional[Terms] = None):
         col = self.colbert
         if not col.enabled:
             return []
@@ -307,16 +344,18 @@ class HybridRetriever:
             "search_colbert", held[1], scope, top_k,
             "search_colbert(scope=): scoped search does not run on a row-sharded index" if getattr(col, "shard", None) is not None
             else None, col.device_index, "maxsim_search",
-            lambda: (col._searcher, np.asarray(col._encoder.encode_query(question), dtype=np.float32)[None]))
+            lambda: (col._searcher, np.asarray(col._encoder.encode_query(question), dtype=np.float32)[None]), terms)
 
-    def search_colbert(self, question: str, top_k: int = 10, *, scope: Optional[Scope] = None) -> List[RetrievalHit]:
+    def search_colbert(self, question: str, top_k: int = 10, *, scope: Optional[Scope] = None,
+                       terms: Optional[Terms] = None) -> List[RetrievalHit]:
         top_k = max(1, int(top_k))
+        terms = None if self._no_terms(None if terms is None else [terms], "search_colbert") else terms
         if self.colbert is None:
             return []
         try:
             hits: List[RetrievalHit] = []
-            for item in (self.colbert.search(question, top_k) if scope is None
-                         else self._search_colbert_scoped(question, top_k, scope)):
+            for item in (self.colbert.search(question, top_k) if scope is None and terms is None
+                         else self._search_colbert_scoped(question, top_k, scope, terms)):
                 if isinstance(item, RetrievalHit):
                     hits.append(item)
                 else:
@@ -458,14 +497,17 @@ class HybridRetriever:
 
     # ---------------------------------------------------------- main search
     def search(self, question: str, llm: Any = None, top_k: int = 10, decision: Any = None, *,
-               scope: Optional[Scope] = None, diversity: Any = None) -> List[RetrievalHit]:
+               scope: Optional[Scope] = None, diversity: Any = None, terms: Optional[Terms] = None) -> List[RetrievalHit]:
         """`scope` (retrieval/scope.py): every channel ranks only that part of the corpus and the fusion normalises over
         those lists — the one-question form of search_batch(scopes=).  None: the whole corpus.
+        `terms` (retrieval/terms.py): every channel ranks only the chunks whose text holds the required and none of the
+        excluded tokens, inside `scope` if both are given — the one-question form of search_batch(terms=).
         `diversity` (retrieval/diversity.py): a Diversity makes MMR selection the last stage, None takes the configured
         default (cfg.retrieval.diversity_lambda), False switches it off."""
-        if scope is not None:
+        if scope is not None or (terms is not None and not self._no_terms([terms], "search")):
             return self.search_batch([question], top_k=top_k, llm=llm, decisions=None if decision is None else [decision],
-                                     scopes=[scope], diversity=diversity)[0]
+                                     scopes=None if scope is None else [scope], diversity=diversity,
+                                     terms=None if terms is None else [terms])[0]
         rcfg = self.cfg.retrieval
         top_k = max(1, int(top_k))
         mmr = self._diversity(diversity, top_k, "search")
@@ -813,14 +855,18 @@ class HybridRetriever:
                 col, q_tok = None, None
         return _Prepared((store, bm, col), q_emb, csr, txt, np.asarray(exact, dtype=bool), q_tok, (t1, t2, time.time()))
 
-    def _run(self, prep: "_Prepared", params: "_native.FuseParams", eff: int, fetch, after=None, scope_table=None, mmr=None):
+    def _run(self, prep: "_Prepared", params: "_native.FuseParams", eff: int, fetch, after=None, scope_table=None, mmr=None,
+             term_table=None):
         """Step 2, under the stage lock (one batch at a time through the handles' "_device" workspace,
         include/amdretrieval.h): engine, upload, eng.search_batch on torch's current stream, the ColBERT fallback,
         `after(engine, result)` (the device graph stage), then `fetch(engine, result)` — the ONE synchronise and
         device-to-host copy of the form the caller decodes.  Returns (what fetch returned, what after returned).
         scope_table (ScopeResolver.table of the batch): the scoped step — the three channels share one chunk list here
         (_native_channels), so one table serves them all.  mmr = (k_sel, lam, pool): the result is diversified on the device
-        (HybridEngine.diversify) behind `after`, whose seeds are the fused list as ranked, and in front of `fetch`."""
+        (HybridEngine.diversify) behind `after`, whose seeds are the fused list as ranked, and in front of `fetch`.
+        term_table (retrieval/terms.py pack of the batch) instead of scope_table: the table is resolved on the device from
+        the term constraints (HybridEngine.term_scopes) in the same stream; its status words ride a pinned copy enqueued
+        behind it and are read after fetch's synchronise — a non-zero one raises RuntimeError naming the constraint."""
         import torch
         (store, bm, col), tdev = prep.native, prep.q_emb.device
         with self._stage().lock:
@@ -840,10 +886,18 @@ class HybridRetriever:
                 q_tok = (q_tok.to(tdev, dtype=torch.float32).contiguous() if torch.is_tensor(q_tok)
                          else torch.from_numpy(q_tok).to(tdev, non_blocking=True))
 
+            status = []
+
             def scoped(e, with_col):
-                if scope_table is None:
+                if term_table is not None:
+                    tb, st = e.term_scopes(term_table)
+                    pin = e._pinned("tsst", 4 * max(int(st.numel()), 1))[:4 * int(st.numel())]
+                    pin.copy_(st.view(torch.uint8), non_blocking=True)
+                    status[:] = [pin]
+                elif scope_table is None:
                     return {}
-                tb = e.upload_scopes(*scope_table[:3])
+                else:
+                    tb = e.upload_scopes(*scope_table[:3])
                 return {"scopes": (tb, tb, tb if with_col else None)}
             try:
                 res = eng.search_batch(params, eff, q_emb=prep.q_emb, q_terms=q_terms_d, q_ptr=q_ptr_d, q_tok=q_tok,
@@ -858,7 +912,15 @@ class HybridRetriever:
             extra = after(eng, res) if after is not None else None
             if mmr is not None:
                 res = eng.diversify(res, *mmr)
-            return fetch(eng, res), extra
+            host = fetch(eng, res)
+            if status:  # (fetch has synchronised the stream the copy was enqueued on)
+                bad = np.flatnonzero(status[0].numpy().view(np.int32))
+                if bad.size:
+                    c = int(bad[0])
+                    raise RuntimeError(f"term constraint {c} of the batch overflowed its bound (status "
+                                       f"{int(status[0].numpy().view(np.int32)[c])}: 1 = candidates beyond cand_max, 2 = rows "
+                                       f"beyond rows_cap); the host model and the resident BM25 index disagree")
+            return host, extra
 
     # Step 3, the decoders: host arrays of ONE fetch -> the caller's form.
     def _decode_hits(self, host, exact, kn, chunks) -> List[List[RetrievalHit]]:
@@ -893,14 +955,39 @@ class HybridRetriever:
 
     # ----------------------------------------------------------- batch form
     @staticmethod
-    def _partition(questions: Sequence[str], scopes, decisions, chunks, colbert: bool, who: str):
+    def _no_terms(terms, who: str) -> bool:
+        """Whether `terms` (None, or one Terms | None per question) restricts no question; TypeError for anything else."""
+        if terms is None:
+            return True
+        for i, t in enumerate(terms):
+            if t is not None and not isinstance(t, Terms):
+                raise TypeError(f"{who}: terms[{i}] is not a Terms")
+        return all(t is None or t.unrestricted for t in terms)
+
+    @staticmethod
+    def _check_terms(terms, native, who: str) -> None:
+        """The refusal of term constraints on a row-sharded index, before anything is launched (the engine refuses too)."""
+        if terms is None:
+            return
+        store, bm, col = native
+        if (getattr(store.index, "spec", None) is not None or getattr(bm, "shard", None) is not None
+                or (col is not None and getattr(col, "shard", None) is not None)):
+            raise ValueError(f"{who}(terms=): term constraints do not run on a row-sharded index (base rows and the "
+                             f"table are global)")
+
+    @staticmethod
+    def _partition(questions: Sequence[str], scopes, decisions, chunks, colbert: bool, who: str, terms=None):
         """(parts, empty) of a batch; needs neither device nor torch.  A part is (indices, scoped, ColBERT on): questions
         that share one engine run.  The order is fixed — plain-blank, plain, scoped-blank, scoped — and a part without an
         index is left out.  A blank question switches the ColBERT channel off for itself (colbert_retriever.py:147-149), so
         with the channel on (`colbert`) the blank ones run apart, without it; with the channel off nothing is split.
         `empty`: the questions whose scope names no row of `chunks` (no launch is made for them).  A graph-mode decision
-        together with a scope raises: the graph channel follows cross-references out of any scope by design."""
+        together with a scope raises: the graph channel follows cross-references out of any scope by design.
+        `terms` (one Terms or None per question): a question with a Terms joins the scoped part — whether it matches
+        anything is known only on the device — and refuses a graph-mode decision as a scope does."""
         n = len(questions)
+        if terms is not None and len(terms) != n:
+            raise ValueError(f"{who}: terms must have one entry per question")
         if scopes is not None and len(scopes) != n:
             raise ValueError(f"{who}: scopes must have one entry per question")
         if decisions is not None and len(decisions) != n:
@@ -915,6 +1002,19 @@ class HybridRetriever:
                 raise ValueError(f"{who}: question {i} has a graph-mode decision and a scope; the graph channel follows "
                                  f"cross-references out of any scope")
             (scoped if resolver_for(chunks).rows(s).size else empty).append(i)
+        for i, t in enumerate(terms if terms is not None else ()):
+            if t is None:
+                continue
+            if not isinstance(t, Terms):
+                raise TypeError(f"{who}: terms[{i}] is not a Terms")
+            if t.unrestricted:
+                continue
+            if decisions is not None and _is_graph_mode(getattr(decisions[i], "mode", None)):
+                raise ValueError(f"{who}: question {i} has a graph-mode decision and term constraints; the graph channel "
+                                 f"follows cross-references to articles that do not hold the terms")
+            if i not in scoped and i not in empty:
+                scoped.append(i)
+        scoped.sort()
         if scoped or empty:
             out = set(scoped).union(empty)
             plain = [i for i in plain if i not in out]
@@ -935,7 +1035,7 @@ class HybridRetriever:
         return by.get(False, []), by.get(True, []), empty
 
     def _run_part(self, part, questions, scopes, q_emb, native, device_tok: bool, params, eff: int, fetch, decode, graph=None,
-                  mmr=None):
+                  mmr=None, terms=None):
         """One part of a batch in one engine run: _prepare -> the scope table of a scoped part -> _run -> `decode(host
         arrays, exact)`; `graph` (what _graph_device_stage returned) rides the part it names.  Returns (what decode
         returned, the _Prepared's time stamps, what the graph stage returned).  A part that is the whole batch takes the
@@ -947,12 +1047,20 @@ class HybridRetriever:
             questions = [questions[i] for i in idxs]
             q_emb = None if q_emb is None else q_emb[idxs]
         prep = self._prepare(questions, (store, bm, col if with_col else None), q_emb, device_tok)
-        table = resolver_for(store.chunks).table([scopes[i] for i in idxs]) if scoped else None
-        host, extra = self._run(prep, params, eff, fetch, after, table, mmr)
+        table = term_table = None
+        if scoped and terms is not None and any(terms[i] is not None and not terms[i].unrestricted for i in idxs):
+            # one table for the part: a question with a Scope alone is the constraint without a group over that base
+            model = bm.bm25  # (looked up per call: an in-place update renumbers the vocabulary)
+            term_table = _pack_terms([(scopes[i] if scopes is not None else None, terms[i] or Terms()) for i in idxs],
+                                     model.vocab(), model._doc_frequencies(), int(model.corpus_size),
+                                     resolver_for(store.chunks).rows)
+        elif scoped:
+            table = resolver_for(store.chunks).table([scopes[i] for i in idxs])
+        host, extra = self._run(prep, params, eff, fetch, after, table, mmr, term_table)
         return decode(host, prep.exact), prep.stamps, extra
 
     def _hit_lists(self, questions: Sequence[str], parts, eff: int, native, min_final: float, q_emb=None,
-                   device_tok: bool = False, scopes=None, graph=None):
+                   device_tok: bool = False, scopes=None, graph=None, terms=None):
         """The parts of a batch as hit lists: ([fused hits with score >= min_final per question; [] for a question no part
         holds: its scope matches nothing], (t_after_dense_prep, t_after_bm25_prep, t_after_colbert_prep) of the last part,
         what the graph stage `graph` (_graph_device_stage) returned)."""
@@ -962,7 +1070,8 @@ class HybridRetriever:
         outs, stamps, gout = [[] for _ in questions], (time.time(),) * 3, None
         for part in parts:
             lists, stamps, g = self._run_part(part, questions, scopes, q_emb, native, device_tok, params, eff, _fetch_full,
-                                              lambda host, exact: self._decode_hits(host, exact, kn, chunks), graph)
+                                              lambda host, exact: self._decode_hits(host, exact, kn, chunks), graph,
+                                              terms=terms)
             gout = gout if g is None else g
             for i, hits in zip(part[0], lists):
                 outs[i] = hits
@@ -978,7 +1087,8 @@ class HybridRetriever:
 
     def search_batch(self, questions: Sequence[str], top_k: int = 10, llm: Any = None,
                      decisions: Optional[Sequence[Any]] = None, q_emb=None, *,
-                     scopes: Optional[Sequence[Optional[Scope]]] = None, diversity: Any = None) -> List[List[RetrievalHit]]:
+                     scopes: Optional[Sequence[Optional[Scope]]] = None, diversity: Any = None,
+                     terms: Optional[Sequence[Optional[Terms]]] = None) -> List[List[RetrievalHit]]:
         """Throughput form: `search_batch(qs)[i]` == `search(qs[i])` for every stage the configuration enables
         (hybrid_retriever.py:282-384) — one kernel pipeline for the whole batch (dense + BM25 (+ ColBERT) -> fuse
         -> filter), the graph stage per query whose `decisions[i]` asks for it, the rerank stage with the
@@ -987,17 +1097,29 @@ class HybridRetriever:
         the corpus and its fusion normalises over those lists; the questions with None run as one part through the
         unscoped step, the scoped ones as another; a scope that matches nothing yields [].  A graph-mode decision with a
         scope raises ValueError.
+        `terms` (one Terms or None per question, retrieval/terms.py): a question with a Terms joins the scoped part; its
+        constraint — inside its Scope, if it has one — is resolved on the GPU from the resident BM25 postings into the
+        part's scope table (HybridEngine.term_scopes), so every channel ranks only the qualifying chunks; a constraint that
+        matches nothing yields [].  ValueError, before any launch, with a graph-mode decision, on a row-sharded index, or
+        when the channels do not share one chunk list.
         `diversity`: as search — MMR selection as the last stage, ONE batched call for all questions."""
         rcfg = self.cfg.retrieval
         top_k = max(1, int(top_k))
         questions = list(questions)
+        if self._no_terms(terms, "search_batch"):
+            terms = None
         mmr = self._diversity(diversity, top_k, "search_batch")
         eff = self._eff_depth(top_k, "search_batch")
         native = self._native_channels(eff)
         if native is None:
+            if terms is not None:
+                raise ValueError("search_batch(terms=): term constraints need this package's own dense / BM25 (/ ColBERT) "
+                                 "retrievers built over one chunk list (a BM25 document id must be a dense row)")
             raise RuntimeError("search_batch requires this package's own dense / BM25 (/ ColBERT) retrievers built "
                                "over the same chunk list")
-        parts, _ = self._partition(questions, scopes, decisions, native[0].chunks, native[2] is not None, "search_batch")
+        self._check_terms(terms, native, "search_batch")
+        parts, _ = self._partition(questions, scopes, decisions, native[0].chunks, native[2] is not None, "search_batch",
+                                   terms)
         sel, seed_n = self._graph_selection(decisions, top_k)
         # The graph walks at the per-channel depth `eff`.  With the device channel off or no graph loaded the stage
         # falls back to the host search_graph per query (which, without a graph, still cuts the list to the seeds).
@@ -1005,7 +1127,7 @@ class HybridRetriever:
         if sel and self.graph is not None and graph_channel_mode(self.cfg) == "device":
             graph = self._graph_device_stage(parts, questions, sel, eff, seed_n, native)
         outs, _, gout = self._hit_lists(questions, parts, eff, native, float(getattr(rcfg, "min_final_score", 0.0)), q_emb,
-                                        query_tokenizer_mode(self.cfg) == "device", scopes, graph)
+                                        query_tokenizer_mode(self.cfg) == "device", scopes, graph, terms)
         for j, i in enumerate(sel):
             seeds = outs[i][:seed_n]
             if graph is not None:
@@ -1097,7 +1219,8 @@ class HybridRetriever:
 
     def search_batch_arrays(self, questions: Sequence[str], top_k: int = 10, q_emb=None, values: bool = True,
                             decisions: Optional[Sequence[Any]] = None, *,
-                            scopes: Optional[Sequence[Optional[Scope]]] = None, diversity: Any = None) -> Dict[str, Any]:
+                            scopes: Optional[Sequence[Optional[Scope]]] = None, diversity: Any = None,
+                            terms: Optional[Sequence[Optional[Terms]]] = None) -> Dict[str, Any]:
         """`search_batch` without building RetrievalHit objects (pydantic construction, not the GPU, bounds
         `search_batch` at a few thousand queries/s): columnar results for bulk callers (evaluation sweeps,
         offline scoring).  rows[q, j] indexes `self.dense.store.chunks`; entries j >= count[q] are -1 / 0.
@@ -1110,6 +1233,7 @@ class HybridRetriever:
         graph_semantic / graph_depth / graph_relation (index into graph_relation_names) / graph_edge_conf [n, top_k] and
         graph_count [n] (0 for the other queries).
         `scopes`: as search_batch — one Scope or None per question; a scope that matches nothing gives count 0.
+        `terms`: as search_batch — one Terms or None per question; a constraint that matches nothing gives count 0.
         `diversity`: as search — the selection runs on the device inside the stage (HybridEngine.diversify) over the
         fused list of every part, scoped ones included; the columns hold the selected hits in selection order and, with
         values=True, `mmr` and `mmr_max_sim` [n, top_k] beside them (MMR_COLUMNS).
@@ -1120,10 +1244,17 @@ class HybridRetriever:
         mmr = None if mmr is None else (top_k, mmr[0].lam, mmr[1])
         eff = self._eff_depth(top_k, "search_batch_arrays")
         native = self._native_channels(eff)
+        if self._no_terms(terms, "search_batch_arrays"):
+            terms = None
         if native is None:
+            if terms is not None:
+                raise ValueError("search_batch_arrays(terms=): term constraints need this package's own retrievers built "
+                                 "over one chunk list (a BM25 document id must be a dense row)")
             raise RuntimeError("search_batch_arrays requires this package's own retrievers built over the same chunk list")
+        self._check_terms(terms, native, "search_batch_arrays")
         questions, chunks = list(questions), native[0].chunks
-        parts, _ = self._partition(questions, scopes, decisions, chunks, native[2] is not None, "search_batch_arrays")
+        parts, _ = self._partition(questions, scopes, decisions, chunks, native[2] is not None, "search_batch_arrays",
+                                   terms)
         if native[2] is not None and not all(with_col for _, _, with_col in parts):
             raise ValueError("search_batch_arrays: empty questions are not supported in the columnar form")
         sel, seed_n = self._graph_selection(decisions, top_k)
@@ -1147,7 +1278,7 @@ class HybridRetriever:
         done = []
         for part in parts:
             cols, _, g = self._run_part(part, questions, scopes, q_emb, native, query_tokenizer_mode(self.cfg) == "device",
-                                        params, eff, fetch, decode, graph, mmr)
+                                        params, eff, fetch, decode, graph, mmr, terms)
             if graph_on and not part[1]:
                 self._graph_columns(cols, g, graph[1] if graph is not None else [], top_k)
             done.append((part[0], cols))
