@@ -8,7 +8,7 @@
  * 0 on success or a negative AMDR_E* code, with a thread-local message available
  * from amdr_last_error(); the caller allocates all outputs; opaque handles are
  * safe for concurrent read-only searches (internally serialised per handle),
- * mutation (add/remove/replace/destroy) must not race with searches on the same handle.
+ * mutation (add/remove/replace/set_tokens/destroy) must not race with searches on the same handle.
  *
  * "_device" variants take DEVICE pointers and a hipStream_t passed as void*
  * (0 = the null stream); they enqueue work and return without synchronising,
@@ -320,6 +320,21 @@ int amdr_bm25_add_kernel_ms(amdr_bm25_t* h, double* ms);
  * doc_len[n_docs] (sizes from amdr_bm25_info); any pointer may be null.  The only way to see what a handle holds. */
 int amdr_bm25_read(amdr_bm25_t* h, int64_t* term_ptr, int32_t* post_doc, int32_t* post_tf, double* post_w, double* idf,
                    int32_t* doc_len);
+/* The token stream (forward index) of the corpus, for phrase constraints (amdr_phrase_lists below; the reference keeps no
+ * token order anywhere).  doc_ptr[n_docs + 1], tokens[doc_ptr[n_docs]]: document d's text, as the index tokeniser cut it,
+ * is the term ids tokens[doc_ptr[d] .. doc_ptr[d + 1]).  4 B per token and 8 B per document on the device.  Validated on
+ * the host, AMDR_EINVAL, handle unchanged: a null handle or array, doc_ptr[0] != 0 or doc_ptr not monotone, a token outside
+ * [0, n_terms), doc_ptr[d + 1] - doc_ptr[d] != doc_len[d] for any d (the handle's doc_len is read once for this: the check
+ * that catches a stream made for another state of the index).  A second call replaces the stream.  amdr_bm25_add /
+ * _remove / _replace renumber documents and terms: a SUCCESSFUL call of any of them DROPS the stream (a failed one leaves
+ * it) and the caller sets a new one.  Setting a stream is a mutation in the sense of the rule at the top of this file.
+ * Searches and amdr_term_scope* calls without virtual lists behave exactly as without a stream. */
+int amdr_bm25_set_tokens(amdr_bm25_t* h, const int64_t* doc_ptr, const int32_t* tokens);
+/* out2: [0] 1 if a token stream is resident else 0, [1] its token count (0 without one) */
+int amdr_bm25_tokens_info(amdr_bm25_t* h, int64_t* out2);
+/* Copies the resident stream to the host: doc_ptr[n_docs + 1], tokens[out2[1]]; either pointer may be null.
+ * AMDR_EINVAL when no stream is resident. */
+int amdr_bm25_read_tokens(amdr_bm25_t* h, int64_t* doc_ptr, int32_t* tokens);
 int amdr_bm25_reserve(amdr_bm25_t* h, int32_t nq_max, int32_t k_max, int64_t total_terms_max);
 /* Host-only (no device is touched): on a corpus of n_docs documents, out2[0] = the slab-list bytes amdr_bm25_reserve
  * (nq_max, k_max) sizes for the "_device" calls, out2[1] = the bytes amdr_bm25_search_device(nq, k) uses.  A test holds
@@ -846,8 +861,9 @@ int amdr_scope_destroy(amdr_scope_t* h);
  * seller and goods but not buyer" over-fetches and filters on the host.  csrc/term_scope.hip, csrc/term_scope_rule.hpp.
  * A constraint is a list of groups; a group is a non-empty list of term ids with a kind: 0 MUST, 1 ANY, 2 NOT.  The id -1
  * (any id outside [0, n_terms)) is a token the vocabulary does not hold: present in no document.  A document satisfies a
- * group when it has a posting for EVERY term of the group — a conjunction, NOT a phrase match: the postings hold no
- * positions.  It qualifies when it satisfies every MUST group, at least one ANY group (or there is none), no NOT group,
+ * group when it has a posting for EVERY term of the group — a conjunction: the words anywhere, in any order.  The words
+ * in sequence are a phrase: amdr_phrase_lists below resolves it into a virtual posting list, which
+ * amdr_term_scope_lists takes as one more term.  It qualifies when it satisfies every MUST group, at least one ANY group (or there is none), no NOT group,
  * and lies in the constraint's base scope, if it has one.
  * Operands: grp_ptr i64 [n_cons + 1] indexes the groups of each constraint, grp_kind i32 [n_groups], grp_term_ptr i64
  * [n_groups + 1] indexes grp_terms i32; base_ptr i64 [n_base + 1] indexes base_rows i64 (each base scope strictly
@@ -887,6 +903,59 @@ int amdr_term_scope(amdr_bm25_t* bm25, const int64_t* grp_ptr, const int32_t* gr
                     const int32_t* grp_terms, const int64_t* base_ptr, const int64_t* base_rows, const int32_t* cons_base,
                     int64_t n_base, int64_t n_cons, int64_t n_groups, int64_t cand_max, int64_t rows_cap,
                     int64_t* out_scope_ptr, int64_t* out_rows, int32_t* out_status);
+
+/* ---- phrase constraints: exact token sequences resolved into virtual posting lists on the device -------------------
+ * No reference counterpart (the reference scores bags of words and keeps no token order).  csrc/phrase_scope.hip,
+ * csrc/phrase_rule.hpp.  Needs the token stream of amdr_bm25_set_tokens.
+ * A phrase is a list of L term ids, 2 <= L <= 16.  A document d HOLDS it when tokens[p + j] == phrase[j] for all j, for
+ * some p with doc_ptr[d] <= p <= doc_ptr[d + 1] - L: a match never reaches into the next document; overlapping occurrences
+ * and repeated tokens are plain cases of this.  An id outside [0, n_terms) anywhere in the phrase gives an empty list
+ * without reading anything.
+ * Operands: phr_ptr i64 [n_phr + 1] indexes phr_terms i32.  Output: out_list_ptr i64 [n_phr + 1] indexes out_docs i32
+ * [rows_cap], each phrase's documents strictly ascending — a posting list in the resident format.  out_status i32 [n_phr]
+ * holds the words of amdr_term_scope: 0; 1 = the phrase's driver is longer than cand_max, its list is left empty; 2 =
+ * documents of the phrase lay at positions >= rows_cap and were dropped (list_ptr is clamped to rows_cap).
+ * The driver of a phrase is the shortest posting list among its tokens, ties -> the first in phrase order, so the output
+ * is ascending without a sort; work is |driver| x the sum of log2(df) of the other tokens plus the lengths of the
+ * documents that hold all the tokens — not the corpus.  cand_max >= the smallest document frequency among a phrase's
+ * tokens, maximised over the phrases, and rows_cap >= the sum of these always suffice.
+ * Three launches (count, scan, write; grid = phrases x tiles of 256 candidates), no atomics, deterministic.
+ * amdr_phrase_lists_plan is host-only arithmetic: the workspace bytes of a call (16 B + 1 KiB per phrase and tile).
+ * amdr_phrase_lists_device only enqueues on `stream` and allocates nothing (capturable); AMDR_EINVAL, enqueueing nothing,
+ * for a null handle, no resident stream, a null operand, a negative size, cand_max beyond 65 535 tiles, or work_bytes
+ * below the plan.  It does not validate the operands' contents: a phrase whose length is outside 2 .. 16 gets an empty
+ * list.  amdr_phrase_lists is the host-pointer twin: it validates (AMDR_EINVAL: phr_ptr not starting at 0 or not
+ * monotone, a length outside 2 .. 16), stages, runs on the BM25 handle's own stream under its mutex and returns the
+ * lists (the first out_list_ptr[n_phr] values of out_docs are written) and the status array in the host buffers.
+ *
+ * amdr_term_scope_lists* are amdr_term_scope* with three more operands, the virtual lists of the call: x_ptr i64
+ * [n_x + 1] indexes x_doc i32, and the term id n_terms + p, p < n_x, names the list x_doc[x_ptr[p] .. x_ptr[p + 1]) —
+ * in a MUST, ANY or NOT group, beside plain terms inside a group, and as the driver of a constraint.  Handed the outputs
+ * of amdr_phrase_lists_device on the same stream, a phrase works wherever a token works; the rule of amdr_term_scope is
+ * untouched and n_x = 0 is that call itself.  Status, plan and workspace are unchanged.  The host twin also validates
+ * the lists (AMDR_EINVAL: x_ptr not starting at 0 or not monotone, a document outside [0, n_docs) or a list not strictly
+ * ascending).
+ * The bound.  A host that packs constraints knows only an UPPER bound for a virtual list's length: the smallest
+ * document frequency among the phrase's tokens.  The device's driver is the shortest of the TRUE lengths, each <= its
+ * upper bound; so cand_max = the longest driver and rows_cap = the sum of the drivers, computed by the rule above with the
+ * upper bounds in place of the lengths, always suffice (tests/test_phrase_scope_gpu.py). */
+int amdr_phrase_lists_plan(int64_t n_phr, int64_t cand_max, int64_t* work_bytes);
+int amdr_phrase_lists_device(amdr_bm25_t* bm25, const int64_t* phr_ptr_dev, const int32_t* phr_terms_dev, int64_t n_phr,
+                             int64_t cand_max, int64_t rows_cap, int64_t* out_list_ptr_dev, int32_t* out_docs_dev,
+                             int32_t* out_status_dev, void* work_dev, int64_t work_bytes, void* stream);
+int amdr_phrase_lists(amdr_bm25_t* bm25, const int64_t* phr_ptr, const int32_t* phr_terms, int64_t n_phr, int64_t cand_max,
+                      int64_t rows_cap, int64_t* out_list_ptr, int32_t* out_docs, int32_t* out_status);
+int amdr_term_scope_lists_device(amdr_bm25_t* bm25, const int64_t* grp_ptr_dev, const int32_t* grp_kind_dev,
+                                 const int64_t* grp_term_ptr_dev, const int32_t* grp_terms_dev, const int64_t* base_ptr_dev,
+                                 const int64_t* base_rows_dev, const int32_t* cons_base_dev, const int64_t* x_ptr_dev,
+                                 const int32_t* x_doc_dev, int64_t n_x, int64_t n_base, int64_t n_cons, int64_t n_groups,
+                                 int64_t cand_max, int64_t rows_cap, int64_t* out_scope_ptr_dev, int64_t* out_rows_dev,
+                                 int32_t* out_status_dev, void* work_dev, int64_t work_bytes, void* stream);
+int amdr_term_scope_lists(amdr_bm25_t* bm25, const int64_t* grp_ptr, const int32_t* grp_kind, const int64_t* grp_term_ptr,
+                          const int32_t* grp_terms, const int64_t* base_ptr, const int64_t* base_rows,
+                          const int32_t* cons_base, const int64_t* x_ptr, const int32_t* x_doc, int64_t n_x, int64_t n_base,
+                          int64_t n_cons, int64_t n_groups, int64_t cand_max, int64_t rows_cap, int64_t* out_scope_ptr,
+                          int64_t* out_rows, int32_t* out_status);
 
 /* ---- multi-GPU: merge per-shard top-k after the RCCL all-gather --------
  * No reference counterpart (the reference is single-process).

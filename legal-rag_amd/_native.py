@@ -36,7 +36,7 @@ SIGNATURES = {
     "amdr_dense_ntotal": "PP", "amdr_dense_dim": "PP", "amdr_dense_reserve": "Pii", "amdr_dense_search": "PPiiPP",
     "amdr_dense_search_device": "PPiiPPP", "amdr_dense_search_fuse_device": "PPiiPPPPiPPPPPPPP", "amdr_hybrid_small_device": "PPPPPiiiPPPPPPPPPPPP", "amdr_dense_small_create": "PP", "amdr_dense_small_approx_device": "PPiPlPP", "amdr_dense_small_destroy": "P", "amdr_dense_two_pass_fallbacks": "PP", "amdr_dense_read_rows": "PllP", "amdr_dense_score_rows": "PPiPiP",
     "amdr_dense_plan_info": "PiiPi", "amdr_dense_workspace_plan": "liiiiiP", "amdr_dense_hi_counters": "PP", "amdr_dense_image_build": "P", "amdr_dense_image_drop": "P", "amdr_dense_image_info": "PP", "amdr_dense_profile_begin": "Pi", "amdr_dense_profile_end": "PPP", "amdr_dense_destroy": "P",
-    "amdr_bm25_create": "PPPPPlldddiP", "amdr_bm25_ndocs": "PP", "amdr_bm25_add": "PPPPPPlld", "amdr_bm25_info": "PP", "amdr_bm25_add_kernel_ms": "PP", "amdr_bm25_remove": "PPlPlPd", "amdr_bm25_remove_kernel_ms": "PP", "amdr_bm25_replace": "PPlPPPPPlPd", "amdr_bm25_replace_kernel_ms": "PP", "amdr_bm25_replaces": "PP", "amdr_bm25_read": "PPPPPPP", "amdr_bm25_reserve": "Piil", "amdr_bm25_workspace_plan": "liiiiP", "amdr_bm25_plan_info": "PiiPi",
+    "amdr_bm25_create": "PPPPPlldddiP", "amdr_bm25_ndocs": "PP", "amdr_bm25_add": "PPPPPPlld", "amdr_bm25_info": "PP", "amdr_bm25_add_kernel_ms": "PP", "amdr_bm25_remove": "PPlPlPd", "amdr_bm25_remove_kernel_ms": "PP", "amdr_bm25_replace": "PPlPPPPPlPd", "amdr_bm25_replace_kernel_ms": "PP", "amdr_bm25_replaces": "PP", "amdr_bm25_read": "PPPPPPP", "amdr_bm25_set_tokens": "PPP", "amdr_bm25_tokens_info": "PP", "amdr_bm25_read_tokens": "PPP", "amdr_bm25_reserve": "Piil", "amdr_bm25_workspace_plan": "liiiiP", "amdr_bm25_plan_info": "PiiPi",
     "amdr_bm25_search": "PPPiiPP", "amdr_bm25_search_device": "PPPiiPPP", "amdr_bm25_scores": "PPPiP",
     "amdr_bm25_destroy": "P",
     "amdr_tokenizer_create": "PPlP", "amdr_tokenizer_encode": "PPPiPlPP", "amdr_tokenizer_encode_joined": "PPliPlPP", "amdr_tokenizer_encode_ptrs": "PPPiPlPP", "amdr_tokenizer_spans": "PlPPiP",
@@ -64,6 +64,8 @@ SIGNATURES = {
     "amdr_hybrid_scope_plan": "iiiillPP",
     "amdr_term_scope_plan": "llP", "amdr_term_scope_device": "P" + "P" * 7 + "l" * 5 + "PPP" + "PlP",
     "amdr_term_scope": "P" + "P" * 7 + "l" * 5 + "PPP",
+    "amdr_phrase_lists_plan": "llP", "amdr_phrase_lists_device": "PPP" + "lll" + "PPP" + "PlP", "amdr_phrase_lists": "PPP" + "lll" + "PPP",
+    "amdr_term_scope_lists_device": "P" + "P" * 9 + "l" * 6 + "PPP" + "PlP", "amdr_term_scope_lists": "P" + "P" * 9 + "l" * 6 + "PPP",
 }
 EXPORTS = tuple(SIGNATURES)  # every symbol include/amdretrieval.h declares (checked by tests/test_abi.py)
 _KIND = {"P": C.c_void_p, "i": C.c_int32, "l": C.c_int64, "d": C.c_double}
@@ -208,6 +210,17 @@ def term_scope_plan(n_cons: int, cand_max: int) -> int:
     """Workspace bytes of BM25Index.term_scope_device(n_cons constraints, longest driver cand_max) — host-only arithmetic."""
     out = C.c_int64(0)
     _check(load().amdr_term_scope_plan(C.c_int64(n_cons), C.c_int64(cand_max), C.byref(out)), "amdr_term_scope_plan")
+    return int(out.value)
+
+
+PHRASE_TILE = 256    # candidates per block of amdr_phrase_lists (kPhTile)
+PHRASE_MAX_LEN = 16  # tokens of a phrase (kPhMaxLen)
+
+
+def phrase_lists_plan(n_phr: int, cand_max: int) -> int:
+    """Workspace bytes of BM25Index.phrase_lists_device(n_phr phrases, longest driver cand_max) — host-only arithmetic."""
+    out = C.c_int64(0)
+    _check(load().amdr_phrase_lists_plan(C.c_int64(n_phr), C.c_int64(cand_max), C.byref(out)), "amdr_phrase_lists_plan")
     return int(out.value)
 
 
@@ -630,10 +643,11 @@ class BM25Index(_Handle):
     # base_rows i64, cons_base i32); retrieval/terms.py pack() makes them
     TERM_OPS = (np.int64, np.int32, np.int64, np.int32, np.int64, np.int64, np.int32)
 
-    def term_scope(self, ops, cand_max: int, rows_cap: int):
+    def term_scope(self, ops, cand_max: int, rows_cap: int, lists=None):
         """The host twin: (scope_ptr i64 [n_cons + 1], rows i64 [scope_ptr[-1]], status i32 [n_cons]) of the constraints
         `ops` — validated, staged, resolved on the handle's own stream.  status: 0, 1 (driver longer than cand_max: scope
-        empty), 2 (rows beyond rows_cap dropped)."""
+        empty), 2 (rows beyond rows_cap dropped).  lists = (x_ptr i64 [n_x + 1], x_doc i32): the virtual posting lists of
+        the call (amdr_term_scope_lists; term id n_terms + p names list p) — what phrase_lists returns."""
         a = [_c(x, t).ravel() for x, t in zip(ops, self.TERM_OPS)]
         n_cons, n_groups, n_base = a[6].size, a[1].size, max(a[4].size - 1, 0)
         if a[0].size != n_cons + 1 or a[2].size != n_groups + 1:
@@ -641,21 +655,83 @@ class BM25Index(_Handle):
         sp = np.zeros(n_cons + 1, dtype=np.int64)
         rows = np.full(max(int(rows_cap), 1), -1, dtype=np.int64)
         status = np.zeros(max(n_cons, 1), dtype=np.int32)
-        _check(load().amdr_term_scope(self._h, *(_p(x, C.c_int64 if t is np.int64 else C.c_int32)
-                                                 for x, t in zip(a, self.TERM_OPS)),
-                                      C.c_int64(n_base), C.c_int64(n_cons), C.c_int64(n_groups), C.c_int64(cand_max),
-                                      C.c_int64(rows_cap), _p(sp, C.c_int64), _p(rows, C.c_int64), _p(status, C.c_int32)),
-               "amdr_term_scope")
+        op_ptrs = [_p(x, C.c_int64 if t is np.int64 else C.c_int32) for x, t in zip(a, self.TERM_OPS)]
+        tail = (C.c_int64(n_base), C.c_int64(n_cons), C.c_int64(n_groups), C.c_int64(cand_max), C.c_int64(rows_cap),
+                _p(sp, C.c_int64), _p(rows, C.c_int64), _p(status, C.c_int32))
+        if lists is None:
+            _check(load().amdr_term_scope(self._h, *op_ptrs, *tail), "amdr_term_scope")
+        else:
+            x_ptr, x_doc = _c(lists[0], np.int64).ravel(), _c(lists[1], np.int32).ravel()
+            if x_ptr.size < 1:
+                raise ValueError("term_scope: x_ptr [n_x + 1]")
+            x_doc_arg = x_doc if x_doc.size else np.zeros(1, dtype=np.int32)
+            _check(load().amdr_term_scope_lists(self._h, *op_ptrs, _p(x_ptr, C.c_int64), _p(x_doc_arg, C.c_int32),
+                                                C.c_int64(x_ptr.size - 1), *tail), "amdr_term_scope_lists")
         return sp, rows[:int(sp[-1])], status[:n_cons]
 
     def term_scope_device(self, op_ptrs: Sequence[int], n_base: int, n_cons: int, n_groups: int, cand_max: int, rows_cap: int,
                           scope_ptr_ptr: int, rows_ptr: int, status_ptr: int, work_ptr: int, work_bytes: int,
-                          stream: int = 0) -> None:
-        """The "_device" form: the seven operand arrays and the outputs as device pointers; enqueues only."""
-        _check(load().amdr_term_scope_device(self._h, *(_vp(x) for x in op_ptrs), C.c_int64(n_base), C.c_int64(n_cons),
-                                             C.c_int64(n_groups), C.c_int64(cand_max), C.c_int64(rows_cap),
-                                             _vp(scope_ptr_ptr), _vp(rows_ptr), _vp(status_ptr), _vp(work_ptr),
-                                             C.c_int64(work_bytes), _vp(stream)), "amdr_term_scope_device")
+                          stream: int = 0, lists=None) -> None:
+        """The "_device" form: the seven operand arrays and the outputs as device pointers; enqueues only.
+        lists = (x_ptr device pointer, x_doc device pointer, n_x): the virtual posting lists (amdr_term_scope_lists_device),
+        the outputs of phrase_lists_device enqueued before on the same stream."""
+        tail = (C.c_int64(n_base), C.c_int64(n_cons), C.c_int64(n_groups), C.c_int64(cand_max), C.c_int64(rows_cap),
+                _vp(scope_ptr_ptr), _vp(rows_ptr), _vp(status_ptr), _vp(work_ptr), C.c_int64(work_bytes), _vp(stream))
+        if lists is None:
+            _check(load().amdr_term_scope_device(self._h, *(_vp(x) for x in op_ptrs), *tail), "amdr_term_scope_device")
+        else:
+            _check(load().amdr_term_scope_lists_device(self._h, *(_vp(x) for x in op_ptrs), _vp(lists[0]), _vp(lists[1]),
+                                                       C.c_int64(lists[2]), *tail), "amdr_term_scope_lists_device")
+
+    # -- the token stream and phrases -> virtual posting lists (amdr_phrase_lists, csrc/phrase_scope.hip) -------------
+    def set_tokens(self, doc_ptr, tokens) -> None:
+        """The token stream of the corpus (amdr_bm25_set_tokens): document d's text as the term ids
+        tokens[doc_ptr[d] : doc_ptr[d + 1]], checked against the resident doc_len.  add / remove / replace drop it."""
+        dp, tk = _c(doc_ptr, np.int64).ravel(), _c(tokens, np.int32).ravel()
+        if dp.size != self.n_docs + 1 or (dp.size and tk.size < int(dp[-1])):
+            raise ValueError("set_tokens: doc_ptr [n_docs + 1], tokens [doc_ptr[-1]]")
+        tk_arg = tk if tk.size else np.zeros(1, dtype=np.int32)
+        _check(load().amdr_bm25_set_tokens(self._h, _p(dp, C.c_int64), _p(tk_arg, C.c_int32)), "amdr_bm25_set_tokens")
+
+    def tokens_info(self) -> Tuple[bool, int]:
+        """(whether a token stream is resident, its token count)."""
+        out = (C.c_int64 * 2)()
+        _check(load().amdr_bm25_tokens_info(self._h, out), "amdr_bm25_tokens_info")
+        return bool(out[0]), int(out[1])
+
+    def read_tokens(self):
+        """The resident token stream, copied to the host: (doc_ptr i64 [n_docs + 1], tokens i32)."""
+        n_tok = self.tokens_info()[1]
+        dp, tk = np.empty(self.info()[0] + 1, np.int64), np.empty(n_tok, np.int32)
+        _check(load().amdr_bm25_read_tokens(self._h, _p(dp, C.c_int64), _p(tk, C.c_int32) if n_tok else None),
+               "amdr_bm25_read_tokens")
+        return dp, tk
+
+    def phrase_lists(self, phr_ptr, phr_terms, cand_max: int, rows_cap: int):
+        """The host twin: (list_ptr i64 [n_phr + 1], docs i32 [list_ptr[-1]], status i32 [n_phr]) of the phrases
+        phr_terms[phr_ptr[p] : phr_ptr[p + 1]] — each list the ascending documents that hold the phrase.  status as
+        term_scope."""
+        pp, pt = _c(phr_ptr, np.int64).ravel(), _c(phr_terms, np.int32).ravel()
+        if pp.size < 1:
+            raise ValueError("phrase_lists: phr_ptr [n_phr + 1]")
+        n_phr = pp.size - 1
+        lp = np.zeros(n_phr + 1, dtype=np.int64)
+        docs = np.full(max(int(rows_cap), 1), -1, dtype=np.int32)
+        status = np.zeros(max(n_phr, 1), dtype=np.int32)
+        pt_arg = pt if pt.size else np.zeros(1, dtype=np.int32)
+        _check(load().amdr_phrase_lists(self._h, _p(pp, C.c_int64), _p(pt_arg, C.c_int32), C.c_int64(n_phr),
+                                        C.c_int64(cand_max), C.c_int64(rows_cap), _p(lp, C.c_int64), _p(docs, C.c_int32),
+                                        _p(status, C.c_int32)), "amdr_phrase_lists")
+        return lp, docs[:int(lp[-1])], status[:n_phr]
+
+    def phrase_lists_device(self, phr_ptr_ptr: int, phr_terms_ptr: int, n_phr: int, cand_max: int, rows_cap: int,
+                            list_ptr_ptr: int, docs_ptr: int, status_ptr: int, work_ptr: int, work_bytes: int,
+                            stream: int = 0) -> None:
+        """The "_device" form: operands and outputs as device pointers; enqueues only."""
+        _check(load().amdr_phrase_lists_device(self._h, _vp(phr_ptr_ptr), _vp(phr_terms_ptr), C.c_int64(n_phr),
+                                               C.c_int64(cand_max), C.c_int64(rows_cap), _vp(list_ptr_ptr), _vp(docs_ptr),
+                                               _vp(status_ptr), _vp(work_ptr), C.c_int64(work_bytes), _vp(stream)),
+               "amdr_phrase_lists_device")
 
     def get_scores(self, queries: Sequence[Sequence[int]]) -> np.ndarray:
         q_terms, q_ptr = self.pack_queries(queries)

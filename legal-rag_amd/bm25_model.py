@@ -381,6 +381,29 @@ class BM25Okapi:
             self.__dict__["_gpu_device"] = key
         return g
 
+    def token_stream(self, docs: Sequence[Sequence[str]]):
+        """(doc_ptr i64 [n + 1], tokens i32) of the corpus given as one token SEQUENCE per document, in text order — the
+        operands of BM25Index.set_tokens (the forward index phrase constraints read).  The index keeps counts, not order,
+        so the sequences come from the caller, cut again from the texts; each is checked against what the index holds of
+        its document: as many tokens as doc_len says and the term counts of doc_freqs.  RuntimeError names the first
+        document that differs (texts or a tokeniser that are not the index's)."""
+        if len(docs) != self.corpus_size:
+            raise RuntimeError(f"token_stream: {len(docs)} documents for an index of {self.corpus_size}")
+        vocab = self.vocab()
+        doc_ptr = np.zeros(len(docs) + 1, dtype=np.int64)
+        np.cumsum([len(d) for d in docs], out=doc_ptr[1:])
+        tokens = np.empty(int(doc_ptr[-1]), dtype=np.int32)
+        for d, doc in enumerate(docs):
+            if len(doc) != self.doc_len[d]:
+                raise RuntimeError(f"token_stream: document {d} has {len(doc)} tokens, the index holds {self.doc_len[d]}")
+            freqs: Dict[str, int] = {}
+            for word in doc:
+                freqs[word] = freqs.get(word, 0) + 1
+            if freqs != self.doc_freqs[d]:
+                raise RuntimeError(f"token_stream: the tokens of document {d} are not the ones the index counted")
+            tokens[doc_ptr[d]:doc_ptr[d + 1]] = [vocab[w] for w in doc]
+        return doc_ptr, tokens
+
     def term_ids(self, tokens: Sequence[str]) -> List[int]:
         v = self.vocab()
         return [v.get(t, -1) for t in tokens]

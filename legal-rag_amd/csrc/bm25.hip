@@ -355,6 +355,7 @@ int amdr_bm25_destroy(amdr_bm25_t* h) {
   h->full.release();
   h->tscope.release();
   h->ticket.release();
+  h->drop_tokens();
   delete h;
   return AMDR_OK;
 }

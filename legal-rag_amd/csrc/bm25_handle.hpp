@@ -1,4 +1,5 @@
-// The BM25 handle, shared by bm25.hip (create, plan, score, search, destroy) and bm25_update.hip (add, remove, info, read).
+// The BM25 handle, shared by bm25.hip (create, plan, score, search, destroy), bm25_update.hip (add, remove, info, read),
+// term_scope.hip (term constraints) and phrase_scope.hip (the token stream, phrases).
 #pragma once
 #include "common.hpp"
 
@@ -89,4 +90,15 @@ struct amdr_bm25 {
   amdr::DevBuf part[2], qterms, qptr, sbuf, ibuf, full;
   amdr::DevBuf tscope;  // amdr_term_scope (term_scope.hip): its staged operands, outputs and workspace
   amdr::DevBuf ticket;  // 64 zeroed ints: arrival counters of the one-launch serving step (dense_tail.hip), self-resetting
+  // The token stream (amdr_bm25_set_tokens, phrase_scope.hip): document d's text as the term ids
+  // tok[tok_ptr[d] .. tok_ptr[d + 1]).  It describes ONE state of the index: every successful update drops it.
+  long long* tok_ptr = nullptr;  // [n_docs + 1]
+  int* tok = nullptr;            // [n_tokens]
+  int64_t n_tokens = 0;
+  bool has_tokens = false;
+  void drop_tokens() {
+    if (tok_ptr) (void)hipFree(tok_ptr);
+    if (tok) (void)hipFree(tok);
+    tok_ptr = nullptr, tok = nullptr, n_tokens = 0, has_tokens = false;
+  }
 };

@@ -427,6 +427,7 @@ int amdr_bm25_add(amdr_bm25_t* h, const int64_t* term_ptr_add, const int32_t* po
   AMDR_HIP(hipStreamSynchronize(st));
   h->add_kernel_ms = timer.ms();
   nx.commit(h->ix, h->adds);  // from here on nothing can fail
+  h->drop_tokens();  // the stream described the index as it was (amdr_bm25_set_tokens)
   return AMDR_OK;
 }
 
@@ -503,6 +504,7 @@ int amdr_bm25_remove(amdr_bm25_t* h, const int64_t* remove_ids, int64_t n_remove
   AMDR_HIP(hipStreamSynchronize(st));
   h->remove_kernel_ms = timer.ms();
   nx.commit(h->ix, h->removes);  // from here on nothing can fail
+  h->drop_tokens();  // the stream described the index as it was (amdr_bm25_set_tokens)
   return AMDR_OK;
 }
 
@@ -609,6 +611,7 @@ int amdr_bm25_replace(amdr_bm25_t* h, const int64_t* replace_ids, int64_t n_rep,
   AMDR_HIP(hipStreamSynchronize(st));
   h->replace_kernel_ms = timer.ms();
   nx.commit(h->ix, h->replaces);  // from here on nothing can fail
+  h->drop_tokens();  // the stream described the index as it was (amdr_bm25_set_tokens)
   return AMDR_OK;
 }
 

@@ -6,7 +6,9 @@
 // from term constraints to the ascending row lists the scoped kernels take (scope.hip) runs on the resident term-major
 // postings (BmIndex::term_ptr / post_doc), without a host synchronise: the table it writes is handed unchanged to
 // amdr_scope_*_search_device and amdr_hybrid_scope_device on the same stream.  The rule — what a group and a constraint
-// are, which list drives a constraint — is term_scope_rule.hpp's, shared with the host check.
+// are, which list drives a constraint — is term_scope_rule.hpp's, shared with the host check.  A call may bring VIRTUAL
+// posting lists (amdr_term_scope_lists*: the phrase lists of phrase_scope.hip, written just before on the same stream):
+// term id n_terms + p names the p-th of them wherever a term id may stand.
 //
 // Three launches, no atomics, deterministic; grid = (x = constraint, y = tile of kTsTile candidates of its driver):
 //   count   a block evaluates its tile's candidates (thread t takes candidates t, t + 256, ...: the driver loads are
@@ -168,14 +170,17 @@ int amdr_term_scope_plan(int64_t n_cons, int64_t cand_max, int64_t* work_bytes) 
   return AMDR_OK;
 }
 
-int amdr_term_scope_device(amdr_bm25_t* bm25, const int64_t* grp_ptr_dev, const int32_t* grp_kind_dev,
-                           const int64_t* grp_term_ptr_dev, const int32_t* grp_terms_dev, const int64_t* base_ptr_dev,
-                           const int64_t* base_rows_dev, const int32_t* cons_base_dev, int64_t n_base, int64_t n_cons,
-                           int64_t n_groups, int64_t cand_max, int64_t rows_cap, int64_t* out_scope_ptr_dev,
-                           int64_t* out_rows_dev, int32_t* out_status_dev, void* work_dev, int64_t work_bytes, void* stream) {
+int amdr_term_scope_lists_device(amdr_bm25_t* bm25, const int64_t* grp_ptr_dev, const int32_t* grp_kind_dev,
+                                 const int64_t* grp_term_ptr_dev, const int32_t* grp_terms_dev, const int64_t* base_ptr_dev,
+                                 const int64_t* base_rows_dev, const int32_t* cons_base_dev, const int64_t* x_ptr_dev,
+                                 const int32_t* x_doc_dev, int64_t n_x, int64_t n_base, int64_t n_cons, int64_t n_groups,
+                                 int64_t cand_max, int64_t rows_cap, int64_t* out_scope_ptr_dev, int64_t* out_rows_dev,
+                                 int32_t* out_status_dev, void* work_dev, int64_t work_bytes, void* stream) {
   AMDR_REQUIRE(bm25 != nullptr, "term_scope: null handle");
   int rc = ts_check_sizes("term_scope", n_base, n_cons, n_groups, cand_max, rows_cap);
   if (rc) return rc;
+  AMDR_REQUIRE(n_x >= 0 && n_x <= INT32_MAX, "term_scope: n_x=%lld", (long long)n_x);
+  AMDR_REQUIRE(n_x == 0 || (x_ptr_dev && x_doc_dev), "term_scope: null virtual lists");
   AMDR_REQUIRE(out_scope_ptr_dev != nullptr, "term_scope: null out_scope_ptr");
   AMDR_REQUIRE(n_cons == 0 || (grp_ptr_dev && grp_term_ptr_dev && cons_base_dev && out_status_dev), "term_scope: null operand");
   AMDR_REQUIRE(n_groups == 0 || (grp_kind_dev && grp_terms_dev), "term_scope: null group arrays");
@@ -187,17 +192,28 @@ int amdr_term_scope_device(amdr_bm25_t* bm25, const int64_t* grp_ptr_dev, const 
                (long long)work_bytes, need);
   AMDR_HIP(hipSetDevice(bm25->device));
   const BmIndex& ix = bm25->ix;
-  const TsIndex I{ix.term_ptr, ix.post_doc, (long)ix.n_terms, (long)ix.n_docs};
+  const TsIndex I{ix.term_ptr, ix.post_doc, (long)ix.n_terms, (long)ix.n_docs, (const long long*)x_ptr_dev, x_doc_dev, (long)n_x};
   const TsCons C{(const long long*)grp_ptr_dev, grp_kind_dev, (const long long*)grp_term_ptr_dev, grp_terms_dev,
                  (const long long*)base_ptr_dev, (const long long*)base_rows_dev, cons_base_dev, (int)n_base};
   const TsOut o{(long long*)out_scope_ptr_dev, (long long*)out_rows_dev, out_status_dev};
   return ts_launch(I, C, n_cons, cand_max, rows_cap, o, static_cast<unsigned char*>(work_dev), (hipStream_t)stream);
 }
 
-int amdr_term_scope(amdr_bm25_t* bm25, const int64_t* grp_ptr, const int32_t* grp_kind, const int64_t* grp_term_ptr,
-                    const int32_t* grp_terms, const int64_t* base_ptr, const int64_t* base_rows, const int32_t* cons_base,
-                    int64_t n_base, int64_t n_cons, int64_t n_groups, int64_t cand_max, int64_t rows_cap,
-                    int64_t* out_scope_ptr, int64_t* out_rows, int32_t* out_status) {
+int amdr_term_scope_device(amdr_bm25_t* bm25, const int64_t* grp_ptr_dev, const int32_t* grp_kind_dev,
+                           const int64_t* grp_term_ptr_dev, const int32_t* grp_terms_dev, const int64_t* base_ptr_dev,
+                           const int64_t* base_rows_dev, const int32_t* cons_base_dev, int64_t n_base, int64_t n_cons,
+                           int64_t n_groups, int64_t cand_max, int64_t rows_cap, int64_t* out_scope_ptr_dev,
+                           int64_t* out_rows_dev, int32_t* out_status_dev, void* work_dev, int64_t work_bytes, void* stream) {
+  return amdr_term_scope_lists_device(bm25, grp_ptr_dev, grp_kind_dev, grp_term_ptr_dev, grp_terms_dev, base_ptr_dev,
+                                      base_rows_dev, cons_base_dev, nullptr, nullptr, 0, n_base, n_cons, n_groups, cand_max,
+                                      rows_cap, out_scope_ptr_dev, out_rows_dev, out_status_dev, work_dev, work_bytes, stream);
+}
+
+int amdr_term_scope_lists(amdr_bm25_t* bm25, const int64_t* grp_ptr, const int32_t* grp_kind, const int64_t* grp_term_ptr,
+                          const int32_t* grp_terms, const int64_t* base_ptr, const int64_t* base_rows,
+                          const int32_t* cons_base, const int64_t* x_ptr, const int32_t* x_doc, int64_t n_x, int64_t n_base,
+                          int64_t n_cons, int64_t n_groups, int64_t cand_max, int64_t rows_cap, int64_t* out_scope_ptr,
+                          int64_t* out_rows, int32_t* out_status) {
   AMDR_REQUIRE(bm25 != nullptr, "term_scope: null handle");
   int rc = ts_check_sizes("term_scope", n_base, n_cons, n_groups, cand_max, rows_cap);
   if (rc) return rc;
@@ -208,6 +224,10 @@ int amdr_term_scope(amdr_bm25_t* bm25, const int64_t* grp_ptr, const int32_t* gr
   const int bad = ts_validate(grp_ptr, grp_kind, grp_term_ptr, base_ptr, base_rows, cons_base, n_base, n_cons, n_groups,
                               bm25->ix.n_docs);
   AMDR_REQUIRE(bad == kTsValid, "term_scope: %s", ts_error_text(bad));
+  AMDR_REQUIRE(n_x <= INT32_MAX, "term_scope: n_x=%lld", (long long)n_x);
+  const int bad_x = ts_validate_lists(x_ptr, x_doc, n_x, bm25->ix.n_docs);
+  AMDR_REQUIRE(bad_x == kTsValid, "term_scope: %s", ts_error_text(bad_x));
+  const int64_t n_x_docs = n_x ? x_ptr[n_x] : 0;
   const int64_t n_terms_all = grp_term_ptr[n_groups], n_base_rows = n_base ? base_ptr[n_base] : 0;
   AMDR_REQUIRE(n_terms_all == 0 || grp_terms, "term_scope: null grp_terms");
   if (n_cons == 0) {
@@ -215,28 +235,32 @@ int amdr_term_scope(amdr_bm25_t* bm25, const int64_t* grp_ptr, const int32_t* gr
     return AMDR_OK;
   }
   AMDR_HIP(hipSetDevice(bm25->device));
-  // Layout of the staging buffer: the seven operand arrays | scope_ptr | rows | status | the workspace, each aligned.
-  const size_t b[7] = {(size_t)(n_cons + 1) * 8, (size_t)n_groups * 4,   (size_t)(n_groups + 1) * 8, (size_t)n_terms_all * 4,
-                       (size_t)(n_base + 1) * 8, (size_t)n_base_rows * 8, (size_t)n_cons * 4};
-  const void* src[7] = {grp_ptr, grp_kind, grp_term_ptr, grp_terms, base_ptr, base_rows, cons_base};
-  size_t at[11], total = 0;
-  for (int i = 0; i < 7; ++i) at[i] = total, total += ts_align(b[i]);
-  at[7] = total, total += ts_align((size_t)(n_cons + 1) * 8);
-  at[8] = total, total += ts_align((size_t)rows_cap * 8);
-  at[9] = total, total += ts_align((size_t)n_cons * 4);
-  at[10] = total, total += ts_work(n_cons, cand_max).total;
+  // Layout of the staging buffer: the seven operand arrays and the two of the virtual lists | scope_ptr | rows | status |
+  // the workspace, each aligned.
+  constexpr int kOps = 9;
+  const size_t b[kOps] = {(size_t)(n_cons + 1) * 8, (size_t)n_groups * 4,    (size_t)(n_groups + 1) * 8,
+                          (size_t)n_terms_all * 4,  (size_t)(n_base + 1) * 8, (size_t)n_base_rows * 8,
+                          (size_t)n_cons * 4,       n_x ? (size_t)(n_x + 1) * 8 : 0, (size_t)n_x_docs * 4};
+  const void* src[kOps] = {grp_ptr, grp_kind, grp_term_ptr, grp_terms, base_ptr, base_rows, cons_base, x_ptr, x_doc};
+  size_t at[kOps + 4], total = 0;
+  for (int i = 0; i < kOps; ++i) at[i] = total, total += ts_align(b[i]);
+  at[kOps] = total, total += ts_align((size_t)(n_cons + 1) * 8);
+  at[kOps + 1] = total, total += ts_align((size_t)rows_cap * 8);
+  at[kOps + 2] = total, total += ts_align((size_t)n_cons * 4);
+  at[kOps + 3] = total, total += ts_work(n_cons, cand_max).total;
   if ((rc = bm25->tscope.ensure(total))) return rc;
   unsigned char* p = bm25->tscope.as<unsigned char>();
   hipStream_t st = bm25->stream;
-  for (int i = 0; i < 7; ++i)
+  for (int i = 0; i < kOps; ++i)
     if (b[i] && src[i]) AMDR_HIP(hipMemcpyAsync(p + at[i], src[i], b[i], hipMemcpyHostToDevice, st));
   if (n_base == 0) AMDR_HIP(hipMemsetAsync(p + at[4], 0, 8, st));
   const BmIndex& ix = bm25->ix;
-  const TsIndex I{ix.term_ptr, ix.post_doc, (long)ix.n_terms, (long)ix.n_docs};
+  const TsIndex I{ix.term_ptr,  ix.post_doc, (long)ix.n_terms, (long)ix.n_docs, (const long long*)(p + at[7]),
+                  (const int*)(p + at[8]), (long)n_x};
   const TsCons C{(const long long*)(p + at[0]), (const int*)(p + at[1]), (const long long*)(p + at[2]), (const int*)(p + at[3]),
                  (const long long*)(p + at[4]), (const long long*)(p + at[5]), (const int*)(p + at[6]), (int)n_base};
-  const TsOut o{(long long*)(p + at[7]), (long long*)(p + at[8]), (int*)(p + at[9])};
-  if ((rc = ts_launch(I, C, n_cons, cand_max, rows_cap, o, p + at[10], st))) return rc;
+  const TsOut o{(long long*)(p + at[kOps]), (long long*)(p + at[kOps + 1]), (int*)(p + at[kOps + 2])};
+  if ((rc = ts_launch(I, C, n_cons, cand_max, rows_cap, o, p + at[kOps + 3], st))) return rc;
   AMDR_HIP(hipMemcpyAsync(out_scope_ptr, o.scope_ptr, (size_t)(n_cons + 1) * 8, hipMemcpyDeviceToHost, st));
   AMDR_HIP(hipMemcpyAsync(out_status, o.status, (size_t)n_cons * 4, hipMemcpyDeviceToHost, st));
   AMDR_HIP(hipStreamSynchronize(st));
@@ -246,6 +270,14 @@ int amdr_term_scope(amdr_bm25_t* bm25, const int64_t* grp_ptr, const int32_t* gr
     AMDR_HIP(hipStreamSynchronize(st));
   }
   return AMDR_OK;
+}
+
+int amdr_term_scope(amdr_bm25_t* bm25, const int64_t* grp_ptr, const int32_t* grp_kind, const int64_t* grp_term_ptr,
+                    const int32_t* grp_terms, const int64_t* base_ptr, const int64_t* base_rows, const int32_t* cons_base,
+                    int64_t n_base, int64_t n_cons, int64_t n_groups, int64_t cand_max, int64_t rows_cap,
+                    int64_t* out_scope_ptr, int64_t* out_rows, int32_t* out_status) {
+  return amdr_term_scope_lists(bm25, grp_ptr, grp_kind, grp_term_ptr, grp_terms, base_ptr, base_rows, cons_base, nullptr,
+                               nullptr, 0, n_base, n_cons, n_groups, cand_max, rows_cap, out_scope_ptr, out_rows, out_status);
 }
 
 }  // extern "C"

@@ -4,9 +4,11 @@
 // CPU) share this one source, in the style of rows_compact.hpp and bm25_*_rule.hpp.
 //
 // The rule.  A constraint is a list of groups; a group is a non-empty list of term ids with a kind.  A document
-// SATISFIES a group when it has a posting for EVERY term of the group: a conjunction.  The postings hold no positions, so
-// this is not a phrase match — ("consequential", "damages") names the documents that hold both words, anywhere.  The id -1
-// (and any id outside [0, n_terms)) is a token the vocabulary does not hold: present in no document, never dereferenced.
+// SATISFIES a group when it has a posting for EVERY term of the group: a conjunction — ("consequential", "damages") names
+// the documents that hold both words, anywhere.  The words in that order are a phrase: amdr_phrase_lists (phrase_rule.hpp)
+// resolves it into an ascending document list of its own, a VIRTUAL posting list, and the term id n_terms + p names the
+// p-th such list of a call (TsIndex::x_ptr / x_doc / n_x), wherever a term id may stand.  The id -1 (and any id outside
+// [0, n_terms + n_x)) is a token the vocabulary does not hold: present in no document, never dereferenced.
 // A document QUALIFIES when it satisfies every MUST group, at least one ANY group (or there is none), no NOT group, and
 // lies in the constraint's base scope (an ascending row list), if it has one.
 //
@@ -36,10 +38,15 @@ enum TsStatus {
 constexpr int kTsTile = 1024;  // candidates per block
 
 // The resident postings (BmIndex): term t's documents are post_doc[term_ptr[t] .. term_ptr[t + 1]), strictly ascending.
+// The virtual lists of the call: term n_terms + p, p < n_x, has the documents x_doc[x_ptr[p] .. x_ptr[p + 1]), strictly
+// ascending as well (n_x = 0, what an initialiser without them yields: none).
 struct TsIndex {
   const long long* term_ptr;
   const int* post_doc;
   long n_terms, n_docs;
+  const long long* x_ptr;
+  const int* x_doc;
+  long n_x;
 };
 
 // The constraints of a call.  Groups of constraint c: grp_ptr[c] .. grp_ptr[c + 1]; terms of group g:
@@ -56,11 +63,11 @@ struct TsCons {
   int n_base;
 };
 
-enum TsDriverKind { kTsDrvEmpty = 0, kTsDrvBase = 1, kTsDrvPosting = 2, kTsDrvIota = 3 };
+enum TsDriverKind { kTsDrvEmpty = 0, kTsDrvBase = 1, kTsDrvPosting = 2, kTsDrvIota = 3, kTsDrvVirtual = 4 };
 struct TsDriver {
   int kind;
-  int term;         // kTsDrvPosting: the term whose list drives (every candidate has it), else -1
-  long long begin;  // first candidate: an index into base_rows / post_doc (0 for the iota form)
+  int term;         // kTsDrvPosting / kTsDrvVirtual: the term whose list drives (every candidate has it), else -1
+  long long begin;  // first candidate: an index into base_rows / post_doc / x_doc (0 for the iota form)
   long long len;    // the candidate count of the constraint
 };
 
@@ -78,6 +85,25 @@ AMDR_TS_HD inline bool posting_has(const long long* term_ptr, const int* post_do
       hi = mid;
   }
   return lo < end && post_doc[lo] == doc;
+}
+
+// The list of term `t` of the index, a resident or a virtual one, as [*lo, *hi) of *docs; false: no such term.
+AMDR_TS_HD inline bool ts_list_of(const TsIndex& I, int t, const int** docs, long long* lo, long long* hi) {
+  if (t < 0) return false;
+  if (t < I.n_terms) {
+    *docs = I.post_doc, *lo = I.term_ptr[t], *hi = I.term_ptr[t + 1];
+    return true;
+  }
+  const long p = (long)t - I.n_terms;
+  if (p >= I.n_x) return false;
+  *docs = I.x_doc, *lo = I.x_ptr[p], *hi = I.x_ptr[p + 1];
+  return true;
+}
+
+// posting_has over the index with its virtual lists: one binary search in the list the id names.
+AMDR_TS_HD inline bool posting_has(const TsIndex& I, int term, long long doc) {
+  if (term < I.n_terms) return posting_has(I.term_ptr, I.post_doc, I.n_terms, term, doc);
+  return posting_has(I.x_ptr, I.x_doc, I.n_x, (int)(term - I.n_terms), doc);
 }
 
 // Whether `doc` is one of the ascending rows[lo .. hi).
@@ -109,7 +135,7 @@ AMDR_TS_HD inline bool ts_group_has(const TsIndex& I, const TsCons& C, long long
   for (long long j = C.grp_term_ptr[g]; j < C.grp_term_ptr[g + 1]; ++j) {
     const int t = C.grp_terms[j];
     if (t >= 0 && t == known_term) continue;
-    if (!posting_has(I.term_ptr, I.post_doc, I.n_terms, t, doc)) return false;
+    if (!posting_has(I, t, doc)) return false;
   }
   return true;
 }
@@ -152,10 +178,12 @@ AMDR_TS_HD inline TsDriver ts_driver(const TsIndex& I, const TsCons& C, long c) 
     if (C.grp_kind[g] != kTsMust) continue;
     for (long long j = C.grp_term_ptr[g]; j < C.grp_term_ptr[g + 1]; ++j) {
       const int t = C.grp_terms[j];
-      if (t < 0 || t >= I.n_terms) return TsDriver{kTsDrvEmpty, -1, 0, 0};
-      const long long p0 = I.term_ptr[t], len = I.term_ptr[t + 1] - p0;
+      const int* docs;
+      long long p0, p1;
+      if (!ts_list_of(I, t, &docs, &p0, &p1)) return TsDriver{kTsDrvEmpty, -1, 0, 0};
+      const long long len = p1 - p0;
       if (!have || len < d.len) {
-        d = TsDriver{kTsDrvPosting, t, p0, len};
+        d = TsDriver{t < I.n_terms ? kTsDrvPosting : kTsDrvVirtual, t, p0, len};
         have = true;
       }
     }
@@ -166,7 +194,10 @@ AMDR_TS_HD inline TsDriver ts_driver(const TsIndex& I, const TsCons& C, long c) 
 
 // Candidate i of the driver, i in [0, D.len).
 AMDR_TS_HD inline long long ts_candidate(const TsIndex& I, const TsCons& C, const TsDriver& D, long long i) {
-  return D.kind == kTsDrvBase ? C.base_rows[D.begin + i] : D.kind == kTsDrvPosting ? (long long)I.post_doc[D.begin + i] : i;
+  return D.kind == kTsDrvBase      ? C.base_rows[D.begin + i]
+         : D.kind == kTsDrvPosting ? (long long)I.post_doc[D.begin + i]
+         : D.kind == kTsDrvVirtual ? (long long)I.x_doc[D.begin + i]
+                                   : i;
 }
 
 // Tiles of kTsTile candidates that cover a driver of up to cand_max candidates (at least one: every constraint has a
@@ -189,6 +220,9 @@ enum TsError {
   kTsBaseRange,   // a base row outside [0, n_docs)
   kTsBaseOrder,   // base rows of one scope not strictly ascending
   kTsConsBase,    // cons_base outside [-1, n_base)
+  kTsListPtr,     // x_ptr does not start at 0 or is not monotone
+  kTsListRange,   // a document of a virtual list outside [0, n_docs)
+  kTsListOrder,   // the documents of a virtual list not strictly ascending
 };
 
 inline const char* ts_error_text(int e) {
@@ -203,6 +237,9 @@ inline const char* ts_error_text(int e) {
     case kTsBaseRange: return "a base row outside [0, n_docs)";
     case kTsBaseOrder: return "the rows of a base scope are not strictly ascending";
     case kTsConsBase: return "a cons_base outside [-1, n_base)";
+    case kTsListPtr: return "x_ptr does not run monotonically from 0";
+    case kTsListRange: return "a document of a virtual list outside [0, n_docs)";
+    case kTsListOrder: return "the documents of a virtual list are not strictly ascending";
     default: return "ok";
   }
 }
@@ -236,6 +273,23 @@ inline int ts_validate(const int64_t* grp_ptr, const int32_t* grp_kind, const in
   }
   for (int64_t c = 0; c < n_cons; ++c)
     if (cons_base[c] < -1 || cons_base[c] >= n_base) return kTsConsBase;
+  return kTsValid;
+}
+
+// The virtual lists of amdr_term_scope_lists (n_x = 0: none, nothing is read).
+inline int ts_validate_lists(const int64_t* x_ptr, const int32_t* x_doc, int64_t n_x, int64_t n_docs) {
+  if (n_x < 0) return kTsSizes;
+  if (n_x == 0) return kTsValid;
+  if (!x_ptr) return kTsNull;
+  if (x_ptr[0] != 0) return kTsListPtr;
+  for (int64_t p = 0; p < n_x; ++p)
+    if (x_ptr[p + 1] < x_ptr[p]) return kTsListPtr;
+  if (x_ptr[n_x] > 0 && !x_doc) return kTsNull;
+  for (int64_t p = 0; p < n_x; ++p)
+    for (int64_t j = x_ptr[p]; j < x_ptr[p + 1]; ++j) {
+      if (x_doc[j] < 0 || x_doc[j] >= n_docs) return kTsListRange;
+      if (j > x_ptr[p] && x_doc[j] <= x_doc[j - 1]) return kTsListOrder;
+    }
   return kTsValid;
 }
 

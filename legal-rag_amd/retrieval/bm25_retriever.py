@@ -56,6 +56,7 @@ class BM25Retriever:
         self.bm25: BM25Okapi | None = None
         self.chunks: List[LawChunk] = []
         self._lock = threading.Lock()
+        self._tokens_lock = threading.Lock()          # one thread makes the token stream (ensure_token_stream)
         self.index_tokenizer: Optional[str] = None  # id recorded in bm25.pkl (None: reference-built)
         self._tls = threading.local()                 # per-thread: did the last query use the stand-in?
         self.shard = None                             # sharding.ShardSpec in a row-sharded deployment
@@ -216,6 +217,41 @@ class BM25Retriever:
         """The _native.BM25Index this retriever scores with (this rank's row block in a sharded deployment)."""
         self.load()
         return self.bm25.gpu(self.device_index, rows=self.shard.bounds(self.bm25.corpus_size) if self.shard else None)
+
+    def document_tokens(self, s: str) -> List[str]:
+        """A string cut as the index cut its documents (builders/bm25_builder.tokenize_corpus): the English regex rule on
+        lower-cased text for an index recorded as "en_regex", else text.jieba_cut in the configured mode — when that is
+        the segmenter the index records.  ValueError on an index that records no tokeniser (a reference rank_bm25 pickle),
+        caller-made tokens ("pretokenized") or a segmenter this process does not have: the text cannot be cut again as
+        the index's documents were, and a phrase needs exactly that."""
+        self.load()
+        tid = self.index_tokenizer
+        if tid == "en_regex":
+            return text.tokenize_en(s)
+        mode = text.cfg_mode(self.cfg)
+        if tid is None or tid != text.tokenizer_id(mode):
+            raise ValueError(
+                f"[BM25] {self.bm25_path} records "
+                + ("no tokenizer (an index built by the reference)" if tid is None else f"the tokenizer {tid!r}")
+                + f", this process cuts documents with {text.tokenizer_id(mode)!r}: the chunk texts cannot be cut again as "
+                  f"the index's documents were, which a phrase constraint needs (the token order is not in the index). "
+                  f"Rebuild the index here, or register the segmenter it was built with.")
+        return text.jieba_cut(s, mode, text.cfg_dict_file(self.cfg))
+
+    def ensure_token_stream(self) -> None:
+        """The resident token stream of the native index (BM25Index.set_tokens), made on the first phrase constraint and
+        again after a live add / remove / replace (the native handle drops it with every update and reports none): the
+        chunk texts cut by document_tokens, each document checked against the model's doc_len and doc_freqs
+        (BM25Okapi.token_stream: RuntimeError on a mismatch).  Not on a row shard."""
+        self.load()
+        if self.shard is not None:
+            raise ValueError("phrase constraints do not run on a row-sharded index")
+        g = self.gpu_index()
+        with self._tokens_lock:
+            if g.tokens_info()[0]:
+                return
+            doc_ptr, tokens = self.bm25.token_stream([self.document_tokens(c.text) for c in self.chunks])
+            g.set_tokens(doc_ptr, tokens)
 
     def tokenize_query(self, query: str) -> List[str]:
         """bm25_retriever.py:73 — jieba.cut, not lower-cased.  Mode "char" / "dict" when the index was built

@@ -7,11 +7,16 @@ names what a chunk's text must contain, `pack()` turns the (Scope, Terms) pairs 
 amdr_term_scope (csrc/term_scope.hip), and the GPU resolves them on the resident BM25 postings into the scope table the
 scoped channels take: every channel then ranks only the qualifying chunks, with the scores and the order of the unscoped
 channels (idf and avgdl stay those of the whole index).
+
+A `Phrase` is an exact token SEQUENCE: Phrase("security", "interest") names the chunks that hold the two words next to
+each other in that order.  It stands wherever a token stands.  The GPU resolves each phrase of a batch from the resident
+token stream into an ascending document list of its own (amdr_phrase_lists, csrc/phrase_scope.hip), and the term step
+reads that list as one more term.
 """
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import Any, Dict, List, Mapping, Optional, Sequence, Tuple
+from typing import Any, Dict, List, Mapping, Optional, Sequence, Tuple, Union
 
 import numpy as np
 
@@ -19,17 +24,70 @@ from .scope import Scope
 
 MUST, ANY, NOT = 0, 1, 2  # the group kinds of the ABI (term_scope_rule.hpp TsKind)
 
-Group = Tuple[str, ...]
+PHRASE_MAX_LEN = 16  # tokens of a phrase (phrase_rule.hpp kPhMaxLen)
+
+
+class Phrase:
+    """An exact token sequence: a chunk holds Phrase(t0, t1, ...) when its text, as the index's tokeniser cuts it, has
+    t0 t1 ... at consecutive positions (never across two chunks).  1 to 16 tokens (ValueError otherwise); one token is
+    the plain term.  Accepted wherever a token is: as an entry of a Terms field or as a member of a tuple group.  Tokens
+    are compared exactly, as a Terms' are (HybridRetriever.phrase cuts a string with the index's own tokeniser).
+    Frozen and hashable: equal phrases are equal and hash alike."""
+    __slots__ = ("tokens",)
+
+    def __init__(self, *tokens: str) -> None:
+        if not 1 <= len(tokens) <= PHRASE_MAX_LEN:
+            raise ValueError(f"Phrase: 1 to {PHRASE_MAX_LEN} tokens, got {len(tokens)}")
+        for t in tokens:
+            if not isinstance(t, str):
+                raise TypeError(f"Phrase: a token is a str, got {type(t).__name__}")
+        object.__setattr__(self, "tokens", tuple(tokens))
+
+    def __setattr__(self, name, value) -> None:
+        raise AttributeError("Phrase is frozen")
+
+    def __delattr__(self, name) -> None:
+        raise AttributeError("Phrase is frozen")
+
+    def __eq__(self, other) -> bool:
+        return isinstance(other, Phrase) and self.tokens == other.tokens
+
+    def __hash__(self) -> int:
+        return hash(("Phrase", self.tokens))
+
+    def __len__(self) -> int:
+        return len(self.tokens)
+
+    def __repr__(self) -> str:
+        return "Phrase(" + ", ".join(repr(t) for t in self.tokens) + ")"
+
+    def __reduce__(self):
+        return (Phrase, self.tokens)
+
+    def within(self, tokens: Sequence[str]) -> bool:
+        """Whether the token sequence `tokens` holds this phrase (the plain window scan)."""
+        L, want = len(self.tokens), self.tokens
+        return any(tuple(tokens[p:p + L]) == want for p in range(len(tokens) - L + 1))
+
+
+Member = Union[str, Phrase]
+Group = Tuple[Member, ...]
+
+
+def _member(t) -> Member:
+    if isinstance(t, Phrase):
+        return t.tokens[0] if len(t) == 1 else t  # one token is the plain term
+    return str(t)
 
 
 def _groups(x, field: str) -> Optional[Tuple[Group, ...]]:
     if x is None:
         return None
-    if isinstance(x, str):
+    if isinstance(x, (str, Phrase)):
         x = (x,)
     out: List[Group] = []
     for e in x:
-        g = (e,) if isinstance(e, str) else tuple(str(t) for t in e)
+        g = (_member(e),) if isinstance(e, (str, Phrase)) else tuple(_member(t) for t in e)
         if not g:
             raise ValueError(f"Terms.{field}: an empty group names no token")
         out.append(g)
@@ -39,8 +97,10 @@ def _groups(x, field: str) -> Optional[Tuple[Group, ...]]:
 @dataclass(frozen=True)
 class Terms:
     """What a chunk's text must contain.  An entry is one vocabulary token (`str`) or a tuple of tokens, one GROUP: a
-    chunk satisfies a group when it holds EVERY token of it, anywhere — a conjunction, not a phrase match: the postings
-    hold no positions.  For a char-cut Han index a word is the group of its characters, ("合", "同").
+    chunk satisfies a group when it holds EVERY token of it, anywhere — a conjunction.  The tokens next to each other
+    in order are a `Phrase`, which stands wherever a token stands: as an entry, or inside a tuple group.  For a
+    char-cut Han index a word is the phrase of its characters, Phrase("合", "同") (the group ("合", "同") also names
+    every chunk that holds 同 … 合).
       all_of   every entry must be satisfied (each entry is a MUST group);
       any_of   at least one entry must be satisfied;
       none_of  no entry may be satisfied (a tuple excludes only the chunks that hold ALL its tokens).
@@ -67,10 +127,20 @@ class Terms:
         return ([(MUST, g) for g in self.all_of or ()] + [(ANY, g) for g in self.any_of or ()]
                 + [(NOT, g) for g in self.none_of or ()])
 
+    @property
+    def has_phrase(self) -> bool:
+        return any(isinstance(t, Phrase) for _, g in self.groups() for t in g)
+
     def matches(self, tokens) -> bool:
-        """The rule on one document's token set (host check; the kernels apply term_scope_rule.hpp)."""
-        have = tokens if isinstance(tokens, (set, frozenset, dict)) else set(tokens)
-        sat = lambda g: all(t in have for t in g)  # noqa: E731
+        """The rule on one document's tokens (host check; the kernels apply term_scope_rule.hpp and phrase_rule.hpp): a
+        token set or sequence — with a Phrase present, the token SEQUENCE in text order (TypeError for a set)."""
+        if self.has_phrase:
+            if isinstance(tokens, (set, frozenset, dict)) or not isinstance(tokens, Sequence):
+                raise TypeError("Terms.matches: a Terms with a Phrase needs the document's token sequence, not a set")
+            have = set(tokens)
+        else:
+            have = tokens if isinstance(tokens, (set, frozenset, dict)) else set(tokens)
+        sat = lambda g: all(t.within(tokens) if isinstance(t, Phrase) else t in have for t in g)  # noqa: E731
         return (all(sat(g) for g in self.all_of or ()) and (self.any_of is None or any(sat(g) for g in self.any_of))
                 and not any(sat(g) for g in self.none_of or ()))
 
@@ -78,7 +148,9 @@ class Terms:
 def driver_length(groups: Sequence[Tuple[int, Sequence[int]]], df: Sequence[int], base_len: Optional[int], n_docs: int) -> int:
     """The candidate count of a constraint by the rule of term_scope_rule.hpp (ts_driver): the shortest of { the base
     scope, the posting list of each MUST term }; 0 with an unknown MUST term; n_docs with neither a MUST term nor a base.
-    groups: (kind, term ids); df[t]: the document frequency of term t."""
+    groups: (kind, term ids); df[t]: the document frequency of term t — for the id of a phrase (a virtual list, ids behind
+    the vocabulary's: pack) the UPPER bound of its list's length, the smallest document frequency among its tokens.  The
+    device's driver is the shortest of the true lengths, each <= its bound, so the result is an upper bound of it."""
     best = base_len
     for kind, ids in groups:
         if kind != MUST:
@@ -102,6 +174,15 @@ class TermTable:
     driver_lens: np.ndarray       # i64 [n_cons]
     cand_max: int                 # the longest driver
     rows_cap: int                 # the sum of the drivers: no table is longer
+    # the phrases of the batch, each stored once; phrase p is term id len(vocab) + p in `ops` (amdr_phrase_lists)
+    phr_ops: Tuple[np.ndarray, ...] = (np.zeros(1, dtype=np.int64), np.zeros(0, dtype=np.int32))  # phr_ptr, phr_terms
+    phrases: Tuple[Phrase, ...] = ()
+    phr_cand_max: int = 0         # the longest phrase driver: the largest of the phrases' upper bounds
+    phr_rows_cap: int = 0         # the sum of the upper bounds
+
+    @property
+    def n_phr(self) -> int:
+        return len(self.phrases)
 
 
 def pack(pairs: Sequence[Tuple[Optional[Scope], Terms]], vocab: Mapping[str, int], doc_freq: Mapping[str, int], n_docs: int,
@@ -111,14 +192,32 @@ def pack(pairs: Sequence[Tuple[Optional[Scope], Terms]], vocab: Mapping[str, int
     vocab / doc_freq: the live host model's token -> term id and token -> document frequency (BM25Okapi.vocab(),
     _doc_frequencies()); base_rows(scope) -> the ascending int64 rows of a Scope (ScopeResolver.rows), needed only when a
     pair carries one.  The bounds come from the host model by the header's own rule: cand_max = the longest driver,
-    rows_cap = the sum of the drivers."""
-    df_by_id = np.zeros(len(vocab), dtype=np.int64)
+    rows_cap = the sum of the drivers.  Equal phrases are stored once as well and stand in the table as the term ids
+    len(vocab) + p; the host knows only an upper bound of a phrase's list — the smallest document frequency among its
+    tokens, 0 with an unknown one — which serves both steps: phr_cand_max / phr_rows_cap are the largest and the sum of
+    these, and the drivers of the term step are computed with them (driver_length)."""
+    n_vocab = len(vocab)
+    df_by_id = np.zeros(n_vocab, dtype=np.int64)
     for w, t in vocab.items():
         df_by_id[t] = doc_freq.get(w, 0)
+    phr_slot: Dict[Phrase, int] = {}
+    phr_ptr, phr_terms, phr_bound = [0], [], []
+
+    def term_id(t) -> int:
+        if not isinstance(t, Phrase):
+            return vocab.get(t, -1)
+        p = phr_slot.get(t)
+        if p is None:
+            p = phr_slot[t] = len(phr_bound)
+            ids = [vocab.get(w, -1) for w in t.tokens]
+            phr_terms.extend(ids)
+            phr_ptr.append(len(phr_terms))
+            phr_bound.append(0 if min(ids) < 0 else int(min(df_by_id[i] for i in ids)))
+        return n_vocab + p
     slot: Dict[Any, int] = {}
     base_slot: Dict[Scope, int] = {}
     bases: List[np.ndarray] = []
-    grp_ptr, grp_kind, grp_term_ptr, grp_terms, cons_base, lens = [0], [], [0], [], [], []
+    grp_ptr, grp_kind, grp_term_ptr, grp_terms, cons_base, cons_groups = [0], [], [0], [], [], []
     qscope = np.empty(len(pairs), dtype=np.int32)
     for i, (scope, terms) in enumerate(pairs):
         if not isinstance(terms, Terms):
@@ -134,14 +233,14 @@ def pack(pairs: Sequence[Tuple[Optional[Scope], Terms]], vocab: Mapping[str, int
                 if b is None:
                     b = base_slot[scope] = len(bases)
                     bases.append(np.ascontiguousarray(base_rows(scope), dtype=np.int64))
-            groups = [(kind, [vocab.get(t, -1) for t in g]) for kind, g in terms.groups()]
+            groups = [(kind, [term_id(t) for t in g]) for kind, g in terms.groups()]
             for kind, ids in groups:
                 grp_kind.append(kind)
                 grp_terms.extend(ids)
                 grp_term_ptr.append(len(grp_terms))
             grp_ptr.append(len(grp_kind))
             cons_base.append(b)
-            lens.append(driver_length(groups, df_by_id, int(bases[b].size) if b >= 0 else None, n_docs))
+            cons_groups.append(groups)
         qscope[i] = j
     base_ptr = np.zeros(len(bases) + 1, dtype=np.int64)
     if bases:
@@ -149,6 +248,10 @@ def pack(pairs: Sequence[Tuple[Optional[Scope], Terms]], vocab: Mapping[str, int
     ops = (np.asarray(grp_ptr, dtype=np.int64), np.asarray(grp_kind, dtype=np.int32), np.asarray(grp_term_ptr, dtype=np.int64),
            np.asarray(grp_terms, dtype=np.int32), base_ptr,
            np.concatenate(bases) if bases else np.zeros(0, dtype=np.int64), np.asarray(cons_base, dtype=np.int32))
-    lens_a = np.asarray(lens, dtype=np.int64)
+    df_all = np.concatenate([df_by_id, np.asarray(phr_bound, dtype=np.int64)])  # (the phrases are all known by now)
+    lens_a = np.asarray([driver_length(g, df_all, int(bases[b].size) if b >= 0 else None, n_docs)
+                         for g, b in zip(cons_groups, cons_base)], dtype=np.int64)
     return TermTable(ops, qscope, len(cons_base), len(grp_kind), len(bases), lens_a,
-                     int(lens_a.max()) if lens_a.size else 0, int(lens_a.sum()))
+                     int(lens_a.max()) if lens_a.size else 0, int(lens_a.sum()),
+                     (np.asarray(phr_ptr, dtype=np.int64), np.asarray(phr_terms, dtype=np.int32)), tuple(phr_slot),
+                     max(phr_bound, default=0), int(sum(phr_bound)))
