@@ -630,6 +630,22 @@ int amdr_hybrid_small_device(amdr_dense_t* dense, amdr_bm25_t* bm25, const float
                              int64_t* dense_ids_dev, double* bm25_scores_dev, int64_t* bm25_ids_dev, int64_t* out_ids,
                              double* out_vals, int32_t* out_mask, int32_t* out_count, void* stream);
 
+/* The long-batch hybrid step — HybridRetriever.search_batch on dense + BM25 (hybrid_retriever.py: search_dense :181-189,
+ * search_bm25 :191-209, _fuse :389-551) — as ONE call: amdr_bm25_search_device + amdr_dense_search_fuse_device, the same
+ * five outputs bit for bit (arguments as amdr_hybrid_small_device).  Where the dense channel takes its two-pass form as
+ * one pass (from 4 096 queries on <= 1 024 rows, d a multiple of 128, kd <= 12, kd + kb <= 32) and both indexes are on
+ * the same device, the call forks inside, behind the first pass's scores kernel: BM25 runs on the dense handle's side
+ * stream beside the second dense pass on the caller's stream, and the fusion runs behind the join.  Fork and join are events: the caller's stream is ordered
+ * behind both branches when the call returns (the next call may reuse the workspaces), and while the caller's stream is
+ * capturing they become graph edges.  Every other shape, and AMDR_HYBRID_BATCH=0, runs the two calls inside.  Only
+ * enqueues; the side stream and its events are made by amdr_dense_create / amdr_dense_reserve, and after
+ * amdr_dense_reserve + amdr_bm25_reserve the call allocates nothing (capturable).  One call at a time per pair of handles. */
+int amdr_hybrid_batch_device(amdr_dense_t* dense, amdr_bm25_t* bm25, const float* Q_dev, const int32_t* q_terms_dev,
+                             const int64_t* q_ptr_dev, int32_t nq, int32_t kd, int32_t kb, const amdr_fuse_params_t* p,
+                             const int64_t* dense_row2uid, const int64_t* bm25_row2uid, float* dense_scores_dev,
+                             int64_t* dense_ids_dev, double* bm25_scores_dev, int64_t* bm25_ids_dev, int64_t* out_ids,
+                             double* out_vals, int32_t* out_mask, int32_t* out_count, void* stream);
+
 /* The first pass of the two-pass form of the long-batch dense channel on a short corpus (search_dense over a batch,
  * hybrid_retriever.py:181-189) — what amdr_dense_search_device / amdr_dense_search_fuse_device run inside from 4 096
  * queries per launch on <= 1 024 rows with d a multiple of 128 and k <= 12 (AMDR_DENSE_SMALL_HI=0: the

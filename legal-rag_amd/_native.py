@@ -34,7 +34,7 @@ SIGNATURES = {
     "amdr_last_error": "", "amdr_version": "", "amdr_device_count": "P", "amdr_device_name": "iPi", "amdr_workspace_growths": "P",
     "amdr_dense_create": "PliiP", "amdr_dense_create_from_device": "PliiP", "amdr_dense_add": "PPl", "amdr_dense_remove": "PPl", "amdr_dense_remove_kernel_ms": "PP", "amdr_dense_replace": "PPPl", "amdr_dense_replace_kernel_ms": "PP",
     "amdr_dense_ntotal": "PP", "amdr_dense_dim": "PP", "amdr_dense_reserve": "Pii", "amdr_dense_search": "PPiiPP",
-    "amdr_dense_search_device": "PPiiPPP", "amdr_dense_search_fuse_device": "PPiiPPPPiPPPPPPPP", "amdr_hybrid_small_device": "PPPPPiiiPPPPPPPPPPPP", "amdr_dense_small_create": "PP", "amdr_dense_small_approx_device": "PPiPlPP", "amdr_dense_small_destroy": "P", "amdr_dense_two_pass_fallbacks": "PP", "amdr_dense_read_rows": "PllP", "amdr_dense_score_rows": "PPiPiP",
+    "amdr_dense_search_device": "PPiiPPP", "amdr_dense_search_fuse_device": "PPiiPPPPiPPPPPPPP", "amdr_hybrid_small_device": "PPPPPiiiPPPPPPPPPPPP", "amdr_hybrid_batch_device": "PPPPPiiiPPPPPPPPPPPP", "amdr_dense_small_create": "PP", "amdr_dense_small_approx_device": "PPiPlPP", "amdr_dense_small_destroy": "P", "amdr_dense_two_pass_fallbacks": "PP", "amdr_dense_read_rows": "PllP", "amdr_dense_score_rows": "PPiPiP",
     "amdr_dense_plan_info": "PiiPi", "amdr_dense_workspace_plan": "liiiiiP", "amdr_dense_hi_counters": "PP", "amdr_dense_image_build": "P", "amdr_dense_image_drop": "P", "amdr_dense_image_info": "PP", "amdr_dense_profile_begin": "Pi", "amdr_dense_profile_end": "PPP", "amdr_dense_destroy": "P",
     "amdr_bm25_create": "PPPPPlldddiP", "amdr_bm25_ndocs": "PP", "amdr_bm25_add": "PPPPPPlld", "amdr_bm25_info": "PP", "amdr_bm25_add_kernel_ms": "PP", "amdr_bm25_remove": "PPlPlPd", "amdr_bm25_remove_kernel_ms": "PP", "amdr_bm25_replace": "PPlPPPPPlPd", "amdr_bm25_replace_kernel_ms": "PP", "amdr_bm25_replaces": "PP", "amdr_bm25_read": "PPPPPPP", "amdr_bm25_set_tokens": "PPP", "amdr_bm25_tokens_info": "PP", "amdr_bm25_read_tokens": "PPP", "amdr_bm25_reserve": "Piil", "amdr_bm25_workspace_plan": "liiiiP", "amdr_bm25_plan_info": "PiiPi",
     "amdr_bm25_search": "PPPiiPP", "amdr_bm25_search_device": "PPPiiPPP", "amdr_bm25_scores": "PPPiP",
@@ -1410,6 +1410,19 @@ def hybrid_small_device(plan, params: "FuseParams", q_emb: int, q_terms: int, q_
     rc = fn(dh, bh, q_emb, q_terms, q_ptr, nq, kd, kb, C.byref(params), m0, m1, ds, di, bs, bi, oi, ov, om, oc, stream)
     if rc:
         _check(rc, "amdr_hybrid_small_device")
+
+
+def hybrid_batch_device(dense: "DenseIndex", bm25: "BM25Index", params: "FuseParams", q_emb: int, q_terms: int, q_ptr: int,
+                        nq: int, kd: int, kb: int, dense_row2uid: int, bm25_row2uid: int, dense_scores: int, dense_ids: int,
+                        bm25_scores: int, bm25_ids: int, out_ids: int, out_vals: int, out_mask: int, out_count: int,
+                        stream: int = 0) -> None:
+    """The long-batch hybrid step as one native call (amdr_hybrid_batch_device): bm25.search_device +
+    dense.search_fuse_device, the same five outputs bit for bit; where the two-pass dense form applies BM25 runs on the
+    dense handle's side stream beside the second dense pass (AMDR_HYBRID_BATCH=0: the serial calls)."""
+    _check(load().amdr_hybrid_batch_device(
+        dense._h, bm25._h, _vp(q_emb), _vp(q_terms), _vp(q_ptr), C.c_int32(nq), C.c_int32(kd), C.c_int32(kb), C.byref(params),
+        _vp(dense_row2uid), _vp(bm25_row2uid), _vp(dense_scores), _vp(dense_ids), _vp(bm25_scores), _vp(bm25_ids),
+        _vp(out_ids), _vp(out_vals), _vp(out_mask), _vp(out_count), _vp(stream)), "amdr_hybrid_batch_device")
 
 
 def fuse_compact_device(nq: int, max_out: int, w: int, ids: int, vals: int, mask: int, count: int, out_rows: int,

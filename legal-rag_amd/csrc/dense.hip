@@ -153,6 +153,7 @@ __global__ __launch_bounds__(256) void dense_all_scores_kernel(const float* __re
 
 using namespace amdr;
 
+constexpr int kSideEvents = 2;  // fork, join
 struct amdr_dense {
   int device = 0;
   int64_t n = 0;
@@ -202,6 +203,10 @@ struct amdr_dense {
   std::vector<hipEvent_t> prof_ev;
   int prof_used = 0;
   bool prof_on = false;
+  // the overlapped long-batch hybrid step (amdr_hybrid_batch_device): one non-blocking side stream and the events of
+  // its fork from / join to the caller's stream (timing disabled), made by create / reserve — a call only enqueues
+  hipStream_t side = nullptr;
+  hipEvent_t side_ev[kSideEvents] = {};
 };
 
 namespace {
@@ -885,6 +890,14 @@ int update_stats(amdr_dense* h, int64_t row0, int64_t rows) {
   return AMDR_OK;
 }
 
+// The side stream and the events of the overlapped hybrid batch step; whatever exists already is kept.
+int side_init(amdr_dense* h) {
+  if (!h->side) AMDR_HIP(hipStreamCreateWithFlags(&h->side, hipStreamNonBlocking));
+  for (hipEvent_t& e : h->side_ev)
+    if (!e) AMDR_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  return AMDR_OK;
+}
+
 // Rows were removed or replaced, so the statistics are about to be taken again from zero (the largest component and row
 // norm can fall): the short-corpus fp16 image is of the old matrix and is made again on demand; what the fp16 first pass
 // learnt starts over, as in amdr_dense_add — and since the statistics words are made again from zero, the device's
@@ -936,6 +949,57 @@ int image_sync(amdr_dense* h, int64_t row0) {
   h->img_rows = h->n;
   h->img_scale = h->fp16.x_scale;
   return AMDR_OK;
+}
+
+// ---- the long-batch hybrid step with BM25 beside the second dense pass (amdr_hybrid_batch_device) --------
+// AMDR_HYBRID_BATCH=0 pins the serial calls (tests, A/B)
+bool hybrid_batch_on() {
+  const char* e = getenv("AMDR_HYBRID_BATCH");
+  return !(e && e[0] == '0');
+}
+
+struct HybridBatch {  // the call's operands and channel lists (device pointers)
+  amdr_bm25_t* bm25;
+  const float* Q;
+  const int32_t* q_terms;
+  const int64_t* q_ptr;
+  int nq, kd, kb;
+  float* ds;
+  int64_t* di;
+  double* bs;
+  int64_t* bi;
+};
+
+// The overlapped step applies to this call: the two-pass dense form as ONE pass, its buffers ready.  p: the pass's plan.
+bool hybrid_batch_applies(amdr_dense* h, const DensePins& pins, const HybridBatch& a, const FuseTail& tail, hipStream_t st,
+                          Route* r, DenseMfmaPlan* p) {
+  if (!hybrid_batch_on() || !h->side || bm25_device_of(a.bm25) != h->device) return false;
+  *r = dense_route(h, pins, a.nq, a.kd);
+  if (r->form != Form::Batched || a.nq > r->chunk) return false;
+  dense_mfma_plan((long)h->n, h->d, a.nq, a.kd, p);
+  return batched_pass_form(h, pins, *r, *p, a.nq, a.kd, &tail).small_hi && small_hi_ready(h, a.nq, st);
+}
+
+// Split and scores on the caller's stream; behind the scores kernel the fork: BM25 on the side stream beside the second
+// dense pass (dense_hi_select_fuse_kernel<false>: the dense lists alone) on the caller's; behind the join the plain
+// fusion.  Released any earlier, BM25 takes the block slots first and the split and the scores kernel wait for them.
+int hybrid_batch_overlapped(amdr_dense* h, const HybridBatch& a, const FuseTail& tail, const DenseMfmaPlan& p, hipStream_t st) {
+  float* S = h->smat[0].as<float>();
+  float* eps = h->small_eps.as<float>();
+  int rc = profiled(h, st, [&] { return amdr_dense_small_approx_device(h->small, a.Q, a.nq, S, p.ld, eps, st); });
+  if (rc) return rc;
+  AMDR_HIP(hipEventRecord(h->side_ev[0], st));
+  AMDR_HIP(hipStreamWaitEvent(h->side, h->side_ev[0], 0));
+  // from here on the branch is open: it is joined whatever happens (a capture must not end with it dangling)
+  rc = amdr_bm25_search_device(a.bm25, a.q_terms, a.q_ptr, a.nq, a.kb, a.bs, a.bi, h->side);
+  if (!rc)
+    rc = dense_hi_select_launch(nullptr, 0, S, p.ld, (long)h->n, a.nq, a.kd, h->X, a.Q, h->d, eps, a.ds, a.di,
+                                h->small_fb.as<unsigned int>(), st);
+  hipError_t e = hipEventRecord(h->side_ev[1], h->side);
+  if (e == hipSuccess) e = hipStreamWaitEvent(st, h->side_ev[1], 0);
+  if (rc) return rc;
+  AMDR_HIP(e);
+  return dense_fuse_plain_launch(tail, 0, a.nq, a.kd, a.ds, a.di, st);
 }
 
 }  // namespace
@@ -992,7 +1056,7 @@ int amdr_dense_create(const float* X_host, int64_t n, int32_t d, int32_t device,
     amdr_dense_destroy(h);
     return fail(e == hipErrorOutOfMemory ? AMDR_ENOMEM : AMDR_EHIP, "dense_create: %s", hipGetErrorString(e));
   }
-  if ((rc = update_stats(h, 0, n))) {
+  if ((rc = update_stats(h, 0, n)) || (rc = side_init(h))) {
     amdr_dense_destroy(h);
     return rc;
   }
@@ -1026,7 +1090,7 @@ int amdr_dense_create_from_device(const float* X_dev, int64_t n, int32_t d, int3
   // have finished first, or the largest component / row norm — the fp16 first pass's error bound — would be taken from
   // a half-written matrix.  Creation is synchronous anyway: wait for the device.
   AMDR_HIP(hipDeviceSynchronize());
-  if ((rc = update_stats(h, 0, n))) {  // the wrapped matrix must not change while the handle lives
+  if ((rc = update_stats(h, 0, n)) || (rc = side_init(h))) {  // the wrapped matrix must not change while the handle lives
     amdr_dense_destroy(h);
     return rc;
   }
@@ -1257,6 +1321,7 @@ int amdr_dense_reserve(amdr_dense_t* h, int32_t nq_max, int32_t k_max) {
   const DensePins pins = read_pins();
   int rc = ensure_need(h, 0, reserve_need(h, pins, nq_max, k_max));
   if (rc) return rc;
+  if ((rc = side_init(h))) return rc;
   if ((rc = h->qbuf.ensure((size_t)nq_max * h->d * sizeof(float)))) return rc;
   if ((rc = h->sbuf.ensure((size_t)nq_max * k_max * sizeof(float)))) return rc;
   if (small_hi_shape(h, pins, nq_max, k_max < 12 ? k_max : 12, 0))  // (so that a later capture finds the two-pass form's buffers)
@@ -1290,6 +1355,38 @@ int amdr_dense_search_fuse_device(amdr_dense_t* h, const float* Q_dev, int32_t n
   AMDR_HIP(hipSetDevice(h->device));
   FuseTail tail{p, dense_row2uid, bm25_ids, bm25_scores, kb, bm25_row2uid, out_ids, out_vals, out_mask, out_count};
   return run_search(h, 0, Q_dev, nq, k, dense_scores_dev, dense_ids_dev, (hipStream_t)stream, &tail);
+}
+
+int amdr_hybrid_batch_device(amdr_dense_t* h, amdr_bm25_t* bm25, const float* Q_dev, const int32_t* q_terms_dev,
+                             const int64_t* q_ptr_dev, int32_t nq, int32_t kd, int32_t kb, const amdr_fuse_params_t* p,
+                             const int64_t* dense_row2uid, const int64_t* bm25_row2uid, float* dense_scores_dev,
+                             int64_t* dense_ids_dev, double* bm25_scores_dev, int64_t* bm25_ids_dev, int64_t* out_ids,
+                             double* out_vals, int32_t* out_mask, int32_t* out_count, void* stream) {
+  AMDR_REQUIRE(h && bm25, "hybrid_batch: null index handle");
+  AMDR_REQUIRE(p != nullptr, "hybrid_batch: null params");
+  AMDR_REQUIRE(p->method >= 0 && p->method <= AMDR_FUSE_WEIGHTED_SUM, "hybrid_batch: method=%d", p->method);
+  AMDR_REQUIRE(nq >= 0 && kd >= 1 && kd <= AMDR_MAX_K && kb >= 1 && kb <= AMDR_MAX_K, "hybrid_batch: bad sizes");
+  if (nq == 0) return AMDR_OK;
+  AMDR_REQUIRE(Q_dev && q_ptr_dev, "hybrid_batch: null query buffers");
+  AMDR_REQUIRE(dense_scores_dev && dense_ids_dev && bm25_scores_dev && bm25_ids_dev, "hybrid_batch: null channel lists");
+  AMDR_REQUIRE(out_ids && out_vals && out_mask && out_count, "hybrid_batch: null output");
+  int rc;
+  {
+    std::lock_guard<std::mutex> g(h->mu);
+    AMDR_HIP(hipSetDevice(h->device));
+    const DensePins pins = read_pins();
+    const HybridBatch a{bm25, Q_dev, q_terms_dev, q_ptr_dev, nq, kd, kb, dense_scores_dev, dense_ids_dev, bm25_scores_dev, bm25_ids_dev};
+    const FuseTail tail{p, dense_row2uid, bm25_ids_dev, bm25_scores_dev, kb, bm25_row2uid, out_ids, out_vals, out_mask, out_count};
+    Route r;
+    DenseMfmaPlan plan;
+    if (hybrid_batch_applies(h, pins, a, tail, (hipStream_t)stream, &r, &plan)) {
+      if ((rc = ensure_need(h, 0, call_need(h, r, nq, kd)))) return rc;
+      return hybrid_batch_overlapped(h, a, tail, plan, (hipStream_t)stream);
+    }
+  }
+  if ((rc = amdr_bm25_search_device(bm25, q_terms_dev, q_ptr_dev, nq, kb, bm25_scores_dev, bm25_ids_dev, stream))) return rc;
+  return amdr_dense_search_fuse_device(h, Q_dev, nq, kd, p, dense_row2uid, bm25_ids_dev, bm25_scores_dev, kb, bm25_row2uid,
+                                       dense_scores_dev, dense_ids_dev, out_ids, out_vals, out_mask, out_count, stream);
 }
 
 int amdr_dense_search(amdr_dense_t* h, const float* Q_host, int32_t nq, int32_t k, float* scores_host,
@@ -1399,8 +1496,9 @@ int amdr_dense_plan_info(const amdr_dense_t* h, int32_t nq, int32_t k, char* buf
       snprintf(buf, buf_len,
                "dsh_scores_kernel fp16 first pass queries_per_launch=%d (dsh_split_queries_kernel + v_mfma_f32_32x32x16_f16 on "
                "fp16 roundings of both operands, proven per-query bound) + dense_hi_select_fuse_kernel (rows inside 2 eps of the "
-               "k-th best re-scored exactly, top-k, fusion); exact form: dense_panel_scores_kernel",
-               m);
+               "k-th best re-scored exactly, top-k, fusion); exact form: dense_panel_scores_kernel; amdr_hybrid_batch_device: %s",
+               m, hybrid_batch_on() ? "BM25 on a side stream beside the second dense pass, then fuse_packed_kernel"
+                                    : "the serial calls (AMDR_HYBRID_BATCH=0)");
     } else if (f.scores == PassForm::RowWaves) {
       snprintf(buf, buf_len, "dense_all_scores_kernel (one wave per query x row) + %s", tail);
     } else if (f.scores == PassForm::Panel) {
@@ -1493,6 +1591,12 @@ int amdr_dense_destroy(amdr_dense_t* h) {
     (void)hipStreamSynchronize(h->stream);
     (void)hipStreamDestroy(h->stream);
   }
+  if (h->side) {
+    (void)hipStreamSynchronize(h->side);
+    (void)hipStreamDestroy(h->side);
+  }
+  for (hipEvent_t e : h->side_ev)
+    if (e) (void)hipEventDestroy(e);
   if (h->owns && h->X) (void)hipFree(h->X);
   image_drop(h);
   for (int w = 0; w < 2; ++w) {

@@ -44,7 +44,7 @@ def packed_views(h: np.ndarray, nq: int, w: int, nvals: int = NV):
 
 # The forms of one hybrid step (step_form):
 ONE_LAUNCH = "one_launch"            # both channels and the fusion in one launch (_hybrid_small)
-BM25_THEN_FUSED = "bm25_then_fused"  # BM25, then the dense channel and the fusion as one native call
+BM25_THEN_FUSED = "bm25_then_fused"  # BM25, the dense channel and the fusion as one native call (amdr_hybrid_batch_device)
 CHANNELS = "channels"                # the channels one after the other on the caller's stream, then the fusion
 CHANNELS_SIDE = "channels_side"      # dense / BM25 on the side stream beside MaxSim, then the fusion
 SCOPED = "scoped"                    # every channel ranks each query's own rows (search_batch(scopes=)), then the fusion
@@ -535,6 +535,25 @@ class HybridEngine:
                                       vals.data_ptr(), mask.data_ptr(), count.data_ptr(), _stream())
         return (s, i), BatchResult(ids=ids, vals=vals, mask=mask, count=count, packed=pk)
 
+    def hybrid_batch(self, params: _native.FuseParams, q_emb: torch.Tensor, q_terms: torch.Tensor, q_ptr: torch.Tensor, k: int):
+        """bm25_topk + dense_topk_fuse as ONE native call (amdr_hybrid_batch_device: on a long batch the BM25 kernel runs
+        on a side stream beside the second dense pass, forked and joined inside the call): (dense lists, BM25 lists, result)."""
+        nq = int(q_emb.shape[0])
+        _check_emb(q_emb)
+        _check_csr(q_terms, q_ptr)
+        assert q_ptr.shape[0] - 1 == nq
+        ds = self._buf("ds", (nq, k), torch.float32)
+        di = self._buf("di", (nq, k), torch.int64)
+        bs = self._buf("bs", (nq, k), torch.float64)
+        bi = self._buf("bi", (nq, k), torch.int64)
+        pk, ids, vals, mask, count = self._fused_outputs(nq, 2 * k)
+        m0, m1 = self.maps[0], self.maps[1]
+        _native.hybrid_batch_device(self.dense, self.bm25, params, q_emb.data_ptr(), q_terms.data_ptr(), q_ptr.data_ptr(),
+                                    nq, k, k, m0.data_ptr() if m0 is not None else 0, m1.data_ptr() if m1 is not None else 0,
+                                    ds.data_ptr(), di.data_ptr(), bs.data_ptr(), bi.data_ptr(), ids.data_ptr(),
+                                    vals.data_ptr(), mask.data_ptr(), count.data_ptr(), _stream())
+        return (ds, di), (bs, bi), BatchResult(ids=ids, vals=vals, mask=mask, count=count, packed=pk)
+
     def _hybrid_small(self, params: _native.FuseParams, q_emb: torch.Tensor, q_terms: torch.Tensor, q_ptr: torch.Tensor,
                       k: int):
         """bm25_topk + dense_topk_fuse through amdr_hybrid_small_device (one launch on a serving corpus): (dense lists,
@@ -672,8 +691,7 @@ class HybridEngine:
         elif form == ONE_LAUNCH:  # the serving call (search(): one query at a time)
             d, b, res = self._hybrid_small(params, q_emb, q_terms, q_ptr, k)
         elif form == BM25_THEN_FUSED:
-            b = self.bm25_topk(q_terms, q_ptr, k)
-            d, res = self.dense_topk_fuse(params, q_emb, k, b)
+            d, b, res = self.hybrid_batch(params, q_emb, q_terms, q_ptr, k)
         else:
             side = None
             if form == CHANNELS_SIDE:
