@@ -1,25 +1,14 @@
 // The BM25 handle, shared by bm25.hip (create, plan, score, search, destroy), bm25_update.hip (add, remove, info, read),
-// term_scope.hip (term constraints) and phrase_scope.hip (the token stream, phrases).
+// term_scope.hip (term constraints) and phrase_scope.hip (the token stream, phrases).  The per-call plumbing of the updates
+// (dev_alloc, CallScratch, KernelSpans, AMDR_TRY) is call_scratch.hpp's, shared with the other two channels.
 #pragma once
+#include "call_scratch.hpp"
 #include "common.hpp"
 
 #include <mutex>
 #include <utility>
 
 namespace amdr {
-
-// count elements of T on the device (count may be 0); a failure names the entry point `who`
-template <class T>
-int bm_dev_alloc(T** dst, size_t count, const char* who) {
-  *dst = nullptr;
-  const size_t bytes = count * sizeof(T);
-  if (hipMalloc((void**)dst, bytes) != hipSuccess) {
-    (void)hipGetLastError();
-    *dst = nullptr;
-    return fail(AMDR_ENOMEM, "%s: device allocation of %zu B failed", who, bytes);
-  }
-  return AMDR_OK;
-}
 
 // The resident index: term-major CSR postings, the per-posting factors, idf and the document lengths.  Every array
 // carries ONE padding element behind its `count` values — the scoring kernel's clamped prefetch may touch [count] — and
@@ -36,7 +25,7 @@ struct BmIndex {
 
   template <class T>
   static int alloc(T** dst, size_t count, const char* who) {
-    return bm_dev_alloc(dst, count + 1, who);
+    return dev_alloc(dst, count + 1, who);
   }
   // the tables of n_terms terms and n_docs documents; the postings, once their number is known
   int alloc_tables(int64_t V, int64_t n, double avg, const char* who) {

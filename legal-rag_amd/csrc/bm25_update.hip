@@ -302,78 +302,6 @@ __global__ __launch_bounds__(kBmTileThreads) void bm25_rp_scatter_add_kernel(
   }
 }
 
-// ---- host: per-call scratch and the kernel timer ---------------------------------------------------------------------
-// Typed device arrays that live for one call: freed on return.  (Not DevBuf: a call's scratch is no workspace growth.)
-struct BmScratch {
-  void* held[16] = {};
-  int n = 0;
-  BmScratch() = default;
-  BmScratch(const BmScratch&) = delete;
-  BmScratch& operator=(const BmScratch&) = delete;
-  ~BmScratch() {
-    for (int i = 0; i < n; ++i) (void)hipFree(held[i]);
-  }
-  template <class T>
-  int alloc(T** p, size_t count, const char* who) {
-    *p = nullptr;
-    if (n == (int)(sizeof(held) / sizeof(held[0]))) return fail(AMDR_EINVAL, "%s: too many scratch arrays", who);
-    const int rc = bm_dev_alloc(p, count, who);
-    if (!rc && *p) held[n++] = (void*)*p;
-    return rc;
-  }
-};
-
-// Device time of up to two stretches of a stream between events.  Events that cannot be made only lose the time: the
-// spans then record nothing and ms() is -1.
-struct BmSpans {
-  hipEvent_t ev[4] = {};
-  int spans, recorded = 0;
-  bool ok = true;
-  explicit BmSpans(int spans_) : spans(spans_) {
-    for (int i = 0; i < 2 * spans && ok; ++i)
-      if (hipEventCreate(&ev[i]) != hipSuccess) {
-        (void)hipGetLastError();
-        ev[i] = nullptr;
-        ok = false;
-      }
-  }
-  BmSpans(const BmSpans&) = delete;
-  BmSpans& operator=(const BmSpans&) = delete;
-  ~BmSpans() {
-    for (hipEvent_t e : ev)
-      if (e) (void)hipEventDestroy(e);
-  }
-  int begin(int i, hipStream_t st) {
-    if (ok) AMDR_HIP(hipEventRecord(ev[2 * i], st));
-    return AMDR_OK;
-  }
-  int end(int i, hipStream_t st) {
-    if (ok) AMDR_HIP(hipEventRecord(ev[2 * i + 1], st));
-    ++recorded;
-    return AMDR_OK;
-  }
-  // the summed milliseconds of the recorded spans, once the stream has finished; exactly -1.0 when there is no time
-  double ms() const {
-    if (!ok || recorded == 0) return -1.0;
-    double sum = 0;
-    for (int i = 0; i < recorded; ++i) {
-      float t = 0.f;
-      if (hipEventElapsedTime(&t, ev[2 * i], ev[2 * i + 1]) != hipSuccess) {
-        (void)hipGetLastError();
-        return -1.0;
-      }
-      sum += (double)t;
-    }
-    return sum;
-  }
-};
-
-#define AMDR_TRY(expr)         \
-  do {                         \
-    const int _rc = (expr);    \
-    if (_rc) return _rc;       \
-  } while (0)
-
 }  // namespace
 
 extern "C" {
@@ -395,7 +323,7 @@ int amdr_bm25_add(amdr_bm25_t* h, const int64_t* term_ptr_add, const int32_t* po
   AMDR_TRY(nx.alloc_tables(n_terms, old.n_docs + n_add, avgdl, who));
   AMDR_TRY(nx.alloc_postings(nnz_new, who));
   // the add's own CSR on the device (never an empty allocation)
-  BmScratch tmp;
+  CallScratch tmp;
   long long* add_ptr;
   int *add_doc, *add_tf;
   AMDR_TRY(tmp.alloc(&add_ptr, (size_t)n_terms + 1, who));
@@ -413,7 +341,7 @@ int amdr_bm25_add(amdr_bm25_t* h, const int64_t* term_ptr_add, const int32_t* po
   hipLaunchKernelGGL(bm25_term_ptr_sum_kernel, dim3((unsigned)((n_terms + 1 + 255) / 256)), dim3(256), 0, st, old.term_ptr,
                      (long)old.n_terms, add_ptr, (long)n_terms, nx.term_ptr);
   AMDR_HIP(hipGetLastError());
-  BmSpans timer(1);  // the merge kernel (amdr_bm25_add_kernel_ms)
+  KernelSpans timer(1);  // the merge kernel (amdr_bm25_add_kernel_ms)
   if (nnz_new > 0) {
     const long long blocks = (nnz_new + kBmTile - 1) / kBmTile;
     AMDR_REQUIRE(blocks < (1ll << 31), "bm25_add: %lld postings exceed the merge grid", (long long)nnz_new);
@@ -448,7 +376,7 @@ int amdr_bm25_remove(amdr_bm25_t* h, const int64_t* remove_ids, int64_t n_remove
   AMDR_REQUIRE(tiles < (1ll << 31), "bm25_remove: %lld postings exceed the grid", (long long)nnz_old);
   BmStagedIndex nx;
   AMDR_TRY(nx.alloc_tables(V_new, n_old - n_remove, avgdl, who));
-  BmScratch tmp;
+  CallScratch tmp;
   long long *rm_ids, *tile_cnt, *tile_base, *rank_at, *df_new;
   int *doc_new, *map_dev = nullptr, *flag_dev;
   unsigned short* tile_rank;
@@ -467,7 +395,7 @@ int amdr_bm25_remove(amdr_bm25_t* h, const int64_t* remove_ids, int64_t n_remove
   if (V_new) AMDR_HIP(hipMemcpyAsync(nx.idf, idf, (size_t)V_new * sizeof(double), hipMemcpyHostToDevice, st));
   AMDR_HIP(hipMemsetAsync(flag_dev, 0, sizeof(int), st));
   // the passes in two stretches, with the host's look at nnz_new between them (amdr_bm25_remove_kernel_ms)
-  BmSpans timer(2);
+  KernelSpans timer(2);
   AMDR_TRY(timer.begin(0, st));
   hipLaunchKernelGGL(bm25_rm_docmap_kernel, dim3((unsigned)((n_old + 255) / 256)), dim3(256), 0, st, rm_ids, (long)n_remove,
                      old.doc_len, (long)n_old, doc_new, nx.doc_len);
@@ -530,7 +458,7 @@ int amdr_bm25_replace(amdr_bm25_t* h, const int64_t* replace_ids, int64_t n_rep,
                (long long)nnz_old, (long long)nnz_add);
   BmStagedIndex nx;
   AMDR_TRY(nx.alloc_tables(V_new, n, avgdl, who));
-  BmScratch tmp;
+  CallScratch tmp;
   long long *rp_ids, *tile_cnt, *tile_base, *rank_at, *df_new, *add_ptr;
   int *doc_keep, *map_dev = nullptr, *inv_dev, *flag_dev, *add_doc, *add_tf, *add_len;
   unsigned short* tile_rank;
@@ -563,7 +491,7 @@ int amdr_bm25_replace(amdr_bm25_t* h, const int64_t* replace_ids, int64_t n_rep,
   }
   AMDR_HIP(hipMemsetAsync(flag_dev, 0, sizeof(int), st));
   // the passes in two stretches, with the host's look at nnz_new between them (amdr_bm25_replace_kernel_ms)
-  BmSpans timer(2);
+  KernelSpans timer(2);
   AMDR_TRY(timer.begin(0, st));
   hipLaunchKernelGGL(bm25_rp_docmap_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, rp_ids, (long)n_rep,
                      old.doc_len, add_len, (long)n, doc_keep, nx.doc_len);

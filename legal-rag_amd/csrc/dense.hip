@@ -9,6 +9,7 @@
 // LDS (topk.hpp), one list per block is written out and a second small kernel
 // merges the per-block lists.  HBM-bound by construction: algorithmic bytes
 // = n*d*4 per pass, flops = 2*n*d*NQ.
+#include "call_scratch.hpp"
 #include "common.hpp"
 #include "dense_dot.hpp"
 #include "dense_fp16.hpp"
@@ -898,11 +899,23 @@ int side_init(amdr_dense* h) {
   return AMDR_OK;
 }
 
-// Rows were removed or replaced, so the statistics are about to be taken again from zero (the largest component and row
-// norm can fall): the short-corpus fp16 image is of the old matrix and is made again on demand; what the fp16 first pass
-// learnt starts over, as in amdr_dense_add — and since the statistics words are made again from zero, the device's
-// counters and the host's view of them start from zero too.
-void first_pass_start_over(amdr_dense* h) {
+// A matrix in the making beside the live one (a growing amdr_dense_add, amdr_dense_remove).  commit() exchanges the two, so
+// the destructor frees the OLD matrix after a commit and the new one after a failure — a failed update leaves the matrix it
+// had.  (hipFree waits for the device: host-pointer searches are behind h->mu, "_device" work is the caller's to order.)
+struct DenseStagedMatrix {
+  float* X = nullptr;
+  DenseStagedMatrix() = default;
+  DenseStagedMatrix(const DenseStagedMatrix&) = delete;
+  ~DenseStagedMatrix() { (void)hipFree(X); }
+  void commit(amdr_dense* h, int64_t cap_rows) {
+    std::swap(h->X, X);
+    h->cap_rows = cap_rows;
+  }
+};
+
+// The matrix changed (every update): the short-corpus fp16 image is of the old one (and may point at freed memory) and is
+// made again on demand; what the fp16 first pass learnt about the matrix (width level, given up) starts over.
+void first_pass_forget(amdr_dense* h) {
   if (h->small) {
     (void)hipDeviceSynchronize();
     (void)amdr_dense_small_destroy(h->small);
@@ -911,6 +924,13 @@ void first_pass_start_over(amdr_dense* h) {
   h->small_failed = false;
   h->hi_level = 0;
   h->hi_off = false;
+}
+
+// Rows were removed or replaced, so the statistics are about to be taken again from zero (the largest component and row
+// norm can fall): first_pass_forget, as in amdr_dense_add — and since the statistics words are made again from zero, the
+// device's counters and the host's view of them start from zero too.
+void first_pass_start_over(amdr_dense* h) {
+  first_pass_forget(h);
   if (h->hi_copy_pending) {
     (void)hipEventSynchronize(h->hi_ev);
     h->hi_copy_pending = false;
@@ -1098,35 +1118,33 @@ int amdr_dense_create_from_device(const float* X_dev, int64_t n, int32_t d, int3
   return AMDR_OK;
 }
 
+// Append rows.  Where the matrix has room the new rows land behind its end, which no search reads; where it has none, a
+// grown matrix (double, or to fit) is staged and takes the old one's place only once both copies have arrived.
 int amdr_dense_add(amdr_dense_t* h, const float* X_host, int64_t n_add) {
+  static const char* const who = "dense_add";
   AMDR_REQUIRE(h != nullptr, "dense_add: null handle");
   AMDR_REQUIRE(h->owns, "dense_add: handle wraps caller-owned memory");
   AMDR_REQUIRE(n_add >= 0 && (n_add == 0 || X_host), "dense_add: bad arguments");
-  AMDR_REQUIRE(h->n + n_add < (1ll << 32), "dense_add: too many rows");
   std::lock_guard<std::mutex> g(h->mu);
+  AMDR_REQUIRE(h->n + n_add < (1ll << 32), "dense_add: too many rows");
   AMDR_HIP(hipSetDevice(h->device));
   if (n_add == 0) return AMDR_OK;
-  if (h->n + n_add > h->cap_rows) {
-    int64_t ncap = h->cap_rows * 2 > h->n + n_add ? h->cap_rows * 2 : h->n + n_add;
-    float* nx = nullptr;
-    AMDR_HIP(hipMalloc((void**)&nx, (size_t)ncap * h->d * sizeof(float)));
-    if (h->n > 0) AMDR_HIP(hipMemcpy(nx, h->X, (size_t)h->n * h->d * sizeof(float), hipMemcpyDeviceToDevice));
-    if (h->X) (void)hipFree(h->X);
-    h->X = nx;
-    h->cap_rows = ncap;
+  const int64_t row0 = h->n, n_new = row0 + n_add;
+  {
+    DenseStagedMatrix grown;
+    float* X = h->X;
+    int64_t cap = h->cap_rows;
+    if (n_new > cap) {
+      cap = cap * 2 > n_new ? cap * 2 : n_new;
+      AMDR_TRY(dev_alloc(&grown.X, (size_t)cap * h->d, who));
+      X = grown.X;
+      if (row0 > 0) AMDR_HIP(hipMemcpy(X, h->X, (size_t)row0 * h->d * sizeof(float), hipMemcpyDeviceToDevice));
+    }
+    AMDR_HIP(hipMemcpy(X + (size_t)row0 * h->d, X_host, (size_t)n_add * h->d * sizeof(float), hipMemcpyHostToDevice));
+    if (grown.X) grown.commit(h, cap);
   }
-  AMDR_HIP(hipMemcpy(h->X + (size_t)h->n * h->d, X_host, (size_t)n_add * h->d * sizeof(float), hipMemcpyHostToDevice));
-  const int64_t row0 = h->n;
-  h->n += n_add;
-  if (h->small) {  // the short-corpus fp16 image is of the old matrix (and may point at freed memory): made again on demand
-    (void)hipDeviceSynchronize();
-    (void)amdr_dense_small_destroy(h->small);
-    h->small = nullptr;
-  }
-  h->small_failed = false;
-  // the matrix changed: what the fp16 first pass learnt about it (width level, given up) starts over
-  h->hi_level = 0;
-  h->hi_off = false;
+  h->n = n_new;
+  first_pass_forget(h);
   if (h->hi_copy_pending && hipEventSynchronize(h->hi_ev) == hipSuccess) {
     h->hi_copy_pending = false;
     for (int i = 0; i < 3; ++i) h->hi_seen[i] = h->hi_host[i];
@@ -1145,9 +1163,10 @@ int amdr_dense_add(amdr_dense_t* h, const float* X_host, int64_t n_add) {
 }
 
 // Remove rows.  Everything that can run out of memory or be refused — the device copy of the list, the new matrix, the
-// compaction kernel (rows_compact.hip) — happens beside the old matrix; the handle's fields change only after the device
-// has finished.  Then what create() does on the new matrix: the statistics from zero, and a present image made again.
+// compaction kernel (rows_compact.hip) — happens beside the old matrix; the staged matrix takes its place only after the
+// device has finished.  Then what create() does on the new matrix: the statistics from zero, and a present image made again.
 int amdr_dense_remove(amdr_dense_t* h, const int64_t* remove_ids, int64_t n_remove) {
+  static const char* const who = "dense_remove";
   AMDR_REQUIRE(h != nullptr, "dense_remove: null handle");
   AMDR_REQUIRE(h->owns, "dense_remove: handle wraps caller-owned memory");
   AMDR_REQUIRE(n_remove >= 0, "dense_remove: n_remove=%lld", (long long)n_remove);
@@ -1157,40 +1176,27 @@ int amdr_dense_remove(amdr_dense_t* h, const int64_t* remove_ids, int64_t n_remo
   AMDR_REQUIRE(bad == kRcOk, "dense_remove: %s", rc_error_text(bad));
   AMDR_HIP(hipSetDevice(h->device));
   const int64_t n_new = h->n - n_remove;
-  float* nx = nullptr;
-  long long* rm = nullptr;
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  float ms = 0.f;
-  int rc = AMDR_OK;
-  hipError_t e = hipSuccess;
-  if (n_new > 0) {
-    e = hipMalloc((void**)&rm, (size_t)n_remove * sizeof(long long));
-    if (e == hipSuccess) e = hipMalloc((void**)&nx, (size_t)n_new * h->d * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpyAsync(rm, remove_ids, (size_t)n_remove * sizeof(long long), hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess) e = hipEventCreate(&ev[0]);
-    if (e == hipSuccess) e = hipEventCreate(&ev[1]);
-    if (e == hipSuccess) e = hipEventRecord(ev[0], h->stream);
-    if (e == hipSuccess)
-      rc = rows_compact_launch(h->X, (long long)n_new, (long)h->d * (long)sizeof(float), rm, (long)n_remove, nx, h->stream);
-    if (e == hipSuccess && rc == AMDR_OK) e = hipEventRecord(ev[1], h->stream);
-    if (e == hipSuccess && rc == AMDR_OK) e = hipStreamSynchronize(h->stream);
-    if (e == hipSuccess && rc == AMDR_OK) e = hipEventElapsedTime(&ms, ev[0], ev[1]);
-    for (hipEvent_t v : ev)
-      if (v) (void)hipEventDestroy(v);
-    if (rm) (void)hipFree(rm);
-    if (e != hipSuccess || rc != AMDR_OK) {
-      if (nx) (void)hipFree(nx);
-      if (rc != AMDR_OK) return rc;
-      return fail(e == hipErrorOutOfMemory ? AMDR_ENOMEM : AMDR_EHIP, "dense_remove: %s", hipGetErrorString(e));
+  hipStream_t st = h->stream;
+  KernelSpans timer(1);  // the compaction kernel (amdr_dense_remove_kernel_ms)
+  {
+    CallScratch tmp;
+    DenseStagedMatrix nx;  // (stays empty when no row is left)
+    if (n_new > 0) {
+      long long* rm;
+      AMDR_TRY(tmp.alloc(&rm, (size_t)n_remove, who));
+      AMDR_TRY(dev_alloc(&nx.X, (size_t)n_new * h->d, who));
+      AMDR_HIP(hipMemcpyAsync(rm, remove_ids, (size_t)n_remove * sizeof(long long), hipMemcpyHostToDevice, st));
+      AMDR_TRY(timer.begin(0, st));
+      AMDR_TRY(rows_compact_launch(h->X, (long long)n_new, (long)h->d * (long)sizeof(float), rm, (long)n_remove, nx.X, st));
+      AMDR_TRY(timer.end(0, st));
+      AMDR_HIP(hipStreamSynchronize(st));
     }
+    first_pass_start_over(h);
+    nx.commit(h, n_new);
+    h->n = n_new;
   }
-  // the swap (hipFree waits for the device: host-pointer searches are behind h->mu, "_device" work is the caller's to order)
-  first_pass_start_over(h);
-  if (h->X) (void)hipFree(h->X);
-  h->X = nx;
-  h->n = h->cap_rows = n_new;
-  h->remove_kernel_ms = (double)ms;
-  rc = update_stats(h, 0, n_new);
+  h->remove_kernel_ms = n_new > 0 ? timer.ms() : 0.0;  // (emptying the index runs no kernel)
+  int rc = update_stats(h, 0, n_new);
   // a handle with an fp16 image keeps one: of the compacted matrix, whose rows sit in other 32-row tiles now
   if (h->img) {
     image_drop(h);  // (a new allocation, sized like the new matrix's own; none for an empty index or unusable statistics)
@@ -1206,11 +1212,13 @@ int amdr_dense_remove_kernel_ms(amdr_dense_t* h, double* ms) {
   return AMDR_OK;
 }
 
-// Replace rows in place.  Everything that can run out of memory or be refused — the staged rows and ids, their copies,
-// the events — has happened and has been waited for before the scatter kernel (rows_compact.hip) is enqueued; until then
-// the matrix is untouched.  Then what remove does after its swap: the statistics from zero, and a present image brought
-// up to the matrix from the first touched 32-row tile on (image_sync converts all of it when the scale changed).
+// Replace rows in place, in two phases.  Everything that can run out of memory or be refused — the staged rows and ids,
+// their copies, the launcher's checks — has happened and has been waited for before the scatter kernel (rows_compact.hip)
+// is enqueued; until then the matrix is untouched.  From then on the handle describes the edited matrix whatever is
+// reported: what remove does after its swap, the statistics from zero, and a present image brought up to the matrix from
+// the first touched 32-row tile on (image_sync converts all of it when the scale changed).
 int amdr_dense_replace(amdr_dense_t* h, const int64_t* replace_ids, const float* X_host, int64_t n_rep) {
+  static const char* const who = "dense_replace";
   AMDR_REQUIRE(h != nullptr, "dense_replace: null handle");
   AMDR_REQUIRE(h->owns, "dense_replace: handle wraps caller-owned memory");
   AMDR_REQUIRE(n_rep >= 0, "dense_replace: n_rep=%lld", (long long)n_rep);
@@ -1221,49 +1229,33 @@ int amdr_dense_replace(amdr_dense_t* h, const int64_t* replace_ids, const float*
   AMDR_REQUIRE(bad == kRcOk, "dense_replace: %s", rs_error_text(bad));
   AMDR_HIP(hipSetDevice(h->device));
   const size_t row_bytes = (size_t)h->d * sizeof(float);
-  float* rows = nullptr;
-  long long* ids = nullptr;
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  hipError_t e = hipMalloc((void**)&ids, (size_t)n_rep * sizeof(long long));
-  if (e == hipSuccess) e = hipMalloc((void**)&rows, (size_t)n_rep * row_bytes);
-  if (e == hipSuccess) e = hipMemcpyAsync(ids, replace_ids, (size_t)n_rep * sizeof(long long), hipMemcpyHostToDevice, h->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(rows, X_host, (size_t)n_rep * row_bytes, hipMemcpyHostToDevice, h->stream);
-  if (e == hipSuccess) e = hipEventCreate(&ev[0]);
-  if (e == hipSuccess) e = hipEventCreate(&ev[1]);
-  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);  // the staged copies are whole; the matrix is still the old one
-  auto release = [&]() {
-    for (hipEvent_t v : ev)
-      if (v) (void)hipEventDestroy(v);
-    if (ids) (void)hipFree(ids);
-    if (rows) (void)hipFree(rows);
-  };
-  if (e != hipSuccess) {
-    release();
-    return fail(e == hipErrorOutOfMemory ? AMDR_ENOMEM : AMDR_EHIP, "dense_replace: %s", hipGetErrorString(e));
-  }
-  float ms = 0.f;
-  e = hipEventRecord(ev[0], h->stream);
-  int rc = e == hipSuccess ? rows_scatter_launch(rows, (long long)n_rep, (long)row_bytes, ids, h->X, h->stream) : AMDR_OK;
-  if (e != hipSuccess || rc != AMDR_OK) {  // (nothing was enqueued: the launcher checks its arguments before it launches)
-    release();
-    return rc != AMDR_OK ? rc : fail(AMDR_EHIP, "dense_replace: %s", hipGetErrorString(e));
-  }
+  hipStream_t st = h->stream;
+  CallScratch tmp;
+  float* rows;
+  long long* ids;
+  AMDR_TRY(tmp.alloc(&ids, (size_t)n_rep, who));
+  AMDR_TRY(tmp.alloc(&rows, (size_t)n_rep * h->d, who));
+  AMDR_HIP(hipMemcpyAsync(ids, replace_ids, (size_t)n_rep * sizeof(long long), hipMemcpyHostToDevice, st));
+  AMDR_HIP(hipMemcpyAsync(rows, X_host, (size_t)n_rep * row_bytes, hipMemcpyHostToDevice, st));
+  KernelSpans timer(1);  // the scatter kernel (amdr_dense_replace_kernel_ms)
+  AMDR_HIP(hipStreamSynchronize(st));  // the staged copies are whole; the matrix is still the old one
+  AMDR_TRY(timer.begin(0, st));
+  // (a refusal enqueues nothing: the launcher checks its arguments before it launches)
+  AMDR_TRY(rows_scatter_launch(rows, (long long)n_rep, (long)row_bytes, ids, h->X, st));
   // from here on the matrix is the edited one; a device error below is reported, and the handle describes that matrix
-  e = hipEventRecord(ev[1], h->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-  if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev[0], ev[1]);
-  release();
+  int late = timer.end(0, st);
+  const hipError_t e = hipStreamSynchronize(st);
+  if (!late && e != hipSuccess) late = fail(AMDR_EHIP, "dense_replace: %s", hipGetErrorString(e));
   first_pass_start_over(h);
-  h->replace_kernel_ms = e == hipSuccess ? (double)ms : -1.0;
-  rc = update_stats(h, 0, h->n);
+  h->replace_kernel_ms = late ? -1.0 : timer.ms();
+  int rc = update_stats(h, 0, h->n);
   if (h->img) {
-    if (rc == AMDR_OK && e == hipSuccess && h->fp16.large_scan_ok())
+    if (rc == AMDR_OK && !late && h->fp16.large_scan_ok())
       rc = image_sync(h, replace_ids[0] / kHiTileRows * kHiTileRows);
     else
       image_drop(h);  // (no first pass is left to read it)
   }
-  if (rc == AMDR_OK && e != hipSuccess) rc = fail(AMDR_EHIP, "dense_replace: %s", hipGetErrorString(e));
-  return rc;
+  return rc ? rc : late;
 }
 
 int amdr_dense_replace_kernel_ms(amdr_dense_t* h, double* ms) {

@@ -14,10 +14,11 @@
 // plus two lane exchanges, and the final sum over query tokens is one DPP reduction per document.
 // (First built on v_mfma_f32_32x32x2_f32; the 16x16 form holds a higher clock, see dense_mfma.hip.)
 // Algorithmic bytes per (query, shard): sum_docs len*128*4; flops 2*32*128*sum len.
+// (The token store — its statistics, images and updates — is maxsim_store.hip; the handle is maxsim_handle.hpp.)
 #include "common.hpp"
 #include "lds_ring.hpp"
 #include "maxsim_core.hpp"
-#include "rows_compact.hpp"
+#include "maxsim_handle.hpp"
 #include "topk.hpp"
 
 #include <cfloat>
@@ -76,55 +77,6 @@ __device__ __forceinline__ float ms_finish(const float (&best)[2], int i16, int 
     if (kq == 0 && 16 * bj + i16 < q_len) contrib += b;
   }
   return ms_wave_sum(contrib);
-}
-
-// fp32 token rows -> the [hi | lo] image (one thread per 8 components), scaled by the store's power of two
-__global__ __launch_bounds__(256) void ms_split_store_kernel(const float* __restrict__ D, long n_tokens, float scale,
-                                                             unsigned char* __restrict__ img,
-                                                             unsigned char* __restrict__ img_hi /* [tok][128 x fp16] */) {
-  const long i = (long)blockIdx.x * 256 + threadIdx.x;  // (token, group of 8 components)
-  if (i >= n_tokens * 16) return;
-  const long tok = i >> 4;
-  const int g = (int)(i & 15);
-  float x[8];
-  const f32x4 v0 = *reinterpret_cast<const f32x4*>(D + tok * kDim + 8 * g);
-  const f32x4 v1 = *reinterpret_cast<const f32x4*>(D + tok * kDim + 8 * g + 4);
-#pragma unroll
-  for (int j = 0; j < 4; ++j) x[j] = v0[j], x[4 + j] = v1[j];
-  h8 hi, lo;
-  ms_split(x, scale, hi, lo);
-  *reinterpret_cast<h8*>(img + tok * 512 + 16 * g) = hi;
-  *reinterpret_cast<h8*>(img + tok * 512 + 256 + 16 * g) = lo;
-  *reinterpret_cast<h8*>(img_hi + tok * 256 + 16 * g) = hi;
-}
-
-// largest token L2 norm of the SCALED store (rows x `scale`, the store's power of two: components in [-1, 1], so no
-// square underflows to nothing or overflows whatever the store's magnitude), as float bits (error bound of the first
-// pass of the two-pass top-k)
-__global__ __launch_bounds__(256) void ms_tokmax_kernel(const float* __restrict__ D, long n_tokens, float scale,
-                                                        unsigned int* __restrict__ out) {
-  const int lane = threadIdx.x & 63;
-  const long wv = ((long)blockIdx.x * 256 + threadIdx.x) >> 6, nw = (long)gridDim.x * 4;
-  float m = 0.f;
-  for (long t = wv; t < n_tokens; t += nw) {
-    const float a = D[t * kDim + lane] * scale, b = D[t * kDim + 64 + lane] * scale;
-    float ss = a * a + b * b;
-#pragma unroll
-    for (int sft = 1; sft < 64; sft <<= 1) ss += __shfl_xor(ss, sft);
-    m = fmaxf(m, sqrtf(ss));
-  }
-  if (lane == 0) atomicMax(out, __float_as_uint(m));
-}
-
-// largest |component| of the store as float bits (non-negative floats order like unsigned integers; NaN sorts
-// above infinity, so a non-finite store is visible in the result)
-__global__ __launch_bounds__(256) void ms_absmax_kernel(const float* __restrict__ D, long n, unsigned int* __restrict__ out) {
-  unsigned int m = 0;
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256)
-    m = max(m, __float_as_uint(D[i]) & 0x7fffffffu);
-#pragma unroll
-  for (int sft = 1; sft < 64; sft <<= 1) m = max(m, (unsigned int)__shfl_xor((int)m, sft));
-  if ((threadIdx.x & 63) == 0) atomicMax(out, m);
 }
 
 // The lane's fragment of a 32-row x 128-float operand in global memory: rows row0 + 16 b + i16
@@ -973,27 +925,6 @@ __global__ __launch_bounds__(256) void maxsim_final_topk_kernel(const float* __r
 
 using namespace amdr;
 
-struct amdr_maxsim {
-  int device = 0;
-  int64_t n_docs = 0;
-  int64_t n_tokens = 0;                  // doc_ptr[n_docs]
-  int64_t cap_tokens = 0, cap_docs = 0;  // rows that D / img / img_hi and entries (+ 1) that doc_ptr have room for (amdr_maxsim_add)
-  float* D = nullptr;
-  unsigned char* img = nullptr;  // [hi 128 x fp16 | lo 128 x fp16] per token, scaled by d_scale (split-fp16 form)
-  unsigned char* img_hi = nullptr;  // [hi 128 x fp16] per token: first pass of the two-pass top-k
-  float d_scale = 1.f;           // power of two; img == nullptr: the store is not finite -> fp32-input form only
-  float d_norm_max = 0.f;        // largest token L2 norm of the store x d_scale (error bound of the first pass)
-  unsigned int amax_bits = 0;    // largest |component| of the store as float bits (what d_scale was taken from)
-  int64_t conversions = 0;       // whole-store conversions to the images so far (amdr_maxsim_info)
-  double remove_kernel_ms = -1.0;  // device time of the doc_ptr rebuild + the compaction of the last successful amdr_maxsim_remove
-  double replace_kernel_ms = -1.0;  // device time of the doc_ptr rebuild + the splice of the last successful amdr_maxsim_replace
-  long long* doc_ptr = nullptr;
-  int cus = 0;  // compute units of `device` (the re-scoring pass's grid)
-  hipStream_t stream = nullptr;
-  std::mutex mu;
-  DevBuf full[2], qbuf, sbuf, ibuf;  // full[0]: "_device" calls, full[1]: host-pointer calls (see dense.hip)
-};
-
 namespace amdr {
 int maxsim_raw(amdr_maxsim_t* h, MaxsimRaw* out) {
   out->img = h->img;
@@ -1194,58 +1125,6 @@ int ms_run(amdr_maxsim* h, const MsRoute& r, const float* Q_dev, int nq, int q_l
   return AMDR_OK;
 }
 
-// ---- the store's statistics and images, over a range of token rows (amdr_maxsim_create: all of them; amdr_maxsim_add:
-// the new ones).  Synchronous, on the null stream. -------------------------------------------------------------------
-// largest |component| of token rows [t0, t1) as float bits (>= 0x7f800000: the range holds a NaN or an infinity)
-hipError_t ms_absmax(const float* D, int64_t t0, int64_t t1, unsigned int* bits) {
-  unsigned int* mx = nullptr;
-  hipError_t e = hipMalloc((void**)&mx, sizeof(unsigned int));
-  if (e == hipSuccess) e = hipMemset(mx, 0, sizeof(unsigned int));
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(ms_absmax_kernel, dim3(1024), dim3(256), 0, 0, D + (size_t)t0 * kDim, (long)((t1 - t0) * kDim), mx);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipMemcpy(bits, mx, sizeof(unsigned int), hipMemcpyDeviceToHost);
-  if (mx) (void)hipFree(mx);
-  return e;
-}
-// Token rows [t0, t1) of D -> both images at `scale`, t1 being the store's end: the zero tile behind it (32 tokens of
-// img, 64 of img_hi) is written too.  *norm_max = the largest L2 norm of the scaled rows of the range.
-hipError_t ms_convert(const float* D, int64_t t0, int64_t t1, float scale, unsigned char* img, unsigned char* img_hi,
-                      float* norm_max) {
-  unsigned int* nm = nullptr;
-  unsigned int nbits = 0;
-  hipError_t e = hipMemset(img + (size_t)t1 * 512, 0, (size_t)32 * 512);
-  if (e == hipSuccess) e = hipMemset(img_hi + (size_t)t1 * 256, 0, (size_t)64 * 256);
-  if (e == hipSuccess) e = hipMalloc((void**)&nm, sizeof(unsigned int));
-  if (e == hipSuccess) e = hipMemset(nm, 0, sizeof(unsigned int));
-  if (e == hipSuccess) {
-    const int64_t nt = t1 - t0;
-    hipLaunchKernelGGL(ms_split_store_kernel, dim3(ceil_div(nt * 16, 256)), dim3(256), 0, 0, D + (size_t)t0 * kDim, (long)nt,
-                       scale, img + (size_t)t0 * 512, img_hi + (size_t)t0 * 256);
-    e = hipGetLastError();
-    if (e == hipSuccess) {
-      hipLaunchKernelGGL(ms_tokmax_kernel, dim3(1024), dim3(256), 0, 0, D + (size_t)t0 * kDim, (long)nt, scale, nm);
-      e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpy(&nbits, nm, sizeof(unsigned int), hipMemcpyDeviceToHost);
-    memcpy(norm_max, &nbits, sizeof(float));
-  }
-  if (nm) (void)hipFree(nm);
-  if (e == hipSuccess) e = hipDeviceSynchronize();
-  return e;
-}
-hipError_t ms_alloc_images(int64_t cap_tokens, unsigned char** img, unsigned char** img_hi) {
-  hipError_t e = hipMalloc((void**)img, (size_t)(cap_tokens + 32) * 512);  // + one tile: the last tile of the last document reads on
-  if (e == hipSuccess) e = hipMalloc((void**)img_hi, (size_t)(cap_tokens + 64) * 256);  // + one 64-token tile
-  return e;
-}
-float ms_scale_of(unsigned int amax_bits) {
-  float m;
-  memcpy(&m, &amax_bits, sizeof(float));
-  return pow2_scale(pow2_exp(m));
-}
-
 int ms_check(const amdr_maxsim* h, const void* Q, int nq, int q_len, int k) {
   AMDR_REQUIRE(h != nullptr, "maxsim: null handle");
   AMDR_REQUIRE(nq >= 0, "maxsim: nq=%d", nq);
@@ -1290,357 +1169,15 @@ int amdr_maxsim_create(const float* D_host, const int64_t* doc_ptr, int64_t n_do
   lds((const void*)maxsim_hi2_ring_kernel<kRing1>, kRing1 * 16384);
   lds((const void*)maxsim_rescore_ring_kernel<kRing2>, kRing2 * 16384);
   lds((const void*)maxsim_overflow_kernel, kPairLds);
-  // the split-fp16 image: the store's largest |component| fixes a power-of-two scale into [0.5, 1), then every
-  // token row is split once (a store with a NaN / infinity keeps the fp32-input form only)
-  if (e == hipSuccess) e = ms_absmax(h->D, 0, nt, &h->amax_bits);
-  if (e == hipSuccess && h->amax_bits < 0x7f800000u) {
-    h->d_scale = ms_scale_of(h->amax_bits);
-    e = ms_alloc_images(nt, &h->img, &h->img_hi);
-    if (e == hipSuccess) e = ms_convert(h->D, 0, nt, h->d_scale, h->img, h->img_hi, &h->d_norm_max);
-    h->conversions = 1;
-  }
   if (e != hipSuccess) {
     amdr_maxsim_destroy(h);
     return fail(e == hipErrorOutOfMemory ? AMDR_ENOMEM : AMDR_EHIP, "maxsim_create: %s", hipGetErrorString(e));
   }
+  if ((rc = ms_finish_store(*h))) {  // the statistics and the images (maxsim_store.hip), as every rebuild takes them
+    amdr_maxsim_destroy(h);
+    return rc;
+  }
   *out = h;
-  return AMDR_OK;
-}
-
-int amdr_maxsim_info(amdr_maxsim_t* h, int64_t* out6) {
-  AMDR_REQUIRE(h && out6, "maxsim_info: null");
-  std::lock_guard<std::mutex> g(h->mu);
-  out6[0] = h->n_docs;
-  out6[1] = h->n_tokens;
-  out6[2] = h->cap_tokens;
-  out6[3] = pow2_exp(h->d_scale) - 1;  // d_scale = 2^e = 0.5 * 2^(e + 1)
-  out6[4] = h->img ? 1 : 0;
-  out6[5] = h->conversions;
-  return AMDR_OK;
-}
-
-int amdr_maxsim_stats(amdr_maxsim_t* h, float* out2) {
-  AMDR_REQUIRE(h && out2, "maxsim_stats: null");
-  std::lock_guard<std::mutex> g(h->mu);
-  out2[0] = h->d_scale;
-  out2[1] = h->d_norm_max;
-  return AMDR_OK;
-}
-
-// Append documents.  Everything that can fail — allocations, copies, the conversion kernels — runs on buffers or buffer
-// tails that no search reads (rows behind n_tokens, entries behind n_docs + 1); the handle's fields change together at
-// the end, so a failed add leaves the store it had.  What create() does for a whole store, on the new rows: their largest
-// |component| joins the store's, and only when that raises the store's power-of-two scale are the images made again from
-// D — otherwise the old rows' image bytes are already what create() would write for the concatenated store.
-int amdr_maxsim_add(amdr_maxsim_t* h, const float* D_host, const int64_t* doc_ptr_add, int64_t n_add) {
-  AMDR_REQUIRE(h != nullptr, "maxsim_add: null handle");
-  AMDR_REQUIRE(n_add >= 0, "maxsim_add: n_add=%lld", (long long)n_add);
-  if (n_add == 0) return AMDR_OK;
-  AMDR_REQUIRE(D_host && doc_ptr_add, "maxsim_add: null D / doc_ptr");
-  std::lock_guard<std::mutex> g(h->mu);
-  AMDR_REQUIRE(n_add < (1ll << 32) && h->n_docs + n_add < (1ll << 32), "maxsim_add: too many documents");  // (before doc_ptr_add is walked)
-  AMDR_REQUIRE(doc_ptr_add[0] == 0, "maxsim_add: doc_ptr[0] != 0");
-  for (int64_t i = 0; i < n_add; ++i)
-    AMDR_REQUIRE(doc_ptr_add[i + 1] > doc_ptr_add[i], "maxsim_add: document %lld has no tokens", (long long)i);
-  AMDR_HIP(hipSetDevice(h->device));
-  const int64_t t0 = h->n_tokens, t1 = t0 + doc_ptr_add[n_add], nd0 = h->n_docs, nd1 = nd0 + n_add;
-  long long* ptr_host = new (std::nothrow) long long[(size_t)n_add];
-  if (!ptr_host) return fail(AMDR_ENOMEM, "maxsim_add: host alloc");
-  for (int64_t i = 0; i < n_add; ++i) ptr_host[i] = (long long)(t0 + doc_ptr_add[i + 1]);
-
-  // the buffers the grown store lives in: the handle's own where there is room, otherwise new ones (double, or to fit)
-  const bool grow_t = t1 > h->cap_tokens, grow_d = nd1 > h->cap_docs;
-  const int64_t cap_t = !grow_t ? h->cap_tokens : (h->cap_tokens * 2 > t1 ? h->cap_tokens * 2 : t1);
-  const int64_t cap_d = !grow_d ? h->cap_docs : (h->cap_docs * 2 > nd1 ? h->cap_docs * 2 : nd1);
-  float* D = h->D;
-  long long* dp = h->doc_ptr;
-  unsigned char *img = h->img, *img_hi = h->img_hi;
-  hipError_t e = hipSuccess;
-  if (grow_t) {
-    D = nullptr;
-    e = hipMalloc((void**)&D, (size_t)cap_t * kDim * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpy(D, h->D, (size_t)t0 * kDim * sizeof(float), hipMemcpyDeviceToDevice);
-  }
-  if (e == hipSuccess && grow_d) {
-    dp = nullptr;
-    e = hipMalloc((void**)&dp, (size_t)(cap_d + 1) * sizeof(long long));
-    if (e == hipSuccess) e = hipMemcpy(dp, h->doc_ptr, (size_t)(nd0 + 1) * sizeof(long long), hipMemcpyDeviceToDevice);
-  }
-  if (e == hipSuccess) e = hipMemcpy(D + (size_t)t0 * kDim, D_host, (size_t)(t1 - t0) * kDim * sizeof(float), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(dp + nd0 + 1, ptr_host, (size_t)n_add * sizeof(long long), hipMemcpyHostToDevice);
-  delete[] ptr_host;
-
-  // statistics from the new rows; the images follow them
-  unsigned int amax = h->amax_bits;
-  float scale = h->d_scale, norm_max = h->d_norm_max;
-  int64_t conversions = h->conversions;
-  bool keep_img = h->img != nullptr;
-  if (e == hipSuccess) {
-    unsigned int add_bits = 0;
-    e = ms_absmax(D, t0, t1, &add_bits);
-    amax = add_bits > amax ? add_bits : amax;  // (float bits of non-negative values order like the values; NaN on top)
-  }
-  if (e == hipSuccess && keep_img) {
-    if (amax >= 0x7f800000u) {  // the store is no longer finite: the fp32-input forms serve, as after such a create()
-      keep_img = false;
-      img = img_hi = nullptr;
-      scale = 1.f;
-      norm_max = 0.f;
-    } else {
-      const bool rescale = ms_scale_of(amax) != scale;  // the exponent can only rise
-      scale = ms_scale_of(amax);
-      if (grow_t || rescale) {  // (a re-split goes to new images too: the old ones serve until it has succeeded)
-        img = img_hi = nullptr;
-        e = ms_alloc_images(cap_t, &img, &img_hi);
-        if (e == hipSuccess && !rescale) e = hipMemcpy(img, h->img, (size_t)t0 * 512, hipMemcpyDeviceToDevice);
-        if (e == hipSuccess && !rescale) e = hipMemcpy(img_hi, h->img_hi, (size_t)t0 * 256, hipMemcpyDeviceToDevice);
-      }
-      float nm = 0.f;
-      if (e == hipSuccess) e = ms_convert(D, rescale ? 0 : t0, t1, scale, img, img_hi, &nm);
-      norm_max = rescale ? nm : (nm > norm_max ? nm : norm_max);
-      conversions += rescale ? 1 : 0;
-    }
-  }
-  if (e == hipSuccess) e = hipDeviceSynchronize();
-  if (e != hipSuccess) {
-    if (D != h->D) (void)hipFree(D);
-    if (dp != h->doc_ptr) (void)hipFree(dp);
-    if (img && img != h->img) (void)hipFree(img);
-    if (img_hi && img_hi != h->img_hi) (void)hipFree(img_hi);
-    if (keep_img && img == h->img) {  // the tail written behind the old end becomes the zero tile again (masked either way)
-      (void)hipMemset(h->img + (size_t)t0 * 512, 0, (size_t)32 * 512);
-      (void)hipMemset(h->img_hi + (size_t)t0 * 256, 0, (size_t)64 * 256);
-    }
-    return fail(e == hipErrorOutOfMemory ? AMDR_ENOMEM : AMDR_EHIP, "maxsim_add: %s", hipGetErrorString(e));
-  }
-  // the swap (hipFree waits for the device: host-pointer searches are behind h->mu, "_device" work is the caller's to order)
-  if (D != h->D) (void)hipFree(h->D);
-  if (dp != h->doc_ptr) (void)hipFree(h->doc_ptr);
-  if (img != h->img && h->img) (void)hipFree(h->img);
-  if (img_hi != h->img_hi && h->img_hi) (void)hipFree(h->img_hi);
-  h->D = D;
-  h->doc_ptr = dp;
-  h->img = img;
-  h->img_hi = img_hi;
-  h->cap_tokens = cap_t;
-  h->cap_docs = cap_d;
-  h->n_tokens = t1;
-  h->n_docs = nd1;
-  h->amax_bits = amax;
-  h->d_scale = scale;
-  h->d_norm_max = norm_max;
-  h->conversions = conversions;
-  return AMDR_OK;
-}
-
-// Remove documents.  The new doc_ptr and the compacted D (rows_compact.hip) are built in new buffers, then create()'s own
-// sequence runs on the new D — largest |component|, scale, new images converted from it, d_norm_max — so the scale and
-// the bound can FALL here and a store whose last NaN / infinity goes gets its images.  The handle's fields change together
-// at the end; until then every search reads the old store.
-int amdr_maxsim_remove(amdr_maxsim_t* h, const int64_t* remove_ids, int64_t n_remove) {
-  AMDR_REQUIRE(h != nullptr, "maxsim_remove: null handle");
-  AMDR_REQUIRE(n_remove >= 0, "maxsim_remove: n_remove=%lld", (long long)n_remove);
-  if (n_remove == 0) return AMDR_OK;
-  std::lock_guard<std::mutex> g(h->mu);
-  const int bad = rc_validate(remove_ids, n_remove, h->n_docs);
-  AMDR_REQUIRE(bad == kRcOk, "maxsim_remove: %s", rc_error_text(bad));
-  AMDR_REQUIRE(n_remove < h->n_docs, "maxsim_remove: n_remove=%lld would leave no document of %lld", (long long)n_remove,
-               (long long)h->n_docs);
-  AMDR_HIP(hipSetDevice(h->device));
-  const int64_t nd1 = h->n_docs - n_remove;
-  long long *rm = nullptr, *len = nullptr, *start = nullptr, *dp = nullptr;
-  float* D = nullptr;
-  unsigned char *img = nullptr, *img_hi = nullptr;
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  long long t1 = 0;
-  int rc = AMDR_OK;
-  hipStream_t st = h->stream;
-  hipError_t e = hipMalloc((void**)&rm, (size_t)n_remove * sizeof(long long));
-  if (e == hipSuccess) e = hipMalloc((void**)&len, (size_t)nd1 * sizeof(long long));
-  if (e == hipSuccess) e = hipMalloc((void**)&start, (size_t)nd1 * sizeof(long long));
-  if (e == hipSuccess) e = hipMalloc((void**)&dp, (size_t)(nd1 + 1) * sizeof(long long));
-  for (int i = 0; i < 4 && e == hipSuccess; ++i) e = hipEventCreate(&ev[i]);
-  if (e == hipSuccess) e = hipMemcpyAsync(rm, remove_ids, (size_t)n_remove * sizeof(long long), hipMemcpyHostToDevice, st);
-  // the doc_ptr rebuild, then the host's look at the new token count
-  if (e == hipSuccess) e = hipEventRecord(ev[0], st);
-  if (e == hipSuccess) rc = segments_ptr_launch(h->doc_ptr, (long)nd1, rm, (long)n_remove, len, start, dp, st);
-  if (e == hipSuccess && rc == AMDR_OK) e = hipEventRecord(ev[1], st);
-  if (e == hipSuccess && rc == AMDR_OK) e = hipMemcpyAsync(&t1, dp + nd1, sizeof(long long), hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess && rc == AMDR_OK) e = hipStreamSynchronize(st);
-  if (e == hipSuccess && rc == AMDR_OK && (t1 < nd1 || t1 >= h->n_tokens))
-    rc = fail(AMDR_EHIP, "maxsim_remove: counted %lld of %lld token rows", t1, (long long)h->n_tokens);
-  // the token rows
-  if (e == hipSuccess && rc == AMDR_OK) e = hipMalloc((void**)&D, (size_t)t1 * kDim * sizeof(float));
-  if (e == hipSuccess && rc == AMDR_OK) e = hipEventRecord(ev[2], st);
-  if (e == hipSuccess && rc == AMDR_OK) rc = segments_compact_launch(h->D, t1, dp, start, (long)nd1, D, st);
-  if (e == hipSuccess && rc == AMDR_OK) e = hipEventRecord(ev[3], st);
-  if (e == hipSuccess && rc == AMDR_OK) e = hipStreamSynchronize(st);
-  float ms0 = 0.f, ms1 = 0.f;
-  if (e == hipSuccess && rc == AMDR_OK) e = hipEventElapsedTime(&ms0, ev[0], ev[1]);
-  if (e == hipSuccess && rc == AMDR_OK) e = hipEventElapsedTime(&ms1, ev[2], ev[3]);
-  // exactly create()'s sequence on the new D
-  unsigned int amax = 0;
-  float scale = 1.f, norm_max = 0.f;
-  int64_t conversions = h->conversions;
-  if (e == hipSuccess && rc == AMDR_OK) e = ms_absmax(D, 0, t1, &amax);
-  if (e == hipSuccess && rc == AMDR_OK && amax < 0x7f800000u) {
-    scale = ms_scale_of(amax);
-    e = ms_alloc_images(t1, &img, &img_hi);
-    if (e == hipSuccess) e = ms_convert(D, 0, t1, scale, img, img_hi, &norm_max);
-    ++conversions;
-  }
-  if (e == hipSuccess && rc == AMDR_OK) e = hipDeviceSynchronize();
-  for (hipEvent_t v : ev)
-    if (v) (void)hipEventDestroy(v);
-  if (rm) (void)hipFree(rm);
-  if (len) (void)hipFree(len);
-  if (start) (void)hipFree(start);
-  if (e != hipSuccess || rc != AMDR_OK) {
-    if (dp) (void)hipFree(dp);
-    if (D) (void)hipFree(D);
-    if (img) (void)hipFree(img);
-    if (img_hi) (void)hipFree(img_hi);
-    if (rc != AMDR_OK) return rc;
-    return fail(e == hipErrorOutOfMemory ? AMDR_ENOMEM : AMDR_EHIP, "maxsim_remove: %s", hipGetErrorString(e));
-  }
-  // the swap (hipFree waits for the device: host-pointer searches are behind h->mu, "_device" work is the caller's to order)
-  (void)hipFree(h->D);
-  (void)hipFree(h->doc_ptr);
-  if (h->img) (void)hipFree(h->img);
-  if (h->img_hi) (void)hipFree(h->img_hi);
-  h->D = D;
-  h->doc_ptr = dp;
-  h->img = img;
-  h->img_hi = img_hi;
-  h->cap_tokens = h->n_tokens = t1;
-  h->cap_docs = h->n_docs = nd1;
-  h->amax_bits = amax;
-  h->d_scale = scale;
-  h->d_norm_max = norm_max;
-  h->conversions = conversions;
-  h->remove_kernel_ms = (double)ms0 + (double)ms1;
-  return AMDR_OK;
-}
-
-int amdr_maxsim_remove_kernel_ms(amdr_maxsim_t* h, double* ms) {
-  AMDR_REQUIRE(h && ms, "maxsim_remove_kernel_ms: null");
-  std::lock_guard<std::mutex> g(h->mu);
-  *ms = h->remove_kernel_ms;
-  return AMDR_OK;
-}
-
-// Replace documents under their pids.  amdr_maxsim_remove with a second source: the new token rows and their doc_ptr are
-// staged on the device, the new doc_ptr and the spliced D (rows_compact.hip) are built in new buffers, then create()'s own
-// sequence runs on the new D.  The handle's fields change together at the end; until then every search reads the old store.
-int amdr_maxsim_replace(amdr_maxsim_t* h, const int64_t* replace_ids, const float* D_host, const int64_t* doc_ptr_add,
-                        int64_t n_rep) {
-  AMDR_REQUIRE(h != nullptr, "maxsim_replace: null handle");
-  AMDR_REQUIRE(n_rep >= 0, "maxsim_replace: n_rep=%lld", (long long)n_rep);
-  if (n_rep == 0) return AMDR_OK;
-  AMDR_REQUIRE(D_host && doc_ptr_add, "maxsim_replace: null D / doc_ptr");
-  std::lock_guard<std::mutex> g(h->mu);
-  const int bad = rc_validate(replace_ids, n_rep, h->n_docs);  // (n_rep <= n_docs, before doc_ptr_add is walked)
-  AMDR_REQUIRE(bad == kRcOk, "maxsim_replace: %s", rs_error_text(bad));
-  AMDR_REQUIRE(doc_ptr_add[0] == 0, "maxsim_replace: doc_ptr[0] != 0");
-  for (int64_t i = 0; i < n_rep; ++i)
-    AMDR_REQUIRE(doc_ptr_add[i + 1] > doc_ptr_add[i], "maxsim_replace: document %lld has no tokens", (long long)i);
-  AMDR_HIP(hipSetDevice(h->device));
-  const int64_t nd = h->n_docs, t_add = doc_ptr_add[n_rep];
-  long long *ids = nullptr, *add_ptr = nullptr, *len = nullptr, *start = nullptr, *dp = nullptr;
-  float *add_rows = nullptr, *D = nullptr;
-  unsigned char *img = nullptr, *img_hi = nullptr;
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  long long t1 = 0;
-  int rc = AMDR_OK;
-  hipStream_t st = h->stream;
-  hipError_t e = hipMalloc((void**)&ids, (size_t)n_rep * sizeof(long long));
-  if (e == hipSuccess) e = hipMalloc((void**)&add_ptr, (size_t)(n_rep + 1) * sizeof(long long));
-  if (e == hipSuccess) e = hipMalloc((void**)&add_rows, (size_t)t_add * kDim * sizeof(float));
-  if (e == hipSuccess) e = hipMalloc((void**)&len, (size_t)nd * sizeof(long long));
-  if (e == hipSuccess) e = hipMalloc((void**)&start, (size_t)nd * sizeof(long long));
-  if (e == hipSuccess) e = hipMalloc((void**)&dp, (size_t)(nd + 1) * sizeof(long long));
-  for (int i = 0; i < 4 && e == hipSuccess; ++i) e = hipEventCreate(&ev[i]);
-  if (e == hipSuccess) e = hipMemcpyAsync(ids, replace_ids, (size_t)n_rep * sizeof(long long), hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(add_ptr, doc_ptr_add, (size_t)(n_rep + 1) * sizeof(long long), hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(add_rows, D_host, (size_t)t_add * kDim * sizeof(float), hipMemcpyHostToDevice, st);
-  // the doc_ptr rebuild, then the host's look at the new token count
-  if (e == hipSuccess) e = hipEventRecord(ev[0], st);
-  if (e == hipSuccess) rc = splice_ptr_launch(h->doc_ptr, (long)nd, add_ptr, ids, (long)n_rep, len, start, dp, st);
-  if (e == hipSuccess && rc == AMDR_OK) e = hipEventRecord(ev[1], st);
-  if (e == hipSuccess && rc == AMDR_OK) e = hipMemcpyAsync(&t1, dp + nd, sizeof(long long), hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess && rc == AMDR_OK) e = hipStreamSynchronize(st);
-  if (e == hipSuccess && rc == AMDR_OK && (t1 < nd || t1 < t_add || t1 - t_add > h->n_tokens - n_rep))
-    rc = fail(AMDR_EHIP, "maxsim_replace: counted %lld token rows from %lld old and %lld new", t1, (long long)h->n_tokens,
-              (long long)t_add);
-  // the token rows
-  if (e == hipSuccess && rc == AMDR_OK) e = hipMalloc((void**)&D, (size_t)t1 * kDim * sizeof(float));
-  if (e == hipSuccess && rc == AMDR_OK) e = hipEventRecord(ev[2], st);
-  if (e == hipSuccess && rc == AMDR_OK) rc = segments_splice_launch(h->D, add_rows, t1, dp, start, (long)nd, D, st);
-  if (e == hipSuccess && rc == AMDR_OK) e = hipEventRecord(ev[3], st);
-  if (e == hipSuccess && rc == AMDR_OK) e = hipStreamSynchronize(st);
-  float ms0 = 0.f, ms1 = 0.f;
-  if (e == hipSuccess && rc == AMDR_OK) e = hipEventElapsedTime(&ms0, ev[0], ev[1]);
-  if (e == hipSuccess && rc == AMDR_OK) e = hipEventElapsedTime(&ms1, ev[2], ev[3]);
-  // exactly create()'s sequence on the new D
-  unsigned int amax = 0;
-  float scale = 1.f, norm_max = 0.f;
-  int64_t conversions = h->conversions;
-  if (e == hipSuccess && rc == AMDR_OK) e = ms_absmax(D, 0, t1, &amax);
-  if (e == hipSuccess && rc == AMDR_OK && amax < 0x7f800000u) {
-    scale = ms_scale_of(amax);
-    e = ms_alloc_images(t1, &img, &img_hi);
-    if (e == hipSuccess) e = ms_convert(D, 0, t1, scale, img, img_hi, &norm_max);
-    ++conversions;
-  }
-  if (e == hipSuccess && rc == AMDR_OK) e = hipDeviceSynchronize();
-  for (hipEvent_t v : ev)
-    if (v) (void)hipEventDestroy(v);
-  if (ids) (void)hipFree(ids);
-  if (add_ptr) (void)hipFree(add_ptr);
-  if (add_rows) (void)hipFree(add_rows);
-  if (len) (void)hipFree(len);
-  if (start) (void)hipFree(start);
-  if (e != hipSuccess || rc != AMDR_OK) {
-    if (dp) (void)hipFree(dp);
-    if (D) (void)hipFree(D);
-    if (img) (void)hipFree(img);
-    if (img_hi) (void)hipFree(img_hi);
-    if (rc != AMDR_OK) return rc;
-    return fail(e == hipErrorOutOfMemory ? AMDR_ENOMEM : AMDR_EHIP, "maxsim_replace: %s", hipGetErrorString(e));
-  }
-  // the swap (hipFree waits for the device: host-pointer searches are behind h->mu, "_device" work is the caller's to order)
-  (void)hipFree(h->D);
-  (void)hipFree(h->doc_ptr);
-  if (h->img) (void)hipFree(h->img);
-  if (h->img_hi) (void)hipFree(h->img_hi);
-  h->D = D;
-  h->doc_ptr = dp;
-  h->img = img;
-  h->img_hi = img_hi;
-  h->cap_tokens = h->n_tokens = t1;
-  h->cap_docs = nd;
-  h->amax_bits = amax;
-  h->d_scale = scale;
-  h->d_norm_max = norm_max;
-  h->conversions = conversions;
-  h->replace_kernel_ms = (double)ms0 + (double)ms1;
-  return AMDR_OK;
-}
-
-int amdr_maxsim_replace_kernel_ms(amdr_maxsim_t* h, double* ms) {
-  AMDR_REQUIRE(h && ms, "maxsim_replace_kernel_ms: null");
-  std::lock_guard<std::mutex> g(h->mu);
-  *ms = h->replace_kernel_ms;
-  return AMDR_OK;
-}
-
-int amdr_maxsim_read(amdr_maxsim_t* h, float* D_host, int64_t* doc_ptr_host) {
-  AMDR_REQUIRE(h != nullptr, "maxsim_read: null handle");
-  std::lock_guard<std::mutex> g(h->mu);
-  AMDR_HIP(hipSetDevice(h->device));
-  if (D_host) AMDR_HIP(hipMemcpy(D_host, h->D, (size_t)h->n_tokens * kDim * sizeof(float), hipMemcpyDeviceToHost));
-  if (doc_ptr_host)
-    AMDR_HIP(hipMemcpy(doc_ptr_host, h->doc_ptr, (size_t)(h->n_docs + 1) * sizeof(long long), hipMemcpyDeviceToHost));
   return AMDR_OK;
 }
 

@@ -209,8 +209,8 @@ int amdr_bm25_set_tokens(amdr_bm25_t* h, const int64_t* doc_ptr, const int32_t* 
   const int64_t n_tok = doc_ptr[n];
   long long* np = nullptr;
   int* nt = nullptr;
-  int rc = bm_dev_alloc(&np, (size_t)n + 1, who);
-  if (!rc) rc = bm_dev_alloc(&nt, (size_t)n_tok + 1, who);  // (+ 1: never an empty allocation)
+  int rc = dev_alloc(&np, (size_t)n + 1, who);
+  if (!rc) rc = dev_alloc(&nt, (size_t)n_tok + 1, who);  // (+ 1: never an empty allocation)
   if (!rc && hipMemcpy(np, doc_ptr, (size_t)(n + 1) * sizeof(long long), hipMemcpyHostToDevice) != hipSuccess) rc = AMDR_EHIP;
   if (!rc && n_tok && hipMemcpy(nt, tokens, (size_t)n_tok * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) rc = AMDR_EHIP;
   if (rc) {  // the handle keeps what it had

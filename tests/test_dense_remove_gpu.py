@@ -148,6 +148,32 @@ def test_remove_add_remove_against_fresh(nat):
     f.close()
 
 
+@pytest.mark.parametrize("with_image", (False, True))
+def test_adds_that_grow_the_matrix_on_their_own(nat, with_image):
+    """A created matrix has no spare rows: one row forces a growth (33 -> 66), 40 more force the next (74 > 66 -> 132), one
+    more fits.  After each add the resident bytes and the searches are those of a fresh handle of the concatenation, and
+    a resident fp16 image covers every row."""
+    rng = np.random.default_rng(56)
+    n, d, nq, k = 33, 128, 3, 5
+    rows, Q = unit_rows(rng, n, d), unit_rows(rng, nq, d)
+    g = nat.DenseIndex(rows)
+    if with_image:
+        g.build_image()
+    for n_add in (1, 40, 1):
+        more = unit_rows(rng, n_add, d)
+        g.add(more)
+        rows = np.concatenate([rows, more])
+        ntotal = rows.shape[0]
+        assert g.ntotal == ntotal and np.array_equal(bits(g.read_rows(0, ntotal)), bits(rows))
+        f = nat.DenseIndex(rows)
+        (gs, gi), (fs, fi) = g.search(Q, k), f.search(Q, k)
+        assert np.array_equal(gi, fi) and np.array_equal(bits(gs), bits(fs)), n_add
+        f.close()
+        if with_image:
+            assert g.image_info()[0] and g.image_info()[2] == ntotal, n_add
+    g.close()
+
+
 def test_removing_everything_leaves_the_empty_index(nat):
     rng = np.random.default_rng(54)
     n, d = 300, 128

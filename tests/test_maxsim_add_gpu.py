@@ -1,6 +1,6 @@
 """amdr_maxsim_add: after any sequence of adds a MaxSim handle is what amdr_maxsim_create makes of the concatenated
 store — the same scale and images, hence the same ids and score BITS from every entry point and on every route
-(csrc/maxsim.hip).  `grown` is created from the first part and added to, `fresh` from the concatenation."""
+(csrc/maxsim_store.hip).  `grown` is created from the first part and added to, `fresh` from the concatenation."""
 import ctypes as C
 
 import numpy as np
@@ -126,6 +126,34 @@ def test_plain_adds_convert_only_the_new_rows(nat, monkeypatch, queries, case1):
     assert_same(nat, monkeypatch, g, f, queries, seam=42)
     g.add(np.zeros((0, 128), np.float32), np.zeros(1, np.int64))  # n_add == 0: a no-op
     assert_same(nat, monkeypatch, g, f, queries)
+    g.close()
+    f.close()
+
+
+def test_an_add_grows_the_document_table_alone(nat, monkeypatch, queries):
+    """Many one-token documents behind a few long ones: doc_ptr has no room for them while D and the images have (the
+    first add doubled 880 token rows to 1 760 and 4 documents to 8).  Then an add that fits both."""
+    rng = np.random.default_rng(2028)
+
+    def docs(lens):
+        ptr = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+        return unit_rows(rng, int(ptr[-1])), ptr
+
+    parts = [docs([220] * 4), docs([220, 220]), docs([1] * 40), docs([1])]
+    g = nat.MaxSimIndex(*parts[0])
+    g.add(*parts[1])
+    assert g.info()[:3] == (6, 1320, 1760) and g.info()[5] == 1
+    g.add(*parts[2])  # 46 documents > 8, 1 360 token rows <= 1 760
+    assert g.info()[:3] == (46, 1360, 1760) and g.info()[5] == 1
+    f = fresh(nat, parts[:3])
+    assert_same(nat, monkeypatch, g, f, queries, seam=6)
+    f.close()
+    g.add(*parts[3])  # 47 documents <= 2 x 46
+    assert g.info()[:3] == (47, 1361, 1760) and g.info()[5] == 1
+    f = fresh(nat, parts)
+    assert_same(nat, monkeypatch, g, f, queries, seam=46)
+    d, p = g.read()
+    assert np.array_equal(bits(d), bits(concat(parts)[0])) and np.array_equal(p, concat(parts)[1])
     g.close()
     f.close()
 

@@ -1,6 +1,6 @@
 """amdr_maxsim_remove: after a remove a MaxSim handle is what amdr_maxsim_create makes of the surviving store — D and
 doc_ptr the same bytes, the scale, the first-pass bound and the images made again from the new D, hence the same ids and
-score BITS from every entry point and on every route (csrc/maxsim.hip, csrc/rows_compact.hip).  `removed` is created from
+score BITS from every entry point and on every route (csrc/maxsim_store.hip, csrc/rows_compact.hip).  `removed` is created from
 the whole store and removed from, `fresh` from the survivors filtered on the host.  The helpers are those of
 tests/test_maxsim_add_gpu.py, restated."""
 import ctypes as C

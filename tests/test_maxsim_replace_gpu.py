@@ -1,6 +1,6 @@
 """amdr_maxsim_replace: after a replace a MaxSim handle is what amdr_maxsim_create makes of the edited store — D and
 doc_ptr the same bytes, the scale, the first-pass bound and the images made again from the new D, hence the same ids and
-score BITS from every entry point and on every route (csrc/maxsim.hip, csrc/rows_compact.hip).  `g` is created from the
+score BITS from every entry point and on every route (csrc/maxsim_store.hip, csrc/rows_compact.hip).  `g` is created from the
 whole store and replaced in, `f` from the store edited on the host.  The helpers are those of
 tests/test_maxsim_remove_gpu.py."""
 import ctypes as C
