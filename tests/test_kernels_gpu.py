@@ -469,6 +469,8 @@ def bm25_pair(nat, docs):
     (1, 5, 5, 3), (1260, 1181, 200, 10), (2048, 900, 30, 40), (2049, 900, 30, 10),
 ])
 def test_bm25_bit_exact(nat, n_docs, vocab, max_len, k):
+    """Seeded Zipf corpora against the oracle.  The structural edges of the scoring walk — list lengths around a chunk and
+    a prefetch window, token groups, slab borders, sums that cancel — are in tests/test_bm25_walk_adversary_gpu.py."""
     from oracle import bm25 as OB
     rng = np.random.default_rng(n_docs + vocab + k)
     docs, words = toy_corpus(rng, n_docs, vocab, max_len)
