@@ -973,6 +973,40 @@ int amdr_term_scope_lists(amdr_bm25_t* bm25, const int64_t* grp_ptr, const int32
                           int64_t n_cons, int64_t n_groups, int64_t cand_max, int64_t rows_cap, int64_t* out_scope_ptr,
                           int64_t* out_rows, int32_t* out_status);
 
+/* ---- proximity constraints: Near(t0, t1, ..., distance = n), beside phrases in one list array ------------------------
+ * No reference counterpart (the reference scores bags of words and keeps no token order).  csrc/phrase_scope.hip,
+ * csrc/near_rule.hpp.  Needs the token stream of amdr_bm25_set_tokens.
+ * amdr_span_lists* are amdr_phrase_lists* over ITEMS of three kinds, so that the phrases and the Nears of one batch land
+ * in ONE list array (amdr_term_scope_lists takes a single x_ptr / x_doc).  item_ptr i64 [n_items + 1] indexes item_terms
+ * i32; item_kind i32 [n_items]: 0 a phrase (the rule above; item_dist is not read), 1 a Near unordered, 2 a Near ordered;
+ * item_dist i32 [n_items]: a Near's distance n.
+ * A Near is M term ids t[0 .. M), 2 <= M <= 8 — repeats are allowed and are meaningful — and a distance 1 <= n <= 255.
+ *   unordered  a document HOLDS it when some run of at most n + 1 consecutive tokens of it contains every distinct term
+ *              at least as many times as the Near names it (two different tokens at p and q: |q - p| <= n);
+ *   ordered    a document HOLDS it when there are positions p0 < p1 < ... < p[M-1] inside it with tokens[p_i] == t[i]
+ *              and p[M-1] - p0 <= n.
+ * A window never reaches into the next document; at a document's end it is clamped.  Near(a, b, 1, ordered) is the
+ * phrase (a, b); with n >= the longest document the unordered form is the conjunction with multiplicities.  An id
+ * outside [0, n_terms) anywhere in a Near gives an empty list without reading anything.
+ * Outputs, status words, driver (the shortest posting list among the tokens, ties -> the first), bounds, launches and
+ * workspace are those of amdr_phrase_lists: amdr_span_lists_plan is the phrase plan's arithmetic, and a call whose items
+ * are all of kind 0 writes the bytes amdr_phrase_lists writes.  One wave walks one surviving document, 64 anchor
+ * positions per round, from a staged run of at most 64 + n tokens; worst case len x (n + 1) steps per document.
+ * amdr_span_lists_device only enqueues and allocates nothing (capturable); it refuses what amdr_phrase_lists_device
+ * refuses, and does not validate the operands' contents: an item with a kind outside 0 .. 2, a length outside its
+ * kind's range or a Near distance outside 1 .. 255 gets an empty list.  amdr_span_lists is the host-pointer twin: it
+ * validates (AMDR_EINVAL: item_ptr not starting at 0 or not monotone, a kind outside 0 .. 2, a phrase length outside
+ * 2 .. 16, a Near length outside 2 .. 8, a distance outside 1 .. 255), stages, runs on the BM25 handle's own stream under
+ * its mutex and returns the lists and the status array in the host buffers. */
+int amdr_span_lists_plan(int64_t n_items, int64_t cand_max, int64_t* work_bytes);
+int amdr_span_lists_device(amdr_bm25_t* bm25, const int64_t* item_ptr_dev, const int32_t* item_terms_dev,
+                           const int32_t* item_kind_dev, const int32_t* item_dist_dev, int64_t n_items, int64_t cand_max,
+                           int64_t rows_cap, int64_t* out_list_ptr_dev, int32_t* out_docs_dev, int32_t* out_status_dev,
+                           void* work_dev, int64_t work_bytes, void* stream);
+int amdr_span_lists(amdr_bm25_t* bm25, const int64_t* item_ptr, const int32_t* item_terms, const int32_t* item_kind,
+                    const int32_t* item_dist, int64_t n_items, int64_t cand_max, int64_t rows_cap, int64_t* out_list_ptr,
+                    int32_t* out_docs, int32_t* out_status);
+
 /* ---- multi-GPU: merge per-shard top-k after the RCCL all-gather --------
  * No reference counterpart (the reference is single-process).
  * parts: [n_parts, nq, k_in] scores + GLOBAL ids (-1 padding); output

@@ -66,6 +66,7 @@ SIGNATURES = {
     "amdr_term_scope": "P" + "P" * 7 + "l" * 5 + "PPP",
     "amdr_phrase_lists_plan": "llP", "amdr_phrase_lists_device": "PPP" + "lll" + "PPP" + "PlP", "amdr_phrase_lists": "PPP" + "lll" + "PPP",
     "amdr_term_scope_lists_device": "P" + "P" * 9 + "l" * 6 + "PPP" + "PlP", "amdr_term_scope_lists": "P" + "P" * 9 + "l" * 6 + "PPP",
+    "amdr_span_lists_plan": "llP", "amdr_span_lists_device": "PPPPP" + "lll" + "PPP" + "PlP", "amdr_span_lists": "PPPPP" + "lll" + "PPP",
 }
 EXPORTS = tuple(SIGNATURES)  # every symbol include/amdretrieval.h declares (checked by tests/test_abi.py)
 _KIND = {"P": C.c_void_p, "i": C.c_int32, "l": C.c_int64, "d": C.c_double}
@@ -221,6 +222,19 @@ def phrase_lists_plan(n_phr: int, cand_max: int) -> int:
     """Workspace bytes of BM25Index.phrase_lists_device(n_phr phrases, longest driver cand_max) — host-only arithmetic."""
     out = C.c_int64(0)
     _check(load().amdr_phrase_lists_plan(C.c_int64(n_phr), C.c_int64(cand_max), C.byref(out)), "amdr_phrase_lists_plan")
+    return int(out.value)
+
+
+NEAR_MAX_TERMS = 8    # tokens of a Near (kNearMaxTerms)
+NEAR_MAX_DIST = 255   # the largest distance of a Near (kNearMaxDist)
+SPAN_PHRASE, SPAN_NEAR_UNORDERED, SPAN_NEAR_ORDERED = 0, 1, 2  # the item kinds of amdr_span_lists (near_rule.hpp SpanKind)
+
+
+def span_lists_plan(n_items: int, cand_max: int) -> int:
+    """Workspace bytes of BM25Index.span_lists_device(n_items phrases and Nears, longest driver cand_max) — host-only
+    arithmetic, the phrase plan's."""
+    out = C.c_int64(0)
+    _check(load().amdr_span_lists_plan(C.c_int64(n_items), C.c_int64(cand_max), C.byref(out)), "amdr_span_lists_plan")
     return int(out.value)
 
 
@@ -732,6 +746,35 @@ class BM25Index(_Handle):
                                                C.c_int64(cand_max), C.c_int64(rows_cap), _vp(list_ptr_ptr), _vp(docs_ptr),
                                                _vp(status_ptr), _vp(work_ptr), C.c_int64(work_bytes), _vp(stream)),
                "amdr_phrase_lists_device")
+
+    # -- phrases and Nears side by side -> one array of virtual posting lists (amdr_span_lists) -----------------------
+    def span_lists(self, item_ptr, item_terms, item_kind, item_dist, cand_max: int, rows_cap: int):
+        """The host twin: (list_ptr i64 [n + 1], docs i32 [list_ptr[-1]], status i32 [n]) of the items
+        item_terms[item_ptr[p] : item_ptr[p + 1]] of kind item_kind[p] (0 phrase, 1 Near unordered, 2 Near ordered) and
+        distance item_dist[p] — each list the ascending documents that hold the item.  status as term_scope."""
+        pp, pt = _c(item_ptr, np.int64).ravel(), _c(item_terms, np.int32).ravel()
+        kd, ds = _c(item_kind, np.int32).ravel(), _c(item_dist, np.int32).ravel()
+        if pp.size < 1 or kd.size != pp.size - 1 or ds.size != pp.size - 1:
+            raise ValueError("span_lists: item_ptr [n + 1], item_kind [n], item_dist [n]")
+        n = pp.size - 1
+        lp = np.zeros(n + 1, dtype=np.int64)
+        docs = np.full(max(int(rows_cap), 1), -1, dtype=np.int32)
+        status = np.zeros(max(n, 1), dtype=np.int32)
+        pad = np.zeros(1, dtype=np.int32)
+        _check(load().amdr_span_lists(self._h, _p(pp, C.c_int64), _p(pt if pt.size else pad, C.c_int32),
+                                      _p(kd if n else pad, C.c_int32), _p(ds if n else pad, C.c_int32), C.c_int64(n),
+                                      C.c_int64(cand_max), C.c_int64(rows_cap), _p(lp, C.c_int64), _p(docs, C.c_int32),
+                                      _p(status, C.c_int32)), "amdr_span_lists")
+        return lp, docs[:int(lp[-1])], status[:n]
+
+    def span_lists_device(self, item_ptr_ptr: int, item_terms_ptr: int, item_kind_ptr: int, item_dist_ptr: int, n_items: int,
+                          cand_max: int, rows_cap: int, list_ptr_ptr: int, docs_ptr: int, status_ptr: int, work_ptr: int,
+                          work_bytes: int, stream: int = 0) -> None:
+        """The "_device" form: operands and outputs as device pointers; enqueues only."""
+        _check(load().amdr_span_lists_device(self._h, _vp(item_ptr_ptr), _vp(item_terms_ptr), _vp(item_kind_ptr),
+                                             _vp(item_dist_ptr), C.c_int64(n_items), C.c_int64(cand_max), C.c_int64(rows_cap),
+                                             _vp(list_ptr_ptr), _vp(docs_ptr), _vp(status_ptr), _vp(work_ptr),
+                                             C.c_int64(work_bytes), _vp(stream)), "amdr_span_lists_device")
 
     def get_scores(self, queries: Sequence[Sequence[int]]) -> np.ndarray:
         q_terms, q_ptr = self.pack_queries(queries)

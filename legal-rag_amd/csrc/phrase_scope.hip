@@ -22,9 +22,23 @@
 // the survivors of one tile, so one long document delays three others at most.
 // Every barrier sits under a block-uniform condition: the driver is computed by one thread and read from LDS by all, the
 // survivor count comes from the block scan, and the wave loop of phase 2 holds no barrier.
+//
+// Proximity (amdr_span_lists*: no reference counterpart either).  The same three launches take ITEMS of three kinds — a
+// phrase, a Near unordered, a Near ordered (near_rule.hpp) — so that the phrases and the Nears of one batch land in one
+// list array; amdr_phrase_lists* are the form in which every item is a phrase.  Driver, phase 1, the ranking, the scan and
+// the write are shared unchanged, which is why a Near lives in this file; only phase 2 differs.  For a Near one wave walks
+// one surviving document, 64 ANCHOR positions per round: the round's run tokens[base, base + 64 + n), clamped to the
+// document — at most kNearStage = 319 ints — is staged once per wave in LDS with coalesced loads (neighbouring lanes would
+// re-read almost the same tokens from memory), each lane scans at most n tokens behind its anchor from there, and a wave
+// vote ends the document at the first round with a hit.  A lane whose token is no member of the Near does nothing; why
+// that loses no match is near_rule.hpp's anchor argument.  The staging is traffic between the lanes of ONE wave, fenced for
+// the compiler alone, so phase 2 still holds no block barrier.  LDS grows by 4 x 319 ints = 5 104 B per block.
+// Worst case of a Near: one wave, len x (n + 1) steps for a document of len tokens in which every token is an anchor that
+// never completes (a 4 550-token document at n = 255: 1.16 M steps, 18 200 per lane); four waves share a tile's
+// survivors, so such a document delays at most the other survivors of its own tile.
 #include "bm25_handle.hpp"
 #include "compact.hpp"
-#include "phrase_rule.hpp"
+#include "near_rule.hpp"
 
 #include <memory>
 #include <mutex>
@@ -55,32 +69,52 @@ PhWork ph_work(int64_t n_phr, int64_t cand_max) {
   return w;
 }
 
-// The block's phrase and driver: the length by all, the tokens into LDS by the first L threads (a length outside
-// 2 .. kPhMaxLen reads none), the driver by thread 0; ends with a barrier.  Returns the phrase's length.
-__device__ __forceinline__ int ph_block_phrase(const PhIndex& I, const long long* __restrict__ phr_ptr,
-                                               const int* __restrict__ phr_terms, long p, int* terms, PhDriver* slot) {
-  const long long b = phr_ptr[p], L = phr_ptr[p + 1] - b;
-  const bool sized = L >= 2 && L <= kPhMaxLen;  // block-uniform
-  if (sized && threadIdx.x < L) terms[threadIdx.x] = phr_terms[b + threadIdx.x];
+// The items of a call: phrases and Nears side by side.  kind == nullptr: every item is a phrase (amdr_phrase_lists).
+struct SpanItems {
+  const long long* ptr;  // [n + 1]
+  const int* terms;      // [ptr[n]]
+  const int* kind;       // [n] SpanKind, or nullptr
+  const int* dist;       // [n]; read for a Near only
+};
+
+// The block's item and driver: the length, kind and distance by all, the tokens into LDS by the first L threads (an item
+// the rule does not define — span_sized — reads none), the driver by thread 0; ends with a barrier.  Returns the item's
+// length, 0 for an item the rule does not define.
+__device__ __forceinline__ int ph_block_phrase(const PhIndex& I, const SpanItems& S, long p, int* terms, PhDriver* slot,
+                                               int* kind_out, int* dist_out) {
+  const long long b = S.ptr[p], L = S.ptr[p + 1] - b;
+  const int kind = S.kind ? S.kind[p] : (int)kSpanPhrase;
+  const int dist = kind == kSpanPhrase || !S.dist ? 0 : S.dist[p];
+  const bool sized = span_sized(kind, L, dist);  // block-uniform
+  if (sized && threadIdx.x < L) terms[threadIdx.x] = S.terms[b + threadIdx.x];
   __syncthreads();
   if (threadIdx.x == 0) *slot = sized ? ph_driver(I, terms, L) : PhDriver{-1, -1, 0, 0};
   __syncthreads();
+  *kind_out = kind, *dist_out = dist;
   return sized ? (int)L : 0;
 }
 
-__global__ __launch_bounds__(kPhThreads) void phrase_count_kernel(PhIndex I, const long long* __restrict__ phr_ptr,
-                                                                 const int* __restrict__ phr_terms, long long cand_max,
+// LDS traffic between the lanes of ONE wave: the LDS unit serves a wave's operations in order, so only the compiler has
+// to be kept from moving them.
+__device__ __forceinline__ void ph_wave_lds_fence() {
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+}
+
+__global__ __launch_bounds__(kPhThreads) void phrase_count_kernel(PhIndex I, SpanItems S, long long cand_max,
                                                                  long long* __restrict__ counts, int* __restrict__ rank_out,
                                                                  int* __restrict__ status) {
   __shared__ PhDriver drv;
   __shared__ int terms[kPhMaxLen];
+  __shared__ int stage[kPhWaves][kNearStage];  // a Near's round: one staged token run per wave
   __shared__ unsigned short surv[kPhThreads];
   __shared__ unsigned char kept[kPhThreads];
   __shared__ int wsum[kPhWaves + 1];
   const long p = blockIdx.x;
   const long long tile = blockIdx.y, tiles = gridDim.y;
   const size_t cell = (size_t)p * tiles + tile;
-  const int L = ph_block_phrase(I, phr_ptr, phr_terms, p, terms, &drv);
+  int kind, dist;
+  const int L = ph_block_phrase(I, S, p, terms, &drv, &kind, &dist);
   const PhDriver D = drv;
   const bool over = D.len > cand_max;
   if (tile == 0 && threadIdx.x == 0) status[p] = over ? kTsCandOverflow : kTsOk;
@@ -102,10 +136,24 @@ __global__ __launch_bounds__(kPhThreads) void phrase_count_kernel(PhIndex I, con
   for (int s = wave; s < n_surv; s += kPhWaves) {
     const int t = surv[s];
     const long long doc = I.post_doc[D.begin + i0 + t];
-    const long long last = ph_last_start(I, doc, L);
     bool found = false;
-    for (long long base = I.doc_ptr[doc]; base <= last && !found; base += kPhLanes)  // wave-uniform
-      found = __ballot(ph_lane_hit(I, terms, L, base, lane, last)) != 0;
+    if (kind == kSpanPhrase) {  // block-uniform
+      const long long last = ph_last_start(I, doc, L);
+      for (long long base = I.doc_ptr[doc]; base <= last && !found; base += kPhLanes)  // wave-uniform
+        found = __ballot(ph_lane_hit(I, terms, L, base, lane, last)) != 0;
+    } else {
+      // A Near: 64 anchors per round; the round's run [base, base + 64 + dist), clamped to the document, goes through
+      // LDS once with coalesced loads and every lane scans its window from there.
+      const long long end = I.doc_ptr[doc + 1];
+      int* run = stage[wave];
+      for (long long base = I.doc_ptr[doc]; base < end && !found; base += kPhLanes) {  // wave-uniform
+        const int len = near_run_len(base, end, dist);  // <= kNearStage; base + len <= end
+        for (int j = lane; j < len; j += kPhLanes) run[j] = I.tokens[base + j];
+        ph_wave_lds_fence();
+        found = __ballot(near_lane_hit(run, len, lane, terms, L, kind == kSpanNearOrdered, dist)) != 0;
+        ph_wave_lds_fence();  // (the next round overwrites the run)
+      }
+    }
     if (lane == 0) kept[t] = found ? 1 : 0;
   }
   __syncthreads();
@@ -116,8 +164,7 @@ __global__ __launch_bounds__(kPhThreads) void phrase_count_kernel(PhIndex I, con
   if (threadIdx.x == 0) counts[cell] = total;
 }
 
-__global__ __launch_bounds__(kPhThreads) void phrase_write_kernel(PhIndex I, const long long* __restrict__ phr_ptr,
-                                                                 const int* __restrict__ phr_terms, long long cand_max,
+__global__ __launch_bounds__(kPhThreads) void phrase_write_kernel(PhIndex I, SpanItems S, long long cand_max,
                                                                  long n_phr, long long rows_cap,
                                                                  const long long* __restrict__ offsets,
                                                                  const int* __restrict__ rank_in,
@@ -134,7 +181,8 @@ __global__ __launch_bounds__(kPhThreads) void phrase_write_kernel(PhIndex I, con
     if (p == n_phr - 1) list_ptr[n_phr] = e < rows_cap ? e : rows_cap;
     if (e > b && e > rows_cap) status[p] = kTsRowsOverflow;  // (a phrase over cand_max has no row: its 1 stays)
   }
-  (void)ph_block_phrase(I, phr_ptr, phr_terms, p, terms, &drv);
+  int kind, dist;
+  (void)ph_block_phrase(I, S, p, terms, &drv, &kind, &dist);
   const PhDriver D = drv;
   const long long i0 = tile * kPhTile;
   if (D.len > cand_max || i0 >= D.len) return;  // block-uniform
@@ -150,8 +198,8 @@ struct PhOut {
   int* status;
 };
 
-int ph_launch(const PhIndex& I, const long long* phr_ptr, const int* phr_terms, int64_t n_phr, int64_t cand_max,
-              int64_t rows_cap, const PhOut& o, unsigned char* work, hipStream_t st) {
+int ph_launch(const PhIndex& I, const SpanItems& S, int64_t n_phr, int64_t cand_max, int64_t rows_cap, const PhOut& o,
+              unsigned char* work, hipStream_t st) {
   if (n_phr == 0) {
     AMDR_HIP(hipMemsetAsync(o.list_ptr, 0, sizeof(long long), st));
     return AMDR_OK;
@@ -162,15 +210,13 @@ int ph_launch(const PhIndex& I, const long long* phr_ptr, const int* phr_terms, 
   long long* offsets = reinterpret_cast<long long*>(work + w.off_offsets);
   int* rank = reinterpret_cast<int*>(work + w.off_rank);
   const dim3 grid((unsigned)n_phr, (unsigned)tiles);
-  hipLaunchKernelGGL(phrase_count_kernel, grid, dim3(kPhThreads), 0, st, I, phr_ptr, phr_terms, (long long)cand_max, counts,
-                     rank, o.status);
+  hipLaunchKernelGGL(phrase_count_kernel, grid, dim3(kPhThreads), 0, st, I, S, (long long)cand_max, counts, rank, o.status);
   AMDR_HIP(hipGetLastError());
   hipLaunchKernelGGL(compact_scan_i64_kernel, dim3(1), dim3(kCompactScanThreads), 0, st, (const long long*)counts,
                      (long)(n_phr * tiles), offsets);
   AMDR_HIP(hipGetLastError());
-  hipLaunchKernelGGL(phrase_write_kernel, grid, dim3(kPhThreads), 0, st, I, phr_ptr, phr_terms, (long long)cand_max,
-                     (long)n_phr, (long long)rows_cap, (const long long*)offsets, (const int*)rank, o.list_ptr, o.docs,
-                     o.status);
+  hipLaunchKernelGGL(phrase_write_kernel, grid, dim3(kPhThreads), 0, st, I, S, (long long)cand_max, (long)n_phr,
+                     (long long)rows_cap, (const long long*)offsets, (const int*)rank, o.list_ptr, o.docs, o.status);
   AMDR_HIP(hipGetLastError());
   return AMDR_OK;
 }
@@ -187,6 +233,80 @@ int ph_check_sizes(const char* who, int64_t n_phr, int64_t cand_max, int64_t row
 PhIndex ph_index(const amdr_bm25* h) {
   const BmIndex& ix = h->ix;
   return PhIndex{ix.term_ptr, ix.post_doc, (long)ix.n_terms, (long)ix.n_docs, h->tok_ptr, h->tok};
+}
+
+// The "_device" entry of phrases (S.kind == nullptr) and of mixed items: checks, then enqueues.
+int span_device(const char* who, amdr_bm25_t* bm25, const SpanItems& S, int64_t n, int64_t cand_max, int64_t rows_cap,
+                int64_t* out_list_ptr_dev, int32_t* out_docs_dev, int32_t* out_status_dev, void* work_dev, int64_t work_bytes,
+                void* stream, bool mixed) {
+  AMDR_REQUIRE(bm25 != nullptr, "%s: null handle", who);
+  int rc = ph_check_sizes(who, n, cand_max, rows_cap);
+  if (rc) return rc;
+  AMDR_REQUIRE(bm25->has_tokens, "%s: no token stream is resident (amdr_bm25_set_tokens; an update drops it)", who);
+  AMDR_REQUIRE(out_list_ptr_dev != nullptr, "%s: null out_list_ptr", who);
+  AMDR_REQUIRE(n == 0 || (S.ptr && S.terms && out_status_dev && (!mixed || (S.kind && S.dist))), "%s: null operand", who);
+  AMDR_REQUIRE(rows_cap == 0 || out_docs_dev, "%s: null out_docs", who);
+  AMDR_REQUIRE(work_bytes >= 0, "%s: work_bytes=%lld", who, (long long)work_bytes);
+  const size_t need = n ? ph_work(n, cand_max).total : 0;
+  AMDR_REQUIRE((size_t)work_bytes >= need && (need == 0 || work_dev), "%s: a workspace of %lld bytes, the plan asks for %zu", who,
+               (long long)work_bytes, need);
+  AMDR_HIP(hipSetDevice(bm25->device));
+  const PhOut o{(long long*)out_list_ptr_dev, out_docs_dev, out_status_dev};
+  return ph_launch(ph_index(bm25), S, n, cand_max, rows_cap, o, static_cast<unsigned char*>(work_dev), (hipStream_t)stream);
+}
+
+// The host-pointer twin of both: validates, stages, resolves on the handle's stream, synchronises.  S holds host arrays.
+int span_host(const char* who, amdr_bm25_t* bm25, const SpanItems& S, int64_t n, int64_t cand_max, int64_t rows_cap,
+              int64_t* out_list_ptr, int32_t* out_docs, int32_t* out_status, bool mixed) {
+  AMDR_REQUIRE(bm25 != nullptr, "%s: null handle", who);
+  int rc = ph_check_sizes(who, n, cand_max, rows_cap);
+  if (rc) return rc;
+  AMDR_REQUIRE(out_list_ptr != nullptr, "%s: null out_list_ptr", who);
+  AMDR_REQUIRE(n == 0 || out_status, "%s: null out_status", who);
+  AMDR_REQUIRE(rows_cap == 0 || out_docs, "%s: null out_docs", who);
+  std::lock_guard<std::mutex> g(bm25->mu);
+  AMDR_REQUIRE(bm25->has_tokens, "%s: no token stream is resident (amdr_bm25_set_tokens; an update drops it)", who);
+  const int bad = mixed ? span_validate((const int64_t*)S.ptr, S.terms, S.kind, S.dist, n)
+                        : ph_validate((const int64_t*)S.ptr, S.terms, n);
+  AMDR_REQUIRE(bad == kPhValid, "%s: %s", who, mixed ? span_error_text(bad) : ph_error_text(bad));
+  if (n == 0) {
+    out_list_ptr[0] = 0;
+    return AMDR_OK;
+  }
+  AMDR_HIP(hipSetDevice(bm25->device));
+  // Layout of the staging buffer: item_ptr | item_terms | list_ptr | docs | status | kind | dist | the workspace, each aligned.
+  const size_t n_all = (size_t)S.ptr[n];
+  size_t at[8], total = 0;
+  at[0] = total, total += ph_align((size_t)(n + 1) * 8);
+  at[1] = total, total += ph_align(n_all * 4);
+  at[2] = total, total += ph_align((size_t)(n + 1) * 8);
+  at[3] = total, total += ph_align((size_t)rows_cap * 4);
+  at[4] = total, total += ph_align((size_t)n * 4);
+  at[5] = total, total += mixed ? ph_align((size_t)n * 4) : 0;
+  at[6] = total, total += mixed ? ph_align((size_t)n * 4) : 0;
+  at[7] = total, total += ph_work(n, cand_max).total;
+  if ((rc = bm25->tscope.ensure(total))) return rc;
+  unsigned char* p = bm25->tscope.as<unsigned char>();
+  hipStream_t st = bm25->stream;
+  AMDR_HIP(hipMemcpyAsync(p + at[0], S.ptr, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, st));
+  AMDR_HIP(hipMemcpyAsync(p + at[1], S.terms, n_all * 4, hipMemcpyHostToDevice, st));
+  if (mixed) {
+    AMDR_HIP(hipMemcpyAsync(p + at[5], S.kind, (size_t)n * 4, hipMemcpyHostToDevice, st));
+    AMDR_HIP(hipMemcpyAsync(p + at[6], S.dist, (size_t)n * 4, hipMemcpyHostToDevice, st));
+  }
+  const SpanItems dev{(const long long*)(p + at[0]), (const int*)(p + at[1]), mixed ? (const int*)(p + at[5]) : nullptr,
+                      mixed ? (const int*)(p + at[6]) : nullptr};
+  const PhOut o{(long long*)(p + at[2]), (int*)(p + at[3]), (int*)(p + at[4])};
+  if ((rc = ph_launch(ph_index(bm25), dev, n, cand_max, rows_cap, o, p + at[7], st))) return rc;
+  AMDR_HIP(hipMemcpyAsync(out_list_ptr, o.list_ptr, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, st));
+  AMDR_HIP(hipMemcpyAsync(out_status, o.status, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+  AMDR_HIP(hipStreamSynchronize(st));
+  const int64_t used = out_list_ptr[n];  // <= rows_cap: only the documents the lists name come back
+  if (used > 0) {
+    AMDR_HIP(hipMemcpyAsync(out_docs, o.docs, (size_t)used * 4, hipMemcpyDeviceToHost, st));
+    AMDR_HIP(hipStreamSynchronize(st));
+  }
+  return AMDR_OK;
 }
 
 }  // namespace
@@ -250,70 +370,43 @@ int amdr_phrase_lists_plan(int64_t n_phr, int64_t cand_max, int64_t* work_bytes)
   return AMDR_OK;
 }
 
+
 int amdr_phrase_lists_device(amdr_bm25_t* bm25, const int64_t* phr_ptr_dev, const int32_t* phr_terms_dev, int64_t n_phr,
                              int64_t cand_max, int64_t rows_cap, int64_t* out_list_ptr_dev, int32_t* out_docs_dev,
                              int32_t* out_status_dev, void* work_dev, int64_t work_bytes, void* stream) {
-  AMDR_REQUIRE(bm25 != nullptr, "phrase_lists: null handle");
-  int rc = ph_check_sizes("phrase_lists", n_phr, cand_max, rows_cap);
-  if (rc) return rc;
-  AMDR_REQUIRE(bm25->has_tokens, "phrase_lists: no token stream is resident (amdr_bm25_set_tokens; an update drops it)");
-  AMDR_REQUIRE(out_list_ptr_dev != nullptr, "phrase_lists: null out_list_ptr");
-  AMDR_REQUIRE(n_phr == 0 || (phr_ptr_dev && phr_terms_dev && out_status_dev), "phrase_lists: null operand");
-  AMDR_REQUIRE(rows_cap == 0 || out_docs_dev, "phrase_lists: null out_docs");
-  AMDR_REQUIRE(work_bytes >= 0, "phrase_lists: work_bytes=%lld", (long long)work_bytes);
-  const size_t need = n_phr ? ph_work(n_phr, cand_max).total : 0;
-  AMDR_REQUIRE((size_t)work_bytes >= need && (need == 0 || work_dev), "phrase_lists: a workspace of %lld bytes, the plan asks for %zu",
-               (long long)work_bytes, need);
-  AMDR_HIP(hipSetDevice(bm25->device));
-  const PhOut o{(long long*)out_list_ptr_dev, out_docs_dev, out_status_dev};
-  return ph_launch(ph_index(bm25), (const long long*)phr_ptr_dev, phr_terms_dev, n_phr, cand_max, rows_cap, o,
-                   static_cast<unsigned char*>(work_dev), (hipStream_t)stream);
+  const SpanItems S{(const long long*)phr_ptr_dev, phr_terms_dev, nullptr, nullptr};
+  return span_device("phrase_lists", bm25, S, n_phr, cand_max, rows_cap, out_list_ptr_dev, out_docs_dev, out_status_dev,
+                     work_dev, work_bytes, stream, false);
 }
 
 int amdr_phrase_lists(amdr_bm25_t* bm25, const int64_t* phr_ptr, const int32_t* phr_terms, int64_t n_phr, int64_t cand_max,
                       int64_t rows_cap, int64_t* out_list_ptr, int32_t* out_docs, int32_t* out_status) {
-  AMDR_REQUIRE(bm25 != nullptr, "phrase_lists: null handle");
-  int rc = ph_check_sizes("phrase_lists", n_phr, cand_max, rows_cap);
+  const SpanItems S{(const long long*)phr_ptr, phr_terms, nullptr, nullptr};
+  return span_host("phrase_lists", bm25, S, n_phr, cand_max, rows_cap, out_list_ptr, out_docs, out_status, false);
+}
+
+int amdr_span_lists_plan(int64_t n_items, int64_t cand_max, int64_t* work_bytes) {
+  AMDR_REQUIRE(work_bytes != nullptr, "span_lists_plan: null");
+  int rc = ph_check_sizes("span_lists_plan", n_items, cand_max, 0);
   if (rc) return rc;
-  AMDR_REQUIRE(out_list_ptr != nullptr, "phrase_lists: null out_list_ptr");
-  AMDR_REQUIRE(n_phr == 0 || out_status, "phrase_lists: null out_status");
-  AMDR_REQUIRE(rows_cap == 0 || out_docs, "phrase_lists: null out_docs");
-  std::lock_guard<std::mutex> g(bm25->mu);
-  AMDR_REQUIRE(bm25->has_tokens, "phrase_lists: no token stream is resident (amdr_bm25_set_tokens; an update drops it)");
-  const int bad = ph_validate(phr_ptr, phr_terms, n_phr);
-  AMDR_REQUIRE(bad == kPhValid, "phrase_lists: %s", ph_error_text(bad));
-  if (n_phr == 0) {
-    out_list_ptr[0] = 0;
-    return AMDR_OK;
-  }
-  AMDR_HIP(hipSetDevice(bm25->device));
-  // Layout of the staging buffer: phr_ptr | phr_terms | list_ptr | docs | status | the workspace, each aligned.
-  const size_t n_all = (size_t)phr_ptr[n_phr];
-  size_t at[6], total = 0;
-  at[0] = total, total += ph_align((size_t)(n_phr + 1) * 8);
-  at[1] = total, total += ph_align(n_all * 4);
-  at[2] = total, total += ph_align((size_t)(n_phr + 1) * 8);
-  at[3] = total, total += ph_align((size_t)rows_cap * 4);
-  at[4] = total, total += ph_align((size_t)n_phr * 4);
-  at[5] = total, total += ph_work(n_phr, cand_max).total;
-  if ((rc = bm25->tscope.ensure(total))) return rc;
-  unsigned char* p = bm25->tscope.as<unsigned char>();
-  hipStream_t st = bm25->stream;
-  AMDR_HIP(hipMemcpyAsync(p + at[0], phr_ptr, (size_t)(n_phr + 1) * 8, hipMemcpyHostToDevice, st));
-  AMDR_HIP(hipMemcpyAsync(p + at[1], phr_terms, n_all * 4, hipMemcpyHostToDevice, st));
-  const PhOut o{(long long*)(p + at[2]), (int*)(p + at[3]), (int*)(p + at[4])};
-  if ((rc = ph_launch(ph_index(bm25), (const long long*)(p + at[0]), (const int*)(p + at[1]), n_phr, cand_max, rows_cap, o,
-                      p + at[5], st)))
-    return rc;
-  AMDR_HIP(hipMemcpyAsync(out_list_ptr, o.list_ptr, (size_t)(n_phr + 1) * 8, hipMemcpyDeviceToHost, st));
-  AMDR_HIP(hipMemcpyAsync(out_status, o.status, (size_t)n_phr * 4, hipMemcpyDeviceToHost, st));
-  AMDR_HIP(hipStreamSynchronize(st));
-  const int64_t used = out_list_ptr[n_phr];  // <= rows_cap: only the documents the lists name come back
-  if (used > 0) {
-    AMDR_HIP(hipMemcpyAsync(out_docs, o.docs, (size_t)used * 4, hipMemcpyDeviceToHost, st));
-    AMDR_HIP(hipStreamSynchronize(st));
-  }
+  *work_bytes = (int64_t)ph_work(n_items, cand_max).total;
   return AMDR_OK;
+}
+
+int amdr_span_lists_device(amdr_bm25_t* bm25, const int64_t* item_ptr_dev, const int32_t* item_terms_dev,
+                           const int32_t* item_kind_dev, const int32_t* item_dist_dev, int64_t n_items, int64_t cand_max,
+                           int64_t rows_cap, int64_t* out_list_ptr_dev, int32_t* out_docs_dev, int32_t* out_status_dev,
+                           void* work_dev, int64_t work_bytes, void* stream) {
+  const SpanItems S{(const long long*)item_ptr_dev, item_terms_dev, item_kind_dev, item_dist_dev};
+  return span_device("span_lists", bm25, S, n_items, cand_max, rows_cap, out_list_ptr_dev, out_docs_dev, out_status_dev,
+                     work_dev, work_bytes, stream, true);
+}
+
+int amdr_span_lists(amdr_bm25_t* bm25, const int64_t* item_ptr, const int32_t* item_terms, const int32_t* item_kind,
+                    const int32_t* item_dist, int64_t n_items, int64_t cand_max, int64_t rows_cap, int64_t* out_list_ptr,
+                    int32_t* out_docs, int32_t* out_status) {
+  const SpanItems S{(const long long*)item_ptr, item_terms, item_kind, item_dist};
+  return span_host("span_lists", bm25, S, n_items, cand_max, rows_cap, out_list_ptr, out_docs, out_status, true);
 }
 
 }  // extern "C"

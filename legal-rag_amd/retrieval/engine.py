@@ -246,14 +246,21 @@ class HybridEngine:
         A table with phrases (table.n_phr > 0): the phrase step (amdr_phrase_lists_device, three launches) is enqueued
         first on the same stream and the term step reads its lists as the terms n_terms + p (amdr_term_scope_lists_device);
         the BM25 handle must hold the token stream (BM25Index.set_tokens).  The status tensor is then i32 [n_cons + n_phr]:
-        the constraints' words, then the phrases'."""
+        the constraints' words, then the phrases'.
+        A table with Nears (table.n_near > 0): ONE span step (amdr_span_lists_device, the same three launches) takes the
+        phrase step's place — the phrases go first as kind 0, then the Nears, into one list array — and the status tensor
+        is i32 [n_cons + n_phr + n_near].  Without a Near the calls are those above."""
         self.check_term_scopes()
         n_cons, cand_max, rows_cap = int(table.n_cons), int(table.cand_max), int(table.rows_cap)
         n_phr = int(getattr(table, "n_phr", 0))
+        n_near = int(getattr(table, "n_near", 0))
         order = (0, 2, 4, 5, 1, 3, 6)  # the i64 arrays first: every one starts on a multiple of its item size
         parts = [(i, np.ascontiguousarray(table.ops[i], dtype=t).view(np.uint8))
                  for i, t in ((i, _native.BM25Index.TERM_OPS[i]) for i in order)]
-        if n_phr:
+        if n_near:  # the items of the one span step: the phrases as kind 0, then the Nears
+            parts.insert(4, (8, np.ascontiguousarray(table.span_ops[0], dtype=np.int64).view(np.uint8)))
+            parts.extend((9 + j, np.ascontiguousarray(table.span_ops[1 + j], dtype=np.int32).view(np.uint8)) for j in range(3))
+        elif n_phr:
             parts.insert(4, (8, np.ascontiguousarray(table.phr_ops[0], dtype=np.int64).view(np.uint8)))
             parts.append((9, np.ascontiguousarray(table.phr_ops[1], dtype=np.int32).view(np.uint8)))
         parts.append((7, np.ascontiguousarray(table.qscope, dtype=np.int32).view(np.uint8)))
@@ -267,9 +274,20 @@ class HybridEngine:
         self._send(host, dev, ev, max(total, 8))
         base = dev.data_ptr()
         o_rows, o_status = 8 * (n_cons + 1), 8 * (n_cons + 1) + 8 * rows_cap
-        out = self._grown("tso", o_status + 4 * (n_cons + n_phr) + 8)
+        n_x = n_phr + n_near  # the virtual lists of the term step
+        out = self._grown("tso", o_status + 4 * (n_cons + n_x) + 8)
         lists = None
-        if n_phr:  # the phrase step: its lists are the virtual terms of the term step behind it
+        if n_near:  # the span step: phrases and Nears into ONE list array
+            p_max, p_cap = int(table.span_cand_max), int(table.span_rows_cap)
+            o_docs = 8 * (n_x + 1)
+            pout = self._grown("pho", o_docs + 4 * p_cap + 8)
+            p_bytes = _native.span_lists_plan(n_x, p_max)
+            pwork = self._grown("phw", p_bytes)
+            self.bm25.span_lists_device(base + where[8][0], base + where[9][0], base + where[10][0], base + where[11][0],
+                                        n_x, p_max, p_cap, pout.data_ptr(), pout.data_ptr() + o_docs,
+                                        out.data_ptr() + o_status + 4 * n_cons, pwork.data_ptr(), p_bytes, _stream())
+            lists = (pout.data_ptr(), pout.data_ptr() + o_docs, n_x)
+        elif n_phr:  # the phrase step: its lists are the virtual terms of the term step behind it
             p_max, p_cap = int(table.phr_cand_max), int(table.phr_rows_cap)
             o_docs = 8 * (n_phr + 1)
             pout = self._grown("pho", o_docs + 4 * p_cap + 8)
@@ -286,7 +304,7 @@ class HybridEngine:
                                     work.data_ptr(), work_bytes, _stream(), lists=lists)
         q0, qn = where[7]
         return ((out[:o_rows].view(torch.int64), out[o_rows:o_status].view(torch.int64), dev[q0:q0 + qn].view(torch.int32),
-                 n_cons, cand_max), out[o_status:o_status + 4 * (n_cons + n_phr)].view(torch.int32))
+                 n_cons, cand_max), out[o_status:o_status + 4 * (n_cons + n_x)].view(torch.int32))
 
     def upload_text(self, ptrs, lens, total: int):
         """Query texts (UTF-8 pointer / length arrays, _native.utf8_views) -> (blob u8 [total], offs i64 [n + 1]) on the

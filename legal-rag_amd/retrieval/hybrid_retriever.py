@@ -41,7 +41,7 @@ from .diversity import Diversity, resolve as _resolve_diversity
 from .graph_retriever import GraphRetriever
 from .rerankers import RerankerFactory, _to_doc_text
 from .scope import Scope, resolver_for
-from .terms import Phrase, Terms, pack as _pack_terms
+from .terms import Near, Phrase, Terms, pack as _pack_terms
 
 logger = logging.getLogger("legalrag.retrieval.hybrid_retriever")
 
@@ -238,7 +238,15 @@ class HybridRetriever:
         if tt.cand_max == 0:
             return np.zeros(0, dtype=np.int64)
         lists = None
-        if tt.n_phr:  # the phrases first, into their own document lists: the virtual terms of the constraint
+        if tt.n_near:  # phrases and Nears in one span step, into one array of document lists
+            bm.ensure_token_stream()
+            lp, docs, p_status = bm.gpu_index().span_lists(*tt.span_ops, tt.span_cand_max, tt.span_rows_cap)
+            if p_status.any():
+                p = int(np.flatnonzero(p_status)[0])
+                raise RuntimeError(f"{who}(terms=): {tt.span_item(p)!r} overflowed its bound (status {int(p_status[p])}); the "
+                                   f"host model and the resident BM25 index disagree")
+            lists = (lp, docs)
+        elif tt.n_phr:  # the phrases first, into their own document lists: the virtual terms of the constraint
             bm.ensure_token_stream()
             lp, docs, p_status = bm.gpu_index().phrase_lists(tt.phr_ops[0], tt.phr_ops[1], tt.phr_cand_max, tt.phr_rows_cap)
             if p_status.any():
@@ -263,6 +271,15 @@ class HybridRetriever:
         if not toks:
             raise ValueError(f"phrase(): {text_!r} holds no token")
         return Phrase(*toks)
+
+    def near(self, text_: str, distance: int, ordered: bool = False) -> Near:
+        """The Near of a string, cut by the BM25 index's DOCUMENT-side tokeniser as phrase() cuts it:
+        retriever.near("Buyer Seller", distance=5) == Near("buyer", "seller", distance=5).  ValueError for a string with
+        fewer than 2 or more than 8 tokens, a distance outside 1 .. 255, or on an index that records no tokeniser."""
+        bm = self.bm25
+        if not isinstance(bm, BM25Retriever):
+            raise ValueError("near(): proximity constraints need this package's own BM25 retriever")
+        return Near(*bm.document_tokens(text_), distance=distance, ordered=ordered)
 
     def _search_scoped(self, who: str, chunks, scope: Optional[Scope], top_k: int, refusal: Optional[str], device, twin: str,
                        operands, terms: Optional[Terms] = None):
@@ -938,7 +955,7 @@ class HybridRetriever:
                 bad = np.flatnonzero(status[0].numpy().view(np.int32))
                 if bad.size and int(bad[0]) >= int(term_table.n_cons):  # the phrases' words stand behind the constraints'
                     p = int(bad[0]) - int(term_table.n_cons)
-                    raise RuntimeError(f"{term_table.phrases[p]!r} of the batch overflowed its bound (status "
+                    raise RuntimeError(f"{term_table.span_item(p)!r} of the batch overflowed its bound (status "
                                        f"{int(status[0].numpy().view(np.int32)[bad[0]])}: 1 = candidates beyond cand_max, "
                                        f"2 = documents beyond rows_cap); the host model and the resident BM25 index disagree")
                 if bad.size:
@@ -1080,8 +1097,8 @@ class HybridRetriever:
             term_table = _pack_terms([(scopes[i] if scopes is not None else None, terms[i] or Terms()) for i in idxs],
                                      model.vocab(), model._doc_frequencies(), int(model.corpus_size),
                                      resolver_for(store.chunks).rows)
-            if term_table.n_phr:
-                bm.ensure_token_stream()  # (made lazily: on the first phrase, and again after a live update)
+            if term_table.n_phr or term_table.n_near:
+                bm.ensure_token_stream()  # (made lazily: on the first phrase or Near, and again after a live update)
         elif scoped:
             table = resolver_for(store.chunks).table([scopes[i] for i in idxs])
         host, extra = self._run(prep, params, eff, fetch, after, table, mmr, term_table)

@@ -12,6 +12,11 @@ A `Phrase` is an exact token SEQUENCE: Phrase("security", "interest") names the 
 each other in that order.  It stands wherever a token stands.  The GPU resolves each phrase of a batch from the resident
 token stream into an ascending document list of its own (amdr_phrase_lists, csrc/phrase_scope.hip), and the term step
 reads that list as one more term.
+
+A `Near` is PROXIMITY: Near("buyer", "seller", distance=5) names the chunks that hold the two words within five tokens of
+each other, in either order (ordered=True: in the order given) — looser than a phrase, stricter than a conjunction.  It
+stands wherever a token or a Phrase stands, and the GPU resolves the phrases and the Nears of a batch in one step into one
+array of document lists (amdr_span_lists).
 """
 from __future__ import annotations
 
@@ -25,6 +30,8 @@ from .scope import Scope
 MUST, ANY, NOT = 0, 1, 2  # the group kinds of the ABI (term_scope_rule.hpp TsKind)
 
 PHRASE_MAX_LEN = 16  # tokens of a phrase (phrase_rule.hpp kPhMaxLen)
+NEAR_MAX_TERMS = 8   # tokens of a Near (near_rule.hpp kNearMaxTerms)
+NEAR_MAX_DIST = 255  # the largest distance of a Near (near_rule.hpp kNearMaxDist)
 
 
 class Phrase:
@@ -70,11 +77,96 @@ class Phrase:
         return any(tuple(tokens[p:p + L]) == want for p in range(len(tokens) - L + 1))
 
 
-Member = Union[str, Phrase]
+class Near:
+    """Proximity: a chunk holds Near(t0, t1, ..., distance=n) when its text, as the index's tokeniser cuts it, has the
+    tokens close together (never across two chunks).
+      ordered=False  some run of at most n + 1 consecutive tokens contains every distinct token at least as many times as
+                     the Near names it: Near("a", "a", "b", distance=5) needs two a and one b inside one window; for two
+                     different tokens at positions p and q this is |q - p| <= n.
+      ordered=True   there are positions p0 < p1 < ... with the tokens in the order given and the last at most n behind
+                     the first.
+    2 to 8 tokens and 1 <= distance <= 255 (ValueError otherwise); repeats are allowed and are meaningful.  Accepted
+    wherever a token or a Phrase is: as an entry of a Terms field or as a member of a tuple group; its members are tokens,
+    not phrases.  Near(a, b, distance=1, ordered=True) names the chunks Phrase(a, b) names.  Tokens are compared exactly,
+    as a Terms' are (HybridRetriever.near cuts a string with the index's own tokeniser).  Frozen and hashable: equal Nears
+    are equal and hash alike."""
+    __slots__ = ("tokens", "distance", "ordered")
+
+    def __init__(self, *tokens: str, distance: int, ordered: bool = False) -> None:
+        if not 2 <= len(tokens) <= NEAR_MAX_TERMS:
+            raise ValueError(f"Near: 2 to {NEAR_MAX_TERMS} tokens, got {len(tokens)}")
+        for t in tokens:
+            if not isinstance(t, str):
+                raise TypeError(f"Near: a token is a str, got {type(t).__name__}")
+        if isinstance(distance, bool) or not isinstance(distance, (int, np.integer)):
+            raise TypeError(f"Near: distance is an int, got {type(distance).__name__}")
+        if not 1 <= int(distance) <= NEAR_MAX_DIST:
+            raise ValueError(f"Near: a distance of 1 to {NEAR_MAX_DIST}, got {int(distance)}")
+        object.__setattr__(self, "tokens", tuple(tokens))
+        object.__setattr__(self, "distance", int(distance))
+        object.__setattr__(self, "ordered", bool(ordered))
+
+    def __setattr__(self, name, value) -> None:
+        raise AttributeError("Near is frozen")
+
+    def __delattr__(self, name) -> None:
+        raise AttributeError("Near is frozen")
+
+    def _key(self):
+        return (self.tokens, self.distance, self.ordered)
+
+    def __eq__(self, other) -> bool:
+        return isinstance(other, Near) and self._key() == other._key()
+
+    def __hash__(self) -> int:
+        return hash(("Near",) + self._key())
+
+    def __len__(self) -> int:
+        return len(self.tokens)
+
+    def __repr__(self) -> str:
+        return ("Near(" + ", ".join(repr(t) for t in self.tokens) + f", distance={self.distance}"
+                + (", ordered=True" if self.ordered else "") + ")")
+
+    def __reduce__(self):
+        return (_make_near, (self.tokens, self.distance, self.ordered))
+
+    def within(self, tokens: Sequence[str]) -> bool:
+        """Whether the token sequence `tokens` holds this Near (the plain scan of every window)."""
+        n, want = self.distance, self.tokens
+        if not set(want) <= set(tokens):  # (a sequence that lacks a token has no such window)
+            return False
+        for s in range(len(tokens)):
+            win = tokens[s:s + n + 1]
+            if self.ordered:
+                if win[0] != want[0]:  # (the span is measured from the first token's position)
+                    continue
+                j = 0
+                for t in win:
+                    if t == want[j]:
+                        j += 1
+                        if j == len(want):
+                            return True
+            else:
+                have: Dict[str, int] = {}
+                for t in win:
+                    have[t] = have.get(t, 0) + 1
+                if all(have.get(t, 0) >= want.count(t) for t in want):
+                    return True
+        return False
+
+
+def _make_near(tokens, distance, ordered) -> Near:
+    return Near(*tokens, distance=distance, ordered=ordered)
+
+
+Member = Union[str, Phrase, Near]
 Group = Tuple[Member, ...]
 
 
 def _member(t) -> Member:
+    if isinstance(t, Near):
+        return t
     if isinstance(t, Phrase):
         return t.tokens[0] if len(t) == 1 else t  # one token is the plain term
     return str(t)
@@ -83,11 +175,11 @@ def _member(t) -> Member:
 def _groups(x, field: str) -> Optional[Tuple[Group, ...]]:
     if x is None:
         return None
-    if isinstance(x, (str, Phrase)):
+    if isinstance(x, (str, Phrase, Near)):
         x = (x,)
     out: List[Group] = []
     for e in x:
-        g = (_member(e),) if isinstance(e, (str, Phrase)) else tuple(_member(t) for t in e)
+        g = (_member(e),) if isinstance(e, (str, Phrase, Near)) else tuple(_member(t) for t in e)
         if not g:
             raise ValueError(f"Terms.{field}: an empty group names no token")
         out.append(g)
@@ -98,7 +190,8 @@ def _groups(x, field: str) -> Optional[Tuple[Group, ...]]:
 class Terms:
     """What a chunk's text must contain.  An entry is one vocabulary token (`str`) or a tuple of tokens, one GROUP: a
     chunk satisfies a group when it holds EVERY token of it, anywhere — a conjunction.  The tokens next to each other
-    in order are a `Phrase`, which stands wherever a token stands: as an entry, or inside a tuple group.  For a
+    in order are a `Phrase`, the tokens within a distance of each other a `Near`; either stands wherever a token stands:
+    as an entry, or inside a tuple group.  For a
     char-cut Han index a word is the phrase of its characters, Phrase("合", "同") (the group ("合", "同") also names
     every chunk that holds 同 … 合).
       all_of   every entry must be satisfied (each entry is a MUST group);
@@ -131,16 +224,21 @@ class Terms:
     def has_phrase(self) -> bool:
         return any(isinstance(t, Phrase) for _, g in self.groups() for t in g)
 
+    @property
+    def has_near(self) -> bool:
+        return any(isinstance(t, Near) for _, g in self.groups() for t in g)
+
     def matches(self, tokens) -> bool:
         """The rule on one document's tokens (host check; the kernels apply term_scope_rule.hpp and phrase_rule.hpp): a
-        token set or sequence — with a Phrase present, the token SEQUENCE in text order (TypeError for a set)."""
-        if self.has_phrase:
+        token set or sequence — with a Phrase or a Near present, the token SEQUENCE in text order (TypeError for a set)."""
+        if self.has_phrase or self.has_near:
             if isinstance(tokens, (set, frozenset, dict)) or not isinstance(tokens, Sequence):
-                raise TypeError("Terms.matches: a Terms with a Phrase needs the document's token sequence, not a set")
+                raise TypeError(f"Terms.matches: a Terms with a {'Phrase' if self.has_phrase else 'Near'} needs the "
+                                f"document's token sequence, not a set")
             have = set(tokens)
         else:
             have = tokens if isinstance(tokens, (set, frozenset, dict)) else set(tokens)
-        sat = lambda g: all(t.within(tokens) if isinstance(t, Phrase) else t in have for t in g)  # noqa: E731
+        sat = lambda g: all(t.within(tokens) if isinstance(t, (Phrase, Near)) else t in have for t in g)  # noqa: E731
         return (all(sat(g) for g in self.all_of or ()) and (self.any_of is None or any(sat(g) for g in self.any_of))
                 and not any(sat(g) for g in self.none_of or ()))
 
@@ -180,9 +278,33 @@ class TermTable:
     phr_cand_max: int = 0         # the longest phrase driver: the largest of the phrases' upper bounds
     phr_rows_cap: int = 0         # the sum of the upper bounds
 
+    # the Nears of the batch, each stored once; Near j is term id len(vocab) + n_phr + j in `ops`.  With a Near present
+    # span_ops holds the items of the ONE span step (amdr_span_lists): the phrases as kind 0, then the Nears
+    span_ops: Tuple[np.ndarray, ...] = (np.zeros(1, dtype=np.int64), np.zeros(0, dtype=np.int32),
+                                        np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.int32))  # ptr, terms, kind, dist
+    nears: Tuple[Near, ...] = ()
+    near_cand_max: int = 0        # the longest Near driver: the largest of the Nears' upper bounds
+    near_rows_cap: int = 0        # the sum of the upper bounds
+
     @property
     def n_phr(self) -> int:
         return len(self.phrases)
+
+    @property
+    def n_near(self) -> int:
+        return len(self.nears)
+
+    @property
+    def span_cand_max(self) -> int:
+        return max(self.phr_cand_max, self.near_cand_max)
+
+    @property
+    def span_rows_cap(self) -> int:
+        return self.phr_rows_cap + self.near_rows_cap
+
+    def span_item(self, i: int):
+        """Item i of the span step: the Phrase or the Near."""
+        return self.phrases[i] if i < self.n_phr else self.nears[i - self.n_phr]
 
 
 def pack(pairs: Sequence[Tuple[Optional[Scope], Terms]], vocab: Mapping[str, int], doc_freq: Mapping[str, int], n_docs: int,
@@ -195,7 +317,10 @@ def pack(pairs: Sequence[Tuple[Optional[Scope], Terms]], vocab: Mapping[str, int
     rows_cap = the sum of the drivers.  Equal phrases are stored once as well and stand in the table as the term ids
     len(vocab) + p; the host knows only an upper bound of a phrase's list — the smallest document frequency among its
     tokens, 0 with an unknown one — which serves both steps: phr_cand_max / phr_rows_cap are the largest and the sum of
-    these, and the drivers of the term step are computed with them (driver_length)."""
+    these, and the drivers of the term step are computed with them (driver_length).  Equal Nears are stored once too and
+    stand as the term ids len(vocab) + n_phr + j, behind the phrases, with the same upper bound (a chunk that holds a Near
+    holds each of its tokens): near_cand_max / near_rows_cap; a table with a Near carries span_ops, the items of the one
+    span step.  A table without one is field for field the table of the phrases alone."""
     n_vocab = len(vocab)
     df_by_id = np.zeros(n_vocab, dtype=np.int64)
     for w, t in vocab.items():
@@ -203,7 +328,19 @@ def pack(pairs: Sequence[Tuple[Optional[Scope], Terms]], vocab: Mapping[str, int
     phr_slot: Dict[Phrase, int] = {}
     phr_ptr, phr_terms, phr_bound = [0], [], []
 
-    def term_id(t) -> int:
+    near_slot: Dict[Near, int] = {}
+    near_ids: List[List[int]] = []
+    near_bound: List[int] = []
+
+    def term_id(t):
+        if isinstance(t, Near):  # (numbered behind the phrases once all of those are known: a placeholder until then)
+            j = near_slot.get(t)
+            if j is None:
+                j = near_slot[t] = len(near_bound)
+                ids = [vocab.get(w, -1) for w in t.tokens]
+                near_ids.append(ids)
+                near_bound.append(0 if min(ids) < 0 else int(min(df_by_id[i] for i in ids)))
+            return (j,)
         if not isinstance(t, Phrase):
             return vocab.get(t, -1)
         p = phr_slot.get(t)
@@ -234,24 +371,39 @@ def pack(pairs: Sequence[Tuple[Optional[Scope], Terms]], vocab: Mapping[str, int
                     b = base_slot[scope] = len(bases)
                     bases.append(np.ascontiguousarray(base_rows(scope), dtype=np.int64))
             groups = [(kind, [term_id(t) for t in g]) for kind, g in terms.groups()]
-            for kind, ids in groups:
-                grp_kind.append(kind)
-                grp_terms.extend(ids)
-                grp_term_ptr.append(len(grp_terms))
-            grp_ptr.append(len(grp_kind))
+            grp_ptr.append(grp_ptr[-1] + len(groups))
             cons_base.append(b)
             cons_groups.append(groups)
         qscope[i] = j
+    n_phr = len(phr_bound)
+    cons_groups = [[(kind, [n_vocab + n_phr + t[0] if isinstance(t, tuple) else t for t in ids]) for kind, ids in groups]
+                   for groups in cons_groups]
+    for groups in cons_groups:
+        for kind, ids in groups:
+            grp_kind.append(kind)
+            grp_terms.extend(ids)
+            grp_term_ptr.append(len(grp_terms))
     base_ptr = np.zeros(len(bases) + 1, dtype=np.int64)
     if bases:
         np.cumsum([b.size for b in bases], out=base_ptr[1:])
     ops = (np.asarray(grp_ptr, dtype=np.int64), np.asarray(grp_kind, dtype=np.int32), np.asarray(grp_term_ptr, dtype=np.int64),
            np.asarray(grp_terms, dtype=np.int32), base_ptr,
            np.concatenate(bases) if bases else np.zeros(0, dtype=np.int64), np.asarray(cons_base, dtype=np.int32))
-    df_all = np.concatenate([df_by_id, np.asarray(phr_bound, dtype=np.int64)])  # (the phrases are all known by now)
+    df_all = np.concatenate([df_by_id, np.asarray(phr_bound + near_bound, dtype=np.int64)])  # (all known by now)
     lens_a = np.asarray([driver_length(g, df_all, int(bases[b].size) if b >= 0 else None, n_docs)
                          for g, b in zip(cons_groups, cons_base)], dtype=np.int64)
-    return TermTable(ops, qscope, len(cons_base), len(grp_kind), len(bases), lens_a,
-                     int(lens_a.max()) if lens_a.size else 0, int(lens_a.sum()),
-                     (np.asarray(phr_ptr, dtype=np.int64), np.asarray(phr_terms, dtype=np.int32)), tuple(phr_slot),
-                     max(phr_bound, default=0), int(sum(phr_bound)))
+    tt = TermTable(ops, qscope, len(cons_base), len(grp_kind), len(bases), lens_a,
+                   int(lens_a.max()) if lens_a.size else 0, int(lens_a.sum()),
+                   (np.asarray(phr_ptr, dtype=np.int64), np.asarray(phr_terms, dtype=np.int32)), tuple(phr_slot),
+                   max(phr_bound, default=0), int(sum(phr_bound)))
+    if near_slot:
+        item_ptr, item_terms = list(phr_ptr), list(phr_terms)
+        for ids in near_ids:
+            item_terms.extend(ids)
+            item_ptr.append(len(item_terms))
+        nears = tuple(near_slot)
+        tt.span_ops = (np.asarray(item_ptr, dtype=np.int64), np.asarray(item_terms, dtype=np.int32),
+                       np.asarray([0] * n_phr + [2 if x.ordered else 1 for x in nears], dtype=np.int32),
+                       np.asarray([0] * n_phr + [x.distance for x in nears], dtype=np.int32))
+        tt.nears, tt.near_cand_max, tt.near_rows_cap = nears, max(near_bound), int(sum(near_bound))
+    return tt
