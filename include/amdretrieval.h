@@ -1007,6 +1007,42 @@ int amdr_span_lists(amdr_bm25_t* bm25, const int64_t* item_ptr, const int32_t* i
                     const int32_t* item_dist, int64_t n_items, int64_t cand_max, int64_t rows_cap, int64_t* out_list_ptr,
                     int32_t* out_docs, int32_t* out_status);
 
+/* ---- unions of posting lists: the root expander (sell!) and alternatives (buyer OR purchaser) -------------------------
+ * No reference counterpart (the reference has no stemmer and no filter; every token is compared exactly).
+ * csrc/union_lists.hip, csrc/union_rule.hpp.  Needs the postings only: a handle WITHOUT a token stream resolves unions.
+ * A union item is M >= 0 term ids, item_terms[item_ptr[p] .. item_ptr[p + 1]).  Its list is the strictly ascending set
+ * of the documents that have a posting for at least one of them.  An id outside [0, n_terms) names a token present in no
+ * document and contributes nothing (never dereferenced); M = 0, or every id unknown, gives an empty list; a repeated id is
+ * harmless.  The lists are merged and de-duplicated, not concatenated: a document two terms share stands once.
+ * One list array.  amdr_term_scope_lists takes a single x_ptr / x_doc, so the call CONTINUES the array a span step began:
+ * list_ptr_dev holds n_before + n_items + 1 entries, of which the first n_before + 1 were written earlier on the same
+ * stream; start = list_ptr[n_before] is read on the device (no host synchronise), the entries n_before + 1 .. are
+ * written and the items' documents are appended behind `start`.  rows_cap is the capacity of the WHOLE docs array.
+ * n_before = 0 starts an array: the call writes list_ptr[0] = 0 itself.
+ *   out_status i32 [n_items]   0, or 2 (the meaning of amdr_term_scope's: documents of the item lie at positions >=
+ *                              rows_cap and were dropped; list_ptr is clamped to rows_cap).  There is no 1: a union has
+ *                              no driver.  Bound a host packer knows: min(n_docs, the sum of the document frequencies of
+ *                              the item's distinct known ids) >= the list's length; rows_cap = the sum of these (plus what
+ *                              stands before) always suffices.
+ * Three launches (count, scan, write), no global atomics, deterministic, nothing allocated, capturable.  The grid is
+ * one-dimensional: n_items x tiles cells, tiles = max(1, ceil(n_docs / 32 768)); a cell is a 4 KiB bitmap of its tile's
+ * documents, set in LDS and parked in the workspace between the passes.  Work per cell: M x 2 binary searches plus the
+ * postings inside the tile — an item of 4 096 terms on 10 M documents is 306 tiles x 4 096 x 2 searches.
+ * amdr_union_lists_plan is host-only arithmetic: the workspace of n_items items on an index of n_docs documents (two i64
+ * and 4 KiB per cell).  amdr_union_lists_device only enqueues; it does not validate the operands' contents and returns
+ * AMDR_EINVAL, enqueueing nothing and leaving the outputs untouched, for a null handle or array, a negative size, more
+ * cells than one launch takes (n_items x tiles x 256 threads must stay below 2^32, so n_items x tiles >= 2^31 is always
+ * refused) or work_bytes below the plan.  amdr_union_lists is the host-pointer twin: it starts its own array
+ * (n_before = 0), validates (AMDR_EINVAL: item_ptr not starting at 0 or not monotone), stages, runs on the BM25 handle's
+ * own stream under its mutex and returns the lists and the status array in the host buffers.
+ * Mutations: amdr_bm25_add's rule; n_docs changes the tile count, so callers plan and capture again. */
+int amdr_union_lists_plan(int64_t n_items, int64_t n_docs, int64_t* work_bytes);
+int amdr_union_lists_device(amdr_bm25_t* bm25, const int64_t* item_ptr_dev, const int32_t* item_terms_dev, int64_t n_items,
+                            int64_t n_before, int64_t rows_cap, int64_t* list_ptr_dev, int32_t* docs_dev,
+                            int32_t* out_status_dev, void* work_dev, int64_t work_bytes, void* stream);
+int amdr_union_lists(amdr_bm25_t* bm25, const int64_t* item_ptr, const int32_t* item_terms, int64_t n_items, int64_t rows_cap,
+                     int64_t* out_list_ptr, int32_t* out_docs, int32_t* out_status);
+
 /* ---- multi-GPU: merge per-shard top-k after the RCCL all-gather --------
  * No reference counterpart (the reference is single-process).
  * parts: [n_parts, nq, k_in] scores + GLOBAL ids (-1 padding); output

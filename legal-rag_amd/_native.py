@@ -67,6 +67,7 @@ SIGNATURES = {
     "amdr_phrase_lists_plan": "llP", "amdr_phrase_lists_device": "PPP" + "lll" + "PPP" + "PlP", "amdr_phrase_lists": "PPP" + "lll" + "PPP",
     "amdr_term_scope_lists_device": "P" + "P" * 9 + "l" * 6 + "PPP" + "PlP", "amdr_term_scope_lists": "P" + "P" * 9 + "l" * 6 + "PPP",
     "amdr_span_lists_plan": "llP", "amdr_span_lists_device": "PPPPP" + "lll" + "PPP" + "PlP", "amdr_span_lists": "PPPPP" + "lll" + "PPP",
+    "amdr_union_lists_plan": "llP", "amdr_union_lists_device": "PPP" + "lll" + "PPP" + "PlP", "amdr_union_lists": "PPP" + "ll" + "PPP",
 }
 EXPORTS = tuple(SIGNATURES)  # every symbol include/amdretrieval.h declares (checked by tests/test_abi.py)
 _KIND = {"P": C.c_void_p, "i": C.c_int32, "l": C.c_int64, "d": C.c_double}
@@ -235,6 +236,17 @@ def span_lists_plan(n_items: int, cand_max: int) -> int:
     arithmetic, the phrase plan's."""
     out = C.c_int64(0)
     _check(load().amdr_span_lists_plan(C.c_int64(n_items), C.c_int64(cand_max), C.byref(out)), "amdr_span_lists_plan")
+    return int(out.value)
+
+
+UNION_TILE = 32768  # documents per tile of amdr_union_lists (kUnTile)
+
+
+def union_lists_plan(n_items: int, n_docs: int) -> int:
+    """Workspace bytes of BM25Index.union_lists_device(n_items union items) on an index of n_docs documents — host-only
+    arithmetic."""
+    out = C.c_int64(0)
+    _check(load().amdr_union_lists_plan(C.c_int64(n_items), C.c_int64(n_docs), C.byref(out)), "amdr_union_lists_plan")
     return int(out.value)
 
 
@@ -775,6 +787,34 @@ class BM25Index(_Handle):
                                              _vp(item_dist_ptr), C.c_int64(n_items), C.c_int64(cand_max), C.c_int64(rows_cap),
                                              _vp(list_ptr_ptr), _vp(docs_ptr), _vp(status_ptr), _vp(work_ptr),
                                              C.c_int64(work_bytes), _vp(stream)), "amdr_span_lists_device")
+
+    # -- unions of posting lists -> virtual posting lists (amdr_union_lists, csrc/union_lists.hip) ---------------------
+    def union_lists(self, item_ptr, item_terms, rows_cap: int):
+        """The host twin: (list_ptr i64 [n + 1], docs i32 [list_ptr[-1]], status i32 [n]) of the union items
+        item_terms[item_ptr[p] : item_ptr[p + 1]] — each list the ascending documents that have a posting for at least one
+        of the item's term ids.  status: 0, or 2 (documents beyond rows_cap dropped).  Needs no token stream."""
+        pp, pt = _c(item_ptr, np.int64).ravel(), _c(item_terms, np.int32).ravel()
+        if pp.size < 1:
+            raise ValueError("union_lists: item_ptr [n + 1]")
+        n = pp.size - 1
+        lp = np.zeros(n + 1, dtype=np.int64)
+        docs = np.full(max(int(rows_cap), 1), -1, dtype=np.int32)
+        status = np.zeros(max(n, 1), dtype=np.int32)
+        pt_arg = pt if pt.size else np.zeros(1, dtype=np.int32)
+        _check(load().amdr_union_lists(self._h, _p(pp, C.c_int64), _p(pt_arg, C.c_int32), C.c_int64(n), C.c_int64(rows_cap),
+                                       _p(lp, C.c_int64), _p(docs, C.c_int32), _p(status, C.c_int32)), "amdr_union_lists")
+        return lp, docs[:int(lp[-1])], status[:n]
+
+    def union_lists_device(self, item_ptr_ptr: int, item_terms_ptr: int, n_items: int, n_before: int, rows_cap: int,
+                           list_ptr_ptr: int, docs_ptr: int, status_ptr: int, work_ptr: int, work_bytes: int,
+                           stream: int = 0) -> None:
+        """The "_device" form: operands and outputs as device pointers; enqueues only.  Continues the list array whose
+        first n_before + 1 entries of list_ptr were written earlier on the same stream (n_before = 0: starts one);
+        rows_cap is the capacity of the whole docs array."""
+        _check(load().amdr_union_lists_device(self._h, _vp(item_ptr_ptr), _vp(item_terms_ptr), C.c_int64(n_items),
+                                              C.c_int64(n_before), C.c_int64(rows_cap), _vp(list_ptr_ptr), _vp(docs_ptr),
+                                              _vp(status_ptr), _vp(work_ptr), C.c_int64(work_bytes), _vp(stream)),
+               "amdr_union_lists_device")
 
     def get_scores(self, queries: Sequence[Sequence[int]]) -> np.ndarray:
         q_terms, q_ptr = self.pack_queries(queries)

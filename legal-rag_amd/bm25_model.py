@@ -100,7 +100,7 @@ class BM25Okapi:
     # -- device side --------------------------------------------------------
     def __getstate__(self):
         st = dict(self.__dict__)
-        for k in ("_vocab", "_gpu", "_gpu_device", "_tokenizer_id", "_nd", "_total"):
+        for k in ("_vocab", "_sorted_vocab", "_gpu", "_gpu_device", "_tokenizer_id", "_nd", "_total"):
             st.pop(k, None)
         return st
 
@@ -110,6 +110,16 @@ class BM25Okapi:
             v = {w: t for t, w in enumerate(self.idf.keys())}
             self.__dict__["_vocab"] = v
         return v
+
+    def sorted_vocab(self) -> List[str]:
+        """The vocabulary's tokens ascending by code point (a Prefix is expanded by bisection over it, retrieval/terms.py
+        pack); cached next to the vocabulary, not pickled.  add_documents extends vocab() IN PLACE, so the cache holds
+        only while vocab() is the same object AND as long as it was; a remove or a replace makes a new vocabulary."""
+        v = self.vocab()
+        held = self.__dict__.get("_sorted_vocab")
+        if held is None or held[0] is not v or held[1] != len(v):
+            held = self.__dict__["_sorted_vocab"] = (v, len(v), sorted(v))
+        return held[2]
 
     def _doc_frequencies(self) -> Dict[str, int]:
         """{word: number of documents holding it} in vocabulary order — __init__'s `nd`, rebuilt once from doc_freqs

@@ -1,5 +1,6 @@
 // The BM25 handle, shared by bm25.hip (create, plan, score, search, destroy), bm25_update.hip (add, remove, info, read),
-// term_scope.hip (term constraints) and phrase_scope.hip (the token stream, phrases).  The per-call plumbing of the updates
+// term_scope.hip (term constraints), phrase_scope.hip (the token stream, phrases, Nears) and union_lists.hip (unions of
+// posting lists).  The per-call plumbing of the updates
 // (dev_alloc, CallScratch, KernelSpans, AMDR_TRY) is call_scratch.hpp's, shared with the other two channels.
 #pragma once
 #include "call_scratch.hpp"

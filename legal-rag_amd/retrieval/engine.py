@@ -249,11 +249,17 @@ class HybridEngine:
         the constraints' words, then the phrases'.
         A table with Nears (table.n_near > 0): ONE span step (amdr_span_lists_device, the same three launches) takes the
         phrase step's place — the phrases go first as kind 0, then the Nears, into one list array — and the status tensor
-        is i32 [n_cons + n_phr + n_near].  Without a Near the calls are those above."""
+        is i32 [n_cons + n_phr + n_near].  Without a Near the calls are those above.
+        A table with unions (table.n_union > 0, a Prefix or a OneOf): the union step (amdr_union_lists_device, three
+        launches, needs no token stream) is enqueued behind the span or phrase step on the same stream — first, with
+        n_before = 0, when there is none — and CONTINUES the same list array, sized for span_rows_cap + union_rows_cap; the
+        term step then reads n_phr + n_near + n_union lists and the status tensor is i32 [n_cons + n_phr + n_near +
+        n_union].  Without a union the calls are those above."""
         self.check_term_scopes()
         n_cons, cand_max, rows_cap = int(table.n_cons), int(table.cand_max), int(table.rows_cap)
         n_phr = int(getattr(table, "n_phr", 0))
         n_near = int(getattr(table, "n_near", 0))
+        n_union = int(getattr(table, "n_union", 0))
         order = (0, 2, 4, 5, 1, 3, 6)  # the i64 arrays first: every one starts on a multiple of its item size
         parts = [(i, np.ascontiguousarray(table.ops[i], dtype=t).view(np.uint8))
                  for i, t in ((i, _native.BM25Index.TERM_OPS[i]) for i in order)]
@@ -263,6 +269,9 @@ class HybridEngine:
         elif n_phr:
             parts.insert(4, (8, np.ascontiguousarray(table.phr_ops[0], dtype=np.int64).view(np.uint8)))
             parts.append((9, np.ascontiguousarray(table.phr_ops[1], dtype=np.int32).view(np.uint8)))
+        if n_union:  # the items of the union step
+            parts.insert(4, (12, np.ascontiguousarray(table.union_ops[0], dtype=np.int64).view(np.uint8)))
+            parts.append((13, np.ascontiguousarray(table.union_ops[1], dtype=np.int32).view(np.uint8)))
         parts.append((7, np.ascontiguousarray(table.qscope, dtype=np.int32).view(np.uint8)))
         total = sum(p.size for _, p in parts)
         host, dev, ev = self._staging("tsc", max(total, 8))
@@ -274,29 +283,34 @@ class HybridEngine:
         self._send(host, dev, ev, max(total, 8))
         base = dev.data_ptr()
         o_rows, o_status = 8 * (n_cons + 1), 8 * (n_cons + 1) + 8 * rows_cap
-        n_x = n_phr + n_near  # the virtual lists of the term step
+        n_span = n_phr + n_near
+        n_x = n_span + n_union  # the virtual lists of the term step
         out = self._grown("tso", o_status + 4 * (n_cons + n_x) + 8)
         lists = None
-        if n_near:  # the span step: phrases and Nears into ONE list array
-            p_max, p_cap = int(table.span_cand_max), int(table.span_rows_cap)
+        if n_x:  # ONE list array: the span (or phrase) step begins it, the union step continues it
+            span_cap = int(table.span_rows_cap) if n_near else int(table.phr_rows_cap)
+            list_cap = span_cap + int(getattr(table, "union_rows_cap", 0))
             o_docs = 8 * (n_x + 1)
-            pout = self._grown("pho", o_docs + 4 * p_cap + 8)
-            p_bytes = _native.span_lists_plan(n_x, p_max)
-            pwork = self._grown("phw", p_bytes)
-            self.bm25.span_lists_device(base + where[8][0], base + where[9][0], base + where[10][0], base + where[11][0],
-                                        n_x, p_max, p_cap, pout.data_ptr(), pout.data_ptr() + o_docs,
-                                        out.data_ptr() + o_status + 4 * n_cons, pwork.data_ptr(), p_bytes, _stream())
-            lists = (pout.data_ptr(), pout.data_ptr() + o_docs, n_x)
-        elif n_phr:  # the phrase step: its lists are the virtual terms of the term step behind it
-            p_max, p_cap = int(table.phr_cand_max), int(table.phr_rows_cap)
-            o_docs = 8 * (n_phr + 1)
-            pout = self._grown("pho", o_docs + 4 * p_cap + 8)
-            p_bytes = _native.phrase_lists_plan(n_phr, p_max)
-            pwork = self._grown("phw", p_bytes)
-            self.bm25.phrase_lists_device(base + where[8][0], base + where[9][0], n_phr, p_max, p_cap, pout.data_ptr(),
-                                          pout.data_ptr() + o_docs, out.data_ptr() + o_status + 4 * n_cons,
-                                          pwork.data_ptr(), p_bytes, _stream())
-            lists = (pout.data_ptr(), pout.data_ptr() + o_docs, n_phr)
+            pout = self._grown("pho", o_docs + 4 * list_cap + 8)
+            x_ptr, x_doc, x_status = pout.data_ptr(), pout.data_ptr() + o_docs, out.data_ptr() + o_status + 4 * n_cons
+            if n_near:  # the span step: phrases and Nears
+                p_max = int(table.span_cand_max)
+                p_bytes = _native.span_lists_plan(n_span, p_max)
+                pwork = self._grown("phw", p_bytes)
+                self.bm25.span_lists_device(base + where[8][0], base + where[9][0], base + where[10][0], base + where[11][0],
+                                            n_span, p_max, span_cap, x_ptr, x_doc, x_status, pwork.data_ptr(), p_bytes, _stream())
+            elif n_phr:  # the phrase step: its lists are the virtual terms of the term step behind it
+                p_max = int(table.phr_cand_max)
+                p_bytes = _native.phrase_lists_plan(n_phr, p_max)
+                pwork = self._grown("phw", p_bytes)
+                self.bm25.phrase_lists_device(base + where[8][0], base + where[9][0], n_phr, p_max, span_cap, x_ptr, x_doc,
+                                              x_status, pwork.data_ptr(), p_bytes, _stream())
+            if n_union:  # the union step: behind the n_span lists on the same stream (first, with n_before = 0)
+                u_bytes = _native.union_lists_plan(n_union, int(self.bm25.n_docs))
+                uwork = self._grown("unw", u_bytes)
+                self.bm25.union_lists_device(base + where[12][0], base + where[13][0], n_union, n_span, list_cap, x_ptr, x_doc,
+                                             x_status + 4 * n_span, uwork.data_ptr(), u_bytes, _stream())
+            lists = (x_ptr, x_doc, n_x)
         work_bytes = _native.term_scope_plan(n_cons, cand_max)
         work = self._grown("tsw", work_bytes)
         self.bm25.term_scope_device([base + where[i][0] for i in range(7)], int(table.n_base), n_cons, int(table.n_groups),

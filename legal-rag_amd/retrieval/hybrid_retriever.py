@@ -41,7 +41,7 @@ from .diversity import Diversity, resolve as _resolve_diversity
 from .graph_retriever import GraphRetriever
 from .rerankers import RerankerFactory, _to_doc_text
 from .scope import Scope, resolver_for
-from .terms import Near, Phrase, Terms, pack as _pack_terms
+from .terms import Near, Phrase, Prefix, Terms, pack as _pack_terms
 
 logger = logging.getLogger("legalrag.retrieval.hybrid_retriever")
 
@@ -234,7 +234,7 @@ class HybridRetriever:
                              f"be a row of the channel)")
         model = bm.bm25
         tt = _pack_terms([(scope, terms)], model.vocab(), model._doc_frequencies(), int(model.corpus_size),
-                         resolver_for(bm.chunks).rows)
+                         resolver_for(bm.chunks).rows, model.sorted_vocab() if terms.has_union else None)
         if tt.cand_max == 0:
             return np.zeros(0, dtype=np.int64)
         lists = None
@@ -254,6 +254,16 @@ class HybridRetriever:
                 raise RuntimeError(f"{who}(terms=): {tt.phrases[p]!r} overflowed its bound (status {int(p_status[p])}); the "
                                    f"host model and the resident BM25 index disagree")
             lists = (lp, docs)
+        if tt.n_union:  # the unions behind them, in the same arrays
+            u_lp, u_docs, u_status = bm.gpu_index().union_lists(*tt.union_ops, tt.union_rows_cap)
+            if u_status.any():
+                u = int(np.flatnonzero(u_status)[0])
+                raise RuntimeError(f"{who}(terms=): {tt.unions[u]!r} overflowed its bound (status {int(u_status[u])}); the "
+                                   f"host model and the resident BM25 index disagree")
+            if lists is None:
+                lists = (u_lp, u_docs)
+            else:
+                lists = (np.concatenate([lists[0], lists[0][-1] + u_lp[1:]]), np.concatenate([lists[1], u_docs]))
         _, rows, status = bm.gpu_index().term_scope(tt.ops, tt.cand_max, tt.rows_cap, lists=lists)
         if int(status[0]) != 0:
             raise RuntimeError(f"{who}(terms=): the term constraint overflowed its bound (status {int(status[0])}); the "
@@ -280,6 +290,18 @@ class HybridRetriever:
         if not isinstance(bm, BM25Retriever):
             raise ValueError("near(): proximity constraints need this package's own BM25 retriever")
         return Near(*bm.document_tokens(text_), distance=distance, ordered=ordered)
+
+    def prefix(self, text_: str) -> Prefix:
+        """The Prefix of a string, cut by the BM25 index's DOCUMENT-side tokeniser as phrase() cuts it:
+        retriever.prefix("Sell") == Prefix("sell").  ValueError unless the string yields exactly one token, or on an index
+        that records no tokeniser."""
+        bm = self.bm25
+        if not isinstance(bm, BM25Retriever):
+            raise ValueError("prefix(): root expanders need this package's own BM25 retriever")
+        toks = bm.document_tokens(text_)
+        if len(toks) != 1:
+            raise ValueError(f"prefix(): {text_!r} holds {len(toks)} tokens; a stem is exactly one")
+        return Prefix(toks[0])
 
     def _search_scoped(self, who: str, chunks, scope: Optional[Scope], top_k: int, refusal: Optional[str], device, twin: str,
                        operands, terms: Optional[Terms] = None):
@@ -955,7 +977,7 @@ class HybridRetriever:
                 bad = np.flatnonzero(status[0].numpy().view(np.int32))
                 if bad.size and int(bad[0]) >= int(term_table.n_cons):  # the phrases' words stand behind the constraints'
                     p = int(bad[0]) - int(term_table.n_cons)
-                    raise RuntimeError(f"{term_table.span_item(p)!r} of the batch overflowed its bound (status "
+                    raise RuntimeError(f"{term_table.list_item(p)!r} of the batch overflowed its bound (status "
                                        f"{int(status[0].numpy().view(np.int32)[bad[0]])}: 1 = candidates beyond cand_max, "
                                        f"2 = documents beyond rows_cap); the host model and the resident BM25 index disagree")
                 if bad.size:
@@ -1096,7 +1118,8 @@ class HybridRetriever:
             model = bm.bm25  # (looked up per call: an in-place update renumbers the vocabulary)
             term_table = _pack_terms([(scopes[i] if scopes is not None else None, terms[i] or Terms()) for i in idxs],
                                      model.vocab(), model._doc_frequencies(), int(model.corpus_size),
-                                     resolver_for(store.chunks).rows)
+                                     resolver_for(store.chunks).rows,
+                                     model.sorted_vocab() if any(terms[i] is not None and terms[i].has_union for i in idxs) else None)
             if term_table.n_phr or term_table.n_near:
                 bm.ensure_token_stream()  # (made lazily: on the first phrase or Near, and again after a live update)
         elif scoped:

@@ -17,9 +17,17 @@ A `Near` is PROXIMITY: Near("buyer", "seller", distance=5) names the chunks that
 each other, in either order (ordered=True: in the order given) — looser than a phrase, stricter than a conjunction.  It
 stands wherever a token or a Phrase stands, and the GPU resolves the phrases and the Nears of a batch in one step into one
 array of document lists (amdr_span_lists).
+
+A `Prefix` is the ROOT EXPANDER (sell! in a Boolean legal search): Prefix("sell") names every vocabulary token that starts
+with "sell" — the index has no stemmer — and a `OneOf` is ALTERNATIVES as one term: OneOf("buyer", "purchaser").  Either
+stands wherever a token stands, also inside a tuple group: (OneOf("buyer", "purchaser"), OneOf("goods", "merchandise")) is
+(buyer OR purchaser) AND (goods OR merchandise).  `pack()` expands both into the term ids they name and the GPU merges the
+posting lists of each into one ascending, de-duplicated document list (amdr_union_lists, csrc/union_lists.hip) behind the
+lists of the phrases and the Nears.
 """
 from __future__ import annotations
 
+from bisect import bisect_left
 from dataclasses import dataclass
 from typing import Any, Dict, List, Mapping, Optional, Sequence, Tuple, Union
 
@@ -32,6 +40,7 @@ MUST, ANY, NOT = 0, 1, 2  # the group kinds of the ABI (term_scope_rule.hpp TsKi
 PHRASE_MAX_LEN = 16  # tokens of a phrase (phrase_rule.hpp kPhMaxLen)
 NEAR_MAX_TERMS = 8   # tokens of a Near (near_rule.hpp kNearMaxTerms)
 NEAR_MAX_DIST = 255  # the largest distance of a Near (near_rule.hpp kNearMaxDist)
+PREFIX_MAX_TERMS = 4096  # vocabulary tokens one Prefix or OneOf may name (pack)
 
 
 class Phrase:
@@ -160,13 +169,97 @@ def _make_near(tokens, distance, ordered) -> Near:
     return Near(*tokens, distance=distance, ordered=ordered)
 
 
-Member = Union[str, Phrase, Near]
+class Prefix:
+    """The root expander: Prefix("sell") names every vocabulary token that starts with "sell" (sell, seller, seller's,
+    selling, sells), and a chunk holds it when it holds at least one of them.  The stem is a non-empty str (TypeError /
+    ValueError otherwise), compared exactly as every token is (HybridRetriever.prefix cuts a string with the index's own
+    tokeniser).  Accepted wherever a token is: as an entry of a Terms field, as a member of a tuple group or of a OneOf —
+    not inside a Phrase or a Near.  A stem that no token starts with is a token the vocabulary does not hold.  Frozen and
+    hashable: equal prefixes are equal and hash alike."""
+    __slots__ = ("stem",)
+
+    def __init__(self, stem: str) -> None:
+        if not isinstance(stem, str):
+            raise TypeError(f"Prefix: the stem is a str, got {type(stem).__name__}")
+        if not stem:
+            raise ValueError("Prefix: an empty stem names every token")
+        object.__setattr__(self, "stem", stem)
+
+    def __setattr__(self, name, value) -> None:
+        raise AttributeError("Prefix is frozen")
+
+    def __delattr__(self, name) -> None:
+        raise AttributeError("Prefix is frozen")
+
+    def __eq__(self, other) -> bool:
+        return isinstance(other, Prefix) and self.stem == other.stem
+
+    def __hash__(self) -> int:
+        return hash(("Prefix", self.stem))
+
+    def __repr__(self) -> str:
+        return f"Prefix({self.stem!r})"
+
+    def __reduce__(self):
+        return (Prefix, (self.stem,))
+
+    def within(self, tokens) -> bool:
+        """Whether one of `tokens` (a set or a sequence) starts with the stem."""
+        return any(t.startswith(self.stem) for t in tokens)
+
+
+class OneOf:
+    """Alternatives as ONE term: a chunk holds OneOf(m0, m1, ...) when it holds at least one member.  A member is a token
+    (str) or a Prefix, at least one (ValueError); a Phrase, a Near or a OneOf as a member is a TypeError — alternatives
+    between token sequences are not resolved yet.  OneOf("x") is the plain term, as a one-token Phrase is.  Accepted
+    wherever a token is: as an entry of a Terms field or as a member of a tuple group — not inside a Phrase or a Near.
+    Frozen and hashable: equal OneOfs (the same members in the same order) are equal and hash alike."""
+    __slots__ = ("members",)
+
+    def __init__(self, *members) -> None:
+        if not members:
+            raise ValueError("OneOf: at least one member")
+        for m in members:
+            if not isinstance(m, (str, Prefix)):
+                raise TypeError(f"OneOf: a member is a str or a Prefix, got {type(m).__name__}")
+        object.__setattr__(self, "members", tuple(members))
+
+    def __setattr__(self, name, value) -> None:
+        raise AttributeError("OneOf is frozen")
+
+    def __delattr__(self, name) -> None:
+        raise AttributeError("OneOf is frozen")
+
+    def __eq__(self, other) -> bool:
+        return isinstance(other, OneOf) and self.members == other.members
+
+    def __hash__(self) -> int:
+        return hash(("OneOf", self.members))
+
+    def __len__(self) -> int:
+        return len(self.members)
+
+    def __repr__(self) -> str:
+        return "OneOf(" + ", ".join(repr(m) for m in self.members) + ")"
+
+    def __reduce__(self):
+        return (OneOf, self.members)
+
+    def within(self, tokens) -> bool:
+        """Whether `tokens` (a set or a sequence) holds one of the members."""
+        return any(m.within(tokens) if isinstance(m, Prefix) else m in tokens for m in self.members)
+
+
+Member = Union[str, Phrase, Near, Prefix, OneOf]
 Group = Tuple[Member, ...]
+_MEMBERS = (str, Phrase, Near, Prefix, OneOf)
 
 
 def _member(t) -> Member:
-    if isinstance(t, Near):
+    if isinstance(t, (Near, Prefix)):
         return t
+    if isinstance(t, OneOf):
+        return t.members[0] if len(t) == 1 else t  # one member is that member
     if isinstance(t, Phrase):
         return t.tokens[0] if len(t) == 1 else t  # one token is the plain term
     return str(t)
@@ -175,11 +268,11 @@ def _member(t) -> Member:
 def _groups(x, field: str) -> Optional[Tuple[Group, ...]]:
     if x is None:
         return None
-    if isinstance(x, (str, Phrase, Near)):
+    if isinstance(x, _MEMBERS):
         x = (x,)
     out: List[Group] = []
     for e in x:
-        g = (_member(e),) if isinstance(e, (str, Phrase, Near)) else tuple(_member(t) for t in e)
+        g = (_member(e),) if isinstance(e, _MEMBERS) else tuple(_member(t) for t in e)
         if not g:
             raise ValueError(f"Terms.{field}: an empty group names no token")
         out.append(g)
@@ -191,7 +284,8 @@ class Terms:
     """What a chunk's text must contain.  An entry is one vocabulary token (`str`) or a tuple of tokens, one GROUP: a
     chunk satisfies a group when it holds EVERY token of it, anywhere — a conjunction.  The tokens next to each other
     in order are a `Phrase`, the tokens within a distance of each other a `Near`; either stands wherever a token stands:
-    as an entry, or inside a tuple group.  For a
+    as an entry, or inside a tuple group.  So do a `Prefix` (every token with that stem) and a `OneOf` (alternatives as
+    one term): all_of=[(OneOf("buyer", "purchaser"), Prefix("sell"))] is (buyer OR purchaser) AND sell!.  For a
     char-cut Han index a word is the phrase of its characters, Phrase("合", "同") (the group ("合", "同") also names
     every chunk that holds 同 … 合).
       all_of   every entry must be satisfied (each entry is a MUST group);
@@ -228,9 +322,14 @@ class Terms:
     def has_near(self) -> bool:
         return any(isinstance(t, Near) for _, g in self.groups() for t in g)
 
+    @property
+    def has_union(self) -> bool:
+        return any(isinstance(t, (Prefix, OneOf)) for _, g in self.groups() for t in g)
+
     def matches(self, tokens) -> bool:
-        """The rule on one document's tokens (host check; the kernels apply term_scope_rule.hpp and phrase_rule.hpp): a
-        token set or sequence — with a Phrase or a Near present, the token SEQUENCE in text order (TypeError for a set)."""
+        """The rule on one document's tokens (host check; the kernels apply term_scope_rule.hpp, phrase_rule.hpp and
+        union_rule.hpp): a token set or sequence — with a Phrase or a Near present, the token SEQUENCE in text order
+        (TypeError for a set); a Prefix or a OneOf takes either."""
         if self.has_phrase or self.has_near:
             if isinstance(tokens, (set, frozenset, dict)) or not isinstance(tokens, Sequence):
                 raise TypeError(f"Terms.matches: a Terms with a {'Phrase' if self.has_phrase else 'Near'} needs the "
@@ -238,7 +337,8 @@ class Terms:
             have = set(tokens)
         else:
             have = tokens if isinstance(tokens, (set, frozenset, dict)) else set(tokens)
-        sat = lambda g: all(t.within(tokens) if isinstance(t, (Phrase, Near)) else t in have for t in g)  # noqa: E731
+        sat = lambda g: all(t.within(tokens) if isinstance(t, (Phrase, Near)) else  # noqa: E731
+                            t.within(have) if isinstance(t, (Prefix, OneOf)) else t in have for t in g)
         return (all(sat(g) for g in self.all_of or ()) and (self.any_of is None or any(sat(g) for g in self.any_of))
                 and not any(sat(g) for g in self.none_of or ()))
 
@@ -286,6 +386,13 @@ class TermTable:
     near_cand_max: int = 0        # the longest Near driver: the largest of the Nears' upper bounds
     near_rows_cap: int = 0        # the sum of the upper bounds
 
+    # the unions of the batch (a Prefix or a OneOf that names two or more vocabulary tokens), equal sets of term ids stored
+    # once; union u is term id len(vocab) + n_phr + n_near + u in `ops`, behind the Nears (amdr_union_lists).  Attributes
+    # with class-level defaults, set per table by pack(), and NOT dataclass fields: the fields above stay the last ones
+    union_ops = (np.zeros(1, dtype=np.int64), np.zeros(0, dtype=np.int32))  # ptr i64 [n_union + 1], terms i32
+    unions = ()          # per union the first Prefix / OneOf of the batch that names it
+    union_rows_cap = 0   # the sum of the upper bounds min(n_docs, the sum of the tokens' document frequencies)
+
     @property
     def n_phr(self) -> int:
         return len(self.phrases)
@@ -293,6 +400,10 @@ class TermTable:
     @property
     def n_near(self) -> int:
         return len(self.nears)
+
+    @property
+    def n_union(self) -> int:
+        return len(self.unions)
 
     @property
     def span_cand_max(self) -> int:
@@ -306,9 +417,24 @@ class TermTable:
         """Item i of the span step: the Phrase or the Near."""
         return self.phrases[i] if i < self.n_phr else self.nears[i - self.n_phr]
 
+    def list_item(self, i: int):
+        """What virtual list i of the term step stands for: the Phrase, the Near, or the union's Prefix / OneOf."""
+        n_span = self.n_phr + self.n_near
+        return self.span_item(i) if i < n_span else self.unions[i - n_span]
+
+
+def prefix_tokens(stem: str, sorted_vocab: Sequence[str]) -> List[str]:
+    """The tokens of `sorted_vocab` (ascending by code point, BM25Okapi.sorted_vocab()) that start with `stem`: they stand
+    next to each other, from the first token >= stem."""
+    at = bisect_left(sorted_vocab, stem)
+    end = at
+    while end < len(sorted_vocab) and sorted_vocab[end].startswith(stem):
+        end += 1
+    return list(sorted_vocab[at:end])
+
 
 def pack(pairs: Sequence[Tuple[Optional[Scope], Terms]], vocab: Mapping[str, int], doc_freq: Mapping[str, int], n_docs: int,
-         base_rows=None) -> TermTable:
+         base_rows=None, sorted_vocab: Optional[Sequence[str]] = None) -> TermTable:
     """The operand arrays of a batch of (Scope | None, Terms) pairs.  Equal pairs are stored once (as ScopeResolver.table
     stores equal scopes once) and `qscope` names each pair's constraint; equal base scopes are stored once as well.
     vocab / doc_freq: the live host model's token -> term id and token -> document frequency (BM25Okapi.vocab(),
@@ -320,11 +446,46 @@ def pack(pairs: Sequence[Tuple[Optional[Scope], Terms]], vocab: Mapping[str, int
     these, and the drivers of the term step are computed with them (driver_length).  Equal Nears are stored once too and
     stand as the term ids len(vocab) + n_phr + j, behind the phrases, with the same upper bound (a chunk that holds a Near
     holds each of its tokens): near_cand_max / near_rows_cap; a table with a Near carries span_ops, the items of the one
-    span step.  A table without one is field for field the table of the phrases alone."""
+    span step.  A table without one is field for field the table of the phrases alone.
+    A Prefix is expanded by bisection over sorted_vocab (the vocabulary's tokens ascending by code point,
+    BM25Okapi.sorted_vocab(); computed from `vocab` when not given) and a OneOf into its members' tokens; what either names
+    is the sorted tuple of its DISTINCT KNOWN term ids.  None: the id -1, a token the vocabulary does not hold; one: that
+    plain term; more than PREFIX_MAX_TERMS: ValueError.  Two or more are a union item (amdr_union_lists): equal tuples are
+    stored once — Prefix("sell") and the OneOf of its tokens share a list — and union u stands as the term id
+    len(vocab) + n_phr + n_near + u, behind the Nears, with the upper bound min(n_docs, the sum of the ids' document
+    frequencies) of its list's length: union_rows_cap is the sum of these, and the drivers are computed with them.  A
+    table without a union is field for field the table of the phrases and the Nears alone."""
     n_vocab = len(vocab)
     df_by_id = np.zeros(n_vocab, dtype=np.int64)
     for w, t in vocab.items():
         df_by_id[t] = doc_freq.get(w, 0)
+    union_slot: Dict[Tuple[int, ...], int] = {}
+    union_first: List[Any] = []
+    union_bound: List[int] = []
+    sorted_held = [sorted_vocab]
+
+    def union_id(t):
+        """The id a Prefix or a OneOf stands for: -1, a plain term's, or the placeholder ("u", u) of union u."""
+        words: List[str] = []
+        for m in (t.members if isinstance(t, OneOf) else (t,)):
+            if isinstance(m, Prefix):
+                if sorted_held[0] is None:
+                    sorted_held[0] = sorted(vocab)
+                words.extend(prefix_tokens(m.stem, sorted_held[0]))
+            else:
+                words.append(m)
+        ids = tuple(sorted({vocab[w] for w in words if w in vocab}))
+        if len(ids) > PREFIX_MAX_TERMS:
+            raise ValueError(f"{t!r} names {len(ids)} vocabulary tokens, more than {PREFIX_MAX_TERMS}: give a longer stem")
+        if len(ids) < 2:
+            return ids[0] if ids else -1
+        u = union_slot.get(ids)
+        if u is None:
+            u = union_slot[ids] = len(union_bound)
+            union_first.append(t)
+            union_bound.append(min(int(n_docs), int(sum(df_by_id[i] for i in ids))))
+        return ("u", u)
+
     phr_slot: Dict[Phrase, int] = {}
     phr_ptr, phr_terms, phr_bound = [0], [], []
 
@@ -340,7 +501,9 @@ def pack(pairs: Sequence[Tuple[Optional[Scope], Terms]], vocab: Mapping[str, int
                 ids = [vocab.get(w, -1) for w in t.tokens]
                 near_ids.append(ids)
                 near_bound.append(0 if min(ids) < 0 else int(min(df_by_id[i] for i in ids)))
-            return (j,)
+            return ("n", j)
+        if isinstance(t, (Prefix, OneOf)):  # (numbered behind the Nears: a placeholder as well)
+            return union_id(t)
         if not isinstance(t, Phrase):
             return vocab.get(t, -1)
         p = phr_slot.get(t)
@@ -376,7 +539,8 @@ def pack(pairs: Sequence[Tuple[Optional[Scope], Terms]], vocab: Mapping[str, int
             cons_groups.append(groups)
         qscope[i] = j
     n_phr = len(phr_bound)
-    cons_groups = [[(kind, [n_vocab + n_phr + t[0] if isinstance(t, tuple) else t for t in ids]) for kind, ids in groups]
+    behind = {"n": n_vocab + n_phr, "u": n_vocab + n_phr + len(near_bound)}
+    cons_groups = [[(kind, [behind[t[0]] + t[1] if isinstance(t, tuple) else t for t in ids]) for kind, ids in groups]
                    for groups in cons_groups]
     for groups in cons_groups:
         for kind, ids in groups:
@@ -389,7 +553,7 @@ def pack(pairs: Sequence[Tuple[Optional[Scope], Terms]], vocab: Mapping[str, int
     ops = (np.asarray(grp_ptr, dtype=np.int64), np.asarray(grp_kind, dtype=np.int32), np.asarray(grp_term_ptr, dtype=np.int64),
            np.asarray(grp_terms, dtype=np.int32), base_ptr,
            np.concatenate(bases) if bases else np.zeros(0, dtype=np.int64), np.asarray(cons_base, dtype=np.int32))
-    df_all = np.concatenate([df_by_id, np.asarray(phr_bound + near_bound, dtype=np.int64)])  # (all known by now)
+    df_all = np.concatenate([df_by_id, np.asarray(phr_bound + near_bound + union_bound, dtype=np.int64)])  # (all known by now)
     lens_a = np.asarray([driver_length(g, df_all, int(bases[b].size) if b >= 0 else None, n_docs)
                          for g, b in zip(cons_groups, cons_base)], dtype=np.int64)
     tt = TermTable(ops, qscope, len(cons_base), len(grp_kind), len(bases), lens_a,
@@ -406,4 +570,9 @@ def pack(pairs: Sequence[Tuple[Optional[Scope], Terms]], vocab: Mapping[str, int
                        np.asarray([0] * n_phr + [2 if x.ordered else 1 for x in nears], dtype=np.int32),
                        np.asarray([0] * n_phr + [x.distance for x in nears], dtype=np.int32))
         tt.nears, tt.near_cand_max, tt.near_rows_cap = nears, max(near_bound), int(sum(near_bound))
+    if union_slot:
+        u_ptr = np.zeros(len(union_slot) + 1, dtype=np.int64)
+        np.cumsum([len(ids) for ids in union_slot], out=u_ptr[1:])
+        tt.union_ops = (u_ptr, np.asarray([i for ids in union_slot for i in ids], dtype=np.int32))
+        tt.unions, tt.union_rows_cap = tuple(union_first), int(sum(union_bound))
     return tt
