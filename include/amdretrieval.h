@@ -1043,6 +1043,56 @@ int amdr_union_lists_device(amdr_bm25_t* bm25, const int64_t* item_ptr_dev, cons
 int amdr_union_lists(amdr_bm25_t* bm25, const int64_t* item_ptr, const int32_t* item_terms, int64_t n_items, int64_t rows_cap,
                      int64_t* out_list_ptr, int32_t* out_docs, int32_t* out_status);
 
+/* ---- class spans: a root expander or alternatives INSIDE a phrase or a Near (sell! /5 good!, "secur! interest") -------
+ * No reference counterpart (the reference keeps no token order and has no stemmer).  csrc/class_span.hip,
+ * csrc/class_span_rule.hpp.  Needs the token stream (amdr_bm25_set_tokens) and the list array of the call.
+ * An item is L slot ids item_slots[item_ptr[p] .. item_ptr[p + 1]), a kind (0 phrase: 2 <= L <= 16; 1 Near unordered, 2
+ * Near ordered: 2 <= L <= 8, 1 <= item_dist[p] <= 255) — the kinds and sizes of amdr_span_lists.  A slot id s is
+ *   0 <= s < n_terms                                        a plain token;
+ *   n_terms + cls_first <= s < n_terms + cls_first + n_cls  class c = s - n_terms - cls_first: its member ids are
+ *                                                           cls_terms[cls_ptr[c] .. cls_ptr[c + 1]), strictly ascending
+ *                                                           (the item_ptr / item_terms of the union step), and its document
+ *                                                           list is list cls_first + c of the list array, written earlier
+ *                                                           on the same stream by amdr_union_lists_device;
+ *   anything else                                           unknown: the item's list is empty, nothing is dereferenced.
+ * A token FILLS a slot when it equals the plain token or is a member of the class.  A document holds a phrase item when
+ * some position p has token p + j filling slot j for every j; an ordered Near when positions p0 < p1 < ... carry tokens
+ * that fill the slots in order, the last at most dist behind the first; an unordered Near when some run of at most
+ * dist + 1 consecutive tokens admits an assignment of the slots to distinct positions of the run.  Never across two
+ * documents.  The unordered form is resolved with the first-unfilled-slot tally, which equals that matching when the
+ * slots' id sets are pairwise EQUAL OR DISJOINT; the host twin refuses an unordered item that breaks this.
+ * One list array, continued as amdr_union_lists_device continues it: list_ptr_dev holds n_before + n_items + 1 entries of
+ * which the first n_before + 1 were written earlier on the same stream, cls_first + n_cls <= n_before; start =
+ * list_ptr[n_before] is read on the device, the entries n_before + 1 .. are written and the items' documents are appended
+ * behind `start`.  rows_cap is the capacity of the WHOLE docs array.  n_before = 0 starts an array.
+ *   out_status i32 [n_items]   0; 1: the item's driver — the shortest of its slots' lists, found on the device — is longer
+ *                              than cand_max, the list is left empty; 2: documents at positions >= rows_cap were dropped,
+ *                              list_ptr is clamped.  An undefined item or an unknown slot: an empty list, status 0.  Bound a
+ *                              host packer knows: the smallest slot bound (df of a plain id, min(n_docs, sum of df) of a
+ *                              class) >= the driver >= the list.
+ * Three launches (count, scan, write), no global atomics, deterministic, nothing allocated, capturable.  The grid is
+ * one-dimensional: n_items x tiles cells, tiles = max(1, ceil(cand_max / 256)).  Each token of a surviving document is
+ * turned once per round into the mask of the slots it fills; worst case one round of 319 tokens x 16 class slots x 12
+ * dependent loads (a class of 4 096 ids).
+ * amdr_class_spans_plan is host-only arithmetic (two i64 and 1 KiB per cell).  amdr_class_spans_device only enqueues; it
+ * does not validate the operands' contents and returns AMDR_EINVAL, enqueueing nothing and leaving the outputs untouched,
+ * for a null handle or array, a negative size, classes that do not lie among the n_before lists, n_items x tiles x 256 >=
+ * 2^32, work_bytes below the plan or a handle without a token stream.  amdr_class_spans is the host-pointer twin: class c is
+ * the slot id n_terms + c; it validates (AMDR_EINVAL: item_ptr or cls_ptr not monotone from 0, a kind, length or distance
+ * out of range, member ids not strictly ascending, overlapping unequal slots in an unordered item), runs the union step
+ * for the classes and then this step in an array of its own on the BM25 handle's stream under its mutex, and returns only
+ * the items' lists, rebased to 0, with rows_cap applied to them alone.
+ * Mutations: amdr_bm25_add's rule; an update drops the token stream. */
+int amdr_class_spans_plan(int64_t n_items, int64_t cand_max, int64_t* work_bytes);
+int amdr_class_spans_device(amdr_bm25_t* bm25, const int64_t* item_ptr_dev, const int32_t* item_slots_dev,
+                            const int32_t* item_kind_dev, const int32_t* item_dist_dev, int64_t n_items,
+                            const int64_t* cls_ptr_dev, const int32_t* cls_terms_dev, int64_t n_cls, int64_t cls_first,
+                            int64_t n_before, int64_t cand_max, int64_t rows_cap, int64_t* list_ptr_dev, int32_t* docs_dev,
+                            int32_t* out_status_dev, void* work_dev, int64_t work_bytes, void* stream);
+int amdr_class_spans(amdr_bm25_t* bm25, const int64_t* item_ptr, const int32_t* item_slots, const int32_t* item_kind,
+                     const int32_t* item_dist, int64_t n_items, const int64_t* cls_ptr, const int32_t* cls_terms, int64_t n_cls,
+                     int64_t cand_max, int64_t rows_cap, int64_t* out_list_ptr, int32_t* out_docs, int32_t* out_status);
+
 /* ---- multi-GPU: merge per-shard top-k after the RCCL all-gather --------
  * No reference counterpart (the reference is single-process).
  * parts: [n_parts, nq, k_in] scores + GLOBAL ids (-1 padding); output

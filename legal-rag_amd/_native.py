@@ -68,6 +68,8 @@ SIGNATURES = {
     "amdr_term_scope_lists_device": "P" + "P" * 9 + "l" * 6 + "PPP" + "PlP", "amdr_term_scope_lists": "P" + "P" * 9 + "l" * 6 + "PPP",
     "amdr_span_lists_plan": "llP", "amdr_span_lists_device": "PPPPP" + "lll" + "PPP" + "PlP", "amdr_span_lists": "PPPPP" + "lll" + "PPP",
     "amdr_union_lists_plan": "llP", "amdr_union_lists_device": "PPP" + "lll" + "PPP" + "PlP", "amdr_union_lists": "PPP" + "ll" + "PPP",
+    "amdr_class_spans_plan": "llP", "amdr_class_spans_device": "PPPPP" + "l" + "PP" + "lllll" + "PPP" + "PlP",
+    "amdr_class_spans": "PPPPP" + "l" + "PP" + "lll" + "PPP",
 }
 EXPORTS = tuple(SIGNATURES)  # every symbol include/amdretrieval.h declares (checked by tests/test_abi.py)
 _KIND = {"P": C.c_void_p, "i": C.c_int32, "l": C.c_int64, "d": C.c_double}
@@ -247,6 +249,14 @@ def union_lists_plan(n_items: int, n_docs: int) -> int:
     arithmetic."""
     out = C.c_int64(0)
     _check(load().amdr_union_lists_plan(C.c_int64(n_items), C.c_int64(n_docs), C.byref(out)), "amdr_union_lists_plan")
+    return int(out.value)
+
+
+def class_spans_plan(n_items: int, cand_max: int) -> int:
+    """Workspace bytes of BM25Index.class_spans_device(n_items class spans, longest driver cand_max) — host-only arithmetic:
+    per cell (item, tile of PHRASE_TILE candidates) two i64 and the parked ranks."""
+    out = C.c_int64(0)
+    _check(load().amdr_class_spans_plan(C.c_int64(n_items), C.c_int64(cand_max), C.byref(out)), "amdr_class_spans_plan")
     return int(out.value)
 
 
@@ -815,6 +825,44 @@ class BM25Index(_Handle):
                                               C.c_int64(n_before), C.c_int64(rows_cap), _vp(list_ptr_ptr), _vp(docs_ptr),
                                               _vp(status_ptr), _vp(work_ptr), C.c_int64(work_bytes), _vp(stream)),
                "amdr_union_lists_device")
+
+    # -- class spans: a Prefix or a OneOf inside a phrase or a Near (amdr_class_spans, csrc/class_span.hip) ---------------
+    def class_spans(self, item_ptr, item_slots, item_kind, item_dist, cls_ptr, cls_terms, cand_max: int, rows_cap: int):
+        """The host twin: (list_ptr i64 [n + 1], docs i32 [list_ptr[-1]], status i32 [n]) of the items
+        item_slots[item_ptr[p] : item_ptr[p + 1]] of kind item_kind[p] and distance item_dist[p] (as span_lists) whose slot
+        ids are plain term ids or n_terms + c for class c, the strictly ascending member ids
+        cls_terms[cls_ptr[c] : cls_ptr[c + 1]].  Runs the union step for the classes and then the class step; returns only
+        the items' lists.  status as term_scope."""
+        pp, pt = _c(item_ptr, np.int64).ravel(), _c(item_slots, np.int32).ravel()
+        kd, ds = _c(item_kind, np.int32).ravel(), _c(item_dist, np.int32).ravel()
+        cp, ct = _c(cls_ptr, np.int64).ravel(), _c(cls_terms, np.int32).ravel()
+        if pp.size < 1 or kd.size != pp.size - 1 or ds.size != pp.size - 1 or cp.size < 1:
+            raise ValueError("class_spans: item_ptr [n + 1], item_kind [n], item_dist [n], cls_ptr [n_cls + 1]")
+        n, n_cls = pp.size - 1, cp.size - 1
+        lp = np.zeros(n + 1, dtype=np.int64)
+        docs = np.full(max(int(rows_cap), 1), -1, dtype=np.int32)
+        status = np.zeros(max(n, 1), dtype=np.int32)
+        pad = np.zeros(1, dtype=np.int32)
+        _check(load().amdr_class_spans(self._h, _p(pp, C.c_int64), _p(pt if pt.size else pad, C.c_int32),
+                                       _p(kd if n else pad, C.c_int32), _p(ds if n else pad, C.c_int32), C.c_int64(n),
+                                       _p(cp, C.c_int64), _p(ct if ct.size else pad, C.c_int32), C.c_int64(n_cls),
+                                       C.c_int64(cand_max), C.c_int64(rows_cap), _p(lp, C.c_int64), _p(docs, C.c_int32),
+                                       _p(status, C.c_int32)), "amdr_class_spans")
+        return lp, docs[:int(lp[-1])], status[:n]
+
+    def class_spans_device(self, item_ptr_ptr: int, item_slots_ptr: int, item_kind_ptr: int, item_dist_ptr: int, n_items: int,
+                           cls_ptr_ptr: int, cls_terms_ptr: int, n_cls: int, cls_first: int, n_before: int, cand_max: int,
+                           rows_cap: int, list_ptr_ptr: int, docs_ptr: int, status_ptr: int, work_ptr: int, work_bytes: int,
+                           stream: int = 0) -> None:
+        """The "_device" form: operands and outputs as device pointers; enqueues only.  Continues the list array whose
+        first n_before + 1 entries of list_ptr were written earlier on the same stream; class c is the slot id
+        n_terms + cls_first + c and its documents are list cls_first + c of that array (cls_first + n_cls <= n_before);
+        rows_cap is the capacity of the whole docs array."""
+        _check(load().amdr_class_spans_device(self._h, _vp(item_ptr_ptr), _vp(item_slots_ptr), _vp(item_kind_ptr),
+                                              _vp(item_dist_ptr), C.c_int64(n_items), _vp(cls_ptr_ptr), _vp(cls_terms_ptr),
+                                              C.c_int64(n_cls), C.c_int64(cls_first), C.c_int64(n_before), C.c_int64(cand_max),
+                                              C.c_int64(rows_cap), _vp(list_ptr_ptr), _vp(docs_ptr), _vp(status_ptr),
+                                              _vp(work_ptr), C.c_int64(work_bytes), _vp(stream)), "amdr_class_spans_device")
 
     def get_scores(self, queries: Sequence[Sequence[int]]) -> np.ndarray:
         q_terms, q_ptr = self.pack_queries(queries)

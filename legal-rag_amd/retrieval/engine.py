@@ -254,12 +254,19 @@ class HybridEngine:
         launches, needs no token stream) is enqueued behind the span or phrase step on the same stream — first, with
         n_before = 0, when there is none — and CONTINUES the same list array, sized for span_rows_cap + union_rows_cap; the
         term step then reads n_phr + n_near + n_union lists and the status tensor is i32 [n_cons + n_phr + n_near +
-        n_union].  Without a union the calls are those above."""
+        n_union].  Without a union the calls are those above.
+        A table with class spans (table.n_cspan > 0, a PhraseOf or a NearOf with a union among its slots): the class step
+        (amdr_class_spans_device, three launches, needs the token stream) is enqueued behind the union step on the same
+        stream and CONTINUES the same list array, sized for span_rows_cap + union_rows_cap + cspan_rows_cap: its classes are
+        the unions (cls_first = n_phr + n_near) and it reads their lists where the union step wrote them.  The term step
+        then reads n_phr + n_near + n_union + n_cspan lists and the status tensor grows by n_cspan.  Without a class span
+        the calls are those above."""
         self.check_term_scopes()
         n_cons, cand_max, rows_cap = int(table.n_cons), int(table.cand_max), int(table.rows_cap)
         n_phr = int(getattr(table, "n_phr", 0))
         n_near = int(getattr(table, "n_near", 0))
         n_union = int(getattr(table, "n_union", 0))
+        n_cspan = int(getattr(table, "n_cspan", 0))
         order = (0, 2, 4, 5, 1, 3, 6)  # the i64 arrays first: every one starts on a multiple of its item size
         parts = [(i, np.ascontiguousarray(table.ops[i], dtype=t).view(np.uint8))
                  for i, t in ((i, _native.BM25Index.TERM_OPS[i]) for i in order)]
@@ -272,6 +279,9 @@ class HybridEngine:
         if n_union:  # the items of the union step
             parts.insert(4, (12, np.ascontiguousarray(table.union_ops[0], dtype=np.int64).view(np.uint8)))
             parts.append((13, np.ascontiguousarray(table.union_ops[1], dtype=np.int32).view(np.uint8)))
+        if n_cspan:  # the items of the class step
+            parts.insert(4, (14, np.ascontiguousarray(table.cspan_ops[0], dtype=np.int64).view(np.uint8)))
+            parts.extend((15 + j, np.ascontiguousarray(table.cspan_ops[1 + j], dtype=np.int32).view(np.uint8)) for j in range(3))
         parts.append((7, np.ascontiguousarray(table.qscope, dtype=np.int32).view(np.uint8)))
         total = sum(p.size for _, p in parts)
         host, dev, ev = self._staging("tsc", max(total, 8))
@@ -284,12 +294,12 @@ class HybridEngine:
         base = dev.data_ptr()
         o_rows, o_status = 8 * (n_cons + 1), 8 * (n_cons + 1) + 8 * rows_cap
         n_span = n_phr + n_near
-        n_x = n_span + n_union  # the virtual lists of the term step
+        n_x = n_span + n_union + n_cspan  # the virtual lists of the term step
         out = self._grown("tso", o_status + 4 * (n_cons + n_x) + 8)
         lists = None
-        if n_x:  # ONE list array: the span (or phrase) step begins it, the union step continues it
+        if n_x:  # ONE list array: the span (or phrase) step begins it, the union step and the class step continue it
             span_cap = int(table.span_rows_cap) if n_near else int(table.phr_rows_cap)
-            list_cap = span_cap + int(getattr(table, "union_rows_cap", 0))
+            list_cap = span_cap + int(getattr(table, "union_rows_cap", 0)) + (int(table.cspan_rows_cap) if n_cspan else 0)
             o_docs = 8 * (n_x + 1)
             pout = self._grown("pho", o_docs + 4 * list_cap + 8)
             x_ptr, x_doc, x_status = pout.data_ptr(), pout.data_ptr() + o_docs, out.data_ptr() + o_status + 4 * n_cons
@@ -310,6 +320,14 @@ class HybridEngine:
                 uwork = self._grown("unw", u_bytes)
                 self.bm25.union_lists_device(base + where[12][0], base + where[13][0], n_union, n_span, list_cap, x_ptr, x_doc,
                                              x_status + 4 * n_span, uwork.data_ptr(), u_bytes, _stream())
+            if n_cspan:  # the class step: behind the unions, which are its classes
+                c_max = int(table.cspan_cand_max)
+                c_bytes = _native.class_spans_plan(n_cspan, c_max)
+                cwork = self._grown("csw", c_bytes)
+                u_ptr, u_terms = (base + where[12][0], base + where[13][0]) if n_union else (0, 0)
+                self.bm25.class_spans_device(base + where[14][0], base + where[15][0], base + where[16][0], base + where[17][0],
+                                             n_cspan, u_ptr, u_terms, n_union, n_span, n_span + n_union, c_max, list_cap, x_ptr,
+                                             x_doc, x_status + 4 * (n_span + n_union), cwork.data_ptr(), c_bytes, _stream())
             lists = (x_ptr, x_doc, n_x)
         work_bytes = _native.term_scope_plan(n_cons, cand_max)
         work = self._grown("tsw", work_bytes)

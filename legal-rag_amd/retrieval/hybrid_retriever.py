@@ -41,7 +41,7 @@ from .diversity import Diversity, resolve as _resolve_diversity
 from .graph_retriever import GraphRetriever
 from .rerankers import RerankerFactory, _to_doc_text
 from .scope import Scope, resolver_for
-from .terms import Near, Phrase, Prefix, Terms, pack as _pack_terms
+from .terms import Near, NearOf, Phrase, PhraseOf, Prefix, Terms, pack as _pack_terms  # noqa: F401 (NearOf, PhraseOf: re-exported)
 
 logger = logging.getLogger("legalrag.retrieval.hybrid_retriever")
 
@@ -234,7 +234,7 @@ class HybridRetriever:
                              f"be a row of the channel)")
         model = bm.bm25
         tt = _pack_terms([(scope, terms)], model.vocab(), model._doc_frequencies(), int(model.corpus_size),
-                         resolver_for(bm.chunks).rows, model.sorted_vocab() if terms.has_union else None)
+                         resolver_for(bm.chunks).rows, model.sorted_vocab() if terms.has_union or terms.has_class_span else None)
         if tt.cand_max == 0:
             return np.zeros(0, dtype=np.int64)
         lists = None
@@ -264,6 +264,21 @@ class HybridRetriever:
                 lists = (u_lp, u_docs)
             else:
                 lists = (np.concatenate([lists[0], lists[0][-1] + u_lp[1:]]), np.concatenate([lists[1], u_docs]))
+        if tt.n_cspan:  # the class spans behind the unions: the twin resolves the classes it needs itself, in its own array
+            bm.ensure_token_stream()
+            c_ptr, c_slots, c_kind, c_dist = tt.cspan_ops
+            first = len(model.vocab()) + tt.n_phr + tt.n_near  # union u is the twin's class u
+            c_lp, c_docs, c_status = bm.gpu_index().class_spans(c_ptr, np.where(c_slots >= first, c_slots - (tt.n_phr + tt.n_near),
+                                                                                 c_slots), c_kind, c_dist, *tt.union_ops,
+                                                                 tt.cspan_cand_max, tt.cspan_rows_cap)
+            if c_status.any():
+                c = int(np.flatnonzero(c_status)[0])
+                raise RuntimeError(f"{who}(terms=): {tt.cspans[c]!r} overflowed its bound (status {int(c_status[c])}); the "
+                                   f"host model and the resident BM25 index disagree")
+            if lists is None:
+                lists = (c_lp, c_docs)
+            else:
+                lists = (np.concatenate([lists[0], lists[0][-1] + c_lp[1:]]), np.concatenate([lists[1], c_docs]))
         _, rows, status = bm.gpu_index().term_scope(tt.ops, tt.cand_max, tt.rows_cap, lists=lists)
         if int(status[0]) != 0:
             raise RuntimeError(f"{who}(terms=): the term constraint overflowed its bound (status {int(status[0])}); the "
@@ -1119,8 +1134,9 @@ class HybridRetriever:
             term_table = _pack_terms([(scopes[i] if scopes is not None else None, terms[i] or Terms()) for i in idxs],
                                      model.vocab(), model._doc_frequencies(), int(model.corpus_size),
                                      resolver_for(store.chunks).rows,
-                                     model.sorted_vocab() if any(terms[i] is not None and terms[i].has_union for i in idxs) else None)
-            if term_table.n_phr or term_table.n_near:
+                                     model.sorted_vocab() if any(terms[i] is not None and (terms[i].has_union or terms[i].has_class_span)
+                                                              for i in idxs) else None)
+            if term_table.n_phr or term_table.n_near or term_table.n_cspan:
                 bm.ensure_token_stream()  # (made lazily: on the first phrase or Near, and again after a live update)
         elif scoped:
             table = resolver_for(store.chunks).table([scopes[i] for i in idxs])

@@ -24,6 +24,13 @@ stands wherever a token stands, also inside a tuple group: (OneOf("buyer", "purc
 (buyer OR purchaser) AND (goods OR merchandise).  `pack()` expands both into the term ids they name and the GPU merges the
 posting lists of each into one ascending, de-duplicated document list (amdr_union_lists, csrc/union_lists.hip) behind the
 lists of the phrases and the Nears.
+
+A `PhraseOf` and a `NearOf` are a phrase and a Near of token CLASSES: a member is a token, a Prefix or a OneOf, so
+PhraseOf(Prefix("secur"), "interest") is "secur! interest" and NearOf(Prefix("sell"), Prefix("good"), distance=5) is
+sell! /5 good!.  They are classes of their own — Phrase, Near and OneOf keep their constructors and their errors — and stand
+wherever a Phrase or a Near stands.  `pack()` resolves each member as it resolves a Prefix or a OneOf; an item of plain
+ids IS the plain Phrase / Near, every other one is a class span that the GPU resolves from the token stream and the
+unions' lists (amdr_class_spans, csrc/class_span.hip) behind the unions.
 """
 from __future__ import annotations
 
@@ -250,13 +257,159 @@ class OneOf:
         return any(m.within(tokens) if isinstance(m, Prefix) else m in tokens for m in self.members)
 
 
-Member = Union[str, Phrase, Near, Prefix, OneOf]
+def fills(slot, token: str) -> bool:
+    """Whether `token` FILLS `slot`, a member of a PhraseOf or a NearOf: it equals the str, starts with the Prefix's stem,
+    or fills a member of the OneOf."""
+    if isinstance(slot, str):
+        return token == slot
+    if isinstance(slot, Prefix):
+        return token.startswith(slot.stem)
+    return any(fills(m, token) for m in slot.members)
+
+
+def _slots(who: str, members, most: int) -> tuple:
+    if not 2 <= len(members) <= most:
+        raise ValueError(f"{who}: 2 to {most} members, got {len(members)}")
+    for m in members:
+        if not isinstance(m, (str, Prefix, OneOf)):
+            raise TypeError(f"{who}: a member is a str, a Prefix or a OneOf, got {type(m).__name__}")
+    return tuple(members)
+
+
+class PhraseOf:
+    """A phrase of token CLASSES ("secur! interest"): a chunk holds PhraseOf(m0, m1, ...) when its text has, at consecutive
+    positions (never across two chunks), a token that FILLS m0, one that fills m1, ...  A member — a slot — is a token
+    (str), a Prefix or a OneOf, and a token fills it when it equals the str, starts with the stem, or fills a member of the
+    OneOf.  2 to 16 members (ValueError); a Phrase, a Near, a PhraseOf or a NearOf as a member is a TypeError.
+    PhraseOf("a", "b") names the chunks Phrase("a", "b") names.  Accepted wherever a Phrase is.  Frozen and hashable."""
+    __slots__ = ("members",)
+
+    def __init__(self, *members) -> None:
+        object.__setattr__(self, "members", _slots("PhraseOf", members, PHRASE_MAX_LEN))
+
+    def __setattr__(self, name, value) -> None:
+        raise AttributeError("PhraseOf is frozen")
+
+    def __delattr__(self, name) -> None:
+        raise AttributeError("PhraseOf is frozen")
+
+    def __eq__(self, other) -> bool:
+        return isinstance(other, PhraseOf) and self.members == other.members
+
+    def __hash__(self) -> int:
+        return hash(("PhraseOf", self.members))
+
+    def __len__(self) -> int:
+        return len(self.members)
+
+    def __repr__(self) -> str:
+        return "PhraseOf(" + ", ".join(repr(m) for m in self.members) + ")"
+
+    def __reduce__(self):
+        return (PhraseOf, self.members)
+
+    def within(self, tokens: Sequence[str]) -> bool:
+        """Whether the token sequence `tokens` holds this phrase (the plain window scan)."""
+        L, want = len(self.members), self.members
+        return any(all(fills(want[j], tokens[p + j]) for j in range(L)) for p in range(len(tokens) - L + 1))
+
+
+class NearOf:
+    """Proximity of token CLASSES (sell! /5 good!): NearOf(m0, m1, ..., distance=n) with members as PhraseOf's.
+      ordered=False  some run of at most n + 1 consecutive tokens admits an assignment of the members to DISTINCT positions
+                     of the run, each token filling its member — a bipartite matching: NearOf(P, P, distance=n) needs two
+                     positions.
+      ordered=True   there are positions p0 < p1 < ... with token p_i filling member i and the last at most n behind the
+                     first.
+    2 to 8 members and 1 <= distance <= 255 (ValueError); a Phrase, a Near, a PhraseOf or a NearOf as a member is a
+    TypeError.  NearOf("a", "b", distance=5) names the chunks Near("a", "b", distance=5) names.  The GPU resolves the
+    unordered form only when the members' token sets are pairwise equal or disjoint: pack() raises ValueError for
+    NearOf("seller", Prefix("sell"), distance=3).  Accepted wherever a Near is.  Frozen and hashable."""
+    __slots__ = ("members", "distance", "ordered")
+
+    def __init__(self, *members, distance: int, ordered: bool = False) -> None:
+        members = _slots("NearOf", members, NEAR_MAX_TERMS)
+        if isinstance(distance, bool) or not isinstance(distance, (int, np.integer)):
+            raise TypeError(f"NearOf: distance is an int, got {type(distance).__name__}")
+        if not 1 <= int(distance) <= NEAR_MAX_DIST:
+            raise ValueError(f"NearOf: a distance of 1 to {NEAR_MAX_DIST}, got {int(distance)}")
+        object.__setattr__(self, "members", members)
+        object.__setattr__(self, "distance", int(distance))
+        object.__setattr__(self, "ordered", bool(ordered))
+
+    def __setattr__(self, name, value) -> None:
+        raise AttributeError("NearOf is frozen")
+
+    def __delattr__(self, name) -> None:
+        raise AttributeError("NearOf is frozen")
+
+    def _key(self):
+        return (self.members, self.distance, self.ordered)
+
+    def __eq__(self, other) -> bool:
+        return isinstance(other, NearOf) and self._key() == other._key()
+
+    def __hash__(self) -> int:
+        return hash(("NearOf",) + self._key())
+
+    def __len__(self) -> int:
+        return len(self.members)
+
+    def __repr__(self) -> str:
+        return ("NearOf(" + ", ".join(repr(m) for m in self.members) + f", distance={self.distance}"
+                + (", ordered=True" if self.ordered else "") + ")")
+
+    def __reduce__(self):
+        return (_make_near_of, (self.members, self.distance, self.ordered))
+
+    def within(self, tokens: Sequence[str]) -> bool:
+        """Whether the token sequence `tokens` holds this NearOf: every anchor with the earliest next match per member
+        (ordered), a bipartite matching by augmenting paths in every window (unordered)."""
+        n, want, M = self.distance, self.members, len(self.members)
+        if self.ordered:
+            for s in range(len(tokens)):
+                if not fills(want[0], tokens[s]):
+                    continue
+                j = 1
+                for t in tokens[s + 1:s + n + 1]:
+                    if fills(want[j], t):
+                        j += 1
+                        if j == M:
+                            return True
+            return False
+        for s in range(len(tokens)):
+            win = tokens[s:s + n + 1]
+            if len(win) < M:
+                break  # (every later window is no longer)
+            may = [[q for q, t in enumerate(win) if fills(m, t)] for m in want]  # the positions each member may take
+            taken: Dict[int, int] = {}  # position -> the member it is assigned to
+
+            def place(j: int, seen: set) -> bool:
+                for q in may[j]:
+                    if q in seen:
+                        continue
+                    seen.add(q)
+                    if q not in taken or place(taken[q], seen):
+                        taken[q] = j
+                        return True
+                return False
+            if all(place(j, set()) for j in range(M)):
+                return True
+        return False
+
+
+def _make_near_of(members, distance, ordered) -> NearOf:
+    return NearOf(*members, distance=distance, ordered=ordered)
+
+
+Member = Union[str, Phrase, Near, Prefix, OneOf, PhraseOf, NearOf]
 Group = Tuple[Member, ...]
-_MEMBERS = (str, Phrase, Near, Prefix, OneOf)
+_MEMBERS = (str, Phrase, Near, Prefix, OneOf, PhraseOf, NearOf)
+_SPANS = (Phrase, Near, PhraseOf, NearOf)  # what needs the token SEQUENCE
 
 
 def _member(t) -> Member:
-    if isinstance(t, (Near, Prefix)):
+    if isinstance(t, (Near, Prefix, PhraseOf, NearOf)):
         return t
     if isinstance(t, OneOf):
         return t.members[0] if len(t) == 1 else t  # one member is that member
@@ -326,18 +479,22 @@ class Terms:
     def has_union(self) -> bool:
         return any(isinstance(t, (Prefix, OneOf)) for _, g in self.groups() for t in g)
 
+    @property
+    def has_class_span(self) -> bool:
+        return any(isinstance(t, (PhraseOf, NearOf)) for _, g in self.groups() for t in g)
+
     def matches(self, tokens) -> bool:
-        """The rule on one document's tokens (host check; the kernels apply term_scope_rule.hpp, phrase_rule.hpp and
-        union_rule.hpp): a token set or sequence — with a Phrase or a Near present, the token SEQUENCE in text order
-        (TypeError for a set); a Prefix or a OneOf takes either."""
-        if self.has_phrase or self.has_near:
+        """The rule on one document's tokens (host check; the kernels apply term_scope_rule.hpp, phrase_rule.hpp,
+        union_rule.hpp and class_span_rule.hpp): a token set or sequence — with a Phrase, a Near, a PhraseOf or a NearOf
+        present, the token SEQUENCE in text order (TypeError for a set); a Prefix or a OneOf takes either."""
+        if self.has_phrase or self.has_near or self.has_class_span:
             if isinstance(tokens, (set, frozenset, dict)) or not isinstance(tokens, Sequence):
-                raise TypeError(f"Terms.matches: a Terms with a {'Phrase' if self.has_phrase else 'Near'} needs the "
-                                f"document's token sequence, not a set")
+                what = "Phrase" if self.has_phrase else "Near" if self.has_near else "PhraseOf or a NearOf"
+                raise TypeError(f"Terms.matches: a Terms with a {what} needs the document's token sequence, not a set")
             have = set(tokens)
         else:
             have = tokens if isinstance(tokens, (set, frozenset, dict)) else set(tokens)
-        sat = lambda g: all(t.within(tokens) if isinstance(t, (Phrase, Near)) else  # noqa: E731
+        sat = lambda g: all(t.within(tokens) if isinstance(t, _SPANS) else  # noqa: E731
                             t.within(have) if isinstance(t, (Prefix, OneOf)) else t in have for t in g)
         return (all(sat(g) for g in self.all_of or ()) and (self.any_of is None or any(sat(g) for g in self.any_of))
                 and not any(sat(g) for g in self.none_of or ()))
@@ -393,6 +550,19 @@ class TermTable:
     unions = ()          # per union the first Prefix / OneOf of the batch that names it
     union_rows_cap = 0   # the sum of the upper bounds min(n_docs, the sum of the tokens' document frequencies)
 
+    # the class spans of the batch (a PhraseOf or a NearOf with at least one slot that is a union), equal ones — compared
+    # after resolution — stored once; class span c is term id len(vocab) + n_phr + n_near + n_union + c, behind the unions
+    # (amdr_class_spans).  A slot is a plain term id or the term id of a union.  Class-level defaults as the unions'
+    cspan_ops = (np.zeros(1, dtype=np.int64), np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.int32),
+                 np.zeros(0, dtype=np.int32))  # ptr i64 [n_cspan + 1], slots i32, kind i32 (SpanKind), dist i32
+    cspans = ()          # per class span the first PhraseOf / NearOf of the batch that names it
+    cspan_cand_max = 0   # the largest of the upper bounds: the smallest slot bound of each item
+    cspan_rows_cap = 0   # their sum
+
+    @property
+    def n_cspan(self) -> int:
+        return len(self.cspans)
+
     @property
     def n_phr(self) -> int:
         return len(self.phrases)
@@ -418,9 +588,12 @@ class TermTable:
         return self.phrases[i] if i < self.n_phr else self.nears[i - self.n_phr]
 
     def list_item(self, i: int):
-        """What virtual list i of the term step stands for: the Phrase, the Near, or the union's Prefix / OneOf."""
+        """What virtual list i of the term step stands for: the Phrase, the Near, the union's Prefix / OneOf, or the class
+        span's PhraseOf / NearOf."""
         n_span = self.n_phr + self.n_near
-        return self.span_item(i) if i < n_span else self.unions[i - n_span]
+        if i < n_span:
+            return self.span_item(i)
+        return self.unions[i - n_span] if i < n_span + self.n_union else self.cspans[i - n_span - self.n_union]
 
 
 def prefix_tokens(stem: str, sorted_vocab: Sequence[str]) -> List[str]:
@@ -454,7 +627,15 @@ def pack(pairs: Sequence[Tuple[Optional[Scope], Terms]], vocab: Mapping[str, int
     stored once — Prefix("sell") and the OneOf of its tokens share a list — and union u stands as the term id
     len(vocab) + n_phr + n_near + u, behind the Nears, with the upper bound min(n_docs, the sum of the ids' document
     frequencies) of its list's length: union_rows_cap is the sum of these, and the drivers are computed with them.  A
-    table without a union is field for field the table of the phrases and the Nears alone."""
+    table without a union is field for field the table of the phrases and the Nears alone.
+    A PhraseOf or a NearOf has each slot resolved as a Prefix or a OneOf is (a str: its term id or -1).  When every slot is
+    a plain id the item IS the plain Phrase / Near of those tokens and is stored as that one: the same slot, the same list,
+    the old step.  Otherwise it is a class span (amdr_class_spans): a union among its slots registers a union item even when
+    nothing else in the batch uses it, equal class spans — compared after resolution — are stored once, and class span c
+    stands as the term id len(vocab) + n_phr + n_near + n_union + c, behind the unions, with the smallest slot bound (df of
+    a plain id, 0 of the id -1, the union's bound) as its upper bound: cspan_cand_max / cspan_rows_cap.  An unordered NearOf
+    whose slots' id sets intersect without being equal is a ValueError: the device's first-unfilled-slot tally is the
+    matching only for pairwise equal or disjoint slots.  A table without a class span is field for field the table without."""
     n_vocab = len(vocab)
     df_by_id = np.zeros(n_vocab, dtype=np.int64)
     for w, t in vocab.items():
@@ -462,6 +643,7 @@ def pack(pairs: Sequence[Tuple[Optional[Scope], Terms]], vocab: Mapping[str, int
     union_slot: Dict[Tuple[int, ...], int] = {}
     union_first: List[Any] = []
     union_bound: List[int] = []
+    union_ids: List[Tuple[int, ...]] = []
     sorted_held = [sorted_vocab]
 
     def union_id(t):
@@ -483,6 +665,7 @@ def pack(pairs: Sequence[Tuple[Optional[Scope], Terms]], vocab: Mapping[str, int
         if u is None:
             u = union_slot[ids] = len(union_bound)
             union_first.append(t)
+            union_ids.append(ids)
             union_bound.append(min(int(n_docs), int(sum(df_by_id[i] for i in ids))))
         return ("u", u)
 
@@ -493,7 +676,41 @@ def pack(pairs: Sequence[Tuple[Optional[Scope], Terms]], vocab: Mapping[str, int
     near_ids: List[List[int]] = []
     near_bound: List[int] = []
 
+    cspan_slot: Dict[Any, int] = {}
+    cspan_first: List[Any] = []
+    cspan_slots: List[list] = []
+    cspan_bound: List[int] = []
+    word_held: List[Optional[Dict[int, str]]] = [None]
+
+    def class_span_id(t):
+        """The id a PhraseOf or a NearOf stands for: that of the equal plain Phrase / Near, or the placeholder ("c", c)."""
+        near = isinstance(t, NearOf)
+        ids = [vocab.get(m, -1) if isinstance(m, str) else union_id(m) for m in t.members]
+        if all(not isinstance(i, tuple) and (i >= 0 or isinstance(m, str)) for i, m in zip(ids, t.members)):
+            if word_held[0] is None:
+                word_held[0] = {i: w for w, i in vocab.items()}
+            words = [m if isinstance(m, str) else word_held[0][i] for i, m in zip(ids, t.members)]
+            return term_id(Near(*words, distance=t.distance, ordered=t.ordered) if near else Phrase(*words))
+        sets = [frozenset(union_ids[i[1]]) if isinstance(i, tuple) else frozenset([i] if i >= 0 else []) for i in ids]
+        if near and not t.ordered:
+            for j in range(len(sets)):
+                for k in range(j):
+                    if sets[j] & sets[k] and sets[j] != sets[k]:
+                        raise ValueError(f"{t!r}: members {k} and {j} name overlapping, unequal token sets "
+                                         f"({t.members[k]!r}, {t.members[j]!r}); the unordered form is resolved only for "
+                                         f"members that are pairwise equal or disjoint")
+        key = (2 if near and t.ordered else 1 if near else 0, tuple(ids), t.distance if near else 0)
+        c = cspan_slot.get(key)
+        if c is None:
+            c = cspan_slot[key] = len(cspan_bound)
+            cspan_first.append(t)
+            cspan_slots.append(ids)
+            cspan_bound.append(min(union_bound[i[1]] if isinstance(i, tuple) else int(df_by_id[i]) if i >= 0 else 0 for i in ids))
+        return ("c", c)
+
     def term_id(t):
+        if isinstance(t, (PhraseOf, NearOf)):  # (numbered behind the unions: a placeholder, or the plain form's id)
+            return class_span_id(t)
         if isinstance(t, Near):  # (numbered behind the phrases once all of those are known: a placeholder until then)
             j = near_slot.get(t)
             if j is None:
@@ -540,6 +757,7 @@ def pack(pairs: Sequence[Tuple[Optional[Scope], Terms]], vocab: Mapping[str, int
         qscope[i] = j
     n_phr = len(phr_bound)
     behind = {"n": n_vocab + n_phr, "u": n_vocab + n_phr + len(near_bound)}
+    behind["c"] = behind["u"] + len(union_bound)
     cons_groups = [[(kind, [behind[t[0]] + t[1] if isinstance(t, tuple) else t for t in ids]) for kind, ids in groups]
                    for groups in cons_groups]
     for groups in cons_groups:
@@ -553,7 +771,7 @@ def pack(pairs: Sequence[Tuple[Optional[Scope], Terms]], vocab: Mapping[str, int
     ops = (np.asarray(grp_ptr, dtype=np.int64), np.asarray(grp_kind, dtype=np.int32), np.asarray(grp_term_ptr, dtype=np.int64),
            np.asarray(grp_terms, dtype=np.int32), base_ptr,
            np.concatenate(bases) if bases else np.zeros(0, dtype=np.int64), np.asarray(cons_base, dtype=np.int32))
-    df_all = np.concatenate([df_by_id, np.asarray(phr_bound + near_bound + union_bound, dtype=np.int64)])  # (all known by now)
+    df_all = np.concatenate([df_by_id, np.asarray(phr_bound + near_bound + union_bound + cspan_bound, dtype=np.int64)])  # (all known by now)
     lens_a = np.asarray([driver_length(g, df_all, int(bases[b].size) if b >= 0 else None, n_docs)
                          for g, b in zip(cons_groups, cons_base)], dtype=np.int64)
     tt = TermTable(ops, qscope, len(cons_base), len(grp_kind), len(bases), lens_a,
@@ -575,4 +793,11 @@ def pack(pairs: Sequence[Tuple[Optional[Scope], Terms]], vocab: Mapping[str, int
         np.cumsum([len(ids) for ids in union_slot], out=u_ptr[1:])
         tt.union_ops = (u_ptr, np.asarray([i for ids in union_slot for i in ids], dtype=np.int32))
         tt.unions, tt.union_rows_cap = tuple(union_first), int(sum(union_bound))
+    if cspan_slot:
+        c_ptr = np.zeros(len(cspan_slot) + 1, dtype=np.int64)
+        np.cumsum([len(ids) for ids in cspan_slots], out=c_ptr[1:])
+        tt.cspan_ops = (c_ptr, np.asarray([behind["u"] + i[1] if isinstance(i, tuple) else i for ids in cspan_slots for i in ids],
+                                          dtype=np.int32),
+                        np.asarray([k[0] for k in cspan_slot], dtype=np.int32), np.asarray([k[2] for k in cspan_slot], dtype=np.int32))
+        tt.cspans, tt.cspan_cand_max, tt.cspan_rows_cap = tuple(cspan_first), max(cspan_bound), int(sum(cspan_bound))
     return tt
