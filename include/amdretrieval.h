@@ -236,7 +236,8 @@ int amdr_bm25_ndocs(const amdr_bm25_t* h, int64_t* n);
  * the handle still in flight is the caller's to finish first (the arrays it reads are freed); workspaces are sized per
  * call from n_docs, so an eager "_device" call after an add grows its workspace if it has to (amdr_workspace_growths
  * shows it), and a captured graph holds the old arrays and sizes and must be re-reserved (amdr_bm25_reserve) and
- * captured again.  The arrival counters of the one-launch serving step stay as they are. */
+ * captured again.  The arrival counters of the one-launch serving step stay as they are.  A successful add drops the
+ * token stream (amdr_bm25_set_tokens); amdr_bm25_add_carry below keeps it current instead. */
 int amdr_bm25_add(amdr_bm25_t* h, const int64_t* term_ptr_add, const int32_t* post_doc_add, const int32_t* post_tf_add,
                   const double* idf, const int32_t* doc_len_add, int64_t n_terms, int64_t n_add, double avgdl);
 /* Remove n_remove documents (the reference has no removal: a corpus that shrinks takes the full re-fit + reload of
@@ -264,7 +265,8 @@ int amdr_bm25_add(amdr_bm25_t* h, const int64_t* term_ptr_add, const int32_t* po
  * call the device also holds 2 B per old posting, 4 B per old document and 8 B per term of scratch).  Runs inside the
  * handle's mutex.  It is a mutation in the sense of the rule at the top of this file, and the rules for in-flight
  * "_device" work, for workspaces and for captured graphs are those of amdr_bm25_add: finish the work first, reserve and
- * capture again.  The arrival counters of the one-launch serving step stay as they are. */
+ * capture again.  The arrival counters of the one-launch serving step stay as they are.  A successful remove drops the
+ * token stream (amdr_bm25_set_tokens); amdr_bm25_remove_carry below keeps it current instead. */
 int amdr_bm25_remove(amdr_bm25_t* h, const int64_t* remove_ids, int64_t n_remove, const int32_t* term_map,
                      int64_t n_terms_new, const double* idf, double avgdl);
 /* Summed device time of the passes of the last successful amdr_bm25_remove, in ms between events on the handle's stream
@@ -301,13 +303,56 @@ int amdr_bm25_remove_kernel_ms(amdr_bm25_t* h, double* ms);
  * posting, 8 B per new term), 12 B per new term and 12 B per replaced document.  Runs inside the handle's mutex.  It is
  * a mutation in the sense of the rule at the top of this file, and the rules for in-flight "_device" work and for
  * captured graphs are those of amdr_bm25_add: finish the work first, reserve and capture again.  n_docs does not change,
- * so no workspace grows.  The arrival counters of the one-launch serving step stay as they are. */
+ * so no workspace grows.  The arrival counters of the one-launch serving step stay as they are.  A successful replace
+ * drops the token stream (amdr_bm25_set_tokens); amdr_bm25_replace_carry below keeps it current instead. */
 int amdr_bm25_replace(amdr_bm25_t* h, const int64_t* replace_ids, int64_t n_rep, const int64_t* term_ptr_add,
                       const int32_t* post_doc_add, const int32_t* post_tf_add, const int32_t* doc_len_add,
                       const int32_t* term_map, int64_t n_terms_new, const double* idf, double avgdl);
 /* Summed device time of the passes of the last successful amdr_bm25_replace, in ms between events on the handle's stream
  * (scripts/bench_replace.py sets it against the passes' algorithmic bytes); -1 before the first replace. */
 int amdr_bm25_replace_kernel_ms(amdr_bm25_t* h, double* ms);
+/* The carrying forms of the three updates: the plain call's arguments in the plain call's order, then the token arguments.
+ * The index part IS the plain call's (one body, csrc/bm25_update.hip): the same validation, the same bytes afterwards, the
+ * same counters and the same *_kernel_ms.  What differs is the token stream of amdr_bm25_set_tokens:
+ *   with a resident stream, a successful call leaves the stream that amdr_bm25_set_tokens makes of the edited corpus, byte
+ *   for byte (amdr_bm25_read_tokens), instead of dropping it, and amdr_bm25_tokens_info reports (1, the new token count);
+ *   without a resident stream the call is the plain call: the token arrays are validated and otherwise unused, and no
+ *   stream appears.
+ * tok_ptr_add[n_add + 1] (n_rep + 1 in a replace), tok_add[tok_ptr_add[last]]: local document i's text as term ids over the
+ * NEW term table, in text order; tok_add may be null when the arrays hold no token.  A removal brings no text and takes no
+ * new array.  The new stream:
+ *   add      the old stream with the added documents behind it (old term ids keep their meaning);
+ *   remove   the survivors' documents in their old order, every token t rewritten to term_map[t] (null: the identity);
+ *   replace  document replace_ids[i] takes local i's tokens, every other document keeps its own, rewritten through
+ *            term_map (null: the identity);
+ * and in all three the new doc_ptr is the exclusive 64-bit scan of the NEW doc_len.  Every position is 64-bit: a stream may
+ * pass 2^31 tokens.  The work is one device pass over the NEW tokens (tiles of 2 048 output tokens, csrc/tok_carry_rule.hpp:
+ * one 4 B read, one 4 B gather of the term map, one 4 B write per token; no atomics, deterministic) plus host work
+ * proportional to the update: the add's token arrays are validated as amdr_bm25_set_tokens validates a stream, against
+ * doc_len_add and n_terms (n_terms_new) — AMDR_EINVAL, handle unchanged: a null tok_ptr_add, a null tok_add with tokens,
+ * tok_ptr_add[0] != 0 or not monotone, a run that is not doc_len_add[i] tokens long, a token outside the new term table.
+ * What only the device sees — a token of a surviving document whose term is mapped to -1 (the flag the counting passes
+ * raise for such a posting), a gather index outside its array — is read before the swap: AMDR_EINVAL, index and stream as
+ * they were.  Staging: the new stream is built beside the old one and committed together with the index, after the
+ * handle's stream has finished, and nothing can fail after that; any failure, AMDR_ENOMEM for the second copy of the
+ * stream included, fails the whole update and leaves index AND stream as they were.  Transient memory on top of the plain
+ * call's: the second copy of the stream (4 B per new token and 8 B per document), the add's stream (4 B per added token,
+ * 8 B per added document), 8 B per document of scratch for the scan, and in a remove 4 B per surviving document.
+ * n_add / n_remove / n_rep == 0 is the plain call's no-op: nothing is read and the stream stays.  Mutations in the sense of
+ * the rule at the top of this file, as the plain calls are. */
+int amdr_bm25_add_carry(amdr_bm25_t* h, const int64_t* term_ptr_add, const int32_t* post_doc_add, const int32_t* post_tf_add,
+                        const double* idf, const int32_t* doc_len_add, int64_t n_terms, int64_t n_add, double avgdl,
+                        const int64_t* tok_ptr_add, const int32_t* tok_add);
+int amdr_bm25_remove_carry(amdr_bm25_t* h, const int64_t* remove_ids, int64_t n_remove, const int32_t* term_map,
+                           int64_t n_terms_new, const double* idf, double avgdl);
+int amdr_bm25_replace_carry(amdr_bm25_t* h, const int64_t* replace_ids, int64_t n_rep, const int64_t* term_ptr_add,
+                            const int32_t* post_doc_add, const int32_t* post_tf_add, const int32_t* doc_len_add,
+                            const int32_t* term_map, int64_t n_terms_new, const double* idf, double avgdl,
+                            const int64_t* tok_ptr_add, const int32_t* tok_add);
+/* Summed device time of the carry passes (the scan of the new lengths and the pass over the new tokens) of the last
+ * successful carrying update that carried a stream, in ms between events on the handle's stream
+ * (scripts/bench_tokens_carry.py sets it against the pass's algorithmic bytes); -1 before the first one. */
+int amdr_bm25_carry_kernel_ms(amdr_bm25_t* h, double* ms);
 /* Replaces so far (amdr_bm25_info keeps its six words: a replace touches neither [3] nor [5]). */
 int amdr_bm25_replaces(amdr_bm25_t* h, int64_t* n);
 /* out6: [0] n_docs, [1] n_terms, [2] nnz (postings), [3] adds so far, [4] the tile length in postings of the merge
@@ -327,7 +372,7 @@ int amdr_bm25_read(amdr_bm25_t* h, int64_t* term_ptr, int32_t* post_doc, int32_t
  * [0, n_terms), doc_ptr[d + 1] - doc_ptr[d] != doc_len[d] for any d (the handle's doc_len is read once for this: the check
  * that catches a stream made for another state of the index).  A second call replaces the stream.  amdr_bm25_add /
  * _remove / _replace renumber documents and terms: a SUCCESSFUL call of any of them DROPS the stream (a failed one leaves
- * it) and the caller sets a new one.  Setting a stream is a mutation in the sense of the rule at the top of this file.
+ * it) and the caller sets a new one, or calls their carrying forms (amdr_bm25_*_carry), which keep it current.  Setting a stream is a mutation in the sense of the rule at the top of this file.
  * Searches and amdr_term_scope* calls without virtual lists behave exactly as without a stream. */
 int amdr_bm25_set_tokens(amdr_bm25_t* h, const int64_t* doc_ptr, const int32_t* tokens);
 /* out2: [0] 1 if a token stream is resident else 0, [1] its token count (0 without one) */

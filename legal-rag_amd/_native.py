@@ -36,7 +36,7 @@ SIGNATURES = {
     "amdr_dense_ntotal": "PP", "amdr_dense_dim": "PP", "amdr_dense_reserve": "Pii", "amdr_dense_search": "PPiiPP",
     "amdr_dense_search_device": "PPiiPPP", "amdr_dense_search_fuse_device": "PPiiPPPPiPPPPPPPP", "amdr_hybrid_small_device": "PPPPPiiiPPPPPPPPPPPP", "amdr_hybrid_batch_device": "PPPPPiiiPPPPPPPPPPPP", "amdr_dense_small_create": "PP", "amdr_dense_small_approx_device": "PPiPlPP", "amdr_dense_small_destroy": "P", "amdr_dense_two_pass_fallbacks": "PP", "amdr_dense_read_rows": "PllP", "amdr_dense_score_rows": "PPiPiP",
     "amdr_dense_plan_info": "PiiPi", "amdr_dense_workspace_plan": "liiiiiP", "amdr_dense_hi_counters": "PP", "amdr_dense_image_build": "P", "amdr_dense_image_drop": "P", "amdr_dense_image_info": "PP", "amdr_dense_profile_begin": "Pi", "amdr_dense_profile_end": "PPP", "amdr_dense_destroy": "P",
-    "amdr_bm25_create": "PPPPPlldddiP", "amdr_bm25_ndocs": "PP", "amdr_bm25_add": "PPPPPPlld", "amdr_bm25_info": "PP", "amdr_bm25_add_kernel_ms": "PP", "amdr_bm25_remove": "PPlPlPd", "amdr_bm25_remove_kernel_ms": "PP", "amdr_bm25_replace": "PPlPPPPPlPd", "amdr_bm25_replace_kernel_ms": "PP", "amdr_bm25_replaces": "PP", "amdr_bm25_read": "PPPPPPP", "amdr_bm25_set_tokens": "PPP", "amdr_bm25_tokens_info": "PP", "amdr_bm25_read_tokens": "PPP", "amdr_bm25_reserve": "Piil", "amdr_bm25_workspace_plan": "liiiiP", "amdr_bm25_plan_info": "PiiPi",
+    "amdr_bm25_create": "PPPPPlldddiP", "amdr_bm25_ndocs": "PP", "amdr_bm25_add": "PPPPPPlld", "amdr_bm25_info": "PP", "amdr_bm25_add_kernel_ms": "PP", "amdr_bm25_remove": "PPlPlPd", "amdr_bm25_remove_kernel_ms": "PP", "amdr_bm25_replace": "PPlPPPPPlPd", "amdr_bm25_replace_kernel_ms": "PP", "amdr_bm25_add_carry": "PPPPPPlldPP", "amdr_bm25_remove_carry": "PPlPlPd", "amdr_bm25_replace_carry": "PPlPPPPPlPdPP", "amdr_bm25_carry_kernel_ms": "PP", "amdr_bm25_replaces": "PP", "amdr_bm25_read": "PPPPPPP", "amdr_bm25_set_tokens": "PPP", "amdr_bm25_tokens_info": "PP", "amdr_bm25_read_tokens": "PPP", "amdr_bm25_reserve": "Piil", "amdr_bm25_workspace_plan": "liiiiP", "amdr_bm25_plan_info": "PiiPi",
     "amdr_bm25_search": "PPPiiPP", "amdr_bm25_search_device": "PPPiiPPP", "amdr_bm25_scores": "PPPiP",
     "amdr_bm25_destroy": "P",
     "amdr_tokenizer_create": "PPlP", "amdr_tokenizer_encode": "PPPiPlPP", "amdr_tokenizer_encode_joined": "PPliPlPP", "amdr_tokenizer_encode_ptrs": "PPPiPlPP", "amdr_tokenizer_spans": "PlPPiP",
@@ -546,35 +546,52 @@ class BM25Index(_Handle):
                                     C.byref(self._h)), "amdr_bm25_create")
         self._arrs = None  # the library holds its own device copy
 
-    def add(self, term_ptr_add, post_doc_add, post_tf_add, idf, doc_len_add, avgdl: float) -> None:
+    @staticmethod
+    def _token_args(tokens, n_docs: int, what: str):
+        """(tok_ptr_add i64 [n_docs + 1], tok_add i32 or None when it is empty) of a carrying update."""
+        tp, tk = _c(tokens[0], np.int64), _c(tokens[1], np.int32)
+        if tp.ndim != 1 or tk.ndim != 1 or tp.shape[0] != n_docs + 1 or (n_docs >= 0 and tk.shape[0] < int(tp[-1])):
+            raise ValueError(f"{what}: tokens = (tok_ptr_add [n + 1], tok_add [tok_ptr_add[-1]])")
+        return tp, (tk if tk.shape[0] else None)
+
+    def add(self, term_ptr_add, post_doc_add, post_tf_add, idf, doc_len_add, avgdl: float, tokens=None) -> None:
         """Append documents (amdr_bm25_add): the added documents' own term-major CSR over the new term table (local
         document ids from 0; len(term_ptr_add) - 1 = the new number of terms >= n_terms), their lengths, the WHOLE new
         idf vector and the new avgdl.  Afterwards the index is what BM25Index makes of the concatenated arrays, bit for
-        bit.  A "_device" caller finishes its work first and reserves again."""
+        bit.  A "_device" caller finishes its work first and reserves again.  The token stream is dropped; with
+        tokens = (tok_ptr_add [n_add + 1], tok_add) — the added documents' texts as term ids over the new table — the call
+        is amdr_bm25_add_carry: a resident stream gets the added documents behind it instead."""
         tp, pd, pt = _c(term_ptr_add, np.int64), _c(post_doc_add, np.int32), _c(post_tf_add, np.int32)
         idf_, dl = _c(idf, np.float64), _c(doc_len_add, np.int32)
         if tp.ndim != 1 or tp.shape[0] < 1 or idf_.shape != (tp.shape[0] - 1,) or pd.shape != pt.shape:
             raise ValueError("add: term_ptr_add [V + 1], idf [V], post_doc_add and post_tf_add of one length")
         if dl.shape[0] and (pd.shape[0] < int(tp[-1])):
             raise ValueError("add: term_ptr_add points past the postings")
-        _check(load().amdr_bm25_add(self._h, _p(tp, C.c_int64), _p(pd, C.c_int32), _p(pt, C.c_int32), _p(idf_, C.c_double),
-                                    _p(dl, C.c_int32), C.c_int64(tp.shape[0] - 1), C.c_int64(dl.shape[0]),
-                                    C.c_double(avgdl)), "amdr_bm25_add")
+        args = (self._h, _p(tp, C.c_int64), _p(pd, C.c_int32), _p(pt, C.c_int32), _p(idf_, C.c_double), _p(dl, C.c_int32),
+                C.c_int64(tp.shape[0] - 1), C.c_int64(dl.shape[0]), C.c_double(avgdl))
+        if tokens is None:
+            _check(load().amdr_bm25_add(*args), "amdr_bm25_add")
+        else:
+            kp, kt = self._token_args(tokens, int(dl.shape[0]), "add")
+            _check(load().amdr_bm25_add_carry(*args, _p(kp, C.c_int64), None if kt is None else _p(kt, C.c_int32)),
+                   "amdr_bm25_add_carry")
         self.n_docs, self.n_terms = self.info()[:2]
 
-    def remove(self, remove_ids, idf, avgdl: float, term_map=None) -> None:
+    def remove(self, remove_ids, idf, avgdl: float, term_map=None, carry: bool = False) -> None:
         """Remove documents (amdr_bm25_remove): remove_ids strictly ascending old ids (not all of them); the survivors are
         renumbered 0 .. n-1 in their old order.  term_map[n_terms]: the new id of each old term or -1, a bijection onto
         [0, len(idf)) (None: the identity, len(idf) == n_terms); idf: the WHOLE new vector; avgdl: the new value.
         Afterwards the index is what BM25Index makes of the survivors' arrays, bit for bit.  A "_device" caller finishes
-        its work first and reserves again."""
+        its work first and reserves again.  The token stream is dropped; carry=True is amdr_bm25_remove_carry: a resident
+        stream keeps the survivors' texts, rewritten through the map."""
         ids, idf_ = _c(remove_ids, np.int64), _c(idf, np.float64)
         tm = None if term_map is None else _c(term_map, np.int32)
         if ids.ndim != 1 or idf_.ndim != 1 or (tm is not None and tm.shape != (self.n_terms,)):
             raise ValueError("remove: remove_ids [n_remove], idf [n_terms_new], term_map [n_terms] or None")
-        _check(load().amdr_bm25_remove(self._h, _p(ids, C.c_int64), C.c_int64(ids.shape[0]),
-                                       None if tm is None else _p(tm, C.c_int32), C.c_int64(idf_.shape[0]),
-                                       _p(idf_, C.c_double), C.c_double(avgdl)), "amdr_bm25_remove")
+        name = "amdr_bm25_remove_carry" if carry else "amdr_bm25_remove"
+        _check(getattr(load(), name)(self._h, _p(ids, C.c_int64), C.c_int64(ids.shape[0]),
+                                     None if tm is None else _p(tm, C.c_int32), C.c_int64(idf_.shape[0]),
+                                     _p(idf_, C.c_double), C.c_double(avgdl)), name)
         self.n_docs, self.n_terms = self.info()[:2]
 
     def remove_kernel_ms(self) -> float:
@@ -584,13 +601,15 @@ class BM25Index(_Handle):
         return float(ms.value)
 
     def replace(self, replace_ids, term_ptr_add, post_doc_add, post_tf_add, doc_len_add, idf, avgdl: float,
-                term_map=None) -> None:
+                term_map=None, tokens=None) -> None:
         """Replace documents under their ids (amdr_bm25_replace): replace_ids strictly ascending; the new documents' own
         term-major CSR over the NEW term table (local id i = document replace_ids[i]) and their lengths; term_map[n_terms]:
         the new id of each old term or -1, injective (None: the identity, new terms behind the old); new ids no old term
         maps to are new terms; idf: the WHOLE new vector; avgdl: the new value.  No document id moves.  Afterwards the
         index is what BM25Index makes of the edited arrays, bit for bit.  A "_device" caller finishes its work first and
-        reserves again."""
+        reserves again.  The token stream is dropped; with tokens = (tok_ptr_add [n_rep + 1], tok_add) — the new
+        documents' texts as term ids over the new table — the call is amdr_bm25_replace_carry: a resident stream takes them
+        in place and keeps every other document's text, rewritten through the map."""
         ids = _c(replace_ids, np.int64)
         tp, pd, pt = _c(term_ptr_add, np.int64), _c(post_doc_add, np.int32), _c(post_tf_add, np.int32)
         idf_, dl = _c(idf, np.float64), _c(doc_len_add, np.int32)
@@ -601,16 +620,28 @@ class BM25Index(_Handle):
                              "post_tf_add of one length, term_map [n_terms] or None")
         if ids.shape[0] and pd.shape[0] < int(tp[-1]):
             raise ValueError("replace: term_ptr_add points past the postings")
-        _check(load().amdr_bm25_replace(self._h, _p(ids, C.c_int64), C.c_int64(ids.shape[0]), _p(tp, C.c_int64),
-                                        _p(pd, C.c_int32), _p(pt, C.c_int32), _p(dl, C.c_int32),
-                                        None if tm is None else _p(tm, C.c_int32), C.c_int64(idf_.shape[0]),
-                                        _p(idf_, C.c_double), C.c_double(avgdl)), "amdr_bm25_replace")
+        args = (self._h, _p(ids, C.c_int64), C.c_int64(ids.shape[0]), _p(tp, C.c_int64), _p(pd, C.c_int32),
+                _p(pt, C.c_int32), _p(dl, C.c_int32), None if tm is None else _p(tm, C.c_int32), C.c_int64(idf_.shape[0]),
+                _p(idf_, C.c_double), C.c_double(avgdl))
+        if tokens is None:
+            _check(load().amdr_bm25_replace(*args), "amdr_bm25_replace")
+        else:
+            kp, kt = self._token_args(tokens, int(ids.shape[0]), "replace")
+            _check(load().amdr_bm25_replace_carry(*args, _p(kp, C.c_int64), None if kt is None else _p(kt, C.c_int32)),
+                   "amdr_bm25_replace_carry")
         self.n_docs, self.n_terms = self.info()[:2]
 
     def replace_kernel_ms(self) -> float:
         """Summed device time of the last replace's passes in ms (-1 before the first replace)."""
         ms = C.c_double(-1.0)
         _check(load().amdr_bm25_replace_kernel_ms(self._h, C.byref(ms)), "amdr_bm25_replace_kernel_ms")
+        return float(ms.value)
+
+    def carry_kernel_ms(self) -> float:
+        """Summed device time of the carry passes of the last carrying update that carried a stream, in ms (-1 before
+        the first one)."""
+        ms = C.c_double(-1.0)
+        _check(load().amdr_bm25_carry_kernel_ms(self._h, C.byref(ms)), "amdr_bm25_carry_kernel_ms")
         return float(ms.value)
 
     def replaces(self) -> int:

@@ -134,13 +134,25 @@ class BM25Okapi:
             self.__dict__["_total"] = sum(self.doc_len)
         return nd
 
-    def add_documents(self, corpus: Sequence[Sequence[str]]) -> int:
+    @staticmethod
+    def _carried_tokens(g, corpus: Sequence[Sequence[str]], vocab: Dict[str, int]):
+        """The `tokens` operand of a carrying update (BM25Index.add / replace): the new documents' sequences as term ids
+        over the NEW vocabulary, in text order — or None when the resident index holds no stream to carry."""
+        if not g.tokens_info()[0]:
+            return None
+        tok_ptr = np.zeros(len(corpus) + 1, dtype=np.int64)
+        np.cumsum([len(d) for d in corpus], out=tok_ptr[1:])
+        return tok_ptr, np.fromiter((vocab[w] for d in corpus for w in d), dtype=np.int32, count=int(tok_ptr[-1]))
+
+    def add_documents(self, corpus: Sequence[Sequence[str]], carry_tokens: bool = False) -> int:
         """Append tokenised documents; afterwards this object equals BM25Okapi(old corpus + corpus): the idf dict in the
         same key order with the same bits (math.log per term and a sequential sum in vocabulary order, as __init__),
         avgdl, average_idf, doc_len, doc_freqs, corpus_size.  O(V + added tokens) after the one-time document-frequency
         cache.  A resident unsharded index (gpu()) takes the same documents in place (BM25Index.add: the added documents'
         CSR, the new idf vector and avgdl); a row shard is dropped and uploaded again on its next use — the in-place
-        append on a row-sharded index is not supported."""
+        append on a row-sharded index is not supported.  The resident token stream is dropped by that, unless
+        carry_tokens is true: the resident unsharded index then keeps its stream current (BM25Index.add with the added
+        documents' sequences; host work proportional to the added tokens)."""
         corpus = list(corpus)
         if not corpus:
             return 0
@@ -188,8 +200,9 @@ class BM25Okapi:
             if self.__dict__.get("_gpu_device", (None, None))[1] is None:
                 term_ptr, post_doc, post_tf = docs_csr(added, self.vocab())
                 try:
+                    carried = {"tokens": self._carried_tokens(g, corpus, self.vocab())} if carry_tokens else {}
                     g.add(term_ptr, post_doc, post_tf, np.fromiter(idf.values(), dtype=np.float64, count=len(idf)),
-                          np.asarray(self.doc_len[-len(corpus):], dtype=np.int32), float(self.avgdl))
+                          np.asarray(self.doc_len[-len(corpus):], dtype=np.int32), float(self.avgdl), **carried)
                 except Exception:  # the resident index is unchanged and now behind this object: upload again on next use
                     self.__dict__.pop("_gpu", None)
                     self.__dict__.pop("_gpu_device", None)
@@ -199,7 +212,7 @@ class BM25Okapi:
                 self.__dict__.pop("_gpu_device", None)
         return len(corpus)
 
-    def remove_documents(self, doc_ids: Sequence[int]) -> int:
+    def remove_documents(self, doc_ids: Sequence[int], carry_tokens: bool = False) -> int:
         """Remove documents by id (duplicates and order do not matter); afterwards this object equals
         BM25Okapi(the surviving documents' tokens), the survivors renumbered 0 .. n-1 in their old order: the idf dict in
         the re-fit's key order — the first-seen order of the SURVIVORS, which drops the terms whose documents are all gone
@@ -208,7 +221,9 @@ class BM25Okapi:
         the one-time document-frequency cache.  ValueError for an id out of range and for removing every document; the
         object is unchanged then.  A resident unsharded index (gpu()) takes the removal in place (BM25Index.remove: the
         ids, the map old term id -> new term id, the new idf vector and avgdl); a row shard is dropped and uploaded
-        again on its next use.  Returns the number of documents removed."""
+        again on its next use.  The resident token stream is dropped by that, unless carry_tokens is true: the resident
+        unsharded index then keeps the survivors' part of its stream (BM25Index.remove with carry=True).  Returns the
+        number of documents removed."""
         ids = sorted({int(i) for i in doc_ids})
         if not ids:
             return 0
@@ -258,7 +273,7 @@ class BM25Okapi:
         if in_place:
             try:
                 g.remove(np.asarray(ids, dtype=np.int64), np.fromiter(idf.values(), dtype=np.float64, count=len(idf)),
-                         float(self.avgdl), term_map=term_map)
+                         float(self.avgdl), term_map=term_map, **({"carry": True} if carry_tokens else {}))
             except Exception:  # the resident index is unchanged and now ahead of this object: upload again on next use
                 self.__dict__.pop("_gpu", None)
                 self.__dict__.pop("_gpu_device", None)
@@ -268,7 +283,7 @@ class BM25Okapi:
             self.__dict__.pop("_gpu_device", None)
         return len(ids)
 
-    def replace_documents(self, doc_ids: Sequence[int], corpus: Sequence[Sequence[str]]) -> int:
+    def replace_documents(self, doc_ids: Sequence[int], corpus: Sequence[Sequence[str]], carry_tokens: bool = False) -> int:
         """Replace documents under their ids: document doc_ids[i] takes the tokens corpus[i] (any order; an id given twice
         is a ValueError) and no document moves.  Afterwards this object equals BM25Okapi(the edited corpus in its original
         order): the idf dict in the re-fit's key order — the first-seen order of the EDITED corpus, which drops a term
@@ -278,7 +293,9 @@ class BM25Okapi:
         ValueError for an id out of range or a length mismatch; the object is unchanged then.  A resident unsharded index
         (gpu()) takes the replacement in place (BM25Index.replace: the ids, the new documents' CSR over the new term
         table, the map old term id -> new term id, the new idf vector and avgdl); a row shard is dropped and uploaded
-        again on its next use.  Returns the number of documents replaced."""
+        again on its next use.  The resident token stream is dropped by that, unless carry_tokens is true: the resident
+        unsharded index then keeps its stream current (BM25Index.replace with the new documents' sequences).  Returns the
+        number of documents replaced."""
         corpus = list(corpus)
         ids = [int(i) for i in doc_ids]
         if len(ids) != len(corpus):
@@ -343,8 +360,10 @@ class BM25Okapi:
         if in_place:
             self.__dict__["_vocab"] = new_vocab
             try:
+                carried = {"tokens": self._carried_tokens(g, corpus, new_vocab)} if carry_tokens else {}
                 g.replace(np.asarray(ids, dtype=np.int64), *add_csr, np.asarray([doc_len[d] for d in ids], dtype=np.int32),
-                          np.fromiter(idf.values(), dtype=np.float64, count=len(idf)), float(self.avgdl), term_map=term_map)
+                          np.fromiter(idf.values(), dtype=np.float64, count=len(idf)), float(self.avgdl), term_map=term_map,
+                          **carried)
             except Exception:  # the resident index is unchanged and now behind this object: upload again on next use
                 self.__dict__.pop("_gpu", None)
                 self.__dict__.pop("_gpu_device", None)

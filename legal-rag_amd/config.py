@@ -92,6 +92,10 @@ class RetrievalConfig:
     dense_image: str = "none"            # resident half-precision copy of the chunk matrix for the fp16 first pass of
                                          # large dense scans: "none" | "fp16" (+ ceil(n/32)*32*d*2 bytes of HBM; the
                                          # exact re-scoring keeps every id and score bit, csrc/dense_hi_image.hpp)
+    token_stream: str = "rebuild"        # the resident token stream (phrase constraints) across a live add / remove /
+                                         # replace of the BM25 index: "rebuild" (dropped; the next phrase query cuts
+                                         # every chunk text again and uploads the stream) | "carry" (kept current on the
+                                         # device by the update itself, amdr_bm25_*_carry: work proportional to the edit)
     diversity_lambda: Optional[float] = None  # MMR selection over the fused hits (retrieval/diversity.py) as the default
                                          # of every search: the weight of the relevance in [0, 1]; None: off
     diversity_pool: int = 0              # its candidates per question, at most 64; 0: min(64, max(3 * top_k, 10))
@@ -100,6 +104,7 @@ class RetrievalConfig:
         query_tokenizer_mode(self)
         graph_channel_mode(self)
         dense_image_mode(self)
+        token_stream_mode(self)
         diversity_default(self)
 
 
@@ -121,6 +126,20 @@ def query_tokenizer_mode(cfg) -> str:
     m = "host" if m is None else m
     if m not in QUERY_TOKENIZERS:
         raise ValueError(f"retrieval.query_tokenizer must be one of {QUERY_TOKENIZERS}, got {m!r}")
+    return m
+
+
+TOKEN_STREAMS = ("rebuild", "carry")
+
+
+def token_stream_mode(cfg) -> str:
+    """`token_stream` of a RetrievalConfig (or of `cfg.retrieval`): "rebuild" by default; ValueError for any other value
+    than "rebuild" / "carry"."""
+    r = getattr(cfg, "retrieval", cfg)
+    m = getattr(r, "token_stream", None)
+    m = "rebuild" if m is None else m
+    if m not in TOKEN_STREAMS:
+        raise ValueError(f"retrieval.token_stream must be one of {TOKEN_STREAMS}, got {m!r}")
     return m
 
 

@@ -74,6 +74,7 @@ struct amdr_bm25 {
   double add_kernel_ms = -1;     // event time of the last add's merge kernel (amdr_bm25_add_kernel_ms)
   double remove_kernel_ms = -1;  // summed event time of the last remove's passes (amdr_bm25_remove_kernel_ms)
   double replace_kernel_ms = -1;  // summed event time of the last replace's passes (amdr_bm25_replace_kernel_ms)
+  double carry_kernel_ms = -1;    // summed event time of the last carrying update's carry passes (amdr_bm25_carry_kernel_ms)
   hipStream_t stream = nullptr;
   std::mutex mu;
   // part[0]: "_device" calls, part[1]: host-pointer calls (see dense.hip)
@@ -81,7 +82,8 @@ struct amdr_bm25 {
   amdr::DevBuf tscope;  // amdr_term_scope (term_scope.hip): its staged operands, outputs and workspace
   amdr::DevBuf ticket;  // 64 zeroed ints: arrival counters of the one-launch serving step (dense_tail.hip), self-resetting
   // The token stream (amdr_bm25_set_tokens, phrase_scope.hip): document d's text as the term ids
-  // tok[tok_ptr[d] .. tok_ptr[d + 1]).  It describes ONE state of the index: every successful update drops it.
+  // tok[tok_ptr[d] .. tok_ptr[d + 1]).  It describes ONE state of the index: every successful plain update drops it, a
+  // carrying one (amdr_bm25_*_carry, bm25_update.hip) commits a new stream together with the new index.
   long long* tok_ptr = nullptr;  // [n_docs + 1]
   int* tok = nullptr;            // [n_tokens]
   int64_t n_tokens = 0;
@@ -92,3 +94,28 @@ struct amdr_bm25 {
     tok_ptr = nullptr, tok = nullptr, n_tokens = 0, has_tokens = false;
   }
 };
+
+namespace amdr {
+
+// A token stream in the making, beside the live one (the carrying updates): BmStagedIndex's contract.  commit() changes the
+// two streams' places, so the destructor frees the OLD arrays after a commit and the half-built ones after a failure.
+struct BmStagedTokens {
+  long long* tok_ptr = nullptr;  // [n_docs + 1]
+  int* tok = nullptr;            // [n_tokens]
+  int64_t n_tokens = 0;
+  BmStagedTokens() = default;
+  BmStagedTokens(const BmStagedTokens&) = delete;
+  BmStagedTokens& operator=(const BmStagedTokens&) = delete;
+  ~BmStagedTokens() {
+    if (tok_ptr) (void)hipFree(tok_ptr);
+    if (tok) (void)hipFree(tok);
+  }
+  void commit(amdr_bm25& h) {
+    std::swap(h.tok_ptr, tok_ptr);
+    std::swap(h.tok, tok);
+    std::swap(h.n_tokens, n_tokens);
+    h.has_tokens = true;
+  }
+};
+
+}  // namespace amdr

@@ -36,6 +36,17 @@
 //                               postings of its new list with a smaller document (one search in that list, mostly empty)
 //   bm25_rp_scatter_add_kernel  per tile of the add's postings: behind the add postings before it and the kept old
 //                               postings with a smaller document (one search in the old list + the tile rank tables)
+//
+// The carrying forms (amdr_bm25_add_carry, _remove_carry, _replace_carry) are the same three bodies with the carry of the
+// resident token stream (bm25_handle.hpp: tok_ptr, tok) switched on: a second stream is built beside the live one and
+// committed with the index, in the same place, after the stream has finished (tok_carry_rule.hpp):
+//   bm25_rm_docmap_kernel       (remove) also writes kept_old[doc_new[d]] = d, the inverse of the document map
+//   tok_len_i64_kernel          the new doc_len widened to 8 B, for
+//   compact_scan_i64_kernel     the new tok_ptr = the exclusive scan of the new lengths (the last one is the token count)
+//   tok_carry_kernel            per tile of kBmTile NEW tokens: the documents of the tile found in the new tok_ptr
+//                               (bm_tile_window), each token read from the old stream or the add's and rewritten through
+//                               the term map                       reads 4 B + a 4 B gather of the map, writes 4 B
+// The plain forms drop the stream, as before.
 #include "common.hpp"
 
 #include <memory>
@@ -48,6 +59,7 @@
 #include "bm25_remove_rule.hpp"
 #include "bm25_replace_rule.hpp"
 #include "compact.hpp"
+#include "tok_carry_rule.hpp"
 
 using namespace amdr;
 
@@ -131,12 +143,16 @@ __global__ __launch_bounds__(kBmTileThreads) void bm25_merge_kernel(
 // ---- amdr_bm25_remove: document map, tile ranks, term table, scatter -------------------------------------------------
 __global__ __launch_bounds__(256) void bm25_rm_docmap_kernel(const long long* __restrict__ remove_ids, long n_remove,
                                                              const int* __restrict__ doc_len_old, long n_docs_old,
-                                                             int* __restrict__ doc_new, int* __restrict__ doc_len_new) {
+                                                             int* __restrict__ doc_new, int* __restrict__ doc_len_new,
+                                                             int* __restrict__ kept_old /* or null */) {
   const long d = (long)blockIdx.x * 256 + threadIdx.x;
   if (d >= n_docs_old) return;
   const int nd = bm_rm_doc_new(remove_ids, n_remove, d);
   doc_new[d] = nd;
-  if (nd >= 0) doc_len_new[nd] = doc_len_old[d];
+  if (nd >= 0) {
+    doc_len_new[nd] = doc_len_old[d];
+    if (kept_old) kept_old[nd] = (int)d;  // the inverse map of the carry: one writer per slot
+  }
 }
 
 // One block = one tile of kBmTile consecutive OLD postings: which of them survive, each one's rank among the tile's
@@ -302,12 +318,123 @@ __global__ __launch_bounds__(kBmTileThreads) void bm25_rp_scatter_add_kernel(
   }
 }
 
-}  // namespace
+// ---- the carry of the token stream: new tok_ptr, one pass over the new tokens ---------------------------------------------
+__global__ __launch_bounds__(256) void tok_len_i64_kernel(const int* __restrict__ doc_len, long n_docs,
+                                                          long long* __restrict__ len64) {
+  const long d = (long)blockIdx.x * 256 + threadIdx.x;
+  if (d < n_docs) len64[d] = (long long)doc_len[d];
+}
 
-extern "C" {
+// One block = kBmTile consecutive NEW tokens, their documents found in the NEW tok_ptr (a document is to the stream what a
+// term is to the postings; a run of empty documents wider than the LDS window is searched in the table itself).  A token
+// reads 4 B from the old stream or the add's, gathers 4 B of the term map and writes 4 B (tc_token_at: every index is
+// compared with its array's count, a miss raises *bad instead of reading).
+__global__ __launch_bounds__(kBmTileThreads) void tok_carry_kernel(const TcArgs a, const long long* __restrict__ new_ptr,
+                                                                   long long n_tok_new, int* __restrict__ out,
+                                                                   int* __restrict__ bad) {
+  __shared__ long long win[kBmTile + 2];
+  const long long p0 = (long long)blockIdx.x * kBmTile;
+  long long p1 = p0 + kBmTile;  // exclusive
+  if (p1 > n_tok_new) p1 = n_tok_new;
+  if (p0 >= p1) return;
+  const BmTileWindow w = bm_tile_window(new_ptr, a.n_docs_new, p0, p1, win);
+  const int tid = threadIdx.x;
+#pragma unroll
+  for (int u = 0; u < kBmTilePerThread; ++u) {
+    const long long q = p0 + (long long)u * kBmTileThreads + tid;
+    if (q < p1) {
+      const long d = w.term_of(q);
+      const int t = tc_token_at(a, d, q - w.start_of(d), bad);
+      if (t >= 0) out[q] = t;
+    }
+  }
+}
 
-int amdr_bm25_add(amdr_bm25_t* h, const int64_t* term_ptr_add, const int32_t* post_doc_add, const int32_t* post_tf_add,
-                  const double* idf, const int32_t* doc_len_add, int64_t n_terms, int64_t n_add, double avgdl) {
+// The carry of one update: the staged stream, its scratch and its timer (amdr_bm25_carry_kernel_ms).  With `on` false every
+// step is skipped and the update ends in drop_tokens(), as the plain calls always have.
+struct TokCarry {
+  bool on;
+  BmStagedTokens nx;
+  CallScratch tmp;
+  KernelSpans timer;
+  long long *len64 = nullptr, *add_ptr = nullptr;
+  int *add_tok = nullptr, *kept_old = nullptr, *flag_dev = nullptr;
+  long long n_tok_new = -1;  // the device's count: new tok_ptr[n_docs_new], valid after the synchronisation behind scan()
+  int flag = 0;              // the kernel's error flag, valid after the synchronisation behind run()
+  explicit TokCarry(bool on_) : on(on_), timer(on_ ? 2 : 0) {}
+
+  // the tables of n_new documents; kept_old for a remove (the document-map pass fills it)
+  int begin(int64_t n_new, bool want_kept, const char* who) {
+    if (!on) return AMDR_OK;
+    AMDR_TRY(dev_alloc(&nx.tok_ptr, (size_t)n_new + 2, who));
+    AMDR_TRY(tmp.alloc(&len64, (size_t)n_new + 1, who));
+    if (want_kept) AMDR_TRY(tmp.alloc(&kept_old, (size_t)n_new + 1, who));
+    AMDR_TRY(tmp.alloc(&flag_dev, 1, who));
+    return AMDR_OK;
+  }
+  // the new tok_ptr from the new lengths (on the device, behind the pass that wrote them)
+  int scan(const int* doc_len_new, int64_t n_new, hipStream_t st) {
+    if (!on) return AMDR_OK;
+    AMDR_TRY(timer.begin(0, st));
+    hipLaunchKernelGGL(tok_len_i64_kernel, dim3((unsigned)((n_new + 255) / 256)), dim3(256), 0, st, doc_len_new, (long)n_new,
+                       len64);
+    AMDR_HIP(hipGetLastError());
+    hipLaunchKernelGGL(compact_scan_i64_kernel, dim3(1), dim3(kCompactScanThreads), 0, st, len64, (long)n_new, nx.tok_ptr);
+    AMDR_HIP(hipGetLastError());
+    AMDR_TRY(timer.end(0, st));
+    AMDR_HIP(hipMemcpyAsync(&n_tok_new, nx.tok_ptr + n_new, sizeof(long long), hipMemcpyDeviceToHost, st));
+    return AMDR_OK;
+  }
+  // the new tokens: n_tok of them (the host's count in an add, the device's after a remove or a replace).  `a` comes
+  // without the add's device arrays: they are uploaded here from tok_ptr_add[a.n_add + 1] / tok_add.
+  int run(TcArgs a, int64_t n_tok, const int64_t* tok_ptr_add, const int32_t* tok_add, hipStream_t st, const char* who) {
+    if (!on) return AMDR_OK;
+    const long long tiles = (n_tok + kBmTile - 1) / kBmTile;
+    if (n_tok < 0 || tiles >= (1ll << 31)) return fail(AMDR_EINVAL, "%s: %lld tokens exceed the carry grid", who, (long long)n_tok);
+    nx.n_tokens = n_tok;
+    AMDR_TRY(dev_alloc(&nx.tok, (size_t)n_tok + 1, who));  // (+ 1: never an empty allocation)
+    a.n_tok_add = a.n_add ? (long long)tok_ptr_add[a.n_add] : 0;
+    AMDR_TRY(tmp.alloc(&add_ptr, (size_t)a.n_add + 1, who));
+    AMDR_TRY(tmp.alloc(&add_tok, (size_t)a.n_tok_add + 1, who));
+    if (a.n_add) AMDR_HIP(hipMemcpyAsync(add_ptr, tok_ptr_add, (size_t)(a.n_add + 1) * sizeof(long long), hipMemcpyHostToDevice, st));
+    if (a.n_tok_add) AMDR_HIP(hipMemcpyAsync(add_tok, tok_add, (size_t)a.n_tok_add * sizeof(int), hipMemcpyHostToDevice, st));
+    a.add_ptr = add_ptr, a.add_tok = add_tok;
+    AMDR_HIP(hipMemsetAsync(flag_dev, 0, sizeof(int), st));
+    AMDR_TRY(timer.begin(1, st));
+    if (tiles > 0) {
+      hipLaunchKernelGGL(tok_carry_kernel, dim3((unsigned)tiles), dim3(kBmTileThreads), 0, st, a, nx.tok_ptr, (long long)n_tok,
+                         nx.tok, flag_dev);
+      AMDR_HIP(hipGetLastError());
+    }
+    AMDR_TRY(timer.end(1, st));
+    AMDR_HIP(hipMemcpyAsync(&flag, flag_dev, sizeof(int), hipMemcpyDeviceToHost, st));
+    return AMDR_OK;
+  }
+  // after the last synchronisation and the flag check: the stream changes places with the index, or goes as it always did
+  void commit(amdr_bm25* h) {
+    if (on) {
+      h->carry_kernel_ms = timer.ms();
+      nx.commit(*h);
+    } else {
+      h->drop_tokens();  // the stream described the index as it was (amdr_bm25_set_tokens)
+    }
+  }
+};
+
+// The old stream's part of a carry's arguments.
+TcArgs tc_args(int mode, const amdr_bm25* h, int64_t n_docs_new, int64_t n_add, int64_t n_terms_new) {
+  TcArgs a = {};
+  a.mode = mode;
+  a.n_docs_new = (long)n_docs_new, a.n_docs_old = (long)h->ix.n_docs, a.n_add = (long)n_add;
+  a.old_ptr = h->tok_ptr, a.old_tok = h->tok, a.n_tok_old = h->n_tokens;
+  a.n_terms_old = (long)h->ix.n_terms, a.n_terms_new = (long)n_terms_new;
+  return a;
+}
+
+// ---- the three updates: each plain call is the carrying body with the carry off ------------------------------------------
+int bm25_add_body(amdr_bm25_t* h, const int64_t* term_ptr_add, const int32_t* post_doc_add, const int32_t* post_tf_add,
+                  const double* idf, const int32_t* doc_len_add, int64_t n_terms, int64_t n_add, double avgdl,
+                  bool carry, const int64_t* tok_ptr_add, const int32_t* tok_add) {
   static const char* const who = "bm25_add";
   AMDR_REQUIRE(h != nullptr, "bm25_add: null handle");
   AMDR_REQUIRE(n_add >= 0, "bm25_add: n_add=%lld", (long long)n_add);
@@ -317,11 +444,17 @@ int amdr_bm25_add(amdr_bm25_t* h, const int64_t* term_ptr_add, const int32_t* po
   const int bad = bm_add_validate(term_ptr_add, post_doc_add, post_tf_add, idf, doc_len_add, n_terms, n_add, avgdl,
                                   old.n_terms, old.n_docs);
   AMDR_REQUIRE(bad == kBmAddOk, "bm25_add: %s", bm_add_error_text(bad));
+  if (carry) {
+    const int tbad = tc_validate_add(tok_ptr_add, tok_add, doc_len_add, n_add, n_terms);
+    AMDR_REQUIRE(tbad == kPhValid, "bm25_add_carry: the added token stream: %s", ph_error_text(tbad));
+  }
+  TokCarry tc(carry && h->has_tokens);  // without a resident stream the call is the plain call
   AMDR_HIP(hipSetDevice(h->device));
   const int64_t nnz_add = term_ptr_add[n_terms], nnz_new = old.nnz + nnz_add;
   BmStagedIndex nx;
   AMDR_TRY(nx.alloc_tables(n_terms, old.n_docs + n_add, avgdl, who));
   AMDR_TRY(nx.alloc_postings(nnz_new, who));
+  AMDR_TRY(tc.begin(old.n_docs + n_add, false, who));
   // the add's own CSR on the device (never an empty allocation)
   CallScratch tmp;
   long long* add_ptr;
@@ -352,15 +485,22 @@ int amdr_bm25_add(amdr_bm25_t* h, const int64_t* term_ptr_add, const int32_t* po
     AMDR_HIP(hipGetLastError());
     AMDR_TRY(timer.end(0, st));
   }
+  // the stream: the old one with the added documents behind it (the host knows the new token count)
+  const int64_t n_tok_new = tc.on ? h->n_tokens + tok_ptr_add[n_add] : 0;
+  AMDR_TRY(tc.scan(nx.doc_len, old.n_docs + n_add, st));
+  AMDR_TRY(tc.run(tc_args(kTcAdd, h, old.n_docs + n_add, n_add, n_terms), n_tok_new, tok_ptr_add, tok_add, st, who));
   AMDR_HIP(hipStreamSynchronize(st));
+  if (tc.on && tc.n_tok_new != n_tok_new)
+    return fail(AMDR_EHIP, "bm25_add_carry: the new lengths sum to %lld tokens, not %lld", tc.n_tok_new, (long long)n_tok_new);
+  AMDR_REQUIRE(tc.flag == 0, "bm25_add_carry: a token or a gather index of the carry is outside its array");
   h->add_kernel_ms = timer.ms();
   nx.commit(h->ix, h->adds);  // from here on nothing can fail
-  h->drop_tokens();  // the stream described the index as it was (amdr_bm25_set_tokens)
+  tc.commit(h);
   return AMDR_OK;
 }
 
-int amdr_bm25_remove(amdr_bm25_t* h, const int64_t* remove_ids, int64_t n_remove, const int32_t* term_map,
-                     int64_t n_terms_new, const double* idf, double avgdl) {
+int bm25_remove_body(amdr_bm25_t* h, const int64_t* remove_ids, int64_t n_remove, const int32_t* term_map,
+                     int64_t n_terms_new, const double* idf, double avgdl, bool carry) {
   static const char* const who = "bm25_remove";
   AMDR_REQUIRE(h != nullptr, "bm25_remove: null handle");
   AMDR_REQUIRE(n_remove >= 0, "bm25_remove: n_remove=%lld", (long long)n_remove);
@@ -370,12 +510,14 @@ int amdr_bm25_remove(amdr_bm25_t* h, const int64_t* remove_ids, int64_t n_remove
   const int bad = bm_rm_validate(remove_ids, n_remove, term_map, n_terms_new, idf, avgdl, old.n_terms, old.n_docs);
   if (bad == kBmRmNoMem) return fail(AMDR_ENOMEM, "bm25_remove: %s", bm_rm_error_text(bad));
   AMDR_REQUIRE(bad == kBmRmOk, "bm25_remove: %s", bm_rm_error_text(bad));
+  TokCarry tc(carry && h->has_tokens);  // without a resident stream the call is the plain call
   AMDR_HIP(hipSetDevice(h->device));
   const int64_t V_old = old.n_terms, V_new = n_terms_new, nnz_old = old.nnz, n_old = old.n_docs;
   const long long tiles = (nnz_old + kBmTile - 1) / kBmTile;
   AMDR_REQUIRE(tiles < (1ll << 31), "bm25_remove: %lld postings exceed the grid", (long long)nnz_old);
   BmStagedIndex nx;
   AMDR_TRY(nx.alloc_tables(V_new, n_old - n_remove, avgdl, who));
+  AMDR_TRY(tc.begin(n_old - n_remove, true, who));
   CallScratch tmp;
   long long *rm_ids, *tile_cnt, *tile_base, *rank_at, *df_new;
   int *doc_new, *map_dev = nullptr, *flag_dev;
@@ -398,7 +540,7 @@ int amdr_bm25_remove(amdr_bm25_t* h, const int64_t* remove_ids, int64_t n_remove
   KernelSpans timer(2);
   AMDR_TRY(timer.begin(0, st));
   hipLaunchKernelGGL(bm25_rm_docmap_kernel, dim3((unsigned)((n_old + 255) / 256)), dim3(256), 0, st, rm_ids, (long)n_remove,
-                     old.doc_len, (long)n_old, doc_new, nx.doc_len);
+                     old.doc_len, (long)n_old, doc_new, nx.doc_len, tc.kept_old);
   AMDR_HIP(hipGetLastError());
   if (tiles > 0) {
     hipLaunchKernelGGL(bm25_rm_count_kernel, dim3((unsigned)tiles), dim3(kBmTileThreads), 0, st, old.post_doc,
@@ -413,6 +555,7 @@ int amdr_bm25_remove(amdr_bm25_t* h, const int64_t* remove_ids, int64_t n_remove
   hipLaunchKernelGGL(compact_scan_i64_kernel, dim3(1), dim3(kCompactScanThreads), 0, st, df_new, (long)V_new, nx.term_ptr);
   AMDR_HIP(hipGetLastError());
   AMDR_TRY(timer.end(0, st));
+  AMDR_TRY(tc.scan(nx.doc_len, n_old - n_remove, st));
   long long nnz_new = 0;
   int flag = 0;
   AMDR_HIP(hipMemcpyAsync(&nnz_new, tile_base + tiles, sizeof(long long), hipMemcpyDeviceToHost, st));
@@ -429,16 +572,23 @@ int amdr_bm25_remove(amdr_bm25_t* h, const int64_t* remove_ids, int64_t n_remove
     AMDR_HIP(hipGetLastError());
   }
   AMDR_TRY(timer.end(1, st));
+  // the stream: the survivors' documents in their old order, every token through the map
+  TcArgs ta = tc_args(kTcRemove, h, n_old - n_remove, 0, V_new);
+  ta.kept_old = tc.kept_old, ta.term_map = map_dev;
+  AMDR_TRY(tc.run(ta, tc.n_tok_new, nullptr, nullptr, st, who));
   AMDR_HIP(hipStreamSynchronize(st));
+  AMDR_REQUIRE(tc.flag == 0, "bm25_remove_carry: a token of a surviving document is mapped to -1, or a gather index of the "
+                             "carry is outside its array");
   h->remove_kernel_ms = timer.ms();
   nx.commit(h->ix, h->removes);  // from here on nothing can fail
-  h->drop_tokens();  // the stream described the index as it was (amdr_bm25_set_tokens)
+  tc.commit(h);
   return AMDR_OK;
 }
 
-int amdr_bm25_replace(amdr_bm25_t* h, const int64_t* replace_ids, int64_t n_rep, const int64_t* term_ptr_add,
+int bm25_replace_body(amdr_bm25_t* h, const int64_t* replace_ids, int64_t n_rep, const int64_t* term_ptr_add,
                       const int32_t* post_doc_add, const int32_t* post_tf_add, const int32_t* doc_len_add,
-                      const int32_t* term_map, int64_t n_terms_new, const double* idf, double avgdl) {
+                      const int32_t* term_map, int64_t n_terms_new, const double* idf, double avgdl, bool carry,
+                      const int64_t* tok_ptr_add, const int32_t* tok_add) {
   static const char* const who = "bm25_replace";
   AMDR_REQUIRE(h != nullptr, "bm25_replace: null handle");
   AMDR_REQUIRE(n_rep >= 0, "bm25_replace: n_rep=%lld", (long long)n_rep);
@@ -451,6 +601,11 @@ int amdr_bm25_replace(amdr_bm25_t* h, const int64_t* replace_ids, int64_t n_rep,
   const int bad = bm_rp_validate(replace_ids, n_rep, term_ptr_add, post_doc_add, post_tf_add, doc_len_add, term_map,
                                  n_terms_new, idf, avgdl, old.n_terms, old.n_docs, inv.get());
   AMDR_REQUIRE(bad == kBmRpOk, "bm25_replace: %s", bm_rp_error_text(bad));
+  if (carry) {
+    const int tbad = tc_validate_add(tok_ptr_add, tok_add, doc_len_add, n_rep, n_terms_new);
+    AMDR_REQUIRE(tbad == kPhValid, "bm25_replace_carry: the new documents' token stream: %s", ph_error_text(tbad));
+  }
+  TokCarry tc(carry && h->has_tokens);  // without a resident stream the call is the plain call
   AMDR_HIP(hipSetDevice(h->device));
   const int64_t V_old = old.n_terms, V_new = n_terms_new, nnz_old = old.nnz, n = old.n_docs, nnz_add = term_ptr_add[V_new];
   const long long tiles = (nnz_old + kBmTile - 1) / kBmTile, add_tiles = (nnz_add + kBmTile - 1) / kBmTile;
@@ -458,6 +613,7 @@ int amdr_bm25_replace(amdr_bm25_t* h, const int64_t* replace_ids, int64_t n_rep,
                (long long)nnz_old, (long long)nnz_add);
   BmStagedIndex nx;
   AMDR_TRY(nx.alloc_tables(V_new, n, avgdl, who));
+  AMDR_TRY(tc.begin(n, false, who));
   CallScratch tmp;
   long long *rp_ids, *tile_cnt, *tile_base, *rank_at, *df_new, *add_ptr;
   int *doc_keep, *map_dev = nullptr, *inv_dev, *flag_dev, *add_doc, *add_tf, *add_len;
@@ -511,6 +667,7 @@ int amdr_bm25_replace(amdr_bm25_t* h, const int64_t* replace_ids, int64_t n_rep,
   hipLaunchKernelGGL(compact_scan_i64_kernel, dim3(1), dim3(kCompactScanThreads), 0, st, df_new, (long)V_new, nx.term_ptr);
   AMDR_HIP(hipGetLastError());
   AMDR_TRY(timer.end(0, st));
+  AMDR_TRY(tc.scan(nx.doc_len, n, st));
   long long kept = 0;
   int flag = 0;
   AMDR_HIP(hipMemcpyAsync(&kept, tile_base + tiles, sizeof(long long), hipMemcpyDeviceToHost, st));
@@ -536,10 +693,65 @@ int amdr_bm25_replace(amdr_bm25_t* h, const int64_t* replace_ids, int64_t n_rep,
     AMDR_HIP(hipGetLastError());
   }
   AMDR_TRY(timer.end(1, st));
+  // the stream: document replace_ids[i] takes local i's tokens, every other document its own through the map
+  TcArgs ta = tc_args(kTcReplace, h, n, n_rep, V_new);
+  ta.replace_ids = rp_ids, ta.term_map = map_dev;
+  AMDR_TRY(tc.run(ta, tc.n_tok_new, tok_ptr_add, tok_add, st, who));
   AMDR_HIP(hipStreamSynchronize(st));
+  AMDR_REQUIRE(tc.flag == 0, "bm25_replace_carry: a token of a surviving document is mapped to -1, or a gather index of the "
+                             "carry is outside its array");
   h->replace_kernel_ms = timer.ms();
   nx.commit(h->ix, h->replaces);  // from here on nothing can fail
-  h->drop_tokens();  // the stream described the index as it was (amdr_bm25_set_tokens)
+  tc.commit(h);
+  return AMDR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int amdr_bm25_add(amdr_bm25_t* h, const int64_t* term_ptr_add, const int32_t* post_doc_add, const int32_t* post_tf_add,
+                  const double* idf, const int32_t* doc_len_add, int64_t n_terms, int64_t n_add, double avgdl) {
+  return bm25_add_body(h, term_ptr_add, post_doc_add, post_tf_add, idf, doc_len_add, n_terms, n_add, avgdl, false, nullptr,
+                       nullptr);
+}
+
+int amdr_bm25_add_carry(amdr_bm25_t* h, const int64_t* term_ptr_add, const int32_t* post_doc_add, const int32_t* post_tf_add,
+                        const double* idf, const int32_t* doc_len_add, int64_t n_terms, int64_t n_add, double avgdl,
+                        const int64_t* tok_ptr_add, const int32_t* tok_add) {
+  return bm25_add_body(h, term_ptr_add, post_doc_add, post_tf_add, idf, doc_len_add, n_terms, n_add, avgdl, true, tok_ptr_add,
+                       tok_add);
+}
+
+int amdr_bm25_remove(amdr_bm25_t* h, const int64_t* remove_ids, int64_t n_remove, const int32_t* term_map,
+                     int64_t n_terms_new, const double* idf, double avgdl) {
+  return bm25_remove_body(h, remove_ids, n_remove, term_map, n_terms_new, idf, avgdl, false);
+}
+
+int amdr_bm25_remove_carry(amdr_bm25_t* h, const int64_t* remove_ids, int64_t n_remove, const int32_t* term_map,
+                           int64_t n_terms_new, const double* idf, double avgdl) {
+  return bm25_remove_body(h, remove_ids, n_remove, term_map, n_terms_new, idf, avgdl, true);
+}
+
+int amdr_bm25_replace(amdr_bm25_t* h, const int64_t* replace_ids, int64_t n_rep, const int64_t* term_ptr_add,
+                      const int32_t* post_doc_add, const int32_t* post_tf_add, const int32_t* doc_len_add,
+                      const int32_t* term_map, int64_t n_terms_new, const double* idf, double avgdl) {
+  return bm25_replace_body(h, replace_ids, n_rep, term_ptr_add, post_doc_add, post_tf_add, doc_len_add, term_map, n_terms_new,
+                           idf, avgdl, false, nullptr, nullptr);
+}
+
+int amdr_bm25_replace_carry(amdr_bm25_t* h, const int64_t* replace_ids, int64_t n_rep, const int64_t* term_ptr_add,
+                            const int32_t* post_doc_add, const int32_t* post_tf_add, const int32_t* doc_len_add,
+                            const int32_t* term_map, int64_t n_terms_new, const double* idf, double avgdl,
+                            const int64_t* tok_ptr_add, const int32_t* tok_add) {
+  return bm25_replace_body(h, replace_ids, n_rep, term_ptr_add, post_doc_add, post_tf_add, doc_len_add, term_map, n_terms_new,
+                           idf, avgdl, true, tok_ptr_add, tok_add);
+}
+
+int amdr_bm25_carry_kernel_ms(amdr_bm25_t* h, double* ms) {
+  AMDR_REQUIRE(h && ms, "bm25_carry_kernel_ms: null");
+  std::lock_guard<std::mutex> g(h->mu);
+  *ms = h->carry_kernel_ms;
   return AMDR_OK;
 }
 

@@ -33,6 +33,7 @@ from typing import ClassVar, List, Optional, Sequence, Tuple
 
 from .. import artifacts, text
 from ..bm25_model import BM25Okapi
+from ..config import token_stream_mode
 from ..schemas import LawChunk
 
 
@@ -111,6 +112,12 @@ class BM25Retriever:
         except OSError:
             return False
 
+    def _carry_tokens(self) -> dict:
+        """The keyword of the in-place updates under cfg.retrieval.token_stream = "carry": they keep the resident token
+        stream current (BM25Okapi.*_documents(carry_tokens=True)) instead of dropping it for ensure_token_stream to
+        rebuild.  Nothing under "rebuild": the calls are the ones they were."""
+        return {"carry_tokens": True} if token_stream_mode(self.cfg) == "carry" else {}
+
     def append_in_place(self, refit: BM25Okapi, corpus: Sequence[LawChunk], new_tokens: Sequence[Sequence[str]],
                         tokenizer: Optional[str]) -> bool:
         """IncrementalBM25Builder, after it has replaced a file that was current (state_is_current, the caller holds
@@ -133,7 +140,7 @@ class BM25Retriever:
             if torch.cuda.is_available():
                 torch.cuda.synchronize(self.device_index)
         try:
-            live.add_documents(new_tokens)
+            live.add_documents(new_tokens, **self._carry_tokens())
         except Exception as exc:  # noqa: BLE001 - e.g. no room for the transient second copy: the file is reloaded instead
             logger.warning("[BM25] in-place append failed (%s): %s is reloaded on the next load()", exc, self.bm25_path)
             return False
@@ -166,7 +173,7 @@ class BM25Retriever:
             if torch.cuda.is_available():
                 torch.cuda.synchronize(self.device_index)
         try:
-            live.remove_documents(sorted(gone))
+            live.remove_documents(sorted(gone), **self._carry_tokens())
         except Exception as exc:  # noqa: BLE001 - e.g. no room for the transient second copy: the file is reloaded instead
             logger.warning("[BM25] in-place removal failed (%s): %s is reloaded on the next load()", exc, self.bm25_path)
             return False
@@ -201,7 +208,7 @@ class BM25Retriever:
             if torch.cuda.is_available():
                 torch.cuda.synchronize(self.device_index)
         try:
-            live.replace_documents(rows, new_tokens)
+            live.replace_documents(rows, new_tokens, **self._carry_tokens())
         except Exception as exc:  # noqa: BLE001 - e.g. no room for the transient second copy: the file is reloaded instead
             logger.warning("[BM25] in-place replacement failed (%s): %s is reloaded on the next load()", exc, self.bm25_path)
             return False
@@ -240,7 +247,8 @@ class BM25Retriever:
 
     def ensure_token_stream(self) -> None:
         """The resident token stream of the native index (BM25Index.set_tokens), made on the first phrase constraint and
-        again after a live add / remove / replace (the native handle drops it with every update and reports none): the
+        again after a live add / remove / replace (the native handle drops it with every update and reports none; under
+        cfg.retrieval.token_stream = "carry" the update keeps it and this returns at once): the
         chunk texts cut by document_tokens, each document checked against the model's doc_len and doc_freqs
         (BM25Okapi.token_stream: RuntimeError on a mismatch).  Not on a row shard."""
         self.load()
