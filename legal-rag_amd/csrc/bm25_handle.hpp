@@ -1,6 +1,6 @@
-// The BM25 handle, shared by bm25.hip (create, plan, score, search, destroy), bm25_update.hip (add, remove, info, read),
-// term_scope.hip (term constraints), phrase_scope.hip (the token stream, phrases, Nears) and union_lists.hip (unions of
-// posting lists).  The per-call plumbing of the updates
+// The BM25 handle, shared by bm25.hip (create, plan, score, search, destroy), bm25_update.hip (add, remove, info, read, the
+// token stream) and the list resolvers of list_step.hpp: term_scope.hip (term constraints), phrase_scope.hip (phrases,
+// Nears), union_lists.hip (unions of posting lists) and class_span.hip (class spans).  The per-call plumbing of the updates
 // (dev_alloc, CallScratch, KernelSpans, AMDR_TRY) is call_scratch.hpp's, shared with the other two channels.
 #pragma once
 #include "call_scratch.hpp"
@@ -79,9 +79,9 @@ struct amdr_bm25 {
   std::mutex mu;
   // part[0]: "_device" calls, part[1]: host-pointer calls (see dense.hip)
   amdr::DevBuf part[2], qterms, qptr, sbuf, ibuf, full;
-  amdr::DevBuf tscope;  // amdr_term_scope (term_scope.hip): its staged operands, outputs and workspace
+  amdr::DevBuf tscope;  // the host twins of the list resolvers (ListStage, list_step.hpp): staged operands, outputs, workspace
   amdr::DevBuf ticket;  // 64 zeroed ints: arrival counters of the one-launch serving step (dense_tail.hip), self-resetting
-  // The token stream (amdr_bm25_set_tokens, phrase_scope.hip): document d's text as the term ids
+  // The token stream (amdr_bm25_set_tokens, bm25_update.hip): document d's text as the term ids
   // tok[tok_ptr[d] .. tok_ptr[d + 1]).  It describes ONE state of the index: every successful plain update drops it, a
   // carrying one (amdr_bm25_*_carry, bm25_update.hip) commits a new stream together with the new index.
   long long* tok_ptr = nullptr;  // [n_docs + 1]
@@ -96,6 +96,12 @@ struct amdr_bm25 {
 };
 
 namespace amdr {
+
+// What every call that reads the token stream asks of the handle (under h->mu where the call takes it).
+inline int bm_require_tokens(const amdr_bm25* h, const char* who) {
+  AMDR_REQUIRE(h->has_tokens, "%s: no token stream is resident (amdr_bm25_set_tokens; an update drops it)", who);
+  return AMDR_OK;
+}
 
 // A token stream in the making, beside the live one (the carrying updates): BmStagedIndex's contract.  commit() changes the
 // two streams' places, so the destructor frees the OLD arrays after a commit and the half-built ones after a failure.

@@ -1,7 +1,8 @@
 // BM25 channel: updates of the resident index (bm25_handle.hpp) — amdr_bm25_add, amdr_bm25_remove, amdr_bm25_replace — and
-// what reads it back (amdr_bm25_info, amdr_bm25_read).  After any sequence of updates the handle is what amdr_bm25_create (bm25.hip)
-// makes of the resulting index, byte for byte: built with -ffp-contract=off, as bm25.hip is, so that bm25_factor gives the
-// bits of create's host loop.
+// what reads it back (amdr_bm25_info, amdr_bm25_read), and the token stream's own entry points (amdr_bm25_set_tokens,
+// amdr_bm25_tokens_info, amdr_bm25_read_tokens: host-side copies and validation).  After any sequence of updates the
+// handle is what amdr_bm25_create (bm25.hip) makes of the resulting index, byte for byte: built with -ffp-contract=off, as
+// bm25.hip is, so that bm25_factor gives the bits of create's host loop.
 //
 // Every update builds a second BmIndex beside the live one and commits it by one swap after the stream has finished: a
 // failed update leaves the handle as it was.  All divide the work by tiles of kBmTile postings, not by terms (a Zipfian
@@ -746,6 +747,55 @@ int amdr_bm25_replace_carry(amdr_bm25_t* h, const int64_t* replace_ids, int64_t 
                             const int64_t* tok_ptr_add, const int32_t* tok_add) {
   return bm25_replace_body(h, replace_ids, n_rep, term_ptr_add, post_doc_add, post_tf_add, doc_len_add, term_map, n_terms_new,
                            idf, avgdl, true, tok_ptr_add, tok_add);
+}
+
+int amdr_bm25_set_tokens(amdr_bm25_t* h, const int64_t* doc_ptr, const int32_t* tokens) {
+  static const char* const who = "bm25_set_tokens";
+  AMDR_REQUIRE(h != nullptr, "bm25_set_tokens: null handle");
+  AMDR_REQUIRE(doc_ptr != nullptr && tokens != nullptr, "bm25_set_tokens: null array");
+  std::lock_guard<std::mutex> g(h->mu);
+  AMDR_HIP(hipSetDevice(h->device));
+  const BmIndex& ix = h->ix;
+  const int64_t n = ix.n_docs;
+  std::unique_ptr<int32_t[]> len(new (std::nothrow) int32_t[(size_t)n + 1]);
+  if (!len) return fail(AMDR_ENOMEM, "bm25_set_tokens: no host memory for %lld document lengths", (long long)n);
+  if (n) AMDR_HIP(hipMemcpy(len.get(), ix.doc_len, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
+  const int bad = ph_validate_stream(doc_ptr, tokens, len.get(), n, ix.n_terms);
+  AMDR_REQUIRE(bad == kPhValid, "bm25_set_tokens: %s", ph_error_text(bad));
+  const int64_t n_tok = doc_ptr[n];
+  long long* np = nullptr;
+  int* nt = nullptr;
+  int rc = dev_alloc(&np, (size_t)n + 1, who);
+  if (!rc) rc = dev_alloc(&nt, (size_t)n_tok + 1, who);  // (+ 1: never an empty allocation)
+  if (!rc && hipMemcpy(np, doc_ptr, (size_t)(n + 1) * sizeof(long long), hipMemcpyHostToDevice) != hipSuccess) rc = AMDR_EHIP;
+  if (!rc && n_tok && hipMemcpy(nt, tokens, (size_t)n_tok * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) rc = AMDR_EHIP;
+  if (rc) {  // the handle keeps what it had
+    if (rc == AMDR_EHIP) (void)fail(AMDR_EHIP, "bm25_set_tokens: the upload failed: %s", hipGetErrorString(hipGetLastError()));
+    if (np) (void)hipFree(np);
+    if (nt) (void)hipFree(nt);
+    return rc;
+  }
+  h->drop_tokens();
+  h->tok_ptr = np, h->tok = nt, h->n_tokens = n_tok, h->has_tokens = true;
+  return AMDR_OK;
+}
+
+int amdr_bm25_tokens_info(amdr_bm25_t* h, int64_t* out2) {
+  AMDR_REQUIRE(h && out2, "bm25_tokens_info: null");
+  std::lock_guard<std::mutex> g(h->mu);
+  out2[0] = h->has_tokens ? 1 : 0;
+  out2[1] = h->has_tokens ? h->n_tokens : 0;
+  return AMDR_OK;
+}
+
+int amdr_bm25_read_tokens(amdr_bm25_t* h, int64_t* doc_ptr, int32_t* tokens) {
+  AMDR_REQUIRE(h != nullptr, "bm25_read_tokens: null handle");
+  std::lock_guard<std::mutex> g(h->mu);
+  if (int rc = bm_require_tokens(h, "bm25_read_tokens")) return rc;
+  AMDR_HIP(hipSetDevice(h->device));
+  if (doc_ptr) AMDR_HIP(hipMemcpy(doc_ptr, h->tok_ptr, (size_t)(h->ix.n_docs + 1) * sizeof(long long), hipMemcpyDeviceToHost));
+  if (tokens && h->n_tokens) AMDR_HIP(hipMemcpy(tokens, h->tok, (size_t)h->n_tokens * sizeof(int), hipMemcpyDeviceToHost));
+  return AMDR_OK;
 }
 
 int amdr_bm25_carry_kernel_ms(amdr_bm25_t* h, double* ms) {

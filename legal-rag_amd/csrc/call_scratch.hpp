@@ -1,5 +1,5 @@
 // Per-call plumbing of the update entry points of all three channels (bm25_update.hip, maxsim_store.hip, dense.hip; the
-// token stream of phrase_scope.hip allocates through dev_alloc): device arrays that live for one call, the event timer of
+// token stream of bm25_update.hip allocates through dev_alloc): device arrays that live for one call, the event timer of
 // a call's kernels, and the early return on a bad status.  With these an entry point is a straight line of AMDR_TRY /
 // AMDR_HIP steps: whatever it leaves through, its scratch and its events go with it.
 #pragma once

@@ -7,7 +7,7 @@
 // already written into the call's list array.  The item is resolved from the resident token stream into ITS OWN ascending
 // document list, appended to that same array, which amdr_term_scope_lists (term_scope.hip) reads as one more term.
 //
-// Three launches in the siblings' shape, no global atomics, deterministic, nothing allocated; the grid is ONE-dimensional,
+// The three launches of list_step.hpp, no global atomics, deterministic, nothing allocated; the grid is ONE-dimensional,
 // n_items x tiles blocks of kPhTile = 256 threads, cell = p * tiles + y (item p, tile y of 256 candidates of its driver):
 //   count   the block resolves the item's slots into LDS (cs_slot: a class slot's member range and list), one thread links
 //           equal slots and finds the driver — the shortest list, a posting list or a class list, known only here.  (1)
@@ -26,15 +26,14 @@
 // which the first n_before + 1 are written — the classes' lists among them, cls_first + n_cls <= n_before — start =
 // list_ptr[n_before] is read ON THE DEVICE by the write pass, the entries n_before + 1 .. are written and the documents go
 // behind `start`.  The count pass reads entries <= n_before only and documents below `start` only.
-// The staging is traffic between the lanes of ONE wave, fenced as phrase_scope.hip fences it, so phase 2 holds no block
+// The staging is traffic between the lanes of ONE wave (list_wave_lds_fence), so phase 2 holds no block
 // barrier; every block barrier sits under a block-uniform condition.
 // LDS: the slots (16 x 56 B), the driver, four runs of 320 u16 (2 560 B), the survivor list (512 B), the keep flags
 // (256 B) and the scan's wave sums: under 4.5 KiB.  Workspace per cell: two i64 and 1 KiB of parked ranks.
 // Worst case: a round of 319 tokens x 16 class slots x 12 dependent loads (a class of 4 096 ids) per wave, before any lane
 // scans; the scan itself is near_rule's len x (n + 1) steps.
-#include "bm25_handle.hpp"
 #include "class_span_rule.hpp"
-#include "compact.hpp"
+#include "list_step.hpp"
 #include "union_rule.hpp"
 
 #include <memory>
@@ -48,23 +47,10 @@ namespace {
 constexpr int kCsThreads = kPhTile;
 constexpr int kCsWaves = kCsThreads / 64;
 constexpr int kCsStage = 320;  // u16 of one wave's staged run (kNearStage, rounded to a whole dword)
-constexpr size_t kCsAlign = 256;
 static_assert(kCsThreads % 64 == 0 && kPhLanes == 64 && kCsStage >= kNearStage, "whole waves; a run fits its stage");
 
-size_t cs_align(size_t b) { return (b + kCsAlign - 1) / kCsAlign * kCsAlign; }
-
-// Workspace: counts i64 [cells] | offsets i64 [cells + 1] | rank-or-minus-one i32 [cells * 256]
-struct CsWork {
-  size_t off_counts, off_offsets, off_rank, total;
-};
-CsWork cs_work(long long cells) {
-  CsWork w;
-  w.off_counts = 0;
-  w.off_offsets = cs_align((size_t)cells * sizeof(long long));
-  w.off_rank = w.off_offsets + cs_align(((size_t)cells + 1) * sizeof(long long));
-  w.total = w.off_rank + cs_align((size_t)cells * kCsThreads * sizeof(int));
-  return w;
-}
+// Workspace (list_work): a cell's payload is rank-or-minus-one i32 [256]
+constexpr size_t kCsCellBytes = kCsThreads * sizeof(int);
 
 struct CsItems {
   const long long* ptr;  // [n + 1]
@@ -92,13 +78,6 @@ __device__ __forceinline__ int cs_block_item(const CsIndex& I, const CsItems& S,
   return sized ? (int)L : 0;
 }
 
-// LDS traffic between the lanes of ONE wave (phrase_scope.hip's ph_wave_lds_fence): the LDS unit serves a wave's
-// operations in order, so only the compiler has to be kept from moving them.
-__device__ __forceinline__ void cs_wave_lds_fence() {
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-}
-
 __global__ __launch_bounds__(kCsThreads) void class_span_count_kernel(CsIndex I, CsItems S, long long tiles, long long cand_max,
                                                                      long long* __restrict__ counts,
                                                                      int* __restrict__ rank_out, int* __restrict__ status) {
@@ -123,11 +102,7 @@ __global__ __launch_bounds__(kCsThreads) void class_span_count_kernel(CsIndex I,
   // phase 1: the conjunction, one candidate per thread
   const long long i = i0 + threadIdx.x;
   const bool all = i < D.len && cs_has_all(slots, L, D, D.docs[D.begin + i]);
-  kept[threadIdx.x] = 0;
-  int n_surv;
-  const int slot = compact_block_exclusive<kCsThreads, int>(all ? 1 : 0, wsum, &n_surv);
-  if (all) surv[slot] = (unsigned short)threadIdx.x;
-  __syncthreads();
+  const int n_surv = list_compact_survivors<kCsThreads>(all, surv, kept, wsum);  // (barriers: every thread is here)
   // phase 2: one wave per survivor (n_surv is block-uniform; the loop holds no barrier)
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   unsigned short* run = stage[wave];
@@ -140,18 +115,13 @@ __global__ __launch_bounds__(kCsThreads) void class_span_count_kernel(CsIndex I,
       const int len = cs_run_len(base, end, kind, L, dist);  // <= kNearStage; base + len <= end
       for (int j = lane; j < len; j += kPhLanes)
         run[j] = (unsigned short)cs_token_mask(I.ph.tokens[base + j], slots, L, I.cls_terms);
-      cs_wave_lds_fence();
+      list_wave_lds_fence();
       found = __ballot(cs_lane_hit(run, len, lane, L, kind, dist)) != 0;
-      cs_wave_lds_fence();  // (the next round overwrites the run)
+      list_wave_lds_fence();  // (the next round overwrites the run)
     }
     if (lane == 0) kept[t] = found ? 1 : 0;
   }
-  __syncthreads();
-  const int keep = kept[threadIdx.x];
-  int total;
-  const int rank = compact_block_exclusive<kCsThreads, int>(keep, wsum, &total);
-  rank_out[(size_t)cell * kCsThreads + threadIdx.x] = keep ? rank : -1;
-  if (threadIdx.x == 0) counts[cell] = total;
+  list_rank_and_park<kCsThreads>(kept, wsum, rank_out + (size_t)cell * kCsThreads, counts + cell);  // (barriers: as above)
 }
 
 // (list_ptr and docs are the array the class lists are read from: neither is __restrict__)
@@ -164,24 +134,18 @@ __global__ __launch_bounds__(kCsThreads) void class_span_write_kernel(CsIndex I,
   __shared__ CsDriver drv;
   const long long cell = blockIdx.x;
   const long long p = cell / tiles, tile = cell - p * tiles;
-  // (entry n_before is not written by this launch unless n_before == 0, and then it is not read)
-  const long long start = n_before > 0 ? list_ptr[n_before] : 0;
+  const long long start = list_start(list_ptr, n_before);
   if (tile == 0 && threadIdx.x == 0) {
-    const long long begin = start + offsets[p * tiles], end = start + offsets[(p + 1) * tiles];
-    if (n_before == 0 && p == 0) list_ptr[0] = 0;
-    list_ptr[n_before + p + 1] = un_clamp(end, rows_cap);
-    if (un_status(begin, end, rows_cap) != kTsOk) status[p] = kTsRowsOverflow;  // (an item over cand_max has no row: its 1 stays)
+    const int s = list_write_header(list_ptr, n_before, p, start + offsets[p * tiles], start + offsets[(p + 1) * tiles], rows_cap);
+    if (s != kTsOk) status[p] = s;  // (an item over cand_max has no row: its 1 stays)
   }
   int kind, dist;
   (void)cs_block_item(I, S, p, slots, &drv, &kind, &dist);
   const CsDriver D = drv;
   const long long i0 = tile * kPhTile;
   if (D.len > cand_max || D.at < 0 || i0 >= D.len) return;  // block-uniform
-  const int rank = rank_in[(size_t)cell * kCsThreads + threadIdx.x];
-  if (rank < 0) return;  // (no barrier follows)
-  const long long at = start + offsets[cell] + rank;
-  // (a kept candidate lies inside the driver; a list_ptr that breaks its promise cannot make the position negative)
-  if (at >= 0 && at < rows_cap) docs[at] = D.docs[D.begin + i0 + threadIdx.x];
+  const long long at = list_kept_at(rank_in + (size_t)cell * kCsThreads, offsets, (size_t)cell, start, rows_cap);
+  if (at >= 0) docs[at] = D.docs[D.begin + i0 + threadIdx.x];  // (a kept candidate lies inside the driver)
 }
 
 struct CsOut {
@@ -192,27 +156,18 @@ struct CsOut {
 
 int cs_launch(const CsIndex& I, const CsItems& S, int64_t n_items, int64_t n_before, int64_t cand_max, int64_t rows_cap,
               const CsOut& o, unsigned char* work, hipStream_t st) {
-  if (n_items == 0) {
-    if (n_before == 0) AMDR_HIP(hipMemsetAsync(o.list_ptr, 0, sizeof(long long), st));
-    return AMDR_OK;
-  }
   const long long tiles = ph_tiles(cand_max), cells = (long long)n_items * tiles;
-  const CsWork w = cs_work(cells);
-  long long* counts = reinterpret_cast<long long*>(work + w.off_counts);
-  long long* offsets = reinterpret_cast<long long*>(work + w.off_offsets);
-  int* rank = reinterpret_cast<int*>(work + w.off_rank);
   const dim3 grid((unsigned)cells);
-  hipLaunchKernelGGL(class_span_count_kernel, grid, dim3(kCsThreads), 0, st, I, S, tiles, (long long)cand_max, counts, rank,
-                     o.status);
-  AMDR_HIP(hipGetLastError());
-  hipLaunchKernelGGL(compact_scan_i64_kernel, dim3(1), dim3(kCompactScanThreads), 0, st, (const long long*)counts, (long)cells,
-                     offsets);
-  AMDR_HIP(hipGetLastError());
-  hipLaunchKernelGGL(class_span_write_kernel, grid, dim3(kCsThreads), 0, st, I, S, tiles, (long long)cand_max,
-                     (long long)n_before, (long long)rows_cap, (const long long*)offsets, (const int*)rank, o.list_ptr, o.docs,
-                     o.status);
-  AMDR_HIP(hipGetLastError());
-  return AMDR_OK;
+  return list_launch(
+      st, n_items, n_before, (size_t)cells, kCsCellBytes, o.list_ptr, work,
+      [&](long long* counts, unsigned char* rank) {
+        hipLaunchKernelGGL(class_span_count_kernel, grid, dim3(kCsThreads), 0, st, I, S, tiles, (long long)cand_max, counts,
+                           (int*)rank, o.status);
+      },
+      [&](const long long* offsets, const unsigned char* rank) {
+        hipLaunchKernelGGL(class_span_write_kernel, grid, dim3(kCsThreads), 0, st, I, S, tiles, (long long)cand_max,
+                           (long long)n_before, (long long)rows_cap, offsets, (const int*)rank, o.list_ptr, o.docs, o.status);
+      });
 }
 
 // sizes every entry point refuses (nothing is enqueued); *cells: the cells of the launch
@@ -229,9 +184,7 @@ int cs_check_sizes(const char* who, int64_t n_items, int64_t n_cls, int64_t cls_
 
 CsIndex cs_index(const amdr_bm25* h, const long long* x_ptr, const int* x_doc, const long long* cls_ptr, const int* cls_terms,
                  int64_t n_cls, int64_t cls_first) {
-  const BmIndex& ix = h->ix;
-  return CsIndex{PhIndex{ix.term_ptr, ix.post_doc, (long)ix.n_terms, (long)ix.n_docs, h->tok_ptr, h->tok},
-                 x_ptr, x_doc, cls_ptr, cls_terms, (long)n_cls, (long)cls_first};
+  return CsIndex{ph_index(h), x_ptr, x_doc, cls_ptr, cls_terms, (long)n_cls, (long)cls_first};
 }
 
 }  // namespace
@@ -243,7 +196,7 @@ int amdr_class_spans_plan(int64_t n_items, int64_t cand_max, int64_t* work_bytes
   long long cells = 0;
   int rc = cs_check_sizes("class_spans_plan", n_items, 0, 0, 0, cand_max, 0, &cells);
   if (rc) return rc;
-  *work_bytes = (int64_t)cs_work(cells).total;
+  *work_bytes = (int64_t)list_work((size_t)cells, kCsCellBytes).total;
   return AMDR_OK;
 }
 
@@ -257,16 +210,14 @@ int amdr_class_spans_device(amdr_bm25_t* bm25, const int64_t* item_ptr_dev, cons
   long long cells = 0;
   int rc = cs_check_sizes(who, n_items, n_cls, cls_first, n_before, cand_max, rows_cap, &cells);
   if (rc) return rc;
-  AMDR_REQUIRE(bm25->has_tokens, "%s: no token stream is resident (amdr_bm25_set_tokens; an update drops it)", who);
+  if ((rc = bm_require_tokens(bm25, who))) return rc;
   AMDR_REQUIRE(list_ptr_dev != nullptr, "%s: null list_ptr", who);
   AMDR_REQUIRE(n_items == 0 || (item_ptr_dev && item_slots_dev && item_kind_dev && item_dist_dev && out_status_dev),
                "%s: null operand", who);
   AMDR_REQUIRE(n_cls == 0 || (cls_ptr_dev && cls_terms_dev), "%s: null class arrays", who);
   AMDR_REQUIRE(rows_cap == 0 || docs_dev, "%s: null docs", who);
-  AMDR_REQUIRE(work_bytes >= 0, "%s: work_bytes=%lld", who, (long long)work_bytes);
-  const size_t need = n_items ? cs_work(cells).total : 0;
-  AMDR_REQUIRE((size_t)work_bytes >= need && (need == 0 || work_dev), "%s: a workspace of %lld bytes, the plan asks for %zu", who,
-               (long long)work_bytes, need);
+  const size_t need = n_items ? list_work((size_t)cells, kCsCellBytes).total : 0;
+  if ((rc = list_check_work(who, work_dev, work_bytes, need))) return rc;
   AMDR_HIP(hipSetDevice(bm25->device));
   const CsItems S{(const long long*)item_ptr_dev, item_slots_dev, item_kind_dev, item_dist_dev};
   const CsOut o{(long long*)list_ptr_dev, docs_dev, out_status_dev};
@@ -287,7 +238,7 @@ int amdr_class_spans(amdr_bm25_t* bm25, const int64_t* item_ptr, const int32_t* 
   long long cells = 0;
   int rc = cs_check_sizes(who, n_items, n_cls, 0, n_cls, cand_max, rows_cap, &cells);
   if (rc) return rc;
-  AMDR_REQUIRE(bm25->has_tokens, "%s: no token stream is resident (amdr_bm25_set_tokens; an update drops it)", who);
+  if ((rc = bm_require_tokens(bm25, who))) return rc;
   const int64_t V = bm25->ix.n_terms, n_docs = bm25->ix.n_docs;
   const int bad = cs_validate(item_ptr, item_slots, item_kind, item_dist, n_items, cls_ptr, cls_terms, n_cls, V);
   AMDR_REQUIRE(bad == kPhValid, "%s: %s", who, cs_error_text(bad));
@@ -313,59 +264,41 @@ int amdr_class_spans(amdr_bm25_t* bm25, const int64_t* item_ptr, const int32_t* 
   int64_t un_bytes = 0;
   if ((rc = amdr_union_lists_plan(n_cls, n_docs, &un_bytes))) return rc;
   const int64_t cap = cls_cap + rows_cap, n_lists = n_cls + n_items;
-  const size_t n_all = (size_t)item_ptr[n_items];
-  // Layout of the staging buffer: item_ptr | cls_ptr | list_ptr | item_slots | kind | dist | cls_terms | docs | status | the
-  // union step's workspace | this step's, each aligned.
-  size_t at[11], total = 0;
-  at[0] = total, total += cs_align((size_t)(n_items + 1) * 8);
-  at[1] = total, total += cs_align((size_t)(n_cls + 1) * 8);
-  at[2] = total, total += cs_align((size_t)(n_lists + 1) * 8);
-  at[3] = total, total += cs_align((n_all + 1) * 4);  // (+ 1: never an empty region)
-  at[4] = total, total += cs_align((size_t)n_items * 4);
-  at[5] = total, total += cs_align((size_t)n_items * 4);
-  at[6] = total, total += cs_align((n_members + 1) * 4);
-  at[7] = total, total += cs_align(((size_t)cap + 1) * 4);
-  at[8] = total, total += cs_align((size_t)n_lists * 4);
-  at[9] = total, total += cs_align((size_t)un_bytes + 1);
-  at[10] = total, total += cs_work(cells).total;
-  if ((rc = bm25->tscope.ensure(total))) return rc;
-  unsigned char* q = bm25->tscope.as<unsigned char>();
+  // The staging buffer: the item arrays, the class arrays, the outputs of both steps (one list array), the union step's
+  // workspace, this step's.
+  ListStage s;
+  const size_t a_ptr = s.add((size_t)(n_items + 1) * 8, item_ptr), a_slots = s.add((size_t)item_ptr[n_items] * 4, item_slots);
+  const size_t a_kind = s.add((size_t)n_items * 4, item_kind), a_dist = s.add((size_t)n_items * 4, item_dist);
+  const size_t a_cls_ptr = s.add((size_t)(n_cls + 1) * 8, n_cls ? cls_ptr : nullptr);
+  const size_t a_cls_terms = s.add(n_members * 4, cls_terms);
+  const size_t a_list_ptr = s.add((size_t)(n_lists + 1) * 8), a_docs = s.add((size_t)cap * 4);
+  const size_t a_status = s.add((size_t)n_lists * 4);
+  const size_t a_un_work = s.add((size_t)un_bytes), a_work = s.add(list_work((size_t)cells, kCsCellBytes).total);
+  if ((rc = s.upload(bm25))) return rc;
   hipStream_t st = bm25->stream;
-  AMDR_HIP(hipMemcpyAsync(q + at[0], item_ptr, (size_t)(n_items + 1) * 8, hipMemcpyHostToDevice, st));
-  if (n_all) AMDR_HIP(hipMemcpyAsync(q + at[3], item_slots, n_all * 4, hipMemcpyHostToDevice, st));
-  AMDR_HIP(hipMemcpyAsync(q + at[4], item_kind, (size_t)n_items * 4, hipMemcpyHostToDevice, st));
-  AMDR_HIP(hipMemcpyAsync(q + at[5], item_dist, (size_t)n_items * 4, hipMemcpyHostToDevice, st));
-  if (n_cls) AMDR_HIP(hipMemcpyAsync(q + at[1], cls_ptr, (size_t)(n_cls + 1) * 8, hipMemcpyHostToDevice, st));
-  if (n_members) AMDR_HIP(hipMemcpyAsync(q + at[6], cls_terms, n_members * 4, hipMemcpyHostToDevice, st));
-  long long* lp = (long long*)(q + at[2]);
-  int* docs = (int*)(q + at[7]);
-  int* status = (int*)(q + at[8]);
+  long long* lp = s.at<long long>(a_list_ptr);
+  int* docs = s.at<int>(a_docs);
+  int* status = s.at<int>(a_status);
   // the classes' lists first (n_cls = 0: the union step writes list_ptr[0] = 0), the spans' behind them
-  if ((rc = amdr_union_lists_device(bm25, (const int64_t*)(q + at[1]), (const int32_t*)(q + at[6]), n_cls, 0, cap, (int64_t*)lp,
-                                    docs, status, q + at[9], un_bytes, st)))
+  if ((rc = amdr_union_lists_device(bm25, s.at<int64_t>(a_cls_ptr), s.at<int32_t>(a_cls_terms), n_cls, 0, cap, (int64_t*)lp, docs,
+                                    status, s.at<void>(a_un_work), un_bytes, st)))
     return rc;
-  const CsItems S{(const long long*)(q + at[0]), (const int*)(q + at[3]), (const int*)(q + at[4]), (const int*)(q + at[5])};
+  const CsItems S{s.at<long long>(a_ptr), s.at<int>(a_slots), s.at<int>(a_kind), s.at<int>(a_dist)};
   const CsOut o{lp, docs, status + n_cls};
-  if ((rc = cs_launch(cs_index(bm25, lp, docs, (const long long*)(q + at[1]), (const int*)(q + at[6]), n_cls, 0), S, n_items,
-                      n_cls, cand_max, cap, o, q + at[10], st)))
+  if ((rc = cs_launch(cs_index(bm25, lp, docs, s.at<long long>(a_cls_ptr), s.at<int>(a_cls_terms), n_cls, 0), S, n_items, n_cls,
+                      cand_max, cap, o, s.at<unsigned char>(a_work), st)))
     return rc;
   std::unique_ptr<long long[]> got(new (std::nothrow) long long[(size_t)n_lists + 1]);
   if (!got) return fail(AMDR_ENOMEM, "%s: no host memory for %lld list pointers", who, (long long)n_lists + 1);
-  AMDR_HIP(hipMemcpyAsync(got.get(), lp, (size_t)(n_lists + 1) * 8, hipMemcpyDeviceToHost, st));
-  AMDR_HIP(hipMemcpyAsync(out_status, o.status, (size_t)n_items * 4, hipMemcpyDeviceToHost, st));
-  AMDR_HIP(hipStreamSynchronize(st));
+  if ((rc = list_fetch_heads(st, lp, n_lists + 1, got.get(), o.status, n_items, out_status))) return rc;
   // The classes' lists fit by construction and usually end below cls_cap, which leaves the spans more room than rows_cap:
   // the caller's capacity is applied here, with the write pass's own clamp and status.
   const long long first = got[n_cls];
   for (int64_t p = 0; p < n_items; ++p)
     if (un_status(got[n_cls + p] - first, got[n_cls + p + 1] - first, rows_cap) != kTsOk) out_status[p] = kTsRowsOverflow;
   for (int64_t p = 0; p <= n_items; ++p) out_list_ptr[p] = un_clamp(got[n_cls + p] - first, rows_cap);
-  const int64_t used = out_list_ptr[n_items];  // <= rows_cap: only the documents the lists name come back
-  if (used > 0) {
-    AMDR_HIP(hipMemcpyAsync(out_docs, docs + first, (size_t)used * 4, hipMemcpyDeviceToHost, st));
-    AMDR_HIP(hipStreamSynchronize(st));
-  }
-  return AMDR_OK;
+  // (<= rows_cap: only the documents the lists name come back)
+  return list_fetch_rows(st, docs + first, 4, out_list_ptr[n_items], out_docs);
 }
 
 }  // extern "C"

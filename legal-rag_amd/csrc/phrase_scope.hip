@@ -6,7 +6,7 @@
 // document list — a virtual posting list — which amdr_term_scope_lists (term_scope.hip) reads as one more term.  The rule
 // — what a phrase is, which posting list drives it — is phrase_rule.hpp's, shared with the host check.
 //
-// Three launches in the shape of term_scope.hip, no atomics, deterministic; grid = (x = phrase, y = tile of kPhTile = 256
+// The three launches of list_step.hpp, no atomics, deterministic; grid = (x = phrase, y = tile of kPhTile = 256
 // candidates of its driver, one per thread):
 //   count   two phases inside the tile.  (1) thread t tests the conjunction for candidate t — posting_has on the other
 //           tokens, as term_scope does — and the survivors are compacted into an LDS list.  (2) one WAVE per survivor
@@ -36,13 +36,10 @@
 // Worst case of a Near: one wave, len x (n + 1) steps for a document of len tokens in which every token is an anchor that
 // never completes (a 4 550-token document at n = 255: 1.16 M steps, 18 200 per lane); four waves share a tile's
 // survivors, so such a document delays at most the other survivors of its own tile.
-#include "bm25_handle.hpp"
-#include "compact.hpp"
+#include "list_step.hpp"
 #include "near_rule.hpp"
 
-#include <memory>
 #include <mutex>
-#include <new>
 
 using namespace amdr;
 
@@ -50,24 +47,11 @@ namespace {
 
 constexpr int kPhThreads = kPhTile;
 constexpr int kPhWaves = kPhThreads / 64;
-constexpr size_t kPhAlign = 256;
 static_assert(kPhThreads % 64 == 0 && kPhLanes == 64, "whole waves; a wave is the scan's lane count");
 
-size_t ph_align(size_t b) { return (b + kPhAlign - 1) / kPhAlign * kPhAlign; }
-
-// Workspace: counts i64 [n_phr * tiles] | offsets i64 [n_phr * tiles + 1] | rank-or-minus-one i32 [n_phr * tiles * 256]
-struct PhWork {
-  size_t off_counts, off_offsets, off_rank, total;
-};
-PhWork ph_work(int64_t n_phr, int64_t cand_max) {
-  const size_t cells = (size_t)n_phr * (size_t)ph_tiles(cand_max);
-  PhWork w;
-  w.off_counts = 0;
-  w.off_offsets = ph_align(cells * sizeof(long long));
-  w.off_rank = w.off_offsets + ph_align((cells + 1) * sizeof(long long));
-  w.total = w.off_rank + ph_align(cells * kPhThreads * sizeof(int));
-  return w;
-}
+// Workspace (list_work): a cell is a tile of an item, its payload rank-or-minus-one i32 [256]
+constexpr size_t kPhCellBytes = kPhThreads * sizeof(int);
+size_t ph_cells(int64_t n_phr, int64_t cand_max) { return (size_t)n_phr * (size_t)ph_tiles(cand_max); }
 
 // The items of a call: phrases and Nears side by side.  kind == nullptr: every item is a phrase (amdr_phrase_lists).
 struct SpanItems {
@@ -92,13 +76,6 @@ __device__ __forceinline__ int ph_block_phrase(const PhIndex& I, const SpanItems
   __syncthreads();
   *kind_out = kind, *dist_out = dist;
   return sized ? (int)L : 0;
-}
-
-// LDS traffic between the lanes of ONE wave: the LDS unit serves a wave's operations in order, so only the compiler has
-// to be kept from moving them.
-__device__ __forceinline__ void ph_wave_lds_fence() {
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
 }
 
 __global__ __launch_bounds__(kPhThreads) void phrase_count_kernel(PhIndex I, SpanItems S, long long cand_max,
@@ -126,11 +103,7 @@ __global__ __launch_bounds__(kPhThreads) void phrase_count_kernel(PhIndex I, Spa
   // phase 1: the conjunction, one candidate per thread
   const long long i = i0 + threadIdx.x;
   const bool all = i < D.len && ph_has_all(I, terms, L, D, I.post_doc[D.begin + i]);
-  kept[threadIdx.x] = 0;
-  int n_surv;
-  const int slot = compact_block_exclusive<kPhThreads, int>(all ? 1 : 0, wsum, &n_surv);
-  if (all) surv[slot] = (unsigned short)threadIdx.x;
-  __syncthreads();
+  const int n_surv = list_compact_survivors<kPhThreads>(all, surv, kept, wsum);  // (barriers: every thread is here)
   // phase 2: one wave per survivor (n_surv is block-uniform; the loop holds no barrier)
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   for (int s = wave; s < n_surv; s += kPhWaves) {
@@ -149,23 +122,18 @@ __global__ __launch_bounds__(kPhThreads) void phrase_count_kernel(PhIndex I, Spa
       for (long long base = I.doc_ptr[doc]; base < end && !found; base += kPhLanes) {  // wave-uniform
         const int len = near_run_len(base, end, dist);  // <= kNearStage; base + len <= end
         for (int j = lane; j < len; j += kPhLanes) run[j] = I.tokens[base + j];
-        ph_wave_lds_fence();
+        list_wave_lds_fence();
         found = __ballot(near_lane_hit(run, len, lane, terms, L, kind == kSpanNearOrdered, dist)) != 0;
-        ph_wave_lds_fence();  // (the next round overwrites the run)
+        list_wave_lds_fence();  // (the next round overwrites the run)
       }
     }
     if (lane == 0) kept[t] = found ? 1 : 0;
   }
-  __syncthreads();
-  const int keep = kept[threadIdx.x];
-  int total;
-  const int rank = compact_block_exclusive<kPhThreads, int>(keep, wsum, &total);
-  rank_out[cell * kPhThreads + threadIdx.x] = keep ? rank : -1;
-  if (threadIdx.x == 0) counts[cell] = total;
+  list_rank_and_park<kPhThreads>(kept, wsum, rank_out + cell * kPhThreads, counts + cell);  // (barriers: as above)
 }
 
 __global__ __launch_bounds__(kPhThreads) void phrase_write_kernel(PhIndex I, SpanItems S, long long cand_max,
-                                                                 long n_phr, long long rows_cap,
+                                                                 long long rows_cap,
                                                                  const long long* __restrict__ offsets,
                                                                  const int* __restrict__ rank_in,
                                                                  long long* __restrict__ list_ptr, int* __restrict__ docs,
@@ -176,20 +144,16 @@ __global__ __launch_bounds__(kPhThreads) void phrase_write_kernel(PhIndex I, Spa
   const long long tile = blockIdx.y, tiles = gridDim.y;
   const size_t cell = (size_t)p * tiles + tile;
   if (tile == 0 && threadIdx.x == 0) {
-    const long long b = offsets[(size_t)p * tiles], e = offsets[(size_t)(p + 1) * tiles];
-    list_ptr[p] = b < rows_cap ? b : rows_cap;
-    if (p == n_phr - 1) list_ptr[n_phr] = e < rows_cap ? e : rows_cap;
-    if (e > b && e > rows_cap) status[p] = kTsRowsOverflow;  // (a phrase over cand_max has no row: its 1 stays)
+    const int s = list_write_header(list_ptr, 0, p, offsets[(size_t)p * tiles], offsets[(size_t)(p + 1) * tiles], rows_cap);
+    if (s != kTsOk) status[p] = s;  // (a phrase over cand_max has no row: its 1 stays)
   }
   int kind, dist;
   (void)ph_block_phrase(I, S, p, terms, &drv, &kind, &dist);
   const PhDriver D = drv;
   const long long i0 = tile * kPhTile;
   if (D.len > cand_max || i0 >= D.len) return;  // block-uniform
-  const int rank = rank_in[cell * kPhThreads + threadIdx.x];
-  if (rank < 0) return;  // (no barrier follows)
-  const long long at = offsets[cell] + rank;
-  if (at < rows_cap) docs[at] = I.post_doc[D.begin + i0 + threadIdx.x];  // (a kept candidate lies inside the driver)
+  const long long at = list_kept_at(rank_in + cell * kPhThreads, offsets, cell, 0, rows_cap);
+  if (at >= 0) docs[at] = I.post_doc[D.begin + i0 + threadIdx.x];  // (a kept candidate lies inside the driver)
 }
 
 struct PhOut {
@@ -200,25 +164,17 @@ struct PhOut {
 
 int ph_launch(const PhIndex& I, const SpanItems& S, int64_t n_phr, int64_t cand_max, int64_t rows_cap, const PhOut& o,
               unsigned char* work, hipStream_t st) {
-  if (n_phr == 0) {
-    AMDR_HIP(hipMemsetAsync(o.list_ptr, 0, sizeof(long long), st));
-    return AMDR_OK;
-  }
-  const PhWork w = ph_work(n_phr, cand_max);
-  const long long tiles = ph_tiles(cand_max);
-  long long* counts = reinterpret_cast<long long*>(work + w.off_counts);
-  long long* offsets = reinterpret_cast<long long*>(work + w.off_offsets);
-  int* rank = reinterpret_cast<int*>(work + w.off_rank);
-  const dim3 grid((unsigned)n_phr, (unsigned)tiles);
-  hipLaunchKernelGGL(phrase_count_kernel, grid, dim3(kPhThreads), 0, st, I, S, (long long)cand_max, counts, rank, o.status);
-  AMDR_HIP(hipGetLastError());
-  hipLaunchKernelGGL(compact_scan_i64_kernel, dim3(1), dim3(kCompactScanThreads), 0, st, (const long long*)counts,
-                     (long)(n_phr * tiles), offsets);
-  AMDR_HIP(hipGetLastError());
-  hipLaunchKernelGGL(phrase_write_kernel, grid, dim3(kPhThreads), 0, st, I, S, (long long)cand_max, (long)n_phr,
-                     (long long)rows_cap, (const long long*)offsets, (const int*)rank, o.list_ptr, o.docs, o.status);
-  AMDR_HIP(hipGetLastError());
-  return AMDR_OK;
+  const dim3 grid((unsigned)n_phr, (unsigned)ph_tiles(cand_max));
+  return list_launch(
+      st, n_phr, 0, ph_cells(n_phr, cand_max), kPhCellBytes, o.list_ptr, work,
+      [&](long long* counts, unsigned char* rank) {
+        hipLaunchKernelGGL(phrase_count_kernel, grid, dim3(kPhThreads), 0, st, I, S, (long long)cand_max, counts, (int*)rank,
+                           o.status);
+      },
+      [&](const long long* offsets, const unsigned char* rank) {
+        hipLaunchKernelGGL(phrase_write_kernel, grid, dim3(kPhThreads), 0, st, I, S, (long long)cand_max, (long long)rows_cap,
+                           offsets, (const int*)rank, o.list_ptr, o.docs, o.status);
+      });
 }
 
 // sizes every entry point refuses (nothing is enqueued)
@@ -230,11 +186,6 @@ int ph_check_sizes(const char* who, int64_t n_phr, int64_t cand_max, int64_t row
   return AMDR_OK;
 }
 
-PhIndex ph_index(const amdr_bm25* h) {
-  const BmIndex& ix = h->ix;
-  return PhIndex{ix.term_ptr, ix.post_doc, (long)ix.n_terms, (long)ix.n_docs, h->tok_ptr, h->tok};
-}
-
 // The "_device" entry of phrases (S.kind == nullptr) and of mixed items: checks, then enqueues.
 int span_device(const char* who, amdr_bm25_t* bm25, const SpanItems& S, int64_t n, int64_t cand_max, int64_t rows_cap,
                 int64_t* out_list_ptr_dev, int32_t* out_docs_dev, int32_t* out_status_dev, void* work_dev, int64_t work_bytes,
@@ -242,14 +193,12 @@ int span_device(const char* who, amdr_bm25_t* bm25, const SpanItems& S, int64_t 
   AMDR_REQUIRE(bm25 != nullptr, "%s: null handle", who);
   int rc = ph_check_sizes(who, n, cand_max, rows_cap);
   if (rc) return rc;
-  AMDR_REQUIRE(bm25->has_tokens, "%s: no token stream is resident (amdr_bm25_set_tokens; an update drops it)", who);
+  if ((rc = bm_require_tokens(bm25, who))) return rc;
   AMDR_REQUIRE(out_list_ptr_dev != nullptr, "%s: null out_list_ptr", who);
   AMDR_REQUIRE(n == 0 || (S.ptr && S.terms && out_status_dev && (!mixed || (S.kind && S.dist))), "%s: null operand", who);
   AMDR_REQUIRE(rows_cap == 0 || out_docs_dev, "%s: null out_docs", who);
-  AMDR_REQUIRE(work_bytes >= 0, "%s: work_bytes=%lld", who, (long long)work_bytes);
-  const size_t need = n ? ph_work(n, cand_max).total : 0;
-  AMDR_REQUIRE((size_t)work_bytes >= need && (need == 0 || work_dev), "%s: a workspace of %lld bytes, the plan asks for %zu", who,
-               (long long)work_bytes, need);
+  const size_t need = n ? list_work(ph_cells(n, cand_max), kPhCellBytes).total : 0;
+  if ((rc = list_check_work(who, work_dev, work_bytes, need))) return rc;
   AMDR_HIP(hipSetDevice(bm25->device));
   const PhOut o{(long long*)out_list_ptr_dev, out_docs_dev, out_status_dev};
   return ph_launch(ph_index(bm25), S, n, cand_max, rows_cap, o, static_cast<unsigned char*>(work_dev), (hipStream_t)stream);
@@ -265,7 +214,7 @@ int span_host(const char* who, amdr_bm25_t* bm25, const SpanItems& S, int64_t n,
   AMDR_REQUIRE(n == 0 || out_status, "%s: null out_status", who);
   AMDR_REQUIRE(rows_cap == 0 || out_docs, "%s: null out_docs", who);
   std::lock_guard<std::mutex> g(bm25->mu);
-  AMDR_REQUIRE(bm25->has_tokens, "%s: no token stream is resident (amdr_bm25_set_tokens; an update drops it)", who);
+  if ((rc = bm_require_tokens(bm25, who))) return rc;
   const int bad = mixed ? span_validate((const int64_t*)S.ptr, S.terms, S.kind, S.dist, n)
                         : ph_validate((const int64_t*)S.ptr, S.terms, n);
   AMDR_REQUIRE(bad == kPhValid, "%s: %s", who, mixed ? span_error_text(bad) : ph_error_text(bad));
@@ -274,99 +223,31 @@ int span_host(const char* who, amdr_bm25_t* bm25, const SpanItems& S, int64_t n,
     return AMDR_OK;
   }
   AMDR_HIP(hipSetDevice(bm25->device));
-  // Layout of the staging buffer: item_ptr | item_terms | list_ptr | docs | status | kind | dist | the workspace, each aligned.
-  const size_t n_all = (size_t)S.ptr[n];
-  size_t at[8], total = 0;
-  at[0] = total, total += ph_align((size_t)(n + 1) * 8);
-  at[1] = total, total += ph_align(n_all * 4);
-  at[2] = total, total += ph_align((size_t)(n + 1) * 8);
-  at[3] = total, total += ph_align((size_t)rows_cap * 4);
-  at[4] = total, total += ph_align((size_t)n * 4);
-  at[5] = total, total += mixed ? ph_align((size_t)n * 4) : 0;
-  at[6] = total, total += mixed ? ph_align((size_t)n * 4) : 0;
-  at[7] = total, total += ph_work(n, cand_max).total;
-  if ((rc = bm25->tscope.ensure(total))) return rc;
-  unsigned char* p = bm25->tscope.as<unsigned char>();
+  // The staging buffer: the item arrays (kind and dist for mixed items only), the outputs, the workspace.
+  ListStage s;
+  const size_t a_ptr = s.add((size_t)(n + 1) * 8, S.ptr), a_terms = s.add((size_t)S.ptr[n] * 4, S.terms);
+  const size_t a_kind = mixed ? s.add((size_t)n * 4, S.kind) : 0, a_dist = mixed ? s.add((size_t)n * 4, S.dist) : 0;
+  const size_t a_list_ptr = s.add((size_t)(n + 1) * 8), a_docs = s.add((size_t)rows_cap * 4), a_status = s.add((size_t)n * 4);
+  const size_t a_work = s.add(list_work(ph_cells(n, cand_max), kPhCellBytes).total);
+  if ((rc = s.upload(bm25))) return rc;
+  const SpanItems dev{s.at<long long>(a_ptr), s.at<int>(a_terms), mixed ? s.at<int>(a_kind) : nullptr,
+                      mixed ? s.at<int>(a_dist) : nullptr};
+  const PhOut o{s.at<long long>(a_list_ptr), s.at<int>(a_docs), s.at<int>(a_status)};
   hipStream_t st = bm25->stream;
-  AMDR_HIP(hipMemcpyAsync(p + at[0], S.ptr, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, st));
-  AMDR_HIP(hipMemcpyAsync(p + at[1], S.terms, n_all * 4, hipMemcpyHostToDevice, st));
-  if (mixed) {
-    AMDR_HIP(hipMemcpyAsync(p + at[5], S.kind, (size_t)n * 4, hipMemcpyHostToDevice, st));
-    AMDR_HIP(hipMemcpyAsync(p + at[6], S.dist, (size_t)n * 4, hipMemcpyHostToDevice, st));
-  }
-  const SpanItems dev{(const long long*)(p + at[0]), (const int*)(p + at[1]), mixed ? (const int*)(p + at[5]) : nullptr,
-                      mixed ? (const int*)(p + at[6]) : nullptr};
-  const PhOut o{(long long*)(p + at[2]), (int*)(p + at[3]), (int*)(p + at[4])};
-  if ((rc = ph_launch(ph_index(bm25), dev, n, cand_max, rows_cap, o, p + at[7], st))) return rc;
-  AMDR_HIP(hipMemcpyAsync(out_list_ptr, o.list_ptr, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, st));
-  AMDR_HIP(hipMemcpyAsync(out_status, o.status, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-  AMDR_HIP(hipStreamSynchronize(st));
-  const int64_t used = out_list_ptr[n];  // <= rows_cap: only the documents the lists name come back
-  if (used > 0) {
-    AMDR_HIP(hipMemcpyAsync(out_docs, o.docs, (size_t)used * 4, hipMemcpyDeviceToHost, st));
-    AMDR_HIP(hipStreamSynchronize(st));
-  }
-  return AMDR_OK;
+  if ((rc = ph_launch(ph_index(bm25), dev, n, cand_max, rows_cap, o, s.at<unsigned char>(a_work), st))) return rc;
+  // (used <= rows_cap: only the documents the lists name come back)
+  return list_fetch(st, n, o.list_ptr, o.status, o.docs, 4, out_list_ptr, out_status, out_docs);
 }
 
 }  // namespace
 
 extern "C" {
 
-int amdr_bm25_set_tokens(amdr_bm25_t* h, const int64_t* doc_ptr, const int32_t* tokens) {
-  static const char* const who = "bm25_set_tokens";
-  AMDR_REQUIRE(h != nullptr, "bm25_set_tokens: null handle");
-  AMDR_REQUIRE(doc_ptr != nullptr && tokens != nullptr, "bm25_set_tokens: null array");
-  std::lock_guard<std::mutex> g(h->mu);
-  AMDR_HIP(hipSetDevice(h->device));
-  const BmIndex& ix = h->ix;
-  const int64_t n = ix.n_docs;
-  std::unique_ptr<int32_t[]> len(new (std::nothrow) int32_t[(size_t)n + 1]);
-  if (!len) return fail(AMDR_ENOMEM, "bm25_set_tokens: no host memory for %lld document lengths", (long long)n);
-  if (n) AMDR_HIP(hipMemcpy(len.get(), ix.doc_len, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
-  const int bad = ph_validate_stream(doc_ptr, tokens, len.get(), n, ix.n_terms);
-  AMDR_REQUIRE(bad == kPhValid, "bm25_set_tokens: %s", ph_error_text(bad));
-  const int64_t n_tok = doc_ptr[n];
-  long long* np = nullptr;
-  int* nt = nullptr;
-  int rc = dev_alloc(&np, (size_t)n + 1, who);
-  if (!rc) rc = dev_alloc(&nt, (size_t)n_tok + 1, who);  // (+ 1: never an empty allocation)
-  if (!rc && hipMemcpy(np, doc_ptr, (size_t)(n + 1) * sizeof(long long), hipMemcpyHostToDevice) != hipSuccess) rc = AMDR_EHIP;
-  if (!rc && n_tok && hipMemcpy(nt, tokens, (size_t)n_tok * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) rc = AMDR_EHIP;
-  if (rc) {  // the handle keeps what it had
-    if (rc == AMDR_EHIP) (void)fail(AMDR_EHIP, "bm25_set_tokens: the upload failed: %s", hipGetErrorString(hipGetLastError()));
-    if (np) (void)hipFree(np);
-    if (nt) (void)hipFree(nt);
-    return rc;
-  }
-  h->drop_tokens();
-  h->tok_ptr = np, h->tok = nt, h->n_tokens = n_tok, h->has_tokens = true;
-  return AMDR_OK;
-}
-
-int amdr_bm25_tokens_info(amdr_bm25_t* h, int64_t* out2) {
-  AMDR_REQUIRE(h && out2, "bm25_tokens_info: null");
-  std::lock_guard<std::mutex> g(h->mu);
-  out2[0] = h->has_tokens ? 1 : 0;
-  out2[1] = h->has_tokens ? h->n_tokens : 0;
-  return AMDR_OK;
-}
-
-int amdr_bm25_read_tokens(amdr_bm25_t* h, int64_t* doc_ptr, int32_t* tokens) {
-  AMDR_REQUIRE(h != nullptr, "bm25_read_tokens: null handle");
-  std::lock_guard<std::mutex> g(h->mu);
-  AMDR_REQUIRE(h->has_tokens, "bm25_read_tokens: no token stream is resident (amdr_bm25_set_tokens; an update drops it)");
-  AMDR_HIP(hipSetDevice(h->device));
-  if (doc_ptr) AMDR_HIP(hipMemcpy(doc_ptr, h->tok_ptr, (size_t)(h->ix.n_docs + 1) * sizeof(long long), hipMemcpyDeviceToHost));
-  if (tokens && h->n_tokens) AMDR_HIP(hipMemcpy(tokens, h->tok, (size_t)h->n_tokens * sizeof(int), hipMemcpyDeviceToHost));
-  return AMDR_OK;
-}
-
 int amdr_phrase_lists_plan(int64_t n_phr, int64_t cand_max, int64_t* work_bytes) {
   AMDR_REQUIRE(work_bytes != nullptr, "phrase_lists_plan: null");
   int rc = ph_check_sizes("phrase_lists_plan", n_phr, cand_max, 0);
   if (rc) return rc;
-  *work_bytes = (int64_t)ph_work(n_phr, cand_max).total;
+  *work_bytes = (int64_t)list_work(ph_cells(n_phr, cand_max), kPhCellBytes).total;
   return AMDR_OK;
 }
 
@@ -389,7 +270,7 @@ int amdr_span_lists_plan(int64_t n_items, int64_t cand_max, int64_t* work_bytes)
   AMDR_REQUIRE(work_bytes != nullptr, "span_lists_plan: null");
   int rc = ph_check_sizes("span_lists_plan", n_items, cand_max, 0);
   if (rc) return rc;
-  *work_bytes = (int64_t)ph_work(n_items, cand_max).total;
+  *work_bytes = (int64_t)list_work(ph_cells(n_items, cand_max), kPhCellBytes).total;
   return AMDR_OK;
 }
 

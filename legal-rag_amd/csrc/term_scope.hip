@@ -21,8 +21,7 @@
 // The constraint is the grid's x in every call (x holds 2^31 - 1 blocks, y 65 535): a batch may carry more than 65 535
 // constraints, and cand_max <= 65 535 tiles is far past any resident index.
 // Every barrier sits under a block-uniform condition: the driver is computed by one thread and read from LDS by all.
-#include "bm25_handle.hpp"
-#include "compact.hpp"
+#include "list_step.hpp"
 #include "term_scope_rule.hpp"
 
 #include <mutex>
@@ -33,24 +32,11 @@ namespace {
 
 constexpr int kTsThreads = 256;
 constexpr int kTsPer = kTsTile / kTsThreads;  // candidates per thread
-constexpr size_t kTsAlign = 256;
 static_assert(kTsPer * kTsThreads == kTsTile && kTsPer <= 32, "one keep bit per candidate of a thread");
 
-size_t ts_align(size_t b) { return (b + kTsAlign - 1) / kTsAlign * kTsAlign; }
-
-// Workspace: counts i64 [n_cons * tiles] | offsets i64 [n_cons * tiles + 1] | keep bits u32 [n_cons * tiles * 256]
-struct TsWork {
-  size_t off_counts, off_offsets, off_bits, total;
-};
-TsWork ts_work(int64_t n_cons, int64_t cand_max) {
-  const size_t cells = (size_t)n_cons * (size_t)ts_tiles(cand_max);
-  TsWork w;
-  w.off_counts = 0;
-  w.off_offsets = ts_align(cells * sizeof(long long));
-  w.off_bits = w.off_offsets + ts_align((cells + 1) * sizeof(long long));
-  w.total = w.off_bits + ts_align(cells * kTsThreads * sizeof(unsigned));
-  return w;
-}
+// Workspace (list_work): a cell is a tile of a constraint, its payload the keep bits u32 [256]
+constexpr size_t kTsCellBytes = kTsThreads * sizeof(unsigned);
+size_t ts_cells(int64_t n_cons, int64_t cand_max) { return (size_t)n_cons * (size_t)ts_tiles(cand_max); }
 
 // the block's driver: computed by thread 0, read by all (ends with a barrier)
 __device__ __forceinline__ TsDriver ts_block_driver(const TsIndex& I, const TsCons& C, long c, TsDriver* slot) {
@@ -87,7 +73,7 @@ __global__ __launch_bounds__(kTsThreads) void term_scope_count_kernel(TsIndex I,
   if (threadIdx.x == 0) counts[cell] = total;
 }
 
-__global__ __launch_bounds__(kTsThreads) void term_scope_write_kernel(TsIndex I, TsCons C, long long cand_max, long n_cons,
+__global__ __launch_bounds__(kTsThreads) void term_scope_write_kernel(TsIndex I, TsCons C, long long cand_max,
                                                                      long long rows_cap,
                                                                      const long long* __restrict__ offsets,
                                                                      const unsigned* __restrict__ bits,
@@ -99,10 +85,8 @@ __global__ __launch_bounds__(kTsThreads) void term_scope_write_kernel(TsIndex I,
   const long long tile = blockIdx.y, tiles = gridDim.y;
   const size_t cell = (size_t)c * tiles + tile;
   if (tile == 0 && threadIdx.x == 0) {
-    const long long b = offsets[(size_t)c * tiles], e = offsets[(size_t)(c + 1) * tiles];
-    scope_ptr[c] = b < rows_cap ? b : rows_cap;
-    if (c == n_cons - 1) scope_ptr[n_cons] = e < rows_cap ? e : rows_cap;
-    if (e > b && e > rows_cap) status[c] = kTsRowsOverflow;  // (a constraint over cand_max has no row: its 1 stays)
+    const int s = list_write_header(scope_ptr, 0, c, offsets[(size_t)c * tiles], offsets[(size_t)(c + 1) * tiles], rows_cap);
+    if (s != kTsOk) status[c] = s;  // (a constraint over cand_max has no row: its 1 stays)
   }
   const TsDriver D = ts_block_driver(I, C, c, &drv);
   const long long i0 = tile * kTsTile;
@@ -128,25 +112,17 @@ struct TsOut {
 
 int ts_launch(const TsIndex& I, const TsCons& C, int64_t n_cons, int64_t cand_max, int64_t rows_cap, const TsOut& o,
               unsigned char* work, hipStream_t st) {
-  if (n_cons == 0) {
-    AMDR_HIP(hipMemsetAsync(o.scope_ptr, 0, sizeof(long long), st));
-    return AMDR_OK;
-  }
-  const TsWork w = ts_work(n_cons, cand_max);
-  const long long tiles = ts_tiles(cand_max);
-  long long* counts = reinterpret_cast<long long*>(work + w.off_counts);
-  long long* offsets = reinterpret_cast<long long*>(work + w.off_offsets);
-  unsigned* bits = reinterpret_cast<unsigned*>(work + w.off_bits);
-  const dim3 grid((unsigned)n_cons, (unsigned)tiles);
-  hipLaunchKernelGGL(term_scope_count_kernel, grid, dim3(kTsThreads), 0, st, I, C, (long long)cand_max, counts, bits, o.status);
-  AMDR_HIP(hipGetLastError());
-  hipLaunchKernelGGL(compact_scan_i64_kernel, dim3(1), dim3(kCompactScanThreads), 0, st, (const long long*)counts,
-                     (long)(n_cons * tiles), offsets);
-  AMDR_HIP(hipGetLastError());
-  hipLaunchKernelGGL(term_scope_write_kernel, grid, dim3(kTsThreads), 0, st, I, C, (long long)cand_max, (long)n_cons,
-                     (long long)rows_cap, (const long long*)offsets, (const unsigned*)bits, o.scope_ptr, o.rows, o.status);
-  AMDR_HIP(hipGetLastError());
-  return AMDR_OK;
+  const dim3 grid((unsigned)n_cons, (unsigned)ts_tiles(cand_max));
+  return list_launch(
+      st, n_cons, 0, ts_cells(n_cons, cand_max), kTsCellBytes, o.scope_ptr, work,
+      [&](long long* counts, unsigned char* bits) {
+        hipLaunchKernelGGL(term_scope_count_kernel, grid, dim3(kTsThreads), 0, st, I, C, (long long)cand_max, counts,
+                           (unsigned*)bits, o.status);
+      },
+      [&](const long long* offsets, const unsigned char* bits) {
+        hipLaunchKernelGGL(term_scope_write_kernel, grid, dim3(kTsThreads), 0, st, I, C, (long long)cand_max, (long long)rows_cap,
+                           offsets, (const unsigned*)bits, o.scope_ptr, o.rows, o.status);
+      });
 }
 
 // sizes both entry points refuse (nothing is enqueued)
@@ -166,7 +142,7 @@ int amdr_term_scope_plan(int64_t n_cons, int64_t cand_max, int64_t* work_bytes) 
   AMDR_REQUIRE(work_bytes != nullptr, "term_scope_plan: null");
   int rc = ts_check_sizes("term_scope_plan", 0, n_cons, 0, cand_max, 0);
   if (rc) return rc;
-  *work_bytes = (int64_t)ts_work(n_cons, cand_max).total;
+  *work_bytes = (int64_t)list_work(ts_cells(n_cons, cand_max), kTsCellBytes).total;
   return AMDR_OK;
 }
 
@@ -186,10 +162,8 @@ int amdr_term_scope_lists_device(amdr_bm25_t* bm25, const int64_t* grp_ptr_dev, 
   AMDR_REQUIRE(n_groups == 0 || (grp_kind_dev && grp_terms_dev), "term_scope: null group arrays");
   AMDR_REQUIRE(n_base == 0 || base_ptr_dev, "term_scope: null base_ptr");
   AMDR_REQUIRE(rows_cap == 0 || out_rows_dev, "term_scope: null out_rows");
-  AMDR_REQUIRE(work_bytes >= 0, "term_scope: work_bytes=%lld", (long long)work_bytes);
-  const size_t need = n_cons ? ts_work(n_cons, cand_max).total : 0;
-  AMDR_REQUIRE((size_t)work_bytes >= need && (need == 0 || work_dev), "term_scope: a workspace of %lld bytes, the plan asks for %zu",
-               (long long)work_bytes, need);
+  const size_t need = n_cons ? list_work(ts_cells(n_cons, cand_max), kTsCellBytes).total : 0;
+  if ((rc = list_check_work("term_scope", work_dev, work_bytes, need))) return rc;
   AMDR_HIP(hipSetDevice(bm25->device));
   const BmIndex& ix = bm25->ix;
   const TsIndex I{ix.term_ptr, ix.post_doc, (long)ix.n_terms, (long)ix.n_docs, (const long long*)x_ptr_dev, x_doc_dev, (long)n_x};
@@ -235,41 +209,29 @@ int amdr_term_scope_lists(amdr_bm25_t* bm25, const int64_t* grp_ptr, const int32
     return AMDR_OK;
   }
   AMDR_HIP(hipSetDevice(bm25->device));
-  // Layout of the staging buffer: the seven operand arrays and the two of the virtual lists | scope_ptr | rows | status |
-  // the workspace, each aligned.
-  constexpr int kOps = 9;
-  const size_t b[kOps] = {(size_t)(n_cons + 1) * 8, (size_t)n_groups * 4,    (size_t)(n_groups + 1) * 8,
-                          (size_t)n_terms_all * 4,  (size_t)(n_base + 1) * 8, (size_t)n_base_rows * 8,
-                          (size_t)n_cons * 4,       n_x ? (size_t)(n_x + 1) * 8 : 0, (size_t)n_x_docs * 4};
-  const void* src[kOps] = {grp_ptr, grp_kind, grp_term_ptr, grp_terms, base_ptr, base_rows, cons_base, x_ptr, x_doc};
-  size_t at[kOps + 4], total = 0;
-  for (int i = 0; i < kOps; ++i) at[i] = total, total += ts_align(b[i]);
-  at[kOps] = total, total += ts_align((size_t)(n_cons + 1) * 8);
-  at[kOps + 1] = total, total += ts_align((size_t)rows_cap * 8);
-  at[kOps + 2] = total, total += ts_align((size_t)n_cons * 4);
-  at[kOps + 3] = total, total += ts_work(n_cons, cand_max).total;
-  if ((rc = bm25->tscope.ensure(total))) return rc;
-  unsigned char* p = bm25->tscope.as<unsigned char>();
+  // The staging buffer: the seven operand arrays and the two of the virtual lists, the outputs, the workspace.
+  ListStage s;
+  const size_t a_grp_ptr = s.add((size_t)(n_cons + 1) * 8, grp_ptr), a_grp_kind = s.add((size_t)n_groups * 4, grp_kind);
+  const size_t a_grp_term_ptr = s.add((size_t)(n_groups + 1) * 8, grp_term_ptr);
+  const size_t a_grp_terms = s.add((size_t)n_terms_all * 4, grp_terms);
+  const size_t a_base_ptr = s.add((size_t)(n_base + 1) * 8, base_ptr), a_base_rows = s.add((size_t)n_base_rows * 8, base_rows);
+  const size_t a_cons_base = s.add((size_t)n_cons * 4, cons_base);
+  const size_t a_x_ptr = s.add(n_x ? (size_t)(n_x + 1) * 8 : 0, x_ptr), a_x_doc = s.add((size_t)n_x_docs * 4, x_doc);
+  const size_t a_scope_ptr = s.add((size_t)(n_cons + 1) * 8), a_rows = s.add((size_t)rows_cap * 8);
+  const size_t a_status = s.add((size_t)n_cons * 4);
+  const size_t a_work = s.add(list_work(ts_cells(n_cons, cand_max), kTsCellBytes).total);
+  if ((rc = s.upload(bm25))) return rc;
   hipStream_t st = bm25->stream;
-  for (int i = 0; i < kOps; ++i)
-    if (b[i] && src[i]) AMDR_HIP(hipMemcpyAsync(p + at[i], src[i], b[i], hipMemcpyHostToDevice, st));
-  if (n_base == 0) AMDR_HIP(hipMemsetAsync(p + at[4], 0, 8, st));
+  if (n_base == 0) AMDR_HIP(hipMemsetAsync(s.at<void>(a_base_ptr), 0, 8, st));
   const BmIndex& ix = bm25->ix;
-  const TsIndex I{ix.term_ptr,  ix.post_doc, (long)ix.n_terms, (long)ix.n_docs, (const long long*)(p + at[7]),
-                  (const int*)(p + at[8]), (long)n_x};
-  const TsCons C{(const long long*)(p + at[0]), (const int*)(p + at[1]), (const long long*)(p + at[2]), (const int*)(p + at[3]),
-                 (const long long*)(p + at[4]), (const long long*)(p + at[5]), (const int*)(p + at[6]), (int)n_base};
-  const TsOut o{(long long*)(p + at[kOps]), (long long*)(p + at[kOps + 1]), (int*)(p + at[kOps + 2])};
-  if ((rc = ts_launch(I, C, n_cons, cand_max, rows_cap, o, p + at[kOps + 3], st))) return rc;
-  AMDR_HIP(hipMemcpyAsync(out_scope_ptr, o.scope_ptr, (size_t)(n_cons + 1) * 8, hipMemcpyDeviceToHost, st));
-  AMDR_HIP(hipMemcpyAsync(out_status, o.status, (size_t)n_cons * 4, hipMemcpyDeviceToHost, st));
-  AMDR_HIP(hipStreamSynchronize(st));
-  const int64_t used = out_scope_ptr[n_cons];  // <= rows_cap: only the rows the table names come back
-  if (used > 0) {
-    AMDR_HIP(hipMemcpyAsync(out_rows, o.rows, (size_t)used * 8, hipMemcpyDeviceToHost, st));
-    AMDR_HIP(hipStreamSynchronize(st));
-  }
-  return AMDR_OK;
+  const TsIndex I{ix.term_ptr, ix.post_doc, (long)ix.n_terms, (long)ix.n_docs, s.at<long long>(a_x_ptr), s.at<int>(a_x_doc),
+                  (long)n_x};
+  const TsCons C{s.at<long long>(a_grp_ptr), s.at<int>(a_grp_kind), s.at<long long>(a_grp_term_ptr), s.at<int>(a_grp_terms),
+                 s.at<long long>(a_base_ptr), s.at<long long>(a_base_rows), s.at<int>(a_cons_base), (int)n_base};
+  const TsOut o{s.at<long long>(a_scope_ptr), s.at<long long>(a_rows), s.at<int>(a_status)};
+  if ((rc = ts_launch(I, C, n_cons, cand_max, rows_cap, o, s.at<unsigned char>(a_work), st))) return rc;
+  // (used <= rows_cap: only the rows the table names come back)
+  return list_fetch(st, n_cons, o.scope_ptr, o.status, o.rows, 8, out_scope_ptr, out_status, out_rows);
 }
 
 int amdr_term_scope(amdr_bm25_t* bm25, const int64_t* grp_ptr, const int32_t* grp_kind, const int64_t* grp_term_ptr,

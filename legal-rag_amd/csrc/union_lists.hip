@@ -7,7 +7,7 @@
 // amdr_term_scope_lists (term_scope.hip) reads as one more term, beside the lists of the phrases and the Nears
 // (phrase_scope.hip).  It needs the postings only, not the token stream.
 //
-// Three launches in the shape of phrase_scope.hip, no global atomics, deterministic, nothing allocated; the grid is ONE-
+// The three launches of list_step.hpp, no global atomics, deterministic, nothing allocated; the grid is ONE-
 // dimensional, n_items x tiles blocks of kUnThreads threads, cell = p * tiles + y (item p, tile y of kUnTile documents):
 //   count   the block clears a bitmap of kUnTile bits in LDS; its waves take the item's terms round-robin; for a term the
 //           wave finds the part of the posting list inside the tile (un_tile_range: two lower-bound searches on
@@ -26,8 +26,7 @@
 // starts an array: start is 0 and the call writes list_ptr[0] itself.
 // Every barrier sits under a block-uniform condition: the term loop holds none, and nothing returns before the last one.
 // LDS: the bitmap (4 096 B) and the scan's wave sums.  Workspace per cell: two i64 and the 4 KiB bitmap.
-#include "bm25_handle.hpp"
-#include "compact.hpp"
+#include "list_step.hpp"
 #include "union_rule.hpp"
 
 #include <mutex>
@@ -37,23 +36,10 @@ using namespace amdr;
 namespace {
 
 constexpr int kUnWaves = kUnThreads / 64;
-constexpr size_t kUnAlign = 256;
 static_assert(kUnThreads % 64 == 0, "whole waves");
 
-size_t un_align(size_t b) { return (b + kUnAlign - 1) / kUnAlign * kUnAlign; }
-
-// Workspace: counts i64 [cells] | offsets i64 [cells + 1] | parked bitmaps u32 [cells * kUnWords]
-struct UnWork {
-  size_t off_counts, off_offsets, off_bits, total;
-};
-UnWork un_work(long long cells) {
-  UnWork w;
-  w.off_counts = 0;
-  w.off_offsets = un_align((size_t)cells * sizeof(long long));
-  w.off_bits = w.off_offsets + un_align(((size_t)cells + 1) * sizeof(long long));
-  w.total = w.off_bits + un_align((size_t)cells * kUnWords * sizeof(unsigned));
-  return w;
-}
+// Workspace (list_work): a cell's payload is its parked bitmap u32 [kUnWords]
+constexpr size_t kUnCellBytes = kUnWords * sizeof(unsigned);
 
 __global__ __launch_bounds__(kUnThreads) void union_count_kernel(UnIndex I, const long long* __restrict__ item_ptr,
                                                                 const int* __restrict__ item_terms, long long tiles,
@@ -96,14 +82,9 @@ __global__ __launch_bounds__(kUnThreads) void union_write_kernel(long long tiles
   __shared__ int wsum[kUnWaves + 1];
   const long long cell = blockIdx.x;
   const long long p = cell / tiles, tile = cell - p * tiles;
-  // (entry n_before is not written by this launch unless n_before == 0, and then it is not read)
-  const long long start = n_before > 0 ? list_ptr[n_before] : 0;
-  if (tile == 0 && threadIdx.x == 0) {
-    const long long begin = start + offsets[p * tiles], end = start + offsets[(p + 1) * tiles];
-    if (n_before == 0 && p == 0) list_ptr[0] = 0;
-    list_ptr[n_before + p + 1] = un_clamp(end, rows_cap);
-    status[p] = un_status(begin, end, rows_cap);
-  }
+  const long long start = list_start(list_ptr, n_before);
+  if (tile == 0 && threadIdx.x == 0)
+    status[p] = list_write_header(list_ptr, n_before, p, start + offsets[p * tiles], start + offsets[(p + 1) * tiles], rows_cap);
   const uint4 w = parked[(size_t)cell * kUnThreads + threadIdx.x];
   const unsigned word[kUnPer] = {w.x, w.y, w.z, w.w};
   int mine = 0;
@@ -124,25 +105,18 @@ struct UnOut {
 
 int un_launch(const UnIndex& I, const long long* item_ptr, const int* item_terms, int64_t n_items, int64_t n_before,
               int64_t rows_cap, const UnOut& o, unsigned char* work, hipStream_t st) {
-  if (n_items == 0) {
-    if (n_before == 0) AMDR_HIP(hipMemsetAsync(o.list_ptr, 0, sizeof(long long), st));
-    return AMDR_OK;
-  }
   const long long tiles = un_tiles(I.n_docs), cells = (long long)n_items * tiles;
-  const UnWork w = un_work(cells);
-  long long* counts = reinterpret_cast<long long*>(work + w.off_counts);
-  long long* offsets = reinterpret_cast<long long*>(work + w.off_offsets);
-  uint4* parked = reinterpret_cast<uint4*>(work + w.off_bits);
   const dim3 grid((unsigned)cells);
-  hipLaunchKernelGGL(union_count_kernel, grid, dim3(kUnThreads), 0, st, I, item_ptr, item_terms, tiles, counts, parked);
-  AMDR_HIP(hipGetLastError());
-  hipLaunchKernelGGL(compact_scan_i64_kernel, dim3(1), dim3(kCompactScanThreads), 0, st, (const long long*)counts, (long)cells,
-                     offsets);
-  AMDR_HIP(hipGetLastError());
-  hipLaunchKernelGGL(union_write_kernel, grid, dim3(kUnThreads), 0, st, tiles, (long long)n_before, (long long)rows_cap,
-                     (const long long*)offsets, (const uint4*)parked, o.list_ptr, o.docs, o.status);
-  AMDR_HIP(hipGetLastError());
-  return AMDR_OK;
+  return list_launch(
+      st, n_items, n_before, (size_t)cells, kUnCellBytes, o.list_ptr, work,
+      [&](long long* counts, unsigned char* parked) {
+        hipLaunchKernelGGL(union_count_kernel, grid, dim3(kUnThreads), 0, st, I, item_ptr, item_terms, tiles, counts,
+                           (uint4*)parked);
+      },
+      [&](const long long* offsets, const unsigned char* parked) {
+        hipLaunchKernelGGL(union_write_kernel, grid, dim3(kUnThreads), 0, st, tiles, (long long)n_before, (long long)rows_cap,
+                           offsets, (const uint4*)parked, o.list_ptr, o.docs, o.status);
+      });
 }
 
 // sizes every entry point refuses (nothing is enqueued); *cells: the cells of the launch
@@ -167,7 +141,7 @@ int amdr_union_lists_plan(int64_t n_items, int64_t n_docs, int64_t* work_bytes) 
   long long cells = 0;
   int rc = un_check_sizes("union_lists_plan", n_items, n_docs, 0, 0, &cells);
   if (rc) return rc;
-  *work_bytes = (int64_t)un_work(cells).total;
+  *work_bytes = (int64_t)list_work((size_t)cells, kUnCellBytes).total;
   return AMDR_OK;
 }
 
@@ -182,10 +156,8 @@ int amdr_union_lists_device(amdr_bm25_t* bm25, const int64_t* item_ptr_dev, cons
   AMDR_REQUIRE(list_ptr_dev != nullptr, "%s: null list_ptr", who);
   AMDR_REQUIRE(n_items == 0 || (item_ptr_dev && item_terms_dev && out_status_dev), "%s: null operand", who);
   AMDR_REQUIRE(rows_cap == 0 || docs_dev, "%s: null docs", who);
-  AMDR_REQUIRE(work_bytes >= 0, "%s: work_bytes=%lld", who, (long long)work_bytes);
-  const size_t need = n_items ? un_work(cells).total : 0;
-  AMDR_REQUIRE((size_t)work_bytes >= need && (need == 0 || work_dev), "%s: a workspace of %lld bytes, the plan asks for %zu", who,
-               (long long)work_bytes, need);
+  const size_t need = n_items ? list_work((size_t)cells, kUnCellBytes).total : 0;
+  if ((rc = list_check_work(who, work_dev, work_bytes, need))) return rc;
   AMDR_HIP(hipSetDevice(bm25->device));
   const UnOut o{(long long*)list_ptr_dev, docs_dev, out_status_dev};
   return un_launch(un_index(bm25), (const long long*)item_ptr_dev, item_terms_dev, n_items, n_before, rows_cap, o,
@@ -211,33 +183,20 @@ int amdr_union_lists(amdr_bm25_t* bm25, const int64_t* item_ptr, const int32_t* 
     return AMDR_OK;
   }
   AMDR_HIP(hipSetDevice(bm25->device));
-  // Layout of the staging buffer: item_ptr | item_terms | list_ptr | docs | status | the workspace, each aligned.
-  const size_t n_all = (size_t)item_ptr[n_items];
-  size_t at[6], total = 0;
-  at[0] = total, total += un_align((size_t)(n_items + 1) * 8);
-  at[1] = total, total += un_align((n_all + 1) * 4);  // (+ 1: never an empty region)
-  at[2] = total, total += un_align((size_t)(n_items + 1) * 8);
-  at[3] = total, total += un_align(((size_t)rows_cap + 1) * 4);
-  at[4] = total, total += un_align((size_t)n_items * 4);
-  at[5] = total, total += un_work(cells).total;
-  if ((rc = bm25->tscope.ensure(total))) return rc;
-  unsigned char* p = bm25->tscope.as<unsigned char>();
+  // The staging buffer: the item arrays, the outputs, the workspace.
+  ListStage s;
+  const size_t a_ptr = s.add((size_t)(n_items + 1) * 8, item_ptr), a_terms = s.add((size_t)item_ptr[n_items] * 4, item_terms);
+  const size_t a_list_ptr = s.add((size_t)(n_items + 1) * 8), a_docs = s.add((size_t)rows_cap * 4);
+  const size_t a_status = s.add((size_t)n_items * 4);
+  const size_t a_work = s.add(list_work((size_t)cells, kUnCellBytes).total);
+  if ((rc = s.upload(bm25))) return rc;
+  const UnOut o{s.at<long long>(a_list_ptr), s.at<int>(a_docs), s.at<int>(a_status)};
   hipStream_t st = bm25->stream;
-  AMDR_HIP(hipMemcpyAsync(p + at[0], item_ptr, (size_t)(n_items + 1) * 8, hipMemcpyHostToDevice, st));
-  if (n_all) AMDR_HIP(hipMemcpyAsync(p + at[1], item_terms, n_all * 4, hipMemcpyHostToDevice, st));
-  const UnOut o{(long long*)(p + at[2]), (int*)(p + at[3]), (int*)(p + at[4])};
-  if ((rc = un_launch(un_index(bm25), (const long long*)(p + at[0]), (const int*)(p + at[1]), n_items, 0, rows_cap, o, p + at[5],
-                      st)))
+  if ((rc = un_launch(un_index(bm25), s.at<long long>(a_ptr), s.at<int>(a_terms), n_items, 0, rows_cap, o,
+                      s.at<unsigned char>(a_work), st)))
     return rc;
-  AMDR_HIP(hipMemcpyAsync(out_list_ptr, o.list_ptr, (size_t)(n_items + 1) * 8, hipMemcpyDeviceToHost, st));
-  AMDR_HIP(hipMemcpyAsync(out_status, o.status, (size_t)n_items * 4, hipMemcpyDeviceToHost, st));
-  AMDR_HIP(hipStreamSynchronize(st));
-  const int64_t used = out_list_ptr[n_items];  // <= rows_cap: only the documents the lists name come back
-  if (used > 0) {
-    AMDR_HIP(hipMemcpyAsync(out_docs, o.docs, (size_t)used * 4, hipMemcpyDeviceToHost, st));
-    AMDR_HIP(hipStreamSynchronize(st));
-  }
-  return AMDR_OK;
+  // (used <= rows_cap: only the documents the lists name come back)
+  return list_fetch(st, n_items, o.list_ptr, o.status, o.docs, 4, out_list_ptr, out_status, out_docs);
 }
 
 }  // extern "C"

@@ -234,107 +234,98 @@ class HybridEngine:
             raise ValueError("term constraints need the BM25 index (they are resolved on its resident postings)")
 
     def term_scopes(self, table):
-        """Term constraints -> the scope table of the scoped channels, on the device (amdr_term_scope_device, three
-        launches on the current stream, no host synchronise).  table: retrieval/terms.py pack() — the operand arrays,
-        each question's constraint and the host bounds.  The operands go up through ONE pinned staging copy (the ring of
-        upload_scopes: they hold until two more term_scopes calls).  Returns ((scope_ptr, rows, qscope, n_scopes,
-        rows_max), status): the 5-tuple upload_scopes returns — n_scopes = the constraint count, rows_max = cand_max —
-        which search_batch(scopes=) and capture take as they take an uploaded table (the channels must share the BM25
-        index's chunk list), and the status tensor i32 [n_cons] (0; 1 / 2: cand_max / rows_cap exceeded — never with
-        pack()'s bounds on the index they were computed from).  The outputs are this engine's buffers: they hold until the
-        next term_scopes call.
-        A table with phrases (table.n_phr > 0): the phrase step (amdr_phrase_lists_device, three launches) is enqueued
-        first on the same stream and the term step reads its lists as the terms n_terms + p (amdr_term_scope_lists_device);
-        the BM25 handle must hold the token stream (BM25Index.set_tokens).  The status tensor is then i32 [n_cons + n_phr]:
-        the constraints' words, then the phrases'.
-        A table with Nears (table.n_near > 0): ONE span step (amdr_span_lists_device, the same three launches) takes the
-        phrase step's place — the phrases go first as kind 0, then the Nears, into one list array — and the status tensor
-        is i32 [n_cons + n_phr + n_near].  Without a Near the calls are those above.
-        A table with unions (table.n_union > 0, a Prefix or a OneOf): the union step (amdr_union_lists_device, three
-        launches, needs no token stream) is enqueued behind the span or phrase step on the same stream — first, with
-        n_before = 0, when there is none — and CONTINUES the same list array, sized for span_rows_cap + union_rows_cap; the
-        term step then reads n_phr + n_near + n_union lists and the status tensor is i32 [n_cons + n_phr + n_near +
-        n_union].  Without a union the calls are those above.
-        A table with class spans (table.n_cspan > 0, a PhraseOf or a NearOf with a union among its slots): the class step
-        (amdr_class_spans_device, three launches, needs the token stream) is enqueued behind the union step on the same
-        stream and CONTINUES the same list array, sized for span_rows_cap + union_rows_cap + cspan_rows_cap: its classes are
-        the unions (cls_first = n_phr + n_near) and it reads their lists where the union step wrote them.  The term step
-        then reads n_phr + n_near + n_union + n_cspan lists and the status tensor grows by n_cspan.  Without a class span
-        the calls are those above."""
+        """Term constraints -> the scope table of the scoped channels, on the device, on the current stream, without a host
+        synchronise.  table: retrieval/terms.py pack() — the operand arrays, each question's constraint and the host bounds.
+        The operands go up through ONE pinned staging copy (the ring of upload_scopes: they hold until two more term_scopes
+        calls).  Returns ((scope_ptr, rows, qscope, n_scopes, rows_max), status): the 5-tuple upload_scopes returns —
+        n_scopes = the constraint count, rows_max = cand_max — which search_batch(scopes=) and capture take as they take an
+        uploaded table (the channels must share the BM25 index's chunk list), and the status tensor i32 (0; 1 / 2: cand_max
+        / rows_cap exceeded — never with pack()'s bounds on the index they were computed from).  The outputs are this
+        engine's buffers: they hold until the next term_scopes call.
+        The chain: the table's LIST STEPS, each three launches, write the lists of its phrases and Nears, its unions (a
+        Prefix or a OneOf) and its class spans (a PhraseOf or a NearOf) back to back into ONE list array, in that order —
+        the first step present starts the array, every later one continues it behind the n_before lists written so far —
+        and the term step (amdr_term_scope_device; with lists amdr_term_scope_lists_device) reads list x as the term
+        n_terms + x.  The steps, each only when the table has its items:
+          span    amdr_span_lists_device over the phrases (kind 0) and then the Nears; a table without a Near takes
+                  amdr_phrase_lists_device over its phrases instead.  Needs the token stream (BM25Index.set_tokens).
+          union   amdr_union_lists_device; needs no token stream.
+          class   amdr_class_spans_device; its classes are the unions (cls_first = the span step's lists) and it reads
+                  their lists where the union step wrote them.  Needs the token stream.
+        The array is sized for the steps' row bounds together, and the status tensor holds the constraints' words and then
+        each step's, in list order: i32 [n_cons + n_phr + n_near + n_union + n_cspan]."""
         self.check_term_scopes()
         n_cons, cand_max, rows_cap = int(table.n_cons), int(table.cand_max), int(table.rows_cap)
         n_phr = int(getattr(table, "n_phr", 0))
         n_near = int(getattr(table, "n_near", 0))
         n_union = int(getattr(table, "n_union", 0))
         n_cspan = int(getattr(table, "n_cspan", 0))
-        order = (0, 2, 4, 5, 1, 3, 6)  # the i64 arrays first: every one starts on a multiple of its item size
-        parts = [(i, np.ascontiguousarray(table.ops[i], dtype=t).view(np.uint8))
-                 for i, t in ((i, _native.BM25Index.TERM_OPS[i]) for i in order)]
-        if n_near:  # the items of the one span step: the phrases as kind 0, then the Nears
-            parts.insert(4, (8, np.ascontiguousarray(table.span_ops[0], dtype=np.int64).view(np.uint8)))
-            parts.extend((9 + j, np.ascontiguousarray(table.span_ops[1 + j], dtype=np.int32).view(np.uint8)) for j in range(3))
-        elif n_phr:
-            parts.insert(4, (8, np.ascontiguousarray(table.phr_ops[0], dtype=np.int64).view(np.uint8)))
-            parts.append((9, np.ascontiguousarray(table.phr_ops[1], dtype=np.int32).view(np.uint8)))
-        if n_union:  # the items of the union step
-            parts.insert(4, (12, np.ascontiguousarray(table.union_ops[0], dtype=np.int64).view(np.uint8)))
-            parts.append((13, np.ascontiguousarray(table.union_ops[1], dtype=np.int32).view(np.uint8)))
-        if n_cspan:  # the items of the class step
-            parts.insert(4, (14, np.ascontiguousarray(table.cspan_ops[0], dtype=np.int64).view(np.uint8)))
-            parts.extend((15 + j, np.ascontiguousarray(table.cspan_ops[1 + j], dtype=np.int32).view(np.uint8)) for j in range(3))
-        parts.append((7, np.ascontiguousarray(table.qscope, dtype=np.int32).view(np.uint8)))
-        total = sum(p.size for _, p in parts)
-        host, dev, ev = self._staging("tsc", max(total, 8))
-        hv, at, where = host.numpy(), 0, {}
-        for i, p in parts:
-            hv[at:at + p.size] = p
-            where[i] = (at, p.size)
-            at += p.size
-        self._send(host, dev, ev, max(total, 8))
-        base = dev.data_ptr()
-        o_rows, o_status = 8 * (n_cons + 1), 8 * (n_cons + 1) + 8 * rows_cap
         n_span = n_phr + n_near
         n_x = n_span + n_union + n_cspan  # the virtual lists of the term step
+        span_cap = (int(table.span_rows_cap) if n_near else int(table.phr_rows_cap)) if n_x else 0
+        list_cap = span_cap + int(getattr(table, "union_rows_cap", 0)) + (int(table.cspan_rows_cap) if n_cspan else 0)
+        # The list steps in call order: (name, operands: item_ptr i64 and then i32 arrays, item count, n_before, the key of
+        # its grown workspace, plan() -> bytes, call(operand pointers, at, the output and workspace arguments)).
+        steps = []
+        if n_near:
+            p_max = int(table.span_cand_max)
+            steps.append(("span", table.span_ops, n_span, 0, "phw", lambda: _native.span_lists_plan(n_span, p_max),
+                          lambda ops, at, out: self.bm25.span_lists_device(*ops, n_span, p_max, span_cap, *out)))
+        elif n_phr:
+            p_max = int(table.phr_cand_max)
+            steps.append(("span", table.phr_ops, n_phr, 0, "phw", lambda: _native.phrase_lists_plan(n_phr, p_max),
+                          lambda ops, at, out: self.bm25.phrase_lists_device(*ops, n_phr, p_max, span_cap, *out)))
+        if n_union:
+            steps.append(("union", table.union_ops, n_union, n_span, "unw",
+                          lambda: _native.union_lists_plan(n_union, int(self.bm25.n_docs)),
+                          lambda ops, at, out: self.bm25.union_lists_device(*ops, n_union, n_span, list_cap, *out)))
+        if n_cspan:
+            c_max = int(table.cspan_cand_max)
+            steps.append(("class", table.cspan_ops, n_cspan, n_span + n_union, "csw",
+                          lambda: _native.class_spans_plan(n_cspan, c_max),
+                          lambda ops, at, out: self.bm25.class_spans_device(
+                              *ops, n_cspan, *((at["union0"], at["union1"]) if n_union else (0, 0)), n_union, n_span,
+                              n_span + n_union, c_max, list_cap, *out)))
+        # Staging, the i64 arrays first (every array starts on a multiple of its item size): the term step's, the steps'
+        # item_ptr (the last step's first); then the i32 arrays: the term step's, each step's in call order, qscope.
+        term_names = ("grp_ptr", "grp_kind", "grp_term_ptr", "grp_terms", "base_ptr", "base_rows", "cons_base")
+        term = {n: np.ascontiguousarray(a, dtype=t) for n, a, t in zip(term_names, table.ops, _native.BM25Index.TERM_OPS)}
+        wide = [(n, term[n]) for n in ("grp_ptr", "grp_term_ptr", "base_ptr", "base_rows")]
+        wide += [(f"{name}0", np.ascontiguousarray(ops[0], dtype=np.int64)) for name, ops, *_ in reversed(steps)]
+        narrow = [(n, term[n]) for n in ("grp_kind", "grp_terms", "cons_base")]
+        narrow += [(f"{name}{j}", np.ascontiguousarray(ops[j], dtype=np.int32)) for name, ops, *_ in steps
+                   for j in range(1, len(ops))]
+        narrow.append(("qscope", np.ascontiguousarray(table.qscope, dtype=np.int32)))
+        parts = [(n, a.view(np.uint8)) for n, a in wide + narrow]
+        total = sum(p.size for _, p in parts)
+        host, dev, ev = self._staging("tsc", max(total, 8))
+        hv, off, at = host.numpy(), 0, {}
+        base = dev.data_ptr()
+        for n, p in parts:
+            hv[off:off + p.size] = p
+            at[n] = base + off
+            off += p.size
+        self._send(host, dev, ev, max(total, 8))
+        o_rows, o_status = 8 * (n_cons + 1), 8 * (n_cons + 1) + 8 * rows_cap
         out = self._grown("tso", o_status + 4 * (n_cons + n_x) + 8)
         lists = None
-        if n_x:  # ONE list array: the span (or phrase) step begins it, the union step and the class step continue it
-            span_cap = int(table.span_rows_cap) if n_near else int(table.phr_rows_cap)
-            list_cap = span_cap + int(getattr(table, "union_rows_cap", 0)) + (int(table.cspan_rows_cap) if n_cspan else 0)
+        if n_x:  # ONE list array: the first step begins it, the later ones continue it
             o_docs = 8 * (n_x + 1)
             pout = self._grown("pho", o_docs + 4 * list_cap + 8)
             x_ptr, x_doc, x_status = pout.data_ptr(), pout.data_ptr() + o_docs, out.data_ptr() + o_status + 4 * n_cons
-            if n_near:  # the span step: phrases and Nears
-                p_max = int(table.span_cand_max)
-                p_bytes = _native.span_lists_plan(n_span, p_max)
-                pwork = self._grown("phw", p_bytes)
-                self.bm25.span_lists_device(base + where[8][0], base + where[9][0], base + where[10][0], base + where[11][0],
-                                            n_span, p_max, span_cap, x_ptr, x_doc, x_status, pwork.data_ptr(), p_bytes, _stream())
-            elif n_phr:  # the phrase step: its lists are the virtual terms of the term step behind it
-                p_max = int(table.phr_cand_max)
-                p_bytes = _native.phrase_lists_plan(n_phr, p_max)
-                pwork = self._grown("phw", p_bytes)
-                self.bm25.phrase_lists_device(base + where[8][0], base + where[9][0], n_phr, p_max, span_cap, x_ptr, x_doc,
-                                              x_status, pwork.data_ptr(), p_bytes, _stream())
-            if n_union:  # the union step: behind the n_span lists on the same stream (first, with n_before = 0)
-                u_bytes = _native.union_lists_plan(n_union, int(self.bm25.n_docs))
-                uwork = self._grown("unw", u_bytes)
-                self.bm25.union_lists_device(base + where[12][0], base + where[13][0], n_union, n_span, list_cap, x_ptr, x_doc,
-                                             x_status + 4 * n_span, uwork.data_ptr(), u_bytes, _stream())
-            if n_cspan:  # the class step: behind the unions, which are its classes
-                c_max = int(table.cspan_cand_max)
-                c_bytes = _native.class_spans_plan(n_cspan, c_max)
-                cwork = self._grown("csw", c_bytes)
-                u_ptr, u_terms = (base + where[12][0], base + where[13][0]) if n_union else (0, 0)
-                self.bm25.class_spans_device(base + where[14][0], base + where[15][0], base + where[16][0], base + where[17][0],
-                                             n_cspan, u_ptr, u_terms, n_union, n_span, n_span + n_union, c_max, list_cap, x_ptr,
-                                             x_doc, x_status + 4 * (n_span + n_union), cwork.data_ptr(), c_bytes, _stream())
+            for name, ops, _, n_before, key, plan, call in steps:
+                w_bytes = plan()
+                work = self._grown(key, w_bytes)
+                call([at[f"{name}{j}"] for j in range(len(ops))], at,
+                     (x_ptr, x_doc, x_status + 4 * n_before, work.data_ptr(), w_bytes, _stream()))
             lists = (x_ptr, x_doc, n_x)
         work_bytes = _native.term_scope_plan(n_cons, cand_max)
         work = self._grown("tsw", work_bytes)
-        self.bm25.term_scope_device([base + where[i][0] for i in range(7)], int(table.n_base), n_cons, int(table.n_groups),
-                                    cand_max, rows_cap, out.data_ptr(), out.data_ptr() + o_rows, out.data_ptr() + o_status,
+        self.bm25.term_scope_device([at[n] for n in term_names], int(table.n_base), n_cons, int(table.n_groups), cand_max,
+                                    rows_cap, out.data_ptr(), out.data_ptr() + o_rows, out.data_ptr() + o_status,
                                     work.data_ptr(), work_bytes, _stream(), lists=lists)
-        q0, qn = where[7]
+        q0 = at["qscope"] - base
+        qn = parts[-1][1].size
         return ((out[:o_rows].view(torch.int64), out[o_rows:o_status].view(torch.int64), dev[q0:q0 + qn].view(torch.int32),
                  n_cons, cand_max), out[o_status:o_status + 4 * (n_cons + n_x)].view(torch.int32))
 

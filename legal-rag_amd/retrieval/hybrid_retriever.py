@@ -237,33 +237,35 @@ class HybridRetriever:
                          resolver_for(bm.chunks).rows, model.sorted_vocab() if terms.has_union or terms.has_class_span else None)
         if tt.cand_max == 0:
             return np.zeros(0, dtype=np.int64)
+        def check(status, name) -> None:
+            """RuntimeError naming the first item whose status word is non-zero (name(i): the item; None: the constraint)."""
+            if status.any():
+                i = int(np.flatnonzero(status)[0])
+                what = f"{name(i)!r}" if name is not None else "the term constraint"
+                raise RuntimeError(f"{who}(terms=): {what} overflowed its bound (status {int(status[i])}); the "
+                                   f"host model and the resident BM25 index disagree")
+
+        def behind(lists, lp, docs):
+            """The lists (lp, docs) of a step appended behind the array `lists` (None: they start it)."""
+            if lists is None:
+                return lp, docs
+            return np.concatenate([lists[0], lists[0][-1] + lp[1:]]), np.concatenate([lists[1], docs])
+
         lists = None
         if tt.n_near:  # phrases and Nears in one span step, into one array of document lists
             bm.ensure_token_stream()
             lp, docs, p_status = bm.gpu_index().span_lists(*tt.span_ops, tt.span_cand_max, tt.span_rows_cap)
-            if p_status.any():
-                p = int(np.flatnonzero(p_status)[0])
-                raise RuntimeError(f"{who}(terms=): {tt.span_item(p)!r} overflowed its bound (status {int(p_status[p])}); the "
-                                   f"host model and the resident BM25 index disagree")
-            lists = (lp, docs)
+            check(p_status, tt.span_item)
+            lists = behind(lists, lp, docs)
         elif tt.n_phr:  # the phrases first, into their own document lists: the virtual terms of the constraint
             bm.ensure_token_stream()
             lp, docs, p_status = bm.gpu_index().phrase_lists(tt.phr_ops[0], tt.phr_ops[1], tt.phr_cand_max, tt.phr_rows_cap)
-            if p_status.any():
-                p = int(np.flatnonzero(p_status)[0])
-                raise RuntimeError(f"{who}(terms=): {tt.phrases[p]!r} overflowed its bound (status {int(p_status[p])}); the "
-                                   f"host model and the resident BM25 index disagree")
-            lists = (lp, docs)
+            check(p_status, lambda p: tt.phrases[p])
+            lists = behind(lists, lp, docs)
         if tt.n_union:  # the unions behind them, in the same arrays
             u_lp, u_docs, u_status = bm.gpu_index().union_lists(*tt.union_ops, tt.union_rows_cap)
-            if u_status.any():
-                u = int(np.flatnonzero(u_status)[0])
-                raise RuntimeError(f"{who}(terms=): {tt.unions[u]!r} overflowed its bound (status {int(u_status[u])}); the "
-                                   f"host model and the resident BM25 index disagree")
-            if lists is None:
-                lists = (u_lp, u_docs)
-            else:
-                lists = (np.concatenate([lists[0], lists[0][-1] + u_lp[1:]]), np.concatenate([lists[1], u_docs]))
+            check(u_status, lambda u: tt.unions[u])
+            lists = behind(lists, u_lp, u_docs)
         if tt.n_cspan:  # the class spans behind the unions: the twin resolves the classes it needs itself, in its own array
             bm.ensure_token_stream()
             c_ptr, c_slots, c_kind, c_dist = tt.cspan_ops
@@ -271,18 +273,10 @@ class HybridRetriever:
             c_lp, c_docs, c_status = bm.gpu_index().class_spans(c_ptr, np.where(c_slots >= first, c_slots - (tt.n_phr + tt.n_near),
                                                                                  c_slots), c_kind, c_dist, *tt.union_ops,
                                                                  tt.cspan_cand_max, tt.cspan_rows_cap)
-            if c_status.any():
-                c = int(np.flatnonzero(c_status)[0])
-                raise RuntimeError(f"{who}(terms=): {tt.cspans[c]!r} overflowed its bound (status {int(c_status[c])}); the "
-                                   f"host model and the resident BM25 index disagree")
-            if lists is None:
-                lists = (c_lp, c_docs)
-            else:
-                lists = (np.concatenate([lists[0], lists[0][-1] + c_lp[1:]]), np.concatenate([lists[1], c_docs]))
+            check(c_status, lambda c: tt.cspans[c])
+            lists = behind(lists, c_lp, c_docs)
         _, rows, status = bm.gpu_index().term_scope(tt.ops, tt.cand_max, tt.rows_cap, lists=lists)
-        if int(status[0]) != 0:
-            raise RuntimeError(f"{who}(terms=): the term constraint overflowed its bound (status {int(status[0])}); the "
-                               f"host model and the resident BM25 index disagree")
+        check(status[:1], None)
         return rows
 
     def phrase(self, text_: str) -> Phrase:
