@@ -1138,6 +1138,61 @@ int amdr_class_spans(amdr_bm25_t* bm25, const int64_t* item_ptr, const int32_t* 
                      const int32_t* item_dist, int64_t n_items, const int64_t* cls_ptr, const int32_t* cls_terms, int64_t n_cls,
                      int64_t cand_max, int64_t rows_cap, int64_t* out_list_ptr, int32_t* out_docs, int32_t* out_status);
 
+/* ---- marks and best passages of the hit documents (csrc/marks.hip, csrc/marks_rule.hpp) --------
+ * No reference counterpart.  For every (query, hit) pair: which tokens of the hit document the query MARKS, and the window
+ * of `window` tokens that holds the most of the query — term highlighting and the best-passage snippet, from the resident
+ * token stream (amdr_bm25_set_tokens; the carrying updates keep it).
+ *   docs i64 [nq, ld_docs]          the hit ids, k per query (ld_docs >= k); -1: no hit.
+ *   mk_ptr i64 [nq + 1], mk_terms i32, mk_slot i32   query q's mark table: mk_terms[mk_ptr[q] .. mk_ptr[q + 1]) strictly
+ *                                   ascending, distinct term ids; mk_slot, parallel, the SLOT 0 .. 31 the token fills.  A slot
+ *                                   is one query word: a plain token or a class (a Prefix's tokens, a OneOf's members).  A
+ *                                   token outside the table fills nothing.
+ *   slot_w f64 [nq, 32]             the slots' weights.
+ *   slot_loose u32 [nq]             bit s: slot s marks its token wherever it stands.
+ *   sq_ptr i64 [nq + 1], sq_off i64 [n_seq + 1], sq_slots i32   query q's sequences sq_ptr[q] .. sq_ptr[q + 1]; sequence s is
+ *                                   the L slots sq_slots[sq_off[s] .. sq_off[s + 1]), 2 <= L <= 16: a phrase.  It OCCURS at
+ *                                   position p of a document when token p + j fills slot j of it for every j and p + L stays
+ *                                   inside the document.
+ * Position p is MARKED when m(p) = (slot mask of token p & slot_loose[q]) | cover(p) != 0, cover(p) the OR of the slot of
+ * member j over every occurrence at p - j; its slot is the lowest set bit of m(p).  A slot that is only a phrase member
+ * marks a token only inside an occurrence of the phrase.  The candidates of the best window are [a, a + window) for every
+ * marked a, clamped to the document; the score is the sum of slot_w over the DISTINCT slots of the window's marks, added
+ * in ascending slot order in fp64; the greatest score wins, ties -> the smallest a.  Marks are kept in position order up to
+ * 1 024 per document; later ones are counted only, and the best window is the best among the kept anchors (status 1).
+ *   out_win i32 [nq, k, 4]          window start (relative to the document), window end (exclusive), marks in the window,
+ *                                   marks in the document (the true count).  No mark: [0, min(window, len)), 0, 0.
+ *   out_score f64 [nq, k]           the window's score; 0.0 without marks.
+ *   out_slots u32 [nq, k, 2]        the slots in the window, the slots among the kept marks.
+ *   out_marks i32 [nq, k, marks_cap, 2]   the first marks_cap marks of the window as (relative position, slot), ascending;
+ *                                   the rest (-1, -1).  May be null when marks_cap is 0.
+ *   out_status i32 [nq, k]          0; 1: more than 1 024 marks.
+ * A hit id of -1 — in the "_device" form any id outside [0, n_docs) — gives zeros, fill marks and status 0 and reads
+ * nothing.  Outputs are packed [nq, k] whatever ld_docs is.
+ * One launch, one wave per pair in the grid's x, LDS only (6 016 B per wave whatever the document's length): no workspace,
+ * no global atomics, deterministic.  Work: the tokens of the hit documents x log2 of the mark table, plus kept marks x
+ * marks per window.
+ * amdr_bm25_marks_device only enqueues and allocates nothing (capturable).  It does not validate the operands' contents —
+ * a sequence with a slot outside 0 .. 31 or a length outside 2 .. 16 never occurs, a table slot outside 0 .. 31 fills
+ * nothing, and no value of docs_dev makes it read out of bounds — and returns AMDR_EINVAL, enqueueing nothing and leaving
+ * the outputs untouched, for a null handle, operand or output, a handle without a token stream, a negative size, ld_docs
+ * < k, nq x k >= 2^31, window outside 1 .. 4096 or marks_cap outside 0 .. 64.  amdr_bm25_marks is the host-pointer twin: it
+ * validates (AMDR_EINVAL: pointers not monotone from 0, terms not strictly ascending or outside [0, n_terms), a slot outside
+ * 0 .. 31, a sequence length outside 2 .. 16, a weight that is not finite, a hit id outside [-1, n_docs)), stages the
+ * operands in device arrays that live for the call and runs on the handle's own stream under its mutex.
+ * amdr_bm25_marks_kernel_ms: the device time of the kernel of the last amdr_bm25_marks; -1.0 when there is none.
+ * Mutations: amdr_bm25_add's rule; a plain update drops the token stream, a carrying one keeps it. */
+int amdr_bm25_marks_device(amdr_bm25_t* bm25, const int64_t* docs_dev, int64_t nq, int64_t k, int64_t ld_docs,
+                           const int64_t* mk_ptr_dev, const int32_t* mk_terms_dev, const int32_t* mk_slot_dev,
+                           const double* slot_w_dev, const uint32_t* slot_loose_dev, const int64_t* sq_ptr_dev,
+                           const int64_t* sq_off_dev, const int32_t* sq_slots_dev, int32_t window, int32_t marks_cap,
+                           int32_t* out_win_dev, double* out_score_dev, uint32_t* out_slots_dev, int32_t* out_marks_dev,
+                           int32_t* out_status_dev, void* stream);
+int amdr_bm25_marks(amdr_bm25_t* bm25, const int64_t* docs, int64_t nq, int64_t k, int64_t ld_docs, const int64_t* mk_ptr,
+                    const int32_t* mk_terms, const int32_t* mk_slot, const double* slot_w, const uint32_t* slot_loose,
+                    const int64_t* sq_ptr, const int64_t* sq_off, const int32_t* sq_slots, int32_t window, int32_t marks_cap,
+                    int32_t* out_win, double* out_score, uint32_t* out_slots, int32_t* out_marks, int32_t* out_status);
+int amdr_bm25_marks_kernel_ms(amdr_bm25_t* h, double* ms);
+
 /* ---- multi-GPU: merge per-shard top-k after the RCCL all-gather --------
  * No reference counterpart (the reference is single-process).
  * parts: [n_parts, nq, k_in] scores + GLOBAL ids (-1 padding); output

@@ -70,6 +70,8 @@ SIGNATURES = {
     "amdr_union_lists_plan": "llP", "amdr_union_lists_device": "PPP" + "lll" + "PPP" + "PlP", "amdr_union_lists": "PPP" + "ll" + "PPP",
     "amdr_class_spans_plan": "llP", "amdr_class_spans_device": "PPPPP" + "l" + "PP" + "lllll" + "PPP" + "PlP",
     "amdr_class_spans": "PPPPP" + "l" + "PP" + "lll" + "PPP",
+    "amdr_bm25_marks_device": "PPlll" + "P" * 8 + "ii" + "P" * 6, "amdr_bm25_marks": "PPlll" + "P" * 8 + "ii" + "P" * 5,
+    "amdr_bm25_marks_kernel_ms": "PP",
 }
 EXPORTS = tuple(SIGNATURES)  # every symbol include/amdretrieval.h declares (checked by tests/test_abi.py)
 _KIND = {"P": C.c_void_p, "i": C.c_int32, "l": C.c_int64, "d": C.c_double}
@@ -894,6 +896,61 @@ class BM25Index(_Handle):
                                               C.c_int64(n_cls), C.c_int64(cls_first), C.c_int64(n_before), C.c_int64(cand_max),
                                               C.c_int64(rows_cap), _vp(list_ptr_ptr), _vp(docs_ptr), _vp(status_ptr),
                                               _vp(work_ptr), C.c_int64(work_bytes), _vp(stream)), "amdr_class_spans_device")
+
+    # -- marks and best passages of the hit documents (amdr_bm25_marks, csrc/marks.hip) ---------------------------------
+    def marks(self, docs, mk_ptr, mk_terms, mk_slot, slot_w, slot_loose, sq_ptr, sq_off, sq_slots, window: int,
+              marks_cap: int):
+        """The host twin: for the hit ids docs i64 [nq, k] (-1: no hit) and per query a mark table
+        (mk_terms[mk_ptr[q] : mk_ptr[q + 1]] strictly ascending, mk_slot parallel, slots 0 .. 31), weights slot_w f64 [nq, 32],
+        loose slots slot_loose u32 [nq] and sequences (sq_ptr [nq + 1] into sq_off [n_seq + 1] into sq_slots) ->
+        (win i32 [nq, k, 4]: start, end, marks in the window, marks in the document; score f64 [nq, k]; slots u32 [nq, k, 2];
+        marks i32 [nq, k, marks_cap, 2]: (position, slot) or (-1, -1); status i32 [nq, k]).  csrc/marks_rule.hpp is the rule."""
+        d = _c(docs, np.int64)
+        if d.ndim != 2:
+            raise ValueError("marks: docs [nq, k]")
+        nq, k = d.shape
+        mp, mt, ms = _c(mk_ptr, np.int64).ravel(), _c(mk_terms, np.int32).ravel(), _c(mk_slot, np.int32).ravel()
+        sw, sl = _c(slot_w, np.float64).reshape(-1), _c(slot_loose, np.uint32).ravel()
+        sp, so, ss = _c(sq_ptr, np.int64).ravel(), _c(sq_off, np.int64).ravel(), _c(sq_slots, np.int32).ravel()
+        if mp.size != nq + 1 or sp.size != nq + 1 or sw.size != nq * 32 or sl.size != nq or so.size < 1 or ms.size != mt.size:
+            raise ValueError("marks: mk_ptr [nq + 1], sq_ptr [nq + 1], slot_w [nq, 32], slot_loose [nq], sq_off [n_seq + 1]")
+        if (mp.size and mt.size < int(mp[-1])) or (sp.size and so.size < int(sp[-1]) + 1) or ss.size < int(so[-1]):
+            raise ValueError("marks: an array shorter than its pointers say")
+        cap = int(marks_cap)
+        win = np.zeros((nq, k, 4), np.int32)
+        score = np.zeros((nq, k), np.float64)
+        slots = np.zeros((nq, k, 2), np.uint32)
+        marks = np.full((nq, k, max(cap, 0), 2), -1, np.int32)
+        status = np.zeros((nq, k), np.int32)
+        pad, padw, padu = np.zeros(1, np.int32), np.zeros(1, np.float64), np.zeros(1, np.uint32)
+        full = lambda a, z: a if a.size else z  # noqa: E731
+        _check(load().amdr_bm25_marks(self._h, _p(full(d, np.zeros(1, np.int64)), C.c_int64), C.c_int64(nq), C.c_int64(k),
+                                      C.c_int64(k), _p(mp, C.c_int64), _p(full(mt, pad), C.c_int32), _p(full(ms, pad), C.c_int32),
+                                      _p(full(sw, padw), C.c_double), _p(full(sl, padu), C.c_uint32), _p(sp, C.c_int64),
+                                      _p(so, C.c_int64), _p(full(ss, pad), C.c_int32), C.c_int32(window), C.c_int32(cap),
+                                      _p(full(win, pad), C.c_int32), _p(full(score, padw), C.c_double),
+                                      _p(full(slots, padu), C.c_uint32), _p(full(marks, pad), C.c_int32),
+                                      _p(full(status, pad), C.c_int32)), "amdr_bm25_marks")
+        return win, score, slots, marks, status
+
+    def marks_device(self, docs_ptr: int, nq: int, k: int, ld_docs: int, mk_ptr_ptr: int, mk_terms_ptr: int, mk_slot_ptr: int,
+                     slot_w_ptr: int, slot_loose_ptr: int, sq_ptr_ptr: int, sq_off_ptr: int, sq_slots_ptr: int, window: int,
+                     marks_cap: int, win_ptr: int, score_ptr: int, slots_ptr: int, marks_ptr: int, status_ptr: int,
+                     stream: int = 0) -> None:
+        """The "_device" form: operands and outputs as device pointers; enqueues one launch and allocates nothing.  Any hit
+        id outside [0, n_docs) is no hit."""
+        _check(load().amdr_bm25_marks_device(self._h, _vp(docs_ptr), C.c_int64(nq), C.c_int64(k), C.c_int64(ld_docs),
+                                             _vp(mk_ptr_ptr), _vp(mk_terms_ptr), _vp(mk_slot_ptr), _vp(slot_w_ptr),
+                                             _vp(slot_loose_ptr), _vp(sq_ptr_ptr), _vp(sq_off_ptr), _vp(sq_slots_ptr),
+                                             C.c_int32(window), C.c_int32(marks_cap), _vp(win_ptr), _vp(score_ptr),
+                                             _vp(slots_ptr), _vp(marks_ptr), _vp(status_ptr), _vp(stream)),
+               "amdr_bm25_marks_device")
+
+    def marks_kernel_ms(self) -> float:
+        """Device time of the kernel of the last marks() call, in ms; -1.0 when there is none."""
+        ms = C.c_double(0.0)
+        _check(load().amdr_bm25_marks_kernel_ms(self._h, C.byref(ms)), "amdr_bm25_marks_kernel_ms")
+        return float(ms.value)
 
     def get_scores(self, queries: Sequence[Sequence[int]]) -> np.ndarray:
         q_terms, q_ptr = self.pack_queries(queries)

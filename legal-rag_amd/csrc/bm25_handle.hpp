@@ -1,6 +1,7 @@
 // The BM25 handle, shared by bm25.hip (create, plan, score, search, destroy), bm25_update.hip (add, remove, info, read, the
 // token stream) and the list resolvers of list_step.hpp: term_scope.hip (term constraints), phrase_scope.hip (phrases,
-// Nears), union_lists.hip (unions of posting lists) and class_span.hip (class spans).  The per-call plumbing of the updates
+// Nears), union_lists.hip (unions of posting lists) and class_span.hip (class spans), and marks.hip (marks and best passages
+// of the hit documents).  The per-call plumbing of the updates
 // (dev_alloc, CallScratch, KernelSpans, AMDR_TRY) is call_scratch.hpp's, shared with the other two channels.
 #pragma once
 #include "call_scratch.hpp"
@@ -75,6 +76,7 @@ struct amdr_bm25 {
   double remove_kernel_ms = -1;  // summed event time of the last remove's passes (amdr_bm25_remove_kernel_ms)
   double replace_kernel_ms = -1;  // summed event time of the last replace's passes (amdr_bm25_replace_kernel_ms)
   double carry_kernel_ms = -1;    // summed event time of the last carrying update's carry passes (amdr_bm25_carry_kernel_ms)
+  double marks_kernel_ms = -1;    // event time of the kernel of the last amdr_bm25_marks (amdr_bm25_marks_kernel_ms)
   hipStream_t stream = nullptr;
   std::mutex mu;
   // part[0]: "_device" calls, part[1]: host-pointer calls (see dense.hip)

@@ -39,6 +39,8 @@ from .colbert_retriever import ColBERTRetriever
 from .dense_retriever import DenseRetriever
 from .diversity import Diversity, resolve as _resolve_diversity
 from .graph_retriever import GraphRetriever
+from .highlight import Highlight, HitHighlight, build as _build_highlight, pack_tables as _pack_slot_tables
+from .highlight import slot_table as _slot_table
 from .rerankers import RerankerFactory, _to_doc_text
 from .scope import Scope, resolver_for
 from .terms import Near, NearOf, Phrase, PhraseOf, Prefix, Terms, pack as _pack_terms  # noqa: F401 (NearOf, PhraseOf: re-exported)
@@ -312,6 +314,80 @@ class HybridRetriever:
             raise ValueError(f"prefix(): {text_!r} holds {len(toks)} tokens; a stem is exactly one")
         return Prefix(toks[0])
 
+    # ------------------------------------------------------------- highlighting
+    def highlight(self, question: str, hits: Sequence[Any], *, terms: Optional[Terms] = None,
+                  spec: Highlight = Highlight()) -> List[Optional[HitHighlight]]:
+        """The one-question form of highlight_batch: one HitHighlight (or None) per hit."""
+        return self.highlight_batch([question], [hits], terms=None if terms is None else [terms], spec=spec)[0]
+
+    def highlight_batch(self, questions: Sequence[str], hits_lists: Sequence[Sequence[Any]],
+                        terms: Optional[Sequence[Optional[Terms]]] = None,
+                        spec: Highlight = Highlight()) -> List[List[Optional[HitHighlight]]]:
+        """Marks and the best passage of every hit (retrieval/highlight.py): for question i and each hit of hits_lists[i]
+        — a RetrievalHit, or anything with a `.chunk` — the tokens of the chunk that the question and terms[i] name and the
+        window of spec.window tokens that holds the most of them, resolved on the GPU from the BM25 index's resident token
+        stream in ONE native call for the batch (amdr_bm25_marks).  A chunk the BM25 index does not hold gets None.  The
+        chunk text is the index's own (after a live replace: the new text).  ValueError on a row-sharded index or a
+        foreign BM25 retriever, as phrase()."""
+        bm = self.bm25
+        if not isinstance(bm, BM25Retriever):
+            raise ValueError("highlight(): highlighting needs this package's own BM25 retriever")
+        if not isinstance(spec, Highlight):
+            raise TypeError(f"highlight(): spec is a Highlight, got {type(spec).__name__}")
+        questions, hits_lists = list(questions), [list(h) for h in hits_lists]
+        if len(hits_lists) != len(questions) or (terms is not None and len(terms) != len(questions)):
+            raise ValueError("highlight_batch(): one hit list (and one Terms or None) per question")
+        bm.load()
+        if getattr(bm, "shard", None) is not None:
+            raise ValueError("highlight(): highlighting does not run on a row-sharded index")
+        bm.ensure_token_stream()
+        model = bm.bm25
+        vocab = model.vocab()
+        held = self.__dict__.get("_highlight_rows")
+        if held is None or held[0] is not bm.chunks or held[1] != (len(bm.chunks), bm.appends):
+            held = self.__dict__["_highlight_rows"] = (bm.chunks, (len(bm.chunks), bm.appends),
+                                                       {c.id: r for r, c in enumerate(bm.chunks)})
+        row_of = held[2]
+        sorted_vocab = None
+        tables = []
+        for i, q in enumerate(questions):
+            t = None if terms is None else terms[i]
+            if t is not None and sorted_vocab is None and (t.has_union or t.has_class_span):
+                sorted_vocab = model.sorted_vocab()
+            tables.append(_slot_table(bm.document_tokens(q) if spec.question else [], t, vocab, model.idf, sorted_vocab or ()))
+        k = max((len(h) for h in hits_lists), default=0)
+        out: List[List[Optional[HitHighlight]]] = [[None] * len(h) for h in hits_lists]
+        if not questions or k == 0:
+            return out
+        docs = np.full((len(questions), k), -1, dtype=np.int64)
+        for i, hits in enumerate(hits_lists):
+            for j, h in enumerate(hits):
+                chunk = getattr(h, "chunk", None)
+                docs[i, j] = row_of.get(getattr(chunk, "id", None), -1)
+        g = bm.gpu_index()
+        win, score, slots, marks, status = g.marks(docs, *_pack_slot_tables(tables), spec.window, spec.marks)
+        lowered = bm.index_tokenizer == "en_regex"
+        cut: Dict[int, Any] = {}
+        for i, hits in enumerate(hits_lists):
+            for j in range(len(hits)):
+                r = int(docs[i, j])
+                if r < 0:
+                    continue
+                if r not in cut:
+                    txt = bm.chunks[r].text
+                    cut[r] = (txt, bm.document_tokens(txt))
+                txt, toks = cut[r]
+                out[i][j] = _build_highlight(tables[i], spec, win[i, j], score[i, j], slots[i, j], marks[i, j], int(status[i, j]),
+                                             txt, toks, lowered, int(model.doc_len[r]))
+        return out
+
+    def _highlight_stage(self, questions: Sequence[str], outs: List[List[RetrievalHit]], terms, spec: Highlight) -> None:
+        """search(highlight=) / search_batch(highlight=): behind every ranking stage, each hit's HitHighlight.as_dict() (or
+        None) at hit.score_breakdown["highlight"]."""
+        for hits, hls in zip(outs, self.highlight_batch(questions, outs, terms=terms, spec=spec)):
+            for h, hl in zip(hits, hls):
+                h.score_breakdown["highlight"] = None if hl is None else hl.as_dict()
+
     def _search_scoped(self, who: str, chunks, scope: Optional[Scope], top_k: int, refusal: Optional[str], device, twin: str,
                        operands, terms: Optional[Terms] = None):
         """The common sequence of the per-channel scoped searches: [(chunk, score)] of the channel's top_k among the rows of
@@ -566,17 +642,22 @@ class HybridRetriever:
 
     # ---------------------------------------------------------- main search
     def search(self, question: str, llm: Any = None, top_k: int = 10, decision: Any = None, *,
-               scope: Optional[Scope] = None, diversity: Any = None, terms: Optional[Terms] = None) -> List[RetrievalHit]:
+               scope: Optional[Scope] = None, diversity: Any = None, terms: Optional[Terms] = None,
+               highlight: Optional[Highlight] = None) -> List[RetrievalHit]:
         """`scope` (retrieval/scope.py): every channel ranks only that part of the corpus and the fusion normalises over
         those lists — the one-question form of search_batch(scopes=).  None: the whole corpus.
         `terms` (retrieval/terms.py): every channel ranks only the chunks whose text holds the required and none of the
         excluded tokens, inside `scope` if both are given — the one-question form of search_batch(terms=).
         `diversity` (retrieval/diversity.py): a Diversity makes MMR selection the last stage, None takes the configured
-        default (cfg.retrieval.diversity_lambda), False switches it off."""
+        default (cfg.retrieval.diversity_lambda), False switches it off.
+        `highlight` (retrieval/highlight.py): a Highlight marks the query's words in every returned hit and picks its best
+        passage, behind every ranking stage; the result is hit.score_breakdown["highlight"].  None: nothing changes."""
+        if highlight is not None and not isinstance(highlight, Highlight):
+            raise TypeError(f"search(highlight=) is a Highlight or None, got {type(highlight).__name__}")
         if scope is not None or (terms is not None and not self._no_terms([terms], "search")):
             return self.search_batch([question], top_k=top_k, llm=llm, decisions=None if decision is None else [decision],
                                      scopes=None if scope is None else [scope], diversity=diversity,
-                                     terms=None if terms is None else [terms])[0]
+                                     terms=None if terms is None else [terms], highlight=highlight)[0]
         rcfg = self.cfg.retrieval
         top_k = max(1, int(top_k))
         mmr = self._diversity(diversity, top_k, "search")
@@ -634,7 +715,10 @@ class HybridRetriever:
             ms(t0, t1), ms(t1, t2), ms(t2, t3), ms(t3, t4), ms(t4, t_graph) if t_graph else 0,
             ms((t_graph or t4), t_rerank) if t_rerank else 0, ms(t_start, t_end),
             int(bool(getattr(rcfg, "enable_graph", False))), int(self.colbert is not None), int(has_gpu))
-        return fused[:top_k]
+        fused = fused[:top_k]
+        if highlight is not None:
+            self._highlight_stage([question], [fused], None, highlight)
+        return fused
 
     # ------------------------------------------------------- diversification
     def _diversity(self, diversity: Any, top_k: int, who: str):
@@ -1166,7 +1250,8 @@ class HybridRetriever:
     def search_batch(self, questions: Sequence[str], top_k: int = 10, llm: Any = None,
                      decisions: Optional[Sequence[Any]] = None, q_emb=None, *,
                      scopes: Optional[Sequence[Optional[Scope]]] = None, diversity: Any = None,
-                     terms: Optional[Sequence[Optional[Terms]]] = None) -> List[List[RetrievalHit]]:
+                     terms: Optional[Sequence[Optional[Terms]]] = None,
+                     highlight: Optional[Highlight] = None) -> List[List[RetrievalHit]]:
         """Throughput form: `search_batch(qs)[i]` == `search(qs[i])` for every stage the configuration enables
         (hybrid_retriever.py:282-384) — one kernel pipeline for the whole batch (dense + BM25 (+ ColBERT) -> fuse
         -> filter), the graph stage per query whose `decisions[i]` asks for it, the rerank stage with the
@@ -1180,7 +1265,10 @@ class HybridRetriever:
         part's scope table (HybridEngine.term_scopes), so every channel ranks only the qualifying chunks; a constraint that
         matches nothing yields [].  ValueError, before any launch, with a graph-mode decision, on a row-sharded index, or
         when the channels do not share one chunk list.
-        `diversity`: as search — MMR selection as the last stage, ONE batched call for all questions."""
+        `diversity`: as search — MMR selection as the last stage, ONE batched call for all questions.
+        `highlight`: as search — behind every ranking stage, ONE native call for the hits of all questions."""
+        if highlight is not None and not isinstance(highlight, Highlight):
+            raise TypeError(f"search_batch(highlight=) is a Highlight or None, got {type(highlight).__name__}")
         rcfg = self.cfg.retrieval
         top_k = max(1, int(top_k))
         questions = list(questions)
@@ -1223,7 +1311,10 @@ class HybridRetriever:
         outs = [_dedup_keep_best(hits) for hits in outs]
         if mmr is not None:
             outs = self._mmr_stage(outs, top_k, *mmr)
-        return [hits[:top_k] for hits in outs]
+        outs = [hits[:top_k] for hits in outs]
+        if highlight is not None:
+            self._highlight_stage(questions, outs, terms, highlight)
+        return outs
 
     def _graph_device_stage(self, parts, questions: Sequence[str], sel: Sequence[int], k: int, seed_n: int, native,
                             lang: Optional[str] = None):
