@@ -1193,6 +1193,51 @@ int amdr_bm25_marks(amdr_bm25_t* bm25, const int64_t* docs, int64_t nq, int64_t 
                     int32_t* out_win, double* out_score, uint32_t* out_slots, int32_t* out_marks, int32_t* out_status);
 int amdr_bm25_marks_kernel_ms(amdr_bm25_t* h, double* ms);
 
+/* ---- facets: a constraint's qualifying rows counted by the values of chunk fields (csrc/facet.hip, csrc/facet_rule.hpp) ----
+ * No reference counterpart (the reference returns hits and counts nothing).  "How many provisions match, and how do they
+ * spread over the statute": the result set is the scope table amdr_term_scope*_device or an upload left on the device.
+ *   scope_ptr i64 [n_cons + 1], rows i64   constraint p's rows are rows[scope_ptr[p] .. scope_ptr[p + 1]), strictly
+ *                                   ascending inside [0, n_rows).
+ *   rows_max                        an upper bound on the longest scope, as the scoped searches take it; rows of a scope
+ *                                   beyond it are not read.
+ *   codes i32 [n_fields, n_rows]    field-major code columns: a value in [0, n_codes[f]) names a value of field f, any other
+ *                                   value (-1 the canonical one) says the row has none.
+ *   n_codes i64 [n_fields]          a HOST array in both forms; 1 <= n_fields <= 8, 0 <= n_codes[f] < 2^31.
+ *   top                             1 .. AMDR_FACET_MAX_TOP.
+ * Per constraint p and field f, R = p's rows:
+ *   out_total i64 [n_cons]                  |R|
+ *   out_missing i64 [n_cons, n_fields]      the rows of R whose code is outside [0, n_codes[f])
+ *   out_distinct i32 [n_cons, n_fields]     the codes with a count > 0
+ *   out_code i32 [n_cons, n_fields, top], out_count i64, the same shape
+ *                                           the first `top` codes with count > 0 by (count descending, code ascending);
+ *                                           slots past `distinct` hold code -1 and count 0.
+ * An empty scope gives total 0, distinct 0 and an all-padding list; n_cons = 0 enqueues nothing.
+ * Work: three launches.  zero: the counters, int32 [n_cons][sum of (n_codes[f] + 1)].  count: grid (n_cons x tiles,
+ * n_fields), tiles = max(1, ceil(min(rows_max, n_rows) / AMDR_FACET_TILE_ROWS)); a block reads its tile's rows once, gathers
+ * their codes and bins them — a field of n_codes <= AMDR_FACET_LDS_BINS in LDS, its non-zero bins then added to the global
+ * counters, a wider field straight in global memory.  select: one block per (constraint, field) sweeps the counters and keeps
+ * the best `top` keys (count, ~code) with the wave selectors of csrc/topk.hpp.  Integer adds: deterministic.
+ * amdr_facet_plan is host-only arithmetic: the bytes of the counters.  amdr_facet_counts_device only enqueues on `stream`,
+ * on the calling thread's current device, and allocates nothing (capturable; the call zeroes its counters itself, so a
+ * captured call may be replayed).  It does not validate the operands' contents — a row outside [0, n_rows) is never
+ * dereferenced and counted nowhere, out_total included — and returns AMDR_EINVAL, enqueueing nothing and leaving the outputs
+ * untouched, for a null array, a negative size, n_rows >= 2^31, n_fields, an n_codes or top out of range, more than 2^24 - 1
+ * cells (n_cons x tiles, or n_cons x n_fields) or work_bytes below the plan.  A batch past 65 535 constraints is one launch:
+ * the constraints stand in the grid's x.  amdr_facet_counts is the host-pointer twin: it validates (AMDR_EINVAL: scope_ptr
+ * not monotone from 0, a scope longer than rows_max, rows not strictly ascending inside [0, n_rows)), stages the operands
+ * in the scope handle's staging buffer, runs on its stream under its mutex and returns the outputs in the host buffers. */
+#define AMDR_FACET_TILE_ROWS 2048
+#define AMDR_FACET_LDS_BINS 4096
+#define AMDR_FACET_MAX_TOP 64
+int amdr_facet_plan(int64_t n_cons, int32_t n_fields, const int64_t* n_codes, int64_t* work_bytes);
+int amdr_facet_counts_device(const int64_t* scope_ptr_dev, const int64_t* rows_dev, int64_t n_cons, int64_t rows_max,
+                             const int32_t* codes_dev, int64_t n_rows, int32_t n_fields, const int64_t* n_codes, int32_t top,
+                             int64_t* out_total_dev, int64_t* out_missing_dev, int32_t* out_distinct_dev,
+                             int32_t* out_code_dev, int64_t* out_count_dev, void* work_dev, int64_t work_bytes, void* stream);
+int amdr_facet_counts(amdr_scope_t* h, const int64_t* scope_ptr, const int64_t* rows, int64_t n_cons, int64_t rows_max,
+                      const int32_t* codes, int64_t n_rows, int32_t n_fields, const int64_t* n_codes, int32_t top,
+                      int64_t* out_total, int64_t* out_missing, int32_t* out_distinct, int32_t* out_code, int64_t* out_count);
+
 /* ---- multi-GPU: merge per-shard top-k after the RCCL all-gather --------
  * No reference counterpart (the reference is single-process).
  * parts: [n_parts, nq, k_in] scores + GLOBAL ids (-1 padding); output

@@ -72,6 +72,8 @@ SIGNATURES = {
     "amdr_class_spans": "PPPPP" + "l" + "PP" + "lll" + "PPP",
     "amdr_bm25_marks_device": "PPlll" + "P" * 8 + "ii" + "P" * 6, "amdr_bm25_marks": "PPlll" + "P" * 8 + "ii" + "P" * 5,
     "amdr_bm25_marks_kernel_ms": "PP",
+    "amdr_facet_plan": "liPP", "amdr_facet_counts_device": "PPll" + "PliPi" + "PPPPP" + "PlP",
+    "amdr_facet_counts": "P" + "PPll" + "PliPi" + "PPPPP",
 }
 EXPORTS = tuple(SIGNATURES)  # every symbol include/amdretrieval.h declares (checked by tests/test_abi.py)
 _KIND = {"P": C.c_void_p, "i": C.c_int32, "l": C.c_int64, "d": C.c_double}
@@ -260,6 +262,32 @@ def class_spans_plan(n_items: int, cand_max: int) -> int:
     out = C.c_int64(0)
     _check(load().amdr_class_spans_plan(C.c_int64(n_items), C.c_int64(cand_max), C.byref(out)), "amdr_class_spans_plan")
     return int(out.value)
+
+
+FACET_TILE_ROWS = 2048  # rows of a scope per block of amdr_facet_counts (AMDR_FACET_TILE_ROWS)
+FACET_LDS_BINS = 4096   # the widest field a block bins in LDS (AMDR_FACET_LDS_BINS)
+FACET_MAX_TOP = 64      # AMDR_FACET_MAX_TOP
+FACET_MAX_FIELDS = 8
+
+
+def facet_plan(n_cons: int, n_codes: Sequence[int]) -> int:
+    """Workspace bytes of facet_counts_device(n_cons constraints, fields of n_codes values each) — host-only arithmetic."""
+    nc = _c(n_codes, np.int64).ravel()
+    out = C.c_int64(0)
+    _check(load().amdr_facet_plan(C.c_int64(n_cons), C.c_int32(nc.size), _p(nc, C.c_int64), C.byref(out)), "amdr_facet_plan")
+    return int(out.value)
+
+
+def facet_counts_device(scope_ptr: int, rows: int, n_cons: int, rows_max: int, codes: int, n_rows: int, n_codes: Sequence[int],
+                        top: int, out_total: int, out_missing: int, out_distinct: int, out_code: int, out_count: int,
+                        work: int, work_bytes: int, stream: int = 0) -> None:
+    """amdr_facet_counts_device: device pointers in, enqueue only, on the current device.  n_codes is a host sequence, one
+    entry per field of the field-major code columns `codes` i32 [n_fields, n_rows]."""
+    nc = _c(n_codes, np.int64).ravel()
+    _check(load().amdr_facet_counts_device(_vp(scope_ptr), _vp(rows), C.c_int64(n_cons), C.c_int64(rows_max), _vp(codes),
+                                           C.c_int64(n_rows), C.c_int32(nc.size), _p(nc, C.c_int64), C.c_int32(top),
+                                           _vp(out_total), _vp(out_missing), _vp(out_distinct), _vp(out_code), _vp(out_count),
+                                           _vp(work), C.c_int64(work_bytes), _vp(stream)), "amdr_facet_counts_device")
 
 
 def maxsim_workspace_plan(n_docs: int, split_image: bool, nq_max: int, k_max: int, nq: int, k: int) -> Tuple[int, int]:
@@ -1477,6 +1505,32 @@ class ScopeWorkspace(_Handle):
                                                C.c_int32(scope_ptr.size - 1), C.c_int32(nq), C.c_int32(k),
                                                _p(scores, C.c_float), _p(ids, C.c_int64)), "amdr_scope_maxsim_search")
         return scores, ids
+
+    def facet_counts(self, scope_ptr, rows, codes, n_codes: Sequence[int], top: int, rows_max: Optional[int] = None):
+        """amdr_facet_counts, the host-pointer twin: (total i64 [n_cons], missing i64 [n_cons, n_fields], distinct i32
+        [n_cons, n_fields], code i32 [n_cons, n_fields, top], count i64 [n_cons, n_fields, top]) of the scope table
+        (scope_ptr i64 [n_cons + 1], rows i64) over the code columns codes i32 [n_fields, n_rows]; n_codes: one entry per
+        field.  rows_max (None: the longest scope) is the bound the call takes."""
+        scope_ptr, rows = _c(scope_ptr, np.int64).ravel(), _c(rows, np.int64).ravel()
+        codes = np.atleast_2d(_c(codes, np.int32))
+        nc = _c(n_codes, np.int64).ravel()
+        n_cons, (n_fields, n_rows) = max(int(scope_ptr.size) - 1, 0), codes.shape
+        if nc.size != n_fields:
+            raise ValueError("facet_counts: one n_codes entry per code column")
+        if rows_max is None:
+            rows_max = int(np.diff(scope_ptr).max()) if n_cons else 0
+        t = max(int(top), 0)
+        total = np.empty(n_cons, dtype=np.int64)
+        missing = np.empty((n_cons, n_fields), dtype=np.int64)
+        distinct = np.empty((n_cons, n_fields), dtype=np.int32)
+        code = np.empty((n_cons, n_fields, t), dtype=np.int32)
+        count = np.empty((n_cons, n_fields, t), dtype=np.int64)
+        _check(load().amdr_facet_counts(self._h, _p(scope_ptr, C.c_int64), _p(rows, C.c_int64), C.c_int64(n_cons),
+                                        C.c_int64(rows_max), _p(codes, C.c_int32), C.c_int64(n_rows), C.c_int32(n_fields),
+                                        _p(nc, C.c_int64), C.c_int32(top), _p(total, C.c_int64), _p(missing, C.c_int64),
+                                        _p(distinct, C.c_int32), _p(code, C.c_int32), _p(count, C.c_int64)),
+               "amdr_facet_counts")
+        return total, missing, distinct, code, count
 
     # -- "_device" forms: pointers in, enqueue only; table = (scope_ptr, rows, qscope, n_scopes, rows_max) ----------
     def dense_search_device(self, dense: "DenseIndex", q_ptr: int, table, nq: int, k: int, scores_ptr: int, ids_ptr: int,

@@ -329,6 +329,68 @@ class HybridEngine:
         return ((out[:o_rows].view(torch.int64), out[o_rows:o_status].view(torch.int64), dev[q0:q0 + qn].view(torch.int32),
                  n_cons, cand_max), out[o_status:o_status + 4 * (n_cons + n_x)].view(torch.int32))
 
+    def check_facets(self) -> None:
+        """ValueError unless facet_counts() can run on this engine; launches nothing."""
+        if self.shard_offset is not None:
+            raise ValueError("facet counts do not run on a row-sharded engine (base rows and the table are global)")
+
+    def _facet_columns(self, columns: np.ndarray) -> torch.Tensor:
+        """The code columns i32 [n_fields, n_rows] on the device: uploaded once per array object (ScopeResolver.code_columns
+        hands out one array per resolver and field tuple, read-only) and kept resident with it."""
+        held = self._bufs.setdefault(("fcol",), {})
+        ent = held.get(id(columns))
+        if ent is None or ent[0] is not columns:
+            if len(held) >= 8:  # (resolvers of chunk lists that live updates have replaced)
+                held.clear()
+            # (a writable host copy: torch does not wrap a read-only array)
+            ent = held[id(columns)] = (columns, torch.from_numpy(np.array(columns, dtype=np.int32, order="C")).to(self.tdev))
+        return ent[1]
+
+    def facet_counts(self, table, columns, n_codes, top: int):
+        """Facet counts of a scope table on the device (amdr_facet_counts_device; the rule is in include/amdretrieval.h).
+        table: the 5-tuple term_scopes or upload_scopes returned — every constraint of it is counted.  columns: the code
+        columns, numpy i32 [n_fields, n_rows] (kept resident, uploaded once per array) or a device tensor of that shape;
+        n_codes: the fields' value counts.  The call is enqueued on the current stream behind whatever wrote the table,
+        without a host synchronise, and its outputs ride ONE copy into pinned memory enqueued behind it.  Returns fetch():
+        it waits for that copy and returns (total i64 [n_cons], missing i64 [n_cons, F], distinct i32 [n_cons, F], code i32
+        [n_cons, F, top], count i64 [n_cons, F, top]) as numpy arrays of the caller's own.  The outputs are this engine's
+        buffers: they hold until the next facet_counts call."""
+        self.check_facets()
+        sp, rw, _, n_cons, rows_max = table
+        n_cons, top = int(n_cons), int(top)
+        cols = columns if torch.is_tensor(columns) else self._facet_columns(columns)
+        assert cols.is_cuda and cols.dtype == torch.int32 and cols.dim() == 2 and cols.is_contiguous()
+        n_fields, n_rows = int(cols.shape[0]), int(cols.shape[1])
+        n_codes = [int(x) for x in n_codes]
+        if len(n_codes) != n_fields:
+            raise ValueError("facet_counts: one n_codes entry per code column")
+        cf = n_cons * n_fields
+        # i64 first: total [n_cons] | missing [cf] | count [cf, top]; then i32: distinct [cf] | code [cf, top]
+        o_missing, o_count = 8 * n_cons, 8 * (n_cons + cf)
+        o_distinct = o_count + 8 * cf * top
+        o_code, nbytes = o_distinct + 4 * cf, o_distinct + 4 * cf + 4 * cf * top
+        out = self._grown("fco", nbytes + 8)
+        work_bytes = _native.facet_plan(n_cons, n_codes)
+        work = self._grown("fcw", work_bytes + 8)
+        base = out.data_ptr()
+        with torch.cuda.device(self.tdev):
+            _native.facet_counts_device(sp.data_ptr(), rw.data_ptr(), n_cons, int(rows_max), cols.data_ptr(), n_rows, n_codes,
+                                        top, base, base + o_missing, base + o_distinct, base + o_code, base + o_count,
+                                        work.data_ptr(), work_bytes, _stream())
+        host = self._pinned("fcoh", max(nbytes, 8))
+        host[:nbytes].copy_(out[:nbytes], non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(self.tdev))
+
+        def fetch():
+            ev.synchronize()
+            h = host.numpy()
+            return (h[:o_missing].view(np.int64).copy(), h[o_missing:o_count].view(np.int64).reshape(n_cons, n_fields).copy(),
+                    h[o_distinct:o_code].view(np.int32).reshape(n_cons, n_fields).copy(),
+                    h[o_code:nbytes].view(np.int32).reshape(n_cons, n_fields, top).copy(),
+                    h[o_count:o_distinct].view(np.int64).reshape(n_cons, n_fields, top).copy())
+        return fetch
+
     def upload_text(self, ptrs, lens, total: int):
         """Query texts (UTF-8 pointer / length arrays, _native.utf8_views) -> (blob u8 [total], offs i64 [n + 1]) on the
         device: packed straight into pinned staging (amdr_tokenizer_pack: offsets first, then the bytes) and sent up

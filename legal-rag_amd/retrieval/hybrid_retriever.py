@@ -38,6 +38,7 @@ from .bm25_retriever import BM25Retriever
 from .colbert_retriever import ColBERTRetriever
 from .dense_retriever import DenseRetriever
 from .diversity import Diversity, resolve as _resolve_diversity
+from .facets import FacetCounts, Facets, build as _build_facets
 from .graph_retriever import GraphRetriever
 from .highlight import Highlight, HitHighlight, build as _build_highlight, pack_tables as _pack_slot_tables
 from .highlight import slot_table as _slot_table
@@ -313,6 +314,96 @@ class HybridRetriever:
         if len(toks) != 1:
             raise ValueError(f"prefix(): {text_!r} holds {len(toks)} tokens; a stem is exactly one")
         return Prefix(toks[0])
+
+    # ------------------------------------------------------------------ facets
+    def _facet_engine(self, bm):
+        """The engine of the facet calls: the BM25 index alone (the constraints are resolved on its postings, the table and
+        the code columns are rows of its chunk list).  Made again when the index is reloaded or updated in place."""
+        from .engine import HybridEngine
+        gpu = bm.gpu_index()
+        key = (id(gpu), id(bm.bm25), getattr(bm, "appends", 0))
+        held = self.__dict__.get("_facet_eng")
+        if held is None or held[0] != key:
+            held = self.__dict__["_facet_eng"] = (key, HybridEngine(None, gpu, None,
+                                                                    device=int(getattr(self.cfg.retrieval, "device", 0))))
+        return held[1]
+
+    def facets_batch(self, *, terms: Optional[Sequence[Optional[Terms]]] = None, scopes: Optional[Sequence[Optional[Scope]]] = None,
+                     spec: Facets = Facets(), _who: str = "facets_batch") -> List[FacetCounts]:
+        """One FacetCounts per (scope, terms) pair: how many chunks of the BM25 index's chunk list lie in scopes[i] (None:
+        all) and satisfy terms[i] (None: no constraint), and how they spread over the fields of `spec`.  The constraints are
+        resolved on the GPU (HybridEngine.term_scopes; without any `terms` the scopes' own rows are uploaded), counted there
+        (HybridEngine.facet_counts) and only the counts come back; equal pairs of a batch are resolved once.  With `terms`
+        the preconditions and errors are those of search_*(terms=): this package's own BM25 retriever on an unsharded index
+        (ValueError before any launch), RuntimeError for a non-zero status word."""
+        if not isinstance(spec, Facets):
+            raise TypeError(f"{_who}: spec must be a Facets, got {type(spec).__name__}")
+        if terms is None and scopes is None:
+            raise ValueError(f"{_who}: give terms, scopes or both (one entry per pair)")
+        n = len(terms) if terms is not None else len(scopes)
+        if scopes is not None and len(scopes) != n:
+            raise ValueError(f"{_who}: scopes must have one entry per pair")
+        for i, s in enumerate(scopes if scopes is not None else ()):
+            if s is not None and not isinstance(s, Scope):
+                raise TypeError(f"{_who}: scopes[{i}] is not a Scope")
+        no_terms = self._no_terms(terms, _who)
+        bm = self.bm25
+        if not isinstance(bm, BM25Retriever):
+            raise ValueError(f"{_who}(terms=): term constraints need this package's own BM25 retriever")
+        bm.load()
+        if getattr(bm, "shard", None) is not None:
+            raise ValueError(f"{_who}(terms=): term constraints do not run on a row-sharded index")
+        if n == 0:
+            return []
+        resolver = resolver_for(bm.chunks)
+        cols, values = resolver.code_columns(spec.by)
+        pairs = [(scopes[i] if scopes is not None else None, (terms[i] if terms is not None else None) or Terms())
+                 for i in range(n)]
+        tt = None
+        if no_terms:
+            sp, rows, qscope, _ = resolver.table([s if s is not None else Scope() for s, _ in pairs])
+        else:
+            model = bm.bm25
+            tt = _pack_terms(pairs, model.vocab(), model._doc_frequencies(), int(model.corpus_size), resolver.rows,
+                             model.sorted_vocab() if any(t.has_union or t.has_class_span for _, t in pairs) else None)
+            if tt.n_phr or tt.n_near or tt.n_cspan:
+                bm.ensure_token_stream()
+            qscope = np.asarray(tt.qscope)
+        import torch
+        with self._stage().lock:
+            eng = self._facet_engine(bm)
+            eng.check_facets()
+            with torch.cuda.device(eng.tdev):
+                if tt is None:
+                    table, pin = eng.upload_scopes(sp, rows, qscope, channel=1), None
+                else:
+                    table, st = eng.term_scopes(tt)
+                    pin = eng._pinned("fcst", 4 * max(int(st.numel()), 1))[:4 * int(st.numel())]
+                    pin.copy_(st.view(torch.uint8), non_blocking=True)
+                got = eng.facet_counts(table, cols, [len(v) for v in values], spec.top)()
+            if pin is not None:  # (fetch has waited for an event recorded behind the copy)
+                status = pin.numpy().view(np.int32)
+                if status.any():
+                    i = int(np.flatnonzero(status)[0])
+                    what = "the term constraint" if i < int(tt.n_cons) else f"{tt.list_item(i - int(tt.n_cons))!r}"
+                    raise RuntimeError(f"{_who}(terms=): {what} overflowed its bound (status {int(status[i])}); the "
+                                       f"host model and the resident BM25 index disagree")
+        per_cons = _build_facets(spec, values, *got)
+        return [per_cons[int(j)] for j in qscope]
+
+    def facets(self, *, terms: Optional[Terms] = None, scope: Optional[Scope] = None, spec: Facets = Facets()) -> FacetCounts:
+        """The one-pair form of facets_batch."""
+        return self.facets_batch(terms=[terms], scopes=[scope], spec=spec, _who="facets")[0]
+
+    def count_batch(self, *, terms: Optional[Sequence[Optional[Terms]]] = None,
+                    scopes: Optional[Sequence[Optional[Scope]]] = None) -> List[int]:
+        """How many chunks each (scope, terms) pair matches: the totals of facets_batch."""
+        return [f.total for f in self.facets_batch(terms=terms, scopes=scopes, spec=Facets(by=("law_name",), top=1),
+                                                   _who="count_batch")]
+
+    def count(self, *, terms: Optional[Terms] = None, scope: Optional[Scope] = None) -> int:
+        """How many chunks lie in `scope` (None: all) and satisfy `terms` (None: no constraint)."""
+        return self.facets_batch(terms=[terms], scopes=[scope], spec=Facets(by=("law_name",), top=1), _who="count")[0].total
 
     # ------------------------------------------------------------- highlighting
     def highlight(self, question: str, hits: Sequence[Any], *, terms: Optional[Terms] = None,

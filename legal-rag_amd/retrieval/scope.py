@@ -15,6 +15,7 @@ from typing import Any, Dict, Iterable, List, Optional, Sequence, Tuple
 import numpy as np
 
 _FIELDS = ("law_name", "chapter", "section")
+FACET_FIELDS = _FIELDS + ("article_id",)  # the fields ScopeResolver.codes() numbers (retrieval/facets.py)
 
 
 def _as_set(x) -> Optional[frozenset]:
@@ -58,6 +59,40 @@ class ScopeResolver:
                 if v is not None:
                     index.setdefault(str(v), []).append(row)
         self._cache: Dict[Scope, np.ndarray] = {}
+        self._codes: Dict[Any, Tuple[np.ndarray, Any]] = {}  # field -> codes(); ("columns", fields...) -> code_columns()
+
+    def codes(self, field: str) -> Tuple[np.ndarray, List[str]]:
+        """(codes i32 [n], values) of a facet field (FACET_FIELDS): row r's value is values[codes[r]], -1 where the chunk's
+        field is None.  A value's code is its order of first appearance by row, so "code ascending" is "first in the
+        statute".  Cached beside the row cache for the resolver's lifetime; the array is read-only."""
+        got = self._codes.get(field)
+        if got is not None:
+            return got
+        if field not in FACET_FIELDS:
+            raise ValueError(f"codes(): {field!r} is not a facet field (one of {', '.join(FACET_FIELDS)})")
+        index = self._by[field]
+        firsts = sorted((rows[0], v) for v, rows in index.items())  # (dict order is first appearance already; said outright)
+        codes = np.full(self.n, -1, dtype=np.int32)
+        values: List[str] = []
+        for c, (_, v) in enumerate(firsts):
+            codes[np.asarray(index[v], dtype=np.int64)] = c
+            values.append(v)
+        codes.setflags(write=False)
+        got = self._codes[field] = (codes, values)
+        return got
+
+    def code_columns(self, fields: Sequence[str]) -> Tuple[np.ndarray, List[List[str]]]:
+        """(codes i32 [len(fields), n] field-major, the fields' value lists): the operand of the facet kernel
+        (csrc/facet.hip).  One read-only array per tuple of fields, cached with the resolver, so that a device copy made of
+        it can be kept as long."""
+        key = ("columns",) + tuple(fields)
+        got = self._codes.get(key)
+        if got is None:
+            per = [self.codes(f) for f in fields]
+            cols = np.ascontiguousarray(np.stack([c for c, _ in per]), dtype=np.int32).reshape(len(per), self.n)
+            cols.setflags(write=False)
+            got = self._codes[key] = (cols, [v for _, v in per])
+        return got
 
     def _rows_of(self, field: str, values: Iterable[str]) -> np.ndarray:
         index = self._by[field]
