@@ -57,6 +57,7 @@ typedef struct amdr_tokenizer amdr_tokenizer_t;
 typedef struct amdr_tokenizer_device amdr_tokenizer_device_t;
 typedef struct amdr_graph amdr_graph_t;
 typedef struct amdr_scope amdr_scope_t;
+typedef struct amdr_vocab amdr_vocab_t;
 
 /* ---- library ---------------------------------------------------------- */
 const char* amdr_last_error(void);
@@ -1237,6 +1238,59 @@ int amdr_facet_counts_device(const int64_t* scope_ptr_dev, const int64_t* rows_d
 int amdr_facet_counts(amdr_scope_t* h, const int64_t* scope_ptr, const int64_t* rows, int64_t n_cons, int64_t rows_max,
                       const int32_t* codes, int64_t n_rows, int32_t n_fields, const int64_t* n_codes, int32_t top,
                       int64_t* out_total, int64_t* out_missing, int32_t* out_distinct, int32_t* out_code, int64_t* out_count);
+
+/* ---- vocabulary patterns: Wildcard and Fuzzy resolved into term ids (csrc/vocab_match.hip, csrc/vocab_match_rule.hpp) ----
+ * No reference counterpart: the reference looks a query token up exactly (legalrag/retrieval/bm25_retriever.py:74-75) and
+ * has no pattern of any kind.  These calls stand beside retrieval/terms.py prefix_tokens, the host expansion of a Prefix: a
+ * prefix is a contiguous range of the sorted vocabulary and is found by bisection; a wildcard or an edit-distance pattern
+ * has no such range and replaces a Python loop over every token per pattern with one scan on the device.
+ * amdr_vocab_t is a resident copy of the vocabulary as amdr_tokenizer_create takes it: a UTF-8 blob and offsets
+ * i64 [n_terms + 1], term i the token with id i, plus the code-point count of every term, computed once at create.
+ * amdr_vocab_create validates (AMDR_EINVAL: a null array, n_terms outside [0, 2^31), offsets that do not ascend from 0, a
+ * term that is not well-formed UTF-8) and copies; the handle is small, separate from the tokeniser's and owns a stream and
+ * a staging buffer for the host-pointer twin.  amdr_vocab_info: out2 = {n_terms, bytes of the blob}.
+ *   pat_cp u32 [cp_total]            the patterns' code points back to back; in a Wildcard 0x110000 is '?' (exactly one
+ *                                    code point) and 0x110001 is '*' (any run, the empty one included): two values above
+ *                                    U+10FFFF, so a literal question mark in a TERM is an ordinary code point.
+ *   pat_ptr i64 [n_pat + 1]          pattern p is pat_cp[pat_ptr[p] .. pat_ptr[p + 1]), 1 .. AMDR_VOCAB_MAX_PATTERN values.
+ *   pat_kind i32 [n_pat], pat_arg    0 Wildcard (arg 0, at least one literal), 1 Fuzzy (arg = edits, 1 or 2: the
+ *                                    optimal-string-alignment distance over code points, transpositions of two adjacent
+ *                                    code points included, distance 0 included).
+ *   item_cap                         1 .. AMDR_VOCAB_MAX_ITEMS: the stride of the outputs.
+ *   ids i32 [n_pat, item_cap]        the first item_cap term ids pattern p names, ascending, then -1.
+ *   dist u8 [n_pat, item_cap]        their distances (0 for a Wildcard), then 255.
+ *   n_match i64 [n_pat]              the TRUE number of terms named, which may exceed item_cap.
+ * The stride is fixed because nobody can bound a pattern's matches without running it: an over-wide pattern truncates its
+ * own row and no neighbour's.  A term of zero bytes is named by nothing.
+ * Work: three launches.  count: a one-dimensional grid of n_pat x tiles blocks, tiles = max(1, ceil(n_terms /
+ * AMDR_VOCAB_TILE_TERMS)); a block stages its pattern in LDS, its threads stride over the tile's terms (length pre-test on
+ * code-point counts, then the rule) and set bits of an LDS bitmap, which is counted and parked in the workspace.  scan:
+ * the cells' offsets.  write: the parked bits expanded, ascending, into the pattern's row; the distance is computed again
+ * for the kept terms only; the block of tile 0 writes n_match and pads the row.  No global atomics, nothing to clear.
+ * amdr_vocab_match_plan is host-only arithmetic: per cell two i64 and the 1 KiB bitmap, each region aligned to 256 bytes.
+ * amdr_vocab_match_device only enqueues on `stream`, on the calling thread's current device, and allocates nothing
+ * (capturable; a captured call may be replayed over rewritten patterns).  It cannot validate the patterns' contents and is
+ * safe for any: a span outside [0, cp_total) or of a length outside 1 .. 64, a kind or an argument out of range, a value
+ * that is no code point (a reserved one in a Fuzzy included) or a Wildcard without a literal names nothing, n_match 0, and
+ * nothing is read or written out of bounds.  It returns AMDR_EINVAL, enqueueing nothing and leaving the outputs untouched,
+ * for a null handle or array, a negative size, item_cap out of range, more than 2^24 - 1 cells, work_bytes below the
+ * plan or a workspace that is not aligned to 8 bytes (its int64 counts).  The current device must be the handle's: as in
+ * the other "_device" calls, that is the caller's to see to.  A batch past 65 535 patterns is one launch.  amdr_vocab_match is the host-pointer twin: it validates the patterns
+ * (AMDR_EINVAL: pat_ptr not monotone from 0 to cp_total, a length, kind, argument or value out of range, a Wildcard
+ * without a literal), stages in the handle's buffer, runs on its stream under its mutex and returns the outputs. */
+#define AMDR_VOCAB_TILE_TERMS 8192
+#define AMDR_VOCAB_MAX_PATTERN 64
+#define AMDR_VOCAB_MAX_ITEMS 4096
+int amdr_vocab_create(const char* blob, const int64_t* offsets, int64_t n_terms, int32_t device, amdr_vocab_t** out);
+int amdr_vocab_destroy(amdr_vocab_t* h);
+int amdr_vocab_info(amdr_vocab_t* h, int64_t* out2);
+int amdr_vocab_match_plan(int64_t n_terms, int64_t n_pat, int64_t* work_bytes);
+int amdr_vocab_match_device(amdr_vocab_t* h, const uint32_t* pat_cp_dev, const int64_t* pat_ptr_dev, const int32_t* pat_kind_dev,
+                            const int32_t* pat_arg_dev, int64_t n_pat, int64_t cp_total, int32_t item_cap, int32_t* ids_dev,
+                            uint8_t* dist_dev, int64_t* n_match_dev, void* work_dev, int64_t work_bytes, void* stream);
+int amdr_vocab_match(amdr_vocab_t* h, const uint32_t* pat_cp, const int64_t* pat_ptr, const int32_t* pat_kind,
+                     const int32_t* pat_arg, int64_t n_pat, int64_t cp_total, int32_t item_cap, int32_t* out_ids,
+                     uint8_t* out_dist, int64_t* out_n_match);
 
 /* ---- multi-GPU: merge per-shard top-k after the RCCL all-gather --------
  * No reference counterpart (the reference is single-process).

@@ -74,6 +74,8 @@ SIGNATURES = {
     "amdr_bm25_marks_kernel_ms": "PP",
     "amdr_facet_plan": "liPP", "amdr_facet_counts_device": "PPll" + "PliPi" + "PPPPP" + "PlP",
     "amdr_facet_counts": "P" + "PPll" + "PliPi" + "PPPPP",
+    "amdr_vocab_create": "PPliP", "amdr_vocab_destroy": "P", "amdr_vocab_info": "PP", "amdr_vocab_match_plan": "llP",
+    "amdr_vocab_match_device": "PPPPP" + "lli" + "PPP" + "PlP", "amdr_vocab_match": "PPPPP" + "lli" + "PPP",
 }
 EXPORTS = tuple(SIGNATURES)  # every symbol include/amdretrieval.h declares (checked by tests/test_abi.py)
 _KIND = {"P": C.c_void_p, "i": C.c_int32, "l": C.c_int64, "d": C.c_double}
@@ -288,6 +290,21 @@ def facet_counts_device(scope_ptr: int, rows: int, n_cons: int, rows_max: int, c
                                            C.c_int64(n_rows), C.c_int32(nc.size), _p(nc, C.c_int64), C.c_int32(top),
                                            _vp(out_total), _vp(out_missing), _vp(out_distinct), _vp(out_code), _vp(out_count),
                                            _vp(work), C.c_int64(work_bytes), _vp(stream)), "amdr_facet_counts_device")
+
+
+VOCAB_TILE_TERMS = 8192   # term ids per tile of amdr_vocab_match (AMDR_VOCAB_TILE_TERMS, kVmTile)
+VOCAB_MAX_PATTERN = 64    # code points of a pattern (AMDR_VOCAB_MAX_PATTERN)
+VOCAB_MAX_ITEMS = 4096    # the widest row of matches (AMDR_VOCAB_MAX_ITEMS)
+VOCAB_ANY_ONE = 0x110000  # '?' in a Wildcard's code points
+VOCAB_ANY_RUN = 0x110001  # '*'
+
+
+def vocab_match_plan(n_terms: int, n_pat: int) -> int:
+    """Workspace bytes of VocabIndex.match_device(n_pat patterns) on a vocabulary of n_terms — host-only arithmetic: per
+    cell (pattern, tile of VOCAB_TILE_TERMS terms) two i64 and the 1 KiB bitmap, each region aligned to 256 bytes."""
+    out = C.c_int64(0)
+    _check(load().amdr_vocab_match_plan(C.c_int64(n_terms), C.c_int64(n_pat), C.byref(out)), "amdr_vocab_match_plan")
+    return int(out.value)
 
 
 def maxsim_workspace_plan(n_docs: int, split_image: bool, nq_max: int, k_max: int, nq: int, k: int) -> Tuple[int, int]:
@@ -1102,6 +1119,64 @@ class Tokenizer(_Handle):
         if n.value < 0:
             return None
         return [b[int(a):int(e)].decode("utf-8") for a, e in zip(st[: n.value], en[: n.value])]
+
+
+class VocabIndex(_Handle):
+    """A resident copy of a vocabulary (token i is term id i) that Wildcard and Fuzzy patterns are matched against on the
+    device (amdr_vocab_*, csrc/vocab_match.hip).  Patterns cross as code points: pack_patterns."""
+    _destroy = "amdr_vocab_destroy"
+
+    def __init__(self, vocab: Sequence[str], *, device: int = 0):
+        enc = [w.encode("utf-8") for w in vocab]
+        blob = b"".join(enc)
+        offs = np.zeros(len(enc) + 1, dtype=np.int64)
+        np.cumsum([len(e) for e in enc], out=offs[1:])
+        self._h = C.c_void_p()
+        self.device = int(device)
+        self.n_terms = len(enc)
+        _check(load().amdr_vocab_create(C.c_char_p(blob), _p(offs, C.c_int64), C.c_int64(len(enc)), C.c_int32(device),
+                                        C.byref(self._h)), "amdr_vocab_create")
+
+    def info(self) -> Tuple[int, int]:
+        """(n_terms, bytes of the blob)."""
+        out = (C.c_int64 * 2)()
+        _check(load().amdr_vocab_info(self._h, out), "amdr_vocab_info")
+        return int(out[0]), int(out[1])
+
+    @staticmethod
+    def pack_patterns(patterns: Sequence[Tuple[int, int, Sequence[int]]]):
+        """(pat_cp u32, pat_ptr i64 [n + 1], pat_kind i32, pat_arg i32) of (kind, arg, code points) triples."""
+        ptr = np.zeros(len(patterns) + 1, dtype=np.int64)
+        np.cumsum([len(p[2]) for p in patterns], out=ptr[1:])
+        cp = np.fromiter((c for p in patterns for c in p[2]), dtype=np.uint32, count=int(ptr[-1]))
+        return (cp, ptr, np.asarray([p[0] for p in patterns], dtype=np.int32), np.asarray([p[1] for p in patterns], dtype=np.int32))
+
+    def match(self, pat_cp, pat_ptr, pat_kind, pat_arg, item_cap: int):
+        """The host twin: (ids i32 [n, item_cap], dist u8 [n, item_cap], n_match i64 [n]) — per pattern the first item_cap
+        term ids it names, ascending, then -1; their distances, then 255; the true count."""
+        cp, ptr = _c(pat_cp, np.uint32).ravel(), _c(pat_ptr, np.int64).ravel()
+        kind, arg = _c(pat_kind, np.int32).ravel(), _c(pat_arg, np.int32).ravel()
+        if ptr.size < 1 or kind.size != ptr.size - 1 or arg.size != kind.size:
+            raise ValueError("match: pat_ptr [n + 1], pat_kind [n], pat_arg [n]")
+        n = ptr.size - 1
+        rows = max(n, 1) * max(int(item_cap), 1)
+        ids, dist = np.full(rows, -2, dtype=np.int32), np.full(rows, 254, dtype=np.uint8)
+        n_match = np.zeros(max(n, 1), dtype=np.int64)
+        pad = lambda a, dt: a if a.size else np.zeros(1, dtype=dt)  # noqa: E731
+        _check(load().amdr_vocab_match(self._h, _p(pad(cp, np.uint32), C.c_uint32), _p(ptr, C.c_int64),
+                                       _p(pad(kind, np.int32), C.c_int32), _p(pad(arg, np.int32), C.c_int32), C.c_int64(n),
+                                       C.c_int64(cp.size), C.c_int32(item_cap), _p(ids, C.c_int32), _p(dist, C.c_uint8),
+                                       _p(n_match, C.c_int64)), "amdr_vocab_match")
+        return ids[:n * int(item_cap)].reshape(n, int(item_cap)), dist[:n * int(item_cap)].reshape(n, int(item_cap)), n_match[:n]
+
+    def match_device(self, pat_cp_ptr: int, pat_ptr_ptr: int, pat_kind_ptr: int, pat_arg_ptr: int, n_pat: int, cp_total: int,
+                     item_cap: int, ids_ptr: int, dist_ptr: int, n_match_ptr: int, work_ptr: int, work_bytes: int,
+                     stream: int = 0) -> None:
+        """The "_device" form: operands and outputs as device pointers; enqueues only, on the current device."""
+        _check(load().amdr_vocab_match_device(self._h, _vp(pat_cp_ptr), _vp(pat_ptr_ptr), _vp(pat_kind_ptr), _vp(pat_arg_ptr),
+                                              C.c_int64(n_pat), C.c_int64(cp_total), C.c_int32(item_cap), _vp(ids_ptr),
+                                              _vp(dist_ptr), _vp(n_match_ptr), _vp(work_ptr), C.c_int64(work_bytes),
+                                              _vp(stream)), "amdr_vocab_match_device")
 
 
 def utf8_views(texts: Sequence[Optional[str]]):

@@ -225,6 +225,20 @@ class BM25Retriever:
         self.load()
         return self.bm25.gpu(self.device_index, rows=self.shard.bounds(self.bm25.corpus_size) if self.shard else None)
 
+    def vocab_matcher(self):
+        """The VocabMatcher (retrieval/vocab_match.py) over the live model's vocabulary, resident on this retriever's
+        device: what a Wildcard or a Fuzzy is matched against.  Cached, and made again under the validity rule of
+        BM25Okapi.sorted_vocab(): the same vocab() object AND the same length — add_documents extends the vocabulary in
+        place, a removal or a replacement makes a new one.  The matcher lays the tokens out by term id.  Two threads that
+        both find the cache stale each make a matcher and the later one is kept: a handle is wasted, nothing is wrong."""
+        from .vocab_match import VocabMatcher
+        self.load()
+        v = self.bm25.vocab()
+        held = self.__dict__.get("_vocab_matcher")
+        if held is None or held[0] is not v or held[1] != len(v) or held[2].device != self.device_index:
+            held = self.__dict__["_vocab_matcher"] = (v, len(v), VocabMatcher(v, device=self.device_index))
+        return held[2]
+
     def document_tokens(self, s: str) -> List[str]:
         """A string cut as the index cut its documents (builders/bm25_builder.tokenize_corpus): the English regex rule on
         lower-cased text for an index recorded as "en_regex", else text.jieba_cut in the configured mode — when that is

@@ -10,8 +10,8 @@ Slots.  A slot is one query word, at most 32 per question:
   * the items of terms.all_of / any_of come first (none_of is never marked), then the question's tokens (question=True),
     cut with the DOCUMENT-side tokeniser so that "Security" marks "security"; a question token without a letter or a digit
     (the blanks and the punctuation a segmenter cuts as tokens of their own) is no query word;
-  * a plain token, a Prefix (every vocabulary token with the stem) and a OneOf are LOOSE slots: they mark their tokens
-    wherever they stand; so are the members of a Near / NearOf;
+  * a plain token, a Prefix (every vocabulary token with the stem), a Wildcard, a Fuzzy and a OneOf are LOOSE slots: they
+    mark their tokens wherever they stand; so are the members of a Near / NearOf;
   * a Phrase / PhraseOf is a SEQUENCE over its members' slots, which are loose only if something else makes them so: its
     members are marked only where the whole phrase stands;
   * a term id that belongs to two slots goes to the lower one; a slot's weight is the model's idf of its token, for a class
@@ -26,7 +26,7 @@ from typing import Any, Dict, List, Mapping, Optional, Sequence, Tuple
 
 import numpy as np
 
-from .terms import Near, NearOf, Phrase, PhraseOf, Prefix, Terms, prefix_tokens
+from .terms import Fuzzy, Near, NearOf, Phrase, PhraseOf, Prefix, Terms, Wildcard, prefix_tokens
 
 MAX_SLOTS = 32      # kMkSlots
 MAX_WINDOW = 4096   # kMkMaxWindow
@@ -106,26 +106,37 @@ def _label(m) -> str:
         return m
     if isinstance(m, Prefix):
         return m.stem + "!"
+    if isinstance(m, Wildcard):
+        return m.pattern
+    if isinstance(m, Fuzzy):
+        return f"{m.token}~{m.edits}"
     return "(" + " ".join(_label(x) for x in m.members) + ")"
 
 
-def _member_ids(m, vocab: Mapping[str, int], sorted_vocab: Sequence[str]) -> List[int]:
-    """The term ids a slot member names: a token, a Prefix's vocabulary tokens, a OneOf's members; [] when unknown."""
+def _member_ids(m, vocab: Mapping[str, int], sorted_vocab: Sequence[str],
+                expansions: Optional[Mapping[Any, Any]] = None) -> List[int]:
+    """The term ids a slot member names: a token, a Prefix's vocabulary tokens, the tokens `expansions` holds for a Wildcard
+    or a Fuzzy (terms.pack: ValueError without an entry), a OneOf's members; [] when unknown."""
     if isinstance(m, str):
         return [vocab[m]] if m in vocab else []
     if isinstance(m, Prefix):
         return [vocab[t] for t in prefix_tokens(m.stem, sorted_vocab)]
+    if isinstance(m, (Wildcard, Fuzzy)):
+        if expansions is None or m not in expansions:
+            raise ValueError(f"{m!r}: no expansion of this pattern was given (expansions=)")
+        return sorted({vocab[w] for w in (e if isinstance(e, str) else e[0] for e in expansions[m]) if w in vocab})
     out: List[int] = []
     for x in m.members:
-        out.extend(_member_ids(x, vocab, sorted_vocab))
+        out.extend(_member_ids(x, vocab, sorted_vocab, expansions))
     return sorted(set(out))
 
 
 def slot_table(question_tokens: Sequence[str], terms: Optional[Terms], vocab: Mapping[str, int], idf,
-               sorted_vocab: Sequence[str]) -> SlotTable:
+               sorted_vocab: Sequence[str], expansions: Optional[Mapping[Any, Any]] = None) -> SlotTable:
     """The slot table of a (question, terms) pair.  question_tokens: the question cut with the document-side tokeniser
     ([] for question=False); vocab: token -> term id; idf: token -> weight, or a sequence indexed by term id;
-    sorted_vocab: the vocabulary ascending (for Prefix)."""
+    sorted_vocab: the vocabulary ascending (for Prefix); expansions: the tokens each Wildcard / Fuzzy names (None: the
+    terms hold no pattern)."""
     words: Optional[List[str]] = None
 
     def weight_of(ids: Sequence[int]) -> float:
@@ -151,7 +162,7 @@ def slot_table(question_tokens: Sequence[str], terms: Optional[Terms], vocab: Ma
         key = m if isinstance(m, str) else repr(m)
         s = by_key.get(key)
         if s is None:
-            ids = _member_ids(m, vocab, sorted_vocab)
+            ids = _member_ids(m, vocab, sorted_vocab, expansions)
             if not ids:
                 miss(_label(m))
                 return None
@@ -165,7 +176,7 @@ def slot_table(question_tokens: Sequence[str], terms: Optional[Terms], vocab: Ma
             for item in group:
                 if isinstance(item, (Phrase, PhraseOf)):
                     members = item.tokens if isinstance(item, Phrase) else item.members
-                    unknown = [m for m in members if not _member_ids(m, vocab, sorted_vocab)]
+                    unknown = [m for m in members if not _member_ids(m, vocab, sorted_vocab, expansions)]
                     if unknown:  # the phrase stands nowhere: none of its members is marked for it
                         for m in unknown:
                             miss(_label(m))

@@ -44,7 +44,8 @@ from .highlight import Highlight, HitHighlight, build as _build_highlight, pack_
 from .highlight import slot_table as _slot_table
 from .rerankers import RerankerFactory, _to_doc_text
 from .scope import Scope, resolver_for
-from .terms import Near, NearOf, Phrase, PhraseOf, Prefix, Terms, pack as _pack_terms  # noqa: F401 (NearOf, PhraseOf: re-exported)
+from .terms import Fuzzy, Near, NearOf, Phrase, PhraseOf, Prefix, Terms, Wildcard, pack as _pack_terms  # noqa: F401 (NearOf, PhraseOf, Wildcard: re-exported)
+from .vocab_match import Suggestion, collect_patterns as _collect_patterns  # noqa: F401 (Suggestion: re-exported)
 
 logger = logging.getLogger("legalrag.retrieval.hybrid_retriever")
 
@@ -237,7 +238,8 @@ class HybridRetriever:
                              f"be a row of the channel)")
         model = bm.bm25
         tt = _pack_terms([(scope, terms)], model.vocab(), model._doc_frequencies(), int(model.corpus_size),
-                         resolver_for(bm.chunks).rows, model.sorted_vocab() if terms.has_union or terms.has_class_span else None)
+                         resolver_for(bm.chunks).rows, model.sorted_vocab() if terms.has_union or terms.has_class_span else None,
+                         self._expansions(bm, [terms]))
         if tt.cand_max == 0:
             return np.zeros(0, dtype=np.int64)
         def check(status, name) -> None:
@@ -282,6 +284,14 @@ class HybridRetriever:
         check(status[:1], None)
         return rows
 
+    @staticmethod
+    def _expansions(bm, terms: Sequence[Optional[Terms]]):
+        """What terms.pack and highlight.slot_table take as `expansions`: the tokens each distinct Wildcard / Fuzzy of these
+        Terms names, resolved on the GPU against the live vocabulary in one native call (BM25Retriever.vocab_matcher); None
+        when they hold no pattern — nothing is launched then."""
+        members = _collect_patterns(terms)
+        return bm.vocab_matcher().expand(members) if members else None
+
     def phrase(self, text_: str) -> Phrase:
         """The Phrase of a string, cut by the BM25 index's DOCUMENT-side tokeniser (an English index lower-cases):
         retriever.phrase("Security Interest") == Phrase("security", "interest").  ValueError for a string without a token,
@@ -314,6 +324,46 @@ class HybridRetriever:
         if len(toks) != 1:
             raise ValueError(f"prefix(): {text_!r} holds {len(toks)} tokens; a stem is exactly one")
         return Prefix(toks[0])
+
+    def fuzzy(self, text_: str, edits: int = 1) -> Fuzzy:
+        """The Fuzzy of a string, cut by the BM25 index's DOCUMENT-side tokeniser as prefix() cuts it:
+        retriever.fuzzy("Warrenty", edits=1) == Fuzzy("warrenty", edits=1).  ValueError unless the string yields exactly
+        one token, or on an index that records no tokeniser.  (There is no wildcard(): a tokeniser would cut at '?'.)"""
+        bm = self.bm25
+        if not isinstance(bm, BM25Retriever):
+            raise ValueError("fuzzy(): vocabulary patterns need this package's own BM25 retriever")
+        toks = bm.document_tokens(text_)
+        if len(toks) != 1:
+            raise ValueError(f"fuzzy(): {text_!r} holds {len(toks)} tokens; a Fuzzy is exactly one")
+        return Fuzzy(toks[0], edits=edits)
+
+    def suggest_batch(self, words: Sequence[str], edits: int = 2, top: int = 5) -> List[tuple]:
+        """"Did you mean": per word a tuple of Suggestion(token, distance, doc_freq) — the vocabulary tokens within `edits`
+        of the word as fuzzy() cuts it, by (distance ascending, document frequency descending, token ascending); the word
+        itself comes first, at distance 0, when the vocabulary holds it.  A word no longer than `edits` takes len(word) - 1
+        edits (one character: only itself), so a short word never fails the batch.  Document frequencies are the host
+        model's; ONE native call serves the batch.  Preconditions as search_*(terms=): this package's own BM25 retriever
+        on an unsharded index (ValueError before any launch)."""
+        bm = self.bm25
+        if not isinstance(bm, BM25Retriever):
+            raise ValueError("suggest(): vocabulary patterns need this package's own BM25 retriever")
+        bm.load()
+        if getattr(bm, "shard", None) is not None:
+            raise ValueError("suggest(): vocabulary patterns do not run on a row-sharded index")
+        words = list(words)
+        if not words:
+            return []
+        cut = []
+        for w in words:
+            toks = bm.document_tokens(w)
+            if len(toks) != 1:
+                raise ValueError(f"suggest(): {w!r} holds {len(toks)} tokens; a word is exactly one")
+            cut.append(toks[0])
+        return list(bm.vocab_matcher().suggest_batch(cut, bm.bm25._doc_frequencies(), edits=edits, top=top))
+
+    def suggest(self, word: str, edits: int = 2, top: int = 5) -> tuple:
+        """The one-word form of suggest_batch."""
+        return self.suggest_batch([word], edits=edits, top=top)[0]
 
     # ------------------------------------------------------------------ facets
     def _facet_engine(self, bm):
@@ -365,7 +415,8 @@ class HybridRetriever:
         else:
             model = bm.bm25
             tt = _pack_terms(pairs, model.vocab(), model._doc_frequencies(), int(model.corpus_size), resolver.rows,
-                             model.sorted_vocab() if any(t.has_union or t.has_class_span for _, t in pairs) else None)
+                             model.sorted_vocab() if any(t.has_union or t.has_class_span for _, t in pairs) else None,
+                             self._expansions(bm, [t for _, t in pairs]))
             if tt.n_phr or tt.n_near or tt.n_cspan:
                 bm.ensure_token_stream()
             qscope = np.asarray(tt.qscope)
@@ -440,12 +491,14 @@ class HybridRetriever:
                                                        {c.id: r for r, c in enumerate(bm.chunks)})
         row_of = held[2]
         sorted_vocab = None
+        expansions = None if terms is None else self._expansions(bm, terms)
         tables = []
         for i, q in enumerate(questions):
             t = None if terms is None else terms[i]
             if t is not None and sorted_vocab is None and (t.has_union or t.has_class_span):
                 sorted_vocab = model.sorted_vocab()
-            tables.append(_slot_table(bm.document_tokens(q) if spec.question else [], t, vocab, model.idf, sorted_vocab or ()))
+            tables.append(_slot_table(bm.document_tokens(q) if spec.question else [], t, vocab, model.idf, sorted_vocab or (),
+                                      expansions))
         k = max((len(h) for h in hits_lists), default=0)
         out: List[List[Optional[HitHighlight]]] = [[None] * len(h) for h in hits_lists]
         if not questions or k == 0:
@@ -1304,7 +1357,8 @@ class HybridRetriever:
                                      model.vocab(), model._doc_frequencies(), int(model.corpus_size),
                                      resolver_for(store.chunks).rows,
                                      model.sorted_vocab() if any(terms[i] is not None and (terms[i].has_union or terms[i].has_class_span)
-                                                              for i in idxs) else None)
+                                                              for i in idxs) else None,
+                                     self._expansions(bm, [terms[i] for i in idxs]))
             if term_table.n_phr or term_table.n_near or term_table.n_cspan:
                 bm.ensure_token_stream()  # (made lazily: on the first phrase or Near, and again after a live update)
         elif scoped:

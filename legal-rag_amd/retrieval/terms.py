@@ -31,6 +31,12 @@ sell! /5 good!.  They are classes of their own — Phrase, Near and OneOf keep t
 wherever a Phrase or a Near stands.  `pack()` resolves each member as it resolves a Prefix or a OneOf; an item of plain
 ids IS the plain Phrase / Near, every other one is a class span that the GPU resolves from the token stream and the
 unions' lists (amdr_class_spans, csrc/class_span.hip) behind the unions.
+
+A `Wildcard` and a `Fuzzy` are vocabulary PATTERNS: Wildcard("s?ll*") names every vocabulary token the pattern fits ('?' one
+character, '*' any run) and Fuzzy("warrenty", edits=1) every token within one edit of the word, transpositions included.
+Either stands wherever a Prefix stands.  Which tokens a pattern names is found by a scan of the resident vocabulary on the
+GPU (amdr_vocab_match, csrc/vocab_match.hip; retrieval/vocab_match.py VocabMatcher.expand) and handed to `pack()` as
+`expansions`; from there on a pattern resolves exactly as a Prefix does.
 """
 from __future__ import annotations
 
@@ -214,10 +220,165 @@ class Prefix:
         """Whether one of `tokens` (a set or a sequence) starts with the stem."""
         return any(t.startswith(self.stem) for t in tokens)
 
+WILDCARD_MAX_LEN = 64  # code points of a Wildcard's pattern or a Fuzzy's token (vocab_match_rule.hpp kVmMaxLen)
+FUZZY_MAX_EDITS = 2    # kVmMaxEdits
+_ANY_ONE, _ANY_RUN = 0x110000, 0x110001  # '?' and '*' among a Wildcard's code points (kVmAnyOne, kVmAnyRun)
+
+
+def wildcard_fits(pattern: str, token: str) -> bool:
+    """Whether `token` fits `pattern` ('?' exactly one character, '*' any run, the empty one included), character by
+    character — code points, as Python's str is: greedy, with the last '*' as the one backtrack point.  The empty token
+    fits nothing."""
+    if not token:
+        return False
+    p = t = 0
+    star_p, star_t = -1, 0
+    while t < len(token):
+        if p < len(pattern) and pattern[p] == "*":
+            star_p, star_t = p, t
+            p += 1
+        elif p < len(pattern) and (pattern[p] == "?" or pattern[p] == token[t]):
+            p, t = p + 1, t + 1
+        elif star_p >= 0:
+            star_t += 1
+            p, t = star_p + 1, star_t
+        else:
+            return False
+    return all(c == "*" for c in pattern[p:])
+
+
+def osa_distance(a: str, b: str) -> int:
+    """The optimal-string-alignment distance of two strings over code points: insertion, deletion, substitution and the
+    transposition of two adjacent characters cost 1 each, and no character is edited twice (osa("ca", "abc") is 3)."""
+    before2: List[int] = []
+    before = list(range(len(b) + 1))
+    for i in range(1, len(a) + 1):
+        row = [i] + [0] * len(b)
+        for j in range(1, len(b) + 1):
+            v = min(before[j] + 1, row[j - 1] + 1, before[j - 1] + (a[i - 1] != b[j - 1]))
+            if i > 1 and j > 1 and a[i - 1] == b[j - 2] and a[i - 2] == b[j - 1]:
+                v = min(v, before2[j - 2] + 1)
+            row[j] = v
+        before2, before = before, row
+    return before[len(b)]
+
+
+class Wildcard:
+    """The universal characters: Wildcard("s?ll*") names every vocabulary token that fits the pattern, and a chunk holds
+    it when it holds at least one of them.  '?' stands for exactly one character, '*' for any run of characters, the empty
+    one included, every other character for itself; characters are Unicode code points, never bytes.  The pattern has 1
+    to 64 code points, at least one of them a literal, and holds a '?' or a '*' (ValueError otherwise: write the plain
+    token).  There is NO escape: a vocabulary token that is literally "?" or holds a '*' cannot be named by a Wildcard (a
+    plain str names it).  Westlaw's wom*n is Wildcard("wom?n"); its sell! stays Prefix("sell").  Accepted wherever a
+    Prefix is: as an entry of a Terms field, in a tuple group, as a member of a OneOf, a PhraseOf or a NearOf — not inside
+    a plain Phrase or Near.  The pattern is compared as it is given (an English index is lower-cased: write it so); no
+    retriever method cuts one, because a tokeniser would cut at '?'.  Frozen and hashable."""
+    __slots__ = ("pattern",)
+
+    def __init__(self, pattern: str) -> None:
+        if not isinstance(pattern, str):
+            raise TypeError(f"Wildcard: the pattern is a str, got {type(pattern).__name__}")
+        if not 1 <= len(pattern) <= WILDCARD_MAX_LEN:
+            raise ValueError(f"Wildcard: 1 to {WILDCARD_MAX_LEN} characters, got {len(pattern)}")
+        if all(c in "?*" for c in pattern):
+            raise ValueError(f"Wildcard: {pattern!r} holds no literal character and names every token of its length")
+        if "?" not in pattern and "*" not in pattern:
+            raise ValueError(f"Wildcard: {pattern!r} holds neither '?' nor '*': write the plain token")
+        object.__setattr__(self, "pattern", pattern)
+
+    def __setattr__(self, name, value) -> None:
+        raise AttributeError("Wildcard is frozen")
+
+    def __delattr__(self, name) -> None:
+        raise AttributeError("Wildcard is frozen")
+
+    def __eq__(self, other) -> bool:
+        return isinstance(other, Wildcard) and self.pattern == other.pattern
+
+    def __hash__(self) -> int:
+        return hash(("Wildcard", self.pattern))
+
+    def __repr__(self) -> str:
+        return f"Wildcard({self.pattern!r})"
+
+    def __reduce__(self):
+        return (Wildcard, (self.pattern,))
+
+    def fits(self, token: str) -> bool:
+        """Whether the one token fits the pattern."""
+        return wildcard_fits(self.pattern, token)
+
+    def within(self, tokens) -> bool:
+        """Whether one of `tokens` (a set or a sequence) fits the pattern."""
+        return any(wildcard_fits(self.pattern, t) for t in tokens)
+
+    def native_pattern(self) -> Tuple[int, int, List[int]]:
+        """(kind 0, arg 0, code points) as amdr_vocab_match takes it: '?' and '*' as the two values above U+10FFFF."""
+        return 0, 0, [_ANY_ONE if c == "?" else _ANY_RUN if c == "*" else ord(c) for c in self.pattern]
+
+
+class Fuzzy:
+    """A word and its misspellings: Fuzzy("warrenty", edits=1) names every vocabulary token within `edits` (1 or 2) of the
+    token under the optimal-string-alignment distance over code points — insertion, deletion, substitution and the
+    transposition of two adjacent characters cost 1 each, no character is edited twice — the token itself included, and a
+    chunk holds it when it holds at least one of them.  With the transposition Fuzzy("recieve") finds "receive"; plain
+    Levenshtein would not.  The token has 1 to 64 code points and more than `edits` of them (ValueError).  Accepted
+    wherever a Prefix is; compared as given (HybridRetriever.fuzzy cuts a string with the index's own tokeniser).  Frozen
+    and hashable."""
+    __slots__ = ("token", "edits")
+
+    def __init__(self, token: str, edits: int = 1) -> None:
+        if not isinstance(token, str):
+            raise TypeError(f"Fuzzy: the token is a str, got {type(token).__name__}")
+        if isinstance(edits, bool) or not isinstance(edits, (int, np.integer)):
+            raise TypeError(f"Fuzzy: edits is an int, got {type(edits).__name__}")
+        if not 1 <= int(edits) <= FUZZY_MAX_EDITS:
+            raise ValueError(f"Fuzzy: edits of 1 or {FUZZY_MAX_EDITS}, got {int(edits)}")
+        if not 1 <= len(token) <= WILDCARD_MAX_LEN:
+            raise ValueError(f"Fuzzy: a token of 1 to {WILDCARD_MAX_LEN} characters, got {len(token)}")
+        if len(token) <= int(edits):
+            raise ValueError(f"Fuzzy: {token!r} within {int(edits)} edits names every token of up to {len(token) + int(edits)} "
+                             f"characters; the token must be longer than the edits")
+        object.__setattr__(self, "token", token)
+        object.__setattr__(self, "edits", int(edits))
+
+    def __setattr__(self, name, value) -> None:
+        raise AttributeError("Fuzzy is frozen")
+
+    def __delattr__(self, name) -> None:
+        raise AttributeError("Fuzzy is frozen")
+
+    def __eq__(self, other) -> bool:
+        return isinstance(other, Fuzzy) and (self.token, self.edits) == (other.token, other.edits)
+
+    def __hash__(self) -> int:
+        return hash(("Fuzzy", self.token, self.edits))
+
+    def __repr__(self) -> str:
+        return f"Fuzzy({self.token!r}, edits={self.edits})"
+
+    def __reduce__(self):
+        return (Fuzzy, (self.token, self.edits))
+
+    def fits(self, token: str) -> bool:
+        """Whether the one token lies within the edits (the empty token never does)."""
+        return bool(token) and abs(len(token) - len(self.token)) <= self.edits and osa_distance(self.token, token) <= self.edits
+
+    def within(self, tokens) -> bool:
+        """Whether one of `tokens` (a set or a sequence) lies within the edits."""
+        return any(self.fits(t) for t in tokens)
+
+    def native_pattern(self) -> Tuple[int, int, List[int]]:
+        """(kind 1, edits, code points) as amdr_vocab_match takes it."""
+        return 1, self.edits, [ord(c) for c in self.token]
+
+
+_PATTERNS = (Wildcard, Fuzzy)  # what names vocabulary tokens by a scan (pack: `expansions`)
+
 
 class OneOf:
     """Alternatives as ONE term: a chunk holds OneOf(m0, m1, ...) when it holds at least one member.  A member is a token
-    (str) or a Prefix, at least one (ValueError); a Phrase, a Near or a OneOf as a member is a TypeError — alternatives
+    (str), a Prefix, a Wildcard or a Fuzzy, at least one (ValueError); a Phrase, a Near or a OneOf as a member is a TypeError — alternatives
     between token sequences are not resolved yet.  OneOf("x") is the plain term, as a one-token Phrase is.  Accepted
     wherever a token is: as an entry of a Terms field or as a member of a tuple group — not inside a Phrase or a Near.
     Frozen and hashable: equal OneOfs (the same members in the same order) are equal and hash alike."""
@@ -227,8 +388,8 @@ class OneOf:
         if not members:
             raise ValueError("OneOf: at least one member")
         for m in members:
-            if not isinstance(m, (str, Prefix)):
-                raise TypeError(f"OneOf: a member is a str or a Prefix, got {type(m).__name__}")
+            if not isinstance(m, (str, Prefix) + _PATTERNS):
+                raise TypeError(f"OneOf: a member is a str, a Prefix, a Wildcard or a Fuzzy, got {type(m).__name__}")
         object.__setattr__(self, "members", tuple(members))
 
     def __setattr__(self, name, value) -> None:
@@ -254,16 +415,18 @@ class OneOf:
 
     def within(self, tokens) -> bool:
         """Whether `tokens` (a set or a sequence) holds one of the members."""
-        return any(m.within(tokens) if isinstance(m, Prefix) else m in tokens for m in self.members)
+        return any(m in tokens if isinstance(m, str) else m.within(tokens) for m in self.members)
 
 
 def fills(slot, token: str) -> bool:
     """Whether `token` FILLS `slot`, a member of a PhraseOf or a NearOf: it equals the str, starts with the Prefix's stem,
-    or fills a member of the OneOf."""
+    fits the Wildcard, lies within the Fuzzy's edits, or fills a member of the OneOf."""
     if isinstance(slot, str):
         return token == slot
     if isinstance(slot, Prefix):
         return token.startswith(slot.stem)
+    if isinstance(slot, _PATTERNS):
+        return slot.fits(token)
     return any(fills(m, token) for m in slot.members)
 
 
@@ -271,8 +434,9 @@ def _slots(who: str, members, most: int) -> tuple:
     if not 2 <= len(members) <= most:
         raise ValueError(f"{who}: 2 to {most} members, got {len(members)}")
     for m in members:
-        if not isinstance(m, (str, Prefix, OneOf)):
-            raise TypeError(f"{who}: a member is a str, a Prefix or a OneOf, got {type(m).__name__}")
+        if not isinstance(m, (str, Prefix, OneOf) + _PATTERNS):
+            # (the first three as the message has always named them: callers match on it)
+            raise TypeError(f"{who}: a member is a str, a Prefix or a OneOf, a Wildcard or a Fuzzy, got {type(m).__name__}")
     return tuple(members)
 
 
@@ -402,14 +566,14 @@ def _make_near_of(members, distance, ordered) -> NearOf:
     return NearOf(*members, distance=distance, ordered=ordered)
 
 
-Member = Union[str, Phrase, Near, Prefix, OneOf, PhraseOf, NearOf]
+Member = Union[str, Phrase, Near, Prefix, OneOf, PhraseOf, NearOf, Wildcard, Fuzzy]
 Group = Tuple[Member, ...]
-_MEMBERS = (str, Phrase, Near, Prefix, OneOf, PhraseOf, NearOf)
+_MEMBERS = (str, Phrase, Near, Prefix, OneOf, PhraseOf, NearOf, Wildcard, Fuzzy)
 _SPANS = (Phrase, Near, PhraseOf, NearOf)  # what needs the token SEQUENCE
 
 
 def _member(t) -> Member:
-    if isinstance(t, (Near, Prefix, PhraseOf, NearOf)):
+    if isinstance(t, (Near, Prefix, PhraseOf, NearOf) + _PATTERNS):
         return t
     if isinstance(t, OneOf):
         return t.members[0] if len(t) == 1 else t  # one member is that member
@@ -483,10 +647,32 @@ class Terms:
     def has_class_span(self) -> bool:
         return any(isinstance(t, (PhraseOf, NearOf)) for _, g in self.groups() for t in g)
 
+    def patterns(self) -> List[Any]:
+        """The distinct Wildcards and Fuzzys of this Terms in order of appearance, wherever they stand: as an entry, in a
+        tuple group, or as a member of a OneOf, a PhraseOf or a NearOf (also inside a OneOf of those)."""
+        seen: Dict[Any, None] = {}
+
+        def walk(t) -> None:
+            if isinstance(t, _PATTERNS):
+                seen.setdefault(t)
+            elif isinstance(t, (OneOf, PhraseOf, NearOf)):
+                for m in t.members:
+                    walk(m)
+        for _, g in self.groups():
+            for t in g:
+                walk(t)
+        return list(seen)
+
+    @property
+    def has_pattern(self) -> bool:
+        """Whether a Wildcard or a Fuzzy stands anywhere in this Terms: pack() then needs their `expansions`."""
+        return bool(self.patterns())
+
     def matches(self, tokens) -> bool:
         """The rule on one document's tokens (host check; the kernels apply term_scope_rule.hpp, phrase_rule.hpp,
         union_rule.hpp and class_span_rule.hpp): a token set or sequence — with a Phrase, a Near, a PhraseOf or a NearOf
-        present, the token SEQUENCE in text order (TypeError for a set); a Prefix or a OneOf takes either."""
+        present, the token SEQUENCE in text order (TypeError for a set); a Prefix, a Wildcard, a Fuzzy or a OneOf takes
+        either."""
         if self.has_phrase or self.has_near or self.has_class_span:
             if isinstance(tokens, (set, frozenset, dict)) or not isinstance(tokens, Sequence):
                 what = "Phrase" if self.has_phrase else "Near" if self.has_near else "PhraseOf or a NearOf"
@@ -495,7 +681,7 @@ class Terms:
         else:
             have = tokens if isinstance(tokens, (set, frozenset, dict)) else set(tokens)
         sat = lambda g: all(t.within(tokens) if isinstance(t, _SPANS) else  # noqa: E731
-                            t.within(have) if isinstance(t, (Prefix, OneOf)) else t in have for t in g)
+                            t.within(have) if isinstance(t, (Prefix, OneOf) + _PATTERNS) else t in have for t in g)
         return (all(sat(g) for g in self.all_of or ()) and (self.any_of is None or any(sat(g) for g in self.any_of))
                 and not any(sat(g) for g in self.none_of or ()))
 
@@ -607,7 +793,8 @@ def prefix_tokens(stem: str, sorted_vocab: Sequence[str]) -> List[str]:
 
 
 def pack(pairs: Sequence[Tuple[Optional[Scope], Terms]], vocab: Mapping[str, int], doc_freq: Mapping[str, int], n_docs: int,
-         base_rows=None, sorted_vocab: Optional[Sequence[str]] = None) -> TermTable:
+         base_rows=None, sorted_vocab: Optional[Sequence[str]] = None,
+         expansions: Optional[Mapping[Any, Any]] = None) -> TermTable:
     """The operand arrays of a batch of (Scope | None, Terms) pairs.  Equal pairs are stored once (as ScopeResolver.table
     stores equal scopes once) and `qscope` names each pair's constraint; equal base scopes are stored once as well.
     vocab / doc_freq: the live host model's token -> term id and token -> document frequency (BM25Okapi.vocab(),
@@ -635,7 +822,12 @@ def pack(pairs: Sequence[Tuple[Optional[Scope], Terms]], vocab: Mapping[str, int
     stands as the term id len(vocab) + n_phr + n_near + n_union + c, behind the unions, with the smallest slot bound (df of
     a plain id, 0 of the id -1, the union's bound) as its upper bound: cspan_cand_max / cspan_rows_cap.  An unordered NearOf
     whose slots' id sets intersect without being equal is a ValueError: the device's first-unfilled-slot tally is the
-    matching only for pairwise equal or disjoint slots.  A table without a class span is field for field the table without."""
+    matching only for pairwise equal or disjoint slots.  A table without a class span is field for field the table without.
+    A Wildcard or a Fuzzy names the tokens `expansions` holds for it — {pattern: the (token, distance) pairs, or the bare
+    tokens, it names}, VocabMatcher.expand's result; this function stays plain host code and scans no vocabulary — and
+    resolves from there on exactly as a Prefix does: none -> -1, one -> that plain term, two or more -> a union item that
+    shares its slot with an equal OneOf or Prefix.  A pattern without an entry is a ValueError.  Without a pattern
+    `expansions` is not looked at and the table is field for field what it was."""
     n_vocab = len(vocab)
     df_by_id = np.zeros(n_vocab, dtype=np.int64)
     for w, t in vocab.items():
@@ -650,7 +842,12 @@ def pack(pairs: Sequence[Tuple[Optional[Scope], Terms]], vocab: Mapping[str, int
         """The id a Prefix or a OneOf stands for: -1, a plain term's, or the placeholder ("u", u) of union u."""
         words: List[str] = []
         for m in (t.members if isinstance(t, OneOf) else (t,)):
-            if isinstance(m, Prefix):
+            if isinstance(m, _PATTERNS):
+                if expansions is None or m not in expansions:
+                    raise ValueError(f"{m!r}: pack() was given no expansion of this pattern (expansions=: "
+                                     f"VocabMatcher.expand resolves the patterns of a batch)")
+                words.extend(e if isinstance(e, str) else e[0] for e in expansions[m])
+            elif isinstance(m, Prefix):
                 if sorted_held[0] is None:
                     sorted_held[0] = sorted(vocab)
                 words.extend(prefix_tokens(m.stem, sorted_held[0]))
@@ -658,7 +855,9 @@ def pack(pairs: Sequence[Tuple[Optional[Scope], Terms]], vocab: Mapping[str, int
                 words.append(m)
         ids = tuple(sorted({vocab[w] for w in words if w in vocab}))
         if len(ids) > PREFIX_MAX_TERMS:
-            raise ValueError(f"{t!r} names {len(ids)} vocabulary tokens, more than {PREFIX_MAX_TERMS}: give a longer stem")
+            raise ValueError(f"{t!r} names {len(ids)} vocabulary tokens, more than {PREFIX_MAX_TERMS}: give a longer stem"
+                             if not isinstance(t, _PATTERNS) else
+                             f"{t!r} names {len(ids)} vocabulary tokens, more than {PREFIX_MAX_TERMS}: give a narrower pattern")
         if len(ids) < 2:
             return ids[0] if ids else -1
         u = union_slot.get(ids)
@@ -719,7 +918,7 @@ def pack(pairs: Sequence[Tuple[Optional[Scope], Terms]], vocab: Mapping[str, int
                 near_ids.append(ids)
                 near_bound.append(0 if min(ids) < 0 else int(min(df_by_id[i] for i in ids)))
             return ("n", j)
-        if isinstance(t, (Prefix, OneOf)):  # (numbered behind the Nears: a placeholder as well)
+        if isinstance(t, (Prefix, OneOf) + _PATTERNS):  # (numbered behind the Nears: a placeholder as well)
             return union_id(t)
         if not isinstance(t, Phrase):
             return vocab.get(t, -1)
