@@ -1139,6 +1139,47 @@ int amdr_class_spans(amdr_bm25_t* bm25, const int64_t* item_ptr, const int32_t* 
                      const int32_t* item_dist, int64_t n_items, const int64_t* cls_ptr, const int32_t* cls_terms, int64_t n_cls,
                      int64_t cand_max, int64_t rows_cap, int64_t* out_list_ptr, int32_t* out_docs, int32_t* out_status);
 
+/* ---- unit spans: same sentence, same paragraph (csrc/unit_span.hip, csrc/unit_span_rule.hpp) --------
+ * No reference counterpart.  buyer /s seller: "one provision speaks of both".
+ * The break flags lie beside the token stream of amdr_bm25_set_tokens, one byte per token: bit 0 (value 1) the token begins a
+ * sentence, bit 1 (value 2) it begins a paragraph; a paragraph start is a sentence start, so a byte is 0, 1 or 3.  The first
+ * token of a document begins both, whatever its byte says.  The flagged tokens partition a document into units.
+ * amdr_bm25_set_breaks needs a resident stream of exactly n_tokens tokens and refuses (AMDR_EINVAL, the handle keeps what it
+ * had) any other count and any byte outside {0, 1, 3}.  The flags describe ONE state of the stream: amdr_bm25_set_tokens,
+ * every successful update — plain or carrying; the carry kernels do not carry the flags — and whatever else drops the stream
+ * drop them.  amdr_bm25_breaks_info: out2[0] 1 if flags are resident else 0, out2[1] their count.  amdr_bm25_read_breaks
+ * copies them back (AMDR_EINVAL without flags).
+ * A unit item is L slot ids, 2 <= L <= 8, exactly as a class span's (a plain term id, or n_terms + cls_first + c for class c),
+ * and a kind: bit 0 ordered, bit 1 paragraph (else sentence).  Within one document
+ *   unordered  some unit admits an assignment of the slots to DISTINCT positions of the unit, each token filling its slot (a
+ *              bipartite matching; slots with different ids must name disjoint token sets — equal sets share one id);
+ *   ordered    positions p0 < p1 < ... inside one unit, token p_i filling slot i.
+ * An item the rule does not define (a length or kind out of range, an unknown slot) gets an empty list; nothing is
+ * dereferenced for it.  Item p's list is the ascending documents that hold it, appended to the call's list array behind the
+ * n_before lists already there (the class spans' last), status as amdr_term_scope: 1 the driver — the shortest slot list —
+ * exceeds cand_max, 2 rows dropped at rows_cap.  Three launches (count, scan, write), no global atomics, deterministic,
+ * nothing allocated or cleared, capturable; grid n_items x max(1, ceil(cand_max / 256)) cells.  The count pass walks a
+ * surviving document 64 tokens per round — 4 B of token and 1 B of flag per lane, each read once — and decides every round
+ * from the wave's ballots.
+ * amdr_unit_spans_plan is host-only arithmetic (two i64 and 1 KiB per cell).  amdr_unit_spans_device only enqueues; it does
+ * not validate the operands' contents and returns AMDR_EINVAL, enqueueing nothing, for a null handle or array, a negative
+ * size, classes that do not lie among the n_before lists, too many cells, work_bytes below the plan, or a handle without a
+ * token stream or without break flags.  amdr_unit_spans is the host-pointer twin: class c is the slot id n_terms + c; it
+ * validates (AMDR_EINVAL), runs the union step for the classes and then this step in an array of its own on the BM25
+ * handle's stream under its mutex, and returns only the items' lists, rebased to 0. */
+int amdr_bm25_set_breaks(amdr_bm25_t* h, const uint8_t* brk, int64_t n_tokens);
+int amdr_bm25_breaks_info(amdr_bm25_t* h, int64_t* out2);
+int amdr_bm25_read_breaks(amdr_bm25_t* h, uint8_t* out);
+int amdr_unit_spans_plan(int64_t n_items, int64_t cand_max, int64_t* work_bytes);
+int amdr_unit_spans_device(amdr_bm25_t* bm25, const int64_t* item_ptr_dev, const int32_t* item_slots_dev,
+                           const int32_t* item_kind_dev, int64_t n_items, const int64_t* cls_ptr_dev, const int32_t* cls_terms_dev,
+                           int64_t n_cls, int64_t cls_first, int64_t n_before, int64_t cand_max, int64_t rows_cap,
+                           int64_t* list_ptr_dev, int32_t* docs_dev, int32_t* out_status_dev, void* work_dev, int64_t work_bytes,
+                           void* stream);
+int amdr_unit_spans(amdr_bm25_t* bm25, const int64_t* item_ptr, const int32_t* item_slots, const int32_t* item_kind,
+                    int64_t n_items, const int64_t* cls_ptr, const int32_t* cls_terms, int64_t n_cls, int64_t cand_max,
+                    int64_t rows_cap, int64_t* out_list_ptr, int32_t* out_docs, int32_t* out_status);
+
 /* ---- marks and best passages of the hit documents (csrc/marks.hip, csrc/marks_rule.hpp) --------
  * No reference counterpart.  For every (query, hit) pair: which tokens of the hit document the query MARKS, and the window
  * of `window` tokens that holds the most of the query — term highlighting and the best-passage snippet, from the resident

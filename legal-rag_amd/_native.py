@@ -70,6 +70,9 @@ SIGNATURES = {
     "amdr_union_lists_plan": "llP", "amdr_union_lists_device": "PPP" + "lll" + "PPP" + "PlP", "amdr_union_lists": "PPP" + "ll" + "PPP",
     "amdr_class_spans_plan": "llP", "amdr_class_spans_device": "PPPPP" + "l" + "PP" + "lllll" + "PPP" + "PlP",
     "amdr_class_spans": "PPPPP" + "l" + "PP" + "lll" + "PPP",
+    "amdr_bm25_set_breaks": "PPl", "amdr_bm25_breaks_info": "PP", "amdr_bm25_read_breaks": "PP",
+    "amdr_unit_spans_plan": "llP", "amdr_unit_spans_device": "PPPP" + "l" + "PP" + "lllll" + "PPP" + "PlP",
+    "amdr_unit_spans": "PPPP" + "l" + "PP" + "lll" + "PPP",
     "amdr_bm25_marks_device": "PPlll" + "P" * 8 + "ii" + "P" * 6, "amdr_bm25_marks": "PPlll" + "P" * 8 + "ii" + "P" * 5,
     "amdr_bm25_marks_kernel_ms": "PP",
     "amdr_facet_plan": "liPP", "amdr_facet_counts_device": "PPll" + "PliPi" + "PPPPP" + "PlP",
@@ -263,6 +266,14 @@ def class_spans_plan(n_items: int, cand_max: int) -> int:
     per cell (item, tile of PHRASE_TILE candidates) two i64 and the parked ranks."""
     out = C.c_int64(0)
     _check(load().amdr_class_spans_plan(C.c_int64(n_items), C.c_int64(cand_max), C.byref(out)), "amdr_class_spans_plan")
+    return int(out.value)
+
+
+def unit_spans_plan(n_items: int, cand_max: int) -> int:
+    """Workspace bytes of BM25Index.unit_spans_device(n_items unit items, longest driver cand_max) — host-only arithmetic:
+    per cell (item, tile of PHRASE_TILE candidates) two i64 and the parked ranks."""
+    out = C.c_int64(0)
+    _check(load().amdr_unit_spans_plan(C.c_int64(n_items), C.c_int64(cand_max), C.byref(out)), "amdr_unit_spans_plan")
     return int(out.value)
 
 
@@ -821,6 +832,12 @@ class BM25Index(_Handle):
                "amdr_bm25_read_tokens")
         return dp, tk
 
+    def token_doc_ptr(self) -> np.ndarray:
+        """doc_ptr i64 [n_docs + 1] of the resident token stream alone (amdr_bm25_read_tokens with a null token array)."""
+        dp = np.empty(self.info()[0] + 1, np.int64)
+        _check(load().amdr_bm25_read_tokens(self._h, _p(dp, C.c_int64), None), "amdr_bm25_read_tokens")
+        return dp
+
     def phrase_lists(self, phr_ptr, phr_terms, cand_max: int, rows_cap: int):
         """The host twin: (list_ptr i64 [n_phr + 1], docs i32 [list_ptr[-1]], status i32 [n_phr]) of the phrases
         phr_terms[phr_ptr[p] : phr_ptr[p + 1]] — each list the ascending documents that hold the phrase.  status as
@@ -941,6 +958,60 @@ class BM25Index(_Handle):
                                               C.c_int64(n_cls), C.c_int64(cls_first), C.c_int64(n_before), C.c_int64(cand_max),
                                               C.c_int64(rows_cap), _vp(list_ptr_ptr), _vp(docs_ptr), _vp(status_ptr),
                                               _vp(work_ptr), C.c_int64(work_bytes), _vp(stream)), "amdr_class_spans_device")
+
+    # -- unit spans: same sentence, same paragraph (amdr_unit_spans, csrc/unit_span.hip) ---------------------------------
+    def set_breaks(self, breaks) -> None:
+        """The break flags beside the resident token stream (amdr_bm25_set_breaks): one byte per token, 1 a sentence start, 3
+        a paragraph start, 0 neither.  set_tokens and every update drop them."""
+        bk = _c(breaks, np.uint8).ravel()
+        arg = bk if bk.size else np.zeros(1, dtype=np.uint8)
+        _check(load().amdr_bm25_set_breaks(self._h, _p(arg, C.c_uint8), C.c_int64(bk.size)), "amdr_bm25_set_breaks")
+
+    def breaks_info(self) -> Tuple[bool, int]:
+        """(whether break flags are resident, their count)."""
+        out = (C.c_int64 * 2)()
+        _check(load().amdr_bm25_breaks_info(self._h, out), "amdr_bm25_breaks_info")
+        return bool(out[0]), int(out[1])
+
+    def read_breaks(self) -> np.ndarray:
+        """The resident break flags, copied to the host: u8 [n_tokens]."""
+        n = self.breaks_info()[1]
+        bk = np.empty(max(n, 1), np.uint8)
+        _check(load().amdr_bm25_read_breaks(self._h, _p(bk, C.c_uint8)), "amdr_bm25_read_breaks")
+        return bk[:n]
+
+    def unit_spans(self, item_ptr, item_slots, item_kind, cls_ptr, cls_terms, cand_max: int, rows_cap: int):
+        """The host twin: (list_ptr i64 [n + 1], docs i32 [list_ptr[-1]], status i32 [n]) of the unit items
+        item_slots[item_ptr[p] : item_ptr[p + 1]] of kind item_kind[p] (bit 0 ordered, bit 1 paragraph) whose slot ids are
+        plain term ids or n_terms + c for class c, as class_spans takes them.  Runs the union step for the classes and then
+        the unit step; returns only the items' lists.  status as term_scope."""
+        pp, pt = _c(item_ptr, np.int64).ravel(), _c(item_slots, np.int32).ravel()
+        kd = _c(item_kind, np.int32).ravel()
+        cp, ct = _c(cls_ptr, np.int64).ravel(), _c(cls_terms, np.int32).ravel()
+        if pp.size < 1 or kd.size != pp.size - 1 or cp.size < 1:
+            raise ValueError("unit_spans: item_ptr [n + 1], item_kind [n], cls_ptr [n_cls + 1]")
+        n, n_cls = pp.size - 1, cp.size - 1
+        lp = np.zeros(n + 1, dtype=np.int64)
+        docs = np.full(max(int(rows_cap), 1), -1, dtype=np.int32)
+        status = np.zeros(max(n, 1), dtype=np.int32)
+        pad = np.zeros(1, dtype=np.int32)
+        _check(load().amdr_unit_spans(self._h, _p(pp, C.c_int64), _p(pt if pt.size else pad, C.c_int32),
+                                      _p(kd if n else pad, C.c_int32), C.c_int64(n), _p(cp, C.c_int64),
+                                      _p(ct if ct.size else pad, C.c_int32), C.c_int64(n_cls), C.c_int64(cand_max),
+                                      C.c_int64(rows_cap), _p(lp, C.c_int64), _p(docs, C.c_int32), _p(status, C.c_int32)),
+               "amdr_unit_spans")
+        return lp, docs[:int(lp[-1])], status[:n]
+
+    def unit_spans_device(self, item_ptr_ptr: int, item_slots_ptr: int, item_kind_ptr: int, n_items: int, cls_ptr_ptr: int,
+                          cls_terms_ptr: int, n_cls: int, cls_first: int, n_before: int, cand_max: int, rows_cap: int,
+                          list_ptr_ptr: int, docs_ptr: int, status_ptr: int, work_ptr: int, work_bytes: int,
+                          stream: int = 0) -> None:
+        """The "_device" form, as class_spans_device without the distances; needs the break flags (set_breaks)."""
+        _check(load().amdr_unit_spans_device(self._h, _vp(item_ptr_ptr), _vp(item_slots_ptr), _vp(item_kind_ptr),
+                                             C.c_int64(n_items), _vp(cls_ptr_ptr), _vp(cls_terms_ptr), C.c_int64(n_cls),
+                                             C.c_int64(cls_first), C.c_int64(n_before), C.c_int64(cand_max),
+                                             C.c_int64(rows_cap), _vp(list_ptr_ptr), _vp(docs_ptr), _vp(status_ptr),
+                                             _vp(work_ptr), C.c_int64(work_bytes), _vp(stream)), "amdr_unit_spans_device")
 
     # -- marks and best passages of the hit documents (amdr_bm25_marks, csrc/marks.hip) ---------------------------------
     def marks(self, docs, mk_ptr, mk_terms, mk_slot, slot_w, slot_loose, sq_ptr, sq_off, sq_slots, window: int,

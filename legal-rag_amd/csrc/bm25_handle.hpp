@@ -1,7 +1,7 @@
 // The BM25 handle, shared by bm25.hip (create, plan, score, search, destroy), bm25_update.hip (add, remove, info, read, the
 // token stream) and the list resolvers of list_step.hpp: term_scope.hip (term constraints), phrase_scope.hip (phrases,
-// Nears), union_lists.hip (unions of posting lists) and class_span.hip (class spans), and marks.hip (marks and best passages
-// of the hit documents).  The per-call plumbing of the updates
+// Nears), union_lists.hip (unions of posting lists), class_span.hip (class spans) and unit_span.hip (unit spans and the break
+// flags), and marks.hip (marks and best passages of the hit documents).  The per-call plumbing of the updates
 // (dev_alloc, CallScratch, KernelSpans, AMDR_TRY) is call_scratch.hpp's, shared with the other two channels.
 #pragma once
 #include "call_scratch.hpp"
@@ -90,10 +90,19 @@ struct amdr_bm25 {
   int* tok = nullptr;            // [n_tokens]
   int64_t n_tokens = 0;
   bool has_tokens = false;
+  // The break flags (amdr_bm25_set_breaks, unit_span.hip): one byte per token of the stream, bit 0 a sentence start, bit 1 a
+  // paragraph start.  They describe ONE state of the stream: whatever drops or replaces the stream drops them.
+  unsigned char* brk = nullptr;  // [n_tokens]
+  bool has_breaks = false;
+  void drop_breaks() {
+    if (brk) (void)hipFree(brk);
+    brk = nullptr, has_breaks = false;
+  }
   void drop_tokens() {
     if (tok_ptr) (void)hipFree(tok_ptr);
     if (tok) (void)hipFree(tok);
     tok_ptr = nullptr, tok = nullptr, n_tokens = 0, has_tokens = false;
+    drop_breaks();
   }
 };
 
@@ -123,6 +132,7 @@ struct BmStagedTokens {
     std::swap(h.tok, tok);
     std::swap(h.n_tokens, n_tokens);
     h.has_tokens = true;
+    h.drop_breaks();  // (they described the stream as it was; the carry kernels do not carry them)
   }
 };
 

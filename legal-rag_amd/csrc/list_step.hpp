@@ -1,6 +1,6 @@
 // What the list resolvers on the BM25 handle share: term_scope.hip (term constraints), phrase_scope.hip (phrases, Nears),
-// union_lists.hip (Prefix / OneOf) and class_span.hip (PhraseOf / NearOf).  Each resolves ITEMS into ascending lists
-// that lie back to back in one array (list_ptr [n + 1] | rows), in three launches without atomics:
+// union_lists.hip (Prefix / OneOf), class_span.hip (PhraseOf / NearOf) and unit_span.hip (Within).  Each resolves ITEMS into
+// ascending lists that lie back to back in one array (list_ptr [n + 1] | rows), in three launches without atomics:
 //   count   the resolver's own kernel, one block per CELL (item x tile): the tile's keep count -> counts[cell], what the
 //           write pass needs again parked in the cell's payload.
 //   scan    compact_scan_i64_kernel over the counts: every cell's offset.
@@ -8,7 +8,7 @@
 //           dropped (status 2); thread 0 of an item's tile 0 writes the item's list_ptr entry (list_write_header).
 // A call may CONTINUE an array: n_before lists stand before its own, start = list_ptr[n_before] is read on the device.
 // Here: the workspace layout, the launch sequence, the device pieces of the write pass and of the candidate-tile kernels
-// (phrase_scope.hip, class_span.hip), and the host twins' staging over bm25->tscope.  What an item is, its grid and its
+// (phrase_scope.hip, class_span.hip, unit_span.hip), and the host twins' staging over bm25->tscope.  What an item is, its grid and its
 // kernels stay with each resolver.
 #pragma once
 #include "bm25_handle.hpp"

@@ -275,6 +275,61 @@ class BM25Retriever:
             doc_ptr, tokens = self.bm25.token_stream([self.document_tokens(c.text) for c in self.chunks])
             g.set_tokens(doc_ptr, tokens)
 
+    def ensure_breaks(self) -> None:
+        """The resident break flags of the native index (BM25Index.set_breaks; retrieval/units.py is the rule), made on the
+        first Within and again after whatever dropped them: set_tokens and every live add / remove / replace, carrying or
+        not.  The stream is made resident first (ensure_token_stream).  The flags come from a PER-CHUNK CACHE keyed by the
+        chunk's id AND its text — a replaced chunk has another text, so its old entry cannot be reused — and only chunks
+        without an entry are cut; entries of chunks that are gone are dropped.  The cached flags are concatenated in chunk
+        order, each document's length is checked against the resident stream's doc_ptr (RuntimeError on a mismatch) and
+        the flags go up, 1 B per token.  After a live update under cfg.retrieval.token_stream = "carry" the next Within
+        therefore costs a cut of the NEW texts, one concatenation and that upload, not a re-cut of the corpus.  Not on a row
+        shard (ValueError)."""
+        import numpy as np
+        from .units import PARAGRAPH, SENTENCE, break_flags
+        self.load()
+        if self.shard is not None:
+            raise ValueError("sentence and paragraph constraints do not run on a row-sharded index")
+        self.ensure_token_stream()
+        g = self.gpu_index()
+        with self._tokens_lock:
+            if g.breaks_info()[0]:
+                return
+            lowered = self.index_tokenizer == "en_regex"
+            old = self.__dict__.get("_break_cache", {})
+            cache, cut, parts, unmapped = {}, [], [], 0
+            for c in self.chunks:
+                key = (c.id, c.text)
+                ent = cache.get(key) or old.get(key)
+                if ent is None:
+                    ent = break_flags(c.text, self.document_tokens(c.text), lowered)
+                    cut.append(c.id)
+                cache[key] = ent
+                parts.append(ent[0])
+                unmapped += 0 if ent[1] else 1
+            self._break_cache = cache
+            self.breaks_cut = cut  # the ids of the chunks the last call had to cut
+            doc_ptr = g.token_doc_ptr()
+            lens = np.diff(doc_ptr)
+            if len(parts) != lens.size:
+                raise RuntimeError(f"[BM25] {len(parts)} chunks, a token stream of {lens.size} documents")
+            for d, (fl, n) in enumerate(zip(parts, lens)):
+                if fl.size != int(n):
+                    raise RuntimeError(f"[BM25] chunk {self.chunks[d].id!r}: {fl.size} break flags for the {int(n)} tokens of its "
+                                       f"resident run (the chunk text and the token stream disagree)")
+            flags = np.concatenate(parts) if parts else np.zeros(0, dtype=np.uint8)
+            g.set_breaks(flags)
+            n_docs = int(np.count_nonzero(lens))
+            self._units_info = (int(flags.size), n_docs + int(np.count_nonzero(flags & SENTENCE)),
+                                n_docs + int(np.count_nonzero(flags & PARAGRAPH)), unmapped)
+
+    def units_info(self):
+        """(tokens, sentences, paragraphs, unmapped documents) of the resident break flags (ensure_breaks makes them): a
+        document's first token opens a sentence and a paragraph, every flagged token one more; an unmapped document — its
+        tokens could not be mapped back to its text — counts as one of each."""
+        self.ensure_breaks()
+        return self._units_info
+
     def tokenize_query(self, query: str) -> List[str]:
         """bm25_retriever.py:73 — jieba.cut, not lower-cased.  Mode "char" / "dict" when the index was built
         that way or the config opts in; otherwise a Han query without a segmenter raises."""

@@ -252,18 +252,22 @@ class HybridEngine:
           union   amdr_union_lists_device; needs no token stream.
           class   amdr_class_spans_device; its classes are the unions (cls_first = the span step's lists) and it reads
                   their lists where the union step wrote them.  Needs the token stream.
+          unit    amdr_unit_spans_device over the Withins, behind the class spans, with the same classes.  Needs the token
+                  stream and its break flags (BM25Index.set_breaks).
         The array is sized for the steps' row bounds together, and the status tensor holds the constraints' words and then
-        each step's, in list order: i32 [n_cons + n_phr + n_near + n_union + n_cspan]."""
+        each step's, in list order: i32 [n_cons + n_phr + n_near + n_union + n_cspan + n_unit]."""
         self.check_term_scopes()
         n_cons, cand_max, rows_cap = int(table.n_cons), int(table.cand_max), int(table.rows_cap)
         n_phr = int(getattr(table, "n_phr", 0))
         n_near = int(getattr(table, "n_near", 0))
         n_union = int(getattr(table, "n_union", 0))
         n_cspan = int(getattr(table, "n_cspan", 0))
+        n_unit = int(getattr(table, "n_unit", 0))
         n_span = n_phr + n_near
-        n_x = n_span + n_union + n_cspan  # the virtual lists of the term step
+        n_x = n_span + n_union + n_cspan + n_unit  # the virtual lists of the term step
         span_cap = (int(table.span_rows_cap) if n_near else int(table.phr_rows_cap)) if n_x else 0
-        list_cap = span_cap + int(getattr(table, "union_rows_cap", 0)) + (int(table.cspan_rows_cap) if n_cspan else 0)
+        list_cap = (span_cap + int(getattr(table, "union_rows_cap", 0)) + (int(table.cspan_rows_cap) if n_cspan else 0)
+                    + (int(table.unit_rows_cap) if n_unit else 0))
         # The list steps in call order: (name, operands: item_ptr i64 and then i32 arrays, item count, n_before, the key of
         # its grown workspace, plan() -> bytes, call(operand pointers, at, the output and workspace arguments)).
         steps = []
@@ -286,6 +290,13 @@ class HybridEngine:
                           lambda ops, at, out: self.bm25.class_spans_device(
                               *ops, n_cspan, *((at["union0"], at["union1"]) if n_union else (0, 0)), n_union, n_span,
                               n_span + n_union, c_max, list_cap, *out)))
+        if n_unit:
+            w_max = int(table.unit_cand_max)
+            steps.append(("unit", table.unit_ops, n_unit, n_span + n_union + n_cspan, "usw",
+                          lambda: _native.unit_spans_plan(n_unit, w_max),
+                          lambda ops, at, out: self.bm25.unit_spans_device(
+                              *ops, n_unit, *((at["union0"], at["union1"]) if n_union else (0, 0)), n_union, n_span,
+                              n_span + n_union + n_cspan, w_max, list_cap, *out)))
         # Staging, the i64 arrays first (every array starts on a multiple of its item size): the term step's, the steps'
         # item_ptr (the last step's first); then the i32 arrays: the term step's, each step's in call order, qscope.
         term_names = ("grp_ptr", "grp_kind", "grp_term_ptr", "grp_terms", "base_ptr", "base_rows", "cons_base")

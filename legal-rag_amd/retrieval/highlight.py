@@ -11,7 +11,7 @@ Slots.  A slot is one query word, at most 32 per question:
     cut with the DOCUMENT-side tokeniser so that "Security" marks "security"; a question token without a letter or a digit
     (the blanks and the punctuation a segmenter cuts as tokens of their own) is no query word;
   * a plain token, a Prefix (every vocabulary token with the stem), a Wildcard, a Fuzzy and a OneOf are LOOSE slots: they
-    mark their tokens wherever they stand; so are the members of a Near / NearOf;
+    mark their tokens wherever they stand; so are the members of a Near / NearOf / Within;
   * a Phrase / PhraseOf is a SEQUENCE over its members' slots, which are loose only if something else makes them so: its
     members are marked only where the whole phrase stands;
   * a term id that belongs to two slots goes to the lower one; a slot's weight is the model's idf of its token, for a class
@@ -26,7 +26,7 @@ from typing import Any, Dict, List, Mapping, Optional, Sequence, Tuple
 
 import numpy as np
 
-from .terms import Fuzzy, Near, NearOf, Phrase, PhraseOf, Prefix, Terms, Wildcard, prefix_tokens
+from .terms import Fuzzy, Near, NearOf, Phrase, PhraseOf, Prefix, Terms, Wildcard, Within, prefix_tokens
 
 MAX_SLOTS = 32      # kMkSlots
 MAX_WINDOW = 4096   # kMkMaxWindow
@@ -182,7 +182,7 @@ def slot_table(question_tokens: Sequence[str], terms: Optional[Terms], vocab: Ma
                             miss(_label(m))
                         continue
                     seqs.append([slot_for(m, False, "terms") for m in members])
-                elif isinstance(item, (Near, NearOf)):
+                elif isinstance(item, (Near, NearOf, Within)):
                     for m in (item.tokens if isinstance(item, Near) else item.members):
                         slot_for(m, True, "terms")
                 else:

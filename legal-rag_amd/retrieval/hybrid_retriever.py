@@ -44,7 +44,7 @@ from .highlight import Highlight, HitHighlight, build as _build_highlight, pack_
 from .highlight import slot_table as _slot_table
 from .rerankers import RerankerFactory, _to_doc_text
 from .scope import Scope, resolver_for
-from .terms import Fuzzy, Near, NearOf, Phrase, PhraseOf, Prefix, Terms, Wildcard, pack as _pack_terms  # noqa: F401 (NearOf, PhraseOf, Wildcard: re-exported)
+from .terms import Fuzzy, Near, NearOf, Phrase, PhraseOf, Prefix, Terms, Wildcard, Within, pack as _pack_terms  # noqa: F401 (NearOf, PhraseOf, Wildcard: re-exported)
 from .vocab_match import Suggestion, collect_patterns as _collect_patterns  # noqa: F401 (Suggestion: re-exported)
 
 logger = logging.getLogger("legalrag.retrieval.hybrid_retriever")
@@ -238,7 +238,7 @@ class HybridRetriever:
                              f"be a row of the channel)")
         model = bm.bm25
         tt = _pack_terms([(scope, terms)], model.vocab(), model._doc_frequencies(), int(model.corpus_size),
-                         resolver_for(bm.chunks).rows, model.sorted_vocab() if terms.has_union or terms.has_class_span else None,
+                         resolver_for(bm.chunks).rows, model.sorted_vocab() if terms.has_union or terms.has_class_span or terms.has_within else None,
                          self._expansions(bm, [terms]))
         if tt.cand_max == 0:
             return np.zeros(0, dtype=np.int64)
@@ -280,6 +280,15 @@ class HybridRetriever:
                                                                  tt.cspan_cand_max, tt.cspan_rows_cap)
             check(c_status, lambda c: tt.cspans[c])
             lists = behind(lists, c_lp, c_docs)
+        if tt.n_unit:  # the Withins behind the class spans: the twin resolves the classes it needs itself, as the class step's
+            bm.ensure_breaks()
+            w_ptr, w_slots, w_kind = tt.unit_ops
+            first = len(model.vocab()) + tt.n_phr + tt.n_near  # union u is the twin's class u
+            w_lp, w_docs, w_status = bm.gpu_index().unit_spans(w_ptr, np.where(w_slots >= first, w_slots - (tt.n_phr + tt.n_near),
+                                                                               w_slots), w_kind, *tt.union_ops,
+                                                               tt.unit_cand_max, tt.unit_rows_cap)
+            check(w_status, lambda w: tt.units[w])
+            lists = behind(lists, w_lp, w_docs)
         _, rows, status = bm.gpu_index().term_scope(tt.ops, tt.cand_max, tt.rows_cap, lists=lists)
         check(status[:1], None)
         return rows
@@ -312,6 +321,15 @@ class HybridRetriever:
         if not isinstance(bm, BM25Retriever):
             raise ValueError("near(): proximity constraints need this package's own BM25 retriever")
         return Near(*bm.document_tokens(text_), distance=distance, ordered=ordered)
+
+    def within(self, text_: str, unit: str = "sentence", ordered: bool = False) -> Within:
+        """The Within of a string, cut by the BM25 index's DOCUMENT-side tokeniser as near() cuts it:
+        retriever.within("Buyer Seller", unit="sentence") == Within("buyer", "seller", unit="sentence").  ValueError for a
+        string with fewer than 2 or more than 8 tokens, an unknown unit, or on an index that records no tokeniser."""
+        bm = self.bm25
+        if not isinstance(bm, BM25Retriever):
+            raise ValueError("within(): sentence and paragraph connectors need this package's own BM25 retriever")
+        return Within(*bm.document_tokens(text_), unit=unit, ordered=ordered)
 
     def prefix(self, text_: str) -> Prefix:
         """The Prefix of a string, cut by the BM25 index's DOCUMENT-side tokeniser as phrase() cuts it:
@@ -415,10 +433,12 @@ class HybridRetriever:
         else:
             model = bm.bm25
             tt = _pack_terms(pairs, model.vocab(), model._doc_frequencies(), int(model.corpus_size), resolver.rows,
-                             model.sorted_vocab() if any(t.has_union or t.has_class_span for _, t in pairs) else None,
+                             model.sorted_vocab() if any(t.has_union or t.has_class_span or t.has_within for _, t in pairs) else None,
                              self._expansions(bm, [t for _, t in pairs]))
             if tt.n_phr or tt.n_near or tt.n_cspan:
                 bm.ensure_token_stream()
+            if tt.n_unit:
+                bm.ensure_breaks()
             qscope = np.asarray(tt.qscope)
         import torch
         with self._stage().lock:
@@ -495,7 +515,7 @@ class HybridRetriever:
         tables = []
         for i, q in enumerate(questions):
             t = None if terms is None else terms[i]
-            if t is not None and sorted_vocab is None and (t.has_union or t.has_class_span):
+            if t is not None and sorted_vocab is None and (t.has_union or t.has_class_span or t.has_within):
                 sorted_vocab = model.sorted_vocab()
             tables.append(_slot_table(bm.document_tokens(q) if spec.question else [], t, vocab, model.idf, sorted_vocab or (),
                                       expansions))
@@ -1356,11 +1376,14 @@ class HybridRetriever:
             term_table = _pack_terms([(scopes[i] if scopes is not None else None, terms[i] or Terms()) for i in idxs],
                                      model.vocab(), model._doc_frequencies(), int(model.corpus_size),
                                      resolver_for(store.chunks).rows,
-                                     model.sorted_vocab() if any(terms[i] is not None and (terms[i].has_union or terms[i].has_class_span)
+                                     model.sorted_vocab() if any(terms[i] is not None and (
+                                         terms[i].has_union or terms[i].has_class_span or terms[i].has_within)
                                                               for i in idxs) else None,
                                      self._expansions(bm, [terms[i] for i in idxs]))
             if term_table.n_phr or term_table.n_near or term_table.n_cspan:
                 bm.ensure_token_stream()  # (made lazily: on the first phrase or Near, and again after a live update)
+            if term_table.n_unit:
+                bm.ensure_breaks()  # (the break flags beside it: only a batch with a Within pays for them)
         elif scoped:
             table = resolver_for(store.chunks).table([scopes[i] for i in idxs])
         host, extra = self._run(prep, params, eff, fetch, after, table, mmr, term_table)

@@ -37,6 +37,13 @@ character, '*' any run) and Fuzzy("warrenty", edits=1) every token within one ed
 Either stands wherever a Prefix stands.  Which tokens a pattern names is found by a scan of the resident vocabulary on the
 GPU (amdr_vocab_match, csrc/vocab_match.hip; retrieval/vocab_match.py VocabMatcher.expand) and handed to `pack()` as
 `expansions`; from there on a pattern resolves exactly as a Prefix does.
+
+A `Within` is the SAME-SENTENCE / SAME-PARAGRAPH connector (buyer /s seller, buyer +p seller): Within("buyer", "seller",
+unit="sentence") names the chunks in which one sentence holds both words — "one provision speaks of both", which no
+distance expresses.  Its members are those of a NearOf and it stands wherever a Near stands.  Where a sentence or a
+paragraph begins is the rule of retrieval/units.py, resident beside the token stream as one break byte per token
+(amdr_bm25_set_breaks); the GPU resolves the Withins of a batch from the stream and the flags (amdr_unit_spans,
+csrc/unit_span.hip) behind the class spans.
 """
 from __future__ import annotations
 
@@ -566,14 +573,118 @@ def _make_near_of(members, distance, ordered) -> NearOf:
     return NearOf(*members, distance=distance, ordered=ordered)
 
 
-Member = Union[str, Phrase, Near, Prefix, OneOf, PhraseOf, NearOf, Wildcard, Fuzzy]
+WITHIN_MAX_TERMS = 8  # members of a Within (unit_span_rule.hpp kUsMaxSlots)
+UNITS = ("sentence", "paragraph")
+BREAK_SENTENCE, BREAK_PARAGRAPH = 1, 2  # the bits of a break byte (retrieval/units.py)
+
+
+class Within:
+    """The same-sentence and same-paragraph connectors (/s and +s, /p and +p of a Boolean legal search): a chunk holds
+    Within(m0, m1, ..., unit="sentence") when ONE sentence of its text holds every member, and unit="paragraph" when one
+    paragraph does.  A chunk's tokens are partitioned into units at the tokens whose break flag says so (retrieval/units.py:
+    a sentence begins behind . ? ! 。 ！ ？, a paragraph behind a line break, a paragraph start is a sentence start, the
+    first token begins both).  Members are a NearOf's: a token (str), a Prefix, a OneOf, a Wildcard or a Fuzzy.
+      ordered=False  some unit admits an assignment of the members to DISTINCT positions of that unit, each token filling
+                     its member — a bipartite matching: Within("goods", "goods") needs two in one sentence.
+      ordered=True   there are positions p0 < p1 < ... inside one unit with token p_i filling member i.
+    2 to 8 members, unit "sentence" or "paragraph" (ValueError); a Phrase, a Near, a PhraseOf, a NearOf or a Within as a
+    member is a TypeError.  The GPU resolves the unordered form only when the members' token sets are pairwise equal or
+    disjoint: pack() raises ValueError for Within("seller", Prefix("sell")).  Accepted wherever a Near is.  Frozen and
+    hashable."""
+    __slots__ = ("members", "unit", "ordered")
+
+    def __init__(self, *members, unit: str = "sentence", ordered: bool = False) -> None:
+        members = _slots("Within", members, WITHIN_MAX_TERMS)
+        if not isinstance(unit, str):
+            raise TypeError(f"Within: unit is a str, got {type(unit).__name__}")
+        if unit not in UNITS:
+            raise ValueError(f"Within: unit is 'sentence' or 'paragraph', got {unit!r}")
+        object.__setattr__(self, "members", members)
+        object.__setattr__(self, "unit", unit)
+        object.__setattr__(self, "ordered", bool(ordered))
+
+    def __setattr__(self, name, value) -> None:
+        raise AttributeError("Within is frozen")
+
+    def __delattr__(self, name) -> None:
+        raise AttributeError("Within is frozen")
+
+    def _key(self):
+        return (self.members, self.unit, self.ordered)
+
+    def __eq__(self, other) -> bool:
+        return isinstance(other, Within) and self._key() == other._key()
+
+    def __hash__(self) -> int:
+        return hash(("Within",) + self._key())
+
+    def __len__(self) -> int:
+        return len(self.members)
+
+    def __repr__(self) -> str:
+        return ("Within(" + ", ".join(repr(m) for m in self.members) + f", unit={self.unit!r}"
+                + (", ordered=True" if self.ordered else "") + ")")
+
+    def __reduce__(self):
+        return (_make_within, (self.members, self.unit, self.ordered))
+
+    @property
+    def kind(self) -> int:
+        """The item kind of the ABI: bit 0 ordered, bit 1 paragraph."""
+        return (1 if self.ordered else 0) | (2 if self.unit == "paragraph" else 0)
+
+    def within(self, tokens: Sequence[str], breaks: Sequence[int]) -> bool:
+        """Whether the token sequence `tokens` with the break flags `breaks` (one per token) holds this Within: the plain
+        scan of every unit — the earliest next match per member (ordered), a bipartite matching by augmenting paths
+        (unordered)."""
+        if len(breaks) != len(tokens):
+            raise ValueError(f"Within.within: {len(tokens)} tokens, {len(breaks)} break flags")
+        bit = BREAK_PARAGRAPH if self.unit == "paragraph" else BREAK_SENTENCE
+        want, M = self.members, len(self.members)
+        begin = 0
+        for end in range(1, len(tokens) + 1):
+            if end < len(tokens) and not (int(breaks[end]) & bit):
+                continue
+            unit, begin = tokens[begin:end], end
+            if len(unit) < M:
+                continue
+            if self.ordered:
+                j = 0
+                for t in unit:
+                    if fills(want[j], t):
+                        j += 1
+                        if j == M:
+                            return True
+                continue
+            may = [[q for q, t in enumerate(unit) if fills(m, t)] for m in want]  # the positions each member may take
+            taken: Dict[int, int] = {}  # position -> the member it is assigned to
+
+            def place(j: int, seen: set) -> bool:
+                for q in may[j]:
+                    if q in seen:
+                        continue
+                    seen.add(q)
+                    if q not in taken or place(taken[q], seen):
+                        taken[q] = j
+                        return True
+                return False
+            if all(place(j, set()) for j in range(M)):
+                return True
+        return False
+
+
+def _make_within(members, unit, ordered) -> Within:
+    return Within(*members, unit=unit, ordered=ordered)
+
+
+Member = Union[str, Phrase, Near, Prefix, OneOf, PhraseOf, NearOf, Wildcard, Fuzzy, Within]
 Group = Tuple[Member, ...]
-_MEMBERS = (str, Phrase, Near, Prefix, OneOf, PhraseOf, NearOf, Wildcard, Fuzzy)
+_MEMBERS = (str, Phrase, Near, Prefix, OneOf, PhraseOf, NearOf, Wildcard, Fuzzy, Within)
 _SPANS = (Phrase, Near, PhraseOf, NearOf)  # what needs the token SEQUENCE
 
 
 def _member(t) -> Member:
-    if isinstance(t, (Near, Prefix, PhraseOf, NearOf) + _PATTERNS):
+    if isinstance(t, (Near, Prefix, PhraseOf, NearOf, Within) + _PATTERNS):
         return t
     if isinstance(t, OneOf):
         return t.members[0] if len(t) == 1 else t  # one member is that member
@@ -647,15 +758,19 @@ class Terms:
     def has_class_span(self) -> bool:
         return any(isinstance(t, (PhraseOf, NearOf)) for _, g in self.groups() for t in g)
 
+    @property
+    def has_within(self) -> bool:
+        return any(isinstance(t, Within) for _, g in self.groups() for t in g)
+
     def patterns(self) -> List[Any]:
         """The distinct Wildcards and Fuzzys of this Terms in order of appearance, wherever they stand: as an entry, in a
-        tuple group, or as a member of a OneOf, a PhraseOf or a NearOf (also inside a OneOf of those)."""
+        tuple group, or as a member of a OneOf, a PhraseOf, a NearOf or a Within (also inside a OneOf of those)."""
         seen: Dict[Any, None] = {}
 
         def walk(t) -> None:
             if isinstance(t, _PATTERNS):
                 seen.setdefault(t)
-            elif isinstance(t, (OneOf, PhraseOf, NearOf)):
+            elif isinstance(t, (OneOf, PhraseOf, NearOf, Within)):
                 for m in t.members:
                     walk(m)
         for _, g in self.groups():
@@ -668,19 +783,24 @@ class Terms:
         """Whether a Wildcard or a Fuzzy stands anywhere in this Terms: pack() then needs their `expansions`."""
         return bool(self.patterns())
 
-    def matches(self, tokens) -> bool:
+    def matches(self, tokens, breaks=None) -> bool:
         """The rule on one document's tokens (host check; the kernels apply term_scope_rule.hpp, phrase_rule.hpp,
-        union_rule.hpp and class_span_rule.hpp): a token set or sequence — with a Phrase, a Near, a PhraseOf or a NearOf
-        present, the token SEQUENCE in text order (TypeError for a set); a Prefix, a Wildcard, a Fuzzy or a OneOf takes
-        either."""
-        if self.has_phrase or self.has_near or self.has_class_span:
+        union_rule.hpp, class_span_rule.hpp and unit_span_rule.hpp): a token set or sequence — with a Phrase, a Near, a
+        PhraseOf, a NearOf or a Within present, the token SEQUENCE in text order (TypeError for a set); a Prefix, a
+        Wildcard, a Fuzzy or a OneOf takes either.  breaks: the document's break flags, one per token (retrieval/units.py
+        break_flags); a Terms that holds a Within raises TypeError without them."""
+        if self.has_within and breaks is None:
+            raise TypeError("Terms.matches: a Terms with a Within needs the document's break flags (breaks=)")
+        if self.has_phrase or self.has_near or self.has_class_span or self.has_within:
             if isinstance(tokens, (set, frozenset, dict)) or not isinstance(tokens, Sequence):
-                what = "Phrase" if self.has_phrase else "Near" if self.has_near else "PhraseOf or a NearOf"
+                what = ("Phrase" if self.has_phrase else "Near" if self.has_near else
+                        "PhraseOf or a NearOf" if self.has_class_span else "Within")
                 raise TypeError(f"Terms.matches: a Terms with a {what} needs the document's token sequence, not a set")
             have = set(tokens)
         else:
             have = tokens if isinstance(tokens, (set, frozenset, dict)) else set(tokens)
-        sat = lambda g: all(t.within(tokens) if isinstance(t, _SPANS) else  # noqa: E731
+        sat = lambda g: all(t.within(tokens, breaks) if isinstance(t, Within) else  # noqa: E731
+                            t.within(tokens) if isinstance(t, _SPANS) else
                             t.within(have) if isinstance(t, (Prefix, OneOf) + _PATTERNS) else t in have for t in g)
         return (all(sat(g) for g in self.all_of or ()) and (self.any_of is None or any(sat(g) for g in self.any_of))
                 and not any(sat(g) for g in self.none_of or ()))
@@ -745,6 +865,18 @@ class TermTable:
     cspan_cand_max = 0   # the largest of the upper bounds: the smallest slot bound of each item
     cspan_rows_cap = 0   # their sum
 
+    # the unit items of the batch (a Within), equal ones — compared after resolution — stored once; unit item w is term id
+    # len(vocab) + n_phr + n_near + n_union + n_cspan + w, behind the class spans (amdr_unit_spans).  A slot is a plain term
+    # id or the term id of a union.  Class-level defaults as the unions'
+    unit_ops = (np.zeros(1, dtype=np.int64), np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.int32))  # ptr, slots, kind
+    units = ()           # per unit item the first Within of the batch that names it
+    unit_cand_max = 0    # the largest of the upper bounds: the smallest slot bound of each item
+    unit_rows_cap = 0    # their sum
+
+    @property
+    def n_unit(self) -> int:
+        return len(self.units)
+
     @property
     def n_cspan(self) -> int:
         return len(self.cspans)
@@ -774,12 +906,15 @@ class TermTable:
         return self.phrases[i] if i < self.n_phr else self.nears[i - self.n_phr]
 
     def list_item(self, i: int):
-        """What virtual list i of the term step stands for: the Phrase, the Near, the union's Prefix / OneOf, or the class
-        span's PhraseOf / NearOf."""
+        """What virtual list i of the term step stands for: the Phrase, the Near, the union's Prefix / OneOf, the class
+        span's PhraseOf / NearOf, or the unit item's Within."""
         n_span = self.n_phr + self.n_near
         if i < n_span:
             return self.span_item(i)
-        return self.unions[i - n_span] if i < n_span + self.n_union else self.cspans[i - n_span - self.n_union]
+        if i < n_span + self.n_union:
+            return self.unions[i - n_span]
+        i -= n_span + self.n_union
+        return self.cspans[i] if i < self.n_cspan else self.units[i - self.n_cspan]
 
 
 def prefix_tokens(stem: str, sorted_vocab: Sequence[str]) -> List[str]:
@@ -827,7 +962,13 @@ def pack(pairs: Sequence[Tuple[Optional[Scope], Terms]], vocab: Mapping[str, int
     tokens, it names}, VocabMatcher.expand's result; this function stays plain host code and scans no vocabulary — and
     resolves from there on exactly as a Prefix does: none -> -1, one -> that plain term, two or more -> a union item that
     shares its slot with an equal OneOf or Prefix.  A pattern without an entry is a ValueError.  Without a pattern
-    `expansions` is not looked at and the table is field for field what it was."""
+    `expansions` is not looked at and the table is field for field what it was.
+    A Within has each member resolved as a NearOf's slot is, and is ALWAYS a unit item (amdr_unit_spans), plain members or
+    not: a union among its members registers a union item, equal Withins — compared after resolution: the same ids, unit and
+    order — are stored once, and unit item w stands as the term id len(vocab) + n_phr + n_near + n_union + n_cspan + w,
+    behind the class spans, with the smallest slot bound as its upper bound: unit_cand_max / unit_rows_cap.  An unordered
+    Within whose members' id sets intersect without being equal is a ValueError (class_span_rule.hpp's reason).  A table
+    without a Within is field for field the table without."""
     n_vocab = len(vocab)
     df_by_id = np.zeros(n_vocab, dtype=np.int64)
     for w, t in vocab.items():
@@ -907,7 +1048,34 @@ def pack(pairs: Sequence[Tuple[Optional[Scope], Terms]], vocab: Mapping[str, int
             cspan_bound.append(min(union_bound[i[1]] if isinstance(i, tuple) else int(df_by_id[i]) if i >= 0 else 0 for i in ids))
         return ("c", c)
 
+    unit_slot: Dict[Any, int] = {}
+    unit_first: List[Any] = []
+    unit_slots: List[list] = []
+    unit_bound: List[int] = []
+
+    def unit_id(t):
+        """The placeholder ("w", w) of the unit item a Within stands for."""
+        ids = [vocab.get(m, -1) if isinstance(m, str) else union_id(m) for m in t.members]
+        sets = [frozenset(union_ids[i[1]]) if isinstance(i, tuple) else frozenset([i] if i >= 0 else []) for i in ids]
+        if not t.ordered:
+            for j in range(len(sets)):
+                for k in range(j):
+                    if sets[j] & sets[k] and sets[j] != sets[k]:
+                        raise ValueError(f"{t!r}: members {k} and {j} name overlapping, unequal token sets "
+                                         f"({t.members[k]!r}, {t.members[j]!r}); the unordered form is resolved only for "
+                                         f"members that are pairwise equal or disjoint")
+        key = (t.kind, tuple(ids))
+        w = unit_slot.get(key)
+        if w is None:
+            w = unit_slot[key] = len(unit_bound)
+            unit_first.append(t)
+            unit_slots.append(ids)
+            unit_bound.append(min(union_bound[i[1]] if isinstance(i, tuple) else int(df_by_id[i]) if i >= 0 else 0 for i in ids))
+        return ("w", w)
+
     def term_id(t):
+        if isinstance(t, Within):  # (numbered behind the class spans: a placeholder)
+            return unit_id(t)
         if isinstance(t, (PhraseOf, NearOf)):  # (numbered behind the unions: a placeholder, or the plain form's id)
             return class_span_id(t)
         if isinstance(t, Near):  # (numbered behind the phrases once all of those are known: a placeholder until then)
@@ -957,6 +1125,7 @@ def pack(pairs: Sequence[Tuple[Optional[Scope], Terms]], vocab: Mapping[str, int
     n_phr = len(phr_bound)
     behind = {"n": n_vocab + n_phr, "u": n_vocab + n_phr + len(near_bound)}
     behind["c"] = behind["u"] + len(union_bound)
+    behind["w"] = behind["c"] + len(cspan_bound)
     cons_groups = [[(kind, [behind[t[0]] + t[1] if isinstance(t, tuple) else t for t in ids]) for kind, ids in groups]
                    for groups in cons_groups]
     for groups in cons_groups:
@@ -970,7 +1139,7 @@ def pack(pairs: Sequence[Tuple[Optional[Scope], Terms]], vocab: Mapping[str, int
     ops = (np.asarray(grp_ptr, dtype=np.int64), np.asarray(grp_kind, dtype=np.int32), np.asarray(grp_term_ptr, dtype=np.int64),
            np.asarray(grp_terms, dtype=np.int32), base_ptr,
            np.concatenate(bases) if bases else np.zeros(0, dtype=np.int64), np.asarray(cons_base, dtype=np.int32))
-    df_all = np.concatenate([df_by_id, np.asarray(phr_bound + near_bound + union_bound + cspan_bound, dtype=np.int64)])  # (all known by now)
+    df_all = np.concatenate([df_by_id, np.asarray(phr_bound + near_bound + union_bound + cspan_bound + unit_bound, dtype=np.int64)])  # (all known by now)
     lens_a = np.asarray([driver_length(g, df_all, int(bases[b].size) if b >= 0 else None, n_docs)
                          for g, b in zip(cons_groups, cons_base)], dtype=np.int64)
     tt = TermTable(ops, qscope, len(cons_base), len(grp_kind), len(bases), lens_a,
@@ -999,4 +1168,10 @@ def pack(pairs: Sequence[Tuple[Optional[Scope], Terms]], vocab: Mapping[str, int
                                           dtype=np.int32),
                         np.asarray([k[0] for k in cspan_slot], dtype=np.int32), np.asarray([k[2] for k in cspan_slot], dtype=np.int32))
         tt.cspans, tt.cspan_cand_max, tt.cspan_rows_cap = tuple(cspan_first), max(cspan_bound), int(sum(cspan_bound))
+    if unit_slot:
+        w_ptr = np.zeros(len(unit_slot) + 1, dtype=np.int64)
+        np.cumsum([len(ids) for ids in unit_slots], out=w_ptr[1:])
+        tt.unit_ops = (w_ptr, np.asarray([behind["u"] + i[1] if isinstance(i, tuple) else i for ids in unit_slots for i in ids],
+                                         dtype=np.int32), np.asarray([k[0] for k in unit_slot], dtype=np.int32))
+        tt.units, tt.unit_cand_max, tt.unit_rows_cap = tuple(unit_first), max(unit_bound), int(sum(unit_bound))
     return tt
